@@ -2,6 +2,8 @@
 """Benchmark of the XR-Linear batch-inference hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W            (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W --full     (+ every figure and check beyond the headline, see below)
+    python bench.py ... --dump-outputs DIR                   (+ the last timed step's output as DIR/*.npy)
 
 One STEP = one full beam search (all layers: prolongate -> inner products + post-processor + combine -> per-query
 top-k) over the whole synthetic query batch of the named workload, queries already resident in HBM, results left in
@@ -12,8 +14,19 @@ Workload: BASELINE.json's Amazon-670K shape (the configuration its target is quo
 queries, D=135,000, L=670,091, tree [2,32,512,8192,670091], beam=10, top-k=10, post-processor l3-hinge, synthetic CSR
 (xrl_synth.py, fixed seeds).  --config eurlex-4k | wiki10-31k | dense-768 (with --scale / --rows) run the other shapes.
 
+A plain run sets up, warms up, times the K steps and prints the line with `value` and `ms_per_step`; nothing else runs.
+--full adds everything below `ms_per_step` on the line: the per-launch hipEvent profile of the timed steps and the untimed stats
+pass (`roofline`), the timed output against the reference (`parity`), `value_host_abi`, `device_featurizer`, `cpu_baseline` and
+the `extra` lines.  The --no-* options below switch single parts of --full off.
+
+--dump-outputs DIR writes what the last timed step returned to its caller, every row (a seeded sample of rows when that would
+exceed 64 MB): labels.npy (label ids, float32 while they are exact in it, else float64), scores.npy (float32) -- both rows x topk,
+-1 / 0 past a row's count -- counts.npy (float32) and rows.npy (float64 row ids of the workload).  The workload is generated from
+fixed seeds, so the same arguments give the same inputs in every run and two builds can be compared file by file.
+
 On the JSON line:
   value           queries/s with X resident in HBM when the timed region starts (the contract's `value`)
+  ms_per_step     milliseconds of one timed step (the timed region / --steps)
   value_host_abi  queries/s through the drop-in entry point c_xlinear_predict_csr_f32 -- pageable host X in, H2D,
                   kernels, D2H, allocator callback, host CSR out -- the figure SURVEY.md 8(d) specifies (N=1 only)
   roofline        the kernel family with the most GPU time (hipEvent pairs around every launch on the stream it runs on, during the
@@ -113,8 +126,11 @@ def main():
     ap.add_argument("--include-upload", action="store_true",
                     help="time the drop-in entry point instead: every rank calls c_xlinear_predict_* on ITS shard (pageable host X in, H2D, kernels, "
                          "D2H, host CSR out); value = all queries / max-over-ranks time (what a caller that shards by process gets, PCIe included)")
-    ap.add_argument("--parity-rows", type=int, default=-1, help="rows per shard of the TIMED output compared with the reference after the timed loop "
-                                                               "(0 = skip; -1, the default = EVERY row when oracle/_ref is built, else 4096)")
+    ap.add_argument("--full", action="store_true", help="also run every figure and check beyond the headline: roofline, timed-output parity, host ABI, "
+                                                         "device featurizer, CPU baseline, extra lines (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's output (labels, scores, counts, row ids) as DIR/*.npy")
+    ap.add_argument("--parity-rows", type=int, default=None, help="rows per shard of the TIMED output compared with the reference after the timed loop "
+                                                                 "(0 = skip; -1 = EVERY row when oracle/_ref is built, else 4096; default: -1 with --full, else 0)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-extra", action="store_true", help="skip the extra lines of the default run (extra.hard: the same shape on the model that does not flatter "
                                                              "bound pruning; extra.text_to_labels: texts -> labels with X never on the host)")
@@ -122,6 +138,8 @@ def main():
     ap.add_argument("--k1-group", type=int, default=0)
     ap.add_argument("--opt", action="append", default=[], help="library option key=int (xrl_set_option), repeatable")
     args = ap.parse_args()
+    if args.parity_rows is None:
+        args.parity_rows = -1 if args.full else 0
 
     import numpy as np
     import scipy.sparse as smat
@@ -268,33 +286,34 @@ def main():
     for _ in range(args.warmup):
         step()
     sync_all()
-    clib.profile_reset(h)
-    clib.profile_enable(h, True)
-    sync_all()
+    if args.full:                                          # per-launch hipEvent pairs: the roofline's kernel times
+        clib.profile_reset(h)
+        clib.profile_enable(h, True)
+        sync_all()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     sync_all()
     dt = time.perf_counter() - t0
-    clib.profile_enable(h, False)
+    if args.full:
+        clib.profile_enable(h, False)
     if use_dist and world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    prof = clib.profile_get(h)
+    prof = clib.profile_get(h) if args.full else []
 
-    # ---- what the TIMED steps produced, compared with the reference on rows of every shard (rank 0)
-    timed_parity = None
-    if len(par_sel):
-        n_sel = [int(min(int(bounds[r + 1]), int(bounds[r]) + max(0, args.parity_rows)) - int(bounds[r])) for r in range(world)]
+    # ---- what the LAST timed step produced, every row on rank 0: fixed-stride (idx, val, cnt) tensors, or host CSR in the upload mode
+    last_out = None
+    if len(par_sel) or args.dump_outputs:
         if args.include_upload:
-            mine = last_host[0].get()[: n_sel[rank]] if (last_host[0] is not None and n_sel[rank]) else None
+            mine = last_host[0].get() if last_host[0] is not None else None
             pieces = [mine]
             if use_dist and world > 1:
                 pieces = [None] * world if rank == 0 else None
                 dist.gather_object(mine, pieces, dst=0)
             if rank == 0:
-                G = smat.vstack([pc for pc in pieces if pc is not None], format="csr")
+                last_out = smat.vstack([pc for pc in pieces if pc is not None], format="csr")
         else:
             pk = pipe.last()                               # what the LAST timed step wrote (and gathered)
             if not use_dist:
@@ -303,19 +322,31 @@ def main():
                         pk.gather(p)                       # no process group: copies the send buffers into the receive side
             torch.cuda.synchronize()
             if rank == 0:
-                gi, gv, gc = pk.unpack()
-                from pecos_amd.distributed import rows_to_csr
-                sel_t = torch.from_numpy(par_sel).to(gi.device)
-                G = rows_to_csr(gi[sel_t].cpu().numpy().view(np.uint32), gv[sel_t].cpu().numpy(), gc[sel_t].cpu().numpy(), model.nr_pred_cols)
-        if rank == 0:
-            timed_parity = timed_output_parity(folder, Xpar, G, beam, args.topk, world, args.parity_rows, log)
+                last_out = pk.unpack()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_out, k, model.nr_pred_cols, log)
+
+    # ---- the TIMED output compared with the reference on rows of every shard (rank 0)
+    timed_parity = None
+    if len(par_sel) and rank == 0:
+        if args.include_upload:
+            G = last_out[par_sel]
+        else:
+            gi, gv, gc = last_out
+            from pecos_amd.distributed import rows_to_csr
+            sel_t = torch.from_numpy(par_sel).to(gi.device)
+            G = rows_to_csr(gi[sel_t].cpu().numpy().view(np.uint32), gv[sel_t].cpu().numpy(), gc[sel_t].cpu().numpy(), model.nr_pred_cols)
+        timed_parity = timed_output_parity(folder, Xpar, G, beam, args.topk, world, args.parity_rows, log)
 
     out = None
     if rank == 0:
         ms_per_step = dt / max(1, args.steps) * 1e3
         value = n_total * args.steps / dt
-        log("per-launch ms: " + "  ".join(f"{r['name']}[{r['layer']}]={r['ms'] / max(1, r['launches']):.3f}" for r in prof))
-        roof = roofline(clib, h, q, Xs, prof, linfo, beam, args, k, rows, world, ms_per_step)
+        log(f"{args.steps} timed steps: {ms_per_step:.3f} ms per step = {value / 1e6:.2f} M q/s")
+        roof = None
+        if args.full:
+            log("per-launch ms: " + "  ".join(f"{r['name']}[{r['layer']}]={r['ms'] / max(1, r['launches']):.3f}" for r in prof))
+            roof = roofline(clib, h, q, Xs, prof, linfo, beam, args, k, rows, world, ms_per_step)
         cfg_out = dict(workload=f"{args.config} synthetic x{args.scale}: N={n_total} D={Xs.shape[1]} L={ks[-1]} tree={ks} "
                                 f"nnz/row={nnz_row:.1f} beam={beam} topk={k} pp=l3-hinge bias=1.0",
                        parallelism=f"query-shard x{world}" + (f" + {'rccl' if backend == 'nccl' else backend + ' (host-staged REHEARSAL, all ranks on one device)'} all-gather of the packed top-k rows of step s on a second stream under the kernels of step s+1 (two result buffers)" if world > 1 else ""),
@@ -332,7 +363,7 @@ def main():
         if args.include_upload:
             cfg_out["mode"] = "include-upload: every rank times c_xlinear_predict_* on its shard (pageable host X in, H2D, kernels, D2H, host CSR out); no gather"
         # ---- the SURVEY 8(d) figure: the drop-in C-ABI entry point, pageable host X in, host CSR out (N=1)
-        if world == 1 and not args.no_host_abi and not args.include_upload:
+        if args.full and world == 1 and not args.no_host_abi and not args.include_upload:
             view = ScipyCsrF32.init_from(Xs) if sparse else ScipyDrmF32.init_from(Xs)
             times = []
             first_call = None
@@ -359,7 +390,7 @@ def main():
         # ---- what keeping the featurizer's output on the device buys.  The queries' values stand in for term counts:
         #      the reference's tf-idf weighting + l2 normalisation runs as a kernel on the device CSR (xrl_queries_tfidf_device), and
         #      the beam search reads its output in place -- against the host ABI, which receives X from the host.
-        if world == 1 and sparse and not args.include_upload and not args.no_host_abi:
+        if args.full and world == 1 and sparse and not args.include_upload and not args.no_host_abi:
             try:
                 tx = torch.from_numpy(Xs.indptr.astype(np.int64)).to(dev), torch.from_numpy(Xs.indices.astype(np.int32)).to(dev), \
                     torch.from_numpy(np.abs(Xs.data).astype(np.float32)).to(dev)
@@ -384,12 +415,12 @@ def main():
                 log(f"device featurizer line skipped: {e}")
 
         # ---- CPU baseline + parity on a bounded sample (N=1 only)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], out["parity"] = cpu_baseline(folder, Xs, model, beam, args.topk, args.cpu_seconds, log)
         if timed_parity is not None:
             out["parity"] = dict(out.get("parity") or {}, **timed_parity)
         # ---- extra lines of the DEFAULT run: the honest model and the text -> labels pipeline, under the driver's eyes
-        if world == 1 and not args.no_extra and not args.include_upload and args.config == "amazon-670k" and args.scale == 1.0 and not args.rows and not args.opt:
+        if args.full and world == 1 and not args.no_extra and not args.include_upload and args.config == "amazon-670k" and args.scale == 1.0 and not args.rows and not args.opt:
             out["extra"] = {}
             try:
                 out["extra"]["text_to_labels"] = text_to_labels(clib, model, folder, Xs, beam, args.topk, args.text_docs, log)
@@ -611,6 +642,40 @@ def timed_output_parity(folder, Xpar, G, beam, topk, world, rows_per_shard, log)
                 f"read back from the buffers the timed steps wrote, vs {kind}", timed_output_indices_identical=same_idx, timed_output_scores_bit_identical=bit)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, last_out, k, n_cols, log):
+    """--dump-outputs: the last timed step's output as DIR/{labels,scores,counts,rows}.npy (see the module docstring).  `last_out` is
+    (idx, val, cnt) tensors of every row (device-resident steps) or the host CSR (upload mode).  Slots past a row's count are set to
+    -1 / 0: a caller reads only the first `count` slots of a row.  Above DUMP_MAX_BYTES a seeded sample of rows is written (rows.npy names them)."""
+    import numpy as np
+    import scipy.sparse as smat
+    if smat.issparse(last_out):
+        n = last_out.shape[0]
+        cnt = np.diff(last_out.indptr).astype(np.int64)
+        idx = np.full((n, k), -1, np.int64); val = np.zeros((n, k), np.float32)
+        slot = np.arange(last_out.nnz) - np.repeat(last_out.indptr[:-1], cnt)
+        row = np.repeat(np.arange(n), cnt)
+        idx[row, slot] = last_out.indices; val[row, slot] = last_out.data
+    else:
+        idx, val, cnt = (t.cpu().numpy() for t in last_out)
+        n = idx.shape[0]
+    lab_t = np.float32 if n_cols <= (1 << 24) else np.float64     # label ids are exact in float32 up to 2^24
+    row_bytes = k * (np.dtype(lab_t).itemsize + 4) + 4 + 8
+    rows = np.arange(n, dtype=np.int64)
+    if n * row_bytes > DUMP_MAX_BYTES - 4096:                      # (4 .npy headers)
+        rows = np.sort(np.random.default_rng(0).choice(n, (DUMP_MAX_BYTES - 4096) // row_bytes, replace=False))
+    cnt = np.asarray(cnt)[rows].astype(np.int64)
+    live = np.arange(k)[None, :] < cnt[:, None]
+    labels = np.where(live, np.asarray(idx)[rows], -1).astype(lab_t)
+    scores = np.where(live, np.asarray(val)[rows], 0).astype(np.float32)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in (("labels", labels), ("scores", scores), ("counts", cnt.astype(np.float32)), ("rows", rows.astype(np.float64))):
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log(f"outputs of the last timed step: {len(rows)} of {n} rows x top-{k} -> {dirname}")
+
+
 def shard8_line(clib, h, q, torch, dev, stream, tstream, beam, args, k, n_total, ms_full, log):
     """extra.shard8: the one-GPU PROXY of the 8-GPU run (SCALE_rNN needs an 8-GPU node): the step on ONE rank's shard -- the first
     n_total / 8 rows, device-resident, same entry point and options -- timed like the main loop.  projected_speedup_8 = full-step time /
@@ -644,7 +709,7 @@ def hard_line(args, log):
     reference on --parity-rows rows.  The headline `value` stays on the BASELINE configuration."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--config", "amazon-670k-hard", "--steps", str(args.steps), "--warmup", str(max(args.warmup, 6)),
-           "--no-cpu-baseline", "--no-host-abi", "--no-extra", "--cache", args.cache, "--parity-rows", str(args.parity_rows)]
+           "--full", "--no-cpu-baseline", "--no-host-abi", "--no-extra", "--cache", args.cache, "--parity-rows", str(args.parity_rows)]
     t0 = time.time()
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500)
     line = next((ln for ln in reversed(r.stdout.splitlines()) if ln.startswith("{")), None)

@@ -4,7 +4,7 @@
 # Stages:
 #   tests[:ARGS]    python -m pytest -m gpu ARGS   (default: tests; ',' separates arguments, '+' is a space inside one, e.g. tests:tests/test_gpu_fuzz.py,-k,fuzz+or+goldens)
 #   smoke           __graft_entry__.smoke()
-#   bench[:ARGS]    python bench.py ARGS            (ARGS with ',' for spaces; output bench_<n>.json / .err)
+#   bench[:ARGS]    python bench.py --full ARGS     (ARGS with ',' for spaces; output bench_<n>.json / .err)
 #   so[:NAME]       the following stages load pecos_amd/lib/NAME (a kernel-tuning variant built by scripts/build_variant.sh) instead of libxrl_amd.so; empty = back to the default
 #   probe[:ARGS]    python scripts/host_abi_probe.py ARGS   (fresh process; per-call times + the library's stage timing lines)
 #   ab:ROWS@CONFIG@STEPS@SET|SET|...   scripts/ab.py on the first ROWS rows (0 = all) of CONFIG: option sets (k=v+k=v, "" = defaults) timed in one process,
@@ -23,7 +23,7 @@ for st in "$@"; do
            [ ${#targs[@]} -eq 0 ] && targs=(tests)
            timeout ${XRL_TESTS_TIMEOUT:-1500} python -m pytest -m gpu -q -x "${targs[@]}" 2>&1 | tail -15 > $O/pytest_gpu.log; cat $O/pytest_gpu.log ;;
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -2 $O/smoke.log ;;
-    bench) n=$((n+1)); echo "== bench $args"; timeout ${XRL_BENCH_TIMEOUT:-600} python bench.py $args > $O/bench_$n.json 2> $O/bench_$n.err; echo "$args" > $O/bench_$n.args
+    bench) n=$((n+1)); echo "== bench $args"; timeout ${XRL_BENCH_TIMEOUT:-600} python bench.py --full $args > $O/bench_$n.json 2> $O/bench_$n.err; echo "$args" > $O/bench_$n.args
            grep -E "per-launch|host ABI|xrl host|cpu reference|Error|error" $O/bench_$n.err | cut -c1-1500; python -c "
 import json,sys
 try:

@@ -273,3 +273,29 @@ def test_counter_sets_recompute_from_the_committed_passes():
             got = e["kernels"][fam]
             for f in ("hbm_bytes_per_step", "fabric_read_req_per_step", "valu_insts_per_step", "launches_per_step"):
                 assert got[f] == pytest.approx(want[f], rel=1e-9), (key, fam, f)
+
+
+def test_dump_outputs_both_output_forms_and_the_size_cap(tmp_path, monkeypatch):
+    # --dump-outputs: the device-resident step's fixed-stride rows and the upload mode's host CSR give the same files (slots past a row's
+    # count -1 / 0), float32 / float64 only; above the cap a seeded, sorted sample of rows is written and rows.npy names it
+    import torch
+    from pecos_amd.distributed import rows_to_csr
+    rng = np.random.default_rng(1)
+    n, k = 1000, 5
+    idx = rng.integers(0, 700, (n, k)).astype(np.int32); val = rng.random((n, k)).astype(np.float32); cnt = rng.integers(0, k + 1, n).astype(np.int32)
+    a, b = tmp_path / "a", tmp_path / "b"
+    bench.dump_outputs(str(a), (torch.from_numpy(idx), torch.from_numpy(val), torch.from_numpy(cnt)), k, 700, lambda *x: None)
+    bench.dump_outputs(str(b), rows_to_csr(idx, val, cnt, 700), k, 700, lambda *x: None)
+    for f in ("labels", "scores", "counts", "rows"):
+        x, y = np.load(a / f"{f}.npy"), np.load(b / f"{f}.npy")
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    lab, sc, c = np.load(a / "labels.npy"), np.load(a / "scores.npy"), np.load(a / "counts.npy")
+    live = np.arange(k)[None, :] < cnt[:, None]
+    assert np.array_equal(c, cnt) and np.array_equal(lab[live], idx[live]) and np.all(lab[~live] == -1) and np.all(sc[~live] == 0)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 16384)
+    for d in (a, b):
+        bench.dump_outputs(str(d), (torch.from_numpy(idx), torch.from_numpy(val), torch.from_numpy(cnt)), k, 700, lambda *x: None)
+    rows = np.load(a / "rows.npy")
+    assert 0 < len(rows) < n and np.all(np.diff(rows) > 0) and np.array_equal(rows, np.load(b / "rows.npy"))
+    assert np.array_equal(np.load(a / "labels.npy"), np.where(live, idx, -1)[rows.astype(np.int64)])
+    assert sum(os.path.getsize(a / f) for f in os.listdir(a)) <= 16384

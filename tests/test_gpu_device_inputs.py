@@ -219,7 +219,7 @@ def test_bench_step_under_rccl_one_rank(tmp_path):
     env = dict(os.environ, XRL_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29577", os.path.join(REPO, "bench.py"), "--gpus", "1", "--config", "eurlex-4k", "--scale", "0.25",
-           "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-host-abi", "--cache", str(tmp_path / "cache")]
+           "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-host-abi", "--cache", str(tmp_path / "cache")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=560)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -236,7 +236,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(tmp_path):
     env = dict(os.environ, XRL_BENCH_BACKEND="gloo", XRL_BENCH_ONE_DEVICE="1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29581", os.path.join(REPO, "bench.py"), "--gpus", "2", "--config", "eurlex-4k", "--scale", "0.5",
-           "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-host-abi", "--parity-rows", "1500", "--cache", str(tmp_path / "cache")]
+           "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-host-abi", "--parity-rows", "1500", "--cache", str(tmp_path / "cache")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=850)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -44,20 +44,31 @@ def test_oracle_bit_exact_vs_reference_on_synthetic(manifest, oracle_mod):
         assert_same_topk(P, G, exact_scores=True, what=str(c))
 
 
-def test_oracle_vs_live_reference_if_present(oracle_mod, tmp_path):
-    # when oracle/_ref is available (it travels to the GPU box), compare on a fresh seeded model too
-    if not oracle_mod.ref_available():
-        pytest.skip("oracle/_ref not built")
+LIVE_PPS = [None, "sigmoid", "log-sigmoid", "l1-hinge", "log-l4-hinge", "noop"]
+
+
+def live_model_case(folder):
+    """The seeded model + queries of the test below (tests/golden/make_golden_live.py stores the reference's predictions on them)."""
     import xrl_synth
-    folder = str(tmp_path / "m")
     xrl_synth.make_model(folder, 400, 700, [120, 80, 25], seed=3, shape=[3, 20, 700])
     X = xrl_synth.make_queries(40, 400, 30, seed=4, relabel_seed=3)
+    return {"sparse": X, "dense": np.ascontiguousarray(X.toarray())}
+
+
+def test_oracle_vs_live_reference_if_present(oracle_mod, tmp_path):
+    # a fresh seeded model: bit for bit against the reference's predictions stored in tests/golden/live/, and against the live
+    # reference too when oracle/_ref is available
+    folder = str(tmp_path / "m")
+    Xs = live_model_case(folder)
     om = oracle_mod.OracleModel.load(folder)
-    rm = oracle_mod.RefModel(folder)
-    for pp in [None, "sigmoid", "log-sigmoid", "l1-hinge", "log-l4-hinge", "noop"]:
-        for Xq in (X, np.ascontiguousarray(X.toarray())):
-            assert_same_topk(om.predict(Xq, beam_size=5, only_topk=7, post_processor=pp),
-                             rm.predict(Xq, beam_size=5, only_topk=7, post_processor=pp), exact_scores=True, what=str(pp))
+    rm = oracle_mod.RefModel(folder) if oracle_mod.ref_available() else None
+    for pp in LIVE_PPS:
+        for form, Xq in Xs.items():
+            P = om.predict(Xq, beam_size=5, only_topk=7, post_processor=pp)
+            G = load_raw_csr(os.path.join(GOLDEN, "live", f"pp_{pp or 'default'}__{form}.npz"))
+            assert_same_topk(P, G, exact_scores=True, what=f"{pp} {form} vs stored reference output")
+            if rm is not None:
+                assert_same_topk(P, rm.predict(Xq, beam_size=5, only_topk=7, post_processor=pp), exact_scores=True, what=str(pp))
 
 
 def test_oracle_sparse_inner_products_kat(oracle_mod):
@@ -72,21 +83,28 @@ def test_oracle_sparse_inner_products_kat(oracle_mod):
         assert np.allclose(oracle_mod.sparse_inner_products(Xq, Wq, r, c), true, atol=1e-9)
 
 
-def test_oracle_sparse_inner_products_pinned_on_reference(oracle_mod):
-    # the restatement of do_dot_product (matrix.hpp:836-877) against the REAL reference's c_sparse_inner_products_*
-    # on random pairs, all four layout combinations, bit for bit (the KAT above only holds 3 pairs)
-    if not oracle_mod.ref_available():
-        pytest.skip("oracle/_ref not built")
+def inner_products_case():
+    """Random pairs of the test below in all four layout combinations (tests/golden/make_golden_live.py stores the reference's results)."""
     rng = np.random.default_rng(5)
     A = smat.random(300, 700, density=0.05, format="csr", dtype=np.float32, random_state=6); A.sort_indices()
     B = smat.random(700, 400, density=0.08, format="csc", dtype=np.float32, random_state=7); B.sort_indices()
     A = A.tolil(); A[3, :] = 0; A[4, :] = rng.standard_normal(700).astype(np.float32); A = A.tocsr().astype(np.float32); A.sort_indices()
     rr = rng.integers(0, 300, 8000).astype(np.uint32); cc = rng.integers(0, 400, 8000).astype(np.uint32)
-    for Aq, Bq in [(A, B), (np.ascontiguousarray(A.toarray()), B), (A, np.asfortranarray(B.toarray())),
-                   (np.ascontiguousarray(A.toarray()), np.asfortranarray(B.toarray()))]:
+    return [(Aq, Bq, rr, cc) for Aq, Bq in [(A, B), (np.ascontiguousarray(A.toarray()), B), (A, np.asfortranarray(B.toarray())),
+                                            (np.ascontiguousarray(A.toarray()), np.asfortranarray(B.toarray()))]]
+
+
+def test_oracle_sparse_inner_products_pinned_on_reference(oracle_mod):
+    # the restatement of do_dot_product (matrix.hpp:836-877) against the REAL reference's c_sparse_inner_products_*
+    # on random pairs, all four layout combinations, bit for bit (the KAT above only holds 3 pairs): against the reference's
+    # results stored in tests/golden/live/, and against the live reference too when oracle/_ref is available
+    stored = np.load(os.path.join(GOLDEN, "live", "sparse_inner_products.npz"))
+    for i, (Aq, Bq, rr, cc) in enumerate(inner_products_case()):
         got = oracle_mod.sparse_inner_products(Aq, Bq, rr, cc)
-        ref = oracle_mod.ref_sparse_inner_products(Aq, Bq, rr, cc)
-        assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
+        assert np.array_equal(got.view(np.uint32), stored[f"case{i}"].view(np.uint32)), i
+        if oracle_mod.ref_available():
+            ref = oracle_mod.ref_sparse_inner_products(Aq, Bq, rr, cc)
+            assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
 
 
 def test_oracle_selected_outputs(manifest, oracle_mod):
