@@ -307,6 +307,10 @@ uint64_t xrl_debug_layout_rows(const uint32_t* rptr, uint32_t nrows, int align, 
  *                         11.9 -> 7.5 ms); 2: on every layer that has the words; 0: never.  XRL_PRESENCE=0 at load builds none.
  *   "prune_mid"           1 (default): bound-pruned tile-format layers entered with >= 16 beam parents score slots 1..4 in a MIDDLE stage before
  *                         "every remaining slot" (three stages instead of two; Wiki10-31K's beam of 20); 0: two stages
+ *   "leaf_fuse"           1 (default): the FIRST stage of a bound-pruned tile-format layer is one launch where K1T serves it with 32 lanes per item, every
+ *                         parent is one tile (<= 128 children) and k <= 20 -- the kernel derives its item from the beam (beams of up to 32 parents; no
+ *                         k0_prolongate launch), ranks the candidates in its epilogue and sets the done flags (no k2_topk launch); 2: ... but the
+ *                         items still come from a k0_prolongate launch; 0: three launches (K0 -> K1 -> K2)
  *   "sort_rest"           1 (default): the second phase of a bound-pruned tile-format layer runs on tile-sorted items (counting sort of the
  *                         compacted list by tile: the items of a tile run back to back on one XCD and share its lookup words and entries in
  *                         that XCD's L2); 0: in query order

@@ -198,6 +198,56 @@ __device__ __forceinline__ uint32_t wave_topk_extract(uint32_t (&kx)[NS], const 
 }
 constexpr uint32_t kTopkExtractMaxK = 20;   // above: the bisection's fixed cost is the smaller one
 
+// Half-wavefront sibling of wave_topk_extract: lanes 0-31 and lanes 32-63 each rank a candidate set of their OWN (two queries per
+// wavefront), NS candidates per lane, in one instruction stream.  Candidate (r, l) -- register r of the half's lane l -- has position
+// NS * l + r: LANE-major, the order in which K1T's lanes hold a tile's columns.  Ties go to the smaller position, so the winner is the
+// half's lowest lane that holds the maximum in any register, and in that lane the lowest such register: every lane picks its own first
+// holder, ONE ballot finds the lanes, and its two 32-bit halves name the two winners.  The four DPP steps of wave_max_u32 leave 16-lane row
+// maxima; rows 0/1 and rows 2/3 meet in two scalars.  k <= 32: lane i of a half receives the half's i-th best (score bits and position);
+// kk_lo / kk_hi = min(k, #candidates) of the halves.  All 64 lanes must be active; the keys are consumed.
+template <int NS>
+__device__ __forceinline__ void halfwave_topk_extract(uint32_t (&kx)[NS], const uint32_t (&sbits)[NS], uint32_t k, int lane,
+                                                      uint32_t& o_sbits, uint32_t& o_pos, uint32_t& kk_lo, uint32_t& kk_hi) {
+    const bool hi = lane >= 32;
+    const uint32_t lig = (uint32_t)lane & 31u;
+    uint32_t osb = 0, ops = 0, nlo = 0, nhi = 0;
+    for (uint32_t i = 0; i < k; ++i) {
+        uint32_t x = kx[0];
+#pragma unroll
+        for (int r = 1; r < NS; ++r) x = max(x, kx[r]);
+        x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
+        x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
+        x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x141, 0xF, 0xF, true));   // row_half_mirror
+        x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x140, 0xF, 0xF, true));   // row_mirror
+        const uint32_t mlo = max((uint32_t)__builtin_amdgcn_readlane((int)x, 0), (uint32_t)__builtin_amdgcn_readlane((int)x, 16));
+        const uint32_t mhi = max((uint32_t)__builtin_amdgcn_readlane((int)x, 32), (uint32_t)__builtin_amdgcn_readlane((int)x, 48));
+        if ((mlo | mhi) == 0u) break;                                   // no candidate left in either half
+        const uint32_t mx = hi ? mhi : mlo;
+        bool hit = false;
+        uint32_t msb = 0, mr = 0;
+#pragma unroll
+        for (int r = NS - 1; r >= 0; --r) {                             // (descending: the lowest holding register is assigned last)
+            const bool e = kx[r] == mx;
+            msb = e ? sbits[r] : msb; mr = e ? (uint32_t)r : mr; hit = hit || e;
+        }
+        hit = hit && mx != 0u;                                          // (a half that has run dry matches its empty slots)
+        const unsigned long long b = __ballot(hit);
+        const uint32_t blo = (uint32_t)b, bhi = (uint32_t)(b >> 32);
+        const int wlo = blo ? __builtin_ctz(blo) : 0, whi = 32 + (bhi ? __builtin_ctz(bhi) : 0);
+        const uint32_t mps = (uint32_t)NS * lig + mr;
+        const uint32_t sb_lo = (uint32_t)__builtin_amdgcn_readlane((int)msb, wlo), ps_lo = (uint32_t)__builtin_amdgcn_readlane((int)mps, wlo);
+        const uint32_t sb_hi = (uint32_t)__builtin_amdgcn_readlane((int)msb, whi), ps_hi = (uint32_t)__builtin_amdgcn_readlane((int)mps, whi);
+        const bool dst = lig == i;
+        osb = dst ? (hi ? sb_hi : sb_lo) : osb;
+        ops = dst ? (hi ? ps_hi : ps_lo) : ops;
+        const bool win = hit && lane == (hi ? whi : wlo);
+#pragma unroll
+        for (int r = 0; r < NS; ++r) kx[r] = (win && mr == (uint32_t)r) ? 0u : kx[r];
+        nlo += mlo != 0u ? 1u : 0u; nhi += mhi != 0u ? 1u : 0u;
+    }
+    o_sbits = osb; o_pos = ops; kk_lo = nlo; kk_hi = nhi;
+}
+
 // Returns kk = min(k, #candidates).  Lanes [0, kk) receive one selected candidate each: its final rank in
 // (value desc, position asc) order, its score bits and its payload.  sc: 64 uint2 of wavefront-private LDS.  k <= 64.
 // The keys are CONSUMED (the extraction clears the winners in place: no second copy in registers).

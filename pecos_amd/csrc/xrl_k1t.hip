@@ -50,6 +50,15 @@ struct K1TArgs {
     uint32_t n_vblocks;
     uint32_t* fb_out;            // pruning feedback: the launch's item count goes to this host-visible word
     uint32_t wt_bytes;           // BUF: size of the whole tile-row array (one buffer resource)
+    // SEL (the selecting epilogue): the previous beam, the guard flags and where the layer's top-k goes
+    const uint32_t* p_cnt; const float* p_val; uint32_t p_stride, beam_in;
+    const uint32_t* xok; const uint32_t* perm_inv;
+    uint32_t* out_idx; float* out_val; uint32_t* out_cnt; uint32_t* done;
+    uint32_t out_stride, k;
+    int mult;
+    // SEL, items == nullptr: the item is DERIVED (k0_prolongate folded into this launch) and the offsets K0 would have written go out here
+    const uint32_t* p_idx; const uint64_t* x_row_ptr;   // (x_row_ptr: of the batch's first row)
+    uint32_t cand_stride; uint32_t* cand_off; uint32_t* ncand;
 };
 
 template <int NR> struct RowVec;
@@ -72,8 +81,12 @@ template <> __device__ __forceinline__ RowVec<4> row_load_buf<4>(__amdgpu_buffer
 
 // G lanes per item (64 / G items per wavefront), NR columns per lane; LK = row lookup: 0 rank-bitmap {bits32, rank}, 2 {bits64, rank, -};
 // BUF: the whole tile-row array is under 4 GiB and is addressed through ONE buffer resource with 32-bit byte offsets (a hit's queue word
-// is its row's absolute offset: one vector add per row instead of a 64-bit address)
-template <int G, int NR, int PPC, int LK, bool BUF>
+// is its row's absolute offset: one vector add per row instead of a 64-bit address).
+// SEL (G == 32, items in query order, one item per query = beam slot 0, one tile per parent): the FIRST STAGE of a bound-pruned layer in one
+// launch.  When the feature loop ends, the 32 lanes of an item hold every candidate K2 would rank for that query (rank_limit == 1), so the
+// epilogue does K2's work on them in registers -- the done flag, the top-k, the child ids -- two queries per wavefront, and stores the
+// candidate row only for the queries that are not done (the later stages rank it again together with the other slots' scores).
+template <int G, int NR, int PPC, int LK, bool BUF, bool SEL>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) k1t_kernel(K1TArgs a) {
     constexpr int W = 64 / G, H = 64, U = (G >= 16) ? 64 / G : 8, UNR = 8, STRIDE = G * NR;
     __shared__ uint2 hq_all[4 * W * (H + UNR)];
@@ -84,6 +97,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))
     const int grp = lane / G, lig = lane % G;
     uint2* __restrict__ my_hq = hq_all + ((size_t)wave * W + grp) * (H + UNR);   // hits {x value, byte offset of the row in the tile's block}
 
+    // SEL without an item list: what k0_prolongate lays out for beam slot 0 of query q when a parent is one tile (its first column is the
+    // chunk's: out_off = q * cand_stride).  The 32 lanes of the half load the same words; one hop more than reading the item (beam -> ptile -> tile).
+    auto derive_item = [&](uint64_t q) {
+        const uint32_t cnt = min(a.p_cnt[q], a.beam_in);
+        const uint32_t parent = cnt ? a.p_idx[q * a.p_stride] : 0u;
+        const float ps = a.p_val[q * a.p_stride];
+        const uint64_t xb = a.x_row_ptr[q];
+        const uint32_t xl = (uint32_t)(a.x_row_ptr[q + 1] - xb);
+        const uint32_t t0 = a.L.ptile[parent], t1 = a.L.ptile[parent + 1];
+        return make_item((uint32_t)q, (cnt && t1 > t0) ? t0 : kNoTile, (uint32_t)q * a.cand_stride, ps, xb, xl);
+    };
     ItemDesc it = make_item(0u, kNoTile, 0u, 0.f, 0, 0u);
     if (a.n_items) {   // tile-sorted list: every XCD takes a contiguous run of tiles
         const uint32_t n = *a.n_items, nb = (n + W - 1) / W;
@@ -92,9 +116,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))
         { const uint64_t slot = (uint64_t)xcd_remap_t(vblock, nb) * W + grp; if (slot < n) it = a.items[slot]; }
     } else {
         const uint64_t slot = (uint64_t)vblock * W + grp;
-        if (slot < a.n_slots) it = a.items[slot];
+        if (slot < a.n_slots) it = (SEL && !a.items) ? derive_item(slot) : a.items[slot];
     }
-    const bool active = it.tile != kNoTile;
+    bool active = it.tile != kNoTile;
     TileDesc td{};
     uint64_t xe = 0, cur = 0, wbase = 0;
     if (active) {
@@ -227,6 +251,81 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))
     drain_any();
 
     // ---- epilogue: bias (sparse X: LAST, inference.hpp:806-811), transform in fp64, combine with the parent's score, store
+    if constexpr (SEL) {
+        static_assert(G == 32, "the selecting epilogue ranks one item per half-wavefront");
+        int lane_e = lane;                                              // (opaque: nothing derived from the lane id stays live across the feature loop)
+        asm volatile("" : "+v"(lane_e));
+        const int grp = lane_e >> 5, lig = lane_e & 31;
+        const uint64_t slot = (uint64_t)vblock * W + grp;               // query order, one item per query: the slot IS the query
+        const bool qv = slot < a.n_slots;
+        const uint64_t q = qv ? slot : 0;
+        if constexpr (NR == 4) {   // four columns per lane leave no registers to carry the item across the feature loop: it is read again
+            it = a.items ? a.items[q] : derive_item(q);
+            active = qv && it.tile != kNoTile;
+            td = a.L.tiles[active ? it.tile : 0u];
+        }
+        // what k2_topk_wave reads for rank_limit == 1 (in flight during the transform)
+        const uint32_t pc = a.p_cnt[q], xok = a.xok[q];
+        const float ps_next = a.p_val[q * a.p_stride + 1u];             // (beam_in >= 2 on a pruned layer: the word exists, valid or not)
+        const float* __restrict__ bp = a.L.bias_prod + td.col_begin;
+        const bool add_bias = a.L.has_bias != 0 && !a.bias_first;
+        // candidate position = tile column NR * lig + k (slot 0, one tile); columns past the tile (and an inactive item) hold no candidate
+        uint32_t key[NR], sb[NR];
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+            const uint32_t c = (uint32_t)(NR * lig + k);
+            key[k] = 0u; sb[k] = 0u;
+            if (active && c < td.ncols) {
+                float s = acc[k];
+                if (add_bias) s = __fadd_rn(s, bp[c]);
+                float v = pp_transform<PPC>(a.pp_kind, a.pp_p, s);
+                if (!a.first_layer) v = pp_combine(a.pp_kind, v, it.pscore);
+                sb[k] = __float_as_uint(v); key[k] = score_key(v);
+            }
+        }
+        // done (before the extraction consumes the keys), as k2_topk_wave: k candidates of this slot score >= the best any later slot can reach
+        const bool limited = min(pc, a.beam_in) > 1u;
+        const uint32_t thr = score_key(a.mult ? fmaxf(ps_next, 0.0f) : ps_next);
+        uint32_t c_lo = 0, c_hi = 0;
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+            const unsigned long long b = __ballot(key[k] >= thr);        // (thr >= 1: an empty slot never counts; each half against its own bound)
+            c_lo += (uint32_t)__popc((uint32_t)b); c_hi += (uint32_t)__popc((uint32_t)(b >> 32));
+        }
+        const bool d = !limited || (xok != 0u && ps_next == ps_next && (grp ? c_hi : c_lo) >= a.k);
+        if (!a.items && __any(qv && !d)) {
+            // K0's other outputs, for the unfinished queries only (k0b_remaining and the later K2 launches skip a done query before they read
+            // them): lane j of the half takes beam slot j (beam_in <= 32), an exclusive prefix sum of the chunk widths gives cand_off, the total ncand
+            const uint32_t cnt = min(pc, a.beam_in);
+            const bool mine = qv && !d && (uint32_t)lig < cnt;
+            uint32_t wd = 0;
+            if (mine) { const uint32_t pj = a.p_idx[q * a.p_stride + (uint32_t)lig]; wd = a.L.chunk_col[pj + 1] - a.L.chunk_col[pj]; }
+            uint32_t incl = wd;
+#pragma unroll
+            for (int s = 1; s < 32; s <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)incl, s, 32); if (lig >= s) incl += y; }
+            const uint32_t total = (uint32_t)__shfl((int)incl, 31, 32);
+            if (mine) a.cand_off[q * a.beam_in + (uint32_t)lig] = incl - wd;
+            if (qv && !d && lig == 0) a.ncand[q] = total;
+        }
+        if (active && !d) {                                             // the later stages read the row of an unfinished query only (always: +0.034 ms on Amazon-670K)
+            float* __restrict__ out = a.cand + it.out_off;
+#pragma unroll
+            for (int k = 0; k < NR; ++k) { const uint32_t c = (uint32_t)(NR * lig + k); if (c < td.ncols) out[c] = __uint_as_float(sb[k]); }
+        }
+        uint32_t osb, ops, kk_lo, kk_hi;
+        halfwave_topk_extract<NR>(key, sb, a.k, lane_e, osb, ops, kk_lo, kk_hi);   // ties by position: see there
+        const uint32_t kk = grp ? kk_hi : kk_lo;
+        if (qv) {
+            if ((uint32_t)lig < kk) {
+                uint32_t child = td.col_begin + ops;                    // a one-tile parent: col_begin == chunk_col[parent]
+                if (a.perm_inv) child = a.perm_inv[child];
+                a.out_idx[q * a.out_stride + (uint32_t)lig] = child;
+                a.out_val[q * a.out_stride + (uint32_t)lig] = __uint_as_float(osb);
+            }
+            if (lig == 0) { a.out_cnt[q] = kk; a.done[q] = d ? 1u : 0u; }
+        }
+        return;
+    }
     if (!active) return;
     float* __restrict__ out = a.cand + it.out_off;
     const float* __restrict__ bp = a.L.bias_prod + td.col_begin;
@@ -282,11 +381,20 @@ void launch_tile_rows(const LayerDev& L, uint64_t total_floats, uint32_t* wt, hi
 
 bool k1t_serves(const LayerDev& L, const QueriesDev& X) { return L.wt != nullptr && !X.dense && (L.bitmap || L.bitmap64) && !L.bucket; }
 
-void launch_k1t(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, const void* items, const uint32_t* n_items, float* cand, hipStream_t s) {
+bool k1t_selects(const LayerDev& L, const LayerPlan& P, const QueriesDev& X) {
+    int g, nr;
+    k1t_shape(L.max_tile_cols, g, nr);
+    return k1t_serves(L, X) && P.tune.tile_rows >= 1 && P.tune.ablate == 0 && L.max_tiles_per_parent == 1 && g == 32 && nr <= 4 &&
+           P.k >= 1 && P.k <= kTopkExtractMaxK && P.beam_in >= 2 && !P.implicit_root && !P.first_layer && k2_wave_path(P);
+}
+
+void launch_k1t(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, const void* items, const uint32_t* n_items, float* cand, hipStream_t s,
+                const K1TSelect* sel) {
     if (P.nrows == 0) return;
-    K1TArgs a;
+    K1TArgs a{};
     a.L = L; a.X = X; a.items = static_cast<const ItemDesc*>(items); a.n_items = n_items; a.cand = cand;
-    a.n_slots = (uint64_t)P.nrows * P.beam_in * L.max_tiles_per_parent;
+    // (with `sel`, P is the WHOLE layer's plan -- `limited` needs its beam_in -- and the launch covers slot 0 of every query, one tile each)
+    a.n_slots = sel ? (uint64_t)P.nrows : (uint64_t)P.nrows * P.beam_in * L.max_tiles_per_parent;
     a.pp_kind = P.pp.kind; a.pp_p = P.pp.p; a.first_layer = P.first_layer; a.bias_first = P.bias_first;
     a.fb_out = (n_items && P.fb_host && P.layer >= 0 && P.layer < 16) ? P.fb_host + 32 + P.layer : nullptr;
     int g, nr;
@@ -295,23 +403,39 @@ void launch_k1t(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, cons
     const uint64_t vblocks = (a.n_slots + (uint64_t)(64 / g) - 1) / (uint64_t)(64 / g);
     if (vblocks > 0x7FFFFFFFull) fail("k1t: grid too large; lower max_batch_rows");
     a.n_vblocks = (uint32_t)vblocks;
-    const dim3 grid((uint32_t)((vblocks + 3) / 4)), block(256);
     const int ppc = pp_class(P.pp);
     const int lk = L.bitmap64 ? 2 : 0;
     const bool buf = L.wt_bytes != 0 && L.wt_bytes < 0xFFFFFF00ull;   // (gfx9 range-checks voffset against num_records: the array's bytes)
     a.wt_bytes = buf ? (uint32_t)L.wt_bytes : 0u;
-#define XRL_K1T_B(GG, NN, BB) do { \
-        if (ppc) { if (lk) hipLaunchKernelGGL((k1t_kernel<GG, NN, 1, 2, BB>), grid, block, 0, s, a); else hipLaunchKernelGGL((k1t_kernel<GG, NN, 1, 0, BB>), grid, block, 0, s, a); } \
-        else     { if (lk) hipLaunchKernelGGL((k1t_kernel<GG, NN, 0, 2, BB>), grid, block, 0, s, a); else hipLaunchKernelGGL((k1t_kernel<GG, NN, 0, 0, BB>), grid, block, 0, s, a); } } while (0)
-#define XRL_K1T(GG, NN) do { if (buf) XRL_K1T_B(GG, NN, true); else XRL_K1T_B(GG, NN, false); } while (0)
+    if (sel) {
+        if (n_items || !k1t_selects(L, P, X)) fail("k1t: the selecting epilogue does not serve this launch");
+        if (!sel->done || !sel->xok) fail("k1t: bound pruning needs the done and the per-query guard flags");
+        a.p_cnt = sel->prev.cnt; a.p_val = sel->prev.val; a.p_stride = sel->prev.stride; a.beam_in = P.beam_in;
+        a.xok = sel->xok; a.perm_inv = L.perm_inv;
+        a.out_idx = sel->out_idx; a.out_val = sel->out_val; a.out_cnt = sel->out_cnt; a.done = sel->done;
+        a.out_stride = sel->out_stride; a.k = P.k;
+        a.mult = (P.pp.kind == PP_SIGMOID || P.pp.kind == PP_LP_HINGE) ? 1 : 0;
+        if (!items) {
+            if (!sel->cand_off || !sel->ncand || P.beam_in > 32u) fail("k1t: the launch cannot derive its items");
+            if ((uint64_t)P.nrows * P.cand_stride > 0xFFFFFFFFull) fail("k1t: candidate buffer exceeds 2^32 floats; lower max_batch_rows");
+            a.p_idx = sel->prev.idx; a.x_row_ptr = X.row_ptr + P.row0; a.cand_stride = P.cand_stride; a.cand_off = sel->cand_off; a.ncand = sel->ncand;
+        }
+    }
+    const dim3 grid((a.n_vblocks + 3u) / 4u), block(256);
+#define XRL_K1T_L(GG, NN, BB, SS) do { \
+        if (ppc) { if (lk) hipLaunchKernelGGL((k1t_kernel<GG, NN, 1, 2, BB, SS>), grid, block, 0, s, a); else hipLaunchKernelGGL((k1t_kernel<GG, NN, 1, 0, BB, SS>), grid, block, 0, s, a); } \
+        else     { if (lk) hipLaunchKernelGGL((k1t_kernel<GG, NN, 0, 2, BB, SS>), grid, block, 0, s, a); else hipLaunchKernelGGL((k1t_kernel<GG, NN, 0, 0, BB, SS>), grid, block, 0, s, a); } } while (0)
+#define XRL_K1T(GG, NN) do { if (buf) XRL_K1T_L(GG, NN, true, false); else XRL_K1T_L(GG, NN, false, false); } while (0)
+#define XRL_K1T_S(NN) do { if (sel) { if (buf) XRL_K1T_L(32, NN, true, true); else XRL_K1T_L(32, NN, false, true); } else XRL_K1T(32, NN); } while (0)
     if (g == 8) XRL_K1T(8, 1);
     else if (g == 16) XRL_K1T(16, 1);
-    else if (nr == 1) XRL_K1T(32, 1);
-    else if (nr == 2) XRL_K1T(32, 2);
-    else if (nr == 3) XRL_K1T(32, 3);
-    else XRL_K1T(32, 4);
+    else if (nr == 1) XRL_K1T_S(1);
+    else if (nr == 2) XRL_K1T_S(2);
+    else if (nr == 3) XRL_K1T_S(3);
+    else XRL_K1T_S(4);
+#undef XRL_K1T_S
 #undef XRL_K1T
-#undef XRL_K1T_B
+#undef XRL_K1T_L
     XRL_LAUNCH_CHECK();
 }
 

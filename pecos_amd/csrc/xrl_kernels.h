@@ -108,7 +108,14 @@ void launch_tfidf_weight(const uint64_t* row_ptr, const uint32_t* col_idx, const
 int k1_auto_group(const LayerDev& L, const Layer& host, int dense);
 // K1T (xrl_k1t.hip): K1 on the densely held tile rows (LayerDev::wt), accumulators in registers; launch_k1 routes to it when k1t_serves
 bool k1t_serves(const LayerDev& L, const QueriesDev& X);
-void launch_k1t(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, const void* items, const uint32_t* n_items, float* cand, hipStream_t s);
+// `sel` (option leaf_fuse): the first stage of a bound-pruned layer in ONE launch -- one item per query (beam slot 0, query order), and the
+// kernel's epilogue does what launch_k2_topk(rank_limit = 1, done) would do on the row it has just computed: top-k, child ids, done[q]
+// for every query; the candidate row is stored for the queries that are not done.  P is the whole layer's plan.  items == nullptr (beam_in <= 32):
+// the launch derives its items from the beam itself and writes cand_off / ncand of the unfinished queries -- no launch_k0_prolongate before it.
+struct K1TSelect { BeamDev prev; const uint32_t* xok; uint32_t* out_idx; float* out_val; uint32_t* out_cnt; uint32_t out_stride; uint32_t* done; uint32_t* cand_off; uint32_t* ncand; };
+bool k1t_selects(const LayerDev& L, const LayerPlan& P, const QueriesDev& X);   // one tile per parent, 32 lanes per item, k <= kTopkExtractMaxK, a combining layer
+void launch_k1t(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, const void* items, const uint32_t* n_items, float* cand, hipStream_t s,
+                const K1TSelect* sel = nullptr);
 // K1Q (xrl_k1q.hip): a whole layer -- prolongate, chunk products against the DENSE row format, post-processor,
 // combine, top-k, child re-ordering -- in one query-stationary kernel: previous beam in, next beam out.
 uint32_t k1q_regs(const LayerDev& L, uint32_t beam_in, uint32_t k, bool dense_x);   // 0: the layer / beam / k cannot (or should not) be served by K1Q

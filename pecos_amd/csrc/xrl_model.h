@@ -215,6 +215,7 @@ struct Model {
     int adaptive = 1;                       // 0: always stage (xrl_set_option "adaptive")
     int presence = 1;                       // K1Q, sparse X: 1 = layers that run UNSTAGED (prune off, or switched by the pruning feedback) request a (feature, parent) weight
                                             // segment only when the layer's presence word says it holds a weight; 2 = every layer that has presence words; 0 = never
+    int leaf_fuse = 1;                      // bound-pruned tile-format layers of one-tile parents: K1T derives its items and selects the first stage's top-k itself (no k0_prolongate / k2_topk launch); 2: K0 still launched; 0: three launches
     int prune_mid = 1;                      // bound-pruned tile-format layers with >= 16 beam parents: a middle stage (slots 1..4) between the first parent and "everything else"
     int sort_rest = 1;                      // bound-pruned tile-format layers: the second phase's compacted items are tile-sorted before K1 runs on them (0: query order)
     int sort_rest_min = 32768;              // ... only when the previous predicts' later stages held at least this many items (pruning feedback's count; 0 = always)

@@ -393,11 +393,22 @@ void predict_device(Model& m, const QueriesDev& X, const PredictOpts& o, uint32_
                 lw.items_sorted.reserve(slots_max * k0_item_bytes());
                 need_x_ok();
                 LayerPlan PA = P; PA.beam_in = J;                  // (K1 sizes its grid from beam_in x tiles per parent)
-                timed("k0_prolongate", (uint32_t)l, [&] { launch_k0_prolongate(L.dev, P, X, prev, lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>(), lw.items.p, S, J); });
+                // option leaf_fuse: with one tile per parent, K1T's lanes end up holding every candidate of slot 0 -- its epilogue selects the top-k
+                // and sets the done flags itself (xrl_k1t.hip, SEL): no k2_topk launch, and no candidate row stored for a query that is done.  The
+                // launch keeps K1's profile name; the later stages find done / cand_off / ncand / cand (unfinished queries) as K0 -> K1 -> K2 leave them.
+                const bool fuse = m.leaf_fuse != 0 && J == 1 && !o.stats_out && k1t_selects(L.dev, P, X);
+                // ... and (beams of up to 32 parents) derives its items from the beam: K0 is not launched either.  leaf_fuse = 2 keeps K0 (A/B runs).
+                const bool fuse_k0 = fuse && m.leaf_fuse != 2 && beam_in[l] <= 32u;
+                if (!fuse_k0) timed("k0_prolongate", (uint32_t)l, [&] { launch_k0_prolongate(L.dev, P, X, prev, lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>(), lw.items.p, S, J); });
                 if (lanes == 2 && k1_done) XRL_HIP(hipStreamWaitEvent(S, k1_done, 0));
+                if (fuse) {
+                    const K1TSelect sel{prev, lw.x_ok.as<uint32_t>(), oi, ov, oc, os, lw.prune_done.as<uint32_t>(), lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>()};
+                    timed("k1_sparse", (uint32_t)l, [&] { launch_k1t(L.dev, P, X, fuse_k0 ? nullptr : lw.items.p, nullptr, lw.cand.as<float>(), S, &sel); });
+                } else {
                 timed(X.dense ? "k1_dense" : "k1_sparse", (uint32_t)l, [&] { launch_k1(L.dev, PA, X, lw.items.p, nullptr, lw.cand.as<float>(), g, S); });
                 timed("k2_topk", (uint32_t)l, [&] { launch_k2_topk(L.dev, P, prev, lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>(), lw.cand.as<float>(), oi, ov, oc, os, S,
                                                                    J, (uint32_t)L.cand_bound(J), lw.prune_done.as<uint32_t>(), nullptr, lw.x_ok.as<uint32_t>()); });
+                }
                 if (o.stats_out) XRL_HIP(hipMemsetAsync(lw.items_sorted.p, 0xFF, slots_b * k0_item_bytes(), S));   // the stats pass walks the whole list: unused slots read as "no tile"
                 bool srt = sorts_rest(l);
                 // ... unless the previous predicts left (almost) nothing for the later stages: four tiny launches of the sort then cost more than
