@@ -353,6 +353,11 @@ uint64_t xrl_debug_layout_rows(const uint32_t* rptr, uint32_t nrows, int align, 
  *   "k1g_min_items"       dense X: a dense-format layer runs the tiled, k-ordered SGEMM K1G (tile-sorted items, weight and query
  *                         panels staged in LDS) once a parent serves this many queries on average (default 16; 0 = never: K1Q)
  *   "k1g_variant"         1: the alternative register-tile / panel shapes of K1G (A/B, tests; results identical)
+ *   "k1g_first"           K1G layers under bound pruning: beam parents scored in the first stage (0 = default: about one candidate register,
+ *                         64 / children per parent)
+ *   "tile_rows"           tile-format layers that carry densely held tile rows, sparse X: 1 (default) = launches on items in query order run
+ *                         K1T, 2 = every launch, 0 = always the entry-list kernel K1
+ *   "k2_big_min_k"        > 0: top-k sizes from this value on take the segmented-sort K2 that otherwise serves k > 20 480 (tests); 0 (default)
  *   "k1_wpb", "k1_lds_pad", "k1_ablate"   debug: wavefronts per K1 workgroup, extra LDS per wavefront, phase ablation
  * Environment read at model load: XRL_LOOKUP=bitmap|bitmap64|bucket (force the row
  * lookup structure; default per layer: bucket table if rank-bitmaps would take more than a quarter of the free HBM, else

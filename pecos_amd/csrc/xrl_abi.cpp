@@ -284,7 +284,7 @@ void host_compute(Model& m, const XT* input_x, PredictOpts o, bool is_csr) {
     // tiled SGEMM K1G needs many queries per parent (a 24 MB batch of 768-float rows would leave ~10 per leaf parent and fall
     // back to the query-stationary kernel, 5x slower).  The upload itself always moves in <= 32 MB chunks through two pinned
     // staging buffers, whatever the batch size.
-    const bool staged = m.host_pipeline && bytes >= (32ull << 20);
+    const bool staged = m.opt.host_pipeline && bytes >= (32ull << 20);
     // CSR: batches GROW (x1.6 from a third of host_batch_mb up to 3x host_batch_mb): the first kernels start after a few megabytes have
     // arrived, the later launches are large enough to fill the chip (a 40 k-row launch of the query-stationary kernel runs at 0.7x
     // the per-row rate of a 490 k-row one: measured with rocprofv3's copy + kernel trace, profiles/r03_pruning_topk.md section 4)
@@ -292,8 +292,8 @@ void host_compute(Model& m, const XT* input_x, PredictOpts o, bool is_csr) {
     if (staged && rows >= 8192) {
         if (is_csr) {
             const double mb = (double)(1u << 20) / 8.0;                    // elements per megabyte of (id, value) pairs
-            double cur = std::max(1, m.host_batch_mb) / 3.0, pos = 0.0;
-            const double cap = 3.0 * std::max(1, m.host_batch_mb);
+            double cur = std::max(1, m.opt.host_batch_mb) / 3.0, pos = 0.0;
+            const double cap = 3.0 * std::max(1, m.opt.host_batch_mb);
             while (pos + cur * mb < (double)elems && share.size() < 31) { pos += cur * mb; share.push_back((uint64_t)pos); cur = std::min(cap, cur * 1.6); }
             // a short last batch joins the previous one (the tail after the upload ends is one launch either way)
             // (round 5 tried a TAPERED end -- last two batches of host_batch_mb and half of it, to shorten the tail after the last byte of X has
@@ -374,7 +374,7 @@ void host_compute(Model& m, const XT* input_x, PredictOpts o, bool is_csr) {
     // option host_register: page-lock the caller's arrays in place for the duration of the call and let the copy engine read them
     // directly (no staging memcpy); falls back to staging when the registration fails
     bool reg_idx = false, reg_val = false;
-    if (m.host_register) {
+    if (m.opt.host_register) {
         if (is_csr) {
             reg_idx = hipHostRegister(const_cast<uint32_t*>(Xs->col_idx), elems * 4, hipHostRegisterDefault) == hipSuccess;
             reg_val = reg_idx && hipHostRegister(const_cast<float*>(Xs->val), elems * 4, hipHostRegisterDefault) == hipSuccess;
@@ -393,7 +393,7 @@ void host_compute(Model& m, const XT* input_x, PredictOpts o, bool is_csr) {
     // two compute lanes for the row batches (see HostLanes above); the handle's lock is held by the caller
     // (overlap_min_rows > 0 makes predict_device itself run two lanes over ws.lane[0 / 1] and the auxiliary stream: the two schemes would share
     //  scratch and stream without an ordering between them, so the host lanes stand down -- ADVICE r5)
-    const bool two = host_streams() == 2 && n_batch >= 3 && !m.profiling && m.overlap_min_rows == 0;
+    const bool two = host_streams() == 2 && n_batch >= 3 && !m.profiling && m.opt.overlap_min_rows == 0;
     Model::HostLanes* hl = &m.host_lanes;
     g_ht.prep += now_ms() - t_ph;
     try {
@@ -945,13 +945,7 @@ static void warm_handle(Model& m) {
     // The warm-up queries (one feature each) say nothing about the caller's data: what the pruning feedback learned from them is discarded -- round 6: their
     // later stages hold almost every item, which marked the leaf "unstaged" and made a fresh handle score all beam parents of every query until the first
     // re-probe, 32 row batches (~3 host-ABI calls) later.
-    if (m.fb_host) {
-        for (int l = 0; l < Model::kFbLayers; ++l) {
-            m.fb_unstaged[l] = 0; m.fb_probing[l] = 0; m.fb_unstaged_calls[l] = 0; m.fb_tile_slots[l] = 0;
-            m.fb_seen[l] = m.fb_host[2 * l]; m.fb_second[l] = m.fb_host[2 * l + 1];
-            m.fb_host[2 * Model::kFbLayers + l] = 0xFFFFFFFFu;
-        }
-    }
+    m.fb.reset();
 }
 
 void* c_xlinear_load_model_from_disk_ext(const char* model_path, int weight_matrix_type) {
@@ -1406,24 +1400,20 @@ uint64_t xrl_debug_layout_rows(const uint32_t* rptr, uint32_t nrows, int align, 
     return v;
 }
 
+// every integer option that is a plain store into Model::Options, under the member's own name (include/xrl_abi.h documents the keys)
+#define XRL_OPT(name) {#name, &Model::Options::name}
+static const struct { const char* name; int Model::Options::*field; } kIntOptions[] = {
+    XRL_OPT(k1_group), XRL_OPT(sort_min_tiles), XRL_OPT(sort_rest), XRL_OPT(sort_rest_min), XRL_OPT(prune_mid), XRL_OPT(leaf_fuse), XRL_OPT(tile_rows),
+    XRL_OPT(k2_big_min_k), XRL_OPT(qsort), XRL_OPT(qsort_min_parents), XRL_OPT(qsort_min_rows), XRL_OPT(presence), XRL_OPT(adaptive), XRL_OPT(prune),
+    XRL_OPT(host_pipeline), XRL_OPT(host_batch_mb), XRL_OPT(host_register), XRL_OPT(overlap_min_rows),
+    XRL_OPT(dense_layers), XRL_OPT(k1q_fuse), XRL_OPT(k1g_first), XRL_OPT(k1g_min_items), XRL_OPT(k1g_variant),
+    XRL_OPT(k1_wpb), XRL_OPT(k1_lds_pad), XRL_OPT(k1_ablate),   // debug: wavefronts per K1 workgroup, occupancy experiments, timing ablations only
+};
+#undef XRL_OPT
+
 static void set_option_one(Model& m, const char* key, int64_t value) {
-    if (!std::strcmp(key, "k1_group")) m.k1_group = (int)value;
-    else if (!std::strcmp(key, "max_batch_rows")) m.max_batch_rows = value;
-    else if (!std::strcmp(key, "sort_min_tiles")) m.sort_min_tiles = (int)value;
-    else if (!std::strcmp(key, "sort_rest")) m.sort_rest = (int)value;
-    else if (!std::strcmp(key, "prune_mid")) m.prune_mid = (int)value;
-    else if (!std::strcmp(key, "leaf_fuse")) m.leaf_fuse = (int)value;
-    else if (!std::strcmp(key, "tile_rows")) m.tile_rows = (int)value;
-    else if (!std::strcmp(key, "k2_big_min_k")) m.k2_big_min_k = (int)value;
-    else if (!std::strcmp(key, "qsort")) m.qsort = (int)value;                         // 0: K1Q never runs a layer on sorted queries
-    else if (!std::strcmp(key, "qsort_min_parents")) m.qsort_min_parents = (int)value;
-    else if (!std::strcmp(key, "qsort_min_rows")) m.qsort_min_rows = (int)value;
-    else if (!std::strcmp(key, "presence")) m.presence = (int)value;
-    else if (!std::strcmp(key, "adaptive")) { m.adaptive = (int)value; for (auto& u : m.fb_unstaged) u = 0; for (auto& u : m.fb_probing) u = 0; }
-    else if (!std::strcmp(key, "host_pipeline")) m.host_pipeline = (int)value;
-    else if (!std::strcmp(key, "host_batch_mb")) m.host_batch_mb = (int)value;
-    else if (!std::strcmp(key, "sort_rest_min")) m.sort_rest_min = (int)value;
-    else if (!std::strcmp(key, "reserve_rows")) {
+    if (!std::strcmp(key, "max_batch_rows")) { m.opt.max_batch_rows = value; return; }
+    if (!std::strcmp(key, "reserve_rows")) {
         // a serving process that knows its largest batch sizes the result buffers of the host ABI once, at start-up (pinned host memory: rows x
         // the model's default top-k x 8 bytes, + the device side), instead of inside its first large call
         if (value < 0 || value > 0x7FFFFFFF) fail("reserve_rows: expected 0 .. 2^31-1");
@@ -1431,21 +1421,12 @@ static void set_option_one(Model& m, const char* key, int64_t value) {
         use_device(m.device);
         if (!m.ws) m.ws = std::make_unique<Workspace>();
         reserve_outputs(m, (uint32_t)value, effective_topk(m, 0));
+        return;
     }
-    else if (!std::strcmp(key, "host_register")) m.host_register = (int)value;   // 1: page-lock the caller's X in place (hipHostRegister) instead of staging it through pinned buffers   // 0: the host ABI uploads X in one piece before computing
-    else if (!std::strcmp(key, "k1q_fuse")) m.k1q_fuse = (int)value;           // 0: one K1Q launch per dense-format layer
-    else if (!std::strcmp(key, "k1g_first")) m.k1g_first = (int)value;
-    else if (!std::strcmp(key, "k1g_min_items")) m.k1g_min_items = (int)value;   // dense X: queries per parent from which a dense-format layer runs the tiled SGEMM K1G (0 = never)
-    else if (!std::strcmp(key, "dense_layers")) m.dense_layers = (int)value;   // 0: never run the fused dense-format kernel K1Q
-    else if (!std::strcmp(key, "overlap_min_rows")) m.overlap_min_rows = (int)value;
-    else if (!std::strcmp(key, "prune")) m.prune = (int)value;            // 0: evaluate every candidate of every beam parent (no exact bound pruning)
-    else if (!std::strcmp(key, "k1g_variant")) m.k1g_variant = (int)value;   // K1G tile-shape alternative (tuning; results identical)
-    else if (!std::strcmp(key, "k1_wpb")) m.k1_wpb = (int)value;
-    else if (!std::strcmp(key, "k1_lds_pad")) m.k1_lds_pad = (int)value;   // debug: occupancy experiments
-    else if (!std::strcmp(key, "k1_ablate")) m.k1_ablate = (int)value;     // debug: timing ablations only
-    else fail(std::string("unknown option ") + key);
+    for (const auto& o : kIntOptions)
+        if (!std::strcmp(key, o.name)) { m.opt.*o.field = (int)value; if (o.field == &Model::Options::adaptive) m.fb.restage(); return; }
+    fail(std::string("unknown option ") + key);
 }
-
 
 int xrl_set_option(void* model, const char* key, int64_t value) {
     int rc = -1;
@@ -1467,10 +1448,7 @@ int xrl_set_option(void* model, const char* key, int64_t value) {
                 use_device(dev);
                 std::unique_ptr<Model> r = m.src_kind == 0 ? load_model_from_disk(m.src_path, m.weight_matrix_type) : load_mmap_model_from_disk(m.src_path);
                 r->device = dev;
-                r->k1_group = m.k1_group; r->max_batch_rows = m.max_batch_rows; r->sort_min_tiles = m.sort_min_tiles; r->sort_rest = m.sort_rest; r->sort_rest_min = m.sort_rest_min; r->prune_mid = m.prune_mid; r->leaf_fuse = m.leaf_fuse; r->tile_rows = m.tile_rows; r->k2_big_min_k = m.k2_big_min_k; r->qsort = m.qsort; r->qsort_min_parents = m.qsort_min_parents; r->qsort_min_rows = m.qsort_min_rows; r->presence = m.presence; r->adaptive = m.adaptive; r->host_pipeline = m.host_pipeline; r->host_batch_mb = m.host_batch_mb; r->host_register = m.host_register;
-                r->k1q_fuse = m.k1q_fuse; r->k1g_min_items = m.k1g_min_items; r->k1g_first = m.k1g_first; r->dense_layers = m.dense_layers;
-                r->overlap_min_rows = m.overlap_min_rows; r->prune = m.prune;
-                r->k1g_variant = m.k1g_variant; r->k1_wpb = m.k1_wpb; r->k1_lds_pad = m.k1_lds_pad; r->k1_ablate = m.k1_ablate;
+                r->opt = m.opt;
                 m.replicas.push_back(std::move(r));
             }
             use_device(m.device);

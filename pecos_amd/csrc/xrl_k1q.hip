@@ -23,8 +23,8 @@ static uint32_t k1q_bucket(uint32_t ns) { return ns <= 1 ? 1 : ns <= 2 ? 2 : ns 
 static uint32_t k1q_kernel_bucket(uint32_t ns) { return ns <= 1 ? 1 : ns <= 3 ? 3 : ns <= 6 ? 6 : 16; }   // kernels are compiled for these maxima
 
 // n consecutive dense-format layers (n <= kK1QMaxLayers) in ONE launch: previous beam in, the last layer's beam out
-void launch_k1q(const LayerDev* const* Ls, const LayerPlan* Ps, int n, const QueriesDev& X, BeamDev prev, uint32_t* out_idx, float* out_val,
-                uint32_t* out_cnt, uint32_t out_stride, hipStream_t s, float prune_wmax, uint32_t* out_xok, const uint32_t* qperm) {
+void launch_k1q(const LayerDev* const* Ls, const LayerPlan* Ps, int n, const QueriesDev& X, BeamDev prev, BeamDev out,
+                hipStream_t s, float prune_wmax, uint32_t* out_xok, const uint32_t* qperm) {
     if (n <= 0 || n > kK1QMaxLayers) fail("k1q: bad layer count");
     if (n > 1) for (int l = 0; l < n; ++l) if (k1q_regs(*Ls[l], Ps[l].beam_in, Ps[l].k, true) > 3) fail("k1q: only layers of <= 3 candidate registers can share a launch");
     if (Ps[0].nrows == 0) return;
@@ -43,7 +43,7 @@ void launch_k1q(const LayerDev* const* Ls, const LayerPlan* Ps, int n, const Que
         y.d_gp_log2 = L.d_gp_log2; y.d_max_tiles = L.d_max_tiles; y.n_parents = L.n_parents; y.w_rows = L.w_rows;
         y.beam_in = P.beam_in; y.k = P.k; y.ns = k1q_bucket(ns);
         y.has_bias = L.has_bias; y.pp_kind = P.pp.kind; y.pp_p = P.pp.p; y.first_layer = P.first_layer; y.implicit_root = P.implicit_root; y.bias_first = P.bias_first; y.prune = P.prune;
-        y.layer_id = (P.layer >= 0 && P.layer < 16) ? P.layer : 0;
+        y.layer_id = (P.layer >= 0 && P.layer < kFbLayers) ? P.layer : 0;
         y.regular = L.d_regular;
         nsmax = std::max(nsmax, y.ns); ppc |= pp_class(P.pp);
     }
@@ -60,7 +60,7 @@ void launch_k1q(const LayerDev* const* Ls, const LayerPlan* Ps, int n, const Que
         a.wd01 = Ls[0]->wd01; a.wd01_c1 = Ls[0]->wd01_c1;
     }
     a.p_idx = prev.idx; a.p_val = prev.val; a.p_cnt = prev.cnt; a.p_stride = prev.stride;
-    a.out_idx = out_idx; a.out_val = out_val; a.out_cnt = out_cnt; a.out_stride = out_stride;
+    a.out_idx = out.idx; a.out_val = out.val; a.out_cnt = out.cnt; a.out_stride = out.stride;
     a.row0 = Ps[0].row0; a.nrows = Ps[0].nrows;
     a.prune_wmax = prune_wmax; a.out_xok = out_xok;
     a.fb_dev = Ps[0].fb_dev; a.fb_host = Ps[0].fb_host;

@@ -363,7 +363,7 @@ __device__ __forceinline__ uint32_t k1q_layer(const K1QLayer& Ly, const QueriesD
         const bool xok = prune_guard_ok(wave_max_u32(xmx), xn, wmax);
         const bool second = !prune_all_in_first && (cge < Ly.k || !xok);
 #ifndef XRL_K1Q_NOFB
-        if (!prune_all_in_first) fbm |= (1u | (second ? 0x10000u : 0u)) << Ly.layer_id;   // pruning feedback: staged here / second pass needed (counted once, at the end of the kernel)
+        if (!prune_all_in_first) fbm |= (1u | (second ? 1u << kFbLayers : 0u)) << Ly.layer_id;   // pruning feedback: staged here / second pass needed (counted once, at the end of the kernel)
 #endif
         if (second) {
             pass(std::integral_constant<int, (NS > 1 ? 1 : 0)>{}, std::integral_constant<int, NS>{});
@@ -662,7 +662,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NSMAX
     }
     wave_sync_lds();
     const uint64_t xrow = (uint64_t)a.row0 + q;
-    uint32_t fbm = 0u;                                                 // pruning feedback: bit l = layer l ran staged, bit 16 + l = its second pass was needed
+    uint32_t fbm = 0u;                                                 // pruning feedback: bit l = layer l ran staged, bit kFbLayers + l = its second pass was needed
     int l_first = 0;
     if (MULTI && !DENSEX && a.fuse01 == 2) { cnt = k1q_layer01m<PPC, BIASF>(a.layer[0], a.layer[1], a.wd01, a.wd01_c1, a.X, xrow, s_bidx, s_bval, sc, lane); l_first = 2; }
     else if (MULTI && !DENSEX && a.fuse01) { cnt = k1q_layer01<PPC, BIASF, BIGW>(a.layer[0], a.layer[1], a.X, xrow, s_bidx, s_bval, sc, lane); l_first = 2; }
@@ -685,12 +685,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NSMAX
         a.out_val[o] = s_bval[lane];
     }
     if (lane == 0) a.out_cnt[q] = cnt;
-    // pruning feedback (Model::fb_*): one query in 64 adds its layers' outcomes to the device counters; query 0 publishes what the
+    // pruning feedback (xrl_feedback.h): one query in 64 adds its layers' outcomes to the device counters; query 0 publishes what the
     // EARLIER launches counted to the host-visible words (read by the host at the start of a later predict, without synchronisation)
 #ifndef XRL_K1Q_NOFB
     if (a.fb_dev && (q & 63u) == 0u) {
-        if (q == 0u && a.fb_host && lane < 32) a.fb_host[lane] = a.fb_dev[lane];
-        if (lane < 16 && ((fbm >> lane) & 1u)) { atomicAdd(&a.fb_dev[2 * lane], 1u); if ((fbm >> (16 + lane)) & 1u) atomicAdd(&a.fb_dev[2 * lane + 1], 1u); }
+        if (q == 0u && a.fb_host && lane < kFbCounterWords) a.fb_host[lane] = a.fb_dev[lane];
+        if (lane < kFbLayers && ((fbm >> lane) & 1u)) { atomicAdd(&a.fb_dev[fb_seen_word(lane)], 1u); if ((fbm >> (kFbLayers + lane)) & 1u) atomicAdd(&a.fb_dev[fb_second_word(lane)], 1u); }
     }
 #endif
     if (a.out_xok) {   // the pruning guard of this query, for a bound-pruned tile-format layer that follows (its K2 decides there)

@@ -396,7 +396,7 @@ void launch_k1t(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, cons
     // (with `sel`, P is the WHOLE layer's plan -- `limited` needs its beam_in -- and the launch covers slot 0 of every query, one tile each)
     a.n_slots = sel ? (uint64_t)P.nrows : (uint64_t)P.nrows * P.beam_in * L.max_tiles_per_parent;
     a.pp_kind = P.pp.kind; a.pp_p = P.pp.p; a.first_layer = P.first_layer; a.bias_first = P.bias_first;
-    a.fb_out = (n_items && P.fb_host && P.layer >= 0 && P.layer < 16) ? P.fb_host + 32 + P.layer : nullptr;
+    a.fb_out = (n_items && P.fb_host && P.layer >= 0 && P.layer < kFbLayers) ? P.fb_host + fb_items_word(P.layer) : nullptr;
     int g, nr;
     k1t_shape(L.max_tile_cols, g, nr);
     if ((uint32_t)(g * nr) != L.wt_stride || nr > 4) fail("k1t: the layer's tile rows were laid out for another shape");
@@ -412,8 +412,8 @@ void launch_k1t(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, cons
         if (!sel->done || !sel->xok) fail("k1t: bound pruning needs the done and the per-query guard flags");
         a.p_cnt = sel->prev.cnt; a.p_val = sel->prev.val; a.p_stride = sel->prev.stride; a.beam_in = P.beam_in;
         a.xok = sel->xok; a.perm_inv = L.perm_inv;
-        a.out_idx = sel->out_idx; a.out_val = sel->out_val; a.out_cnt = sel->out_cnt; a.done = sel->done;
-        a.out_stride = sel->out_stride; a.k = P.k;
+        a.out_idx = sel->out.idx; a.out_val = sel->out.val; a.out_cnt = sel->out.cnt; a.done = sel->done;
+        a.out_stride = sel->out.stride; a.k = P.k;
         a.mult = (P.pp.kind == PP_SIGMOID || P.pp.kind == PP_LP_HINGE) ? 1 : 0;
         if (!items) {
             if (!sel->cand_off || !sel->ncand || P.beam_in > 32u) fail("k1t: the launch cannot derive its items");

@@ -23,7 +23,7 @@ struct BeamDev {
     uint32_t stride;
 };
 
-struct K1Tune { int wpb = 1, lds_pad = 0, ablate = 0, k1g_variant = 0, pres_mode = 1, tile_rows = 1, k2_big_min_k = 0; };   // per-model tuning / debug knobs (xrl_set_option k1_wpb, k1_lds_pad, k1_ablate, k1g_variant)
+struct K1Tune { int wpb = 1, lds_pad = 0, ablate = 0, k1g_variant = 0, pres_mode = 1, tile_rows = 1, k2_big_min_k = 0; };   // per-model tuning / debug knobs (xrl_set_option k1_wpb, k1_lds_pad, k1_ablate, k1g_variant, presence, tile_rows, k2_big_min_k), filled by make_plan (xrl_predict.cpp)
 
 struct LayerPlan {
     uint32_t row0, nrows;       // query rows [row0, row0+nrows) of the query matrix
@@ -33,13 +33,13 @@ struct LayerPlan {
     PostProc pp;
     int first_layer;            // no combine (no_prev_pred)
     int implicit_root;          // previous beam is the implicit all-ones root
-    int prune;                  // exact bound pruning allowed (Model::prune)
+    int prune;                  // exact bound pruning allowed (option prune, and the layer not switched to unstaged by the pruning feedback)
     int bias_first;             // sparse X under weight_matrix_type HASH_CHUNKED: the bias row is applied BEFORE the query's features
                                 // (chunk_ops<csr, hash>, inference.hpp:705-735); dense X is bias-first in every layout
     int layer;                  // index in the chain (profiling, feedback slot)
     K1Tune tune;
-    uint32_t* fb_host = nullptr;  // pruning feedback (Model::fb_host), or nullptr
-    uint32_t* fb_dev = nullptr;   // K1Q's sampled counters (Model::fb_dev)
+    uint32_t* fb_host = nullptr;  // pruning feedback (PruneFeedback::host), or nullptr
+    uint32_t* fb_dev = nullptr;   // K1Q's sampled counters (PruneFeedback::dev)
 };
 
 // K0  prolongate: per query, offsets of every beam parent's child block + candidate count, and one
@@ -67,8 +67,7 @@ uint32_t sort_max_tiles();
 size_t sort_hist_bytes(uint64_t n_slots, uint32_t n_tiles);
 // K2  per-query top-k with (value desc, position asc) order; maps positions to original child ids.
 void launch_k2_topk(const LayerDev& L, const LayerPlan& P, BeamDev prev, const uint32_t* cand_off,
-                    const uint32_t* ncand, const float* cand, uint32_t* out_idx, float* out_val,
-                    uint32_t* out_cnt, uint32_t out_stride, hipStream_t s,
+                    const uint32_t* ncand, const float* cand, BeamDev out, hipStream_t s,
                     uint32_t rank_limit = 0 /* > 0: only the candidates of the first rank_limit beam slots */, uint32_t limited_cands = 0 /* their maximum number */,
                     uint32_t* done = nullptr /* out: that selection is final (exact bound, see K2Args) */, const uint32_t* skip_done = nullptr /* queries to skip */,
                     const uint32_t* xok = nullptr /* with done: the per-query pruning guard (launch_xguard / K1Q's out_xok) */);
@@ -112,7 +111,7 @@ bool k1t_serves(const LayerDev& L, const QueriesDev& X);
 // kernel's epilogue does what launch_k2_topk(rank_limit = 1, done) would do on the row it has just computed: top-k, child ids, done[q]
 // for every query; the candidate row is stored for the queries that are not done.  P is the whole layer's plan.  items == nullptr (beam_in <= 32):
 // the launch derives its items from the beam itself and writes cand_off / ncand of the unfinished queries -- no launch_k0_prolongate before it.
-struct K1TSelect { BeamDev prev; const uint32_t* xok; uint32_t* out_idx; float* out_val; uint32_t* out_cnt; uint32_t out_stride; uint32_t* done; uint32_t* cand_off; uint32_t* ncand; };
+struct K1TSelect { BeamDev prev; const uint32_t* xok; BeamDev out; uint32_t* done; uint32_t* cand_off; uint32_t* ncand; };
 bool k1t_selects(const LayerDev& L, const LayerPlan& P, const QueriesDev& X);   // one tile per parent, 32 lanes per item, k <= kTopkExtractMaxK, a combining layer
 void launch_k1t(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, const void* items, const uint32_t* n_items, float* cand, hipStream_t s,
                 const K1TSelect* sel = nullptr);
@@ -120,8 +119,8 @@ void launch_k1t(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, cons
 // combine, top-k, child re-ordering -- in one query-stationary kernel: previous beam in, next beam out.
 uint32_t k1q_regs(const LayerDev& L, uint32_t beam_in, uint32_t k, bool dense_x);   // 0: the layer / beam / k cannot (or should not) be served by K1Q
 // n consecutive dense-format layers in ONE launch (the beam stays in LDS between them); n <= 8
-void launch_k1q(const LayerDev* const* Ls, const LayerPlan* Ps, int n, const QueriesDev& X, BeamDev prev, uint32_t* out_idx, float* out_val,
-                uint32_t* out_cnt, uint32_t out_stride, hipStream_t s, float prune_wmax, uint32_t* out_xok = nullptr,
+void launch_k1q(const LayerDev* const* Ls, const LayerPlan* Ps, int n, const QueriesDev& X, BeamDev prev, BeamDev out,
+                hipStream_t s, float prune_wmax, uint32_t* out_xok = nullptr,
                 const uint32_t* qperm = nullptr /* launch slot -> query (launch_sort_queries); every XCD then takes a contiguous range of slots */);
                 // prune_wmax / out_xok: the bound-pruning guard (prune_guard_ok, xrl_device.h); out_xok[q] receives every query's flag
 size_t k2_max_k();

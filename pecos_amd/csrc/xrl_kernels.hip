@@ -707,7 +707,7 @@ void launch_k1(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, const
     a.ablate = ablate & 0xFF;
     // debug: bit 6 = per-phase cycle accounting; bits 8.. select one layer (value layer+1, 0 = every layer)
     a.phase = ((ablate & 64) && ((ablate >> 8) == 0 || (ablate >> 8) == P.layer + 1)) ? k1_phase_buffer() : nullptr;
-    a.fb_out = (n_items && P.fb_host && P.layer >= 0 && P.layer < 16) ? P.fb_host + 32 + P.layer : nullptr;
+    a.fb_out = (n_items && P.fb_host && P.layer >= 0 && P.layer < kFbLayers) ? P.fb_host + fb_items_word(P.layer) : nullptr;
     const int ppc = pp_class(P.pp);
 #define XRL_K1_PP(GG, NN, DD, LL) do { if (ppc) launch_k1_any(&k1_kernel<GG, NN, 1, DD, LL>, a, 64 / GG, lds, P.tune, s); else launch_k1_any(&k1_kernel<GG, NN, 0, DD, LL>, a, 64 / GG, lds, P.tune, s); } while (0)
 #define XRL_K1(GG, NN) do { \
@@ -936,8 +936,7 @@ size_t k2_max_k() { return (160 * 1024) / 8; }
 bool k2_wave_path(const LayerPlan& P) { return P.k <= 64 && P.cand_stride <= 64u * 32u; }
 
 void launch_k2_topk(const LayerDev& L, const LayerPlan& P, BeamDev prev, const uint32_t* cand_off,
-                    const uint32_t* ncand, const float* cand, uint32_t* out_idx, float* out_val,
-                    uint32_t* out_cnt, uint32_t out_stride, hipStream_t s, uint32_t rank_limit, uint32_t limited_cands,
+                    const uint32_t* ncand, const float* cand, BeamDev out, hipStream_t s, uint32_t rank_limit, uint32_t limited_cands,
                     uint32_t* done, const uint32_t* skip_done, const uint32_t* xok) {
     if (P.nrows == 0) return;
     K2Args a;
@@ -948,13 +947,13 @@ void launch_k2_topk(const LayerDev& L, const LayerPlan& P, BeamDev prev, const u
     a.chunk_col = L.chunk_col; a.perm_inv = L.perm_inv;
     a.p_idx = prev.idx; a.p_cnt = prev.cnt; a.p_stride = prev.stride;
     a.cand_off = cand_off; a.ncand = ncand; a.cand = cand;
-    a.out_idx = out_idx; a.out_val = out_val; a.out_cnt = out_cnt;
-    a.nrows = P.nrows; a.beam_in = P.beam_in; a.cand_stride = P.cand_stride; a.k = P.k; a.out_stride = out_stride;
+    a.out_idx = out.idx; a.out_val = out.val; a.out_cnt = out.cnt;
+    a.nrows = P.nrows; a.beam_in = P.beam_in; a.cand_stride = P.cand_stride; a.k = P.k; a.out_stride = out.stride;
     a.implicit_root = P.implicit_root;
     if (P.k == 0) fail("k2: only_topk / beam_size resolved to 0");
     // beyond the LDS kernel's reach (or forced, tests: k2_big_min_k): the segmented sort of xrl_topk_big.hip
     if (!rank_limit && !done && !skip_done && (P.k > k2_max_k() || (P.tune.k2_big_min_k > 0 && P.k >= (uint32_t)P.tune.k2_big_min_k))) {
-        launch_k2_topk_big(L, P, prev, cand_off, ncand, cand, out_idx, out_val, out_cnt, out_stride, s);
+        launch_k2_topk_big(L, P, prev, cand_off, ncand, cand, out.idx, out.val, out.cnt, out.stride, s);
         return;
     }
     if (k2_wave_path(P)) {

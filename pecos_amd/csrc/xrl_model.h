@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "xrl_common.h"
+#include "xrl_feedback.h"
 #include "xrl_io.h"
 
 namespace xrl {
@@ -173,56 +174,47 @@ struct Model {
     hipStream_t copy_stream = nullptr;      // H2D of the pipelined host-ABI path
     hipStream_t d2h_stream = nullptr;       // D2H of its results: a batch's rows travel back under the next batch's kernels
     std::vector<hipEvent_t> d2h_events;     // "batch b's kernels are queued" (grow-only, reused)
-    int host_register = 0;                  // host ABI: 1 = hipHostRegister the caller's arrays for the call and DMA from them directly (no staging copy)
-    int host_batch_mb = 12;                 // host ABI, CSR input: megabytes of (column id, value) pairs per compute batch
-    int host_pipeline = 1;                  // host ABI: cut large X into row batches whose upload overlaps the previous batch's kernels
     std::vector<hipEvent_t> events;         // cross-stream ordering (timing disabled), reused across predicts
     // host ABI, two compute lanes (xrl_abi.cpp host_compute): lane 0 uses ws_done / ws_stream above; lane 1 keeps its own "scratch in use
     // until" event between calls, and one join event orders the lanes.  Owned by the handle: ~Model destroys them on the handle's device.
     struct HostLanes { hipEvent_t done[2] = {nullptr, nullptr}; hipStream_t strm[2] = {nullptr, nullptr}; hipEvent_t join = nullptr; } host_lanes;
     std::mutex mu;                          // one predict at a time per handle
     std::unique_ptr<Workspace> ws;
-    // options
-    int k1_group = 0;                       // 0 = auto
-    int k1_wpb = 1, k1_lds_pad = 0, k1_ablate = 0;   // K1 tuning / debug knobs (xrl_set_option), per handle
-    int k1g_variant = 0;                            // 1: K1G's alternative register-tile / panel shapes (A/B, tests)
-    int64_t max_batch_rows = 0;             // 0 = auto
-    int overlap_min_rows = 0;               // split a predict of at least this many rows into two half batches on two streams so that one half's
-                                            // K0/K2 run under the other half's K1; 0 = never (measured on Amazon-670K: 25.9 vs 25.5 ms, no gain)
-    int prune = 1;                          // exact bound pruning (xrl_predict.cpp): 1 = a layer first scores the children of the best beam parent(s) only and
-                                            // skips the rest for every query whose k-th best already reaches the next parent's score; 0 = score every candidate
-    int k2_big_min_k = 0;                   // > 0: top-k sizes from this value on take the segmented-sort K2 (xrl_topk_big.hip) that otherwise serves k > 20 480 (tests)
-    int tile_rows = 1;                      // tile-format layers that carry densely held tile rows (LayerDev::wt), sparse X: 1 = launches on items in query order run K1T (xrl_k1t.hip), 2 = every launch, 0 = always the entry-list kernel K1
-    int dense_layers = 1;                   // 1 = layers that carry the dense row format run the fused query-stationary kernel K1Q (0: K0 -> K1 -> K2 everywhere)
     bool csc_route = false;                 // weight_matrix_type == CSC: every layer runs the reference's CSC arithmetic (K0 -> K1C -> K2)
-    int k1q_fuse = 3;                       // consecutive dense-format layers of <= this many candidate registers (1..3) share one K1Q launch (the beam stays in LDS); 0: one launch per layer
-    int k1g_first = 0;                      // K1G layers under bound pruning: beam parents scored in the first stage (0 = about one candidate register, 64 / children per parent)
-    int k1g_min_items = 16;                 // dense X: run a dense-format layer as the tiled SGEMM K1G once a parent serves this many queries on average (0 = never)
-    // ---- pruning feedback (xrl_predict.cpp): what the bound pruning of the PREVIOUS predicts of this handle achieved, per layer, so that a
-    // model on which the first stage settles almost nothing (scores that do not saturate, routing spread over the tree) stops paying for
-    // the staging -- the layer then scores every candidate in one pass (tile format: on tile-sorted items).  Results never depend on it.
-    static constexpr int kFbLayers = 16;
-    uint32_t* fb_host = nullptr;            // pinned, device-visible: [0, 2*kFbLayers) K1Q's sampled counters {queries seen, queries that needed the second pass}
-                                            //   per layer (copied from fb_dev by the first wavefront of the next K1Q launch), [2*kFbLayers, 3*kFbLayers) the
-                                            //   second stage's item count of tile-format layers (written by its K1 launch)
-    DevBuf fb_dev;                          // K1Q's counters (device atomics)
     DevBuf d_wd01;                          // levels 0 + 1 merged dense rows (LayerDev::wd01 of the root layer)
-    uint32_t fb_seen[kFbLayers] = {0}, fb_second[kFbLayers] = {0};   // K1Q counters at the last decision
-    uint64_t fb_tile_slots[kFbLayers] = {0};                          // second-stage slots the item count of a tile-format layer refers to
-    uint32_t fb_unstaged_calls[kFbLayers] = {0};                      // predicts in a row a layer has run unstaged (re-probed every kFbReprobe)
-    uint8_t fb_unstaged[kFbLayers] = {0};
-    uint8_t fb_probing[kFbLayers] = {0};                              // an unstaged layer was staged ONCE (the probe) and its outcome has not arrived yet: it keeps running unstaged meanwhile
-    int adaptive = 1;                       // 0: always stage (xrl_set_option "adaptive")
-    int presence = 1;                       // K1Q, sparse X: 1 = layers that run UNSTAGED (prune off, or switched by the pruning feedback) request a (feature, parent) weight
-                                            // segment only when the layer's presence word says it holds a weight; 2 = every layer that has presence words; 0 = never
-    int leaf_fuse = 1;                      // bound-pruned tile-format layers of one-tile parents: K1T derives its items and selects the first stage's top-k itself (no k0_prolongate / k2_topk launch); 2: K0 still launched; 0: three launches
-    int prune_mid = 1;                      // bound-pruned tile-format layers with >= 16 beam parents: a middle stage (slots 1..4) between the first parent and "everything else"
-    int sort_rest = 1;                      // bound-pruned tile-format layers: the second phase's compacted items are tile-sorted before K1 runs on them (0: query order)
-    int sort_rest_min = 32768;              // ... only when the previous predicts' later stages held at least this many items (pruning feedback's count; 0 = always)
-    int qsort = 1;                          // K1Q, sparse X: the last layer of a run of dense-format layers runs on queries SORTED by the best parent of their beam,
-                                            // every XCD on a contiguous range of them (xrl_predict.cpp), when it has >= qsort_min_parents parents and the batch >= qsort_min_rows rows
-    int qsort_min_parents = 64, qsort_min_rows = 131072;
-    int sort_min_tiles = 0;                 // tile-sort a layer's items once it has this many tiles (0 = never; measured: cuts HBM fetch 15x at the leaf but K1 is issue-bound, not HBM-bound, so it does not pay yet)
+    PruneFeedback fb;                       // what the bound pruning of this handle's previous predicts achieved (xrl_feedback.h)
+    // Everything xrl_set_option sets by name (include/xrl_abi.h lists the keys; xrl_abi.cpp kIntOptions maps them to these members).  A replica
+    // takes the whole struct in one assignment.
+    struct Options {
+        int k1_group = 0;                       // 0 = auto
+        int k1_wpb = 1, k1_lds_pad = 0, k1_ablate = 0;   // K1 tuning / debug knobs (xrl_set_option), per handle
+        int k1g_variant = 0;                            // 1: K1G's alternative register-tile / panel shapes (A/B, tests)
+        int64_t max_batch_rows = 0;             // 0 = auto
+        int overlap_min_rows = 0;               // split a predict of at least this many rows into two half batches on two streams so that one half's
+                                                // K0/K2 run under the other half's K1; 0 = never (measured on Amazon-670K: 25.9 vs 25.5 ms, no gain)
+        int prune = 1;                          // exact bound pruning (xrl_predict.cpp): 1 = a layer first scores the children of the best beam parent(s) only and
+                                                // skips the rest for every query whose k-th best already reaches the next parent's score; 0 = score every candidate
+        int k2_big_min_k = 0;                   // > 0: top-k sizes from this value on take the segmented-sort K2 (xrl_topk_big.hip) that otherwise serves k > 20 480 (tests)
+        int tile_rows = 1;                      // tile-format layers that carry densely held tile rows (LayerDev::wt), sparse X: 1 = launches on items in query order run K1T (xrl_k1t.hip), 2 = every launch, 0 = always the entry-list kernel K1
+        int dense_layers = 1;                   // 1 = layers that carry the dense row format run the fused query-stationary kernel K1Q (0: K0 -> K1 -> K2 everywhere)
+        int k1q_fuse = 3;                       // consecutive dense-format layers of <= this many candidate registers (1..3) share one K1Q launch (the beam stays in LDS); 0: one launch per layer
+        int k1g_first = 0;                      // K1G layers under bound pruning: beam parents scored in the first stage (0 = about one candidate register, 64 / children per parent)
+        int k1g_min_items = 16;                 // dense X: run a dense-format layer as the tiled SGEMM K1G once a parent serves this many queries on average (0 = never)
+        int adaptive = 1;                       // 0: always stage (xrl_set_option "adaptive")
+        int presence = 1;                       // K1Q, sparse X: 1 = layers that run UNSTAGED (prune off, or switched by the pruning feedback) request a (feature, parent) weight
+                                                // segment only when the layer's presence word says it holds a weight; 2 = every layer that has presence words; 0 = never
+        int leaf_fuse = 1;                      // bound-pruned tile-format layers of one-tile parents: K1T derives its items and selects the first stage's top-k itself (no k0_prolongate / k2_topk launch); 2: K0 still launched; 0: three launches
+        int prune_mid = 1;                      // bound-pruned tile-format layers with >= 16 beam parents: a middle stage (slots 1..4) between the first parent and "everything else"
+        int sort_rest = 1;                      // bound-pruned tile-format layers: the second phase's compacted items are tile-sorted before K1 runs on them (0: query order)
+        int sort_rest_min = 32768;              // ... only when the previous predicts' later stages held at least this many items (pruning feedback's count; 0 = always)
+        int qsort = 1;                          // K1Q, sparse X: the last layer of a run of dense-format layers runs on queries SORTED by the best parent of their beam,
+                                                // every XCD on a contiguous range of them (xrl_predict.cpp), when it has >= qsort_min_parents parents and the batch >= qsort_min_rows rows
+        int qsort_min_parents = 64, qsort_min_rows = 131072;
+        int sort_min_tiles = 0;                 // tile-sort a layer's items once it has this many tiles (0 = never; measured: cuts HBM fetch 15x at the leaf but K1 is issue-bound, not HBM-bound, so it does not pay yet)
+        int host_register = 0;                  // host ABI: 1 = hipHostRegister the caller's arrays for the call and DMA from them directly (no staging copy)
+        int host_batch_mb = 12;                 // host ABI, CSR input: megabytes of (column id, value) pairs per compute batch
+        int host_pipeline = 1;                  // host ABI: cut large X into row batches whose upload overlaps the previous batch's kernels
+    } opt;
     // multi-GPU behind the drop-in entry points (xrl_set_option "devices"): further copies of the compiled model on other devices; the
     // host-ABI predict shards the rows over this handle's device and the replicas' (xrl_abi.cpp predict_host)
     std::string src_path; int src_kind = -1;   // where the model came from: 0 = npz folder, 1 = mmap folder, -1 = arrays (no replicas)

@@ -3,6 +3,10 @@
 //
 // Reference driver being restated: HierarchicalMLModel::predict (inference.hpp:2446-2488) calling
 // MLModel::predict_internal (:2029-2080) per layer.
+//
+// predict_device is an outline: resolve_layers (k / beam / candidate stride per layer) -> PruneFeedback::begin_predict -> reserve_scratch
+// (walks the routes once) -> per row batch and layer: route_layer DECIDES (a Route, nothing launched), one of launch_csc_layer /
+// launch_k1g_layer / launch_k1q_group / launch_tile_layer LAUNCHES what it says (launch_batch).  A new way to run a layer is a Route field + a branch there.
 #include "xrl_predict.h"
 
 #include <algorithm>
@@ -18,473 +22,495 @@ size_t profile_slot(Model& m, const char* name, uint32_t layer) {
     m.profile.push_back(ProfileSlot{name, layer});
     return m.profile.size() - 1;
 }
-}  // namespace
 
 // dense-X SGEMM layers, bound pruning: beam slots whose children fill about one candidate register (64) are scored first -- never all of
 // them (the second stage must keep at least one slot)
-static uint32_t k1g_first_slots(const Layer& L, uint32_t beam_in, int forced = 0) {
+uint32_t k1g_first_slots(const Layer& L, uint32_t beam_in, int forced = 0) {
     if (forced > 0) return (uint32_t)std::max<int64_t>(1, std::min<int64_t>(beam_in > 1 ? (int64_t)beam_in - 1 : 1, forced));
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(beam_in > 1 ? beam_in - 1 : 1, 64 / std::max<uint64_t>(1, L.cand_bound(1))));
 }
 
-uint32_t effective_topk(const Model& m, uint32_t only_topk) {
-    return only_topk ? only_topk : m.layers.back()->only_topk;   // inference.hpp:2055
-}
+struct LayerShape { uint32_t k, beam_in, cand_stride; PostProc pp; };   // resolve_layers: what a layer keeps, takes in and may evaluate per query
 
-void predict_device(Model& m, const QueriesDev& X, const PredictOpts& o, uint32_t* d_out_idx, float* d_out_val,
-                    uint32_t* d_out_cnt, uint32_t out_stride, hipStream_t stream, bool sync, uint32_t row_begin, uint32_t row_count) {
-    const size_t T = m.layers.size();
-    // rows [row_begin, row_end) of X (results land at the same rows of the output buffers); default: all rows
-    if (row_begin > X.rows) fail("predict: row range outside X");
-    const uint64_t row_end = std::min<uint64_t>(X.rows, (uint64_t)row_begin + row_count);
-    const uint64_t n_rows = row_end - row_begin;
-    if (!m.ws) m.ws = std::make_unique<Workspace>();
-    Workspace& ws = *m.ws;
-    if (!stream) stream = m.stream;
-    // the scratch buffers are shared by every predict of the handle: an asynchronous predict still running on another stream must finish first
-    if (m.ws_done && m.ws_stream != stream) XRL_HIP(hipStreamWaitEvent(stream, m.ws_done, 0));
-    static const bool step_marker = [] { const char* e = std::getenv("XRL_STEP_MARKER"); return e && e[0] == '1'; }();
-    if (step_marker && !o.stats_out) launch_step_marker(stream);
+// Every decision about how layers [l, last] run on a batch of a given size (route_layer); the launch functions read it and decide nothing.
+enum RouteKind { ROUTE_CSC, ROUTE_K1G, ROUTE_K1Q, ROUTE_TILE };
+struct Route {
+    RouteKind kind;
+    size_t last;             // K1Q: last layer of the group that shares the launch (every other kind: the layer itself) ...
+    bool sorted_last;        // ... and that layer runs on its own, on queries sorted by their best beam parent (option qsort)
+    int mode;                // items K1 walks: 0 = natural order, 1 = tile-sorted, 3 = K1G's tiled SGEMM over tile-sorted items (dense X)
+    int group;               // tile format: lanes per item
+    bool pruned;             // K1G, tile format: exact bound pruning in stages of beam slots
+    uint32_t J;              // ... slots [0, J) are the first stage (K1G unpruned: the whole beam)
+    uint32_t stage_end[3]; int n_stage;   // tile format: stage s scores the slots [stage_end[s-1], stage_end[s])
+    bool fuse, fuse_k0;      // tile format (option leaf_fuse): K1T selects the first stage's top-k itself / derives its items too
+    bool sorts_rest;         // tile format (option sort_rest): the later stages run on tile-sorted items, unless the feedback's item count says too few
+};
 
+// What the launch functions share: the predict's constants and the row batch in flight (begin_batch).
+struct Batch {
+    Model& m; const Model::Options& opt; const QueriesDev& X; const PredictOpts& o; const std::vector<LayerShape>& shape;
+    BeamDev result{}; uint32_t beam_stride = 1;   // the caller's output buffers (row 0); stride of the lanes' ping-pong beams
+    bool has_init = false, csc = false, stats = false; double* stats_dev = nullptr;
+    uint64_t nb = 1; int lanes = 1;      // rows per batch; batches alternate between this many lanes
+    PruneFeedback::Plan fb{};
+    float prune_wmax = 0.0f;             // the bound-pruning guard (prune_guard_ok, xrl_device.h) prices a query's largest |x| with the model's largest |weight| x max(1, |bias|)
+    hipEvent_t k1_done = nullptr; size_t ev_next = 0;   // the most recent K1 launch (either lane); how many of m.events this predict has used
+    // ---- the row batch in flight: rows [row0, row0 + nrows) on stream S, typed views of its lane's scratch
+    uint64_t row0 = 0; uint32_t nrows = 0; hipStream_t S = nullptr;
+    bool x_ok_done = false;              // x_ok[q] = the pruning guard of query q (also "all x finite" for K1G's fast loop) is written: by launch_xguard
+                                         // or, for free, by a K1Q launch that runs before the first layer that needs it
+    BeamDev beam[2]{};
+    uint32_t *cand_off, *ncand, *sort_hist, *sort_start, *blk_start, *x_ok, *qperm, *qsort_hist, *qsort_start, *prune_done, *prune_cnt;
+    float* cand; void *items, *items_sorted;
+
+    void begin_batch(const LaneWs& lw, hipStream_t s, uint64_t r0, uint32_t n) {
+        auto u32 = [](const DevBuf& d) { return d.as<uint32_t>(); };
+        row0 = r0; nrows = n; S = s; x_ok_done = false;
+        for (int i = 0; i < 2; ++i) beam[i] = BeamDev{u32(lw.beam_idx[i]), lw.beam_val[i].as<float>(), u32(lw.beam_cnt[i]), beam_stride};
+        cand_off = u32(lw.cand_off); ncand = u32(lw.ncand); cand = lw.cand.as<float>(); items = lw.items.p; items_sorted = lw.items_sorted.p;
+        sort_hist = u32(lw.sort_hist); sort_start = u32(lw.sort_start); blk_start = u32(lw.blk_start); x_ok = u32(lw.x_ok);
+        qperm = u32(lw.qperm); qsort_hist = u32(lw.qsort_hist); qsort_start = u32(lw.qsort_start); prune_done = u32(lw.prune_done); prune_cnt = u32(lw.prune_cnt);
+    }
+    bool unstaged(size_t l) const { return l < (size_t)kFbLayers && fb.unstaged[l]; }   // pruning feedback: the layer scores everything in one pass this time
+    // (route_layer reads the plan's shape and policy fields only: it is asked about batch sizes, not about a batch)
+    LayerPlan make_plan(size_t l) const {
+        LayerPlan P{};
+        P.layer = (int)l; P.row0 = (uint32_t)row0; P.nrows = nrows;
+        P.beam_in = shape[l].beam_in; P.k = shape[l].k; P.cand_stride = shape[l].cand_stride; P.pp = shape[l].pp;
+        P.tune = K1Tune{opt.k1_wpb, opt.k1_lds_pad, opt.k1_ablate, opt.k1g_variant, opt.presence, opt.tile_rows, opt.k2_big_min_k};
+        P.first_layer = (l == 0 && (!has_init || o.no_prev_pred)) ? 1 : 0; P.implicit_root = (l == 0 && !has_init) ? 1 : 0;   // no_prev_pred
+        P.bias_first = (m.weight_matrix_type == 1 && !X.dense) ? 1 : 0; P.prune = (opt.prune && !unstaged(l)) ? 1 : 0;
+        if (opt.prune && opt.adaptive && !stats && l < (size_t)kFbLayers) { P.fb_host = m.fb.host; P.fb_dev = m.fb.dev.as<uint32_t>(); }
+        return P;
+    }
+    BeamDev beam_prev(size_t l) const {   // what layer l reads: the explicit initial beam, the implicit root (all null), or the lane's ping-pong buffer
+        if (l > 0 || !has_init) return l > 0 ? beam[(l - 1) & 1] : BeamDev{};
+        const BeamDev& i = *o.initial;
+        return BeamDev{i.idx + row0 * i.stride, i.val + row0 * i.stride, i.cnt + row0, i.stride};
+    }
+    BeamDev beam_out(size_t l) const {    // what layer l writes: the other ping-pong buffer, or (last layer) the batch's rows of the caller's buffers
+        if (l + 1 < shape.size()) return beam[l & 1];
+        return BeamDev{result.idx + row0 * result.stride, result.val + row0 * result.stride, result.cnt + row0, result.stride};
+    }
+    hipEvent_t next_event() {
+        if (ev_next == m.events.size()) { hipEvent_t e; XRL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); m.events.push_back(e); }
+        return m.events[ev_next++];
+    }
+    void chain(hipStream_t from, hipStream_t to) { hipEvent_t e = next_event(); XRL_HIP(hipEventRecord(e, from)); XRL_HIP(hipStreamWaitEvent(to, e, 0)); }   // `to` continues after what `from` holds now
+    static bool debug_sync() { static const bool on = [] { const char* e = std::getenv("XRL_DEBUG_SYNC"); return e && e[0] == '1'; }(); return on; }
+    bool named() const { return m.profiling || debug_sync(); }   // somebody reads the launch names (K1Q composes its own only then)
+    template <class F> void timed(const char* name, uint32_t layer, F&& fn) {
+        if (debug_sync()) {   // XRL_DEBUG_SYNC=1: every launch group is announced and synchronised on its own, a device fault names the kernel family and the layer
+            std::fprintf(stderr, "[xrl debug] %s layer %u rows %llu+%u\n", name, layer, (unsigned long long)row0, nrows); std::fflush(stderr);
+            fn(); const hipError_t e = hipStreamSynchronize(S);
+            if (e != hipSuccess) fail(std::string("device fault in ") + name + " (layer " + std::to_string(layer) + ", rows " + std::to_string(row0) + "+" + std::to_string(nrows) + "): " + hipGetErrorString(e));
+            return;
+        }
+        if (!m.profiling) { fn(); return; }
+        PendingEvent ev; ev.slot = profile_slot(m, name, layer);
+        XRL_HIP(hipEventCreate(&ev.a)); XRL_HIP(hipEventCreate(&ev.b));
+        XRL_HIP(hipEventRecord(ev.a, S));
+        fn();
+        XRL_HIP(hipEventRecord(ev.b, S));
+        m.pending.push_back(ev);
+    }
+    void need_x_ok() {   // once per row batch
+        if (!x_ok_done) timed("xguard", 0, [&] { launch_xguard(X, (uint32_t)row0, nrows, prune_wmax, x_ok, S); });
+        x_ok_done = true;
+    }
+};
+
+// ---- resolve per-layer k / post-processor (inference.hpp:2471, 2055-2058)
+std::vector<LayerShape> resolve_layers(const Model& m, const QueriesDev& X, const PredictOpts& o) {
     // MLModel::predict_internal's shape checks live in Python for the reference
     // (xmc/base.py:1603-1607); here a mismatch is a loud error instead of UB.
     if (!X.dense && X.cols != m.nr_features && X.cols != m.layers[0]->w_rows)
         fail("X.shape[1] (" + std::to_string(X.cols) + ") != nr_features (" + std::to_string(m.nr_features) + ")");
     if (X.dense && X.cols < m.nr_features)
         fail("dense X has fewer columns (" + std::to_string(X.cols) + ") than nr_features (" + std::to_string(m.nr_features) + ")");
-
-    // ---- resolve per-layer k / post-processor (inference.hpp:2471, 2055-2058)
-    std::vector<uint32_t> k(T), beam_in(T), cstride(T);
-    std::vector<PostProc> pp(T);
+    const size_t T = m.layers.size();
     const bool has_init = o.initial != nullptr;
-    const bool csc = o.csc_route || m.csc_route;
+    std::vector<LayerShape> shape(T);
     for (size_t l = 0; l < T; ++l) {
-        const Layer& L = *m.layers[l];
+        const Layer& L = *m.layers[l]; LayerShape& s = shape[l];
         const uint32_t ov = (l == T - 1) ? o.only_topk : o.beam_size;
-        k[l] = ov ? ov : L.only_topk;
-        if (k[l] == 0) fail("layer " + std::to_string(l) + ": only_topk resolved to 0");
-        pp[l] = o.post_processor ? parse_post_processor(o.post_processor) : L.pp;
-        uint64_t bin = (l == 0) ? (has_init ? std::max<uint32_t>(1, o.initial_max) : 1)
-                                : std::min<uint64_t>(k[l - 1], cstride[l - 1]);
+        s.k = ov ? ov : L.only_topk;
+        if (s.k == 0) fail("layer " + std::to_string(l) + ": only_topk resolved to 0");
+        s.pp = o.post_processor ? parse_post_processor(o.post_processor) : L.pp;
+        uint64_t bin = (l == 0) ? (has_init ? std::max<uint32_t>(1, o.initial_max) : 1) : std::min<uint64_t>(shape[l - 1].k, shape[l - 1].cand_stride);
         if (!(l == 0 && has_init)) bin = std::min<uint64_t>(bin, L.c_cols ? L.c_cols : 1);   // explicit codes may list a parent more than once
-        beam_in[l] = (uint32_t)std::max<uint64_t>(1, bin);
-        const uint64_t cb = std::max<uint64_t>(1, (l == 0 && has_init && o.initial_cand_bound) ? o.initial_cand_bound : L.cand_bound(beam_in[l]));
+        s.beam_in = (uint32_t)std::max<uint64_t>(1, bin);
+        const uint64_t cb = std::max<uint64_t>(1, (l == 0 && has_init && o.initial_cand_bound) ? o.initial_cand_bound : L.cand_bound(s.beam_in));
         if (cb > 0x7FFFFFFFull) fail("candidate row too long; lower beam_size");
-        cstride[l] = (uint32_t)cb;
+        s.cand_stride = (uint32_t)cb;
     }
-    const uint32_t k_last = k[T - 1];
-    if (k_last > out_stride) fail("out_stride smaller than the effective only_topk");
-    uint32_t beam_stride = 1;
-    for (size_t l = 0; l + 1 < T; ++l) beam_stride = std::max(beam_stride, k[l]);
-    uint32_t bin_max = 1, cs_max = 1;
-    for (size_t l = 0; l < T; ++l) { bin_max = std::max(bin_max, beam_in[l]); cs_max = std::max(cs_max, cstride[l]); }
+    return shape;
+}
 
-    // ---- batch rows so that the candidate buffer stays bounded (default 6 GiB of 288)
+// ---- batch rows so that the candidate buffer stays bounded (default 6 GiB of 288)
+void size_batches(Batch& b, uint64_t n_rows) {
+    uint32_t cs_max = 1;
+    for (const LayerShape& s : b.shape) cs_max = std::max(cs_max, s.cand_stride);
     const uint64_t cand_budget = 6ull << 30;
-    uint64_t nb = std::max<uint64_t>(1, cand_budget / ((uint64_t)cs_max * 4));
-    nb = std::min<uint64_t>(nb, 1u << 22);
-    if (m.max_batch_rows > 0) nb = std::min<uint64_t>(nb, (uint64_t)m.max_batch_rows);
-    nb = std::min<uint64_t>(nb, std::max<uint64_t>(1, std::max<uint64_t>(n_rows, o.reserve_rows)));   // reserve_rows: size the scratch for the caller's largest batch up front
+    uint64_t nb = std::min<uint64_t>(std::max<uint64_t>(1, cand_budget / ((uint64_t)cs_max * 4)), 1u << 22);
+    if (b.opt.max_batch_rows > 0) nb = std::min<uint64_t>(nb, (uint64_t)b.opt.max_batch_rows);
+    nb = std::min<uint64_t>(nb, std::max<uint64_t>(1, std::max<uint64_t>(n_rows, b.o.reserve_rows)));   // reserve_rows: size the scratch for the caller's largest batch up front
     // two lanes: the row batches alternate between the caller's stream and an auxiliary one.  K1 launches are chained
     // across the lanes (one K1 at a time owns the memory system); a lane's K0 / sort / K2 run under the other lane's K1.
-    const int lanes = (m.overlap_min_rows > 0 && !o.stats_out && !m.profiling && n_rows >= (uint64_t)m.overlap_min_rows) ? 2 : 1;
-    if (lanes == 2) nb = std::min<uint64_t>(nb, (n_rows + 1) / 2);
+    b.lanes = (b.opt.overlap_min_rows > 0 && !b.stats && !b.m.profiling && n_rows >= (uint64_t)b.opt.overlap_min_rows) ? 2 : 1;
+    b.nb = b.lanes == 2 ? std::min<uint64_t>(nb, (n_rows + 1) / 2) : nb;
+}
 
-    for (int ln = 0; ln < lanes; ++ln) {
-        LaneWs& lw = ws.lane[ln];
-        for (int i = 0; i < 2; ++i) {
-            lw.beam_idx[i].reserve(nb * beam_stride * 4);
-            lw.beam_val[i].reserve(nb * beam_stride * 4);
-            lw.beam_cnt[i].reserve(nb * 4);
-        }
-    }
-    uint64_t slots_max = 1;
-    for (size_t l = 0; l < T; ++l) slots_max = std::max<uint64_t>(slots_max, nb * beam_in[l] * m.layers[l]->max_tiles_per_parent);
-    for (int ln = 0; ln < lanes; ++ln) ws.lane[ln].items.reserve(slots_max * k0_item_bytes());
-    // per layer: 0 = K1 on the items in natural order, 1 = K1 on tile-sorted items, 3 = K1G (dense X, tiled SGEMM over tile-sorted items)
-    auto layer_mode = [&](size_t l, uint64_t rows) -> int {
-        const Layer& L = *m.layers[l];
-        if (L.n_tiles > sort_max_tiles()) return 0;
-        const uint64_t slots = rows * beam_in[l] * L.max_tiles_per_parent;
-        // 3 = K1G: dense queries against a dense-format layer as a tiled SGEMM over tile-sorted items
-        if (X.dense && m.dense_layers && m.k1g_min_items > 0 && !csc && k1g_cols(L.dev) != 0 && k[l] <= k2_max_k() &&
-            slots / std::max<uint32_t>(1, L.n_tiles) >= (uint64_t)m.k1g_min_items) return 3;
-        if (m.sort_min_tiles > 0 && L.n_tiles >= (uint32_t)m.sort_min_tiles) return 1;
-        return 0;
-    };
+// per layer: 0 = K1 on the items in natural order, 1 = K1 on tile-sorted items, 3 = K1G (dense X, tiled SGEMM over tile-sorted items)
+int tile_mode(const Batch& b, size_t l, uint64_t rows) {
+    const Layer& L = *b.m.layers[l];
+    if (L.n_tiles > sort_max_tiles()) return 0;
+    const uint64_t slots = rows * b.shape[l].beam_in * L.max_tiles_per_parent;
+    // 3 = K1G: dense queries against a dense-format layer as a tiled SGEMM over tile-sorted items
+    if (b.X.dense && b.opt.dense_layers && b.opt.k1g_min_items > 0 && !b.csc && k1g_cols(L.dev) != 0 && b.shape[l].k <= k2_max_k() &&
+        slots / std::max<uint32_t>(1, L.n_tiles) >= (uint64_t)b.opt.k1g_min_items) return 3;
+    return (b.opt.sort_min_tiles > 0 && L.n_tiles >= (uint32_t)b.opt.sort_min_tiles) ? 1 : 0;
+}
+
+// How layer l (and, for K1Q, the layers that share its launch) runs on a batch of `nrows` rows.  Launches nothing, reads no device-written word.
+Route route_layer(const Batch& b, size_t l, uint64_t nrows) {
+    const Model& m = b.m; const Model::Options& opt = b.opt; const Layer& L = *m.layers[l];
+    const uint32_t beam_in = b.shape[l].beam_in;
+    Route r{}; r.last = l; r.J = 1; r.mode = tile_mode(b, l, nrows);
     // the second phase of a bound-pruned tile-format layer runs on TILE-SORTED items (option sort_rest): what is left after the first phase
     // is, on a model that does not let the bound stop much, most of the layer's work, and in query order every (query, tile) item finds its
     // tile's lookup words and entries cold (Amazon-670K-hard: 7 % L2 hits, the fabric's request ceiling); tile-sorted, the items of a tile
     // run back to back on one XCD and share them
-    auto sorts_rest = [&](size_t l) { return m.sort_rest != 0 && !o.stats_out && m.layers[l]->n_tiles <= sort_max_tiles() && m.layers[l]->n_tiles >= 64u; };
-    {
-        size_t hist_max = 0; uint32_t tiles_max = 0; bool any = false;
-        for (size_t l = 0; l < T; ++l) {
-            const Layer& L = *m.layers[l];
-            if (layer_mode(l, nb) != 0 || (n_rows % nb && layer_mode(l, n_rows % nb) != 0) || (m.prune && sorts_rest(l))) {
-                any = true;
-                hist_max = std::max(hist_max, sort_hist_bytes(nb * beam_in[l] * L.max_tiles_per_parent, L.n_tiles));
-                tiles_max = std::max(tiles_max, L.n_tiles);
-            }
+    r.sorts_rest = opt.sort_rest != 0 && !b.stats && L.n_tiles <= sort_max_tiles() && L.n_tiles >= 64u;
+    // CSC route (weight_matrix_type CSC, single-layer API): one (query, child) dot product per candidate, bias first
+    if (b.csc) { r.kind = ROUTE_CSC; return r; }
+    const LayerPlan P = b.make_plan(l);
+    // exact bound pruning needs a combiner (a child's score is then <= its parent's) and the register top-k kernel
+    const bool boundable = !P.implicit_root && !P.first_layer && P.pp.kind != PP_NOOP && beam_in > 1 && k2_wave_path(P);
+    if (!b.stats && r.mode == 3) {
+        // ---- exact bound pruning (see the tile-format route below): the GEMM over the children of the J best beam parents first,
+        //      then a second, tile-sorted GEMM over the remaining slots of the queries whose top-k is not final yet.  J covers about
+        //      one candidate register (64 candidates), like K1Q's first stage.
+        r.kind = ROUTE_K1G; r.pruned = opt.prune && boundable;
+        r.J = r.pruned ? k1g_first_slots(L, beam_in, opt.k1g_first) : beam_in;
+        return r;
+    }
+    // layers held in the dense row format: the whole layer is one query-stationary kernel (beam in, beam out)
+    const bool dense_x = b.X.dense != 0 || opt.dense_layers >= 2;
+    auto regs = [&](size_t ll) { return k1q_regs(m.layers[ll]->dev, b.shape[ll].beam_in, b.shape[ll].k, dense_x); };
+    auto runs_k1q = [&](size_t ll) { return opt.dense_layers && !b.stats && tile_mode(b, ll, nrows) != 3 && regs(ll) != 0; };
+    if (runs_k1q(l)) {
+        r.kind = ROUTE_K1Q;
+        // consecutive dense-format layers run in ONE launch: the wavefront that owns a query carries its beam through them in LDS
+        // (only narrow layers share a launch: a fused kernel is compiled for -- and holds the registers of -- its widest layer)
+        auto narrow = [&](size_t ll) { return regs(ll) <= (uint32_t)std::min(3, opt.k1q_fuse); };
+        while (opt.k1q_fuse && narrow(l) && r.last + 1 < b.shape.size() && r.last + 1 - l < 8 && runs_k1q(r.last + 1) && narrow(r.last + 1)) ++r.last;
+        // SORTED launch of the group's last layer (option qsort): a layer of many parents whose matrix is far larger than the L2s is
+        // request-bound -- one 64-byte fabric request per (feature, beam parent) and query -- and the queries that share beam
+        // parents are scattered over the batch.  The layers before it run as usual; the queries are then counting-sorted by the best
+        // parent of the beam they produced and the last layer runs in that order, every XCD on a contiguous range of it.
+        const uint32_t nk = m.layers[r.last]->dev.n_parents;
+        r.sorted_last = opt.qsort != 0 && !b.X.dense && r.last > 0 && nrows >= (uint64_t)std::max(1, opt.qsort_min_rows) &&
+                        nk >= (uint32_t)std::max(2, opt.qsort_min_parents) && nk <= qsort_max_keys();
+        return r;
+    }
+    r.kind = ROUTE_TILE; r.group = opt.k1_group > 0 ? opt.k1_group : k1_auto_group(L.dev, L, b.X.dense);
+    if (b.unstaged(l) && r.mode == 0 && r.sorts_rest) r.mode = 1;    // pruning feedback: everything in one pass, on tile-sorted items
+    // ---- exact bound pruning, tile format: score the children of the best beam parent first (K0 -> K1 -> K2 on one slot), then
+    //      only the remaining slots of the queries whose top-k is not final yet (see K2Args).
+    r.pruned = opt.prune && !b.unstaged(l) && boundable;
+    if (b.stats) {
+        // the stats pass walks the tile format whatever kernel the timed pass runs: stage it the way THAT kernel stages the layer, so
+        // that the work it counts is the work the timed kernels evaluate (K1G: J parents first; K1Q: the parents of candidate
+        // register 0 first, nothing skipped when the whole beam fits one register)
+        if (r.mode == 3) r.J = k1g_first_slots(L, beam_in, opt.k1g_first);      // (the SAME staging the timed K1G path uses: ADVICE r3)
+        else if (opt.dense_layers && regs(l) != 0) {
+            if (regs(l) <= 1) r.pruned = false;
+            else r.J = std::max<uint32_t>(1, (64u >> L.dev.d_gp_log2) / std::max<uint32_t>(1, L.dev.d_max_tiles));
         }
-        if (any) for (int ln = 0; ln < lanes; ++ln) { LaneWs& lw = ws.lane[ln]; lw.items_sorted.reserve(slots_max * k0_item_bytes()); lw.sort_hist.reserve(hist_max); lw.sort_start.reserve(((size_t)tiles_max + 1) * 4); lw.blk_start.reserve(((size_t)tiles_max + 1) * 4); }
+        if (r.J >= beam_in) r.pruned = false;
+    } else if (r.mode != 0) r.pruned = false;
+    if (!r.pruned) return r;
+    // stages of beam slots: [0, J) first, then -- wide beams only (>= 16 parents: Wiki10-31K's 20) -- a MIDDLE stage [J, J2) before
+    // "everything else": with 20 parents of ~60 children and k = 20 the first parent alone rarely settles the top-k, the first
+    // five usually do, and the last stage then sees few queries.
+    r.stage_end[r.n_stage++] = r.J;
+    if (opt.prune_mid != 0 && beam_in >= 16u && !b.stats) r.stage_end[r.n_stage++] = std::min<uint32_t>(beam_in - 1u, r.J + 4u);
+    r.stage_end[r.n_stage++] = beam_in;
+    // option leaf_fuse: with one tile per parent, K1T's lanes end up holding every candidate of slot 0 -- its epilogue selects the top-k
+    // and sets the done flags itself (xrl_k1t.hip, SEL): no k2_topk launch, and no candidate row stored for a query that is done.
+    r.fuse = opt.leaf_fuse != 0 && r.J == 1 && !b.stats && k1t_selects(L.dev, P, b.X);
+    // ... and (beams of up to 32 parents) derives its items from the beam: K0 is not launched either.  leaf_fuse = 2 keeps K0 (A/B runs).
+    r.fuse_k0 = r.fuse && opt.leaf_fuse != 2 && beam_in <= 32u;
+    return r;
+}
+
+// Everything the routes of this predict's batch sizes (nb rows, and the remainder) touch, reserved once, before the first launch.
+void reserve_scratch(const Batch& b, Workspace& ws, uint64_t n_rows) {
+    const Model& m = b.m; const size_t T = b.shape.size(); const uint64_t nb = b.nb;
+    uint32_t bin_max = 1, cs_max = 1; uint64_t slots_max = 1;
+    for (size_t l = 0; l < T; ++l) {
+        bin_max = std::max(bin_max, b.shape[l].beam_in); cs_max = std::max(cs_max, b.shape[l].cand_stride); slots_max = std::max<uint64_t>(slots_max, nb * b.shape[l].beam_in * m.layers[l]->max_tiles_per_parent);
     }
-    for (int ln = 0; ln < lanes; ++ln) { LaneWs& lw = ws.lane[ln]; lw.cand_off.reserve(nb * bin_max * 4); lw.ncand.reserve(nb * 4); lw.cand.reserve(nb * (uint64_t)cs_max * 4); }
-    if (o.stats_out) {
-        ws.stats.reserve(T * kStatsPerLayer * sizeof(double));
-        XRL_HIP(hipMemsetAsync(ws.stats.p, 0, T * kStatsPerLayer * sizeof(double), stream));
+    // bytes per lane of the buffers only some routes use (0: none does, nothing is allocated)
+    size_t sorted = 0, hist = 0, starts = 0, x_ok = 0, done = 0, cnt = 0, qperm = 0, qhist = 0, qstarts = 0;
+    for (const uint64_t rows : {nb, n_rows % nb}) {
+        // (every layer is asked, also the inner ones of a K1Q group: they answer like the group does)
+        for (size_t l = 0; l < T && rows; ++l) {
+            const Route r = route_layer(b, l, rows); const Layer& L = *m.layers[l];
+            const bool staged_tile = r.kind == ROUTE_TILE && r.pruned;
+            if (r.mode != 0 || (b.opt.prune && r.sorts_rest)) { hist = std::max(hist, sort_hist_bytes(nb * b.shape[l].beam_in * L.max_tiles_per_parent, L.n_tiles)); starts = std::max(starts, ((size_t)L.n_tiles + 1) * 4); }
+            if (starts || staged_tile) sorted = slots_max * k0_item_bytes();   // (the compacted items of the later stages go to items_sorted, sorted or not)
+            if (staged_tile || (r.kind == ROUTE_K1G && r.pruned)) { done = (size_t)nb * 4; cnt = 256; }
+            // (a later layer of a batch that is NOT served by K1Q decides its pruning in K2 and needs the guard flags: the K1Q launch writes them)
+            if (r.kind == ROUTE_K1G || staged_tile || (r.kind == ROUTE_K1Q && b.opt.prune && r.last + 1 < T)) x_ok = (size_t)nb * 4;
+            const uint32_t nk = m.layers[r.last]->dev.n_parents;
+            if (r.kind == ROUTE_K1Q && r.sorted_last) { qperm = (size_t)nb * 4; qhist = std::max(qhist, qsort_hist_bytes((uint32_t)nb, nk)); qstarts = std::max(qstarts, ((size_t)nk + 1) * 4); }
+        }
     }
+    for (int ln = 0; ln < b.lanes; ++ln) {
+        LaneWs& lw = ws.lane[ln];
+        for (int i = 0; i < 2; ++i) { lw.beam_idx[i].reserve(nb * b.beam_stride * 4); lw.beam_val[i].reserve(nb * b.beam_stride * 4); lw.beam_cnt[i].reserve(nb * 4); }
+        lw.items.reserve(slots_max * k0_item_bytes());
+        lw.cand_off.reserve(nb * bin_max * 4); lw.ncand.reserve(nb * 4); lw.cand.reserve(nb * (uint64_t)cs_max * 4);
+        lw.items_sorted.reserve(sorted); lw.sort_hist.reserve(hist); lw.sort_start.reserve(starts); lw.blk_start.reserve(starts);
+        lw.x_ok.reserve(x_ok); lw.prune_done.reserve(done); lw.prune_cnt.reserve(cnt);
+        lw.qperm.reserve(qperm); lw.qsort_hist.reserve(qhist); lw.qsort_start.reserve(qstarts);
+    }
+    if (b.stats) m.ws->stats.reserve(T * kStatsPerLayer * sizeof(double));
+}
+
+void launch_csc_layer(Batch& b, size_t l) {
+    Layer& L = *b.m.layers[l]; const LayerPlan P = b.make_plan(l); const BeamDev prev = b.beam_prev(l);
+    ensure_device_csc(L);
+    b.timed("k0_prolongate", l, [&] { launch_k0_prolongate(L.dev, P, b.X, prev, b.cand_off, b.ncand, b.items, b.S); });
+    b.timed("k1c_csc", l, [&] { launch_k1c_csc(L.dev, L.d_csc_ptr.as<uint64_t>(), L.d_csc_idx.as<uint32_t>(), L.d_csc_val.as<float>(), P, b.X, prev, b.cand_off, b.ncand, b.cand, b.S); });
+    b.timed("k2_topk", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, b.beam_out(l), b.S); });
+}
+
+// K0 -> sort -> K1G -> K2 over the first r.J beam slots (unpruned: all of them, and that is the layer); pruned: the same over the remaining
+// slots of the queries K2 did not mark done
+void launch_k1g_layer(Batch& b, size_t l, const Route& r) {
+    const Layer& L = *b.m.layers[l]; const QueriesDev& X = b.X; hipStream_t S = b.S;
+    const LayerPlan P = b.make_plan(l); const BeamDev prev = b.beam_prev(l), out = b.beam_out(l);
+    const uint32_t J = r.J, rest = P.beam_in - J;
+    b.need_x_ok();   // once per row batch: which dense query rows are finite (K1G's fast loop needs it on layers with missing cells) + the pruning guard
+    LayerPlan PA = P; PA.beam_in = J;
+    b.timed("k0_prolongate", l, [&] { launch_k0_prolongate(L.dev, P, X, prev, b.cand_off, b.ncand, b.items, S, J); });
+    b.timed("k1_sort_items", l, [&] { launch_sort_items(L.dev, (uint64_t)b.nrows * J * L.max_tiles_per_parent, b.items, b.items_sorted, b.sort_hist, b.sort_start, S); });
+    b.timed("k1g_dense_x", l, [&] { launch_k1g(L.dev, PA, X, b.items_sorted, b.sort_start, b.blk_start, b.x_ok, b.cand, S); });
+    if (!r.pruned) { b.timed("k2_topk", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S); }); return; }
+    LayerPlan PB = P; PB.beam_in = rest;
+    b.timed("k2_topk", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S, J, (uint32_t)L.cand_bound(J), b.prune_done, nullptr, b.x_ok); });
+    b.timed("k0b_remaining", l, [&] { launch_k0b_remaining(L.dev, P, X, prev, b.cand_off, b.prune_done, J, b.items, b.prune_cnt, S); });
+    b.timed("k1_sort_items_rest", l, [&] { launch_sort_items(L.dev, (uint64_t)b.nrows * rest * L.max_tiles_per_parent, b.items, b.items_sorted, b.sort_hist, b.sort_start, S, b.prune_cnt); });
+    b.timed("k1g_dense_x_rest", l, [&] { launch_k1g(L.dev, PB, X, b.items_sorted, b.sort_start, b.blk_start, b.x_ok, b.cand, S); });
+    b.timed("k2_topk_rest", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S, 0, 0, nullptr, b.prune_done); });
+}
+
+// layers [l, r.last] in one K1Q launch; with r.sorted_last the last one in a launch of its own, after the queries were sorted by the beam it reads
+void launch_k1q_group(Batch& b, size_t l, const Route& r) {
+    const QueriesDev& X = b.X; hipStream_t S = b.S; const LayerDev* Ls[8]; LayerPlan Ps[8];
+    for (size_t ll = l; ll <= r.last; ++ll) {
+        Ls[ll - l] = &b.m.layers[ll]->dev; Ps[ll - l] = b.make_plan(ll);
+        Ps[ll - l].fb_host = Ps[0].fb_host; Ps[ll - l].fb_dev = Ps[0].fb_dev;   // (a launch samples through the feedback words of its group's first layer)
+    }
+    const BeamDev prev = b.beam_prev(l);
+    const size_t n_shared = r.last - l + (r.sorted_last ? 0 : 1), ls = r.last;   // layers [l, l + n_shared) share a launch
+    const char* const single = X.dense ? "k1q_dense_x" : "k1q_dense";
+    char fused[48] = "";   // profile / trace name of a launch of several layers; composed only when somebody reads it
+    if (n_shared > 1 && b.named()) std::snprintf(fused, sizeof fused, "k1q_fused_%s%zu_%zu", X.dense ? "x_" : "", l, l + n_shared - 1);
+    // (a later layer of this batch that is NOT served by K1Q decides its pruning in K2 and needs the guard flags: this launch writes them)
+    uint32_t* xok_out = nullptr;
+    if (!b.x_ok_done && b.opt.prune && r.last + 1 < b.shape.size()) { xok_out = b.x_ok; b.x_ok_done = true; }
+    BeamDev pv = prev;
+    if (n_shared) {
+        pv = b.beam_out(l + n_shared - 1);
+        b.timed(n_shared > 1 ? fused : single, l, [&] { launch_k1q(Ls, Ps, (int)n_shared, X, prev, pv, S, b.prune_wmax, xok_out); });
+        xok_out = nullptr;
+    }
+    if (!r.sorted_last) return;
+    b.timed("k1_sort_queries", ls, [&] { launch_sort_queries(pv, b.nrows, Ls[ls - l]->n_parents, b.qsort_hist, b.qsort_start, b.qperm, S); });
+    b.timed(single, ls, [&] { launch_k1q(Ls + (ls - l), Ps + (ls - l), 1, X, pv, b.beam_out(ls), S, b.prune_wmax, xok_out, b.qperm); });
+}
+
+const char* const kK1Name[2][3] = {{"k1_sparse", "k1_sparse_mid", "k1_sparse_rest"}, {"k1_dense", "k1_dense_mid", "k1_dense_rest"}};   // [dense X][first / middle / last stage]
+
+// tile-format layer: K0 -> (sort) -> K1 -> K2 in one pass, or bound-pruned in r.n_stage stages of beam slots
+void launch_tile_layer(Batch& b, size_t l, const Route& r) {
+    Model& m = b.m; const Layer& L = *m.layers[l]; const QueriesDev& X = b.X; hipStream_t S = b.S;
+    const LayerPlan P = b.make_plan(l); const BeamDev prev = b.beam_prev(l), out = b.beam_out(l);
+    const uint32_t beam_in = P.beam_in, nrows = b.nrows, J = r.J;
+    const char* const* k1_name = kK1Name[X.dense ? 1 : 0];
+    double* const stats = b.stats ? b.stats_dev + kStatsPerLayer * l : nullptr;
+    if (!r.pruned) {
+        b.timed("k0_prolongate", l, [&] { launch_k0_prolongate(L.dev, P, X, prev, b.cand_off, b.ncand, b.items, S); });
+        if (r.mode != 0) b.timed("k1_sort_items", l, [&] { launch_sort_items(L.dev, (uint64_t)nrows * beam_in * L.max_tiles_per_parent, b.items, b.items_sorted, b.sort_hist, b.sort_start, S); });
+        if (b.lanes == 2 && b.k1_done) XRL_HIP(hipStreamWaitEvent(S, b.k1_done, 0));   // K1 launches take turns across the lanes
+        LayerPlan PU = P; PU.fb_host = nullptr;   // (an unstaged pass's item count is not a feedback sample: a probe's outcome may be pending)
+        b.timed(k1_name[0], l, [&] { launch_k1(L.dev, PU, X, r.mode == 1 ? b.items_sorted : b.items, r.mode == 1 ? b.sort_start + L.n_tiles : nullptr, b.cand, r.group, S); });
+        if (b.lanes == 2) { b.k1_done = b.next_event(); XRL_HIP(hipEventRecord(b.k1_done, S)); }
+        b.timed("k2_topk", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S); });
+        if (stats) launch_stats(L.dev, P, X, prev, b.ncand, b.items, stats, S);
+        return;
+    }
+    // Every stage: k0b (the unfinished queries' items of its slots) -> sort -> K1 -> K2 over the candidates of all slots scored so far
+    // (+ the done flag for the next stage).  The first one takes its items from K0, or (r.fuse) is one K1T launch that keeps K1's profile
+    // name; the later stages find done / cand_off / ncand / cand (unfinished queries) as K0 -> K1 -> K2 leave them.
+    const uint64_t slots_b = (uint64_t)nrows * (beam_in - J) * L.max_tiles_per_parent;
+    b.need_x_ok();
+    if (!r.fuse_k0) b.timed("k0_prolongate", l, [&] { launch_k0_prolongate(L.dev, P, X, prev, b.cand_off, b.ncand, b.items, S, J); });
+    if (b.lanes == 2 && b.k1_done) XRL_HIP(hipStreamWaitEvent(S, b.k1_done, 0));
+    if (r.fuse) {
+        const K1TSelect sel{prev, b.x_ok, out, b.prune_done, b.cand_off, b.ncand};
+        b.timed("k1_sparse", l, [&] { launch_k1t(L.dev, P, X, r.fuse_k0 ? nullptr : b.items, nullptr, b.cand, S, &sel); });
+    } else {
+        LayerPlan PA = P; PA.beam_in = J;                  // (K1 sizes its grid from beam_in x tiles per parent)
+        b.timed(k1_name[0], l, [&] { launch_k1(L.dev, PA, X, b.items, nullptr, b.cand, r.group, S); });
+        b.timed("k2_topk", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S, J, (uint32_t)L.cand_bound(J), b.prune_done, nullptr, b.x_ok); });
+    }
+    if (stats) XRL_HIP(hipMemsetAsync(b.items_sorted, 0xFF, slots_b * k0_item_bytes(), S));   // the stats pass walks the whole list: unused slots read as "no tile"
+    bool srt = r.sorts_rest;
+    // ... unless the previous predicts left (almost) nothing for the later stages: four tiny launches of the sort then cost more than
+    // the locality buys (a 61 250-row shard of Amazon-670K: 0.99 -> 0.93 ms per step, profiles/r05_k1q/README.md).  The count is the one the
+    // pruning feedback already samples (the last stage's K1 launch writes it to a host-visible word); results never depend on it.  It is
+    // read HERE, while the batches are being enqueued: the device may have written it since the predict began.
+    if (srt && P.fb_host && b.opt.sort_rest_min > 0) {
+        const uint32_t seen = m.fb.word(fb_items_word((int)l));
+        // (measured, Amazon-670K shape, 8192 leaf tiles: 78 k items = 9.5 per tile -- K1 runs 0.295 ms sorted, 0.298 unsorted, the sort costs 0.062;
+        //  4.4 M items = 537 per tile on the hard model -- unsorted K1 finds 7 % of its lines in the L2, sorted 94 %: the sort pays once
+        //  a tile's lookup words and entries are re-used a few dozen times)
+        const uint64_t need = std::max<uint64_t>((uint64_t)b.opt.sort_rest_min, 32ull * L.n_tiles);
+        if (seen != kFbPending && (uint64_t)seen < need) srt = false;
+    }
+    if (P.fb_host) m.fb.tile_slots[l] = (uint64_t)nrows * (beam_in - r.stage_end[r.n_stage - 2]) * L.max_tiles_per_parent;
+    for (int st = 1; st < r.n_stage; ++st) {
+        const uint32_t r0 = r.stage_end[st - 1], r1 = r.stage_end[st]; const bool last = st == r.n_stage - 1;
+        LayerPlan PB = P; PB.beam_in = r1 - r0; PB.tune.wpb = 4;   // a later stage's grid is sized for "nothing pruned": mostly empty wavefronts, 4 per workgroup to dispatch fewer groups
+        // (sorted: the compacted list goes where the first phase's items were -- K1 has consumed them -- and is sorted into items_sorted)
+        b.timed(last ? "k0b_remaining" : "k0b_remaining_mid", l, [&] { launch_k0b_remaining(L.dev, P, X, prev, b.cand_off, b.prune_done, r0, srt ? b.items : b.items_sorted, b.prune_cnt, S, r1); });
+        if (srt) b.timed(last ? "k1_sort_items_rest" : "k1_sort_items_mid", l, [&] { launch_sort_items(L.dev, (uint64_t)nrows * (r1 - r0) * L.max_tiles_per_parent, b.items, b.items_sorted, b.sort_hist, b.sort_start, S, b.prune_cnt); });
+        b.timed(k1_name[last ? 2 : 1], l, [&] { launch_k1(L.dev, PB, X, b.items_sorted, srt ? b.sort_start + L.n_tiles : b.prune_cnt, b.cand, r.group, S); });
+        if (b.lanes == 2 && last) { b.k1_done = b.next_event(); XRL_HIP(hipEventRecord(b.k1_done, S)); }
+        // (a middle stage selects among the slots scored so far and renews the done flags; queries finished earlier are skipped: one buffer serves both)
+        if (last) b.timed("k2_topk_rest", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S, 0, 0, nullptr, b.prune_done); });
+        else b.timed("k2_topk_mid", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S, r1, (uint32_t)L.cand_bound(r1), b.prune_done, b.prune_done, b.x_ok); });
+        if (stats && last) { launch_stats(L.dev, P, X, prev, b.ncand, b.items, stats, S, (uint64_t)nrows * J * L.max_tiles_per_parent); launch_stats(L.dev, PB, X, prev, nullptr, b.items_sorted, stats, S, slots_b); }
+    }
+}
+
+void launch_batch(Batch& b) {   // every layer of the row batch in flight
+    for (size_t l = 0; l < b.shape.size(); ++l) {
+        const Route r = route_layer(b, l, b.nrows);
+        switch (r.kind) {
+            case ROUTE_CSC: launch_csc_layer(b, l); break;
+            case ROUTE_K1G: launch_k1g_layer(b, l, r); break;
+            case ROUTE_K1Q: launch_k1q_group(b, l, r); break;
+            case ROUTE_TILE: launch_tile_layer(b, l, r); break;
+        }
+        l = r.last;
+    }
+}
+}  // namespace
+
+// ---- pruning feedback: which layers run UNSTAGED this time because their first stage settled (almost) no query the last times
+PruneFeedback::Plan PruneFeedback::begin_predict(size_t n_layers, bool sample) {
+    Plan plan;
+    if (!host) {
+        XRL_HIP(hipHostMalloc(reinterpret_cast<void**>(&host), kFbHostWords * 4, hipHostMallocDefault));
+        for (int i = 0; i < kFbHostWords; ++i) host[i] = i < kFbCounterWords ? 0u : kFbPending;
+        dev.reserve(kFbCounterWords * 4); XRL_HIP(hipMemset(dev.p, 0, kFbCounterWords * 4));
+    }
+    for (int l = 0; l < (int)std::min<size_t>(n_layers, kFbLayers); ++l) {
+        if (sample && unstaged[l]) {
+            // An unstaged layer is PROBED every kReprobe predicts: that one predict stages it, the following ones keep running
+            // unstaged until the probe's counters arrive (a caller that queues predicts without synchronising is many predicts
+            // ahead of the device: waiting for the outcome in the staged state would run all of them staged).
+            bool decided = false, stage_again = false;
+            if (probing[l]) {
+                const uint32_t sn = word(fb_seen_word(l)), sec = word(fb_second_word(l)), dseen = sn - seen[l], dsec = sec - second[l];
+                const uint32_t cnt = word(fb_items_word(l));
+                if (dseen >= kMinSamples) { decided = true; stage_again = !((double)dsec > kSecondShare * (double)dseen); seen[l] = sn; second[l] = sec; }
+                else if (cnt != kFbPending && tile_slots[l] > 0) { decided = true; stage_again = !((double)cnt > kItemShare * (double)tile_slots[l]); }
+                if (decided) { probing[l] = 0; unstaged_calls[l] = 0; if (stage_again) unstaged[l] = 0; }
+            }
+            if (unstaged[l] && ++unstaged_calls[l] >= kReprobe) {    // (an undecided probe -- a batch too small to sample 256 queries -- is repeated)
+                unstaged_calls[l] = 0; probing[l] = 1; plan.probed[l] = true;
+                // (advisor, round 6: re-basing the counters after an UNDECIDED probe drops the samples it did collect -- kept as it is here)
+                if (!decided) { seen[l] = word(fb_seen_word(l)); second[l] = word(fb_second_word(l)); }
+                host[fb_items_word(l)] = kFbPending; tile_slots[l] = 0;
+            }
+        } else if (sample) {
+            // query-stationary layers: of the sampled queries that ran staged, how many needed the second pass
+            const uint32_t sn = word(fb_seen_word(l)), sec = word(fb_second_word(l)), dseen = sn - seen[l], dsec = sec - second[l];
+            if (dseen >= kMinSamples) {
+                if ((double)dsec > kSecondShare * (double)dseen) { unstaged[l] = 1; unstaged_calls[l] = 0; probing[l] = 0; }
+                seen[l] = sn; second[l] = sec;
+            }
+            // tile-format layers: the item count of the last stage against the slots it was sized for
+            const uint32_t cnt = word(fb_items_word(l));
+            if (cnt != kFbPending && tile_slots[l] > 0 && (double)cnt > kItemShare * (double)tile_slots[l]) { unstaged[l] = 1; unstaged_calls[l] = 0; probing[l] = 0; }
+        }
+        plan.unstaged[l] = unstaged[l] != 0 && !plan.probed[l];
+    }
+    return plan;
+}
+
+uint32_t effective_topk(const Model& m, uint32_t only_topk) { return only_topk ? only_topk : m.layers.back()->only_topk; }   // inference.hpp:2055
+
+void predict_device(Model& m, const QueriesDev& X, const PredictOpts& o, uint32_t* d_out_idx, float* d_out_val,
+                    uint32_t* d_out_cnt, uint32_t out_stride, hipStream_t stream, bool sync, uint32_t row_begin, uint32_t row_count) {
+    const size_t T = m.layers.size();
+    // rows [row_begin, row_end) of X (results land at the same rows of the output buffers); default: all rows
+    if (row_begin > X.rows) fail("predict: row range outside X");
+    const uint64_t row_end = std::min<uint64_t>(X.rows, (uint64_t)row_begin + row_count), n_rows = row_end - row_begin;
+    if (!m.ws) m.ws = std::make_unique<Workspace>();
+    if (!stream) stream = m.stream;
+    // the scratch buffers are shared by every predict of the handle: an asynchronous predict still running on another stream must finish first
+    if (m.ws_done && m.ws_stream != stream) XRL_HIP(hipStreamWaitEvent(stream, m.ws_done, 0));
+    static const bool step_marker = [] { const char* e = std::getenv("XRL_STEP_MARKER"); return e && e[0] == '1'; }();
+    if (step_marker && !o.stats_out) launch_step_marker(stream);
+
+    const std::vector<LayerShape> shape = resolve_layers(m, X, o);
+    if (shape[T - 1].k > out_stride) fail("out_stride smaller than the effective only_topk");
+    Batch b{m, m.opt, X, o, shape, BeamDev{d_out_idx, d_out_val, d_out_cnt, out_stride}};
+    b.has_init = o.initial != nullptr; b.csc = o.csc_route || m.csc_route; b.stats = o.stats_out != nullptr;
+    for (size_t l = 0; l < T; ++l) {
+        if (l + 1 < T) b.beam_stride = std::max(b.beam_stride, shape[l].k);
+        b.prune_wmax = std::max(b.prune_wmax, m.layers[l]->w_absmax);
+    }
+    if (!(b.prune_wmax <= 3.0e38f)) b.prune_wmax = INFINITY;
+    size_batches(b, n_rows);
+    if (m.opt.prune && m.opt.adaptive) b.fb = m.fb.begin_predict(T, !b.stats);
+    reserve_scratch(b, *m.ws, n_rows);
+    if (b.stats) { b.stats_dev = m.ws->stats.as<double>(); XRL_HIP(hipMemsetAsync(m.ws->stats.p, 0, T * kStatsPerLayer * sizeof(double), stream)); }
 
     // ---- streams and cross-stream ordering
     hipStream_t lane_stream[2] = {stream, stream};
-    size_t ev_next = 0;
-    auto next_event = [&]() -> hipEvent_t {
-        if (ev_next == m.events.size()) { hipEvent_t e; XRL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); m.events.push_back(e); }
-        return m.events[ev_next++];
-    };
-    if (lanes == 2) {
+    if (b.lanes == 2) {
         if (!m.aux_stream) XRL_HIP(hipStreamCreateWithFlags(&m.aux_stream, hipStreamNonBlocking));
         lane_stream[1] = m.aux_stream;
-        hipEvent_t e = next_event();                                   // the auxiliary lane starts after everything queued so far
-        XRL_HIP(hipEventRecord(e, stream));
-        XRL_HIP(hipStreamWaitEvent(m.aux_stream, e, 0));
-    }
-    hipEvent_t k1_done = nullptr;                                      // the most recent K1 launch (either lane)
-    // the bound-pruning guard (prune_guard_ok, xrl_device.h) prices a query's largest |x| with the model's largest |weight| x max(1, |bias|)
-    float prune_wmax = 0.0f;
-    for (size_t l = 0; l < T; ++l) prune_wmax = std::max(prune_wmax, m.layers[l]->w_absmax);
-    if (!(prune_wmax <= 3.0e38f)) prune_wmax = INFINITY;
-    // ---- pruning feedback (Model::fb_*): which layers run UNSTAGED this time because their first stage settled (almost) no query the last times
-    bool unst[Model::kFbLayers] = {false}, probe_now[Model::kFbLayers] = {false};
-    if (m.prune && m.adaptive) {
-        constexpr uint32_t kFbReprobe = 32;                             // an unstaged layer is staged again every so many predicts: the data may have changed
-        constexpr uint32_t kPending = 0xFFFFFFFFu;
-        if (!m.fb_host) {
-            XRL_HIP(hipHostMalloc(reinterpret_cast<void**>(&m.fb_host), 3 * Model::kFbLayers * 4, hipHostMallocDefault));
-            for (int i = 0; i < 3 * Model::kFbLayers; ++i) m.fb_host[i] = i < 2 * Model::kFbLayers ? 0u : kPending;
-            m.fb_dev.reserve(2 * Model::kFbLayers * 4);
-            XRL_HIP(hipMemset(m.fb_dev.p, 0, 2 * Model::kFbLayers * 4));
-        }
-        volatile uint32_t* fh = m.fb_host;
-        for (size_t l = 0; l < T && l < (size_t)Model::kFbLayers; ++l) {
-            if (!o.stats_out) {
-                if (m.fb_unstaged[l]) {
-                    // An unstaged layer is PROBED every kFbReprobe predicts: that one predict stages it, the following ones keep running
-                    // unstaged until the probe's counters arrive (a caller that queues predicts without synchronising is many predicts
-                    // ahead of the device: waiting for the outcome in the staged state would run all of them staged).
-                    bool decided = false, stage_again = false;
-                    if (m.fb_probing[l]) {
-                        const uint32_t seen = fh[2 * l], sec = fh[2 * l + 1], dseen = seen - m.fb_seen[l], dsec = sec - m.fb_second[l];
-                        const uint32_t cnt = fh[2 * Model::kFbLayers + l];
-                        if (dseen >= 256u) { decided = true; stage_again = !((double)dsec > 0.7 * (double)dseen); m.fb_seen[l] = seen; m.fb_second[l] = sec; }
-                        else if (cnt != kPending && m.fb_tile_slots[l] > 0) { decided = true; stage_again = !((double)cnt > 0.6 * (double)m.fb_tile_slots[l]); }
-                        if (decided) { m.fb_probing[l] = 0; m.fb_unstaged_calls[l] = 0; if (stage_again) m.fb_unstaged[l] = 0; }
-                    }
-                    if (m.fb_unstaged[l] && ++m.fb_unstaged_calls[l] >= kFbReprobe) {    // (an undecided probe -- a batch too small to sample 256 queries -- is repeated)
-                        m.fb_unstaged_calls[l] = 0; m.fb_probing[l] = 1; probe_now[l] = true;
-                        if (!decided) { m.fb_seen[l] = fh[2 * l]; m.fb_second[l] = fh[2 * l + 1]; }
-                        fh[2 * Model::kFbLayers + l] = kPending; m.fb_tile_slots[l] = 0;
-                    }
-                } else {
-                    // query-stationary layers: of the sampled queries that ran staged, how many needed the second pass
-                    const uint32_t seen = fh[2 * l], sec = fh[2 * l + 1], dseen = seen - m.fb_seen[l], dsec = sec - m.fb_second[l];
-                    if (dseen >= 256u) {
-                        if ((double)dsec > 0.7 * (double)dseen) { m.fb_unstaged[l] = 1; m.fb_unstaged_calls[l] = 0; m.fb_probing[l] = 0; }
-                        m.fb_seen[l] = seen; m.fb_second[l] = sec;
-                    }
-                    // tile-format layers: the item count of the last stage against the slots it was sized for
-                    const uint32_t cnt = fh[2 * Model::kFbLayers + l];
-                    if (cnt != kPending && m.fb_tile_slots[l] > 0 && (double)cnt > 0.6 * (double)m.fb_tile_slots[l]) { m.fb_unstaged[l] = 1; m.fb_unstaged_calls[l] = 0; m.fb_probing[l] = 0; }
-                }
-            }
-            unst[l] = m.fb_unstaged[l] != 0 && !probe_now[l];
-        }
+        b.chain(stream, m.aux_stream);                                 // the auxiliary lane starts after everything queued so far
     }
 
     uint64_t batch = 0;
-    for (uint64_t row0 = row_begin; row0 < row_end; row0 += nb, ++batch) {
-        const uint32_t nrows = (uint32_t)std::min<uint64_t>(nb, row_end - row0);
-        const int ln = (int)(batch % (uint64_t)lanes);
-        LaneWs& lw = ws.lane[ln];
-        hipStream_t S = lane_stream[ln];
-        static const bool debug_sync = [] { const char* e = std::getenv("XRL_DEBUG_SYNC"); return e && e[0] == '1'; }();
-        auto timed = [&](const char* name, uint32_t layer, auto&& fn) {
-            if (debug_sync) {   // XRL_DEBUG_SYNC=1: every launch group is announced and synchronised on its own, a device fault names the kernel family and the layer
-                std::fprintf(stderr, "[xrl debug] %s layer %u rows %llu+%u\n", name, layer, (unsigned long long)row0, nrows); std::fflush(stderr);
-                fn();
-                const hipError_t e = hipStreamSynchronize(S);
-                if (e != hipSuccess) fail(std::string("device fault in ") + name + " (layer " + std::to_string(layer) + ", rows " + std::to_string(row0) + "+" + std::to_string(nrows) + "): " + hipGetErrorString(e));
-                return;
-            }
-            if (!m.profiling) { fn(); return; }
-            PendingEvent ev; ev.slot = profile_slot(m, name, layer);
-            XRL_HIP(hipEventCreate(&ev.a)); XRL_HIP(hipEventCreate(&ev.b));
-            XRL_HIP(hipEventRecord(ev.a, S));
-            fn();
-            XRL_HIP(hipEventRecord(ev.b, S));
-            m.pending.push_back(ev);
-        };
-        // per row batch: lw.x_ok[q] = the pruning guard of query q (also "all x finite" for K1G's fast loop); written by launch_xguard or,
-        // for free, by a K1Q launch that runs before the first layer that needs it
-        bool x_ok_done = false;
-        auto need_x_ok = [&]() {
-            if (x_ok_done) return;
-            lw.x_ok.reserve((size_t)nb * 4);
-            timed("xguard", 0u, [&] { launch_xguard(X, (uint32_t)row0, nrows, prune_wmax, lw.x_ok.as<uint32_t>(), S); });
-            x_ok_done = true;
-        };
-        for (size_t l = 0; l < T; ++l) {
-            const Layer& L = *m.layers[l];
-            LayerPlan P{};
-            P.layer = (int)l;
-            P.row0 = (uint32_t)row0; P.nrows = nrows; P.beam_in = beam_in[l]; P.k = k[l];
-            P.cand_stride = cstride[l]; P.pp = pp[l];
-            P.tune.wpb = m.k1_wpb; P.tune.lds_pad = m.k1_lds_pad; P.tune.ablate = m.k1_ablate; P.tune.k1g_variant = m.k1g_variant; P.tune.pres_mode = m.presence; P.tune.tile_rows = m.tile_rows; P.tune.k2_big_min_k = m.k2_big_min_k;
-            P.first_layer = (l == 0 && (!has_init || o.no_prev_pred)) ? 1 : 0;   // no_prev_pred
-            P.implicit_root = (l == 0 && !has_init) ? 1 : 0;
-            P.bias_first = (m.weight_matrix_type == 1 && !X.dense) ? 1 : 0;
-            P.prune = (m.prune && !(l < (size_t)Model::kFbLayers && unst[l])) ? 1 : 0;
-            if (m.prune && m.adaptive && !o.stats_out && l < (size_t)Model::kFbLayers) { P.fb_host = m.fb_host; P.fb_dev = m.fb_dev.as<uint32_t>(); }
-            BeamDev prev{};
-            if (l == 0 && has_init) {
-                prev = *o.initial;
-                prev.idx += row0 * prev.stride; prev.val += row0 * prev.stride; prev.cnt += row0;
-            } else if (l > 0) {
-                const int b = (int)((l - 1) & 1);
-                prev = BeamDev{lw.beam_idx[b].as<uint32_t>(), lw.beam_val[b].as<float>(), lw.beam_cnt[b].as<uint32_t>(), beam_stride};
-            }
-            uint32_t *oi, *oc; float* ov; uint32_t os;
-            if (l == T - 1) { oi = d_out_idx + row0 * out_stride; ov = d_out_val + row0 * out_stride; oc = d_out_cnt + row0; os = out_stride; }
-            else { const int b = (int)(l & 1); oi = lw.beam_idx[b].as<uint32_t>(); ov = lw.beam_val[b].as<float>(); oc = lw.beam_cnt[b].as<uint32_t>(); os = beam_stride; }
-
-            // layers held in the dense row format: the whole layer is one query-stationary kernel (beam in, beam out)
-            if (csc) {
-                // CSC route (weight_matrix_type CSC, single-layer API): one (query, child) dot product per candidate, bias first
-                Layer& Lm = *m.layers[l];
-                ensure_device_csc(Lm);
-                timed("k0_prolongate", (uint32_t)l, [&] { launch_k0_prolongate(L.dev, P, X, prev, lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>(), lw.items.p, S); });
-                timed("k1c_csc", (uint32_t)l, [&] { launch_k1c_csc(L.dev, Lm.d_csc_ptr.as<uint64_t>(), Lm.d_csc_idx.as<uint32_t>(), Lm.d_csc_val.as<float>(), P, X, prev,
-                                                                   lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>(), lw.cand.as<float>(), S); });
-                timed("k2_topk", (uint32_t)l, [&] { launch_k2_topk(L.dev, P, prev, lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>(), lw.cand.as<float>(), oi, ov, oc, os, S); });
-                continue;
-            }
-            if (!o.stats_out && layer_mode(l, nrows) == 3) {
-                need_x_ok();   // once per row batch: which dense query rows are finite (K1G's fast loop needs it on layers with missing cells) + the pruning guard
-                // ---- exact bound pruning (see the tile-format path below): the GEMM over the children of the J best beam parents first,
-                //      then a second, tile-sorted GEMM over the remaining slots of the queries whose top-k is not final yet.  J covers about
-                //      one candidate register (64 candidates), like K1Q's first stage.
-                if (m.prune && !P.implicit_root && !P.first_layer && P.pp.kind != PP_NOOP && beam_in[l] > 1 && k2_wave_path(P)) {
-                    const uint32_t J = k1g_first_slots(L, beam_in[l], m.k1g_first);
-                    const uint64_t slots_a = (uint64_t)nrows * J * L.max_tiles_per_parent, slots_b = (uint64_t)nrows * (beam_in[l] - J) * L.max_tiles_per_parent;
-                    lw.prune_done.reserve((size_t)nb * 4); lw.prune_cnt.reserve(256);
-                    LayerPlan PA = P; PA.beam_in = J;
-                    LayerPlan PB = P; PB.beam_in = beam_in[l] - J;
-                    timed("k0_prolongate", (uint32_t)l, [&] { launch_k0_prolongate(L.dev, P, X, prev, lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>(), lw.items.p, S, J); });
-                    timed("k1_sort_items", (uint32_t)l, [&] { launch_sort_items(L.dev, slots_a, lw.items.p, lw.items_sorted.p, lw.sort_hist.as<uint32_t>(), lw.sort_start.as<uint32_t>(), S); });
-                    timed("k1g_dense_x", (uint32_t)l, [&] { launch_k1g(L.dev, PA, X, lw.items_sorted.p, lw.sort_start.as<uint32_t>(), lw.blk_start.as<uint32_t>(), lw.x_ok.as<uint32_t>(), lw.cand.as<float>(), S); });
-                    timed("k2_topk", (uint32_t)l, [&] { launch_k2_topk(L.dev, P, prev, lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>(), lw.cand.as<float>(), oi, ov, oc, os, S,
-                                                                       J, (uint32_t)L.cand_bound(J), lw.prune_done.as<uint32_t>(), nullptr, lw.x_ok.as<uint32_t>()); });
-                    timed("k0b_remaining", (uint32_t)l, [&] { launch_k0b_remaining(L.dev, P, X, prev, lw.cand_off.as<uint32_t>(), lw.prune_done.as<uint32_t>(), J, lw.items.p,
-                                                                                   lw.prune_cnt.as<uint32_t>(), S); });
-                    timed("k1_sort_items_rest", (uint32_t)l, [&] { launch_sort_items(L.dev, slots_b, lw.items.p, lw.items_sorted.p, lw.sort_hist.as<uint32_t>(), lw.sort_start.as<uint32_t>(), S,
-                                                                                     lw.prune_cnt.as<uint32_t>()); });
-                    timed("k1g_dense_x_rest", (uint32_t)l, [&] { launch_k1g(L.dev, PB, X, lw.items_sorted.p, lw.sort_start.as<uint32_t>(), lw.blk_start.as<uint32_t>(), lw.x_ok.as<uint32_t>(), lw.cand.as<float>(), S); });
-                    timed("k2_topk_rest", (uint32_t)l, [&] { launch_k2_topk(L.dev, P, prev, lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>(), lw.cand.as<float>(), oi, ov, oc, os, S,
-                                                                            0, 0, nullptr, lw.prune_done.as<uint32_t>()); });
-                    continue;
-                }
-                timed("k0_prolongate", (uint32_t)l, [&] { launch_k0_prolongate(L.dev, P, X, prev, lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>(), lw.items.p, S); });
-                const uint64_t n_slots3 = (uint64_t)nrows * beam_in[l] * L.max_tiles_per_parent;
-                timed("k1_sort_items", (uint32_t)l, [&] { launch_sort_items(L.dev, n_slots3, lw.items.p, lw.items_sorted.p, lw.sort_hist.as<uint32_t>(), lw.sort_start.as<uint32_t>(), S); });
-                timed("k1g_dense_x", (uint32_t)l, [&] { launch_k1g(L.dev, P, X, lw.items_sorted.p, lw.sort_start.as<uint32_t>(), lw.blk_start.as<uint32_t>(), lw.x_ok.as<uint32_t>(), lw.cand.as<float>(), S); });
-                timed("k2_topk", (uint32_t)l, [&] { launch_k2_topk(L.dev, P, prev, lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>(), lw.cand.as<float>(), oi, ov, oc, os, S); });
-                continue;
-            }
-            auto runs_k1q = [&](size_t ll) { return m.dense_layers && !o.stats_out && !csc && layer_mode(ll, nrows) != 3 && k1q_regs(m.layers[ll]->dev, beam_in[ll], k[ll], X.dense != 0 || m.dense_layers >= 2) != 0; };
-            if (runs_k1q(l)) {
-                // consecutive dense-format layers run in ONE launch: the wavefront that owns a query carries its beam through them in LDS
-                size_t l1 = l;
-                // (only narrow layers share a launch: a fused kernel is compiled for -- and holds the registers of -- its widest layer)
-                auto narrow = [&](size_t ll) { return k1q_regs(m.layers[ll]->dev, beam_in[ll], k[ll], X.dense != 0 || m.dense_layers >= 2) <= (uint32_t)std::min(3, m.k1q_fuse); };
-                while (m.k1q_fuse && narrow(l) && l1 + 1 < T && l1 + 1 - l < 8 && runs_k1q(l1 + 1) && narrow(l1 + 1)) ++l1;
-                const LayerDev* Ls[8]; LayerPlan Ps[8];
-                for (size_t ll = l; ll <= l1; ++ll) {
-                    Ls[ll - l] = &m.layers[ll]->dev;
-                    LayerPlan Q = P;
-                    Q.layer = (int)ll; Q.beam_in = beam_in[ll]; Q.k = k[ll]; Q.cand_stride = cstride[ll]; Q.pp = pp[ll];
-                    Q.first_layer = (ll == 0 && (!has_init || o.no_prev_pred)) ? 1 : 0;
-                    Q.implicit_root = (ll == 0 && !has_init) ? 1 : 0;
-                    Q.prune = (m.prune && !(ll < (size_t)Model::kFbLayers && unst[ll])) ? 1 : 0;
-                    Ps[ll - l] = Q;
-                }
-                auto beam_out = [&](size_t ll, uint32_t*& qi, float*& qv, uint32_t*& qc, uint32_t& qs) {
-                    if (ll == T - 1) { qi = d_out_idx + row0 * out_stride; qv = d_out_val + row0 * out_stride; qc = d_out_cnt + row0; qs = out_stride; }
-                    else { const int b = (int)(ll & 1); qi = lw.beam_idx[b].as<uint32_t>(); qv = lw.beam_val[b].as<float>(); qc = lw.beam_cnt[b].as<uint32_t>(); qs = beam_stride; }
-                };
-                auto launch_name = [&](size_t a, size_t b) {
-                    return (b > a) ? std::string(X.dense ? "k1q_fused_x_" : "k1q_fused_") + std::to_string(a) + "_" + std::to_string(b) : std::string(X.dense ? "k1q_dense_x" : "k1q_dense");
-                };
-                // (a later layer of this batch that is NOT served by K1Q decides its pruning in K2 and needs the guard flags: this launch writes them)
-                uint32_t* xok_out = nullptr;
-                if (!x_ok_done && m.prune && l1 + 1 < T) { lw.x_ok.reserve((size_t)nb * 4); xok_out = lw.x_ok.as<uint32_t>(); x_ok_done = true; }
-                // SORTED launch of the group's last layer (option qsort): a layer of many parents whose matrix is far larger than the L2s is
-                // request-bound -- one 64-byte fabric request per (feature, beam parent) and query -- and the queries that share beam
-                // parents are scattered over the batch.  The layers before it run as usual; the queries are then counting-sorted by the best
-                // parent of the beam they produced and the last layer runs in that order, every XCD on a contiguous range of it.
-                const size_t ls = l1;
-                const bool sorted_last = m.qsort != 0 && !X.dense && ls > 0 && !(ls == 0 && has_init) && nrows >= (uint32_t)std::max(1, m.qsort_min_rows) &&
-                                         m.layers[ls]->dev.n_parents >= (uint32_t)std::max(2, m.qsort_min_parents) && m.layers[ls]->dev.n_parents <= qsort_max_keys();
-                if (sorted_last) {
-                    BeamDev pv = prev;
-                    if (ls > l) {
-                        uint32_t *qi, *qc; float* qv; uint32_t qs;
-                        beam_out(ls - 1, qi, qv, qc, qs);
-                        timed(launch_name(l, ls - 1).c_str(), (uint32_t)l, [&] { launch_k1q(Ls, Ps, (int)(ls - l), X, prev, qi, qv, qc, qs, S, prune_wmax, xok_out); });
-                        xok_out = nullptr;
-                        pv = BeamDev{qi, qv, qc, qs};
-                    }
-                    const uint32_t nk = m.layers[ls]->dev.n_parents;
-                    lw.qperm.reserve((size_t)nb * 4); lw.qsort_hist.reserve(qsort_hist_bytes((uint32_t)nb, nk)); lw.qsort_start.reserve(((size_t)nk + 1) * 4);
-                    timed("k1_sort_queries", (uint32_t)ls, [&] { launch_sort_queries(pv, nrows, nk, lw.qsort_hist.as<uint32_t>(), lw.qsort_start.as<uint32_t>(), lw.qperm.as<uint32_t>(), S); });
-                    uint32_t *qi, *qc; float* qv; uint32_t qs;
-                    beam_out(ls, qi, qv, qc, qs);
-                    timed(X.dense ? "k1q_dense_x" : "k1q_dense", (uint32_t)ls, [&] { launch_k1q(Ls + (ls - l), Ps + (ls - l), 1, X, pv, qi, qv, qc, qs, S, prune_wmax, xok_out, lw.qperm.as<uint32_t>()); });
-                    l = l1;
-                    continue;
-                }
-                uint32_t *qi, *qc; float* qv; uint32_t qs;
-                beam_out(l1, qi, qv, qc, qs);
-                timed(launch_name(l, l1).c_str(), (uint32_t)l, [&] { launch_k1q(Ls, Ps, (int)(l1 - l + 1), X, prev, qi, qv, qc, qs, S, prune_wmax, xok_out); });
-                l = l1;
-                continue;
-            }
-            int g = m.k1_group > 0 ? m.k1_group : k1_auto_group(L.dev, L, X.dense);
-            int mode = layer_mode(l, nrows);
-            const bool fb_unstaged = l < (size_t)Model::kFbLayers && unst[l];
-            if (fb_unstaged && mode == 0 && sorts_rest(l)) mode = 1;    // pruning feedback: everything in one pass, on tile-sorted items
-            // ---- exact bound pruning, tile format: score the children of the best beam parent first (K0 -> K1 -> K2 on one slot), then
-            //      only the remaining slots of the queries whose top-k is not final yet (see K2Args).  Needs a combiner (a child's score
-            //      is then <= its parent's) and the register top-k kernel.
-            bool pruned = m.prune && !fb_unstaged && !P.implicit_root && !P.first_layer && P.pp.kind != PP_NOOP && beam_in[l] > 1 && k2_wave_path(P);
-            uint32_t J = 1;
-            if (o.stats_out) {
-                // the stats pass walks the tile format whatever kernel the timed pass runs: stage it the way THAT kernel stages the layer, so
-                // that the work it counts is the work the timed kernels evaluate (K1G: J parents first; K1Q: the parents of candidate
-                // register 0 first, nothing skipped when the whole beam fits one register)
-                const bool dense_x = X.dense != 0 || m.dense_layers >= 2;
-                if (mode == 3) J = k1g_first_slots(L, beam_in[l], m.k1g_first);      // (the SAME staging the timed K1G path uses: ADVICE r3)
-                else if (m.dense_layers && k1q_regs(L.dev, beam_in[l], k[l], dense_x) != 0) {
-                    if (k1q_regs(L.dev, beam_in[l], k[l], dense_x) <= 1) pruned = false;
-                    else J = std::max<uint32_t>(1, (64u >> L.dev.d_gp_log2) / std::max<uint32_t>(1, L.dev.d_max_tiles));
-                }
-                if (J >= beam_in[l]) pruned = false;
-            } else if (mode != 0) pruned = false;
-            if (pruned) {
-                // stages of beam slots: [0, J) first, then -- wide beams only (>= 16 parents: Wiki10-31K's 20) -- a MIDDLE stage [J, J2) before
-                // "everything else": with 20 parents of ~60 children and k = 20 the first parent alone rarely settles the top-k, the first
-                // five usually do, and the last stage then sees few queries.  Every stage: k0b (the unfinished queries' items of its slots) ->
-                // sort -> K1 -> K2 over the candidates of all slots scored so far (+ the done flag for the next stage).
-                uint32_t stage_end[3]; int n_stage = 0;
-                stage_end[n_stage++] = J;
-                if (m.prune_mid != 0 && beam_in[l] >= 16u && !o.stats_out) stage_end[n_stage++] = std::min<uint32_t>(beam_in[l] - 1u, J + 4u);
-                stage_end[n_stage++] = beam_in[l];
-                const uint64_t slots_b = (uint64_t)nrows * (beam_in[l] - J) * L.max_tiles_per_parent;
-                lw.prune_done.reserve((size_t)nb * 4); lw.prune_cnt.reserve(256);
-                lw.items_sorted.reserve(slots_max * k0_item_bytes());
-                need_x_ok();
-                LayerPlan PA = P; PA.beam_in = J;                  // (K1 sizes its grid from beam_in x tiles per parent)
-                // option leaf_fuse: with one tile per parent, K1T's lanes end up holding every candidate of slot 0 -- its epilogue selects the top-k
-                // and sets the done flags itself (xrl_k1t.hip, SEL): no k2_topk launch, and no candidate row stored for a query that is done.  The
-                // launch keeps K1's profile name; the later stages find done / cand_off / ncand / cand (unfinished queries) as K0 -> K1 -> K2 leave them.
-                const bool fuse = m.leaf_fuse != 0 && J == 1 && !o.stats_out && k1t_selects(L.dev, P, X);
-                // ... and (beams of up to 32 parents) derives its items from the beam: K0 is not launched either.  leaf_fuse = 2 keeps K0 (A/B runs).
-                const bool fuse_k0 = fuse && m.leaf_fuse != 2 && beam_in[l] <= 32u;
-                if (!fuse_k0) timed("k0_prolongate", (uint32_t)l, [&] { launch_k0_prolongate(L.dev, P, X, prev, lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>(), lw.items.p, S, J); });
-                if (lanes == 2 && k1_done) XRL_HIP(hipStreamWaitEvent(S, k1_done, 0));
-                if (fuse) {
-                    const K1TSelect sel{prev, lw.x_ok.as<uint32_t>(), oi, ov, oc, os, lw.prune_done.as<uint32_t>(), lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>()};
-                    timed("k1_sparse", (uint32_t)l, [&] { launch_k1t(L.dev, P, X, fuse_k0 ? nullptr : lw.items.p, nullptr, lw.cand.as<float>(), S, &sel); });
-                } else {
-                timed(X.dense ? "k1_dense" : "k1_sparse", (uint32_t)l, [&] { launch_k1(L.dev, PA, X, lw.items.p, nullptr, lw.cand.as<float>(), g, S); });
-                timed("k2_topk", (uint32_t)l, [&] { launch_k2_topk(L.dev, P, prev, lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>(), lw.cand.as<float>(), oi, ov, oc, os, S,
-                                                                   J, (uint32_t)L.cand_bound(J), lw.prune_done.as<uint32_t>(), nullptr, lw.x_ok.as<uint32_t>()); });
-                }
-                if (o.stats_out) XRL_HIP(hipMemsetAsync(lw.items_sorted.p, 0xFF, slots_b * k0_item_bytes(), S));   // the stats pass walks the whole list: unused slots read as "no tile"
-                bool srt = sorts_rest(l);
-                // ... unless the previous predicts left (almost) nothing for the later stages: four tiny launches of the sort then cost more than
-                // the locality buys (a 61 250-row shard of Amazon-670K: 0.99 -> 0.93 ms per step, profiles/r05_k1q/README.md).  The count is the one the
-                // pruning feedback already samples (the last stage's K1 launch writes it to a host-visible word); results never depend on it.
-                if (srt && P.fb_host && l < (size_t)Model::kFbLayers && m.sort_rest_min > 0) {
-                    const uint32_t seen = static_cast<volatile uint32_t*>(m.fb_host)[2 * Model::kFbLayers + l];
-                    // (measured, Amazon-670K shape, 8192 leaf tiles: 78 k items = 9.5 per tile -- K1 runs 0.295 ms sorted, 0.298 unsorted, the sort costs 0.062;
-                    //  4.4 M items = 537 per tile on the hard model -- unsorted K1 finds 7 % of its lines in the L2, sorted 94 %: the sort pays once
-                    //  a tile's lookup words and entries are re-used a few dozen times)
-                    const uint64_t need = std::max<uint64_t>((uint64_t)m.sort_rest_min, 32ull * L.n_tiles);
-                    if (seen != 0xFFFFFFFFu && (uint64_t)seen < need) srt = false;
-                }
-                if (P.fb_host && l < (size_t)Model::kFbLayers) m.fb_tile_slots[l] = (uint64_t)nrows * (beam_in[l] - stage_end[n_stage - 2]) * L.max_tiles_per_parent;
-                for (int st = 1; st < n_stage; ++st) {
-                    const uint32_t r0 = stage_end[st - 1], r1 = stage_end[st];
-                    const bool last = st == n_stage - 1;
-                    const uint64_t slots_s = (uint64_t)nrows * (r1 - r0) * L.max_tiles_per_parent;
-                    LayerPlan PB = P; PB.beam_in = r1 - r0;
-                    PB.tune.wpb = 4;                               // a later stage's grid is sized for "nothing pruned": mostly empty wavefronts, 4 per workgroup to dispatch fewer groups
-                    const char* sfx = last ? "_rest" : "_mid";
-                    // (sorted: the compacted list goes where the first phase's items were -- K1 has consumed them -- and is sorted into items_sorted)
-                    timed(last ? "k0b_remaining" : "k0b_remaining_mid", (uint32_t)l, [&] { launch_k0b_remaining(L.dev, P, X, prev, lw.cand_off.as<uint32_t>(), lw.prune_done.as<uint32_t>(), r0,
-                                                                                                                 srt ? lw.items.p : lw.items_sorted.p, lw.prune_cnt.as<uint32_t>(), S, r1); });
-                    if (srt) timed((std::string("k1_sort_items") + sfx).c_str(), (uint32_t)l, [&] { launch_sort_items(L.dev, slots_s, lw.items.p, lw.items_sorted.p, lw.sort_hist.as<uint32_t>(),
-                                                                                                                      lw.sort_start.as<uint32_t>(), S, lw.prune_cnt.as<uint32_t>()); });
-                    timed((std::string(X.dense ? "k1_dense" : "k1_sparse") + sfx).c_str(), (uint32_t)l, [&] {
-                        launch_k1(L.dev, PB, X, lw.items_sorted.p, srt ? lw.sort_start.as<uint32_t>() + L.n_tiles : lw.prune_cnt.as<uint32_t>(), lw.cand.as<float>(), g, S); });
-                    if (lanes == 2 && last) { k1_done = next_event(); XRL_HIP(hipEventRecord(k1_done, S)); }
-                    // (a middle stage selects among the slots scored so far and renews the done flags; queries finished earlier are skipped: one buffer serves both)
-                    if (last) timed("k2_topk_rest", (uint32_t)l, [&] { launch_k2_topk(L.dev, P, prev, lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>(), lw.cand.as<float>(), oi, ov, oc, os, S,
-                                                                                      0, 0, nullptr, lw.prune_done.as<uint32_t>()); });
-                    else timed("k2_topk_mid", (uint32_t)l, [&] { launch_k2_topk(L.dev, P, prev, lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>(), lw.cand.as<float>(), oi, ov, oc, os, S,
-                                                                                 r1, (uint32_t)L.cand_bound(r1), lw.prune_done.as<uint32_t>(), lw.prune_done.as<uint32_t>(), lw.x_ok.as<uint32_t>()); });
-                    if (o.stats_out && last) {
-                        launch_stats(L.dev, P, X, prev, lw.ncand.as<uint32_t>(), lw.items.p, ws.stats.as<double>() + kStatsPerLayer * l, S, (uint64_t)nrows * J * L.max_tiles_per_parent);
-                        launch_stats(L.dev, PB, X, prev, nullptr, lw.items_sorted.p, ws.stats.as<double>() + kStatsPerLayer * l, S, slots_b);
-                    }
-                }
-                continue;
-            }
-            timed("k0_prolongate", (uint32_t)l, [&] { launch_k0_prolongate(L.dev, P, X, prev, lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>(), lw.items.p, S); });
-            const uint64_t n_slots = (uint64_t)nrows * beam_in[l] * L.max_tiles_per_parent;
-            if (mode != 0) timed("k1_sort_items", (uint32_t)l, [&] { launch_sort_items(L.dev, n_slots, lw.items.p, lw.items_sorted.p, lw.sort_hist.as<uint32_t>(), lw.sort_start.as<uint32_t>(), S); });
-            if (lanes == 2 && k1_done) XRL_HIP(hipStreamWaitEvent(S, k1_done, 0));   // K1 launches take turns across the lanes
-            LayerPlan PU = P; PU.fb_host = nullptr;   // (an unstaged pass's item count is not a feedback sample: a probe's outcome may be pending)
-            timed(X.dense ? "k1_dense" : "k1_sparse", (uint32_t)l, [&] {
-                    launch_k1(L.dev, PU, X, mode == 1 ? lw.items_sorted.p : lw.items.p, mode == 1 ? lw.sort_start.as<uint32_t>() + L.n_tiles : nullptr,
-                              lw.cand.as<float>(), g, S); });
-            if (lanes == 2) { k1_done = next_event(); XRL_HIP(hipEventRecord(k1_done, S)); }
-            timed("k2_topk", (uint32_t)l, [&] { launch_k2_topk(L.dev, P, prev, lw.cand_off.as<uint32_t>(), lw.ncand.as<uint32_t>(), lw.cand.as<float>(), oi, ov, oc, os, S); });
-            if (o.stats_out) launch_stats(L.dev, P, X, prev, lw.ncand.as<uint32_t>(), lw.items.p, ws.stats.as<double>() + kStatsPerLayer * l, S);
-        }
+    for (uint64_t row0 = row_begin; row0 < row_end; row0 += b.nb, ++batch) {
+        const int ln = (int)(batch % (uint64_t)b.lanes);
+        b.begin_batch(m.ws->lane[ln], lane_stream[ln], row0, (uint32_t)std::min<uint64_t>(b.nb, row_end - row0));
+        launch_batch(b);
     }
-    if (lanes == 2) {                                                   // the caller's stream continues after the auxiliary lane
-        hipEvent_t e = next_event();
-        XRL_HIP(hipEventRecord(e, m.aux_stream));
-        XRL_HIP(hipStreamWaitEvent(stream, e, 0));
-    }
+    if (b.lanes == 2) b.chain(m.aux_stream, stream);                    // the caller's stream continues after the auxiliary lane
 
     if (!m.ws_done) XRL_HIP(hipEventCreateWithFlags(&m.ws_done, hipEventDisableTiming));
     XRL_HIP(hipEventRecord(m.ws_done, stream)); m.ws_stream = stream;
 
-    if (o.stats_out) {
-        // per layer (kStatsPerLayer doubles): [0] algorithmic bytes of the reference chunks streamed (8E + 4R + 4(R+1) each,
-        // SURVEY.md 8d), [1] candidates evaluated, [2..7] matched work of the (query, tile) items (launch_stats)
-        XRL_HIP(hipStreamSynchronize(stream));
-        XRL_HIP(hipMemcpy(o.stats_out, ws.stats.p, T * kStatsPerLayer * sizeof(double), hipMemcpyDeviceToHost));
-    } else if (sync) {
-        XRL_HIP(hipStreamSynchronize(stream));
-    }
+    if (o.stats_out || sync) XRL_HIP(hipStreamSynchronize(stream));
+    // per layer (kStatsPerLayer doubles): [0] algorithmic bytes of the reference chunks streamed (8E + 4R + 4(R+1) each,
+    // SURVEY.md 8d), [1] candidates evaluated, [2..7] matched work of the (query, tile) items (launch_stats)
+    if (o.stats_out) XRL_HIP(hipMemcpy(o.stats_out, m.ws->stats.p, T * kStatsPerLayer * sizeof(double), hipMemcpyDeviceToHost));
 }
 
-}  // namespace xrl
-
-namespace xrl {
 void resolve_profile(Model& m) {
     if (m.pending.empty()) return;
     XRL_HIP(hipSetDevice(m.device));
@@ -498,4 +524,5 @@ void resolve_profile(Model& m) {
     }
     m.pending.clear();
 }
+
 }  // namespace xrl
