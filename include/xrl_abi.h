@@ -292,6 +292,10 @@ int xrl_predict_stats(void* model, void* queries, uint32_t beam_size, const char
  *   `offset | (len-1) << 25` per row to ext_out (may be NULL) and returns the padded entry count of the tile. */
 uint32_t xrl_debug_split_chunk(const uint64_t* cum, uint32_t n, uint64_t limit);
 uint64_t xrl_debug_layout_rows(const uint32_t* rptr, uint32_t nrows, int align, uint32_t* ext_out);
+/* Host-only piece of the host ABI: the row batches c_xlinear_predict_{csr,drm}_f32 cuts an X of this shape into at option
+ * "host_batch_mb" (with "host_pipeline" on).  row_ptr[0..rows] for a CSR X, NULL for a dense rows x cols X.  Writes the boundaries
+ * rb[0] = 0 <= ... <= rb[n] = rows to rb_out (at most cap of them; may be NULL) and returns their number n + 1. */
+uint32_t xrl_debug_host_batches(const uint64_t* row_ptr, uint32_t rows, uint32_t cols, int host_batch_mb, uint32_t* rb_out, uint32_t cap);
 
 /* Tuning knobs (benchmark / tests only).  Results never depend on them.
  *   "k1_group"            lanes per (query, tile) item in K1: 0 = auto, else a power of two <= 64

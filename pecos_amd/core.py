@@ -625,6 +625,19 @@ class corelib(object):
         self._check()
         return ext & 0x1FFFFFF, (ext >> 25) + 1, total
 
+    def debug_host_batches(self, indptr, rows, cols, host_batch_mb=12):
+        """Host-only: row-batch boundaries of the pipelined host ABI for a CSR X with this row pointer (``None``: dense rows x cols)."""
+        ptr = None if indptr is None else np.ascontiguousarray(indptr, dtype=np.uint64)
+        fn = self.clib_float32.xrl_debug_host_batches
+        fn.restype = ctypes.c_uint32
+        fn.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
+                       ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32]
+        rb = np.zeros(34, dtype=np.uint32)          # at most 32 batches
+        n = int(fn(None if ptr is None else ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), int(rows), int(cols), int(host_batch_mb),
+                   rb.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(rb)))
+        self._check()
+        return rb[:n].copy()
+
     def profile_enable(self, c_model, on=True):
         self.clib_float32.xrl_profile_enable(c_void_p(c_model), 1 if on else 0)
 

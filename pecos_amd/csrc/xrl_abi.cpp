@@ -1,39 +1,21 @@
-// extern "C" surface of libxrl_amd.so (include/xrl_abi.h).  Every entry point catches all C++
-// exceptions and records them for xrl_last_error(); nothing is ever thrown across the C boundary.
-#include "../../include/xrl_abi.h"
-
+// extern "C" surface of libxrl_amd.so (include/xrl_abi.h): device selection, model load / destruct / attributes, the host-ABI predict
+// wrappers, query handles, device-resident predicts, profile, options and the debug entry points.  The host pipeline behind
+// c_xlinear_predict_* is xrl_host_pipeline.cpp, the single-layer / selected-outputs / inner-product entry points are xrl_single_layer.cpp,
+// the TF-IDF producer is xrl_tfidf_abi.cpp.  Every entry point catches all C++ exceptions and records them for xrl_last_error();
+// nothing is ever thrown across the C boundary.
 #include <algorithm>
-#include <cfloat>
-#include <chrono>
-#include <cmath>
-#include <cstdio>
 #include <cstring>
-#include <functional>
-#include <condition_variable>
 #include <memory>
 #include <mutex>
-#include <atomic>
-#include <thread>
-#include <unordered_map>
 
-#include "xrl_predict.h"
-#include "xrl_tfidf.h"
+#include "xrl_host_pipeline.h"
 
-using namespace xrl;
-
-namespace {
+namespace xrl {
 thread_local std::string g_err;
 thread_local bool g_has_err = false;
 thread_local int g_device = 0;
 
 void set_err(const std::string& s) { g_err = s; g_has_err = true; }
-
-template <class F> void guarded(F&& fn) {
-    g_has_err = false;
-    try { fn(); }
-    catch (const std::exception& e) { set_err(e.what()); }
-    catch (...) { set_err("unknown error"); }
-}
 
 Model* as_model(void* p) {
     if (!p) fail("null model handle");
@@ -48,831 +30,20 @@ void require_gpu() {
         fail("libxrl_amd: no HIP device visible -- this library has no CPU fallback");
 }
 
-void upload_csr(const ScipyCsrF32* X, DevBuf& ptr, DevBuf& idx, DevBuf& val, QueriesDev& d) {
-    if (!X) fail("null X");
-    const uint64_t nnz = X->rows ? X->row_ptr[X->rows] : 0;
-    ptr.upload_raw(X->row_ptr, ((size_t)X->rows + 1) * 8);
-    idx.upload_raw(X->col_idx, nnz * 4);
-    val.upload_raw(X->val, nnz * 4);
-    d.row_ptr = ptr.as<uint64_t>(); d.col_idx = idx.as<uint32_t>(); d.val = val.as<float>();
-    d.rows = X->rows; d.cols = X->cols; d.dense = 0; d.nnz = nnz;
+void upload_x(const HostX& x, DevBuf& ptr, DevBuf& idx, DevBuf& val, QueriesDev& d) {
+    if (!x.given) fail("null X");
+    const uint64_t elems = x.elems();
+    if (x.csr) {
+        ptr.upload_raw(x.row_ptr, ((size_t)x.rows + 1) * 8);
+        idx.upload_raw(x.col_idx, elems * 4);
+    }
+    val.upload_raw(x.val, elems * 4);
+    d.row_ptr = x.csr ? ptr.as<uint64_t>() : nullptr; d.col_idx = x.csr ? idx.as<uint32_t>() : nullptr; d.val = val.as<float>();
+    d.rows = x.rows; d.cols = x.cols; d.dense = x.csr ? 0 : 1; d.nnz = x.csr ? elems : 0;
 }
+}  // namespace xrl
 
-void upload_drm(const ScipyDrmF32* X, DevBuf& val, QueriesDev& d) {
-    if (!X) fail("null X");
-    val.upload_raw(X->val, (size_t)X->rows * X->cols * 4);
-    d.row_ptr = nullptr; d.col_idx = nullptr; d.val = val.as<float>();
-    d.rows = X->rows; d.cols = X->cols; d.dense = 1; d.nnz = 0;
-}
-
-// Host-side worker threads for the bulk copies of the host ABI (staging X into pinned memory, writing the result CSR):
-// one thread moves ~6-10 GB/s, which would make a 300 MB X the slowest stage of the pipeline below.
-// The workers are persistent (creating 16 threads per 32 MB chunk cost as much as the copy itself): a process-wide pool, never
-// destroyed (its threads sleep on a condition variable until the process exits).  One job at a time owns the pool; a caller that
-// finds it busy (the per-device host threads of a multi-device handle) spawns its own threads as before.
-class CopyPool {
-public:
-    static CopyPool& get() { static CopyPool* p = new CopyPool(); return *p; }
-    unsigned size() const { return (unsigned)workers_.size() + 1u; }      // + the calling thread
-    // runs fn(n*i/parts, n*(i+1)/parts) for i in [0, parts) on the workers and the caller; false: the pool is busy, nothing was run
-    bool try_run(size_t n, unsigned parts, const std::function<void(size_t, size_t)>& fn) {
-        std::unique_lock<std::mutex> owner(owner_, std::try_to_lock);
-        if (!owner.owns_lock()) return false;
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            fn_ = &fn; n_ = n; parts_ = parts; next_ = 0; pending_ = parts; err_ = nullptr; ++gen_;
-        }
-        cv_.notify_all();
-        work();
-        std::unique_lock<std::mutex> g(mu_);
-        done_.wait(g, [&] { return pending_ == 0; });
-        fn_ = nullptr;
-        if (err_) std::rethrow_exception(err_);
-        return true;
-    }
-private:
-    CopyPool() {
-        const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-        const unsigned nw = std::min(15u, hw > 1 ? hw - 1 : 0u);
-        for (unsigned i = 0; i < nw; ++i) workers_.emplace_back([this] { loop(); });
-        for (auto& t : workers_) t.detach();
-    }
-    void work() {
-        for (;;) {
-            unsigned i; const std::function<void(size_t, size_t)>* f; size_t n; unsigned parts;
-            {
-                std::lock_guard<std::mutex> g(mu_);
-                if (!fn_ || next_ >= parts_) return;
-                i = next_++; f = fn_; n = n_; parts = parts_;
-            }
-            std::exception_ptr e;
-            try { (*f)(n * i / parts, n * (i + 1) / parts); } catch (...) { e = std::current_exception(); }
-            std::lock_guard<std::mutex> g(mu_);
-            if (e && !err_) err_ = e;
-            if (--pending_ == 0) done_.notify_all();
-        }
-    }
-    void loop() {
-        uint64_t seen = 0;
-        for (;;) {
-            { std::unique_lock<std::mutex> g(mu_); cv_.wait(g, [&] { return gen_ != seen; }); seen = gen_; }
-            work();
-        }
-    }
-    std::vector<std::thread> workers_;
-    std::mutex owner_, mu_;
-    std::condition_variable cv_, done_;
-    const std::function<void(size_t, size_t)>* fn_ = nullptr;
-    size_t n_ = 0; unsigned parts_ = 0, next_ = 0, pending_ = 0; uint64_t gen_ = 0;
-    std::exception_ptr err_;
-};
-
-template <class F> void parallel_ranges(size_t n, size_t min_per_thread, F&& fn) {
-    unsigned nt = (unsigned)std::min<size_t>(16, std::max<size_t>(1, n / std::max<size_t>(1, min_per_thread)));
-    nt = std::min(nt, std::max(1u, std::thread::hardware_concurrency()));
-    if (nt <= 1) { fn((size_t)0, n); return; }
-    {
-        const std::function<void(size_t, size_t)> f = [&](size_t b, size_t e) { fn(b, e); };
-        if (CopyPool::get().try_run(n, nt, f)) return;
-    }
-    std::vector<std::thread> th;
-    std::exception_ptr err; std::mutex emu;
-    for (unsigned t = 0; t < nt; ++t)
-        th.emplace_back([&, t] {
-            try { fn(n * t / nt, n * (t + 1) / nt); }
-            catch (...) { std::lock_guard<std::mutex> g(emu); err = std::current_exception(); }
-        });
-    for (auto& t : th) t.join();
-    if (err) std::rethrow_exception(err);
-}
-void parallel_copy(void* dst, const void* src, size_t bytes) {
-    parallel_ranges(bytes, 1u << 20, [&](size_t b, size_t e) { std::memcpy((char*)dst + b, (const char*)src + b, e - b); });
-}
-// two equally long arrays at once (labels + scores, column ids + values): one set of threads, each takes its share of both
-void parallel_copy2(void* dst0, const void* src0, void* dst1, const void* src1, size_t bytes_each) {
-    parallel_ranges(bytes_each, 512u << 10, [&](size_t b, size_t e) {
-        std::memcpy((char*)dst0 + b, (const char*)src0 + b, e - b);
-        std::memcpy((char*)dst1 + b, (const char*)src1 + b, e - b);
-    });
-}
-
-// XRL_HOST_TIMING=1: one stderr line per host-ABI call with the wall time of every stage of the pipeline (diagnostics only)
-struct HostTimes { double prep = 0, stage = 0, slot_wait = 0, enqueue = 0, final_sync = 0, prefix = 0, alloc = 0, copy_out = 0; };
-static thread_local HostTimes g_ht;
-static bool host_timing() { static const bool on = [] { const char* e = std::getenv("XRL_HOST_TIMING"); return e && e[0] == '1'; }(); return on; }
-static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-// csr_t::create_pycsr, pecos/core/utils/matrix.hpp:300-316: one synchronous allocator call, then copy.
-void emit_csr(uint32_t rows, uint32_t cols, uint32_t stride, const uint32_t* idx, const float* val,
-              const uint32_t* cnt, py_sparse_allocator_t alloc) {
-    double t0 = now_ms();
-    // row lengths -> nnz in P partial sums (the allocator needs nnz first), then the row pointers are written straight into the
-    // allocator's array, every part continuing from its partial sum
-    constexpr size_t P = 16;
-    uint64_t part[P + 1] = {0};
-    parallel_ranges(P, 1, [&](size_t pb, size_t pe) {
-        for (size_t p = pb; p < pe; ++p) {
-            uint64_t s = 0;
-            for (size_t r = (size_t)rows * p / P, re = (size_t)rows * (p + 1) / P; r < re; ++r) s += std::min(cnt[r], stride);
-            part[p + 1] = s;
-        }
-    });
-    for (size_t p = 0; p < P; ++p) part[p + 1] += part[p];
-    const uint64_t nnz = part[P];
-    uint32_t* o_idx = nullptr; uint64_t* o_ptr = nullptr; float* o_val = nullptr;
-    g_ht.prefix += now_ms() - t0; t0 = now_ms();
-    alloc(false, rows, cols, nnz, &o_idx, &o_ptr, &o_val);
-    g_ht.alloc += now_ms() - t0; t0 = now_ms();
-    if (!o_ptr || (nnz && (!o_idx || !o_val))) fail("allocator callback returned null buffers");
-    o_ptr[0] = 0;
-    parallel_ranges(P, 1, [&](size_t pb, size_t pe) {
-        for (size_t p = pb; p < pe; ++p) {
-            uint64_t run = part[p];
-            for (size_t r = (size_t)rows * p / P, re = (size_t)rows * (p + 1) / P; r < re; ++r) { run += std::min(cnt[r], stride); o_ptr[r + 1] = run; }
-        }
-    });
-    if (nnz == (uint64_t)rows * stride) {          // every row full: the fixed-stride buffers ARE the CSR arrays
-        parallel_copy2(o_idx, idx, o_val, val, nnz * 4);
-        g_ht.copy_out += now_ms() - t0;
-        return;
-    }
-    parallel_ranges(rows, 1u << 15, [&](size_t b, size_t e) {
-        for (size_t r = b; r < e; ++r) {
-            const size_t n = (size_t)(o_ptr[r + 1] - o_ptr[r]);
-            std::memcpy(o_idx + o_ptr[r], idx + r * stride, n * 4);
-            std::memcpy(o_val + o_ptr[r], val + r * stride, n * 4);
-        }
-    });
-    g_ht.copy_out += now_ms() - t0;
-}
-
-void reserve_outputs(Model& m, uint32_t rows, uint32_t k) {
-    Workspace& ws = *m.ws;
-    const size_t cells = (size_t)rows * k;
-    ws.out_idx.reserve(cells * 4); ws.out_val.reserve(cells * 4); ws.out_cnt.reserve((size_t)rows * 4);
-    ws.h_idx.reserve(cells * 4); ws.h_val.reserve(cells * 4); ws.h_cnt.reserve((size_t)rows * 4);
-}
-
-// `batch` >= 0: the copies run on the handle's D2H stream behind an event recorded on the compute stream, so that they do not
-// hold up the next batch's kernels (callers finish with sync_downloads); -1: on the compute stream itself.
-void download_rows(Model& m, uint32_t r0, uint32_t r1, uint32_t k, int batch = -1) {
-    Workspace& ws = *m.ws;
-    if (r1 <= r0) return;
-    hipStream_t s = m.stream;
-    if (batch >= 0) {
-        if (!m.d2h_stream) XRL_HIP(hipStreamCreateWithFlags(&m.d2h_stream, hipStreamNonBlocking));
-        while (m.d2h_events.size() <= (size_t)batch) { hipEvent_t e; XRL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); m.d2h_events.push_back(e); }
-        XRL_HIP(hipEventRecord(m.d2h_events[batch], m.stream));
-        XRL_HIP(hipStreamWaitEvent(m.d2h_stream, m.d2h_events[batch], 0));
-        s = m.d2h_stream;
-    }
-    const size_t o = (size_t)r0 * k, n = (size_t)(r1 - r0) * k;
-    XRL_HIP(hipMemcpyAsync(ws.h_idx.as<uint32_t>() + o, ws.out_idx.as<uint32_t>() + o, n * 4, hipMemcpyDeviceToHost, s));
-    XRL_HIP(hipMemcpyAsync(ws.h_val.as<float>() + o, ws.out_val.as<float>() + o, n * 4, hipMemcpyDeviceToHost, s));
-    XRL_HIP(hipMemcpyAsync(ws.h_cnt.as<uint32_t>() + r0, ws.out_cnt.as<uint32_t>() + r0, (size_t)(r1 - r0) * 4, hipMemcpyDeviceToHost, s));
-}
-void sync_downloads(Model& m) {
-    XRL_HIP(hipStreamSynchronize(m.stream));
-    if (m.d2h_stream) XRL_HIP(hipStreamSynchronize(m.d2h_stream));
-}
-
-void run_and_emit(Model& m, const QueriesDev& X, const PredictOpts& o, py_sparse_allocator_t alloc) {
-    Workspace& ws = *m.ws;
-    const Layer& last = *m.layers.back();
-    const uint32_t k = effective_topk(m, o.only_topk);
-    const uint32_t out_cols = last.reordered ? last.c_rows : last.w_cols;   // inference.hpp:1776-1784
-    reserve_outputs(m, X.rows, k);
-    predict_device(m, X, o, ws.out_idx.as<uint32_t>(), ws.out_val.as<float>(), ws.out_cnt.as<uint32_t>(), k, m.stream, false);
-    download_rows(m, 0, X.rows, k);
-    XRL_HIP(hipStreamSynchronize(m.stream));
-    emit_csr(X.rows, out_cols, k, ws.h_idx.as<uint32_t>(), ws.h_val.as<float>(), ws.h_cnt.as<uint32_t>(), alloc);
-}
-
-// The host ABI (c_xlinear_predict_{csr,drm}_f32) hands over PAGEABLE host arrays.  Large inputs are cut into nnz-balanced
-// row batches and pipelined: batch b+1 is copied into pinned staging memory by host threads and travels over PCIe on a copy
-// stream while batch b's kernels run; every batch's results start their way back as soon as its last kernel is queued.
-// The allocator callback is invoked once, synchronously, on the calling thread, after everything has finished
-// (pecos/core/base.py:431-464 discipline).  Small inputs take the single-batch path.
-// Runs the whole host-ABI pipeline of ONE device for the rows of `input_x` and leaves the fixed-stride results in the handle's
-// pinned host buffers (ws.h_idx / h_val / h_cnt, stride k); the caller holds m.mu and emits the CSR afterwards.
-constexpr int kStageSlots = 3;   // == the length of Workspace::stage
-
-// Round 5: the row batches of one call ALTERNATE between two compute streams (the handle's own and its auxiliary one), each with its own
-// set of per-batch scratch buffers (Workspace::lane[0] / lane[1], swapped into place around the predict_device call) and its own
-// "scratch in use until" event.  A row batch of 30-60 k queries ends in a tail of latency-bound wavefronts (the query-stationary kernel runs
-// ~8 rounds of 67 us at that size); on one stream the next batch's first kernel waits for that tail, on two it fills the CUs the tail
-// leaves idle.  Batches write disjoint rows of the result buffers; the uploads they wait for are ordered by the copy stream's events as
-// before.  XRL_HOST_STREAMS=1 restores the single compute stream.
-// The lanes' events live in the handle (Model::host_lanes): they are destroyed with it, on its device.
-static int host_streams() {
-    static const int n = [] { const char* e = std::getenv("XRL_HOST_STREAMS"); return (e && e[0] == '1') ? 1 : 2; }();
-    return n;
-}
-
-template <class XT>
-void host_compute(Model& m, const XT* input_x, PredictOpts o, bool is_csr) {
-    use_device(m.device);
-    if (!m.ws) m.ws = std::make_unique<Workspace>();
-    Workspace& ws = *m.ws;
-    double t_ph = now_ms();
-    const ScipyCsrF32* Xs = is_csr ? reinterpret_cast<const ScipyCsrF32*>(input_x) : nullptr;
-    const ScipyDrmF32* Xd = is_csr ? nullptr : reinterpret_cast<const ScipyDrmF32*>(input_x);
-    const uint32_t rows = is_csr ? Xs->rows : Xd->rows;
-    const uint64_t elems = is_csr ? (rows ? Xs->row_ptr[rows] : 0) : (uint64_t)rows * Xd->cols;
-    const uint64_t bytes = elems * (is_csr ? 8u : 4u);
-    // compute batches: CSR -- ~24 MB of nnz each (the kernels' cost follows nnz); dense -- at least 64 k rows each, because the
-    // tiled SGEMM K1G needs many queries per parent (a 24 MB batch of 768-float rows would leave ~10 per leaf parent and fall
-    // back to the query-stationary kernel, 5x slower).  The upload itself always moves in <= 32 MB chunks through two pinned
-    // staging buffers, whatever the batch size.
-    const bool staged = m.opt.host_pipeline && bytes >= (32ull << 20);
-    // CSR: batches GROW (x1.6 from a third of host_batch_mb up to 3x host_batch_mb): the first kernels start after a few megabytes have
-    // arrived, the later launches are large enough to fill the chip (a 40 k-row launch of the query-stationary kernel runs at 0.7x
-    // the per-row rate of a 490 k-row one: measured with rocprofv3's copy + kernel trace, profiles/r03_pruning_topk.md section 4)
-    std::vector<uint64_t> share;                                        // cumulative element targets of the batch ends
-    if (staged && rows >= 8192) {
-        if (is_csr) {
-            const double mb = (double)(1u << 20) / 8.0;                    // elements per megabyte of (id, value) pairs
-            double cur = std::max(1, m.opt.host_batch_mb) / 3.0, pos = 0.0;
-            const double cap = 3.0 * std::max(1, m.opt.host_batch_mb);
-            while (pos + cur * mb < (double)elems && share.size() < 31) { pos += cur * mb; share.push_back((uint64_t)pos); cur = std::min(cap, cur * 1.6); }
-            // a short last batch joins the previous one (the tail after the upload ends is one launch either way)
-            // (round 5 tried a TAPERED end -- last two batches of host_batch_mb and half of it, to shorten the tail after the last byte of X has
-            //  arrived: 9.57 -> 9.06 ms on Amazon-670K but 18.5 -> 19.2 ms on the hard workload, and the extra batches shift the pruning feedback's
-            //  re-probe cadence; not kept: profiles/r05_host_abi.md)
-            if (!share.empty() && (double)elems - (double)share.back() < 0.25 * cur * mb) share.pop_back();
-        } else {
-            const uint32_t nb = (uint32_t)std::min<uint64_t>(8, std::max<uint64_t>(1, rows / 65536u));
-            for (uint32_t b = 1; b < nb; ++b) share.push_back(elems * b / nb);
-        }
-    }
-    const uint32_t n_batch = (uint32_t)share.size() + 1;
-    QueriesDev X{};
-    if (!staged) {
-        if (is_csr) upload_csr(Xs, ws.x_ptr, ws.x_idx, ws.x_val, X);
-        else upload_drm(Xd, ws.x_val, X);
-        const uint32_t k1 = effective_topk(m, o.only_topk);
-        reserve_outputs(m, X.rows, k1);
-        predict_device(m, X, o, ws.out_idx.as<uint32_t>(), ws.out_val.as<float>(), ws.out_cnt.as<uint32_t>(), k1, m.stream, false);
-        download_rows(m, 0, X.rows, k1);
-        XRL_HIP(hipStreamSynchronize(m.stream));
-        return;
-    }
-    // ---- batch boundaries: equal shares of the elements (CSR: of the nnz -- cost follows nnz, not rows)
-    std::vector<uint32_t> rb(n_batch + 1, rows);
-    rb[0] = 0;
-    for (uint32_t b = 1; b < n_batch; ++b) {
-        if (is_csr) rb[b] = (uint32_t)(std::lower_bound(Xs->row_ptr, Xs->row_ptr + rows + 1, share[b - 1]) - Xs->row_ptr);
-        else rb[b] = (uint32_t)((uint64_t)rows * b / n_batch);
-        rb[b] = std::min(std::max(rb[b], rb[b - 1]), rows);
-    }
-    auto elem_at = [&](uint32_t r) -> uint64_t { return is_csr ? Xs->row_ptr[r] : (uint64_t)r * Xd->cols; };
-    uint64_t max_elems = 0;
-    for (uint32_t b = 0; b < n_batch; ++b) max_elems = std::max(max_elems, elem_at(rb[b + 1]) - elem_at(rb[b]));
-    double t_fine = now_ms();
-    auto fine = [&](const char* what) {   // (diagnostics, XRL_HOST_TIMING=1: which step of the preparation took long)
-        if (host_timing() && now_ms() - t_fine > 1.0) std::fprintf(stderr, "[xrl host]   prep: %s took %.2f ms\n", what, now_ms() - t_fine);
-        t_fine = now_ms();
-    };
-    fine("batch planning");
-    if (is_csr) {
-        // the row pointer travels like the rest of X: through pinned staging, first on the copy stream (every row batch waits for a later event of that
-        // stream).  A synchronous hipMemcpy from the caller's pageable array took 14-26 ms in the SECOND call of a process (the runtime pins the region it
-        // sees again), 0.1 ms otherwise.
-        {
-            const size_t pb = ((size_t)rows + 1) * 8;
-            ws.x_ptr.reserve(pb); ws.stage_ptr.reserve(pb);
-            if (!m.copy_stream) XRL_HIP(hipStreamCreateWithFlags(&m.copy_stream, hipStreamNonBlocking));
-            parallel_copy(ws.stage_ptr.p, Xs->row_ptr, pb);
-            XRL_HIP(hipMemcpyAsync(ws.x_ptr.p, ws.stage_ptr.p, pb, hipMemcpyHostToDevice, m.copy_stream));
-        }
-        fine("row-pointer upload (pinned staging, copy stream)");
-        ws.x_idx.reserve(elems * 4); ws.x_val.reserve(elems * 4);
-        X.row_ptr = ws.x_ptr.as<uint64_t>(); X.col_idx = ws.x_idx.as<uint32_t>(); X.val = ws.x_val.as<float>();
-        X.rows = rows; X.cols = Xs->cols; X.dense = 0; X.nnz = elems;
-    } else {
-        ws.x_val.reserve(elems * 4);
-        X.row_ptr = nullptr; X.col_idx = nullptr; X.val = ws.x_val.as<float>();
-        X.rows = rows; X.cols = Xd->cols; X.dense = 1; X.nnz = 0;
-    }
-    for (uint32_t b = 0; b < n_batch; ++b) o.reserve_rows = std::max(o.reserve_rows, rb[b + 1] - rb[b]);
-    const uint64_t chunk_elems = (32ull << 20) / (is_csr ? 8u : 4u);      // elements per staged upload chunk
-    fine("device arrays of X");
-    for (int s2 = 0; s2 < kStageSlots; ++s2) ws.stage[s2].reserve(std::min(max_elems, chunk_elems) * (is_csr ? 8u : 4u));
-    fine("pinned staging ring");
-    if (!m.copy_stream) XRL_HIP(hipStreamCreateWithFlags(&m.copy_stream, hipStreamNonBlocking));
-    hipEvent_t up[kStageSlots];
-    for (auto& e : up) XRL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (is_csr) {   // the compute streams start after the row pointer has arrived (matters only when X holds no element: no chunk event would order them)
-        XRL_HIP(hipEventRecord(up[0], m.copy_stream));
-        XRL_HIP(hipStreamWaitEvent(m.stream, up[0], 0));
-        if (m.aux_stream) XRL_HIP(hipStreamWaitEvent(m.aux_stream, up[0], 0));
-    }
-    fine("copy stream + events");
-    const uint32_t k = effective_topk(m, o.only_topk);
-    reserve_outputs(m, rows, k);
-    fine("result buffers (device + pinned host)");
-    // option host_register: page-lock the caller's arrays in place for the duration of the call and let the copy engine read them
-    // directly (no staging memcpy); falls back to staging when the registration fails
-    bool reg_idx = false, reg_val = false;
-    if (m.opt.host_register) {
-        if (is_csr) {
-            reg_idx = hipHostRegister(const_cast<uint32_t*>(Xs->col_idx), elems * 4, hipHostRegisterDefault) == hipSuccess;
-            reg_val = reg_idx && hipHostRegister(const_cast<float*>(Xs->val), elems * 4, hipHostRegisterDefault) == hipSuccess;
-            if (reg_idx && !reg_val) { (void)hipHostUnregister(const_cast<uint32_t*>(Xs->col_idx)); reg_idx = false; }
-        } else {
-            reg_val = hipHostRegister(const_cast<float*>(Xd->val), elems * 4, hipHostRegisterDefault) == hipSuccess;
-        }
-        (void)hipGetLastError();
-    }
-    const bool direct = reg_val;
-    auto unregister = [&] {
-        if (reg_idx) (void)hipHostUnregister(const_cast<uint32_t*>(Xs->col_idx));
-        if (reg_val) (void)hipHostUnregister(const_cast<float*>(is_csr ? Xs->val : Xd->val));
-        reg_idx = reg_val = false;
-    };
-    // two compute lanes for the row batches (see HostLanes above); the handle's lock is held by the caller
-    // (overlap_min_rows > 0 makes predict_device itself run two lanes over ws.lane[0 / 1] and the auxiliary stream: the two schemes would share
-    //  scratch and stream without an ordering between them, so the host lanes stand down -- ADVICE r5)
-    const bool two = host_streams() == 2 && n_batch >= 3 && !m.profiling && m.opt.overlap_min_rows == 0;
-    Model::HostLanes* hl = &m.host_lanes;
-    g_ht.prep += now_ms() - t_ph;
-    try {
-        if (two) {
-            if (!m.aux_stream) XRL_HIP(hipStreamCreateWithFlags(&m.aux_stream, hipStreamNonBlocking));
-            if (!hl->join) XRL_HIP(hipEventCreateWithFlags(&hl->join, hipEventDisableTiming));
-            hl->done[0] = m.ws_done; hl->strm[0] = m.ws_stream;              // lane 0 = the handle's own bookkeeping; lane 1 keeps its event between calls
-            // the auxiliary lane starts after everything queued on the handle's stream so far (an earlier asynchronous predict may still use the scratch)
-            XRL_HIP(hipEventRecord(hl->join, m.stream));
-            XRL_HIP(hipStreamWaitEvent(m.aux_stream, hl->join, 0));
-        }
-        uint64_t chunk = 0;                                                 // staged chunks so far: slot = chunk & 1
-        for (uint32_t b = 0; b < n_batch; ++b) {
-            const uint64_t e0 = elem_at(rb[b]), e1 = elem_at(rb[b + 1]);
-            int last_slot = -1;
-            for (uint64_t c0 = e0; c0 < e1; c0 += chunk_elems, ++chunk) {
-                const int slot = (int)(chunk % (uint64_t)kStageSlots);
-                const uint64_t n = std::min(chunk_elems, e1 - c0);
-                if (direct) {
-                    if (is_csr) {
-                        XRL_HIP(hipMemcpyAsync(ws.x_idx.as<uint32_t>() + c0, Xs->col_idx + c0, n * 4, hipMemcpyHostToDevice, m.copy_stream));
-                        XRL_HIP(hipMemcpyAsync(ws.x_val.as<float>() + c0, Xs->val + c0, n * 4, hipMemcpyHostToDevice, m.copy_stream));
-                    } else {
-                        XRL_HIP(hipMemcpyAsync(ws.x_val.as<float>() + c0, Xd->val + c0, n * 4, hipMemcpyHostToDevice, m.copy_stream));
-                    }
-                    XRL_HIP(hipEventRecord(up[slot], m.copy_stream));
-                    last_slot = slot;
-                    continue;
-                }
-                t_ph = now_ms();
-                if (chunk >= (uint64_t)kStageSlots) XRL_HIP(hipEventSynchronize(up[slot]));    // the slot's previous upload has left the staging buffer
-                g_ht.slot_wait += now_ms() - t_ph; t_ph = now_ms();
-                char* st = ws.stage[slot].as<char>();
-                if (is_csr) {
-                    parallel_copy2(st, Xs->col_idx + c0, st + n * 4, Xs->val + c0, n * 4);
-                    XRL_HIP(hipMemcpyAsync(ws.x_idx.as<uint32_t>() + c0, st, n * 4, hipMemcpyHostToDevice, m.copy_stream));
-                    XRL_HIP(hipMemcpyAsync(ws.x_val.as<float>() + c0, st + n * 4, n * 4, hipMemcpyHostToDevice, m.copy_stream));
-                } else {
-                    parallel_copy(st, Xd->val + c0, n * 4);
-                    XRL_HIP(hipMemcpyAsync(ws.x_val.as<float>() + c0, st, n * 4, hipMemcpyHostToDevice, m.copy_stream));
-                }
-                XRL_HIP(hipEventRecord(up[slot], m.copy_stream));
-                last_slot = slot;
-                g_ht.stage += now_ms() - t_ph;
-            }
-            t_ph = now_ms();
-            const int L = two ? (int)(b & 1u) : 0;
-            hipStream_t S = L ? m.aux_stream : m.stream;
-            if (last_slot >= 0) XRL_HIP(hipStreamWaitEvent(S, up[last_slot], 0));   // batch b's kernels start when its rows have arrived (the copy stream is in order)
-            if (rb[b + 1] > rb[b]) {
-                if (two) {                                               // this lane's scratch and its "in use until" event into place
-                    if (L) std::swap(ws.lane[0], ws.lane[1]);
-                    m.ws_done = hl->done[L]; m.ws_stream = hl->strm[L];
-                }
-                try {
-                    const double t_pd = now_ms();
-                    predict_device(m, X, o, ws.out_idx.as<uint32_t>(), ws.out_val.as<float>(), ws.out_cnt.as<uint32_t>(), k, S, false,
-                                   rb[b], rb[b + 1] - rb[b]);
-                    if (host_timing() && now_ms() - t_pd > 0.5)      // (diagnostics: a launch sequence that blocked -- an allocation, a code-object load)
-                        std::fprintf(stderr, "[xrl host]   batch %u/%u (%u rows, lane %d): enqueue took %.2f ms\n", b, n_batch, rb[b + 1] - rb[b], L, now_ms() - t_pd);
-                } catch (...) {
-                    if (two) { hl->done[L] = m.ws_done; hl->strm[L] = m.ws_stream; if (L) std::swap(ws.lane[0], ws.lane[1]); m.ws_done = hl->done[0]; m.ws_stream = hl->strm[0]; }
-                    throw;
-                }
-                if (two) { hl->done[L] = m.ws_done; hl->strm[L] = m.ws_stream; if (L) std::swap(ws.lane[0], ws.lane[1]); }
-            }
-            // results: everything but the last batch goes back in ONE set of copies on the D2H stream, queued before the last batch's
-            // kernels (per-batch copies are blit kernels that held up the next batch's launch: 12 x 0.15 ms); the last batch follows
-            // on its compute stream
-            if (b + 2 == n_batch) {
-                if (two) {                                               // the copies wait for BOTH lanes' batches (download_rows adds the handle's stream)
-                    if (!m.d2h_stream) XRL_HIP(hipStreamCreateWithFlags(&m.d2h_stream, hipStreamNonBlocking));
-                    XRL_HIP(hipEventRecord(hl->join, m.aux_stream));
-                    XRL_HIP(hipStreamWaitEvent(m.d2h_stream, hl->join, 0));
-                }
-                const double t_dl = now_ms();
-                download_rows(m, 0, rb[b + 1], k, 0);
-                if (host_timing() && now_ms() - t_dl > 0.5) std::fprintf(stderr, "[xrl host]   download of rows [0, %u): enqueue took %.2f ms\n", rb[b + 1], now_ms() - t_dl);
-            } else if (b + 1 == n_batch) {
-                if (two && L) {                                          // the last batch ran on the auxiliary stream: its copies follow on the handle's stream
-                    XRL_HIP(hipEventRecord(hl->join, m.aux_stream));
-                    XRL_HIP(hipStreamWaitEvent(m.stream, hl->join, 0));
-                }
-                const double t_dl = now_ms();
-                download_rows(m, n_batch > 1 ? rb[b] : 0, rb[b + 1], k, 1);    // (on the D2H stream behind an event, like the rest: queued on the compute stream itself the copies blocked the enqueuing thread for 5-9 ms in a process's first two calls)
-                if (host_timing() && now_ms() - t_dl > 0.5) std::fprintf(stderr, "[xrl host]   download of the last batch: enqueue took %.2f ms\n", now_ms() - t_dl);
-            }
-            g_ht.enqueue += now_ms() - t_ph;
-        }
-        t_ph = now_ms();
-        if (two) XRL_HIP(hipStreamSynchronize(m.aux_stream));
-        sync_downloads(m);
-        if (two) { m.ws_done = hl->done[0]; m.ws_stream = hl->strm[0]; }
-        g_ht.final_sync += now_ms() - t_ph;
-    } catch (...) {
-        (void)hipStreamSynchronize(m.copy_stream); (void)hipStreamSynchronize(m.stream);
-        if (two) { (void)hipStreamSynchronize(m.aux_stream); m.ws_done = hl->done[0]; m.ws_stream = hl->strm[0]; }
-        if (m.d2h_stream) (void)hipStreamSynchronize(m.d2h_stream);
-        for (auto& e : up) (void)hipEventDestroy(e);
-        unregister();
-        throw;
-    }
-    for (auto& e : up) (void)hipEventDestroy(e);
-    unregister();
-}
-
-// csr_t::create_pycsr over the row shards of several devices: ONE synchronous allocator call on the calling thread, then every
-// shard's fixed-stride rows are copied to their place
-struct ShardOut { uint32_t r0, r1; const uint32_t* idx; const float* val; const uint32_t* cnt; };
-void emit_csr_shards(uint32_t rows, uint32_t cols, uint32_t stride, const std::vector<ShardOut>& sh, py_sparse_allocator_t alloc) {
-    // like emit_csr: nnz from partial sums (one per shard), then the row pointers are written straight into the allocator's array, every
-    // shard continuing from its partial sum, and all shards' rows are copied by one parallel pass over the global rows
-    double t0 = now_ms();
-    const size_t S = sh.size();
-    std::vector<uint64_t> part(S + 1, 0);
-    parallel_ranges(S, 1, [&](size_t sb, size_t se) {
-        for (size_t i = sb; i < se; ++i) { uint64_t a = 0; const ShardOut& s = sh[i]; for (uint32_t r = s.r0; r < s.r1; ++r) a += std::min(s.cnt[r - s.r0], stride); part[i + 1] = a; }
-    });
-    for (size_t i = 0; i < S; ++i) part[i + 1] += part[i];
-    const uint64_t nnz = part[S];
-    uint32_t* o_idx = nullptr; uint64_t* o_ptr = nullptr; float* o_val = nullptr;
-    g_ht.prefix += now_ms() - t0; t0 = now_ms();
-    alloc(false, rows, cols, nnz, &o_idx, &o_ptr, &o_val);
-    g_ht.alloc += now_ms() - t0; t0 = now_ms();
-    if (!o_ptr || (nnz && (!o_idx || !o_val))) fail("allocator callback returned null buffers");
-    o_ptr[0] = 0;
-    parallel_ranges(S, 1, [&](size_t sb, size_t se) {
-        for (size_t i = sb; i < se; ++i) { uint64_t run = part[i]; const ShardOut& s = sh[i]; for (uint32_t r = s.r0; r < s.r1; ++r) { run += std::min(s.cnt[r - s.r0], stride); o_ptr[r + 1] = run; } }
-    });
-    // shard of a global row: the shards are contiguous and ordered
-    std::vector<uint32_t> first(S);
-    for (size_t i = 0; i < S; ++i) first[i] = sh[i].r0;
-    parallel_ranges(rows, 1u << 15, [&](size_t b, size_t e) {
-        size_t i = (size_t)(std::upper_bound(first.begin(), first.end(), (uint32_t)b) - first.begin()) - 1;
-        for (size_t g = b; g < e; ++g) {
-            while (i + 1 < S && g >= sh[i + 1].r0) ++i;
-            const ShardOut& s = sh[i];
-            const size_t r = g - s.r0, n = (size_t)(o_ptr[g + 1] - o_ptr[g]);
-            std::memcpy(o_idx + o_ptr[g], s.idx + r * stride, n * 4);
-            std::memcpy(o_val + o_ptr[g], s.val + r * stride, n * 4);
-        }
-    });
-    g_ht.copy_out += now_ms() - t0;
-}
-
-// c_xlinear_predict_{csr,drm}_f32.  With replicas behind the handle (xrl_set_option "devices"): the rows are cut into nnz-balanced
-// shards, one host thread per device runs the single-device pipeline above on its shard (its own stream, pinned staging and PCIe
-// link; no inter-GPU traffic), and the results of all shards go into the arrays of the one allocator call.
-template <class XT>
-void predict_host(void* ptr, const XT* input_x, uint32_t beam, const char* pp, uint32_t topk,
-                  py_sparse_allocator_t alloc, bool is_csr) {
-    Model& m = *as_model(ptr);
-    if (!alloc) fail("null allocator callback");
-    if (!input_x) fail("null X");
-    std::lock_guard<std::mutex> g(m.mu);
-    PredictOpts o; o.beam_size = beam; o.only_topk = topk; o.post_processor = pp;
-    const ScipyCsrF32* Xs = is_csr ? reinterpret_cast<const ScipyCsrF32*>(input_x) : nullptr;
-    const ScipyDrmF32* Xd = is_csr ? nullptr : reinterpret_cast<const ScipyDrmF32*>(input_x);
-    const uint32_t rows = is_csr ? Xs->rows : Xd->rows;
-    const Layer& last = *m.layers.back();
-    const uint32_t out_cols = last.reordered ? last.c_rows : last.w_cols;
-    const uint32_t k = effective_topk(m, o.only_topk);
-    const size_t R = 1 + m.replicas.size();
-    if (R == 1 || rows < 2 * R) {
-        const double t_call = now_ms();
-        g_ht = HostTimes{};
-        host_compute(m, input_x, o, is_csr);
-        Workspace& ws = *m.ws;
-        emit_csr(rows, out_cols, k, ws.h_idx.as<uint32_t>(), ws.h_val.as<float>(), ws.h_cnt.as<uint32_t>(), alloc);
-        if (host_timing())
-            std::fprintf(stderr, "[xrl host] rows=%u total=%.2f ms: prep %.2f | stage-memcpy+h2d-enqueue %.2f | wait for a staging slot %.2f | kernel+d2h enqueue %.2f | "
-                                 "final sync %.2f | row-pointer prefix %.2f | allocator callback %.2f | copy out %.2f\n",
-                         rows, now_ms() - t_call, g_ht.prep, g_ht.stage, g_ht.slot_wait, g_ht.enqueue, g_ht.final_sync, g_ht.prefix, g_ht.alloc, g_ht.copy_out);
-        return;
-    }
-    // ---- shard boundaries: equal shares of the nnz (+1 per row so that empty rows still count); dense X: equal rows
-    std::vector<uint32_t> sb(R + 1, rows);
-    sb[0] = 0;
-    for (size_t d = 1; d < R; ++d) {
-        if (is_csr) {
-            const uint64_t total = Xs->row_ptr[rows] + rows, want = total * d / R;
-            uint32_t lo = sb[d - 1], hi = rows;                          // first row r with row_ptr[r] + r >= want
-            while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (Xs->row_ptr[mid] + mid < want) lo = mid + 1; else hi = mid; }
-            sb[d] = lo;
-        } else sb[d] = (uint32_t)((uint64_t)rows * d / R);
-    }
-    std::vector<std::exception_ptr> errs(R);
-    std::vector<std::vector<uint64_t>> rebased(R);
-    auto work = [&](size_t d) {
-        try {
-            Model& md = d == 0 ? m : *m.replicas[d - 1];
-            std::unique_lock<std::mutex> lk(md.mu, std::defer_lock);
-            if (d != 0) lk.lock();
-            const uint32_t r0 = sb[d], r1 = sb[d + 1];
-            if (r1 <= r0) return;
-            if (is_csr) {
-                const uint64_t e0 = Xs->row_ptr[r0];
-                rebased[d].resize((size_t)(r1 - r0) + 1);
-                for (uint32_t r = r0; r <= r1; ++r) rebased[d][r - r0] = Xs->row_ptr[r] - e0;
-                ScipyCsrF32 v = *Xs;
-                v.rows = r1 - r0; v.row_ptr = rebased[d].data(); v.col_idx = Xs->col_idx + e0; v.val = Xs->val + e0;
-                host_compute(md, &v, o, true);
-            } else {
-                ScipyDrmF32 v = *Xd;
-                v.rows = r1 - r0; v.val = Xd->val + (size_t)r0 * Xd->cols;
-                host_compute(md, &v, o, false);
-            }
-        } catch (...) { errs[d] = std::current_exception(); }
-    };
-    std::vector<std::thread> th;
-    for (size_t d = 1; d < R; ++d) th.emplace_back(work, d);
-    work(0);
-    for (auto& t : th) t.join();
-    use_device(m.device);
-    for (auto& e : errs) if (e) std::rethrow_exception(e);
-    std::vector<ShardOut> sh;
-    for (size_t d = 0; d < R; ++d) {
-        if (sb[d + 1] <= sb[d]) continue;
-        Workspace& ws = *(d == 0 ? m : *m.replicas[d - 1]).ws;
-        sh.push_back(ShardOut{sb[d], sb[d + 1], ws.h_idx.as<uint32_t>(), ws.h_val.as<float>(), ws.h_cnt.as<uint32_t>()});
-    }
-    g_ht = HostTimes{};                                       // (the shards' pipelines ran on their own threads: only the shared tail is timed here)
-    const double t_emit = now_ms();
-    emit_csr_shards(rows, out_cols, k, sh, alloc);
-    if (host_timing())
-        std::fprintf(stderr, "[xrl host] rows=%u devices=%zu: result hand-off %.2f ms: row-pointer prefix %.2f | allocator callback %.2f | copy out %.2f\n",
-                     rows, R, now_ms() - t_emit, g_ht.prefix, g_ht.alloc, g_ht.copy_out);
-}
-
-HostCsc host_csc(const ScipyCscF32* M, const char* what) {
-    if (!M) fail(std::string("null ") + what);
-    HostCsc h; h.rows = M->rows; h.cols = M->cols;
-    h.col_ptr.assign(M->col_ptr, M->col_ptr + M->cols + 1);
-    const uint64_t nnz = h.col_ptr.back();
-    h.row_idx.assign(M->row_idx, M->row_idx + nnz);
-    h.val.assign(M->val, M->val + nnz);
-    return h;
-}
-
-std::unique_ptr<Model> model_from_arrays(uint32_t depth, const ScipyCscF32* const* W, const ScipyCscF32* const* C,
-                                         const float* bias, const uint32_t* only_topk, const char* const* pp, bool csc_route = false) {
-    auto m = std::make_unique<Model>();
-    m->csc_route = csc_route;
-    if (csc_route) m->weight_matrix_type = 0;
-    m->device = g_device;
-    for (uint32_t d = 0; d < depth; ++d) {
-        HostCsc w = host_csc(W[d], "W");
-        HostCsc c;
-        if (C && C[d]) c = host_csc(C[d], "C");
-        else {
-            c.rows = w.cols; c.cols = 1; c.col_ptr = {0, w.cols};
-            c.row_idx.resize(w.cols); c.val.assign(w.cols, 1.f);
-            for (uint32_t i = 0; i < w.cols; ++i) c.row_idx[i] = i;
-        }
-        m->layers.push_back(compile_layer(w, c, bias[d], only_topk[d], pp[d] ? pp[d] : "noop", nullptr, 0, csc_route));
-        m->layers.back()->w_host = std::make_shared<HostCsc>(std::move(w));
-    }
-    finalize_model(*m);
-    return m;
-}
-
-// ---- single-layer API (libpecos.cpp:201-274): the reference builds a temporary MLModel<csc_t> around the caller's W / C
-// on every call.  Here the compiled one-layer handle (tree bookkeeping + W in CSC form on the device) is CACHED, keyed
-// by the identity of the caller's arrays (pointers, shapes, nnz, bias) plus a fingerprint of their contents, so that
-// loops which call the layer again and again with the same weights -- MAN negative mining (xmc/base.py:1562-1563), the
-// matcher -> ranker hand-off -- pay the compile + upload once.  The fingerprint covers every byte of W and C, so an in-place
-// edit is seen on the next call; xrl_single_layer_cache_clear() drops every entry (frees the device copies).
-struct SlKey {
-    // identity of the caller's VALUE arrays (the reference's Python binding hands over W.data / C.data as they are, while
-    // the index arrays are re-cast to u32 / u64 copies on every call, pecos/core/base.py:235-239), shapes, nnz, bias,
-    // and a fingerprint of the contents of all arrays
-    const void *wv, *cv;
-    uint32_t wr, wc, cr, cc; uint64_t wnnz, cnnz; float bias; uint64_t fp; int device;
-    bool operator==(const SlKey& o) const {
-        return wv == o.wv && cv == o.cv && wr == o.wr && wc == o.wc && cr == o.cr &&
-               cc == o.cc && wnnz == o.wnnz && cnnz == o.cnnz && bias == o.bias && fp == o.fp && device == o.device;
-    }
-};
-struct SlEntry { SlKey key; std::shared_ptr<Model> model; uint64_t stamp; };
-std::mutex g_sl_mu;
-std::vector<SlEntry> g_sl_cache;
-uint64_t g_sl_clock = 0, g_sl_hits = 0, g_sl_misses = 0;
-constexpr size_t kSlCacheCap = 8;
-
-uint64_t fingerprint(uint64_t h, const void* data, size_t elems, size_t elem_bytes) {
-    // 64-bit hash of EVERY byte (four independent multiply-xorshift lanes over 8-byte words, ~10 GB/s on one core): an in-place
-    // edit of W / C anywhere, or a different matrix of the same shape at the same address, changes the key -- cheap next to the
-    // compile + upload a hit saves
-    const unsigned char* p = static_cast<const unsigned char*>(data);
-    size_t n = elems * elem_bytes;
-    if (!p || !n) return h ^ 0x9E3779B97F4A7C15ull;
-    uint64_t l[4] = {h ^ 0x243F6A8885A308D3ull, h ^ 0x13198A2E03707344ull, h ^ 0xA4093822299F31D0ull, h ^ 0x082EFA98EC4E6C89ull};
-    auto mix = [](uint64_t a, uint64_t w) { a = (a ^ w) * 0x9FB21C651E98DF25ull; return a ^ (a >> 29); };
-    while (n >= 32) {
-        uint64_t w[4]; std::memcpy(w, p, 32);
-        l[0] = mix(l[0], w[0]); l[1] = mix(l[1], w[1]); l[2] = mix(l[2], w[2]); l[3] = mix(l[3], w[3]);
-        p += 32; n -= 32;
-    }
-    uint64_t tail[4] = {0, 0, 0, 0}; std::memcpy(tail, p, n);
-    for (int i = 0; i < 4; ++i) l[i] = mix(l[i], tail[i] + n);
-    return mix(mix(mix(l[0], l[1]), l[2]), l[3]) ^ (uint64_t)(elems * elem_bytes);
-}
-
-std::shared_ptr<Model> single_layer_model(const ScipyCscF32* W, const ScipyCscF32* C, float bias) {
-    if (!W) fail("null W");
-    SlKey k{};
-    k.wv = W->val; k.wr = W->rows; k.wc = W->cols; k.wnnz = W->cols ? W->col_ptr[W->cols] : 0;
-    k.cv = C ? (const void*)C->val : nullptr;
-    k.cr = C ? C->rows : 0; k.cc = C ? C->cols : 0; k.cnnz = (C && C->cols) ? C->col_ptr[C->cols] : 0;
-    k.bias = bias; k.device = g_device;
-    uint64_t h = 1469598103934665603ull;
-    h = fingerprint(h, W->col_ptr, (size_t)W->cols + 1, 8);
-    h = fingerprint(h, W->row_idx, k.wnnz, 4);
-    h = fingerprint(h, W->val, k.wnnz, 4);
-    if (C) { h = fingerprint(h, C->col_ptr, (size_t)C->cols + 1, 8); h = fingerprint(h, C->row_idx, k.cnnz, 4); h = fingerprint(h, C->val, k.cnnz, 4); }
-    k.fp = h;
-    {
-        std::lock_guard<std::mutex> g(g_sl_mu);
-        for (auto& e : g_sl_cache) if (e.key == k) { e.stamp = ++g_sl_clock; ++g_sl_hits; return e.model; }
-        ++g_sl_misses;
-    }
-    const ScipyCscF32* Wp = W; const ScipyCscF32* Cp = C;
-    const uint32_t topk = 0; const char* pps = "noop";     // per call: only_topk and the post-processor arrive through PredictOpts
-    std::shared_ptr<Model> m = model_from_arrays(1, &Wp, &Cp, &bias, &topk, &pps, /*csc_route=*/true);
-    m->ws = std::make_unique<Workspace>();
-    ensure_device_csc(*m->layers[0]);
-    std::lock_guard<std::mutex> g(g_sl_mu);
-    if (g_sl_cache.size() >= kSlCacheCap) {
-        size_t victim = 0;
-        for (size_t i = 1; i < g_sl_cache.size(); ++i) if (g_sl_cache[i].stamp < g_sl_cache[victim].stamp) victim = i;
-        g_sl_cache.erase(g_sl_cache.begin() + victim);
-    }
-    g_sl_cache.push_back(SlEntry{k, m, ++g_sl_clock});
-    return m;
-}
-
-template <class XT>
-void single_layer_predict(const XT* input_x, bool is_csr, const ScipyCsrF32* csr_codes, ScipyCscF32* W, ScipyCscF32* C,
-                          const char* pp, uint32_t only_topk, float bias, py_sparse_allocator_t alloc) {
-    // libpecos.cpp:201-235: MLModel<csc_t> around caller-owned W / C -> the CSC arithmetic (K1C), bit for bit
-    require_gpu();
-    use_device(g_device);
-    if (!alloc) fail("null allocator callback");
-    const char* pps = pp ? pp : "noop";
-    std::shared_ptr<Model> mp = single_layer_model(W, C, bias);
-    Model& m = *mp;
-    std::lock_guard<std::mutex> g(m.mu);
-    Workspace& ws = *m.ws;
-    QueriesDev X{};
-    if (is_csr) upload_csr(reinterpret_cast<const ScipyCsrF32*>(input_x), ws.x_ptr, ws.x_idx, ws.x_val, X);
-    else upload_drm(reinterpret_cast<const ScipyDrmF32*>(input_x), ws.x_val, X);
-    PredictOpts o; o.only_topk = only_topk; o.post_processor = pps; o.csc_route = true;
-    if (only_topk == 0) fail("only_topk must be positive");
-    BeamDev init{};
-    const Layer& L = *m.layers[0];
-    const uint32_t P = L.c_cols;
-    std::vector<uint32_t> hi, hc; std::vector<float> hv;
-    uint32_t stride = 1;
-    const bool with_codes = csr_codes != nullptr;
-    if (with_codes) {
-        if (csr_codes->rows != X.rows) fail("Instance dimension of query and prev_layer_pred matrix do not match");
-        if (csr_codes->cols != P) fail("Label dimension of prev_layer_pred and C matrix do not match");
-        // every parent id must exist; a row may list a parent more than once (a non-canonical CSR): the reference
-        // prolongates each occurrence, so the candidate row is sized from the real per-row sum of chunk sizes
-        uint64_t bound = 1;
-        for (uint32_t r = 0; r < X.rows; ++r) {
-            const uint64_t b = csr_codes->row_ptr[r], e = csr_codes->row_ptr[r + 1];
-            if (e < b) fail("csr_codes: row_ptr is not monotone");
-            stride = std::max<uint32_t>(stride, (uint32_t)(e - b));
-            uint64_t sum = 0;
-            for (uint64_t t = b; t < e; ++t) {
-                const uint32_t p = csr_codes->col_idx[t];
-                if (p >= P) fail("csr_codes: parent id " + std::to_string(p) + " out of range (C has " + std::to_string(P) + " columns)");
-                sum += L.h_c_ptr[p + 1] - L.h_c_ptr[p];
-            }
-            bound = std::max(bound, sum);
-        }
-        o.initial_cand_bound = bound;
-        hi.assign((size_t)X.rows * stride, 0); hv.assign((size_t)X.rows * stride, 0.f); hc.assign(X.rows, 0);
-        for (uint32_t r = 0; r < X.rows; ++r) {
-            const uint64_t b = csr_codes->row_ptr[r], e = csr_codes->row_ptr[r + 1];
-            hc[r] = (uint32_t)(e - b);
-            for (uint64_t t = b; t < e; ++t) { hi[(size_t)r * stride + (t - b)] = csr_codes->col_idx[t]; hv[(size_t)r * stride + (t - b)] = csr_codes->val[t]; }
-        }
-    } else if (P > 1) {   // fill_ones(X.rows, C->cols): every parent, score 1, and NO combine
-        stride = P;
-        hi.resize((size_t)X.rows * P); hv.assign((size_t)X.rows * P, 1.f); hc.assign(X.rows, P);
-        for (uint32_t r = 0; r < X.rows; ++r) for (uint32_t p = 0; p < P; ++p) hi[(size_t)r * P + p] = p;
-    }
-    if (!hi.empty()) {
-        ws.init_idx.upload(hi); ws.init_val.upload(hv); ws.init_cnt.upload(hc);
-        init = BeamDev{ws.init_idx.as<uint32_t>(), ws.init_val.as<float>(), ws.init_cnt.as<uint32_t>(), stride};
-        o.initial = &init; o.initial_max = stride;
-    }
-    o.no_prev_pred = !with_codes;   // combine only when csr_codes were given (libpecos.cpp:215-222)
-    run_and_emit(m, X, o, alloc);
-}
-
-template <class XT>
-void selected_host(void* ptr, const XT* input_x, bool is_csr, const ScipyCsrF32* S, const char* pp, py_sparse_allocator_t alloc) {
-    // libpecos.cpp:179-198 (C_XLINEAR_PREDICT_ON_SELECTED_OUTPUTS)
-    Model& m = *as_model(ptr);
-    if (!alloc) fail("null allocator callback");
-    if (!S) fail("null selected_outputs_csr");
-    std::lock_guard<std::mutex> g(m.mu);
-    use_device(m.device);
-    if (!m.ws) m.ws = std::make_unique<Workspace>();
-    QueriesDev X{};
-    if (is_csr) upload_csr(reinterpret_cast<const ScipyCsrF32*>(input_x), m.ws->x_ptr, m.ws->x_idx, m.ws->x_val, X);
-    else upload_drm(reinterpret_cast<const ScipyDrmF32*>(input_x), m.ws->x_val, X);
-    std::vector<uint32_t> oi; std::vector<float> ov;
-    predict_selected(m, X, S->rows, S->cols, S->row_ptr, S->col_idx, pp, oi, ov);
-    uint32_t* o_idx = nullptr; uint64_t* o_ptr = nullptr; float* o_val = nullptr;
-    alloc(false, S->rows, S->cols, oi.size(), &o_idx, &o_ptr, &o_val);
-    if (!o_ptr || (!oi.empty() && (!o_idx || !o_val))) fail("allocator callback returned null buffers");
-    std::memcpy(o_ptr, S->row_ptr, ((size_t)S->rows + 1) * 8);
-    if (!oi.empty()) { std::memcpy(o_idx, oi.data(), oi.size() * 4); std::memcpy(o_val, ov.data(), ov.size() * 4); }
-}
-
-template <class XT>
-void single_layer_selected(const XT* input_x, bool is_csr, const ScipyCsrF32* S, const ScipyCsrF32* csr_codes, ScipyCscF32* W,
-                           ScipyCscF32* C, const char* pp, float bias, py_sparse_allocator_t alloc) {
-    // libpecos.cpp:237-274: a temporary one-layer model around caller-owned W / C, selected outputs only
-    require_gpu();
-    use_device(g_device);
-    if (!alloc) fail("null allocator callback");
-    if (!S) fail("null selected_outputs_csr");
-    const char* pps = pp ? pp : "noop";
-    std::shared_ptr<Model> m = single_layer_model(W, C, bias);
-    std::lock_guard<std::mutex> g(m->mu);
-    QueriesDev X{};
-    if (is_csr) upload_csr(reinterpret_cast<const ScipyCsrF32*>(input_x), m->ws->x_ptr, m->ws->x_idx, m->ws->x_val, X);
-    else upload_drm(reinterpret_cast<const ScipyDrmF32*>(input_x), m->ws->x_val, X);
-    ScipyCsrF32View cv{};
-    SelectedInit init{nullptr, true};
-    if (csr_codes) { cv = ScipyCsrF32View{csr_codes->rows, csr_codes->cols, csr_codes->row_ptr, csr_codes->col_idx, csr_codes->val}; init.codes = &cv; init.no_prev_pred = false; }
-    std::vector<uint32_t> oi; std::vector<float> ov;
-    predict_selected(*m, X, S->rows, S->cols, S->row_ptr, S->col_idx, pps, oi, ov, &init);
-    uint32_t* o_idx = nullptr; uint64_t* o_ptr = nullptr; float* o_val = nullptr;
-    alloc(false, S->rows, S->cols, oi.size(), &o_idx, &o_ptr, &o_val);
-    if (!o_ptr || (!oi.empty() && (!o_idx || !o_val))) fail("allocator callback returned null buffers");
-    std::memcpy(o_ptr, S->row_ptr, ((size_t)S->rows + 1) * 8);
-    if (!oi.empty()) { std::memcpy(o_idx, oi.data(), oi.size() * 4); std::memcpy(o_val, ov.data(), ov.size() * 4); }
-}
-
-template <class XT, class WT>
-void inner_products(const XT* pX, bool x_csr, const WT* pW, bool w_csc, uint64_t len, uint32_t* rows, uint32_t* cols, float* out) {
-    require_gpu();
-    use_device(g_device);
-    if (!pX || !pW) fail("null matrix");
-    DevBuf xp, xi, xv, wp, wi, wv, dr, dc, dout;
-    const uint64_t *dxp = nullptr, *dwp = nullptr; const uint32_t *dxi = nullptr, *dwi = nullptr;
-    uint32_t dim;
-    if (x_csr) {
-        auto* X = reinterpret_cast<const ScipyCsrF32*>(pX);
-        const uint64_t nnz = X->rows ? X->row_ptr[X->rows] : 0;
-        xp.upload_raw(X->row_ptr, ((size_t)X->rows + 1) * 8); xi.upload_raw(X->col_idx, nnz * 4); xv.upload_raw(X->val, nnz * 4);
-        dxp = xp.as<uint64_t>(); dxi = xi.as<uint32_t>(); dim = X->cols;
-    } else {
-        auto* X = reinterpret_cast<const ScipyDrmF32*>(pX);
-        xv.upload_raw(X->val, (size_t)X->rows * X->cols * 4); dim = X->cols;
-    }
-    if (w_csc) {
-        auto* Wm = reinterpret_cast<const ScipyCscF32*>(pW);
-        const uint64_t nnz = Wm->cols ? Wm->col_ptr[Wm->cols] : 0;
-        wp.upload_raw(Wm->col_ptr, ((size_t)Wm->cols + 1) * 8); wi.upload_raw(Wm->row_idx, nnz * 4); wv.upload_raw(Wm->val, nnz * 4);
-        dwp = wp.as<uint64_t>(); dwi = wi.as<uint32_t>();
-    } else {
-        auto* Wm = reinterpret_cast<const ScipyDcmF32*>(pW);
-        wv.upload_raw(Wm->val, (size_t)Wm->rows * Wm->cols * 4);
-        dim = Wm->rows;
-    }
-    dr.upload_raw(rows, len * 4); dc.upload_raw(cols, len * 4); dout.reserve(len * 4);
-    launch_k3_inner_products(dxp, dxi, xv.as<float>(), x_csr ? 0 : 1, dwp, dwi, wv.as<float>(), w_csc ? 0 : 1, dim, len,
-                             dr.as<uint32_t>(), dc.as<uint32_t>(), dout.as<float>(), nullptr);
-    XRL_HIP(hipDeviceSynchronize());
-    if (len) XRL_HIP(hipMemcpy(out, dout.p, len * 4, hipMemcpyDeviceToHost));
-}
-}  // namespace
+using namespace xrl;
 
 extern "C" {
 
@@ -887,99 +58,26 @@ int xrl_device_count(void) {
 }
 
 int xrl_set_device(int device) {
-    int rc = -1;
-    guarded([&] { use_device(device); g_device = device; rc = 0; });
-    return rc;
+    return guarded_value(-1, [&] { use_device(device); g_device = device; return 0; });
 }
 
-
-// Everything the host ABI needs that does not depend on the caller's X is created when a model is LOADED from a folder, not inside the first
-// predict (a user's first call cost 42-66 ms, 25 of them allocations, 15 more the first launches): the copy-thread pool,
-// the copy / auxiliary / D2H streams, the three pinned staging buffers of the upload ring, the code objects of the kernels the default
-// policy runs, and BOTH scratch lanes sized for the row batches the pipeline cuts (a 36 MB batch of Amazon-shape rows is ~60 k queries).
-// One tiny predict per lane does the last two.  XRL_WARM=0 skips it (tests that load hundreds of throw-away models may want to).
-constexpr uint32_t kWarmRows = 65536;
-static void warm_handle(Model& m) {
-    static const bool off = [] { const char* e = std::getenv("XRL_WARM"); return e && e[0] == '0'; }();
-    if (off || m.layers.empty()) return;
-    use_device(m.device);
-    if (!m.ws) m.ws = std::make_unique<Workspace>();
-    Workspace& ws = *m.ws;
-    (void)CopyPool::get();
-    if (!m.copy_stream) XRL_HIP(hipStreamCreateWithFlags(&m.copy_stream, hipStreamNonBlocking));
-    if (!m.aux_stream) XRL_HIP(hipStreamCreateWithFlags(&m.aux_stream, hipStreamNonBlocking));
-    if (!m.d2h_stream) XRL_HIP(hipStreamCreateWithFlags(&m.d2h_stream, hipStreamNonBlocking));
-    for (int s2 = 0; s2 < kStageSlots; ++s2) ws.stage[s2].reserve((size_t)32 << 20);
-    ws.stage_ptr.reserve((((size_t)1 << 19) + 1) * 8);
-    // 256 one-feature queries through the default policy, once per scratch lane
-    const uint32_t R = 256, D = std::max<uint32_t>(1, m.nr_features);
-    std::vector<uint64_t> ptr(R + 1); std::vector<uint32_t> idx(R); std::vector<float> val(R, 1.0f);
-    for (uint32_t r = 0; r <= R; ++r) ptr[r] = r;
-    for (uint32_t r = 0; r < R; ++r) idx[r] = (uint32_t)(((uint64_t)r * 2654435761ull) % D);
-    ScipyCsrF32 Xh{}; Xh.rows = R; Xh.cols = m.nr_features; Xh.row_ptr = ptr.data(); Xh.col_idx = idx.data(); Xh.val = val.data();
-    QueriesDev X{};
-    upload_csr(&Xh, ws.x_ptr, ws.x_idx, ws.x_val, X);
-    PredictOpts o; o.reserve_rows = kWarmRows;
-    const uint32_t k = effective_topk(m, 0);
-    // result buffers (device + PINNED host: 4-10 ms to allocate inside a first call) for calls of up to 2^19 rows / 2^23 result cells: 64 MiB pinned per handle at most
-    reserve_outputs(m, std::max<uint32_t>(R, (uint32_t)std::min<uint64_t>(1u << 19, (1ull << 23) / std::max<uint32_t>(1u, k))), k);
-    for (int L = 0; L < 2 && !m.csc_route; ++L) {   // (the CSC route builds its device copy of W on first use: not here)
-        if (L) std::swap(ws.lane[0], ws.lane[1]);
-        try { predict_device(m, X, o, ws.out_idx.as<uint32_t>(), ws.out_val.as<float>(), ws.out_cnt.as<uint32_t>(), k, m.stream, true); }
-        catch (...) { if (L) std::swap(ws.lane[0], ws.lane[1]); throw; }
-        if (L) std::swap(ws.lane[0], ws.lane[1]);
-    }
-    // Every stream's FIRST copy pays for the runtime setting up its copy path (measured: 5.5 ms inside the first call's download on the D2H stream, 5.5 ms
-    // again two calls later when the last row batch first lands on the other compute lane): one 1 MiB copy each way on each stream now, at load.
-    {
-        const size_t nb = std::min<size_t>((size_t)1 << 20, std::min(ws.out_idx.cap, ws.h_idx.cap));
-        if (nb) {
-            for (hipStream_t st : {m.stream, m.aux_stream, m.d2h_stream, m.copy_stream}) {
-                if (!st) continue;
-                XRL_HIP(hipMemcpyAsync(ws.h_idx.p, ws.out_idx.p, nb, hipMemcpyDeviceToHost, st));
-                XRL_HIP(hipMemcpyAsync(ws.out_idx.p, ws.stage[0].p, std::min(nb, ws.stage[0].cap), hipMemcpyHostToDevice, st));
-                XRL_HIP(hipStreamSynchronize(st));
-            }
-        }
-    }
-    // The warm-up queries (one feature each) say nothing about the caller's data: what the pruning feedback learned from them is discarded -- round 6: their
-    // later stages hold almost every item, which marked the leaf "unstaged" and made a fresh handle score all beam parents of every query until the first
-    // re-probe, 32 row batches (~3 host-ABI calls) later.
-    m.fb.reset();
-}
-
-void* c_xlinear_load_model_from_disk_ext(const char* model_path, int weight_matrix_type) {
-    void* out = nullptr;
-    guarded([&] {
+// a model folder in the npz (kind 0) or the mmap (kind 1) layout -> a warmed-up handle on the calling thread's device
+static void* load_handle(const char* model_path, int kind, int weight_matrix_type) {
+    return guarded_value((void*)nullptr, [&]() -> void* {
         if (!model_path) fail("null model path");
         require_gpu();
         use_device(g_device);
-        auto m = load_model_from_disk(model_path, weight_matrix_type);
-        m->device = g_device; m->src_path = model_path; m->src_kind = 0;
+        auto m = kind == 0 ? load_model_from_disk(model_path, weight_matrix_type) : load_mmap_model_from_disk(model_path);
+        m->device = g_device; m->src_path = model_path; m->src_kind = kind;
         warm_handle(*m);
-        out = m.release();
+        return m.release();
     });
-    return out;
 }
 
-void* c_xlinear_load_model_from_disk(const char* model_path) {
-    return c_xlinear_load_model_from_disk_ext(model_path, 2 /* DEFAULT_LAYER_TYPE = BINARY_SEARCH_CHUNKED */);
-}
-
-void* c_xlinear_load_mmap_model_from_disk(const char* model_path, const bool lazy_load) {
-    (void)lazy_load;   // the model is copied to HBM either way
-    void* out = nullptr;
-    guarded([&] {
-        if (!model_path) fail("null model path");
-        require_gpu();
-        use_device(g_device);
-        auto m = load_mmap_model_from_disk(model_path);
-        m->device = g_device; m->src_path = model_path; m->src_kind = 1;
-        warm_handle(*m);
-        out = m.release();
-    });
-    return out;
-}
+void* c_xlinear_load_model_from_disk_ext(const char* model_path, int weight_matrix_type) { return load_handle(model_path, 0, weight_matrix_type); }
+void* c_xlinear_load_model_from_disk(const char* model_path) { return load_handle(model_path, 0, 2 /* DEFAULT_LAYER_TYPE = BINARY_SEARCH_CHUNKED */); }
+// (lazy_load: the model is copied to HBM either way)
+void* c_xlinear_load_mmap_model_from_disk(const char* model_path, const bool) { return load_handle(model_path, 1, 2); }
 
 void c_xlinear_compile_mmap_model(const char* model_path, const char* mmap_model_path) {
     guarded([&] {
@@ -1038,83 +136,14 @@ int c_xlinear_get_layer_type(void* ptr, int layer_depth) {
 
 void c_xlinear_predict_csr_f32(void* ptr, const ScipyCsrF32* input_x, const uint32_t overridden_beam_size,
                                const char* overridden_post_processor_str, const uint32_t overridden_only_topk,
-                               const int threads, py_sparse_allocator_t pred_alloc) {
-    (void)threads;
-    guarded([&] { predict_host(ptr, input_x, overridden_beam_size, overridden_post_processor_str, overridden_only_topk, pred_alloc, true); });
+                               const int /*threads*/, py_sparse_allocator_t pred_alloc) {
+    guarded([&] { predict_host(ptr, HostX(input_x), overridden_beam_size, overridden_post_processor_str, overridden_only_topk, pred_alloc); });
 }
 
 void c_xlinear_predict_drm_f32(void* ptr, const ScipyDrmF32* input_x, const uint32_t overridden_beam_size,
                                const char* overridden_post_processor_str, const uint32_t overridden_only_topk,
-                               const int threads, py_sparse_allocator_t pred_alloc) {
-    (void)threads;
-    guarded([&] { predict_host(ptr, input_x, overridden_beam_size, overridden_post_processor_str, overridden_only_topk, pred_alloc, false); });
-}
-
-void c_xlinear_predict_on_selected_outputs_csr_f32(void* ptr, const ScipyCsrF32* input_x, const ScipyCsrF32* selected_outputs_csr,
-                                                   const char* overridden_post_processor_str, const int threads,
-                                                   py_sparse_allocator_t pred_alloc) {
-    (void)threads;
-    guarded([&] { selected_host(ptr, input_x, true, selected_outputs_csr, overridden_post_processor_str, pred_alloc); });
-}
-
-void c_xlinear_predict_on_selected_outputs_drm_f32(void* ptr, const ScipyDrmF32* input_x, const ScipyCsrF32* selected_outputs_csr,
-                                                   const char* overridden_post_processor_str, const int threads,
-                                                   py_sparse_allocator_t pred_alloc) {
-    (void)threads;
-    guarded([&] { selected_host(ptr, input_x, false, selected_outputs_csr, overridden_post_processor_str, pred_alloc); });
-}
-
-void c_xlinear_single_layer_predict_csr_f32(const ScipyCsrF32* input_x, const ScipyCsrF32* csr_codes, ScipyCscF32* W,
-                                            ScipyCscF32* C, const char* post_processor_str, const uint32_t only_topk,
-                                            const int num_threads, const float bias, py_sparse_allocator_t pred_alloc) {
-    (void)num_threads;
-    guarded([&] { single_layer_predict(input_x, true, csr_codes, W, C, post_processor_str, only_topk, bias, pred_alloc); });
-}
-
-void c_xlinear_single_layer_predict_drm_f32(const ScipyDrmF32* input_x, const ScipyCsrF32* csr_codes, ScipyCscF32* W,
-                                            ScipyCscF32* C, const char* post_processor_str, const uint32_t only_topk,
-                                            const int num_threads, const float bias, py_sparse_allocator_t pred_alloc) {
-    (void)num_threads;
-    guarded([&] { single_layer_predict(input_x, false, csr_codes, W, C, post_processor_str, only_topk, bias, pred_alloc); });
-}
-
-void c_xlinear_single_layer_predict_on_selected_outputs_csr_f32(const ScipyCsrF32* input_x, const ScipyCsrF32* selected_outputs_csr,
-                                                                const ScipyCsrF32* csr_codes, ScipyCscF32* W, ScipyCscF32* C,
-                                                                const char* post_processor_str, const int num_threads,
-                                                                const float bias, py_sparse_allocator_t pred_alloc) {
-    (void)num_threads;
-    guarded([&] { single_layer_selected(input_x, true, selected_outputs_csr, csr_codes, W, C, post_processor_str, bias, pred_alloc); });
-}
-
-void c_xlinear_single_layer_predict_on_selected_outputs_drm_f32(const ScipyDrmF32* input_x, const ScipyCsrF32* selected_outputs_csr,
-                                                                const ScipyCsrF32* csr_codes, ScipyCscF32* W, ScipyCscF32* C,
-                                                                const char* post_processor_str, const int num_threads,
-                                                                const float bias, py_sparse_allocator_t pred_alloc) {
-    (void)num_threads;
-    guarded([&] { single_layer_selected(input_x, false, selected_outputs_csr, csr_codes, W, C, post_processor_str, bias, pred_alloc); });
-}
-
-void xrl_single_layer_cache_clear(void) {
-    guarded([&] { std::lock_guard<std::mutex> g(g_sl_mu); g_sl_cache.clear(); });
-}
-void xrl_single_layer_cache_stats(uint64_t* hits, uint64_t* misses, uint64_t* entries) {
-    std::lock_guard<std::mutex> g(g_sl_mu);
-    if (hits) *hits = g_sl_hits;
-    if (misses) *misses = g_sl_misses;
-    if (entries) *entries = g_sl_cache.size();
-}
-
-void c_sparse_inner_products_csr2csc_f32(const ScipyCsrF32* pX, const ScipyCscF32* pW, uint64_t len, uint32_t* r, uint32_t* c, float* val, int threads) {
-    (void)threads; guarded([&] { inner_products(pX, true, pW, true, len, r, c, val); });
-}
-void c_sparse_inner_products_drm2csc_f32(const ScipyDrmF32* pX, const ScipyCscF32* pW, uint64_t len, uint32_t* r, uint32_t* c, float* val, int threads) {
-    (void)threads; guarded([&] { inner_products(pX, false, pW, true, len, r, c, val); });
-}
-void c_sparse_inner_products_csr2dcm_f32(const ScipyCsrF32* pX, const ScipyDcmF32* pW, uint64_t len, uint32_t* r, uint32_t* c, float* val, int threads) {
-    (void)threads; guarded([&] { inner_products(pX, true, pW, false, len, r, c, val); });
-}
-void c_sparse_inner_products_drm2dcm_f32(const ScipyDrmF32* pX, const ScipyDcmF32* pW, uint64_t len, uint32_t* r, uint32_t* c, float* val, int threads) {
-    (void)threads; guarded([&] { inner_products(pX, false, pW, false, len, r, c, val); });
+                               const int /*threads*/, py_sparse_allocator_t pred_alloc) {
+    guarded([&] { predict_host(ptr, HostX(input_x), overridden_beam_size, overridden_post_processor_str, overridden_only_topk, pred_alloc); });
 }
 
 int xrl_inspect_model(const char* model_path, uint64_t* out, uint32_t cap) {
@@ -1141,65 +170,37 @@ int xrl_inspect_model(const char* model_path, uint64_t* out, uint32_t cap) {
     return depth;
 }
 
-void* xrl_model_create(uint32_t depth, const ScipyCscF32* const* W, const ScipyCscF32* const* C, const float* bias,
-                       const uint32_t* only_topk, const char* const* post_processor) {
-    void* out = nullptr;
-    guarded([&] {
-        require_gpu();
-        use_device(g_device);
-        if (!depth || !W || !bias || !only_topk || !post_processor) fail("xrl_model_create: bad arguments");
-        out = model_from_arrays(depth, W, C, bias, only_topk, post_processor).release();
-    });
-    return out;
-}
-
-void* xrl_queries_upload_csr(void* model, const ScipyCsrF32* X) {
-    void* out = nullptr;
-    guarded([&] {
+static void* queries_upload(void* model, const HostX& x) {
+    return guarded_value((void*)nullptr, [&]() -> void* {
         Model& m = *as_model(model);
         use_device(m.device);
         auto q = std::make_unique<Queries>();
         q->device = m.device;
-        upload_csr(X, q->ptr, q->idx, q->val, q->dev);
+        upload_x(x, q->ptr, q->idx, q->val, q->dev);
         q->nnz = q->dev.nnz;
-        out = q.release();
+        return q.release();
     });
-    return out;
 }
-
-void* xrl_queries_upload_drm(void* model, const ScipyDrmF32* X) {
-    void* out = nullptr;
-    guarded([&] {
-        Model& m = *as_model(model);
-        use_device(m.device);
-        auto q = std::make_unique<Queries>();
-        q->device = m.device;
-        upload_drm(X, q->val, q->dev);
-        out = q.release();
-    });
-    return out;
-}
+void* xrl_queries_upload_csr(void* model, const ScipyCsrF32* X) { return queries_upload(model, HostX(X)); }
+void* xrl_queries_upload_drm(void* model, const ScipyDrmF32* X) { return queries_upload(model, HostX(X)); }
 
 void* xrl_queries_from_device_csr(void* model, uint32_t rows, uint32_t cols, const uint64_t* d_row_ptr, const uint32_t* d_col_idx,
                                   const float* d_val, uint64_t nnz) {
-    void* out = nullptr;
-    guarded([&] {
+    return guarded_value((void*)nullptr, [&]() -> void* {
         Model& m = *as_model(model);
         if (rows && (!d_row_ptr || (nnz && (!d_col_idx || !d_val)))) fail("xrl_queries_from_device_csr: null device pointer");
         auto q = std::make_unique<Queries>();
         q->device = m.device; q->nnz = nnz;
         q->dev.row_ptr = d_row_ptr; q->dev.col_idx = d_col_idx; q->dev.val = d_val;
         q->dev.rows = rows; q->dev.cols = cols; q->dev.dense = 0; q->dev.nnz = nnz;
-        out = q.release();
+        return q.release();
     });
-    return out;
 }
 
 void* xrl_queries_tfidf_device(void* model, uint32_t rows, uint32_t cols, const uint64_t* d_row_ptr, const uint32_t* d_col_idx,
                                const float* d_count, uint64_t nnz, const float* d_idf, int binary, int sublinear_tf, int norm_p, float* d_out,
                                void* hip_stream) {
-    void* out = nullptr;
-    guarded([&] {
+    return guarded_value((void*)nullptr, [&]() -> void* {
         Model& m = *as_model(model);
         if (rows && (!d_row_ptr || (nnz && (!d_col_idx || !d_count)))) fail("xrl_queries_tfidf_device: null device pointer");
         use_device(m.device);
@@ -1217,23 +218,20 @@ void* xrl_queries_tfidf_device(void* model, uint32_t rows, uint32_t cols, const 
         if (err) fail("xrl_queries_tfidf_device: a column id outside [0, cols) (the reference's idx_idf.at() throws)");
         q->dev.row_ptr = d_row_ptr; q->dev.col_idx = d_col_idx; q->dev.val = dst;
         q->dev.rows = rows; q->dev.cols = cols; q->dev.dense = 0; q->dev.nnz = nnz;
-        out = q.release();
+        return q.release();
     });
-    return out;
 }
 
 void* xrl_queries_from_device_drm(void* model, uint32_t rows, uint32_t cols, const float* d_val) {
-    void* out = nullptr;
-    guarded([&] {
+    return guarded_value((void*)nullptr, [&]() -> void* {
         Model& m = *as_model(model);
         if (rows && cols && !d_val) fail("xrl_queries_from_device_drm: null device pointer");
         auto q = std::make_unique<Queries>();
         q->device = m.device;
         q->dev.row_ptr = nullptr; q->dev.col_idx = nullptr; q->dev.val = d_val;
         q->dev.rows = rows; q->dev.cols = cols; q->dev.dense = 1; q->dev.nnz = 0;
-        out = q.release();
+        return q.release();
     });
-    return out;
 }
 
 void* xrl_queries_concat_device(void* model, uint32_t rows, uint32_t sparse_cols, const uint64_t* d_row_ptr, const uint32_t* d_col_idx,
@@ -1243,8 +241,7 @@ void* xrl_queries_concat_device(void* model, uint32_t rows, uint32_t sparse_cols
 
 void* xrl_queries_concat_device_ex(void* model, uint32_t rows, uint32_t sparse_cols, const uint64_t* d_row_ptr, const uint32_t* d_col_idx,
                                    const float* d_val, uint64_t nnz, uint32_t dense_cols, const float* d_emb, int normalize_emb, void* hip_stream) {
-    void* out = nullptr;
-    guarded([&] {
+    return guarded_value((void*)nullptr, [&]() -> void* {
         Model& m = *as_model(model);
         if (rows && (!d_row_ptr || (nnz && (!d_col_idx || !d_val)) || (dense_cols && !d_emb))) fail("xrl_queries_concat_device: null device pointer");
         use_device(m.device);
@@ -1259,25 +256,21 @@ void* xrl_queries_concat_device_ex(void* model, uint32_t rows, uint32_t sparse_c
         q->nnz = out_nnz;
         q->dev.row_ptr = q->ptr.as<uint64_t>(); q->dev.col_idx = q->idx.as<uint32_t>(); q->dev.val = q->val.as<float>();
         q->dev.rows = rows; q->dev.cols = sparse_cols + dense_cols; q->dev.dense = 0; q->dev.nnz = out_nnz;
-        out = q.release();
+        return q.release();
     });
-    return out;
 }
 
 int xrl_queries_info(void* queries, uint64_t* out4) {
-    int rc = -1;
-    guarded([&] {
+    return guarded_value(-1, [&] {
         if (!queries || !out4) fail("null argument");
         const Queries* q = static_cast<const Queries*>(queries);
         out4[0] = q->dev.rows; out4[1] = q->dev.cols; out4[2] = q->dev.dense ? (uint64_t)q->dev.rows * q->dev.cols : q->dev.nnz; out4[3] = q->dev.dense ? 1 : 0;
-        rc = 0;
+        return 0;
     });
-    return rc;
 }
 
 int xrl_queries_download(void* queries, uint64_t* row_ptr, uint32_t* col_idx, float* val) {
-    int rc = -1;
-    guarded([&] {
+    return guarded_value(-1, [&] {
         if (!queries || !val) fail("null argument");
         const Queries* q = static_cast<const Queries*>(queries);
         XRL_HIP(hipSetDevice(q->device));
@@ -1292,9 +285,8 @@ int xrl_queries_download(void* queries, uint64_t* row_ptr, uint32_t* col_idx, fl
                 XRL_HIP(hipMemcpy(val, q->dev.val, (size_t)q->dev.nnz * 4, hipMemcpyDeviceToHost));
             }
         }
-        rc = 0;
+        return 0;
     });
-    return rc;
 }
 
 void xrl_queries_free(void* queries) {
@@ -1306,45 +298,38 @@ void xrl_queries_free(void* queries) {
     });
 }
 
+// xrl_predict_device and xrl_predict_device_rows (`ranged`: the scratch is sized for any row range of these queries)
+static int predict_device_entry(const char* what, bool ranged, void* model, void* queries, uint32_t beam_size, const char* post_processor,
+                                uint32_t only_topk, uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride,
+                                void* hip_stream, int sync, uint32_t row_begin = 0, uint32_t row_count = 0xFFFFFFFFu) {
+    return guarded_value(-1, [&] {
+        Model& m = *as_model(model);
+        if (!queries || !d_out_idx || !d_out_val || !d_out_cnt) fail(std::string(what) + ": null argument");
+        std::lock_guard<std::mutex> g(m.mu);
+        use_device(m.device);
+        const QueriesDev& X = static_cast<Queries*>(queries)->dev;
+        PredictOpts o; o.beam_size = beam_size; o.only_topk = only_topk; o.post_processor = post_processor;
+        if (ranged) o.reserve_rows = X.rows;
+        predict_device(m, X, o, d_out_idx, d_out_val, d_out_cnt, out_stride, static_cast<hipStream_t>(hip_stream), sync != 0, row_begin, row_count);
+        return 0;
+    });
+}
+
 int xrl_predict_device(void* model, void* queries, uint32_t beam_size, const char* post_processor, uint32_t only_topk,
                        uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride,
                        void* hip_stream, int sync) {
-    int rc = -1;
-    guarded([&] {
-        Model& m = *as_model(model);
-        if (!queries || !d_out_idx || !d_out_val || !d_out_cnt) fail("xrl_predict_device: null argument");
-        std::lock_guard<std::mutex> g(m.mu);
-        use_device(m.device);
-        PredictOpts o; o.beam_size = beam_size; o.only_topk = only_topk; o.post_processor = post_processor;
-        predict_device(m, static_cast<Queries*>(queries)->dev, o, d_out_idx, d_out_val, d_out_cnt, out_stride,
-                       static_cast<hipStream_t>(hip_stream), sync != 0);
-        rc = 0;
-    });
-    return rc;
+    return predict_device_entry("xrl_predict_device", false, model, queries, beam_size, post_processor, only_topk, d_out_idx, d_out_val, d_out_cnt, out_stride, hip_stream, sync);
 }
 
 int xrl_predict_device_rows(void* model, void* queries, uint32_t beam_size, const char* post_processor, uint32_t only_topk,
                             uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride,
                             void* hip_stream, int sync, uint32_t row_begin, uint32_t row_count) {
-    int rc = -1;
-    guarded([&] {
-        Model& m = *as_model(model);
-        if (!queries || !d_out_idx || !d_out_val || !d_out_cnt) fail("xrl_predict_device_rows: null argument");
-        std::lock_guard<std::mutex> g(m.mu);
-        use_device(m.device);
-        PredictOpts o; o.beam_size = beam_size; o.only_topk = only_topk; o.post_processor = post_processor;
-        o.reserve_rows = static_cast<Queries*>(queries)->dev.rows;     // scratch sized once for any row range of these queries
-        predict_device(m, static_cast<Queries*>(queries)->dev, o, d_out_idx, d_out_val, d_out_cnt, out_stride,
-                       static_cast<hipStream_t>(hip_stream), sync != 0, row_begin, row_count);
-        rc = 0;
-    });
-    return rc;
+    return predict_device_entry("xrl_predict_device_rows", true, model, queries, beam_size, post_processor, only_topk, d_out_idx, d_out_val, d_out_cnt, out_stride, hip_stream, sync, row_begin, row_count);
 }
 
 int xrl_predict_stats(void* model, void* queries, uint32_t beam_size, const char* post_processor, uint32_t only_topk,
                       double* stats_out, uint32_t stats_cap) {
-    int rc = -1;
-    guarded([&] {
+    return guarded_value(-1, [&] {
         Model& m = *as_model(model);
         if (!queries || !stats_out) fail("xrl_predict_stats: null argument");
         if (stats_cap < kStatsPerLayer * m.layers.size()) fail("xrl_predict_stats: stats_out too small (need 8*depth doubles)");
@@ -1359,15 +344,12 @@ int xrl_predict_stats(void* model, void* queries, uint32_t beam_size, const char
         const bool was = m.profiling; m.profiling = false;
         predict_device(m, X, o, ws.out_idx.as<uint32_t>(), ws.out_val.as<float>(), ws.out_cnt.as<uint32_t>(), k, m.stream, true);
         m.profiling = was;
-        rc = 0;
+        return 0;
     });
-    return rc;
 }
 
 uint32_t xrl_effective_topk(void* model, uint32_t only_topk) {
-    uint32_t v = 0;
-    guarded([&] { v = effective_topk(*as_model(model), only_topk); });
-    return v;
+    return guarded_value(0u, [&] { return effective_topk(*as_model(model), only_topk); });
 }
 
 void xrl_profile_enable(void* model, int enable) { guarded([&] { as_model(model)->profiling = enable != 0; }); }
@@ -1389,15 +371,20 @@ uint32_t xrl_profile_get(void* model, xrl_profile_rec_t* out, uint32_t cap) {
 }
 
 uint32_t xrl_debug_split_chunk(const uint64_t* cum, uint32_t n, uint64_t limit) {
-    uint32_t v = 0;
-    guarded([&] { if (!cum) fail("null cum"); v = split_chunk(cum, n, limit); });
-    return v;
+    return guarded_value(0u, [&] { if (!cum) fail("null cum"); return split_chunk(cum, n, limit); });
 }
 
 uint64_t xrl_debug_layout_rows(const uint32_t* rptr, uint32_t nrows, int align, uint32_t* ext_out) {
-    uint64_t v = 0;
-    guarded([&] { if (!rptr) fail("null rptr"); v = layout_tile_rows(rptr, nrows, align != 0, ext_out); });
-    return v;
+    return guarded_value((uint64_t)0, [&] { if (!rptr) fail("null rptr"); return layout_tile_rows(rptr, nrows, align != 0, ext_out); });
+}
+
+uint32_t xrl_debug_host_batches(const uint64_t* row_ptr, uint32_t rows, uint32_t cols, int host_batch_mb, uint32_t* rb_out, uint32_t cap) {
+    return guarded_value(0u, [&] {
+        HostX x; x.given = true; x.csr = row_ptr != nullptr; x.rows = rows; x.cols = cols; x.row_ptr = row_ptr;
+        const std::vector<uint32_t> rb = plan_row_batches(x, host_batch_mb, staged_upload(x, 1));
+        for (size_t i = 0; i < rb.size() && i < cap && rb_out; ++i) rb_out[i] = rb[i];
+        return (uint32_t)rb.size();
+    });
 }
 
 // every integer option that is a plain store into Model::Options, under the member's own name (include/xrl_abi.h documents the keys)
@@ -1429,8 +416,7 @@ static void set_option_one(Model& m, const char* key, int64_t value) {
 }
 
 int xrl_set_option(void* model, const char* key, int64_t value) {
-    int rc = -1;
-    guarded([&] {
+    return guarded_value(-1, [&] {
         Model& m = *as_model(model);
         if (!key) fail("null key");
         if (!std::strcmp(key, "devices")) {
@@ -1456,9 +442,8 @@ int xrl_set_option(void* model, const char* key, int64_t value) {
             set_option_one(m, key, value);
             for (auto& r : m.replicas) set_option_one(*r, key, value);
         }
-        rc = 0;
+        return 0;
     });
-    return rc;
 }
 
 void xrl_debug_k1_phases(unsigned long long* out8, int reset) { guarded([&] { k1_phase_read(out8, reset != 0); }); }
@@ -1479,300 +464,7 @@ uint32_t xrl_layer_info(void* model, uint32_t layer, uint64_t* out, uint32_t cap
 }
 
 uint64_t xrl_model_device_bytes(void* model) {
-    uint64_t v = 0;
-    guarded([&] { v = as_model(model)->device_bytes(); });
-    return v;
-}
-
-// ---------------------------------------------------------------------------------------------
-// TF-IDF query producer (libpecos.cpp:398-445): c_tfidf_load / c_tfidf_destruct / c_tfidf_predict with the
-// reference's signatures, and xrl_tfidf_predict_device, which leaves X in HBM for xrl_predict_device.
-// ---------------------------------------------------------------------------------------------
-}  // extern "C"
-
-namespace {
-// pinned staging for the H2D copy of the term counts: the worker threads of the host half write straight into it (no intermediate, no page
-// faults -- pinned memory is resident), and the copy runs at link speed instead of through the runtime's pageable path.  Grows, never shrinks;
-// one producer call per handle at a time uses it.
-struct PinnedStage {
-    void* p = nullptr; size_t cap = 0; std::mutex mu;
-    ~PinnedStage() { if (p) (void)hipHostFree(p); }
-    void* need(size_t bytes) {
-        if (bytes > cap) {
-            if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-            const size_t want = bytes + bytes / 4 + (1u << 20);
-            XRL_HIP(hipHostMalloc(&p, want, hipHostMallocDefault));
-            cap = want;
-        }
-        return p;
-    }
-};
-
-// dst <- src on host threads, 1 MiB pieces
-void parallel_copy(void* dst, const void* src, size_t bytes, int threads) {
-    const size_t piece = (size_t)1 << 20, n = (bytes + piece - 1) / piece;
-    unsigned nt = threads > 0 ? (unsigned)threads : std::min(32u, std::max(1u, std::thread::hardware_concurrency()));
-    nt = (unsigned)std::max<size_t>(1, std::min<size_t>(nt, n));
-    std::atomic<size_t> next{0};
-    auto work = [&] {
-        for (;;) {
-            const size_t i = next.fetch_add(1, std::memory_order_relaxed);
-            if (i >= n) break;
-            std::memcpy(static_cast<char*>(dst) + i * piece, static_cast<const char*>(src) + i * piece, std::min(piece, bytes - i * piece));
-        }
-    };
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < nt; ++t) th.emplace_back(work);
-    work();
-    for (auto& x : th) x.join();
-}
-
-struct TfidfHandle {
-    TfidfVectorizer v;
-    std::vector<float> idf_all;                  // the base vectorizers' idf side by side (hstack column order)
-    mutable PinnedStage stage;
-    // c_tfidf_predict's stream, created once per (handle, device) instead of per call
-    mutable std::mutex stream_mu;
-    mutable hipStream_t stream = nullptr;
-    mutable int stream_device = -1;
-    // call with the staging lock (stage.mu) HELD and keep it until the stream has been synchronised: a caller that switched devices
-    // replaces the stream, which must not happen under another thread's transfer
-    hipStream_t stream_on(int device) const {
-        std::lock_guard<std::mutex> g(stream_mu);
-        if (stream && stream_device != device) { (void)hipSetDevice(stream_device); (void)hipStreamDestroy(stream); stream = nullptr; (void)hipSetDevice(device); }
-        if (!stream) { XRL_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)); stream_device = device; }
-        return stream;
-    }
-    ~TfidfHandle() { if (stream) { (void)hipSetDevice(stream_device); (void)hipStreamDestroy(stream); } }
-};
-
-// texts -> term counts (host threads, into pinned staging) -> device -> weighting + normalisation (K5): a query handle that owns its three arrays
-std::unique_ptr<Queries> tfidf_to_device(const TfidfHandle& H, const char* const* corpus, const size_t* doc_lens, size_t nr_doc, int threads, int device, hipStream_t s) {
-    if (nr_doc > 0xFFFFFFFFull) fail("tfidf: too many documents");
-    const TfidfVectorizer& V = H.v;
-    const uint32_t nb = (uint32_t)V.base.size(), rows = (uint32_t)nr_doc;
-    use_device(device);
-    std::lock_guard<std::mutex> stage_lock(H.stage.mu);          // held until the stream has consumed the staging buffer (the synchronize below)
-    if (!s) s = H.stream_on(device);                             // the handle's pooled stream, taken under the staging lock
-    std::vector<uint64_t> seg_ptr;
-    uint32_t* h_col = nullptr; float* h_cnt = nullptr; uint64_t nnz = 0;
-    V.count_corpus(corpus, doc_lens, nr_doc, threads, seg_ptr, [&](uint64_t n, uint32_t*& c, float*& v) {
-        char* base = static_cast<char*>(H.stage.need((size_t)n * 8 + 16));
-        c = h_col = reinterpret_cast<uint32_t*>(base); v = h_cnt = reinterpret_cast<float*>(base + (size_t)n * 4);
-        nnz = n;
-    });
-    auto q = std::make_unique<Queries>();
-    q->device = device; q->nnz = nnz;
-    DevBuf d_seg, d_idf, d_err;
-    d_seg.upload(seg_ptr);
-    q->idx.reserve((size_t)nnz * 4); q->val.reserve((size_t)nnz * 4);
-    if (nnz) {
-        XRL_HIP(hipMemcpyAsync(q->idx.p, h_col, (size_t)nnz * 4, hipMemcpyHostToDevice, s));
-        XRL_HIP(hipMemcpyAsync(q->val.p, h_cnt, (size_t)nnz * 4, hipMemcpyHostToDevice, s));
-    }
-    d_idf.upload(H.idf_all);
-    d_err.reserve(4); XRL_HIP(hipMemsetAsync(d_err.p, 0, 4, s));
-    for (uint32_t b = 0; b < nb; ++b) {
-        const TfidfBase& B = V.base[b];
-        launch_tfidf_weight(d_seg.as<uint64_t>(), q->idx.as<uint32_t>(), q->val.as<float>(), B.use_idf ? d_idf.as<float>() : nullptr, rows, V.nr_features,
-                            B.binary ? 1 : 0, B.sublinear_tf ? 1 : 0, B.norm_p, q->val.as<float>(), s, nb, b, d_err.as<uint32_t>());
-    }
-    // whole rows: the hstacked CSR's row pointer; the ensemble's normalisation (Vectorizer::predict, tfidf.hpp:1405-1430)
-    if (nb == 1) q->ptr = std::move(d_seg);
-    else {
-        std::vector<uint64_t> row_ptr((size_t)rows + 1);
-        for (size_t r = 0; r <= rows; ++r) row_ptr[r] = seg_ptr[r * nb];
-        q->ptr.upload(row_ptr);
-    }
-    if (nb > 1 || V.norm_p != V.base[0].norm_p)
-        launch_tfidf_weight(q->ptr.as<uint64_t>(), q->idx.as<uint32_t>(), q->val.as<float>(), nullptr, rows, V.nr_features, 0, 0, V.norm_p, q->val.as<float>(), s);
-    uint32_t err = 0;
-    XRL_HIP(hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, s));
-    XRL_HIP(hipStreamSynchronize(s));
-    if (err) fail("tfidf: a feature id outside the model's feature range");
-    q->dev.row_ptr = q->ptr.as<uint64_t>(); q->dev.col_idx = q->idx.as<uint32_t>(); q->dev.val = q->val.as<float>();
-    q->dev.rows = rows; q->dev.cols = V.nr_features; q->dev.dense = 0; q->dev.nnz = q->nnz;
-    return q;
-}
-}  // namespace
-
-extern "C" {
-
-void* c_tfidf_load(const char* model_dir) {
-    void* out = nullptr;
-    guarded([&] {
-        if (!model_dir) fail("null model_dir");
-        auto h = std::make_unique<TfidfHandle>();
-        h->v.load(model_dir);
-        for (const auto& b : h->v.base) h->idf_all.insert(h->idf_all.end(), b.idf.begin(), b.idf.end());
-        out = h.release();
-    });
-    return out;
-}
-
-void c_tfidf_destruct(void* ptr) { guarded([&] { delete static_cast<TfidfHandle*>(ptr); }); }
-
-uint32_t xrl_tfidf_nr_features(void* ptr) {
-    uint32_t v = 0;
-    guarded([&] { if (!ptr) fail("null vectorizer handle"); v = static_cast<TfidfHandle*>(ptr)->v.nr_features; });
-    return v;
-}
-
-// documents -> weighted CSR on the device -> the caller's arrays through ONE allocator call (shared by c_tfidf_predict and c_tfidf_predict_from_file)
-// The weighting half on the HOST, for calls of a handful of documents (the reference serves nr_doc == 1 with a direct host call, libpecos.cpp:437-439:
-// microseconds -- a device round trip costs a hundred times that).  tfidf.hpp:798-822 operation by operation in fp32, like the kernel
-// (csrc/xrl_features.hip): sequential norm in ascending feature order, separate multiply and add (-ffp-contract=off), glibc's logf (the reference's own).
-static void tfidf_weight_host(const uint64_t* row_ptr, const uint32_t* col, float* val, const float* idf, uint32_t rows, uint32_t cols, bool binary,
-                              bool sublinear, int norm_p, uint32_t seg_stride, uint32_t seg_off) {
-    if (norm_p != 1 && norm_p != 2) fail("tfidf: invalid normalize option, norm_p: [ 1| 2]");
-    for (uint32_t r = 0; r < rows; ++r) {
-        const uint64_t b = row_ptr[(uint64_t)r * seg_stride + seg_off], e = row_ptr[(uint64_t)r * seg_stride + seg_off + 1];
-        float denom = 0.0f;
-        for (uint64_t t = b; t < e; ++t) {
-            float v = binary ? 1.0f : val[t];
-            if (sublinear) v = (float)((double)std::log(v) + 1.0);
-            if (idf) {
-                if (col[t] >= cols) fail("tfidf: a feature id outside the model's feature range");
-                v = v * idf[col[t]];
-            }
-            val[t] = v;
-            const float term = norm_p == 1 ? std::fabs(v) : v * v;
-            denom = denom + term;
-        }
-        if (std::fabs(denom) < FLT_EPSILON) denom = 1.0f;
-        else if (norm_p == 2) denom = std::sqrt(denom);
-        for (uint64_t t = b; t < e; ++t) val[t] = val[t] / denom;
-    }
-}
-
-constexpr size_t kTfidfHostDocs = 4;   // c_tfidf_predict calls of at most this many documents are weighted on the host
-
-static void tfidf_predict_small_on_host(const TfidfHandle& H, const char* const* corpus, const size_t* doc_lens, size_t nr_doc, py_sparse_allocator_t pred_alloc) {
-    const TfidfVectorizer& V = H.v;
-    const uint32_t nb = (uint32_t)V.base.size(), rows = (uint32_t)nr_doc;
-    std::vector<uint64_t> seg_ptr;
-    std::vector<uint32_t> h_col; std::vector<float> h_val;
-    V.count_corpus(corpus, doc_lens, nr_doc, 1, seg_ptr, [&](uint64_t n, uint32_t*& c, float*& v) { h_col.resize(n + 1); h_val.resize(n + 1); c = h_col.data(); v = h_val.data(); });
-    const uint64_t nnz = seg_ptr.empty() ? 0 : seg_ptr.back();
-    for (uint32_t b = 0; b < nb; ++b) {
-        const TfidfBase& B = V.base[b];
-        tfidf_weight_host(seg_ptr.data(), h_col.data(), h_val.data(), B.use_idf ? H.idf_all.data() : nullptr, rows, V.nr_features, B.binary, B.sublinear_tf, B.norm_p, nb, b);
-    }
-    std::vector<uint64_t> row_ptr((size_t)rows + 1);
-    for (size_t r = 0; r <= rows; ++r) row_ptr[r] = seg_ptr[r * nb];
-    if (nb > 1 || V.norm_p != V.base[0].norm_p)
-        tfidf_weight_host(row_ptr.data(), h_col.data(), h_val.data(), nullptr, rows, V.nr_features, false, false, V.norm_p, 1, 0);
-    uint32_t* indices = nullptr; uint64_t* indptr = nullptr; float* data = nullptr;
-    pred_alloc(false, rows, V.nr_features, nnz, &indices, &indptr, &data);
-    if (!indptr || (nnz && (!indices || !data))) fail("allocator returned null");
-    std::memcpy(indptr, row_ptr.data(), ((size_t)rows + 1) * 8);
-    if (nnz) { std::memcpy(indices, h_col.data(), (size_t)nnz * 4); std::memcpy(data, h_val.data(), (size_t)nnz * 4); }
-}
-
-static void tfidf_predict_to_host(const TfidfHandle& H, const char* const* corpus, const size_t* doc_lens, size_t nr_doc, int threads, py_sparse_allocator_t pred_alloc) {
-    const char* hs = std::getenv("XRL_TFIDF_HOST_DOCS");                     // XRL_TFIDF_HOST_DOCS=0: always the device (tests; read per call)
-    if (!(hs && hs[0] == '0') && nr_doc <= kTfidfHostDocs) { tfidf_predict_small_on_host(H, corpus, doc_lens, nr_doc, pred_alloc); return; }
-    use_device(g_device);
-    // (stream = nullptr: tfidf_to_device takes the handle's pooled stream under its staging lock and holds the lock until it has synchronised)
-    std::unique_ptr<Queries> q = tfidf_to_device(H, corpus, doc_lens, nr_doc, threads, g_device, nullptr);
-    uint32_t* indices = nullptr; uint64_t* indptr = nullptr; float* data = nullptr;
-    pred_alloc(false, q->dev.rows, q->dev.cols, q->nnz, &indices, &indptr, &data);
-    if (!indptr || (q->nnz && (!indices || !data))) fail("allocator returned null");
-    XRL_HIP(hipMemcpy(indptr, q->dev.row_ptr, ((size_t)q->dev.rows + 1) * 8, hipMemcpyDeviceToHost));
-    if (q->nnz) {
-        // D2H into the pinned staging buffer (link speed), then host threads spread it over the allocator's fresh arrays: their first touch
-        // in parallel, instead of the runtime's single-threaded pageable path
-        std::lock_guard<std::mutex> stage_lock(H.stage.mu);
-        const size_t nb4 = (size_t)q->nnz * 4;
-        char* st = static_cast<char*>(H.stage.need(2 * nb4));
-        XRL_HIP(hipMemcpy(st, q->dev.col_idx, nb4, hipMemcpyDeviceToHost));
-        XRL_HIP(hipMemcpy(st + nb4, q->dev.val, nb4, hipMemcpyDeviceToHost));
-        parallel_copy(indices, st, nb4, threads);
-        parallel_copy(data, st + nb4, nb4, threads);
-    }
-}
-
-void c_tfidf_predict(void* ptr, void* corpus_ptr, const size_t* doc_lens, size_t nr_doc, int threads, py_sparse_allocator_t pred_alloc) {
-    guarded([&] {
-        if (!ptr || !pred_alloc) fail("c_tfidf_predict: null argument");
-        if (nr_doc == 0) fail("Invalid nr_doc 0");                         // libpecos.cpp:442-444
-        if (!corpus_ptr || !doc_lens) fail("c_tfidf_predict: null corpus");
-        require_gpu();
-        tfidf_predict_to_host(*static_cast<TfidfHandle*>(ptr), static_cast<const char* const*>(corpus_ptr), doc_lens, nr_doc, threads, pred_alloc);
-    });
-}
-
-// c_tfidf_predict_from_file (libpecos.cpp:413-425 -> Vectorizer::predict_from_file, tfidf.hpp:1041-1120, 1365-1389): one document per LINE of the
-// file.  The reference cuts the file into chunks at newlines (file_util.hpp:180-200) and every chunk into lines (append_lines_to_string_view,
-// tfidf.hpp:279-294): every '\n' ends a document (empty lines are documents), and a last line WITHOUT a newline is a document too -- with the
-// terminating NUL that load_file_block appends counted into its length (tfidf.hpp:290-293 takes `end - start` after the loop has walked over it),
-// which is reproduced here.  buffer_size only sizes the reference's read chunks: the file is read whole.
-void c_tfidf_predict_from_file(void* ptr, void* corpus_fname_ptr, size_t fname_len, size_t buffer_size, int threads, py_sparse_allocator_t pred_alloc) {
-    (void)buffer_size;
-    guarded([&] {
-        if (!ptr || !pred_alloc || !corpus_fname_ptr) fail("c_tfidf_predict_from_file: null argument");
-        require_gpu();
-        const std::string fname(static_cast<const char*>(corpus_fname_ptr), fname_len);
-        std::FILE* fp = std::fopen(fname.c_str(), "rb");
-        if (!fp) fail("c_tfidf_predict_from_file: can't read " + fname);
-        std::vector<char> buf;
-        {
-            std::fseek(fp, 0, SEEK_END);
-            const long sz = std::ftell(fp);
-            std::fseek(fp, 0, SEEK_SET);
-            if (sz < 0) { std::fclose(fp); fail("c_tfidf_predict_from_file: can't size " + fname); }
-            buf.resize((size_t)sz + 1);
-            const size_t got = sz ? std::fread(buf.data(), 1, (size_t)sz, fp) : 0;
-            std::fclose(fp);
-            if (got != (size_t)sz) fail("c_tfidf_predict_from_file: error reading " + fname);
-            buf[(size_t)sz] = '\0';
-        }
-        const size_t n = buf.size() - 1;
-        std::vector<const char*> docs; std::vector<size_t> lens;
-        size_t start = 0;
-        for (size_t i = 0; i < n; ++i)
-            if (buf[i] == '\n') { docs.push_back(buf.data() + start); lens.push_back(i - start); start = i + 1; }
-        if (start < n) { docs.push_back(buf.data() + start); lens.push_back(n + 1 - start); }   // (the NUL is part of the reference's last document)
-        if (docs.empty()) fail("c_tfidf_predict_from_file: " + fname + " holds no document");
-        tfidf_predict_to_host(*static_cast<TfidfHandle*>(ptr), docs.data(), lens.data(), docs.size(), threads, pred_alloc);
-    });
-}
-
-void* xrl_tfidf_predict_device(void* vectorizer, void* model, void* corpus_ptr, const size_t* doc_lens, size_t nr_doc, int threads) {
-    void* out = nullptr;
-    guarded([&] {
-        if (!vectorizer) fail("xrl_tfidf_predict_device: null vectorizer handle");
-        if (nr_doc && (!corpus_ptr || !doc_lens)) fail("xrl_tfidf_predict_device: null corpus");
-        Model& m = *as_model(model);
-        const TfidfHandle& H = *static_cast<TfidfHandle*>(vectorizer);
-        out = tfidf_to_device(H, static_cast<const char* const*>(corpus_ptr), doc_lens, nr_doc, threads, m.device, m.stream).release();
-    });
-    return out;
-}
-
-void* xrl_queries_concat_handle(void* model, void* queries, uint32_t dense_cols, const float* d_emb, int normalize_emb, void* hip_stream) {
-    if (!queries) { set_err("xrl_queries_concat_handle: null query handle"); return nullptr; }
-    const Queries& q = *static_cast<Queries*>(queries);
-    if (q.dev.dense) { set_err("xrl_queries_concat_handle: the query handle must hold a CSR"); return nullptr; }
-    return xrl_queries_concat_device_ex(model, q.dev.rows, q.dev.cols, q.dev.row_ptr, q.dev.col_idx, q.dev.val, q.dev.nnz, dense_cols, d_emb, normalize_emb, hip_stream);
-}
-
-// host only (no GPU): the hstacked TERM-COUNT CSR the device weighting starts from -- what the tokenizer and the n-gram lookup produce
-void xrl_tfidf_counts(void* ptr, void* corpus_ptr, const size_t* doc_lens, size_t nr_doc, int threads, py_sparse_allocator_t alloc) {
-    guarded([&] {
-        if (!ptr || !alloc || (nr_doc && (!corpus_ptr || !doc_lens))) fail("xrl_tfidf_counts: null argument");
-        const TfidfVectorizer& V = static_cast<TfidfHandle*>(ptr)->v;
-        std::vector<uint64_t> seg_ptr;
-        uint32_t* indices = nullptr; uint64_t* indptr = nullptr; float* data = nullptr;
-        // the allocator's arrays ARE the destination: the worker threads fill (and first-touch) them in parallel
-        V.count_corpus(static_cast<const char* const*>(corpus_ptr), doc_lens, nr_doc, threads, seg_ptr, [&](uint64_t n, uint32_t*& c, float*& v) {
-            alloc(false, nr_doc, V.nr_features, n, &indices, &indptr, &data);
-            if (!indptr || (n && (!indices || !data))) fail("allocator returned null");
-            c = indices; v = data;
-        });
-        const size_t nb = V.base.size();
-        for (size_t r = 0; r <= nr_doc; ++r) indptr[r] = seg_ptr[r * nb];
-    });
+    return guarded_value((uint64_t)0, [&] { return as_model(model)->device_bytes(); });
 }
 
 }  // extern "C"

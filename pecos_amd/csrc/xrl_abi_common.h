@@ -1,0 +1,57 @@
+// What the units behind the extern "C" surface share (xrl_abi.cpp, xrl_host_pipeline.cpp, xrl_single_layer.cpp, xrl_tfidf_abi.cpp):
+// the per-thread error and device state, the exception barrier of every entry point, and the upload of a caller's host X.
+#pragma once
+#include "../../include/xrl_abi.h"
+
+#include <string>
+
+#include "xrl_predict.h"
+
+namespace xrl {
+
+// per calling thread: what xrl_last_error() reports, and the device xrl_set_device() chose (defined in xrl_abi.cpp)
+extern thread_local std::string g_err;
+extern thread_local bool g_has_err;
+extern thread_local int g_device;
+
+void set_err(const std::string& s);
+
+// Every entry point catches all C++ exceptions and records them for xrl_last_error(); nothing is ever thrown across the C boundary.
+template <class F> void guarded(F&& fn) {
+    g_has_err = false;
+    try { fn(); }
+    catch (const std::exception& e) { set_err(e.what()); }
+    catch (...) { set_err("unknown error"); }
+}
+
+// ... for the entry points that return a value: fn()'s, or `on_error` after an exception
+template <class T, class F> T guarded_value(T on_error, F&& fn) {
+    guarded([&] { on_error = fn(); });
+    return on_error;
+}
+
+Model* as_model(void* p);
+void use_device(int dev);
+void require_gpu();
+
+// The caller's host X, CSR or dense row-major, as one view: built once at the entry point from ScipyCsrF32 / ScipyDrmF32.
+struct HostX {
+    bool given = false;                  // false: the caller passed a null X (reported where the arrays are first needed, as "null X")
+    bool csr = false;
+    uint32_t rows = 0, cols = 0;
+    const uint64_t* row_ptr = nullptr;   // CSR only
+    const uint32_t* col_idx = nullptr;   // CSR only
+    const float* val = nullptr;
+    HostX() = default;
+    explicit HostX(const ScipyCsrF32* X) { if (X) { given = true; csr = true; rows = X->rows; cols = X->cols; row_ptr = X->row_ptr; col_idx = X->col_idx; val = X->val; } }
+    explicit HostX(const ScipyDrmF32* X) { if (X) { given = true; rows = X->rows; cols = X->cols; val = X->val; } }
+    // elements (CSR: (column id, value) pairs; dense: values) before row r, in all rows, and the bytes one of them takes on its way to the device
+    uint64_t elem_at(uint32_t r) const { return csr ? row_ptr[r] : (uint64_t)r * cols; }
+    uint64_t elems() const { return csr ? (rows ? row_ptr[rows] : 0) : (uint64_t)rows * cols; }
+    uint32_t elem_bytes() const { return csr ? 8u : 4u; }
+};
+
+// synchronous upload of the whole X into the given buffers (dense X: `val` only); `d` describes the device copy
+void upload_x(const HostX& x, DevBuf& ptr, DevBuf& idx, DevBuf& val, QueriesDev& d);
+
+}  // namespace xrl

@@ -156,7 +156,7 @@ struct Workspace {
     DevBuf x_ptr, x_idx, x_val;
     DevBuf out_idx, out_val, out_cnt;
     PinnedBuf h_idx, h_val, h_cnt;
-    PinnedBuf stage[3];   // pinned staging ring of the pipelined host-ABI upload (kStageSlots, xrl_abi.cpp)
+    PinnedBuf stage[3];   // pinned staging ring of the pipelined host-ABI upload (kStageSlots, xrl_host_pipeline.cpp)
     PinnedBuf stage_ptr;  // ... and the row pointer's own pinned staging buffer (it travels first, on the copy stream)
     // initial beam for the single-layer API
     DevBuf init_idx, init_val, init_cnt;
@@ -175,7 +175,7 @@ struct Model {
     hipStream_t d2h_stream = nullptr;       // D2H of its results: a batch's rows travel back under the next batch's kernels
     std::vector<hipEvent_t> d2h_events;     // "batch b's kernels are queued" (grow-only, reused)
     std::vector<hipEvent_t> events;         // cross-stream ordering (timing disabled), reused across predicts
-    // host ABI, two compute lanes (xrl_abi.cpp host_compute): lane 0 uses ws_done / ws_stream above; lane 1 keeps its own "scratch in use
+    // host ABI, two compute lanes (xrl_host_pipeline.cpp LaneScope): lane 0 uses ws_done / ws_stream above; lane 1 keeps its own "scratch in use
     // until" event between calls, and one join event orders the lanes.  Owned by the handle: ~Model destroys them on the handle's device.
     struct HostLanes { hipEvent_t done[2] = {nullptr, nullptr}; hipStream_t strm[2] = {nullptr, nullptr}; hipEvent_t join = nullptr; } host_lanes;
     std::mutex mu;                          // one predict at a time per handle
@@ -216,7 +216,7 @@ struct Model {
         int host_pipeline = 1;                  // host ABI: cut large X into row batches whose upload overlaps the previous batch's kernels
     } opt;
     // multi-GPU behind the drop-in entry points (xrl_set_option "devices"): further copies of the compiled model on other devices; the
-    // host-ABI predict shards the rows over this handle's device and the replicas' (xrl_abi.cpp predict_host)
+    // host-ABI predict shards the rows over this handle's device and the replicas' (xrl_host_pipeline.cpp predict_host)
     std::string src_path; int src_kind = -1;   // where the model came from: 0 = npz folder, 1 = mmap folder, -1 = arrays (no replicas)
     std::vector<std::unique_ptr<Model>> replicas;
     bool profiling = false;

@@ -1,0 +1,299 @@
+// TF-IDF query producer (libpecos.cpp:398-445): c_tfidf_load / c_tfidf_destruct / c_tfidf_predict with the
+// reference's signatures, and xrl_tfidf_predict_device, which leaves X in HBM for xrl_predict_device.
+#include <atomic>
+#include <cfloat>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <thread>
+
+#include "xrl_abi_common.h"
+#include "xrl_tfidf.h"
+
+using namespace xrl;
+
+namespace {
+// pinned staging for the H2D copy of the term counts: the worker threads of the host half write straight into it (no intermediate, no page
+// faults -- pinned memory is resident), and the copy runs at link speed instead of through the runtime's pageable path.  Grows, never shrinks;
+// one producer call per handle at a time uses it.
+struct PinnedStage {
+    void* p = nullptr; size_t cap = 0; std::mutex mu;
+    ~PinnedStage() { if (p) (void)hipHostFree(p); }
+    void* need(size_t bytes) {
+        if (bytes > cap) {
+            if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
+            const size_t want = bytes + bytes / 4 + (1u << 20);
+            XRL_HIP(hipHostMalloc(&p, want, hipHostMallocDefault));
+            cap = want;
+        }
+        return p;
+    }
+};
+
+// dst <- src on host threads, 1 MiB pieces
+void parallel_copy(void* dst, const void* src, size_t bytes, int threads) {
+    const size_t piece = (size_t)1 << 20, n = (bytes + piece - 1) / piece;
+    unsigned nt = threads > 0 ? (unsigned)threads : std::min(32u, std::max(1u, std::thread::hardware_concurrency()));
+    nt = (unsigned)std::max<size_t>(1, std::min<size_t>(nt, n));
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (;;) {
+            const size_t i = next.fetch_add(1, std::memory_order_relaxed);
+            if (i >= n) break;
+            std::memcpy(static_cast<char*>(dst) + i * piece, static_cast<const char*>(src) + i * piece, std::min(piece, bytes - i * piece));
+        }
+    };
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < nt; ++t) th.emplace_back(work);
+    work();
+    for (auto& x : th) x.join();
+}
+
+struct TfidfHandle {
+    TfidfVectorizer v;
+    std::vector<float> idf_all;                  // the base vectorizers' idf side by side (hstack column order)
+    mutable PinnedStage stage;
+    // c_tfidf_predict's stream, created once per (handle, device) instead of per call
+    mutable std::mutex stream_mu;
+    mutable hipStream_t stream = nullptr;
+    mutable int stream_device = -1;
+    // call with the staging lock (stage.mu) HELD and keep it until the stream has been synchronised: a caller that switched devices
+    // replaces the stream, which must not happen under another thread's transfer
+    hipStream_t stream_on(int device) const {
+        std::lock_guard<std::mutex> g(stream_mu);
+        if (stream && stream_device != device) { (void)hipSetDevice(stream_device); (void)hipStreamDestroy(stream); stream = nullptr; (void)hipSetDevice(device); }
+        if (!stream) { XRL_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)); stream_device = device; }
+        return stream;
+    }
+    ~TfidfHandle() { if (stream) { (void)hipSetDevice(stream_device); (void)hipStreamDestroy(stream); } }
+};
+
+// texts -> term counts (host threads, into pinned staging) -> device -> weighting + normalisation (K5): a query handle that owns its three arrays
+std::unique_ptr<Queries> tfidf_to_device(const TfidfHandle& H, const char* const* corpus, const size_t* doc_lens, size_t nr_doc, int threads, int device, hipStream_t s) {
+    if (nr_doc > 0xFFFFFFFFull) fail("tfidf: too many documents");
+    const TfidfVectorizer& V = H.v;
+    const uint32_t nb = (uint32_t)V.base.size(), rows = (uint32_t)nr_doc;
+    use_device(device);
+    std::lock_guard<std::mutex> stage_lock(H.stage.mu);          // held until the stream has consumed the staging buffer (the synchronize below)
+    if (!s) s = H.stream_on(device);                             // the handle's pooled stream, taken under the staging lock
+    std::vector<uint64_t> seg_ptr;
+    uint32_t* h_col = nullptr; float* h_cnt = nullptr; uint64_t nnz = 0;
+    V.count_corpus(corpus, doc_lens, nr_doc, threads, seg_ptr, [&](uint64_t n, uint32_t*& c, float*& v) {
+        char* base = static_cast<char*>(H.stage.need((size_t)n * 8 + 16));
+        c = h_col = reinterpret_cast<uint32_t*>(base); v = h_cnt = reinterpret_cast<float*>(base + (size_t)n * 4);
+        nnz = n;
+    });
+    auto q = std::make_unique<Queries>();
+    q->device = device; q->nnz = nnz;
+    DevBuf d_seg, d_idf, d_err;
+    d_seg.upload(seg_ptr);
+    q->idx.reserve((size_t)nnz * 4); q->val.reserve((size_t)nnz * 4);
+    if (nnz) {
+        XRL_HIP(hipMemcpyAsync(q->idx.p, h_col, (size_t)nnz * 4, hipMemcpyHostToDevice, s));
+        XRL_HIP(hipMemcpyAsync(q->val.p, h_cnt, (size_t)nnz * 4, hipMemcpyHostToDevice, s));
+    }
+    d_idf.upload(H.idf_all);
+    d_err.reserve(4); XRL_HIP(hipMemsetAsync(d_err.p, 0, 4, s));
+    for (uint32_t b = 0; b < nb; ++b) {
+        const TfidfBase& B = V.base[b];
+        launch_tfidf_weight(d_seg.as<uint64_t>(), q->idx.as<uint32_t>(), q->val.as<float>(), B.use_idf ? d_idf.as<float>() : nullptr, rows, V.nr_features,
+                            B.binary ? 1 : 0, B.sublinear_tf ? 1 : 0, B.norm_p, q->val.as<float>(), s, nb, b, d_err.as<uint32_t>());
+    }
+    // whole rows: the hstacked CSR's row pointer; the ensemble's normalisation (Vectorizer::predict, tfidf.hpp:1405-1430)
+    if (nb == 1) q->ptr = std::move(d_seg);
+    else {
+        std::vector<uint64_t> row_ptr((size_t)rows + 1);
+        for (size_t r = 0; r <= rows; ++r) row_ptr[r] = seg_ptr[r * nb];
+        q->ptr.upload(row_ptr);
+    }
+    if (nb > 1 || V.norm_p != V.base[0].norm_p)
+        launch_tfidf_weight(q->ptr.as<uint64_t>(), q->idx.as<uint32_t>(), q->val.as<float>(), nullptr, rows, V.nr_features, 0, 0, V.norm_p, q->val.as<float>(), s);
+    uint32_t err = 0;
+    XRL_HIP(hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, s));
+    XRL_HIP(hipStreamSynchronize(s));
+    if (err) fail("tfidf: a feature id outside the model's feature range");
+    q->dev.row_ptr = q->ptr.as<uint64_t>(); q->dev.col_idx = q->idx.as<uint32_t>(); q->dev.val = q->val.as<float>();
+    q->dev.rows = rows; q->dev.cols = V.nr_features; q->dev.dense = 0; q->dev.nnz = q->nnz;
+    return q;
+}
+}  // namespace
+
+extern "C" {
+
+void* c_tfidf_load(const char* model_dir) {
+    return guarded_value((void*)nullptr, [&]() -> void* {
+        if (!model_dir) fail("null model_dir");
+        auto h = std::make_unique<TfidfHandle>();
+        h->v.load(model_dir);
+        for (const auto& b : h->v.base) h->idf_all.insert(h->idf_all.end(), b.idf.begin(), b.idf.end());
+        return h.release();
+    });
+}
+
+void c_tfidf_destruct(void* ptr) { guarded([&] { delete static_cast<TfidfHandle*>(ptr); }); }
+
+uint32_t xrl_tfidf_nr_features(void* ptr) {
+    uint32_t v = 0;
+    guarded([&] { if (!ptr) fail("null vectorizer handle"); v = static_cast<TfidfHandle*>(ptr)->v.nr_features; });
+    return v;
+}
+
+// documents -> weighted CSR on the device -> the caller's arrays through ONE allocator call (shared by c_tfidf_predict and c_tfidf_predict_from_file)
+// The weighting half on the HOST, for calls of a handful of documents (the reference serves nr_doc == 1 with a direct host call, libpecos.cpp:437-439:
+// microseconds -- a device round trip costs a hundred times that).  tfidf.hpp:798-822 operation by operation in fp32, like the kernel
+// (csrc/xrl_features.hip): sequential norm in ascending feature order, separate multiply and add (-ffp-contract=off), glibc's logf (the reference's own).
+static void tfidf_weight_host(const uint64_t* row_ptr, const uint32_t* col, float* val, const float* idf, uint32_t rows, uint32_t cols, bool binary,
+                              bool sublinear, int norm_p, uint32_t seg_stride, uint32_t seg_off) {
+    if (norm_p != 1 && norm_p != 2) fail("tfidf: invalid normalize option, norm_p: [ 1| 2]");
+    for (uint32_t r = 0; r < rows; ++r) {
+        const uint64_t b = row_ptr[(uint64_t)r * seg_stride + seg_off], e = row_ptr[(uint64_t)r * seg_stride + seg_off + 1];
+        float denom = 0.0f;
+        for (uint64_t t = b; t < e; ++t) {
+            float v = binary ? 1.0f : val[t];
+            if (sublinear) v = (float)((double)std::log(v) + 1.0);
+            if (idf) {
+                if (col[t] >= cols) fail("tfidf: a feature id outside the model's feature range");
+                v = v * idf[col[t]];
+            }
+            val[t] = v;
+            const float term = norm_p == 1 ? std::fabs(v) : v * v;
+            denom = denom + term;
+        }
+        if (std::fabs(denom) < FLT_EPSILON) denom = 1.0f;
+        else if (norm_p == 2) denom = std::sqrt(denom);
+        for (uint64_t t = b; t < e; ++t) val[t] = val[t] / denom;
+    }
+}
+
+constexpr size_t kTfidfHostDocs = 4;   // c_tfidf_predict calls of at most this many documents are weighted on the host
+
+static void tfidf_predict_small_on_host(const TfidfHandle& H, const char* const* corpus, const size_t* doc_lens, size_t nr_doc, py_sparse_allocator_t pred_alloc) {
+    const TfidfVectorizer& V = H.v;
+    const uint32_t nb = (uint32_t)V.base.size(), rows = (uint32_t)nr_doc;
+    std::vector<uint64_t> seg_ptr;
+    std::vector<uint32_t> h_col; std::vector<float> h_val;
+    V.count_corpus(corpus, doc_lens, nr_doc, 1, seg_ptr, [&](uint64_t n, uint32_t*& c, float*& v) { h_col.resize(n + 1); h_val.resize(n + 1); c = h_col.data(); v = h_val.data(); });
+    const uint64_t nnz = seg_ptr.empty() ? 0 : seg_ptr.back();
+    for (uint32_t b = 0; b < nb; ++b) {
+        const TfidfBase& B = V.base[b];
+        tfidf_weight_host(seg_ptr.data(), h_col.data(), h_val.data(), B.use_idf ? H.idf_all.data() : nullptr, rows, V.nr_features, B.binary, B.sublinear_tf, B.norm_p, nb, b);
+    }
+    std::vector<uint64_t> row_ptr((size_t)rows + 1);
+    for (size_t r = 0; r <= rows; ++r) row_ptr[r] = seg_ptr[r * nb];
+    if (nb > 1 || V.norm_p != V.base[0].norm_p)
+        tfidf_weight_host(row_ptr.data(), h_col.data(), h_val.data(), nullptr, rows, V.nr_features, false, false, V.norm_p, 1, 0);
+    uint32_t* indices = nullptr; uint64_t* indptr = nullptr; float* data = nullptr;
+    pred_alloc(false, rows, V.nr_features, nnz, &indices, &indptr, &data);
+    if (!indptr || (nnz && (!indices || !data))) fail("allocator returned null");
+    std::memcpy(indptr, row_ptr.data(), ((size_t)rows + 1) * 8);
+    if (nnz) { std::memcpy(indices, h_col.data(), (size_t)nnz * 4); std::memcpy(data, h_val.data(), (size_t)nnz * 4); }
+}
+
+static void tfidf_predict_to_host(const TfidfHandle& H, const char* const* corpus, const size_t* doc_lens, size_t nr_doc, int threads, py_sparse_allocator_t pred_alloc) {
+    const char* hs = std::getenv("XRL_TFIDF_HOST_DOCS");                     // XRL_TFIDF_HOST_DOCS=0: always the device (tests; read per call)
+    if (!(hs && hs[0] == '0') && nr_doc <= kTfidfHostDocs) { tfidf_predict_small_on_host(H, corpus, doc_lens, nr_doc, pred_alloc); return; }
+    use_device(g_device);
+    // (stream = nullptr: tfidf_to_device takes the handle's pooled stream under its staging lock and holds the lock until it has synchronised)
+    std::unique_ptr<Queries> q = tfidf_to_device(H, corpus, doc_lens, nr_doc, threads, g_device, nullptr);
+    uint32_t* indices = nullptr; uint64_t* indptr = nullptr; float* data = nullptr;
+    pred_alloc(false, q->dev.rows, q->dev.cols, q->nnz, &indices, &indptr, &data);
+    if (!indptr || (q->nnz && (!indices || !data))) fail("allocator returned null");
+    XRL_HIP(hipMemcpy(indptr, q->dev.row_ptr, ((size_t)q->dev.rows + 1) * 8, hipMemcpyDeviceToHost));
+    if (q->nnz) {
+        // D2H into the pinned staging buffer (link speed), then host threads spread it over the allocator's fresh arrays: their first touch
+        // in parallel, instead of the runtime's single-threaded pageable path
+        std::lock_guard<std::mutex> stage_lock(H.stage.mu);
+        const size_t nb4 = (size_t)q->nnz * 4;
+        char* st = static_cast<char*>(H.stage.need(2 * nb4));
+        XRL_HIP(hipMemcpy(st, q->dev.col_idx, nb4, hipMemcpyDeviceToHost));
+        XRL_HIP(hipMemcpy(st + nb4, q->dev.val, nb4, hipMemcpyDeviceToHost));
+        parallel_copy(indices, st, nb4, threads);
+        parallel_copy(data, st + nb4, nb4, threads);
+    }
+}
+
+void c_tfidf_predict(void* ptr, void* corpus_ptr, const size_t* doc_lens, size_t nr_doc, int threads, py_sparse_allocator_t pred_alloc) {
+    guarded([&] {
+        if (!ptr || !pred_alloc) fail("c_tfidf_predict: null argument");
+        if (nr_doc == 0) fail("Invalid nr_doc 0");                         // libpecos.cpp:442-444
+        if (!corpus_ptr || !doc_lens) fail("c_tfidf_predict: null corpus");
+        require_gpu();
+        tfidf_predict_to_host(*static_cast<TfidfHandle*>(ptr), static_cast<const char* const*>(corpus_ptr), doc_lens, nr_doc, threads, pred_alloc);
+    });
+}
+
+// c_tfidf_predict_from_file (libpecos.cpp:413-425 -> Vectorizer::predict_from_file, tfidf.hpp:1041-1120, 1365-1389): one document per LINE of the
+// file.  The reference cuts the file into chunks at newlines (file_util.hpp:180-200) and every chunk into lines (append_lines_to_string_view,
+// tfidf.hpp:279-294): every '\n' ends a document (empty lines are documents), and a last line WITHOUT a newline is a document too -- with the
+// terminating NUL that load_file_block appends counted into its length (tfidf.hpp:290-293 takes `end - start` after the loop has walked over it),
+// which is reproduced here.  buffer_size only sizes the reference's read chunks: the file is read whole.
+void c_tfidf_predict_from_file(void* ptr, void* corpus_fname_ptr, size_t fname_len, size_t buffer_size, int threads, py_sparse_allocator_t pred_alloc) {
+    (void)buffer_size;
+    guarded([&] {
+        if (!ptr || !pred_alloc || !corpus_fname_ptr) fail("c_tfidf_predict_from_file: null argument");
+        require_gpu();
+        const std::string fname(static_cast<const char*>(corpus_fname_ptr), fname_len);
+        std::FILE* fp = std::fopen(fname.c_str(), "rb");
+        if (!fp) fail("c_tfidf_predict_from_file: can't read " + fname);
+        std::vector<char> buf;
+        {
+            std::fseek(fp, 0, SEEK_END);
+            const long sz = std::ftell(fp);
+            std::fseek(fp, 0, SEEK_SET);
+            if (sz < 0) { std::fclose(fp); fail("c_tfidf_predict_from_file: can't size " + fname); }
+            buf.resize((size_t)sz + 1);
+            const size_t got = sz ? std::fread(buf.data(), 1, (size_t)sz, fp) : 0;
+            std::fclose(fp);
+            if (got != (size_t)sz) fail("c_tfidf_predict_from_file: error reading " + fname);
+            buf[(size_t)sz] = '\0';
+        }
+        const size_t n = buf.size() - 1;
+        std::vector<const char*> docs; std::vector<size_t> lens;
+        size_t start = 0;
+        for (size_t i = 0; i < n; ++i)
+            if (buf[i] == '\n') { docs.push_back(buf.data() + start); lens.push_back(i - start); start = i + 1; }
+        if (start < n) { docs.push_back(buf.data() + start); lens.push_back(n + 1 - start); }   // (the NUL is part of the reference's last document)
+        if (docs.empty()) fail("c_tfidf_predict_from_file: " + fname + " holds no document");
+        tfidf_predict_to_host(*static_cast<TfidfHandle*>(ptr), docs.data(), lens.data(), docs.size(), threads, pred_alloc);
+    });
+}
+
+void* xrl_tfidf_predict_device(void* vectorizer, void* model, void* corpus_ptr, const size_t* doc_lens, size_t nr_doc, int threads) {
+    return guarded_value((void*)nullptr, [&]() -> void* {
+        if (!vectorizer) fail("xrl_tfidf_predict_device: null vectorizer handle");
+        if (nr_doc && (!corpus_ptr || !doc_lens)) fail("xrl_tfidf_predict_device: null corpus");
+        Model& m = *as_model(model);
+        const TfidfHandle& H = *static_cast<TfidfHandle*>(vectorizer);
+        return tfidf_to_device(H, static_cast<const char* const*>(corpus_ptr), doc_lens, nr_doc, threads, m.device, m.stream).release();
+    });
+}
+
+void* xrl_queries_concat_handle(void* model, void* queries, uint32_t dense_cols, const float* d_emb, int normalize_emb, void* hip_stream) {
+    if (!queries) { set_err("xrl_queries_concat_handle: null query handle"); return nullptr; }
+    const Queries& q = *static_cast<Queries*>(queries);
+    if (q.dev.dense) { set_err("xrl_queries_concat_handle: the query handle must hold a CSR"); return nullptr; }
+    return xrl_queries_concat_device_ex(model, q.dev.rows, q.dev.cols, q.dev.row_ptr, q.dev.col_idx, q.dev.val, q.dev.nnz, dense_cols, d_emb, normalize_emb, hip_stream);
+}
+
+// host only (no GPU): the hstacked TERM-COUNT CSR the device weighting starts from -- what the tokenizer and the n-gram lookup produce
+void xrl_tfidf_counts(void* ptr, void* corpus_ptr, const size_t* doc_lens, size_t nr_doc, int threads, py_sparse_allocator_t alloc) {
+    guarded([&] {
+        if (!ptr || !alloc || (nr_doc && (!corpus_ptr || !doc_lens))) fail("xrl_tfidf_counts: null argument");
+        const TfidfVectorizer& V = static_cast<TfidfHandle*>(ptr)->v;
+        std::vector<uint64_t> seg_ptr;
+        uint32_t* indices = nullptr; uint64_t* indptr = nullptr; float* data = nullptr;
+        // the allocator's arrays ARE the destination: the worker threads fill (and first-touch) them in parallel
+        V.count_corpus(static_cast<const char* const*>(corpus_ptr), doc_lens, nr_doc, threads, seg_ptr, [&](uint64_t n, uint32_t*& c, float*& v) {
+            alloc(false, nr_doc, V.nr_features, n, &indices, &indptr, &data);
+            if (!indptr || (n && (!indices || !data))) fail("allocator returned null");
+            c = indices; v = data;
+        });
+        const size_t nb = V.base.size();
+        for (size_t r = 0; r <= nr_doc; ++r) indptr[r] = seg_ptr[r * nb];
+    });
+}
+
+}  // extern "C"

@@ -161,6 +161,88 @@ def test_model_compiler_tile_split_and_row_placement():
         clib.debug_layout_rows([3, 200, 1])
 
 
+def _host_batches_restated(indptr, rows, cols, host_batch_mb):
+    """The row-batch planning of the host ABI as host_compute wrote it inline before it became plan_row_batches, statement by
+    statement (Python floats are C doubles, int() is the cast to uint64_t, searchsorted 'left' is std::lower_bound)."""
+    is_csr = indptr is not None
+    elems = (int(indptr[rows]) if rows else 0) if is_csr else rows * cols
+    staged = elems * (8 if is_csr else 4) >= (32 << 20)
+    if not staged:
+        return [0, rows]                                  # the direct path: all rows in one predict
+    share = []
+    if rows >= 8192:
+        if is_csr:
+            mb = float(1 << 20) / 8.0
+            cur, pos = max(1, host_batch_mb) / 3.0, 0.0
+            cap = 3.0 * max(1, host_batch_mb)
+            while pos + cur * mb < float(elems) and len(share) < 31:
+                pos += cur * mb
+                share.append(int(pos))
+                cur = min(cap, cur * 1.6)
+            if share and float(elems) - float(share[-1]) < 0.25 * cur * mb:
+                share.pop()
+        else:
+            nb = min(8, max(1, rows // 65536))
+            share = [elems * b // nb for b in range(1, nb)]
+    n_batch = len(share) + 1
+    rb = [rows] * (n_batch + 1)
+    rb[0] = 0
+    for b in range(1, n_batch):
+        if is_csr:
+            rb[b] = int(np.searchsorted(indptr[:rows + 1], np.uint64(share[b - 1]), "left"))
+        else:
+            rb[b] = rows * b // n_batch
+        rb[b] = min(max(rb[b], rb[b - 1]), rows)
+    return rb
+
+
+def test_host_batch_plan():
+    """The row batches of the pipelined host ABI (no GPU): the boundaries decide how often the pruning feedback re-probes, so they are
+    held to the restatement above exactly."""
+    from pecos_amd import clib
+    rng = np.random.default_rng(20)
+    MB = (1 << 20) // 8                                   # (column id, value) pairs per megabyte
+
+    def ptr_of(lens):
+        return np.concatenate([[0], np.cumsum(np.asarray(lens, dtype=np.uint64))]).astype(np.uint64)
+
+    def even_ptr(rows, elems):
+        return (np.arange(rows + 1, dtype=np.uint64) * np.uint64(elems)) // np.uint64(rows)
+
+    def check(indptr, rows, cols, mb=12):
+        got = clib.debug_host_batches(indptr, rows, cols, mb).tolist()
+        want = _host_batches_restated(indptr, rows, cols, mb)
+        assert got == want, (rows, cols, mb, got, want)
+        return got
+
+    # under 32 MB -> one batch; fewer than 8192 rows at 40 MB -> one batch
+    assert check(ptr_of(rng.integers(0, 61, 100_000)), 100_000, 1000) == [0, 100_000]
+    assert check(even_ptr(8000, 40 * MB), 8000, 1000) == [0, 8000]
+    # Amazon-shaped: 490 000 rows, ~300 MB of pairs
+    amazon = ptr_of(rng.integers(10, 151, 490_000))
+    assert 280 * MB < int(amazon[-1]) < 320 * MB
+    n12 = len(check(amazon, 490_000, 135_909, 12))
+    n4 = len(check(amazon, 490_000, 135_909, 4))
+    n1 = len(check(amazon, 490_000, 135_909, 1))
+    assert 3 < n12 < n4 < n1 == 33                        # host_batch_mb 1 hits the cap of 32 batches
+    # host_batch_mb 12: the shares end at 4, 10.4, 20.64, 37.024, 63.2384 MB and the next batch would be 36 MB: a rest under a
+    # quarter of that (9 MB) joins the batch before it
+    dropped = check(even_ptr(100_000, int((63.2384 + 8.99) * MB)), 100_000, 5000)
+    kept = check(even_ptr(100_000, int((63.2384 + 9.01) * MB)), 100_000, 5000)
+    assert len(dropped) == 6 and len(kept) == 7
+    # long runs of empty rows around the boundaries: several shares end in the same row, the boundaries repeat and never go back
+    lens = np.zeros(50_000, dtype=np.uint64)
+    lens[100] = lens[30_000] = 24 * MB
+    holes = check(ptr_of(lens), 50_000, 1 << 26)
+    assert holes[:5] == [0, 101, 101, 101, 30_001] and np.all(np.diff(holes) >= 0)
+    lens = np.zeros(50_000, dtype=np.uint64)
+    lens[:64] = MB                                        # every element in the first rows, 49 936 empty rows behind them
+    check(ptr_of(lens), 50_000, 1 << 21)
+    # dense X of 768 columns: min(8, rows / 65536) equal parts
+    for rows, parts in ((65_535, 1), (65_536, 1), (200_000, 3), (1_000_000, 8)):
+        assert len(check(None, rows, 768)) == parts + 1
+
+
 def test_native_reader_survives_corrupt_files(tmp_path):
     # ADVICE r1: a truncated or corrupt model file must end in an xrl_last_error, never in an out-of-bounds access.  The host-only
     # parser (xrl_inspect_model -> load_csc_npz) is run over systematically damaged copies of a valid W.npz: truncations, byte
