@@ -88,7 +88,9 @@ void c_xlinear_compile_mmap_model(const char* model_path, const char* mmap_model
 void c_xlinear_destruct_model(void* ptr);
 
 /* libpecos.cpp:147-150; attr in {depth, nr_features, nr_labels, nr_codes} (inference.hpp:2367-2379).
- * Additive attrs: nr_pred_cols (columns of predict()'s CSR), nr_bucket_layers / nr_bitmap64_layers (layers on the bucket / 64-feature-word row lookup). */
+ * Additive attrs: nr_pred_cols (columns of predict()'s CSR), nr_bucket_layers / nr_bitmap64_layers (layers on the bucket / 64-feature-word row lookup),
+ * nr_dense_layers (layers that also carry the dense row format), merged01 (1: levels 0 and 1 are also held as one merged dense matrix, which
+ * K1Q's fused walk of the two levels reads with one load per feature; built only while its byte offsets fit 32 bits), device, nr_devices. */
 uint32_t c_xlinear_get_int_attr(void* ptr, const char* attr);
 
 /* libpecos.cpp:152-156 */

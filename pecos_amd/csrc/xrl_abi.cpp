@@ -118,6 +118,7 @@ uint32_t c_xlinear_get_int_attr(void* ptr, const char* attr) {
         else if (!std::strcmp(attr, "nr_dense_layers")) {    // additive: layers that also carry the dense row format (K1Q)
             for (auto& l : m.layers) v += l->dev.wd ? 1u : 0u;
         }
+        else if (!std::strcmp(attr, "merged01")) v = m.layers[0]->dev.wd01 ? 1u : 0u;   // additive: the root carries levels 0 + 1 as one merged dense matrix (LayerDev::wd01)
         else if (!std::strcmp(attr, "nr_devices")) v = 1u + (uint32_t)m.replicas.size();   // additive: devices behind the handle (xrl_set_option "devices")
         else fail(std::string(attr) + " is not implemented in get_int_attr.");
     });

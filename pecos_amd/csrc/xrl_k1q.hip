@@ -56,7 +56,8 @@ void launch_k1q(const LayerDev* const* Ls, const LayerPlan* Ps, int n, const Que
         const uint64_t c1 = ((uint64_t)K0 * Ls[1]->d_max_tiles) << Ls[1]->d_gp_log2;
         if (K0 >= 1 && K0 <= 64 && K0 <= Ps[0].k && Ps[1].beam_in >= K0 && c1 <= 64 && Ls[0]->w_rows == Ls[1]->w_rows && a.layer[0].ns == 1 && a.layer[1].ns == 1 && Ps[1].k <= 64) a.fuse01 = k1q_fuse01_enabled();
         // one load per feature for both levels when the model carries their merged matrix (finalize_model) and the candidate layout is the one it was built for
-        if (a.fuse01 == 2 && !(Ls[0]->wd01 && Ls[0]->wd01_c1 == c1 && c1 + K0 <= 64)) a.fuse01 = 1;
+        // ... and its byte offsets fit 32 bits (finalize_model does not build it otherwise; checked again where it is used)
+        if (a.fuse01 == 2 && !(Ls[0]->wd01 && Ls[0]->wd01_c1 == c1 && c1 + K0 <= 64 && k1q_merged01_addressable(Ls[0]->w_rows))) a.fuse01 = 1;
         a.wd01 = Ls[0]->wd01; a.wd01_c1 = Ls[0]->wd01_c1;
     }
     a.p_idx = prev.idx; a.p_val = prev.val; a.p_cnt = prev.cnt; a.p_stride = prev.stride;

@@ -627,7 +627,10 @@ void finalize_model(Model& m) {
         const char* e = std::getenv("XRL_K1Q_MERGE01");
         if (!(e && e[0] == '0') && d0.wd && d1.wd && d0.n_parents == 1 && d0.d_max_tiles == 1 && d0.w_rows == d1.w_rows && d1.n_parents == d0.n_children) {
             const uint64_t K0 = d0.n_children, c1 = (K0 * d1.d_max_tiles) << d1.d_gp_log2;
-            if (K0 >= 1 && c1 + K0 <= 64 && c1 <= d1.d_ld && K0 <= d0.d_ld) {
+            // k1q_layer01m reads the merged matrix as ONE buffer resource with 32-bit byte offsets (it has no BIGW form): (w_rows + 1) rows of 256 bytes
+            // must stay below the lane offset that switches a lane off, or num_records wraps (exactly 0 at w_rows + 1 == 2^24) and f * 256 aliases onto
+            // low rows.  Larger models keep the two levels' own matrices and the two-load walk (k1q_layer01<BIGW>).
+            if (K0 >= 1 && c1 + K0 <= 64 && c1 <= d1.d_ld && K0 <= d0.d_ld && k1q_merged01_addressable(d0.w_rows)) {
                 m.d_wd01.reserve(((size_t)d0.w_rows + 1) * 64 * 4);
                 launch_merge01(d0.wd, d0.d_ld, (uint32_t)K0, d1.wd, d1.d_ld, (uint32_t)c1, d0.w_rows + 1, m.d_wd01.as<uint32_t>(), nullptr);
                 XRL_HIP(hipStreamSynchronize(nullptr));

@@ -250,6 +250,8 @@ void ensure_device_csc(Layer& L);
 // xrl_k1q.hip: presence words of a dense-format layer (LayerDev::pres) from its matrix
 void k1t_shape(uint32_t max_tile_cols, int& g, int& nr);   // lanes per item / columns per lane of K1T for a layer's widest tile
 void launch_tile_rows(const LayerDev& L, uint64_t total_floats, uint32_t* wt, hipStream_t s);   // fills LayerDev::wt from the tile format on the device (xrl_k1t.hip)
+// the merged level-0/1 matrix (LayerDev::wd01: w_rows + 1 rows of 64 floats) is read with 32-bit byte offsets: usable only while they cannot wrap
+inline bool k1q_merged01_addressable(uint32_t w_rows) { return ((uint64_t)w_rows + 2) * 256ull < 0xFFFFFFF0ull; }
 void launch_merge01(const uint32_t* wd0, uint64_t ld0, uint32_t k0, const uint32_t* wd1, uint64_t ld1, uint32_t c1, uint32_t rows, uint32_t* out, hipStream_t s);
 void launch_presence(const uint32_t* wd, uint64_t ld, uint32_t rows, uint32_t gp_log2, uint32_t n_tiles, uint32_t pres_words, uint32_t* pres, hipStream_t s);
 void launch_densify(const uint64_t* col_ptr, const uint32_t* row_idx, const float* val, const uint32_t* src_col,
