@@ -25,6 +25,8 @@ struct Error : std::runtime_error {
             ::xrl::fail(std::string("HIP error: ") + hipGetErrorString(_e) + " at " #expr + \
                         " (" __FILE__ ":" + std::to_string(__LINE__) + ")");               \
     } while (0)
+// after a kernel launch: a bad launch configuration surfaces here, not at the next synchronisation
+#define XRL_LAUNCH_CHECK() XRL_HIP(hipGetLastError())
 
 // Grow-only device buffer.
 struct DevBuf {

@@ -1,4 +1,4 @@
-// Device-side helpers shared by the HIP kernels (xrl_kernels.hip, xrl_k1q.hip): the reference's
+// Device-side helpers shared by the HIP kernels (xrl_k1.hip, xrl_k1t.hip, xrl_k2.hip, xrl_k1q.hip): the reference's
 // post-processors, and a wavefront-wide top-k with the reference's ordering.
 #pragma once
 #include <hip/hip_runtime.h>

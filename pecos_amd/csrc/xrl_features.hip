@@ -64,7 +64,48 @@ void launch_tfidf_weight(const uint64_t* row_ptr, const uint32_t* col_idx, const
     if (norm_p != 1 && norm_p != 2) fail("tfidf: invalid normalize option, norm_p: [ 1| 2]");
     hipLaunchKernelGGL(tfidf_weight_kernel, dim3((rows + 3u) / 4u), dim3(256), 0, s, row_ptr, col_idx, count, idf, rows, cols, binary,
                        sublinear_tf, norm_p, out, seg_stride, seg_off, err);
-    XRL_HIP(hipGetLastError());
+    XRL_LAUNCH_CHECK();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Query-side helper for device-resident featurizers: [X_feat | X_emb] as one CSR, the query form of
+// XR-Transformer's concat_model (TransformerMatcher.concat_features, pecos/xmc/xtransformer/matcher.py:864-890 followed by
+// smat_util.hstack_csr): row r = the sparse features of row r, then dense_cols entries with column ids sparse_cols + j.
+// One wavefront per row; the output row pointer is closed-form (in_ptr[r] + r * dense_cols).
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+concat_csr_kernel(const uint64_t* __restrict__ in_ptr, const uint32_t* __restrict__ in_idx, const float* __restrict__ in_val,
+                  const float* __restrict__ emb, uint32_t rows, uint32_t sparse_cols, uint32_t dense_cols, int normalize,
+                  uint64_t* __restrict__ out_ptr, uint32_t* __restrict__ out_idx, float* __restrict__ out_val) {
+    const uint32_t r = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (r > rows) return;
+    const uint64_t ob = in_ptr[r] + (uint64_t)r * dense_cols;
+    if (lane == 0) out_ptr[r] = ob;
+    if (r == rows) return;
+    const uint64_t ib = in_ptr[r];
+    const uint32_t n = (uint32_t)(in_ptr[r + 1] - ib);
+    for (uint32_t t = lane; t < n; t += 64u) { out_idx[ob + t] = in_idx[ib + t]; out_val[ob + t] = in_val[ib + t]; }
+    const float* __restrict__ e = emb + (uint64_t)r * dense_cols;
+    // normalize != 0: sklearn.preprocessing.normalize(X_emb) (l2, rows; matcher.py:879-880) on the device: x / sqrt(sum x^2), rows of
+    // norm < 10 eps left as they are.  The sum is a wavefront tree reduction, so values agree with numpy's to ~1e-7 relative, not bitwise.
+    float scale = 1.0f;
+    if (normalize) {
+        float ss = 0.0f;
+        for (uint32_t j = lane; j < dense_cols; j += 64u) ss += e[j] * e[j];
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) ss += __shfl_xor(ss, d, 64);
+        const float nrm = sqrtf(ss);
+        scale = nrm < 10.0f * FLT_EPSILON ? 1.0f : nrm;
+    }
+    for (uint32_t j = lane; j < dense_cols; j += 64u) { out_idx[ob + n + j] = sparse_cols + j; out_val[ob + n + j] = normalize ? e[j] / scale : e[j]; }
+}
+
+void launch_concat_csr(const uint64_t* in_ptr, const uint32_t* in_idx, const float* in_val, const float* emb, uint32_t rows,
+                       uint32_t sparse_cols, uint32_t dense_cols, int normalize, uint64_t* out_ptr, uint32_t* out_idx, float* out_val, hipStream_t s) {
+    hipLaunchKernelGGL(concat_csr_kernel, dim3((rows + 1u + 3u) / 4u), dim3(256), 0, s, in_ptr, in_idx, in_val, emb, rows, sparse_cols,
+                       dense_cols, normalize, out_ptr, out_idx, out_val);
+    XRL_LAUNCH_CHECK();
 }
 
 }  // namespace xrl

@@ -7,7 +7,7 @@
 namespace xrl {
 
 constexpr int kFbLayers = 16;               // layers 0 .. kFbLayers-1 of a model take part
-// Word layout of the pinned, device-visible array PruneFeedback::host (the kernels that write it: xrl_k1q_impl.h, xrl_kernels.hip, xrl_k1t.hip):
+// Word layout of the pinned, device-visible array PruneFeedback::host (the kernels that write it: xrl_k1q_impl.h, xrl_k1.hip, xrl_k1t.hip):
 //   [0, kFbCounterWords)             K1Q's sampled counters {queries seen, queries that needed the second pass} per layer, a copy of
 //                                    PruneFeedback::dev made by the first wavefront of the next K1Q launch
 //   [kFbCounterWords, kFbHostWords)  the last stage's item count of tile-format layers (written by its K1 launch)

@@ -5,7 +5,7 @@
 // multiply-adds over weights that every other query of the same parent needs too.  K1Q (query-stationary) streams the
 // weight rows once PER QUERY -- BASELINE.json's dense-input config (D = 768, 3 M labels) then moves ~4 MB of weights per
 // query through the L2.  K1G turns the loop nest around, the way a GEMM does:
-//   * the layer's items are tile-sorted (counting sort of xrl_kernels.hip), so the queries that share a parent are adjacent;
+//   * the layer's items are tile-sorted (counting sort of xrl_sort.hip), so the queries that share a parent are adjacent;
 //   * a workgroup owns ONE parent and up to QB of its queries: the parent's weight panel W[k0..k0+64, cols] and the queries'
 //     X[q, k0..k0+64] are staged in LDS once per 64-feature step and every weight is reused QB times, every x value WP times;
 //   * lane (cl, ql) holds an RQ x RC register tile of accumulators: queries {ql + 8 r}, column PAIRS {16 c2 + 2 cl, +1}; per 4
@@ -28,10 +28,9 @@
 
 #include "xrl_device.h"
 #include "xrl_kernels.h"
+#include "xrl_items.h"
 
 namespace xrl {
-
-#define XRL_LAUNCH_CHECK() XRL_HIP(hipGetLastError())
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 
@@ -39,17 +38,11 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 #define XRL_K1G_UNROLL 2
 #endif
 
-struct alignas(16) ItemDescG {   // == ItemDesc of xrl_kernels.hip (K0 writes it)
-    uint32_t q, tile, out_off; float pscore;
-    uint64_t x_begin; uint32_t x_len, pad;
-};
-constexpr uint32_t kNoTileG = 0xFFFFFFFFu;
-
 // KC features per LDS step (template parameter); the x panel's row stride in LDS is KC + 4 floats: 16-byte aligned rows on distinct banks
 
 struct K1GArgs {
     LayerDev L; QueriesDev X;
-    const ItemDescG* items;       // tile-sorted, all active
+    const ItemDesc* items;        // tile-sorted, all active
     const uint32_t* start;        // [n_tiles+1] first sorted item of every tile
     const uint32_t* blk_start;    // [n_tiles+1] first workgroup of every tile
     float* cand;
@@ -153,7 +146,7 @@ __global__ void __launch_bounds__(256) k1g_kernel(K1GArgs a) {
     if (tid == 0) s_exact = 0;
     __syncthreads();
     for (uint32_t i = tid; i < (uint32_t)QB; i += 256u) {
-        ItemDescG it{}; it.tile = kNoTileG;
+        ItemDesc it{}; it.tile = kNoTile;
         if (i < nq) it = a.items[i0 + i];
         sRow[i] = it.q; sOut[i] = it.out_off; sPs[i] = it.pscore;
         // the layer has cells without a weight AND this query holds an inf / NaN: the whole workgroup takes the exact loop
@@ -354,7 +347,7 @@ void launch_k1g(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, cons
     const uint32_t wp = k1g_cols(L);
     if (wp == 0 || !X.dense) fail("k1g: layer not eligible");
     K1GArgs a;
-    a.L = L; a.X = X; a.items = static_cast<const ItemDescG*>(items_sorted); a.start = start; a.blk_start = blk_start; a.cand = cand; a.x_ok = x_ok;
+    a.L = L; a.X = X; a.items = static_cast<const ItemDesc*>(items_sorted); a.start = start; a.blk_start = blk_start; a.cand = cand; a.x_ok = x_ok;
     a.row0 = P.row0; a.pp_kind = P.pp.kind; a.pp_p = P.pp.p; a.first_layer = P.first_layer;
     // shapes per class of padded parent width, chosen from the measurements in profiles/r02_k1g_shapes.txt; tune.k1g_variant = 1
     // (xrl_set_option "k1g_variant") runs the one-wavefront-per-64-queries shapes they replaced (A/B, tests)

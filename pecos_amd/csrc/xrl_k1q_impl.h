@@ -3,7 +3,7 @@
 // top-k with the positional tie-break (:1223-1298) and the child re-ordering (:1919-1923) -- query-stationary:
 // a wavefront owns one query, its lanes own the query's candidate columns.
 //
-// Why a second row format.  K1 (xrl_kernels.hip) looks every query feature up in a per-tile rank-bitmap and
+// Why a second row format.  K1 (xrl_k1.hip) looks every query feature up in a per-tile rank-bitmap and
 // gathers the matching 8-byte entry rows; on MI355X it is bound by the NUMBER of cache lines those gathers
 // request from the L2 (profiles/): a probe line per (feature, tile), an extent line and 1..5 entry
 // lines per hit, three dependent loads deep.  For the narrow chunks of the upper tree levels (nr_splits = 16
@@ -42,8 +42,6 @@
 #include "xrl_kernels.h"
 
 namespace xrl {
-
-#define XRL_LAUNCH_CHECK() XRL_HIP(hipGetLastError())
 
 // what K1Q needs of one layer (a compact copy of LayerDev's dense-format fields + the layer's plan)
 struct K1QLayer {

@@ -1,7 +1,7 @@
 // K1T: the tile-format layer product on TILE ROWS held densely -- compute_sparse_predictions + chunk_ops<csr, bin_search>
 // (inference.hpp:925-1007, 769-813) + bias + post-processor + combine (:506-518, 192-240, 1360-1384) for sparse queries.
 //
-// The tile format's own kernel (k1_kernel, xrl_kernels.hip) keeps a tile row as a list of {column, value} entries and applies a
+// The tile format's own kernel (k1_kernel, xrl_k1.hip) keeps a tile row as a list of {column, value} entries and applies a
 // row to accumulators that live in LDS (the lanes of an item stride over the row's entries, each a read-modify-write of one LDS word).
 // On a model the bound does not prune (Amazon-670K-hard: 4.9 M leaf items of ~47 matched rows x ~26 entries) that kernel is bound by
 // vector-instruction issue: per matched row an extent lookup, a unit queue, a column select and an LDS read-add-write.
@@ -28,16 +28,7 @@
 
 namespace xrl {
 
-#define XRL_LAUNCH_CHECK() XRL_HIP(hipGetLastError())
-
 namespace {
-
-// block b of nb -> XCD b % 8 -> a contiguous eighth of the tile-sorted work (same mapping as k1_kernel)
-__device__ __forceinline__ uint32_t xcd_remap_t(uint32_t b, uint32_t nb) {
-    const uint32_t xcd = b & 7u, q = nb >> 3, r = nb & 7u;
-    const uint32_t base = (xcd < r) ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q;
-    return base + (b >> 3);
-}
 
 struct K1TArgs {
     LayerDev L;
@@ -108,16 +99,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))
         const uint32_t t0 = a.L.ptile[parent], t1 = a.L.ptile[parent + 1];
         return make_item((uint32_t)q, (cnt && t1 > t0) ? t0 : kNoTile, (uint32_t)q * a.cand_stride, ps, xb, xl);
     };
-    ItemDesc it = make_item(0u, kNoTile, 0u, 0.f, 0, 0u);
-    if (a.n_items) {   // tile-sorted list: every XCD takes a contiguous run of tiles
-        const uint32_t n = *a.n_items, nb = (n + W - 1) / W;
-        if (a.fb_out && vblock == 0 && lane == 0) *a.fb_out = n;
-        if (vblock >= nb) return;   // a compacted list (later stage of a pruned layer) usually fills a small part of the grid
-        { const uint64_t slot = (uint64_t)xcd_remap_t(vblock, nb) * W + grp; if (slot < n) it = a.items[slot]; }
-    } else {
+    ItemDesc it;
+    if (SEL && !a.items && !a.n_items) {   // derived items come in query order only, never with a list count (launch_k1t)
         const uint64_t slot = (uint64_t)vblock * W + grp;
-        if (slot < a.n_slots) it = (SEL && !a.items) ? derive_item(slot) : a.items[slot];
-    }
+        it = slot < a.n_slots ? derive_item(slot) : make_item(0u, kNoTile, 0u, 0.f, 0, 0u);
+    } else if (!fetch_item<W>(a.items, a.n_items, a.n_slots, a.fb_out, vblock, grp, lane, it)) return;
     bool active = it.tile != kNoTile;
     TileDesc td{};
     uint64_t xe = 0, cur = 0, wbase = 0;
@@ -140,11 +126,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))
             acc[k] = (a.bias_first && a.L.has_bias && c < td.ncols) ? bp[c] : 0.0f;   // chunk_ops<csr, hash>: 0.0 + bias * w first
         }
     }
-    const uint32_t* __restrict__ xi = a.X.col_idx;
-    const float* __restrict__ xv = a.X.val;
     const BmWord* __restrict__ bm = a.L.bitmap + (LK != 0 ? 0ull : (uint64_t)(active ? it.tile : 0u) * a.L.nwords);
     const BmWord64* __restrict__ bm64 = a.L.bitmap64 + (LK != 2 ? 0ull : (uint64_t)(active ? it.tile : 0u) * a.L.nwords64);
-    const unsigned long long below = (1ull << lig) - 1ull;
     const uint64_t xlast = xe > cur ? xe - 1 : 0;                       // a valid x index for clamped loads
     uint32_t nh = 0;                                                    // hits waiting in this item's queue
     bool nonfin = false;                                                // (wavefront-uniform) a queued hit carries a non-finite x
@@ -190,61 +173,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))
         {
             // ---- load step: U*G consecutive features of the item
             uint32_t f[U]; float v[U];
-            bool nf = false;
+            load_features<G, U>(a.X.col_idx, a.X.val, cur, xe, xlast, a.L.w_rows, lig, f, v);
+            bool nf = false;                   // a value of the row (not a clamped re-read past its end) is inf / NaN
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const uint64_t t = cur + (uint64_t)(u * G + lig);
-                const bool ok = t < xe;
-                const uint64_t tc = ok ? t : xlast;          // clamped: the load itself is unconditional
-                const uint32_t fi = xi[tc];
-                const float vi = xv[tc];
-                f[u] = (ok && fi < a.L.w_rows) ? fi : 0xFFFFFFFFu;
-                v[u] = vi;
-                nf = nf || (ok && (__float_as_uint(vi) & 0x7F800000u) == 0x7F800000u);
-            }
+            for (int u = 0; u < U; ++u) nf |= (cur + (uint64_t)(u * G + lig) < xe) & ((__float_as_uint(v[u]) & 0x7F800000u) == 0x7F800000u);
             nonfin = nonfin || __any(nf);
-            // ---- row lookup: is feature f a row of the tile, and which slot
+            // ---- row lookup: is feature f a row of the tile, and which -- the queue word is the byte offset of that row
             bool hit[U]; uint32_t off[U];
-            if (LK == 0) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const bool inr = f[u] != 0xFFFFFFFFu;
-                    const BmWord wi = bm[inr ? (f[u] >> 5) : 0u];
-                    const uint32_t b = f[u] & 31u;
-                    hit[u] = inr && ((wi.bits >> b) & 1u);
-                    off[u] = tbase + (wi.rank + (uint32_t)__popc(wi.bits & ((1u << b) - 1u))) * (uint32_t)(STRIDE * 4);
-                }
-            } else {
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const bool inr = f[u] != 0xFFFFFFFFu;
-                    const BmWord64 wi = bm64[inr ? (f[u] >> 6) : 0u];
-                    const uint32_t b = f[u] & 63u;
-                    const unsigned long long bits = ((unsigned long long)wi.hi << 32) | wi.lo;
-                    hit[u] = inr && ((bits >> b) & 1ull);
-                    off[u] = tbase + (wi.rank + (uint32_t)__popcll(bits & ((1ull << b) - 1ull))) * (uint32_t)(STRIDE * 4);
-                }
-            }
-            // ---- queue the hits in feature order.  If an item's queue fills up the step is abandoned at slice `skip`, the queue is
-            //      drained and the same step is re-loaded and resumed from that slice.
-            uint32_t done = skip;
-            bool stopped = false;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const unsigned long long m = __ballot(hit[u]);
-                const unsigned long long gm = (G == 64) ? m : ((m >> (grp * G)) & ((1ull << G) - 1ull));
-                const uint32_t cnt = (uint32_t)__popcll(gm);
-                if ((uint32_t)u >= done && !stopped) {
-                    if (nh + cnt <= (uint32_t)H) {
-                        if (hit[u]) my_hq[nh + (uint32_t)__popcll(gm & below)] = make_uint2(__float_as_uint(v[u]), off[u]);
-                        nh += cnt; done = u + 1;
-                    } else {
-                        stopped = true;
-                    }
-                }
-            }
-            if (done == (uint32_t)U) { if (cur < xe) cur += (uint64_t)U * G; skip = 0; }
-            else { skip = done; overflow = true; }
+            if (LK == 0) probe_bitmap32<U>(bm, f, hit, off, [&](const BmWord& w, uint32_t before) { return tbase + (w.rank + before) * (uint32_t)(STRIDE * 4); });
+            else probe_bitmap64<U>(bm64, f, hit, off, [&](const BmWord64& w, uint32_t before) { return tbase + (w.rank + before) * (uint32_t)(STRIDE * 4); });
+            // ---- queue the hits in feature order; on overflow the queue is drained outside this scope and the step resumed
+            overflow = queue_hits<G, U, H>(hit, v, off, my_hq, grp, lig, nh, skip, cur, xe);
         }
         if (__any(overflow)) drain_any();
     }
@@ -276,10 +215,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))
             const uint32_t c = (uint32_t)(NR * lig + k);
             key[k] = 0u; sb[k] = 0u;
             if (active && c < td.ncols) {
-                float s = acc[k];
-                if (add_bias) s = __fadd_rn(s, bp[c]);
-                float v = pp_transform<PPC>(a.pp_kind, a.pp_p, s);
-                if (!a.first_layer) v = pp_combine(a.pp_kind, v, it.pscore);
+                const float v = finish_score<PPC>(acc[k], add_bias, bp + c, a.pp_kind, a.pp_p, a.first_layer, it.pscore);
                 sb[k] = __float_as_uint(v); key[k] = score_key(v);
             }
         }
@@ -333,13 +269,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))
 #pragma unroll
     for (int k = 0; k < NR; ++k) {
         const uint32_t c = (uint32_t)(NR * lig + k);
-        if (c < td.ncols) {
-            float s = acc[k];
-            if (add_bias) s = __fadd_rn(s, bp[c]);
-            float v = pp_transform<PPC>(a.pp_kind, a.pp_p, s);
-            if (!a.first_layer) v = pp_combine(a.pp_kind, v, it.pscore);
-            out[c] = v;
-        }
+        if (c < td.ncols) out[c] = finish_score<PPC>(acc[k], add_bias, bp + c, a.pp_kind, a.pp_p, a.first_layer, it.pscore);
     }
 }
 

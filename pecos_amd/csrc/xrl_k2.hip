@@ -1,0 +1,255 @@
+// Per-query top-k of a layer's candidates and the winners' child ids, on gfx950 (64-wide wavefronts).
+//   K2 k2_topk_*       sorted_csr + reorder_prediction      inference.hpp:1223-1298, 1919-1923
+#include <hip/hip_runtime.h>
+
+#include "xrl_device.h"
+#include "xrl_kernels.h"
+
+namespace xrl {
+
+// ---------------------------------------------------------------------------------------------
+// K2: one wavefront per query.  Candidates are scanned in POSITION order; the running top-k list
+// is kept sorted by (value desc, position asc), which is the comparator of sorted_csr
+// (inference.hpp:1265-1273): a later candidate only displaces the current k-th if it is
+// STRICTLY greater, and is inserted after every element that is >= it.
+// ---------------------------------------------------------------------------------------------
+struct K2Args {
+    const uint32_t* chunk_col;
+    const uint32_t* perm_inv;
+    const uint32_t* p_idx; const uint32_t* p_cnt; uint32_t p_stride;
+    const uint32_t* cand_off; const uint32_t* ncand; const float* cand;
+    uint32_t* out_idx; float* out_val; uint32_t* out_cnt;
+    uint32_t nrows, beam_in, cand_stride, k, out_stride;
+    int implicit_root;
+    // exact bound pruning (k2_topk_wave only): rank_limit > 0 restricts the selection to the candidates of the first rank_limit beam
+    // slots and reports in done[q] whether that selection is already FINAL -- every candidate of a later slot scores at most its
+    // parent's score (transform <= 1 times / <= 0 plus the parent's score) and would lose a tie by position, so once k selected
+    // candidates score >= the next parent's score nothing can change.  skip_done: queries to leave untouched (second phase).
+    const float* p_val;
+    int mult;                    // the combiner multiplies (sigmoid, l{p}-hinge): a child of a parent with a NEGATIVE score (possible when an
+                                 // earlier layer used another post-processor) lies in [score, 0], so the bound is max(score, 0); additive
+                                 // combiners (log-*) add a transform <= 0: the bound is the score itself
+    uint32_t rank_limit;
+    uint32_t* done;
+    const uint32_t* skip_done;
+    const uint32_t* xok;         // [nrows] the pruning guard of every query (prune_guard_ok): 0 = never final before every candidate is scored
+};
+
+__device__ __forceinline__ uint32_t k2_child_id(const K2Args& a, uint64_t q, uint32_t pos) {
+    // position -> (beam slot, child) -> original child id (reorder_prediction, inference.hpp:1776-1784)
+    uint32_t parent = 0, off = 0;
+    if (!a.implicit_root) {
+        const uint32_t cnt = min(a.p_cnt[q], a.beam_in);
+        uint32_t jj = 0;
+        for (uint32_t j = 1; j < cnt; ++j) if (a.cand_off[q * a.beam_in + j] <= pos) jj = j; else break;
+        off = a.cand_off[q * a.beam_in + jj];
+        parent = a.p_idx[q * a.p_stride + jj];
+    }
+    const uint32_t child = a.chunk_col[parent] + (pos - off);
+    return a.perm_inv ? a.perm_inv[child] : child;
+}
+
+__global__ void __launch_bounds__(64) k2_topk_reg(K2Args a) {   // k <= 64: lane i holds the i-th best
+    const uint64_t q = blockIdx.x;
+    const int lane = threadIdx.x;
+    const uint32_t n = a.ncand[q], k = a.k;
+    const float* __restrict__ cv = a.cand + q * a.cand_stride;
+    float lv = -INFINITY, th = -INFINITY;
+    uint32_t lp = 0, m = 0;
+    constexpr int KB = 4;     // candidate batches (64 each) fetched per iteration: KB loads in flight
+    const uint32_t nlast = n ? n - 1 : 0;
+    for (uint32_t base0 = 0; base0 < n; base0 += 64 * KB) {
+        float vb[KB];
+#pragma unroll
+        for (int b = 0; b < KB; ++b) { const uint32_t p = base0 + b * 64 + lane; vb[b] = cv[p < n ? p : nlast]; }   // unconditional, clamped
+#pragma unroll
+        for (int b = 0; b < KB; ++b) {
+            const uint32_t base = base0 + b * 64;
+            const uint32_t p = base + lane;
+            const bool valid = p < n;
+            const float v = vb[b];
+            unsigned long long mask = __ballot(valid && (m < k || v > th));
+            while (mask) {
+                const int l = __ffsll((long long)mask) - 1;
+                mask &= mask - 1;
+                const float vv = __shfl(v, l);
+                if (m == k && !(vv > th)) continue;
+                const int r = __popcll(__ballot((uint32_t)lane < m && lv >= vv));
+                const float uv = __shfl_up(lv, 1);
+                const uint32_t up = __shfl_up(lp, 1);
+                if (lane > r) { lv = uv; lp = up; }
+                else if (lane == r) { lv = vv; lp = base + l; }
+                if (m < k) ++m;
+                th = (m == k) ? __shfl(lv, (int)k - 1) : -INFINITY;
+            }
+        }
+    }
+    if ((uint32_t)lane < m) {
+        a.out_idx[q * a.out_stride + lane] = k2_child_id(a, q, lp);
+        a.out_val[q * a.out_stride + lane] = lv;
+    }
+    if (lane == 0) a.out_cnt[q] = m;
+}
+
+__global__ void __launch_bounds__(64) k2_topk_lds(K2Args a) {   // any k that fits LDS: sorted list in LDS
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float* lv = reinterpret_cast<float*>(smem);
+    uint32_t* lp = reinterpret_cast<uint32_t*>(lv + a.k);
+    const uint64_t q = blockIdx.x;
+    const int lane = threadIdx.x;
+    const uint32_t n = a.ncand[q], k = a.k;
+    const float* __restrict__ cv = a.cand + q * a.cand_stride;
+    float th = -INFINITY;
+    uint32_t m = 0;
+    for (uint32_t base = 0; base < n; base += 64) {
+        const uint32_t p = base + lane;
+        const bool valid = p < n;
+        const float v = valid ? cv[p] : 0.f;
+        unsigned long long mask = __ballot(valid && (m < k || v > th));
+        while (mask) {
+            const int l = __ffsll((long long)mask) - 1;
+            mask &= mask - 1;
+            const float vv = __shfl(v, l);
+            if (m == k && !(vv > th)) continue;
+            uint32_t r = 0;
+            for (uint32_t i0 = 0; i0 < m; i0 += 64) {
+                const uint32_t i = i0 + lane;
+                r += (uint32_t)__popcll(__ballot(i < m && lv[i] >= vv));
+            }
+            const uint32_t e = (m < k) ? m : k - 1;        // elements [r, e) move up by one
+            for (uint32_t hi = e; hi > r;) {
+                const uint32_t lo = (hi - r > 64) ? hi - 64 : r;
+                const uint32_t i = lo + lane;
+                const bool mv = i < hi;
+                float tv = 0.f; uint32_t tp = 0;
+                if (mv) { tv = lv[i]; tp = lp[i]; }
+                wave_sync_lds();
+                if (mv) { lv[i + 1] = tv; lp[i + 1] = tp; }
+                wave_sync_lds();
+                hi = lo;
+            }
+            if (lane == 0) { lv[r] = vv; lp[r] = base + l; }
+            wave_sync_lds();
+            if (m < k) ++m;
+            th = (m == k) ? lv[k - 1] : -INFINITY;
+        }
+    }
+    wave_sync_lds();
+    for (uint32_t i = lane; i < m; i += 64) {
+        a.out_idx[q * a.out_stride + i] = k2_child_id(a, q, lp[i]);
+        a.out_val[q * a.out_stride + i] = lv[i];
+    }
+    if (lane == 0) a.out_cnt[q] = m;
+}
+
+// K2, register form (k <= 64, candidate rows of up to 64 * NS scores): the whole candidate row sits in registers
+// (candidate p = r*64 + lane) and wave_topk (xrl_device.h) selects and ranks with ballot bisection instead of
+// serial insertions.  Four queries (wavefronts) per workgroup.
+template <int NS>
+__global__ void __launch_bounds__(256) k2_topk_wave(K2Args a) {
+    __shared__ uint2 sc_all[4 * 64];
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t q32 = blockIdx.x * 4u + wave;
+    if (q32 >= a.nrows) return;
+    const uint64_t q = q32;
+    if (a.skip_done && a.skip_done[q]) return;
+    uint32_t n = min(a.ncand[q], (uint32_t)(64 * NS));
+    const uint32_t bcnt0 = a.implicit_root ? 1u : min(a.p_cnt[q], a.beam_in);
+    // (both loads are issued up front, whether or not the query has that many parents: no dependent round trips later)
+    const uint32_t rl = min(a.rank_limit, a.beam_in - 1u);
+    const uint32_t lim_off = a.rank_limit ? a.cand_off[q * a.beam_in + rl] : 0u;
+    const float ps_next = a.rank_limit ? a.p_val[q * a.p_stride + rl] : 0.0f;
+    const bool limited = a.rank_limit != 0u && bcnt0 > a.rank_limit;
+    if (limited) n = min(n, lim_off);
+    const float* __restrict__ cv = a.cand + q * a.cand_stride;
+    const uint32_t slast = a.cand_stride - 1u;                  // last float of the query's candidate row (the loads below do not wait for n)
+    // the beam's block offsets and parents, one per lane (beams of up to 64 parents): in flight while the candidates are ranked,
+    // so that mapping a winner's position back to its child needs no dependent loads afterwards
+    const uint32_t bcnt = a.implicit_root ? 1u : min(a.p_cnt[q], a.beam_in);
+    const bool lane_beam = !a.implicit_root && bcnt <= 64u;
+    uint32_t b_off = 0xFFFFFFFFu, b_par = 0u, b_cc = 0u;
+    if (lane_beam && (uint32_t)lane < bcnt) { b_off = a.cand_off[q * a.beam_in + lane]; b_par = a.p_idx[q * a.p_stride + lane]; b_cc = a.chunk_col[b_par]; }
+    uint32_t key[NS], sbits[NS], pos[NS];
+#pragma unroll
+    for (int r = 0; r < NS; ++r) {
+        const uint32_t p = (uint32_t)r * 64u + (uint32_t)lane;
+        const float v = cv[min(p, slast)];                         // unconditional, clamped to the row (positions >= n are masked below)
+        sbits[r] = __float_as_uint(v); pos[r] = p;
+        key[r] = p < n ? score_key(v) : 0u;
+    }
+    if (a.done) {   // (before the selection: it consumes the keys)
+        bool d = true;
+        // the k-th best >= the best any later slot can reach (a NaN parent score proves nothing: no pruning)
+        if (limited) d = a.xok[q] != 0u && ps_next == ps_next && wave_count_ge<NS>(key, score_key(a.mult ? fmaxf(ps_next, 0.0f) : ps_next)) >= a.k;
+        if (lane == 0) a.done[q] = d ? 1u : 0u;
+    }
+    uint32_t rank, sb, pp;
+    const uint32_t kk = wave_topk<NS>(key, sbits, pos, a.k, sc_all + wave * 64u, lane, rank, sb, pp);
+    uint32_t child;
+    if (lane_beam) {
+        uint32_t jj = 0;                                            // last beam slot whose block starts at or before the position
+        for (uint32_t j = 1; j < bcnt; ++j) jj = ((uint32_t)__builtin_amdgcn_readlane((int)b_off, (int)j) <= pp) ? j : jj;
+        const uint32_t off = (uint32_t)__shfl((int)b_off, (int)jj, 64), cc = (uint32_t)__shfl((int)b_cc, (int)jj, 64);
+        child = cc + (pp - off);
+        if ((uint32_t)lane < kk && a.perm_inv) child = a.perm_inv[child];
+    } else {
+        child = (uint32_t)lane < kk ? k2_child_id(a, q, pp) : 0u;
+    }
+    if ((uint32_t)lane < kk) {
+        a.out_idx[q * a.out_stride + rank] = child;
+        a.out_val[q * a.out_stride + rank] = __uint_as_float(sb);
+    }
+    if (lane == 0) a.out_cnt[q] = kk;
+}
+
+size_t k2_max_k() { return (160 * 1024) / 8; }
+
+bool k2_wave_path(const LayerPlan& P) { return P.k <= 64 && P.cand_stride <= 64u * 32u; }
+
+void launch_k2_topk(const LayerDev& L, const LayerPlan& P, BeamDev prev, const uint32_t* cand_off,
+                    const uint32_t* ncand, const float* cand, BeamDev out, hipStream_t s, uint32_t rank_limit, uint32_t limited_cands,
+                    uint32_t* done, const uint32_t* skip_done, const uint32_t* xok) {
+    if (P.nrows == 0) return;
+    K2Args a;
+    a.p_val = prev.val; a.rank_limit = rank_limit; a.done = done; a.skip_done = skip_done; a.xok = xok;
+    if (done && !xok) fail("k2: bound pruning needs the per-query guard flags");
+    a.mult = (P.pp.kind == PP_SIGMOID || P.pp.kind == PP_LP_HINGE) ? 1 : 0;
+    if ((rank_limit || done || skip_done) && !k2_wave_path(P)) fail("k2: bound pruning needs the register top-k path");
+    a.chunk_col = L.chunk_col; a.perm_inv = L.perm_inv;
+    a.p_idx = prev.idx; a.p_cnt = prev.cnt; a.p_stride = prev.stride;
+    a.cand_off = cand_off; a.ncand = ncand; a.cand = cand;
+    a.out_idx = out.idx; a.out_val = out.val; a.out_cnt = out.cnt;
+    a.nrows = P.nrows; a.beam_in = P.beam_in; a.cand_stride = P.cand_stride; a.k = P.k; a.out_stride = out.stride;
+    a.implicit_root = P.implicit_root;
+    if (P.k == 0) fail("k2: only_topk / beam_size resolved to 0");
+    // beyond the LDS kernel's reach (or forced, tests: k2_big_min_k): the segmented sort of xrl_topk_big.hip
+    if (!rank_limit && !done && !skip_done && (P.k > k2_max_k() || (P.tune.k2_big_min_k > 0 && P.k >= (uint32_t)P.tune.k2_big_min_k))) {
+        launch_k2_topk_big(L, P, prev, cand_off, ncand, cand, out.idx, out.val, out.cnt, out.stride, s);
+        return;
+    }
+    if (k2_wave_path(P)) {
+        // (a rank-limited selection looks at the first slots' candidates only: registers for that many)
+        const uint32_t ns = ((rank_limit ? std::min(P.cand_stride, std::max(1u, limited_cands)) : P.cand_stride) + 63u) / 64u;
+        const dim3 grid((P.nrows + 3u) / 4u), block(256);
+        if (ns <= 1) hipLaunchKernelGGL(k2_topk_wave<1>, grid, block, 0, s, a);
+        else if (ns <= 2) hipLaunchKernelGGL(k2_topk_wave<2>, grid, block, 0, s, a);
+        else if (ns <= 4) hipLaunchKernelGGL(k2_topk_wave<4>, grid, block, 0, s, a);
+        else if (ns <= 8) hipLaunchKernelGGL(k2_topk_wave<8>, grid, block, 0, s, a);
+        else if (ns <= 13) hipLaunchKernelGGL(k2_topk_wave<13>, grid, block, 0, s, a);
+        else if (ns <= 16) hipLaunchKernelGGL(k2_topk_wave<16>, grid, block, 0, s, a);
+        else if (ns <= 24) hipLaunchKernelGGL(k2_topk_wave<24>, grid, block, 0, s, a);
+        else hipLaunchKernelGGL(k2_topk_wave<32>, grid, block, 0, s, a);
+    } else if (P.k <= 64) {
+        hipLaunchKernelGGL(k2_topk_reg, dim3(P.nrows), dim3(64), 0, s, a);
+    } else {
+        const size_t lds = (size_t)P.k * 8;
+        if (P.k > k2_max_k()) fail("k2: only_topk/beam_size " + std::to_string(P.k) + " exceeds the device limit " + std::to_string(k2_max_k()));
+        if (lds > 48 * 1024)   // per DEVICE attribute: set on every large launch
+            XRL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k2_topk_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(k2_topk_lds, dim3(P.nrows), dim3(64), lds, s, a);
+    }
+    XRL_LAUNCH_CHECK();
+}
+
+}  // namespace xrl

@@ -1,4 +1,4 @@
-// Launch interface of the HIP kernels (xrl_kernels.hip).  All pointers are device pointers.
+// Launch interface of the HIP kernels (the xrl_*.hip units).  All pointers are device pointers.
 #pragma once
 #include "xrl_model.h"
 

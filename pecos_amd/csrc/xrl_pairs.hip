@@ -24,8 +24,6 @@
 
 namespace xrl {
 
-#define XRL_LAUNCH_CHECK() XRL_HIP(hipGetLastError())
-
 constexpr int PG = 16;            // lanes per pair
 constexpr int PAIRS_PER_BLOCK = 256 / PG;
 

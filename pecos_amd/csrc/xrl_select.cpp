@@ -5,7 +5,7 @@
 //   * per layer top-down, prolongate_sparse_predictions (:1302-1358) walks the previous layer's
 //     entries IN THEIR ORDER and appends, for each, the children (in C's stored order) that belong to
 //     this layer's pattern -- that walk defines the order of the output row;
-//   * scores come from the CSC route (vector_ops::inner_product, :1018-1078), K4 in xrl_kernels.hip.
+//   * scores come from the CSC route (vector_ops::inner_product, :1018-1078), K4 in xrl_pairs.hip.
 // The pattern bookkeeping is integer work on small sets and stays on the host; the inner products,
 // transform and combine run on the GPU, one launch per layer.
 #include <algorithm>

@@ -229,6 +229,98 @@ def test_full_width_rows_every_lookup(XLM, clib, oracle_mod, tmp_path):
                          om.predict(np.ascontiguousarray(X.toarray()), beam_size=128, only_topk=30), exact_scores=True, what=f"dense X, lookup={mode}")
 
 
+def _queue_stop_slices(present, feats, G, depth=64, step=64):
+    """The queue rule of the tile walk (queue_hits, xrl_items.h) for ONE item on the CPU: the row's features are walked in steps of `step`,
+    each in slices of G; a slice whose hits do not fit the `depth`-deep queue abandons the step there, the queue is drained and the step
+    resumes from that slice.  Returns the slice index of every such stop."""
+    U, stops, nh, skip, cur = step // G, [], 0, 0, 0
+    while cur < len(feats):
+        done, stopped = skip, False
+        for u in range(U):
+            cnt = sum(1 for f in feats[cur + u * G:cur + (u + 1) * G] if present(f))
+            if u >= done and not stopped:
+                if nh + cnt <= depth:
+                    nh, done = nh + cnt, u + 1
+                else:
+                    stopped = True
+        if done == U:
+            cur, skip = cur + step, 0
+        else:
+            skip, nh = done, 0
+            stops.append(done)
+    return stops
+
+
+def test_tile_walk_queue_overflow(XLM, clib, oracle_mod, tmp_path):
+    """The abandon-at-slice / resume-from-skip protocol of the hit queue that k1_kernel and k1t_kernel share, pinned: a weight pattern whose
+    dense query row fills the 64-deep queue in the MIDDLE of a 64-feature step for every lane grouping (G = 8, 16, 32; leaf chunks of 8, 16,
+    24 and 96 columns reach K1 <8,1> <16,1> <32,1> <32,3> and K1T alike), a row that fills the queue exactly, one that overflows it by one
+    hit, and the dense row again with +inf at a feature no leaf tile holds (K1T's exact drain across a resumed step).  Bit-exact against the
+    reference under every row lookup, K1 and K1T, natural and tile-sorted item order."""
+    import json
+    D, K0 = 192, 4
+    present = lambda f: f % 2 == 0 if 64 <= f < 96 else f % 4 != 3          # noqa: E731  feature f has a row in every leaf tile
+    feats = [list(range(192)), list(range(96)), list(range(97)), [], list(range(8)), list(range(192))]
+    assert [sum(map(present, fs)) for fs in feats[:3]] == [136, 64, 65]
+    for G in (8, 16, 32):
+        stops = [_queue_stop_slices(present, fs, G) for fs in feats[:3]]
+        print(f"G={G}: stop slices {stops}")
+        assert any(s >= 1 for s in stops[0]), (G, stops)                    # a resume with skip >= 1
+        assert stops[1] == [] and len(stops[2]) == 1, (G, stops)            # exactly full: no overflow; one hit more: one
+    rng = np.random.default_rng(11)
+    vals = [rng.standard_normal(len(fs)).astype(np.float32) for fs in feats]
+    vals[5] = vals[0].copy(); vals[5][151] = np.inf
+    assert not present(151)
+    X = smat.csr_matrix((np.concatenate(vals), np.concatenate([np.asarray(fs, np.int64) for fs in feats]),
+                         np.cumsum([0] + [len(fs) for fs in feats])), shape=(len(feats), D), dtype=np.float32)
+    X.sort_indices()
+    for c in (8, 16, 24, 96):
+        folder = str(tmp_path / f"m{c}")
+        for d, (K, Kp) in enumerate(((K0, 1), (K0 * c, K0))):
+            lf = os.path.join(folder, "ranker", f"{d}.model"); os.makedirs(lf, exist_ok=True)
+            W = rng.standard_normal((D + 1, K)).astype(np.float32)
+            if d == 1:
+                for f in range(D):
+                    for p in range(K0):
+                        keep = rng.random(c) < 0.7
+                        keep[rng.integers(c)] = True                     # at least one weight
+                        W[f, p * c:(p + 1) * c] = np.where(keep & present(f), W[f, p * c:(p + 1) * c], np.float32(0.0))
+            smat.save_npz(os.path.join(lf, "W.npz"), smat.csc_matrix(W), compressed=False)
+            par = np.arange(K) * Kp // K
+            smat.save_npz(os.path.join(lf, "C.npz"), smat.csc_matrix((np.ones(K, np.float32), (np.arange(K), par)), shape=(K, Kp)), compressed=False)
+            json.dump({"model": "MLModel", "bias": 1.0, "pred_kwargs": {"only_topk": 20, "post_processor": "l3-hinge"}},
+                      open(os.path.join(lf, "param.json"), "w"))
+        json.dump({"model": "HierarchicalMLModel", "depth": 2}, open(os.path.join(folder, "ranker", "param.json"), "w"))
+        json.dump({"model": "XLinearModel"}, open(os.path.join(folder, "param.json"), "w"))
+        ref = oracle_mod.RefModel(folder) if oracle_mod.ref_available() else oracle_mod.OracleModel.load(folder)
+        kws = [dict(beam_size=4, only_topk=10), dict(beam_size=4, only_topk=10, post_processor="log-sigmoid")]
+        want = [ref.predict(X, **kw) for kw in kws]
+        for mode in ("bitmap", "bitmap64", "bucket"):
+            os.environ["XRL_LOOKUP"] = mode
+            try:
+                m = XLM.load(folder)
+            finally:
+                os.environ.pop("XRL_LOOKUP", None)
+            mc = m.model.model_chain
+            clib.set_option(mc, "dense_layers", 0)
+            try:
+                for tile_rows in (1, 0, 2):                                  # K1T on query-order launches (default) / K1 only / K1T everywhere
+                    for srt in (0, 1):                                       # items in natural order / tile-sorted
+                        clib.set_option(mc, "tile_rows", tile_rows)
+                        clib.set_option(mc, "sort_min_tiles", srt)
+                        for kw, w in zip(kws, want):
+                            got = m.predict(X, **kw)
+                            what = f"c={c} lookup={mode} tile_rows={tile_rows} sort_min_tiles={srt} {kw.get('post_processor', 'l3-hinge')}"
+                            if got.data.shape == w.data.shape:
+                                print(what, "score bit patterns that differ:", int(np.count_nonzero(got.data.view(np.uint32) != w.data.view(np.uint32))), "of", got.data.size)
+                            assert_same_topk(got, w, exact_scores=True, what=what)
+            finally:
+                clib.set_option(mc, "tile_rows", 1)
+                clib.set_option(mc, "sort_min_tiles", 0)
+                clib.set_option(mc, "dense_layers", 1)
+            del m
+
+
 def test_edge_cases(XLM, clib, oracle_mod, tmp_path):
     import xrl_synth
     folder = str(tmp_path / "m")
