@@ -132,7 +132,8 @@ struct Layer {
     uint64_t dense_bytes = 0;
     uint32_t bk_shift = 0, bk_n = 0, bk_levels = 0;
     LayerDev dev{};
-    uint64_t device_bytes = 0;
+    uint64_t device_bytes = 0;             // buffer_bytes() as of the last build step (+ Model::d_wd01 on the root layer)
+    uint64_t buffer_bytes() const;         // capacity of every DevBuf above
     // sum of the `beam` largest chunks: upper bound on candidates per query entering this layer
     uint64_t cand_bound(uint32_t beam) const;
 };
@@ -245,16 +246,16 @@ std::unique_ptr<Model> load_model_from_disk(const std::string& path, int weight_
 void finalize_model(Model& m);
 std::unique_ptr<Model> load_mmap_model_from_disk(const std::string& path);        // xrl_mmap.cpp
 void compile_mmap_model(const std::string& npz_path, const std::string& mmap_path);   // xrl_mmap.cpp
-void ensure_device_csc(Layer& L);
-// xrl_k1q.hip: memset wd to kMissing and scatter the CSC columns src_col[c] to padded column dst_off[c]
-// xrl_k1q.hip: presence words of a dense-format layer (LayerDev::pres) from its matrix
+void ensure_device_csc(Layer& L);   // upload W as CSC (original column ids) if not there yet
 void k1t_shape(uint32_t max_tile_cols, int& g, int& nr);   // lanes per item / columns per lane of K1T for a layer's widest tile
 void launch_tile_rows(const LayerDev& L, uint64_t total_floats, uint32_t* wt, hipStream_t s);   // fills LayerDev::wt from the tile format on the device (xrl_k1t.hip)
 // the merged level-0/1 matrix (LayerDev::wd01: w_rows + 1 rows of 64 floats) is read with 32-bit byte offsets: usable only while they cannot wrap
 inline bool k1q_merged01_addressable(uint32_t w_rows) { return ((uint64_t)w_rows + 2) * 256ull < 0xFFFFFFF0ull; }
 void launch_merge01(const uint32_t* wd0, uint64_t ld0, uint32_t k0, const uint32_t* wd1, uint64_t ld1, uint32_t c1, uint32_t rows, uint32_t* out, hipStream_t s);
+// xrl_k1q.hip: presence words of a dense-format layer (LayerDev::pres) from its matrix
 void launch_presence(const uint32_t* wd, uint64_t ld, uint32_t rows, uint32_t gp_log2, uint32_t n_tiles, uint32_t pres_words, uint32_t* pres, hipStream_t s);
+// xrl_k1q.hip: memset wd to kMissing and scatter the CSC columns src_col[c] to padded column dst_off[c]
 void launch_densify(const uint64_t* col_ptr, const uint32_t* row_idx, const float* val, const uint32_t* src_col,
-                    const uint32_t* dst_off, uint32_t n_children, uint32_t w_rows, uint64_t ld, uint32_t* wd, hipStream_t s);   // upload W as CSC (original column ids) if not there yet
+                    const uint32_t* dst_off, uint32_t n_children, uint32_t w_rows, uint64_t ld, uint32_t* wd, hipStream_t s);
 
 }  // namespace xrl

@@ -371,6 +371,103 @@ def test_edge_cases(XLM, clib, oracle_mod, tmp_path):
     assert_same_topk(m2.predict(Xq, beam_size=3, only_topk=7), o2.predict(Xq, beam_size=3, only_topk=7), exact_scores=True, what="ties")
 
 
+def test_model_compiler_format_switches(XLM, clib, oracle_mod, tmp_path):
+    # every "format declined or disabled" branch of the model compiler (xrl_model.cpp): the same small model loaded under each environment
+    # switch -- predictions stay bit-identical to the oracle, and layer_info / model_device_bytes / merged01 show what was (not) built
+    import xrl_synth
+    folder = str(tmp_path / "m")
+    xrl_synth.make_model(folder, 300, 400, [80, 50, 15], seed=11, shape=[3, 20, 400])
+    X = xrl_synth.make_queries(33, 300, 20, seed=12, relabel_seed=11)
+    om = oracle_mod.OracleModel.load(folder)
+    # beam 4 / top-k 6 fits K1Q's registers (dense format); beam 70 / top-k 100 does not (tile format: K1 / K1T)
+    kws = [dict(beam_size=b, only_topk=k, **pp) for b, k in ((4, 6), (70, 100)) for pp in ({}, {"post_processor": "noop"})]
+    want = [om.predict(X, **kw) for kw in kws]
+
+    def load(**env):
+        old = {k: os.environ.get(k) for k in env}
+        os.environ.update(env)
+        try:
+            m = XLM.load(folder)
+        finally:
+            for k, v in old.items():
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
+        h = m.model.model_chain
+        return m, h, [clib.layer_info(h, l) for l in range(3)]
+
+    def check(m, what):
+        for kw, w in zip(kws, want):
+            assert_same_topk(m.predict(X, **kw), w, exact_scores=True, what=f"{what} {kw}")
+
+    def dev_bytes(info):
+        return [i["device_bytes"] for i in info]
+
+    m0, h0, i0 = load()
+    check(m0, "default")
+    assert [i["dense"] for i in i0] == [1, 1, 1] and all(i["dense_bytes"] > 0 for i in i0), i0
+    assert clib.xlinear_get_int_attr(h0, "merged01") == 1                       # 3 + 3 * 8 = 27 columns <= 64
+    assert clib.model_device_bytes(h0) == sum(dev_bytes(i0))
+
+    # dense row format off / declined by its budget: the same layers, tile format only, and no merged level-0/1 matrix
+    off = [load(XRL_DENSE="0"), load(XRL_DENSE_MAX_MB="0")]
+    for (m, h, info), what in zip(off, ("XRL_DENSE=0", "XRL_DENSE_MAX_MB=0")):
+        assert all(i["dense"] == 0 and i["dense_bytes"] == 0 for i in info), (what, info)
+        assert clib.xlinear_get_int_attr(h, "merged01") == 0, what
+        check(m, what)
+    assert dev_bytes(off[0][2]) == dev_bytes(off[1][2])
+    assert clib.model_device_bytes(off[0][1]) == clib.model_device_bytes(off[1][1]) < clib.model_device_bytes(h0)
+    del off
+
+    # densely held tile rows (K1T) off / declined by their budget: option tile_rows then has nothing to select
+    off = [load(XRL_TILE_ROWS="0"), load(XRL_TILE_ROWS_MAX_MB="0")]
+    for (m, h, info), what in zip(off, ("XRL_TILE_ROWS=0", "XRL_TILE_ROWS_MAX_MB=0")):
+        assert all(a < b for a, b in zip(dev_bytes(info), dev_bytes(i0))), (what, info, i0)
+        try:
+            for tr in (0, 2, 1):
+                clib.set_option(h, "tile_rows", tr)
+                check(m, f"{what} tile_rows={tr}")
+        finally:
+            clib.set_option(h, "tile_rows", 1)
+    assert dev_bytes(off[0][2]) == dev_bytes(off[1][2])
+    del off
+
+    # rows packed instead of line-aligned: the same entries in the same tiles, without the padding
+    m, h, info = load(XRL_ROW_ALIGN="0")
+    assert [(i["entries"], i["tiles"]) for i in info] == [(i["entries"], i["tiles"]) for i in i0]
+    assert all(a <= b for a, b in zip(dev_bytes(info), dev_bytes(i0))), (info, i0)
+    check(m, "XRL_ROW_ALIGN=0")
+
+    # presence words: the default builds them for the leaf only (20 dense tiles >= 16: one 32-bit word per feature row, w_rows + 1 rows)
+    m, h, info = load(XRL_PRESENCE="0")
+    assert [b - a for a, b in zip(dev_bytes(info), dev_bytes(i0))] == [0, 0, (i0[2]["w_rows"] + 1) * 4], (info, i0)
+    assert clib.model_device_bytes(h) < clib.model_device_bytes(h0)
+    for mm, hh, what in ((m, h, "XRL_PRESENCE=0"), (m0, h0, "default")):
+        try:
+            for pres in (0, 2, 1):
+                clib.set_option(hh, "presence", pres)
+                check(mm, f"{what} presence={pres}")
+        finally:
+            clib.set_option(hh, "presence", 1)
+
+    m, h, info = load(XRL_K1Q_MERGE01="0")
+    assert clib.xlinear_get_int_attr(h, "merged01") == 0
+    assert [i["dense"] for i in info] == [1, 1, 1]
+    check(m, "XRL_K1Q_MERGE01=0")
+
+    # bucket lookup: the K1T format needs the slots a rank-bitmap returns, so no tile rows are built -- switching them off changes nothing
+    m, h, info = load(XRL_LOOKUP="bucket")
+    assert [i["lookup"] for i in info] == [1, 1, 1]
+    assert dev_bytes(info) == dev_bytes(load(XRL_LOOKUP="bucket", XRL_TILE_ROWS="0")[2])
+    check(m, "XRL_LOOKUP=bucket")
+    try:
+        clib.set_option(h, "dense_layers", 0)
+        check(m, "XRL_LOOKUP=bucket, tile format")
+    finally:
+        clib.set_option(h, "dense_layers", 1)
+
+
 def test_attributes_and_errors(XLM, clib, tmp_path):
     m = XLM.load(os.path.join(GOLDEN, "synth", "s_pruned"))
     info = clib.inspect_model(os.path.join(GOLDEN, "synth", "s_pruned", "ranker"))
