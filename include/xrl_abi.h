@@ -259,6 +259,29 @@ int xrl_predict_device_rows(void* model, void* queries, uint32_t beam_size, cons
                             uint32_t* d_out_cnt, uint32_t out_stride, void* hip_stream, int sync,
                             uint32_t row_begin, uint32_t row_count);
 
+/* Ensembles on the device (K6): the fixed-stride results of n_models <= 8 predicts over the SAME rows -- model m's d_idx[m]
+ * u32[rows*in_stride[m]], d_val[m] f32[rows*in_stride[m]], d_cnt[m] u32[rows], rows best first, as xrl_predict_device writes them;
+ * a count above its stride is read as the stride -- merged into ONE fixed-stride result in the caller's device buffers, without a
+ * visit to the host.  The four tables d_idx / d_val / d_cnt / in_stride are HOST arrays of n_models entries.  sum(in_stride) <= 1024.
+ *   mode 0 average       CsrEnsembler.average (pecos/utils/smat_util.py:828-842): per label the fp32 sum of its scores in model order; with
+ *                        two or more models a sum of exactly zero is not stored (scipy's CSR addition); rows ordered by (sum descending,
+ *                        NaN last, label ascending); values sum / n_models
+ *   mode 1 finish        Text2Text.predict's tail (pecos/apps/text2text/model.py:418-427): average; with a threshold, values <= *threshold and
+ *                        zeros are dropped; rows ordered by (value descending, NaN last, label ascending) and cut to only_topk (0 = all)
+ *   mode 2 rank_average  CsrEnsembler.rank_average (:845-859): position p of a row scores mm - p, mm = the longest row of any model in the
+ *                        call (reduced on the device, no host synchronisation); rows ordered by (sum descending, label ascending); values
+ *                        (double)sum / n_models, written as fp32
+ * threshold (NULL = none) and only_topk belong to mode finish.  out_stride >= the longest possible row: sum(in_stride), or
+ * min(sum(in_stride), only_topk) for finish with only_topk > 0.  Entries of an output row beyond its count are left untouched.
+ * The work runs on `hip_stream` of `device` -- NULL is the device's default (null) stream here: the call has no model handle whose stream it
+ * could borrow -- and the call returns without synchronising when `sync` == 0.  rows == 0 is a successful no-op.  Every argument is
+ * checked before a GPU is required.  Returns 0 on success, -1 with a message in xrl_last_error otherwise. */
+int xrl_ensemble_device(int device, uint32_t n_models, uint32_t rows,
+                        const uint32_t* const* d_idx, const float* const* d_val, const uint32_t* const* d_cnt, const uint32_t* in_stride,
+                        int mode /* 0 average, 1 finish, 2 rank_average */, const float* threshold /* NULL = none; finish only */,
+                        uint32_t only_topk /* 0 = all; finish only */,
+                        uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride, void* hip_stream, int sync);
+
 /* Effective only_topk of the last layer for the given override (0 = model default). */
 uint32_t xrl_effective_topk(void* model, uint32_t only_topk);
 

@@ -231,6 +231,8 @@ class corelib(object):
             "xrl_queries_concat_handle": (c_void_p, [c_void_p, c_void_p, c_uint32, c_void_p, c_int, c_void_p]),
             "xrl_predict_device": (c_int, [c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int]),
             "xrl_predict_device_rows": (c_int, [c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int, c_uint32, c_uint32]),
+            "xrl_ensemble_device": (c_int, [c_int, c_uint32, c_uint32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint32), c_int,
+                                            POINTER(c_float), c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int]),
             "xrl_predict_stats": (c_int, [c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, POINTER(c_double), c_uint32]),
             "xrl_effective_topk": (c_uint32, [c_void_p, c_uint32]),
             "xrl_profile_enable": (None, [c_void_p, c_int]),
@@ -599,6 +601,23 @@ class corelib(object):
             post_processor.encode("utf-8") if post_processor else None, only_topk or 0,
             c_void_p(d_idx), c_void_p(d_val), c_void_p(d_cnt), out_stride, c_void_p(stream or 0), 1 if sync else 0,
             int(row_begin), int(row_count))
+        self._check()
+        return rc
+
+    ENSEMBLE_MODES = {"average": 0, "finish": 1, "rank_average": 2}
+
+    def ensemble_device(self, device, rows, d_idx, d_val, d_cnt, in_stride, mode, threshold, only_topk, d_out_idx, d_out_val, d_out_cnt,
+                        out_stride, stream=None, sync=True):
+        """K6: merge the fixed-stride results of ``len(d_idx)`` models (lists of raw device addresses, one per model, and their row
+        strides) into one, on the device.  ``mode``: a key of ``ENSEMBLE_MODES`` or its number; ``threshold`` / ``only_topk``: mode
+        ``finish`` only, ``None`` = none."""
+        n = len(d_idx)
+        assert len(d_val) == n and len(d_cnt) == n and len(in_stride) == n
+        tab = lambda a: (c_void_p * max(n, 1))(*[c_void_p(int(x) if x else 0) for x in a])                   # noqa: E731
+        rc = self.clib_float32.xrl_ensemble_device(
+            int(device), n, int(rows), tab(d_idx), tab(d_val), tab(d_cnt), (c_uint32 * max(n, 1))(*[int(s) for s in in_stride]),
+            self.ENSEMBLE_MODES.get(mode, mode), None if threshold is None else ctypes.byref(c_float(threshold)), only_topk or 0,
+            c_void_p(d_out_idx), c_void_p(d_out_val), c_void_p(d_out_cnt), int(out_stride), c_void_p(stream or 0), 1 if sync else 0)
         self._check()
         return rc
 

@@ -128,4 +128,29 @@ size_t k2_max_k();
 void launch_k2_topk_big(const LayerDev& L, const LayerPlan& P, BeamDev prev, const uint32_t* cand_off, const uint32_t* ncand, const float* cand,
                         uint32_t* out_idx, float* out_val, uint32_t* out_cnt, uint32_t out_stride, hipStream_t s);
 
+// xrl_ensemble.hip, K6: the result rows of n_models predicts (xrl_predict_device's output form, idx / val row stride stride[m]) merged
+// into one fixed-stride result like CsrEnsembler.average, Text2Text.predict's tail or CsrEnsembler.rank_average do on the host.  The
+// pointer tables travel to the kernel by value.  Capacity: n_models <= 8, sum of the strides <= 1024 (one wavefront holds a row).
+constexpr int kEnsembleMaxModels = 8;
+constexpr uint32_t kEnsembleMaxTotal = 1024;
+enum { kEnsembleAverage = 0, kEnsembleFinish = 1, kEnsembleRankAverage = 2 };
+struct EnsembleArgs {
+    const uint32_t* idx[kEnsembleMaxModels];
+    const float* val[kEnsembleMaxModels];
+    const uint32_t* cnt[kEnsembleMaxModels];      // row lengths; a length above the stride counts as the stride
+    uint32_t stride[kEnsembleMaxModels];
+    uint32_t n_models, rows;
+    int mode;
+    int has_threshold;                            // finish only
+    float threshold;
+    uint32_t only_topk;                           // finish only; 0 = all
+    uint32_t* out_idx;
+    float* out_val;
+    uint32_t* out_cnt;
+    uint32_t out_stride;                          // >= the longest possible output row (the caller checks)
+};
+uint32_t ensemble_slots(uint32_t stride_sum);     // entries per lane (1, 2, 4, 8 or 16) of the instantiation that serves this total
+// mm_scratch: one device uint32 (rank_average only: the call's largest row length, reduced on `s` ahead of K6)
+void launch_ensemble(const EnsembleArgs& A, uint32_t* mm_scratch, hipStream_t s);
+
 }  // namespace xrl

@@ -9,6 +9,8 @@
 * :func:`predict_from_torch` -- X already in HBM as torch tensors (a GPU TF-IDF featurizer's CSR -- the reference's
   ``c_tfidf_predict`` produces that CSR on the host, pecos/core/libpecos.cpp:427-445 -- optionally with a dense embedding block to
   append on the device): no host round trip of X, results stay on the device.
+* :func:`ensemble_device` -- the results of several models merged on the device (K6) like ``CsrEnsembler.average`` / ``rank_average`` /
+  ``Text2Text.predict``'s tail; :func:`predict_text` and :class:`Text2Text` use it for ensembles that share a device.
 """
 import numpy as np
 import scipy.sparse as smat
@@ -216,7 +218,117 @@ def _predict_handle_to_csr(model, q, rows, beam_size=None, only_topk=None, post_
     return rows_to_csr(idx.cpu().numpy().view(np.uint32), sc.cpu().numpy(), cnt.cpu().numpy(), model.nr_pred_cols)
 
 
-def predict_text(vectorizer, models, corpus, X_emb=None, normalize_emb=True, threads=-1, **kwargs):
+ENSEMBLE_MAX_MODELS = 8          # capacity of the device merge (K6, xrl_ensemble_device): models, and entries of one row over all models
+ENSEMBLE_MAX_TOTAL = 1024
+
+
+def ensemble_device(results, mode="average", threshold=None, only_topk=None, stream=None, sync=True):
+    """The results of several models over the same rows merged ON THE DEVICE (K6): ``results`` is a list of ``(labels, scores, counts)``
+    CUDA tensors as :func:`predict_from_torch` returns them (int32 [rows, k_m], float32 [rows, k_m], int32 [rows]); the return value has
+    the same form, its rows ordered and valued like the host code's: ``mode="average"`` = :func:`ensemble_average`
+    (``CsrEnsembler.average``), ``"finish"`` = :meth:`Text2Text.finish` (average, ``threshold``, ``sorted_csr(only_topk)``),
+    ``"rank_average"`` = ``CsrEnsembler.rank_average``.  Runs on ``stream`` (a raw HIP stream; default: torch's current one); inputs and
+    outputs must be ordered on it."""
+    import torch
+    if mode not in clib.ENSEMBLE_MODES:
+        raise ValueError(f"ensemble mode {mode!r}: expected one of {sorted(clib.ENSEMBLE_MODES)}")
+    if not results:
+        raise ValueError("ensemble_device: no results given")
+    dev = results[0][0].device
+    rows = results[0][0].shape[0]
+    res = []
+    for idx, sc, cnt in results:
+        assert idx.is_cuda and idx.device == dev and sc.device == dev and cnt.device == dev, "ensemble_device: results on different devices"
+        assert idx.dtype == torch.int32 and sc.dtype == torch.float32 and cnt.dtype == torch.int32
+        assert idx.dim() == 2 and idx.shape == sc.shape and idx.shape[0] == rows and cnt.shape == (rows,)
+        res.append((idx.contiguous(), sc.contiguous(), cnt.contiguous()))
+    total = sum(r[0].shape[1] for r in res)
+    out_stride = min(total, only_topk) if (mode == "finish" and only_topk) else total
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        # (allocated on torch's current stream; with another `stream` nothing is queued on the buffers ahead of the kernel: no fill)
+        o_idx = torch.empty((rows, out_stride), dtype=torch.int32, device=dev)
+        o_sc = torch.empty((rows, out_stride), dtype=torch.float32, device=dev)
+        o_cnt = torch.empty((rows,), dtype=torch.int32, device=dev)
+        if rows and out_stride:
+            clib.ensemble_device(dev.index, rows, [r[0].data_ptr() for r in res], [r[1].data_ptr() for r in res], [r[2].data_ptr() for r in res],
+                                 [r[0].shape[1] for r in res], mode, threshold, only_topk, o_idx.data_ptr(), o_sc.data_ptr(),
+                                 o_cnt.data_ptr(), out_stride, stream=s or None, sync=sync)
+        else:
+            o_cnt.zero_()
+    return o_idx, o_sc, o_cnt
+
+
+def _ensemble_on_device(models, ensemble, only_topk, finish=None):
+    """Whether the ensemble of ``models`` merges on the device: one device, one feature count and one label count, within K6's capacity."""
+    if ensemble not in ("auto", "device", "host"):
+        raise ValueError(f"ensemble={ensemble!r}: expected 'auto', 'device' or 'host'")
+    if ensemble == "host":
+        return False
+    hs = [m.model.model_chain for m in models]
+    why = None
+    if len(models) > ENSEMBLE_MAX_MODELS:
+        why = f"{len(models)} models, more than {ENSEMBLE_MAX_MODELS}"
+    elif len({clib.xlinear_get_int_attr(h, "device") for h in hs}) != 1:
+        why = "the models live on different devices"
+    elif len({clib.xlinear_get_int_attr(h, "nr_features") for h in hs}) != 1:
+        why = "the models differ in nr_features: one X cannot serve them all"
+    elif len({m.nr_pred_cols for m in models}) != 1:
+        why = "the models differ in their label count"
+    elif sum(clib.effective_topk(h, only_topk) for h in hs) > ENSEMBLE_MAX_TOTAL:
+        why = f"the models' top-k sum to more than {ENSEMBLE_MAX_TOTAL} entries per row"
+    elif finish is not None and finish[1] is not None and finish[1] < 1:
+        why = "a final only_topk below 1 (sorted_csr then keeps nothing; K6 reads 0 as 'all')"
+    if why is not None and ensemble == "device":
+        raise ValueError(f"ensemble='device': {why}")
+    return why is None
+
+
+_ensemble_streams = {}
+
+
+def _predict_text_ensemble_device(vectorizer, models, corpus, X_emb, normalize_emb, threads, beam_size, only_topk, post_processor, finish):
+    """predict_text's ensemble on the device: ONE tokenisation and upload (and one concatenation with X_emb), every model's beam search on
+    that handle, the merge (K6) and nothing else on one stream, one synchronisation, one copy back, one CSR."""
+    import torch
+    from .distributed import rows_to_csr
+    hs = [m.model.model_chain for m in models]
+    dev = torch.device("cuda", clib.xlinear_get_int_attr(hs[0], "device"))
+    rows = len(corpus)
+    q = vectorizer.predict_device(models[0], corpus, threads=threads)
+    q2 = None
+    try:
+        if X_emb is not None:
+            assert X_emb.is_cuda and X_emb.dtype == torch.float32 and X_emb.shape[0] == rows
+            X_emb = X_emb.contiguous()
+            torch.cuda.current_stream().synchronize()
+            q2 = clib.queries_concat_handle(hs[0], q, X_emb.shape[1], X_emb.data_ptr(), normalize_emb=normalize_emb)
+        s = _ensemble_streams.get(dev.index)
+        if s is None:
+            s = _ensemble_streams[dev.index] = torch.cuda.Stream(device=dev)
+        mode, thr, topk = ("average", None, None) if finish is None else ("finish", finish[0], finish[1])
+        with torch.cuda.stream(s):
+            res = []
+            for h in hs:
+                k = clib.effective_topk(h, only_topk)
+                idx = torch.zeros((rows, k), dtype=torch.int32, device=dev)
+                sc = torch.zeros((rows, k), dtype=torch.float32, device=dev)
+                cnt = torch.zeros((rows,), dtype=torch.int32, device=dev)
+                if rows:
+                    clib.predict_device(h, q2 if q2 is not None else q, beam_size, post_processor, only_topk, idx.data_ptr(), sc.data_ptr(),
+                                        cnt.data_ptr(), k, stream=s.cuda_stream, sync=False)
+                res.append((idx, sc, cnt))
+            o_idx, o_sc, o_cnt = ensemble_device(res, mode=mode, threshold=thr, only_topk=topk, stream=s.cuda_stream, sync=False)
+            s.synchronize()
+            return rows_to_csr(o_idx.cpu().numpy().view(np.uint32), o_sc.cpu().numpy(), o_cnt.cpu().numpy(), models[0].nr_pred_cols)
+    finally:
+        torch.cuda.synchronize(dev)                # (also on an error: nothing may still read X when its handle goes)
+        clib.queries_free(q)
+        if q2 is not None:
+            clib.queries_free(q2)
+
+
+def predict_text(vectorizer, models, corpus, X_emb=None, normalize_emb=True, threads=-1, ensemble="auto", finish=None, **kwargs):
     """The reference's text call sites with X DEVICE-RESIDENT end to end:
 
     * ``Text2Text.predict`` (pecos/apps/text2text/model.py:416-422): ``X = preprocessor.predict(corpus); Y = [m.predict(X) ...]`` --
@@ -225,10 +337,21 @@ def predict_text(vectorizer, models, corpus, X_emb=None, normalize_emb=True, thr
     * ``XTransformer.predict`` (pecos/xmc/xtransformer/model.py:589-603): with ``X_emb`` (float32 [rows, H] CUDA tensor, the encoder's
       output) the concat model's input ``[X_feat | normalize(X_emb)]`` is assembled on the device as well.
 
+    Several models: ``ensemble="auto"`` (default) merges their results on the device (K6) -- one tokenisation and upload, one copy back --
+    where they share a device, ``nr_features`` and label count and their top-k sum to at most 1024 entries per row, and on the host
+    otherwise; ``"device"`` raises where "auto" would take the host path; ``"host"`` is the host path (one tokenisation, upload and copy
+    back per model, scipy's merge).  The result is the same bit for bit.  ``finish=(threshold, only_topk)`` also applies
+    :meth:`Text2Text.finish`'s threshold and cut to the merged rows (on whichever path).
+
     kwargs: beam_size, only_topk, post_processor.  Returns the predicted label matrix as scipy CSR (rows score-sorted)."""
     models = list(models) if isinstance(models, (list, tuple)) else [models]
     if isinstance(vectorizer, Preprocessor):
         vectorizer = vectorizer.vectorizer
+    if len(models) > 1 and _ensemble_on_device(models, ensemble, kwargs.get("only_topk"), finish):
+        return _predict_text_ensemble_device(vectorizer, models, corpus, X_emb, normalize_emb, threads, kwargs.get("beam_size"),
+                                             kwargs.get("only_topk"), kwargs.get("post_processor"), finish)
+    elif ensemble not in ("auto", "device", "host"):
+        raise ValueError(f"ensemble={ensemble!r}: expected 'auto', 'device' or 'host'")
     outs = []
     for m in models:
         q = vectorizer.predict_device(m, corpus, threads=threads)
@@ -245,6 +368,8 @@ def predict_text(vectorizer, models, corpus, X_emb=None, normalize_emb=True, thr
             clib.queries_free(q)
             if q2 is not None:
                 clib.queries_free(q2)
+    if finish is not None:
+        return Text2Text.finish(outs, threshold=finish[0], only_topk=finish[1])
     if len(outs) == 1:
         return outs[0]
     return ensemble_average(outs)                 # CsrEnsembler.average (smat_util.py:828-842): sum, sorted_csr, divide -- rows score-sorted like the reference's
@@ -324,8 +449,9 @@ class Text2Text:
     def predict(self, corpus, threshold=None, **kwargs):
         """Same arguments and result as the reference's ``Text2Text.predict`` (``threads`` applies to the tokenizer's host threads)."""
         threads = kwargs.pop("threads", -1)
-        Y_pred = [predict_text(self.preprocessor, m, corpus, threads=threads, **kwargs) for m, _ in self.xlinear_models]
-        return self.finish(Y_pred, threshold=threshold, only_topk=kwargs.get("only_topk", None))
+        # (an ensemble: one tokenisation and upload, the merge, threshold and cut on the device where predict_text finds that possible)
+        return predict_text(self.preprocessor, [m for m, _ in self.xlinear_models], corpus, threads=threads,
+                            finish=(threshold, kwargs.get("only_topk", None)), **kwargs)
 
     def get_output_item(self, output_id):
         return self.output_items[output_id]
