@@ -30,6 +30,13 @@
 // dense tile tt of that parent), column u & (Gp-1).  u is also the candidate's POSITION in the reference's
 // order (beam rank major, child order minor), which is what ties are broken by.
 //
+// Layout of this file.  Three layer bodies -- k1q_layer (any layer), k1q_layer01 and k1q_layer01m (levels 0 + 1 in one feature walk) -- are
+// outlines over parts that exist once: k1q_row (the query's row as a source of (feature, value) pairs, also the guard tail of k1q_kernel),
+// k1q_candidate (prolongation of one candidate), k1q_walk (the feature walk: chunks, the non-finite ballot, the batch forms, how a batch gets
+// its pairs), k1q_select01 (ranking level 0 and placing level 1 of the fused bodies) and k1q_store_beam.  A body supplies the walk with "issue
+// these U loads, then apply them" only.  k1q_layer's `pass` still carries a copy of the walk's loop: every shared form tried cost the fused
+// headline kernel spills (this kernel sits at 64 VGPRs and the 80-SGPR budget of 8 wavefronts; profiles/k1q_walk.md has the figures).
+//
 // This header holds the device code; the kernel instantiations are spread over xrl_k1q_n*.hip (one translation unit per candidate-register
 // bucket and post-processor class, so that `make -j` compiles them side by side) and the host side lives in xrl_k1q.hip.
 #pragma once
@@ -162,6 +169,115 @@ __device__ __forceinline__ uint32_t k1q_presence_mask(__amdgpu_buffer_rsrc_t pre
     return pm;
 }
 
+// The query's row as a source of (feature, value) pairs: its CSR row (chunk_ops<csr, bin_search>, inference.hpp:769-813: ascending features), or
+// the first dense_n values of its dense row, x gathered by row id (chunk_ops<drm, bin_search>, :815-839; fsrc stays null: feature = index).
+// room: elements readable from fsrc[0] / vsrc[0] on -- the tail batch of every row but the arrays' last may run on into the next row.
+struct K1QRow { const uint32_t* fsrc; const float* vsrc; uint32_t n; uint64_t room; };
+template <bool DENSEX>
+__device__ __forceinline__ K1QRow k1q_row(const QueriesDev& X, uint64_t xrow, uint32_t dense_n) {
+    if (DENSEX) return {nullptr, X.val + xrow * X.cols, dense_n, ((uint64_t)X.rows - xrow) * X.cols};
+    const uint64_t xb = X.row_ptr[xrow];
+    return {X.col_idx + xb, X.val + xb, (uint32_t)(X.row_ptr[xrow + 1] - xb), X.nnz - xb};
+}
+
+// Prolongation of one candidate: column `col` of dense tile `tt` of beam parent `parent` (v: the beam holds that parent) -> the candidate's BYTE
+// offset inside a feature row (d_ld < 2^30), its child id in the layer's column order, and whether it exists.
+struct K1QCand { uint32_t woff, child; bool valid; };
+__device__ __forceinline__ K1QCand k1q_candidate(const K1QLayer& Ly, bool v, uint32_t parent, uint32_t tt, uint32_t col) {
+    const uint32_t gl = Ly.d_gp_log2;
+    v = v && parent < Ly.n_parents;
+    if (!v) parent = 0;
+    uint32_t dtc, cb;
+    if (Ly.regular) { dtc = parent; cb = parent << gl; }                // one full tile per parent: nothing to look up (and no dependent round trips before the first weight load)
+    else {
+        const uint32_t dt = Ly.d_ptile[parent] + tt;
+        v = v && dt < Ly.d_ptile[parent + 1];
+        dtc = v ? dt : 0u;
+        cb = Ly.d_tcol[dtc];
+        const uint32_t ce = Ly.d_tcol[dtc + 1];
+        v = v && col < ce - cb;
+    }
+    return {v ? ((dtc << gl) + col) * 4u : 0u, v ? cb + col : 0u, v};
+}
+
+// The new beam, best first (reorder_prediction, inference.hpp:1919-1923): lane < kk holds the rank-th best candidate's score bits and child
+__device__ __forceinline__ void k1q_store_beam(const K1QLayer& Ly, uint32_t kk, uint32_t rank, uint32_t sb, uint32_t ch, uint32_t* s_bidx, float* s_bval, int lane) {
+    if ((uint32_t)lane < kk) {
+        s_bidx[rank] = Ly.perm_inv ? Ly.perm_inv[ch] : ch;
+        s_bval[rank] = __uint_as_float(sb);
+    }
+    wave_sync_lds();
+}
+
+// THE FEATURE WALK: the query's (feature, value) pairs, 64 at a time (a chunk: lane t holds pair t0 + t -- the pruning guard's maximum, and the
+// ballot "a value is not finite, or an id lies beyond the layer's rows"), and inside a chunk UU at a time (a batch).  For every batch the body is
+// called as batch(exact, getf, getx, tl): getf(u) / getx(u) are the id and value of the batch's u-th pair, tl its first slot in the chunk; the
+// body issues its UU x (registers) weight loads together and then applies them in feature order.  exact = std::false_type: every id is <= w_rows
+// (slots past the row's end name the all-missing row w_rows the model compiler appends, with x = 0) and every x finite, so `acc + x * w` is right
+// for every cell; std::true_type (a chunk the ballot flagged; RL = false also the tail batch of the arrays' last row): ids are clamped to the
+// all-missing row and the body must skip cells on the kMissing marker, like the reference's row walk.  on_chunk(exact, ib) runs once per chunk
+// before its batches (ib: this lane's feature id) -- the presence masks.
+//   RL = false: a batch's pairs are SCALAR loads (the row is wavefront-uniform): a full batch as it is; a row's tail batch reads on into the
+//               next row, the slots past the end neutralised; where the arrays end (room) the loads are clamped instead
+//   RL = true (sparse X): v_readlane from the chunk's registers at the point of use -- no scalar-load round trip per batch, no register arrays --
+//               and lanes past the chunk's end hold the padding pair, so the last batch needs no path of its own
+template <int UU, bool DENSEX, bool RL, class OnChunk, class Batch>
+__device__ __forceinline__ void k1q_walk(const K1QRow& row, uint32_t w_rows, int lane, uint32_t& xmx, OnChunk&& on_chunk, Batch&& batch) {
+    static_assert(!RL || (!DENSEX && 64 % UU == 0), "k1q_walk: the v_readlane form takes sparse X and a batch width that divides the chunk");
+    const uint32_t* __restrict__ fsrc = row.fsrc; const float* __restrict__ vsrc = row.vsrc;
+    const uint32_t n = row.n; const uint64_t room = row.room;
+    for (uint32_t t0 = 0; t0 < n; t0 += 64u) {
+        const uint32_t nc = min(64u, n - t0);
+        const uint32_t xraw = (uint32_t)lane < nc ? __float_as_uint(vsrc[t0 + (uint32_t)lane]) : 0u;
+        const uint32_t vb = xraw & 0x7FFFFFFFu;
+        xmx = max(xmx, vb);
+        // the fast loops take a feature id as it is (no clamp per feature): a chunk that holds an id beyond the layer's rows takes the exact
+        // loop, which sends such features to the all-missing row like the reference's row lookup finds nothing for them
+        const uint32_t ir = (!DENSEX && (uint32_t)lane < nc) ? fsrc[t0 + (uint32_t)lane] : RL ? w_rows : 0u;
+        const bool nonfinite = __ballot(vb >= 0x7F800000u || ir > w_rows) != 0ull;
+        const uint32_t ib = RL ? min(ir, w_rows) : ir;
+        on_chunk(nonfinite, ib);
+        if (RL) {
+            for (uint32_t tl = 0; tl < nc; tl += (uint32_t)UU) {
+                auto getf = [&](int u) { return (uint32_t)__builtin_amdgcn_readlane((int)ib, (int)tl + u); };
+                auto getx = [&](int u) { return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)xraw, (int)tl + u)); };
+                if (!nonfinite) batch(std::false_type{}, getf, getx, tl);
+                else batch(std::true_type{}, getf, getx, tl);
+            }
+            continue;
+        }
+        for (uint32_t t = t0; t < t0 + nc; t += (uint32_t)UU) {
+            uint32_t fs[UU]; float xs[UU];
+            auto getf = [&](int u) { return fs[u]; };
+            auto getx = [&](int u) { return xs[u]; };
+            if (!nonfinite && t + (uint32_t)UU <= t0 + nc) {             // a full batch: plain uniform loads
+#pragma unroll
+                for (int u = 0; u < UU; ++u) { fs[u] = DENSEX ? t + (uint32_t)u : fsrc[t + (uint32_t)u]; xs[u] = vsrc[t + (uint32_t)u]; }
+                batch(std::false_type{}, getf, getx, t - t0);
+            } else if (!nonfinite && (uint64_t)t + (uint32_t)UU <= room) {  // the row's tail: the loads run on into the next row, the slots past the end are neutralised
+#pragma unroll
+                for (int u = 0; u < UU; ++u) {
+                    const bool ok = t + (uint32_t)u < n;
+                    const uint32_t f = DENSEX ? t + (uint32_t)u : fsrc[t + (uint32_t)u];
+                    const float x = vsrc[t + (uint32_t)u];
+                    fs[u] = ok ? f : w_rows; xs[u] = ok ? x : 0.0f;
+                }
+                batch(std::false_type{}, getf, getx, t - t0);
+            } else {                                                      // non-finite x in the chunk, or the end of the X arrays: clamped loads, exact loop
+#pragma unroll
+                for (int u = 0; u < UU; ++u) {
+                    const bool ok = t + (uint32_t)u < n;
+                    const uint32_t ic = ok ? t + (uint32_t)u : n - 1u;
+                    const uint32_t f = DENSEX ? ic : fsrc[ic];
+                    const float x = vsrc[ic];
+                    fs[u] = ok ? min(f, w_rows) : w_rows; xs[u] = ok ? x : 0.0f;
+                }
+                batch(std::true_type{}, getf, getx, t - t0);
+            }
+        }
+    }
+}
+
 // One layer for one query (one wavefront): beam in s_bidx / s_bval[0..cnt) -> beam out in the same arrays; returns the new count.
 // BIASF: the accumulators start at the bias product (dense X; sparse X under HASH_CHUNKED, inference.hpp:716-722) instead of receiving it
 // last -- a compile-time switch: as a run-time one it cost the widest kernel 8 VGPRs and a wavefront per SIMD
@@ -183,21 +299,9 @@ __device__ __forceinline__ uint32_t k1q_layer(const K1QLayer& Ly, const QueriesD
         bool v = j < cnt;
         uint32_t parent = 0; float pscore = 1.0f;
         if (!Ly.implicit_root) { parent = s_bidx[v ? j : 0u]; pscore = s_bval[v ? j : 0u]; }
-        v = v && parent < Ly.n_parents;
-        if (!v) parent = 0;
-        uint32_t dtc, cb;
-        if (Ly.regular) { dtc = parent; cb = parent << gl; }            // one full tile per parent: nothing to look up (and no dependent round trips before the first weight load)
-        else {
-            const uint32_t dt = Ly.d_ptile[parent] + tt;
-            v = v && dt < Ly.d_ptile[parent + 1];
-            dtc = v ? dt : 0u;
-            cb = Ly.d_tcol[dtc];
-            const uint32_t ce = Ly.d_tcol[dtc + 1];
-            v = v && col < ce - cb;
-        }
-        woff[r] = v ? ((dtc << gl) + col) * 4u : 0u;                   // BYTE offset inside a feature row (d_ld < 2^30)
-        child[r] = v ? cb + col : 0u;
-        ps[r] = pscore; valid[r] = v;
+        const K1QCand c = k1q_candidate(Ly, v, parent, tt, col);
+        woff[r] = c.woff; child[r] = c.child; valid[r] = c.valid;
+        ps[r] = pscore;
         // dense queries: bias FIRST (inference.hpp:824-830); bias_prod holds fl32(bias * w) or +0.0
         acc[r] = (BIASF && Ly.has_bias) ? Ly.bias_prod[child[r]] : 0.0f;
     }
@@ -271,22 +375,13 @@ __device__ __forceinline__ uint32_t k1q_layer(const K1QLayer& Ly, const QueriesD
         auto body = [&](auto exact_tag, const uint32_t (&fs)[UU], const float (&xs)[UU], uint32_t tl) {
             body_f(exact_tag, [&](int u) { return fs[u]; }, [&](int u) { return xs[u]; }, tl);
         };
-        // the query's (feature, value) pairs: its CSR row (chunk_ops<csr, bin_search>, inference.hpp:769-813: ascending features), or every
-        // chunk row except the bias row with x gathered by row id (chunk_ops<drm, bin_search>, :815-839)
-        const uint32_t* __restrict__ fsrc = nullptr; const float* __restrict__ vsrc; uint32_t n; uint64_t room;
-        if (DENSEX) {
-            vsrc = X.val + xrow * X.cols;
-            n = Ly.has_bias ? w_rows - 1u : w_rows;
-            room = ((uint64_t)X.rows - xrow) * X.cols;                    // floats readable from vsrc[0]
-        } else {
-            const uint64_t xb = X.row_ptr[xrow];
-            n = (uint32_t)(X.row_ptr[xrow + 1] - xb);
-            fsrc = X.col_idx + xb; vsrc = X.val + xb;
-            room = X.nnz - xb;
-        }
+        // (dense X: every chunk row except the bias row)
+        const K1QRow row = k1q_row<DENSEX>(X, xrow, Ly.has_bias ? w_rows - 1u : w_rows);
+        const uint32_t* __restrict__ fsrc = row.fsrc; const float* __restrict__ vsrc = row.vsrc;
+        const uint32_t n = row.n; const uint64_t room = row.room;
         xn = n;
         constexpr uint32_t CH = 64u;
-        for (uint32_t t0 = 0; t0 < n; t0 += CH) {
+        for (uint32_t t0 = 0; t0 < n; t0 += CH) {                       // k1q_walk's loop, kept here by the register gate (profiles/k1q_walk.md): a fix to one goes to the other
             const uint32_t nc = min(CH, n - t0);
             // the chunk's values once per lane: the pruning guard's maximum, and "is every value finite"
             const uint32_t xraw = (uint32_t)lane < nc ? __float_as_uint(vsrc[t0 + (uint32_t)lane]) : 0u;
@@ -380,11 +475,43 @@ __device__ __forceinline__ uint32_t k1q_layer(const K1QLayer& Ly, const QueriesD
     // ---- top-k (value desc, position asc) and reorder_prediction: the next beam, best first
     uint32_t rank, sb, ch;
     const uint32_t kk = wave_topk<NS>(key, sbits, child, Ly.k, sc, lane, rank, sb, ch);
-    if ((uint32_t)lane < kk) {
-        s_bidx[rank] = Ly.perm_inv ? Ly.perm_inv[ch] : ch;
-        s_bval[rank] = __uint_as_float(sb);
+    k1q_store_beam(Ly, kk, rank, sb, ch, s_bidx, s_bval, lane);
+    return kk;
+}
+
+// The selection of the two fused bodies below.  Level 0's K0 scores s0v sit on lanes [base, base + K0) (v0), every lane v1 holds one level-1
+// candidate -- child1, of the parent in level-0 COLUMN j, tile tt, column col -- with its transformed score s1t.  Level 0 is ranked in (value
+// desc, position asc) order (first layer: no combine), level 1 is combined with its parent's score and moved to the lane its reference
+// position names (rank of the parent, tile, column), where the usual top-k runs; returns the new beam's count.
+__device__ __forceinline__ uint32_t k1q_select01(const K1QLayer& L1, float s0v, float s1t, bool v0, bool v1, uint32_t base, uint32_t K0, uint32_t j, uint32_t tt, uint32_t col,
+                                                  uint32_t child1, uint32_t* s_bidx, float* s_bval, uint2* sc, int lane) {
+    const uint32_t gl = L1.d_gp_log2, TT = L1.d_max_tiles;
+    const uint32_t l0 = (uint32_t)lane - base;
+    const uint32_t k0key = v0 ? score_key(s0v) : 0u;
+    uint32_t rank0 = 0;
+    for (uint32_t c = 0; c < K0; ++c) {
+        const uint32_t kc = (uint32_t)__builtin_amdgcn_readlane((int)k0key, (int)(base + c));
+        rank0 += (kc > k0key || (kc == k0key && c < l0)) ? 1u : 0u;
     }
+    const uint32_t jsrc = base + (j < K0 ? j : 0u);
+    const float psv = __shfl(s0v, (int)jsrc, 64);
+    float s1v = s1t;
+    if (!L1.first_layer) s1v = pp_combine(L1.pp_kind, s1t, psv);
+    const uint32_t prank = (uint32_t)__shfl((int)rank0, (int)jsrc, 64);
+    const uint32_t position = (((prank * TT) + tt) << gl) + col;       // < 64: one candidate register
+    // move every candidate to the lane its position names (slots no candidate names stay marked empty)
+    sc[lane] = make_uint2(0u, 0xFFFFFFFFu);
     wave_sync_lds();
+    if (v1) sc[position] = make_uint2(__float_as_uint(s1v), child1);
+    wave_sync_lds();
+    const uint2 mine = sc[lane];
+    wave_sync_lds();
+    uint32_t key[1], sbits[1], payload[1];
+    sbits[0] = mine.x; payload[0] = mine.y;
+    key[0] = mine.y != 0xFFFFFFFFu ? score_key(__uint_as_float(mine.x)) : 0u;
+    uint32_t rank, sb, ch;
+    const uint32_t kk = wave_topk<1>(key, sbits, payload, L1.k, sc, lane, rank, sb, ch);
+    k1q_store_beam(L1, kk, rank, sb, ch, s_bidx, s_bval, lane);
     return kk;
 }
 
@@ -413,105 +540,41 @@ __device__ __forceinline__ uint32_t k1q_layer01(const K1QLayer& L0, const K1QLay
     const uint32_t gl = L1.d_gp_log2, gmask = (1u << gl) - 1u, TT = L1.d_max_tiles;
     const uint32_t slot = (uint32_t)lane >> gl, col = (uint32_t)lane & gmask;
     const uint32_t j = TT == 1u ? slot : slot / TT, tt = TT == 1u ? 0u : slot - j * TT;
-    bool v1 = j < K0;
-    uint32_t parent = (uint32_t)__shfl((int)orig0, (int)(v1 ? j : 0u), 64);
-    v1 = v1 && parent < L1.n_parents;
-    if (!v1) parent = 0;
-    const uint32_t dt = L1.d_ptile[parent] + tt;
-    v1 = v1 && dt < L1.d_ptile[parent + 1];
-    const uint32_t dtc = v1 ? dt : 0u;
-    const uint32_t cb = L1.d_tcol[dtc], ce = L1.d_tcol[dtc + 1];
-    v1 = v1 && col < ce - cb;
-    const uint32_t woff1 = v1 ? ((dtc << gl) + col) * 4u : 0u;
-    const uint32_t child1 = v1 ? cb + col : 0u;
+    const K1QCand cd = k1q_candidate(L1, j < K0, (uint32_t)__shfl((int)orig0, (int)(j < K0 ? j : 0u), 64), tt, col);
+    const bool v1 = cd.valid;
+    const uint32_t woff1 = cd.woff, child1 = cd.child;
     float acc1 = (BIASF && L1.has_bias && v1) ? L1.bias_prod[child1] : 0.0f;
 
-    // ---- one walk over the query's features, UU at a time: 2 * UU loads in flight (scalar feature loads, buffer-resource rows, fast /
-    //      exact loops: see k1q_layer's pass)
+    // ---- one walk over the query's features, UU at a time: 2 * UU loads in flight
     const uint32_t* __restrict__ wd0 = L0.wd; const uint32_t* __restrict__ wd1 = L1.wd;
     const uint32_t ld0 = (uint32_t)(L0.d_ld * 4u), ld1 = (uint32_t)(L1.d_ld * 4u);   // bytes per feature row
     const uint32_t wr = L0.w_rows;                                      // == L1.w_rows (launch_k1q fuses the two levels only then)
-    const uint64_t xb = X.row_ptr[xrow];
-    const uint32_t xl = (uint32_t)(X.row_ptr[xrow + 1] - xb);
-    const uint32_t* __restrict__ xi = X.col_idx + xb;
-    const float* __restrict__ xv = X.val + xb;
-    const uint64_t room = X.nnz - xb;
-    auto body = [&](auto exact_tag, const uint32_t (&fs)[UU], const float (&xs)[UU]) {
+    uint32_t xmx = 0u;
+    k1q_walk<UU, false, false>(k1q_row<false>(X, xrow, 0u), wr, lane, xmx, [](bool, uint32_t) {}, [&](auto exact_tag, auto&& getf, auto&& getx, uint32_t) {
         constexpr bool EX = decltype(exact_tag)::value;
         uint32_t w0[UU], w1[UU];
 #pragma unroll
         for (int u = 0; u < UU; ++u) {
-            w0[u] = k1q_load_w<BIGW>(wd0, ld0, wr + 1u, fs[u], woff0);
-            w1[u] = k1q_load_w<BIGW>(wd1, ld1, wr + 1u, fs[u], woff1);
+            const uint32_t fu = getf(u);
+            w0[u] = k1q_load_w<BIGW>(wd0, ld0, wr + 1u, fu, woff0);
+            w1[u] = k1q_load_w<BIGW>(wd1, ld1, wr + 1u, fu, woff1);
         }
 #pragma unroll
         for (int u = 0; u < UU; ++u) {
-            const float s0 = __fadd_rn(acc0, __fmul_rn(xs[u], __uint_as_float(w0[u])));
+            const float xu = getx(u);
+            const float s0 = __fadd_rn(acc0, __fmul_rn(xu, __uint_as_float(w0[u])));
             acc0 = (EX && w0[u] == kMissing) ? acc0 : s0;
-            const float s1 = __fadd_rn(acc1, __fmul_rn(xs[u], __uint_as_float(w1[u])));
+            const float s1 = __fadd_rn(acc1, __fmul_rn(xu, __uint_as_float(w1[u])));
             acc1 = (EX && w1[u] == kMissing) ? acc1 : s1;
         }
-    };
-    for (uint32_t t0 = 0; t0 < xl; t0 += 64u) {
-        const uint32_t nc = min(64u, xl - t0);
-        const uint32_t vb = (uint32_t)lane < nc ? (__float_as_uint(xv[t0 + (uint32_t)lane]) & 0x7FFFFFFFu) : 0u;
-        const uint32_t ib = (uint32_t)lane < nc ? xi[t0 + (uint32_t)lane] : 0u;
-        const bool nonfinite = __ballot(vb >= 0x7F800000u || ib > wr) != 0ull;   // (or a feature id beyond the layers' rows: the exact loop clamps it, see k1q_layer)
-        for (uint32_t t = t0; t < t0 + nc; t += (uint32_t)UU) {
-            uint32_t fs[UU]; float xs[UU];
-            if (!nonfinite && t + (uint32_t)UU <= t0 + nc) {
-#pragma unroll
-                for (int u = 0; u < UU; ++u) { fs[u] = xi[t + (uint32_t)u]; xs[u] = xv[t + (uint32_t)u]; }
-                body(std::false_type{}, fs, xs);
-            } else if (!nonfinite && (uint64_t)t + (uint32_t)UU <= room) {
-#pragma unroll
-                for (int u = 0; u < UU; ++u) { const bool ok = t + (uint32_t)u < xl; const uint32_t f = xi[t + (uint32_t)u]; const float x = xv[t + (uint32_t)u]; fs[u] = ok ? f : wr; xs[u] = ok ? x : 0.0f; }
-                body(std::false_type{}, fs, xs);
-            } else {
-#pragma unroll
-                for (int u = 0; u < UU; ++u) {
-                    const bool ok = t + (uint32_t)u < xl; const uint32_t ic = ok ? t + (uint32_t)u : xl - 1u;
-                    const uint32_t f = xi[ic]; const float x = xv[ic];
-                    fs[u] = ok ? min(f, wr) : wr; xs[u] = ok ? x : 0.0f;
-                }
-                body(std::true_type{}, fs, xs);
-            }
-        }
-    }
-    // ---- level 0: bias, transform (first layer: no combine), rank of every node in (value desc, position asc) order
+    });
+    // ---- level 0: bias, transform
     if (!BIASF && L0.has_bias && v0) acc0 = __fadd_rn(acc0, L0.bias_prod[child0]);
     const float s0v = pp_transform<PPC>(L0.pp_kind, L0.pp_p, acc0);
-    const uint32_t k0key = v0 ? score_key(s0v) : 0u;
-    uint32_t rank0 = 0;
-    for (uint32_t c = 0; c < K0; ++c) {
-        const uint32_t kc = (uint32_t)__builtin_amdgcn_readlane((int)k0key, (int)c);
-        rank0 += (kc > k0key || (kc == k0key && c < (uint32_t)lane)) ? 1u : 0u;
-    }
-    // ---- level 1: bias, transform, combine with the parent's score; candidate position = (rank of the parent, tile, column)
+    // ---- level 1: bias, transform; k1q_select01 combines it with the parent's score
     if (!BIASF && L1.has_bias && v1) acc1 = __fadd_rn(acc1, L1.bias_prod[child1]);
-    float s1v = pp_transform<PPC>(L1.pp_kind, L1.pp_p, acc1);
-    const float psv = __shfl(s0v, (int)(j < K0 ? j : 0u), 64);
-    if (!L1.first_layer) s1v = pp_combine(L1.pp_kind, s1v, psv);
-    const uint32_t prank = (uint32_t)__shfl((int)rank0, (int)(j < K0 ? j : 0u), 64);
-    const uint32_t position = (((prank * TT) + tt) << gl) + col;       // < 64: one candidate register
-    // move every candidate to the lane its position names (slots no candidate names stay marked empty)
-    sc[lane] = make_uint2(0u, 0xFFFFFFFFu);
-    wave_sync_lds();
-    if (v1) sc[position] = make_uint2(__float_as_uint(s1v), child1);
-    wave_sync_lds();
-    const uint2 mine = sc[lane];
-    wave_sync_lds();
-    uint32_t key[1], sbits[1], payload[1];
-    sbits[0] = mine.x; payload[0] = mine.y;
-    key[0] = mine.y != 0xFFFFFFFFu ? score_key(__uint_as_float(mine.x)) : 0u;
-    uint32_t rank, sb, ch;
-    const uint32_t kk = wave_topk<1>(key, sbits, payload, L1.k, sc, lane, rank, sb, ch);
-    if ((uint32_t)lane < kk) {
-        s_bidx[rank] = L1.perm_inv ? L1.perm_inv[ch] : ch;
-        s_bval[rank] = __uint_as_float(sb);
-    }
-    wave_sync_lds();
-    return kk;
+    const float s1t = pp_transform<PPC>(L1.pp_kind, L1.pp_p, acc1);
+    return k1q_select01(L1, s0v, s1t, v0, v1, 0u, K0, j, tt, col, child1, s_bidx, s_bval, sc, lane);
 }
 
 
@@ -533,94 +596,36 @@ __device__ __forceinline__ uint32_t k1q_layer01m(const K1QLayer& L0, const K1QLa
     const uint32_t gl = L1.d_gp_log2, gmask = (1u << gl) - 1u, TT = L1.d_max_tiles;
     const uint32_t slot = (uint32_t)lane >> gl, col = (uint32_t)lane & gmask;
     const uint32_t j = TT == 1u ? slot : slot / TT, tt = TT == 1u ? 0u : slot - j * TT;
-    bool v1 = (uint32_t)lane < c1 && j < K0;
-    uint32_t parent = (uint32_t)__shfl((int)orig0, (int)(c1 + (v1 ? j : 0u)), 64);
-    v1 = v1 && parent < L1.n_parents;
-    if (!v1) parent = 0;
-    uint32_t dtc, cb;
-    if (L1.regular) { dtc = parent; cb = parent << gl; }
-    else {
-        const uint32_t dt = L1.d_ptile[parent] + tt;
-        v1 = v1 && dt < L1.d_ptile[parent + 1];
-        dtc = v1 ? dt : 0u;
-        cb = L1.d_tcol[dtc];
-        const uint32_t ce = L1.d_tcol[dtc + 1];
-        v1 = v1 && col < ce - cb;
-    }
-    const uint32_t child1 = v1 ? cb + col : 0u;
+    const bool j1 = (uint32_t)lane < c1 && j < K0;
+    const K1QCand cd = k1q_candidate(L1, j1, (uint32_t)__shfl((int)orig0, (int)(c1 + (j1 ? j : 0u)), 64), tt, col);
+    const bool v1 = cd.valid;
+    const uint32_t child1 = cd.child;
     // this lane's column of the merged row; lanes that hold neither a level-1 candidate nor a level-0 column address outside the resource (no request)
-    const uint32_t woff = v1 ? ((dtc << gl) + col) * 4u : v0 ? (c1 + l0) * 4u : 0xFFFFFFF0u;
+    const uint32_t woff = v1 ? cd.woff : v0 ? (c1 + l0) * 4u : 0xFFFFFFF0u;
     const float bp1 = (v1 && L1.has_bias) ? L1.bias_prod[child1] : 0.0f, bp0 = (v0 && L0.has_bias) ? L0.bias_prod[child0] : 0.0f;
     const float bp = v1 ? bp1 : bp0;
     float acc = BIASF ? bp : 0.0f;
 
     const uint32_t wr = L0.w_rows;                                      // == L1.w_rows
-    const uint64_t xb = X.row_ptr[xrow];
-    const uint32_t xl = (uint32_t)(X.row_ptr[xrow + 1] - xb);
-    const uint32_t* __restrict__ xi = X.col_idx + xb;
-    const float* __restrict__ xv = X.val + xb;
-    // One 64-feature chunk at a time in the lanes (lane t holds feature t0 + t); a batch takes its UU (feature id, value) pairs by v_readlane at
-    // the point of use -- no scalar loads, no register arrays -- and slots past the row's end name the all-missing row with x = 0, so the last
-    // batch needs no path of its own.  A chunk with a non-finite x or an id beyond the layers' rows runs the exact loop (skips cells on the marker).
-    auto body = [&](auto exact_tag, uint32_t ib, uint32_t xr, uint32_t tl) {
+    uint32_t xmx = 0u;
+    k1q_walk<UU, false, true>(k1q_row<false>(X, xrow, 0u), wr, lane, xmx, [](bool, uint32_t) {}, [&](auto exact_tag, auto&& getf, auto&& getx, uint32_t) {
         constexpr bool EX = decltype(exact_tag)::value;
         uint32_t w[UU];
 #pragma unroll
-        for (int u = 0; u < UU; ++u) w[u] = k1q_load_w<false>(wd01, 256u, wr + 1u, (uint32_t)__builtin_amdgcn_readlane((int)ib, (int)(tl + (uint32_t)u)), woff);
+        for (int u = 0; u < UU; ++u) w[u] = k1q_load_w<false>(wd01, 256u, wr + 1u, getf(u), woff);
 #pragma unroll
         for (int u = 0; u < UU; ++u) {
-            const float x = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)xr, (int)(tl + (uint32_t)u)));
-            const float sm = __fadd_rn(acc, __fmul_rn(x, __uint_as_float(w[u])));
+            const float sm = __fadd_rn(acc, __fmul_rn(getx(u), __uint_as_float(w[u])));
             acc = (EX && w[u] == kMissing) ? acc : sm;
         }
-    };
-    for (uint32_t t0 = 0; t0 < xl; t0 += 64u) {
-        const uint32_t nc = min(64u, xl - t0);
-        const uint32_t xr = (uint32_t)lane < nc ? __float_as_uint(xv[t0 + (uint32_t)lane]) : 0u;
-        const uint32_t ir = (uint32_t)lane < nc ? xi[t0 + (uint32_t)lane] : wr;
-        const bool nonfinite = __ballot((xr & 0x7FFFFFFFu) >= 0x7F800000u || ir > wr) != 0ull;
-        const uint32_t ib = min(ir, wr);                                  // (features beyond the layers' rows: the all-missing row, like the reference's lookup finds nothing)
-        for (uint32_t tl = 0; tl < nc; tl += (uint32_t)UU) {
-            if (!nonfinite) body(std::false_type{}, ib, xr, tl);
-            else body(std::true_type{}, ib, xr, tl);
-        }
-    }
+    });
     // ---- bias last, transform (one pass when both levels share the post-processor)
     if (!BIASF) acc = __fadd_rn(acc, bp);      // (bp is +0.0 where the level has no bias or the column no bias entry: leaves the accumulator as it is, like the `if` of k1q_layer01 -- accumulators are never -0.0)
     float sv;
     if (L0.pp_kind == L1.pp_kind && L0.pp_p == L1.pp_p) sv = pp_transform<PPC>(L1.pp_kind, L1.pp_p, acc);
     else { const float a1 = pp_transform<PPC>(L1.pp_kind, L1.pp_p, acc), a0 = pp_transform<PPC>(L0.pp_kind, L0.pp_p, acc); sv = v1 ? a1 : a0; }
-    // ---- level 0 (first layer: no combine): rank of every node in (value desc, position asc) order, on lanes [c1, c1 + K0)
-    const uint32_t k0key = v0 ? score_key(sv) : 0u;
-    uint32_t rank0 = 0;
-    for (uint32_t c = 0; c < K0; ++c) {
-        const uint32_t kc = (uint32_t)__builtin_amdgcn_readlane((int)k0key, (int)(c1 + c));
-        rank0 += (kc > k0key || (kc == k0key && c < l0)) ? 1u : 0u;
-    }
-    // ---- level 1: combine with the parent's score; candidate position = (rank of the parent, tile, column)
-    const uint32_t jsrc = c1 + (j < K0 ? j : 0u);
-    const float psv = __shfl(sv, (int)jsrc, 64);
-    float s1v = sv;
-    if (!L1.first_layer) s1v = pp_combine(L1.pp_kind, sv, psv);
-    const uint32_t prank = (uint32_t)__shfl((int)rank0, (int)jsrc, 64);
-    const uint32_t position = (((prank * TT) + tt) << gl) + col;       // < c1 <= 64: one candidate register
-    sc[lane] = make_uint2(0u, 0xFFFFFFFFu);
-    wave_sync_lds();
-    if (v1) sc[position] = make_uint2(__float_as_uint(s1v), child1);
-    wave_sync_lds();
-    const uint2 mine = sc[lane];
-    wave_sync_lds();
-    uint32_t key[1], sbits[1], payload[1];
-    sbits[0] = mine.x; payload[0] = mine.y;
-    key[0] = mine.y != 0xFFFFFFFFu ? score_key(__uint_as_float(mine.x)) : 0u;
-    uint32_t rank, sb, ch;
-    const uint32_t kk = wave_topk<1>(key, sbits, payload, L1.k, sc, lane, rank, sb, ch);
-    if ((uint32_t)lane < kk) {
-        s_bidx[rank] = L1.perm_inv ? L1.perm_inv[ch] : ch;
-        s_bval[rank] = __uint_as_float(sb);
-    }
-    wave_sync_lds();
-    return kk;
+    // ---- level 0 sits on lanes [c1, c1 + K0)
+    return k1q_select01(L1, sv, sv, v0, v1, c1, K0, j, tt, col, child1, s_bidx, s_bval, sc, lane);
 }
 
 // MULTI = false: exactly one layer (layer[0]); the layer loop and its run-time descriptor indexing cost ~20 VGPRs, which the
@@ -692,18 +697,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NSMAX
     }
 #endif
     if (a.out_xok) {   // the pruning guard of this query, for a bound-pruned tile-format layer that follows (its K2 decides there)
-        uint32_t mx = 0u, n;
-        if (DENSEX) {
-            n = a.X.cols;
-            const float* __restrict__ xd = a.X.val + xrow * a.X.cols;
-            for (uint32_t c = (uint32_t)lane; c < n; c += 64u) mx = max(mx, __float_as_uint(xd[c]) & 0x7FFFFFFFu);
-        } else {
-            const uint64_t xb = a.X.row_ptr[xrow];
-            n = (uint32_t)(a.X.row_ptr[xrow + 1] - xb);
-            for (uint32_t c = (uint32_t)lane; c < n; c += 64u) mx = max(mx, __float_as_uint(a.X.val[xb + c]) & 0x7FFFFFFFu);
-        }
+        const K1QRow row = k1q_row<DENSEX>(a.X, xrow, a.X.cols);
+        uint32_t mx = 0u;
+        for (uint32_t c = (uint32_t)lane; c < row.n; c += 64u) mx = max(mx, __float_as_uint(row.vsrc[c]) & 0x7FFFFFFFu);
         mx = wave_max_u32(mx);
-        if (lane == 0) a.out_xok[q] = prune_guard_ok(mx, n, a.prune_wmax) ? 1u : 0u;
+        if (lane == 0) a.out_xok[q] = prune_guard_ok(mx, row.n, a.prune_wmax) ? 1u : 0u;
     }
 }
 

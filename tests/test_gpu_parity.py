@@ -920,6 +920,111 @@ def test_bound_pruning_guard_nonfinite(variant, XLM, clib, oracle_mod, tmp_path)
     clib.set_option(h, "dense_layers", 1); clib.set_option(h, "prune", 1); clib.set_option(h, "tile_rows", 1)
 
 
+# ---- K1Q's feature walk at its own boundaries (csrc/xrl_k1q_impl.h): a query's features are taken 64 at a time (a chunk) and inside a chunk in
+# batches of 2, 4, 8 or 16; a batch is full, or a row's tail that reads on into the next row, or -- on the last row of X, and in a chunk that holds
+# a non-finite value -- the clamped exact loop.  One row per length on either side of every batch width and of the chunk:
+WALK_NNZ = (0, 1, 7, 8, 9, 15, 16, 17, 63, 64, 65, 71, 72, 73, 79, 80, 81, 127, 128, 129, 200)
+WALK_SHAPE = [4, 32, 400]   # the root keeps its 4 children and level 1 is 4 x 8 = 32 candidates: levels 0 + 1 fuse, the merged rows exist;
+                            # the leaf has 32 parents of 12..13 children: dense tiles of 16 columns, so it takes ceil(min(beam_size, 32) / 4) registers
+# (beam_size, only_topk) -> candidate registers of the leaf by k1q_regs' formula: 4 parents x 16 / 64 = 1, 12 -> 3, 24 -> 6, 32 -> 8 (the bucket 8..16)
+WALK_BEAMS = ((4, 5, 1), (12, 10, 3), (24, 20, 6), (32, 40, 8))
+WALK_PPS = ("l3-hinge", "noop")
+
+
+def _walk_rows(D, nnz, seed, nonfinite=None):
+    """CSR rows of exactly nnz[i] distinct sorted features with finite values.  nonfinite = (unused feature ids, lo, hi): every row that can holds
+    ONE inf / nan, on an unused feature placed at a sorted position in [lo, hi) counted from the row's start (negative: from its end)."""
+    rng = np.random.default_rng(seed)
+    indptr, idx, val, placed = [0], [], [], 0
+    for r, n in enumerate(nnz):
+        f = np.sort(rng.choice(D, n, replace=False))
+        v = rng.standard_normal(n).astype(np.float32)
+        if nonfinite is not None:
+            unused, lo, hi = nonfinite
+            lo, hi = (max(0, n + lo), n) if lo < 0 else (lo, min(hi, n))
+            spot = next(((u, p) for p in range(lo, hi) for u in unused if p <= u and n - 1 - p <= D - 1 - u), None)
+            assert spot is not None or hi <= lo, (n, lo, hi)
+            if spot is not None:
+                u, p = spot
+                f = np.concatenate([np.sort(rng.choice(u, p, replace=False)), [u], u + 1 + np.sort(rng.choice(D - 1 - u, n - 1 - p, replace=False))])
+                v[p] = np.inf if r % 2 == 0 else np.nan
+                placed += 1
+        idx.append(f); val.append(v); indptr.append(indptr[-1] + n)
+    X = smat.csr_matrix((np.concatenate(val), np.concatenate(idx).astype(np.int32), np.array(indptr, np.int64)), shape=(len(nnz), D), dtype=np.float32)
+    return X, placed
+
+
+def _head(P, rows):
+    """The first `rows` rows of a prediction, the order inside the rows kept."""
+    e = P.indptr[rows]
+    return smat.csr_matrix((P.data[:e], P.indices[:e], P.indptr[:rows + 1]), shape=(rows, P.shape[1]))
+
+
+@pytest.fixture(scope="module")
+def walk_cases(XLM, oracle_mod, tmp_path_factory):
+    """The two models, every prefix of their query sets (sparse, and the dense copy) and the oracle's predictions for all rows at once (rows do
+    not interact: the prediction for a prefix of X is that prefix of the prediction)."""
+    import xrl_synth
+    root = tmp_path_factory.mktemp("walk")
+    cases = []
+    for D, w_nnz, seed in ((300, [60, 30, 4], 71), (64, [40, 30, 12], 73)):   # (D = 300: sparse enough to leave some twenty features unused)
+        folder = str(root / f"d{D}")
+        xrl_synth.make_model(folder, D, 400, w_nnz, seed=seed, shape=WALK_SHAPE)
+        nnz = [n for n in WALK_NNZ if n <= D]
+        sets = {"finite": _walk_rows(D, nnz, seed + 1)[0]}
+        if D == 300:
+            # inf / nan on a feature no weight column uses (the reference never multiplies it: the results stay finite), in the first chunk
+            # only, in the second chunk only, in the tail batch only (the row's last position sits in the tail batch of every batch width)
+            W = [smat.load_npz(os.path.join(folder, "ranker", f"{d}.model", "W.npz")).tocsr() for d in range(3)]
+            unused = [f for f in range(D) if all(w.indptr[f + 1] == w.indptr[f] for w in W)]
+            for name, lo, hi, rows_hit in (("first chunk", 0, 64, 20), ("second chunk", 64, 128, 11), ("tail batch", -1, 0, 20)):
+                sets[name], placed = _walk_rows(D, nnz, seed + 1, (unused, lo, hi))
+                assert placed == rows_hit, (name, placed, len(unused))
+        m, om = XLM.load(folder), oracle_mod.OracleModel.load(folder)
+        for name, Xs in sets.items():
+            for Xq in (Xs, np.ascontiguousarray(Xs.toarray())):
+                want = {}
+                for beam, topk, _ in WALK_BEAMS:
+                    for pp in WALK_PPS:
+                        want[beam, pp] = om.predict(Xq, beam_size=beam, only_topk=topk, post_processor=pp)
+                        assert np.all(np.isfinite(want[beam, pp].data)), (D, name, beam, pp)
+                cases.append((f"D={D} {name} {'sparse' if smat.issparse(Xq) else 'dense'} X", m, [Xq[:i + 1] for i in range(Xq.shape[0])], want))
+    return cases
+
+
+@pytest.mark.parametrize("beam,topk,regs", WALK_BEAMS)
+def test_k1q_feature_walk_boundaries(beam, topk, regs, walk_cases, clib):
+    # Every prefix X[:i + 1]: each row length is once the LAST row of the arrays (the clamped exact loop: nothing may be read past them) and
+    # once followed by another row (its tail batch runs on into that row).  Bit-exact against the oracle under every way K1Q walks levels 0 + 1
+    # (separately / one walk, two loads / merged rows), staged and unstaged passes (prune), with and without the presence masks.
+    old = os.environ.get("XRL_K1Q_FUSE01")
+    try:
+        for what, m, prefixes, want in walk_cases:
+            h = m.model.model_chain
+            assert [clib.layer_info(h, l)["dense_tile_width"] for l in (1, 2)] == [8, 16], what
+            assert -(-min(beam, 32) * 16 // 64) == regs
+            clib.set_option(h, "dense_layers", 2)                                  # K1Q on every layer it can serve
+            for fuse in ("0", "1", "2"):
+                os.environ["XRL_K1Q_FUSE01"] = fuse
+                for prune in (0, 1):
+                    clib.set_option(h, "prune", prune)
+                    for pres in (0, 2):
+                        clib.set_option(h, "presence", pres)
+                        for pp in WALK_PPS:
+                            for i, Xp in enumerate(prefixes):
+                                got = m.predict(Xp, beam_size=beam, only_topk=topk, post_processor=pp)
+                                assert_same_topk(got, _head(want[beam, pp], i + 1), exact_scores=True,
+                                                 what=f"{what} rows [0, {i}] beam={beam} topk={topk} {pp} FUSE01={fuse} prune={prune} presence={pres}")
+    finally:
+        if old is None:
+            os.environ.pop("XRL_K1Q_FUSE01", None)
+        else:
+            os.environ["XRL_K1Q_FUSE01"] = old
+        for _, m, _, _ in walk_cases:
+            for key in ("dense_layers", "prune", "presence"):
+                clib.set_option(m.model.model_chain, key, 1)
+
+
 def _bench_workload(name, cache=None):
     """The folder bench.py generates / re-uses for a workload at scale 1.0 (so that the driver's pytest and bench runs build it once)."""
     import json
