@@ -282,6 +282,29 @@ int xrl_ensemble_device(int device, uint32_t n_models, uint32_t rows,
                         uint32_t only_topk /* 0 = all; finish only */,
                         uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride, void* hip_stream, int sync);
 
+/* predict_on_selected_outputs on the device (K7 + K4): score a given set of labels per query row through the tree, with labels, plan and
+ * scores resident in HBM.  The labels arrive in the fixed-stride form xrl_predict_device writes and xrl_ensemble_device reads: row r is
+ * d_sel_idx[r*sel_stride ..], d_sel_cnt[r] entries long (NULL = sel_stride each; a count above the stride is read as the stride), in any
+ * order.  `queries` is any query handle of the model's device (CSR or dense, uploaded or wrapping caller memory); its rows are the rows.
+ * Result: row r of d_out_idx / d_out_val (row stride out_stride >= sel_stride) holds d_out_cnt[r] (label, score) pairs -- the labels in the
+ * order the reference's walk emits them for that set (prolongate_sparse_predictions, inference.hpp:1302-1358: the order of
+ * c_xlinear_predict_on_selected_outputs_*), the scores its CSC-route arithmetic, bit for bit what that entry point returns.  Entries
+ * beyond a row's count are left untouched.  post_processor NULL = each layer's own.
+ * Bad rows: a row with a label >= nr_pred_cols (code 1), a label twice (2) or a label without a parent in some layer (3: pruned tree) gets
+ * count 0; every other row is still correct.  d_status (u32[2], may be NULL) receives {code, row} of the LOWEST bad row, or
+ * {0, 0xFFFFFFFF} when there is none.  With `sync` != 0 the library reads the status itself: on a bad row the call returns -1 and
+ * xrl_last_error holds the host entry point's message for that row.  With `sync` == 0 the call returns 0 without synchronising and the
+ * status is the caller's to read, in stream order.
+ * One plan launch and one scoring launch per layer run on `hip_stream` (NULL = the handle's stream, as for xrl_predict_device), without a
+ * host synchronisation between them.  Capacity: sel_stride <= 1024 labels per row (longer rows: the host entry point); trees only (a C
+ * that lists a node under two parents is refused); mmap handles are refused like the host entry point refuses them.  Every argument is
+ * checked before the GPU is touched (messages start with "xrl_predict_selected_device: "); zero rows is a successful no-op. */
+int xrl_predict_selected_device(void* model, void* queries, const char* post_processor /* NULL = each layer's own */,
+                                const uint32_t* d_sel_idx /* u32[rows*sel_stride] */, const uint32_t* d_sel_cnt /* u32[rows]; NULL = sel_stride each */,
+                                uint32_t sel_stride,
+                                uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride /* >= sel_stride */,
+                                uint32_t* d_status /* u32[2] {code, row}; may be NULL */, void* hip_stream, int sync);
+
 /* Effective only_topk of the last layer for the given override (0 = model default). */
 uint32_t xrl_effective_topk(void* model, uint32_t only_topk);
 

@@ -233,6 +233,7 @@ class corelib(object):
             "xrl_predict_device_rows": (c_int, [c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int, c_uint32, c_uint32]),
             "xrl_ensemble_device": (c_int, [c_int, c_uint32, c_uint32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint32), c_int,
                                             POINTER(c_float), c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int]),
+            "xrl_predict_selected_device": (c_int, [c_void_p, c_void_p, c_char_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_int]),
             "xrl_predict_stats": (c_int, [c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, POINTER(c_double), c_uint32]),
             "xrl_effective_topk": (c_uint32, [c_void_p, c_uint32]),
             "xrl_profile_enable": (None, [c_void_p, c_int]),
@@ -601,6 +602,20 @@ class corelib(object):
             post_processor.encode("utf-8") if post_processor else None, only_topk or 0,
             c_void_p(d_idx), c_void_p(d_val), c_void_p(d_cnt), out_stride, c_void_p(stream or 0), 1 if sync else 0,
             int(row_begin), int(row_count))
+        self._check()
+        return rc
+
+    def predict_selected_device(self, c_model, queries, post_processor, d_sel_idx, d_sel_cnt, sel_stride, d_idx, d_val, d_cnt, out_stride,
+                                d_status=None, stream=None, sync=True):
+        """K7 + K4: the scores of a given set of labels per query row (``d_sel_idx`` u32 [rows, sel_stride], ``d_sel_cnt`` u32 [rows] or None --
+        raw device addresses, the form ``predict_device`` writes) in the reference's order for that set, into ``d_idx`` / ``d_val`` /
+        ``d_cnt`` (row stride ``out_stride`` >= ``sel_stride``).  ``d_status``: optional device u32[2] that receives {code, row} of the lowest
+        bad row.  ``sync=True`` raises RuntimeError with the host path's message on a bad row; ``sync=False`` returns without synchronising.
+        Returns the library's return code."""
+        rc = self.clib_float32.xrl_predict_selected_device(
+            c_void_p(c_model), c_void_p(queries), post_processor.encode("utf-8") if post_processor else None,
+            c_void_p(d_sel_idx), c_void_p(d_sel_cnt or 0), int(sel_stride), c_void_p(d_idx), c_void_p(d_val), c_void_p(d_cnt), int(out_stride),
+            c_void_p(d_status or 0), c_void_p(stream or 0), 1 if sync else 0)
         self._check()
         return rc
 

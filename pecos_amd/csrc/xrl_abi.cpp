@@ -366,6 +366,29 @@ int xrl_ensemble_device(int device, uint32_t n_models, uint32_t rows, const uint
     });
 }
 
+int xrl_predict_selected_device(void* model, void* queries, const char* post_processor, const uint32_t* d_sel_idx, const uint32_t* d_sel_cnt,
+                                uint32_t sel_stride, uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride,
+                                uint32_t* d_status, void* hip_stream, int sync) {
+    return guarded_value(-1, [&] {
+        // every argument is checked before the GPU is touched
+        const std::string what = "xrl_predict_selected_device: ";
+        if (!model || !queries || !d_sel_idx || !d_out_idx || !d_out_val || !d_out_cnt) fail(what + "null argument");
+        Model& m = *as_model(model);
+        const Queries& q = *static_cast<Queries*>(queries);
+        if (sel_stride == 0 || sel_stride > kSelectMaxStride) fail(what + "sel_stride must be 1.." + std::to_string(kSelectMaxStride) + ", got " + std::to_string(sel_stride) + " (the host entry point serves longer rows)");
+        if (out_stride < sel_stride) fail(what + "out_stride " + std::to_string(out_stride) + " smaller than sel_stride " + std::to_string(sel_stride));
+        if (q.device != m.device) fail(what + "the queries live on device " + std::to_string(q.device) + ", the model on device " + std::to_string(m.device));
+        std::lock_guard<std::mutex> g(m.mu);
+        try { check_selected_inputs(m, q.dev); }
+        catch (const Error& e) { fail(what + e.what()); }
+        if (q.dev.rows == 0) return 0;
+        use_device(m.device);
+        predict_selected_device(m, q.dev, post_processor, d_sel_idx, d_sel_cnt, sel_stride, d_out_idx, d_out_val, d_out_cnt, out_stride, d_status,
+                                static_cast<hipStream_t>(hip_stream), sync != 0);
+        return 0;
+    });
+}
+
 int xrl_predict_stats(void* model, void* queries, uint32_t beam_size, const char* post_processor, uint32_t only_topk,
                       double* stats_out, uint32_t stats_cap) {
     return guarded_value(-1, [&] {

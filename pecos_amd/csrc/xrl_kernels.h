@@ -153,4 +153,38 @@ uint32_t ensemble_slots(uint32_t stride_sum);     // entries per lane (1, 2, 4, 
 // mm_scratch: one device uint32 (rank_average only: the call's largest row length, reduced on `s` ahead of K6)
 void launch_ensemble(const EnsembleArgs& A, uint32_t* mm_scratch, hipStream_t s);
 
+// xrl_select_plan.hip, K7: predict_on_selected_outputs on the device.  One launch plans the reference's tree walk for every row of a batch
+// (per layer: the row's nodes in the walk's order, the position of every node's parent in the previous layer's list, the count), then one
+// K4 launch per layer scores the planned slots.  Rows are fixed-stride like xrl_predict_device's results; capacity kSelectMaxStride labels.
+constexpr uint32_t kSelectMaxStride = 1024;
+constexpr uint32_t kSelectNone = 0xFFFFFFFFu;
+enum { kSelectOk = 0, kSelectOutOfRange = 1, kSelectTwice = 2, kSelectNoParent = 3 };
+struct SelectTreeLayer {                          // one layer of the tree, ORIGINAL node ids (Model::d_sel_tree holds `depth` of them)
+    const uint32_t* parent;                       // [c_rows] the node's parent, kSelectNone = none (layer 0: anything not under the root)
+    const uint32_t* crank;                        // [c_rows] the node's position inside its parent's column of C, in stored order
+    uint32_t c_rows, pad;
+};
+struct SelectPlanArgs {
+    const uint32_t* sel_idx; const uint32_t* sel_cnt;   // the caller's rows (all of them; sel_cnt may be null = sel_stride each)
+    uint32_t sel_stride;
+    uint32_t row0, nrows;                         // the batch: rows [row0, row0 + nrows) of the caller's arrays = rows [0, nrows) of the scratch
+    uint32_t depth, nr_labels;
+    const SelectTreeLayer* tree;
+    // scratch, layer l at l * layer_elems (node, ppos: rows of sel_stride) / l * layer_rows (cnt)
+    uint32_t* node; uint32_t* ppos; uint32_t* cnt; uint64_t layer_elems, layer_rows;
+    uint32_t* out_idx; uint32_t* out_cnt; uint32_t out_stride;   // the caller's buffers (all rows): the last layer's nodes and counts
+    unsigned long long* status;                   // (row << 32 | code) of the lowest bad row, atomicMin; starts as 0xFFFFFFFF << 32
+};
+void launch_select_plan(const SelectPlanArgs& A, hipStream_t s);
+// K4 on the planned slots of one layer: slot i = (row i / sel_stride, position i % sel_stride), live below cnt[row]; 16 lanes per slot
+struct SelectScoreArgs {
+    const uint64_t* col_ptr; const uint32_t* row_idx; const float* val; uint32_t w_rows; float bias;   // W, CSC, original column ids
+    const uint32_t* node; uint32_t node_stride;   // the layer's ordered nodes (batch row 0): scratch rows, or the caller's d_out_idx
+    const uint32_t* ppos; const uint32_t* cnt;    // scratch (batch rows)
+    const float* prev_val;                        // [nrows * sel_stride] the previous layer's values, null on layer 0
+    float* out_val; uint32_t out_stride;          // (batch row 0) scratch rows, or the caller's d_out_val
+    uint32_t row0, nrows, sel_stride;
+};
+void launch_k4_selected_dev(const SelectScoreArgs& A, const QueriesDev& X, const PostProc& pp, hipStream_t s);
+
 }  // namespace xrl

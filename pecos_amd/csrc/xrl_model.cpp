@@ -8,6 +8,7 @@
 //                                                         columns ascending inside a row)
 //   check_bias_explicit                     :500-502
 #include "xrl_model.h"
+#include "xrl_kernels.h"   // SelectTreeLayer (ensure_device_tree)
 
 #include <algorithm>
 #include <atomic>
@@ -142,7 +143,7 @@ uint64_t layout_tile_rows(const uint32_t* rptr, uint32_t nrows, bool align, uint
 uint64_t Layer::buffer_bytes() const {
     uint64_t b = 0;
     for (const DevBuf* d : {&d_csc_ptr, &d_csc_idx, &d_csc_val, &d_tiles, &d_ptile, &d_chunk_col, &d_bitmap, &d_row_ptr, &d_row_idx, &d_entries, &d_perm_inv,
-                            &d_chunk_alg, &d_bias_prod, &d_bucket, &d_bitmap64, &d_wd, &d_dptile, &d_dtcol, &d_tile_parent, &d_pres, &d_wt, &d_wt_base})
+                            &d_chunk_alg, &d_bias_prod, &d_bucket, &d_bitmap64, &d_wd, &d_dptile, &d_dtcol, &d_tile_parent, &d_pres, &d_wt, &d_wt_base, &d_sel_parent, &d_sel_crank})
         b += d->cap;
     return b;
 }
@@ -702,6 +703,33 @@ void ensure_device_csc(Layer& L) {
     L.d_csc_ptr.upload(W->col_ptr); L.d_csc_idx.upload(W->row_idx); L.d_csc_val.upload(W->val);
     L.device_bytes = L.buffer_bytes() + models;
     L.csc_ready = true;
+}
+
+void ensure_device_tree(Model& m) {
+    if (m.sel_tree_ready) return;
+    std::vector<SelectTreeLayer> table(m.layers.size());
+    for (size_t l = 0; l < m.layers.size(); ++l) {
+        Layer& L = *m.layers[l];
+        // from C as stored (original ids): a node's parent is the column that holds it, its crank the position inside that column
+        std::vector<uint32_t> parent(L.c_rows, kSelectNone), crank(L.c_rows, 0u);
+        std::vector<uint8_t> seen(L.c_rows, 0);
+        for (uint32_t p = 0; p + 1 < L.h_c_ptr.size(); ++p)
+            for (uint64_t c = L.h_c_ptr[p]; c < L.h_c_ptr[p + 1]; ++c) {
+                const uint32_t j = L.h_c_idx[c];
+                if (j >= L.c_rows) fail("layer " + std::to_string(l) + ": C holds a row id out of range");
+                if (seen[j]) fail("layer " + std::to_string(l) + ": node " + std::to_string(j) + " appears under two parents (C is not a tree)");
+                seen[j] = 1;
+                parent[j] = (l == 0 && p != 0) ? kSelectNone : p;   // layer 0 hangs under the implicit root, parent 0
+                crank[j] = (uint32_t)(c - L.h_c_ptr[p]);
+            }
+        const uint64_t models = L.device_bytes - L.buffer_bytes();   // (what ensure_device_csc keeps too)
+        L.d_sel_parent.upload(parent); L.d_sel_crank.upload(crank);
+        L.device_bytes = L.buffer_bytes() + models;
+        table[l] = SelectTreeLayer{L.d_sel_parent.as<uint32_t>(), L.d_sel_crank.as<uint32_t>(), L.c_rows, 0u};
+    }
+    m.d_sel_tree.upload(table);
+    m.layers[0]->device_bytes += m.d_sel_tree.cap;
+    m.sel_tree_ready = true;
 }
 
 void finalize_model(Model& m) {

@@ -124,6 +124,8 @@ struct Layer {
     std::vector<uint64_t> h_c_ptr; std::vector<uint32_t> h_c_idx, h_parent;
     std::string w_path; std::shared_ptr<HostCsc> w_host;
     DevBuf d_csc_ptr, d_csc_idx, d_csc_val; bool csc_ready = false;
+    // xrl_predict_selected_device (K7): child -> parent and child -> position inside the parent's column of C, original ids (ensure_device_tree)
+    DevBuf d_sel_parent, d_sel_crank;
     // device storage
     DevBuf d_tiles, d_ptile, d_chunk_col, d_bitmap, d_row_ptr, d_row_idx, d_entries, d_perm_inv, d_chunk_alg, d_bias_prod;
     DevBuf d_bucket, d_bitmap64;
@@ -161,6 +163,8 @@ struct Workspace {
     PinnedBuf stage_ptr;  // ... and the row pointer's own pinned staging buffer (it travels first, on the copy stream)
     // initial beam for the single-layer API
     DevBuf init_idx, init_val, init_cnt;
+    // xrl_predict_selected_device: per layer the planned nodes / parent positions / counts of a row batch, two value buffers, the status word
+    DevBuf sel_node, sel_ppos, sel_cnt, sel_val[2], sel_status;
 };
 
 struct Model {
@@ -183,6 +187,7 @@ struct Model {
     std::unique_ptr<Workspace> ws;
     bool csc_route = false;                 // weight_matrix_type == CSC: every layer runs the reference's CSC arithmetic (K0 -> K1C -> K2)
     DevBuf d_wd01;                          // levels 0 + 1 merged dense rows (LayerDev::wd01 of the root layer)
+    DevBuf d_sel_tree; bool sel_tree_ready = false;   // K7: one SelectTreeLayer per layer (ensure_device_tree; counted on the root layer like d_wd01)
     PruneFeedback fb;                       // what the bound pruning of this handle's previous predicts achieved (xrl_feedback.h)
     // Everything xrl_set_option sets by name (include/xrl_abi.h lists the keys; xrl_abi.cpp kIntOptions maps them to these members).  A replica
     // takes the whole struct in one assignment.
@@ -247,6 +252,7 @@ void finalize_model(Model& m);
 std::unique_ptr<Model> load_mmap_model_from_disk(const std::string& path);        // xrl_mmap.cpp
 void compile_mmap_model(const std::string& npz_path, const std::string& mmap_path);   // xrl_mmap.cpp
 void ensure_device_csc(Layer& L);   // upload W as CSC (original column ids) if not there yet
+void ensure_device_tree(Model& m);  // K7's tree arrays (Layer::d_sel_parent / d_sel_crank, Model::d_sel_tree) if not there yet; refuses a C that is no tree
 void k1t_shape(uint32_t max_tile_cols, int& g, int& nr);   // lanes per item / columns per lane of K1T for a layer's widest tile
 void launch_tile_rows(const LayerDev& L, uint64_t total_floats, uint32_t* wt, hipStream_t s);   // fills LayerDev::wt from the tile format on the device (xrl_k1t.hip)
 // the merged level-0/1 matrix (LayerDev::wd01: w_rows + 1 rows of 64 floats) is read with 32-bit byte offsets: usable only while they cannot wrap

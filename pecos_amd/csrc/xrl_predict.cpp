@@ -15,13 +15,14 @@
 
 namespace xrl {
 
-namespace {
 size_t profile_slot(Model& m, const char* name, uint32_t layer) {
     for (size_t i = 0; i < m.profile.size(); ++i)
         if (m.profile[i].layer == layer && m.profile[i].name == name) return i;
     m.profile.push_back(ProfileSlot{name, layer});
     return m.profile.size() - 1;
 }
+
+namespace {
 
 // dense-X SGEMM layers, bound pruning: beam slots whose children fill about one candidate register (64) are scored first -- never all of
 // them (the second stage must keep at least one slot)
@@ -107,13 +108,7 @@ struct Batch {
             if (e != hipSuccess) fail(std::string("device fault in ") + name + " (layer " + std::to_string(layer) + ", rows " + std::to_string(row0) + "+" + std::to_string(nrows) + "): " + hipGetErrorString(e));
             return;
         }
-        if (!m.profiling) { fn(); return; }
-        PendingEvent ev; ev.slot = profile_slot(m, name, layer);
-        XRL_HIP(hipEventCreate(&ev.a)); XRL_HIP(hipEventCreate(&ev.b));
-        XRL_HIP(hipEventRecord(ev.a, S));
-        fn();
-        XRL_HIP(hipEventRecord(ev.b, S));
-        m.pending.push_back(ev);
+        profiled(m, S, name, layer, fn);
     }
     void need_x_ok() {   // once per row batch
         if (!x_ok_done) timed("xguard", 0, [&] { launch_xguard(X, (uint32_t)row0, nrows, prune_wmax, x_ok, S); });
@@ -152,8 +147,7 @@ std::vector<LayerShape> resolve_layers(const Model& m, const QueriesDev& X, cons
 void size_batches(Batch& b, uint64_t n_rows) {
     uint32_t cs_max = 1;
     for (const LayerShape& s : b.shape) cs_max = std::max(cs_max, s.cand_stride);
-    const uint64_t cand_budget = 6ull << 30;
-    uint64_t nb = std::min<uint64_t>(std::max<uint64_t>(1, cand_budget / ((uint64_t)cs_max * 4)), 1u << 22);
+    uint64_t nb = std::min<uint64_t>(std::max<uint64_t>(1, kCandBudgetBytes / ((uint64_t)cs_max * 4)), 1u << 22);
     if (b.opt.max_batch_rows > 0) nb = std::min<uint64_t>(nb, (uint64_t)b.opt.max_batch_rows);
     nb = std::min<uint64_t>(nb, std::max<uint64_t>(1, std::max<uint64_t>(n_rows, b.o.reserve_rows)));   // reserve_rows: size the scratch for the caller's largest batch up front
     // two lanes: the row batches alternate between the caller's stream and an auxiliary one.  K1 launches are chained

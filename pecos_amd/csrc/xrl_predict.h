@@ -26,13 +26,33 @@ struct PredictOpts {
 };
 
 uint32_t effective_topk(const Model& m, uint32_t only_topk);
+constexpr uint64_t kCandBudgetBytes = 6ull << 30;   // per-row scratch of a predict (candidates; planned slots of selected outputs) stays below this: rows go in batches
 void resolve_profile(Model& m);   // synchronise and fold pending hipEvent pairs into m.profile
+size_t profile_slot(Model& m, const char* name, uint32_t layer);
+// fn() launches on `s`; with profiling on, a hipEvent pair around it is queued for resolve_profile under (name, layer) -- no synchronisation here
+template <class F> void profiled(Model& m, hipStream_t s, const char* name, uint32_t layer, F&& fn) {
+    if (!m.profiling) { fn(); return; }
+    PendingEvent ev; ev.slot = profile_slot(m, name, layer);
+    XRL_HIP(hipEventCreate(&ev.a)); XRL_HIP(hipEventCreate(&ev.b));
+    XRL_HIP(hipEventRecord(ev.a, s));
+    fn();
+    XRL_HIP(hipEventRecord(ev.b, s));
+    m.pending.push_back(ev);
+}
 // predict_on_selected_outputs (xrl_select.cpp): values for the pattern (s_ptr, s_idx), in the reference's walk order
 struct ScipyCsrF32View { uint32_t rows, cols; const uint64_t* row_ptr; const uint32_t* col_idx; const float* val; };
 struct SelectedInit { const ScipyCsrF32View* codes; bool no_prev_pred; };   // explicit predictions entering layer 0
 void predict_selected(Model& m, const QueriesDev& X, uint32_t s_rows, uint32_t s_cols, const uint64_t* s_ptr,
                       const uint32_t* s_idx, const char* post_processor, std::vector<uint32_t>& out_idx,
                       std::vector<float>& out_val, const SelectedInit* init = nullptr);
+// the same for fixed-stride rows of labels that live on the device (xrl_predict_selected_device; K7 + one K4 launch per layer), results in the
+// caller's fixed-stride device buffers in the reference's order.  d_status (may be null) receives {code, row} of the lowest bad row; with
+// `sync` a bad row throws the host path's message for it.
+void predict_selected_device(Model& m, const QueriesDev& X, const char* post_processor, const uint32_t* d_sel_idx, const uint32_t* d_sel_cnt,
+                             uint32_t sel_stride, uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride,
+                             uint32_t* d_status, hipStream_t stream, bool sync);
+// what the device form refuses before it touches the GPU, in the host path's words: the feature dimension; handles without CSC weights (mmap folders)
+void check_selected_inputs(const Model& m, const QueriesDev& X);
 
 // Enqueue the whole beam search on `stream`; results land in fixed-stride device buffers.
 void predict_device(Model& m, const QueriesDev& X, const PredictOpts& o, uint32_t* d_out_idx, float* d_out_val,

@@ -9,6 +9,8 @@
 * :func:`predict_from_torch` -- X already in HBM as torch tensors (a GPU TF-IDF featurizer's CSR -- the reference's
   ``c_tfidf_predict`` produces that CSR on the host, pecos/core/libpecos.cpp:427-445 -- optionally with a dense embedding block to
   append on the device): no host round trip of X, results stay on the device.
+* :func:`predict_selected_from_torch` -- ``predict_on_selected_outputs`` with the queries and the labels to score in HBM (K7 + K4): re-scores
+  one model's candidates with another without a host round trip.
 * :func:`ensemble_device` -- the results of several models merged on the device (K6) like ``CsrEnsembler.average`` / ``rank_average`` /
   ``Text2Text.predict``'s tail; :func:`predict_text` and :class:`Text2Text` use it for ensembles that share a device.
 """
@@ -74,6 +76,53 @@ def predict_from_torch(model, crow, col, val, n_cols, beam_size=None, only_topk=
         if rows:
             clib.predict_device(h, q, beam_size, post_processor, only_topk, idx.data_ptr(), sc.data_ptr(), cnt.data_ptr(), k,
                                 stream=s or None, sync=True)
+    finally:
+        clib.queries_free(q)
+    return idx, sc, cnt
+
+
+def predict_selected_from_torch(model, crow, col, val, n_cols, sel_idx, sel_cnt=None, post_processor=None, emb=None, normalize_emb=False,
+                                stream=None):
+    """``predict_on_selected_outputs`` with queries AND labels already on the GPU (K7 + K4): the scores of the labels ``sel_idx`` names per row.
+
+    crow / col / val / n_cols / emb / normalize_emb: the queries, as for :func:`predict_from_torch`.  sel_idx: int32 [rows, stride] CUDA tensor
+    (stride <= 1024), sel_cnt: int32 [rows] or None (= stride labels in every row) -- the form :func:`predict_from_torch` returns; the order
+    of the labels inside a row does not matter.  Returns CUDA tensors (labels int32 [rows, stride], scores float32 [rows, stride], counts
+    int32 [rows]): row r holds counts[r] pairs in the order the reference's ``predict_on_selected_outputs`` returns that set, with its scores
+    bit for bit.  Raises RuntimeError with the library's message when a row holds a label twice, one out of range or one without a parent.
+
+    The device pieces compose without a host visit: ``predict_from_torch`` of model A (candidates), ``predict_selected_from_torch`` of
+    model B on A's ``(labels, counts)`` (re-scoring), then ``ensemble_device([a, b], mode="finish")`` for a score-sorted result."""
+    import torch
+    h = model.model.model_chain
+    assert crow.is_cuda and col.is_cuda and val.is_cuda and crow.dtype == torch.int64 and col.dtype == torch.int32 and val.dtype == torch.float32
+    assert sel_idx.is_cuda and sel_idx.dtype == torch.int32 and sel_idx.dim() == 2
+    crow, col, val, sel_idx = crow.contiguous(), col.contiguous(), val.contiguous(), sel_idx.contiguous()
+    rows = crow.numel() - 1
+    nnz = int(val.numel())
+    stride = sel_idx.shape[1]
+    assert sel_idx.shape[0] == rows
+    if sel_cnt is not None:
+        assert sel_cnt.is_cuda and sel_cnt.dtype == torch.int32 and sel_cnt.shape == (rows,)
+        sel_cnt = sel_cnt.contiguous()
+    # outputs first: their zero-fills run on torch's current stream and must be complete (like the inputs, produced on that
+    # stream) before the work starts on `stream`
+    idx = torch.zeros((rows, stride), dtype=torch.int32, device=val.device)
+    sc = torch.zeros((rows, stride), dtype=torch.float32, device=val.device)
+    cnt = torch.zeros((rows,), dtype=torch.int32, device=val.device)
+    torch.cuda.current_stream().synchronize()
+    if emb is not None:
+        assert emb.is_cuda and emb.dtype == torch.float32 and emb.shape[0] == rows
+        emb = emb.contiguous()
+        q = clib.queries_concat_device(h, rows, n_cols, crow.data_ptr(), col.data_ptr(), val.data_ptr(), nnz, emb.shape[1], emb.data_ptr(),
+                                       normalize_emb=normalize_emb)
+    else:
+        q = clib.queries_from_device_csr(h, rows, n_cols, crow.data_ptr(), col.data_ptr(), val.data_ptr(), nnz)
+    try:
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        if rows and stride:
+            clib.predict_selected_device(h, q, post_processor, sel_idx.data_ptr(), sel_cnt.data_ptr() if sel_cnt is not None else None, stride,
+                                         idx.data_ptr(), sc.data_ptr(), cnt.data_ptr(), stride, stream=s or None, sync=True)
     finally:
         clib.queries_free(q)
     return idx, sc, cnt
