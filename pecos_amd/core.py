@@ -13,6 +13,7 @@ with the same names, argument order and meaning, so that code written against
 ``pecos.core.clib`` reads the same against :data:`clib` here.  There is NO CPU fallback: every
 compute call needs a visible HIP device and raises ``RuntimeError`` otherwise.
 """
+import contextlib
 import ctypes
 import sys
 import os
@@ -183,74 +184,109 @@ class corelib(object):
             self._link(self._lib)
         return self._lib
 
-    @staticmethod
-    def _link(lib):
-        alloc_t = ScipyCompressedSparseAllocator.CFUNCTYPE
-        sigs = {
-            "xrl_last_error": (c_char_p, []),
-            "xrl_clear_error": (None, []),
-            "xrl_version": (c_char_p, []),
-            "xrl_device_count": (c_int, []),
-            "xrl_set_device": (c_int, [c_int]),
-            "c_xlinear_load_model_from_disk": (c_void_p, [c_char_p]),
-            "c_xlinear_load_model_from_disk_ext": (c_void_p, [c_char_p, c_int]),
-            "c_xlinear_load_mmap_model_from_disk": (c_void_p, [c_char_p, c_bool]),
-            "c_xlinear_compile_mmap_model": (None, [c_char_p, c_char_p]),
-            "c_xlinear_destruct_model": (None, [c_void_p]),
-            "c_xlinear_get_int_attr": (c_uint32, [c_void_p, c_char_p]),
-            "c_xlinear_get_layer_type": (c_int, [c_void_p, c_int]),
-            "c_xlinear_predict_csr_f32": (None, [c_void_p, POINTER(ScipyCsrF32), c_uint32, c_char_p, c_uint32, c_int, alloc_t]),
-            "c_xlinear_predict_drm_f32": (None, [c_void_p, POINTER(ScipyDrmF32), c_uint32, c_char_p, c_uint32, c_int, alloc_t]),
-            "c_xlinear_predict_on_selected_outputs_csr_f32": (None, [c_void_p, POINTER(ScipyCsrF32), POINTER(ScipyCsrF32), c_char_p, c_int, alloc_t]),
-            "c_xlinear_predict_on_selected_outputs_drm_f32": (None, [c_void_p, POINTER(ScipyDrmF32), POINTER(ScipyCsrF32), c_char_p, c_int, alloc_t]),
-            "c_xlinear_single_layer_predict_csr_f32": (None, [POINTER(ScipyCsrF32), POINTER(ScipyCsrF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), c_char_p, c_uint32, c_int, c_float, alloc_t]),
-            "c_xlinear_single_layer_predict_drm_f32": (None, [POINTER(ScipyDrmF32), POINTER(ScipyCsrF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), c_char_p, c_uint32, c_int, c_float, alloc_t]),
-            "c_xlinear_single_layer_predict_on_selected_outputs_csr_f32": (None, [POINTER(ScipyCsrF32), POINTER(ScipyCsrF32), POINTER(ScipyCsrF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), c_char_p, c_int, c_float, alloc_t]),
-            "c_xlinear_single_layer_predict_on_selected_outputs_drm_f32": (None, [POINTER(ScipyDrmF32), POINTER(ScipyCsrF32), POINTER(ScipyCsrF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), c_char_p, c_int, c_float, alloc_t]),
-            "c_sparse_inner_products_csr2csc_f32": (None, [POINTER(ScipyCsrF32), POINTER(ScipyCscF32), c_uint64, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_float), c_int]),
-            "c_sparse_inner_products_drm2csc_f32": (None, [POINTER(ScipyDrmF32), POINTER(ScipyCscF32), c_uint64, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_float), c_int]),
-            "c_sparse_inner_products_csr2dcm_f32": (None, [POINTER(ScipyCsrF32), POINTER(ScipyDcmF32), c_uint64, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_float), c_int]),
-            "c_sparse_inner_products_drm2dcm_f32": (None, [POINTER(ScipyDrmF32), POINTER(ScipyDcmF32), c_uint64, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_float), c_int]),
-            "xrl_inspect_model": (c_int, [c_char_p, POINTER(c_uint64), c_uint32]),
-            "xrl_model_create": (c_void_p, [c_uint32, c_void_p, c_void_p, POINTER(c_float), POINTER(c_uint32), POINTER(c_char_p)]),
-            "xrl_queries_upload_csr": (c_void_p, [c_void_p, POINTER(ScipyCsrF32)]),
-            "xrl_queries_upload_drm": (c_void_p, [c_void_p, POINTER(ScipyDrmF32)]),
-            "xrl_queries_from_device_csr": (c_void_p, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64]),
-            "xrl_queries_from_device_drm": (c_void_p, [c_void_p, c_uint32, c_uint32, c_void_p]),
-            "xrl_queries_concat_device": (c_void_p, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p]),
-            "xrl_queries_tfidf_device": (c_void_p, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-            "xrl_queries_concat_device_ex": (c_void_p, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_int, c_void_p]),
-            "xrl_queries_free": (None, [c_void_p]),
-            "c_tfidf_load": (c_void_p, [c_char_p]),
-            "c_tfidf_destruct": (None, [c_void_p]),
-            "c_tfidf_predict": (None, [c_void_p, c_void_p, POINTER(c_uint64), c_uint64, c_int, ScipyCompressedSparseAllocator.CFUNCTYPE]),
-            "c_tfidf_predict_from_file": (None, [c_void_p, c_void_p, c_uint64, c_uint64, c_int, ScipyCompressedSparseAllocator.CFUNCTYPE]),
-            "xrl_tfidf_counts": (None, [c_void_p, c_void_p, POINTER(c_uint64), c_uint64, c_int, ScipyCompressedSparseAllocator.CFUNCTYPE]),
-            "xrl_tfidf_nr_features": (c_uint32, [c_void_p]),
-            "xrl_tfidf_predict_device": (c_void_p, [c_void_p, c_void_p, c_void_p, POINTER(c_uint64), c_uint64, c_int]),
-            "xrl_queries_concat_handle": (c_void_p, [c_void_p, c_void_p, c_uint32, c_void_p, c_int, c_void_p]),
-            "xrl_predict_device": (c_int, [c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int]),
-            "xrl_predict_device_rows": (c_int, [c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int, c_uint32, c_uint32]),
-            "xrl_ensemble_device": (c_int, [c_int, c_uint32, c_uint32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint32), c_int,
-                                            POINTER(c_float), c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int]),
-            "xrl_predict_selected_device": (c_int, [c_void_p, c_void_p, c_char_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_int]),
-            "xrl_predict_stats": (c_int, [c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, POINTER(c_double), c_uint32]),
-            "xrl_effective_topk": (c_uint32, [c_void_p, c_uint32]),
-            "xrl_profile_enable": (None, [c_void_p, c_int]),
-            "xrl_profile_reset": (None, [c_void_p]),
-            "xrl_profile_get": (c_uint32, [c_void_p, POINTER(ProfileRec), c_uint32]),
-            "xrl_set_option": (c_int, [c_void_p, c_char_p, c_int64]),
-            "xrl_model_device_bytes": (c_uint64, [c_void_p]),
-            "xrl_debug_k1_phases": (None, [POINTER(c_uint64), c_int]),
-            "xrl_layer_info": (c_uint32, [c_void_p, c_uint32, POINTER(c_uint64), c_uint32]),
-            "xrl_single_layer_cache_clear": (None, []),
-            "xrl_single_layer_cache_stats": (None, [POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
-        }
-        for name, (res, args) in sigs.items():
+    _alloc_t = ScipyCompressedSparseAllocator.CFUNCTYPE
+    # name -> (result type, argument types) of every function include/xrl_abi.h declares
+    SIGNATURES = {
+        "xrl_last_error": (c_char_p, []),
+        "xrl_clear_error": (None, []),
+        "xrl_version": (c_char_p, []),
+        "xrl_device_count": (c_int, []),
+        "xrl_set_device": (c_int, [c_int]),
+        "c_xlinear_load_model_from_disk": (c_void_p, [c_char_p]),
+        "c_xlinear_load_model_from_disk_ext": (c_void_p, [c_char_p, c_int]),
+        "c_xlinear_load_mmap_model_from_disk": (c_void_p, [c_char_p, c_bool]),
+        "c_xlinear_compile_mmap_model": (None, [c_char_p, c_char_p]),
+        "c_xlinear_destruct_model": (None, [c_void_p]),
+        "c_xlinear_get_int_attr": (c_uint32, [c_void_p, c_char_p]),
+        "c_xlinear_get_layer_type": (c_int, [c_void_p, c_int]),
+        "c_xlinear_predict_csr_f32": (None, [c_void_p, POINTER(ScipyCsrF32), c_uint32, c_char_p, c_uint32, c_int, _alloc_t]),
+        "c_xlinear_predict_drm_f32": (None, [c_void_p, POINTER(ScipyDrmF32), c_uint32, c_char_p, c_uint32, c_int, _alloc_t]),
+        "c_xlinear_predict_on_selected_outputs_csr_f32": (None, [c_void_p, POINTER(ScipyCsrF32), POINTER(ScipyCsrF32), c_char_p, c_int, _alloc_t]),
+        "c_xlinear_predict_on_selected_outputs_drm_f32": (None, [c_void_p, POINTER(ScipyDrmF32), POINTER(ScipyCsrF32), c_char_p, c_int, _alloc_t]),
+        "c_xlinear_single_layer_predict_csr_f32": (None, [POINTER(ScipyCsrF32), POINTER(ScipyCsrF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), c_char_p, c_uint32, c_int, c_float, _alloc_t]),
+        "c_xlinear_single_layer_predict_drm_f32": (None, [POINTER(ScipyDrmF32), POINTER(ScipyCsrF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), c_char_p, c_uint32, c_int, c_float, _alloc_t]),
+        "c_xlinear_single_layer_predict_on_selected_outputs_csr_f32": (None, [POINTER(ScipyCsrF32), POINTER(ScipyCsrF32), POINTER(ScipyCsrF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), c_char_p, c_int, c_float, _alloc_t]),
+        "c_xlinear_single_layer_predict_on_selected_outputs_drm_f32": (None, [POINTER(ScipyDrmF32), POINTER(ScipyCsrF32), POINTER(ScipyCsrF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), c_char_p, c_int, c_float, _alloc_t]),
+        "c_sparse_inner_products_csr2csc_f32": (None, [POINTER(ScipyCsrF32), POINTER(ScipyCscF32), c_uint64, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_float), c_int]),
+        "c_sparse_inner_products_drm2csc_f32": (None, [POINTER(ScipyDrmF32), POINTER(ScipyCscF32), c_uint64, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_float), c_int]),
+        "c_sparse_inner_products_csr2dcm_f32": (None, [POINTER(ScipyCsrF32), POINTER(ScipyDcmF32), c_uint64, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_float), c_int]),
+        "c_sparse_inner_products_drm2dcm_f32": (None, [POINTER(ScipyDrmF32), POINTER(ScipyDcmF32), c_uint64, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_float), c_int]),
+        "xrl_inspect_model": (c_int, [c_char_p, POINTER(c_uint64), c_uint32]),
+        "xrl_model_create": (c_void_p, [c_uint32, c_void_p, c_void_p, POINTER(c_float), POINTER(c_uint32), POINTER(c_char_p)]),
+        "xrl_queries_upload_csr": (c_void_p, [c_void_p, POINTER(ScipyCsrF32)]),
+        "xrl_queries_upload_drm": (c_void_p, [c_void_p, POINTER(ScipyDrmF32)]),
+        "xrl_queries_from_device_csr": (c_void_p, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64]),
+        "xrl_queries_from_device_drm": (c_void_p, [c_void_p, c_uint32, c_uint32, c_void_p]),
+        "xrl_queries_concat_device": (c_void_p, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p]),
+        "xrl_queries_tfidf_device": (c_void_p, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+        "xrl_queries_concat_device_ex": (c_void_p, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_int, c_void_p]),
+        "xrl_queries_info": (c_int, [c_void_p, POINTER(c_uint64)]),
+        "xrl_queries_download": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+        "xrl_queries_free": (None, [c_void_p]),
+        "c_tfidf_load": (c_void_p, [c_char_p]),
+        "c_tfidf_destruct": (None, [c_void_p]),
+        "c_tfidf_predict": (None, [c_void_p, c_void_p, POINTER(c_uint64), c_uint64, c_int, _alloc_t]),
+        "c_tfidf_predict_from_file": (None, [c_void_p, c_void_p, c_uint64, c_uint64, c_int, _alloc_t]),
+        "xrl_tfidf_counts": (None, [c_void_p, c_void_p, POINTER(c_uint64), c_uint64, c_int, _alloc_t]),
+        "xrl_tfidf_nr_features": (c_uint32, [c_void_p]),
+        "xrl_tfidf_predict_device": (c_void_p, [c_void_p, c_void_p, c_void_p, POINTER(c_uint64), c_uint64, c_int]),
+        "xrl_queries_concat_handle": (c_void_p, [c_void_p, c_void_p, c_uint32, c_void_p, c_int, c_void_p]),
+        "xrl_predict_device": (c_int, [c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int]),
+        "xrl_predict_device_rows": (c_int, [c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int, c_uint32, c_uint32]),
+        "xrl_ensemble_device": (c_int, [c_int, c_uint32, c_uint32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint32), c_int,
+                                        POINTER(c_float), c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int]),
+        "xrl_predict_selected_device": (c_int, [c_void_p, c_void_p, c_char_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_int]),
+        "xrl_predict_stats": (c_int, [c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, POINTER(c_double), c_uint32]),
+        "xrl_effective_topk": (c_uint32, [c_void_p, c_uint32]),
+        "xrl_profile_enable": (None, [c_void_p, c_int]),
+        "xrl_profile_reset": (None, [c_void_p]),
+        "xrl_profile_get": (c_uint32, [c_void_p, POINTER(ProfileRec), c_uint32]),
+        "xrl_set_option": (c_int, [c_void_p, c_char_p, c_int64]),
+        "xrl_model_device_bytes": (c_uint64, [c_void_p]),
+        "xrl_debug_k1_phases": (None, [POINTER(c_uint64), c_int]),
+        "xrl_debug_split_chunk": (c_uint32, [POINTER(c_uint64), c_uint32, c_uint64]),
+        "xrl_debug_layout_rows": (c_uint64, [POINTER(c_uint32), c_uint32, c_int, POINTER(c_uint32)]),
+        "xrl_debug_host_batches": (c_uint32, [POINTER(c_uint64), c_uint32, c_uint32, c_int, POINTER(c_uint32), c_uint32]),
+        "xrl_layer_info": (c_uint32, [c_void_p, c_uint32, POINTER(c_uint64), c_uint32]),
+        "xrl_single_layer_cache_clear": (None, []),
+        "xrl_single_layer_cache_stats": (None, [POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    }
+
+    @classmethod
+    def _link(cls, lib):
+        for name, (res, args) in cls.SIGNATURES.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
 
-    EXPORTED_SYMBOLS = None  # filled below from include/xrl_abi.h by tests
+    @staticmethod
+    def _x_view(X, check_sorted=True, not_implemented=None):
+        """A caller's query matrix as (zero-copy view, "csr" or "drm": the suffix of the symbol that takes that view)."""
+        if isinstance(X, smat.csr_matrix):
+            if check_sorted and not X.has_sorted_indices:
+                raise ValueError("Query matrix does not have sorted indices!")
+            X = ScipyCsrF32.init_from(X)
+        elif isinstance(X, np.ndarray):
+            X = ScipyDrmF32.init_from(X)
+        if isinstance(X, ScipyCsrF32):
+            return X, "csr"
+        if isinstance(X, ScipyDrmF32):
+            return X, "drm"
+        raise NotImplementedError(not_implemented or "type(X) = {} not implemented".format(type(X)))
+
+    @staticmethod
+    def _cstr(s):
+        """An optional string argument: utf-8 bytes, or NULL for None / ""."""
+        return s.encode("utf-8") if s else None
+
+    @contextlib.contextmanager
+    def freeing(self, *handles):
+        """``with clib.freeing(q, q2): ...`` frees the query handles when the block ends, also by an exception; ``None`` is skipped."""
+        try:
+            yield
+        finally:
+            for h in handles:
+                if h is not None:
+                    self.queries_free(h)
 
     def _check(self):
         err = self.clib_float32.xrl_last_error()
@@ -312,46 +348,24 @@ class corelib(object):
                         threads, pred_alloc):
         """Full beam-search prediction (base.py:1041-1095).  ``None``/0 overrides = model defaults."""
         clib = self.clib_float32
-        if isinstance(X, smat.csr_matrix):
-            if not X.has_sorted_indices:
-                raise ValueError("Query matrix does not have sorted indices!")
-            X = ScipyCsrF32.init_from(X)
-        elif isinstance(X, np.ndarray):
-            X = ScipyDrmF32.init_from(X)
-        if isinstance(X, ScipyCsrF32):
-            c_predict = clib.c_xlinear_predict_csr_f32
-        elif isinstance(X, ScipyDrmF32):
-            c_predict = clib.c_xlinear_predict_drm_f32
-        else:
-            raise NotImplementedError("type(X) = {} not implemented".format(type(X)))
+        X, fmt = self._x_view(X)
+        c_predict = getattr(clib, f"c_xlinear_predict_{fmt}_f32")
         cb = pred_alloc.cfunc
         c_predict(c_void_p(c_model), byref(X), overriden_beam_size if overriden_beam_size else 0,
-                  overriden_post_processor_str.encode("utf-8") if overriden_post_processor_str else None,
-                  overriden_only_topk if overriden_only_topk else 0, threads, cb)
+                  self._cstr(overriden_post_processor_str), overriden_only_topk if overriden_only_topk else 0, threads, cb)
         self._check()
 
     def xlinear_predict_on_selected_outputs(self, c_model, X, selected_outputs_csr, overriden_post_processor_str, threads,
                                             pred_alloc):
         """Scores for a given (query, label) pattern (base.py:1097-1141)."""
         clib = self.clib_float32
-        if isinstance(X, smat.csr_matrix):
-            if not X.has_sorted_indices:
-                raise ValueError("Query matrix does not have sorted indices!")
-            X = ScipyCsrF32.init_from(X)
-        elif isinstance(X, np.ndarray):
-            X = ScipyDrmF32.init_from(X)
+        X, fmt = self._x_view(X)
         if not isinstance(selected_outputs_csr, smat.csr_matrix):
             raise ValueError("type(selected_outputs_csr) = {} not implemented".format(type(selected_outputs_csr)))
         S = ScipyCsrF32.init_from(selected_outputs_csr.astype(np.float32))
-        if isinstance(X, ScipyCsrF32):
-            c_predict = clib.c_xlinear_predict_on_selected_outputs_csr_f32
-        elif isinstance(X, ScipyDrmF32):
-            c_predict = clib.c_xlinear_predict_on_selected_outputs_drm_f32
-        else:
-            raise NotImplementedError("type(X) = {} not implemented".format(type(X)))
+        c_predict = getattr(clib, f"c_xlinear_predict_on_selected_outputs_{fmt}_f32")
         cb = pred_alloc.cfunc
-        c_predict(c_void_p(c_model), byref(X), byref(S),
-                  overriden_post_processor_str.encode("utf-8") if overriden_post_processor_str else None, threads, cb)
+        c_predict(c_void_p(c_model), byref(X), byref(S), self._cstr(overriden_post_processor_str), threads, cb)
         self._check()
 
     def xlinear_single_layer_predict(self, X, csr_codes, W, C, post_processor_str, only_topk, num_threads, bias, pred_alloc):
@@ -360,18 +374,8 @@ class corelib(object):
         post_processor_str = post_processor_str.encode("utf-8")
         W = ScipyCscF32.init_from(W)
         C = ScipyCscF32.init_from(C)
-        if isinstance(X, smat.csr_matrix):
-            if not X.has_sorted_indices:
-                raise ValueError("Query matrix does not have sorted indices!")
-            X = ScipyCsrF32.init_from(X)
-        elif isinstance(X, np.ndarray):
-            X = ScipyDrmF32.init_from(X)
-        if isinstance(X, ScipyCsrF32):
-            c_predict = clib.c_xlinear_single_layer_predict_csr_f32
-        elif isinstance(X, ScipyDrmF32):
-            c_predict = clib.c_xlinear_single_layer_predict_drm_f32
-        else:
-            raise NotImplementedError("type(X) = {} not implemented".format(type(X)))
+        X, fmt = self._x_view(X)
+        c_predict = getattr(clib, f"c_xlinear_single_layer_predict_{fmt}_f32")
         codes = ScipyCsrF32.init_from(csr_codes)
         cb = pred_alloc.cfunc
         c_predict(byref(X), byref(codes) if codes is not None else None, byref(W),
@@ -385,18 +389,8 @@ class corelib(object):
         post_processor_str = post_processor_str.encode("utf-8")
         W = ScipyCscF32.init_from(W)
         S = ScipyCsrF32.init_from(selected_outputs_csr.astype(np.float32))
-        if isinstance(X, smat.csr_matrix):
-            if not X.has_sorted_indices:
-                raise ValueError("Query matrix does not have sorted indices!")
-            X = ScipyCsrF32.init_from(X)
-        elif isinstance(X, np.ndarray):
-            X = ScipyDrmF32.init_from(X)
-        if isinstance(X, ScipyCsrF32):
-            fn = clib.c_xlinear_single_layer_predict_on_selected_outputs_csr_f32
-        elif isinstance(X, ScipyDrmF32):
-            fn = clib.c_xlinear_single_layer_predict_on_selected_outputs_drm_f32
-        else:
-            raise NotImplementedError("type(X) = {} not implemented".format(type(X)))
+        X, fmt = self._x_view(X)
+        fn = getattr(clib, f"c_xlinear_single_layer_predict_on_selected_outputs_{fmt}_f32")
         if C is None:
             C = smat.csc_matrix(np.ones((W.shape[1], 1), dtype=np.float32))
         C = ScipyCscF32.init_from(C)
@@ -417,16 +411,15 @@ class corelib(object):
         nnz = len(X_row_idx)
         assert nnz == len(W_col_idx)
         assert X.shape[1] == W.shape[0]
-        if isinstance(X, smat.csr_matrix) and isinstance(W, smat.csc_matrix):
-            pX, pW, fn = ScipyCsrF32.init_from(X), ScipyCscF32.init_from(W), clib.c_sparse_inner_products_csr2csc_f32
-        elif isinstance(X, np.ndarray) and isinstance(W, smat.csc_matrix):
-            pX, pW, fn = ScipyDrmF32.init_from(X), ScipyCscF32.init_from(W), clib.c_sparse_inner_products_drm2csc_f32
-        elif isinstance(X, smat.csr_matrix) and isinstance(W, np.ndarray):
-            pX, pW, fn = ScipyCsrF32.init_from(X), ScipyDcmF32.init_from(W), clib.c_sparse_inner_products_csr2dcm_f32
-        elif isinstance(X, np.ndarray) and isinstance(W, np.ndarray):
-            pX, pW, fn = ScipyDrmF32.init_from(X), ScipyDcmF32.init_from(W), clib.c_sparse_inner_products_drm2dcm_f32
+        unknown = "type(X)={} and type(W)={} no implemented".format(type(X), type(W))
+        pX, x_fmt = self._x_view(X, check_sorted=False, not_implemented=unknown)      # (unsorted indices are accepted here)
+        if isinstance(W, smat.csc_matrix):
+            pW, w_fmt = ScipyCscF32.init_from(W), "csc"
+        elif isinstance(W, np.ndarray):
+            pW, w_fmt = ScipyDcmF32.init_from(W), "dcm"
         else:
-            raise NotImplementedError("type(X)={} and type(W)={} no implemented".format(type(X), type(W)))
+            raise NotImplementedError(unknown)
+        fn = getattr(clib, f"c_sparse_inner_products_{x_fmt}2{w_fmt}_f32")
         if pred_values is None or len(pred_values) != nnz or pred_values.dtype != np.float32:
             pred_values = np.zeros(nnz, pW.dtype)
         rows = np.ascontiguousarray(X_row_idx, dtype=np.uint32)
@@ -439,14 +432,8 @@ class corelib(object):
     # ------------------------------------------------------------------ device-resident path (additive)
     def queries_upload(self, c_model, X):
         lib = self.clib_float32
-        if isinstance(X, smat.csr_matrix):
-            if not X.has_sorted_indices:
-                raise ValueError("Query matrix does not have sorted indices!")
-            h = lib.xrl_queries_upload_csr(c_void_p(c_model), byref(ScipyCsrF32.init_from(X)))
-        elif isinstance(X, np.ndarray):
-            h = lib.xrl_queries_upload_drm(c_void_p(c_model), byref(ScipyDrmF32.init_from(X)))
-        else:
-            raise NotImplementedError("type(X) = {} not implemented".format(type(X)))
+        X, fmt = self._x_view(X)
+        h = getattr(lib, f"xrl_queries_upload_{fmt}")(c_void_p(c_model), byref(X))
         self._check()
         return h
 
@@ -564,12 +551,9 @@ class corelib(object):
     def queries_download(self, h):
         """Copy of a query handle's matrix back to the host (scipy CSR with the stored order, or ndarray)."""
         info = (ctypes.c_uint64 * 4)()
-        fn = self.clib_float32.xrl_queries_info
-        fn.restype = ctypes.c_int; fn.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_uint64)]
-        fn(c_void_p(h), info); self._check()
+        self.clib_float32.xrl_queries_info(c_void_p(h), info); self._check()
         rows, cols, nnz, dense = (int(v) for v in info)
         dl = self.clib_float32.xrl_queries_download
-        dl.restype = ctypes.c_int; dl.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
         if dense:
             out = np.zeros((rows, cols), dtype=np.float32)
             dl(c_void_p(h), None, None, out.ctypes.data_as(c_void_p)); self._check()
@@ -589,7 +573,7 @@ class corelib(object):
         """``d_*`` are raw device addresses (e.g. ``tensor.data_ptr()``)."""
         rc = self.clib_float32.xrl_predict_device(
             c_void_p(c_model), c_void_p(queries), beam_size or 0,
-            post_processor.encode("utf-8") if post_processor else None, only_topk or 0,
+            self._cstr(post_processor), only_topk or 0,
             c_void_p(d_idx), c_void_p(d_val), c_void_p(d_cnt), out_stride, c_void_p(stream or 0), 1 if sync else 0)
         self._check()
         return rc
@@ -599,7 +583,7 @@ class corelib(object):
         """predict_device for rows [row_begin, row_begin + row_count) only; results land at the same rows of the output buffers."""
         rc = self.clib_float32.xrl_predict_device_rows(
             c_void_p(c_model), c_void_p(queries), beam_size or 0,
-            post_processor.encode("utf-8") if post_processor else None, only_topk or 0,
+            self._cstr(post_processor), only_topk or 0,
             c_void_p(d_idx), c_void_p(d_val), c_void_p(d_cnt), out_stride, c_void_p(stream or 0), 1 if sync else 0,
             int(row_begin), int(row_count))
         self._check()
@@ -613,7 +597,7 @@ class corelib(object):
         bad row.  ``sync=True`` raises RuntimeError with the host path's message on a bad row; ``sync=False`` returns without synchronising.
         Returns the library's return code."""
         rc = self.clib_float32.xrl_predict_selected_device(
-            c_void_p(c_model), c_void_p(queries), post_processor.encode("utf-8") if post_processor else None,
+            c_void_p(c_model), c_void_p(queries), self._cstr(post_processor),
             c_void_p(d_sel_idx), c_void_p(d_sel_cnt or 0), int(sel_stride), c_void_p(d_idx), c_void_p(d_val), c_void_p(d_cnt), int(out_stride),
             c_void_p(d_status or 0), c_void_p(stream or 0), 1 if sync else 0)
         self._check()
@@ -643,8 +627,6 @@ class corelib(object):
         """Host-only: number of even column tiles the model compiler cuts a chunk with these column nnz into."""
         cum = np.concatenate([[0], np.cumsum(np.asarray(col_nnz, dtype=np.uint64))]).astype(np.uint64)
         fn = self.clib_float32.xrl_debug_split_chunk
-        fn.restype = ctypes.c_uint32
-        fn.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_uint64]
         return int(fn(cum.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), len(col_nnz), int(limit)))
 
     def debug_layout_rows(self, row_len, align=True):
@@ -652,8 +634,6 @@ class corelib(object):
         rptr = np.concatenate([[0], np.cumsum(np.asarray(row_len, dtype=np.int64))]).astype(np.uint32)
         ext = np.zeros(len(row_len), dtype=np.uint32)
         fn = self.clib_float32.xrl_debug_layout_rows
-        fn.restype = ctypes.c_uint64
-        fn.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]
         total = int(fn(rptr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(row_len), 1 if align else 0,
                        ext.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
         self._check()
@@ -663,9 +643,6 @@ class corelib(object):
         """Host-only: row-batch boundaries of the pipelined host ABI for a CSR X with this row pointer (``None``: dense rows x cols)."""
         ptr = None if indptr is None else np.ascontiguousarray(indptr, dtype=np.uint64)
         fn = self.clib_float32.xrl_debug_host_batches
-        fn.restype = ctypes.c_uint32
-        fn.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
-                       ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32]
         rb = np.zeros(34, dtype=np.uint32)          # at most 32 batches
         n = int(fn(None if ptr is None else ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), int(rows), int(cols), int(host_batch_mb),
                    rb.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(rb)))
@@ -691,8 +668,7 @@ class corelib(object):
         depth = self.xlinear_get_int_attr(c_model, "depth")
         out = (c_double * (8 * depth))()
         self.clib_float32.xrl_predict_stats(c_void_p(c_model), c_void_p(queries), beam_size or 0,
-                                            post_processor.encode("utf-8") if post_processor else None,
-                                            only_topk or 0, out, 8 * depth)
+                                            self._cstr(post_processor), only_topk or 0, out, 8 * depth)
         self._check()
         keys = ("ref_chunk_bytes", "candidates", "items", "probes", "hit_rows", "hit_entries", "item_cols", "x_cols")
         return [dict(zip(keys, [out[8 * l + i] for i in range(8)])) for l in range(depth)]

@@ -38,8 +38,7 @@ void upload_x(const HostX& x, DevBuf& ptr, DevBuf& idx, DevBuf& val, QueriesDev&
         idx.upload_raw(x.col_idx, elems * 4);
     }
     val.upload_raw(x.val, elems * 4);
-    d.row_ptr = x.csr ? ptr.as<uint64_t>() : nullptr; d.col_idx = x.csr ? idx.as<uint32_t>() : nullptr; d.val = val.as<float>();
-    d.rows = x.rows; d.cols = x.cols; d.dense = x.csr ? 0 : 1; d.nnz = x.csr ? elems : 0;
+    d = device_view(x, ptr, idx, val);
 }
 }  // namespace xrl
 
@@ -176,9 +175,9 @@ static void* queries_upload(void* model, const HostX& x) {
         Model& m = *as_model(model);
         use_device(m.device);
         auto q = std::make_unique<Queries>();
-        q->device = m.device;
-        upload_x(x, q->ptr, q->idx, q->val, q->dev);
-        q->nnz = q->dev.nnz;
+        QueriesDev d{};
+        upload_x(x, q->ptr, q->idx, q->val, d);
+        set_view(*q, m.device, d);
         return q.release();
     });
 }
@@ -191,9 +190,7 @@ void* xrl_queries_from_device_csr(void* model, uint32_t rows, uint32_t cols, con
         Model& m = *as_model(model);
         if (rows && (!d_row_ptr || (nnz && (!d_col_idx || !d_val)))) fail("xrl_queries_from_device_csr: null device pointer");
         auto q = std::make_unique<Queries>();
-        q->device = m.device; q->nnz = nnz;
-        q->dev.row_ptr = d_row_ptr; q->dev.col_idx = d_col_idx; q->dev.val = d_val;
-        q->dev.rows = rows; q->dev.cols = cols; q->dev.dense = 0; q->dev.nnz = nnz;
+        set_view(*q, m.device, csr_view(rows, cols, d_row_ptr, d_col_idx, d_val, nnz));
         return q.release();
     });
 }
@@ -206,7 +203,6 @@ void* xrl_queries_tfidf_device(void* model, uint32_t rows, uint32_t cols, const 
         if (rows && (!d_row_ptr || (nnz && (!d_col_idx || !d_count)))) fail("xrl_queries_tfidf_device: null device pointer");
         use_device(m.device);
         auto q = std::make_unique<Queries>();
-        q->device = m.device; q->nnz = nnz;
         if (!d_out) q->val.reserve(nnz * 4);         // the handle owns the weighted values unless the caller supplies the buffer; row pointers and column ids stay the caller's
         float* dst = d_out ? d_out : q->val.as<float>();
         hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : m.stream;
@@ -217,8 +213,7 @@ void* xrl_queries_tfidf_device(void* model, uint32_t rows, uint32_t cols, const 
         XRL_HIP(hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, s));
         XRL_HIP(hipStreamSynchronize(s));
         if (err) fail("xrl_queries_tfidf_device: a column id outside [0, cols) (the reference's idx_idf.at() throws)");
-        q->dev.row_ptr = d_row_ptr; q->dev.col_idx = d_col_idx; q->dev.val = dst;
-        q->dev.rows = rows; q->dev.cols = cols; q->dev.dense = 0; q->dev.nnz = nnz;
+        set_view(*q, m.device, csr_view(rows, cols, d_row_ptr, d_col_idx, dst, nnz));
         return q.release();
     });
 }
@@ -228,11 +223,26 @@ void* xrl_queries_from_device_drm(void* model, uint32_t rows, uint32_t cols, con
         Model& m = *as_model(model);
         if (rows && cols && !d_val) fail("xrl_queries_from_device_drm: null device pointer");
         auto q = std::make_unique<Queries>();
-        q->device = m.device;
-        q->dev.row_ptr = nullptr; q->dev.col_idx = nullptr; q->dev.val = d_val;
-        q->dev.rows = rows; q->dev.cols = cols; q->dev.dense = 1; q->dev.nnz = 0;
+        set_view(*q, m.device, dense_view(rows, cols, d_val));
         return q.release();
     });
+}
+
+// [X_feat | X_emb] as one CSR the handle owns (the body of the two concat makers; runs inside their exception barrier)
+static void* concat_csr(void* model, uint32_t rows, uint32_t sparse_cols, const uint64_t* d_row_ptr, const uint32_t* d_col_idx, const float* d_val,
+                        uint64_t nnz, uint32_t dense_cols, const float* d_emb, int normalize_emb, void* hip_stream) {
+    Model& m = *as_model(model);
+    if (rows && (!d_row_ptr || (nnz && (!d_col_idx || !d_val)) || (dense_cols && !d_emb))) fail("xrl_queries_concat_device: null device pointer");
+    use_device(m.device);
+    auto q = std::make_unique<Queries>();
+    const uint64_t out_nnz = nnz + (uint64_t)rows * dense_cols;
+    q->ptr.reserve(((size_t)rows + 1) * 8); q->idx.reserve(out_nnz * 4); q->val.reserve(out_nnz * 4);
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : m.stream;
+    launch_concat_csr(d_row_ptr, d_col_idx, d_val, d_emb, rows, sparse_cols, dense_cols, normalize_emb, q->ptr.as<uint64_t>(), q->idx.as<uint32_t>(),
+                      q->val.as<float>(), s);
+    XRL_HIP(hipStreamSynchronize(s));
+    set_own_csr(*q, m.device, rows, sparse_cols + dense_cols, out_nnz);
+    return q.release();
 }
 
 void* xrl_queries_concat_device(void* model, uint32_t rows, uint32_t sparse_cols, const uint64_t* d_row_ptr, const uint32_t* d_col_idx,
@@ -242,22 +252,17 @@ void* xrl_queries_concat_device(void* model, uint32_t rows, uint32_t sparse_cols
 
 void* xrl_queries_concat_device_ex(void* model, uint32_t rows, uint32_t sparse_cols, const uint64_t* d_row_ptr, const uint32_t* d_col_idx,
                                    const float* d_val, uint64_t nnz, uint32_t dense_cols, const float* d_emb, int normalize_emb, void* hip_stream) {
-    return guarded_value((void*)nullptr, [&]() -> void* {
-        Model& m = *as_model(model);
-        if (rows && (!d_row_ptr || (nnz && (!d_col_idx || !d_val)) || (dense_cols && !d_emb))) fail("xrl_queries_concat_device: null device pointer");
-        use_device(m.device);
-        auto q = std::make_unique<Queries>();
-        q->device = m.device;
-        const uint64_t out_nnz = nnz + (uint64_t)rows * dense_cols;
-        q->ptr.reserve(((size_t)rows + 1) * 8); q->idx.reserve(out_nnz * 4); q->val.reserve(out_nnz * 4);
-        hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : m.stream;
-        launch_concat_csr(d_row_ptr, d_col_idx, d_val, d_emb, rows, sparse_cols, dense_cols, normalize_emb, q->ptr.as<uint64_t>(), q->idx.as<uint32_t>(),
-                          q->val.as<float>(), s);
-        XRL_HIP(hipStreamSynchronize(s));
-        q->nnz = out_nnz;
-        q->dev.row_ptr = q->ptr.as<uint64_t>(); q->dev.col_idx = q->idx.as<uint32_t>(); q->dev.val = q->val.as<float>();
-        q->dev.rows = rows; q->dev.cols = sparse_cols + dense_cols; q->dev.dense = 0; q->dev.nnz = out_nnz;
-        return q.release();
+    return guarded_value((void*)nullptr, [&] {
+        return concat_csr(model, rows, sparse_cols, d_row_ptr, d_col_idx, d_val, nnz, dense_cols, d_emb, normalize_emb, hip_stream);
+    });
+}
+
+void* xrl_queries_concat_handle(void* model, void* queries, uint32_t dense_cols, const float* d_emb, int normalize_emb, void* hip_stream) {
+    return guarded_value((void*)nullptr, [&] {
+        if (!queries) fail("xrl_queries_concat_handle: null query handle");
+        const QueriesDev& X = static_cast<Queries*>(queries)->dev;
+        if (X.dense) fail("xrl_queries_concat_handle: the query handle must hold a CSR");
+        return concat_csr(model, X.rows, X.cols, X.row_ptr, X.col_idx, X.val, X.nnz, dense_cols, d_emb, normalize_emb, hip_stream);
     });
 }
 

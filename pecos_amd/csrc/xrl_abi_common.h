@@ -1,5 +1,5 @@
 // What the units behind the extern "C" surface share (xrl_abi.cpp, xrl_host_pipeline.cpp, xrl_single_layer.cpp, xrl_tfidf_abi.cpp):
-// the per-thread error and device state, the exception barrier of every entry point, and the upload of a caller's host X.
+// the per-thread error and device state, the exception barrier of every entry point, the makers of X's device view, and the upload of a caller's host X.
 #pragma once
 #include "../../include/xrl_abi.h"
 
@@ -50,6 +50,32 @@ struct HostX {
     uint64_t elems() const { return csr ? (rows ? row_ptr[rows] : 0) : (uint64_t)rows * cols; }
     uint32_t elem_bytes() const { return csr ? 8u : 4u; }
 };
+
+// The two forms of X on the device.  Every QueriesDev is made by one of them, so `dense`, `nnz` and the null CSR arrays of a dense X
+// cannot disagree (k1q_row clamps with X.nnz).
+inline QueriesDev csr_view(uint32_t rows, uint32_t cols, const uint64_t* row_ptr, const uint32_t* col_idx, const float* val, uint64_t nnz) {
+    QueriesDev d{};
+    d.row_ptr = row_ptr; d.col_idx = col_idx; d.val = val;
+    d.rows = rows; d.cols = cols; d.dense = 0; d.nnz = nnz;
+    return d;
+}
+inline QueriesDev dense_view(uint32_t rows, uint32_t cols, const float* val) {
+    QueriesDev d{};
+    d.val = val;
+    d.rows = rows; d.cols = cols; d.dense = 1; d.nnz = 0;
+    return d;
+}
+// ... of a host X whose device copy lives (or will live) in these buffers
+inline QueriesDev device_view(const HostX& x, const DevBuf& ptr, const DevBuf& idx, const DevBuf& val) {
+    return x.csr ? csr_view(x.rows, x.cols, ptr.as<uint64_t>(), idx.as<uint32_t>(), val.as<float>(), x.elems()) : dense_view(x.rows, x.cols, val.as<float>());
+}
+
+// The only writer of a handle's device, view and (redundant) nnz: from a view of arrays it may or may not own ...
+inline void set_view(Queries& q, int device, const QueriesDev& v) { q.device = device; q.dev = v; q.nnz = v.nnz; }
+// ... or as a CSR in its own ptr / idx / val buffers
+inline void set_own_csr(Queries& q, int device, uint32_t rows, uint32_t cols, uint64_t nnz) {
+    set_view(q, device, csr_view(rows, cols, q.ptr.as<uint64_t>(), q.idx.as<uint32_t>(), q.val.as<float>(), nnz));
+}
 
 // synchronous upload of the whole X into the given buffers (dense X: `val` only); `d` describes the device copy
 void upload_x(const HostX& x, DevBuf& ptr, DevBuf& idx, DevBuf& val, QueriesDev& d);

@@ -338,7 +338,6 @@ struct HostCall {
 QueriesDev device_arrays(Model& m, const HostX& x, PrepLap& fine) {
     Workspace& ws = *m.ws;
     const uint64_t elems = x.elems();
-    QueriesDev X{};
     if (x.csr) {
         // the row pointer travels like the rest of X: through pinned staging, first on the copy stream (every row batch waits for a later event of that
         // stream).  A synchronous hipMemcpy from the caller's pageable array took 14-26 ms in the SECOND call of a process (the runtime pins the region it
@@ -352,9 +351,7 @@ QueriesDev device_arrays(Model& m, const HostX& x, PrepLap& fine) {
         ws.x_idx.reserve(elems * 4);
     }
     ws.x_val.reserve(elems * 4);
-    X.row_ptr = x.csr ? ws.x_ptr.as<uint64_t>() : nullptr; X.col_idx = x.csr ? ws.x_idx.as<uint32_t>() : nullptr; X.val = ws.x_val.as<float>();
-    X.rows = x.rows; X.cols = x.cols; X.dense = x.csr ? 0 : 1; X.nnz = x.csr ? elems : 0;
-    return X;
+    return device_view(x, ws.x_ptr, ws.x_idx, ws.x_val);
 }
 
 // two lanes: the auxiliary one starts after everything queued on the handle's stream so far (an earlier asynchronous predict may still use the scratch)

@@ -87,7 +87,6 @@ std::unique_ptr<Queries> tfidf_to_device(const TfidfHandle& H, const char* const
         nnz = n;
     });
     auto q = std::make_unique<Queries>();
-    q->device = device; q->nnz = nnz;
     DevBuf d_seg, d_idf, d_err;
     d_seg.upload(seg_ptr);
     q->idx.reserve((size_t)nnz * 4); q->val.reserve((size_t)nnz * 4);
@@ -115,8 +114,7 @@ std::unique_ptr<Queries> tfidf_to_device(const TfidfHandle& H, const char* const
     XRL_HIP(hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, s));
     XRL_HIP(hipStreamSynchronize(s));
     if (err) fail("tfidf: a feature id outside the model's feature range");
-    q->dev.row_ptr = q->ptr.as<uint64_t>(); q->dev.col_idx = q->idx.as<uint32_t>(); q->dev.val = q->val.as<float>();
-    q->dev.rows = rows; q->dev.cols = V.nr_features; q->dev.dense = 0; q->dev.nnz = q->nnz;
+    set_own_csr(*q, device, rows, V.nr_features, nnz);
     return q;
 }
 }  // namespace
@@ -269,13 +267,6 @@ void* xrl_tfidf_predict_device(void* vectorizer, void* model, void* corpus_ptr, 
         const TfidfHandle& H = *static_cast<TfidfHandle*>(vectorizer);
         return tfidf_to_device(H, static_cast<const char* const*>(corpus_ptr), doc_lens, nr_doc, threads, m.device, m.stream).release();
     });
-}
-
-void* xrl_queries_concat_handle(void* model, void* queries, uint32_t dense_cols, const float* d_emb, int normalize_emb, void* hip_stream) {
-    if (!queries) { set_err("xrl_queries_concat_handle: null query handle"); return nullptr; }
-    const Queries& q = *static_cast<Queries*>(queries);
-    if (q.dev.dense) { set_err("xrl_queries_concat_handle: the query handle must hold a CSR"); return nullptr; }
-    return xrl_queries_concat_device_ex(model, q.dev.rows, q.dev.cols, q.dev.row_ptr, q.dev.col_idx, q.dev.val, q.dev.nnz, dense_cols, d_emb, normalize_emb, hip_stream);
 }
 
 // host only (no GPU): the hstacked TERM-COUNT CSR the device weighting starts from -- what the tokenizer and the n-gram lookup produce

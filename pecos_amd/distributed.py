@@ -191,6 +191,7 @@ class ShardedXLinear:
     def _predict_shard_gpu(self, Xs, beam_size, only_topk, post_processor):
         import torch
         from .core import clib
+        from .features import result_buffers
         h = self.model.model.model_chain
         k = clib.effective_topk(h, only_topk)
         n = Xs.shape[0]
@@ -199,16 +200,12 @@ class ShardedXLinear:
         if model_dev != dev.index:   # the handle lives on the device that was current when it was loaded (clib.set_device)
             raise RuntimeError(f"model handle is on GPU {model_dev} but torch's current device is {dev.index}: call "
                                "pecos_amd.clib.set_device(local_rank) before XLinearModel.load")
-        idx = torch.zeros((n, k), dtype=torch.int32, device=dev)
-        val = torch.zeros((n, k), dtype=torch.float32, device=dev)
-        cnt = torch.zeros((n,), dtype=torch.int32, device=dev)
+        idx, val, cnt = result_buffers(n, k, dev)
         if n:
             q = clib.queries_upload(h, Xs)
-            try:
+            with clib.freeing(q):
                 clib.predict_device(h, q, beam_size, post_processor, only_topk, idx.data_ptr(), val.data_ptr(),
                                     cnt.data_ptr(), k, stream=torch.cuda.current_stream().cuda_stream, sync=True)
-            finally:
-                clib.queries_free(q)
         return idx, val, cnt
 
     def predict(self, X, beam_size=None, only_topk=None, post_processor=None):

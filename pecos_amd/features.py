@@ -14,6 +14,8 @@
 * :func:`ensemble_device` -- the results of several models merged on the device (K6) like ``CsrEnsembler.average`` / ``rank_average`` /
   ``Text2Text.predict``'s tail; :func:`predict_text` and :class:`Text2Text` use it for ensembles that share a device.
 """
+import contextlib
+
 import numpy as np
 import scipy.sparse as smat
 
@@ -43,6 +45,44 @@ def concat_features(X_feat, X_emb, normalize_emb=True):
     return X_cat
 
 
+def result_buffers(rows, k, device, sync=False):
+    """The zeroed result triple (labels int32 [rows, k], scores float32 [rows, k], counts int32 [rows]) on ``device``.
+
+    Outputs first: their zero-fills run on torch's current stream, and a predict on any other stream may start only when they (like the
+    inputs, produced on that stream) are complete -- ``sync=True`` waits for torch's current stream.  A predict on the current stream
+    itself is ordered behind the fills and needs no wait."""
+    import torch
+    idx = torch.zeros((rows, k), dtype=torch.int32, device=device)
+    sc = torch.zeros((rows, k), dtype=torch.float32, device=device)
+    cnt = torch.zeros((rows,), dtype=torch.int32, device=device)
+    if sync:
+        torch.cuda.current_stream().synchronize()
+    return idx, sc, cnt
+
+
+@contextlib.contextmanager
+def _device_csr_queries(h, crow, col, val, n_cols, emb, normalize_emb, out_cols):
+    """A CSR that is already in HBM (and, with ``emb``, the dense block to append on the device) as a query handle of model handle ``h``,
+    with the result triple for ``out_cols`` entries per row: yields ``(q, rows, (idx, sc, cnt))`` and frees ``q`` on exit.  The triple is
+    made here because its place is fixed: after the inputs' ``contiguous()`` copies, before the wait that lets the concatenation (which
+    runs on the model's stream) read them."""
+    import torch
+    assert crow.is_cuda and col.is_cuda and val.is_cuda and crow.dtype == torch.int64 and col.dtype == torch.int32 and val.dtype == torch.float32
+    crow, col, val = crow.contiguous(), col.contiguous(), val.contiguous()
+    rows = crow.numel() - 1
+    nnz = int(val.numel())
+    out = result_buffers(rows, out_cols, val.device, sync=True)
+    if emb is not None:
+        assert emb.is_cuda and emb.dtype == torch.float32 and emb.shape[0] == rows
+        emb = emb.contiguous()
+        q = clib.queries_concat_device(h, rows, n_cols, crow.data_ptr(), col.data_ptr(), val.data_ptr(), nnz, emb.shape[1], emb.data_ptr(),
+                                       normalize_emb=normalize_emb)
+    else:
+        q = clib.queries_from_device_csr(h, rows, n_cols, crow.data_ptr(), col.data_ptr(), val.data_ptr(), nnz)
+    with clib.freeing(q):
+        yield q, rows, out
+
+
 def predict_from_torch(model, crow, col, val, n_cols, beam_size=None, only_topk=None, post_processor=None, emb=None, stream=None,
                        normalize_emb=False):
     """Beam search on queries that are already on the GPU.
@@ -53,31 +93,12 @@ def predict_from_torch(model, crow, col, val, n_cols, beam_size=None, only_topk=
     (labels int32 [rows, k], scores float32 [rows, k], counts int32 [rows]); row r holds counts[r] valid entries, best first."""
     import torch
     h = model.model.model_chain
-    assert crow.is_cuda and col.is_cuda and val.is_cuda and crow.dtype == torch.int64 and col.dtype == torch.int32 and val.dtype == torch.float32
-    crow, col, val = crow.contiguous(), col.contiguous(), val.contiguous()
-    rows = crow.numel() - 1
-    nnz = int(val.numel())
-    # outputs first: their zero-fills run on torch's current stream and must be complete (like the inputs, produced on that
-    # stream) before the predict starts on `stream`
     k = clib.effective_topk(h, only_topk)
-    idx = torch.zeros((rows, k), dtype=torch.int32, device=val.device)
-    sc = torch.zeros((rows, k), dtype=torch.float32, device=val.device)
-    cnt = torch.zeros((rows,), dtype=torch.int32, device=val.device)
-    torch.cuda.current_stream().synchronize()
-    if emb is not None:
-        assert emb.is_cuda and emb.dtype == torch.float32 and emb.shape[0] == rows
-        emb = emb.contiguous()
-        q = clib.queries_concat_device(h, rows, n_cols, crow.data_ptr(), col.data_ptr(), val.data_ptr(), nnz, emb.shape[1], emb.data_ptr(),
-                                       normalize_emb=normalize_emb)
-    else:
-        q = clib.queries_from_device_csr(h, rows, n_cols, crow.data_ptr(), col.data_ptr(), val.data_ptr(), nnz)
-    try:
+    with _device_csr_queries(h, crow, col, val, n_cols, emb, normalize_emb, k) as (q, rows, (idx, sc, cnt)):
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
         if rows:
             clib.predict_device(h, q, beam_size, post_processor, only_topk, idx.data_ptr(), sc.data_ptr(), cnt.data_ptr(), k,
                                 stream=s or None, sync=True)
-    finally:
-        clib.queries_free(q)
     return idx, sc, cnt
 
 
@@ -95,36 +116,18 @@ def predict_selected_from_torch(model, crow, col, val, n_cols, sel_idx, sel_cnt=
     model B on A's ``(labels, counts)`` (re-scoring), then ``ensemble_device([a, b], mode="finish")`` for a score-sorted result."""
     import torch
     h = model.model.model_chain
-    assert crow.is_cuda and col.is_cuda and val.is_cuda and crow.dtype == torch.int64 and col.dtype == torch.int32 and val.dtype == torch.float32
     assert sel_idx.is_cuda and sel_idx.dtype == torch.int32 and sel_idx.dim() == 2
-    crow, col, val, sel_idx = crow.contiguous(), col.contiguous(), val.contiguous(), sel_idx.contiguous()
-    rows = crow.numel() - 1
-    nnz = int(val.numel())
-    stride = sel_idx.shape[1]
-    assert sel_idx.shape[0] == rows
+    sel_idx = sel_idx.contiguous()
+    rows, stride = sel_idx.shape
+    assert crow.numel() - 1 == rows
     if sel_cnt is not None:
         assert sel_cnt.is_cuda and sel_cnt.dtype == torch.int32 and sel_cnt.shape == (rows,)
         sel_cnt = sel_cnt.contiguous()
-    # outputs first: their zero-fills run on torch's current stream and must be complete (like the inputs, produced on that
-    # stream) before the work starts on `stream`
-    idx = torch.zeros((rows, stride), dtype=torch.int32, device=val.device)
-    sc = torch.zeros((rows, stride), dtype=torch.float32, device=val.device)
-    cnt = torch.zeros((rows,), dtype=torch.int32, device=val.device)
-    torch.cuda.current_stream().synchronize()
-    if emb is not None:
-        assert emb.is_cuda and emb.dtype == torch.float32 and emb.shape[0] == rows
-        emb = emb.contiguous()
-        q = clib.queries_concat_device(h, rows, n_cols, crow.data_ptr(), col.data_ptr(), val.data_ptr(), nnz, emb.shape[1], emb.data_ptr(),
-                                       normalize_emb=normalize_emb)
-    else:
-        q = clib.queries_from_device_csr(h, rows, n_cols, crow.data_ptr(), col.data_ptr(), val.data_ptr(), nnz)
-    try:
+    with _device_csr_queries(h, crow, col, val, n_cols, emb, normalize_emb, stride) as (q, rows, (idx, sc, cnt)):
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
         if rows and stride:
             clib.predict_selected_device(h, q, post_processor, sel_idx.data_ptr(), sel_cnt.data_ptr() if sel_cnt is not None else None, stride,
                                          idx.data_ptr(), sc.data_ptr(), cnt.data_ptr(), stride, stream=s or None, sync=True)
-    finally:
-        clib.queries_free(q)
     return idx, sc, cnt
 
 
@@ -163,18 +166,13 @@ def predict_tfidf_from_torch(model, crow, col, count, n_cols, idf=None, binary=F
     crow, col, count = crow.contiguous(), col.contiguous(), count.contiguous()
     rows = crow.numel() - 1
     k = clib.effective_topk(h, only_topk)
-    idx = torch.zeros((rows, k), dtype=torch.int32, device=count.device)
-    sc = torch.zeros((rows, k), dtype=torch.float32, device=count.device)
-    cnt = torch.zeros((rows,), dtype=torch.int32, device=count.device)
-    torch.cuda.current_stream().synchronize()
+    idx, sc, cnt = result_buffers(rows, k, count.device, sync=True)
     q = clib.queries_tfidf_device(h, rows, n_cols, crow.data_ptr(), col.data_ptr(), count.data_ptr(), int(count.numel()),
                                   idf.data_ptr() if idf is not None else None, binary, sublinear_tf, 1 if norm == "l1" else 2)
-    try:
+    with clib.freeing(q):
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
         if rows:
             clib.predict_device(h, q, beam_size, post_processor, only_topk, idx.data_ptr(), sc.data_ptr(), cnt.data_ptr(), k, stream=s or None, sync=True)
-    finally:
-        clib.queries_free(q)
     return idx, sc, cnt
 
 
@@ -208,7 +206,7 @@ class Tfidf:
         return clib.tfidf_predict(self.model, corpus, buffer_size=kwargs.get("buffer_size", 0), threads=kwargs.get("threads", -1))
 
     def predict_device(self, xlinear_model, corpus, threads=-1):
-        """Texts -> X resident on ``xlinear_model``'s GPU: a query handle (``clib.queries_free`` it) for ``clib.predict_device``."""
+        """Texts -> X resident on ``xlinear_model``'s GPU: a query handle (to be freed: ``clib.freeing``) for ``clib.predict_device``."""
         return clib.tfidf_predict_device(self.model, xlinear_model.model.model_chain, corpus, threads)
 
 
@@ -258,9 +256,7 @@ def _predict_handle_to_csr(model, q, rows, beam_size=None, only_topk=None, post_
     h = model.model.model_chain
     k = clib.effective_topk(h, only_topk)
     dev = torch.device("cuda", clib.xlinear_get_int_attr(h, "device"))
-    idx = torch.zeros((rows, k), dtype=torch.int32, device=dev)
-    sc = torch.zeros((rows, k), dtype=torch.float32, device=dev)
-    cnt = torch.zeros((rows,), dtype=torch.int32, device=dev)
+    idx, sc, cnt = result_buffers(rows, k, dev)
     torch.cuda.synchronize(dev)
     if rows:
         clib.predict_device(h, q, beam_size, post_processor, only_topk, idx.data_ptr(), sc.data_ptr(), cnt.data_ptr(), k, stream=None, sync=True)
@@ -336,6 +332,24 @@ def _ensemble_on_device(models, ensemble, only_topk, finish=None):
 _ensemble_streams = {}
 
 
+@contextlib.contextmanager
+def _text_queries(vectorizer, model, corpus, X_emb, normalize_emb, threads):
+    """Texts -> the query handle to search, on ``model``'s device: the tf-idf X, or with ``X_emb`` (float32 [rows, H] CUDA tensor) the
+    concatenation [X | X_emb] made from it on the device.  Both handles are freed on exit."""
+    q = vectorizer.predict_device(model, corpus, threads=threads)
+    with clib.freeing(q):
+        if X_emb is None:
+            yield q
+            return
+        import torch
+        assert X_emb.is_cuda and X_emb.dtype == torch.float32 and X_emb.shape[0] == len(corpus)
+        X_emb = X_emb.contiguous()
+        torch.cuda.current_stream().synchronize()
+        q2 = clib.queries_concat_handle(model.model.model_chain, q, X_emb.shape[1], X_emb.data_ptr(), normalize_emb=normalize_emb)
+        with clib.freeing(q2):
+            yield q2
+
+
 def _predict_text_ensemble_device(vectorizer, models, corpus, X_emb, normalize_emb, threads, beam_size, only_topk, post_processor, finish):
     """predict_text's ensemble on the device: ONE tokenisation and upload (and one concatenation with X_emb), every model's beam search on
     that handle, the merge (K6) and nothing else on one stream, one synchronisation, one copy back, one CSR."""
@@ -344,37 +358,26 @@ def _predict_text_ensemble_device(vectorizer, models, corpus, X_emb, normalize_e
     hs = [m.model.model_chain for m in models]
     dev = torch.device("cuda", clib.xlinear_get_int_attr(hs[0], "device"))
     rows = len(corpus)
-    q = vectorizer.predict_device(models[0], corpus, threads=threads)
-    q2 = None
-    try:
-        if X_emb is not None:
-            assert X_emb.is_cuda and X_emb.dtype == torch.float32 and X_emb.shape[0] == rows
-            X_emb = X_emb.contiguous()
-            torch.cuda.current_stream().synchronize()
-            q2 = clib.queries_concat_handle(hs[0], q, X_emb.shape[1], X_emb.data_ptr(), normalize_emb=normalize_emb)
-        s = _ensemble_streams.get(dev.index)
-        if s is None:
-            s = _ensemble_streams[dev.index] = torch.cuda.Stream(device=dev)
-        mode, thr, topk = ("average", None, None) if finish is None else ("finish", finish[0], finish[1])
-        with torch.cuda.stream(s):
-            res = []
-            for h in hs:
-                k = clib.effective_topk(h, only_topk)
-                idx = torch.zeros((rows, k), dtype=torch.int32, device=dev)
-                sc = torch.zeros((rows, k), dtype=torch.float32, device=dev)
-                cnt = torch.zeros((rows,), dtype=torch.int32, device=dev)
-                if rows:
-                    clib.predict_device(h, q2 if q2 is not None else q, beam_size, post_processor, only_topk, idx.data_ptr(), sc.data_ptr(),
-                                        cnt.data_ptr(), k, stream=s.cuda_stream, sync=False)
-                res.append((idx, sc, cnt))
-            o_idx, o_sc, o_cnt = ensemble_device(res, mode=mode, threshold=thr, only_topk=topk, stream=s.cuda_stream, sync=False)
-            s.synchronize()
-            return rows_to_csr(o_idx.cpu().numpy().view(np.uint32), o_sc.cpu().numpy(), o_cnt.cpu().numpy(), models[0].nr_pred_cols)
-    finally:
-        torch.cuda.synchronize(dev)                # (also on an error: nothing may still read X when its handle goes)
-        clib.queries_free(q)
-        if q2 is not None:
-            clib.queries_free(q2)
+    with _text_queries(vectorizer, models[0], corpus, X_emb, normalize_emb, threads) as q:
+        try:
+            s = _ensemble_streams.get(dev.index)
+            if s is None:
+                s = _ensemble_streams[dev.index] = torch.cuda.Stream(device=dev)
+            mode, thr, topk = ("average", None, None) if finish is None else ("finish", finish[0], finish[1])
+            with torch.cuda.stream(s):
+                res = []
+                for h in hs:
+                    k = clib.effective_topk(h, only_topk)
+                    idx, sc, cnt = result_buffers(rows, k, dev)          # (filled on `s`, the stream of the predict)
+                    if rows:
+                        clib.predict_device(h, q, beam_size, post_processor, only_topk, idx.data_ptr(), sc.data_ptr(), cnt.data_ptr(), k,
+                                            stream=s.cuda_stream, sync=False)
+                    res.append((idx, sc, cnt))
+                o_idx, o_sc, o_cnt = ensemble_device(res, mode=mode, threshold=thr, only_topk=topk, stream=s.cuda_stream, sync=False)
+                s.synchronize()
+                return rows_to_csr(o_idx.cpu().numpy().view(np.uint32), o_sc.cpu().numpy(), o_cnt.cpu().numpy(), models[0].nr_pred_cols)
+        finally:
+            torch.cuda.synchronize(dev)            # (also on an error: nothing may still read X when its handle goes)
 
 
 def predict_text(vectorizer, models, corpus, X_emb=None, normalize_emb=True, threads=-1, ensemble="auto", finish=None, **kwargs):
@@ -403,20 +406,8 @@ def predict_text(vectorizer, models, corpus, X_emb=None, normalize_emb=True, thr
         raise ValueError(f"ensemble={ensemble!r}: expected 'auto', 'device' or 'host'")
     outs = []
     for m in models:
-        q = vectorizer.predict_device(m, corpus, threads=threads)
-        q2 = None
-        try:
-            if X_emb is not None:
-                import torch
-                assert X_emb.is_cuda and X_emb.dtype == torch.float32 and X_emb.shape[0] == len(corpus)
-                X_emb = X_emb.contiguous()
-                torch.cuda.current_stream().synchronize()
-                q2 = clib.queries_concat_handle(m.model.model_chain, q, X_emb.shape[1], X_emb.data_ptr(), normalize_emb=normalize_emb)
-            outs.append(_predict_handle_to_csr(m, q2 if q2 is not None else q, len(corpus), kwargs.get("beam_size"), kwargs.get("only_topk"), kwargs.get("post_processor")))
-        finally:
-            clib.queries_free(q)
-            if q2 is not None:
-                clib.queries_free(q2)
+        with _text_queries(vectorizer, m, corpus, X_emb, normalize_emb, threads) as q:
+            outs.append(_predict_handle_to_csr(m, q, len(corpus), kwargs.get("beam_size"), kwargs.get("only_topk"), kwargs.get("post_processor")))
     if finish is not None:
         return Text2Text.finish(outs, threshold=finish[0], only_topk=finish[1])
     if len(outs) == 1:

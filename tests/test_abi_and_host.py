@@ -39,6 +39,108 @@ def test_library_exports_every_declared_symbol():
     assert set(names) <= set(exported)
 
 
+def test_binding_table_matches_the_header():
+    # one table binds every declared function, with as many argument types as the declaration has parameters
+    from pecos_amd.core import corelib
+    src = open(os.path.join(REPO, "include", "xrl_abi.h")).read()
+    src = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+    names = _declared_symbols()
+    assert set(corelib.SIGNATURES) == set(names)
+    for n in names:
+        decl = re.findall(r"\b%s\s*\(([^()]*)\)\s*;" % n, src)
+        assert len(decl) == 1, f"{n}: {len(decl)} declarations found"
+        params = decl[0].strip()
+        want = 0 if params in ("", "void") else params.count(",") + 1
+        assert len(corelib.SIGNATURES[n][1]) == want, f"{n}: {len(corelib.SIGNATURES[n][1])} argument types bound, {want} parameters declared"
+
+
+class _RecordingClib:
+    """Stands in for pecos_amd.features.clib: hands out handles, records every call, frees through the binding's own `freeing`."""
+
+    def __init__(self):
+        self.calls, self.freed = [], []
+
+    def freeing(self, *handles):
+        from pecos_amd.core import corelib
+        return corelib.freeing(self, *handles)
+
+    def tfidf_predict_device(self, vec, c_model, corpus, threads):
+        self.calls.append("tfidf_predict_device")
+        return 101
+
+    def queries_concat_handle(self, c_model, q, dense_cols, emb_addr, normalize_emb=False, stream=None):
+        self.calls.append(("queries_concat_handle", q, dense_cols, emb_addr, normalize_emb))
+        return 202
+
+    def queries_free(self, h):
+        self.freed.append(h)
+
+    def predict_device(self, *a, **kw):
+        raise RuntimeError("predict failed")
+
+
+class _FakeEmb:
+    """What _text_queries asks of X_emb, without a device behind it."""
+    is_cuda, shape = True, (3, 5)
+
+    @property
+    def dtype(self):
+        import torch
+        return torch.float32
+
+    def contiguous(self):
+        return self
+
+    def data_ptr(self):
+        return 0x7000
+
+
+@pytest.mark.parametrize("with_emb", [False, True], ids=["handle_alone", "handle_and_concat"])
+@pytest.mark.parametrize("fails", [False, True], ids=["normal_exit", "exception"])
+def test_query_handles_are_freed_exactly_once(monkeypatch, with_emb, fails):
+    import types
+    from pecos_amd import features
+    fake = _RecordingClib()
+    monkeypatch.setattr(features, "clib", fake)
+    if with_emb:
+        import torch
+        monkeypatch.setattr(torch.cuda, "current_stream", lambda *a: types.SimpleNamespace(synchronize=lambda: None))
+    model = types.SimpleNamespace(model=types.SimpleNamespace(model_chain=7))
+    vec = features.Tfidf(model=None)
+    corpus = ["a", "b", "c"]
+
+    def run():
+        with features._text_queries(vec, model, corpus, _FakeEmb() if with_emb else None, True, 1) as q:
+            assert q == (202 if with_emb else 101)              # the handle to search: the concatenation when there is one
+            assert fake.freed == []
+            if fails:
+                fake.predict_device(7, q)
+    if fails:
+        with pytest.raises(RuntimeError, match="^predict failed$"):
+            run()
+    else:
+        run()
+    assert sorted(fake.freed) == ([101, 202] if with_emb else [101]) and None not in fake.freed
+    assert fake.calls == ["tfidf_predict_device"] + ([("queries_concat_handle", 101, 5, 0x7000, True)] if with_emb else [])
+    # the handle maker failing after the first handle exists: that one is still freed, once
+    if with_emb:
+        fake2 = _RecordingClib()
+        fake2.queries_concat_handle = lambda *a, **kw: (_ for _ in ()).throw(RuntimeError("concat failed"))
+        monkeypatch.setattr(features, "clib", fake2)
+        with pytest.raises(RuntimeError, match="^concat failed$"):
+            with features._text_queries(vec, model, corpus, _FakeEmb(), True, 1):
+                pass
+        assert fake2.freed == [101]
+    # clib.freeing itself: any number of handles, None skipped, also on an exception
+    fake3 = _RecordingClib()
+    with pytest.raises(KeyError):
+        with fake3.freeing(1, None, 2):
+            raise KeyError("x")
+    with fake3.freeing():
+        pass
+    assert fake3.freed == [1, 2]
+
+
 def test_binding_links_and_reports_no_gpu_loudly():
     from pecos_amd import XLinearModel, clib
     assert b"gfx950" in clib.clib_float32.xrl_version()

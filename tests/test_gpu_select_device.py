@@ -139,6 +139,40 @@ def test_parity_with_oracle_reference_and_host_route(name, loaded, clib):
         t = predict_selected_from_torch(L.m, crow, col, val, L.X.shape[1], torch.from_numpy(idx).cuda(), torch.from_numpy(cnt).cuda(), post_processor=pp)
         assert t[0].shape == (len(rows), 8) and t[0].dtype == torch.int32 and t[1].dtype == torch.float32
         assert_same_topk(to_csr(t, L.nr), L.m.predict(L.X, selected_outputs_csr=S, **kw), exact_scores=True, what=f"from_torch {name} {pp}")
+    if name == "s_eurlex":
+        _from_torch_with_embedding_block(L, clib)
+
+
+def _from_torch_with_embedding_block(L, clib):
+    """predict_selected_from_torch(emb=...): [X_feat | X_emb] assembled on the device, then K7 + K4.  The last H feature columns play the
+    embedding block (+ 0.25: no cell is zero), the labels are the model's own top 7; labels, order and score bits must be the host route's on
+    the same matrix -- concat_features' for normalize_emb=False, and for True the matrix the device assembled (read back), because the device
+    normalisation is only within 1e-6 of sklearn's."""
+    import torch
+    from pecos_amd.features import concat_features, predict_selected_from_torch
+    H, D = 24, L.X.shape[1]
+    X_feat = L.X[:, : D - H].tocsr(); X_feat.sort_indices()
+    emb = np.ascontiguousarray(L.X[:, D - H:].toarray()) + np.float32(0.25)
+    host_cat = concat_features(X_feat, emb, normalize_emb=False)
+    T = L.m.predict(host_cat, only_topk=7)
+    S = smat.csr_matrix((T.data, T.indices, T.indptr), shape=(T.shape[0], L.nr))
+    idx, cnt = sp.fixed_stride([S.indices[S.indptr[r]: S.indptr[r + 1]].astype(np.uint32) for r in range(S.shape[0])], 7, fill=0)
+    crow = torch.from_numpy(X_feat.indptr.astype(np.int64)).cuda()
+    col = torch.from_numpy(X_feat.indices.astype(np.int32)).cuda()
+    val = torch.from_numpy(X_feat.data.astype(np.float32)).cuda()
+    temb = torch.from_numpy(emb).cuda()
+    q = clib.queries_concat_device(L.h, X_feat.shape[0], D - H, crow.data_ptr(), col.data_ptr(), val.data_ptr(), int(X_feat.nnz), H, temb.data_ptr(),
+                                   normalize_emb=True)
+    try:
+        device_cat = clib.queries_download(q)
+    finally:
+        clib.queries_free(q)
+    assert device_cat.shape == host_cat.shape and np.array_equal(device_cat.indices, host_cat.indices)
+    for normalize, X_cat in ((False, host_cat), (True, device_cat)):
+        t = predict_selected_from_torch(L.m, crow, col, val, D - H, torch.from_numpy(idx).cuda(), torch.from_numpy(cnt).cuda(), emb=temb,
+                                        normalize_emb=normalize)
+        assert t[0].shape == (S.shape[0], 7)
+        assert_same_topk(to_csr(t, L.nr), L.m.predict(X_cat, selected_outputs_csr=S), exact_scores=True, what=f"from_torch emb normalize_emb={normalize}")
 
 
 # ------------------------------------------------------------------------------------------------------------------ 2. row shapes
