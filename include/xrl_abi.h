@@ -305,6 +305,36 @@ int xrl_predict_selected_device(void* model, void* queries, const char* post_pro
                                 uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride /* >= sel_stride */,
                                 uint32_t* d_status /* u32[2] {code, row}; may be NULL */, void* hip_stream, int sync);
 
+/* OUTPUT CONSTRAINT: XLinearModel.set_output_constraint (pecos/xmc/base.py:1796-1824) on a loaded handle.  The beam search of the handle is
+ * restricted to the given labels: a constrained predict returns, bit for bit (ids, order, scores, counts), what the same library -- or the
+ * reference -- returns for a model folder whose C matrices were pruned by the reference's rule (bottom-up: delete every entry of C whose row
+ * is not kept, keep for the layer above the columns that still hold an entry, stop at the first layer of which every node is kept), under
+ * the handle's weight_matrix_type, for sparse and dense X.  Nothing is rewritten or recompiled: per layer, a second (child range, child id)
+ * pair of arrays that lists the kept children in their stored order is built on the device (a few launches per layer), and every layer
+ * then runs the CONSTRAINED ROUTE -- offsets, one 16-lane inner product per (query, kept child) against the CSC copy of W in the arithmetic
+ * of the handle's layout, top-k -- whose grid shrinks with the kept set.  It is not the full-speed path: no bound pruning, no fused layers.
+ *   labels / d_labels   n label ids (u32) on the host / in HBM on the handle's device (read on hip_stream, NULL = the handle's stream); any
+ *                       order, duplicates allowed; a label the loaded tree does not contain is simply absent from the results
+ *   n == 0 is refused.  An id >= nr_pred_cols is refused: xrl_last_error names the lowest such index, and the constraint that was in force
+ *   stays in force.  A set that covers every label clears the constraint (the reference's rule stops at once).
+ * Honoured by every predict that goes through the beam search on this handle: c_xlinear_predict_{csr,drm}_f32, xrl_predict_device,
+ * xrl_predict_device_rows and the tf-idf forms.  NOT affected: the selected-outputs entry points (host and device), the single-layer API and
+ * sparse_inner_products.  Refused: mmap handles (no CSC weights), handles with option "devices" > 1 (and "devices" > 1 on a constrained
+ * handle), xrl_predict_stats on a constrained handle.
+ * Setting and clearing are synchronous: they wait for the whole DEVICE (hipDeviceSynchronize) -- every stream a predict of the handle may run
+ * on, the caller's included, and with them the work of every other handle of the process on that device -- and must not run
+ * concurrently with a predict on the same handle.  Profile names of the route: "k0_constrained", "k1p_constrained", "k2_constrained".
+ * xrl_output_constraint_info: out[0] = 1 if a constraint is in force, out[1 + l] = kept children of layer l (top-down; all of them for a layer
+ * above the rule's stop); returns 1 + depth, the number of values available.  The setters and the clear return 0 on success, -1 with a message otherwise.
+ * xrl_debug_output_constraint_view: FOR TESTS ONLY, NOT A STABLE INTERFACE (like the other xrl_debug_* entry points it may change or go
+ * without notice): the kept-child ranges (n_parents + 1 words) and kept child ids of one layer; returns 1, or 0 when the layer runs on its
+ * own arrays. */
+int xrl_set_output_constraint(void* model, const uint32_t* labels, uint64_t n);
+int xrl_set_output_constraint_device(void* model, const uint32_t* d_labels, uint64_t n, void* hip_stream);
+int xrl_clear_output_constraint(void* model);
+int xrl_output_constraint_info(void* model, uint64_t* out, uint32_t cap);
+int xrl_debug_output_constraint_view(void* model, uint32_t layer, uint32_t* chunk_col_out, uint64_t chunk_col_cap, uint32_t* perm_inv_out, uint64_t perm_inv_cap);
+
 /* Effective only_topk of the last layer for the given override (0 = model default). */
 uint32_t xrl_effective_topk(void* model, uint32_t only_topk);
 
@@ -313,7 +343,7 @@ uint32_t xrl_effective_topk(void* model, uint32_t only_topk);
  * xrl_profile_get synchronises, folds the pending pairs and fills up to `cap` records; it returns
  * the number of records available. */
 typedef struct {
-    char name[32];          /* kernel family: "k0_prolongate", "k1_sparse", "k1_dense", "k1q_dense", "k1q_dense_x", "k1c_csc", "k2_topk" */
+    char name[32];          /* kernel family: "k0_prolongate", "k1_sparse", "k1_dense", "k1q_dense", "k1q_dense_x", "k1c_csc", "k2_topk"; the constrained route: "k0_constrained", "k1p_constrained", "k2_constrained" */
     uint32_t layer;
     uint32_t launches;
     double ms;              /* accumulated GPU time of those launches */

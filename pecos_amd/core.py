@@ -236,6 +236,11 @@ class corelib(object):
         "xrl_ensemble_device": (c_int, [c_int, c_uint32, c_uint32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint32), c_int,
                                         POINTER(c_float), c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int]),
         "xrl_predict_selected_device": (c_int, [c_void_p, c_void_p, c_char_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_int]),
+        "xrl_set_output_constraint": (c_int, [c_void_p, c_void_p, c_uint64]),
+        "xrl_set_output_constraint_device": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p]),
+        "xrl_clear_output_constraint": (c_int, [c_void_p]),
+        "xrl_output_constraint_info": (c_int, [c_void_p, POINTER(c_uint64), c_uint32]),
+        "xrl_debug_output_constraint_view": (c_int, [c_void_p, c_uint32, c_void_p, c_uint64, c_void_p, c_uint64]),
         "xrl_predict_stats": (c_int, [c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, POINTER(c_double), c_uint32]),
         "xrl_effective_topk": (c_uint32, [c_void_p, c_uint32]),
         "xrl_profile_enable": (None, [c_void_p, c_int]),
@@ -619,6 +624,42 @@ class corelib(object):
             c_void_p(d_out_idx), c_void_p(d_out_val), c_void_p(d_out_cnt), int(out_stride), c_void_p(stream or 0), 1 if sync else 0)
         self._check()
         return rc
+
+    # ------------------------------------------------------------------ output constraint (xmc/base.py:1796-1824, on the device)
+    def set_output_constraint(self, c_model, labels):
+        """Restrict the handle's beam search to ``labels`` (a contiguous uint32 numpy array on the host); a set that covers every label clears."""
+        labels = np.ascontiguousarray(labels, dtype=np.uint32)
+        rc = self.clib_float32.xrl_set_output_constraint(c_void_p(c_model), c_void_p(labels.ctypes.data), int(labels.size))
+        self._check()
+        return rc
+
+    def set_output_constraint_device(self, c_model, d_labels, n, stream=None):
+        """... from ``n`` uint32 label ids in HBM on the handle's device (raw address), read on ``stream`` (None: the handle's)."""
+        rc = self.clib_float32.xrl_set_output_constraint_device(c_void_p(c_model), c_void_p(d_labels), int(n), c_void_p(stream or 0))
+        self._check()
+        return rc
+
+    def clear_output_constraint(self, c_model):
+        rc = self.clib_float32.xrl_clear_output_constraint(c_void_p(c_model))
+        self._check()
+        return rc
+
+    def output_constraint_info(self, c_model):
+        """(active, [kept children of every layer, top-down])."""
+        depth = self.xlinear_get_int_attr(c_model, "depth")
+        out = (c_uint64 * (1 + depth))()
+        self.clib_float32.xrl_output_constraint_info(c_void_p(c_model), out, 1 + depth)
+        self._check()
+        return bool(out[0]), [int(out[1 + l]) for l in range(depth)]
+
+    def debug_output_constraint_view(self, c_model, layer, n_parents, kept):
+        """Tests: (chunk_col', perm_inv') of one layer's constrained view, or None when the layer runs on its own arrays."""
+        cc = np.zeros(n_parents + 1, dtype=np.uint32)
+        pi = np.zeros(max(1, kept), dtype=np.uint32)
+        rc = self.clib_float32.xrl_debug_output_constraint_view(c_void_p(c_model), int(layer), c_void_p(cc.ctypes.data), cc.size,
+                                                                c_void_p(pi.ctypes.data), int(kept))
+        self._check()
+        return (cc, pi[:kept]) if rc == 1 else None
 
     def effective_topk(self, c_model, only_topk):
         return int(self.clib_float32.xrl_effective_topk(c_void_p(c_model), only_topk or 0))

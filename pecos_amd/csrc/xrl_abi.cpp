@@ -401,6 +401,7 @@ int xrl_predict_stats(void* model, void* queries, uint32_t beam_size, const char
         if (!queries || !stats_out) fail("xrl_predict_stats: null argument");
         if (stats_cap < kStatsPerLayer * m.layers.size()) fail("xrl_predict_stats: stats_out too small (need 8*depth doubles)");
         std::lock_guard<std::mutex> g(m.mu);
+        if (m.constrained) fail("xrl_predict_stats: not available while an output constraint is set (the constrained route runs none of the counted kernels)");
         use_device(m.device);
         if (!m.ws) m.ws = std::make_unique<Workspace>();
         const QueriesDev& X = static_cast<Queries*>(queries)->dev;
@@ -412,6 +413,65 @@ int xrl_predict_stats(void* model, void* queries, uint32_t beam_size, const char
         predict_device(m, X, o, ws.out_idx.as<uint32_t>(), ws.out_val.as<float>(), ws.out_cnt.as<uint32_t>(), k, m.stream, true);
         m.profiling = was;
         return 0;
+    });
+}
+
+// xrl_set_output_constraint and xrl_set_output_constraint_device
+static int set_constraint_entry(const char* what, void* model, const uint32_t* labels, uint64_t n, bool on_device, void* hip_stream) {
+    return guarded_value(-1, [&] {
+        Model& m = *as_model(model);
+        std::lock_guard<std::mutex> g(m.mu);
+        use_device(m.device);
+        set_output_constraint(m, labels, n, on_device, static_cast<hipStream_t>(hip_stream), what);
+        return 0;
+    });
+}
+
+int xrl_set_output_constraint(void* model, const uint32_t* labels, uint64_t n) {
+    return set_constraint_entry("xrl_set_output_constraint", model, labels, n, false, nullptr);
+}
+
+int xrl_set_output_constraint_device(void* model, const uint32_t* d_labels, uint64_t n, void* hip_stream) {
+    return set_constraint_entry("xrl_set_output_constraint_device", model, d_labels, n, true, hip_stream);
+}
+
+int xrl_clear_output_constraint(void* model) {
+    return guarded_value(-1, [&] {
+        Model& m = *as_model(model);
+        std::lock_guard<std::mutex> g(m.mu);
+        use_device(m.device);
+        clear_output_constraint(m);
+        return 0;
+    });
+}
+
+int xrl_output_constraint_info(void* model, uint64_t* out, uint32_t cap) {
+    return guarded_value(-1, [&] {
+        Model& m = *as_model(model);
+        std::lock_guard<std::mutex> g(m.mu);
+        const uint32_t n = 1u + (uint32_t)m.layers.size();
+        for (uint32_t i = 0; i < n && i < cap && out; ++i) {
+            if (i == 0) { out[0] = m.constrained ? 1 : 0; continue; }
+            const Layer& L = *m.layers[i - 1];
+            out[i] = L.view.active ? L.view.kept : L.n_children;
+        }
+        return (int)n;
+    });
+}
+
+int xrl_debug_output_constraint_view(void* model, uint32_t layer, uint32_t* chunk_col_out, uint64_t chunk_col_cap, uint32_t* perm_inv_out, uint64_t perm_inv_cap) {
+    return guarded_value(-1, [&] {
+        Model& m = *as_model(model);
+        if (layer >= m.layers.size()) fail("xrl_debug_output_constraint_view: layer out of range");
+        std::lock_guard<std::mutex> g(m.mu);
+        const Layer& L = *m.layers[layer];
+        if (!L.view.active) return 0;
+        use_device(m.device);
+        XRL_HIP(hipDeviceSynchronize());
+        const uint64_t n_cc = std::min<uint64_t>(chunk_col_cap, (uint64_t)L.dev.n_parents + 1), n_pi = std::min<uint64_t>(perm_inv_cap, L.view.kept);
+        if (chunk_col_out && n_cc) XRL_HIP(hipMemcpy(chunk_col_out, L.view.d_chunk_col.p, n_cc * 4, hipMemcpyDeviceToHost));
+        if (perm_inv_out && n_pi) XRL_HIP(hipMemcpy(perm_inv_out, L.view.d_perm_inv.p, n_pi * 4, hipMemcpyDeviceToHost));
+        return 1;
     });
 }
 
@@ -493,6 +553,7 @@ int xrl_set_option(void* model, const char* key, int64_t value) {
             if (value < 1 || value > 64) fail("devices: expected 1..64");
             if (m.src_kind < 0 && value > 1) fail("devices: only models loaded from a folder can be replicated");
             std::lock_guard<std::mutex> g(m.mu);
+            if (m.constrained && value > 1) fail("devices: the handle carries an output constraint, which replicas do not share (xrl_clear_output_constraint first)");
             int ndev = 0;
             XRL_HIP(hipGetDeviceCount(&ndev));
             m.replicas.clear();

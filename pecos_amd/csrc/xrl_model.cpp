@@ -48,6 +48,12 @@ uint64_t Layer::cand_bound(uint32_t beam) const {
     return s;
 }
 
+uint64_t ConstraintView::cand_bound(uint32_t beam) const {
+    uint64_t s = 0;
+    for (uint32_t i = 0; i < beam && i < chunk_sizes_desc.size(); ++i) s += chunk_sizes_desc[i];
+    return s;
+}
+
 Model::Model() {}
 Model::~Model() {
     replicas.clear();                       // each replica releases its objects with ITS device current
@@ -143,7 +149,8 @@ uint64_t layout_tile_rows(const uint32_t* rptr, uint32_t nrows, bool align, uint
 uint64_t Layer::buffer_bytes() const {
     uint64_t b = 0;
     for (const DevBuf* d : {&d_csc_ptr, &d_csc_idx, &d_csc_val, &d_tiles, &d_ptile, &d_chunk_col, &d_bitmap, &d_row_ptr, &d_row_idx, &d_entries, &d_perm_inv,
-                            &d_chunk_alg, &d_bias_prod, &d_bucket, &d_bitmap64, &d_wd, &d_dptile, &d_dtcol, &d_tile_parent, &d_pres, &d_wt, &d_wt_base, &d_sel_parent, &d_sel_crank})
+                            &d_chunk_alg, &d_bias_prod, &d_bucket, &d_bitmap64, &d_wd, &d_dptile, &d_dtcol, &d_tile_parent, &d_pres, &d_wt, &d_wt_base, &d_sel_parent, &d_sel_crank,
+                            &view.d_chunk_col, &view.d_perm_inv})
         b += d->cap;
     return b;
 }

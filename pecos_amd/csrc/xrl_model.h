@@ -105,6 +105,17 @@ struct LayerDev {
                                  // -- K1Q's prolongation then needs neither d_ptile nor d_tcol (two dependent loads per candidate register); balanced trees are like this
 };
 
+// Output constraint (xrl_constrain.hip): the children of a layer that lead to a kept label, as a second (chunk_col, perm_inv) pair -- the
+// only two arrays through which K0, K2 and the pair kernels map a candidate position to a child.  Kept children stay in their stored order.
+struct ConstraintView {
+    bool active = false;                     // false: the layer runs on its own arrays (no constraint, or above the reference rule's early stop)
+    DevBuf d_chunk_col, d_perm_inv;          // [n_parents + 1] kept-child range of every parent; [kept] original child ids (never null while active)
+    std::vector<uint32_t> chunk_sizes_desc;  // kept chunk sizes, descending (the view's own candidate bound)
+    uint64_t kept = 0;                       // kept children of the layer
+    uint64_t cand_bound(uint32_t beam) const;
+    void clear() { active = false; d_chunk_col.release(); d_perm_inv.release(); chunk_sizes_desc.clear(); kept = 0; }
+};
+
 struct Layer {
     // host metadata
     uint32_t w_rows = 0, w_cols = 0, c_rows = 0, c_cols = 0;
@@ -133,11 +144,14 @@ struct Layer {
     DevBuf d_wt, d_wt_base;                                   // tile rows held densely (see LayerDev::wt)
     uint64_t dense_bytes = 0;
     uint32_t bk_shift = 0, bk_n = 0, bk_levels = 0;
+    ConstraintView view;                                      // output constraint of the handle, if any (Model::constrained)
     LayerDev dev{};
     uint64_t device_bytes = 0;             // buffer_bytes() as of the last build step (+ Model::d_wd01 on the root layer)
     uint64_t buffer_bytes() const;         // capacity of every DevBuf above
     // sum of the `beam` largest chunks: upper bound on candidates per query entering this layer
     uint64_t cand_bound(uint32_t beam) const;
+    // ... the same through the output constraint's view when the layer carries one (what resolve_layers sizes the candidate rows with)
+    uint64_t cand_bound_kept(uint32_t beam) const { return view.active ? view.cand_bound(beam) : cand_bound(beam); }
 };
 
 struct ProfileSlot { std::string name; uint32_t layer; uint32_t launches = 0; double ms = 0; };
@@ -185,6 +199,7 @@ struct Model {
     struct HostLanes { hipEvent_t done[2] = {nullptr, nullptr}; hipStream_t strm[2] = {nullptr, nullptr}; hipEvent_t join = nullptr; } host_lanes;
     std::mutex mu;                          // one predict at a time per handle
     std::unique_ptr<Workspace> ws;
+    bool constrained = false;               // xrl_set_output_constraint is in force: every layer runs ROUTE_CONSTRAINED (xrl_predict.cpp) over Layer::view
     bool csc_route = false;                 // weight_matrix_type == CSC: every layer runs the reference's CSC arithmetic (K0 -> K1C -> K2)
     DevBuf d_wd01;                          // levels 0 + 1 merged dense rows (LayerDev::wd01 of the root layer)
     DevBuf d_sel_tree; bool sel_tree_ready = false;   // K7: one SelectTreeLayer per layer (ensure_device_tree; counted on the root layer like d_wd01)
@@ -252,6 +267,10 @@ void finalize_model(Model& m);
 std::unique_ptr<Model> load_mmap_model_from_disk(const std::string& path);        // xrl_mmap.cpp
 void compile_mmap_model(const std::string& npz_path, const std::string& mmap_path);   // xrl_mmap.cpp
 void ensure_device_csc(Layer& L);   // upload W as CSC (original column ids) if not there yet
+// xrl_constrain.hip: restrict the beam search to `labels` (n ids, on the host or -- on_device -- in HBM, read on stream s), the reference's
+// set_output_constraint rule as per-layer views; a set that covers every label clears.  Synchronous.  what: the entry point's name for messages.
+void set_output_constraint(Model& m, const uint32_t* labels, uint64_t n, bool on_device, hipStream_t s, const char* what);
+void clear_output_constraint(Model& m);
 void ensure_device_tree(Model& m);  // K7's tree arrays (Layer::d_sel_parent / d_sel_crank, Model::d_sel_tree) if not there yet; refuses a C that is no tree
 void k1t_shape(uint32_t max_tile_cols, int& g, int& nr);   // lanes per item / columns per lane of K1T for a layer's widest tile
 void launch_tile_rows(const LayerDev& L, uint64_t total_floats, uint32_t* wt, hipStream_t s);   // fills LayerDev::wt from the tile format on the device (xrl_k1t.hip)

@@ -61,6 +61,28 @@ __device__ __forceinline__ float dot_sparse_sparse(const uint32_t* __restrict__ 
     return dot;
 }
 
+// The same walk CONTINUING a running value: acc = fl32(acc + fl32(x_f * w_f)) over the matching indices in ascending order -- the chunked
+// route's single chain (chunk_ops<csr, *>, inference.hpp:705-735, 769-813), where the products join the sum the bias may already be part of
+__device__ __forceinline__ float chain_sparse_sparse(float acc, const uint32_t* __restrict__ xi, const float* __restrict__ xv, uint32_t xn,
+                                                     const uint32_t* __restrict__ wi, const float* __restrict__ wv, uint32_t wn,
+                                                     int lig, int gbase) {
+    const bool sx = xn <= wn;
+    const uint32_t* __restrict__ ai = sx ? xi : wi; const float* __restrict__ av = sx ? xv : wv; const uint32_t an = sx ? xn : wn;
+    const uint32_t* __restrict__ bi = sx ? wi : xi; const float* __restrict__ bv = sx ? wv : xv; const uint32_t bn = sx ? wn : xn;
+    for (uint32_t c0 = 0; c0 < an; c0 += PG) {
+        const uint32_t t = c0 + (uint32_t)lig;
+        const bool ok = t < an;
+        const uint32_t key = ai[ok ? t : 0u];
+        const float a = av[ok ? t : 0u];
+        const uint32_t pos = ok && bn ? lower_bound_u32(bi, bn, key) : bn;
+        const bool hit = pos < bn && bi[pos] == key;
+        const float prod = hit ? __fmul_rn(a, bv[pos]) : 0.0f;
+        const uint32_t gm = (uint32_t)(__ballot(hit) >> gbase) & 0xFFFFu;
+        if (gm) acc = fold_in_lane_order(acc, prod, gm, gbase);
+    }
+    return acc;
+}
+
 // res = fl32(res + fl32(x[idx_s] * w_s)) over s in [0, n) in order: do_dot_product(dense, sparse) / the dense-X bias-first loop
 __device__ __forceinline__ float chain_dense_x(float res, const float* __restrict__ x, uint32_t x_cols, const uint32_t* __restrict__ wi,
                                                const float* __restrict__ wv, uint32_t n, int lig, int gbase) {
@@ -93,6 +115,25 @@ __device__ __forceinline__ float csc_route_product(const CscDev& W, const Querie
     const uint64_t xb = X.row_ptr[q];
     const uint32_t xn = (uint32_t)(X.row_ptr[q + 1] - xb);
     return __fadd_rn(res, dot_sparse_sparse(X.col_idx + xb, X.val + xb, xn, wi, wv, wn, lig, gbase));
+}
+
+// The CHUNKED routes' arithmetic for column j against query row q, from the CSC copy of W (oracle/xrl_oracle.c
+// orc_layer_predict).  Sparse X: one chain from +0.0 over the matching features in ascending order, the bias product -- only for a column
+// that holds a bias entry -- LAST (BINARY_SEARCH_CHUNKED) or FIRST (HASH_CHUNKED, bias_first).  Dense X is bias first, then every entry of
+// the column in order, in every layout: csc_route_product's dense branch.
+__device__ __forceinline__ float chunked_route_product(const CscDev& W, const QueriesDev& X, uint64_t q, uint32_t j, int bias_first, int lig, int gbase) {
+    if (X.dense) return csc_route_product(W, X, q, j, lig, gbase);
+    const uint64_t cb = W.col_ptr[j], ce = W.col_ptr[j + 1];
+    const uint32_t wn = (uint32_t)(ce - cb);
+    const uint32_t* __restrict__ wi = W.row_idx + cb; const float* __restrict__ wv = W.val + cb;
+    const bool has_b = W.bias > 0.0f && wn > 0 && wi[wn - 1] == W.w_rows - 1;
+    const float bprod = has_b ? __fmul_rn(W.bias, wv[wn - 1]) : 0.0f;
+    float acc = 0.0f;
+    if (has_b && bias_first) acc = __fadd_rn(acc, bprod);
+    const uint64_t xb = X.row_ptr[q];
+    acc = chain_sparse_sparse(acc, X.col_idx + xb, X.val + xb, (uint32_t)(X.row_ptr[q + 1] - xb), wi, wv, has_b ? wn - 1 : wn, lig, gbase);
+    if (has_b && !bias_first) acc = __fadd_rn(acc, bprod);
+    return acc;
 }
 
 }  // namespace xrl

@@ -6,8 +6,10 @@
 //
 // predict_device is an outline: resolve_layers (k / beam / candidate stride per layer) -> PruneFeedback::begin_predict -> reserve_scratch
 // (walks the routes once) -> per row batch and layer: route_layer DECIDES (a Route, nothing launched), one of launch_csc_layer /
-// launch_k1g_layer / launch_k1q_group / launch_tile_layer LAUNCHES what it says (launch_batch).  A new way to run a layer is a Route field + a branch there.
+// launch_k1g_layer / launch_k1q_group / launch_tile_layer / launch_constrained_layer LAUNCHES what it says (launch_batch).  A new way to run a layer is a
+// Route field + a branch there.
 #include "xrl_predict.h"
+#include "xrl_constrain.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -34,7 +36,7 @@ uint32_t k1g_first_slots(const Layer& L, uint32_t beam_in, int forced = 0) {
 struct LayerShape { uint32_t k, beam_in, cand_stride; PostProc pp; };   // resolve_layers: what a layer keeps, takes in and may evaluate per query
 
 // Every decision about how layers [l, last] run on a batch of a given size (route_layer); the launch functions read it and decide nothing.
-enum RouteKind { ROUTE_CSC, ROUTE_K1G, ROUTE_K1Q, ROUTE_TILE };
+enum RouteKind { ROUTE_CSC, ROUTE_K1G, ROUTE_K1Q, ROUTE_TILE, ROUTE_CONSTRAINED };
 struct Route {
     RouteKind kind;
     size_t last;             // K1Q: last layer of the group that shares the launch (every other kind: the layer itself) ...
@@ -136,7 +138,7 @@ std::vector<LayerShape> resolve_layers(const Model& m, const QueriesDev& X, cons
         uint64_t bin = (l == 0) ? (has_init ? std::max<uint32_t>(1, o.initial_max) : 1) : std::min<uint64_t>(shape[l - 1].k, shape[l - 1].cand_stride);
         if (!(l == 0 && has_init)) bin = std::min<uint64_t>(bin, L.c_cols ? L.c_cols : 1);   // explicit codes may list a parent more than once
         s.beam_in = (uint32_t)std::max<uint64_t>(1, bin);
-        const uint64_t cb = std::max<uint64_t>(1, (l == 0 && has_init && o.initial_cand_bound) ? o.initial_cand_bound : L.cand_bound(s.beam_in));
+        const uint64_t cb = std::max<uint64_t>(1, (l == 0 && has_init && o.initial_cand_bound) ? o.initial_cand_bound : L.cand_bound_kept(s.beam_in));
         if (cb > 0x7FFFFFFFull) fail("candidate row too long; lower beam_size");
         s.cand_stride = (uint32_t)cb;
     }
@@ -171,7 +173,11 @@ int tile_mode(const Batch& b, size_t l, uint64_t rows) {
 Route route_layer(const Batch& b, size_t l, uint64_t nrows) {
     const Model& m = b.m; const Model::Options& opt = b.opt; const Layer& L = *m.layers[l];
     const uint32_t beam_in = b.shape[l].beam_in;
-    Route r{}; r.last = l; r.J = 1; r.mode = tile_mode(b, l, nrows);
+    Route r{}; r.last = l; r.J = 1;
+    // a handle under an output constraint (xrl_set_output_constraint): every layer scores the kept candidates of its view one pair at a time
+    // (offsets -> K1P -> K2), whatever the layout -- no bound pruning, no feedback sampling, no sorted launch, no scratch beyond the candidate rows
+    if (m.constrained) { r.kind = ROUTE_CONSTRAINED; return r; }
+    r.mode = tile_mode(b, l, nrows);
     // the second phase of a bound-pruned tile-format layer runs on TILE-SORTED items (option sort_rest): what is left after the first phase
     // is, on a model that does not let the bound stop much, most of the layer's work, and in query order every (query, tile) item finds its
     // tile's lookup words and entries cold (Amazon-670K-hard: 7 % L2 hits, the fabric's request ceiling); tile-sorted, the items of a tile
@@ -281,6 +287,19 @@ void launch_csc_layer(Batch& b, size_t l) {
     b.timed("k0_prolongate", l, [&] { launch_k0_prolongate(L.dev, P, b.X, prev, b.cand_off, b.ncand, b.items, b.S); });
     b.timed("k1c_csc", l, [&] { launch_k1c_csc(L.dev, L.d_csc_ptr.as<uint64_t>(), L.d_csc_idx.as<uint32_t>(), L.d_csc_val.as<float>(), P, b.X, prev, b.cand_off, b.ncand, b.cand, b.S); });
     b.timed("k2_topk", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, b.beam_out(l), b.S); });
+}
+
+// the constrained route: K0 and K2 as they are, on a copy of the layer's view of itself whose chunk_col / perm_inv are the constraint's (layers above
+// the rule's early stop keep their own); K0 writes offsets and counts only (no item descriptors: item_ranks = 0); K1P scores with the handle's arithmetic
+void launch_constrained_layer(Batch& b, size_t l) {
+    Layer& L = *b.m.layers[l]; LayerPlan P = b.make_plan(l); const BeamDev prev = b.beam_prev(l);
+    P.fb_host = nullptr; P.fb_dev = nullptr; P.prune = 0;   // (the CSC copy of W is there: the setter uploads it before it sets Model::constrained)
+    LayerDev V = L.dev;
+    if (L.view.active) { V.chunk_col = L.view.d_chunk_col.as<uint32_t>(); V.perm_inv = L.view.d_perm_inv.as<uint32_t>(); }
+    const int chain = (b.csc || b.X.dense) ? kChainCsc : kChainChunked;
+    b.timed("k0_constrained", l, [&] { launch_k0_prolongate(V, P, b.X, prev, b.cand_off, b.ncand, b.items, b.S, 0); });
+    b.timed("k1p_constrained", l, [&] { launch_k1p_constrained(V, L.d_csc_ptr.as<uint64_t>(), L.d_csc_idx.as<uint32_t>(), L.d_csc_val.as<float>(), P, chain, b.X, prev, b.cand_off, b.ncand, b.cand, b.S); });
+    b.timed("k2_constrained", l, [&] { launch_k2_topk(V, P, prev, b.cand_off, b.ncand, b.cand, b.beam_out(l), b.S); });
 }
 
 // K0 -> sort -> K1G -> K2 over the first r.J beam slots (unpruned: all of them, and that is the layer); pruned: the same over the remaining
@@ -402,6 +421,7 @@ void launch_batch(Batch& b) {   // every layer of the row batch in flight
             case ROUTE_K1G: launch_k1g_layer(b, l, r); break;
             case ROUTE_K1Q: launch_k1q_group(b, l, r); break;
             case ROUTE_TILE: launch_tile_layer(b, l, r); break;
+            case ROUTE_CONSTRAINED: launch_constrained_layer(b, l); break;
         }
         l = r.last;
     }
@@ -476,7 +496,7 @@ void predict_device(Model& m, const QueriesDev& X, const PredictOpts& o, uint32_
     }
     if (!(b.prune_wmax <= 3.0e38f)) b.prune_wmax = INFINITY;
     size_batches(b, n_rows);
-    if (m.opt.prune && m.opt.adaptive) b.fb = m.fb.begin_predict(T, !b.stats);
+    if (m.opt.prune && m.opt.adaptive && !m.constrained) b.fb = m.fb.begin_predict(T, !b.stats);
     reserve_scratch(b, *m.ws, n_rows);
     if (b.stats) { b.stats_dev = m.ws->stats.as<double>(); XRL_HIP(hipMemsetAsync(m.ws->stats.p, 0, T * kStatsPerLayer * sizeof(double), stream)); }
 

@@ -450,7 +450,8 @@ class Text2Text:
     """The PREDICT half of ``pecos.apps.text2text.model.Text2Text`` (model.py:136-190 load, :389-427 predict) over the device-resident
     pipeline: ``load`` the folder its ``save`` wrote (``preprocessor/``, ``xlinear_ensemble/{config.json, 0, 1, ...}``, ``output_items.json``),
     ``predict`` a list of strings -- texts -> term counts (host threads) -> X in HBM -> beam search in place, per model; ensemble average,
-    threshold and the final ``sorted_csr(only_topk)`` as the reference does them.  Training, saving and ``set_output_constraint`` stay the
+    threshold and the final ``sorted_csr(only_topk)`` as the reference does them.  ``set_output_constraint`` restricts every model of the
+    ensemble to a set of output items, on the loaded handles (the constrained route of the beam search).  Training and saving stay the
     reference's."""
 
     def __init__(self, preprocessor, xlinear_models, output_items):
@@ -492,6 +493,18 @@ class Text2Text:
         # (an ensemble: one tokenisation and upload, the merge, threshold and cut on the device where predict_text finds that possible)
         return predict_text(self.preprocessor, [m for m, _ in self.xlinear_models], corpus, threads=threads,
                             finish=(threshold, kwargs.get("only_topk", None)), **kwargs)
+
+    def set_output_constraint(self, output_items_to_keep):
+        """Restrict predict() to the given output items (model.py:430-444): strings that are no output item are ignored, every model of
+        the ensemble gets the set.  ``None`` clears the constraint."""
+        if output_items_to_keep is None:
+            for model, _ in self.xlinear_models:
+                model.set_output_constraint(None)
+            return
+        index = {item: i for i, item in enumerate(self.output_items)}      # (an item listed twice answers to its last position)
+        keep = {index[item] for item in output_items_to_keep if item in index}
+        for model, _ in self.xlinear_models:
+            model.set_output_constraint(keep)
 
     def get_output_item(self, output_id):
         return self.output_items[output_id]

@@ -164,6 +164,38 @@ class HierarchicalMLModel:
     def get_pred_params(self):
         return copy.deepcopy(self.pred_params)
 
+    def set_output_constraint(self, labels_to_keep):
+        """Restrict predict() to the labels in ``labels_to_keep`` (xmc/base.py:1796-1824) -- here on the loaded, predict-only handle: the
+        result equals a model whose C matrices were pruned by the reference's rule, saved and reloaded.  Any iterable of ints; a torch
+        integer tensor on the model's device is read where it is (no host copy); ``None`` clears the constraint, and so does a set
+        that covers every label.  Synchronous; not to be called while a predict of this model is running."""
+        if labels_to_keep is None:
+            clib.clear_output_constraint(self.model_chain)
+            return
+        if type(labels_to_keep).__module__.split(".")[0] == "torch" and hasattr(labels_to_keep, "data_ptr"):
+            import torch
+            t = labels_to_keep
+            if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+                raise TypeError("can not convert labels_to_keep as set variable type!")
+            if t.is_cuda and t.device.index == clib.xlinear_get_int_attr(self.model_chain, "device"):
+                t = t.reshape(-1)
+                if t.numel() and (int(t.min()) < 0 or int(t.max()) > 0xFFFFFFFF):
+                    raise ValueError("labels_to_keep holds an id outside [0, 2^32)")
+                # (the ids travel as 32-bit words: a reinterpreting view of an int32 tensor, a converted copy -- on the device -- of any other)
+                t32 = t.contiguous() if t.dtype == torch.int32 else t.to(torch.int64).bitwise_and(0xFFFFFFFF).to(torch.int32).contiguous()
+                stream = torch.cuda.current_stream(t.device).cuda_stream
+                clib.set_output_constraint_device(self.model_chain, t32.data_ptr(), t32.numel(), stream=stream)
+                return
+            labels_to_keep = t.detach().cpu().reshape(-1).tolist()
+        try:
+            labels_to_keep = set(labels_to_keep)
+        except TypeError:
+            raise TypeError("can not convert labels_to_keep as set variable type!")
+        ids = np.fromiter((int(v) for v in labels_to_keep), dtype=np.int64, count=len(labels_to_keep))
+        if ids.size and (ids.min() < 0 or ids.max() > 0xFFFFFFFF):
+            raise ValueError("labels_to_keep holds an id outside [0, 2^32)")
+        clib.set_output_constraint(self.model_chain, ids.astype(np.uint32))
+
     @classmethod
     def load(cls, model_folder, is_predict_only=True, **kwargs):
         param = json.loads(open(f"{model_folder}/param.json", "r", encoding="utf-8").read())
@@ -366,6 +398,11 @@ class XLinearModel:
 
     def get_pred_params(self):
         return self.PredParams(hlm_args=self.model.get_pred_params())
+
+    def set_output_constraint(self, labels_to_keep):
+        """Prune the tree to the labels in ``labels_to_keep`` (pecos/xmc/xlinear/model.py:285-293); works on the predict-only model,
+        ``None`` clears (HierarchicalMLModel.set_output_constraint)."""
+        self.model.set_output_constraint(labels_to_keep)
 
     def predict(self, X, pred_params=None, selected_outputs_csr=None, **kwargs):
         if (pred_params is not None) and (not isinstance(pred_params, self.PredParams)):
