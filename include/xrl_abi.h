@@ -393,6 +393,11 @@ uint32_t xrl_debug_host_batches(const uint64_t* row_ptr, uint32_t rows, uint32_t
  *                         parent is one tile (<= 128 children) and k <= 20 -- the kernel derives its item from the beam (beams of up to 32 parents; no
  *                         k0_prolongate launch), ranks the candidates in its epilogue and sets the done flags (no k2_topk launch); 2: ... but the
  *                         items still come from a k0_prolongate launch; 0: three launches (K0 -> K1 -> K2)
+ *   "leaf_tail"           1 (default): bound-pruned tile-format layers of TWO stages (beams of fewer than 16 parents, or prune_mid = 0): the first stage also
+ *                         lists the queries it left unfinished, and the later stage's launches walk that list -- k0b_remaining and k2_topk_rest on a small
+ *                         fixed grid, K1 on a fixed grid of 6144 workgroups once the pruning feedback's last item count is known and at most an eighth of
+ *                         a worst-case grid of >= 2^21 item slots; n >= 2: ... and K1 always on a fixed grid of n workgroups (A/B runs, tests);
+ *                         0: launches sized for the whole batch.  Results never depend on it.
  *   "sort_rest"           1 (default): the second phase of a bound-pruned tile-format layer runs on tile-sorted items (counting sort of the
  *                         compacted list by tile: the items of a tile run back to back on one XCD and share its lookup words and entries in
  *                         that XCD's L2); 0: in query order

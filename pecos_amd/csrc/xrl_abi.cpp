@@ -517,7 +517,7 @@ uint32_t xrl_debug_host_batches(const uint64_t* row_ptr, uint32_t rows, uint32_t
 // every integer option that is a plain store into Model::Options, under the member's own name (include/xrl_abi.h documents the keys)
 #define XRL_OPT(name) {#name, &Model::Options::name}
 static const struct { const char* name; int Model::Options::*field; } kIntOptions[] = {
-    XRL_OPT(k1_group), XRL_OPT(sort_min_tiles), XRL_OPT(sort_rest), XRL_OPT(sort_rest_min), XRL_OPT(prune_mid), XRL_OPT(leaf_fuse), XRL_OPT(tile_rows),
+    XRL_OPT(k1_group), XRL_OPT(sort_min_tiles), XRL_OPT(sort_rest), XRL_OPT(sort_rest_min), XRL_OPT(prune_mid), XRL_OPT(leaf_fuse), XRL_OPT(leaf_tail), XRL_OPT(tile_rows),
     XRL_OPT(k2_big_min_k), XRL_OPT(qsort), XRL_OPT(qsort_min_parents), XRL_OPT(qsort_min_rows), XRL_OPT(presence), XRL_OPT(adaptive), XRL_OPT(prune),
     XRL_OPT(host_pipeline), XRL_OPT(host_batch_mb), XRL_OPT(host_register), XRL_OPT(overlap_min_rows),
     XRL_OPT(dense_layers), XRL_OPT(k1q_fuse), XRL_OPT(k1g_first), XRL_OPT(k1g_min_items), XRL_OPT(k1g_variant),

@@ -92,9 +92,63 @@ k0b_remaining(const uint32_t* __restrict__ chunk_col, const uint32_t* __restrict
     }
 }
 
+// The same from the LIST of unfinished queries the first stage wrote (rest_q[0 .. *rest_cnt), any order): a small fixed grid, each wavefront takes
+// GROUPS of 64 / lpq listed queries (wavefront-stride loop over the device-side count), lpq = min(slots per query, 64) lanes per query, a lane on the
+// beam slots first_rank + its position, + lpq, ...; one prefix sum over the lanes' tile counts and ONE atomicAdd on n_items per group -- the
+// returning atomics on that one word are what the batch-sized kernel spends its time on (one per wavefront that holds an unfinished query).
+// The work is in proportion to the list, not to the batch.
+__global__ void __launch_bounds__(256)
+k0b_remaining_list(const uint32_t* __restrict__ chunk_col, const uint32_t* __restrict__ ptile, const TileDesc* __restrict__ tiles,
+                   uint32_t nrows, uint32_t beam_in, uint32_t first_rank, uint32_t end_rank, uint32_t cand_stride, const uint32_t* __restrict__ p_idx,
+                   const float* __restrict__ p_val, const uint32_t* __restrict__ p_cnt, uint32_t p_stride, const uint32_t* __restrict__ cand_off,
+                   const uint32_t* __restrict__ rest_q, const uint32_t* __restrict__ rest_cnt, uint32_t lpq, ItemDesc* __restrict__ items,
+                   uint32_t* __restrict__ n_items, const uint64_t* __restrict__ x_row_ptr) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave0 = blockIdx.x * 4u + (threadIdx.x >> 6), n_waves = gridDim.x * 4u;
+    const uint32_t nq = min(*rest_cnt, nrows);                                   // (a query is listed at most once)
+    const uint32_t qpw = 64u / lpq, qi = lane / lpq, j0 = first_rank + lane % lpq;
+    for (uint32_t g = wave0; g * qpw < nq; g += n_waves) {
+        const uint32_t i = g * qpw + qi;
+        uint32_t q = (qi < qpw && i < nq) ? rest_q[i] : nrows;
+        const bool live = q < nrows;
+        if (!live) q = 0;
+        const uint32_t cnt = live ? min(min(p_cnt[q], beam_in), end_rank) : 0u;  // slots [first_rank, end_rank) of the query
+        uint32_t n = 0;
+        for (uint32_t j = j0; j < cnt; j += lpq) { const uint32_t parent = p_idx[(size_t)q * p_stride + j]; n += ptile[parent + 1] - ptile[parent]; }
+        uint32_t incl = n;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)incl, d, 64); if (lane >= (uint32_t)d) incl += y; }
+        const uint32_t total = (uint32_t)__shfl((int)incl, 63, 64);
+        if (total == 0) continue;
+        uint32_t base = 0;
+        if (lane == 63u) base = atomicAdd(n_items, total);
+        base = (uint32_t)__shfl((int)base, 63, 64) + incl - n;
+        uint64_t xb = 0; uint32_t xl = 0;
+        if (n != 0 && x_row_ptr) { xb = x_row_ptr[q]; xl = (uint32_t)(x_row_ptr[q + 1] - xb); }
+        for (uint32_t j = j0; n != 0 && j < cnt; j += lpq) {
+            const uint32_t parent = p_idx[(size_t)q * p_stride + j];
+            const float ps = p_val[(size_t)q * p_stride + j];
+            const uint32_t cb = chunk_col[parent], t0 = ptile[parent], nt = ptile[parent + 1] - t0;
+            const uint32_t off = cand_off[(size_t)q * beam_in + j];
+            for (uint32_t tt = 0; tt < nt; ++tt)
+                items[base++] = make_item(q, t0 + tt, q * cand_stride + off + (tiles[t0 + tt].col_begin - cb), ps, xb, xl);
+        }
+    }
+}
+
 void launch_k0b_remaining(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, BeamDev prev, const uint32_t* cand_off, const uint32_t* done,
-                          uint32_t first_rank, void* items, uint32_t* n_items, hipStream_t s, uint32_t end_rank) {
+                          uint32_t first_rank, void* items, uint32_t* n_items, hipStream_t s, uint32_t end_rank, const uint32_t* rest_q, const uint32_t* rest_cnt) {
     if (P.nrows == 0) return;
+    if (rest_q) {   // (n_items was zeroed together with *rest_cnt, before the first stage)
+        if (!rest_cnt) fail("k0b: the list of unfinished queries needs its count");
+        const uint32_t hi = std::min(P.beam_in, end_rank);
+        const uint32_t lpq = std::max(1u, std::min(hi > first_rank ? hi - first_rank : 1u, 64u));   // lanes per listed query: its slots, at most a wavefront
+        hipLaunchKernelGGL(k0b_remaining_list, dim3(std::min<uint32_t>((P.nrows + 3u) / 4u, 512u)), dim3(256), 0, s, L.chunk_col, L.ptile, L.tiles, P.nrows, P.beam_in,
+                           first_rank, end_rank, P.cand_stride, prev.idx, prev.val, prev.cnt, prev.stride, cand_off, rest_q, rest_cnt, lpq, static_cast<ItemDesc*>(items),
+                           n_items, X.dense ? nullptr : X.row_ptr + P.row0);
+        XRL_LAUNCH_CHECK();
+        return;
+    }
     XRL_HIP(hipMemsetAsync(n_items, 0, 4, s));
     hipLaunchKernelGGL(k0b_remaining, dim3((P.nrows + 255) / 256), dim3(256), 0, s, L.chunk_col, L.ptile, L.tiles, P.nrows, P.beam_in, first_rank, end_rank,
                        P.cand_stride, prev.idx, prev.val, prev.cnt, prev.stride, cand_off, done, static_cast<ItemDesc*>(items), n_items,

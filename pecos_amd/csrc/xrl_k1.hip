@@ -44,6 +44,7 @@ struct K1Args {
     uint32_t n_vblocks;          // number of wavefront-sized work blocks
     unsigned long long* phase;   // debug (ablate bit 6): per-phase cycle totals [prologue, fill, D1, D3, epilogue, waves]
     uint32_t* fb_out;            // pruning feedback: the launch's item count (a later stage of a bound-pruned layer) goes to this host-visible word
+    uint32_t stride_vblocks;     // k1_list_kernel: the grid is a fixed number of wavefronts, each walks the list's work blocks with this stride
 };
 
 template <int G, int PPC, class ACC>
@@ -102,15 +103,17 @@ template <int G, int NS> struct K1Cfg {
 #endif
 // LK = row lookup: 0 rank-bitmap {bits32, rank} (8 B / 32 features), 1 bucket table + binary search,
 //      2 rank-bitmap {bits64, rank, extent of the word's first row} (16 B / 64 features; sparse tiles)
-template <int G, int NS, int PPC, bool DENSE, int LK>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(XRL_K1_WPE, 8))) k1_kernel(K1Args a) {
+// k1_run: the body of both kernels below.  PERSIST (k1_list_kernel): the wavefront walks a compacted list with a fixed grid; a kernel of its own so
+// that the one-block-per-wavefront kernel keeps its registers.
+template <int G, int NS, int PPC, bool DENSE, int LK, bool PERSIST>
+__device__ __forceinline__ void k1_run(const K1Args& a) {
     constexpr int W = K1Cfg<G, NS>::W, H = K1Cfg<G, NS>::H, UH = K1Cfg<G, NS>::UH, P = K1Cfg<G, NS>::P, U = K1Cfg<G, NS>::U,
                   NB = K1Cfg<G, NS>::NB, TAIL = K1Cfg<G, NS>::TAIL;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
     // the wavefronts of a block are fully independent: each owns a slice of the dynamic LDS
     const uint32_t wave = threadIdx.x >> 6;
-    const uint32_t vblock = blockIdx.x * (blockDim.x >> 6) + wave;
-    if (vblock >= a.n_vblocks) return;
+    const uint32_t vblock0 = blockIdx.x * (blockDim.x >> 6) + wave;
+    if (vblock0 >= a.n_vblocks) return;
     unsigned char* smem = smem_all + (size_t)wave * a.lds_per_wave;
     uint2* uq = reinterpret_cast<uint2*>(smem);                        // units {x value, entry start | count << 25}
     uint2* hq = reinterpret_cast<uint2*>(uq + W * (UH + TAIL));                 // hits  {x value, row slot}
@@ -126,6 +129,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(XRL_K1
 #else
     auto tick = [](int) {};
 #endif
+    auto body = [&](const uint32_t vblock) {
     ItemDesc it;
     if (!fetch_item<W>(a.items, a.n_items, a.n_slots, a.fb_out, vblock, grp, lane, it)) return;
     const bool active = it.tile != kNoTile;
@@ -323,10 +327,24 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(XRL_K1
         if (lane == 0) { for (int i = 0; i < 5; ++i) atomicAdd(&a.phase[i], t_ph[i]); atomicAdd(&a.phase[5], 1ull); }
     }
 #endif
+    };
+    if constexpr (PERSIST) {
+        // A later stage's compacted list usually fills a small part of the worst-case grid (Amazon-670K: 78 k items of 4.4 M slots -- 2.2 M wavefronts
+        // that only read the count and leave cost more than the work): a fixed grid of wavefronts walks the list instead (wavefront-uniform loop).
+        const uint32_t nb = (*a.n_items + W - 1) / W;
+        if (a.fb_out && vblock0 == 0 && lane == 0) *a.fb_out = *a.n_items;          // (also when the list is empty)
+        for (uint32_t vb = vblock0; vb < nb; vb += a.stride_vblocks) { body(vb); wave_sync_lds(); }
+    } else body(vblock0);
 }
 
+template <int G, int NS, int PPC, bool DENSE, int LK>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(XRL_K1_WPE, 8))) k1_kernel(K1Args a) { k1_run<G, NS, PPC, DENSE, LK, false>(a); }
+
+template <int G, int NS, int PPC, int LK>   // sparse queries, a compacted list (a.n_items): what launch_k1 picks for list_grid > 0
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) k1_list_kernel(K1Args a) { k1_run<G, NS, PPC, false, LK, true>(a); }
+
 template <class KERNEL>
-static void launch_k1_any(KERNEL kernel, K1Args a, int W, size_t lds_wave, const K1Tune& tune, hipStream_t s) {
+static void launch_k1_any(KERNEL kernel, K1Args a, int W, size_t lds_wave, const K1Tune& tune, hipStream_t s, uint32_t list_grid = 0) {
     lds_wave = (lds_wave + (size_t)std::max(0, tune.lds_pad) + 15) & ~(size_t)15;
     int wpb = (tune.wpb == 2 || tune.wpb == 4) ? tune.wpb : 1;
     while (wpb > 1 && lds_wave * wpb > 160 * 1024) wpb >>= 1;
@@ -338,7 +356,13 @@ static void launch_k1_any(KERNEL kernel, K1Args a, int W, size_t lds_wave, const
     const uint64_t blocks = (vblocks + wpb - 1) / wpb;
     if (vblocks > 0x7FFFFFFFull) fail("k1: grid too large; lower max_batch_rows");
     a.lds_per_wave = (uint32_t)lds_wave; a.n_vblocks = (uint32_t)vblocks;
-    hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(64 * wpb), lds, s, a);
+    uint64_t grid = blocks;
+    a.stride_vblocks = 0;
+    if (list_grid) {   // k1_list_kernel: a fixed grid (a multiple of 8: block b stays on XCD b % 8), never larger than the worst-case one
+        grid = std::min<uint64_t>(blocks, ((uint64_t)list_grid + 7) & ~7ull);
+        a.stride_vblocks = (uint32_t)(grid * wpb); a.n_vblocks = (uint32_t)std::min<uint64_t>(vblocks, grid * wpb);
+    }
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(64 * wpb), lds, s, a);
     XRL_LAUNCH_CHECK();
 }
 
@@ -361,13 +385,13 @@ int k1_auto_group(const LayerDev& L, const Layer& host, int dense) {
     return 32;
 }
 
-void launch_k1(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, const void* items, const uint32_t* n_items,
-               float* cand, int group, hipStream_t s) {
-    if (P.nrows == 0) return;
+bool launch_k1(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, const void* items, const uint32_t* n_items,
+               float* cand, int group, hipStream_t s, uint32_t list_grid) {
+    if (P.nrows == 0) return false;
     // K1T (densely held tile rows, accumulators in registers): measured faster on items in QUERY order (a bound-pruned layer's first stage: Amazon-670K
     // 1.010 -> 0.959 ms, Wiki10-31K 0.334 -> 0.286 ms) and slower on tile-sorted lists (Amazon-670K-hard 7.29 -> 8.48 ms: both kernels run at the L1-miss
     // request ceiling of ~80 G requests/s and a 384-byte dense row is 6 requests against ~4 for its entry list) -- tile_rows 1 = query-order launches only, 2 = all
-    if ((P.tune.tile_rows >= 2 || (P.tune.tile_rows == 1 && !n_items)) && P.tune.ablate == 0 && k1t_serves(L, X)) { launch_k1t(L, P, X, items, n_items, cand, s); return; }
+    if ((P.tune.tile_rows >= 2 || (P.tune.tile_rows == 1 && !n_items)) && P.tune.ablate == 0 && k1t_serves(L, X)) { launch_k1t(L, P, X, items, n_items, cand, s); return false; }
     K1Args a;
     a.L = L; a.X = X; a.items = static_cast<const ItemDesc*>(items); a.n_items = n_items; a.cand = cand;
     a.n_slots = (uint64_t)P.nrows * P.beam_in * L.max_tiles_per_parent;
@@ -379,13 +403,25 @@ void launch_k1(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, const
     a.phase = ((ablate & 64) && ((ablate >> 8) == 0 || (ablate >> 8) == P.layer + 1)) ? k1_phase_buffer() : nullptr;
     a.fb_out = (n_items && P.fb_host && P.layer >= 0 && P.layer < kFbLayers) ? P.fb_host + fb_items_word(P.layer) : nullptr;
     const int ppc = pp_class(P.pp);
+    // (the fixed-grid form exists where it keeps everything in registers at 4 wavefronts per SIMD: sparse queries, 16 or 32 lanes per item, the
+    //  post-processors of class 0; everything else keeps the worst-case grid)
+    const bool persist = n_items != nullptr && list_grid > 0 && ablate == 0 && !X.dense && ppc == 0;
+    bool ran_list = false;
 #define XRL_K1_PP(GG, NN, DD, LL) do { if (ppc) launch_k1_any(&k1_kernel<GG, NN, 1, DD, LL>, a, 64 / GG, lds, P.tune, s); else launch_k1_any(&k1_kernel<GG, NN, 0, DD, LL>, a, 64 / GG, lds, P.tune, s); } while (0)
+#define XRL_K1_LIST(GG, NN, LL) launch_k1_any(&k1_list_kernel<GG, NN, 0, LL>, a, 64 / GG, lds, P.tune, s, list_grid)
 #define XRL_K1(GG, NN) do { \
         const size_t lds = K1Cfg<GG, NN>::lds_bytes(a.acc_stride); \
         if (X.dense) XRL_K1_PP(GG, NN, true, 0); \
         else if (L.bucket) XRL_K1_PP(GG, NN, false, 1); \
         else if (L.bitmap64) XRL_K1_PP(GG, NN, false, 2); \
         else XRL_K1_PP(GG, NN, false, 0); } while (0)
+#define XRL_K1P(GG, NN) do { \
+        if (!persist) { XRL_K1(GG, NN); break; } \
+        const size_t lds = K1Cfg<GG, NN>::lds_bytes(a.acc_stride); \
+        ran_list = true; \
+        if (L.bucket) XRL_K1_LIST(GG, NN, 1); \
+        else if (L.bitmap64) XRL_K1_LIST(GG, NN, 2); \
+        else XRL_K1_LIST(GG, NN, 0); } while (0)
     // a tile row must fit NS units of `group` lanes; widen a (forced) group that is too narrow
     if (group < 1 || group > 64 || (group & (group - 1))) fail("k1: lanes-per-item must be a power of two in [1, 64]");
     auto max_ns = [](int g) { return g < 8 ? 1u : (g == 32 ? 4u : 2u); };
@@ -397,12 +433,15 @@ void launch_k1(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, const
     case 2: XRL_K1(2, 1); break;
     case 4: XRL_K1(4, 1); break;
     case 8: if (ns <= 1) XRL_K1(8, 1); else XRL_K1(8, 2); break;
-    case 16: if (ns <= 1) XRL_K1(16, 1); else XRL_K1(16, 2); break;
-    case 32: if (ns <= 1) XRL_K1(32, 1); else if (ns == 2) XRL_K1(32, 2); else if (ns == 3) XRL_K1(32, 3); else XRL_K1(32, 4); break;
+    case 16: if (ns <= 1) XRL_K1P(16, 1); else XRL_K1P(16, 2); break;
+    case 32: if (ns <= 1) XRL_K1P(32, 1); else if (ns == 2) XRL_K1P(32, 2); else if (ns == 3) XRL_K1P(32, 3); else XRL_K1P(32, 4); break;
     default: if (ns <= 1) XRL_K1(64, 1); else XRL_K1(64, 2); break;
     }
+#undef XRL_K1P
 #undef XRL_K1
+#undef XRL_K1_LIST
 #undef XRL_K1_PP
+    return ran_list;
 }
 
 }  // namespace xrl

@@ -50,6 +50,8 @@ struct K1TArgs {
     // SEL, items == nullptr: the item is DERIVED (k0_prolongate folded into this launch) and the offsets K0 would have written go out here
     const uint32_t* p_idx; const uint64_t* x_row_ptr;   // (x_row_ptr: of the batch's first row)
     uint32_t cand_stride; uint32_t* cand_off; uint32_t* ncand;
+    // SEL, rest_q != nullptr: the unfinished queries are appended to this list (count *rest_cnt): the later stages' launches walk it
+    uint32_t* rest_q; uint32_t* rest_cnt;
 };
 
 template <int NR> struct RowVec;
@@ -243,6 +245,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))
             if (mine) a.cand_off[q * a.beam_in + (uint32_t)lig] = incl - wd;
             if (qv && !d && lig == 0) a.ncand[q] = total;
         }
+        if (a.rest_q) {   // the later stages' list: one atomicAdd per wavefront, and only where one of its two queries is unfinished
+            const unsigned long long um = __ballot(qv && !d && lig == 0);
+            if (um) {
+                uint32_t base = 0;
+                if (lane_e == 0) base = atomicAdd(a.rest_cnt, (uint32_t)__popcll(um));
+                base = (uint32_t)__shfl((int)base, 0, 64);
+                if (qv && !d && lig == 0) a.rest_q[base + (grp ? (uint32_t)(um & 1ull) : 0u)] = (uint32_t)q;
+            }
+        }
         if (active && !d) {                                             // the later stages read the row of an unfinished query only (always: +0.034 ms on Amazon-670K)
             float* __restrict__ out = a.cand + it.out_off;
 #pragma unroll
@@ -350,6 +361,8 @@ void launch_k1t(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, cons
             if ((uint64_t)P.nrows * P.cand_stride > 0xFFFFFFFFull) fail("k1t: candidate buffer exceeds 2^32 floats; lower max_batch_rows");
             a.p_idx = sel->prev.idx; a.x_row_ptr = X.row_ptr + P.row0; a.cand_stride = P.cand_stride; a.cand_off = sel->cand_off; a.ncand = sel->ncand;
         }
+        if (sel->rest_q && !sel->rest_cnt) fail("k1t: the list of unfinished queries needs its count");
+        a.rest_q = sel->rest_q; a.rest_cnt = sel->rest_cnt;
     }
     const dim3 grid((a.n_vblocks + 3u) / 4u), block(256);
 #define XRL_K1T_L(GG, NN, BB, SS) do { \

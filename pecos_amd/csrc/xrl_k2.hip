@@ -2,6 +2,8 @@
 //   K2 k2_topk_*       sorted_csr + reorder_prediction      inference.hpp:1223-1298, 1919-1923
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "xrl_device.h"
 #include "xrl_kernels.h"
 
@@ -33,6 +35,9 @@ struct K2Args {
     uint32_t* done;
     const uint32_t* skip_done;
     const uint32_t* xok;         // [nrows] the pruning guard of every query (prune_guard_ok): 0 = never final before every candidate is scored
+    // the list of the queries a first stage left unfinished (count *rest_cnt, any order): with `done` the launch APPENDS to it (one atomicAdd per
+    // wavefront, i.e. per unfinished query), without it k2_topk_list ranks the listed queries only
+    uint32_t* rest_q; uint32_t* rest_cnt;
 };
 
 __device__ __forceinline__ uint32_t k2_child_id(const K2Args& a, uint64_t q, uint32_t pos) {
@@ -146,14 +151,7 @@ __global__ void __launch_bounds__(64) k2_topk_lds(K2Args a) {   // any k that fi
 // (candidate p = r*64 + lane) and wave_topk (xrl_device.h) selects and ranks with ballot bisection instead of
 // serial insertions.  Four queries (wavefronts) per workgroup.
 template <int NS>
-__global__ void __launch_bounds__(256) k2_topk_wave(K2Args a) {
-    __shared__ uint2 sc_all[4 * 64];
-    const int lane = threadIdx.x & 63;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t q32 = blockIdx.x * 4u + wave;
-    if (q32 >= a.nrows) return;
-    const uint64_t q = q32;
-    if (a.skip_done && a.skip_done[q]) return;
+__device__ __forceinline__ void k2_wave_query(const K2Args& a, const uint64_t q, uint2* sc, const int lane) {
     uint32_t n = min(a.ncand[q], (uint32_t)(64 * NS));
     const uint32_t bcnt0 = a.implicit_root ? 1u : min(a.p_cnt[q], a.beam_in);
     // (both loads are issued up front, whether or not the query has that many parents: no dependent round trips later)
@@ -182,10 +180,13 @@ __global__ void __launch_bounds__(256) k2_topk_wave(K2Args a) {
         bool d = true;
         // the k-th best >= the best any later slot can reach (a NaN parent score proves nothing: no pruning)
         if (limited) d = a.xok[q] != 0u && ps_next == ps_next && wave_count_ge<NS>(key, score_key(a.mult ? fmaxf(ps_next, 0.0f) : ps_next)) >= a.k;
-        if (lane == 0) a.done[q] = d ? 1u : 0u;
+        if (lane == 0) {
+            a.done[q] = d ? 1u : 0u;
+            if (!d && a.rest_q) a.rest_q[atomicAdd(a.rest_cnt, 1u)] = (uint32_t)q;
+        }
     }
     uint32_t rank, sb, pp;
-    const uint32_t kk = wave_topk<NS>(key, sbits, pos, a.k, sc_all + wave * 64u, lane, rank, sb, pp);
+    const uint32_t kk = wave_topk<NS>(key, sbits, pos, a.k, sc, lane, rank, sb, pp);
     uint32_t child;
     if (lane_beam) {
         uint32_t jj = 0;                                            // last beam slot whose block starts at or before the position
@@ -203,16 +204,61 @@ __global__ void __launch_bounds__(256) k2_topk_wave(K2Args a) {
     if (lane == 0) a.out_cnt[q] = kk;
 }
 
+template <int NS>
+__global__ void __launch_bounds__(256) k2_topk_wave(K2Args a) {
+    __shared__ uint2 sc_all[4 * 64];
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t q32 = blockIdx.x * 4u + wave;
+    if (q32 >= a.nrows) return;
+    if (a.skip_done && a.skip_done[q32]) return;
+    k2_wave_query<NS>(a, q32, sc_all + wave * 64u, lane);
+}
+
+// (k2_topk_list re-reads the kernel arguments for every listed query, through a pointer the compiler cannot see through: with the argument words
+//  hoisted out of its loop and kept live around the selection the instantiations lose an occupancy step -- NS = 13: 75 VGPRs against 50)
+//  K2Args must stay k2_topk_list's ONLY kernel argument: it is read from offset 0 of the kernel-argument segment, word by word.
+typedef const __attribute__((address_space(4))) uint32_t K2ArgWord;
+static_assert(sizeof(K2Args) % 4 == 0 && alignof(K2Args) <= 8 && std::is_trivially_copyable<K2Args>::value, "k2_wave_query_reload copies K2Args as 32-bit words");
+template <int NS>
+__device__ __forceinline__ void k2_wave_query_reload(K2ArgWord* wp, const uint32_t q32, uint2* sc, const int lane) {
+    constexpr int NW = (int)(sizeof(K2Args) / 4);
+    union { K2Args a; uint32_t w[NW]; } u;
+    asm volatile("" : "+s"(wp));
+#pragma unroll
+    for (int i = 0; i < NW; ++i) u.w[i] = wp[i];
+    k2_wave_query<NS>(u.a, q32, sc, lane);
+}
+
+// The last stage of a bound-pruned layer on the LIST of unfinished queries: a small fixed grid, every wavefront takes the listed queries
+// wave, wave + #wavefronts, ... of the device-side count (the batch-sized grid of k2_topk_wave would return on skip_done[q] almost everywhere).
+template <int NS>
+__global__ void __launch_bounds__(256) k2_topk_list(K2Args a) {
+    __shared__ uint2 sc_all[4 * 64];
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t n_waves = gridDim.x * 4u, nq = min(*a.rest_cnt, a.nrows);
+    for (uint32_t i = blockIdx.x * 4u + wave; i < nq; i += n_waves) {
+        const uint32_t q32 = __builtin_amdgcn_readfirstlane(a.rest_q[i]);
+        if (q32 < a.nrows) k2_wave_query_reload<NS>((K2ArgWord*)__builtin_amdgcn_kernarg_segment_ptr(), q32, sc_all + wave * 64u, lane);
+        wave_sync_lds();
+    }
+}
+
 size_t k2_max_k() { return (160 * 1024) / 8; }
 
 bool k2_wave_path(const LayerPlan& P) { return P.k <= 64 && P.cand_stride <= 64u * 32u; }
 
 void launch_k2_topk(const LayerDev& L, const LayerPlan& P, BeamDev prev, const uint32_t* cand_off,
                     const uint32_t* ncand, const float* cand, BeamDev out, hipStream_t s, uint32_t rank_limit, uint32_t limited_cands,
-                    uint32_t* done, const uint32_t* skip_done, const uint32_t* xok) {
+                    uint32_t* done, const uint32_t* skip_done, const uint32_t* xok, uint32_t* rest_q, uint32_t* rest_cnt) {
     if (P.nrows == 0) return;
     K2Args a;
-    a.p_val = prev.val; a.rank_limit = rank_limit; a.done = done; a.skip_done = skip_done; a.xok = xok;
+    a.p_val = prev.val; a.rank_limit = rank_limit; a.done = done; a.skip_done = skip_done; a.xok = xok; a.rest_q = rest_q; a.rest_cnt = rest_cnt;
+    if (rest_q && !rest_cnt) fail("k2: the list of unfinished queries needs its count");
+    bool list = rest_q && !done;         // (with done: the launch appends)
+    if (list && !skip_done) fail("k2: the list form also takes the done flags (one instantiation keeps the batch-sized grid)");
+    if (list && (rank_limit || !k2_wave_path(P))) fail("k2: the list form serves the last stage of a bound-pruned layer");
     if (done && !xok) fail("k2: bound pruning needs the per-query guard flags");
     a.mult = (P.pp.kind == PP_SIGMOID || P.pp.kind == PP_LP_HINGE) ? 1 : 0;
     if ((rank_limit || done || skip_done) && !k2_wave_path(P)) fail("k2: bound pruning needs the register top-k path");
@@ -224,22 +270,29 @@ void launch_k2_topk(const LayerDev& L, const LayerPlan& P, BeamDev prev, const u
     a.implicit_root = P.implicit_root;
     if (P.k == 0) fail("k2: only_topk / beam_size resolved to 0");
     // beyond the LDS kernel's reach (or forced, tests: k2_big_min_k): the segmented sort of xrl_topk_big.hip
-    if (!rank_limit && !done && !skip_done && (P.k > k2_max_k() || (P.tune.k2_big_min_k > 0 && P.k >= (uint32_t)P.tune.k2_big_min_k))) {
+    if (!rank_limit && !done && !skip_done && !list && (P.k > k2_max_k() || (P.tune.k2_big_min_k > 0 && P.k >= (uint32_t)P.tune.k2_big_min_k))) {
         launch_k2_topk_big(L, P, prev, cand_off, ncand, cand, out.idx, out.val, out.cnt, out.stride, s);
         return;
     }
     if (k2_wave_path(P)) {
         // (a rank-limited selection looks at the first slots' candidates only: registers for that many)
         const uint32_t ns = ((rank_limit ? std::min(P.cand_stride, std::max(1u, limited_cands)) : P.cand_stride) + 63u) / 64u;
-        const dim3 grid((P.nrows + 3u) / 4u), block(256);
-        if (ns <= 1) hipLaunchKernelGGL(k2_topk_wave<1>, grid, block, 0, s, a);
-        else if (ns <= 2) hipLaunchKernelGGL(k2_topk_wave<2>, grid, block, 0, s, a);
-        else if (ns <= 4) hipLaunchKernelGGL(k2_topk_wave<4>, grid, block, 0, s, a);
-        else if (ns <= 8) hipLaunchKernelGGL(k2_topk_wave<8>, grid, block, 0, s, a);
-        else if (ns <= 13) hipLaunchKernelGGL(k2_topk_wave<13>, grid, block, 0, s, a);
-        else if (ns <= 16) hipLaunchKernelGGL(k2_topk_wave<16>, grid, block, 0, s, a);
-        else if (ns <= 24) hipLaunchKernelGGL(k2_topk_wave<24>, grid, block, 0, s, a);
-        else hipLaunchKernelGGL(k2_topk_wave<32>, grid, block, 0, s, a);
+        // (the looped instantiation for 16 candidate registers would lose an occupancy step -- 68 VGPRs against 60: those rows keep the
+        //  batch-sized grid and skip on the done flags)
+        if (ns > 13 && ns <= 16) list = false;
+        const dim3 grid(list ? std::min<uint32_t>((P.nrows + 3u) / 4u, 1024u) : (P.nrows + 3u) / 4u), block(256);
+#define XRL_K2_WAVE(NN) do { if (list) hipLaunchKernelGGL(k2_topk_list<NN>, grid, block, 0, s, a); else hipLaunchKernelGGL(k2_topk_wave<NN>, grid, block, 0, s, a); } while (0)
+#define XRL_K2_GRID(NN) hipLaunchKernelGGL(k2_topk_wave<NN>, grid, block, 0, s, a)
+        if (ns <= 1) XRL_K2_WAVE(1);
+        else if (ns <= 2) XRL_K2_WAVE(2);
+        else if (ns <= 4) XRL_K2_WAVE(4);
+        else if (ns <= 8) XRL_K2_WAVE(8);
+        else if (ns <= 13) XRL_K2_WAVE(13);
+        else if (ns <= 16) XRL_K2_GRID(16);
+        else if (ns <= 24) XRL_K2_WAVE(24);
+        else XRL_K2_WAVE(32);
+#undef XRL_K2_GRID
+#undef XRL_K2_WAVE
     } else if (P.k <= 64) {
         hipLaunchKernelGGL(k2_topk_reg, dim3(P.nrows), dim3(64), 0, s, a);
     } else {

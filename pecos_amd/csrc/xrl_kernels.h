@@ -48,12 +48,15 @@ void launch_k0_prolongate(const LayerDev& L, const LayerPlan& P, const QueriesDe
                           uint32_t* ncand, void* items, hipStream_t s, uint32_t item_ranks = 0xFFFFFFFFu /* beam slots that get item descriptors */);
 // bound-pruned layers, second phase: items of the beam slots >= first_rank of the queries with done[q] == 0, compact; *n_items = their number
 void launch_k0b_remaining(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, BeamDev prev, const uint32_t* cand_off, const uint32_t* done,
-                          uint32_t first_rank, void* items, uint32_t* n_items, hipStream_t s, uint32_t end_rank = 0xFFFFFFFFu);   // beam slots [first_rank, end_rank)
+                          uint32_t first_rank, void* items, uint32_t* n_items, hipStream_t s, uint32_t end_rank = 0xFFFFFFFFu,   // beam slots [first_rank, end_rank)
+                          const uint32_t* rest_q = nullptr, const uint32_t* rest_cnt = nullptr);   // the LIST form: the queries rest_q[0 .. *rest_cnt) instead of every query with done[q] == 0; *n_items is NOT zeroed here
 bool k2_wave_path(const LayerPlan& P);   // the register top-k kernel serves this layer (what bound pruning needs)
 size_t k0_item_bytes();
 // K1  (query, tile) inner products + bias + post-processor + combine, one item per G lanes.
-void launch_k1(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, const void* items, const uint32_t* n_items,
-               float* cand, int group, hipStream_t s);
+// list_grid > 0 (a compacted list, n_items != nullptr): a fixed grid of about this many workgroups walks the list (k1_list_kernel) where that form is
+// compiled -- sparse queries, 16 or 32 lanes per item, post-processors of class 0 -- instead of a grid sized for n_slots.  Returns whether it ran.
+bool launch_k1(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, const void* items, const uint32_t* n_items,
+               float* cand, int group, hipStream_t s, uint32_t list_grid = 0);
 // counting sort of the item descriptors by tile (LDS histograms, no global atomics); start[n_tiles] = #items
 void launch_sort_items(const LayerDev& L, uint64_t n_slots, const void* items, void* sorted, uint32_t* H,
                        uint32_t* start, hipStream_t s,
@@ -70,7 +73,9 @@ void launch_k2_topk(const LayerDev& L, const LayerPlan& P, BeamDev prev, const u
                     const uint32_t* ncand, const float* cand, BeamDev out, hipStream_t s,
                     uint32_t rank_limit = 0 /* > 0: only the candidates of the first rank_limit beam slots */, uint32_t limited_cands = 0 /* their maximum number */,
                     uint32_t* done = nullptr /* out: that selection is final (exact bound, see K2Args) */, const uint32_t* skip_done = nullptr /* queries to skip */,
-                    const uint32_t* xok = nullptr /* with done: the per-query pruning guard (launch_xguard / K1Q's out_xok) */);
+                    const uint32_t* xok = nullptr /* with done: the per-query pruning guard (launch_xguard / K1Q's out_xok) */,
+                    uint32_t* rest_q = nullptr, uint32_t* rest_cnt = nullptr /* with done: the queries that are NOT done are also appended to rest_q (count *rest_cnt);
+                                                                               without done: the launch ranks the listed queries only (fixed grid) */);
 // stats: sum over (query, parent) of the reference chunk's algorithmic bytes, and of candidates
 constexpr int kStatsPerLayer = 8;   // [0] reference-chunk bytes, [1] candidates, [2] items, [3] probes, [4] matched rows, [5] their entries,
                                     // [6] tile columns over the items, [7] query features x tile columns over the items
@@ -111,7 +116,8 @@ bool k1t_serves(const LayerDev& L, const QueriesDev& X);
 // kernel's epilogue does what launch_k2_topk(rank_limit = 1, done) would do on the row it has just computed: top-k, child ids, done[q]
 // for every query; the candidate row is stored for the queries that are not done.  P is the whole layer's plan.  items == nullptr (beam_in <= 32):
 // the launch derives its items from the beam itself and writes cand_off / ncand of the unfinished queries -- no launch_k0_prolongate before it.
-struct K1TSelect { BeamDev prev; const uint32_t* xok; BeamDev out; uint32_t* done; uint32_t* cand_off; uint32_t* ncand; };
+struct K1TSelect { BeamDev prev; const uint32_t* xok; BeamDev out; uint32_t* done; uint32_t* cand_off; uint32_t* ncand;
+                   uint32_t* rest_q = nullptr; uint32_t* rest_cnt = nullptr; };   // rest_q: the queries that are not done are also appended here (count *rest_cnt)
 bool k1t_selects(const LayerDev& L, const LayerPlan& P, const QueriesDev& X);   // one tile per parent, 32 lanes per item, k <= kTopkExtractMaxK, a combining layer
 void launch_k1t(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, const void* items, const uint32_t* n_items, float* cand, hipStream_t s,
                 const K1TSelect* sel = nullptr);

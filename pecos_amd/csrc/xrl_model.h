@@ -164,7 +164,8 @@ struct LaneWs {      // scratch of one row batch in flight
     DevBuf items, items_sorted, sort_hist, sort_start;   // item descriptors (K0) and their tile-sorted copy
     DevBuf blk_start, x_ok;                              // K1G: first workgroup of every tile; per-row "all x finite" flags
     DevBuf qperm, qsort_hist, qsort_start;               // K1Q's sorted launch: launch slot -> query, and the counting sort's scratch
-    DevBuf prune_done, prune_cnt;                        // bound-pruned layers: per-query "first phase was final" flags; item count of the second phase
+    DevBuf prune_done, prune_cnt;                        // bound-pruned layers: per-query "first phase was final" flags; word 0: item count of the second phase, word 1: length of rest_q
+    DevBuf rest_q;                                       // ... the queries the first stage left unfinished, any order (option leaf_tail: the later stages' launches walk this list)
 };
 struct Workspace {
     LaneWs lane[2];      // two row batches are in flight on two streams (xrl_predict.cpp)
@@ -225,6 +226,9 @@ struct Model {
         int presence = 1;                       // K1Q, sparse X: 1 = layers that run UNSTAGED (prune off, or switched by the pruning feedback) request a (feature, parent) weight
                                                 // segment only when the layer's presence word says it holds a weight; 2 = every layer that has presence words; 0 = never
         int leaf_fuse = 1;                      // bound-pruned tile-format layers of one-tile parents: K1T derives its items and selects the first stage's top-k itself (no k0_prolongate / k2_topk launch); 2: K0 still launched; 0: three launches
+        int leaf_tail = 1;                      // bound-pruned tile-format layers of two stages (narrow beams): the first stage lists the unfinished queries and the later stage's three launches
+                                                // work in proportion to that list (k0b / K2 on a small fixed grid; K1 on a fixed grid of 6144 workgroups once the feedback's item count is known
+                                                // and small against the worst case); n >= 2: K1 always on a fixed grid of n workgroups (A/B runs, tests); 0: batch-sized launches
         int prune_mid = 1;                      // bound-pruned tile-format layers with >= 16 beam parents: a middle stage (slots 1..4) between the first parent and "everything else"
         int sort_rest = 1;                      // bound-pruned tile-format layers: the second phase's compacted items are tile-sorted before K1 runs on them (0: query order)
         int sort_rest_min = 32768;              // ... only when the previous predicts' later stages held at least this many items (pruning feedback's count; 0 = always)

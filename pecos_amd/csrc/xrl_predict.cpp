@@ -48,6 +48,7 @@ struct Route {
     uint32_t stage_end[3]; int n_stage;   // tile format: stage s scores the slots [stage_end[s-1], stage_end[s])
     bool fuse, fuse_k0;      // tile format (option leaf_fuse): K1T selects the first stage's top-k itself / derives its items too
     bool sorts_rest;         // tile format (option sort_rest): the later stages run on tile-sorted items, unless the feedback's item count says too few
+    bool compact_rest;       // tile format, two stages (option leaf_tail): the first stage lists the unfinished queries, the later stage's launches walk that list
 };
 
 // What the launch functions share: the predict's constants and the row batch in flight (begin_batch).
@@ -64,7 +65,7 @@ struct Batch {
     bool x_ok_done = false;              // x_ok[q] = the pruning guard of query q (also "all x finite" for K1G's fast loop) is written: by launch_xguard
                                          // or, for free, by a K1Q launch that runs before the first layer that needs it
     BeamDev beam[2]{};
-    uint32_t *cand_off, *ncand, *sort_hist, *sort_start, *blk_start, *x_ok, *qperm, *qsort_hist, *qsort_start, *prune_done, *prune_cnt;
+    uint32_t *cand_off, *ncand, *sort_hist, *sort_start, *blk_start, *x_ok, *qperm, *qsort_hist, *qsort_start, *prune_done, *prune_cnt, *rest_q;
     float* cand; void *items, *items_sorted;
 
     void begin_batch(const LaneWs& lw, hipStream_t s, uint64_t r0, uint32_t n) {
@@ -73,7 +74,7 @@ struct Batch {
         for (int i = 0; i < 2; ++i) beam[i] = BeamDev{u32(lw.beam_idx[i]), lw.beam_val[i].as<float>(), u32(lw.beam_cnt[i]), beam_stride};
         cand_off = u32(lw.cand_off); ncand = u32(lw.ncand); cand = lw.cand.as<float>(); items = lw.items.p; items_sorted = lw.items_sorted.p;
         sort_hist = u32(lw.sort_hist); sort_start = u32(lw.sort_start); blk_start = u32(lw.blk_start); x_ok = u32(lw.x_ok);
-        qperm = u32(lw.qperm); qsort_hist = u32(lw.qsort_hist); qsort_start = u32(lw.qsort_start); prune_done = u32(lw.prune_done); prune_cnt = u32(lw.prune_cnt);
+        qperm = u32(lw.qperm); qsort_hist = u32(lw.qsort_hist); qsort_start = u32(lw.qsort_start); prune_done = u32(lw.prune_done); prune_cnt = u32(lw.prune_cnt); rest_q = u32(lw.rest_q);
     }
     bool unstaged(size_t l) const { return l < (size_t)kFbLayers && fb.unstaged[l]; }   // pruning feedback: the layer scores everything in one pass this time
     // (route_layer reads the plan's shape and policy fields only: it is asked about batch sizes, not about a batch)
@@ -243,6 +244,10 @@ Route route_layer(const Batch& b, size_t l, uint64_t nrows) {
     r.fuse = opt.leaf_fuse != 0 && r.J == 1 && !b.stats && k1t_selects(L.dev, P, b.X);
     // ... and (beams of up to 32 parents) derives its items from the beam: K0 is not launched either.  leaf_fuse = 2 keeps K0 (A/B runs).
     r.fuse_k0 = r.fuse && opt.leaf_fuse != 2 && beam_in <= 32u;
+    // option leaf_tail: narrow beams (two stages) -- whatever writes done[q] in the first stage also appends the unfinished queries to a list, and
+    // k0b_remaining / K1 / k2_topk_rest are pointed at that list instead of the batch (Amazon-670K: 1.6 % of the queries).  Wide beams with a
+    // middle stage and the stats pass keep the batch-sized launches.
+    r.compact_rest = opt.leaf_tail != 0 && r.n_stage == 2 && !b.stats;
     return r;
 }
 
@@ -254,7 +259,7 @@ void reserve_scratch(const Batch& b, Workspace& ws, uint64_t n_rows) {
         bin_max = std::max(bin_max, b.shape[l].beam_in); cs_max = std::max(cs_max, b.shape[l].cand_stride); slots_max = std::max<uint64_t>(slots_max, nb * b.shape[l].beam_in * m.layers[l]->max_tiles_per_parent);
     }
     // bytes per lane of the buffers only some routes use (0: none does, nothing is allocated)
-    size_t sorted = 0, hist = 0, starts = 0, x_ok = 0, done = 0, cnt = 0, qperm = 0, qhist = 0, qstarts = 0;
+    size_t sorted = 0, hist = 0, starts = 0, x_ok = 0, done = 0, cnt = 0, rest = 0, qperm = 0, qhist = 0, qstarts = 0;
     for (const uint64_t rows : {nb, n_rows % nb}) {
         // (every layer is asked, also the inner ones of a K1Q group: they answer like the group does)
         for (size_t l = 0; l < T && rows; ++l) {
@@ -263,6 +268,7 @@ void reserve_scratch(const Batch& b, Workspace& ws, uint64_t n_rows) {
             if (r.mode != 0 || (b.opt.prune && r.sorts_rest)) { hist = std::max(hist, sort_hist_bytes(nb * b.shape[l].beam_in * L.max_tiles_per_parent, L.n_tiles)); starts = std::max(starts, ((size_t)L.n_tiles + 1) * 4); }
             if (starts || staged_tile) sorted = slots_max * k0_item_bytes();   // (the compacted items of the later stages go to items_sorted, sorted or not)
             if (staged_tile || (r.kind == ROUTE_K1G && r.pruned)) { done = (size_t)nb * 4; cnt = 256; }
+            if (staged_tile && r.compact_rest) rest = (size_t)nb * 4;
             // (a later layer of a batch that is NOT served by K1Q decides its pruning in K2 and needs the guard flags: the K1Q launch writes them)
             if (r.kind == ROUTE_K1G || staged_tile || (r.kind == ROUTE_K1Q && b.opt.prune && r.last + 1 < T)) x_ok = (size_t)nb * 4;
             const uint32_t nk = m.layers[r.last]->dev.n_parents;
@@ -275,7 +281,7 @@ void reserve_scratch(const Batch& b, Workspace& ws, uint64_t n_rows) {
         lw.items.reserve(slots_max * k0_item_bytes());
         lw.cand_off.reserve(nb * bin_max * 4); lw.ncand.reserve(nb * 4); lw.cand.reserve(nb * (uint64_t)cs_max * 4);
         lw.items_sorted.reserve(sorted); lw.sort_hist.reserve(hist); lw.sort_start.reserve(starts); lw.blk_start.reserve(starts);
-        lw.x_ok.reserve(x_ok); lw.prune_done.reserve(done); lw.prune_cnt.reserve(cnt);
+        lw.x_ok.reserve(x_ok); lw.prune_done.reserve(done); lw.prune_cnt.reserve(cnt); lw.rest_q.reserve(rest);
         lw.qperm.reserve(qperm); lw.qsort_hist.reserve(qhist); lw.qsort_start.reserve(qstarts);
     }
     if (b.stats) m.ws->stats.reserve(T * kStatsPerLayer * sizeof(double));
@@ -373,15 +379,19 @@ void launch_tile_layer(Batch& b, size_t l, const Route& r) {
     // name; the later stages find done / cand_off / ncand / cand (unfinished queries) as K0 -> K1 -> K2 leave them.
     const uint64_t slots_b = (uint64_t)nrows * (beam_in - J) * L.max_tiles_per_parent;
     b.need_x_ok();
+    // (compact_rest) the later stage's item count and the length of the list of unfinished queries, both zeroed once per layer and batch
+    uint32_t* const rest_q = r.compact_rest ? b.rest_q : nullptr; uint32_t* const rest_cnt = r.compact_rest ? b.prune_cnt + 1 : nullptr;
+    // (a profile slot of its own -- "rest_list", and "rest_list_grid" below: the three later launches keep their names, these say which form ran)
+    if (r.compact_rest) b.timed("rest_list", l, [&] { XRL_HIP(hipMemsetAsync(b.prune_cnt, 0, 8, S)); });
     if (!r.fuse_k0) b.timed("k0_prolongate", l, [&] { launch_k0_prolongate(L.dev, P, X, prev, b.cand_off, b.ncand, b.items, S, J); });
     if (b.lanes == 2 && b.k1_done) XRL_HIP(hipStreamWaitEvent(S, b.k1_done, 0));
     if (r.fuse) {
-        const K1TSelect sel{prev, b.x_ok, out, b.prune_done, b.cand_off, b.ncand};
+        const K1TSelect sel{prev, b.x_ok, out, b.prune_done, b.cand_off, b.ncand, rest_q, rest_cnt};
         b.timed("k1_sparse", l, [&] { launch_k1t(L.dev, P, X, r.fuse_k0 ? nullptr : b.items, nullptr, b.cand, S, &sel); });
     } else {
         LayerPlan PA = P; PA.beam_in = J;                  // (K1 sizes its grid from beam_in x tiles per parent)
         b.timed(k1_name[0], l, [&] { launch_k1(L.dev, PA, X, b.items, nullptr, b.cand, r.group, S); });
-        b.timed("k2_topk", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S, J, (uint32_t)L.cand_bound(J), b.prune_done, nullptr, b.x_ok); });
+        b.timed("k2_topk", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S, J, (uint32_t)L.cand_bound(J), b.prune_done, nullptr, b.x_ok, rest_q, rest_cnt); });
     }
     if (stats) XRL_HIP(hipMemsetAsync(b.items_sorted, 0xFF, slots_b * k0_item_bytes(), S));   // the stats pass walks the whole list: unused slots read as "no tile"
     bool srt = r.sorts_rest;
@@ -402,12 +412,24 @@ void launch_tile_layer(Batch& b, size_t l, const Route& r) {
         const uint32_t r0 = r.stage_end[st - 1], r1 = r.stage_end[st]; const bool last = st == r.n_stage - 1;
         LayerPlan PB = P; PB.beam_in = r1 - r0; PB.tune.wpb = 4;   // a later stage's grid is sized for "nothing pruned": mostly empty wavefronts, 4 per workgroup to dispatch fewer groups
         // (sorted: the compacted list goes where the first phase's items were -- K1 has consumed them -- and is sorted into items_sorted)
-        b.timed(last ? "k0b_remaining" : "k0b_remaining_mid", l, [&] { launch_k0b_remaining(L.dev, P, X, prev, b.cand_off, b.prune_done, r0, srt ? b.items : b.items_sorted, b.prune_cnt, S, r1); });
+        uint32_t list_grid = 0; bool ran_list = false;
+        if (rest_q) {
+            // K1 on the compacted list: a fixed grid that walks it, when the feedback's last item count says that the list fills a small part of a LARGE
+            // worst-case grid (measured, profiles/r06_leaf.md section 7: Amazon-670K's 78 k items of 4.4 M slots 0.297 -> 0.239 ms with 6144 workgroups;
+            // a 61 250-row shard's 551 k slots 0.053 -> 0.057 ms: not there).  Either kernel is right for any count: results never depend on the choice.
+            const uint64_t slots_s = (uint64_t)nrows * (r1 - r0) * L.max_tiles_per_parent;
+            const uint32_t seen = P.fb_host ? m.fb.word(fb_items_word((int)l)) : kFbPending;
+            if (b.opt.leaf_tail >= 2) list_grid = (uint32_t)b.opt.leaf_tail;
+            else if (seen != kFbPending && slots_s >= (1ull << 21) && (uint64_t)seen * 8u <= slots_s) list_grid = 6144;
+        }
+        b.timed(last ? "k0b_remaining" : "k0b_remaining_mid", l, [&] { launch_k0b_remaining(L.dev, P, X, prev, b.cand_off, b.prune_done, r0, srt ? b.items : b.items_sorted, b.prune_cnt, S, r1, rest_q, rest_cnt); });
         if (srt) b.timed(last ? "k1_sort_items_rest" : "k1_sort_items_mid", l, [&] { launch_sort_items(L.dev, (uint64_t)nrows * (r1 - r0) * L.max_tiles_per_parent, b.items, b.items_sorted, b.sort_hist, b.sort_start, S, b.prune_cnt); });
-        b.timed(k1_name[last ? 2 : 1], l, [&] { launch_k1(L.dev, PB, X, b.items_sorted, srt ? b.sort_start + L.n_tiles : b.prune_cnt, b.cand, r.group, S); });
+        b.timed(k1_name[last ? 2 : 1], l, [&] { ran_list = launch_k1(L.dev, PB, X, b.items_sorted, srt ? b.sort_start + L.n_tiles : b.prune_cnt, b.cand, r.group, S, list_grid); });
+        if (ran_list && b.named()) b.timed("rest_list_grid", l, [] {});   // (an empty slot: K1 ran its fixed-grid form)
         if (b.lanes == 2 && last) { b.k1_done = b.next_event(); XRL_HIP(hipEventRecord(b.k1_done, S)); }
         // (a middle stage selects among the slots scored so far and renews the done flags; queries finished earlier are skipped: one buffer serves both)
-        if (last) b.timed("k2_topk_rest", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S, 0, 0, nullptr, b.prune_done); });
+        if (last && rest_q) b.timed("k2_topk_rest", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S, 0, 0, nullptr, b.prune_done, nullptr, rest_q, rest_cnt); });
+        else if (last) b.timed("k2_topk_rest", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S, 0, 0, nullptr, b.prune_done); });
         else b.timed("k2_topk_mid", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S, r1, (uint32_t)L.cand_bound(r1), b.prune_done, b.prune_done, b.x_ok); });
         if (stats && last) { launch_stats(L.dev, P, X, prev, b.ncand, b.items, stats, S, (uint64_t)nrows * J * L.max_tiles_per_parent); launch_stats(L.dev, PB, X, prev, nullptr, b.items_sorted, stats, S, slots_b); }
     }

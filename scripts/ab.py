@@ -18,7 +18,7 @@ name, scale, steps = sys.argv[1], float(sys.argv[2]), int(sys.argv[3])
 sets = sys.argv[4:] or [""]
 rows_limit = int(os.environ.get("AB_ROWS", "0"))
 shard_rows = int(os.environ.get("AB_SHARD_ROWS", "0"))   # > 0: predict only the first AB_SHARD_ROWS rows of the (whole, device-resident) X: bench.py's extra.shard8 shape
-DEFAULTS = dict(tile_rows=1, k1g_first=0, k1g_variant=0, sort_rest_min=32768, qsort=1, qsort_min_parents=64, qsort_min_rows=131072, prune=1, adaptive=1, presence=1, sort_rest=1, prune_mid=1, leaf_fuse=1, k1q_fuse=3, dense_layers=1, k1_group=0, sort_min_tiles=0)
+DEFAULTS = dict(tile_rows=1, k1g_first=0, k1g_variant=0, sort_rest_min=32768, qsort=1, qsort_min_parents=64, qsort_min_rows=131072, prune=1, adaptive=1, presence=1, sort_rest=1, prune_mid=1, leaf_fuse=1, leaf_tail=1, k1q_fuse=3, dense_layers=1, k1_group=0, sort_min_tiles=0)
 folder = f"/tmp/xrl_bench/{name}_{scale}"
 if not os.path.exists(folder + "/.done"):
     t0 = time.time()
