@@ -375,6 +375,14 @@ uint64_t xrl_debug_layout_rows(const uint32_t* rptr, uint32_t nrows, int align, 
  * rb[0] = 0 <= ... <= rb[n] = rows to rb_out (at most cap of them; may be NULL) and returns their number n + 1. */
 uint32_t xrl_debug_host_batches(const uint64_t* row_ptr, uint32_t rows, uint32_t cols, int host_batch_mb, uint32_t* rb_out, uint32_t cap);
 
+/* Host-only piece of the per-query top-k (K2): the form launch_k2_topk takes for a layer that keeps k of the cand_stride candidates a query row
+ * reserves, at option "k2_big_min_k".  stage: 0 = the whole row in one launch, 1 = a stage of the bound pruning on the batch-sized grid (limited_cands:
+ * the most candidates a rank-limited stage looks at, 0 = the row), 2 = its last stage on the list of unfinished queries.  Returns 0 = k2_topk_wave<NS>,
+ * 1 = k2_topk_list<NS>, 2 = k2_topk_reg, 3 = k2_topk_lds, 4 = the segmented sort (launch_k2_topk_big), or -1 with a message for a launch the library
+ * refuses (k = 0; a pruning stage beyond the wave form's reach); *ns_out (may be NULL) receives NS for forms 0 and 1, else 0.  The launch itself
+ * dispatches on this function. */
+int xrl_debug_k2_form(uint32_t k, uint32_t cand_stride, int64_t k2_big_min_k, int stage, uint32_t limited_cands, uint32_t* ns_out);
+
 /* Tuning knobs (benchmark / tests only).  Results never depend on them.
  *   "k1_group"            lanes per (query, tile) item in K1: 0 = auto, else a power of two <= 64
  *   "max_batch_rows"      rows of X per internal batch (0 = auto: candidate buffer <= 6 GiB)

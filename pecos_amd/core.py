@@ -251,6 +251,7 @@ class corelib(object):
         "xrl_debug_k1_phases": (None, [POINTER(c_uint64), c_int]),
         "xrl_debug_split_chunk": (c_uint32, [POINTER(c_uint64), c_uint32, c_uint64]),
         "xrl_debug_layout_rows": (c_uint64, [POINTER(c_uint32), c_uint32, c_int, POINTER(c_uint32)]),
+        "xrl_debug_k2_form": (c_int, [c_uint32, c_uint32, c_int64, c_int, c_uint32, POINTER(c_uint32)]),
         "xrl_debug_host_batches": (c_uint32, [POINTER(c_uint64), c_uint32, c_uint32, c_int, POINTER(c_uint32), c_uint32]),
         "xrl_layer_info": (c_uint32, [c_void_p, c_uint32, POINTER(c_uint64), c_uint32]),
         "xrl_single_layer_cache_clear": (None, []),
@@ -689,6 +690,17 @@ class corelib(object):
                    rb.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(rb)))
         self._check()
         return rb[:n].copy()
+
+    K2_FORMS = ("wave", "list", "reg", "lds", "big")
+
+    def debug_k2_form(self, k, cand_stride, k2_big_min_k=0, stage=0, limited_cands=0):
+        """Host-only: (form, NS) of the per-query top-k launch for a layer that keeps ``k`` of ``cand_stride`` candidates -- a name of
+        ``K2_FORMS`` and the candidate registers per lane of the wave / list form (0 otherwise).  ``stage``: 0 = whole row, 1 = a stage of the
+        bound pruning (``limited_cands``: what a rank-limited stage looks at), 2 = its last stage on the list of unfinished queries."""
+        ns = c_uint32(0)
+        f = int(self.clib_float32.xrl_debug_k2_form(int(k), int(cand_stride), int(k2_big_min_k), int(stage), int(limited_cands), byref(ns)))
+        self._check()
+        return self.K2_FORMS[f], int(ns.value)
 
     def profile_enable(self, c_model, on=True):
         self.clib_float32.xrl_profile_enable(c_void_p(c_model), 1 if on else 0)

@@ -514,6 +514,14 @@ uint32_t xrl_debug_host_batches(const uint64_t* row_ptr, uint32_t rows, uint32_t
     });
 }
 
+int xrl_debug_k2_form(uint32_t k, uint32_t cand_stride, int64_t k2_big_min_k, int stage, uint32_t limited_cands, uint32_t* ns_out) {
+    return guarded_value(-1, [&] {
+        const K2Choice c = k2_form(k, cand_stride, k2_big_min_k, stage, limited_cands);
+        if (ns_out) *ns_out = c.ns;
+        return (int)c.form;
+    });
+}
+
 // every integer option that is a plain store into Model::Options, under the member's own name (include/xrl_abi.h documents the keys)
 #define XRL_OPT(name) {#name, &Model::Options::name}
 static const struct { const char* name; int Model::Options::*field; } kIntOptions[] = {

@@ -13,7 +13,10 @@ namespace xrl {
 // K2: one wavefront per query.  Candidates are scanned in POSITION order; the running top-k list
 // is kept sorted by (value desc, position asc), which is the comparator of sorted_csr
 // (inference.hpp:1265-1273): a later candidate only displaces the current k-th if it is
-// STRICTLY greater, and is inserted after every element that is >= it.
+// STRICTLY greater, and is inserted after every element that is >= it.  "Greater" is a compare of
+// score_key values (xrl_device.h), as in every other form of the top-k: one total order on the
+// fp32 bit patterns, NaN scores included (a float compare would rank a NaN first while the list
+// fills and drop it afterwards).
 // ---------------------------------------------------------------------------------------------
 struct K2Args {
     const uint32_t* chunk_col;
@@ -59,7 +62,8 @@ __global__ void __launch_bounds__(64) k2_topk_reg(K2Args a) {   // k <= 64: lane
     const int lane = threadIdx.x;
     const uint32_t n = a.ncand[q], k = a.k;
     const float* __restrict__ cv = a.cand + q * a.cand_stride;
-    float lv = -INFINITY, th = -INFINITY;
+    float lv = -INFINITY;
+    uint32_t th = 0u;         // key of the current k-th best once the list is full (0: not full; every candidate's key is >= 1)
     uint32_t lp = 0, m = 0;
     constexpr int KB = 4;     // candidate batches (64 each) fetched per iteration: KB loads in flight
     const uint32_t nlast = n ? n - 1 : 0;
@@ -73,19 +77,20 @@ __global__ void __launch_bounds__(64) k2_topk_reg(K2Args a) {   // k <= 64: lane
             const uint32_t p = base + lane;
             const bool valid = p < n;
             const float v = vb[b];
-            unsigned long long mask = __ballot(valid && (m < k || v > th));
+            unsigned long long mask = __ballot(valid && (m < k || score_key(v) > th));
             while (mask) {
                 const int l = __ffsll((long long)mask) - 1;
                 mask &= mask - 1;
                 const float vv = __shfl(v, l);
-                if (m == k && !(vv > th)) continue;
-                const int r = __popcll(__ballot((uint32_t)lane < m && lv >= vv));
+                const uint32_t kv = score_key(vv);
+                if (m == k && !(kv > th)) continue;
+                const int r = __popcll(__ballot((uint32_t)lane < m && score_key(lv) >= kv));
                 const float uv = __shfl_up(lv, 1);
                 const uint32_t up = __shfl_up(lp, 1);
                 if (lane > r) { lv = uv; lp = up; }
                 else if (lane == r) { lv = vv; lp = base + l; }
                 if (m < k) ++m;
-                th = (m == k) ? __shfl(lv, (int)k - 1) : -INFINITY;
+                th = (m == k) ? score_key(__shfl(lv, (int)k - 1)) : 0u;
             }
         }
     }
@@ -104,22 +109,23 @@ __global__ void __launch_bounds__(64) k2_topk_lds(K2Args a) {   // any k that fi
     const int lane = threadIdx.x;
     const uint32_t n = a.ncand[q], k = a.k;
     const float* __restrict__ cv = a.cand + q * a.cand_stride;
-    float th = -INFINITY;
+    uint32_t th = 0u;         // key of the current k-th best once the list is full (0: not full)
     uint32_t m = 0;
     for (uint32_t base = 0; base < n; base += 64) {
         const uint32_t p = base + lane;
         const bool valid = p < n;
         const float v = valid ? cv[p] : 0.f;
-        unsigned long long mask = __ballot(valid && (m < k || v > th));
+        unsigned long long mask = __ballot(valid && (m < k || score_key(v) > th));
         while (mask) {
             const int l = __ffsll((long long)mask) - 1;
             mask &= mask - 1;
             const float vv = __shfl(v, l);
-            if (m == k && !(vv > th)) continue;
+            const uint32_t kv = score_key(vv);
+            if (m == k && !(kv > th)) continue;
             uint32_t r = 0;
             for (uint32_t i0 = 0; i0 < m; i0 += 64) {
                 const uint32_t i = i0 + lane;
-                r += (uint32_t)__popcll(__ballot(i < m && lv[i] >= vv));
+                r += (uint32_t)__popcll(__ballot(i < m && score_key(lv[i]) >= kv));
             }
             const uint32_t e = (m < k) ? m : k - 1;        // elements [r, e) move up by one
             for (uint32_t hi = e; hi > r;) {
@@ -136,7 +142,7 @@ __global__ void __launch_bounds__(64) k2_topk_lds(K2Args a) {   // any k that fi
             if (lane == 0) { lv[r] = vv; lp[r] = base + l; }
             wave_sync_lds();
             if (m < k) ++m;
-            th = (m == k) ? lv[k - 1] : -INFINITY;
+            th = (m == k) ? score_key(lv[k - 1]) : 0u;
         }
     }
     wave_sync_lds();
@@ -247,7 +253,29 @@ __global__ void __launch_bounds__(256) k2_topk_list(K2Args a) {
 
 size_t k2_max_k() { return (160 * 1024) / 8; }
 
-bool k2_wave_path(const LayerPlan& P) { return P.k <= 64 && P.cand_stride <= 64u * 32u; }
+static bool k2_wave_shape(uint32_t k, uint32_t cand_stride) { return k <= 64 && cand_stride <= 64u * 32u; }
+bool k2_wave_path(const LayerPlan& P) { return k2_wave_shape(P.k, P.cand_stride); }
+
+K2Choice k2_form(uint32_t k, uint32_t cand_stride, int64_t big_min_k, int stage, uint32_t limited_cands) {
+    if (k == 0) fail("k2: only_topk / beam_size resolved to 0");
+    if (stage < 0 || stage > 2) fail("k2: stage is 0 (whole row), 1 (bound-pruning stage) or 2 (list of unfinished queries)");
+    const bool wave = k2_wave_shape(k, cand_stride);
+    if (stage != 0 && !wave) fail("k2: bound pruning needs the register top-k path");
+    // beyond the LDS kernel's reach (or forced, tests: k2_big_min_k): the segmented sort of xrl_topk_big.hip
+    if (stage == 0 && (k > k2_max_k() || (big_min_k > 0 && (int64_t)k >= big_min_k))) return {K2_FORM_BIG, 0u};
+    if (wave) {
+        // (a rank-limited selection looks at the first slots' candidates only: registers for that many)
+        const uint32_t ns = ((limited_cands ? std::min(cand_stride, limited_cands) : cand_stride) + 63u) / 64u;
+        static const uint32_t buckets[] = {1, 2, 4, 8, 13, 16, 24, 32};
+        uint32_t nn = 32;
+        for (const uint32_t b : buckets) if (ns <= b) { nn = b; break; }
+        // (the looped instantiation for 16 candidate registers would lose an occupancy step -- 68 VGPRs against 60: those rows keep the
+        //  batch-sized grid and skip on the done flags)
+        return {stage == 2 && nn != 16 ? K2_FORM_LIST : K2_FORM_WAVE, nn};
+    }
+    if (k <= 64) return {K2_FORM_REG, 0u};
+    return {K2_FORM_LDS, 0u};   // (k <= k2_max_k(): a whole-row launch beyond it went to the segmented sort above, a pruning stage was refused)
+}
 
 void launch_k2_topk(const LayerDev& L, const LayerPlan& P, BeamDev prev, const uint32_t* cand_off,
                     const uint32_t* ncand, const float* cand, BeamDev out, hipStream_t s, uint32_t rank_limit, uint32_t limited_cands,
@@ -256,51 +284,46 @@ void launch_k2_topk(const LayerDev& L, const LayerPlan& P, BeamDev prev, const u
     K2Args a;
     a.p_val = prev.val; a.rank_limit = rank_limit; a.done = done; a.skip_done = skip_done; a.xok = xok; a.rest_q = rest_q; a.rest_cnt = rest_cnt;
     if (rest_q && !rest_cnt) fail("k2: the list of unfinished queries needs its count");
-    bool list = rest_q && !done;         // (with done: the launch appends)
+    const bool list = rest_q && !done;         // (with done: the launch appends)
     if (list && !skip_done) fail("k2: the list form also takes the done flags (one instantiation keeps the batch-sized grid)");
     if (list && (rank_limit || !k2_wave_path(P))) fail("k2: the list form serves the last stage of a bound-pruned layer");
     if (done && !xok) fail("k2: bound pruning needs the per-query guard flags");
     a.mult = (P.pp.kind == PP_SIGMOID || P.pp.kind == PP_LP_HINGE) ? 1 : 0;
-    if ((rank_limit || done || skip_done) && !k2_wave_path(P)) fail("k2: bound pruning needs the register top-k path");
     a.chunk_col = L.chunk_col; a.perm_inv = L.perm_inv;
     a.p_idx = prev.idx; a.p_cnt = prev.cnt; a.p_stride = prev.stride;
     a.cand_off = cand_off; a.ncand = ncand; a.cand = cand;
     a.out_idx = out.idx; a.out_val = out.val; a.out_cnt = out.cnt;
     a.nrows = P.nrows; a.beam_in = P.beam_in; a.cand_stride = P.cand_stride; a.k = P.k; a.out_stride = out.stride;
     a.implicit_root = P.implicit_root;
-    if (P.k == 0) fail("k2: only_topk / beam_size resolved to 0");
-    // beyond the LDS kernel's reach (or forced, tests: k2_big_min_k): the segmented sort of xrl_topk_big.hip
-    if (!rank_limit && !done && !skip_done && !list && (P.k > k2_max_k() || (P.tune.k2_big_min_k > 0 && P.k >= (uint32_t)P.tune.k2_big_min_k))) {
+    const int stage = list ? 2 : (rank_limit || done || skip_done) ? 1 : 0;
+    const K2Choice c = k2_form(P.k, P.cand_stride, P.tune.k2_big_min_k, stage, rank_limit ? std::max(1u, limited_cands) : 0u);
+    switch (c.form) {
+    case K2_FORM_BIG:
         launch_k2_topk_big(L, P, prev, cand_off, ncand, cand, out.idx, out.val, out.cnt, out.stride, s);
         return;
-    }
-    if (k2_wave_path(P)) {
-        // (a rank-limited selection looks at the first slots' candidates only: registers for that many)
-        const uint32_t ns = ((rank_limit ? std::min(P.cand_stride, std::max(1u, limited_cands)) : P.cand_stride) + 63u) / 64u;
-        // (the looped instantiation for 16 candidate registers would lose an occupancy step -- 68 VGPRs against 60: those rows keep the
-        //  batch-sized grid and skip on the done flags)
-        if (ns > 13 && ns <= 16) list = false;
-        const dim3 grid(list ? std::min<uint32_t>((P.nrows + 3u) / 4u, 1024u) : (P.nrows + 3u) / 4u), block(256);
-#define XRL_K2_WAVE(NN) do { if (list) hipLaunchKernelGGL(k2_topk_list<NN>, grid, block, 0, s, a); else hipLaunchKernelGGL(k2_topk_wave<NN>, grid, block, 0, s, a); } while (0)
-#define XRL_K2_GRID(NN) hipLaunchKernelGGL(k2_topk_wave<NN>, grid, block, 0, s, a)
-        if (ns <= 1) XRL_K2_WAVE(1);
-        else if (ns <= 2) XRL_K2_WAVE(2);
-        else if (ns <= 4) XRL_K2_WAVE(4);
-        else if (ns <= 8) XRL_K2_WAVE(8);
-        else if (ns <= 13) XRL_K2_WAVE(13);
-        else if (ns <= 16) XRL_K2_GRID(16);
-        else if (ns <= 24) XRL_K2_WAVE(24);
-        else XRL_K2_WAVE(32);
-#undef XRL_K2_GRID
+    case K2_FORM_WAVE:
+    case K2_FORM_LIST: {
+        const bool walk = c.form == K2_FORM_LIST;
+        const dim3 grid(walk ? std::min<uint32_t>((P.nrows + 3u) / 4u, 1024u) : (P.nrows + 3u) / 4u), block(256);
+#define XRL_K2_WAVE(NN) case NN: if (walk) hipLaunchKernelGGL(k2_topk_list<NN>, grid, block, 0, s, a); else hipLaunchKernelGGL(k2_topk_wave<NN>, grid, block, 0, s, a); break
+        switch (c.ns) {
+        XRL_K2_WAVE(1); XRL_K2_WAVE(2); XRL_K2_WAVE(4); XRL_K2_WAVE(8); XRL_K2_WAVE(13); XRL_K2_WAVE(24); XRL_K2_WAVE(32);
+        case 16: hipLaunchKernelGGL(k2_topk_wave<16>, grid, block, 0, s, a); break;     // (never the list form: k2_form)
+        default: fail("k2: no instantiation for " + std::to_string(c.ns) + " candidate registers");
+        }
 #undef XRL_K2_WAVE
-    } else if (P.k <= 64) {
+        break;
+    }
+    case K2_FORM_REG:
         hipLaunchKernelGGL(k2_topk_reg, dim3(P.nrows), dim3(64), 0, s, a);
-    } else {
+        break;
+    case K2_FORM_LDS: {
         const size_t lds = (size_t)P.k * 8;
-        if (P.k > k2_max_k()) fail("k2: only_topk/beam_size " + std::to_string(P.k) + " exceeds the device limit " + std::to_string(k2_max_k()));
         if (lds > 48 * 1024)   // per DEVICE attribute: set on every large launch
             XRL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k2_topk_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(k2_topk_lds, dim3(P.nrows), dim3(64), lds, s, a);
+        break;
+    }
     }
     XRL_LAUNCH_CHECK();
 }

@@ -130,6 +130,12 @@ void launch_k1q(const LayerDev* const* Ls, const LayerPlan* Ps, int n, const Que
                 const uint32_t* qperm = nullptr /* launch slot -> query (launch_sort_queries); every XCD then takes a contiguous range of slots */);
                 // prune_wmax / out_xok: the bound-pruning guard (prune_guard_ok, xrl_device.h); out_xok[q] receives every query's flag
 size_t k2_max_k();
+// Which K2 form serves a launch: pure host arithmetic, launch_k2_topk dispatches on its result (xrl_debug_k2_form exports it for the tests).
+// stage: 0 = the whole candidate row in one launch; 1 = a stage of the bound pruning on the batch-sized grid (rank-limited, sets or skips on the
+// done flags); 2 = its last stage on the list of unfinished queries.  limited_cands: the most candidates a rank-limited stage looks at (0: the row).
+enum K2Form : int { K2_FORM_WAVE = 0, K2_FORM_LIST = 1, K2_FORM_REG = 2, K2_FORM_LDS = 3, K2_FORM_BIG = 4 };
+struct K2Choice { K2Form form; uint32_t ns; };   // ns: candidate registers per lane of the wave / list form (0 otherwise)
+K2Choice k2_form(uint32_t k, uint32_t cand_stride, int64_t big_min_k, int stage, uint32_t limited_cands);
 // xrl_topk_big.hip: top-k sizes beyond k2_max_k() -- one segmented radix sort over the batch's candidate rows (no cap, like the reference's sorted_csr)
 void launch_k2_topk_big(const LayerDev& L, const LayerPlan& P, BeamDev prev, const uint32_t* cand_off, const uint32_t* ncand, const float* cand,
                         uint32_t* out_idx, float* out_val, uint32_t* out_cnt, uint32_t out_stride, hipStream_t s);
