@@ -136,22 +136,22 @@ k0b_remaining_list(const uint32_t* __restrict__ chunk_col, const uint32_t* __res
     }
 }
 
-void launch_k0b_remaining(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, BeamDev prev, const uint32_t* cand_off, const uint32_t* done,
-                          uint32_t first_rank, void* items, uint32_t* n_items, hipStream_t s, uint32_t end_rank, const uint32_t* rest_q, const uint32_t* rest_cnt) {
+void launch_k0b_remaining(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, BeamDev prev, const uint32_t* cand_off, const Stage& st, void* items, hipStream_t s) {
     if (P.nrows == 0) return;
-    if (rest_q) {   // (n_items was zeroed together with *rest_cnt, before the first stage)
-        if (!rest_cnt) fail("k0b: the list of unfinished queries needs its count");
+    const StageLinks& io = st.io; const uint32_t first_rank = st.slot_begin, end_rank = st.slot_end;
+    io.check("k0b", false);
+    if (io.rest_q) {   // (*io.n_items was zeroed together with *io.rest_cnt, before the first stage: StageLinks)
         const uint32_t hi = std::min(P.beam_in, end_rank);
         const uint32_t lpq = std::max(1u, std::min(hi > first_rank ? hi - first_rank : 1u, 64u));   // lanes per listed query: its slots, at most a wavefront
         hipLaunchKernelGGL(k0b_remaining_list, dim3(std::min<uint32_t>((P.nrows + 3u) / 4u, 512u)), dim3(256), 0, s, L.chunk_col, L.ptile, L.tiles, P.nrows, P.beam_in,
-                           first_rank, end_rank, P.cand_stride, prev.idx, prev.val, prev.cnt, prev.stride, cand_off, rest_q, rest_cnt, lpq, static_cast<ItemDesc*>(items),
-                           n_items, X.dense ? nullptr : X.row_ptr + P.row0);
+                           first_rank, end_rank, P.cand_stride, prev.idx, prev.val, prev.cnt, prev.stride, cand_off, io.rest_q, io.rest_cnt, lpq, static_cast<ItemDesc*>(items),
+                           io.n_items, X.dense ? nullptr : X.row_ptr + P.row0);
         XRL_LAUNCH_CHECK();
         return;
     }
-    XRL_HIP(hipMemsetAsync(n_items, 0, 4, s));
+    XRL_HIP(hipMemsetAsync(io.n_items, 0, 4, s));
     hipLaunchKernelGGL(k0b_remaining, dim3((P.nrows + 255) / 256), dim3(256), 0, s, L.chunk_col, L.ptile, L.tiles, P.nrows, P.beam_in, first_rank, end_rank,
-                       P.cand_stride, prev.idx, prev.val, prev.cnt, prev.stride, cand_off, done, static_cast<ItemDesc*>(items), n_items,
+                       P.cand_stride, prev.idx, prev.val, prev.cnt, prev.stride, cand_off, io.done, static_cast<ItemDesc*>(items), io.n_items,
                        X.dense ? nullptr : X.row_ptr + P.row0);
     XRL_LAUNCH_CHECK();
 }

@@ -350,10 +350,10 @@ void launch_k1t(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, cons
     a.wt_bytes = buf ? (uint32_t)L.wt_bytes : 0u;
     if (sel) {
         if (n_items || !k1t_selects(L, P, X)) fail("k1t: the selecting epilogue does not serve this launch");
-        if (!sel->done || !sel->xok) fail("k1t: bound pruning needs the done and the per-query guard flags");
+        sel->io.check("k1t", true);
         a.p_cnt = sel->prev.cnt; a.p_val = sel->prev.val; a.p_stride = sel->prev.stride; a.beam_in = P.beam_in;
-        a.xok = sel->xok; a.perm_inv = L.perm_inv;
-        a.out_idx = sel->out.idx; a.out_val = sel->out.val; a.out_cnt = sel->out.cnt; a.done = sel->done;
+        a.xok = sel->io.xok; a.perm_inv = L.perm_inv;
+        a.out_idx = sel->out.idx; a.out_val = sel->out.val; a.out_cnt = sel->out.cnt; a.done = sel->io.done;
         a.out_stride = sel->out.stride; a.k = P.k;
         a.mult = (P.pp.kind == PP_SIGMOID || P.pp.kind == PP_LP_HINGE) ? 1 : 0;
         if (!items) {
@@ -361,8 +361,7 @@ void launch_k1t(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, cons
             if ((uint64_t)P.nrows * P.cand_stride > 0xFFFFFFFFull) fail("k1t: candidate buffer exceeds 2^32 floats; lower max_batch_rows");
             a.p_idx = sel->prev.idx; a.x_row_ptr = X.row_ptr + P.row0; a.cand_stride = P.cand_stride; a.cand_off = sel->cand_off; a.ncand = sel->ncand;
         }
-        if (sel->rest_q && !sel->rest_cnt) fail("k1t: the list of unfinished queries needs its count");
-        a.rest_q = sel->rest_q; a.rest_cnt = sel->rest_cnt;
+        a.rest_q = sel->io.rest_q; a.rest_cnt = sel->io.rest_cnt;
     }
     const dim3 grid((a.n_vblocks + 3u) / 4u), block(256);
 #define XRL_K1T_L(GG, NN, BB, SS) do { \

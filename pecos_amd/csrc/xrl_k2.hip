@@ -277,26 +277,18 @@ K2Choice k2_form(uint32_t k, uint32_t cand_stride, int64_t big_min_k, int stage,
     return {K2_FORM_LDS, 0u};   // (k <= k2_max_k(): a whole-row launch beyond it went to the segmented sort above, a pruning stage was refused)
 }
 
-void launch_k2_topk(const LayerDev& L, const LayerPlan& P, BeamDev prev, const uint32_t* cand_off,
-                    const uint32_t* ncand, const float* cand, BeamDev out, hipStream_t s, uint32_t rank_limit, uint32_t limited_cands,
-                    uint32_t* done, const uint32_t* skip_done, const uint32_t* xok, uint32_t* rest_q, uint32_t* rest_cnt) {
-    if (P.nrows == 0) return;
-    K2Args a;
-    a.p_val = prev.val; a.rank_limit = rank_limit; a.done = done; a.skip_done = skip_done; a.xok = xok; a.rest_q = rest_q; a.rest_cnt = rest_cnt;
-    if (rest_q && !rest_cnt) fail("k2: the list of unfinished queries needs its count");
-    const bool list = rest_q && !done;         // (with done: the launch appends)
-    if (list && !skip_done) fail("k2: the list form also takes the done flags (one instantiation keeps the batch-sized grid)");
-    if (list && (rank_limit || !k2_wave_path(P))) fail("k2: the list form serves the last stage of a bound-pruned layer");
-    if (done && !xok) fail("k2: bound pruning needs the per-query guard flags");
+namespace {
+// fills what every launch sets and runs the form k2_form names; `a` arrives with its bound-pruning words set (all zero: the whole row)
+void k2_launch(const LayerDev& L, const LayerPlan& P, BeamDev prev, const uint32_t* cand_off, const uint32_t* ncand, const float* cand, BeamDev out,
+               hipStream_t s, K2Args a, int stage, uint32_t limited_cands) {
     a.mult = (P.pp.kind == PP_SIGMOID || P.pp.kind == PP_LP_HINGE) ? 1 : 0;
     a.chunk_col = L.chunk_col; a.perm_inv = L.perm_inv;
-    a.p_idx = prev.idx; a.p_cnt = prev.cnt; a.p_stride = prev.stride;
+    a.p_idx = prev.idx; a.p_cnt = prev.cnt; a.p_stride = prev.stride; a.p_val = prev.val;
     a.cand_off = cand_off; a.ncand = ncand; a.cand = cand;
     a.out_idx = out.idx; a.out_val = out.val; a.out_cnt = out.cnt;
     a.nrows = P.nrows; a.beam_in = P.beam_in; a.cand_stride = P.cand_stride; a.k = P.k; a.out_stride = out.stride;
     a.implicit_root = P.implicit_root;
-    const int stage = list ? 2 : (rank_limit || done || skip_done) ? 1 : 0;
-    const K2Choice c = k2_form(P.k, P.cand_stride, P.tune.k2_big_min_k, stage, rank_limit ? std::max(1u, limited_cands) : 0u);
+    const K2Choice c = k2_form(P.k, P.cand_stride, P.tune.k2_big_min_k, stage, limited_cands);
     switch (c.form) {
     case K2_FORM_BIG:
         launch_k2_topk_big(L, P, prev, cand_off, ncand, cand, out.idx, out.val, out.cnt, out.stride, s);
@@ -326,6 +318,26 @@ void launch_k2_topk(const LayerDev& L, const LayerPlan& P, BeamDev prev, const u
     }
     }
     XRL_LAUNCH_CHECK();
+}
+}  // namespace
+
+void launch_k2_topk(const LayerDev& L, const LayerPlan& P, BeamDev prev, const uint32_t* cand_off,
+                    const uint32_t* ncand, const float* cand, BeamDev out, hipStream_t s) {
+    if (P.nrows != 0) k2_launch(L, P, prev, cand_off, ncand, cand, out, s, K2Args{}, 0, 0u);
+}
+
+void launch_k2_stage(const LayerDev& L, const LayerPlan& P, BeamDev prev, const uint32_t* cand_off,
+                     const uint32_t* ncand, const float* cand, BeamDev out, const Stage& st, hipStream_t s) {
+    if (P.nrows == 0) return;
+    const bool last = st.kind == STAGE_LAST, list = last && st.io.rest_q;
+    st.io.check("k2", !last);
+    if (st.kind == STAGE_MID && st.io.rest_q) fail("k2: a middle stage keeps the batch-sized grid (the list belongs to layers of two stages)");
+    if (list && !k2_wave_path(P)) fail("k2: the list form serves the last stage of a bound-pruned layer");
+    K2Args a{};
+    if (!last) { a.rank_limit = st.slot_end; a.done = st.io.done; a.xok = st.io.xok; }
+    if (st.kind != STAGE_FIRST) a.skip_done = st.io.done;   // (a middle stage skips the queries finished earlier and renews the flags: one buffer serves both)
+    if (st.kind != STAGE_MID) { a.rest_q = st.io.rest_q; a.rest_cnt = st.io.rest_cnt; }   // FIRST (with done) appends, LAST (without) walks the list
+    k2_launch(L, P, prev, cand_off, ncand, cand, out, s, a, list ? 2 : 1, last ? 0u : std::max(1u, st.cands));
 }
 
 }  // namespace xrl

@@ -46,10 +46,26 @@ struct LayerPlan {
 //     16-byte item descriptor per (query, beam slot, tile-in-parent) for K1.
 void launch_k0_prolongate(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, BeamDev prev, uint32_t* cand_off,
                           uint32_t* ncand, void* items, hipStream_t s, uint32_t item_ranks = 0xFFFFFFFFu /* beam slots that get item descriptors */);
-// bound-pruned layers, second phase: items of the beam slots >= first_rank of the queries with done[q] == 0, compact; *n_items = their number
-void launch_k0b_remaining(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, BeamDev prev, const uint32_t* cand_off, const uint32_t* done,
-                          uint32_t first_rank, void* items, uint32_t* n_items, hipStream_t s, uint32_t end_rank = 0xFFFFFFFFu,   // beam slots [first_rank, end_rank)
-                          const uint32_t* rest_q = nullptr, const uint32_t* rest_cnt = nullptr);   // the LIST form: the queries rest_q[0 .. *rest_cnt) instead of every query with done[q] == 0; *n_items is NOT zeroed here
+// ---- Bound-pruned layers run in STAGES of beam slots (route_layer, xrl_predict.cpp).  What the stages hand to each other, per row batch
+// (LaneWs::prune_done / x_ok / prune_cnt / rest_q):
+//   done[q]     the top-k selected so far is final (exact bound, K2Args): FIRST writes it, MID skips on it and renews it, LAST skips on it
+//   xok[q]      the per-query pruning guard (launch_xguard / K1Q's out_xok), read by whatever writes done
+//   *n_items    the number of items launch_k0b_remaining compacted for the stage's sort and K1
+//   rest_q      (nullptr: no list) the queries FIRST left unfinished, *rest_cnt of them in any order: whatever writes done in FIRST appends to it,
+//               the launches of LAST walk it on small fixed grids instead of the batch
+// Who zeroes *n_items: without a list launch_k0b_remaining does (a memset ahead of its kernel); with a list the CALLER zeroes it together with
+// *rest_cnt before the first stage's launches (xrl_predict.cpp, "rest_list") -- the list's count has to be zero by then anyway.
+struct StageLinks {
+    uint32_t* done; const uint32_t* xok; uint32_t* n_items; uint32_t* rest_q; uint32_t* rest_cnt;
+    void check(const char* who, bool writes_done) const {   // the one copy of what K2, K0b and K1T's selecting epilogue ask of them
+        if (rest_q && !rest_cnt) fail(std::string(who) + ": the list of unfinished queries needs its count");
+        if (!done || (writes_done && !xok)) fail(std::string(who) + ": bound pruning needs the done and the per-query guard flags");
+    }
+};
+enum StageKind { STAGE_FIRST, STAGE_MID, STAGE_LAST };
+struct Stage { StageKind kind; uint32_t slot_begin, slot_end /* its beam slots */; uint32_t cands /* FIRST, MID: cand_bound(slot_end), the most candidates K2 ranks */; StageLinks io; };
+// a later stage's items: those of its beam slots of the queries with done[q] == 0 (list form: of the listed queries), compact; *io.n_items = their number
+void launch_k0b_remaining(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, BeamDev prev, const uint32_t* cand_off, const Stage& st, void* items, hipStream_t s);
 bool k2_wave_path(const LayerPlan& P);   // the register top-k kernel serves this layer (what bound pruning needs)
 size_t k0_item_bytes();
 // K1  (query, tile) inner products + bias + post-processor + combine, one item per G lanes.
@@ -68,14 +84,14 @@ size_t qsort_hist_bytes(uint32_t nrows, uint32_t n_keys);
 void launch_step_marker(hipStream_t s);   // XRL_STEP_MARKER=1: an empty kernel at the start of every predict (step boundaries in kernel traces)
 uint32_t sort_max_tiles();
 size_t sort_hist_bytes(uint64_t n_slots, uint32_t n_tiles);
-// K2  per-query top-k with (value desc, position asc) order; maps positions to original child ids.
+// K2  per-query top-k with (value desc, position asc) order; maps positions to original child ids.  The whole candidate row:
 void launch_k2_topk(const LayerDev& L, const LayerPlan& P, BeamDev prev, const uint32_t* cand_off,
-                    const uint32_t* ncand, const float* cand, BeamDev out, hipStream_t s,
-                    uint32_t rank_limit = 0 /* > 0: only the candidates of the first rank_limit beam slots */, uint32_t limited_cands = 0 /* their maximum number */,
-                    uint32_t* done = nullptr /* out: that selection is final (exact bound, see K2Args) */, const uint32_t* skip_done = nullptr /* queries to skip */,
-                    const uint32_t* xok = nullptr /* with done: the per-query pruning guard (launch_xguard / K1Q's out_xok) */,
-                    uint32_t* rest_q = nullptr, uint32_t* rest_cnt = nullptr /* with done: the queries that are NOT done are also appended to rest_q (count *rest_cnt);
-                                                                               without done: the launch ranks the listed queries only (fixed grid) */);
+                    const uint32_t* ncand, const float* cand, BeamDev out, hipStream_t s);
+// ... and one stage of a bound-pruned layer (see K2Args).  FIRST: the candidates of the slots [0, slot_end) only, writes done, appends the unfinished
+// queries to the list if there is one.  MID: the same, skipping the queries that are done and renewing their flags (never with a list).  LAST: every
+// candidate of the queries that are not done -- with a list: of the listed queries, on a fixed grid.
+void launch_k2_stage(const LayerDev& L, const LayerPlan& P, BeamDev prev, const uint32_t* cand_off,
+                     const uint32_t* ncand, const float* cand, BeamDev out, const Stage& st, hipStream_t s);
 // stats: sum over (query, parent) of the reference chunk's algorithmic bytes, and of candidates
 constexpr int kStatsPerLayer = 8;   // [0] reference-chunk bytes, [1] candidates, [2] items, [3] probes, [4] matched rows, [5] their entries,
                                     // [6] tile columns over the items, [7] query features x tile columns over the items
@@ -112,12 +128,11 @@ void launch_tfidf_weight(const uint64_t* row_ptr, const uint32_t* col_idx, const
 int k1_auto_group(const LayerDev& L, const Layer& host, int dense);
 // K1T (xrl_k1t.hip): K1 on the densely held tile rows (LayerDev::wt), accumulators in registers; launch_k1 routes to it when k1t_serves
 bool k1t_serves(const LayerDev& L, const QueriesDev& X);
-// `sel` (option leaf_fuse): the first stage of a bound-pruned layer in ONE launch -- one item per query (beam slot 0, query order), and the
-// kernel's epilogue does what launch_k2_topk(rank_limit = 1, done) would do on the row it has just computed: top-k, child ids, done[q]
-// for every query; the candidate row is stored for the queries that are not done.  P is the whole layer's plan.  items == nullptr (beam_in <= 32):
+// `sel` (option leaf_fuse): the FIRST stage of a bound-pruned layer in ONE launch -- one item per query (beam slot 0, query order), and the
+// kernel's epilogue does what launch_k2_stage would do on the row it has just computed: top-k, child ids, done[q] for every query (and the list);
+// the candidate row is stored for the queries that are not done.  P is the whole layer's plan.  items == nullptr (beam_in <= 32):
 // the launch derives its items from the beam itself and writes cand_off / ncand of the unfinished queries -- no launch_k0_prolongate before it.
-struct K1TSelect { BeamDev prev; const uint32_t* xok; BeamDev out; uint32_t* done; uint32_t* cand_off; uint32_t* ncand;
-                   uint32_t* rest_q = nullptr; uint32_t* rest_cnt = nullptr; };   // rest_q: the queries that are not done are also appended here (count *rest_cnt)
+struct K1TSelect { BeamDev prev, out; uint32_t* cand_off; uint32_t* ncand; StageLinks io; };
 bool k1t_selects(const LayerDev& L, const LayerPlan& P, const QueriesDev& X);   // one tile per parent, 32 lanes per item, k <= kTopkExtractMaxK, a combining layer
 void launch_k1t(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, const void* items, const uint32_t* n_items, float* cand, hipStream_t s,
                 const K1TSelect* sel = nullptr);
@@ -130,7 +145,7 @@ void launch_k1q(const LayerDev* const* Ls, const LayerPlan* Ps, int n, const Que
                 const uint32_t* qperm = nullptr /* launch slot -> query (launch_sort_queries); every XCD then takes a contiguous range of slots */);
                 // prune_wmax / out_xok: the bound-pruning guard (prune_guard_ok, xrl_device.h); out_xok[q] receives every query's flag
 size_t k2_max_k();
-// Which K2 form serves a launch: pure host arithmetic, launch_k2_topk dispatches on its result (xrl_debug_k2_form exports it for the tests).
+// Which K2 form serves a launch: pure host arithmetic, launch_k2_topk / launch_k2_stage dispatch on its result (xrl_debug_k2_form exports it for the tests).
 // stage: 0 = the whole candidate row in one launch; 1 = a stage of the bound pruning on the batch-sized grid (rank-limited, sets or skips on the
 // done flags); 2 = its last stage on the list of unfinished queries.  limited_cands: the most candidates a rank-limited stage looks at (0: the row).
 enum K2Form : int { K2_FORM_WAVE = 0, K2_FORM_LIST = 1, K2_FORM_REG = 2, K2_FORM_LDS = 3, K2_FORM_BIG = 4 };

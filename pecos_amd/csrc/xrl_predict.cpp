@@ -6,8 +6,11 @@
 //
 // predict_device is an outline: resolve_layers (k / beam / candidate stride per layer) -> PruneFeedback::begin_predict -> reserve_scratch
 // (walks the routes once) -> per row batch and layer: route_layer DECIDES (a Route, nothing launched), one of launch_csc_layer /
-// launch_k1g_layer / launch_k1q_group / launch_tile_layer / launch_constrained_layer LAUNCHES what it says (launch_batch).  A new way to run a layer is a
-// Route field + a branch there.
+// launch_k1g_layer / launch_k1q_group / launch_tile_layer / launch_constrained_layer LAUNCHES what it says (launch_batch): the launch functions decide
+// nothing.  A new way to run a layer is a Route field + a branch there.  Bound-pruned layers run in the stages the Route lists: Batch::stage builds
+// the descriptor (Stage, xrl_kernels.h) every launch of a stage takes.  Tile format: launch_tile_layer is launch_tile_unstaged, or launch_tile_first
+// -> rest_form -> launch_tile_later per later stage; rest_form is the one decision taken while a batch is being enqueued (between two equivalent
+// forms of the later stages, from the pruning feedback's item count) -- it launches nothing.
 #include "xrl_predict.h"
 #include "xrl_constrain.h"
 
@@ -45,7 +48,7 @@ struct Route {
     int group;               // tile format: lanes per item
     bool pruned;             // K1G, tile format: exact bound pruning in stages of beam slots
     uint32_t J;              // ... slots [0, J) are the first stage (K1G unpruned: the whole beam)
-    uint32_t stage_end[3]; int n_stage;   // tile format: stage s scores the slots [stage_end[s-1], stage_end[s])
+    uint32_t stage_end[3]; int n_stage;   // pruned: stage s scores the slots [stage_end[s-1], stage_end[s])
     bool fuse, fuse_k0;      // tile format (option leaf_fuse): K1T selects the first stage's top-k itself / derives its items too
     bool sorts_rest;         // tile format (option sort_rest): the later stages run on tile-sorted items, unless the feedback's item count says too few
     bool compact_rest;       // tile format, two stages (option leaf_tail): the first stage lists the unfinished queries, the later stage's launches walk that list
@@ -75,6 +78,18 @@ struct Batch {
         cand_off = u32(lw.cand_off); ncand = u32(lw.ncand); cand = lw.cand.as<float>(); items = lw.items.p; items_sorted = lw.items_sorted.p;
         sort_hist = u32(lw.sort_hist); sort_start = u32(lw.sort_start); blk_start = u32(lw.blk_start); x_ok = u32(lw.x_ok);
         qperm = u32(lw.qperm); qsort_hist = u32(lw.qsort_hist); qsort_start = u32(lw.qsort_start); prune_done = u32(lw.prune_done); prune_cnt = u32(lw.prune_cnt); rest_q = u32(lw.rest_q);
+    }
+    // What the stages of a bound-pruned layer hand to each other.  prune_cnt is two words -- [0] the later stage's item count, [1] the length of rest_q --
+    // and only these two functions know: clear_list zeroes both in one memset, before the first stage (StageLinks, xrl_kernels.h: who zeroes *n_items).
+    StageLinks links(const Route& r) const {
+        StageLinks io{prune_done, x_ok, prune_cnt, nullptr, nullptr};
+        if (r.compact_rest) { io.rest_q = rest_q; io.rest_cnt = prune_cnt + 1; }
+        return io;
+    }
+    void clear_list() { XRL_HIP(hipMemsetAsync(prune_cnt, 0, 8, S)); }
+    Stage stage(const Route& r, int st, const Layer& L) const {   // stage st of r.n_stage
+        const bool last = st == r.n_stage - 1; const uint32_t end = r.stage_end[st];
+        return Stage{st == 0 ? STAGE_FIRST : last ? STAGE_LAST : STAGE_MID, st ? r.stage_end[st - 1] : 0u, end, last ? 0u : (uint32_t)L.cand_bound(end), links(r)};
     }
     bool unstaged(size_t l) const { return l < (size_t)kFbLayers && fb.unstaged[l]; }   // pruning feedback: the layer scores everything in one pass this time
     // (route_layer reads the plan's shape and policy fields only: it is asked about batch sizes, not about a batch)
@@ -193,8 +208,8 @@ Route route_layer(const Batch& b, size_t l, uint64_t nrows) {
         // ---- exact bound pruning (see the tile-format route below): the GEMM over the children of the J best beam parents first,
         //      then a second, tile-sorted GEMM over the remaining slots of the queries whose top-k is not final yet.  J covers about
         //      one candidate register (64 candidates), like K1Q's first stage.
-        r.kind = ROUTE_K1G; r.pruned = opt.prune && boundable;
-        r.J = r.pruned ? k1g_first_slots(L, beam_in, opt.k1g_first) : beam_in;
+        r.kind = ROUTE_K1G; r.pruned = opt.prune && boundable; r.J = r.pruned ? k1g_first_slots(L, beam_in, opt.k1g_first) : beam_in;
+        if (r.pruned) { r.stage_end[0] = r.J; r.stage_end[1] = beam_in; r.n_stage = 2; }
         return r;
     }
     // layers held in the dense row format: the whole layer is one query-stationary kernel (beam in, beam out)
@@ -313,19 +328,19 @@ void launch_constrained_layer(Batch& b, size_t l) {
 void launch_k1g_layer(Batch& b, size_t l, const Route& r) {
     const Layer& L = *b.m.layers[l]; const QueriesDev& X = b.X; hipStream_t S = b.S;
     const LayerPlan P = b.make_plan(l); const BeamDev prev = b.beam_prev(l), out = b.beam_out(l);
-    const uint32_t J = r.J, rest = P.beam_in - J;
     b.need_x_ok();   // once per row batch: which dense query rows are finite (K1G's fast loop needs it on layers with missing cells) + the pruning guard
-    LayerPlan PA = P; PA.beam_in = J;
-    b.timed("k0_prolongate", l, [&] { launch_k0_prolongate(L.dev, P, X, prev, b.cand_off, b.ncand, b.items, S, J); });
-    b.timed("k1_sort_items", l, [&] { launch_sort_items(L.dev, (uint64_t)b.nrows * J * L.max_tiles_per_parent, b.items, b.items_sorted, b.sort_hist, b.sort_start, S); });
+    LayerPlan PA = P; PA.beam_in = r.J;
+    b.timed("k0_prolongate", l, [&] { launch_k0_prolongate(L.dev, P, X, prev, b.cand_off, b.ncand, b.items, S, r.J); });
+    b.timed("k1_sort_items", l, [&] { launch_sort_items(L.dev, (uint64_t)b.nrows * r.J * L.max_tiles_per_parent, b.items, b.items_sorted, b.sort_hist, b.sort_start, S); });
     b.timed("k1g_dense_x", l, [&] { launch_k1g(L.dev, PA, X, b.items_sorted, b.sort_start, b.blk_start, b.x_ok, b.cand, S); });
     if (!r.pruned) { b.timed("k2_topk", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S); }); return; }
-    LayerPlan PB = P; PB.beam_in = rest;
-    b.timed("k2_topk", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S, J, (uint32_t)L.cand_bound(J), b.prune_done, nullptr, b.x_ok); });
-    b.timed("k0b_remaining", l, [&] { launch_k0b_remaining(L.dev, P, X, prev, b.cand_off, b.prune_done, J, b.items, b.prune_cnt, S); });
-    b.timed("k1_sort_items_rest", l, [&] { launch_sort_items(L.dev, (uint64_t)b.nrows * rest * L.max_tiles_per_parent, b.items, b.items_sorted, b.sort_hist, b.sort_start, S, b.prune_cnt); });
+    const Stage first = b.stage(r, 0, L), rest = b.stage(r, 1, L);
+    LayerPlan PB = P; PB.beam_in = rest.slot_end - rest.slot_begin;
+    b.timed("k2_topk", l, [&] { launch_k2_stage(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, first, S); });
+    b.timed("k0b_remaining", l, [&] { launch_k0b_remaining(L.dev, P, X, prev, b.cand_off, rest, b.items, S); });
+    b.timed("k1_sort_items_rest", l, [&] { launch_sort_items(L.dev, (uint64_t)b.nrows * PB.beam_in * L.max_tiles_per_parent, b.items, b.items_sorted, b.sort_hist, b.sort_start, S, rest.io.n_items); });
     b.timed("k1g_dense_x_rest", l, [&] { launch_k1g(L.dev, PB, X, b.items_sorted, b.sort_start, b.blk_start, b.x_ok, b.cand, S); });
-    b.timed("k2_topk_rest", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S, 0, 0, nullptr, b.prune_done); });
+    b.timed("k2_topk_rest", l, [&] { launch_k2_stage(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, rest, S); });
 }
 
 // layers [l, r.last] in one K1Q launch; with r.sorted_last the last one in a launch of its own, after the queries were sorted by the beam it reads
@@ -356,83 +371,99 @@ void launch_k1q_group(Batch& b, size_t l, const Route& r) {
 
 const char* const kK1Name[2][3] = {{"k1_sparse", "k1_sparse_mid", "k1_sparse_rest"}, {"k1_dense", "k1_dense_mid", "k1_dense_rest"}};   // [dense X][first / middle / last stage]
 
-// tile-format layer: K0 -> (sort) -> K1 -> K2 in one pass, or bound-pruned in r.n_stage stages of beam slots
-void launch_tile_layer(Batch& b, size_t l, const Route& r) {
-    Model& m = b.m; const Layer& L = *m.layers[l]; const QueriesDev& X = b.X; hipStream_t S = b.S;
-    const LayerPlan P = b.make_plan(l); const BeamDev prev = b.beam_prev(l), out = b.beam_out(l);
-    const uint32_t beam_in = P.beam_in, nrows = b.nrows, J = r.J;
-    const char* const* k1_name = kK1Name[X.dense ? 1 : 0];
-    double* const stats = b.stats ? b.stats_dev + kStatsPerLayer * l : nullptr;
-    if (!r.pruned) {
-        b.timed("k0_prolongate", l, [&] { launch_k0_prolongate(L.dev, P, X, prev, b.cand_off, b.ncand, b.items, S); });
-        if (r.mode != 0) b.timed("k1_sort_items", l, [&] { launch_sort_items(L.dev, (uint64_t)nrows * beam_in * L.max_tiles_per_parent, b.items, b.items_sorted, b.sort_hist, b.sort_start, S); });
-        if (b.lanes == 2 && b.k1_done) XRL_HIP(hipStreamWaitEvent(S, b.k1_done, 0));   // K1 launches take turns across the lanes
-        LayerPlan PU = P; PU.fb_host = nullptr;   // (an unstaged pass's item count is not a feedback sample: a probe's outcome may be pending)
-        b.timed(k1_name[0], l, [&] { launch_k1(L.dev, PU, X, r.mode == 1 ? b.items_sorted : b.items, r.mode == 1 ? b.sort_start + L.n_tiles : nullptr, b.cand, r.group, S); });
-        if (b.lanes == 2) { b.k1_done = b.next_event(); XRL_HIP(hipEventRecord(b.k1_done, S)); }
-        b.timed("k2_topk", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S); });
-        if (stats) launch_stats(L.dev, P, X, prev, b.ncand, b.items, stats, S);
-        return;
-    }
-    // Every stage: k0b (the unfinished queries' items of its slots) -> sort -> K1 -> K2 over the candidates of all slots scored so far
-    // (+ the done flag for the next stage).  The first one takes its items from K0, or (r.fuse) is one K1T launch that keeps K1's profile
-    // name; the later stages find done / cand_off / ncand / cand (unfinished queries) as K0 -> K1 -> K2 leave them.
-    const uint64_t slots_b = (uint64_t)nrows * (beam_in - J) * L.max_tiles_per_parent;
+// What the passes of a tile-format layer share
+struct TileLayer { size_t l; const Layer& L; LayerPlan P; BeamDev prev, out; const char* const* k1_name; double* stats; };
+
+// tile-format layer in one pass: K0 -> (sort) -> K1 -> K2
+void launch_tile_unstaged(Batch& b, const TileLayer& t, const Route& r) {
+    const Layer& L = t.L; const LayerPlan& P = t.P; const QueriesDev& X = b.X; hipStream_t S = b.S; const size_t l = t.l;
+    b.timed("k0_prolongate", l, [&] { launch_k0_prolongate(L.dev, P, X, t.prev, b.cand_off, b.ncand, b.items, S); });
+    if (r.mode != 0) b.timed("k1_sort_items", l, [&] { launch_sort_items(L.dev, (uint64_t)b.nrows * P.beam_in * L.max_tiles_per_parent, b.items, b.items_sorted, b.sort_hist, b.sort_start, S); });
+    if (b.lanes == 2 && b.k1_done) XRL_HIP(hipStreamWaitEvent(S, b.k1_done, 0));   // K1 launches take turns across the lanes
+    LayerPlan PU = P; PU.fb_host = nullptr;   // (an unstaged pass's item count is not a feedback sample: a probe's outcome may be pending)
+    b.timed(t.k1_name[0], l, [&] { launch_k1(L.dev, PU, X, r.mode == 1 ? b.items_sorted : b.items, r.mode == 1 ? b.sort_start + L.n_tiles : nullptr, b.cand, r.group, S); });
+    if (b.lanes == 2) { b.k1_done = b.next_event(); XRL_HIP(hipEventRecord(b.k1_done, S)); }
+    b.timed("k2_topk", l, [&] { launch_k2_topk(L.dev, P, t.prev, b.cand_off, b.ncand, b.cand, t.out, S); });
+    if (t.stats) launch_stats(L.dev, P, X, t.prev, b.ncand, b.items, t.stats, S);
+}
+
+// The first stage takes its items from K0 (K0 -> K1 -> K2 on its slots, + the done flags and the list for the later stages), or (r.fuse) is one K1T
+// launch that keeps K1's profile name.
+void launch_tile_first(Batch& b, const TileLayer& t, const Route& r, const Stage& st) {
+    const Layer& L = t.L; const LayerPlan& P = t.P; const QueriesDev& X = b.X; hipStream_t S = b.S; const size_t l = t.l;
     b.need_x_ok();
-    // (compact_rest) the later stage's item count and the length of the list of unfinished queries, both zeroed once per layer and batch
-    uint32_t* const rest_q = r.compact_rest ? b.rest_q : nullptr; uint32_t* const rest_cnt = r.compact_rest ? b.prune_cnt + 1 : nullptr;
-    // (a profile slot of its own -- "rest_list", and "rest_list_grid" below: the three later launches keep their names, these say which form ran)
-    if (r.compact_rest) b.timed("rest_list", l, [&] { XRL_HIP(hipMemsetAsync(b.prune_cnt, 0, 8, S)); });
-    if (!r.fuse_k0) b.timed("k0_prolongate", l, [&] { launch_k0_prolongate(L.dev, P, X, prev, b.cand_off, b.ncand, b.items, S, J); });
+    // (a profile slot of its own -- "rest_list", and "rest_list_grid" in the later stage: the three later launches keep their names, these say which form ran)
+    if (st.io.rest_q) b.timed("rest_list", l, [&] { b.clear_list(); });
+    if (!r.fuse_k0) b.timed("k0_prolongate", l, [&] { launch_k0_prolongate(L.dev, P, X, t.prev, b.cand_off, b.ncand, b.items, S, st.slot_end); });
     if (b.lanes == 2 && b.k1_done) XRL_HIP(hipStreamWaitEvent(S, b.k1_done, 0));
     if (r.fuse) {
-        const K1TSelect sel{prev, b.x_ok, out, b.prune_done, b.cand_off, b.ncand, rest_q, rest_cnt};
+        const K1TSelect sel{t.prev, t.out, b.cand_off, b.ncand, st.io};
         b.timed("k1_sparse", l, [&] { launch_k1t(L.dev, P, X, r.fuse_k0 ? nullptr : b.items, nullptr, b.cand, S, &sel); });
     } else {
-        LayerPlan PA = P; PA.beam_in = J;                  // (K1 sizes its grid from beam_in x tiles per parent)
-        b.timed(k1_name[0], l, [&] { launch_k1(L.dev, PA, X, b.items, nullptr, b.cand, r.group, S); });
-        b.timed("k2_topk", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S, J, (uint32_t)L.cand_bound(J), b.prune_done, nullptr, b.x_ok, rest_q, rest_cnt); });
+        LayerPlan PA = P; PA.beam_in = st.slot_end;        // (K1 sizes its grid from beam_in x tiles per parent)
+        b.timed(t.k1_name[0], l, [&] { launch_k1(L.dev, PA, X, b.items, nullptr, b.cand, r.group, S); });
+        b.timed("k2_topk", l, [&] { launch_k2_stage(L.dev, P, t.prev, b.cand_off, b.ncand, b.cand, t.out, st, S); });
     }
-    if (stats) XRL_HIP(hipMemsetAsync(b.items_sorted, 0xFF, slots_b * k0_item_bytes(), S));   // the stats pass walks the whole list: unused slots read as "no tile"
-    bool srt = r.sorts_rest;
-    // ... unless the previous predicts left (almost) nothing for the later stages: four tiny launches of the sort then cost more than
-    // the locality buys (a 61 250-row shard of Amazon-670K: 0.99 -> 0.93 ms per step, profiles/r05_k1q/README.md).  The count is the one the
-    // pruning feedback already samples (the last stage's K1 launch writes it to a host-visible word); results never depend on it.  It is
-    // read HERE, while the batches are being enqueued: the device may have written it since the predict began.
-    if (srt && P.fb_host && b.opt.sort_rest_min > 0) {
-        const uint32_t seen = m.fb.word(fb_items_word((int)l));
+    // the stats pass walks the whole list of the later stage: unused slots read as "no tile"
+    if (t.stats) XRL_HIP(hipMemsetAsync(b.items_sorted, 0xFF, (uint64_t)b.nrows * (P.beam_in - st.slot_end) * L.max_tiles_per_parent * k0_item_bytes(), S));
+}
+
+// Which of two equivalent forms the later stages of a bound-pruned tile-format layer take: decided from the item count the pruning feedback already samples
+// (the last stage's K1 launch writes it to a host-visible word), read while the batch is being enqueued -- after the first stage's launches, the device
+// may have written it since the predict began.  Launches nothing; results never depend on either answer.
+struct RestForm { bool srt; uint32_t list_grid; };   // the items are tile-sorted before K1; > 0: K1 walks the compacted list on a fixed grid of about this many workgroups
+RestForm rest_form(const Batch& b, const TileLayer& t, const Route& r) {
+    const Layer& L = t.L; RestForm f{r.sorts_rest, 0};
+    const uint32_t seen = t.P.fb_host ? b.m.fb.word(fb_items_word((int)t.l)) : kFbPending;
+    // srt, unless the previous predicts left (almost) nothing for the later stages: four tiny launches of the sort then cost more than
+    // the locality buys (a 61 250-row shard of Amazon-670K: 0.99 -> 0.93 ms per step, profiles/r05_k1q/README.md).
+    if (f.srt && t.P.fb_host && b.opt.sort_rest_min > 0) {
         // (measured, Amazon-670K shape, 8192 leaf tiles: 78 k items = 9.5 per tile -- K1 runs 0.295 ms sorted, 0.298 unsorted, the sort costs 0.062;
         //  4.4 M items = 537 per tile on the hard model -- unsorted K1 finds 7 % of its lines in the L2, sorted 94 %: the sort pays once
         //  a tile's lookup words and entries are re-used a few dozen times)
         const uint64_t need = std::max<uint64_t>((uint64_t)b.opt.sort_rest_min, 32ull * L.n_tiles);
-        if (seen != kFbPending && (uint64_t)seen < need) srt = false;
+        if (seen != kFbPending && (uint64_t)seen < need) f.srt = false;
     }
-    if (P.fb_host) m.fb.tile_slots[l] = (uint64_t)nrows * (beam_in - r.stage_end[r.n_stage - 2]) * L.max_tiles_per_parent;
-    for (int st = 1; st < r.n_stage; ++st) {
-        const uint32_t r0 = r.stage_end[st - 1], r1 = r.stage_end[st]; const bool last = st == r.n_stage - 1;
-        LayerPlan PB = P; PB.beam_in = r1 - r0; PB.tune.wpb = 4;   // a later stage's grid is sized for "nothing pruned": mostly empty wavefronts, 4 per workgroup to dispatch fewer groups
-        // (sorted: the compacted list goes where the first phase's items were -- K1 has consumed them -- and is sorted into items_sorted)
-        uint32_t list_grid = 0; bool ran_list = false;
-        if (rest_q) {
-            // K1 on the compacted list: a fixed grid that walks it, when the feedback's last item count says that the list fills a small part of a LARGE
-            // worst-case grid (measured, profiles/r06_leaf.md section 7: Amazon-670K's 78 k items of 4.4 M slots 0.297 -> 0.239 ms with 6144 workgroups;
-            // a 61 250-row shard's 551 k slots 0.053 -> 0.057 ms: not there).  Either kernel is right for any count: results never depend on the choice.
-            const uint64_t slots_s = (uint64_t)nrows * (r1 - r0) * L.max_tiles_per_parent;
-            const uint32_t seen = P.fb_host ? m.fb.word(fb_items_word((int)l)) : kFbPending;
-            if (b.opt.leaf_tail >= 2) list_grid = (uint32_t)b.opt.leaf_tail;
-            else if (seen != kFbPending && slots_s >= (1ull << 21) && (uint64_t)seen * 8u <= slots_s) list_grid = 6144;
-        }
-        b.timed(last ? "k0b_remaining" : "k0b_remaining_mid", l, [&] { launch_k0b_remaining(L.dev, P, X, prev, b.cand_off, b.prune_done, r0, srt ? b.items : b.items_sorted, b.prune_cnt, S, r1, rest_q, rest_cnt); });
-        if (srt) b.timed(last ? "k1_sort_items_rest" : "k1_sort_items_mid", l, [&] { launch_sort_items(L.dev, (uint64_t)nrows * (r1 - r0) * L.max_tiles_per_parent, b.items, b.items_sorted, b.sort_hist, b.sort_start, S, b.prune_cnt); });
-        b.timed(k1_name[last ? 2 : 1], l, [&] { ran_list = launch_k1(L.dev, PB, X, b.items_sorted, srt ? b.sort_start + L.n_tiles : b.prune_cnt, b.cand, r.group, S, list_grid); });
-        if (ran_list && b.named()) b.timed("rest_list_grid", l, [] {});   // (an empty slot: K1 ran its fixed-grid form)
-        if (b.lanes == 2 && last) { b.k1_done = b.next_event(); XRL_HIP(hipEventRecord(b.k1_done, S)); }
-        // (a middle stage selects among the slots scored so far and renews the done flags; queries finished earlier are skipped: one buffer serves both)
-        if (last && rest_q) b.timed("k2_topk_rest", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S, 0, 0, nullptr, b.prune_done, nullptr, rest_q, rest_cnt); });
-        else if (last) b.timed("k2_topk_rest", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S, 0, 0, nullptr, b.prune_done); });
-        else b.timed("k2_topk_mid", l, [&] { launch_k2_topk(L.dev, P, prev, b.cand_off, b.ncand, b.cand, out, S, r1, (uint32_t)L.cand_bound(r1), b.prune_done, b.prune_done, b.x_ok); });
-        if (stats && last) { launch_stats(L.dev, P, X, prev, b.ncand, b.items, stats, S, (uint64_t)nrows * J * L.max_tiles_per_parent); launch_stats(L.dev, PB, X, prev, nullptr, b.items_sorted, stats, S, slots_b); }
+    if (r.compact_rest) {
+        // K1 on the compacted list: a fixed grid that walks it, when the feedback's last item count says that the list fills a small part of a LARGE
+        // worst-case grid (measured, profiles/r06_leaf.md section 7: Amazon-670K's 78 k items of 4.4 M slots 0.297 -> 0.239 ms with 6144 workgroups;
+        // a 61 250-row shard's 551 k slots 0.053 -> 0.057 ms: not there).  Either kernel is right for any count.
+        const uint64_t slots_s = (uint64_t)b.nrows * (r.stage_end[1] - r.stage_end[0]) * L.max_tiles_per_parent;   // (a list: two stages)
+        if (b.opt.leaf_tail >= 2) f.list_grid = (uint32_t)b.opt.leaf_tail;
+        else if (seen != kFbPending && slots_s >= (1ull << 21) && (uint64_t)seen * 8u <= slots_s) f.list_grid = 6144;
     }
+    return f;
+}
+
+// One later stage: k0b (the unfinished queries' items of its slots) -> (sort) -> K1 -> K2 over the candidates of all slots scored so far (a middle
+// stage: + the done flags for the next one).  It finds done / cand_off / ncand / cand (unfinished queries) as the stage before left them.
+void launch_tile_later(Batch& b, const TileLayer& t, const Route& r, const Stage& st, const RestForm& f) {
+    const Layer& L = t.L; const LayerPlan& P = t.P; const QueriesDev& X = b.X; hipStream_t S = b.S; const size_t l = t.l;
+    const bool last = st.kind == STAGE_LAST; const uint64_t mtp = L.max_tiles_per_parent;
+    LayerPlan PB = P; PB.beam_in = st.slot_end - st.slot_begin; PB.tune.wpb = 4;   // a later stage's grid is sized for "nothing pruned": mostly empty wavefronts, 4 per workgroup to dispatch fewer groups
+    // (sorted: the compacted list goes where the first phase's items were -- K1 has consumed them -- and is sorted into items_sorted)
+    bool ran_list = false;
+    b.timed(last ? "k0b_remaining" : "k0b_remaining_mid", l, [&] { launch_k0b_remaining(L.dev, P, X, t.prev, b.cand_off, st, f.srt ? b.items : b.items_sorted, S); });
+    if (f.srt) b.timed(last ? "k1_sort_items_rest" : "k1_sort_items_mid", l, [&] { launch_sort_items(L.dev, (uint64_t)b.nrows * PB.beam_in * mtp, b.items, b.items_sorted, b.sort_hist, b.sort_start, S, st.io.n_items); });
+    b.timed(t.k1_name[last ? 2 : 1], l, [&] { ran_list = launch_k1(L.dev, PB, X, b.items_sorted, f.srt ? b.sort_start + L.n_tiles : st.io.n_items, b.cand, r.group, S, f.list_grid); });
+    if (ran_list && b.named()) b.timed("rest_list_grid", l, [] {});   // (an empty slot: K1 ran its fixed-grid form)
+    if (b.lanes == 2 && last) { b.k1_done = b.next_event(); XRL_HIP(hipEventRecord(b.k1_done, S)); }
+    b.timed(last ? "k2_topk_rest" : "k2_topk_mid", l, [&] { launch_k2_stage(L.dev, P, t.prev, b.cand_off, b.ncand, b.cand, t.out, st, S); });
+    if (t.stats && last) {   // (the stats pass has two stages)
+        launch_stats(L.dev, P, X, t.prev, b.ncand, b.items, t.stats, S, (uint64_t)b.nrows * st.slot_begin * mtp);
+        launch_stats(L.dev, PB, X, t.prev, nullptr, b.items_sorted, t.stats, S, (uint64_t)b.nrows * PB.beam_in * mtp);
+    }
+}
+
+// tile-format layer: one pass, or bound-pruned in r.n_stage stages of beam slots
+void launch_tile_layer(Batch& b, size_t l, const Route& r) {
+    const LayerPlan P = b.make_plan(l);
+    const TileLayer t{l, *b.m.layers[l], P, b.beam_prev(l), b.beam_out(l), kK1Name[b.X.dense ? 1 : 0], b.stats ? b.stats_dev + kStatsPerLayer * l : nullptr};
+    if (!r.pruned) { launch_tile_unstaged(b, t, r); return; }
+    launch_tile_first(b, t, r, b.stage(r, 0, t.L));
+    const RestForm f = rest_form(b, t, r);
+    if (P.fb_host) b.m.fb.tile_slots[l] = (uint64_t)b.nrows * (P.beam_in - r.stage_end[r.n_stage - 2]) * t.L.max_tiles_per_parent;
+    for (int st = 1; st < r.n_stage; ++st) launch_tile_later(b, t, r, b.stage(r, st, t.L), f);
 }
 
 void launch_batch(Batch& b) {   // every layer of the row batch in flight
