@@ -282,6 +282,34 @@ int xrl_ensemble_device(int device, uint32_t n_models, uint32_t rows,
                         uint32_t only_topk /* 0 = all; finish only */,
                         uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride, void* hip_stream, int sync);
 
+/* Metrics on the device (K8): the sums behind precision and recall at 1 .. topk -- smat_util.Metrics.generate(tY, pY, topk)
+ * (pecos/utils/smat_util.py:968-997) -- of ONE fixed-stride result (d_idx u32[rows*stride], d_val f32[rows*stride], d_cnt u32[rows], as
+ * xrl_predict_device and xrl_ensemble_device write it; a count above the stride is read as the stride) against the true labels as a device CSR
+ * pattern: d_true_ptr u64[rows+1], d_true_idx u32[...].  Row r of the call reads d_true_ptr[r] and d_true_ptr[r+1] as ABSOLUTE offsets into
+ * d_true_idx, so a caller evaluates a window of rows by offsetting d_idx / d_val / d_cnt / d_true_ptr and passing d_true_idx as it is.
+ *   order    a row's T = min(count, stride) entries are ranked as the reference's sorted_csr ranks them: value descending, -0.0 tied with
+ *            +0.0, every NaN last, ties by label ascending.  The stored order is not trusted (predict breaks ties by candidate position);
+ *            entries with score exactly 0 are entries.
+ *   match    entry of rank p matches when its label occurs in the true row; cum[p] = matched entries of rank <= p
+ *   carry    positions T <= p < topk carry cum[T-1]; a row with T == 0 adds nothing at all, whatever its true row holds
+ *   sums     d_matched[p] = sum over rows of cum[p] (u64); d_recall_sum[p] = sum over rows of (double)cum[p] / (double)max(n_true, 1), each
+ *            quotient correctly rounded; n_true = d_true_ptr[r+1] - d_true_ptr[r], duplicates included
+ * The call returns the raw sums, not the metrics: they add over row batches and ranks, and prec[p] = matched[p] / rows / (p + 1),
+ * recall[p] = recall_sum[p] / rows.
+ * Preconditions (not checked): the labels of a result row are distinct; every true row is ascending.  Capacity: stride and topk in 1..1024.
+ * Summation order, a function of the inputs only (no atomics; independent of the CU count and the launch order): with R(rows) =
+ * 64 * max(1, ceil(rows / 262144)), block w = rows [w*R, (w+1)*R) is summed in ascending row order from 0.0, then the blocks in ascending w
+ * from 0.0.  For rows <= R(rows) the fp64 sums are therefore the reference's own row-order sums, bit for bit; d_matched is exact always.
+ * The work runs on `hip_stream` of `device` -- NULL is the device's default (null) stream -- with its scratch allocated and freed in stream
+ * order, and the call returns without synchronising when `sync` == 0.  rows == 0 zero-fills both outputs when a GPU is visible and is a
+ * successful no-op otherwise.  Every argument is checked before a GPU is required (messages start with "xrl_metrics_device: "): null
+ * pointers, stride or topk outside 1..1024.  Returns 0 on success, -1 with a message in xrl_last_error otherwise. */
+int xrl_metrics_device(int device, uint32_t rows,
+                       const uint32_t* d_idx, const float* d_val, const uint32_t* d_cnt, uint32_t stride,
+                       const uint64_t* d_true_ptr, const uint32_t* d_true_idx,
+                       uint32_t topk, uint64_t* d_matched /* u64[topk] */, double* d_recall_sum /* f64[topk] */,
+                       void* hip_stream, int sync);
+
 /* predict_on_selected_outputs on the device (K7 + K4): score a given set of labels per query row through the tree, with labels, plan and
  * scores resident in HBM.  The labels arrive in the fixed-stride form xrl_predict_device writes and xrl_ensemble_device reads: row r is
  * d_sel_idx[r*sel_stride ..], d_sel_cnt[r] entries long (NULL = sel_stride each; a count above the stride is read as the stride), in any

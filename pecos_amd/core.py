@@ -235,6 +235,7 @@ class corelib(object):
         "xrl_predict_device_rows": (c_int, [c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int, c_uint32, c_uint32]),
         "xrl_ensemble_device": (c_int, [c_int, c_uint32, c_uint32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint32), c_int,
                                         POINTER(c_float), c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int]),
+        "xrl_metrics_device": (c_int, [c_int, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_int]),
         "xrl_predict_selected_device": (c_int, [c_void_p, c_void_p, c_char_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_int]),
         "xrl_set_output_constraint": (c_int, [c_void_p, c_void_p, c_uint64]),
         "xrl_set_output_constraint_device": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p]),
@@ -624,6 +625,24 @@ class corelib(object):
             self.ENSEMBLE_MODES.get(mode, mode), None if threshold is None else ctypes.byref(c_float(threshold)), only_topk or 0,
             c_void_p(d_out_idx), c_void_p(d_out_val), c_void_p(d_out_cnt), int(out_stride), c_void_p(stream or 0), 1 if sync else 0)
         self._check()
+        return rc
+
+    METRICS_MAX = 1024          # capacity of K8 (xrl_metrics_device): entries per result row, and positions
+
+    def metrics_device(self, device, rows, d_idx, d_val, d_cnt, stride, d_true_ptr, d_true_idx, topk, d_matched, d_recall_sum,
+                       stream=None, sync=True):
+        """K8: the sums behind precision / recall at 1 .. ``topk`` of one fixed-stride result (raw device addresses, row stride ``stride``)
+        against the true labels as a device CSR pattern (``d_true_ptr`` u64 [rows+1], ``d_true_idx`` u32), into ``d_matched`` u64 [topk] and
+        ``d_recall_sum`` f64 [topk].  A stride or topk outside 1..1024 raises ValueError with the library's message."""
+        rc = self.clib_float32.xrl_metrics_device(
+            int(device), int(rows), c_void_p(d_idx), c_void_p(d_val), c_void_p(d_cnt), int(stride), c_void_p(d_true_ptr), c_void_p(d_true_idx),
+            int(topk), c_void_p(d_matched), c_void_p(d_recall_sum), c_void_p(stream or 0), 1 if sync else 0)
+        try:
+            self._check()
+        except RuntimeError as e:
+            if " must be 1.." in str(e):
+                raise ValueError(str(e)) from None
+            raise
         return rc
 
     # ------------------------------------------------------------------ output constraint (xmc/base.py:1796-1824, on the device)

@@ -371,6 +371,41 @@ int xrl_ensemble_device(int device, uint32_t n_models, uint32_t rows, const uint
     });
 }
 
+int xrl_metrics_device(int device, uint32_t rows, const uint32_t* d_idx, const float* d_val, const uint32_t* d_cnt, uint32_t stride,
+                       const uint64_t* d_true_ptr, const uint32_t* d_true_idx, uint32_t topk, uint64_t* d_matched, double* d_recall_sum,
+                       void* hip_stream, int sync) {
+    return guarded_value(-1, [&] {
+        // every argument is checked before a GPU is required
+        const std::string what = "xrl_metrics_device: ";
+        if (!d_idx || !d_val || !d_cnt || !d_true_ptr || !d_true_idx || !d_matched || !d_recall_sum) fail(what + "null argument");
+        if (stride == 0 || stride > kMetricsMax) fail(what + "stride must be 1.." + std::to_string(kMetricsMax) + ", got " + std::to_string(stride));
+        if (topk == 0 || topk > kMetricsMax) fail(what + "topk must be 1.." + std::to_string(kMetricsMax) + ", got " + std::to_string(topk));
+        hipStream_t s = static_cast<hipStream_t>(hip_stream);
+        if (rows == 0) {                                                // no rows: the sums are zero (without a GPU there is nothing to fill)
+            int n = 0;
+            if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return 0;
+            use_device(device);
+            XRL_HIP(hipMemsetAsync(d_matched, 0, (size_t)topk * sizeof(uint64_t), s));
+            XRL_HIP(hipMemsetAsync(d_recall_sum, 0, (size_t)topk * sizeof(double), s));
+            if (sync) XRL_HIP(hipStreamSynchronize(s));
+            return 0;
+        }
+        require_gpu();
+        use_device(device);
+        MetricsArgs A{};
+        A.idx = d_idx; A.val = d_val; A.cnt = d_cnt; A.stride = stride; A.rows = rows; A.topk = topk;
+        A.true_ptr = d_true_ptr; A.true_idx = d_true_idx; A.matched = d_matched; A.recall_sum = d_recall_sum;
+        // the partial sums live and die in stream order: no synchronisation, and concurrent calls do not share them
+        void* scratch = nullptr;
+        XRL_HIP(hipMallocAsync(&scratch, metrics_scratch_bytes(rows, topk), s));
+        try { launch_metrics(A, scratch, s); }
+        catch (...) { (void)hipFreeAsync(scratch, s); throw; }
+        XRL_HIP(hipFreeAsync(scratch, s));
+        if (sync) XRL_HIP(hipStreamSynchronize(s));
+        return 0;
+    });
+}
+
 int xrl_predict_selected_device(void* model, void* queries, const char* post_processor, const uint32_t* d_sel_idx, const uint32_t* d_sel_cnt,
                                 uint32_t sel_stride, uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride,
                                 uint32_t* d_status, void* hip_stream, int sync) {

@@ -121,6 +121,12 @@ __device__ __forceinline__ uint32_t score_key(float v) {
     return k ? k : 1u;                                             // 0 is reserved for "no candidate"
 }
 
+// Ordering key of a score under the python-side sorted_csr (K6's merged scores, K8's predicted scores): larger key first.  score_key
+// orders like the floats do (-0.0 ties with +0.0) but ranks a positive NaN above +inf; sorted_csr's argsort of -value puts every NaN
+// LAST, and NaNs tie with each other (the label decides).  The smallest key score_key gives a number is -inf's 0x007FFFFF, so NaN
+// takes 1; 0 stays "no entry".
+__device__ __forceinline__ uint32_t ensemble_key(float v) { return v != v ? 1u : score_key(v); }
+
 __device__ __forceinline__ uint32_t lanes_below(unsigned long long m) {   // set bits of m below this lane
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }

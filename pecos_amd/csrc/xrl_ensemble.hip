@@ -29,11 +29,6 @@ namespace xrl {
 
 constexpr int kEnsembleWaves = 4;        // wavefronts (= rows) per workgroup
 
-// Ordering key of a merged score: larger key first.  score_key orders like the floats do (-0.0 ties with +0.0) but ranks a positive
-// NaN above +inf; sorted_csr's argsort of -value puts every NaN LAST, and NaNs tie with each other (the label decides).  The
-// smallest key score_key gives a number is -inf's 0x007FFFFF, so NaN takes 1; 0 stays "no entry".
-__device__ __forceinline__ uint32_t ensemble_key(float v) { return v != v ? 1u : score_key(v); }
-
 // mm of rank_average: the largest row length over all models and all rows of the call (smat_util.py:855), row lengths clamped to
 // the stride.  One workgroup, so that the result is a plain store.
 __global__ void __launch_bounds__(1024)

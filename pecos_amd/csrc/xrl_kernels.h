@@ -180,7 +180,22 @@ uint32_t ensemble_slots(uint32_t stride_sum);     // entries per lane (1, 2, 4, 
 // mm_scratch: one device uint32 (rank_average only: the call's largest row length, reduced on `s` ahead of K6)
 void launch_ensemble(const EnsembleArgs& A, uint32_t* mm_scratch, hipStream_t s);
 
-// xrl_select_plan.hip, K7: predict_on_selected_outputs on the device.  One launch plans the reference's tree walk for every row of a batch
+// xrl_metrics.hip, K8: the sums behind precision / recall at 1 .. topk (smat_util.Metrics.generate) of one fixed-stride result against the true
+// labels as a device CSR pattern.  One wavefront per block of R(rows) consecutive rows writes one partial; a one-workgroup kernel adds the
+// partials in block order.  Capacity: stride, topk <= 1024 (one wavefront holds a row).
+constexpr uint32_t kMetricsMax = 1024;
+struct MetricsArgs {
+    const uint32_t* idx; const float* val; const uint32_t* cnt;   // the result; a count above the stride counts as the stride
+    uint32_t stride, rows, topk;
+    const uint64_t* true_ptr; const uint32_t* true_idx;           // [rows + 1] absolute offsets into true_idx; ascending inside a row
+    uint64_t* matched; double* recall_sum;                        // [topk] each
+};
+uint32_t metrics_rows_per_wave(uint32_t rows);    // R(rows) = 64 * max(1, ceil(rows / 262144)): at most 4096 wavefronts, a function of rows only
+uint32_t metrics_waves(uint32_t rows);            // ceil(rows / R(rows))
+size_t metrics_scratch_bytes(uint32_t rows, uint32_t topk);   // the partials: per wavefront u64 matched[topk], then per wavefront f64 recall_sum[topk]
+void launch_metrics(const MetricsArgs& A, void* scratch, hipStream_t s);
+
+// xrl_select_plan.hip, K7: predict_on_selected_outputs on the device. One launch plans the reference's tree walk for every row of a batch
 // (per layer: the row's nodes in the walk's order, the position of every node's parent in the previous layer's list, the count), then one
 // K4 launch per layer scores the planned slots.  Rows are fixed-stride like xrl_predict_device's results; capacity kSelectMaxStride labels.
 constexpr uint32_t kSelectMaxStride = 1024;

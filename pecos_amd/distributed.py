@@ -179,7 +179,7 @@ class ShardedXLinear:
     GPU with inputs resident in HBM.  (tests inject a CPU stand-in to exercise the shard/gather
     algebra under gloo -- the product default has no CPU path.)"""
 
-    def __init__(self, model, group=None, predict_shard_fn=None):
+    def __init__(self, model, group=None, predict_shard_fn=None, metrics_shard_fn=None):
         import torch  # noqa: F401  (first, so the HIP runtime is shared)
         import torch.distributed as dist
         self.model = model
@@ -187,6 +187,12 @@ class ShardedXLinear:
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self._fn = predict_shard_fn or self._predict_shard_gpu
+        self._metrics_fn = metrics_shard_fn or self._metrics_shard_gpu
+
+    def _metrics_shard_gpu(self, result, Y_local, topk):
+        """This rank's sums (K8) from its shard's result in HBM: (matched int64 [topk], recall_sum float64 [topk]) on the device."""
+        from .features import metrics_sums_device
+        return metrics_sums_device(result, Y_local, topk=topk, n_cols=self.model.nr_pred_cols)
 
     def _predict_shard_gpu(self, Xs, beam_size, only_topk, post_processor):
         import torch
@@ -213,6 +219,39 @@ class ShardedXLinear:
         bounds = shard_bounds(X, self.world)
         lo, hi = int(bounds[self.rank]), int(bounds[self.rank + 1])
         return self.predict_shard(take_rows(X, lo, hi), bounds, beam_size, only_topk, post_processor)
+
+    def evaluate(self, X, Y, topk=10, beam_size=None, only_topk=None, post_processor=None):
+        """X, Y: the FULL query and true-label matrices (identical on every rank).  Returns the :class:`pecos_amd.features.Metrics` of the
+        whole prediction on every rank."""
+        bounds = shard_bounds(X, self.world)
+        lo, hi = int(bounds[self.rank]), int(bounds[self.rank + 1])
+        return self.evaluate_shard(take_rows(X, lo, hi), take_rows(Y.tocsr(), lo, hi), bounds, topk, beam_size, only_topk, post_processor)
+
+    def evaluate_shard(self, X_local, Y_local, bounds, topk=10, beam_size=None, only_topk=None, post_processor=None):
+        """Precision / recall at 1 .. ``topk`` of the whole prediction WITHOUT gathering it: every rank predicts its rows (X_local, Y_local:
+        THIS rank's rows; ``bounds`` as for :meth:`predict_shard`), computes its sums where the result lies, and ONE all_reduce(SUM) of
+        topk int64 and topk float64 values joins them -- the sums are additive over rows.  Returns the same Metrics on every rank; ``prec``
+        is exact, ``recall`` an fp64 sum of the ranks' sums in the collective's order."""
+        import torch
+        import torch.distributed as dist
+        from .features import Metrics
+        bounds = np.asarray(bounds, dtype=np.int64)
+        n_local = int(bounds[self.rank + 1] - bounds[self.rank])
+        if X_local.shape[0] != n_local or Y_local.shape[0] != n_local:
+            raise ValueError("X_local / Y_local do not hold the rows bounds assign to this rank")
+        result = self._fn(X_local, beam_size, only_topk, post_processor)
+        matched, recall_sum = self._metrics_fn(result, Y_local, int(topk))
+        if self.world > 1:
+            # one collective for both: the counts ride as fp64 -- exact, every count is at most rows x 1024 < 2^53
+            both = torch.cat([matched.to(torch.float64), recall_sum])
+            if both.is_cuda and dist.get_backend(self.group) == "gloo":
+                host = both.cpu()
+                dist.all_reduce(host, op=dist.ReduceOp.SUM, group=self.group)
+                both = host
+            else:
+                dist.all_reduce(both, op=dist.ReduceOp.SUM, group=self.group)
+            matched, recall_sum = both[: int(topk)].to(torch.int64), both[int(topk):]
+        return Metrics.from_sums(matched.cpu().numpy(), recall_sum.cpu().numpy(), int(bounds[-1]))
 
     def predict_shard(self, X_local, bounds, beam_size=None, only_topk=None, post_processor=None):
         """X_local: THIS rank's rows only, ``bounds``: the global row boundaries (world+1 ints, identical on every rank;

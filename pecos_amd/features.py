@@ -13,7 +13,10 @@
   one model's candidates with another without a host round trip.
 * :func:`ensemble_device` -- the results of several models merged on the device (K6) like ``CsrEnsembler.average`` / ``rank_average`` /
   ``Text2Text.predict``'s tail; :func:`predict_text` and :class:`Text2Text` use it for ensembles that share a device.
+* :func:`metrics_device` / :func:`metrics_sums_device` / :class:`Metrics` -- ``smat_util.Metrics.generate`` (precision and recall at
+  1 .. topk) from a result in HBM (K8): 2 x topk numbers come back instead of the result.
 """
+import collections
 import contextlib
 
 import numpy as np
@@ -302,6 +305,96 @@ def ensemble_device(results, mode="average", threshold=None, only_topk=None, str
         else:
             o_cnt.zero_()
     return o_idx, o_sc, o_cnt
+
+
+class Metrics(collections.namedtuple("Metrics", ["prec", "recall"])):
+    """Precision and recall at 1 .. topk, the pair ``smat_util.Metrics`` holds (smat_util.py:950-997); prints like it: one line per
+    field, the values as percentages with two decimals."""
+
+    __slots__ = ()
+
+    def __str__(self):
+        lines = []
+        for name in self._fields:
+            shown = " ".join("{:4.2f}".format(100 * v) for v in getattr(self, name))
+            lines.append("{:7}= {}".format(name, shown))
+        return "\n".join(lines)
+
+    @classmethod
+    def from_sums(cls, matched, recall_sum, rows):
+        """The metrics of ``rows`` rows from their sums (:func:`metrics_sums_device`, added over batches or ranks): the reference's own last
+        two operations in numpy fp64 -- ``total_matched / rows / arange(1, topk + 1)`` and ``recall / rows``."""
+        matched = np.asarray(matched).astype(np.uint64)          # (int64 tensors hold the u64 bits)
+        recall_sum = np.asarray(recall_sum, dtype=np.float64)
+        rows = int(rows)
+        prec = matched / rows / np.arange(1, len(matched) + 1)
+        return cls(prec=prec, recall=recall_sum / rows)
+
+
+def _true_pattern_device(Y_true, rows, dev, n_cols):
+    """The pattern of the true labels on ``dev``: (crow int64 [rows+1], col int32 [nnz >= 1]) CUDA tensors, ascending inside every row."""
+    import torch
+    if isinstance(Y_true, smat.csr_matrix):
+        if Y_true.shape[0] != rows:
+            raise ValueError(f"Y_true has {Y_true.shape[0]} rows, the result {rows}")
+        if n_cols is not None and Y_true.shape[1] != n_cols:
+            raise ValueError(f"Y_true has {Y_true.shape[1]} columns, expected {n_cols}")
+        if not Y_true.has_sorted_indices:
+            Y_true = Y_true.sorted_indices()                     # a copy: the caller's matrix stays as it is
+        crow = torch.from_numpy(Y_true.indptr.astype(np.int64)).to(dev)
+        col = torch.from_numpy(Y_true.indices.astype(np.uint32).view(np.int32)).to(dev)
+    else:
+        crow, col = Y_true
+        assert crow.is_cuda and col.is_cuda and crow.device == dev and col.device == dev, "metrics: Y_true on another device than the result"
+        assert crow.dtype == torch.int64 and col.dtype == torch.int32 and crow.shape == (rows + 1,)
+        crow, col = crow.contiguous(), col.contiguous()
+    if col.numel() == 0:                                         # (no true label at all: the library still wants an address)
+        col = torch.zeros(1, dtype=torch.int32, device=dev)
+    return crow, col
+
+
+def metrics_sums_device(result, Y_true, topk=10, stream=None, sync=True, n_cols=None):
+    """The sums behind ``smat_util.Metrics.generate(Y_true, Y_pred, topk)`` computed ON THE DEVICE (K8) from a result that is already there.
+
+    result: the ``(labels, scores, counts)`` CUDA triple of :func:`predict_from_torch` / :func:`ensemble_device` (int32 [rows, k], float32
+    [rows, k], int32 [rows]); the labels of a row are distinct, their stored order does not matter (rows are ranked by score descending, NaN
+    last, ties by label ascending, as the reference's ``sorted_csr`` does).  Y_true: a scipy ``csr_matrix`` (checked for its rows and, with
+    ``n_cols``, its columns; indices sorted into a copy when they are not; only the pattern is uploaded) or a ``(crow int64 [rows+1],
+    col int32)`` pair of CUDA tensors on the result's device, ascending inside every row.  Returns CUDA tensors ``(matched int64 [topk] --
+    the u64 bits --, recall_sum float64 [topk])``: additive over row batches and ranks, :meth:`Metrics.from_sums` turns them into the
+    metrics.  Runs on ``stream`` (a raw HIP stream; default: torch's current one); inputs must be ordered on it.  topk and k in 1..1024."""
+    import torch
+    idx, sc, cnt = result
+    dev = idx.device
+    assert idx.is_cuda and sc.device == dev and cnt.device == dev, "metrics: result on different devices"
+    assert idx.dtype == torch.int32 and sc.dtype == torch.float32 and cnt.dtype == torch.int32
+    assert idx.dim() == 2 and idx.shape == sc.shape and cnt.shape == (idx.shape[0],)
+    rows, stride = idx.shape
+    topk = int(topk)
+    for name, v in (("stride", stride), ("topk", topk)):
+        if not 1 <= v <= clib.METRICS_MAX:                          # (the library's own check and words; made here too, since no rows = no call)
+            raise ValueError(f"xrl_metrics_device: {name} must be 1..{clib.METRICS_MAX}, got {v}")
+    idx, sc, cnt = idx.contiguous(), sc.contiguous(), cnt.contiguous()
+    with torch.cuda.device(dev):
+        crow, col = _true_pattern_device(Y_true, rows, dev, n_cols)
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        if stream is not None:
+            torch.cuda.current_stream().synchronize()            # the upload and the contiguous() copies ran on torch's current stream
+        if rows == 0:
+            return torch.zeros(topk, dtype=torch.int64, device=dev), torch.zeros(topk, dtype=torch.float64, device=dev)
+        matched = torch.empty(topk, dtype=torch.int64, device=dev)
+        recall_sum = torch.empty(topk, dtype=torch.float64, device=dev)
+        clib.metrics_device(dev.index, rows, idx.data_ptr(), sc.data_ptr(), cnt.data_ptr(), stride, crow.data_ptr(), col.data_ptr(), topk,
+                            matched.data_ptr(), recall_sum.data_ptr(), stream=s or None, sync=sync)
+    return matched, recall_sum
+
+
+def metrics_device(result, Y_true, topk=10, stream=None, n_cols=None):
+    """``smat_util.Metrics.generate(Y_true, Y_pred, topk)`` for a result in HBM: :func:`metrics_sums_device`, one copy back of 2 x topk
+    numbers, :meth:`Metrics.from_sums`.  ``prec`` is the reference's bit for bit; ``recall`` too up to 64 rows, beyond that within the
+    rounding of a differently ordered fp64 sum (include/xrl_abi.h)."""
+    matched, recall_sum = metrics_sums_device(result, Y_true, topk=topk, stream=stream, sync=True, n_cols=n_cols)
+    return Metrics.from_sums(matched.cpu().numpy(), recall_sum.cpu().numpy(), result[0].shape[0])
 
 
 def _ensemble_on_device(models, ensemble, only_topk, finish=None):
