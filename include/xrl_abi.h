@@ -222,6 +222,30 @@ void c_tfidf_predict_from_file(void* ptr, void* corpus_fname_ptr /* const char* 
 uint32_t xrl_tfidf_nr_features(void* ptr);
 void* xrl_tfidf_predict_device(void* vectorizer, void* model, void* corpus_ptr /* const char** */, const size_t* doc_lens, size_t nr_doc, int threads);
 void xrl_tfidf_counts(void* ptr, void* corpus_ptr /* const char** */, const size_t* doc_lens, size_t nr_doc, int threads, py_sparse_allocator_t alloc);
+/* ---- The tokenizer on the device (K9, csrc/xrl_tokenize.hip): term counts from document bytes that are in HBM ----------------------
+ * d_text: bytes on `model`'s device, any alignment; document i is d_text[d_doc_off[i], d_doc_off[i] + d_doc_len[i]) -- offsets and
+ * lengths apart, so documents may leave gaps, overlap or come in any address order (the host's char** + lengths).  The vectorizer's
+ * tables are copied to the device by the first such call (xrl_tfidf_device_bytes reports their size; c_tfidf_destruct frees them).
+ * The counts are the host tokenizer's (xrl_tfidf_counts) exactly.  Character tokenizers (token_type 20 / 30) decode in parallel, which
+ * equals the host's sequential decode only where every lead byte is followed by the continuation bytes it names (or the buffer end);
+ * a per-document status says where that does not hold, up to the max_length cut: 1 = a continuation byte where a character starts
+ * (the host fails: "the string is not utf-8 encoded!"), 2 = a lead byte followed by too few continuation bytes (the host decodes on
+ * along another path).  Without d_status the lowest such document fails the call (status 2: with the advice to use the host
+ * tokenizer); with d_status [nr_doc] the call reports instead and leaves those rows empty.  nr_doc == 0 gives an empty handle; more
+ * than 2^32 - 1 documents are refused; null arguments are refused before the GPU is touched.  hip_stream NULL = the model's stream.
+ * The calls synchronise the stream; the caller's buffers must be complete when they are made. */
+/* term-count CSR (unweighted; val = counts) as a query handle on model's device; xrl_queries_download reads it */
+void* xrl_tfidf_counts_device(void* vectorizer, void* model, const uint8_t* d_text, const uint64_t* d_doc_off,
+                              const uint64_t* d_doc_len, uint64_t nr_doc, uint32_t* d_status /* nr_doc, may be NULL */, void* hip_stream);
+/* the same + the weighting tail xrl_tfidf_predict_device runs (per-base K5, ensemble norm): X ready for xrl_predict_device */
+void* xrl_tfidf_predict_device_text(void* vectorizer, void* model, const uint8_t* d_text, const uint64_t* d_doc_off,
+                                    const uint64_t* d_doc_len, uint64_t nr_doc, void* hip_stream);
+/* host corpus (char** + lens): tokenizer 0 = xrl_tfidf_predict_device; 1 = packed into the handle's pinned staging, copied once, then as above */
+void* xrl_tfidf_predict_device_tok(void* vectorizer, void* model, void* corpus_ptr /* const char** */, const size_t* doc_lens, size_t nr_doc,
+                                   int tokenizer /* 0 host, 1 device */, int threads);
+uint64_t xrl_tfidf_device_bytes(void* vectorizer, int device);
+/* debug: out[0..n), n <= 4 <- {segments served by the LDS form, by the global form, batches, calls} of the device tokenizer since the load */
+int xrl_debug_tfidf_device_forms(void* vectorizer, uint64_t* out, uint32_t n);
 /* xrl_queries_concat_device_ex for a CSR query handle (e.g. xrl_tfidf_predict_device's): [X of the handle | X_emb] as a NEW handle on the
  * same device (XR-Transformer's concat_model call site, pecos/xmc/xtransformer/model.py:589-603, with both halves device-resident). */
 void* xrl_queries_concat_handle(void* model, void* queries, uint32_t dense_cols, const float* d_emb, int normalize_emb, void* hip_stream);

@@ -230,6 +230,11 @@ class corelib(object):
         "xrl_tfidf_counts": (None, [c_void_p, c_void_p, POINTER(c_uint64), c_uint64, c_int, _alloc_t]),
         "xrl_tfidf_nr_features": (c_uint32, [c_void_p]),
         "xrl_tfidf_predict_device": (c_void_p, [c_void_p, c_void_p, c_void_p, POINTER(c_uint64), c_uint64, c_int]),
+        "xrl_tfidf_counts_device": (c_void_p, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p]),
+        "xrl_tfidf_predict_device_text": (c_void_p, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p]),
+        "xrl_tfidf_predict_device_tok": (c_void_p, [c_void_p, c_void_p, c_void_p, POINTER(c_uint64), c_uint64, c_int, c_int]),
+        "xrl_tfidf_device_bytes": (c_uint64, [c_void_p, c_int]),
+        "xrl_debug_tfidf_device_forms": (c_int, [c_void_p, POINTER(c_uint64), c_uint32]),
         "xrl_queries_concat_handle": (c_void_p, [c_void_p, c_void_p, c_uint32, c_void_p, c_int, c_void_p]),
         "xrl_predict_device": (c_int, [c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int]),
         "xrl_predict_device_rows": (c_int, [c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int, c_uint32, c_uint32]),
@@ -487,13 +492,11 @@ class corelib(object):
             self._lib.c_tfidf_destruct(c_void_p(model))
 
     @staticmethod
-    def _corpus_arrays(corpus):
-        """(char** as a ctypes pointer, byte lengths u64[n], n) for a list of str / bytes.  The documents are packed into ONE bytes object
-        and the pointer table is numpy arithmetic on its address: per-document Python work is what bounds the producer once the native
-        half runs at millions of documents a second, so an all-ASCII corpus is encoded in one go (byte length == len(str))."""
+    def _corpus_joined(corpus):
+        """(the documents of a non-empty list of str / bytes joined into ONE bytes object, their byte lengths u64[n]).  Per-document Python work
+        is what bounds the producer once the native half runs at millions of documents a second, so an all-ASCII corpus is encoded in one
+        go (byte length == len(str))."""
         nr_doc = len(corpus)
-        if nr_doc == 0:
-            return c_void_p(0), np.zeros(1, dtype=np.uint64), 0
         if all(type(d) is str for d in corpus):
             joined = "".join(corpus)
             if joined.isascii():
@@ -507,6 +510,16 @@ class corelib(object):
             enc = [d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in corpus]
             buf = b"".join(enc)
             lens = np.fromiter(map(len, enc), dtype=np.uint64, count=nr_doc)
+        return buf, lens
+
+    @classmethod
+    def _corpus_arrays(cls, corpus):
+        """(char** as a ctypes pointer, byte lengths u64[n], n) for a list of str / bytes: the joined buffer of :meth:`_corpus_joined`, the
+        pointer table numpy arithmetic on its address."""
+        nr_doc = len(corpus)
+        if nr_doc == 0:
+            return c_void_p(0), np.zeros(1, dtype=np.uint64), 0
+        buf, lens = cls._corpus_joined(corpus)
         base = ctypes.cast(c_char_p(buf), c_void_p).value or 0
         ptrs = np.empty(nr_doc, dtype=np.uint64)
         ptrs[0] = base
@@ -515,6 +528,19 @@ class corelib(object):
         arr = ptrs.ctypes.data_as(c_void_p)
         arr._keep = (buf, ptrs)               # the table and the text live as long as the pointer object does
         return arr, lens, nr_doc
+
+    @classmethod
+    def corpus_packed(cls, corpus):
+        """(bytes, offsets u64[n], byte lengths u64[n]) of a list of str / bytes: the device tokenizer's input form (documents back to back
+        in the joined buffer ``_corpus_arrays`` points into)."""
+        nr_doc = len(corpus)
+        if nr_doc == 0:
+            return b"", np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint64)
+        buf, lens = cls._corpus_joined(corpus)
+        off = np.zeros(nr_doc, dtype=np.uint64)
+        if nr_doc > 1:
+            np.cumsum(lens[:-1], out=off[1:])
+        return buf, off, lens
 
     def tfidf_predict(self, model, corpus, buffer_size=0, threads=-1):
         """Vectorize a list of strings, or -- corpus given as a path -- the lines of a text file (pecos/core/base.py:1820-1863)."""
@@ -543,12 +569,48 @@ class corelib(object):
         self._check()
         return v
 
-    def tfidf_predict_device(self, model, c_model, corpus, threads=-1):
-        """Texts -> tf-idf X that STAYS on c_model's device: a query handle for predict_device (free it with queries_free)."""
+    TOKENIZERS = {"host": 0, "device": 1}
+
+    def tfidf_predict_device(self, model, c_model, corpus, threads=-1, tokenizer="host"):
+        """Texts -> tf-idf X that STAYS on c_model's device: a query handle for predict_device (free it with queries_free).
+        tokenizer: "host" (host threads count, the counts are uploaded) or "device" (the text is uploaded, K9 counts)."""
+        if tokenizer not in self.TOKENIZERS:
+            raise ValueError(f"tokenizer={tokenizer!r}: expected 'host' or 'device'")
         arr, lens, nr_doc = self._corpus_arrays(corpus)
-        h = self.clib_float32.xrl_tfidf_predict_device(c_void_p(model), c_void_p(c_model), arr, lens.ctypes.data_as(POINTER(c_uint64)), nr_doc, threads)
+        if tokenizer == "host":
+            h = self.clib_float32.xrl_tfidf_predict_device(c_void_p(model), c_void_p(c_model), arr, lens.ctypes.data_as(POINTER(c_uint64)), nr_doc, threads)
+        else:
+            h = self.clib_float32.xrl_tfidf_predict_device_tok(c_void_p(model), c_void_p(c_model), arr, lens.ctypes.data_as(POINTER(c_uint64)), nr_doc,
+                                                              self.TOKENIZERS[tokenizer], threads)
         self._check()
         return h
+
+    def tfidf_counts_device(self, model, c_model, text_addr, off_addr, len_addr, nr_doc, status_addr=None, stream=None):
+        """Document bytes in HBM (raw device addresses: u8 text, u64 offsets, u64 lengths) -> the term-count CSR as a query handle (K9);
+        ``status_addr`` (u32 [nr_doc]) takes the per-document status instead of an error."""
+        h = self.clib_float32.xrl_tfidf_counts_device(c_void_p(model), c_void_p(c_model), c_void_p(text_addr), c_void_p(off_addr), c_void_p(len_addr), nr_doc,
+                                                     c_void_p(status_addr or 0), c_void_p(stream or 0))
+        self._check()
+        return h
+
+    def tfidf_predict_device_text(self, model, c_model, text_addr, off_addr, len_addr, nr_doc, stream=None):
+        """Document bytes in HBM -> tf-idf X on c_model's device (K9 + the weighting tail): a query handle for predict_device."""
+        h = self.clib_float32.xrl_tfidf_predict_device_text(c_void_p(model), c_void_p(c_model), c_void_p(text_addr), c_void_p(off_addr), c_void_p(len_addr), nr_doc,
+                                                           c_void_p(stream or 0))
+        self._check()
+        return h
+
+    def tfidf_device_bytes(self, model, device):
+        v = int(self.clib_float32.xrl_tfidf_device_bytes(c_void_p(model), int(device)))
+        self._check()
+        return v
+
+    def tfidf_device_forms(self, model):
+        """Debug counters of the device tokenizer since the load: segments served by the LDS form, by the global form, batches, calls."""
+        out = (c_uint64 * 4)()
+        self.clib_float32.xrl_debug_tfidf_device_forms(c_void_p(model), out, 4)
+        self._check()
+        return dict(zip(("lds_segments", "global_segments", "batches", "calls"), (int(v) for v in out)))
 
     def queries_concat_handle(self, c_model, queries, dense_cols, emb_addr, normalize_emb=False, stream=None):
         h = self.clib_float32.xrl_queries_concat_handle(c_void_p(c_model), c_void_p(queries), dense_cols, c_void_p(emb_addr), 1 if normalize_emb else 0, c_void_p(stream or 0))

@@ -49,16 +49,7 @@ unsigned table_bits(size_t n) {
     while (((size_t)1 << bits) < 2 * n + 2) ++bits;
     return bits;
 }
-// the first n (1..8) bytes at p, zero-extended; one unaligned load when 8 bytes are readable
-inline uint64_t load_key(const char* p, size_t n, const char* last) {
-    uint64_t v = 0;
-    if (p + 8 <= last) {
-        std::memcpy(&v, p, 8);
-        return n == 8 ? v : v & ((1ull << (8 * n)) - 1);
-    }
-    std::memcpy(&v, p, n);
-    return v;
-}
+using tft::load_key;   // the first n (1..8) bytes at p, zero-extended; one unaligned load when 8 bytes are readable
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------------- tables
@@ -79,23 +70,6 @@ template struct HugeArray<TokenTable::Short>;
 template struct HugeArray<TokenTable::Long>;
 template struct HugeArray<NgramTable::Packed>;
 template struct HugeArray<NgramTable::Gen>;
-
-uint64_t TokenTable::hash_long(const char* p, size_t n) {
-    uint64_t h = 0x2545F4914F6CDD1Dull ^ n;
-    while (n >= 8) { uint64_t w; std::memcpy(&w, p, 8); h = mix(h ^ w) + 0x9E3779B97F4A7C15ull; p += 8; n -= 8; }
-    if (n) { uint64_t w = 0; std::memcpy(&w, p, n); h = mix(h ^ w) + 0x9E3779B97F4A7C15ull; }
-    return h * 0xD6E8FEB86659FD93ull;
-}
-
-int32_t TokenTable::find_long(const char* p, size_t n, uint64_t h) const {
-    if (l.empty()) return -1;
-    const size_t mask = l.size() - 1;
-    for (size_t slot = (size_t)(h >> l_shift);; slot = (slot + 1) & mask) {
-        const Long& e = l[slot];
-        if (e.len == 0) return -1;
-        if (e.hash == h && e.len == n && std::memcmp(arena.data() + e.off, p, n) == 0) return e.idx;
-    }
-}
 
 void TokenTable::build(const std::vector<std::pair<std::string, int32_t>>& items) {
     size_t ns = 0, nl = 0, bytes = 0;
@@ -132,16 +106,6 @@ void TokenTable::build(const std::vector<std::pair<std::string, int32_t>>& items
                 if (e.hash == h && e.len == t.size() && std::memcmp(arena.data() + e.off, t.data(), t.size()) == 0) { e.idx = it.second; break; }
             }
         }
-    }
-}
-
-uint32_t NgramTable::find_gen(const int32_t* t, int n, uint64_t h) const {
-    if (gen.empty()) return kNone;
-    const size_t mask = gen.size() - 1;
-    for (size_t slot = gen_slot(h);; slot = (slot + 1) & mask) {
-        const Gen& e = gen[slot];
-        if (e.id1 == kNone) return kNone;
-        if (e.hash == h && e.n == (uint32_t)n && std::memcmp(arena.data() + e.off, t, (size_t)n * 4) == 0) return e.id1;
     }
 }
 
@@ -348,7 +312,7 @@ inline void grow(std::vector<int32_t>& v, size_t n) { if (v.size() < n) v.resize
 size_t TfidfBase::count(const char* doc, size_t len, TfidfScratch& S, uint32_t col_off, TfidfOut& O) const {
     const char* p = doc; const char* const last = doc + len;
     // the scratch arrays only ever grow (no per-document clearing): a word document has at most (len + 1) / 2 tokens, a character one len
-    const size_t tok_bound = std::min<size_t>(max_length > 0 ? (size_t)max_length : ~(size_t)0, tok_type == 10 ? (len + 1) / 2 : len);
+    const size_t tok_bound = (size_t)tft::token_bound(tok_type, max_length, len);
     grow(S.key, tok_bound + 1); grow(S.len, tok_bound + 1); grow(S.aux, tok_bound + 1); grow(S.tok, tok_bound + 1); grow(S.run, tok_bound + 2);
     uint64_t* const K = S.key.data(); uint32_t* const L = S.len.data(); uint64_t* const A = S.aux.data();
     size_t T = 0;
@@ -402,11 +366,13 @@ size_t TfidfBase::count(const char* doc, size_t len, TfidfScratch& S, uint32_t c
     }
     // pass 2: token indices (unknown -> -1)
     int32_t* const tok = S.tok.data();
+    const tft::TokenView TV = vocab.view();   // (the views once per document: the probe loops read their fields from registers)
     for (size_t i = 0; i < T; ++i)
-        tok[i] = L[i] <= 8 ? vocab.find_short(K[i], L[i], (size_t)A[i]) : vocab.find_long(doc + A[i], L[i], K[i]);
+        tok[i] = L[i] <= 8 ? tft::find_short(TV, K[i], L[i], (size_t)A[i]) : tft::find_long(TV, doc + A[i], L[i], K[i]);
     // run[i] = tokens in a row from i that the model's n-grams name at all (0 <= index <= max_tok): an n-gram with any other token in it can
     // only be a feature through the general table, and only when the model file names negative token indices
     const NgramTable& G = features;
+    const tft::NgramView GV = G.view();
     int32_t* const run = S.run.data();
     run[T] = 0;
     for (size_t i = T; i-- > 0;) run[i] = (tok[i] < 0 || tok[i] > G.max_tok) ? 0 : run[i + 1] + 1;
@@ -429,8 +395,8 @@ size_t TfidfBase::count(const char* doc, size_t len, TfidfScratch& S, uint32_t c
                 const int32_t t = tok[i];
                 uint32_t id1 = NgramTable::kNone;
                 if (t >= 0 && (size_t)t < U) id1 = uni[t];
-                else if (t >= 0) { if (in_packed && t <= G.max_tok) { const uint64_t k = (uint64_t)(uint32_t)t + 1u; id1 = G.find_packed(k, G.packed_slot(k)); } }
-                else if (in_gen) id1 = G.find_gen(tok + i, 1, NgramTable::gen_hash(tok + i, 1));
+                else if (t >= 0) { if (in_packed && t <= G.max_tok) { const uint64_t k = (uint64_t)(uint32_t)t + 1u; id1 = tft::find_packed(GV, k, G.packed_slot(k)); } }
+                else if (in_gen) id1 = tft::find_gen(GV, tok + i, 1, NgramTable::gen_hash(tok + i, 1));
                 F[nf] = id1 - 1; nf += id1 != 0;
             }
             continue;
@@ -448,7 +414,7 @@ size_t TfidfBase::count(const char* doc, size_t len, TfidfScratch& S, uint32_t c
             }
             for (size_t i = 0; i < cnt; ++i) {
                 if (run[i] < n) continue;
-                const uint32_t id1 = G.find_packed(K[i], G.packed_slot(K[i]));
+                const uint32_t id1 = tft::find_packed(GV, K[i], G.packed_slot(K[i]));
                 F[nf] = id1 - 1; nf += id1 != 0;
             }
         }
@@ -463,7 +429,7 @@ size_t TfidfBase::count(const char* doc, size_t len, TfidfScratch& S, uint32_t c
             }
             for (size_t i = 0; i < cnt; ++i) {
                 if (!wanted(i)) continue;
-                const uint32_t id1 = G.find_gen(tok + i, n, K[i]);
+                const uint32_t id1 = tft::find_gen(GV, tok + i, n, K[i]);
                 F[nf] = id1 - 1; nf += id1 != 0;
             }
         }

@@ -2,6 +2,8 @@
 // tokenizer, :707-745 model files, :775-822 get_sorted_feature, :1212-1466 ensemble) split where the hardware suggests: tokenisation and
 // the n-gram -> feature lookup are string work and run on host threads; their output -- a CSR of term COUNTS -- goes to the device
 // once, and the weighting / normalisation (K5, xrl_features.hip) leaves X in HBM for the beam search.  No D2H / H2D of X.
+// (The same counts can be made on the device from the document bytes: K9, xrl_tokenize.hip, over copies of these tables; the lookups both
+// halves use are stated once, in xrl_tfidf_tables.h.)
 //
 // The host half is the slowest stage of text -> labels by two orders of magnitude (10^5..10^6 documents/s against the beam search's
 // 10^7..10^8 queries/s), so its containers are built for the lookup loop rather than for generality: flat open-addressing tables with the
@@ -15,6 +17,7 @@
 #include <vector>
 
 #include "xrl_common.h"
+#include "xrl_tfidf_tables.h"
 
 namespace xrl {
 
@@ -38,10 +41,10 @@ template <class T> struct HugeArray {
     const T& operator[](size_t i) const { return p[i]; }
 };
 
-// token bytes -> token index (tokenizer/vocab.txt)
+// token bytes -> token index (tokenizer/vocab.txt).  The hashing, slot and probe functions are xrl_tfidf_tables.h's, shared with the device.
 struct TokenTable {
-    struct Short { uint64_t key; uint32_t len; int32_t idx; };                 // tokens of 1..8 bytes: the bytes themselves, zero-extended; len 0 = empty slot
-    struct Long { uint64_t hash; uint32_t off, len; int32_t idx; uint32_t pad; };   // longer tokens: hash, bytes in `arena`
+    using Short = tft::ShortEntry;                                             // tokens of 1..8 bytes: the bytes themselves, zero-extended; len 0 = empty slot
+    using Long = tft::LongEntry;                                               // longer tokens: hash, bytes in `arena`
     HugeArray<Short> s;
     HugeArray<Long> l;
     std::string arena;
@@ -49,18 +52,17 @@ struct TokenTable {
     size_t n_short = 0, n_long = 0;
 
     void build(const std::vector<std::pair<std::string, int32_t>>& items);     // later duplicates overwrite earlier ones (the reference's map assignment)
-    static inline uint64_t mix(uint64_t x) { x *= 0x9E3779B97F4A7C15ull; return x ^ (x >> 29); }
-    static uint64_t hash_long(const char* p, size_t n);
-    inline size_t short_slot(uint64_t key, uint32_t len) const { return (size_t)(mix(key ^ ((uint64_t)len << 56) ^ 0x5bd1e995u) * 0xD6E8FEB86659FD93ull >> s_shift); }
-    inline int32_t find_short(uint64_t key, uint32_t len, size_t slot) const {
-        const size_t mask = s.size() - 1;
-        for (;; slot = (slot + 1) & mask) {
-            const Short& e = s[slot];
-            if (e.len == 0) return -1;
-            if (e.key == key && e.len == len) return e.idx;
-        }
+    tft::TokenView view() const {
+        tft::TokenView v;
+        v.s = s.data(); v.l = l.empty() ? nullptr : l.data(); v.arena = arena.data();
+        v.s_mask = s.size() - 1; v.l_mask = l.empty() ? 0 : l.size() - 1; v.s_shift = s_shift; v.l_shift = l_shift;
+        return v;
     }
-    int32_t find_long(const char* p, size_t n, uint64_t h) const;
+    static inline uint64_t mix(uint64_t x) { return tft::mix(x); }
+    static inline uint64_t hash_long(const char* p, size_t n) { return tft::hash_long(p, n); }
+    inline size_t short_slot(uint64_t key, uint32_t len) const { return tft::short_slot(s_shift, key, len); }
+    inline int32_t find_short(uint64_t key, uint32_t len, size_t slot) const { return tft::find_short(view(), key, len, slot); }
+    inline int32_t find_long(const char* p, size_t n, uint64_t h) const { return tft::find_long(view(), p, n, h); }
 };
 
 // n-gram of token indices -> feature id (vectorizer/tfidf-model.txt).  Three homes, by what the key needs:
@@ -69,11 +71,11 @@ struct TokenTable {
 //            EVERY bigram, and e.g. up to 9-grams of a 100-character vocabulary or 4-grams of a 60k-word one -- key compared inline
 //   gen      the rest (longer n-grams, n-grams naming the unknown token -1): hash + token ids in an arena
 struct NgramTable {
-    static constexpr uint32_t kNone = 0;                                       // stored ids are feature id + 1
+    static constexpr uint32_t kNone = tft::kNone;                              // stored ids are feature id + 1
     std::vector<uint32_t> uni;
-    struct Packed { uint64_t key; uint32_t id1; uint32_t pad; };
+    using Packed = tft::PackedEntry;
     HugeArray<Packed> packed;
-    struct Gen { uint64_t hash; uint32_t off, n, id1, pad; };
+    using Gen = tft::GenEntry;
     HugeArray<Gen> gen;
     std::vector<int32_t> arena;
     unsigned p_shift = 63, g_shift = 63;
@@ -86,29 +88,23 @@ struct NgramTable {
     int max_n = 0;
 
     void build(const std::vector<int32_t>& flat, const std::vector<uint64_t>& off, const std::vector<uint32_t>& ids, size_t vocab_hint);
-    static inline uint64_t mix(uint64_t x) { x *= 0x9E3779B97F4A7C15ull; return x ^ (x >> 29); }
-    static inline uint64_t n_bit(int n) { return 1ull << (n < 63 ? n : 63); }
-    inline uint64_t pack(const int32_t* t, int n) const {
-        uint64_t k = 0;
-        for (int i = 0; i < n; ++i) k |= (uint64_t)((uint32_t)t[i] + 1u) << (pack_bits * (unsigned)i);
-        return k;
+    tft::NgramView view() const {
+        tft::NgramView v;
+        v.uni = uni.data(); v.uni_size = uni.size();
+        v.packed = packed.empty() ? nullptr : packed.data(); v.gen = gen.empty() ? nullptr : gen.data(); v.arena = arena.data();
+        v.p_mask = packed.empty() ? 0 : packed.size() - 1; v.g_mask = gen.empty() ? 0 : gen.size() - 1; v.p_shift = p_shift; v.g_shift = g_shift;
+        v.max_tok = max_tok; v.pack_bits = pack_bits; v.pack_max_n = pack_max_n;
+        v.packed_n_mask = packed_n_mask; v.gen_n_mask = gen_n_mask; v.negative_keys = negative_keys; v.max_n = max_n;
+        return v;
     }
-    inline size_t packed_slot(uint64_t key) const { return (size_t)(mix(key) * 0xD6E8FEB86659FD93ull >> p_shift); }
-    static inline uint64_t gen_hash(const int32_t* t, int n) {
-        uint64_t h = 0x2545F4914F6CDD1Dull ^ (uint64_t)n;
-        for (int i = 0; i < n; ++i) h = mix(h ^ (uint32_t)t[i]) + 0x9E3779B97F4A7C15ull;
-        return h * 0xD6E8FEB86659FD93ull;
-    }
-    inline size_t gen_slot(uint64_t h) const { return (size_t)(h >> g_shift); }
-    inline uint32_t find_packed(uint64_t key, size_t slot) const {
-        const size_t mask = packed.size() - 1;
-        for (;; slot = (slot + 1) & mask) {
-            const Packed& e = packed[slot];
-            if (e.id1 == kNone) return kNone;
-            if (e.key == key) return e.id1;
-        }
-    }
-    uint32_t find_gen(const int32_t* t, int n, uint64_t h) const;
+    static inline uint64_t mix(uint64_t x) { return tft::mix(x); }
+    static inline uint64_t n_bit(int n) { return tft::n_bit(n); }
+    inline uint64_t pack(const int32_t* t, int n) const { return tft::pack(pack_bits, t, n); }
+    inline size_t packed_slot(uint64_t key) const { return tft::packed_slot(p_shift, key); }
+    static inline uint64_t gen_hash(const int32_t* t, int n) { return tft::gen_hash(t, n); }
+    inline size_t gen_slot(uint64_t h) const { return tft::gen_slot(g_shift, h); }
+    inline uint32_t find_packed(uint64_t key, size_t slot) const { return tft::find_packed(view(), key, slot); }
+    inline uint32_t find_gen(const int32_t* t, int n, uint64_t h) const { return tft::find_gen(view(), t, n, h); }
 };
 
 // per-thread scratch of the counting loop

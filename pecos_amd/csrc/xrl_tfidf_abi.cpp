@@ -6,12 +6,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <thread>
 
 #include "xrl_abi_common.h"
 #include "xrl_tfidf.h"
+#include "xrl_tokenize.h"
 
 using namespace xrl;
 
@@ -68,14 +70,84 @@ struct TfidfHandle {
         if (!stream) { XRL_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)); stream_device = device; }
         return stream;
     }
-    ~TfidfHandle() { if (stream) { (void)hipSetDevice(stream_device); (void)hipStreamDestroy(stream); } }
+    // The device tokenizer's tables (K9): a copy of every base vectorizer's s, l, token arena, uni, packed, gen and n-gram arena in HBM with
+    // their views, built under dev_mu by the first device-tokenizer call on a device and kept until the handle goes.
+    struct DeviceTables { std::vector<DevBuf> bufs; std::vector<TokBase> bases; uint64_t bytes = 0; };
+    mutable std::mutex dev_mu;
+    mutable std::map<int, std::unique_ptr<DeviceTables>> dev_tables;
+    mutable std::atomic<uint64_t> forms[4] = {};    // segments served by the LDS form, by the global form; batches; calls (xrl_debug_tfidf_device_forms)
+    const DeviceTables& tables_on(int device) const {
+        std::lock_guard<std::mutex> g(dev_mu);
+        auto it = dev_tables.find(device);
+        if (it != dev_tables.end()) return *it->second;
+        auto T = std::make_unique<DeviceTables>();
+        auto put = [&](const void* src, size_t bytes) -> const void* {
+            if (!bytes) return nullptr;
+            T->bufs.emplace_back();
+            T->bufs.back().upload_raw(src, bytes);
+            T->bytes += bytes;
+            return T->bufs.back().p;
+        };
+        uint32_t col_off = 0;
+        for (const TfidfBase& B : v.base) {
+            TokBase D;
+            D.tv = B.vocab.view(); D.gv = B.features.view();
+            D.tv.s = static_cast<const tft::ShortEntry*>(put(B.vocab.s.data(), B.vocab.s.size() * sizeof(tft::ShortEntry)));
+            D.tv.l = static_cast<const tft::LongEntry*>(put(B.vocab.l.data(), B.vocab.l.size() * sizeof(tft::LongEntry)));
+            D.tv.arena = static_cast<const char*>(put(B.vocab.arena.data(), B.vocab.arena.size()));
+            D.gv.uni = static_cast<const uint32_t*>(put(B.features.uni.data(), B.features.uni.size() * 4));
+            D.gv.packed = static_cast<const tft::PackedEntry*>(put(B.features.packed.data(), B.features.packed.size() * sizeof(tft::PackedEntry)));
+            D.gv.gen = static_cast<const tft::GenEntry*>(put(B.features.gen.data(), B.features.gen.size() * sizeof(tft::GenEntry)));
+            D.gv.arena = static_cast<const int32_t*>(put(B.features.arena.data(), B.features.arena.size() * 4));
+            D.tok_type = B.tok_type; D.min_ngram = B.min_ngram; D.max_ngram = B.max_ngram; D.max_length = B.max_length;
+            D.col_off = col_off; col_off += B.nr_features;
+            T->bases.push_back(D);
+        }
+        return *(dev_tables[device] = std::move(T));
+    }
+    ~TfidfHandle() {
+        if (stream) { (void)hipSetDevice(stream_device); (void)hipStreamDestroy(stream); }
+        for (auto& kv : dev_tables) { (void)hipSetDevice(kv.first); kv.second.reset(); }   // (freed with their device set)
+    }
 };
+
+// The weighting tail both count forms share: q holds the term counts (idx, val) of the segments d_seg points at (h_seg: the same on the
+// host when the host counted; nullptr: an ensemble's row pointer is gathered on the device) -> per-base K5, the ensemble's norm, one synchronise.
+void tfidf_weight_counts(const TfidfHandle& H, Queries* q, DevBuf& d_seg, const std::vector<uint64_t>* h_seg, uint32_t rows, uint64_t nnz, int device, hipStream_t s) {
+    const TfidfVectorizer& V = H.v;
+    const uint32_t nb = (uint32_t)V.base.size();
+    DevBuf d_idf, d_err;
+    d_idf.upload(H.idf_all);
+    d_err.reserve(4); XRL_HIP(hipMemsetAsync(d_err.p, 0, 4, s));
+    for (uint32_t b = 0; b < nb; ++b) {
+        const TfidfBase& B = V.base[b];
+        launch_tfidf_weight(d_seg.as<uint64_t>(), q->idx.as<uint32_t>(), q->val.as<float>(), B.use_idf ? d_idf.as<float>() : nullptr, rows, V.nr_features,
+                            B.binary ? 1 : 0, B.sublinear_tf ? 1 : 0, B.norm_p, q->val.as<float>(), s, nb, b, d_err.as<uint32_t>());
+    }
+    // whole rows: the hstacked CSR's row pointer; the ensemble's normalisation (Vectorizer::predict, tfidf.hpp:1405-1430)
+    if (nb == 1) q->ptr = std::move(d_seg);
+    else if (h_seg) {
+        std::vector<uint64_t> row_ptr((size_t)rows + 1);
+        for (size_t r = 0; r <= rows; ++r) row_ptr[r] = (*h_seg)[r * nb];
+        q->ptr.upload(row_ptr);
+    } else {
+        q->ptr.reserve(((size_t)rows + 1) * 8);
+        launch_seg_to_row_ptr(d_seg.as<uint64_t>(), nb, rows, q->ptr.as<uint64_t>(), s);
+    }
+    if (nb > 1 || V.norm_p != V.base[0].norm_p)
+        launch_tfidf_weight(q->ptr.as<uint64_t>(), q->idx.as<uint32_t>(), q->val.as<float>(), nullptr, rows, V.nr_features, 0, 0, V.norm_p, q->val.as<float>(), s);
+    uint32_t err = 0;
+    XRL_HIP(hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, s));
+    XRL_HIP(hipStreamSynchronize(s));
+    if (err) fail("tfidf: a feature id outside the model's feature range");
+    set_own_csr(*q, device, rows, V.nr_features, nnz);
+}
 
 // texts -> term counts (host threads, into pinned staging) -> device -> weighting + normalisation (K5): a query handle that owns its three arrays
 std::unique_ptr<Queries> tfidf_to_device(const TfidfHandle& H, const char* const* corpus, const size_t* doc_lens, size_t nr_doc, int threads, int device, hipStream_t s) {
     if (nr_doc > 0xFFFFFFFFull) fail("tfidf: too many documents");
     const TfidfVectorizer& V = H.v;
-    const uint32_t nb = (uint32_t)V.base.size(), rows = (uint32_t)nr_doc;
+    const uint32_t rows = (uint32_t)nr_doc;
     use_device(device);
     std::lock_guard<std::mutex> stage_lock(H.stage.mu);          // held until the stream has consumed the staging buffer (the synchronize below)
     if (!s) s = H.stream_on(device);                             // the handle's pooled stream, taken under the staging lock
@@ -87,34 +159,43 @@ std::unique_ptr<Queries> tfidf_to_device(const TfidfHandle& H, const char* const
         nnz = n;
     });
     auto q = std::make_unique<Queries>();
-    DevBuf d_seg, d_idf, d_err;
+    DevBuf d_seg;
     d_seg.upload(seg_ptr);
     q->idx.reserve((size_t)nnz * 4); q->val.reserve((size_t)nnz * 4);
     if (nnz) {
         XRL_HIP(hipMemcpyAsync(q->idx.p, h_col, (size_t)nnz * 4, hipMemcpyHostToDevice, s));
         XRL_HIP(hipMemcpyAsync(q->val.p, h_cnt, (size_t)nnz * 4, hipMemcpyHostToDevice, s));
     }
-    d_idf.upload(H.idf_all);
-    d_err.reserve(4); XRL_HIP(hipMemsetAsync(d_err.p, 0, 4, s));
-    for (uint32_t b = 0; b < nb; ++b) {
-        const TfidfBase& B = V.base[b];
-        launch_tfidf_weight(d_seg.as<uint64_t>(), q->idx.as<uint32_t>(), q->val.as<float>(), B.use_idf ? d_idf.as<float>() : nullptr, rows, V.nr_features,
-                            B.binary ? 1 : 0, B.sublinear_tf ? 1 : 0, B.norm_p, q->val.as<float>(), s, nb, b, d_err.as<uint32_t>());
-    }
-    // whole rows: the hstacked CSR's row pointer; the ensemble's normalisation (Vectorizer::predict, tfidf.hpp:1405-1430)
-    if (nb == 1) q->ptr = std::move(d_seg);
-    else {
-        std::vector<uint64_t> row_ptr((size_t)rows + 1);
-        for (size_t r = 0; r <= rows; ++r) row_ptr[r] = seg_ptr[r * nb];
-        q->ptr.upload(row_ptr);
-    }
-    if (nb > 1 || V.norm_p != V.base[0].norm_p)
-        launch_tfidf_weight(q->ptr.as<uint64_t>(), q->idx.as<uint32_t>(), q->val.as<float>(), nullptr, rows, V.nr_features, 0, 0, V.norm_p, q->val.as<float>(), s);
-    uint32_t err = 0;
-    XRL_HIP(hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, s));
-    XRL_HIP(hipStreamSynchronize(s));
-    if (err) fail("tfidf: a feature id outside the model's feature range");
-    set_own_csr(*q, device, rows, V.nr_features, nnz);
+    tfidf_weight_counts(H, q.get(), d_seg, &seg_ptr, rows, nnz, device, s);
+    return q;
+}
+
+// Texts in HBM -> term counts on the device (K9), synchronised.  A caller's d_status takes every document's status and no status fails
+// the call; without one the lowest bad document fails it, in the host tokenizer's words where the host fails too.
+void tfidf_count_on_device(const TfidfHandle& H, const uint8_t* d_text, const uint64_t* d_doc_off, const uint64_t* d_doc_len, const uint64_t* h_doc_len,
+                           uint64_t nr_doc, uint32_t* d_status, int device, hipStream_t s, TokCounts& C) {
+    if (nr_doc > 0xFFFFFFFFull) fail("tfidf: too many documents");
+    const TfidfHandle::DeviceTables& T = H.tables_on(device);
+    DevBuf own_status;
+    const bool report = d_status != nullptr;
+    if (!report) { own_status.reserve(nr_doc * 4); d_status = own_status.as<uint32_t>(); }
+    tokenize_count_device(T.bases, d_text, d_doc_off, d_doc_len, h_doc_len, nr_doc, d_status, s, C);
+    H.forms[0] += C.lds_segments; H.forms[1] += C.global_segments; H.forms[2] += C.batches; H.forms[3] += 1;
+    if (report) return;
+    if (C.first_bad[0] != ~0ull) fail("the string is not utf-8 encoded! (document " + std::to_string(C.first_bad[0]) + ")");
+    if (C.first_bad[1] != ~0ull)
+        fail("tfidf (device tokenizer): document " + std::to_string(C.first_bad[1]) + " holds a UTF-8 lead byte followed by too few continuation bytes, "
+             "which the host tokenizer decodes along another path: use the host tokenizer for this text");
+}
+
+// text -> counts (K9) -> the weighting tail: X ready for xrl_predict_device
+std::unique_ptr<Queries> tfidf_device_text_to_x(const TfidfHandle& H, const uint8_t* d_text, const uint64_t* d_doc_off, const uint64_t* d_doc_len,
+                                                const uint64_t* h_doc_len, uint64_t nr_doc, int device, hipStream_t s) {
+    TokCounts C;
+    tfidf_count_on_device(H, d_text, d_doc_off, d_doc_len, h_doc_len, nr_doc, nullptr, device, s, C);
+    auto q = std::make_unique<Queries>();
+    q->idx = std::move(C.col); q->val = std::move(C.cnt);
+    tfidf_weight_counts(H, q.get(), C.seg_ptr, nullptr, (uint32_t)nr_doc, C.nnz, device, s);
     return q;
 }
 }  // namespace
@@ -266,6 +347,115 @@ void* xrl_tfidf_predict_device(void* vectorizer, void* model, void* corpus_ptr, 
         Model& m = *as_model(model);
         const TfidfHandle& H = *static_cast<TfidfHandle*>(vectorizer);
         return tfidf_to_device(H, static_cast<const char* const*>(corpus_ptr), doc_lens, nr_doc, threads, m.device, m.stream).release();
+    });
+}
+
+// ---- the device tokenizer (K9): document bytes in HBM.  Null arguments are refused before the GPU is touched.
+static void check_device_text_args(const char* what, void* vectorizer, void* model, const void* d_text, const void* d_doc_off, const void* d_doc_len, uint64_t nr_doc) {
+    const std::string w = std::string(what) + ": ";
+    if (!vectorizer) fail(w + "null vectorizer handle");
+    if (!model) fail(w + "null model handle");
+    if (nr_doc && (!d_text || !d_doc_off || !d_doc_len)) fail(w + "null text, offsets or lengths");
+    if (nr_doc > 0xFFFFFFFFull) fail("tfidf: too many documents");
+}
+
+void* xrl_tfidf_counts_device(void* vectorizer, void* model, const uint8_t* d_text, const uint64_t* d_doc_off, const uint64_t* d_doc_len, uint64_t nr_doc,
+                              uint32_t* d_status, void* hip_stream) {
+    return guarded_value((void*)nullptr, [&]() -> void* {
+        check_device_text_args("xrl_tfidf_counts_device", vectorizer, model, d_text, d_doc_off, d_doc_len, nr_doc);
+        Model& m = *as_model(model);
+        const TfidfHandle& H = *static_cast<TfidfHandle*>(vectorizer);
+        use_device(m.device);
+        std::lock_guard<std::mutex> stage_lock(H.stage.mu);      // (the pooled stream is handed out under this lock)
+        hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : m.stream ? m.stream : H.stream_on(m.device);
+        TokCounts C;
+        tfidf_count_on_device(H, d_text, d_doc_off, d_doc_len, nullptr, nr_doc, d_status, m.device, s, C);
+        const uint32_t nb = (uint32_t)H.v.base.size(), rows = (uint32_t)nr_doc;
+        auto q = std::make_unique<Queries>();
+        q->idx = std::move(C.col); q->val = std::move(C.cnt);
+        if (nb == 1) q->ptr = std::move(C.seg_ptr);
+        else {
+            q->ptr.reserve(((size_t)rows + 1) * 8);
+            launch_seg_to_row_ptr(C.seg_ptr.as<uint64_t>(), nb, rows, q->ptr.as<uint64_t>(), s);
+            XRL_HIP(hipStreamSynchronize(s));                    // (C.seg_ptr goes with this scope)
+        }
+        set_own_csr(*q, m.device, rows, H.v.nr_features, C.nnz);
+        return q.release();
+    });
+}
+
+void* xrl_tfidf_predict_device_text(void* vectorizer, void* model, const uint8_t* d_text, const uint64_t* d_doc_off, const uint64_t* d_doc_len, uint64_t nr_doc,
+                                    void* hip_stream) {
+    return guarded_value((void*)nullptr, [&]() -> void* {
+        check_device_text_args("xrl_tfidf_predict_device_text", vectorizer, model, d_text, d_doc_off, d_doc_len, nr_doc);
+        Model& m = *as_model(model);
+        const TfidfHandle& H = *static_cast<TfidfHandle*>(vectorizer);
+        use_device(m.device);
+        std::lock_guard<std::mutex> stage_lock(H.stage.mu);
+        hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : m.stream ? m.stream : H.stream_on(m.device);
+        return tfidf_device_text_to_x(H, d_text, d_doc_off, d_doc_len, nullptr, nr_doc, m.device, s).release();
+    });
+}
+
+void* xrl_tfidf_predict_device_tok(void* vectorizer, void* model, void* corpus_ptr, const size_t* doc_lens, size_t nr_doc, int tokenizer, int threads) {
+    return guarded_value((void*)nullptr, [&]() -> void* {
+        if (!vectorizer) fail("xrl_tfidf_predict_device_tok: null vectorizer handle");
+        if (!model) fail("xrl_tfidf_predict_device_tok: null model handle");
+        if (nr_doc && (!corpus_ptr || !doc_lens)) fail("xrl_tfidf_predict_device_tok: null corpus");
+        if (tokenizer != 0 && tokenizer != 1) fail("xrl_tfidf_predict_device_tok: tokenizer must be 0 (host) or 1 (device)");
+        if (nr_doc > 0xFFFFFFFFull) fail("tfidf: too many documents");
+        Model& m = *as_model(model);
+        const TfidfHandle& H = *static_cast<TfidfHandle*>(vectorizer);
+        const char* const* corpus = static_cast<const char* const*>(corpus_ptr);
+        if (tokenizer == 0) return tfidf_to_device(H, corpus, doc_lens, nr_doc, threads, m.device, m.stream).release();
+        use_device(m.device);
+        std::lock_guard<std::mutex> stage_lock(H.stage.mu);      // held until the stream has consumed the staging buffer
+        hipStream_t s = m.stream ? m.stream : H.stream_on(m.device);
+        // the corpus packed into the pinned staging as [offsets u64 | lengths u64 | bytes], one copy to the device
+        std::vector<uint64_t> off((size_t)nr_doc + 1, 0);
+        for (size_t d = 0; d < nr_doc; ++d) off[d + 1] = off[d] + doc_lens[d];
+        const size_t head = nr_doc * 16, total = head + (size_t)off[nr_doc];
+        char* st = static_cast<char*>(H.stage.need(total + 16));
+        std::memcpy(st, off.data(), nr_doc * 8);
+        for (size_t d = 0; d < nr_doc; ++d) reinterpret_cast<uint64_t*>(st + nr_doc * 8)[d] = doc_lens[d];
+        {
+            unsigned nt = threads > 0 ? (unsigned)threads : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+            nt = (unsigned)std::max<size_t>(1, std::min<size_t>(nt, (size_t)off[nr_doc] >> 20));
+            auto work = [&](unsigned t) {
+                for (size_t d = nr_doc * t / nt, e = nr_doc * (t + 1) / nt; d < e; ++d)
+                    if (doc_lens[d]) std::memcpy(st + head + off[d], corpus[d], doc_lens[d]);
+            };
+            std::vector<std::thread> th;
+            for (unsigned t = 1; t < nt; ++t) th.emplace_back(work, t);
+            work(0);
+            for (auto& x : th) x.join();
+        }
+        DevBuf d_in;
+        d_in.reserve(total + 16);
+        if (total) XRL_HIP(hipMemcpyAsync(d_in.p, st, total, hipMemcpyHostToDevice, s));
+        const uint64_t* d_off = d_in.as<uint64_t>();
+        return tfidf_device_text_to_x(H, reinterpret_cast<const uint8_t*>(d_in.p) + head, d_off, d_off + nr_doc, reinterpret_cast<const uint64_t*>(st + nr_doc * 8), nr_doc,
+                                      m.device, s).release();
+    });
+}
+
+uint64_t xrl_tfidf_device_bytes(void* vectorizer, int device) {
+    return guarded_value((uint64_t)0, [&]() -> uint64_t {
+        if (!vectorizer) fail("xrl_tfidf_device_bytes: null vectorizer handle");
+        const TfidfHandle& H = *static_cast<TfidfHandle*>(vectorizer);
+        std::lock_guard<std::mutex> g(H.dev_mu);
+        auto it = H.dev_tables.find(device);
+        return it == H.dev_tables.end() ? 0 : it->second->bytes;
+    });
+}
+
+// debug: out[0..n) <- {segments the LDS form served, segments the global form served, batches, calls} of the device tokenizer since the load
+int xrl_debug_tfidf_device_forms(void* vectorizer, uint64_t* out, uint32_t n) {
+    return guarded_value(-1, [&]() -> int {
+        if (!vectorizer || !out) fail("xrl_debug_tfidf_device_forms: null argument");
+        const TfidfHandle& H = *static_cast<TfidfHandle*>(vectorizer);
+        for (uint32_t i = 0; i < n && i < 4; ++i) out[i] = H.forms[i].load();
+        return 0;
     });
 }
 

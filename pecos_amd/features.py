@@ -179,6 +179,60 @@ def predict_tfidf_from_torch(model, crow, col, count, n_cols, idf=None, binary=F
     return idx, sc, cnt
 
 
+def _device_text(text_u8, doc_off, doc_len):
+    """The device tokenizer's inputs checked and made contiguous: (text uint8, offsets int64, lengths int64) CUDA tensors on one device
+    (the int64 tensors hold the u64 values).  The copies, if any, run on torch's current stream, which is then synchronised: K9 runs on
+    the model's stream."""
+    import torch
+    assert text_u8.is_cuda and doc_off.is_cuda and doc_len.is_cuda and text_u8.device == doc_off.device == doc_len.device
+    assert text_u8.dtype == torch.uint8 and doc_off.dtype == torch.int64 and doc_len.dtype == torch.int64
+    assert text_u8.dim() == 1 and doc_off.dim() == 1 and doc_off.shape == doc_len.shape
+    if text_u8.stride(0) != 1:
+        text_u8 = text_u8.contiguous()
+    doc_off, doc_len = doc_off.contiguous(), doc_len.contiguous()
+    torch.cuda.current_stream(text_u8.device).synchronize()
+    return text_u8, doc_off, doc_len
+
+
+def tfidf_counts_device(vectorizer, model, text_u8, doc_off, doc_len, status=None, stream=None):
+    """Term counts of documents whose bytes are already in HBM (K9): ``text_u8`` uint8 [bytes] (any alignment: a slice of a larger tensor is
+    fine), ``doc_off`` / ``doc_len`` int64 [n] CUDA tensors on ``model``'s device; document i is ``text_u8[doc_off[i] : doc_off[i] + doc_len[i]]``
+    (gaps, overlaps and any order are fine).  Returns a query handle (``clib.freeing`` / ``clib.queries_download``) holding the hstacked CSR
+    of term COUNTS, equal to ``clib.tfidf_counts`` of the same documents.  ``status``: optional int32 [n] CUDA tensor that takes each
+    document's status (0 fine; 1 / 2: not decodable in parallel, row left empty) instead of a RuntimeError."""
+    import torch
+    if isinstance(vectorizer, Preprocessor):
+        vectorizer = vectorizer.vectorizer
+    text_u8, doc_off, doc_len = _device_text(text_u8, doc_off, doc_len)
+    if status is not None:
+        assert status.is_cuda and status.dtype == torch.int32 and status.shape == doc_len.shape and status.is_contiguous()
+    n = int(doc_len.numel())
+    # (an empty tensor has no address: the library wants one for every array of a non-empty corpus)
+    text_addr = text_u8.data_ptr() if text_u8.numel() else doc_len.data_ptr()
+    return clib.tfidf_counts_device(vectorizer.model, model.model.model_chain, text_addr, doc_off.data_ptr(), doc_len.data_ptr(), n,
+                                    status.data_ptr() if status is not None else None, stream=stream)
+
+
+def predict_text_from_torch(vectorizer, model, text_u8, doc_off, doc_len, beam_size=None, only_topk=None, post_processor=None, stream=None):
+    """Text that is already in HBM (tensors as for :func:`tfidf_counts_device`) -> term counts (K9) -> tf-idf weighting (K5) -> beam search,
+    with no host copy of the text, of X or of the result: returns (labels, scores, counts) CUDA tensors like :func:`predict_from_torch`."""
+    import torch
+    if isinstance(vectorizer, Preprocessor):
+        vectorizer = vectorizer.vectorizer
+    h = model.model.model_chain
+    text_u8, doc_off, doc_len = _device_text(text_u8, doc_off, doc_len)
+    rows = int(doc_len.numel())
+    k = clib.effective_topk(h, only_topk)
+    idx, sc, cnt = result_buffers(rows, k, doc_len.device, sync=True)
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    text_addr = text_u8.data_ptr() if text_u8.numel() else doc_len.data_ptr()
+    q = clib.tfidf_predict_device_text(vectorizer.model, h, text_addr, doc_off.data_ptr(), doc_len.data_ptr(), rows, stream=s or None)
+    with clib.freeing(q):
+        if rows:
+            clib.predict_device(h, q, beam_size, post_processor, only_topk, idx.data_ptr(), sc.data_ptr(), cnt.data_ptr(), k, stream=s or None, sync=True)
+    return idx, sc, cnt
+
+
 class Tfidf:
     """The PREDICT half of the reference's ``pecos.utils.featurization.text.vectorizers.Tfidf`` (vectorizers.py:163-308): ``load`` a
     folder the reference saved, ``predict`` a list of strings to a scipy CSR -- same names, arguments and result -- with the tokenizer on
@@ -208,9 +262,12 @@ class Tfidf:
     def predict(self, corpus, **kwargs):
         return clib.tfidf_predict(self.model, corpus, buffer_size=kwargs.get("buffer_size", 0), threads=kwargs.get("threads", -1))
 
-    def predict_device(self, xlinear_model, corpus, threads=-1):
-        """Texts -> X resident on ``xlinear_model``'s GPU: a query handle (to be freed: ``clib.freeing``) for ``clib.predict_device``."""
-        return clib.tfidf_predict_device(self.model, xlinear_model.model.model_chain, corpus, threads)
+    def predict_device(self, xlinear_model, corpus, threads=-1, tokenizer="host"):
+        """Texts -> X resident on ``xlinear_model``'s GPU: a query handle (to be freed: ``clib.freeing``) for ``clib.predict_device``.
+        ``tokenizer="host"`` counts the terms on host threads and uploads the counts; ``"device"`` uploads the text and counts on the GPU (K9)."""
+        if tokenizer == "host":              # (the call as it always was)
+            return clib.tfidf_predict_device(self.model, xlinear_model.model.model_chain, corpus, threads)
+        return clib.tfidf_predict_device(self.model, xlinear_model.model.model_chain, corpus, threads, tokenizer=tokenizer)
 
 
 class Preprocessor:
@@ -249,8 +306,8 @@ class Preprocessor:
             raise NotImplementedError("predict from a corpus FILE is not offered by pecos_amd: read the lines and pass a list")
         return self.vectorizer.predict(corpus, **kwargs)
 
-    def predict_device(self, xlinear_model, corpus, threads=-1):
-        return self.vectorizer.predict_device(xlinear_model, corpus, threads=threads)
+    def predict_device(self, xlinear_model, corpus, threads=-1, tokenizer="host"):
+        return self.vectorizer.predict_device(xlinear_model, corpus, threads=threads, tokenizer=tokenizer)
 
 
 def _predict_handle_to_csr(model, q, rows, beam_size=None, only_topk=None, post_processor=None):
@@ -426,10 +483,11 @@ _ensemble_streams = {}
 
 
 @contextlib.contextmanager
-def _text_queries(vectorizer, model, corpus, X_emb, normalize_emb, threads):
+def _text_queries(vectorizer, model, corpus, X_emb, normalize_emb, threads, tokenizer="host"):
     """Texts -> the query handle to search, on ``model``'s device: the tf-idf X, or with ``X_emb`` (float32 [rows, H] CUDA tensor) the
     concatenation [X | X_emb] made from it on the device.  Both handles are freed on exit."""
-    q = vectorizer.predict_device(model, corpus, threads=threads)
+    extra = {} if tokenizer == "host" else {"tokenizer": tokenizer}          # (a vectorizer object without the option still serves the default)
+    q = vectorizer.predict_device(model, corpus, threads=threads, **extra)
     with clib.freeing(q):
         if X_emb is None:
             yield q
@@ -443,7 +501,8 @@ def _text_queries(vectorizer, model, corpus, X_emb, normalize_emb, threads):
             yield q2
 
 
-def _predict_text_ensemble_device(vectorizer, models, corpus, X_emb, normalize_emb, threads, beam_size, only_topk, post_processor, finish):
+def _predict_text_ensemble_device(vectorizer, models, corpus, X_emb, normalize_emb, threads, beam_size, only_topk, post_processor, finish,
+                                  tokenizer="host"):
     """predict_text's ensemble on the device: ONE tokenisation and upload (and one concatenation with X_emb), every model's beam search on
     that handle, the merge (K6) and nothing else on one stream, one synchronisation, one copy back, one CSR."""
     import torch
@@ -451,7 +510,7 @@ def _predict_text_ensemble_device(vectorizer, models, corpus, X_emb, normalize_e
     hs = [m.model.model_chain for m in models]
     dev = torch.device("cuda", clib.xlinear_get_int_attr(hs[0], "device"))
     rows = len(corpus)
-    with _text_queries(vectorizer, models[0], corpus, X_emb, normalize_emb, threads) as q:
+    with _text_queries(vectorizer, models[0], corpus, X_emb, normalize_emb, threads, tokenizer) as q:
         try:
             s = _ensemble_streams.get(dev.index)
             if s is None:
@@ -473,7 +532,7 @@ def _predict_text_ensemble_device(vectorizer, models, corpus, X_emb, normalize_e
             torch.cuda.synchronize(dev)            # (also on an error: nothing may still read X when its handle goes)
 
 
-def predict_text(vectorizer, models, corpus, X_emb=None, normalize_emb=True, threads=-1, ensemble="auto", finish=None, **kwargs):
+def predict_text(vectorizer, models, corpus, X_emb=None, normalize_emb=True, threads=-1, ensemble="auto", finish=None, tokenizer="host", **kwargs):
     """The reference's text call sites with X DEVICE-RESIDENT end to end:
 
     * ``Text2Text.predict`` (pecos/apps/text2text/model.py:416-422): ``X = preprocessor.predict(corpus); Y = [m.predict(X) ...]`` --
@@ -488,18 +547,23 @@ def predict_text(vectorizer, models, corpus, X_emb=None, normalize_emb=True, thr
     back per model, scipy's merge).  The result is the same bit for bit.  ``finish=(threshold, only_topk)`` also applies
     :meth:`Text2Text.finish`'s threshold and cut to the merged rows (on whichever path).
 
+    ``tokenizer="host"`` (default) counts the terms on host threads; ``"device"`` uploads the text once and counts on the GPU (K9) -- the same
+    counts, hence the same labels and score bits.
+
     kwargs: beam_size, only_topk, post_processor.  Returns the predicted label matrix as scipy CSR (rows score-sorted)."""
+    if tokenizer not in clib.TOKENIZERS:
+        raise ValueError(f"tokenizer={tokenizer!r}: expected 'host' or 'device'")
     models = list(models) if isinstance(models, (list, tuple)) else [models]
     if isinstance(vectorizer, Preprocessor):
         vectorizer = vectorizer.vectorizer
     if len(models) > 1 and _ensemble_on_device(models, ensemble, kwargs.get("only_topk"), finish):
         return _predict_text_ensemble_device(vectorizer, models, corpus, X_emb, normalize_emb, threads, kwargs.get("beam_size"),
-                                             kwargs.get("only_topk"), kwargs.get("post_processor"), finish)
+                                             kwargs.get("only_topk"), kwargs.get("post_processor"), finish, tokenizer)
     elif ensemble not in ("auto", "device", "host"):
         raise ValueError(f"ensemble={ensemble!r}: expected 'auto', 'device' or 'host'")
     outs = []
     for m in models:
-        with _text_queries(vectorizer, m, corpus, X_emb, normalize_emb, threads) as q:
+        with _text_queries(vectorizer, m, corpus, X_emb, normalize_emb, threads, tokenizer) as q:
             outs.append(_predict_handle_to_csr(m, q, len(corpus), kwargs.get("beam_size"), kwargs.get("only_topk"), kwargs.get("post_processor")))
     if finish is not None:
         return Text2Text.finish(outs, threshold=finish[0], only_topk=finish[1])
@@ -581,10 +645,12 @@ class Text2Text:
         return sorted_csr(Y, only_topk=only_topk)
 
     def predict(self, corpus, threshold=None, **kwargs):
-        """Same arguments and result as the reference's ``Text2Text.predict`` (``threads`` applies to the tokenizer's host threads)."""
+        """Same arguments and result as the reference's ``Text2Text.predict`` (``threads`` applies to the tokenizer's host threads;
+        ``tokenizer="device"`` counts the terms on the GPU instead, see :func:`predict_text`)."""
         threads = kwargs.pop("threads", -1)
+        tokenizer = kwargs.pop("tokenizer", "host")
         # (an ensemble: one tokenisation and upload, the merge, threshold and cut on the device where predict_text finds that possible)
-        return predict_text(self.preprocessor, [m for m, _ in self.xlinear_models], corpus, threads=threads,
+        return predict_text(self.preprocessor, [m for m, _ in self.xlinear_models], corpus, threads=threads, tokenizer=tokenizer,
                             finish=(threshold, kwargs.get("only_topk", None)), **kwargs)
 
     def set_output_constraint(self, output_items_to_keep):
