@@ -306,6 +306,45 @@ int xrl_ensemble_device(int device, uint32_t n_models, uint32_t rows,
                         uint32_t only_topk /* 0 = all; finish only */,
                         uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride, void* hip_stream, int sync);
 
+/* The other methods of CsrEnsembler on the device (K6M), and the cut of TransformerMatcher.ensemble_prediction
+ * (pecos/xmc/xtransformer/matcher.py:535-579).  Inputs, output, tables and capacity are xrl_ensemble_device's: n_models <= 8 results over
+ * the same rows, sum(in_stride) <= 1024, a count above its stride is read as the stride, inputs are only read.  M = n_models; a "segment"
+ * is one model's entries of a row, p an entry's position in its segment.
+ *   method 0 average          as mode 0 of xrl_ensemble_device
+ *   method 2 rank_average     as mode 2 of xrl_ensemble_device
+ *   method 3 sigmoid_average  CsrEnsembler.sigmoid_average (smat_util.py:862-881): every score z becomes 1 / (1 + exp(-z)) in fp32 steps as
+ *                             numpy takes them on a float32 array (exp rounded to fp32, one fp32 add, one fp32 division; NOT the
+ *                             post-processor's sigmoid, which continues in double), then average.  sigmoid(+inf) = 1; sigmoid(z) = 0 once
+ *                             exp(-z) overflows fp32, and for -inf; NaN stays NaN.  (The reference overwrites its arguments' data.)
+ *   method 4 softmax_average  CsrEnsembler.softmax_average (:884-900, csr_row_softmax :788-811): per segment, over its stored entries
+ *                             (explicit zeros included), x_max = the maximum (NaN when the segment holds a NaN), e_j = exp(x_j - x_max)
+ *                             rounded to fp32, denominator = the fp64 sum of the e_j rounded once to fp32, value = e_j / denominator in
+ *                             fp32; then average.  Order of the fp64 sum, a function of the inputs only: entry j of the row's
+ *                             model-ordered list belongs to lane j % 64; every lane adds its entries of the segment in ascending j,
+ *                             starting from 0.0; the 64 lane sums then meet in six exchange steps, s[l] = s[l] + s[l ^ d] for
+ *                             d = 1, 2, 4, 8, 16, 32.  A segment whose maximum is +inf, or that is all -inf, comes out NaN by IEEE
+ *                             arithmetic alone, as scipy's does.  An EMPTY segment contributes nothing (the reference raises ValueError
+ *                             there: it takes the maximum of an empty array).
+ *   method 5 round_robin      CsrEnsembler.round_robin (:903-923 with get_relevance_csr, :638-659), all in fp64, every operation rounded
+ *                             on its own: base = 1.0 / (M + 1.0); the entry at position p of model m scores
+ *                             (double)(mm - p) + (double)(M - m) * base, mm = the longest row of any model in the call (reduced on the
+ *                             device, no host synchronisation); a label's key is the MAXIMUM over its holders; rows ordered by (key
+ *                             descending, label ascending); values (float)(key / (double)M).  Scores are not read.
+ *   method 1 (finish) is refused: it is xrl_ensemble_device's.
+ * only_topk == 0 keeps the method's own order and length.  only_topk > 0 is ensemble_prediction's last line,
+ * sorted_csr(pred.astype(float32), only_topk): the merged row is ranked AGAIN by its fp32 VALUE descending (NaN last, -0.0 tied with +0.0),
+ * then label ascending, and the first only_topk entries are kept.  out_stride >= the longest possible row: sum(in_stride), or
+ * min(sum(in_stride), only_topk) with only_topk > 0.  Entries of an output row beyond its count are left untouched.
+ * Stream, `sync`, rows == 0 and the order of the checks are xrl_ensemble_device's: the work runs on `hip_stream` of `device` (NULL = the
+ * null stream), returns without synchronising when `sync` == 0, the device scalar of methods 2 and 5 lives and dies in stream order,
+ * rows == 0 is a successful no-op, every argument is checked before a GPU is required.  Returns 0 on success, -1 with a message
+ * (starting "xrl_ensemble_methods_device: ") in xrl_last_error otherwise. */
+int xrl_ensemble_methods_device(int device, uint32_t n_models, uint32_t rows,
+                                const uint32_t* const* d_idx, const float* const* d_val, const uint32_t* const* d_cnt, const uint32_t* in_stride,
+                                int method /* 0 average, 2 rank_average, 3 sigmoid_average, 4 softmax_average, 5 round_robin */,
+                                uint32_t only_topk /* 0 = the method's own rows */,
+                                uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride, void* hip_stream, int sync);
+
 /* Metrics on the device (K8): the sums behind precision and recall at 1 .. topk -- smat_util.Metrics.generate(tY, pY, topk)
  * (pecos/utils/smat_util.py:968-997) -- of ONE fixed-stride result (d_idx u32[rows*stride], d_val f32[rows*stride], d_cnt u32[rows], as
  * xrl_predict_device and xrl_ensemble_device write it; a count above the stride is read as the stride) against the true labels as a device CSR

@@ -240,6 +240,8 @@ class corelib(object):
         "xrl_predict_device_rows": (c_int, [c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int, c_uint32, c_uint32]),
         "xrl_ensemble_device": (c_int, [c_int, c_uint32, c_uint32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint32), c_int,
                                         POINTER(c_float), c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int]),
+        "xrl_ensemble_methods_device": (c_int, [c_int, c_uint32, c_uint32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint32), c_int,
+                                                c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int]),
         "xrl_metrics_device": (c_int, [c_int, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_int]),
         "xrl_predict_selected_device": (c_int, [c_void_p, c_void_p, c_char_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_int]),
         "xrl_set_output_constraint": (c_int, [c_void_p, c_void_p, c_uint64]),
@@ -685,6 +687,24 @@ class corelib(object):
         rc = self.clib_float32.xrl_ensemble_device(
             int(device), n, int(rows), tab(d_idx), tab(d_val), tab(d_cnt), (c_uint32 * max(n, 1))(*[int(s) for s in in_stride]),
             self.ENSEMBLE_MODES.get(mode, mode), None if threshold is None else ctypes.byref(c_float(threshold)), only_topk or 0,
+            c_void_p(d_out_idx), c_void_p(d_out_val), c_void_p(d_out_cnt), int(out_stride), c_void_p(stream or 0), 1 if sync else 0)
+        self._check()
+        return rc
+
+    # xrl_ensemble_methods_device's numbers (finish is listed for its number only: that entry point refuses it)
+    ENSEMBLE_METHODS = {"average": 0, "finish": 1, "rank_average": 2, "sigmoid_average": 3, "softmax_average": 4, "round_robin": 5}
+
+    def ensemble_methods_device(self, device, rows, d_idx, d_val, d_cnt, in_stride, method, only_topk, d_out_idx, d_out_val, d_out_cnt,
+                                out_stride, stream=None, sync=True):
+        """K6M: like :meth:`ensemble_device` for the methods of ``CsrEnsembler`` -- ``method``: a key of ``ENSEMBLE_METHODS`` (not
+        ``finish``) or its number; ``only_topk``: ``None`` / 0 = the method's own rows, else they are ranked again by their fp32 value and
+        cut, as ``TransformerMatcher.ensemble_prediction`` does."""
+        n = len(d_idx)
+        assert len(d_val) == n and len(d_cnt) == n and len(in_stride) == n
+        tab = lambda a: (c_void_p * max(n, 1))(*[c_void_p(int(x) if x else 0) for x in a])                   # noqa: E731
+        rc = self.clib_float32.xrl_ensemble_methods_device(
+            int(device), n, int(rows), tab(d_idx), tab(d_val), tab(d_cnt), (c_uint32 * max(n, 1))(*[int(s) for s in in_stride]),
+            self.ENSEMBLE_METHODS.get(method, method), only_topk or 0,
             c_void_p(d_out_idx), c_void_p(d_out_val), c_void_p(d_out_cnt), int(out_stride), c_void_p(stream or 0), 1 if sync else 0)
         self._check()
         return rc

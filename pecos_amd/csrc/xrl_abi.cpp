@@ -371,6 +371,44 @@ int xrl_ensemble_device(int device, uint32_t n_models, uint32_t rows, const uint
     });
 }
 
+int xrl_ensemble_methods_device(int device, uint32_t n_models, uint32_t rows, const uint32_t* const* d_idx, const float* const* d_val,
+                                const uint32_t* const* d_cnt, const uint32_t* in_stride, int method, uint32_t only_topk,
+                                uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride, void* hip_stream, int sync) {
+    return guarded_value(-1, [&] {
+        // every argument is checked before the GPU is required, in xrl_ensemble_device's order
+        const std::string what = "xrl_ensemble_methods_device: ";
+        if (!d_idx || !d_val || !d_cnt || !in_stride || !d_out_idx || !d_out_val || !d_out_cnt) fail(what + "null argument");
+        if (n_models == 0 || n_models > (uint32_t)kEnsembleMaxModels) fail(what + "n_models must be 1.." + std::to_string(kEnsembleMaxModels) + ", got " + std::to_string(n_models));
+        EnsembleArgs A{};
+        uint64_t total = 0;
+        for (uint32_t m = 0; m < n_models; ++m) {
+            if (!d_idx[m] || !d_val[m] || !d_cnt[m]) fail(what + "null device pointer for model " + std::to_string(m));
+            A.idx[m] = d_idx[m]; A.val[m] = d_val[m]; A.cnt[m] = d_cnt[m]; A.stride[m] = in_stride[m];
+            total += in_stride[m];
+        }
+        if (total > kEnsembleMaxTotal) fail(what + "the input strides sum to " + std::to_string(total) + ", more than " + std::to_string(kEnsembleMaxTotal));
+        if (method == kEnsembleFinish) fail(what + "method 1 (finish) is served by xrl_ensemble_device");
+        if (method != kEnsembleAverage && method != kEnsembleRankAverage && method != kEnsembleSigmoidAverage &&
+            method != kEnsembleSoftmaxAverage && method != kEnsembleRoundRobin) fail(what + "unknown method " + std::to_string(method));
+        const uint64_t longest = only_topk ? std::min<uint64_t>(total, only_topk) : total;
+        if (out_stride < longest) fail(what + "out_stride " + std::to_string(out_stride) + " smaller than the longest possible row, " + std::to_string(longest));
+        if (rows == 0) return 0;
+        require_gpu();
+        use_device(device);
+        A.n_models = n_models; A.rows = rows; A.mode = method; A.only_topk = only_topk;
+        A.out_idx = d_out_idx; A.out_val = d_out_val; A.out_cnt = d_out_cnt; A.out_stride = out_stride;
+        hipStream_t s = static_cast<hipStream_t>(hip_stream);
+        // the device scalar of rank_average and round_robin lives and dies in stream order, as xrl_ensemble_device's
+        void* mm = nullptr;
+        if (method == kEnsembleRankAverage || method == kEnsembleRoundRobin) XRL_HIP(hipMallocAsync(&mm, sizeof(uint32_t), s));
+        try { launch_ensemble_methods(A, static_cast<uint32_t*>(mm), s); }
+        catch (...) { if (mm) (void)hipFreeAsync(mm, s); throw; }
+        if (mm) XRL_HIP(hipFreeAsync(mm, s));
+        if (sync) XRL_HIP(hipStreamSynchronize(s));
+        return 0;
+    });
+}
+
 int xrl_metrics_device(int device, uint32_t rows, const uint32_t* d_idx, const float* d_val, const uint32_t* d_cnt, uint32_t stride,
                        const uint64_t* d_true_ptr, const uint32_t* d_true_idx, uint32_t topk, uint64_t* d_matched, double* d_recall_sum,
                        void* hip_stream, int sync) {

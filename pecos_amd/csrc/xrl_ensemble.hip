@@ -27,8 +27,6 @@
 
 namespace xrl {
 
-constexpr int kEnsembleWaves = 4;        // wavefronts (= rows) per workgroup
-
 // mm of rank_average: the largest row length over all models and all rows of the call (smat_util.py:855), row lengths clamped to
 // the stride.  One workgroup, so that the result is a plain store.
 __global__ void __launch_bounds__(1024)
@@ -176,6 +174,11 @@ uint32_t ensemble_slots(uint32_t stride_sum) {
     return ns;
 }
 
+void launch_ensemble_max_len(const EnsembleArgs& A, uint32_t* mm, hipStream_t s) {
+    hipLaunchKernelGGL(ensemble_max_len_kernel, dim3(1), dim3(1024), 0, s, A, mm);
+    XRL_LAUNCH_CHECK();
+}
+
 void launch_ensemble(const EnsembleArgs& A, uint32_t* mm_scratch, hipStream_t s) {
     if (A.rows == 0) return;
     uint32_t stride_sum = 0;
@@ -183,8 +186,7 @@ void launch_ensemble(const EnsembleArgs& A, uint32_t* mm_scratch, hipStream_t s)
     if (A.n_models == 0 || A.n_models > (uint32_t)kEnsembleMaxModels || stride_sum > kEnsembleMaxTotal) fail("ensemble: shape outside the kernel's capacity");
     if (A.mode == kEnsembleRankAverage) {
         if (!mm_scratch) fail("ensemble: rank_average needs its device scalar");
-        hipLaunchKernelGGL(ensemble_max_len_kernel, dim3(1), dim3(1024), 0, s, A, mm_scratch);
-        XRL_LAUNCH_CHECK();
+        launch_ensemble_max_len(A, mm_scratch, s);
     }
     switch (ensemble_slots(stride_sum)) {
     case 1: launch_ensemble_ns<1>(A, mm_scratch, s); break;

@@ -12,7 +12,9 @@
 * :func:`predict_selected_from_torch` -- ``predict_on_selected_outputs`` with the queries and the labels to score in HBM (K7 + K4): re-scores
   one model's candidates with another without a host round trip.
 * :func:`ensemble_device` -- the results of several models merged on the device (K6) like ``CsrEnsembler.average`` / ``rank_average`` /
-  ``Text2Text.predict``'s tail; :func:`predict_text` and :class:`Text2Text` use it for ensembles that share a device.
+  ``Text2Text.predict``'s tail; :func:`predict_text` and :class:`Text2Text` use it for ensembles that share a device.  ``sigmoid_average``,
+  ``softmax_average``, ``round_robin`` and ``only_topk`` go through K6M; :func:`ensemble_prediction_device` is
+  ``TransformerMatcher.ensemble_prediction`` on two device results, :func:`ensemble_host` the same methods on scipy matrices.
 * :func:`metrics_device` / :func:`metrics_sums_device` / :class:`Metrics` -- ``smat_util.Metrics.generate`` (precision and recall at
   1 .. topk) from a result in HBM (K8): 2 x topk numbers come back instead of the result.
 """
@@ -332,11 +334,17 @@ def ensemble_device(results, mode="average", threshold=None, only_topk=None, str
     CUDA tensors as :func:`predict_from_torch` returns them (int32 [rows, k_m], float32 [rows, k_m], int32 [rows]); the return value has
     the same form, its rows ordered and valued like the host code's: ``mode="average"`` = :func:`ensemble_average`
     (``CsrEnsembler.average``), ``"finish"`` = :meth:`Text2Text.finish` (average, ``threshold``, ``sorted_csr(only_topk)``),
-    ``"rank_average"`` = ``CsrEnsembler.rank_average``.  Runs on ``stream`` (a raw HIP stream; default: torch's current one); inputs and
+    ``"rank_average"`` = ``CsrEnsembler.rank_average``.  ``"sigmoid_average"``, ``"softmax_average"`` and ``"round_robin"`` are
+    ``CsrEnsembler``'s methods of those names (K6M; see :func:`ensemble_host` for their rules); with them, and with ``"average"`` /
+    ``"rank_average"``, ``only_topk`` ranks the merged rows again by their fp32 value and cuts them, as
+    ``TransformerMatcher.ensemble_prediction`` does.  Runs on ``stream`` (a raw HIP stream; default: torch's current one); inputs and
     outputs must be ordered on it."""
     import torch
-    if mode not in clib.ENSEMBLE_MODES:
-        raise ValueError(f"ensemble mode {mode!r}: expected one of {sorted(clib.ENSEMBLE_MODES)}")
+    if mode not in clib.ENSEMBLE_METHODS:
+        raise ValueError(f"ensemble mode {mode!r}: expected one of {sorted(clib.ENSEMBLE_METHODS)}")
+    methods = mode not in clib.ENSEMBLE_MODES or (mode != "finish" and bool(only_topk))     # K6M's part; everything else is K6's, as before
+    if methods and threshold is not None:
+        raise ValueError(f"ensemble mode {mode!r}: a threshold belongs to mode 'finish'")
     if not results:
         raise ValueError("ensemble_device: no results given")
     dev = results[0][0].device
@@ -348,14 +356,18 @@ def ensemble_device(results, mode="average", threshold=None, only_topk=None, str
         assert idx.dim() == 2 and idx.shape == sc.shape and idx.shape[0] == rows and cnt.shape == (rows,)
         res.append((idx.contiguous(), sc.contiguous(), cnt.contiguous()))
     total = sum(r[0].shape[1] for r in res)
-    out_stride = min(total, only_topk) if (mode == "finish" and only_topk) else total
+    out_stride = min(total, only_topk) if ((mode == "finish" or methods) and only_topk) else total
     with torch.cuda.device(dev):
         s = torch.cuda.current_stream().cuda_stream if stream is None else stream
         # (allocated on torch's current stream; with another `stream` nothing is queued on the buffers ahead of the kernel: no fill)
         o_idx = torch.empty((rows, out_stride), dtype=torch.int32, device=dev)
         o_sc = torch.empty((rows, out_stride), dtype=torch.float32, device=dev)
         o_cnt = torch.empty((rows,), dtype=torch.int32, device=dev)
-        if rows and out_stride:
+        if rows and out_stride and methods:
+            clib.ensemble_methods_device(dev.index, rows, [r[0].data_ptr() for r in res], [r[1].data_ptr() for r in res],
+                                         [r[2].data_ptr() for r in res], [r[0].shape[1] for r in res], mode, only_topk, o_idx.data_ptr(),
+                                         o_sc.data_ptr(), o_cnt.data_ptr(), out_stride, stream=s or None, sync=sync)
+        elif rows and out_stride:
             clib.ensemble_device(dev.index, rows, [r[0].data_ptr() for r in res], [r[1].data_ptr() for r in res], [r[2].data_ptr() for r in res],
                                  [r[0].shape[1] for r in res], mode, threshold, only_topk, o_idx.data_ptr(), o_sc.data_ptr(),
                                  o_cnt.data_ptr(), out_stride, stream=s or None, sync=sync)
@@ -502,7 +514,7 @@ def _text_queries(vectorizer, model, corpus, X_emb, normalize_emb, threads, toke
 
 
 def _predict_text_ensemble_device(vectorizer, models, corpus, X_emb, normalize_emb, threads, beam_size, only_topk, post_processor, finish,
-                                  tokenizer="host"):
+                                  tokenizer="host", method="average"):
     """predict_text's ensemble on the device: ONE tokenisation and upload (and one concatenation with X_emb), every model's beam search on
     that handle, the merge (K6) and nothing else on one stream, one synchronisation, one copy back, one CSR."""
     import torch
@@ -515,7 +527,7 @@ def _predict_text_ensemble_device(vectorizer, models, corpus, X_emb, normalize_e
             s = _ensemble_streams.get(dev.index)
             if s is None:
                 s = _ensemble_streams[dev.index] = torch.cuda.Stream(device=dev)
-            mode, thr, topk = ("average", None, None) if finish is None else ("finish", finish[0], finish[1])
+            mode, thr, topk = (method, None, None) if finish is None else ("finish", finish[0], finish[1])
             with torch.cuda.stream(s):
                 res = []
                 for h in hs:
@@ -532,7 +544,8 @@ def _predict_text_ensemble_device(vectorizer, models, corpus, X_emb, normalize_e
             torch.cuda.synchronize(dev)            # (also on an error: nothing may still read X when its handle goes)
 
 
-def predict_text(vectorizer, models, corpus, X_emb=None, normalize_emb=True, threads=-1, ensemble="auto", finish=None, tokenizer="host", **kwargs):
+def predict_text(vectorizer, models, corpus, X_emb=None, normalize_emb=True, threads=-1, ensemble="auto", finish=None, tokenizer="host",
+                 ensemble_method="average", **kwargs):
     """The reference's text call sites with X DEVICE-RESIDENT end to end:
 
     * ``Text2Text.predict`` (pecos/apps/text2text/model.py:416-422): ``X = preprocessor.predict(corpus); Y = [m.predict(X) ...]`` --
@@ -545,7 +558,9 @@ def predict_text(vectorizer, models, corpus, X_emb=None, normalize_emb=True, thr
     where they share a device, ``nr_features`` and label count and their top-k sum to at most 1024 entries per row, and on the host
     otherwise; ``"device"`` raises where "auto" would take the host path; ``"host"`` is the host path (one tokenisation, upload and copy
     back per model, scipy's merge).  The result is the same bit for bit.  ``finish=(threshold, only_topk)`` also applies
-    :meth:`Text2Text.finish`'s threshold and cut to the merged rows (on whichever path).
+    :meth:`Text2Text.finish`'s threshold and cut to the merged rows (on whichever path).  ``ensemble_method``: any method of
+    ``CsrEnsembler`` (:data:`ENSEMBLE_METHOD_NAMES`; default ``"average"``) -- merged on the device (K6M) where ``ensemble`` allows it, by
+    :func:`ensemble_host` otherwise, values as float32 either way; ``finish`` goes with ``"average"`` only.
 
     ``tokenizer="host"`` (default) counts the terms on host threads; ``"device"`` uploads the text once and counts on the GPU (K9) -- the same
     counts, hence the same labels and score bits.
@@ -554,11 +569,15 @@ def predict_text(vectorizer, models, corpus, X_emb=None, normalize_emb=True, thr
     if tokenizer not in clib.TOKENIZERS:
         raise ValueError(f"tokenizer={tokenizer!r}: expected 'host' or 'device'")
     models = list(models) if isinstance(models, (list, tuple)) else [models]
+    if ensemble_method not in ENSEMBLE_METHOD_NAMES:
+        raise ValueError(f"ensemble_method={ensemble_method!r}: expected one of {list(ENSEMBLE_METHOD_NAMES)}")
+    if ensemble_method != "average" and finish is not None:
+        raise ValueError(f"ensemble_method={ensemble_method!r}: finish=(threshold, only_topk) goes with 'average' only")
     if isinstance(vectorizer, Preprocessor):
         vectorizer = vectorizer.vectorizer
     if len(models) > 1 and _ensemble_on_device(models, ensemble, kwargs.get("only_topk"), finish):
         return _predict_text_ensemble_device(vectorizer, models, corpus, X_emb, normalize_emb, threads, kwargs.get("beam_size"),
-                                             kwargs.get("only_topk"), kwargs.get("post_processor"), finish, tokenizer)
+                                             kwargs.get("only_topk"), kwargs.get("post_processor"), finish, tokenizer, ensemble_method)
     elif ensemble not in ("auto", "device", "host"):
         raise ValueError(f"ensemble={ensemble!r}: expected 'auto', 'device' or 'host'")
     outs = []
@@ -567,9 +586,12 @@ def predict_text(vectorizer, models, corpus, X_emb=None, normalize_emb=True, thr
             outs.append(_predict_handle_to_csr(m, q, len(corpus), kwargs.get("beam_size"), kwargs.get("only_topk"), kwargs.get("post_processor")))
     if finish is not None:
         return Text2Text.finish(outs, threshold=finish[0], only_topk=finish[1])
+    if ensemble_method != "average":
+        Y = ensemble_host(outs, ensemble_method)      # rank_average and round_robin: float64 in the reference; float32 here, as the device
+        return smat.csr_matrix((Y.data.astype(np.float32), Y.indices, Y.indptr), shape=Y.shape)     # (scipy's astype would sort the columns)
     if len(outs) == 1:
         return outs[0]
-    return ensemble_average(outs)                 # CsrEnsembler.average (smat_util.py:828-842): sum, sorted_csr, divide -- rows score-sorted like the reference's
+    return ensemble_average(outs)               # CsrEnsembler.average (smat_util.py:828-842): sum, sorted_csr, divide -- rows score-sorted like the reference's
 
 
 def sorted_csr(csr, only_topk=None):
@@ -601,6 +623,113 @@ def ensemble_average(mats):
     ret = sorted_csr(sum(mats).tocsr())
     ret.data /= len(mats)
     return ret
+
+
+ENSEMBLE_METHOD_NAMES = ("average", "rank_average", "sigmoid_average", "softmax_average", "round_robin")     # CsrEnsembler's methods
+
+
+def _relevance_csr(csr, mm):
+    """``get_relevance_csr`` (smat_util.py:638-659): position p of a row scores ``mm - p``, float64."""
+    counts = np.diff(csr.indptr)
+    rows = np.repeat(np.arange(csr.shape[0], dtype=np.int64), counts)
+    rel = (mm - (np.arange(len(csr.data), dtype=np.int64) - csr.indptr[rows])).astype(np.float64)
+    return smat.csr_matrix((rel, csr.indices.copy(), csr.indptr.copy()), shape=csr.shape)
+
+
+def _exp_f32(x):
+    """exp of a float32 array taken in float64 and rounded to float32 (the device's ``ref_expf``)."""
+    return np.exp(x.astype(np.float64)).astype(np.float32)
+
+
+def _sigmoid_csr(csr):
+    """``sigmoid_average``'s transform in fp32 steps: 1 / (1 + exp(-z)).  Returns a new matrix (the reference overwrites its argument)."""
+    one = np.float32(1)
+    with np.errstate(over="ignore", invalid="ignore"):
+        data = one / (one + _exp_f32(-csr.data.astype(np.float32)))
+    return smat.csr_matrix((data, csr.indices.copy(), csr.indptr.copy()), shape=csr.shape)
+
+
+def _softmax_csrs(mats):
+    """``csr_row_softmax`` of every matrix by the device's rule (include/xrl_abi.h, method 4): per row and matrix x_max = amax, e = exp(x -
+    x_max) rounded to fp32, denominator = the fp64 sum of e in the kernel's order -- entry j of the row's model-ordered list belongs to lane
+    j % 64, a lane adds its entries in ascending j, the lanes meet in six exchange steps -- rounded once to fp32.  An empty row of a matrix
+    contributes nothing."""
+    out = [smat.csr_matrix((m.data.astype(np.float32), m.indices.copy(), m.indptr.copy()), shape=m.shape) for m in mats]
+    lanes = np.arange(64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for r in range(out[0].shape[0]):
+            pre = 0
+            for m in out:
+                a, b = int(m.indptr[r]), int(m.indptr[r + 1])
+                if b > a:
+                    x = m.data[a:b]
+                    e = _exp_f32(x - np.amax(x))
+                    s = np.zeros(64, dtype=np.float64)
+                    np.add.at(s, (pre + np.arange(b - a)) % 64, e.astype(np.float64))      # (unbuffered: in ascending j per lane)
+                    for d in (1, 2, 4, 8, 16, 32):
+                        s = s + s[lanes ^ d]
+                    m.data[a:b] = e / np.float32(s[0])
+                pre += b - a
+    return out
+
+
+def ensemble_host(mats, method="average", only_topk=None):
+    """The methods of ``CsrEnsembler`` (smat_util.py:814-923) on the host, written against scipy by the rules the device merge follows
+    (include/xrl_abi.h): ``average``; ``rank_average``; ``sigmoid_average`` (1 / (1 + exp(-z)) in fp32 steps, then average);
+    ``softmax_average`` (softmax over the stored entries of every row of every matrix, then average; an empty row contributes nothing, where
+    the reference raises); ``round_robin`` (fp64 relevance ``mm - p + (M - m) / (M + 1)``, maximum over the holders).  The exponentials are
+    taken in float64 and rounded to float32.  Rows must be stored best first; the inputs are left as they are.  ``only_topk``:
+    ``TransformerMatcher.ensemble_prediction``'s last line, ``sorted_csr(ret.astype(float32), only_topk)``.  rank_average and round_robin
+    return float64 like the reference."""
+    if method not in ENSEMBLE_METHOD_NAMES:
+        raise ValueError(f"ensemble method {method!r}: expected one of {list(ENSEMBLE_METHOD_NAMES)}")
+    mats = [m.tocsr() for m in mats]
+    assert all(m.shape == mats[0].shape for m in mats)
+    M = len(mats)
+    if method in ("rank_average", "round_robin"):
+        mm = max(int(np.diff(m.indptr).max(initial=0)) for m in mats)
+        if method == "rank_average":
+            ret = sum(_relevance_csr(m, mm) for m in mats).tocsr()
+        else:
+            base = 1.0 / (M + 1.0)
+            ret = None
+            for i, m in enumerate(mats):
+                rel = _relevance_csr(m, mm)
+                rel.data += (M - i) * base
+                ret = rel if ret is None else ret.maximum(rel)
+        ret = sorted_csr(ret.tocsr())
+        ret.data /= M
+    else:
+        if method == "sigmoid_average":
+            mats = [_sigmoid_csr(m) for m in mats]
+        elif method == "softmax_average":
+            mats = _softmax_csrs(mats)
+        ret = ensemble_average(mats)
+    if only_topk is not None:
+        ret = sorted_csr(ret.astype(np.float32), only_topk=only_topk)
+    return ret
+
+
+def ensemble_prediction_device(transformer_pred, concat_pred, only_topk, ens_method):
+    """``TransformerMatcher.ensemble_prediction`` (pecos/xmc/xtransformer/matcher.py:535-579) on two ``(labels, scores, counts)`` device
+    triples: ``ens_method`` is ``"concat-only"``, ``"transformer-only"``, ``"average"``, ``"rank_average"`` or ``"round_robin"``; the merged
+    rows are ranked by their fp32 value (ties by label) and cut to ``only_topk`` (``None``: all), as its last line does.  Returns a triple.
+
+    Precondition: the rows of both inputs are stored in ``sorted_csr`` order -- score descending, ties by ascending label.  The reference
+    re-sorts its inputs that way before rank_average and round_robin look at the positions; a predict stores ties by candidate position, so
+    rows with tied scores may need that sort first (average, concat-only and transformer-only do not depend on the stored order)."""
+    if transformer_pred[0].shape[0] != concat_pred[0].shape[0]:
+        raise ValueError(f"Transformer/concat prediction mismatch: {tuple(transformer_pred[0].shape)} and {tuple(concat_pred[0].shape)}")
+    if ens_method == "concat-only":
+        results, mode = [concat_pred], "average"                  # (one model: nothing summed or dropped, value / 1)
+    elif ens_method == "transformer-only":
+        results, mode = [transformer_pred], "average"
+    elif ens_method in ("average", "rank_average", "round_robin"):
+        results, mode = [transformer_pred, concat_pred], ens_method
+    else:
+        raise ValueError(f"Unknown ensemble method {ens_method}")
+    total = sum(r[0].shape[1] for r in results)
+    return ensemble_device(results, mode=mode, only_topk=only_topk if only_topk is not None else max(total, 1))
 
 
 class Text2Text:
