@@ -306,7 +306,7 @@ int xrl_ensemble_device(int device, uint32_t n_models, uint32_t rows,
                         uint32_t only_topk /* 0 = all; finish only */,
                         uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride, void* hip_stream, int sync);
 
-/* The other methods of CsrEnsembler on the device (K6M), and the cut of TransformerMatcher.ensemble_prediction
+/* The other methods of CsrEnsembler on the device (K6 too), and the cut of TransformerMatcher.ensemble_prediction
  * (pecos/xmc/xtransformer/matcher.py:535-579).  Inputs, output, tables and capacity are xrl_ensemble_device's: n_models <= 8 results over
  * the same rows, sum(in_stride) <= 1024, a count above its stride is read as the stride, inputs are only read.  M = n_models; a "segment"
  * is one model's entries of a row, p an entry's position in its segment.

@@ -675,39 +675,36 @@ class corelib(object):
         return rc
 
     ENSEMBLE_MODES = {"average": 0, "finish": 1, "rank_average": 2}
+    # xrl_ensemble_methods_device's numbers (finish is listed for its number only: that entry point refuses it)
+    ENSEMBLE_METHODS = {"average": 0, "finish": 1, "rank_average": 2, "sigmoid_average": 3, "softmax_average": 4, "round_robin": 5}
+
+    def _ensemble_call(self, fn, device, rows, d_idx, d_val, d_cnt, in_stride, middle, d_out_idx, d_out_val, d_out_cnt, out_stride, stream, sync):
+        """The pointer tables and the call of either ensemble entry point; ``middle``: its arguments between the strides and the outputs."""
+        n = len(d_idx)
+        assert len(d_val) == n and len(d_cnt) == n and len(in_stride) == n
+        tab = lambda a: (c_void_p * max(n, 1))(*[c_void_p(int(x) if x else 0) for x in a])                   # noqa: E731
+        rc = fn(int(device), n, int(rows), tab(d_idx), tab(d_val), tab(d_cnt), (c_uint32 * max(n, 1))(*[int(s) for s in in_stride]), *middle,
+                c_void_p(d_out_idx), c_void_p(d_out_val), c_void_p(d_out_cnt), int(out_stride), c_void_p(stream or 0), 1 if sync else 0)
+        self._check()
+        return rc
 
     def ensemble_device(self, device, rows, d_idx, d_val, d_cnt, in_stride, mode, threshold, only_topk, d_out_idx, d_out_val, d_out_cnt,
                         out_stride, stream=None, sync=True):
         """K6: merge the fixed-stride results of ``len(d_idx)`` models (lists of raw device addresses, one per model, and their row
         strides) into one, on the device.  ``mode``: a key of ``ENSEMBLE_MODES`` or its number; ``threshold`` / ``only_topk``: mode
         ``finish`` only, ``None`` = none."""
-        n = len(d_idx)
-        assert len(d_val) == n and len(d_cnt) == n and len(in_stride) == n
-        tab = lambda a: (c_void_p * max(n, 1))(*[c_void_p(int(x) if x else 0) for x in a])                   # noqa: E731
-        rc = self.clib_float32.xrl_ensemble_device(
-            int(device), n, int(rows), tab(d_idx), tab(d_val), tab(d_cnt), (c_uint32 * max(n, 1))(*[int(s) for s in in_stride]),
-            self.ENSEMBLE_MODES.get(mode, mode), None if threshold is None else ctypes.byref(c_float(threshold)), only_topk or 0,
-            c_void_p(d_out_idx), c_void_p(d_out_val), c_void_p(d_out_cnt), int(out_stride), c_void_p(stream or 0), 1 if sync else 0)
-        self._check()
-        return rc
-
-    # xrl_ensemble_methods_device's numbers (finish is listed for its number only: that entry point refuses it)
-    ENSEMBLE_METHODS = {"average": 0, "finish": 1, "rank_average": 2, "sigmoid_average": 3, "softmax_average": 4, "round_robin": 5}
+        middle = (self.ENSEMBLE_MODES.get(mode, mode), None if threshold is None else ctypes.byref(c_float(threshold)), only_topk or 0)
+        return self._ensemble_call(self.clib_float32.xrl_ensemble_device, device, rows, d_idx, d_val, d_cnt, in_stride, middle,
+                                   d_out_idx, d_out_val, d_out_cnt, out_stride, stream, sync)
 
     def ensemble_methods_device(self, device, rows, d_idx, d_val, d_cnt, in_stride, method, only_topk, d_out_idx, d_out_val, d_out_cnt,
                                 out_stride, stream=None, sync=True):
-        """K6M: like :meth:`ensemble_device` for the methods of ``CsrEnsembler`` -- ``method``: a key of ``ENSEMBLE_METHODS`` (not
+        """K6: like :meth:`ensemble_device` for the methods of ``CsrEnsembler`` -- ``method``: a key of ``ENSEMBLE_METHODS`` (not
         ``finish``) or its number; ``only_topk``: ``None`` / 0 = the method's own rows, else they are ranked again by their fp32 value and
         cut, as ``TransformerMatcher.ensemble_prediction`` does."""
-        n = len(d_idx)
-        assert len(d_val) == n and len(d_cnt) == n and len(in_stride) == n
-        tab = lambda a: (c_void_p * max(n, 1))(*[c_void_p(int(x) if x else 0) for x in a])                   # noqa: E731
-        rc = self.clib_float32.xrl_ensemble_methods_device(
-            int(device), n, int(rows), tab(d_idx), tab(d_val), tab(d_cnt), (c_uint32 * max(n, 1))(*[int(s) for s in in_stride]),
-            self.ENSEMBLE_METHODS.get(method, method), only_topk or 0,
-            c_void_p(d_out_idx), c_void_p(d_out_val), c_void_p(d_out_cnt), int(out_stride), c_void_p(stream or 0), 1 if sync else 0)
-        self._check()
-        return rc
+        middle = (self.ENSEMBLE_METHODS.get(method, method), only_topk or 0)
+        return self._ensemble_call(self.clib_float32.xrl_ensemble_methods_device, device, rows, d_idx, d_val, d_cnt, in_stride, middle,
+                                   d_out_idx, d_out_val, d_out_cnt, out_stride, stream, sync)
 
     METRICS_MAX = 1024          # capacity of K8 (xrl_metrics_device): entries per result row, and positions
 

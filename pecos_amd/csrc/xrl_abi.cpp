@@ -333,12 +333,13 @@ int xrl_predict_device_rows(void* model, void* queries, uint32_t beam_size, cons
     return predict_device_entry("xrl_predict_device_rows", true, model, queries, beam_size, post_processor, only_topk, d_out_idx, d_out_val, d_out_cnt, out_stride, hip_stream, sync, row_begin, row_count);
 }
 
-int xrl_ensemble_device(int device, uint32_t n_models, uint32_t rows, const uint32_t* const* d_idx, const float* const* d_val,
-                        const uint32_t* const* d_cnt, const uint32_t* in_stride, int mode, const float* threshold, uint32_t only_topk,
-                        uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride, void* hip_stream, int sync) {
+// xrl_ensemble_device and xrl_ensemble_methods_device (`methods`: no finish, no threshold, only_topk cuts every method)
+static int ensemble_entry(const char* name, bool methods, int device, uint32_t n_models, uint32_t rows, const uint32_t* const* d_idx,
+                          const float* const* d_val, const uint32_t* const* d_cnt, const uint32_t* in_stride, int mode, const float* threshold,
+                          uint32_t only_topk, uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride, void* hip_stream, int sync) {
     return guarded_value(-1, [&] {
         // every argument is checked before the GPU is required
-        const std::string what = "xrl_ensemble_device: ";
+        const std::string what = std::string(name) + ": ";
         if (!d_idx || !d_val || !d_cnt || !in_stride || !d_out_idx || !d_out_val || !d_out_cnt) fail(what + "null argument");
         if (n_models == 0 || n_models > (uint32_t)kEnsembleMaxModels) fail(what + "n_models must be 1.." + std::to_string(kEnsembleMaxModels) + ", got " + std::to_string(n_models));
         EnsembleArgs A{};
@@ -349,9 +350,14 @@ int xrl_ensemble_device(int device, uint32_t n_models, uint32_t rows, const uint
             total += in_stride[m];
         }
         if (total > kEnsembleMaxTotal) fail(what + "the input strides sum to " + std::to_string(total) + ", more than " + std::to_string(kEnsembleMaxTotal));
-        if (mode != kEnsembleAverage && mode != kEnsembleFinish && mode != kEnsembleRankAverage) fail(what + "unknown mode " + std::to_string(mode));
-        if (mode != kEnsembleFinish && (threshold || only_topk)) fail(what + "threshold and only_topk belong to mode finish");
-        const uint64_t longest = mode == kEnsembleFinish && only_topk ? std::min<uint64_t>(total, only_topk) : total;
+        if (methods) {
+            if (mode == kEnsembleFinish) fail(what + "method 1 (finish) is served by xrl_ensemble_device");
+            if (mode < kEnsembleAverage || mode > kEnsembleRoundRobin) fail(what + "unknown method " + std::to_string(mode));
+        } else {
+            if (mode != kEnsembleAverage && mode != kEnsembleFinish && mode != kEnsembleRankAverage) fail(what + "unknown mode " + std::to_string(mode));
+            if (mode != kEnsembleFinish && (threshold || only_topk)) fail(what + "threshold and only_topk belong to mode finish");
+        }
+        const uint64_t longest = only_topk ? std::min<uint64_t>(total, only_topk) : total;
         if (out_stride < longest) fail(what + "out_stride " + std::to_string(out_stride) + " smaller than the longest possible row, " + std::to_string(longest));
         if (rows == 0) return 0;
         require_gpu();
@@ -360,9 +366,9 @@ int xrl_ensemble_device(int device, uint32_t n_models, uint32_t rows, const uint
         A.has_threshold = threshold ? 1 : 0; A.threshold = threshold ? *threshold : 0.0f; A.only_topk = only_topk;
         A.out_idx = d_out_idx; A.out_val = d_out_val; A.out_cnt = d_out_cnt; A.out_stride = out_stride;
         hipStream_t s = static_cast<hipStream_t>(hip_stream);
-        // rank_average's device scalar lives and dies in stream order: no synchronisation, and concurrent calls do not share it
+        // the device scalar of rank_average and round_robin lives and dies in stream order: no synchronisation, and concurrent calls do not share it
         void* mm = nullptr;
-        if (mode == kEnsembleRankAverage) XRL_HIP(hipMallocAsync(&mm, sizeof(uint32_t), s));
+        if (mode == kEnsembleRankAverage || mode == kEnsembleRoundRobin) XRL_HIP(hipMallocAsync(&mm, sizeof(uint32_t), s));
         try { launch_ensemble(A, static_cast<uint32_t*>(mm), s); }
         catch (...) { if (mm) (void)hipFreeAsync(mm, s); throw; }
         if (mm) XRL_HIP(hipFreeAsync(mm, s));
@@ -371,42 +377,16 @@ int xrl_ensemble_device(int device, uint32_t n_models, uint32_t rows, const uint
     });
 }
 
+int xrl_ensemble_device(int device, uint32_t n_models, uint32_t rows, const uint32_t* const* d_idx, const float* const* d_val,
+                        const uint32_t* const* d_cnt, const uint32_t* in_stride, int mode, const float* threshold, uint32_t only_topk,
+                        uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride, void* hip_stream, int sync) {
+    return ensemble_entry("xrl_ensemble_device", false, device, n_models, rows, d_idx, d_val, d_cnt, in_stride, mode, threshold, only_topk, d_out_idx, d_out_val, d_out_cnt, out_stride, hip_stream, sync);
+}
+
 int xrl_ensemble_methods_device(int device, uint32_t n_models, uint32_t rows, const uint32_t* const* d_idx, const float* const* d_val,
                                 const uint32_t* const* d_cnt, const uint32_t* in_stride, int method, uint32_t only_topk,
                                 uint32_t* d_out_idx, float* d_out_val, uint32_t* d_out_cnt, uint32_t out_stride, void* hip_stream, int sync) {
-    return guarded_value(-1, [&] {
-        // every argument is checked before the GPU is required, in xrl_ensemble_device's order
-        const std::string what = "xrl_ensemble_methods_device: ";
-        if (!d_idx || !d_val || !d_cnt || !in_stride || !d_out_idx || !d_out_val || !d_out_cnt) fail(what + "null argument");
-        if (n_models == 0 || n_models > (uint32_t)kEnsembleMaxModels) fail(what + "n_models must be 1.." + std::to_string(kEnsembleMaxModels) + ", got " + std::to_string(n_models));
-        EnsembleArgs A{};
-        uint64_t total = 0;
-        for (uint32_t m = 0; m < n_models; ++m) {
-            if (!d_idx[m] || !d_val[m] || !d_cnt[m]) fail(what + "null device pointer for model " + std::to_string(m));
-            A.idx[m] = d_idx[m]; A.val[m] = d_val[m]; A.cnt[m] = d_cnt[m]; A.stride[m] = in_stride[m];
-            total += in_stride[m];
-        }
-        if (total > kEnsembleMaxTotal) fail(what + "the input strides sum to " + std::to_string(total) + ", more than " + std::to_string(kEnsembleMaxTotal));
-        if (method == kEnsembleFinish) fail(what + "method 1 (finish) is served by xrl_ensemble_device");
-        if (method != kEnsembleAverage && method != kEnsembleRankAverage && method != kEnsembleSigmoidAverage &&
-            method != kEnsembleSoftmaxAverage && method != kEnsembleRoundRobin) fail(what + "unknown method " + std::to_string(method));
-        const uint64_t longest = only_topk ? std::min<uint64_t>(total, only_topk) : total;
-        if (out_stride < longest) fail(what + "out_stride " + std::to_string(out_stride) + " smaller than the longest possible row, " + std::to_string(longest));
-        if (rows == 0) return 0;
-        require_gpu();
-        use_device(device);
-        A.n_models = n_models; A.rows = rows; A.mode = method; A.only_topk = only_topk;
-        A.out_idx = d_out_idx; A.out_val = d_out_val; A.out_cnt = d_out_cnt; A.out_stride = out_stride;
-        hipStream_t s = static_cast<hipStream_t>(hip_stream);
-        // the device scalar of rank_average and round_robin lives and dies in stream order, as xrl_ensemble_device's
-        void* mm = nullptr;
-        if (method == kEnsembleRankAverage || method == kEnsembleRoundRobin) XRL_HIP(hipMallocAsync(&mm, sizeof(uint32_t), s));
-        try { launch_ensemble_methods(A, static_cast<uint32_t*>(mm), s); }
-        catch (...) { if (mm) (void)hipFreeAsync(mm, s); throw; }
-        if (mm) XRL_HIP(hipFreeAsync(mm, s));
-        if (sync) XRL_HIP(hipStreamSynchronize(s));
-        return 0;
-    });
+    return ensemble_entry("xrl_ensemble_methods_device", true, device, n_models, rows, d_idx, d_val, d_cnt, in_stride, method, nullptr, only_topk, d_out_idx, d_out_val, d_out_cnt, out_stride, hip_stream, sync);
 }
 
 int xrl_metrics_device(int device, uint32_t rows, const uint32_t* d_idx, const float* d_val, const uint32_t* d_cnt, uint32_t stride,

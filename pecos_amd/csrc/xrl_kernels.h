@@ -156,12 +156,14 @@ void launch_k2_topk_big(const LayerDev& L, const LayerPlan& P, BeamDev prev, con
                         uint32_t* out_idx, float* out_val, uint32_t* out_cnt, uint32_t out_stride, hipStream_t s);
 
 // xrl_ensemble.hip, K6: the result rows of n_models predicts (xrl_predict_device's output form, idx / val row stride stride[m]) merged
-// into one fixed-stride result like CsrEnsembler.average, Text2Text.predict's tail or CsrEnsembler.rank_average do on the host.  The
-// pointer tables travel to the kernel by value.  Capacity: n_models <= 8, sum of the strides <= 1024 (one wavefront holds a row).
+// into one fixed-stride result like CsrEnsembler's average, rank_average, sigmoid_average, softmax_average and round_robin or
+// Text2Text.predict's tail do on the host, each but finish with an optional cut (A.only_topk) like
+// TransformerMatcher.ensemble_prediction's.  One kernel serves every mode.  The pointer tables travel to the kernel by value.
+// Capacity: n_models <= 8, sum of the strides <= 1024 (one wavefront holds a row).
 constexpr int kEnsembleMaxModels = 8;
 constexpr uint32_t kEnsembleMaxTotal = 1024;
-constexpr int kEnsembleWaves = 4;                // wavefronts (= rows) per workgroup of K6 and K6M
-// modes 0-2 are xrl_ensemble_device's; xrl_ensemble_methods_device (K6M, xrl_ensemble_methods.hip) serves 0, 2 and 3-5
+constexpr int kEnsembleWaves = 4;                // wavefronts (= rows) per workgroup of K6
+// modes 0-2 are xrl_ensemble_device's; xrl_ensemble_methods_device serves 0, 2 and 3-5
 enum { kEnsembleAverage = 0, kEnsembleFinish = 1, kEnsembleRankAverage = 2, kEnsembleSigmoidAverage = 3, kEnsembleSoftmaxAverage = 4,
        kEnsembleRoundRobin = 5 };
 struct EnsembleArgs {
@@ -173,20 +175,15 @@ struct EnsembleArgs {
     int mode;
     int has_threshold;                            // finish only
     float threshold;
-    uint32_t only_topk;                           // finish, and every mode of K6M; 0 = all
+    uint32_t only_topk;                           // finish: the cut after the threshold; every other mode: the cut of xrl_ensemble_methods_device; 0 = all
     uint32_t* out_idx;
     float* out_val;
     uint32_t* out_cnt;
     uint32_t out_stride;                          // >= the longest possible output row (the caller checks)
 };
 uint32_t ensemble_slots(uint32_t stride_sum);     // entries per lane (1, 2, 4, 8 or 16) of the instantiation that serves this total
-// mm_scratch: one device uint32 (rank_average only: the call's largest row length, reduced on `s` ahead of K6)
+// mm_scratch: one device uint32 (rank_average and round_robin only: the call's largest row length, reduced on `s` ahead of K6)
 void launch_ensemble(const EnsembleArgs& A, uint32_t* mm_scratch, hipStream_t s);
-void launch_ensemble_max_len(const EnsembleArgs& A, uint32_t* mm, hipStream_t s);   // *mm = the call's largest (clamped) row length, on `s`
-// xrl_ensemble_methods.hip, K6M: sigmoid_average, softmax_average and round_robin of CsrEnsembler, and average / rank_average, each with
-// an optional cut (A.only_topk) like TransformerMatcher.ensemble_prediction's.  A.mode: not finish; threshold unused.  mm_scratch: one
-// device uint32, for rank_average and round_robin.
-void launch_ensemble_methods(const EnsembleArgs& A, uint32_t* mm_scratch, hipStream_t s);
 
 // xrl_metrics.hip, K8: the sums behind precision / recall at 1 .. topk (smat_util.Metrics.generate) of one fixed-stride result against the true
 // labels as a device CSR pattern.  One wavefront per block of R(rows) consecutive rows writes one partial; a one-workgroup kernel adds the

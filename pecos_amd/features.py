@@ -13,7 +13,7 @@
   one model's candidates with another without a host round trip.
 * :func:`ensemble_device` -- the results of several models merged on the device (K6) like ``CsrEnsembler.average`` / ``rank_average`` /
   ``Text2Text.predict``'s tail; :func:`predict_text` and :class:`Text2Text` use it for ensembles that share a device.  ``sigmoid_average``,
-  ``softmax_average``, ``round_robin`` and ``only_topk`` go through K6M; :func:`ensemble_prediction_device` is
+  ``softmax_average``, ``round_robin`` and ``only_topk`` go through ``xrl_ensemble_methods_device``; :func:`ensemble_prediction_device` is
   ``TransformerMatcher.ensemble_prediction`` on two device results, :func:`ensemble_host` the same methods on scipy matrices.
 * :func:`metrics_device` / :func:`metrics_sums_device` / :class:`Metrics` -- ``smat_util.Metrics.generate`` (precision and recall at
   1 .. topk) from a result in HBM (K8): 2 x topk numbers come back instead of the result.
@@ -335,14 +335,14 @@ def ensemble_device(results, mode="average", threshold=None, only_topk=None, str
     the same form, its rows ordered and valued like the host code's: ``mode="average"`` = :func:`ensemble_average`
     (``CsrEnsembler.average``), ``"finish"`` = :meth:`Text2Text.finish` (average, ``threshold``, ``sorted_csr(only_topk)``),
     ``"rank_average"`` = ``CsrEnsembler.rank_average``.  ``"sigmoid_average"``, ``"softmax_average"`` and ``"round_robin"`` are
-    ``CsrEnsembler``'s methods of those names (K6M; see :func:`ensemble_host` for their rules); with them, and with ``"average"`` /
+    ``CsrEnsembler``'s methods of those names (see :func:`ensemble_host` for their rules); with them, and with ``"average"`` /
     ``"rank_average"``, ``only_topk`` ranks the merged rows again by their fp32 value and cuts them, as
     ``TransformerMatcher.ensemble_prediction`` does.  Runs on ``stream`` (a raw HIP stream; default: torch's current one); inputs and
     outputs must be ordered on it."""
     import torch
     if mode not in clib.ENSEMBLE_METHODS:
         raise ValueError(f"ensemble mode {mode!r}: expected one of {sorted(clib.ENSEMBLE_METHODS)}")
-    methods = mode not in clib.ENSEMBLE_MODES or (mode != "finish" and bool(only_topk))     # K6M's part; everything else is K6's, as before
+    methods = mode not in clib.ENSEMBLE_MODES or (mode != "finish" and bool(only_topk))     # xrl_ensemble_methods_device's part; everything else is xrl_ensemble_device's
     if methods and threshold is not None:
         raise ValueError(f"ensemble mode {mode!r}: a threshold belongs to mode 'finish'")
     if not results:
@@ -363,14 +363,14 @@ def ensemble_device(results, mode="average", threshold=None, only_topk=None, str
         o_idx = torch.empty((rows, out_stride), dtype=torch.int32, device=dev)
         o_sc = torch.empty((rows, out_stride), dtype=torch.float32, device=dev)
         o_cnt = torch.empty((rows,), dtype=torch.int32, device=dev)
-        if rows and out_stride and methods:
-            clib.ensemble_methods_device(dev.index, rows, [r[0].data_ptr() for r in res], [r[1].data_ptr() for r in res],
-                                         [r[2].data_ptr() for r in res], [r[0].shape[1] for r in res], mode, only_topk, o_idx.data_ptr(),
-                                         o_sc.data_ptr(), o_cnt.data_ptr(), out_stride, stream=s or None, sync=sync)
-        elif rows and out_stride:
-            clib.ensemble_device(dev.index, rows, [r[0].data_ptr() for r in res], [r[1].data_ptr() for r in res], [r[2].data_ptr() for r in res],
-                                 [r[0].shape[1] for r in res], mode, threshold, only_topk, o_idx.data_ptr(), o_sc.data_ptr(),
-                                 o_cnt.data_ptr(), out_stride, stream=s or None, sync=sync)
+        if rows and out_stride:
+            ins = (dev.index, rows, [r[0].data_ptr() for r in res], [r[1].data_ptr() for r in res], [r[2].data_ptr() for r in res],
+                   [r[0].shape[1] for r in res])
+            outs = (o_idx.data_ptr(), o_sc.data_ptr(), o_cnt.data_ptr(), out_stride)
+            if methods:
+                clib.ensemble_methods_device(*ins, mode, only_topk, *outs, stream=s or None, sync=sync)
+            else:
+                clib.ensemble_device(*ins, mode, threshold, only_topk, *outs, stream=s or None, sync=sync)
         else:
             o_cnt.zero_()
     return o_idx, o_sc, o_cnt
@@ -559,7 +559,7 @@ def predict_text(vectorizer, models, corpus, X_emb=None, normalize_emb=True, thr
     otherwise; ``"device"`` raises where "auto" would take the host path; ``"host"`` is the host path (one tokenisation, upload and copy
     back per model, scipy's merge).  The result is the same bit for bit.  ``finish=(threshold, only_topk)`` also applies
     :meth:`Text2Text.finish`'s threshold and cut to the merged rows (on whichever path).  ``ensemble_method``: any method of
-    ``CsrEnsembler`` (:data:`ENSEMBLE_METHOD_NAMES`; default ``"average"``) -- merged on the device (K6M) where ``ensemble`` allows it, by
+    ``CsrEnsembler`` (:data:`ENSEMBLE_METHOD_NAMES`; default ``"average"``) -- merged on the device (K6) where ``ensemble`` allows it, by
     :func:`ensemble_host` otherwise, values as float32 either way; ``finish`` goes with ``"average"`` only.
 
     ``tokenizer="host"`` (default) counts the terms on host threads; ``"device"`` uploads the text once and counts on the GPU (K9) -- the same

@@ -1,7 +1,7 @@
 """The ensemble methods on the GPU box (profiles/ensemble_methods.md): the time of every method of `features.ensemble_device` next to
 `average` in ONE process, at the shape of scripts/ensemble_bench.py -- the top-k of three Eurlex-4K-shape models (seeds 0-2) over 100 000
-rows, k = 10 and k = 100 -- between events on one stream, median of 5 launches after a warm-up.  `average` is timed through K6
-(xrl_ensemble_device) and, with only_topk, through K6M (xrl_ensemble_methods_device).
+rows, k = 10 and k = 100 -- between events on one stream, median of 5 launches after a warm-up.  `average` is timed through
+xrl_ensemble_device and, with only_topk, through xrl_ensemble_methods_device; `finish` is xrl_ensemble_device's cut.
 
 Usage: python scripts/ensemble_methods_bench.py [--rows 100000] [--out FILE.json]   (the result is printed as one JSON line)"""
 import argparse
@@ -42,7 +42,7 @@ def main():
         outs = [features.predict_from_torch(m, crow, col, val, D, beam_size=max(cfg["beam"], k), only_topk=k) for m in models]
         torch.cuda.synchronize()
         s = torch.cuda.Stream()
-        for mode, topk in (("average", None), ("average", k), ("rank_average", None), ("sigmoid_average", None), ("softmax_average", None),
+        for mode, topk in (("average", None), ("average", k), ("finish", k), ("rank_average", None), ("sigmoid_average", None), ("softmax_average", None),
                            ("round_robin", None), ("round_robin", k)):
             ts = []
             for rep in range(6):

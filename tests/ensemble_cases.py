@@ -1,5 +1,6 @@
 """What the ensemble tests (test_ensemble_cpu.py, test_gpu_ensemble.py) and the fixture generator (golden/make_golden_ensemble.py) share:
-the case list, the `finish` settings, and the fixtures' array forms.
+the case list, the `finish` settings, and the fixtures' array forms; and what test_gpu_ensemble.py and test_gpu_ensemble_methods.py
+share on the GPU: upload, fixed-stride result -> rows, the sentinel-filled raw call, the padded and over-count inputs, `text_models`.
 
 A fixture tests/golden/ensemble/<case>.npz holds, per model m, the fixed-stride arrays K6 reads (idx<m> u32 [rows, stride_m], val<m> f32,
 cnt<m> u32 [rows]; entries beyond cnt are filler), n_cols, and the reference's outputs as raw CSR triplets (<name>_indptr / _indices /
@@ -8,6 +9,7 @@ FINISH[i]."""
 import os
 
 import numpy as np
+import pytest
 import scipy.sparse as smat
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ensemble")
@@ -61,6 +63,81 @@ class Case:
         """(indptr int64, indices uint32, fp32 value bits) of a recorded output; the float64 of rank_average cast like K6 casts it."""
         ip, ix, dv = self.out[name]
         return ip.astype(np.int64), ix.astype(np.uint32), dv.astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------ what the two GPU test files share
+def upload(c):
+    """A case's models as the (labels, scores, counts) CUDA tensors ensemble_device takes."""
+    import torch
+    return [(torch.from_numpy(i.view(np.int32)).cuda(), torch.from_numpy(v).cuda(), torch.from_numpy(n.view(np.int32)).cuda())
+            for i, v, n in zip(c.idx, c.val, c.cnt)]
+
+
+def rows_of(o_idx, o_sc, o_cnt):
+    """(indptr, labels, values) of a fixed-stride device result; entries beyond a row's count are not looked at."""
+    idx, sc, cnt = o_idx.cpu().numpy().view(np.uint32), o_sc.cpu().numpy(), o_cnt.cpu().numpy().astype(np.int64)
+    assert (cnt >= 0).all() and (cnt <= idx.shape[1]).all()
+    mask = np.arange(idx.shape[1])[None, :] < cnt[:, None]
+    return np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64), idx[mask], sc[mask]
+
+
+SENTINEL = 0x5A5A5A5A
+
+
+def raw_call(entry, c, t, args, out_stride, stream=None, sync=True):
+    """clib.<entry>(..., *args, ...) on the tensors `t` of case `c`, into outputs filled with SENTINEL / -7.0 / -1."""
+    import torch
+    from pecos_amd import clib
+    o_idx = torch.full((c.rows, out_stride), SENTINEL, dtype=torch.int32, device="cuda")
+    o_sc = torch.full((c.rows, out_stride), -7.0, dtype=torch.float32, device="cuda")
+    o_cnt = torch.full((c.rows,), -1, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    getattr(clib, entry)(0, c.rows, [x[0].data_ptr() for x in t], [x[1].data_ptr() for x in t], [x[2].data_ptr() for x in t],
+                         [x[0].shape[1] for x in t], *args, o_idx.data_ptr(), o_sc.data_ptr(), o_cnt.data_ptr(), out_stride,
+                         stream=stream, sync=sync)
+    return o_idx, o_sc, o_cnt
+
+
+def untouched_tail(o):
+    """Nothing is written beyond a row's count."""
+    cnt = o[2].cpu().numpy()
+    tail = np.arange(o[0].shape[1])[None, :] >= cnt[:, None]
+    return (o[0].cpu().numpy()[tail] == SENTINEL).all() and (o[1].cpu().numpy()[tail] == -7.0).all()
+
+
+def over_counts(t):
+    """Counts above the stride where a row is full (read as the stride)."""
+    import torch
+    return [(i, v, torch.where(n == i.shape[1], n + 4000, n)) for i, v, n in t]
+
+
+def padded(c, t, pad):
+    """Input strides `pad` larger than the rows, filler behind every row."""
+    import torch
+    wide = []
+    for i, v, n in t:
+        wi = torch.full((c.rows, i.shape[1] + pad), 424242, dtype=torch.int32, device="cuda"); wi[:, : i.shape[1]] = i
+        wv = torch.full((c.rows, i.shape[1] + pad), 3.5, dtype=torch.float32, device="cuda"); wv[:, : i.shape[1]] = v
+        wide.append((wi, wv, n))
+    return wide
+
+
+@pytest.fixture(scope="module")
+def text_models(tmp_path_factory):
+    """(vectorizer, corpus, three models on its features, three on its features + H embedding columns, H)"""
+    import xrl_synth
+    from pecos_amd import XLinearModel as XLM
+    from pecos_amd.features import Tfidf
+    from test_tfidf import _case
+    folder, corpus, X = _case("word_bigram_trunc")
+    D, H = X.shape[1], 16
+    root = tmp_path_factory.mktemp("ens")
+    plain, concat = [], []
+    for i, seed in enumerate((81, 82, 83)):
+        xrl_synth.make_model(str(root / f"p{i}"), D, 600, [120, 60, 20], seed=seed, shape=[6, 48, 600])
+        xrl_synth.make_model(str(root / f"c{i}"), D + H, 600, [120, 60, 20], seed=seed + 10, shape=[6, 48, 600])
+        plain.append(XLM.load(str(root / f"p{i}"))); concat.append(XLM.load(str(root / f"c{i}")))
+    return Tfidf.load(folder), corpus, plain, concat, H
 
 
 def same_rows(got, want, what=""):

@@ -101,17 +101,20 @@ def test_predict_text_rejects_an_unknown_ensemble_value():
 
 
 def test_k6_resources(tmp_path):
-    # every instantiation: no scratch, no spills, wavefront-private LDS of at most 8 KB per wavefront (4 wavefronts per workgroup)
+    # every instantiation of the one kernel: no scratch, no spills to memory, wavefront-private LDS of at most 8 KB per wavefront (4 wavefronts per workgroup)
     from test_kernel_resources import demangle, kernel_notes
     notes = kernel_notes(tmp_path)
     nice = demangle(sorted(notes))
-    k6 = {nice[k]: v for k, v in notes.items() if "ensemble_kernel<" in nice[k]}
     seen = set()
-    for name, d in k6.items():
-        ns, rank = re.search(r"ensemble_kernel<(\d+), (true|false)>", name).groups()
-        seen.add((int(ns), rank))
-        assert d["scratch"] == 0 and d["vgpr_spill"] == 0, (name, d)      # (the 16-entry instantiations park some SGPRs in VGPR lanes: no memory)
-        assert d["lds"] == int(ns) * 64 * 8 * 4 and d["lds"] <= 8192 * 4, (name, d)
-    assert seen == {(ns, r) for ns in (1, 2, 4, 8, 16) for r in ("true", "false")}, sorted(seen)
+    for k, d in notes.items():
+        got = re.search(r"ensemble_kernel<(\d+), (\d+)>", nice[k])
+        if not got:
+            continue
+        ns, method = int(got.group(1)), int(got.group(2))
+        seen.add((ns, method))
+        assert d["scratch"] == 0 and d["vgpr_spill"] == 0, (nice[k], d)      # (the 16-entry instantiations park some SGPRs in VGPR lanes: no memory)
+        assert d["lds"] == ns * 64 * 8 * 4 and d["lds"] <= 8192 * 4, (nice[k], d)
+    assert seen == {(ns, m) for ns in (1, 2, 4, 8, 16) for m in (0, 2, 3, 4, 5)}, sorted(seen)    # (finish, 1, runs in average's)
+    assert not [k for k in notes if "ensemble_methods_kernel" in nice[k]]
     mm = [v for k, v in notes.items() if "ensemble_max_len_kernel" in nice[k]]
     assert len(mm) == 1 and mm[0]["scratch"] == 0

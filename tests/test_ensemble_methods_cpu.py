@@ -1,8 +1,7 @@
-"""The ensemble methods (K6M, xrl_ensemble_methods_device) without a GPU: the restatement of its rules (ensemble_methods_rule.py) against
+"""The ensemble methods (xrl_ensemble_methods_device) without a GPU: the restatement of its rules (ensemble_methods_rule.py) against
 the reference's recorded outputs, the host implementation behind predict_text's fallback against the restatement, the entry point's
-export, binding and argument checks (all made before a GPU is required), and the compiled kernels' resources."""
+export, binding and argument checks (all made before a GPU is required).  The kernel's resources: test_ensemble_cpu.py."""
 import ctypes
-import re
 
 import numpy as np
 import pytest
@@ -145,20 +144,3 @@ def test_python_argument_errors():
         ensemble_prediction_device(t, t, 3, "softmax_average")
     with pytest.raises(ValueError, match="Transformer/concat prediction mismatch"):
         ensemble_prediction_device(t, (t[0][:1], t[1][:1], t[2][:1]), 3, "average")
-
-
-def test_k6m_resources(tmp_path):
-    # every instantiation: no scratch, no spills to memory, wavefront-private LDS of at most 8 KB per wavefront (4 wavefronts per workgroup)
-    from test_kernel_resources import demangle, kernel_notes
-    notes = kernel_notes(tmp_path)
-    nice = demangle(sorted(notes))
-    seen = set()
-    for k, d in notes.items():
-        got = re.search(r"ensemble_methods_kernel<(\d+), (\d+)>", nice[k])
-        if not got:
-            continue
-        ns, method = int(got.group(1)), int(got.group(2))
-        seen.add((ns, method))
-        assert d["scratch"] == 0 and d["vgpr_spill"] == 0, (nice[k], d)
-        assert d["lds"] == ns * 64 * 8 * 4 and d["lds"] <= 8192 * 4, (nice[k], d)
-    assert seen == {(ns, m) for ns in (1, 2, 4, 8, 16) for m in (0, 2, 3, 4, 5)}, sorted(seen)

@@ -4,7 +4,7 @@ end against the host path."""
 import numpy as np
 import pytest
 
-from ensemble_cases import CASES, FINISH, Case, same_rows
+from ensemble_cases import CASES, FINISH, Case, over_counts, padded, raw_call, rows_of as _rows, same_rows, text_models, untouched_tail, upload  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -14,19 +14,8 @@ SETTINGS = [("average", None, None, "average"), ("rank_average", None, None, "ra
 
 @pytest.fixture(scope="module", params=CASES)
 def dev_case(request):
-    import torch
     c = Case(request.param)
-    t = [(torch.from_numpy(i.view(np.int32)).cuda(), torch.from_numpy(v).cuda(), torch.from_numpy(n.view(np.int32)).cuda())
-         for i, v, n in zip(c.idx, c.val, c.cnt)]
-    return c, t
-
-
-def _rows(o_idx, o_sc, o_cnt):
-    """(indptr, labels, values) of a fixed-stride device result; entries beyond a row's count are not looked at."""
-    idx, sc, cnt = o_idx.cpu().numpy().view(np.uint32), o_sc.cpu().numpy(), o_cnt.cpu().numpy().astype(np.int64)
-    assert (cnt <= idx.shape[1]).all()
-    mask = np.arange(idx.shape[1])[None, :] < cnt[:, None]
-    return np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64), idx[mask], sc[mask]
+    return c, upload(c)
 
 
 @pytest.mark.parametrize("mode, thr, topk, name", SETTINGS, ids=[s[3] for s in SETTINGS])
@@ -39,46 +28,44 @@ def test_modes_equal_the_reference(dev_case, mode, thr, topk, name):
     same_rows(_rows(*out), c.expected(name), f"case {c.name} {name}")
 
 
-def _raw(c, t, mode, thr, topk, out_stride, stream=None, sync=True, sentinel=0x5A5A5A5A):
-    import torch
-    from pecos_amd import clib
-    o_idx = torch.full((c.rows, out_stride), sentinel, dtype=torch.int32, device="cuda")
-    o_sc = torch.full((c.rows, out_stride), -7.0, dtype=torch.float32, device="cuda")
-    o_cnt = torch.full((c.rows,), -1, dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
-    clib.ensemble_device(0, c.rows, [x[0].data_ptr() for x in t], [x[1].data_ptr() for x in t], [x[2].data_ptr() for x in t],
-                         [x[0].shape[1] for x in t], mode, thr, topk, o_idx.data_ptr(), o_sc.data_ptr(), o_cnt.data_ptr(), out_stride,
-                         stream=stream, sync=sync)
-    return o_idx, o_sc, o_cnt
+def _raw(c, t, mode, thr, topk, out_stride, stream=None, sync=True):
+    return raw_call("ensemble_device", c, t, (mode, thr, topk), out_stride, stream, sync)
 
 
 def test_wider_output_and_input_strides(dev_case):
-    import torch
     c, t = dev_case
     total = sum(i.shape[1] for i in c.idx)
     # out_stride larger than needed: same rows, and nothing is written beyond a row's count
     for mode, thr, topk, name in (SETTINGS[0], SETTINGS[3], SETTINGS[1]):
         o = _raw(c, t, mode, thr, topk, total + 5)
         same_rows(_rows(*o), c.expected(name), f"case {c.name} {name}, out_stride + 5")
-        cnt = o[2].cpu().numpy()
-        tail = np.arange(total + 5)[None, :] >= cnt[:, None]
-        assert (o[0].cpu().numpy()[tail] == 0x5A5A5A5A).all() and (o[1].cpu().numpy()[tail] == -7.0).all()
+        assert untouched_tail(o)
     # input strides larger than the rows (filler behind every row), and counts above the stride where a row is full (read as the stride)
-    over = [(i, v, torch.where(n == i.shape[1], n + 4000, n)) for i, v, n in t]
     for pad in (7, 60):                                                  # (+ 60: cases a-c move to 4, 4 and 8 entries per lane)
         if total + pad * c.n_models > 1024:
             continue
-        wide = []
-        for i, v, n in t:
-            wi = torch.full((c.rows, i.shape[1] + pad), 424242, dtype=torch.int32, device="cuda"); wi[:, : i.shape[1]] = i
-            wv = torch.full((c.rows, i.shape[1] + pad), 3.5, dtype=torch.float32, device="cuda"); wv[:, : i.shape[1]] = v
-            wide.append((wi, wv, n))
+        wide = padded(c, t, pad)
         for mode, thr, topk, name in (SETTINGS[0], SETTINGS[1], SETTINGS[3]):
             o = _raw(c, wide, mode, thr, topk, total + pad * c.n_models)
             same_rows(_rows(*o), c.expected(name), f"case {c.name} {name}, input stride + {pad}")
+    over = over_counts(t)
     for mode, thr, topk, name in (SETTINGS[0], SETTINGS[1]):            # (rank_average: mm is the largest CLAMPED length)
         o = _raw(c, over, mode, thr, topk, total)
         same_rows(_rows(*o), c.expected(name), f"case {c.name} {name}, counts above the stride")
+
+
+def test_the_methods_entry_equals_the_recorded_modes(dev_case):
+    # one kernel behind both entry points: xrl_ensemble_methods_device's average / rank_average, uncut and cut, are xrl_ensemble_device's
+    # average / rank_average / finish without a threshold, on every entries-per-lane count (1, 4, 16 as recorded; 2 and 8 padded)
+    c, t = dev_case
+    total = sum(i.shape[1] for i in c.idx)
+    runs = [(t, total, "")] + [(padded(c, t, pad), total + pad * c.n_models, f", input stride + {pad}")
+                               for name, pad in (("b", 7), ("c", 60)) if c.name == name]
+    for tt, stride, what in runs:
+        for method, k, name in (("average", 0, "average"), ("rank_average", 0, "rank_average"), ("average", 100, "finish3"),
+                                ("average", total, "finish0")):
+            o = raw_call("ensemble_methods_device", c, tt, (method, k), stride)
+            same_rows(_rows(*o), c.expected(name), f"case {c.name} methods entry {method} only_topk={k} vs {name}{what}")
 
 
 def test_on_a_side_stream_without_sync(dev_case):
@@ -102,23 +89,6 @@ def test_no_rows():
 
 
 # ------------------------------------------------------------------------------------------------------------------ end to end
-@pytest.fixture(scope="module")
-def text_models(tmp_path_factory):
-    import xrl_synth
-    from pecos_amd import XLinearModel as XLM
-    from pecos_amd.features import Tfidf
-    from test_tfidf import _case
-    folder, corpus, X = _case("word_bigram_trunc")
-    D, H = X.shape[1], 16
-    root = tmp_path_factory.mktemp("ens")
-    plain, concat = [], []
-    for i, seed in enumerate((81, 82, 83)):
-        xrl_synth.make_model(str(root / f"p{i}"), D, 600, [120, 60, 20], seed=seed, shape=[6, 48, 600])
-        xrl_synth.make_model(str(root / f"c{i}"), D + H, 600, [120, 60, 20], seed=seed + 10, shape=[6, 48, 600])
-        plain.append(XLM.load(str(root / f"p{i}"))); concat.append(XLM.load(str(root / f"c{i}")))
-    return Tfidf.load(folder), corpus, plain, concat, H
-
-
 def _same_csr(a, b, what):
     assert a.shape == b.shape, what
     same_rows((a.indptr, a.indices, a.data), (b.indptr, b.indices, b.data), what)

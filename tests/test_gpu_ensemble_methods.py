@@ -1,22 +1,16 @@
-"""The ensemble methods (K6M, xrl_ensemble_methods_device) on the GPU: round_robin and the cuts of average / rank_average / round_robin
+"""The ensemble methods (xrl_ensemble_methods_device) on the GPU: round_robin and the cuts of average / rank_average / round_robin
 against the reference's recorded outputs (tests/golden/ensemble_methods) bit for bit; sigmoid_average and softmax_average against the
 restatement of the rules (ensemble_methods_rule.py) within the bound derived there for exponentials one fp32 ulp apart; output / input
 layouts; a caller's stream; ensemble_prediction_device; predict_text and metrics_device on a round_robin result."""
 import numpy as np
 import pytest
 
-from ensemble_cases import same_rows
+from ensemble_cases import over_counts, padded, raw_call, rows_of as _rows, same_rows, text_models, untouched_tail, upload as _upload  # noqa: F401
 from ensemble_methods_rule import CASES, CUT_METHODS, TOPKS, MCase, close_rows, restate, value_bound
 
 pytestmark = pytest.mark.gpu
 
 DEVICE_EXP_ULP = 1       # the device's fp64 exp and libm's differ by at most one fp32 ulp after rounding (ensemble_methods_rule.py)
-
-
-def _upload(c):
-    import torch
-    return [(torch.from_numpy(i.view(np.int32)).cuda(), torch.from_numpy(v).cuda(), torch.from_numpy(n.view(np.int32)).cuda())
-            for i, v, n in zip(c.idx, c.val, c.cnt)]
 
 
 @pytest.fixture(scope="module", params=CASES)
@@ -34,14 +28,6 @@ def _restate(c, method, k=0):
     if key not in _restated:
         _restated[key] = restate(c.idx, c.val, c.cnt, method, k)
     return _restated[key]
-
-
-def _rows(o_idx, o_sc, o_cnt):
-    """(indptr, labels, values) of a fixed-stride device result; entries beyond a row's count are not looked at."""
-    idx, sc, cnt = o_idx.cpu().numpy().view(np.uint32), o_sc.cpu().numpy(), o_cnt.cpu().numpy().astype(np.int64)
-    assert (cnt >= 0).all() and (cnt <= idx.shape[1]).all()
-    mask = np.arange(idx.shape[1])[None, :] < cnt[:, None]
-    return np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64), idx[mask], sc[mask]
 
 
 def test_round_robin_and_the_cuts_equal_the_reference(dev_case):
@@ -73,17 +59,8 @@ def test_sigmoid_and_softmax_are_within_the_bound_of_the_restatement(dev_case):
     close_rows(got, _restate(c, "sigmoid_average", 3), value_bound("sigmoid_average", c.n_models, DEVICE_EXP_ULP), f"case {c.name} sigmoid top 3")
 
 
-def _raw(c, t, method, topk, out_stride, stream=None, sync=True, sentinel=0x5A5A5A5A):
-    import torch
-    from pecos_amd import clib
-    o_idx = torch.full((c.rows, out_stride), sentinel, dtype=torch.int32, device="cuda")
-    o_sc = torch.full((c.rows, out_stride), -7.0, dtype=torch.float32, device="cuda")
-    o_cnt = torch.full((c.rows,), -1, dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
-    clib.ensemble_methods_device(0, c.rows, [x[0].data_ptr() for x in t], [x[1].data_ptr() for x in t], [x[2].data_ptr() for x in t],
-                                 [x[0].shape[1] for x in t], method, topk, o_idx.data_ptr(), o_sc.data_ptr(), o_cnt.data_ptr(), out_stride,
-                                 stream=stream, sync=sync)
-    return o_idx, o_sc, o_cnt
+def _raw(c, t, method, topk, out_stride, stream=None, sync=True):
+    return raw_call("ensemble_methods_device", c, t, (method, topk), out_stride, stream, sync)
 
 
 def _check(c, o, method, topk, what):
@@ -97,29 +74,22 @@ SETTINGS = (("round_robin", 0), ("round_robin", 3), ("rank_average", 3), ("avera
 
 
 def test_wider_output_and_input_strides(dev_case):
-    import torch
     c, t, _, _ = dev_case
     total = sum(i.shape[1] for i in c.idx)
     # out_stride larger than needed: same rows, and nothing is written beyond a row's count
     for method, topk in SETTINGS:
         o = _raw(c, t, method, topk, total + 5)
         _check(c, o, method, topk, f"case {c.name} {method} top {topk}, out_stride + 5")
-        cnt = o[2].cpu().numpy()
-        tail = np.arange(total + 5)[None, :] >= cnt[:, None]
-        assert (o[0].cpu().numpy()[tail] == 0x5A5A5A5A).all() and (o[1].cpu().numpy()[tail] == -7.0).all()
+        assert untouched_tail(o)
     # input strides larger than the rows (filler behind every row), and counts above the stride where a row is full (read as the stride)
-    over = [(i, v, torch.where(n == i.shape[1], n + 4000, n)) for i, v, n in t]
     for pad in (7, 60):                                                  # (+ 60: cases a-c move to 4, 4 and 8 entries per lane)
         if total + pad * c.n_models > 1024:
             continue
-        wide = []
-        for i, v, n in t:
-            wi = torch.full((c.rows, i.shape[1] + pad), 424242, dtype=torch.int32, device="cuda"); wi[:, : i.shape[1]] = i
-            wv = torch.full((c.rows, i.shape[1] + pad), 3.5, dtype=torch.float32, device="cuda"); wv[:, : i.shape[1]] = v
-            wide.append((wi, wv, n))
+        wide = padded(c, t, pad)
         for method, topk in SETTINGS:
             o = _raw(c, wide, method, topk, total + pad * c.n_models)
             _check(c, o, method, topk, f"case {c.name} {method} top {topk}, input stride + {pad}")
+    over = over_counts(t)
     for method, topk in SETTINGS[:3]:                                    # (mm is the largest CLAMPED length)
         o = _raw(c, over, method, topk, total)
         _check(c, o, method, topk, f"case {c.name} {method} top {topk}, counts above the stride")
@@ -187,24 +157,9 @@ def test_metrics_of_a_round_robin_result():
 
 
 # ------------------------------------------------------------------------------------------------------------------ end to end
-@pytest.fixture(scope="module")
-def text_models(tmp_path_factory):
-    import xrl_synth
-    from pecos_amd import XLinearModel as XLM
-    from pecos_amd.features import Tfidf
-    from test_tfidf import _case
-    folder, corpus, X = _case("word_bigram_trunc")
-    root = tmp_path_factory.mktemp("ensm")
-    plain = []
-    for i, seed in enumerate((81, 82, 83)):
-        xrl_synth.make_model(str(root / f"p{i}"), X.shape[1], 600, [120, 60, 20], seed=seed, shape=[6, 48, 600])
-        plain.append(XLM.load(str(root / f"p{i}")))
-    return Tfidf.load(folder), corpus, plain
-
-
 def test_predict_text_round_robin_device_equals_host(text_models):
     from pecos_amd.features import predict_text
-    vec, corpus, plain = text_models
+    vec, corpus, plain, _, _ = text_models
     kw = dict(beam_size=5, only_topk=7, ensemble_method="round_robin")
     dev = predict_text(vec, plain, corpus, ensemble="device", **kw)
     host = predict_text(vec, plain, corpus, ensemble="host", **kw)
