@@ -196,9 +196,9 @@ void* xrl_queries_from_device_drm(void* model, uint32_t rows, uint32_t cols, con
 /* The weighting half of the reference's TF-IDF vectorizer on the device (BaseVectorizer::get_sorted_feature,
  * pecos/core/utils/tfidf.hpp:798-822; c_tfidf_predict, libpecos.cpp:427-445): a device CSR of term COUNTS (column ids ascending
  * inside every row, what the reference's tokenizer + n-gram lookup produce) -> binary / sublinear tf -> x idf (d_idf[cols], NULL =
- * use_idf false) -> l1 / l2 normalisation (norm_p 1 | 2), float32 operation by operation like the reference (bit-identical; with
- * sublinear_tf <= 1 ulp, the device's logf).  The weighted values go to d_out (nnz floats, caller-owned; may alias d_count) or, with
- * d_out == NULL, into a buffer the returned query handle owns; the handle REFERENCES d_row_ptr / d_col_idx (and d_out): keep them
+ * use_idf false) -> l1 / l2 normalisation (norm_p 1 | 2), float32 operation by operation like the reference (bit-identical; sublinear_tf
+ * is (float)(log((double)count) + 1.0), the double log of tfidf.hpp:801, rounded once).  The weighted values go to d_out (nnz floats,
+ * caller-owned; may alias d_count) or, with d_out == NULL, into a buffer the returned query handle owns; the handle REFERENCES d_row_ptr / d_col_idx (and d_out): keep them
  * alive.  It feeds xrl_predict_device directly: the queries never visit the host. */
 void* xrl_queries_tfidf_device(void* model, uint32_t rows, uint32_t cols, const uint64_t* d_row_ptr, const uint32_t* d_col_idx,
                                const float* d_count, uint64_t nnz, const float* d_idf, int binary, int sublinear_tf, int norm_p,
@@ -208,7 +208,7 @@ void* xrl_queries_tfidf_device(void* model, uint32_t rows, uint32_t cols, const 
  * vectorizer/{config.json, tfidf-model.txt}; or an ensemble: meta.json + <i>.base/) -- host only.  c_tfidf_predict has the
  * reference's signature and result (host CSR through the allocator, rows = documents, sorted feature ids): the tokenizer and the
  * n-gram lookup run on host threads (`threads`, <= 0: all), their term counts go to the device once, weighting and normalisation run
- * there (K5) and the result is copied back -- bit-identical to the reference (sublinear_tf: <= 1 ulp).  Training, saving and the
+ * there (K5) and the result is copied back -- bit-identical to the reference, sublinear_tf included.  Training, saving and the
  * *_from_file variants stay the reference's.
  * xrl_tfidf_predict_device is the same pipeline WITHOUT the copy back: it returns a query handle (xrl_queries_free) whose X lives in
  * the HBM of `model`'s device and feeds xrl_predict_device / xrl_predict_device_rows directly -- the call sites SURVEY.md 8f N4 names

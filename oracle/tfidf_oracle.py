@@ -9,11 +9,12 @@ Restated from pecos/core/utils/tfidf.hpp (behaviour, not code):
   Tokenizer::tokenize          :433-448   the first max_length tokens when max_length > 0; unknown token -> -1
   BaseVectorizer::load         :707-745   tfidf-model.txt: "<n>" then per feature "<id> <idf> <len> <tok>*len"
   get_sorted_feature           :775-822   n-grams of min_ngram..min(max_ngram, #tokens) tokens looked up, a float count per feature (+= 1.0),
-                                          ascending ids; binary -> 1; sublinear -> log(v) + 1.0; x idf; l1 / l2 norm summed in that order
+                                          ascending ids; binary -> 1; sublinear -> (float)(log((double)v) + 1.0) -- the unqualified log of
+                                          :801 is <cmath>'s DOUBLE log --; x idf; l1 / l2 norm summed in that order
   Vectorizer::load / predict   :1247-1266, :1405-1430; normalize_csr :1318-1354   ensembles: hstack + one more normalisation
 
-PINNED: tests/test_tfidf.py::test_oracle_restatement_vs_reference_goldens holds it bit for bit (sublinear tf: <= 1 ulp, numpy's logf vs
-glibc's) against tests/golden/tfidf_models/*/X.npz, which the reference itself produced (tests/golden/make_golden_r04.py).
+PINNED: tests/test_tfidf.py::test_oracle_restatement_vs_reference_goldens holds it bit for bit, sublinear tf included, against
+tests/golden/tfidf_models/*/X.npz, which the reference itself produced (tests/golden/make_golden_r04.py); tests/test_tfidf_weight_cpu.py holds it against the live reference on counts up to 20 000 and rows up to 1025 entries.
 """
 import json
 import os
@@ -85,7 +86,7 @@ class BaseOracle:
         for f, cnt in pairs:
             v = F32(1.0) if self.binary else F32(cnt)
             if self.sublinear_tf:
-                v = F32(np.float64(np.log(v, dtype=F32)) + 1.0)
+                v = F32(np.log(np.float64(v)) + 1.0)
             if self.use_idf:
                 v = F32(v * self.idf[f])
             denom = F32(denom + (F32(abs(v)) if self.norm_p == 1 else F32(v * v)))

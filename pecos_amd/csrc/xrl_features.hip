@@ -8,7 +8,8 @@
 //
 // Arithmetic follows the reference's float32 code operation by operation: the norm is accumulated SEQUENTIALLY in ascending
 // feature order (one wavefront per document, a scalar loop over its lanes), multiply and add rounded separately (-ffp-contract=off), sqrtf / division IEEE.
-// With sublinear_tf the reference calls glibc's logf, whose last bit the device's logf may not share: <= 1 ulp there.
+// With sublinear_tf the reference's unqualified log(float) + 1.0 (tfidf.hpp:801) is the DOUBLE log of <cmath>: log in fp64, the add in fp64, one
+// rounding to fp32 -- here the device's fp64 log, which gave glibc's fp32 result for every count 1 .. 2^24.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -40,7 +41,7 @@ tfidf_weight_kernel(const uint64_t* __restrict__ row_ptr, const uint32_t* __rest
         float v = 0.0f;
         if (ok) {
             v = binary ? 1.0f : count[t];                                      // tfidf.hpp:800
-            if (sublinear_tf) v = (float)((double)logf(v) + 1.0);              // :801  (std::log(float) + 1.0)
+            if (sublinear_tf) v = (float)(log((double)v) + 1.0);               // :801  (the double log, a separate fp64 add, one rounding)
             if (idf) {                                                         // :802-804
                 const uint32_t f = col_idx[t];
                 if (f >= cols) { if (err) *err = 1u; }

@@ -223,7 +223,7 @@ uint32_t xrl_tfidf_nr_features(void* ptr) {
 // documents -> weighted CSR on the device -> the caller's arrays through ONE allocator call (shared by c_tfidf_predict and c_tfidf_predict_from_file)
 // The weighting half on the HOST, for calls of a handful of documents (the reference serves nr_doc == 1 with a direct host call, libpecos.cpp:437-439:
 // microseconds -- a device round trip costs a hundred times that).  tfidf.hpp:798-822 operation by operation in fp32, like the kernel
-// (csrc/xrl_features.hip): sequential norm in ascending feature order, separate multiply and add (-ffp-contract=off), glibc's logf (the reference's own).
+// (csrc/xrl_features.hip): sequential norm in ascending feature order, separate multiply and add (-ffp-contract=off), the double log of :801 rounded once.
 static void tfidf_weight_host(const uint64_t* row_ptr, const uint32_t* col, float* val, const float* idf, uint32_t rows, uint32_t cols, bool binary,
                               bool sublinear, int norm_p, uint32_t seg_stride, uint32_t seg_off) {
     if (norm_p != 1 && norm_p != 2) fail("tfidf: invalid normalize option, norm_p: [ 1| 2]");
@@ -232,7 +232,7 @@ static void tfidf_weight_host(const uint64_t* row_ptr, const uint32_t* col, floa
         float denom = 0.0f;
         for (uint64_t t = b; t < e; ++t) {
             float v = binary ? 1.0f : val[t];
-            if (sublinear) v = (float)((double)std::log(v) + 1.0);
+            if (sublinear) v = (float)(std::log((double)v) + 1.0);
             if (idf) {
                 if (col[t] >= cols) fail("tfidf: a feature id outside the model's feature range");
                 v = v * idf[col[t]];

@@ -147,7 +147,7 @@ def tfidf_weight(counts, idf=None, binary=False, sublinear_tf=False, norm="l2"):
         b, e = C.indptr[r], C.indptr[r + 1]
         v = np.ones(e - b, f32) if binary else C.data[b:e].astype(f32)
         if sublinear_tf:
-            v = (np.log(v).astype(f32).astype(np.float64) + 1.0).astype(f32)
+            v = (np.log(v.astype(np.float64)) + 1.0).astype(f32)          # :801: the DOUBLE log, one rounding
         if idf is not None:
             v = (v * np.asarray(idf, f32)[C.indices[b:e]]).astype(f32)
         denom = f32(0.0)

@@ -403,10 +403,7 @@ def test_tfidf_device_banded_three_destinations(manifest, loaded, clib):
             assert np.array_equal(got.indptr, want.indptr) and np.array_equal(got.indices, want.indices), what
             views = [got.data] + ([po.cpu().numpy()] if dest == "caller" else []) + ([cnt.cpu().numpy()] if dest == "in place" else [])
             for data in views:
-                if kw["sublinear_tf"]:           # the bound of test_device_tfidf_weighting_vs_reference (the device's logf)
-                    assert np.all(np.abs(data - want.data) <= 2.5e-7 * np.abs(want.data)), what
-                else:
-                    assert np.array_equal(data.view(np.uint32), want.data.view(np.uint32)), what
+                assert np.array_equal(data.view(np.uint32), want.data.view(np.uint32)), what          # (sublinear_tf included)
             if dest != "in place":
                 assert np.array_equal(cnt.cpu().numpy().view(np.uint32), counts.data.astype(np.float32).view(np.uint32)), f"{what}: the counts were changed"
             V.assert_bands_intact(wv, cnt, V.poison_like("value"), what + " counts")       # (in place: the elements past nnz)
