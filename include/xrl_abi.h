@@ -158,6 +158,21 @@ void c_sparse_inner_products_csr2dcm_f32(const ScipyCsrF32* pX, const ScipyDcmF3
 void c_sparse_inner_products_drm2dcm_f32(const ScipyDrmF32* pX, const ScipyDcmF32* pW, uint64_t len,
                                          uint32_t* X_row_idx, uint32_t* W_col_idx, float* val, int threads);
 
+/* libpecos.cpp:320-334 (C_SPARSE_MATMUL -> smat_x_smat, matrix.hpp:1075-1292): Z = X * Y of two CSR / two CSC matrices through the
+ * allocator, computed on the device (K10, csrc/xrl_spgemm.hip) by the rule stated at xrl_sparse_matmul_device below, bit for bit the
+ * reference's arrays.  Both operands are uploaded to the calling thread's device (xrl_set_device); the allocator is called once,
+ * synchronously, with (is_col_major, X.rows, Y.cols, nnz BEFORE eliminate_zeros), as the reference calls it; the result is copied back.
+ * With eliminate_zeros the reference compacts in place inside those arrays, so indices / data past the final indptr[-1] keep what the
+ * un-compacted product held at those positions: so do they here.  `threads` is accepted and ignored (the reference's result does not
+ * depend on it).  The CSC form is the CSR form of the transposes, xrl_sparse_matmul_device's identity.  Refused, before a GPU is
+ * required and with messages that start with the function's name: a null matrix, array or allocator; X.cols != Y.rows (which the
+ * reference lets through, matrix.hpp:1085-1087).  Refused by the kernel's first pass: a row of the product that takes 2^31
+ * multiplications or more. */
+void c_sparse_matmul_csr_f32(const ScipyCsrF32* pX, const ScipyCsrF32* pY, py_sparse_allocator_t pred_alloc,
+                             const bool eliminate_zeros, const bool sorted_indices, int threads);
+void c_sparse_matmul_csc_f32(const ScipyCscF32* pX, const ScipyCscF32* pY, py_sparse_allocator_t pred_alloc,
+                             const bool eliminate_zeros, const bool sorted_indices, int threads);
+
 /* ------------------------------------------------------------------------------------------
  * Part 2: additive entry points (no reference counterpart)
  * ---------------------------------------------------------------------------------------- */
@@ -372,6 +387,52 @@ int xrl_metrics_device(int device, uint32_t rows,
                        const uint64_t* d_true_ptr, const uint32_t* d_true_idx,
                        uint32_t topk, uint64_t* d_matched /* u64[topk] */, double* d_recall_sum /* f64[topk] */,
                        void* hip_stream, int sync);
+
+/* SPARSE MATRIX PRODUCTS ON THE DEVICE (K10, csrc/xrl_spgemm.hip): clib.sparse_matmul (pecos/core/base.py:1460-1534) with the operands
+ * and the product in HBM -- csr_codes * C^T of XR-Transformer's descent (pecos/xmc/xtransformer/matcher.py:723), Y * C of the matching
+ * matrices and label roll-ups (pecos/xmc/base.py:556, 1520, 1550), S * C, Y^T * X -- on matrix handles bound to a DEVICE, not to a model.
+ * THE RULE (smat_x_smat, matrix.hpp:1075-1292, bit for bit).  Z = A * B, A rows x inner, B inner x cols, both CSR (u64 row_ptr, u32
+ * col_idx, f32 val).  For every row i of A walk its stored entries s = 0, 1, ... in STORED order (whatever it is, duplicates allowed);
+ * for entry (k, a) walk the stored entries t = 0, 1, ... of row k of B in stored order (duplicates allowed): acc[j] = acc[j] + a * b,
+ * a rounded multiply then a rounded add (no FMA), every acc from +0.0f -- so 0 + (-0) is +0, and the order of the additions to one column
+ * is the order of the walk.  A column is touched by its first product, a zero product included.  Row i of Z: the touched columns,
+ * ascending with sorted_indices, otherwise in the order of first touch.  With eliminate_zeros, entries with val == 0 are then dropped
+ * (NaN stays).  Subnormal products and sums are kept.  The result is a function of the inputs only: no float atomics, no dependence on
+ * the CU count, the launch order or a hash seed.
+ * A CSC product X * W is xrl_sparse_matmul_device(W^T as CSR, X^T as CSR) read as CSC: the CSC arrays of a matrix are the CSR arrays of
+ * its transpose, and (X * W)^T = W^T * X^T.
+ * Capacity: an output row of at most 1024 products (xrl_spgemm.h: CAP) is served by one wavefront in LDS; longer rows go through HBM
+ * scratch and a segmented sort, in batches that keep the scratch under 6 GiB.  Refused: a row of 2^31 products or more; an entry of A
+ * whose column is not a row of B; operands on two devices; A.cols != B.rows ("X.cols != W.rows"); null handles and pointers (all but
+ * the first two before a GPU is required; messages start with the function's name).
+ *   xrl_smat_upload_csr          a host CSR copied to `device`; the handle owns the copy
+ *   xrl_smat_from_device_csr     wraps arrays that are in HBM on `device`; NOT owned: keep them alive until xrl_smat_free; no GPU call
+ *   xrl_smat_from_device_result  a fixed-stride result (d_idx / d_val [rows * stride], d_cnt [rows] or NULL = stride each; a count above
+ *                                the stride is read as the stride -- what xrl_predict_device and xrl_ensemble_device write) compacted
+ *                                into a CSR the handle owns, rows x cols, the stored best-first order kept; synchronises hip_stream
+ *   xrl_smat_info                out[0..cap), cap <= 7 <- {rows, cols, nnz, device, address of row_ptr, of col_idx, of val}: a product
+ *                                feeds xrl_queries_from_device_csr (sorted_indices, as queries must be) or a torch tensor view
+ *   xrl_smat_download            row_ptr[rows + 1], col_idx[nnz], val[nnz] back to the host (synchronises the device)
+ *   xrl_smat_copy_device         the same three arrays into the caller's buffers in HBM on the handle's device (e.g. torch tensors sized
+ *                                from xrl_smat_info), on hip_stream, which it synchronises
+ *   xrl_smat_free                frees the handle and what it owns (NULL: no-op)
+ *   xrl_sparse_matmul_device     a NEW owned handle with Z = A * B on the operands' device, computed on hip_stream (NULL = the device's
+ *                                null stream).  The call SYNCHRONISES the stream: once, to learn nnz, when every row fits the LDS form;
+ *                                again per pass when rows need the big form or eliminate_zeros is set.  Zero rows, an empty operand and
+ *                                nnz == 0 succeed and give an empty handle.  NULL + xrl_last_error on failure.
+ *   xrl_debug_spgemm_forms       FOR TESTS ONLY: out[0..n), n <= 5 <- {CAP, rows served by the LDS form, rows served by the big form, batches
+ *                                of the big form (its count pass), products computed} of this process since the library was loaded */
+void* xrl_smat_upload_csr(int device, const ScipyCsrF32* X);
+void* xrl_smat_from_device_csr(int device, uint32_t rows, uint32_t cols, const uint64_t* d_row_ptr, const uint32_t* d_col_idx,
+                               const float* d_val, uint64_t nnz);
+void* xrl_smat_from_device_result(int device, uint32_t rows, uint32_t cols, const uint32_t* d_idx, const float* d_val,
+                                  const uint32_t* d_cnt /* NULL = stride each */, uint32_t stride, void* hip_stream);
+int xrl_smat_info(void* smat, uint64_t* out, uint32_t cap);
+int xrl_smat_download(void* smat, uint64_t* row_ptr, uint32_t* col_idx, float* val);
+int xrl_smat_copy_device(void* smat, uint64_t* d_row_ptr, uint32_t* d_col_idx, float* d_val, void* hip_stream);
+void xrl_smat_free(void* smat);
+void* xrl_sparse_matmul_device(void* A, void* B, int eliminate_zeros, int sorted_indices, void* hip_stream);
+int xrl_debug_spgemm_forms(uint64_t* out, uint32_t n);
 
 /* predict_on_selected_outputs on the device (K7 + K4): score a given set of labels per query row through the tree, with labels, plan and
  * scores resident in HBM.  The labels arrive in the fixed-stride form xrl_predict_device writes and xrl_ensemble_device reads: row r is

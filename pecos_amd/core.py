@@ -7,7 +7,8 @@ Mirrors, for that path only, the reference's binding layer (pecos/core/base.py):
 * ``ScipyCompressedSparseAllocator`` (python-side result allocator)        base.py:357-478
 * ``corelib`` methods ``xlinear_load_predict_only``, ``xlinear_destruct_model``,
   ``xlinear_get_int_attr``, ``xlinear_get_layer_type``, ``xlinear_predict``,
-  ``xlinear_single_layer_predict``, ``sparse_inner_products``             base.py:978-1405, 1536-1589
+  ``xlinear_single_layer_predict``, ``sparse_matmul``,
+  ``sparse_inner_products``                                               base.py:978-1405, 1460-1589
 
 with the same names, argument order and meaning, so that code written against
 ``pecos.core.clib`` reads the same against :data:`clib` here.  There is NO CPU fallback: every
@@ -211,6 +212,17 @@ class corelib(object):
         "c_sparse_inner_products_drm2csc_f32": (None, [POINTER(ScipyDrmF32), POINTER(ScipyCscF32), c_uint64, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_float), c_int]),
         "c_sparse_inner_products_csr2dcm_f32": (None, [POINTER(ScipyCsrF32), POINTER(ScipyDcmF32), c_uint64, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_float), c_int]),
         "c_sparse_inner_products_drm2dcm_f32": (None, [POINTER(ScipyDrmF32), POINTER(ScipyDcmF32), c_uint64, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_float), c_int]),
+        "c_sparse_matmul_csr_f32": (None, [POINTER(ScipyCsrF32), POINTER(ScipyCsrF32), _alloc_t, c_bool, c_bool, c_int]),
+        "c_sparse_matmul_csc_f32": (None, [POINTER(ScipyCscF32), POINTER(ScipyCscF32), _alloc_t, c_bool, c_bool, c_int]),
+        "xrl_smat_upload_csr": (c_void_p, [c_int, POINTER(ScipyCsrF32)]),
+        "xrl_smat_from_device_csr": (c_void_p, [c_int, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64]),
+        "xrl_smat_from_device_result": (c_void_p, [c_int, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+        "xrl_smat_info": (c_int, [c_void_p, POINTER(c_uint64), c_uint32]),
+        "xrl_smat_download": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+        "xrl_smat_copy_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+        "xrl_smat_free": (None, [c_void_p]),
+        "xrl_sparse_matmul_device": (c_void_p, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+        "xrl_debug_spgemm_forms": (c_int, [POINTER(c_uint64), c_uint32]),
         "xrl_inspect_model": (c_int, [c_char_p, POINTER(c_uint64), c_uint32]),
         "xrl_model_create": (c_void_p, [c_uint32, c_void_p, c_void_p, POINTER(c_float), POINTER(c_uint32), POINTER(c_char_p)]),
         "xrl_queries_upload_csr": (c_void_p, [c_void_p, POINTER(ScipyCsrF32)]),
@@ -442,6 +454,104 @@ class corelib(object):
            pred_values.ctypes.data_as(POINTER(c_float)), threads)
         self._check()
         return pred_values
+
+    def sparse_matmul(self, X, Y, eliminate_zeros=False, sorted_indices=True, threads=-1):
+        """X * Y of two sparse matrices on the device (K10), with the reference's dispatch and result (base.py:1460-1534): CSC x CSC and
+        CSR x CSR go to the entry point of their format, a mixed pair converts the operand with the smaller nnz; returns a
+        ``csc_matrix`` / ``csr_matrix`` of that format.  ``threads`` is accepted and ignored."""
+        if X.shape[1] != Y.shape[0]:
+            raise ValueError("X.shape[1]={} != Y.shape[0]={}".format(X.shape[1], Y.shape[0]))
+        clib = self.clib_float32
+        pred_alloc = ScipyCompressedSparseAllocator()
+
+        def is_col_major(A):
+            return isinstance(A, (smat.csc_matrix, ScipyCscF32))
+
+        def is_row_major(A):
+            return isinstance(A, (smat.csr_matrix, ScipyCsrF32))
+
+        if is_col_major(X) and is_col_major(Y):
+            fmt = "csc"
+        elif is_row_major(X) and is_row_major(Y):
+            fmt = "csr"
+        elif is_col_major(X) and is_row_major(Y):
+            fmt = "csc" if X.nnz > Y.nnz else "csr"
+        elif is_row_major(X) and is_col_major(Y):
+            fmt = "csr" if X.nnz > Y.nnz else "csc"
+        else:
+            raise ValueError("X and Y should be either csr_matrix/csc_matrix/ScipyCscF32/ScipyCsrF32 !")
+        if fmt == "csc":
+            view, to_fmt, is_fmt = ScipyCscF32, "tocsc", is_col_major
+        else:
+            view, to_fmt, is_fmt = ScipyCsrF32, "tocsr", is_row_major
+        pX, pY = (view.init_from(A if is_fmt(A) else getattr(A, to_fmt)()) for A in (X, Y))
+        getattr(clib, f"c_sparse_matmul_{fmt}_f32")(pX, pY, pred_alloc.cfunc, eliminate_zeros, sorted_indices, threads)
+        self._check()
+        return pred_alloc.get()
+
+    # ------------------------------------------------------------------ device matrices and their products (additive, K10)
+    def smat_upload_csr(self, device, X):
+        """A scipy CSR (float32) copied to ``device``: a matrix handle that owns the copy (free it with :meth:`smat_free`)."""
+        h = self.clib_float32.xrl_smat_upload_csr(int(device), byref(ScipyCsrF32.init_from(X)))
+        self._check()
+        return h
+
+    def smat_from_device_csr(self, device, rows, cols, row_ptr_addr, col_idx_addr, val_addr, nnz):
+        """Wrap a CSR that already lives in HBM on ``device`` (raw addresses: u64 row_ptr, u32 col_idx, f32 val); non-owning."""
+        h = self.clib_float32.xrl_smat_from_device_csr(int(device), int(rows), int(cols), c_void_p(row_ptr_addr), c_void_p(col_idx_addr),
+                                                       c_void_p(val_addr), int(nnz))
+        self._check()
+        return h
+
+    def smat_from_device_result(self, device, rows, cols, d_idx, d_val, d_cnt, stride, stream=None):
+        """A fixed-stride result (raw addresses; ``d_cnt`` None = ``stride`` entries in every row) as a rows x cols CSR the handle owns."""
+        h = self.clib_float32.xrl_smat_from_device_result(int(device), int(rows), int(cols), c_void_p(d_idx), c_void_p(d_val), c_void_p(d_cnt or 0),
+                                                          int(stride), c_void_p(stream or 0))
+        self._check()
+        return h
+
+    def smat_info(self, h):
+        """dict(rows, cols, nnz, device, row_ptr, col_idx, val) of a matrix handle; the last three are device addresses."""
+        out = (c_uint64 * 7)()
+        self.clib_float32.xrl_smat_info(c_void_p(h), out, 7)
+        self._check()
+        return dict(zip(("rows", "cols", "nnz", "device", "row_ptr", "col_idx", "val"), (int(v) for v in out)))
+
+    def smat_download(self, h):
+        """Copy of a matrix handle back to the host: a scipy CSR with the stored order and explicit zeros kept."""
+        info = self.smat_info(h)
+        rows, cols, nnz = info["rows"], info["cols"], info["nnz"]
+        ptr = np.zeros(rows + 1, dtype=np.uint64); idx = np.zeros(max(nnz, 1), dtype=np.uint32); val = np.zeros(max(nnz, 1), dtype=np.float32)
+        self.clib_float32.xrl_smat_download(c_void_p(h), ptr.ctypes.data_as(c_void_p), idx.ctypes.data_as(c_void_p), val.ctypes.data_as(c_void_p))
+        self._check()
+        m = smat.csr_matrix((rows, cols), dtype=np.float32)
+        m.indptr, m.indices, m.data = ptr.astype(np.int64), idx[:nnz].astype(np.int64), val[:nnz]      # assigned directly: keeps explicit zeros / order
+        return m
+
+    def smat_copy_device(self, h, row_ptr_addr, col_idx_addr, val_addr, stream=None):
+        """The handle's arrays into the caller's device buffers (raw addresses, sized from :meth:`smat_info`); synchronises ``stream``."""
+        rc = self.clib_float32.xrl_smat_copy_device(c_void_p(h), c_void_p(row_ptr_addr), c_void_p(col_idx_addr or 0), c_void_p(val_addr or 0),
+                                                    c_void_p(stream or 0))
+        self._check()
+        return rc
+
+    def smat_free(self, h):
+        if self._lib is not None and h:
+            self._lib.xrl_smat_free(c_void_p(h))
+
+    def sparse_matmul_device(self, A, B, eliminate_zeros=False, sorted_indices=True, stream=None):
+        """A new matrix handle with A * B of two matrix handles of one device (free it with :meth:`smat_free`)."""
+        h = self.clib_float32.xrl_sparse_matmul_device(c_void_p(A), c_void_p(B), 1 if eliminate_zeros else 0, 1 if sorted_indices else 0,
+                                                       c_void_p(stream or 0))
+        self._check()
+        return h
+
+    def debug_spgemm_forms(self):
+        """Debug counters of K10 since the load: its CAP, rows served by the LDS form, by the big form, batches of the big form, products."""
+        out = (c_uint64 * 5)()
+        self.clib_float32.xrl_debug_spgemm_forms(out, 5)
+        self._check()
+        return dict(zip(("cap", "lds_rows", "big_rows", "batches", "calls"), (int(v) for v in out)))
 
     # ------------------------------------------------------------------ device-resident path (additive)
     def queries_upload(self, c_model, X):

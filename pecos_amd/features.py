@@ -15,6 +15,8 @@
   ``Text2Text.predict``'s tail; :func:`predict_text` and :class:`Text2Text` use it for ensembles that share a device.  ``sigmoid_average``,
   ``softmax_average``, ``round_robin`` and ``only_topk`` go through ``xrl_ensemble_methods_device``; :func:`ensemble_prediction_device` is
   ``TransformerMatcher.ensemble_prediction`` on two device results, :func:`ensemble_host` the same methods on scipy matrices.
+* :func:`sparse_matmul_device` / :class:`DeviceMatrix` / :func:`result_to_csr_device` -- the reference's ``clib.sparse_matmul`` with operands and
+  product in HBM (K10): a result triple times ``C^T`` (XR-Transformer's descent) or ``C`` (a roll-up of labels to clusters), bit for bit.
 * :func:`metrics_device` / :func:`metrics_sums_device` / :class:`Metrics` -- ``smat_util.Metrics.generate`` (precision and recall at
   1 .. topk) from a result in HBM (K8): 2 x topk numbers come back instead of the result.
 """
@@ -374,6 +376,139 @@ def ensemble_device(results, mode="average", threshold=None, only_topk=None, str
         else:
             o_cnt.zero_()
     return o_idx, o_sc, o_cnt
+
+
+class DeviceMatrix:
+    """A CSR in HBM behind a matrix handle of the library (``xrl_smat_*``): uploaded, wrapped around torch tensors (which it keeps
+    alive), compacted from a fixed-stride result, or the product of two others.  Freed with the object."""
+
+    def __init__(self, handle, keep=()):
+        self.handle, self._keep = handle, keep
+
+    def __del__(self):
+        h, self.handle = getattr(self, "handle", None), None
+        if h:
+            clib.smat_free(h)
+
+    @property
+    def info(self):
+        return clib.smat_info(self.handle)
+
+    @property
+    def shape(self):
+        i = self.info
+        return i["rows"], i["cols"]
+
+    @classmethod
+    def upload(cls, X, device=0):
+        """A scipy sparse matrix (any format; float32 CSR as it is, stored order kept) copied to ``device``."""
+        X = X if isinstance(X, smat.csr_matrix) else smat.csr_matrix(X)
+        return cls(clib.smat_upload_csr(device, X if X.dtype == np.float32 else X.astype(np.float32)))
+
+    @classmethod
+    def from_torch(cls, crow, col, val, shape):
+        """Wraps CUDA tensors crow int64 [rows + 1], col int32 [nnz], val float32 [nnz] of a CSR of ``shape`` (no copy of contiguous ones)."""
+        import torch
+        assert crow.is_cuda and col.device == crow.device and val.device == crow.device
+        assert crow.dtype == torch.int64 and col.dtype == torch.int32 and val.dtype == torch.float32
+        crow, col, val = crow.contiguous(), col.contiguous(), val.contiguous()
+        rows, cols = shape
+        assert crow.numel() == rows + 1 and col.numel() == val.numel()
+        return cls(clib.smat_from_device_csr(crow.device.index, rows, cols, crow.data_ptr(), col.data_ptr(), val.data_ptr(), val.numel()), keep=(crow, col, val))
+
+    @classmethod
+    def from_result(cls, result, n_cols, stream=None):
+        """A result triple ``(labels int32 [rows, k], scores float32 [rows, k], counts int32 [rows] or None)`` as a rows x ``n_cols`` CSR, rows best first."""
+        import torch
+        idx, sc, cnt = result
+        assert idx.is_cuda and idx.dtype == torch.int32 and sc.dtype == torch.float32 and idx.dim() == 2 and idx.shape == sc.shape and sc.device == idx.device
+        idx, sc = idx.contiguous(), sc.contiguous()
+        rows, stride = idx.shape
+        if cnt is not None:
+            assert cnt.device == idx.device and cnt.dtype == torch.int32 and cnt.shape == (rows,)
+            cnt = cnt.contiguous()
+        with torch.cuda.device(idx.device):
+            s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+            return cls(clib.smat_from_device_result(idx.device.index, rows, n_cols, idx.data_ptr(), sc.data_ptr(), None if cnt is None else cnt.data_ptr(),
+                                                    stride, stream=s or None))
+
+    def to_torch(self, stream=None):
+        """``(crow int64, col int32, val float32, (rows, cols))``: CUDA tensors copied out of the handle."""
+        import torch
+        i = self.info
+        dev = torch.device("cuda", i["device"])
+        with torch.cuda.device(dev):
+            s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+            crow = torch.empty(i["rows"] + 1, dtype=torch.int64, device=dev)
+            col = torch.empty(i["nnz"], dtype=torch.int32, device=dev)
+            val = torch.empty(i["nnz"], dtype=torch.float32, device=dev)
+            clib.smat_copy_device(self.handle, crow.data_ptr(), col.data_ptr(), val.data_ptr(), stream=s or None)
+        return crow, col, val, (i["rows"], i["cols"])
+
+    def download(self):
+        """scipy CSR copy on the host, stored order and explicit zeros kept."""
+        return clib.smat_download(self.handle)
+
+    def multiply(self, other, eliminate_zeros=False, sorted_indices=True, stream=None):
+        """``self * other`` as a new :class:`DeviceMatrix` (K10; the rule is stated at ``xrl_sparse_matmul_device``)."""
+        return DeviceMatrix(clib.sparse_matmul_device(self.handle, other.handle, eliminate_zeros, sorted_indices, stream=stream))
+
+
+def result_to_csr_device(result, n_cols=0, stream=None):
+    """A result triple (:func:`result_buffers`' form; counts may be None = full rows) as CSR tensors on its device: ``(crow int64 [rows + 1],
+    col int32 [nnz], val float32 [nnz])``, every row best first as the result stores it."""
+    return DeviceMatrix.from_result(result, n_cols, stream).to_torch(stream)[:3]
+
+
+def _as_device_matrix(M, device, n_cols, stream):
+    """An operand of :func:`sparse_matmul_device` as a :class:`DeviceMatrix`."""
+    if isinstance(M, DeviceMatrix):
+        return M
+    if smat.issparse(M):
+        return DeviceMatrix.upload(M, device)
+    if isinstance(M, (tuple, list)) and len(M) == 4 and isinstance(M[3], (tuple, list)):
+        return DeviceMatrix.from_torch(*M)
+    if isinstance(M, (tuple, list)) and len(M) in (3, 4):
+        if len(M) == 4:
+            n_cols = M[3]
+        if n_cols is None:
+            raise ValueError("sparse_matmul_device: a result triple as the right operand needs its column count: pass (labels, scores, counts, n_cols)")
+        return DeviceMatrix.from_result(tuple(M[:3]), n_cols, stream)
+    raise TypeError(f"sparse_matmul_device: operand of type {type(M)}")
+
+
+def _operand_device(M):
+    if isinstance(M, DeviceMatrix):
+        return M.info["device"]
+    if isinstance(M, (tuple, list)):
+        return M[0].device.index
+    return None
+
+
+def sparse_matmul_device(A, B, eliminate_zeros=False, sorted_indices=True, stream=None):
+    """``A * B`` of two sparse matrices ON THE DEVICE (K10), by the reference's ``clib.sparse_matmul`` rule bit for bit (stored order of
+    the left rows = order of the additions; see ``xrl_sparse_matmul_device``).  An operand is a :class:`DeviceMatrix`; a scipy sparse matrix
+    (uploaded to the other operand's device); CSR tensors ``(crow, col, val, (rows, cols))``; or a result triple ``(labels, scores, counts)``
+    as :func:`predict_from_torch` / :func:`ensemble_device` return it, one row per query and one column per label -- as the left operand its
+    column count is the right operand's row count, as the right operand it is given as a fourth element.  Returns CSR tensors ``(crow int64,
+    col int32, val float32, (rows, cols))`` on that device, which can be an operand again.  Runs on ``stream`` (a raw HIP stream; default:
+    torch's current one), which it synchronises."""
+    dev = _operand_device(A)
+    if dev is None:
+        dev = _operand_device(B)
+    if dev is None:
+        dev = 0
+    b = _as_device_matrix(B, dev, None, stream)
+    a = _as_device_matrix(A, dev, b.shape[0], stream)
+    return a.multiply(b, eliminate_zeros, sorted_indices, stream=_stream_or_current(dev, stream)).to_torch(stream)
+
+
+def _stream_or_current(device, stream):
+    import torch
+    if stream is not None:
+        return stream
+    with torch.cuda.device(device):
+        return torch.cuda.current_stream().cuda_stream or None
 
 
 class Metrics(collections.namedtuple("Metrics", ["prec", "recall"])):
