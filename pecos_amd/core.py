@@ -517,16 +517,18 @@ class corelib(object):
         self._check()
         return dict(zip(("rows", "cols", "nnz", "device", "row_ptr", "col_idx", "val"), (int(v) for v in out)))
 
-    def smat_download(self, h):
-        """Copy of a matrix handle back to the host: a scipy CSR with the stored order and explicit zeros kept."""
-        info = self.smat_info(h)
-        rows, cols, nnz = info["rows"], info["cols"], info["nnz"]
+    def _download_csr(self, download, h, rows, cols, nnz):
+        """``download(h, row_ptr, col_idx, val)`` of a handle's CSR into fresh arrays -> a scipy CSR with the stored order and explicit zeros kept."""
         ptr = np.zeros(rows + 1, dtype=np.uint64); idx = np.zeros(max(nnz, 1), dtype=np.uint32); val = np.zeros(max(nnz, 1), dtype=np.float32)
-        self.clib_float32.xrl_smat_download(c_void_p(h), ptr.ctypes.data_as(c_void_p), idx.ctypes.data_as(c_void_p), val.ctypes.data_as(c_void_p))
-        self._check()
+        download(c_void_p(h), ptr.ctypes.data_as(c_void_p), idx.ctypes.data_as(c_void_p), val.ctypes.data_as(c_void_p)); self._check()
         m = smat.csr_matrix((rows, cols), dtype=np.float32)
         m.indptr, m.indices, m.data = ptr.astype(np.int64), idx[:nnz].astype(np.int64), val[:nnz]      # assigned directly: keeps explicit zeros / order
         return m
+
+    def smat_download(self, h):
+        """Copy of a matrix handle back to the host: a scipy CSR with the stored order and explicit zeros kept."""
+        info = self.smat_info(h)
+        return self._download_csr(self.clib_float32.xrl_smat_download, h, info["rows"], info["cols"], info["nnz"])
 
     def smat_copy_device(self, h, row_ptr_addr, col_idx_addr, val_addr, stream=None):
         """The handle's arrays into the caller's device buffers (raw addresses, sized from :meth:`smat_info`); synchronises ``stream``."""
@@ -739,11 +741,7 @@ class corelib(object):
             out = np.zeros((rows, cols), dtype=np.float32)
             dl(c_void_p(h), None, None, out.ctypes.data_as(c_void_p)); self._check()
             return out
-        ptr = np.zeros(rows + 1, dtype=np.uint64); idx = np.zeros(max(nnz, 1), dtype=np.uint32); val = np.zeros(max(nnz, 1), dtype=np.float32)
-        dl(c_void_p(h), ptr.ctypes.data_as(c_void_p), idx.ctypes.data_as(c_void_p), val.ctypes.data_as(c_void_p)); self._check()
-        m = smat.csr_matrix((rows, cols), dtype=np.float32)
-        m.indptr, m.indices, m.data = ptr.astype(np.int64), idx[:nnz].astype(np.int64), val[:nnz]      # assigned directly: keeps explicit zeros / order
-        return m
+        return self._download_csr(dl, h, rows, cols, nnz)
 
     def queries_free(self, h):
         if self._lib is not None and h:

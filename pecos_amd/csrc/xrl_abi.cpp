@@ -1,5 +1,6 @@
 // extern "C" surface of libxrl_amd.so (include/xrl_abi.h): device selection, model load / destruct / attributes, the host-ABI predict
-// wrappers, query handles, device-resident predicts, profile, options and the debug entry points.  The host pipeline behind
+// wrappers, query handles (and the upload / download / free bodies they share with the matrix handles of xrl_smat_abi.cpp),
+// device-resident predicts, profile, options and the debug entry points.  The host pipeline behind
 // c_xlinear_predict_* is xrl_host_pipeline.cpp, the single-layer / selected-outputs / inner-product entry points are xrl_single_layer.cpp,
 // the TF-IDF producer is xrl_tfidf_abi.cpp.  Every entry point catches all C++ exceptions and records them for xrl_last_error();
 // nothing is ever thrown across the C boundary.
@@ -34,11 +35,37 @@ void upload_x(const HostX& x, DevBuf& ptr, DevBuf& idx, DevBuf& val, QueriesDev&
     if (!x.given) fail("null X");
     const uint64_t elems = x.elems();
     if (x.csr) {
-        ptr.upload_raw(x.row_ptr, ((size_t)x.rows + 1) * 8);
+        if (x.rows) ptr.upload_raw(x.row_ptr, ((size_t)x.rows + 1) * 8);
+        else { ptr.reserve(8); XRL_HIP(hipMemset(ptr.p, 0, 8)); }
         idx.upload_raw(x.col_idx, elems * 4);
     }
     val.upload_raw(x.val, elems * 4);
     d = device_view(x, ptr, idx, val);
+}
+
+Queries* upload_handle(const HostX& x, int device) {
+    use_device(device);
+    auto q = std::make_unique<Queries>();
+    QueriesDev d{};
+    upload_x(x, q->own.ptr, q->own.idx, q->own.val, d);
+    q->own.nnz = d.nnz;
+    set_view(*q, device, d);
+    return q.release();
+}
+
+void download_csr(const QueriesDev& v, uint64_t* row_ptr, uint32_t* col_idx, float* val) {
+    XRL_HIP(hipMemcpy(row_ptr, v.row_ptr, ((size_t)v.rows + 1) * 8, hipMemcpyDeviceToHost));
+    if (v.nnz) {
+        XRL_HIP(hipMemcpy(col_idx, v.col_idx, (size_t)v.nnz * 4, hipMemcpyDeviceToHost));
+        XRL_HIP(hipMemcpy(val, v.val, (size_t)v.nnz * 4, hipMemcpyDeviceToHost));
+    }
+}
+
+void free_handle(void* h) {
+    Queries* q = static_cast<Queries*>(h);
+    if (!q) return;
+    if (q->own.ptr.p || q->own.idx.p || q->own.val.p) (void)hipSetDevice(q->device);
+    delete q;
 }
 }  // namespace xrl
 
@@ -171,15 +198,7 @@ int xrl_inspect_model(const char* model_path, uint64_t* out, uint32_t cap) {
 }
 
 static void* queries_upload(void* model, const HostX& x) {
-    return guarded_value((void*)nullptr, [&]() -> void* {
-        Model& m = *as_model(model);
-        use_device(m.device);
-        auto q = std::make_unique<Queries>();
-        QueriesDev d{};
-        upload_x(x, q->ptr, q->idx, q->val, d);
-        set_view(*q, m.device, d);
-        return q.release();
-    });
+    return guarded_value((void*)nullptr, [&]() -> void* { return upload_handle(x, as_model(model)->device); });
 }
 void* xrl_queries_upload_csr(void* model, const ScipyCsrF32* X) { return queries_upload(model, HostX(X)); }
 void* xrl_queries_upload_drm(void* model, const ScipyDrmF32* X) { return queries_upload(model, HostX(X)); }
@@ -203,8 +222,8 @@ void* xrl_queries_tfidf_device(void* model, uint32_t rows, uint32_t cols, const 
         if (rows && (!d_row_ptr || (nnz && (!d_col_idx || !d_count)))) fail("xrl_queries_tfidf_device: null device pointer");
         use_device(m.device);
         auto q = std::make_unique<Queries>();
-        if (!d_out) q->val.reserve(nnz * 4);         // the handle owns the weighted values unless the caller supplies the buffer; row pointers and column ids stay the caller's
-        float* dst = d_out ? d_out : q->val.as<float>();
+        if (!d_out) q->own.val.reserve(nnz * 4);         // the handle owns the weighted values unless the caller supplies the buffer; row pointers and column ids stay the caller's
+        float* dst = d_out ? d_out : q->own.val.as<float>();
         hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : m.stream;
         DevBuf d_err; d_err.reserve(4);
         XRL_HIP(hipMemsetAsync(d_err.p, 0, 4, s));
@@ -235,13 +254,13 @@ static void* concat_csr(void* model, uint32_t rows, uint32_t sparse_cols, const 
     if (rows && (!d_row_ptr || (nnz && (!d_col_idx || !d_val)) || (dense_cols && !d_emb))) fail("xrl_queries_concat_device: null device pointer");
     use_device(m.device);
     auto q = std::make_unique<Queries>();
-    const uint64_t out_nnz = nnz + (uint64_t)rows * dense_cols;
-    q->ptr.reserve(((size_t)rows + 1) * 8); q->idx.reserve(out_nnz * 4); q->val.reserve(out_nnz * 4);
+    DevCsr& o = q->own;
+    o.nnz = nnz + (uint64_t)rows * dense_cols;
+    o.ptr.reserve(((size_t)rows + 1) * 8); o.idx.reserve(o.nnz * 4); o.val.reserve(o.nnz * 4);
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : m.stream;
-    launch_concat_csr(d_row_ptr, d_col_idx, d_val, d_emb, rows, sparse_cols, dense_cols, normalize_emb, q->ptr.as<uint64_t>(), q->idx.as<uint32_t>(),
-                      q->val.as<float>(), s);
+    launch_concat_csr(d_row_ptr, d_col_idx, d_val, d_emb, rows, sparse_cols, dense_cols, normalize_emb, o.ptr.as<uint64_t>(), o.idx.as<uint32_t>(), o.val.as<float>(), s);
     XRL_HIP(hipStreamSynchronize(s));
-    set_own_csr(*q, m.device, rows, sparse_cols + dense_cols, out_nnz);
+    set_own_csr(*q, m.device, rows, sparse_cols + dense_cols);
     return q.release();
 }
 
@@ -285,24 +304,13 @@ int xrl_queries_download(void* queries, uint64_t* row_ptr, uint32_t* col_idx, fl
             XRL_HIP(hipMemcpy(val, q->dev.val, (size_t)q->dev.rows * q->dev.cols * 4, hipMemcpyDeviceToHost));
         } else {
             if (!row_ptr || (q->dev.nnz && !col_idx)) fail("null argument");
-            XRL_HIP(hipMemcpy(row_ptr, q->dev.row_ptr, ((size_t)q->dev.rows + 1) * 8, hipMemcpyDeviceToHost));
-            if (q->dev.nnz) {
-                XRL_HIP(hipMemcpy(col_idx, q->dev.col_idx, (size_t)q->dev.nnz * 4, hipMemcpyDeviceToHost));
-                XRL_HIP(hipMemcpy(val, q->dev.val, (size_t)q->dev.nnz * 4, hipMemcpyDeviceToHost));
-            }
+            download_csr(q->dev, row_ptr, col_idx, val);
         }
         return 0;
     });
 }
 
-void xrl_queries_free(void* queries) {
-    guarded([&] {
-        if (!queries) return;
-        Queries* q = static_cast<Queries*>(queries);
-        (void)hipSetDevice(q->device);
-        delete q;
-    });
-}
+void xrl_queries_free(void* queries) { guarded([&] { free_handle(queries); }); }
 
 // xrl_predict_device and xrl_predict_device_rows (`ranged`: the scratch is sized for any row range of these queries)
 static int predict_device_entry(const char* what, bool ranged, void* model, void* queries, uint32_t beam_size, const char* post_processor,

@@ -1,5 +1,6 @@
-// What the units behind the extern "C" surface share (xrl_abi.cpp, xrl_host_pipeline.cpp, xrl_single_layer.cpp, xrl_tfidf_abi.cpp):
-// the per-thread error and device state, the exception barrier of every entry point, the makers of X's device view, and the upload of a caller's host X.
+// What the units behind the extern "C" surface share (xrl_abi.cpp, xrl_host_pipeline.cpp, xrl_single_layer.cpp, xrl_tfidf_abi.cpp, xrl_smat_abi.cpp):
+// the per-thread error and device state, the exception barrier of every entry point, the makers of X's device view, the upload of a caller's host X,
+// and the bodies the query and matrix handles share.
 #pragma once
 #include "../../include/xrl_abi.h"
 
@@ -70,14 +71,20 @@ inline QueriesDev device_view(const HostX& x, const DevBuf& ptr, const DevBuf& i
     return x.csr ? csr_view(x.rows, x.cols, ptr.as<uint64_t>(), idx.as<uint32_t>(), val.as<float>(), x.elems()) : dense_view(x.rows, x.cols, val.as<float>());
 }
 
-// The only writer of a handle's device, view and (redundant) nnz: from a view of arrays it may or may not own ...
-inline void set_view(Queries& q, int device, const QueriesDev& v) { q.device = device; q.dev = v; q.nnz = v.nnz; }
-// ... or as a CSR in its own ptr / idx / val buffers
-inline void set_own_csr(Queries& q, int device, uint32_t rows, uint32_t cols, uint64_t nnz) {
-    set_view(q, device, csr_view(rows, cols, q.ptr.as<uint64_t>(), q.idx.as<uint32_t>(), q.val.as<float>(), nnz));
+// The only writer of a handle's device and view: from a view of arrays it may or may not own ...
+inline void set_view(Queries& q, int device, const QueriesDev& v) { q.device = device; q.dev = v; }
+// ... or as a CSR of the q.own.nnz entries in its own buffers
+inline void set_own_csr(Queries& q, int device, uint32_t rows, uint32_t cols) {
+    set_view(q, device, csr_view(rows, cols, q.own.ptr.as<uint64_t>(), q.own.idx.as<uint32_t>(), q.own.val.as<float>(), q.own.nnz));
 }
 
-// synchronous upload of the whole X into the given buffers (dense X: `val` only); `d` describes the device copy
+// synchronous upload of the whole X into the given buffers (dense X: `val` only; a CSR without rows: a zero ptr[0]); `d` describes the device copy
 void upload_x(const HostX& x, DevBuf& ptr, DevBuf& idx, DevBuf& val, QueriesDev& d);
+
+// What the xrl_queries_* and xrl_smat_* entry points share (xrl_abi.cpp), after their own argument checks: a host X as a handle on
+// `device` that owns its copy; a CSR view into the caller's host arrays (synchronous); a handle's end, its buffers freed with their device set.
+Queries* upload_handle(const HostX& x, int device);
+void download_csr(const QueriesDev& v, uint64_t* row_ptr, uint32_t* col_idx, float* val);
+void free_handle(void* h);
 
 }  // namespace xrl

@@ -1,4 +1,4 @@
-// Shared host-side helpers: error plumbing, HIP status checks, RAII device buffers.
+// Shared host-side helpers: error plumbing, HIP status checks, RAII device buffers, the owner of a CSR in HBM.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -60,6 +60,13 @@ struct DevBuf {
         reserve(bytes);
         if (bytes) XRL_HIP(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
     }
+};
+
+// The owner of a CSR in HBM: ptr u64 [rows + 1], idx u32 [nnz], val f32 [nnz].  Every producer of a device matrix fills one, and
+// it moves as a unit.
+struct DevCsr {
+    DevBuf ptr, idx, val;
+    uint64_t nnz = 0;
 };
 
 // Pinned host staging buffer (grow-only).

@@ -17,8 +17,7 @@
 
 #include <algorithm>
 
-#include <rocprim/device/device_scan.hpp>
-
+#include "xrl_devprim.h"
 #include "xrl_pairs.h"
 
 namespace xrl {
@@ -149,10 +148,7 @@ void set_output_constraint(Model& m, const uint32_t* labels, uint64_t n, bool on
         const dim3 grid((P + 3u) / 4u), block(256);
         if (P) { hipLaunchKernelGGL(kc_parent<0>, grid, block, 0, s, a); XRL_LAUNCH_CHECK(); }
         V.d_chunk_col.reserve(((size_t)P + 1) * 4);
-        size_t tmp_bytes = 0;
-        XRL_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, a.cnt, V.d_chunk_col.as<uint32_t>(), 0u, (size_t)P + 1, rocprim::plus<uint32_t>(), s));
-        d_tmp.reserve(tmp_bytes);
-        XRL_HIP(rocprim::exclusive_scan(d_tmp.p, tmp_bytes, a.cnt, V.d_chunk_col.as<uint32_t>(), 0u, (size_t)P + 1, rocprim::plus<uint32_t>(), s));
+        exclusive_scan(d_tmp, a.cnt, V.d_chunk_col.as<uint32_t>(), (size_t)P + 1, s);
         std::vector<uint32_t> cc((size_t)P + 1);
         XRL_HIP(hipMemcpyAsync(cc.data(), V.d_chunk_col.p, ((size_t)P + 1) * 4, hipMemcpyDeviceToHost, s));
         XRL_HIP(hipStreamSynchronize(s));

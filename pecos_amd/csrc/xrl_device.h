@@ -1,5 +1,5 @@
-// Device-side helpers shared by the HIP kernels (xrl_k1.hip, xrl_k1t.hip, xrl_k2.hip, xrl_k1q.hip): the reference's
-// post-processors, and a wavefront-wide top-k with the reference's ordering.
+// Device-side helpers shared by the HIP kernels (xrl_k1.hip, xrl_k1t.hip, xrl_k2.hip, xrl_k1q.hip; K9 and K10 for the lane rank and the
+// bisections): the reference's post-processors, a wavefront-wide top-k with the reference's ordering, lanes_below / lower_bound / segment_of.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -129,6 +129,19 @@ __device__ __forceinline__ uint32_t ensemble_key(float v) { return v != v ? 1u :
 
 __device__ __forceinline__ uint32_t lanes_below(unsigned long long m) {   // set bits of m below this lane
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+// the first position of the ascending a[0, n) whose entry is not below key (n: none)
+template <class T> __device__ __forceinline__ uint32_t lower_bound(const T* __restrict__ a, uint32_t n, T key) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (a[mid] < key) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+// the segment of position x under the offsets off[0, n_seg): the last one that starts at or before it (empty segments share their successor's offset)
+__device__ __forceinline__ uint32_t segment_of(const uint32_t* off, uint32_t n_seg, uint32_t x) {
+    uint32_t lo = 0, hi = n_seg;
+    while (hi - lo > 1) { const uint32_t mid = lo + ((hi - lo) >> 1); if (off[mid] <= x) lo = mid; else hi = mid; }
+    return lo;
 }
 
 template <int N>

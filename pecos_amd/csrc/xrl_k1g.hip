@@ -83,31 +83,6 @@ __global__ void __launch_bounds__(256) k1g_count_blocks(const uint32_t* __restri
     if (t < n_tiles) blk[t] = (start[t + 1] - start[t] + qb - 1u) / qb;
 }
 
-// single block: exclusive scan of v[0..n) in place; v[n] = grand total
-__global__ void __launch_bounds__(1024) k1g_scan_kernel(uint32_t* __restrict__ v, uint32_t n) {
-    __shared__ uint32_t part[1024];
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < n; base += 1024) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t x = i < n ? v[i] : 0u;
-        part[threadIdx.x] = x;
-        __syncthreads();
-        for (uint32_t off = 1; off < 1024; off <<= 1) {
-            const uint32_t t = threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
-            __syncthreads();
-            part[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < n) v[i] = carry + part[threadIdx.x] - x;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += part[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) v[n] = carry;
-}
-
 // RQ x RC: register tile of a lane (queries x columns); CS: wavefronts of the workgroup side by side along the COLUMNS (1 or 2; the
 // other 4 / CS stack along the queries); KC: features per LDS step.
 template <int RQ, int RC, int CS, int KC, int PPC>
@@ -330,7 +305,7 @@ template <int RQ, int RC, int CS, int KC>
 static void k1g_go(K1GArgs& a, const LayerDev& L, const LayerPlan& P, uint32_t* blk_start, hipStream_t s) {
     constexpr uint32_t qb = K1GShape<RQ, RC, CS, KC>::QB;
     hipLaunchKernelGGL(k1g_count_blocks, dim3((L.n_tiles + 255u) / 256u), dim3(256), 0, s, a.start, L.n_tiles, qb, blk_start);
-    hipLaunchKernelGGL(k1g_scan_kernel, dim3(1), dim3(1024), 0, s, blk_start, L.n_tiles);
+    launch_block_scan(blk_start, L.n_tiles, s);
     const uint64_t n_slots = (uint64_t)P.nrows * P.beam_in * L.max_tiles_per_parent;
     const uint64_t blocks = (n_slots + qb - 1) / qb + L.n_tiles;      // every tile adds at most one partial workgroup
     if (blocks > 0x7FFFFFFFull) fail("k1g: grid too large; lower max_batch_rows");

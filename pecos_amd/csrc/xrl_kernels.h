@@ -73,6 +73,8 @@ size_t k0_item_bytes();
 // compiled -- sparse queries, 16 or 32 lanes per item, post-processors of class 0 -- instead of a grid sized for n_slots.  Returns whether it ran.
 bool launch_k1(const LayerDev& L, const LayerPlan& P, const QueriesDev& X, const void* items, const uint32_t* n_items,
                float* cand, int group, hipStream_t s, uint32_t list_grid = 0);
+// one workgroup: exclusive scan of v[0, n) in place, v[n] = the total (xrl_devprim.hip); the caller checks the launch with its own
+void launch_block_scan(uint32_t* v, uint32_t n, hipStream_t s);
 // counting sort of the item descriptors by tile (LDS histograms, no global atomics); start[n_tiles] = #items
 void launch_sort_items(const LayerDev& L, uint64_t n_slots, const void* items, void* sorted, uint32_t* H,
                        uint32_t* start, hipStream_t s,

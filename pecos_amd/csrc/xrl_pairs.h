@@ -22,12 +22,6 @@ namespace xrl {
 constexpr int PG = 16;            // lanes per pair
 constexpr int PAIRS_PER_BLOCK = 256 / PG;
 
-__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* __restrict__ a, uint32_t n, uint32_t key) {
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (a[mid] < key) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-
 // acc = fl32(acc + p_b) for the lanes b of this group whose bit is set in gm, in lane order
 __device__ __forceinline__ float fold_in_lane_order(float acc, float prod, uint32_t gm, int gbase) {
     float p[PG];
@@ -52,7 +46,7 @@ __device__ __forceinline__ float dot_sparse_sparse(const uint32_t* __restrict__ 
         const bool ok = t < an;
         const uint32_t key = ai[ok ? t : 0u];
         const float a = av[ok ? t : 0u];
-        const uint32_t pos = ok && bn ? lower_bound_u32(bi, bn, key) : bn;
+        const uint32_t pos = ok && bn ? lower_bound(bi, bn, key) : bn;
         const bool hit = pos < bn && bi[pos] == key;
         const float prod = hit ? __fmul_rn(a, bv[pos]) : 0.0f;
         const uint32_t gm = (uint32_t)(__ballot(hit) >> gbase) & 0xFFFFu;
@@ -74,7 +68,7 @@ __device__ __forceinline__ float chain_sparse_sparse(float acc, const uint32_t* 
         const bool ok = t < an;
         const uint32_t key = ai[ok ? t : 0u];
         const float a = av[ok ? t : 0u];
-        const uint32_t pos = ok && bn ? lower_bound_u32(bi, bn, key) : bn;
+        const uint32_t pos = ok && bn ? lower_bound(bi, bn, key) : bn;
         const bool hit = pos < bn && bi[pos] == key;
         const float prod = hit ? __fmul_rn(a, bv[pos]) : 0.0f;
         const uint32_t gm = (uint32_t)(__ballot(hit) >> gbase) & 0xFFFFu;

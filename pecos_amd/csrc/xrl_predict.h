@@ -5,11 +5,12 @@
 
 namespace xrl {
 
+// A matrix on one device, behind every xrl_queries_* and xrl_smat_* handle: a view (CSR or dense) of arrays the handle owns or of the
+// caller's.  set_view / set_own_csr (xrl_abi_common.h) are the only writers of the view.
 struct Queries {
     int device = 0;
-    DevBuf ptr, idx, val;
+    DevCsr own;
     QueriesDev dev{};
-    uint64_t nnz = 0;
 };
 
 struct PredictOpts {

@@ -12,8 +12,9 @@ namespace xrl {
 // working on one tile run back to back on ONE XCD and find the tile's bitmap / rows / entries in
 // that XCD's L2 instead of HBM (the reference sorts its (query, chunk) pairs by chunk for the same
 // reason, inference.hpp:991-993).  Device-scope atomics are slow across the 8 XCDs, so the sort
-// uses only LDS atomics: per-block LDS histograms -> per-(block, tile) offsets -> LDS-ranked
-// scatter.  Order inside a tile is arbitrary; results do not depend on it.
+// uses only LDS atomics: per-block LDS histograms -> per-(block, tile) offsets -> the shared
+// single-block scan of the tile totals (launch_block_scan) -> LDS-ranked scatter.  Order
+// inside a tile is arbitrary; results do not depend on it.
 // ---------------------------------------------------------------------------------------------
 constexpr uint32_t kSortChunk = 8192;    // item slots per block
 
@@ -42,31 +43,6 @@ sort_colsum_kernel(uint32_t* __restrict__ H, uint32_t B, const uint32_t* __restr
     uint32_t run = 0;
     for (uint32_t b = 0; b < B; ++b) { const uint32_t c = H[(size_t)b * T + t]; H[(size_t)b * T + t] = run; run += c; }
     total[t] = run;
-}
-
-// single block: exclusive scan of v[0..n) in place; v[n] = grand total
-__global__ void __launch_bounds__(1024) sort_scan_kernel(uint32_t* __restrict__ v, uint32_t n) {
-    __shared__ uint32_t part[1024];
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < n; base += 1024) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t x = i < n ? v[i] : 0u;
-        part[threadIdx.x] = x;
-        __syncthreads();
-        for (uint32_t off = 1; off < 1024; off <<= 1) {
-            const uint32_t t = threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
-            __syncthreads();
-            part[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < n) v[i] = carry + part[threadIdx.x] - x;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += part[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) v[n] = carry;
 }
 
 __global__ void __launch_bounds__(256)
@@ -100,7 +76,7 @@ void launch_sort_items(const LayerDev& L, uint64_t n_slots, const void* items, v
     }
     hipLaunchKernelGGL(sort_hist_kernel, dim3(B), dim3(256), lds, s, static_cast<const ItemDesc*>(items), n_slots, n_dev, T, H);
     hipLaunchKernelGGL(sort_colsum_kernel, dim3((T + 255) / 256), dim3(256), 0, s, H, B, n_dev, T, start);
-    hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(1024), 0, s, start, T);
+    launch_block_scan(start, T, s);
     hipLaunchKernelGGL(sort_scatter_kernel, dim3(B), dim3(256), lds, s, static_cast<const ItemDesc*>(items), n_slots, n_dev, T, H,
                        start, static_cast<ItemDesc*>(sorted));
     XRL_LAUNCH_CHECK();
@@ -153,7 +129,7 @@ void launch_sort_queries(BeamDev prev, uint32_t nrows, uint32_t n_keys, uint32_t
     const size_t lds = (size_t)n_keys * 4;
     hipLaunchKernelGGL(qsort_hist_kernel, dim3(B), dim3(256), lds, s, prev.idx, prev.cnt, prev.stride, nrows, n_keys, H);
     hipLaunchKernelGGL(sort_colsum_kernel, dim3((n_keys + 255) / 256), dim3(256), 0, s, H, B, nullptr, n_keys, start);
-    hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(1024), 0, s, start, n_keys);
+    launch_block_scan(start, n_keys, s);
     hipLaunchKernelGGL(qsort_scatter_kernel, dim3(B), dim3(256), lds, s, prev.idx, prev.cnt, prev.stride, nrows, n_keys, H, start, perm);
     XRL_LAUNCH_CHECK();
 }

@@ -2,7 +2,7 @@
 // the arithmetic of the reference's smat_x_smat (pecos/core/utils/matrix.hpp:1075-1292) bit for bit -- the rule is stated in
 // include/xrl_abi.h at xrl_sparse_matmul_device.
 #pragma once
-#include "xrl_common.h"
+#include "xrl_kernels.h"
 
 namespace xrl {
 
@@ -15,30 +15,19 @@ constexpr uint32_t kSpgemmCap = 1024;
 // scratch of one batch of big-form rows per product: two 8-byte sort keys, the product, the head flag and its scan
 constexpr uint64_t kSpgemmBigBytesPerProduct = 28;
 
-// a CSR in HBM as the kernels see it; nnz bounds every row_ptr entry that is read
-struct CsrDev {
-    uint32_t rows = 0, cols = 0;
-    uint64_t nnz = 0;
-    const uint64_t* row_ptr = nullptr;
-    const uint32_t* col_idx = nullptr;
-    const float* val = nullptr;
-};
-
 struct SpgemmOut {
-    DevBuf ptr, idx, val;          // the product before eliminate_zeros: u64 [rows + 1], u32 [nnz], f32 [nnz]
-    uint64_t nnz = 0;
-    DevBuf e_ptr, e_idx, e_val;    // with eliminate_zeros: the compacted product
-    uint64_t e_nnz = 0;
+    DevCsr z;                      // the product before eliminate_zeros
+    DevCsr e;                      // with eliminate_zeros: the compacted product
     uint64_t lds_rows = 0, big_rows = 0, batches = 0;
 };
 
-// Enqueues on s and synchronises it (once when no row needs the big form).  A.cols == B.rows is the caller's to check.  Fails when an
-// entry of A names a row B does not have, or a row holds 2^31 products or more.
-void spgemm_device(const CsrDev& A, const CsrDev& B, bool eliminate_zeros, bool sorted_indices, hipStream_t s, SpgemmOut& out);
+// A and B: CSR views (the callers check); nnz bounds every row_ptr entry that is read.  Enqueues on s and synchronises it (once when no
+// row needs the big form).  A.cols == B.rows is the caller's to check.  Fails when an entry of A names a row B does not have, or a row
+// holds 2^31 products or more.
+void spgemm_device(const QueriesDev& A, const QueriesDev& B, bool eliminate_zeros, bool sorted_indices, hipStream_t s, SpgemmOut& out);
 
 // fixed-stride result (idx / val [rows * stride], cnt [rows] or nullptr = stride entries in every row; a count above the stride is read
-// as the stride) -> CSR with the stored best-first order kept.  Enqueues on s and synchronises it; returns nnz.
-uint64_t topk_to_csr_device(uint32_t rows, const uint32_t* d_idx, const float* d_val, const uint32_t* d_cnt, uint32_t stride, hipStream_t s,
-                            DevBuf& ptr, DevBuf& idx, DevBuf& val);
+// as the stride) -> CSR with the stored best-first order kept.  Enqueues on s and synchronises it.
+void topk_to_csr_device(uint32_t rows, const uint32_t* d_idx, const float* d_val, const uint32_t* d_cnt, uint32_t stride, hipStream_t s, DevCsr& out);
 
 }  // namespace xrl

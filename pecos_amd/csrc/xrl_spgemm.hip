@@ -14,23 +14,26 @@
 //                    segmented radix sort of the 64-bit keys (no reliance on stability), k10_big_flags marks the run heads at their
 //                    output rank's position, an exclusive scan ranks them, k10_big_cnt / k10_big_fill count / sum and write.
 //   counts -> exclusive scan (u64) -> fill; eliminate_zeros is one more counted, scanned and copied pass (k10_nz<FILL>).
-//   k10_topk_cnt / k10_copy_rows: a fixed-stride result as a CSR.
+//   k10_topk_cnt, then the shared row copy (xrl_devprim.h): a fixed-stride result as a CSR.
 //
 // Bounds: every row span is clamped to the operand's nnz; an LDS index is below CAP and a scratch index below its row's share before the
 // write; an output index is below the row's end in the scanned row pointer.
 #include "xrl_spgemm.h"
+#include "xrl_device.h"
+#include "xrl_devprim.h"
 #include "xrl_predict.h"
 
 #include <algorithm>
 #include <cstdlib>
 #include <vector>
 
-#include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 namespace xrl {
 
 namespace {
+
+constexpr const char* kWhat = "sparse_matmul";         // the family in a "grid too large" message
 
 struct K10Args {
     const uint64_t* a_ptr; const uint32_t* a_col; const float* a_val; uint64_t a_nnz;
@@ -41,8 +44,6 @@ struct K10Args {
     uint64_t* cnt;                                         // [rows + 1] the count passes' output
     const uint64_t* out_ptr; uint32_t* out_col; float* out_val;   // the fill passes' output
 };
-
-__device__ __forceinline__ uint32_t below(unsigned long long m, uint32_t lane) { return (uint32_t)__popcll(m & ((1ull << lane) - 1ull)); }
 
 // The NaN the reference's host (x86 SSE) leaves: a NaN operand comes back quieted, the first operand's first; an invalid operation
 // (0 * inf, inf - inf) gives the default NaN, whose sign bit is set.  r = x op y as the device computed it.
@@ -125,8 +126,7 @@ __global__ void __launch_bounds__(64) k10_lds(K10Args a) {
         for (uint32_t p0 = 0; p0 < total; p0 += 64u) {
             const uint32_t p = p0 + lane, qq = q + p;
             if (p < total && qq < kSpgemmCap) {
-                uint32_t lo = 0, hi = 64;                  // the last entry whose products start at or before p (empty B rows share their successor's offset)
-                while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (s_off[mid] <= p) lo = mid; else hi = mid; }
+                const uint32_t lo = segment_of(s_off, 64u, p);             // the last entry whose products start at or before p
                 const uint64_t at = s_kb[lo] + (p - s_off[lo]);
                 s_key[qq] = ((uint64_t)a.b_col[at] << 32) | qq;
                 if (FILL) s_val[qq] = ref_mul(s_a[lo], a.b_val[at]);
@@ -181,7 +181,7 @@ __global__ void __launch_bounds__(64) k10_lds(K10Args a) {
             uint32_t j = x;
             do { acc = ref_add(acc, s_val[(uint32_t)s_key[j] & (kSpgemmCap - 1u)]); ++j; } while (j < nf && (uint32_t)(s_key[j] >> 32) == col);
             uint32_t slot;
-            if (a.sorted) slot = r0 + below(m, lane);
+            if (a.sorted) slot = r0 + lanes_below(m);
             else {
                 const uint32_t w = q0 >> 5;
                 slot = (uint32_t)__popc(s_bm[w] & ((1u << (q0 & 31u)) - 1u));
@@ -218,13 +218,6 @@ k10_big_expand(K10Args a, const uint32_t* __restrict__ big_row, const uint32_t* 
         }
         q += len;
     }
-}
-
-// the segment of position x: the last one that starts at or before it
-__device__ __forceinline__ uint32_t segment_of(const uint32_t* off, uint32_t n_seg, uint32_t x) {
-    uint32_t lo = 0, hi = n_seg;
-    while (hi - lo > 1) { const uint32_t mid = lo + ((hi - lo) >> 1); if (off[mid] <= x) lo = mid; else hi = mid; }
-    return lo;
 }
 
 // flag <- 1 at the position whose exclusive scan is the run's output rank: the head's own (by column) or its row's offset + first q
@@ -284,7 +277,7 @@ k10_nz(const uint64_t* __restrict__ ptr, const uint32_t* __restrict__ col, const
         const bool keep = x < e && v != 0.0f;
         const unsigned long long m = __ballot(keep);
         if (FILL && keep) {
-            const uint64_t at = dst + n + below(m, lane);
+            const uint64_t at = dst + n + lanes_below(m);
             if (at < dst_end) { e_col[at] = col[x]; e_val[at] = v; }
         }
         n += (uint64_t)__popcll(m);
@@ -296,36 +289,6 @@ k10_nz(const uint64_t* __restrict__ ptr, const uint32_t* __restrict__ col, const
 __global__ void __launch_bounds__(256) k10_topk_cnt(const uint32_t* __restrict__ d_cnt, uint32_t stride, uint64_t rows, uint64_t* __restrict__ cnt) {
     const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (r < rows) cnt[r] = d_cnt ? min(d_cnt[r], stride) : stride;
-}
-
-// one wavefront per row: its ptr[r + 1] - ptr[r] entries from src_stride * r
-__global__ void __launch_bounds__(256)
-k10_copy_rows(const uint64_t* __restrict__ ptr, uint64_t rows, uint32_t src_stride, const uint32_t* __restrict__ s_idx, const float* __restrict__ s_val,
-              uint32_t* __restrict__ idx, float* __restrict__ val) {
-    const uint64_t r = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (r >= rows) return;
-    const uint64_t dst = ptr[r], n = min(ptr[r + 1] - dst, (uint64_t)src_stride), src = r * src_stride;
-    for (uint64_t x = threadIdx.x & 63u; x < n; x += 64u) { idx[dst + x] = s_idx[src + x]; val[dst + x] = s_val[src + x]; }
-}
-
-uint32_t blocks_of(uint64_t n, uint32_t per) {
-    const uint64_t b = (n + per - 1) / per;
-    if (b > 0x7FFFFFFFull) fail("sparse_matmul: grid too large");
-    return (uint32_t)b;
-}
-
-void scan_u64(DevBuf& tmp, const uint64_t* in, uint64_t* out, size_t n, hipStream_t s) {
-    size_t bytes = 0;
-    XRL_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s));
-    tmp.reserve(bytes);
-    XRL_HIP(rocprim::exclusive_scan(tmp.p, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s));
-}
-
-void scan_u32(DevBuf& tmp, const uint32_t* in, uint32_t* out, size_t n, hipStream_t s) {
-    size_t bytes = 0;
-    XRL_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), s));
-    tmp.reserve(bytes);
-    XRL_HIP(rocprim::exclusive_scan(tmp.p, bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), s));
 }
 
 constexpr uint32_t kLdsGridRows = 1u << 30;                // rows of one launch of the LDS form
@@ -367,16 +330,15 @@ uint64_t run_big(K10Args a, const std::vector<uint32_t>& big, const std::vector<
         const uint32_t* d_row = B.row.as<uint32_t>(); const uint32_t* d_off = B.off.as<uint32_t>();
         hipLaunchKernelGGL(k10_big_expand, dim3(n_seg), dim3(256), 0, s, a, d_row, d_off, B.keys.as<uint64_t>(), fill ? B.prod.as<float>() : nullptr);
         XRL_LAUNCH_CHECK();
-        size_t bytes = 0;
-        XRL_HIP(rocprim::segmented_radix_sort_keys(nullptr, bytes, B.keys.as<uint64_t>(), B.keys2.as<uint64_t>(), total, n_seg, d_off, d_off + 1, 0u, 64u, s));
-        B.tmp.reserve(bytes);
-        XRL_HIP(rocprim::segmented_radix_sort_keys(B.tmp.p, bytes, B.keys.as<uint64_t>(), B.keys2.as<uint64_t>(), total, n_seg, d_off, d_off + 1, 0u, 64u, s));
+        with_rocprim_tmp(B.tmp, [&](void* t, size_t& bytes) {
+            return rocprim::segmented_radix_sort_keys(t, bytes, B.keys.as<uint64_t>(), B.keys2.as<uint64_t>(), total, n_seg, d_off, d_off + 1, 0u, 64u, s);
+        });
         XRL_HIP(hipMemsetAsync(B.flag.p, 0, ((size_t)total + 1) * 4, s));
-        hipLaunchKernelGGL(k10_big_flags, dim3(blocks_of(total, 256)), dim3(256), 0, s, B.keys2.as<uint64_t>(), d_off, n_seg, total, a.sorted, B.flag.as<uint32_t>());
+        hipLaunchKernelGGL(k10_big_flags, dim3(blocks_of(total, 256, kWhat)), dim3(256), 0, s, B.keys2.as<uint64_t>(), d_off, n_seg, total, a.sorted, B.flag.as<uint32_t>());
         XRL_LAUNCH_CHECK();
-        scan_u32(B.tmp, B.flag.as<uint32_t>(), B.slot.as<uint32_t>(), (size_t)total + 1, s);
-        if (!fill) hipLaunchKernelGGL(k10_big_cnt, dim3(blocks_of(n_seg, 256)), dim3(256), 0, s, B.slot.as<uint32_t>(), d_row, d_off, n_seg, a.cnt);
-        else hipLaunchKernelGGL(k10_big_fill, dim3(blocks_of(total, 256)), dim3(256), 0, s, a, B.keys2.as<uint64_t>(), B.prod.as<float>(), B.slot.as<uint32_t>(), d_row, d_off, n_seg, total);
+        exclusive_scan(B.tmp, B.flag.as<uint32_t>(), B.slot.as<uint32_t>(), (size_t)total + 1, s);
+        if (!fill) hipLaunchKernelGGL(k10_big_cnt, dim3(blocks_of(n_seg, 256, kWhat)), dim3(256), 0, s, B.slot.as<uint32_t>(), d_row, d_off, n_seg, a.cnt);
+        else hipLaunchKernelGGL(k10_big_fill, dim3(blocks_of(total, 256, kWhat)), dim3(256), 0, s, a, B.keys2.as<uint64_t>(), B.prod.as<float>(), B.slot.as<uint32_t>(), d_row, d_off, n_seg, total);
         XRL_LAUNCH_CHECK();
         ++batches;
         g0 = g1;
@@ -386,12 +348,14 @@ uint64_t run_big(K10Args a, const std::vector<uint32_t>& big, const std::vector<
 
 }  // namespace
 
-void spgemm_device(const CsrDev& A, const CsrDev& Bm, bool eliminate_zeros, bool sorted_indices, hipStream_t s, SpgemmOut& out) {
+void spgemm_device(const QueriesDev& A, const QueriesDev& Bm, bool eliminate_zeros, bool sorted_indices, hipStream_t s, SpgemmOut& out) {
     const uint64_t rows = A.rows;
-    out.ptr.reserve((rows + 1) * 8);
-    XRL_HIP(hipMemsetAsync(out.ptr.p, 0, (rows + 1) * 8, s));
-    out.nnz = out.e_nnz = 0;
-    if (eliminate_zeros) { out.e_ptr.reserve((rows + 1) * 8); XRL_HIP(hipMemsetAsync(out.e_ptr.p, 0, (rows + 1) * 8, s)); }
+    DevCsr& Z = out.z;
+    DevCsr& E = out.e;
+    Z.ptr.reserve((rows + 1) * 8);
+    XRL_HIP(hipMemsetAsync(Z.ptr.p, 0, (rows + 1) * 8, s));
+    Z.nnz = E.nnz = 0;
+    if (eliminate_zeros) { E.ptr.reserve((rows + 1) * 8); XRL_HIP(hipMemsetAsync(E.ptr.p, 0, (rows + 1) * 8, s)); }
     if (rows == 0 || A.nnz == 0 || Bm.nnz == 0 || Bm.rows == 0) { XRL_HIP(hipStreamSynchronize(s)); return; }
 
     K10Args a{};
@@ -403,14 +367,15 @@ void spgemm_device(const CsrDev& A, const CsrDev& Bm, bool eliminate_zeros, bool
     XRL_HIP(hipMemsetAsync(d_cnt.p, 0, (rows + 1) * 8, s));
     XRL_HIP(hipMemsetAsync(d_words.p, 0, 24, s));
     a.flops = d_flops.as<uint64_t>(); a.cnt = d_cnt.as<uint64_t>();
-    hipLaunchKernelGGL(k10_flops, dim3(blocks_of(rows, 256)), dim3(256), 0, s, a, d_flops.as<uint64_t>(), d_words.as<unsigned long long>());
+    hipLaunchKernelGGL(k10_flops, dim3(blocks_of(rows, 256, kWhat)), dim3(256), 0, s, a, d_flops.as<uint64_t>(), d_words.as<unsigned long long>());
     XRL_LAUNCH_CHECK();
-    // the LDS form's counts go ahead of the answer to "does any row need the big form": the common case synchronises once
+    // the LDS form's counts go ahead of the answer to "does any row need the big form": the common case synchronises once, so this
+    // scan reads its total back next to the words instead of through scan_total
     launch_lds<false>(a, s);
-    scan_u64(d_tmp, d_cnt.as<uint64_t>(), out.ptr.as<uint64_t>(), (size_t)rows + 1, s);
+    exclusive_scan(d_tmp, d_cnt.as<uint64_t>(), Z.ptr.as<uint64_t>(), (size_t)rows + 1, s);
     uint64_t words[3] = {0, 0, 0};
     XRL_HIP(hipMemcpyAsync(words, d_words.p, 24, hipMemcpyDeviceToHost, s));
-    XRL_HIP(hipMemcpyAsync(&out.nnz, out.ptr.as<uint64_t>() + rows, 8, hipMemcpyDeviceToHost, s));
+    XRL_HIP(hipMemcpyAsync(&Z.nnz, Z.ptr.as<uint64_t>() + rows, 8, hipMemcpyDeviceToHost, s));
     XRL_HIP(hipStreamSynchronize(s));
     if (words[1]) fail("sparse_matmul: an entry of the left operand names a row the right operand does not have");
     if (words[2]) fail("sparse_matmul: a row of the product takes 2^31 multiplications or more; split the left operand's row");
@@ -423,57 +388,48 @@ void spgemm_device(const CsrDev& A, const CsrDev& Bm, bool eliminate_zeros, bool
         XRL_HIP(hipStreamSynchronize(s));
         for (uint64_t i = 0; i < rows; ++i) if (F[i] > kSpgemmCap) big.push_back((uint32_t)i);
         out.batches = run_big(a, big, F, false, s, scratch);
-        scan_u64(d_tmp, d_cnt.as<uint64_t>(), out.ptr.as<uint64_t>(), (size_t)rows + 1, s);
-        XRL_HIP(hipMemcpyAsync(&out.nnz, out.ptr.as<uint64_t>() + rows, 8, hipMemcpyDeviceToHost, s));
-        XRL_HIP(hipStreamSynchronize(s));
+        Z.nnz = scan_total(d_tmp, d_cnt.as<uint64_t>(), Z.ptr.as<uint64_t>(), rows, s);
     }
     out.big_rows = big.size();
     out.lds_rows = rows - big.size();
 
-    out.idx.reserve(out.nnz * 4); out.val.reserve(out.nnz * 4);
-    if (out.nnz) {
-        a.out_ptr = out.ptr.as<uint64_t>(); a.out_col = out.idx.as<uint32_t>(); a.out_val = out.val.as<float>();
+    Z.idx.reserve(Z.nnz * 4); Z.val.reserve(Z.nnz * 4);
+    if (Z.nnz) {
+        a.out_ptr = Z.ptr.as<uint64_t>(); a.out_col = Z.idx.as<uint32_t>(); a.out_val = Z.val.as<float>();
         if (big.size() < rows) launch_lds<true>(a, s);
         if (!big.empty()) run_big(a, big, F, true, s, scratch);
     }
-    if (eliminate_zeros && out.nnz) {
-        hipLaunchKernelGGL(k10_nz<false>, dim3(blocks_of(rows, 4)), dim3(256), 0, s, out.ptr.as<uint64_t>(), out.idx.as<uint32_t>(), out.val.as<float>(), rows,
+    if (eliminate_zeros && Z.nnz) {
+        hipLaunchKernelGGL(k10_nz<false>, dim3(blocks_of(rows, 4, kWhat)), dim3(256), 0, s, Z.ptr.as<uint64_t>(), Z.idx.as<uint32_t>(), Z.val.as<float>(), rows,
                            d_cnt.as<uint64_t>(), (const uint64_t*)nullptr, (uint32_t*)nullptr, (float*)nullptr);
         XRL_LAUNCH_CHECK();
-        scan_u64(d_tmp, d_cnt.as<uint64_t>(), out.e_ptr.as<uint64_t>(), (size_t)rows + 1, s);
-        XRL_HIP(hipMemcpyAsync(&out.e_nnz, out.e_ptr.as<uint64_t>() + rows, 8, hipMemcpyDeviceToHost, s));
-        XRL_HIP(hipStreamSynchronize(s));
-        out.e_idx.reserve(out.e_nnz * 4); out.e_val.reserve(out.e_nnz * 4);
-        if (out.e_nnz) {
-            hipLaunchKernelGGL(k10_nz<true>, dim3(blocks_of(rows, 4)), dim3(256), 0, s, out.ptr.as<uint64_t>(), out.idx.as<uint32_t>(), out.val.as<float>(), rows,
-                               (uint64_t*)nullptr, out.e_ptr.as<uint64_t>(), out.e_idx.as<uint32_t>(), out.e_val.as<float>());
+        E.nnz = scan_total(d_tmp, d_cnt.as<uint64_t>(), E.ptr.as<uint64_t>(), rows, s);
+        E.idx.reserve(E.nnz * 4); E.val.reserve(E.nnz * 4);
+        if (E.nnz) {
+            hipLaunchKernelGGL(k10_nz<true>, dim3(blocks_of(rows, 4, kWhat)), dim3(256), 0, s, Z.ptr.as<uint64_t>(), Z.idx.as<uint32_t>(), Z.val.as<float>(), rows,
+                               (uint64_t*)nullptr, E.ptr.as<uint64_t>(), E.idx.as<uint32_t>(), E.val.as<float>());
             XRL_LAUNCH_CHECK();
         }
     }
     XRL_HIP(hipStreamSynchronize(s));                      // the scratch goes with this scope
 }
 
-uint64_t topk_to_csr_device(uint32_t rows, const uint32_t* d_idx, const float* d_val, const uint32_t* d_cnt, uint32_t stride, hipStream_t s,
-                            DevBuf& ptr, DevBuf& idx, DevBuf& val) {
-    ptr.reserve(((size_t)rows + 1) * 8);
-    XRL_HIP(hipMemsetAsync(ptr.p, 0, ((size_t)rows + 1) * 8, s));
-    uint64_t nnz = 0;
-    if (rows == 0 || stride == 0) { XRL_HIP(hipStreamSynchronize(s)); return 0; }
+void topk_to_csr_device(uint32_t rows, const uint32_t* d_idx, const float* d_val, const uint32_t* d_cnt, uint32_t stride, hipStream_t s, DevCsr& out) {
+    out.ptr.reserve(((size_t)rows + 1) * 8);
+    XRL_HIP(hipMemsetAsync(out.ptr.p, 0, ((size_t)rows + 1) * 8, s));
+    out.nnz = 0;
+    if (rows == 0 || stride == 0) { XRL_HIP(hipStreamSynchronize(s)); return; }
     DevBuf d_n, d_tmp;
     d_n.reserve(((size_t)rows + 1) * 8);
     XRL_HIP(hipMemsetAsync(d_n.p, 0, ((size_t)rows + 1) * 8, s));
-    hipLaunchKernelGGL(k10_topk_cnt, dim3(blocks_of(rows, 256)), dim3(256), 0, s, d_cnt, stride, (uint64_t)rows, d_n.as<uint64_t>());
+    hipLaunchKernelGGL(k10_topk_cnt, dim3(blocks_of(rows, 256, kWhat)), dim3(256), 0, s, d_cnt, stride, (uint64_t)rows, d_n.as<uint64_t>());
     XRL_LAUNCH_CHECK();
-    scan_u64(d_tmp, d_n.as<uint64_t>(), ptr.as<uint64_t>(), (size_t)rows + 1, s);
-    XRL_HIP(hipMemcpyAsync(&nnz, ptr.as<uint64_t>() + rows, 8, hipMemcpyDeviceToHost, s));
-    XRL_HIP(hipStreamSynchronize(s));
-    idx.reserve(nnz * 4); val.reserve(nnz * 4);
-    if (nnz) {
-        hipLaunchKernelGGL(k10_copy_rows, dim3(blocks_of(rows, 4)), dim3(256), 0, s, ptr.as<uint64_t>(), (uint64_t)rows, stride, d_idx, d_val, idx.as<uint32_t>(), val.as<float>());
-        XRL_LAUNCH_CHECK();
+    out.nnz = scan_total(d_tmp, d_n.as<uint64_t>(), out.ptr.as<uint64_t>(), rows, s);
+    out.idx.reserve(out.nnz * 4); out.val.reserve(out.nnz * 4);
+    if (out.nnz) {
+        launch_copy_rows(out.ptr.as<uint64_t>(), rows, nullptr, stride, d_idx, d_val, out.idx.as<uint32_t>(), out.val.as<float>(), kWhat, s);
         XRL_HIP(hipStreamSynchronize(s));
     }
-    return nnz;
 }
 
 }  // namespace xrl

@@ -111,36 +111,46 @@ struct TfidfHandle {
     }
 };
 
-// The weighting tail both count forms share: q holds the term counts (idx, val) of the segments d_seg points at (h_seg: the same on the
-// host when the host counted; nullptr: an ensemble's row pointer is gathered on the device) -> per-base K5, the ensemble's norm, one synchronise.
-void tfidf_weight_counts(const TfidfHandle& H, Queries* q, DevBuf& d_seg, const std::vector<uint64_t>* h_seg, uint32_t rows, uint64_t nnz, int device, hipStream_t s) {
+// c.ptr holds the SEGMENT pointer of nb base vectorizers side by side -> the hstacked CSR's row pointer (every nb-th entry; h_seg: the
+// segment pointer on the host when the host counted, nullptr: gathered by a kernel on s).  Returns the segment pointer, which the work
+// enqueued on s may still read: the caller keeps it until s is synchronised.
+DevBuf seg_to_row_ptr(DevCsr& c, const std::vector<uint64_t>* h_seg, uint32_t nb, uint32_t rows, hipStream_t s) {
+    if (nb == 1) return {};
+    DevBuf seg = std::move(c.ptr);
+    if (h_seg) {
+        std::vector<uint64_t> row_ptr((size_t)rows + 1);
+        for (size_t r = 0; r <= rows; ++r) row_ptr[r] = (*h_seg)[r * nb];
+        c.ptr.upload(row_ptr);
+    } else {
+        c.ptr.reserve(((size_t)rows + 1) * 8);
+        launch_seg_to_row_ptr(seg.as<uint64_t>(), nb, rows, c.ptr.as<uint64_t>(), s);
+    }
+    return seg;
+}
+
+// The weighting tail both count forms share: q->own holds the term counts (idx, val, nnz) and, as ptr, their segment pointer (h_seg: as in
+// seg_to_row_ptr) -> per-base K5, the ensemble's norm, one synchronise.
+void tfidf_weight_counts(const TfidfHandle& H, Queries* q, const std::vector<uint64_t>* h_seg, uint32_t rows, int device, hipStream_t s) {
     const TfidfVectorizer& V = H.v;
     const uint32_t nb = (uint32_t)V.base.size();
+    DevCsr& c = q->own;
     DevBuf d_idf, d_err;
     d_idf.upload(H.idf_all);
     d_err.reserve(4); XRL_HIP(hipMemsetAsync(d_err.p, 0, 4, s));
     for (uint32_t b = 0; b < nb; ++b) {
         const TfidfBase& B = V.base[b];
-        launch_tfidf_weight(d_seg.as<uint64_t>(), q->idx.as<uint32_t>(), q->val.as<float>(), B.use_idf ? d_idf.as<float>() : nullptr, rows, V.nr_features,
-                            B.binary ? 1 : 0, B.sublinear_tf ? 1 : 0, B.norm_p, q->val.as<float>(), s, nb, b, d_err.as<uint32_t>());
+        launch_tfidf_weight(c.ptr.as<uint64_t>(), c.idx.as<uint32_t>(), c.val.as<float>(), B.use_idf ? d_idf.as<float>() : nullptr, rows, V.nr_features,
+                            B.binary ? 1 : 0, B.sublinear_tf ? 1 : 0, B.norm_p, c.val.as<float>(), s, nb, b, d_err.as<uint32_t>());
     }
     // whole rows: the hstacked CSR's row pointer; the ensemble's normalisation (Vectorizer::predict, tfidf.hpp:1405-1430)
-    if (nb == 1) q->ptr = std::move(d_seg);
-    else if (h_seg) {
-        std::vector<uint64_t> row_ptr((size_t)rows + 1);
-        for (size_t r = 0; r <= rows; ++r) row_ptr[r] = (*h_seg)[r * nb];
-        q->ptr.upload(row_ptr);
-    } else {
-        q->ptr.reserve(((size_t)rows + 1) * 8);
-        launch_seg_to_row_ptr(d_seg.as<uint64_t>(), nb, rows, q->ptr.as<uint64_t>(), s);
-    }
+    const DevBuf seg = seg_to_row_ptr(c, h_seg, nb, rows, s);
     if (nb > 1 || V.norm_p != V.base[0].norm_p)
-        launch_tfidf_weight(q->ptr.as<uint64_t>(), q->idx.as<uint32_t>(), q->val.as<float>(), nullptr, rows, V.nr_features, 0, 0, V.norm_p, q->val.as<float>(), s);
+        launch_tfidf_weight(c.ptr.as<uint64_t>(), c.idx.as<uint32_t>(), c.val.as<float>(), nullptr, rows, V.nr_features, 0, 0, V.norm_p, c.val.as<float>(), s);
     uint32_t err = 0;
     XRL_HIP(hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, s));
     XRL_HIP(hipStreamSynchronize(s));
     if (err) fail("tfidf: a feature id outside the model's feature range");
-    set_own_csr(*q, device, rows, V.nr_features, nnz);
+    set_own_csr(*q, device, rows, V.nr_features);
 }
 
 // texts -> term counts (host threads, into pinned staging) -> device -> weighting + normalisation (K5): a query handle that owns its three arrays
@@ -159,14 +169,15 @@ std::unique_ptr<Queries> tfidf_to_device(const TfidfHandle& H, const char* const
         nnz = n;
     });
     auto q = std::make_unique<Queries>();
-    DevBuf d_seg;
-    d_seg.upload(seg_ptr);
-    q->idx.reserve((size_t)nnz * 4); q->val.reserve((size_t)nnz * 4);
+    DevCsr& c = q->own;
+    c.nnz = nnz;
+    c.ptr.upload(seg_ptr);
+    c.idx.reserve((size_t)nnz * 4); c.val.reserve((size_t)nnz * 4);
     if (nnz) {
-        XRL_HIP(hipMemcpyAsync(q->idx.p, h_col, (size_t)nnz * 4, hipMemcpyHostToDevice, s));
-        XRL_HIP(hipMemcpyAsync(q->val.p, h_cnt, (size_t)nnz * 4, hipMemcpyHostToDevice, s));
+        XRL_HIP(hipMemcpyAsync(c.idx.p, h_col, (size_t)nnz * 4, hipMemcpyHostToDevice, s));
+        XRL_HIP(hipMemcpyAsync(c.val.p, h_cnt, (size_t)nnz * 4, hipMemcpyHostToDevice, s));
     }
-    tfidf_weight_counts(H, q.get(), d_seg, &seg_ptr, rows, nnz, device, s);
+    tfidf_weight_counts(H, q.get(), &seg_ptr, rows, device, s);
     return q;
 }
 
@@ -194,8 +205,8 @@ std::unique_ptr<Queries> tfidf_device_text_to_x(const TfidfHandle& H, const uint
     TokCounts C;
     tfidf_count_on_device(H, d_text, d_doc_off, d_doc_len, h_doc_len, nr_doc, nullptr, device, s, C);
     auto q = std::make_unique<Queries>();
-    q->idx = std::move(C.col); q->val = std::move(C.cnt);
-    tfidf_weight_counts(H, q.get(), C.seg_ptr, nullptr, (uint32_t)nr_doc, C.nnz, device, s);
+    q->own = std::move(C.csr);
+    tfidf_weight_counts(H, q.get(), nullptr, (uint32_t)nr_doc, device, s);
     return q;
 }
 }  // namespace
@@ -278,14 +289,15 @@ static void tfidf_predict_to_host(const TfidfHandle& H, const char* const* corpu
     // (stream = nullptr: tfidf_to_device takes the handle's pooled stream under its staging lock and holds the lock until it has synchronised)
     std::unique_ptr<Queries> q = tfidf_to_device(H, corpus, doc_lens, nr_doc, threads, g_device, nullptr);
     uint32_t* indices = nullptr; uint64_t* indptr = nullptr; float* data = nullptr;
-    pred_alloc(false, q->dev.rows, q->dev.cols, q->nnz, &indices, &indptr, &data);
-    if (!indptr || (q->nnz && (!indices || !data))) fail("allocator returned null");
+    const uint64_t nnz = q->dev.nnz;
+    pred_alloc(false, q->dev.rows, q->dev.cols, nnz, &indices, &indptr, &data);
+    if (!indptr || (nnz && (!indices || !data))) fail("allocator returned null");
     XRL_HIP(hipMemcpy(indptr, q->dev.row_ptr, ((size_t)q->dev.rows + 1) * 8, hipMemcpyDeviceToHost));
-    if (q->nnz) {
+    if (nnz) {
         // D2H into the pinned staging buffer (link speed), then host threads spread it over the allocator's fresh arrays: their first touch
         // in parallel, instead of the runtime's single-threaded pageable path
         std::lock_guard<std::mutex> stage_lock(H.stage.mu);
-        const size_t nb4 = (size_t)q->nnz * 4;
+        const size_t nb4 = (size_t)nnz * 4;
         char* st = static_cast<char*>(H.stage.need(2 * nb4));
         XRL_HIP(hipMemcpy(st, q->dev.col_idx, nb4, hipMemcpyDeviceToHost));
         XRL_HIP(hipMemcpy(st + nb4, q->dev.val, nb4, hipMemcpyDeviceToHost));
@@ -372,14 +384,10 @@ void* xrl_tfidf_counts_device(void* vectorizer, void* model, const uint8_t* d_te
         tfidf_count_on_device(H, d_text, d_doc_off, d_doc_len, nullptr, nr_doc, d_status, m.device, s, C);
         const uint32_t nb = (uint32_t)H.v.base.size(), rows = (uint32_t)nr_doc;
         auto q = std::make_unique<Queries>();
-        q->idx = std::move(C.col); q->val = std::move(C.cnt);
-        if (nb == 1) q->ptr = std::move(C.seg_ptr);
-        else {
-            q->ptr.reserve(((size_t)rows + 1) * 8);
-            launch_seg_to_row_ptr(C.seg_ptr.as<uint64_t>(), nb, rows, q->ptr.as<uint64_t>(), s);
-            XRL_HIP(hipStreamSynchronize(s));                    // (C.seg_ptr goes with this scope)
-        }
-        set_own_csr(*q, m.device, rows, H.v.nr_features, C.nnz);
+        q->own = std::move(C.csr);
+        const DevBuf seg = seg_to_row_ptr(q->own, nullptr, nb, rows, s);
+        if (nb > 1) XRL_HIP(hipStreamSynchronize(s));            // (the segment pointer goes with this scope)
+        set_own_csr(*q, m.device, rows, H.v.nr_features);
         return q.release();
     });
 }

@@ -31,8 +31,7 @@ XRL_HD bool tok_segment_is_big(int tok_type, int max_length, int min_ngram, int 
 }
 
 struct TokCounts {
-    DevBuf seg_ptr, col, cnt;                        // u64 [nr_doc * nb + 1], u32 [nnz], f32 [nnz]
-    uint64_t nnz = 0;
+    DevCsr csr;                                      // ptr: the SEGMENT pointer [nr_doc * nb + 1]; idx / val: feature ids and counts
     uint64_t first_bad[2] = {~0ull, ~0ull};          // the lowest document with status 1 / status 2 (~0: none)
     uint64_t lds_segments = 0, global_segments = 0, batches = 0;
 };

@@ -15,22 +15,25 @@
 //                                 sentinel and writes (segment << 32 | id) on a hit
 //   global form, per batch: rocPRIM radix sort of the keys, run-length encode, k9_big_runs scatters the runs to the same scratch
 //   k9_mask_bad      documents with a status keep no entry in any base
-//   exclusive scan of the segment lengths (rocPRIM), k9_compact copies the runs to their final place
+//   exclusive scan of the segment lengths (rocPRIM), the shared row copy (xrl_devprim.h) moves the runs to their final place
 //
 // No kernel reads a document byte at or past doc + len, and no lane writes outside the bound its segment was given (each index is below
 // tft::token_bound / occurrence_bound of the document's length, which size the arrays).
 #include "xrl_tokenize.h"
+#include "xrl_device.h"
+#include "xrl_devprim.h"
 
 #include <algorithm>
 #include <cstdlib>
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_run_length_encode.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 namespace xrl {
 
 namespace {
+
+constexpr const char* kWhat = "tfidf (device tokenizer)";   // the family in a "grid too large" message
 
 struct K9Args {
     tft::TokenView tv; tft::NgramView gv;
@@ -46,7 +49,6 @@ struct K9Args {
     int32_t* g_tok; const uint64_t* tok_base; uint64_t* keys; const uint64_t* key_base;   // global form
 };
 
-__device__ __forceinline__ uint32_t below(unsigned long long m, uint32_t lane) { return (uint32_t)__popcll(m & ((1ull << lane) - 1ull)); }
 __device__ __forceinline__ bool is_cont(uint8_t c) { return (c & 0xC0u) == 0x80u; }
 
 // feature id + 1 of the n-gram at t (0: none), TfidfBase::count's rule
@@ -93,7 +95,7 @@ __global__ void __launch_bounds__(64) k9_count(K9Args a) {
             const unsigned long long starts = ~sp & ((sp << 1) | carry);
             carry = sp >> 63;
             if ((starts >> lane) & 1ull) {
-                const uint64_t ord = count + below(starts, lane);
+                const uint64_t ord = count + lanes_below(starts);
                 if (ord < tb) {
                     const unsigned long long m = sp >> lane;
                     uint64_t end;
@@ -119,7 +121,7 @@ __global__ void __launch_bounds__(64) k9_count(K9Args a) {
             const unsigned long long starts = __ballot(start);
             uint32_t viol = 0;
             if (start) {
-                const uint64_t ord = count + below(starts, lane);
+                const uint64_t ord = count + lanes_below(starts);
                 if (ord < tb) {                            // (positions past the max_length cut are not checked; nor does the host)
                     const uint64_t cs = c >= 0xF0 ? 4 : c >= 0xE0 ? 3 : c >= 0xC0 ? 2 : 1;
                     const uint64_t n = cs < len - pos ? cs : len - pos;
@@ -162,7 +164,7 @@ __global__ void __launch_bounds__(64) k9_count(K9Args a) {
             if (BIG) { if (id1) a.keys[slot + i] = key_hi | (uint64_t)(id1 - 1u); }
             else {
                 const unsigned long long m = __ballot(id1 != 0);
-                if (id1) s_occ[nf + below(m, lane)] = id1 - 1u;
+                if (id1) s_occ[nf + lanes_below(m)] = id1 - 1u;
                 nf += (uint32_t)__popcll(m);
             }
         }
@@ -191,7 +193,7 @@ __global__ void __launch_bounds__(64) k9_count(K9Args a) {
         const uint32_t i = i0 + lane;
         const bool head = i < nf && (i == 0 || s_occ[i] != s_occ[i - 1]);
         const unsigned long long m = __ballot(head);
-        if (head) heads[nr + below(m, lane)] = i;
+        if (head) heads[nr + lanes_below(m)] = i;
         nr += (uint32_t)__popcll(m);
     }
     __syncthreads();
@@ -209,12 +211,6 @@ __global__ void __launch_bounds__(256) k9_fill(uint64_t* p, uint64_t n, uint64_t
     if (i < n) p[i] = v;
 }
 
-__device__ __forceinline__ uint32_t lower_bound_u64(const uint64_t* a, uint32_t n, uint64_t key) {
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (a[mid] < key) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-
 // the runs of the sorted keys of the global form -> the batch's run scratch and the lengths of their segments
 __global__ void __launch_bounds__(256)
 k9_big_runs(const uint64_t* __restrict__ uniq, const uint32_t* __restrict__ runlen, const uint32_t* __restrict__ n_runs, uint32_t n_big,
@@ -226,27 +222,17 @@ k9_big_runs(const uint64_t* __restrict__ uniq, const uint32_t* __restrict__ runl
     const uint64_t u = uniq[r];
     const uint64_t sb = u >> 32;
     if (sb >= n_big) return;                               // the sentinel's run
-    const uint32_t first = lower_bound_u64(uniq, nr, sb << 32);
+    const uint32_t first = lower_bound(uniq, nr, sb << 32);
     const uint64_t gseg = big_seg[sb];
     const uint64_t at = seg_base[gseg - seg0] + ((uint32_t)r - first);
     run_col[at] = (uint32_t)u + col_off[gseg % nb];
     run_cnt[at] = (float)min(runlen[r], tft::kCountCap);
-    if ((uint32_t)r == first) seg_cnt[gseg] = lower_bound_u64(uniq, nr, (sb + 1) << 32) - first;
+    if ((uint32_t)r == first) seg_cnt[gseg] = lower_bound(uniq, nr, (sb + 1) << 32) - first;
 }
 
 __global__ void __launch_bounds__(256) k9_mask_bad(const uint32_t* __restrict__ status, uint64_t seg0, uint64_t n_seg, uint32_t nb, uint64_t* __restrict__ seg_cnt) {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (i < n_seg && status[(seg0 + i) / nb] != 0u) seg_cnt[seg0 + i] = 0;
-}
-
-// one wavefront per segment: its runs from the scratch to their place in the batch's arrays
-__global__ void __launch_bounds__(256)
-k9_compact(const uint64_t* __restrict__ seg_base, const uint64_t* __restrict__ local_ptr, uint64_t n_seg, const uint32_t* __restrict__ run_col,
-           const float* __restrict__ run_cnt, uint32_t* __restrict__ col, float* __restrict__ cnt) {
-    const uint64_t sgm = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (sgm >= n_seg) return;
-    const uint64_t src = seg_base[sgm], dst = local_ptr[sgm], n = local_ptr[sgm + 1] - dst;
-    for (uint64_t i = threadIdx.x & 63u; i < n; i += 64u) { col[dst + i] = run_col[src + i]; cnt[dst + i] = run_cnt[src + i]; }
 }
 
 __global__ void __launch_bounds__(256) k9_first_bad(const uint32_t* __restrict__ status, uint64_t n, unsigned long long* __restrict__ first) {
@@ -261,23 +247,10 @@ __global__ void __launch_bounds__(256) k9_row_ptr(const uint64_t* __restrict__ s
     if (r <= rows) row_ptr[r] = seg_ptr[r * nb];
 }
 
-uint32_t blocks_of(uint64_t n, uint32_t per) {
-    const uint64_t b = (n + per - 1) / per;
-    if (b > 0x7FFFFFFFull) fail("tfidf (device tokenizer): grid too large");
-    return (uint32_t)b;
-}
-
-void scan_u64(DevBuf& tmp, const uint64_t* in, uint64_t* out, size_t n, hipStream_t s) {
-    size_t bytes = 0;
-    XRL_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s));
-    tmp.reserve(bytes);
-    XRL_HIP(rocprim::exclusive_scan(tmp.p, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s));
-}
-
 }  // namespace
 
 void launch_seg_to_row_ptr(const uint64_t* seg_ptr, uint32_t nb, uint32_t rows, uint64_t* row_ptr, hipStream_t s) {
-    hipLaunchKernelGGL(k9_row_ptr, dim3(blocks_of((uint64_t)rows + 1, 256)), dim3(256), 0, s, seg_ptr, nb, rows, row_ptr);
+    hipLaunchKernelGGL(k9_row_ptr, dim3(blocks_of((uint64_t)rows + 1, 256, kWhat)), dim3(256), 0, s, seg_ptr, nb, rows, row_ptr);
     XRL_LAUNCH_CHECK();
 }
 
@@ -299,14 +272,12 @@ void tokenize_count_device(const std::vector<TokBase>& bases, const uint8_t* d_t
     XRL_HIP(hipMemsetAsync(d_seg_cnt.p, 0, (n_seg + 1) * 8, s));
     if (nr_doc) XRL_HIP(hipMemsetAsync(d_status, 0, nr_doc * 4, s));
     { std::vector<uint32_t> co(nb); for (uint32_t b = 0; b < nb; ++b) co[b] = bases[b].col_off; d_col_off.upload(co); }
-    d_words.reserve(32);                                   // [0, 16) first_bad, [16, 24) a batch's entries, [24, 28) the runs of its global form
+    d_words.reserve(32);                                   // [0, 16) first_bad, [24, 28) the runs of a batch's global form
     XRL_HIP(hipMemsetAsync(d_words.p, 0xFF, 16, s));
-    out.seg_ptr.reserve((n_seg + 1) * 8);
 
     uint64_t budget = kTokScratchEntries;
     if (const char* e = std::getenv("XRL_TOK_SCRATCH_ENTRIES")) budget = std::strtoull(e, nullptr, 10);   // (tests: a small budget cuts a small corpus into batches)
-    struct Piece { DevBuf col, cnt; uint64_t n = 0; };
-    std::vector<Piece> pieces;
+    std::vector<DevCsr> pieces;                            // a batch's (idx, val, nnz); no ptr
     DevBuf d_seg_base, d_local_ptr, d_run_col, d_run_cnt, d_big_doc, d_big_seg, d_tok_base, d_key_base, d_tok, d_keys, d_keys2, d_uniq, d_runlen;
     std::vector<uint64_t> seg_base, tok_base, key_base, big_seg;
     std::vector<uint32_t> big_doc;
@@ -361,7 +332,7 @@ void tokenize_count_device(const std::vector<TokBase>& bases, const uint8_t* d_t
             d_tok.reserve(tok_base.back() * 4); d_keys.reserve(n_keys * 8); d_keys2.reserve(n_keys * 8);
             a.big_doc = d_big_doc.as<uint32_t>(); a.g_tok = d_tok.as<int32_t>(); a.tok_base = d_tok_base.as<uint64_t>();
             a.keys = d_keys.as<uint64_t>(); a.key_base = d_key_base.as<uint64_t>();
-            if (n_keys) { hipLaunchKernelGGL(k9_fill, dim3(blocks_of(n_keys, 256)), dim3(256), 0, s, a.keys, n_keys, n_big << 32); XRL_LAUNCH_CHECK(); }
+            if (n_keys) { hipLaunchKernelGGL(k9_fill, dim3(blocks_of(n_keys, 256, kWhat)), dim3(256), 0, s, a.keys, n_keys, n_big << 32); XRL_LAUNCH_CHECK(); }
         }
         for (uint32_t b = 0; b < nb; ++b) {
             const TokBase& B = bases[b];
@@ -374,58 +345,52 @@ void tokenize_count_device(const std::vector<TokBase>& bases, const uint8_t* d_t
             // ---- global form: sort the (segment, id) keys (the sentinel n_big << 32 sorts last), run lengths, scatter
             unsigned end_bit = 33;
             while (end_bit < 64 && (n_big >> (end_bit - 32)) != 0) ++end_bit;
-            size_t bytes = 0;
-            XRL_HIP(rocprim::radix_sort_keys(nullptr, bytes, d_keys.as<uint64_t>(), d_keys2.as<uint64_t>(), (unsigned int)n_keys, 0u, end_bit, s));
-            d_tmp.reserve(bytes);
-            XRL_HIP(rocprim::radix_sort_keys(d_tmp.p, bytes, d_keys.as<uint64_t>(), d_keys2.as<uint64_t>(), (unsigned int)n_keys, 0u, end_bit, s));
+            with_rocprim_tmp(d_tmp, [&](void* t, size_t& bytes) {
+                return rocprim::radix_sort_keys(t, bytes, d_keys.as<uint64_t>(), d_keys2.as<uint64_t>(), (unsigned int)n_keys, 0u, end_bit, s);
+            });
             d_uniq.reserve(n_keys * 8); d_runlen.reserve(n_keys * 4);
             uint32_t* const d_n_runs = d_words.as<uint32_t>() + 6;
-            bytes = 0;
-            XRL_HIP(rocprim::run_length_encode(nullptr, bytes, d_keys2.as<uint64_t>(), (unsigned int)n_keys, d_uniq.as<uint64_t>(), d_runlen.as<uint32_t>(), d_n_runs, s));
-            d_tmp.reserve(bytes);
-            XRL_HIP(rocprim::run_length_encode(d_tmp.p, bytes, d_keys2.as<uint64_t>(), (unsigned int)n_keys, d_uniq.as<uint64_t>(), d_runlen.as<uint32_t>(), d_n_runs, s));
-            hipLaunchKernelGGL(k9_big_runs, dim3(blocks_of(n_keys, 256)), dim3(256), 0, s, d_uniq.as<uint64_t>(), d_runlen.as<uint32_t>(), d_n_runs, (uint32_t)n_big,
+            with_rocprim_tmp(d_tmp, [&](void* t, size_t& bytes) {
+                return rocprim::run_length_encode(t, bytes, d_keys2.as<uint64_t>(), (unsigned int)n_keys, d_uniq.as<uint64_t>(), d_runlen.as<uint32_t>(), d_n_runs, s);
+            });
+            hipLaunchKernelGGL(k9_big_runs, dim3(blocks_of(n_keys, 256, kWhat)), dim3(256), 0, s, d_uniq.as<uint64_t>(), d_runlen.as<uint32_t>(), d_n_runs, (uint32_t)n_big,
                                d_big_seg.as<uint64_t>(), seg0, d_seg_base.as<uint64_t>(), d_col_off.as<uint32_t>(), nb, a.run_col, a.run_cnt, a.seg_cnt);
             XRL_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(k9_mask_bad, dim3(blocks_of(nsb, 256)), dim3(256), 0, s, d_status, seg0, nsb, nb, a.seg_cnt);
+        hipLaunchKernelGGL(k9_mask_bad, dim3(blocks_of(nsb, 256, kWhat)), dim3(256), 0, s, d_status, seg0, nsb, nb, a.seg_cnt);
         XRL_LAUNCH_CHECK();
         // ---- the batch's entries: lengths -> offsets inside the batch (the count after the batch's last is still zero), then the copy
         d_local_ptr.reserve((nsb + 1) * 8);
-        scan_u64(d_tmp, a.seg_cnt + seg0, d_local_ptr.as<uint64_t>(), (size_t)nsb + 1, s);
-        Piece pc;
-        XRL_HIP(hipMemcpyAsync(&pc.n, d_local_ptr.as<uint64_t>() + nsb, 8, hipMemcpyDeviceToHost, s));
-        XRL_HIP(hipStreamSynchronize(s));
-        pc.col.reserve(pc.n * 4); pc.cnt.reserve(pc.n * 4);
-        if (pc.n) {
-            hipLaunchKernelGGL(k9_compact, dim3(blocks_of(nsb, 4)), dim3(256), 0, s, d_seg_base.as<uint64_t>(), d_local_ptr.as<uint64_t>(), nsb, a.run_col, a.run_cnt,
-                               pc.col.as<uint32_t>(), pc.cnt.as<float>());
-            XRL_LAUNCH_CHECK();
-        }
+        DevCsr pc;
+        pc.nnz = scan_total(d_tmp, a.seg_cnt + seg0, d_local_ptr.as<uint64_t>(), nsb, s);
+        pc.idx.reserve(pc.nnz * 4); pc.val.reserve(pc.nnz * 4);
+        if (pc.nnz) launch_copy_rows(d_local_ptr.as<uint64_t>(), nsb, d_seg_base.as<uint64_t>(), 0, a.run_col, a.run_cnt, pc.idx.as<uint32_t>(), pc.val.as<float>(), kWhat, s);
         pieces.push_back(std::move(pc));
         d0 = d1;
         if (d0 < nr_doc) XRL_HIP(hipStreamSynchronize(s));   // the next batch's uploads reuse the buffers this batch's kernels read
     }
 
-    // ---- the whole call: segment pointer, the lowest bad documents, the pieces side by side
-    scan_u64(d_tmp, d_seg_cnt.as<uint64_t>(), out.seg_ptr.as<uint64_t>(), (size_t)n_seg + 1, s);
-    if (nr_doc) {
-        hipLaunchKernelGGL(k9_first_bad, dim3(blocks_of(nr_doc, 256)), dim3(256), 0, s, d_status, nr_doc, d_words.as<unsigned long long>());
-        XRL_LAUNCH_CHECK();
-    }
-    out.nnz = 0;
-    for (const Piece& pc : pieces) out.nnz += pc.n;
-    if (pieces.size() == 1) { out.col = std::move(pieces[0].col); out.cnt = std::move(pieces[0].cnt); }
+    // ---- the whole call: the pieces side by side (one piece: it is the result), segment pointer, the lowest bad documents
+    DevCsr& C = out.csr;
+    if (pieces.size() == 1) C = std::move(pieces[0]);
     else {
-        out.col.reserve(out.nnz * 4); out.cnt.reserve(out.nnz * 4);
+        C.nnz = 0;
+        for (const DevCsr& pc : pieces) C.nnz += pc.nnz;
+        C.idx.reserve(C.nnz * 4); C.val.reserve(C.nnz * 4);
         uint64_t at = 0;
-        for (const Piece& pc : pieces) {
-            if (pc.n) {
-                XRL_HIP(hipMemcpyAsync(out.col.as<uint32_t>() + at, pc.col.p, pc.n * 4, hipMemcpyDeviceToDevice, s));
-                XRL_HIP(hipMemcpyAsync(out.cnt.as<float>() + at, pc.cnt.p, pc.n * 4, hipMemcpyDeviceToDevice, s));
+        for (const DevCsr& pc : pieces) {
+            if (pc.nnz) {
+                XRL_HIP(hipMemcpyAsync(C.idx.as<uint32_t>() + at, pc.idx.p, pc.nnz * 4, hipMemcpyDeviceToDevice, s));
+                XRL_HIP(hipMemcpyAsync(C.val.as<float>() + at, pc.val.p, pc.nnz * 4, hipMemcpyDeviceToDevice, s));
             }
-            at += pc.n;
+            at += pc.nnz;
         }
+    }
+    C.ptr.reserve((n_seg + 1) * 8);
+    exclusive_scan(d_tmp, d_seg_cnt.as<uint64_t>(), C.ptr.as<uint64_t>(), (size_t)n_seg + 1, s);
+    if (nr_doc) {
+        hipLaunchKernelGGL(k9_first_bad, dim3(blocks_of(nr_doc, 256, kWhat)), dim3(256), 0, s, d_status, nr_doc, d_words.as<unsigned long long>());
+        XRL_LAUNCH_CHECK();
     }
     XRL_HIP(hipMemcpyAsync(out.first_bad, d_words.p, 16, hipMemcpyDeviceToHost, s));
     XRL_HIP(hipStreamSynchronize(s));

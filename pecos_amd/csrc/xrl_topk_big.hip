@@ -8,6 +8,7 @@
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include "xrl_device.h"
+#include "xrl_devprim.h"
 #include "xrl_kernels.h"
 
 namespace xrl {
@@ -42,8 +43,7 @@ __global__ void __launch_bounds__(256) k2big_emit(EmitArgs a) {
         const uint32_t pos = a.pos_sorted[q * a.cand_stride + i];
         uint32_t parent = 0, off = 0;
         if (!a.implicit_root) {
-            uint32_t lo = 0, hi = bcnt;                                 // last beam slot whose block starts at or before the position
-            while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (a.cand_off[q * a.beam_in + mid] <= pos) lo = mid; else hi = mid; }
+            const uint32_t lo = segment_of(a.cand_off + q * a.beam_in, bcnt, pos);   // last beam slot whose block starts at or before the position
             off = a.cand_off[q * a.beam_in + lo];
             parent = a.p_idx[q * a.p_stride + lo];
         }
@@ -62,27 +62,24 @@ void launch_k2_topk_big(const LayerDev& L, const LayerPlan& P, BeamDev prev, con
     const uint64_t total = (uint64_t)P.nrows * P.cand_stride;
     if (total > 0xFFFFFFF0ull) fail("k2: candidate buffer exceeds 2^32 floats; lower max_batch_rows");
     // (a rare path: scratch is allocated per call and released after the stream has drained)
-    uint32_t *keys = nullptr, *keys2 = nullptr, *vals = nullptr, *vals2 = nullptr, *offs = nullptr; void* tmp = nullptr;
-    auto release = [&] { for (void* p : {(void*)keys, (void*)keys2, (void*)vals, (void*)vals2, (void*)offs, tmp}) if (p) (void)hipFree(p); };
-    try {
-        XRL_HIP(hipMalloc(&keys, total * 4)); XRL_HIP(hipMalloc(&keys2, total * 4)); XRL_HIP(hipMalloc(&vals, total * 4)); XRL_HIP(hipMalloc(&vals2, total * 4));
-        XRL_HIP(hipMalloc(&offs, ((size_t)P.nrows + 1) * 4));
-        hipLaunchKernelGGL(k2big_keys, dim3((uint32_t)((total + 256) / 256)), dim3(256), 0, s, cand, ncand, P.nrows, P.cand_stride, keys, vals, offs);
-        XRL_HIP(hipGetLastError());
-        size_t tmp_bytes = 0;
-        XRL_HIP(rocprim::segmented_radix_sort_pairs(nullptr, tmp_bytes, keys, keys2, vals, vals2, (unsigned int)total, P.nrows, offs, offs + 1, 0, 32, s));
-        XRL_HIP(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16));
-        XRL_HIP(rocprim::segmented_radix_sort_pairs(tmp, tmp_bytes, keys, keys2, vals, vals2, (unsigned int)total, P.nrows, offs, offs + 1, 0, 32, s));
-        EmitArgs a;
-        a.chunk_col = L.chunk_col; a.perm_inv = L.perm_inv; a.p_idx = prev.idx; a.p_cnt = prev.cnt; a.p_stride = prev.stride;
-        a.cand_off = cand_off; a.ncand = ncand; a.cand = cand; a.pos_sorted = vals2;
-        a.out_idx = out_idx; a.out_val = out_val; a.out_cnt = out_cnt;
-        a.nrows = P.nrows; a.beam_in = P.beam_in; a.cand_stride = P.cand_stride; a.k = P.k; a.out_stride = out_stride; a.implicit_root = P.implicit_root;
-        hipLaunchKernelGGL(k2big_emit, dim3(P.nrows), dim3(256), 0, s, a);
-        XRL_HIP(hipGetLastError());
-        XRL_HIP(hipStreamSynchronize(s));
-    } catch (...) { release(); throw; }
-    release();
+    DevBuf keys, keys2, vals, vals2, offs, tmp;
+    keys.reserve(total * 4); keys2.reserve(total * 4); vals.reserve(total * 4); vals2.reserve(total * 4);
+    offs.reserve(((size_t)P.nrows + 1) * 4);
+    uint32_t* const d_offs = offs.as<uint32_t>();
+    hipLaunchKernelGGL(k2big_keys, dim3((uint32_t)((total + 256) / 256)), dim3(256), 0, s, cand, ncand, P.nrows, P.cand_stride, keys.as<uint32_t>(), vals.as<uint32_t>(), d_offs);
+    XRL_LAUNCH_CHECK();
+    with_rocprim_tmp(tmp, [&](void* t, size_t& bytes) {
+        return rocprim::segmented_radix_sort_pairs(t, bytes, keys.as<uint32_t>(), keys2.as<uint32_t>(), vals.as<uint32_t>(), vals2.as<uint32_t>(), (unsigned int)total,
+                                                   P.nrows, d_offs, d_offs + 1, 0, 32, s);
+    });
+    EmitArgs a;
+    a.chunk_col = L.chunk_col; a.perm_inv = L.perm_inv; a.p_idx = prev.idx; a.p_cnt = prev.cnt; a.p_stride = prev.stride;
+    a.cand_off = cand_off; a.ncand = ncand; a.cand = cand; a.pos_sorted = vals2.as<uint32_t>();
+    a.out_idx = out_idx; a.out_val = out_val; a.out_cnt = out_cnt;
+    a.nrows = P.nrows; a.beam_in = P.beam_in; a.cand_stride = P.cand_stride; a.k = P.k; a.out_stride = out_stride; a.implicit_root = P.implicit_root;
+    hipLaunchKernelGGL(k2big_emit, dim3(P.nrows), dim3(256), 0, s, a);
+    XRL_LAUNCH_CHECK();
+    XRL_HIP(hipStreamSynchronize(s));
 }
 
 }  // namespace xrl

@@ -236,6 +236,40 @@ def test_upload_download_and_chained_products(ref, clib):
     assert R.same(to_host(Z2.to_torch()), R.logical(R.rule(AB, Cm, True, True)))
 
 
+# ------------------------------------------------------- the shared scan, row copy and handle bodies at their smallest shapes
+def test_tiny_result_with_an_empty_and_an_overfull_row():
+    import torch
+    from pecos_amd.features import DeviceMatrix
+    idx = np.arange(12, dtype=np.int32).reshape(3, 4)
+    val = (np.arange(12, dtype=np.float32) + 0.5).reshape(3, 4)
+    t = [torch.from_numpy(a).cuda() for a in (idx, val, np.array([0, 4, 9], dtype=np.int32))]
+    for counts, ptr in ((t[2], [0, 0, 4, 8]), (None, [0, 4, 8, 12])):     # the 9 is read as 4
+        back = DeviceMatrix.from_result((t[0], t[1], counts), n_cols=12).download()
+        first = 12 - ptr[-1]
+        assert back.shape == (3, 12) and np.array_equal(back.indptr, ptr)
+        assert np.array_equal(back.indices, idx.ravel()[first:]) and np.array_equal(R.bits(back.data), R.bits(val.ravel()[first:]))
+
+
+def test_upload_download_of_matrices_without_rows_columns_or_entries():
+    from pecos_amd.features import DeviceMatrix
+    zeros = smat.csr_matrix((2, 3), dtype=np.float32)                     # an explicit zero, an empty row
+    zeros.indptr, zeros.indices, zeros.data = np.array([0, 2, 2]), np.array([2, 0]), np.array([0.0, -0.0], dtype=np.float32)
+    mats = [smat.csr_matrix((0, 5), dtype=np.float32), smat.csr_matrix((5, 0), dtype=np.float32), smat.csr_matrix((3, 3), dtype=np.float32), zeros]
+    held = [DeviceMatrix.upload(M) for M in mats]                         # no rows next to no entries: all alive at once
+    for M, h in zip(mats, held):
+        back = h.download()
+        assert back.shape == M.shape == h.shape and h.info["nnz"] == len(M.data)
+        assert np.array_equal(back.indptr, M.indptr) and np.array_equal(back.indices, M.indices) and np.array_equal(R.bits(back.data), R.bits(M.data))
+
+
+def test_left_rows_of_1_64_and_65_entries():
+    rng = np.random.default_rng(65)
+    B = R.rand_csr(rng, 65, 30, 6, sort=True)
+    A = R.from_rows([list(zip(rng.permutation(65)[:n].tolist(), rng.standard_normal(n).astype(np.float32).tolist())) for n in (1, 64, 65)], 65)
+    for si in (True, False):
+        assert R.same(device_product(A, B, False, si), R.logical(R.rule(A, B, False, si))), si
+
+
 # --------------------------------------------------------------------------------------------------- end to end on a golden model
 @pytest.fixture(scope="module")
 def eurlex():
