@@ -434,6 +434,58 @@ void xrl_smat_free(void* smat);
 void* xrl_sparse_matmul_device(void* A, void* B, int eliminate_zeros, int sorted_indices, void* hip_stream);
 int xrl_debug_spgemm_forms(uint64_t* out, uint32_t n);
 
+/* ------------------------------------------------------------------------------------------
+ * Label clustering on the device (K11, csrc/xrl_cluster.hip): the reference's balanced hierarchical 2-means (libpecos.cpp:357-370 ->
+ * Tree::run_clustering, pecos/core/utils/clustering.hpp:403-503), which turns the rows of a feature matrix (label embeddings) into leaf
+ * codes 0 .. 2^depth - 1.  The answer is the reference's at threads = 1; `threads` is accepted and ignored.
+ * The rule.  Elements 0 .. L-1 in an array `elements`; an mt19937 seeded with `seed` draws one 32-bit seed per node id 0 .. 2^(depth+1)-1;
+ * node 1 owns [0, L), the children of [s, e) own [s, m) and [m, e), m = (s + e) >> 1.  Level d = nodes 2^d .. 2^(d+1)-1, each with its
+ * own mt19937 from its seed:
+ *   1. the level's sample rate (clustering.hpp:156-167, float arithmetic); below 1 the node shuffles its range (std::shuffle; the
+ *      shuffle stays) and works on its first size_t(rate * size) elements, split at their midpoint;
+ *   2. iterations k = 0 .. kmeans_max_iter-1; every product and every addition is rounded, no FMA.  k = 0: r = randint(0, n-1),
+ *      l = (r + randint(1, n-1)) % n over the n working elements, centre = x_r - x_l per feature.  k > 0, KMEANS (partition_algo 0):
+ *      one accumulator per feature from +0, walked over the right half's elements in stored order (ascending id), each row in stored
+ *      order, c[f] = c[f] + float(1.0 / |right|) * v, then over the left half with float(-1.0 / |left|).  SKMEANS (5): c1 sums the right
+ *      half, c2 the left half; each is scaled by 1.0 / sqrt((double)||c||^2) when ||c||^2 > 0 (the double product rounded to float), then
+ *      c1 - c2.  ||c||^2 is an fp32 chain of c[f] * c[f], in ascending f while the level is dense, and in the order of first touch during
+ *      the accumulation once nnz / (nodes of the level * cols) < 1 has held at this or an earlier level.  score[e] = the fp32 chain over
+ *      row e's stored entries of c[f] * v from +0.  The working range is sorted by (score ascending, id ascending), -0 == +0, then each
+ *      half by id; the node stops when its first half is what it was before the sort;
+ *   3. the node's children are the midpoint split of its whole range; a level that sampled scores and sorts the whole range once more
+ *      with the last centre.
+ * label_codes[elements[i]] = the leaf that owns position i.  Non-finite feature values are not pinned.
+ * Refused before a GPU is required (messages start with the function's name): null pointers; 2^depth > rows; depth > 30; a sampled
+ * node of fewer than 2 elements; the reference's invalid rates (0 < min <= max <= 1, 0 <= warmup_ratio <= 1); a partition_algo other
+ * than 0 or 5.  Refused by a check kernel: a row whose column ids are not strictly ascending, or an id >= cols.  Scratch is one level
+ * at a time; when it does not fit the message names the bytes needed.
+ *   c_run_clustering_csr_f32 / _drm_f32   the reference's signatures: upload, run, copy label_codes [rows] back.  The dense form is the
+ *                                same computation on rows that store every entry, zeros included, always with the dense norm order.
+ *   xrl_run_clustering_device    the feature matrix is an xrl_smat_* CSR handle (e.g. a product of xrl_sparse_matmul_device); d_codes [rows]
+ *                                and d_scores (NULL or [depth * rows]: the reference's `scores` array as it stands after each level) are
+ *                                in HBM on the handle's device.  Runs on hip_stream and synchronises it every iteration.  0, or -1 +
+ *                                xrl_last_error.
+ *   xrl_debug_cluster_plan       FOR TESTS ONLY, needs no GPU: the draws.  node_seed [2^(depth+1)]; level_info [2 * depth] = {sampled,
+ *                                first-touch norm order} per level; work [4 * 2^depth], by node id = {range start, working end, position
+ *                                of r, position of l}; perm [depth * rows] = each level's shuffle as source positions.  Each may be NULL.
+ *   xrl_debug_cluster_forms      FOR TESTS ONLY: of the last clustering of this process, out[0..n) <- {runs served one per lane, runs
+ *                                served by a wavefront (64 entries and more), segmented sorts issued, level at which the norm order
+ *                                switched (~0: never, or KMEANS), depth, iterations run at level 0, 1, ...}; runs count once per level */
+typedef struct {            /* clustering.hpp:35-72  ClusteringParam */
+    size_t partition_algo;
+    int seed;
+    size_t kmeans_max_iter;
+    int threads;
+    float max_sample_rate, min_sample_rate, warmup_ratio;
+} ClusteringParam;
+void c_run_clustering_csr_f32(const ScipyCsrF32* X, size_t depth, ClusteringParam* param, uint32_t* label_codes);
+void c_run_clustering_drm_f32(const ScipyDrmF32* X, size_t depth, ClusteringParam* param, uint32_t* label_codes);
+int xrl_run_clustering_device(void* smat, uint64_t depth, const ClusteringParam* param, uint32_t* d_codes, float* d_scores /* NULL or [depth * rows] */,
+                              void* hip_stream);
+int xrl_debug_cluster_plan(uint64_t rows, uint64_t cols, uint64_t nnz, uint64_t depth, const ClusteringParam* param, uint32_t* node_seed, uint32_t* level_info,
+                           uint32_t* work, uint32_t* perm);
+int xrl_debug_cluster_forms(uint64_t* out, uint32_t n);
+
 /* predict_on_selected_outputs on the device (K7 + K4): score a given set of labels per query row through the tree, with labels, plan and
  * scores resident in HBM.  The labels arrive in the fixed-stride form xrl_predict_device writes and xrl_ensemble_device reads: row r is
  * d_sel_idx[r*sel_stride ..], d_sel_cnt[r] entries long (NULL = sel_stride each; a count above the stride is read as the stride), in any

@@ -30,6 +30,17 @@ XLINEAR_INFERENCE_MODEL_TYPES = {"CSC": 0, "HASH_CHUNKED": 1, "BINARY_SEARCH_CHU
 _LIB_PATH = os.environ.get("PECOS_XRL_AMD_SO") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libxrl_amd.so")
 
 
+class ClusteringParam(ctypes.Structure):
+    """struct ClusteringParam of include/xrl_abi.h (clustering.hpp:35-72); built from any object with these attributes, or from keywords."""
+    _fields_ = [("partition_algo", c_uint64), ("seed", c_int), ("kmeans_max_iter", c_uint64), ("threads", c_int),
+                ("max_sample_rate", c_float), ("min_sample_rate", c_float), ("warmup_ratio", c_float)]
+
+    def __init__(self, params=None, **kw):
+        super().__init__()
+        for name, _ in self._fields_:
+            setattr(self, name, kw[name] if name in kw else getattr(params, name))
+
+
 class _MatView(ctypes.Structure):
     """Common behaviour of the zero-copy matrix views (the buffers are kept alive in py_buf)."""
 
@@ -223,6 +234,9 @@ class corelib(object):
         "xrl_smat_free": (None, [c_void_p]),
         "xrl_sparse_matmul_device": (c_void_p, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
         "xrl_debug_spgemm_forms": (c_int, [POINTER(c_uint64), c_uint32]),
+        "xrl_run_clustering_device": (c_int, [c_void_p, c_uint64, POINTER(ClusteringParam), c_void_p, c_void_p, c_void_p]),
+        "xrl_debug_cluster_plan": (c_int, [c_uint64, c_uint64, c_uint64, c_uint64, POINTER(ClusteringParam), c_void_p, c_void_p, c_void_p, c_void_p]),
+        "xrl_debug_cluster_forms": (c_int, [POINTER(c_uint64), c_uint32]),
         "xrl_inspect_model": (c_int, [c_char_p, POINTER(c_uint64), c_uint32]),
         "xrl_model_create": (c_void_p, [c_uint32, c_void_p, c_void_p, POINTER(c_float), POINTER(c_uint32), POINTER(c_char_p)]),
         "xrl_queries_upload_csr": (c_void_p, [c_void_p, POINTER(ScipyCsrF32)]),
@@ -278,9 +292,15 @@ class corelib(object):
         "xrl_single_layer_cache_stats": (None, [POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     }
 
+    # ... and the two the header declares under the reference's own prefix (base.py:1591-1606 link_clustering)
+    CLUSTERING_SIGNATURES = {
+        "c_run_clustering_csr_f32": (None, [POINTER(ScipyCsrF32), c_uint64, POINTER(ClusteringParam), POINTER(c_uint32)]),
+        "c_run_clustering_drm_f32": (None, [POINTER(ScipyDrmF32), c_uint64, POINTER(ClusteringParam), POINTER(c_uint32)]),
+    }
+
     @classmethod
     def _link(cls, lib):
-        for name, (res, args) in cls.SIGNATURES.items():
+        for name, (res, args) in list(cls.SIGNATURES.items()) + list(cls.CLUSTERING_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
 
@@ -554,6 +574,49 @@ class corelib(object):
         self.clib_float32.xrl_debug_spgemm_forms(out, 5)
         self._check()
         return dict(zip(("cap", "lds_rows", "big_rows", "batches", "calls"), (int(v) for v in out)))
+
+    # ------------------------------------------------------------------ label clustering (K11)
+    def run_clustering(self, py_feat_mat, train_params, codes=None):
+        """Hierarchical 2-means of a label embedding on the device, with the reference's dispatch and return (base.py:1608-1646):
+        ``py_feat_mat`` is a ScipyCsrF32 or ScipyDrmF32 view, ``train_params`` carries ``depth`` and the ClusteringParam fields;
+        returns the leaf codes (``codes`` when it fits, else a new uint32 array).  The answer is the reference's at threads = 1."""
+        clib = self.clib_float32
+        if isinstance(py_feat_mat, ScipyCsrF32):
+            run = clib.c_run_clustering_csr_f32
+        elif isinstance(py_feat_mat, ScipyDrmF32):
+            run = clib.c_run_clustering_drm_f32
+        else:
+            raise NotImplementedError("type(py_feat_mat) = {} is not implemented".format(type(py_feat_mat)))
+        if codes is None or len(codes) != py_feat_mat.shape[0] or codes.dtype != np.uint32:
+            codes = np.zeros(py_feat_mat.rows, dtype=np.uint32)
+        run(byref(py_feat_mat), int(train_params.depth), byref(ClusteringParam(train_params)), codes.ctypes.data_as(POINTER(c_uint32)))
+        self._check()
+        return codes
+
+    def run_clustering_device(self, smat_handle, depth, param, d_codes, d_scores=None, stream=None):
+        """Cluster the rows of a matrix handle; ``d_codes`` (u32 [rows]) and ``d_scores`` (f32 [depth * rows] or None) are device addresses."""
+        rc = self.clib_float32.xrl_run_clustering_device(c_void_p(smat_handle), int(depth), byref(param), c_void_p(d_codes), c_void_p(d_scores or 0),
+                                                         c_void_p(stream or 0))
+        self._check()
+        return rc
+
+    def debug_cluster_plan(self, rows, cols, nnz, depth, param):
+        """The draws of a clustering, without a GPU: dict(node_seed [2^(depth+1)], level_info [depth, 2] = (sampled, first-touch),
+        work [2^depth, 4] by node id = (start, working end, position of r, position of l), perm [depth, rows])."""
+        node_seed = np.zeros(2 << depth, dtype=np.uint32); level_info = np.zeros((max(depth, 1), 2), dtype=np.uint32)
+        work = np.zeros((1 << depth, 4), dtype=np.uint32); perm = np.zeros((max(depth, 1), rows), dtype=np.uint32)
+        self.clib_float32.xrl_debug_cluster_plan(int(rows), int(cols), int(nnz), int(depth), byref(param), *(a.ctypes.data_as(c_void_p) for a in
+                                                                                                         (node_seed, level_info, work, perm)))
+        self._check()
+        return dict(node_seed=node_seed, level_info=level_info[:depth], work=work, perm=perm[:depth])
+
+    def debug_cluster_forms(self, depth=32):
+        """Of the last clustering: dict(lane_runs, wave_runs, seg_sorts, switch_level (None: never), iters per level)."""
+        out = (c_uint64 * (5 + depth))()
+        self.clib_float32.xrl_debug_cluster_forms(out, 5 + depth)
+        self._check()
+        v = [int(x) for x in out]
+        return dict(lane_runs=v[0], wave_runs=v[1], seg_sorts=v[2], switch_level=None if v[3] == 2**64 - 1 else v[3], iters=v[5:5 + min(v[4], depth)])
 
     # ------------------------------------------------------------------ device-resident path (additive)
     def queries_upload(self, c_model, X):
