@@ -390,7 +390,8 @@ int xrl_metrics_device(int device, uint32_t rows,
 
 /* SPARSE MATRIX PRODUCTS ON THE DEVICE (K10, csrc/xrl_spgemm.hip): clib.sparse_matmul (pecos/core/base.py:1460-1534) with the operands
  * and the product in HBM -- csr_codes * C^T of XR-Transformer's descent (pecos/xmc/xtransformer/matcher.py:723), Y * C of the matching
- * matrices and label roll-ups (pecos/xmc/base.py:556, 1520, 1550), S * C, Y^T * X -- on matrix handles bound to a DEVICE, not to a model.
+ * matrices and label roll-ups (pecos/xmc/base.py:556, 1520, 1550), S * C, the Yn^T * X inside xrl_label_embedding_device -- on matrix handles bound to a
+ * DEVICE, not to a model.
  * THE RULE (smat_x_smat, matrix.hpp:1075-1292, bit for bit).  Z = A * B, A rows x inner, B inner x cols, both CSR (u64 row_ptr, u32
  * col_idx, f32 val).  For every row i of A walk its stored entries s = 0, 1, ... in STORED order (whatever it is, duplicates allowed);
  * for entry (k, a) walk the stored entries t = 0, 1, ... of row k of B in stored order (duplicates allowed): acc[j] = acc[j] + a * b,
@@ -461,7 +462,7 @@ int xrl_debug_spgemm_forms(uint64_t* out, uint32_t n);
  * at a time; when it does not fit the message names the bytes needed.
  *   c_run_clustering_csr_f32 / _drm_f32   the reference's signatures: upload, run, copy label_codes [rows] back.  The dense form is the
  *                                same computation on rows that store every entry, zeros included, always with the dense norm order.
- *   xrl_run_clustering_device    the feature matrix is an xrl_smat_* CSR handle (e.g. a product of xrl_sparse_matmul_device); d_codes [rows]
+ *   xrl_run_clustering_device    the feature matrix is an xrl_smat_* CSR handle (e.g. the label embedding xrl_label_embedding_device leaves in HBM); d_codes [rows]
  *                                and d_scores (NULL or [depth * rows]: the reference's `scores` array as it stands after each level) are
  *                                in HBM on the handle's device.  Runs on hip_stream and synchronises it every iteration.  0, or -1 +
  *                                xrl_last_error.
@@ -485,6 +486,48 @@ int xrl_run_clustering_device(void* smat, uint64_t depth, const ClusteringParam*
 int xrl_debug_cluster_plan(uint64_t rows, uint64_t cols, uint64_t nnz, uint64_t depth, const ClusteringParam* param, uint32_t* node_seed, uint32_t* level_info,
                            uint32_t* work, uint32_t* perm);
 int xrl_debug_cluster_forms(uint64_t* out, uint32_t n);
+
+/* ------------------------------------------------------------------------------------------
+ * LABEL EMBEDDINGS ON THE DEVICE (K12, csrc/xrl_embed.hip, composed with K10): LabelEmbeddingFactory.create (pecos/xmc/base.py:1903-2094)
+ * for CSR operands, from a label matrix Y (samples x labels) and features X (samples x features) in HBM to the embedding E (labels x
+ * features) in HBM -- the feature matrix of xrl_run_clustering_device -- bit for bit the reference's at threads = 1.
+ * R1, row normalisation = sklearn.preprocessing.normalize(M, axis=1, norm="l2") on float32 CSR (inplace_csr_row_normalize_l2).  Per
+ *   row, s is a DOUBLE that starts at +0.0; the stored entries are walked in STORED order: s = s + (double)fl32(v * v), the square a
+ *   rounded fp32 product widened afterwards, the sum one chain (no tree: an fp32 result can see the order).  s == 0.0: the row stays as
+ *   it is, explicit zeros included.  Otherwise n = sqrt(s) in double and every entry becomes (float)((double)v / n), both correctly
+ *   rounded.  A square that overflows gives s = inf and a row of zeros; an inf entry becomes NaN and a NaN entry makes the whole row NaN
+ *   (with the bits an x86 host leaves: the first NaN of the row quieted, a NaN entry its own bits quieted, inf / inf 0xFFC00000).
+ *   Column ids and the row pointer are unchanged; duplicates and unsorted rows are walked as stored.
+ * R2, transposition = M.T.tocsr() (scipy's csr_tocsc).  Output row j holds every stored entry of column j ordered by SOURCE POSITION:
+ *   source row ascending, stored order inside a source row.  Duplicates are kept, not summed; explicit zeros are kept; the output's
+ *   column ids are the source row ids.  A function of the input only: integer atomics count and claim slots, the order inside an output
+ *   row is then made the stable one (xrl_sparse_matmul_device sums a left row in stored order, so the order reaches the score bits).
+ * R3, pifa(Y, X, normalized_Y): Yn = R1(Y) when normalized_Y, else Y; YT = R2(Yn); E = xrl_sparse_matmul_device(YT, X, eliminate_zeros
+ *   = 0, sorted_indices = 1); R1(E) in place.
+ * R4, pii(Y): R1(R2(Y)); Y is not normalised first.
+ * R5, pifa_lf_concat(Y, X, Z), Z labels x label-features: hstack([E, Z]) -- per row E's entries as stored, then Z's entries as stored
+ *   with E.cols added to their ids.
+ * Capacity: an output row of the transpose of at most 1024 entries (xrl_embed.h: CAP) is ordered by one wavefront in LDS, longer ones by
+ * a segmented sort in HBM; a transpose serves fewer than 2^32 - 1 stored entries.  Every call runs on hip_stream (NULL = the device's null
+ * stream) and SYNCHRONISES it before it returns.  Refused, before a GPU is required (messages start with the function's name): null
+ * handles; dense handles; Y.rows != X.rows; Z.rows != Y.cols; an unknown method; operands on two devices; widths that add up to 2^32 or
+ * more; 2^32 - 1 entries or more to transpose.  Refused by a kernel: an entry to transpose whose column id is not below cols.  Zero
+ * rows, zero columns and nnz == 0 succeed and give empty handles.  Dense X / Z and pifa_lf_convex_combine are not served.
+ *   xrl_smat_transpose_device       a NEW owned handle, cols x rows, by R2
+ *   xrl_smat_normalize_rows_device  R1 (L2 only).  in_place: writes the handle's own val array -- for a handle that wraps caller memory
+ *                                   (xrl_smat_from_device_csr) that IS the caller's array; `out` is not touched.  Otherwise *out <- a NEW
+ *                                   owned handle and A stays as it is.  0, or -1 + xrl_last_error
+ *   xrl_smat_hstack_device          a NEW owned handle [mats[0] mats[1] ...]: one row count, one device, n >= 1
+ *   xrl_label_embedding_device      method 0 = pifa (R3), 1 = pifa_lf_concat (R5), 2 = pii (R4; X is ignored and may be NULL).  A NEW owned
+ *                                   handle; the intermediates are freed; Y, X and Z stay as they are (the normalised Y is a private copy)
+ *   xrl_debug_embed_forms           FOR TESTS ONLY: out[0..n), n <= 5 <- {CAP, transposed rows served in LDS, by the big form, normalised
+ *                                   rows served one per lane, by a wavefront (64 entries and more)} of this process since the library
+ *                                   was loaded; rows without entries are served by neither */
+void* xrl_smat_transpose_device(void* A, void* hip_stream);
+int xrl_smat_normalize_rows_device(void* A, int in_place, void** out, void* hip_stream);
+void* xrl_smat_hstack_device(void* const* mats, uint32_t n, void* hip_stream);
+void* xrl_label_embedding_device(void* Y, void* X, void* Z_or_null, int method, int normalized_Y, void* hip_stream);
+int xrl_debug_embed_forms(uint64_t* out, uint32_t n);
 
 /* predict_on_selected_outputs on the device (K7 + K4): score a given set of labels per query row through the tree, with labels, plan and
  * scores resident in HBM.  The labels arrive in the fixed-stride form xrl_predict_device writes and xrl_ensemble_device reads: row r is

@@ -237,6 +237,11 @@ class corelib(object):
         "xrl_run_clustering_device": (c_int, [c_void_p, c_uint64, POINTER(ClusteringParam), c_void_p, c_void_p, c_void_p]),
         "xrl_debug_cluster_plan": (c_int, [c_uint64, c_uint64, c_uint64, c_uint64, POINTER(ClusteringParam), c_void_p, c_void_p, c_void_p, c_void_p]),
         "xrl_debug_cluster_forms": (c_int, [POINTER(c_uint64), c_uint32]),
+        "xrl_smat_transpose_device": (c_void_p, [c_void_p, c_void_p]),
+        "xrl_smat_normalize_rows_device": (c_int, [c_void_p, c_int, POINTER(c_void_p), c_void_p]),
+        "xrl_smat_hstack_device": (c_void_p, [POINTER(c_void_p), c_uint32, c_void_p]),
+        "xrl_label_embedding_device": (c_void_p, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+        "xrl_debug_embed_forms": (c_int, [POINTER(c_uint64), c_uint32]),
         "xrl_inspect_model": (c_int, [c_char_p, POINTER(c_uint64), c_uint32]),
         "xrl_model_create": (c_void_p, [c_uint32, c_void_p, c_void_p, POINTER(c_float), POINTER(c_uint32), POINTER(c_char_p)]),
         "xrl_queries_upload_csr": (c_void_p, [c_void_p, POINTER(ScipyCsrF32)]),
@@ -574,6 +579,48 @@ class corelib(object):
         self.clib_float32.xrl_debug_spgemm_forms(out, 5)
         self._check()
         return dict(zip(("cap", "lds_rows", "big_rows", "batches", "calls"), (int(v) for v in out)))
+
+    # ------------------------------------------------------------------ label embeddings (K12)
+    EMBED_METHODS = {"pifa": 0, "pifa_lf_concat": 1, "pii": 2}
+
+    def smat_transpose_device(self, h, stream=None):
+        """A new matrix handle with the transpose of a CSR handle in scipy's stable order (free it with :meth:`smat_free`)."""
+        t = self.clib_float32.xrl_smat_transpose_device(c_void_p(h), c_void_p(stream or 0))
+        self._check()
+        return t
+
+    def smat_normalize_rows_device(self, h, in_place=False, stream=None):
+        """L2 row normalisation in sklearn's arithmetic: a new matrix handle, or with ``in_place`` None after the handle's own values
+        (the caller's array, for a wrapped handle) were rewritten."""
+        out = c_void_p()
+        self.clib_float32.xrl_smat_normalize_rows_device(c_void_p(h), 1 if in_place else 0, byref(out), c_void_p(stream or 0))
+        self._check()
+        return None if in_place else out.value
+
+    def smat_hstack_device(self, handles, stream=None):
+        """A new matrix handle ``[M0 M1 ...]`` of matrix handles with one row count on one device."""
+        arr = (c_void_p * max(len(handles), 1))(*handles)
+        h = self.clib_float32.xrl_smat_hstack_device(arr, len(handles), c_void_p(stream or 0))
+        self._check()
+        return h
+
+    def label_embedding_device(self, Y, X=None, Z=None, method="pifa", normalized_Y=True, stream=None):
+        """A new matrix handle with the label embedding of matrix handles ``Y`` (samples x labels), ``X`` (samples x features) and, for
+        ``pifa_lf_concat``, ``Z`` (labels x label-features); ``method`` is a name of :attr:`EMBED_METHODS` or its number."""
+        m = self.EMBED_METHODS.get(method, method) if isinstance(method, str) else method
+        if not isinstance(m, int):
+            raise NotImplementedError(f"label embedding method '{method}' is not served on the device; served: {sorted(self.EMBED_METHODS)}")
+        h = self.clib_float32.xrl_label_embedding_device(c_void_p(Y), c_void_p(X or 0), c_void_p(Z or 0), m, 1 if normalized_Y else 0, c_void_p(stream or 0))
+        self._check()
+        return h
+
+    def debug_embed_forms(self):
+        """Debug counters of K12 since the load: its CAP, transposed rows served in LDS and by the big form, normalised rows served one
+        per lane and by a wavefront."""
+        out = (c_uint64 * 5)()
+        self.clib_float32.xrl_debug_embed_forms(out, 5)
+        self._check()
+        return dict(zip(("cap", "t_lds", "t_big", "n_lane", "n_wave"), (int(v) for v in out)))
 
     # ------------------------------------------------------------------ label clustering (K11)
     def run_clustering(self, py_feat_mat, train_params, codes=None):

@@ -1,4 +1,4 @@
-// What the units behind the extern "C" surface share (xrl_abi.cpp, xrl_host_pipeline.cpp, xrl_single_layer.cpp, xrl_tfidf_abi.cpp, xrl_smat_abi.cpp):
+// What the units behind the extern "C" surface share (xrl_abi.cpp, xrl_host_pipeline.cpp, xrl_single_layer.cpp, xrl_tfidf_abi.cpp, xrl_smat_abi.cpp, xrl_embed_abi.cpp):
 // the per-thread error and device state, the exception barrier of every entry point, the makers of X's device view, the upload of a caller's host X,
 // and the bodies the query and matrix handles share.
 #pragma once

@@ -138,10 +138,17 @@ template <class T> __device__ __forceinline__ uint32_t lower_bound(const T* __re
     return lo;
 }
 // the segment of position x under the offsets off[0, n_seg): the last one that starts at or before it (empty segments share their successor's offset)
-__device__ __forceinline__ uint32_t segment_of(const uint32_t* off, uint32_t n_seg, uint32_t x) {
+// (u32 offsets everywhere but over a CSR's u64 row pointer, K12)
+template <class T> __device__ __forceinline__ uint32_t segment_of(const T* off, uint32_t n_seg, T x) {
     uint32_t lo = 0, hi = n_seg;
     while (hi - lo > 1) { const uint32_t mid = lo + ((hi - lo) >> 1); if (off[mid] <= x) lo = mid; else hi = mid; }
     return lo;
+}
+// stored entries [b, e) of row r of a CSR, clamped to the arrays' nnz entries
+__device__ __forceinline__ void row_span(const uint64_t* ptr, uint64_t r, uint64_t nnz, uint64_t& b, uint64_t& e) {
+    const uint64_t e0 = ptr[r + 1], b0 = ptr[r];
+    e = e0 < nnz ? e0 : nnz;
+    b = b0 < e ? b0 : e;
 }
 
 template <int N>

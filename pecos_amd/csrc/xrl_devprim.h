@@ -41,5 +41,9 @@ template <class T> T scan_total(DevBuf& tmp, const T* in, T* out, size_t n, hipS
 // (then a row holds at most stride).  Checks the launch.
 void launch_copy_rows(const uint64_t* ptr, uint64_t rows, const uint64_t* src_off, uint32_t stride, const uint32_t* s_idx, const float* s_val,
                       uint32_t* idx, float* val, const char* what, hipStream_t s);
+// The same copy loop for hstack (K12): row r of the CSR (s_ptr, s_idx, s_val) of s_nnz entries, its span clamped to them, goes to dst[r]
+// with col_add added to every column id.
+void launch_copy_csr_rows(const uint64_t* dst, uint64_t rows, const uint64_t* s_ptr, const uint32_t* s_idx, const float* s_val, uint64_t s_nnz, uint32_t col_add,
+                          uint32_t* idx, float* val, const char* what, hipStream_t s);
 
 }  // namespace xrl

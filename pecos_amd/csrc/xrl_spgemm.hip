@@ -56,13 +56,6 @@ __device__ __forceinline__ float host_nan(float r, float x, float y) {
 __device__ __forceinline__ float ref_mul(float a, float b) { return host_nan(__fmul_rn(a, b), a, b); }
 __device__ __forceinline__ float ref_add(float acc, float p) { return host_nan(__fadd_rn(acc, p), acc, p); }
 
-// stored entries [b, e) of row r, clamped to the arrays
-__device__ __forceinline__ void row_span(const uint64_t* ptr, uint64_t r, uint64_t nnz, uint64_t& b, uint64_t& e) {
-    const uint64_t e0 = ptr[r + 1], b0 = ptr[r];
-    e = e0 < nnz ? e0 : nnz;
-    b = b0 < e ? b0 : e;
-}
-
 __global__ void __launch_bounds__(256) k10_flops(K10Args a, uint64_t* __restrict__ flops, unsigned long long* __restrict__ words) {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (i >= a.rows) return;

@@ -454,6 +454,23 @@ class DeviceMatrix:
         return DeviceMatrix(clib.sparse_matmul_device(self.handle, other.handle, eliminate_zeros, sorted_indices, stream=stream))
 
 
+    def transpose(self, stream=None):
+        """The transpose as a new :class:`DeviceMatrix`, rows in scipy's ``.T.tocsr()`` order (K12; rule R2 at ``xrl_label_embedding_device``)."""
+        return DeviceMatrix(clib.smat_transpose_device(self.handle, stream=stream))
+
+    def normalize_rows(self, in_place=False, stream=None):
+        """Rows scaled to unit L2 norm in sklearn's arithmetic (K12; rule R1).  ``in_place`` rewrites this matrix's values -- the wrapped
+        tensor's, for :meth:`from_torch` -- and returns ``self``; otherwise a new :class:`DeviceMatrix`."""
+        h = clib.smat_normalize_rows_device(self.handle, in_place, stream=stream)
+        return self if in_place else DeviceMatrix(h)
+
+    @classmethod
+    def hstack(cls, mats, stream=None):
+        """``[M0 M1 ...]`` of :class:`DeviceMatrix` with one row count on one device, as a new one (stored order kept inside each part)."""
+        mats = list(mats)
+        return cls(clib.smat_hstack_device([m.handle for m in mats], stream=stream))
+
+
 def result_to_csr_device(result, n_cols=0, stream=None):
     """A result triple (:func:`result_buffers`' form; counts may be None = full rows) as CSR tensors on its device: ``(crow int64 [rows + 1],
     col int32 [nnz], val float32 [nnz])``, every row best first as the result stores it."""

@@ -1,6 +1,9 @@
 """Label indexing on the device: :class:`HierarchicalKMeans` (the surface of ``pecos.xmc.base.HierarchicalKMeans``: ``TrainParams``,
 ``gen``) over K11's balanced hierarchical 2-means, and :func:`run_clustering_device`, whose feature matrix and codes stay in HBM.
-The codes are the reference's at ``threads = 1`` (``xrl_run_clustering_device`` in include/xrl_abi.h states the rule)."""
+The codes are the reference's at ``threads = 1`` (``xrl_run_clustering_device`` in include/xrl_abi.h states the rule).
+Ahead of it :class:`LabelEmbeddingFactory` (the surface of ``pecos.xmc.base.LabelEmbeddingFactory``) and
+:func:`label_embedding_device` over K12 and K10: label matrix and features in, the PIFA / PII embedding out, which the clustering
+takes as it is (``xrl_label_embedding_device`` states the rules)."""
 import dataclasses as dc
 import math
 
@@ -135,3 +138,74 @@ def run_clustering_device(feat, depth, partition_algo=HierarchicalKMeans.SKMEANS
     if dtype is not None:
         codes = codes.view(dtype)
     return (codes, scores) if return_scores else codes
+
+
+def _embedding_operand(name, M):
+    """An operand of a label embedding as the device form takes it; what is not served says so."""
+    if isinstance(M, np.ndarray):
+        raise NotImplementedError(f"label embedding: a dense {name} is not served on the device (CSR operands only)")
+    if smat.issparse(M) and M.dtype != np.float32:
+        raise ValueError(f"label embedding: {name} must be float32, got {M.dtype}")
+    return M
+
+
+def label_embedding_device(Y, X=None, method="pifa", Z=None, normalized_Y=True, stream=None):
+    """The label embedding of ``Y`` (samples x labels) computed and left in HBM as a :class:`~pecos_amd.features.DeviceMatrix`
+    (labels x features): ``method`` is ``"pifa"`` = normalize(normalize(Y)^T * X) over ``X`` (samples x features), ``"pifa_lf_concat"`` =
+    that next to ``Z`` (labels x label-features), or ``"pii"`` = normalize(Y^T), in the reference's arithmetic bit for bit.  An operand is
+    what :func:`~pecos_amd.features.sparse_matmul_device` accepts: a DeviceMatrix, a float32 scipy sparse matrix (uploaded), or CSR tensors
+    ``(crow, col, val, (rows, cols))``; none of them is changed.  The result feeds :func:`run_clustering_device`.  Runs on ``stream``
+    (default: torch's current one), which it synchronises."""
+    from .features import DeviceMatrix, _as_device_matrix, _operand_device, _stream_or_current
+    method = str(method).lower()
+    if method == "pifa_lf_convex_combine":
+        raise NotImplementedError("label embedding: pifa_lf_convex_combine is not served on the device")
+    if method not in clib.EMBED_METHODS:
+        raise NotImplementedError(f"label embedding method '{method}' is not implemented; served: {sorted(clib.EMBED_METHODS)}")
+    if Y is None or (method != "pii" and X is None) or (method == "pifa_lf_concat" and Z is None):
+        raise ValueError(f"label embedding: method '{method}' needs " + {"pii": "Y", "pifa": "Y and X", "pifa_lf_concat": "Y, X and Z"}[method])
+    ops = [_embedding_operand("Y", Y), None if method == "pii" else _embedding_operand("X", X),
+           _embedding_operand("Z", Z) if method == "pifa_lf_concat" else None]
+    dev = next((d for d in (_operand_device(M) for M in ops if M is not None) if d is not None), 0)
+    y, x, z = (None if M is None else _as_device_matrix(M, dev, None, stream) for M in ops)
+    return DeviceMatrix(clib.label_embedding_device(y.handle, x and x.handle, z and z.handle, method, normalized_Y, stream=_stream_or_current(dev, stream)))
+
+
+class LabelEmbeddingFactory(object):
+    """The reference's ``LabelEmbeddingFactory`` (pecos/xmc/base.py:1903-2094) computed on the device: scipy matrices in, a scipy
+    ``csr_matrix`` out, bit for bit the reference's at ``threads = 1``.  ``threads`` is accepted and ignored.  Dense ``X`` / ``Z`` and
+    ``pifa_lf_convex_combine`` are not served."""
+
+    @staticmethod
+    def create(Y=None, X=None, method="pifa", **kwargs):
+        mapping = {"pifa": LabelEmbeddingFactory.pifa, "pifa_lf_concat": LabelEmbeddingFactory.pifa_lf_concat,
+                   "pifa_lf_convex_combine": LabelEmbeddingFactory.pifa_lf_convex_combine, "pii": LabelEmbeddingFactory.pii}
+        m = str(method).lower()
+        if m not in mapping:
+            raise NotImplementedError(f"Label embedding method '{method}' is not implemented. Valid ones: {list(mapping)}")
+        return mapping[m](Y) if m == "pii" else mapping[m](Y, X, **kwargs)
+
+    @staticmethod
+    def _run(method, Y, X=None, Z=None, normalized_Y=True):
+        if not smat.issparse(Y):
+            raise NotImplementedError("type(Y) should be scipy.sparse.spmatrix")
+        for name, M in (("X", X), ("Z", Z)):
+            if M is not None and not isinstance(M, (smat.csr_matrix, np.ndarray)):
+                raise NotImplementedError(f"type({name}) should be row-major spmatrix or ndarray")
+        return label_embedding_device(Y, X, method=method, Z=Z, normalized_Y=normalized_Y).download()
+
+    @staticmethod
+    def pifa(Y, X, threads=-1, normalized_Y=True):
+        return LabelEmbeddingFactory._run("pifa", Y, X, normalized_Y=normalized_Y)
+
+    @staticmethod
+    def pifa_lf_concat(Y, X, Z, threads=-1, normalized_Y=True):
+        return LabelEmbeddingFactory._run("pifa_lf_concat", Y, X, Z, normalized_Y=normalized_Y)
+
+    @staticmethod
+    def pifa_lf_convex_combine(Y, X, Z, alpha=0.5, threads=-1, normalized_Y=True):
+        raise NotImplementedError("LabelEmbeddingFactory: pifa_lf_convex_combine is not served on the device")
+
+    @staticmethod
+    def pii(Y):
+        return LabelEmbeddingFactory._run("pii", Y)
