@@ -91,6 +91,7 @@ struct K1QArgs {
 // BIGW = true: the row's 64-bit base is rebuilt per feature (s_mul_hi, s_mul, s_add, s_addc, s_and), num_records = one row.
 // Round 4 used the second form everywhere, with a clamp: 6 scalar instructions per weight load against 2 vector ones -- and a CU has ONE
 // scalar unit (profiles/r05_k1q_scalar.md).
+constexpr uint32_t kK1QLaneOff = 0xFFFFFFF0u;   // the lane offset that switches a lane's weight load off: outside the resource in both forms (launch_k1q keeps every matrix below it)
 template <bool BIGW>
 __device__ __forceinline__ uint32_t k1q_load_w(const uint32_t* wd, uint32_t row_bytes, uint32_t rows, uint32_t f, uint32_t voff) {
     if (BIGW) {
@@ -182,8 +183,13 @@ __device__ __forceinline__ K1QRow k1q_row(const QueriesDev& X, uint64_t xrow, ui
 
 // Prolongation of one candidate: column `col` of dense tile `tt` of beam parent `parent` (v: the beam holds that parent) -> the candidate's BYTE
 // offset inside a feature row (d_ld < 2^30), its child id in the layer's column order, and whether it exists.
+// A lane WITHOUT a candidate (a beam shorter than the register, the padding columns of a parent with fewer children than the tile is wide) gets the
+// offset `idle`.  0 asks for column 0 of the layer: one more 64-byte request per (feature, register) whenever no candidate of the instruction
+// shares that line -- a fifth request beside the four of a 62-children parent's register (Eurlex-4K's leaf), a seventh beside the six parents of a
+// second pass.  k1q_layer passes kK1QLaneOff instead (no request; the lane's accumulator is never read: valid = false), except in the PRES
+// instantiations, whose presence masks derive a tile from the offset.  The fused bodies of levels 0 + 1 keep 0: their column 0 is always a candidate's.
 struct K1QCand { uint32_t woff, child; bool valid; };
-__device__ __forceinline__ K1QCand k1q_candidate(const K1QLayer& Ly, bool v, uint32_t parent, uint32_t tt, uint32_t col) {
+__device__ __forceinline__ K1QCand k1q_candidate(const K1QLayer& Ly, bool v, uint32_t parent, uint32_t tt, uint32_t col, uint32_t idle = 0u) {
     const uint32_t gl = Ly.d_gp_log2;
     v = v && parent < Ly.n_parents;
     if (!v) parent = 0;
@@ -197,7 +203,7 @@ __device__ __forceinline__ K1QCand k1q_candidate(const K1QLayer& Ly, bool v, uin
         const uint32_t ce = Ly.d_tcol[dtc + 1];
         v = v && col < ce - cb;
     }
-    return {v ? ((dtc << gl) + col) * 4u : 0u, v ? cb + col : 0u, v};
+    return {v ? ((dtc << gl) + col) * 4u : idle, v ? cb + col : 0u, v};
 }
 
 // The new beam, best first (reorder_prediction, inference.hpp:1919-1923): lane < kk holds the rank-th best candidate's score bits and child
@@ -299,7 +305,7 @@ __device__ __forceinline__ uint32_t k1q_layer(const K1QLayer& Ly, const QueriesD
         bool v = j < cnt;
         uint32_t parent = 0; float pscore = 1.0f;
         if (!Ly.implicit_root) { parent = s_bidx[v ? j : 0u]; pscore = s_bval[v ? j : 0u]; }
-        const K1QCand c = k1q_candidate(Ly, v, parent, tt, col);
+        const K1QCand c = k1q_candidate(Ly, v, parent, tt, col, PRES ? 0u : kK1QLaneOff);
         woff[r] = c.woff; child[r] = c.child; valid[r] = c.valid;
         ps[r] = pscore;
         // dense queries: bias FIRST (inference.hpp:824-830); bias_prod holds fl32(bias * w) or +0.0
@@ -350,7 +356,7 @@ __device__ __forceinline__ uint32_t k1q_layer(const K1QLayer& Ly, const QueriesD
                     const uint32_t fu = getf(u);
                     const uint32_t sm = (uint32_t)__builtin_amdgcn_readlane((int)pm, (int)((tl + (uint32_t)u) & 63u));
 #pragma unroll
-                    for (int r = 0; r < NR; ++r) wb[u][r] = k1q_load_w<BIGW>(wd, ld, w_rows + 1u, fu, (sm & mybit[r]) ? woff[RB + r] : 0xFFFFFFF0u);
+                    for (int r = 0; r < NR; ++r) wb[u][r] = k1q_load_w<BIGW>(wd, ld, w_rows + 1u, fu, (sm & mybit[r]) ? woff[RB + r] : kK1QLaneOff);
                 }
             } else {
 #pragma unroll
@@ -601,7 +607,7 @@ __device__ __forceinline__ uint32_t k1q_layer01m(const K1QLayer& L0, const K1QLa
     const bool v1 = cd.valid;
     const uint32_t child1 = cd.child;
     // this lane's column of the merged row; lanes that hold neither a level-1 candidate nor a level-0 column address outside the resource (no request)
-    const uint32_t woff = v1 ? cd.woff : v0 ? (c1 + l0) * 4u : 0xFFFFFFF0u;
+    const uint32_t woff = v1 ? cd.woff : v0 ? (c1 + l0) * 4u : kK1QLaneOff;
     const float bp1 = (v1 && L1.has_bias) ? L1.bias_prod[child1] : 0.0f, bp0 = (v0 && L0.has_bias) ? L0.bias_prod[child0] : 0.0f;
     const float bp = v1 ? bp1 : bp0;
     float acc = BIASF ? bp : 0.0f;
