@@ -529,6 +529,77 @@ void* xrl_smat_hstack_device(void* const* mats, uint32_t n, void* hip_stream);
 void* xrl_label_embedding_device(void* Y, void* X, void* Z_or_null, int method, int normalized_Y, void* hip_stream);
 int xrl_debug_embed_forms(uint64_t* out, uint32_t n);
 
+/* ------------------------------------------------------------------------------------------
+ * RANKER TRAINING ON THE DEVICE (K13, csrc/xrl_train.hip): one layer of XR-Linear's weights from X (N x d), the label matrix Y (N x L),
+ * the label-to-cluster matrix C (L x K) and the matching matrix M (N x K) -- libpecos.cpp:277-316 -> multilabel_train_with_codes
+ * (pecos/core/xmc/linear_solver.hpp:797-860) -- bit for bit the reference's at threads = 1.  `threads` is accepted and ignored: a
+ * job's weights do not depend on it, only the order of the reference's COO does.  The reference is the one compiled with libstdc++
+ * (std::shuffle and std::uniform_int_distribution are the library's) and without FMA.
+ * THE RULE.  Only the PATTERNS of Y, C and M are read: explicit zeros count, values are ignored.  R (optional, Y's pattern) gives the
+ * cost of a positive.
+ *   Jobs (:828-844).  With C and M: for every column `code` of C in order, for every stored entry `label` of that column in STORED order,
+ *     one job (code, label).  With C or M null (pure multi-label): one job per label 0 .. L-1.  Jobs are independent.
+ *   Instances (:667-712).  index <- the stored row ids of M[:, code] in stored order (pure: 0 .. N-1), each with y = -1, cost = 1.  Then the
+ *     stored row ids i of Y[:, label] in stored order: y[i] = +1; i is appended to index when M's column did not list it; cost[i] =
+ *     R's value at that stored position, or 1.
+ *   Storage.  w [d], b, alpha and QD are fp32.  G, C, PG, d and the alpha update are fp64, rounded on the store.
+ *   Set-up (:438-447).  class_cost = y > 0 ? Cp : Cn (fp64).  diag_i = 0.5 / (class_cost * (double)cost_i) for the L2 loss
+ *     (L2R_L2LOSS_SVC_DUAL = 1), 0 for the L1 loss (L2R_L1LOSS_SVC_DUAL = 3).  QD_i = fl32(diag_i), then QD_i = fl32((double)QD_i +
+ *     ((double)xx + bb)): xx the fp32 chain from +0 over the row's stored entries of fl32(v * v) (matrix.hpp:837-859), bb = bias * bias
+ *     when bias > 0, else 0.  alpha = 0, w = 0, b = 0.
+ *   Sweep (:456-527), iter = 0 .. max_iter-1, active = |index| at first.  std::shuffle(index[0, active)) with ONE std::mt19937(0) per
+ *     job that lives across its sweeps.  libstdc++'s shuffle: up to 65 535 elements an even count first swaps position 1 with a draw
+ *     from {0, 1}, then positions i, i+1 are taken two at a time from one draw x in [0, (i+1)(i+2)): swap(i, x / (i+2)), swap(i+1, x %
+ *     (i+2)); from 65 536 elements one draw in [0, i] per position i.  A draw in [0, r) is Lemire's: p = u64(next word) * r; when
+ *     u32(p) < r, redraw while u32(p) < (2^32 - r) % r; the draw is p >> 32.  Then s = 0, 1, ... while s < active, i = index[s]:
+ *       dot = the fp32 chain from +0 of fl32(w[f] * v) over row i's stored entries in stored order (matrix.hpp:870-877)
+ *       G = y * ((double)dot + (bias > 0 ? (double)b * bias : 0)) - 1 + (double)alpha_i * diag_i;  C = inf (L2 loss), class_cost * cost (L1)
+ *       alpha_i == 0: G > PGmax_old shrinks; else PG = min(G, 0).  alpha_i == C: G < PGmin_old shrinks; else PG = max(G, 0).  Else PG = G.
+ *       Shrinking: active -= 1, swap(index[s], index[active]), and s is visited again.
+ *       PGmax_new, PGmin_new follow PG.  When |PG| > 1e-12: alpha_i <- fl32(min(max(alpha_i - G / (double)QD_i, 0), C)); d = ((double)
+ *       alpha_i - alpha_old) * y; w[f] <- fl32((double)w[f] + d * (double)v) per stored entry (an fp64 product and an fp64 add, :971-976);
+ *       b <- fl32((double)b + d * bias) when bias > 0.
+ *     After the sweep: PGmax_new - PGmin_new <= eps ends the job when active == |index|, otherwise active = |index| and the old bounds
+ *     reset (a re-activation); else the old bounds become the new ones, PGmax_old <= 0 -> inf, PGmin_old >= 0 -> -inf.
+ *   Emission (:718-779), fabs(v) >= threshold compared in fp64 (NaN fails).  max_nonzeros_per_label = 0: the features that pass, ascending,
+ *     then the bias as row d when bias > 0 and it passes.  max_nonzeros_per_label = k > 0: of the features that pass, the k with the
+ *     largest |w|, ties to the lower feature; when fewer than k pass, all of them and the bias (if it passes); otherwise the bias
+ *     replaces the least kept feature when |b| > |w_least|.  The reference leaves the order inside such a label to std::nth_element; here
+ *     a label's entries are ascending in both cases.
+ * Not pinned: non-finite values in X, a relevance of 0, a row id stored twice in one column of Y or M.
+ * Capacity.  One wavefront owns one job at a time, with a slot of scratch (w, a bitmap of touched features, index, alpha, QD, cost, y);
+ * jobs go in batches whose emission staging stays under the budget (4 GiB each for slots and staging; XRL_TRAIN_SCRATCH_BYTES in the
+ * environment replaces it).  All jobs read ONE table of mt19937(0) outputs the host fills (XRL_TRAIN_RANDOM_WORDS = its first length,
+ * 2^22 by default); a job that reaches its end is run again after the table has grown fourfold.
+ * Refused, with messages that start with the function's name.  Before a GPU is required: L2R_LR_DUAL (7), L2R_L2LOSS_SVC_PRIMAL (2) and
+ * unknown solvers; null arguments; shape mismatches; operands on two devices; 2^31 rows or more; 2^32 - 1 jobs or more; (host forms) a
+ * label listed twice in C, an R that does not share Y's pattern.  By check kernels: the same two for the resident form; a row of X whose
+ * column ids are not strictly ascending (the lanes apply the axpy in parallel); ids out of range; row pointers that do not ascend.
+ *   xrl_single_layer_train_csr_f32 / _drm_f32   the signatures of the reference's c_xlinear_single_layer_train_* and its COO allocator:
+ *                                upload, train, copy back rows (features; d = the bias), cols (labels) and values in job order.  The
+ *                                dense form is the same computation on rows that store every entry, zeros included.  The names carry
+ *                                this library's prefix ON PURPOSE: a binding that resolves symbols here first and in the reference
+ *                                otherwise (the drop-in deployment, tests/test_reference_binding.py) keeps the reference's trainer,
+ *                                with L2R_LR_DUAL and L2R_L2LOSS_SVC_PRIMAL; a caller that wants K13 binds these two names with the
+ *                                reference's argument list.
+ *   xrl_train_layer_device       X (N x d), Yt (L x N), Ct (K x L) and Mt (K x N) are CSR handles of the transposes -- the CSC arrays the
+ *                                solver reads; Ct and Mt NULL together = pure multi-label; Rt NULL or Yt's pattern.  A NEW owned handle with
+ *                                W^T, L x (d + (bias > 0)): the CSC of W with ascending features; a label without a job has an empty row.
+ *                                Runs on hip_stream and synchronises it per batch.  NULL + xrl_last_error on failure.
+ *   xrl_debug_train_counters     FOR TESTS ONLY: of the last training of this process, out[0..n), n <= 13 <- {jobs, batches, slots, staging
+ *                                stride, sweeps, shrink events, re-activations, jobs stopped by max_iter, alpha clipped at C, x'x rows
+ *                                summed one per lane, by a wavefront (64 entries and more), table extensions, jobs run again} */
+typedef void (*py_coo_allocator_t)(uint64_t rows, uint64_t cols, uint64_t nnz, void* row_pp, void* col_pp, void* val_pp);   /* matrix.hpp:46: u64 rows, u64 cols, f32 values */
+void xrl_single_layer_train_csr_f32(const ScipyCsrF32* pX, const ScipyCscF32* pY, const ScipyCscF32* pC, const ScipyCscF32* pM, const ScipyCscF32* pR,
+                                    py_coo_allocator_t coo_alloc, double threshold, uint32_t max_nonzeros_per_label, int solver_type, double Cp, double Cn,
+                                          size_t max_iter, double eps, double bias, int threads);
+void xrl_single_layer_train_drm_f32(const ScipyDrmF32* pX, const ScipyCscF32* pY, const ScipyCscF32* pC, const ScipyCscF32* pM, const ScipyCscF32* pR,
+                                    py_coo_allocator_t coo_alloc, double threshold, uint32_t max_nonzeros_per_label, int solver_type, double Cp, double Cn,
+                                          size_t max_iter, double eps, double bias, int threads);
+void* xrl_train_layer_device(void* X, void* Yt, void* Ct_or_null, void* Mt_or_null, void* Rt_or_null, double threshold, uint32_t max_nonzeros_per_label,
+                             int solver_type, double Cp, double Cn, uint64_t max_iter, double eps, double bias, void* hip_stream);
+int xrl_debug_train_counters(uint64_t* out, uint32_t n);
+
 /* predict_on_selected_outputs on the device (K7 + K4): score a given set of labels per query row through the tree, with labels, plan and
  * scores resident in HBM.  The labels arrive in the fixed-stride form xrl_predict_device writes and xrl_ensemble_device reads: row r is
  * d_sel_idx[r*sel_stride ..], d_sel_cnt[r] entries long (NULL = sel_stride each; a count above the stride is read as the stride), in any

@@ -7,7 +7,8 @@ Mirrors, for that path only, the reference's binding layer (pecos/core/base.py):
 * ``ScipyCompressedSparseAllocator`` (python-side result allocator)        base.py:357-478
 * ``corelib`` methods ``xlinear_load_predict_only``, ``xlinear_destruct_model``,
   ``xlinear_get_int_attr``, ``xlinear_get_layer_type``, ``xlinear_predict``,
-  ``xlinear_single_layer_predict``, ``sparse_matmul``,
+  ``xlinear_single_layer_predict``, ``xlinear_single_layer_train`` (with
+  ``ScipyCoordinateSparseAllocator``), ``sparse_matmul``,
   ``sparse_inner_products``                                               base.py:978-1405, 1460-1589
 
 with the same names, argument order and meaning, so that code written against
@@ -152,6 +153,42 @@ class ScipyCompressedSparseAllocator(object):
         return self.CFUNCTYPE(self)
 
 
+class ScipyCoordinateSparseAllocator(object):
+    """Python-side allocator of a COO result (base.py:481-540): u64 row and column ids and float32 values, allocated when the native
+    training call knows the count."""
+
+    CFUNCTYPE = CFUNCTYPE(None, c_uint64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p)
+
+    def __init__(self, rows=0, cols=0, dtype=np.float32):
+        assert dtype == np.float32
+        self.rows, self.cols, self.dtype = rows, cols, dtype
+        self.row_ptr = self.col_ptr = self.data = None
+
+    def __call__(self, rows, cols, nnz, row_ptr, col_ptr, val_ptr):
+        self.rows, self.cols = rows, cols
+        self.row_ptr, self.col_ptr, self.data = np.zeros(nnz, dtype=np.uint64), np.zeros(nnz, dtype=np.uint64), np.zeros(nnz, dtype=self.dtype)
+        for dst, arr in ((row_ptr, self.row_ptr), (col_ptr, self.col_ptr), (val_ptr, self.data)):
+            cast(dst, POINTER(c_uint64)).contents.value = arr.ctypes.data_as(c_void_p).value or 0
+
+    def _coo(self):
+        if self.data is None:
+            raise RuntimeError("native call did not produce a result")
+        return smat.coo_matrix((self.data, (self.row_ptr.astype(np.int64), self.col_ptr.astype(np.int64))), shape=(self.rows, self.cols))
+
+    def tocsr(self):
+        return self._coo().tocsr()
+
+    def tocsc(self):
+        return self._coo().tocsc()
+
+    @property
+    def cfunc(self):
+        return self.CFUNCTYPE(self)
+
+
+XLINEAR_SOLVERS = {"L2R_L2LOSS_SVC_DUAL": 1, "L2R_L1LOSS_SVC_DUAL": 3, "L2R_LR_DUAL": 7, "L2R_L2LOSS_SVC_PRIMAL": 2}  # base.py:42-47
+
+
 class ProfileRec(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("layer", c_uint32), ("launches", c_uint32),
                 ("ms", c_double), ("reserved", c_double)]
@@ -197,6 +234,7 @@ class corelib(object):
         return self._lib
 
     _alloc_t = ScipyCompressedSparseAllocator.CFUNCTYPE
+    _coo_alloc_t = ScipyCoordinateSparseAllocator.CFUNCTYPE
     # name -> (result type, argument types) of every function include/xrl_abi.h declares
     SIGNATURES = {
         "xrl_last_error": (c_char_p, []),
@@ -242,6 +280,13 @@ class corelib(object):
         "xrl_smat_hstack_device": (c_void_p, [POINTER(c_void_p), c_uint32, c_void_p]),
         "xrl_label_embedding_device": (c_void_p, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
         "xrl_debug_embed_forms": (c_int, [POINTER(c_uint64), c_uint32]),
+        "xrl_single_layer_train_csr_f32": (None, [POINTER(ScipyCsrF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32),
+                                                        _coo_alloc_t, c_double, c_uint32, c_int, c_double, c_double, c_uint64, c_double, c_double, c_int]),
+        "xrl_single_layer_train_drm_f32": (None, [POINTER(ScipyDrmF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32),
+                                                        _coo_alloc_t, c_double, c_uint32, c_int, c_double, c_double, c_uint64, c_double, c_double, c_int]),
+        "xrl_train_layer_device": (c_void_p, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_uint32, c_int, c_double, c_double, c_uint64, c_double,
+                                              c_double, c_void_p]),
+        "xrl_debug_train_counters": (c_int, [POINTER(c_uint64), c_uint32]),
         "xrl_inspect_model": (c_int, [c_char_p, POINTER(c_uint64), c_uint32]),
         "xrl_model_create": (c_void_p, [c_uint32, c_void_p, c_void_p, POINTER(c_float), POINTER(c_uint32), POINTER(c_char_p)]),
         "xrl_queries_upload_csr": (c_void_p, [c_void_p, POINTER(ScipyCsrF32)]),
@@ -621,6 +666,56 @@ class corelib(object):
         self.clib_float32.xrl_debug_embed_forms(out, 5)
         self._check()
         return dict(zip(("cap", "t_lds", "t_big", "n_lane", "n_wave"), (int(v) for v in out)))
+
+    # ------------------------------------------------------------------ ranker training (K13)
+    TRAIN_COUNTERS = ("jobs", "batches", "slots", "stride", "iters", "shrinks", "reactivations", "max_iter_stops", "clipped", "lane_rows", "wave_rows",
+                      "extensions", "reruns")
+
+    @staticmethod
+    def _solver_number(solver_type):
+        if isinstance(solver_type, str):
+            if solver_type not in XLINEAR_SOLVERS:
+                raise ValueError(f"unknown solver_type '{solver_type}'; known: {sorted(XLINEAR_SOLVERS)}")
+            return XLINEAR_SOLVERS[solver_type]
+        return int(solver_type)
+
+    def xlinear_single_layer_train(self, pX, pY, pC, pM, pR, threshold=0.1, max_nonzeros_per_label=None, solver_type="L2R_L2LOSS_SVC_DUAL", Cp=1.0, Cn=1.0,
+                                   max_iter=1000, eps=0.1, bias=1.0, threads=-1, verbose=0, **kwargs):
+        """One layer's weights trained on the device (K13; ``xrl_single_layer_train_{csr,drm}_f32``, the reference's argument list under this
+        library's prefix), with the reference's dispatch and return (base.py:1302-1373): ``pX`` is a
+        ScipyCsrF32 or ScipyDrmF32 view, ``pY`` / ``pC`` / ``pM`` / ``pR`` are ScipyCscF32 views (``pC`` / ``pM`` None: pure multi-label,
+        ``pR`` None: every positive costs 1).  Returns the float32 ``csc_matrix`` W, (features + (bias > 0)) x labels.  The weights are
+        the reference's at threads = 1 bit for bit; ``threads`` and ``verbose`` are accepted and ignored."""
+        clib = self.clib_float32
+        coo_alloc = ScipyCoordinateSparseAllocator(dtype=np.float32)
+        if isinstance(pX, ScipyCsrF32):
+            train = clib.xrl_single_layer_train_csr_f32
+        elif isinstance(pX, ScipyDrmF32):
+            train = clib.xrl_single_layer_train_drm_f32
+        else:
+            raise NotImplementedError("type(pX) = {} not implemented".format(type(pX)))
+        train(byref(pX), byref(pY), byref(pC) if pC is not None else None, byref(pM) if pM is not None else None, byref(pR) if pR is not None else None,
+              coo_alloc.cfunc, threshold, 0 if max_nonzeros_per_label is None else max_nonzeros_per_label, self._solver_number(solver_type), Cp, Cn, max_iter,
+              eps, bias, threads)
+        self._check()
+        return coo_alloc.tocsc().astype(np.float32)
+
+    def train_layer_device(self, X, Yt, Ct=None, Mt=None, Rt=None, threshold=0.1, max_nonzeros_per_label=None, solver_type="L2R_L2LOSS_SVC_DUAL", Cp=1.0,
+                           Cn=1.0, max_iter=1000, eps=0.1, bias=1.0, stream=None):
+        """A new matrix handle with W^T (labels x (features + (bias > 0)), CSR = the CSC of W) trained from matrix handles: X and the
+        TRANSPOSES of Y, C, M and R (free it with :meth:`smat_free`)."""
+        h = self.clib_float32.xrl_train_layer_device(c_void_p(X), c_void_p(Yt), c_void_p(Ct or 0), c_void_p(Mt or 0), c_void_p(Rt or 0), threshold,
+                                                     0 if max_nonzeros_per_label is None else max_nonzeros_per_label, self._solver_number(solver_type), Cp, Cn,
+                                                     max_iter, eps, bias, c_void_p(stream or 0))
+        self._check()
+        return h
+
+    def debug_train_counters(self):
+        """What the last training of this process ran (``xrl_debug_train_counters``), by name."""
+        out = (c_uint64 * len(self.TRAIN_COUNTERS))()
+        self.clib_float32.xrl_debug_train_counters(out, len(self.TRAIN_COUNTERS))
+        self._check()
+        return dict(zip(self.TRAIN_COUNTERS, (int(v) for v in out)))
 
     # ------------------------------------------------------------------ label clustering (K11)
     def run_clustering(self, py_feat_mat, train_params, codes=None):

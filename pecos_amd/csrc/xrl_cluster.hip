@@ -253,7 +253,7 @@ __global__ void __launch_bounds__(256) k11_norm(K11Level a, const uint64_t* __re
         float p = 0.0f;
         if (x < e) { const float v = c[order ? (uint32_t)order[(uint64_t)side * a.runs + x] : x]; p = __fmul_rn(v, v); }
         const uint32_t n = min(64u, e - x0);
-        for (uint32_t j = 0; j < n; ++j) acc = __fadd_rn(acc, __shfl(p, (int)j));
+        acc = wave_chain(acc, p, n);
     }
     if (lane == 0) scale[w] = acc > 0.0f ? 1.0 / sqrt((double)acc) : 0.0;
 }

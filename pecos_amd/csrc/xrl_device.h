@@ -151,6 +151,17 @@ __device__ __forceinline__ void row_span(const uint64_t* ptr, uint64_t r, uint64
     b = b0 < e ? b0 : e;
 }
 
+// The chain served by a wavefront (K11's norms, K12's row sums, K13's dot products and x'x): acc + p(lane 0) + p(lane 1) + ... over the
+// first n <= 64 lanes, ONE rounded addition after the other in lane order -- the order a host loop over the stored entries adds in.
+__device__ __forceinline__ float wave_chain(float acc, float p, uint32_t n) {
+    for (uint32_t j = 0; j < n; ++j) acc = __fadd_rn(acc, __shfl(p, (int)j));
+    return acc;
+}
+__device__ __forceinline__ double wave_chain(double acc, double p, uint32_t n) {
+    for (uint32_t j = 0; j < n; ++j) acc = __dadd_rn(acc, __shfl(p, (int)j));
+    return acc;
+}
+
 template <int N>
 __device__ __forceinline__ uint32_t wave_count_ge(const uint32_t (&key)[N], uint32_t t) {
     uint32_t c = 0;

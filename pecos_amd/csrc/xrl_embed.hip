@@ -183,7 +183,7 @@ k12_normalize(const uint64_t* __restrict__ ptr, const float* val, float* out, ui
             const unsigned long long mn = __ballot(v != v);
             if (!tn && mn) tn = (uint32_t)__shfl((int)__float_as_uint(v), __ffsll((long long)mn) - 1) | kQuiet;
             const uint32_t n = (uint32_t)min((uint64_t)64u, we - x0);
-            for (uint32_t j = 0; j < n; ++j) t = __dadd_rn(t, __shfl(p, (int)j));
+            t = wave_chain(t, p, n);
         }
         if ((int)lane == i) { s = t; nanb = tn; }
     }

@@ -1,0 +1,645 @@
+// K13: ranker training.  One (cluster, label) job of the reference's multilabel_train_with_codes (linear_solver.hpp:797-860) is the dual
+// coordinate descent of solve_l2r_l1l2_svc (:420-528) over the instances init_worker (:667-712) lists, and its weights pass the emission
+// of SVMJob::solve (:718-779).  The rule is stated in include/xrl_abi.h.
+//   k13_check        ids of a CSR below a bound, optionally strictly ascending per row, row pointers monotone
+//   k13_same         two row pointers / id arrays are the same (R against Y)
+//   k13_labels       a label listed twice in C
+//   k13_sizes        the longest M and Y columns and the largest sums of feature-row lengths over them: the sizes of a slot and of a staging row
+//   k13_solve        ONE WAVEFRONT OWNS ONE JOB AT A TIME and takes the next from a counter by an atomic add; no wavefront waits on another.
+//                    Its slot of scratch: the dense w [cols] with a bitmap of the features its instances touch, and index / alpha / QD /
+//                    cost / y per instance.  Per coordinate the lanes load the row 64 pairs a step, gather w, round the fp32 products and
+//                    add them as ONE chain in stored order; every lane computes the same fp64 scalars; the lanes apply the axpy in parallel
+//                    (a row's ids are strictly ascending, so no two lanes meet).  The shuffle and the order of the coordinates are serial
+//                    by the rule: lane 0 shuffles, reading the shared table of mt19937(0) outputs through the job's own cursor.  A job that
+//                    reaches the table's end cleans its slot, is put on the redo list and ends; the host extends the table and the listed
+//                    jobs run again from their start.  Loop bounds: a sweep visits at most `active` coordinates (each visit advances or
+//                    shrinks), sweeps <= max_iter, a draw's rejections end with the table.
+//   k13_label_counts, k13_place   the jobs' staged rows -> W^T by label
+#include <cstdlib>
+#include <random>
+
+#include "xrl_device.h"
+#include "xrl_devprim.h"
+#include "xrl_train.h"
+
+namespace xrl {
+
+namespace {
+
+constexpr const char* kWhat = "K13";
+
+enum : uint32_t { kBadPtr = 1u, kBadId = 2u, kUnsorted = 4u, kDiffers = 8u, kTwice = 16u, kStageFull = 32u };
+
+// What a wavefront's lanes wrote to HBM is visible to its other lanes afterwards.  A slot is touched by ONE wavefront, so workgroup scope
+// is all that is needed: the workgroup's CU has one vector L1, write-through, which its own stores and atomics keep coherent, so the fence
+// is a drain of the memory counters and no cache is invalidated.  Nothing in a slot is ever read by another workgroup during the launch.
+__device__ __forceinline__ void wave_sync_hbm() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ uint32_t first_lane(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+__global__ void __launch_bounds__(256)
+k13_check(const uint64_t* __restrict__ ptr, const uint32_t* __restrict__ idx, uint32_t rows, uint64_t nnz, uint32_t bound, int sorted, uint32_t* __restrict__ flags) {
+    const uint32_t r = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (r >= rows) return;
+    const uint64_t b = ptr[r], e = ptr[r + 1];
+    uint32_t bad = 0;
+    if (b > e || e > nnz || (r == 0 && b != 0) || (r + 1 == rows && e != nnz)) bad |= kBadPtr;
+    else
+        for (uint64_t x = b + lane; x < e; x += 64u) {
+            const uint32_t f = idx[x];
+            if (f >= bound) bad |= kBadId;
+            if (sorted && x > b && idx[x - 1] >= f) bad |= kUnsorted;
+        }
+    if (bad) atomicOr(flags, bad);
+}
+
+__global__ void __launch_bounds__(256)
+k13_same(const uint64_t* __restrict__ pa, const uint64_t* __restrict__ pb, uint64_t np, const uint32_t* __restrict__ ia, const uint32_t* __restrict__ ib, uint64_t ni,
+         uint32_t* __restrict__ flags) {
+    const uint64_t x = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if ((x < np && pa[x] != pb[x]) || (x < ni && ia[x] != ib[x])) atomicOr(flags, (uint32_t)kDiffers);
+}
+
+__global__ void __launch_bounds__(256) k13_labels(const uint32_t* __restrict__ c_idx, uint64_t n, uint32_t* __restrict__ seen, uint32_t* __restrict__ flags) {
+    const uint64_t x = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (x < n && atomicAdd(&seen[c_idx[x]], 1u)) atomicOr(flags, (uint32_t)kTwice);
+}
+
+// rows [0, m_rows) of M^T then rows of Y^T: out[0] / out[2] <- the longest row, out[1] / out[3] <- the largest sum of the feature-row lengths of a row's instances
+__global__ void __launch_bounds__(256)
+k13_sizes(const uint64_t* __restrict__ m_ptr, const uint32_t* __restrict__ m_idx, uint32_t m_rows, const uint64_t* __restrict__ y_ptr, const uint32_t* __restrict__ y_idx,
+          uint32_t y_rows, const uint64_t* __restrict__ x_ptr, unsigned long long* __restrict__ out) {
+    const uint32_t r0 = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (r0 >= m_rows + y_rows) return;
+    const bool isy = r0 >= m_rows;
+    const uint32_t r = isy ? r0 - m_rows : r0;
+    const uint64_t* ptr = isy ? y_ptr : m_ptr;
+    const uint32_t* idx = isy ? y_idx : m_idx;
+    const uint64_t b = ptr[r], e = ptr[r + 1];
+    unsigned long long sum = 0;
+    for (uint64_t x = b + lane; x < e; x += 64u) { const uint32_t i = idx[x]; sum += x_ptr[i + 1] - x_ptr[i]; }
+    for (int d = 1; d < 64; d <<= 1) sum += __shfl_xor(sum, d, 64);
+    if (lane == 0) { atomicMax(&out[isy ? 2 : 0], (unsigned long long)(e - b)); atomicMax(&out[isy ? 3 : 1], sum); }
+}
+
+struct K13Args {
+    const uint64_t* x_ptr; const uint32_t* x_idx; const float* x_val; uint64_t x_nnz; uint32_t N, d;
+    const uint64_t* y_ptr; const uint32_t* y_idx; const float* r_val; uint64_t y_nnz;
+    const uint64_t* c_ptr; const uint32_t* c_idx; uint32_t K;            // null: job j is label j, its instances are all rows
+    const uint64_t* m_ptr; const uint32_t* m_idx; uint64_t m_nnz;
+    double threshold, Cp, Cn, eps, bias;
+    uint32_t max_nz; int l2loss; uint64_t max_iter;
+    // a slot's scratch, [slot * its size]
+    uint32_t* index; uint32_t index_cap; float* alpha; float* qd; float* cost; signed char* ysg; float* w; uint32_t* touched; uint32_t dw;
+    const uint32_t* table; uint64_t table_n;
+    const uint32_t* job_list; uint32_t job0, n_jobs; uint32_t* next;      // job_list null: jobs job0 .. job0 + n_jobs - 1
+    uint32_t* st_idx; float* st_val; uint32_t stride;                     // staging row of job j: (j - job0) * stride
+    unsigned long long* cnt; uint32_t* job_label;                         // per job
+    uint32_t* redo; uint32_t* n_redo; uint32_t* flags;
+    unsigned long long* counters;                                          // iters, shrinks, reactivations, max_iter stops, clipped, lane rows, wave rows
+};
+
+// one uniform draw in [0, range), 1 <= range < 2^32: libstdc++'s uniform_int_distribution over a 32-bit generator (_S_nd: Lemire's
+// multiply with the (-range) % range rejection).  false: the table ended.
+__device__ __forceinline__ bool k13_draw(const uint32_t* __restrict__ table, uint64_t tn, uint64_t& cur, uint32_t range, uint32_t& out) {
+    if (cur >= tn) return false;
+    uint64_t prod = (uint64_t)table[cur++] * range;
+    uint32_t low = (uint32_t)prod;
+    if (low < range) {
+        const uint32_t thr = (0u - range) % range;
+        while (low < thr) {
+            if (cur >= tn) return false;
+            prod = (uint64_t)table[cur++] * range;
+            low = (uint32_t)prod;
+        }
+    }
+    out = (uint32_t)(prod >> 32);
+    return true;
+}
+
+__device__ __forceinline__ void k13_swap(uint32_t* a, uint32_t i, uint32_t j) { const uint32_t t = a[i]; a[i] = a[j]; a[j] = t; }
+
+// libstdc++'s std::shuffle (bits/stl_algo.h) of a[0, n) by one lane
+__device__ bool k13_shuffle(uint32_t* a, uint32_t n, const uint32_t* __restrict__ table, uint64_t tn, uint64_t& cur) {
+    if (n < 2) return true;
+    uint32_t r;
+    if (n <= 65535u) {
+        uint32_t i = 1;
+        if ((n & 1u) == 0) {
+            if (!k13_draw(table, tn, cur, 2u, r)) return false;
+            k13_swap(a, 1, r);
+            i = 2;
+        }
+        for (; i < n; i += 2) {
+            const uint32_t sr = i + 1u;
+            if (!k13_draw(table, tn, cur, sr * (sr + 1u), r)) return false;
+            k13_swap(a, i, r / (sr + 1u));
+            k13_swap(a, i + 1, r % (sr + 1u));
+        }
+        return true;
+    }
+    for (uint32_t i = 1; i < n; ++i) {
+        if (!k13_draw(table, tn, cur, i + 1u, r)) return false;
+        k13_swap(a, i, r);
+    }
+    return true;
+}
+
+__device__ __forceinline__ uint32_t k13_word_mask(uint32_t wd, uint32_t d) { return (uint64_t)wd * 32u + 32u <= d ? 0xFFFFFFFFu : (1u << (d - wd * 32u)) - 1u; }
+
+// (|w| bits, lower feature first) of a staged entry: the larger key is kept first
+__device__ __forceinline__ uint64_t k13_key(float v, uint32_t f) { return ((uint64_t)(__float_as_uint(v) & 0x7FFFFFFFu) << 32) | (0xFFFFFFFFu - f); }
+
+__device__ void k13_job(const K13Args& a, uint32_t job, uint32_t slot, uint32_t lane, unsigned long long (&ctr)[7]) {
+    uint32_t* index = a.index + (uint64_t)slot * a.index_cap;
+    float* alpha = a.alpha + (uint64_t)slot * a.N;
+    float* qd = a.qd + (uint64_t)slot * a.N;
+    float* cost = a.cost + (uint64_t)slot * a.N;
+    signed char* ysg = a.ysg + (uint64_t)slot * a.N;
+    float* w = a.w + (uint64_t)slot * a.d;
+    uint32_t* touched = a.touched + (uint64_t)slot * a.dw;
+    const double bias2 = a.bias > 0 ? a.bias * a.bias : 0.0;
+    unsigned long long before[7];
+    for (int k = 0; k < 7; ++k) before[k] = ctr[k];
+
+    uint32_t label = job, code = 0;
+    if (a.c_ptr) { label = a.c_idx[job]; code = segment_of(a.c_ptr, a.K, (uint64_t)job); }
+
+    // ---- the instances (init_worker): M's column as stored, then Y's positives that are not among them, as stored
+    uint32_t n = 0;
+    if (a.m_ptr) {
+        uint64_t mb, me;
+        row_span(a.m_ptr, code, a.m_nnz, mb, me);
+        for (uint64_t x = mb + lane; x < me; x += 64u) {
+            const uint32_t i = a.m_idx[x];
+            index[x - mb] = i; cost[i] = 1.0f; ysg[i] = -1;
+        }
+        n = (uint32_t)(me - mb);
+    } else {
+        for (uint32_t i = lane; i < a.N; i += 64u) { index[i] = i; cost[i] = 1.0f; ysg[i] = -1; }
+        n = a.N;
+    }
+    wave_sync_hbm();
+    {
+        uint64_t yb, ye;
+        row_span(a.y_ptr, label, a.y_nnz, yb, ye);
+        for (uint64_t x0 = yb; x0 < ye; x0 += 64u) {
+            const uint64_t x = x0 + lane;
+            bool fresh = false;
+            uint32_t i = 0;
+            if (x < ye) {
+                i = a.y_idx[x];
+                const float c = a.r_val ? a.r_val[x] : 1.0f;
+                const uint32_t old = atomicExch(reinterpret_cast<uint32_t*>(&cost[i]), __float_as_uint(c));
+                ysg[i] = 1;
+                fresh = __uint_as_float(old) == 0.0f;
+            }
+            const unsigned long long m = __ballot(fresh);
+            const uint32_t at = n + lanes_below(m);
+            if (fresh && at < a.index_cap) index[at] = i;
+            n += (uint32_t)__popcll(m);
+        }
+        if (n > a.index_cap) n = a.index_cap;                          // (cannot happen: the cap is the longest M column plus the longest Y column)
+    }
+    wave_sync_hbm();
+
+    // ---- QD = diag + x'x + bias^2, alpha = 0, and the features the job can touch
+    for (uint32_t s0 = 0; s0 < n; s0 += 64u) {
+        const uint32_t s = s0 + lane;
+        const bool have = s < n;
+        uint32_t i = 0;
+        uint64_t b = 0, e = 0;
+        if (have) { i = index[s]; row_span(a.x_ptr, i, a.x_nnz, b, e); }
+        const bool wide = have && e - b >= kTrainWaveRow;
+        float acc = 0.0f;
+        if (have && !wide)
+            for (uint64_t j = b; j < e; ++j) {
+                const float v = a.x_val[j];
+                const uint32_t f = a.x_idx[j];
+                acc = __fadd_rn(acc, __fmul_rn(v, v));
+                atomicOr(&touched[f >> 5], 1u << (f & 31u));
+            }
+        unsigned long long wm = __ballot(wide);
+        ctr[5] += (unsigned long long)__popcll(__ballot(have && !wide));
+        ctr[6] += (unsigned long long)__popcll(wm);
+        while (wm) {                                                   // at most 64 turns
+            const int l = __builtin_ctzll(wm);
+            wm &= wm - 1;
+            const uint64_t bb = __shfl(b, l), ee = __shfl(e, l);
+            float ws = 0.0f;
+            for (uint64_t x0 = bb; x0 < ee; x0 += 64u) {
+                const uint64_t x = x0 + lane;
+                float p = 0.0f;
+                if (x < ee) {
+                    const float v = a.x_val[x];
+                    const uint32_t f = a.x_idx[x];
+                    p = __fmul_rn(v, v);
+                    atomicOr(&touched[f >> 5], 1u << (f & 31u));
+                }
+                ws = wave_chain(ws, p, (uint32_t)min((uint64_t)64u, ee - x0));
+            }
+            if ((int)lane == l) acc = ws;
+        }
+        if (have) {
+            const double cc = (ysg[i] > 0 ? a.Cp : a.Cn) * (double)cost[i];
+            float q = a.l2loss ? (float)(0.5 / cc) : 0.0f;
+            q = (float)__dadd_rn((double)q, __dadd_rn((double)acc, bias2));
+            qd[i] = q; alpha[i] = 0.0f;
+        }
+    }
+    wave_sync_hbm();
+
+    // ---- the sweeps
+    const double kInf = HUGE_VAL;
+    double pgmax_old = kInf, pgmin_old = -kInf;
+    uint32_t active = n;
+    uint64_t iter = 0, cur = 0;
+    float bw = 0.0f;
+    bool table_end = false, converged = false;
+    while (iter < a.max_iter) {
+        double pgmax_new = -kInf, pgmin_new = kInf;
+        uint32_t ok = 1;
+        if (lane == 0) ok = k13_shuffle(index, active, a.table, a.table_n, cur) ? 1u : 0u;
+        if (!first_lane(ok)) { table_end = true; break; }
+        for (uint32_t s = 0; s < active;) {                            // every turn advances s or lowers active
+            uint32_t i = 0, ab = 0;
+            if (lane == 0) { i = index[s]; ab = __float_as_uint(alpha[i]); }
+            i = first_lane(i);
+            const float al = __uint_as_float(first_lane(ab));
+            const int yi = ysg[i];
+            uint64_t rb, re;
+            row_span(a.x_ptr, i, a.x_nnz, rb, re);
+            float acc = 0.0f;
+            for (uint64_t x0 = rb; x0 < re; x0 += 64u) {
+                const uint64_t x = x0 + lane;
+                float p = 0.0f;
+                if (x < re) p = __fmul_rn(w[a.x_idx[x]], a.x_val[x]);
+                acc = wave_chain(acc, p, (uint32_t)min((uint64_t)64u, re - x0));
+            }
+            const double cc = (yi > 0 ? a.Cp : a.Cn) * (double)cost[i];
+            const double diag = a.l2loss ? 0.5 / cc : 0.0, C = a.l2loss ? kInf : cc;
+            double G = __dadd_rn(__dmul_rn((double)yi, __dadd_rn((double)acc, a.bias > 0 ? __dmul_rn((double)bw, a.bias) : 0.0)), -1.0);
+            G = __dadd_rn(G, __dmul_rn((double)al, diag));
+            double PG = 0.0;
+            bool shrink = false;
+            if (al == 0.0f) {
+                if (G > pgmax_old) shrink = true;
+                else if (G < 0.0) PG = G;
+            } else if ((double)al == C) {
+                if (G < pgmin_old) shrink = true;
+                else if (G > 0.0) PG = G;
+            } else {
+                PG = G;
+            }
+            if (shrink) {
+                --active;
+                if (lane == 0) k13_swap(index, s, active);
+                ++ctr[1];
+                continue;
+            }
+            pgmax_new = pgmax_new < PG ? PG : pgmax_new;              // std::max(a, b) = a < b ? b : a
+            pgmin_new = PG < pgmin_new ? PG : pgmin_new;              // std::min(a, b) = b < a ? b : a
+            if (fabs(PG) > 1.0e-12) {
+                const double ao = (double)al;
+                double t = __dadd_rn(ao, -(G / (double)qd[i]));
+                t = t < 0.0 ? 0.0 : t;
+                if (C < t) { t = C; ++ctr[4]; }
+                const float an = (float)t;
+                const double dd = __dmul_rn(__dadd_rn((double)an, -ao), (double)yi);
+                for (uint64_t x = rb + lane; x < re; x += 64u) {
+                    const uint32_t f = a.x_idx[x];
+                    w[f] = (float)__dadd_rn((double)w[f], __dmul_rn(dd, (double)a.x_val[x]));
+                }
+                if (a.bias > 0) bw = (float)__dadd_rn((double)bw, __dmul_rn(dd, a.bias));
+                if (lane == 0) alpha[i] = an;
+                wave_sync_hbm();
+            }
+            ++s;
+        }
+        ++iter;
+        if (pgmax_new - pgmin_new <= a.eps) {
+            if (active == n) { converged = true; break; }
+            active = n; pgmax_old = kInf; pgmin_old = -kInf;
+            ++ctr[2];
+            continue;
+        }
+        pgmax_old = pgmax_new; pgmin_old = pgmin_new;
+        if (pgmax_old <= 0) pgmax_old = kInf;
+        if (pgmin_old >= 0) pgmin_old = -kInf;
+    }
+    ctr[0] += iter;
+    if (!converged && !table_end) ++ctr[3];
+    wave_sync_hbm();                                                   // lane 0's last swaps of index, and the last axpy, before every lane reads them below
+
+    // ---- emission (SVMJob::solve): the entries with |w| >= threshold by ascending feature into the job's staging row; w and the bitmap
+    //      go back to zero on the way.  A job the table failed stages nothing.
+    const uint32_t bj = job - a.job0;
+    uint32_t* sidx = a.st_idx + (uint64_t)bj * a.stride;
+    float* sval = a.st_val + (uint64_t)bj * a.stride;
+    const bool every = a.threshold <= 0.0;
+    uint32_t c = 0, full = 0;
+    for (uint32_t w0 = 0; w0 < a.dw; w0 += 64u) {
+        const uint32_t wd = w0 + lane;
+        uint32_t bits = 0;
+        if (wd < a.dw) {
+            bits = touched[wd];
+            if (bits) touched[wd] = 0u;
+            if (every) bits = k13_word_mask(wd, a.d);
+        }
+        uint32_t mine = 0;
+        if (!table_end)
+            for (uint32_t bb = bits; bb; bb &= bb - 1u) mine += (double)fabsf(w[wd * 32u + (uint32_t)__builtin_ctz(bb)]) >= a.threshold ? 1u : 0u;
+        uint32_t incl = mine;
+        for (int dlt = 1; dlt < 64; dlt <<= 1) { const uint32_t t = __shfl_up(incl, dlt, 64); if ((int)lane >= dlt) incl += t; }
+        uint32_t at = c + incl - mine;
+        for (uint32_t bb = bits; bb; bb &= bb - 1u) {
+            const uint32_t f = wd * 32u + (uint32_t)__builtin_ctz(bb);
+            const float v = w[f];
+            w[f] = 0.0f;
+            if (!table_end && (double)fabsf(v) >= a.threshold) {
+                if (at < a.stride) { sidx[at] = f; sval[at] = v; } else full = 1;
+                ++at;
+            }
+        }
+        c += (uint32_t)__shfl(incl, 63);
+    }
+    // the instances' marks
+    for (uint32_t s = lane; s < n; s += 64u) cost[index[s]] = 0.0f;
+    wave_sync_hbm();
+    if (__ballot(full)) { if (lane == 0) atomicOr(a.flags, (uint32_t)kStageFull); c = min(c, a.stride); }
+    if (table_end) {                                                   // the job runs again from its start: this attempt is not counted
+        if (lane == 0) a.redo[atomicAdd(a.n_redo, 1u)] = job;
+        for (int k = 0; k < 7; ++k) ctr[k] = before[k];
+        return;
+    }
+    bool push_bias = a.bias > 0 && (double)fabsf(bw) >= a.threshold;
+    if (a.max_nz && c >= a.max_nz) {
+        // the max_nz largest |w|, ties to the lower feature: T = the max_nz-th largest key, by bisection over the key's value (64 steps)
+        unsigned long long lo = 0, hi = ~0ull;
+        while (lo < hi) {
+            const unsigned long long mid = lo + ((hi - lo) >> 1) + 1ull;
+            uint32_t ge = 0;
+            for (uint32_t x0 = 0; x0 < c; x0 += 64u) {
+                const uint32_t x = x0 + lane;
+                ge += (uint32_t)__popcll(__ballot(x < c && k13_key(sval[x], sidx[x]) >= mid));
+            }
+            if (ge >= a.max_nz) lo = mid; else hi = mid - 1ull;
+        }
+        // the bias competes with the least kept feature (:764-773)
+        const float least = __uint_as_float((uint32_t)(lo >> 32));
+        bool drop_least = false;
+        if (a.bias > 0) {
+            if (fabsf(bw) > least) drop_least = true; else push_bias = false;
+        }
+        uint32_t kept = 0;
+        for (uint32_t x0 = 0; x0 < c; x0 += 64u) {
+            const uint32_t x = x0 + lane;
+            uint32_t f = 0;
+            float v = 0.0f;
+            bool keep = false;
+            if (x < c) { f = sidx[x]; v = sval[x]; const unsigned long long k = k13_key(v, f); keep = drop_least ? k > lo : k >= lo; }
+            const unsigned long long m = __ballot(keep);
+            if (keep) { sidx[kept + lanes_below(m)] = f; sval[kept + lanes_below(m)] = v; }
+            kept += (uint32_t)__popcll(m);
+            wave_sync_hbm();
+        }
+        c = kept;
+    }
+    if (push_bias) {
+        if (c < a.stride) { if (lane == 0) { sidx[c] = a.d; sval[c] = bw; } ++c; }
+        else if (lane == 0) atomicOr(a.flags, (uint32_t)kStageFull);
+    }
+    if (lane == 0) { a.cnt[job] = c; a.job_label[job] = label; }
+}
+
+__global__ void __launch_bounds__(64) k13_solve(K13Args a) {
+    const uint32_t lane = threadIdx.x, slot = blockIdx.x;
+    unsigned long long ctr[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (;;) {                                                         // at most n_jobs + 1 turns
+        uint32_t t = 0;
+        if (lane == 0) t = atomicAdd(a.next, 1u);
+        t = first_lane(t);
+        if (t >= a.n_jobs) break;
+        k13_job(a, a.job_list ? a.job_list[t] : a.job0 + t, slot, lane, ctr);
+    }
+    if (lane == 0)
+        for (int k = 0; k < 7; ++k)
+            if (ctr[k]) atomicAdd(&a.counters[k], ctr[k]);
+}
+
+__global__ void __launch_bounds__(256)
+k13_label_counts(const unsigned long long* __restrict__ cnt, const uint32_t* __restrict__ job_label, uint32_t jobs, uint32_t labels, unsigned long long* __restrict__ by_label) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j < jobs && job_label[j] < labels) by_label[job_label[j]] = cnt[j];
+}
+
+// one wavefront per job of a chunk: its row, compacted at src[j] .. src[j + 1], goes to the row of its label
+__global__ void __launch_bounds__(256)
+k13_place(const unsigned long long* __restrict__ src, const uint32_t* __restrict__ job_label, uint32_t n, uint32_t labels, const uint32_t* __restrict__ c_idx,
+          const float* __restrict__ c_val, const unsigned long long* __restrict__ out_ptr, uint32_t* __restrict__ idx, float* __restrict__ val) {
+    const uint32_t j = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (j >= n || job_label[j] >= labels) return;
+    const unsigned long long b = src[j], len = src[j + 1] - b, dst = out_ptr[job_label[j]];
+    for (unsigned long long x = threadIdx.x & 63u; x < len; x += 64u) { idx[dst + x] = c_idx[b + x]; val[dst + x] = c_val[b + x]; }
+}
+
+uint64_t env_u64(const char* name, uint64_t dflt) {
+    if (const char* e = std::getenv(name)) { const uint64_t v = std::strtoull(e, nullptr, 10); if (v) return v; }
+    return dflt;
+}
+
+uint32_t read_flags(const DevBuf& flags, hipStream_t s) {
+    uint32_t f = 0;
+    XRL_HIP(hipMemcpyAsync(&f, flags.p, 4, hipMemcpyDeviceToHost, s));
+    XRL_HIP(hipStreamSynchronize(s));
+    return f;
+}
+
+void check_csr(const std::string& what, const char* name, const QueriesDev& m, uint32_t bound, bool sorted, DevBuf& flags, hipStream_t s) {
+    if (!m.rows) { if (m.nnz) fail(what + name + " has stored entries and no rows"); return; }
+    hipLaunchKernelGGL(k13_check, dim3(blocks_of(m.rows, 4, kWhat)), dim3(256), 0, s, m.row_ptr, m.col_idx, m.rows, m.nnz, bound, sorted ? 1 : 0, flags.as<uint32_t>());
+    XRL_LAUNCH_CHECK();
+    const uint32_t f = read_flags(flags, s);
+    if (f & kBadPtr) fail(what + name + "'s row pointer does not ascend from 0 to its count of stored entries");
+    if (f & kBadId) fail(what + name + " holds an id that is not below " + std::to_string(bound));
+    if (f & kUnsorted) fail(what + name + " has a row whose column ids are not strictly ascending");
+}
+
+struct Chunk { DevBuf ptr, idx, val; uint32_t job0 = 0, n = 0; };
+
+}  // namespace
+
+void same_pattern_device(const char* what, const QueriesDev& A, const QueriesDev& B, hipStream_t s) {
+    DevBuf flags;
+    flags.reserve(4);
+    XRL_HIP(hipMemsetAsync(flags.p, 0, 4, s));
+    const uint64_t np = (uint64_t)A.rows + 1, n = std::max(np, A.nnz);
+    hipLaunchKernelGGL(k13_same, dim3(blocks_of(n, 256, kWhat)), dim3(256), 0, s, A.row_ptr, B.row_ptr, np, A.col_idx, B.col_idx, A.nnz, flags.as<uint32_t>());
+    XRL_LAUNCH_CHECK();
+    if (read_flags(flags, s) & kDiffers) fail(std::string(what) + ": Rt does not share Yt's pattern (row pointer and column ids)");
+}
+
+void check_train_params(const std::string& what, const TrainParams& p) {
+    if (p.solver_type == 7) fail(what + "solver L2R_LR_DUAL is not served on the device (its Newton steps and logarithms are not part of K13)");
+    if (p.solver_type == 2) fail(what + "solver L2R_L2LOSS_SVC_PRIMAL is not served on the device (its Newton method is not part of K13)");
+    if (p.solver_type != kSolverL2LossDual && p.solver_type != kSolverL1LossDual)
+        fail(what + "unknown solver_type " + std::to_string(p.solver_type) + " (1 = L2R_L2LOSS_SVC_DUAL, 3 = L2R_L1LOSS_SVC_DUAL)");
+}
+
+void train_layer_device(const char* what_c, const QueriesDev& X, const QueriesDev& Yt, const float* r_val, const QueriesDev* Ct, const QueriesDev* Mt,
+                        const TrainParams& p, hipStream_t s, DevCsr& out, TrainCounters& T) {
+    const std::string what = std::string(what_c) + ": ";
+    check_train_params(what, p);
+    const bool coded = Ct && Mt;
+    const uint32_t N = X.rows, d = X.cols, L = Yt.rows;
+    const uint64_t jobs64 = coded ? Ct->nnz : L;
+    if (jobs64 >= 0xFFFFFFFFull) fail(what + "2^32 - 1 jobs or more");
+    const uint32_t jobs = (uint32_t)jobs64;
+
+    DevBuf flags, tmp;
+    flags.reserve(4);
+    XRL_HIP(hipMemsetAsync(flags.p, 0, 4, s));
+    check_csr(what, "X", X, d, true, flags, s);
+    check_csr(what, "Y", Yt, N, false, flags, s);
+    if (coded) {
+        check_csr(what, "C", *Ct, L, false, flags, s);
+        check_csr(what, "M", *Mt, N, false, flags, s);
+        DevBuf seen;
+        seen.reserve((size_t)L * 4 + 4);
+        XRL_HIP(hipMemsetAsync(seen.p, 0, (size_t)L * 4 + 4, s));
+        if (Ct->nnz) {
+            hipLaunchKernelGGL(k13_labels, dim3(blocks_of(Ct->nnz, 256, kWhat)), dim3(256), 0, s, Ct->col_idx, Ct->nnz, seen.as<uint32_t>(), flags.as<uint32_t>());
+            XRL_LAUNCH_CHECK();
+        }
+        if (read_flags(flags, s) & kTwice) fail(what + "a label is listed under two columns of C (or twice in one); a label has one weight vector");
+    }
+
+    // sizes of a slot and of a staging row
+    DevBuf sizes;
+    sizes.reserve(32);
+    XRL_HIP(hipMemsetAsync(sizes.p, 0, 32, s));
+    {
+        const uint32_t mr = coded ? Mt->rows : 0u;
+        if (mr + L) {
+            hipLaunchKernelGGL(k13_sizes, dim3(blocks_of((uint64_t)mr + L, 4, kWhat)), dim3(256), 0, s, coded ? Mt->row_ptr : nullptr, coded ? Mt->col_idx : nullptr, mr,
+                               Yt.row_ptr, Yt.col_idx, L, X.row_ptr, sizes.as<unsigned long long>());
+            XRL_LAUNCH_CHECK();
+        }
+    }
+    uint64_t sz[4];
+    XRL_HIP(hipMemcpyAsync(sz, sizes.p, 32, hipMemcpyDeviceToHost, s));
+    XRL_HIP(hipStreamSynchronize(s));
+    const uint64_t index_cap64 = coded ? sz[0] + sz[2] : (uint64_t)N;
+    if (index_cap64 >= (1ull << 31)) fail(what + "a job of 2^31 instances or more");
+    const uint32_t index_cap = (uint32_t)(index_cap64 ? index_cap64 : 1);
+    const uint64_t touched_max = coded ? sz[1] + sz[3] : X.nnz;
+    const uint64_t stride64 = (p.threshold <= 0.0 ? (uint64_t)d : std::min<uint64_t>(d, touched_max)) + 1;
+    const uint32_t stride = (uint32_t)stride64;
+    const uint32_t dw = (d + 31u) / 32u;
+
+    const uint64_t budget = env_u64("XRL_TRAIN_SCRATCH_BYTES", kTrainScratchBytes);
+    const uint64_t slot_bytes = (uint64_t)index_cap * 4 + (uint64_t)N * 13 + (uint64_t)d * 4 + (uint64_t)dw * 4;
+    const uint32_t slots = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({budget / std::max<uint64_t>(slot_bytes, 1), kTrainMaxSlots, std::max<uint32_t>(jobs, 1)}));
+    const uint32_t batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(budget / (stride64 * 8), std::max<uint32_t>(jobs, 1)));
+    T.jobs = jobs; T.slots = slots; T.stride = stride;
+
+    DevBuf b_index, b_alpha, b_qd, b_cost, b_y, b_w, b_touched, b_next, b_stidx, b_stval, b_cnt, b_label, b_redo, b_ctr, b_table, b_list;
+    b_index.reserve((size_t)slots * index_cap * 4);
+    b_alpha.reserve((size_t)slots * N * 4); b_qd.reserve((size_t)slots * N * 4); b_cost.reserve((size_t)slots * N * 4); b_y.reserve((size_t)slots * N);
+    b_w.reserve((size_t)slots * d * 4); b_touched.reserve((size_t)slots * dw * 4);
+    // a slot is clean between jobs: cost, w and the bitmap are zero (every job leaves them so)
+    if (N) XRL_HIP(hipMemsetAsync(b_cost.p, 0, (size_t)slots * N * 4, s));
+    if (d) XRL_HIP(hipMemsetAsync(b_w.p, 0, (size_t)slots * d * 4, s));
+    if (d) XRL_HIP(hipMemsetAsync(b_touched.p, 0, (size_t)slots * dw * 4, s));
+    b_next.reserve(8);                                                 // {next job, redo count}
+    b_stidx.reserve((size_t)batch * stride * 4); b_stval.reserve((size_t)batch * stride * 4);
+    b_cnt.reserve(((size_t)jobs + 1) * 8); b_label.reserve(((size_t)jobs + 1) * 4);
+    XRL_HIP(hipMemsetAsync(b_cnt.p, 0, ((size_t)jobs + 1) * 8, s));
+    XRL_HIP(hipMemsetAsync(b_label.p, 0xFF, ((size_t)jobs + 1) * 4, s));
+    b_redo.reserve((size_t)batch * 4); b_list.reserve((size_t)batch * 4);
+    b_ctr.reserve(7 * 8);
+    XRL_HIP(hipMemsetAsync(b_ctr.p, 0, 7 * 8, s));
+
+    // the one stream every job reads: std::mt19937(0), filled and extended by the host
+    std::mt19937 gen(0);
+    std::vector<uint32_t> table;
+    auto grow_table = [&](uint64_t words) {
+        const size_t from = table.size();
+        table.resize((size_t)words);
+        for (size_t k = from; k < table.size(); ++k) table[k] = (uint32_t)gen();
+        b_table.release();
+        b_table.upload(table);
+    };
+    grow_table(env_u64("XRL_TRAIN_RANDOM_WORDS", kTrainRandomWords));
+
+    K13Args a{};
+    a.x_ptr = X.row_ptr; a.x_idx = X.col_idx; a.x_val = X.val; a.x_nnz = X.nnz; a.N = N; a.d = d;
+    a.y_ptr = Yt.row_ptr; a.y_idx = Yt.col_idx; a.r_val = r_val; a.y_nnz = Yt.nnz;
+    if (coded) { a.c_ptr = Ct->row_ptr; a.c_idx = Ct->col_idx; a.K = Ct->rows; a.m_ptr = Mt->row_ptr; a.m_idx = Mt->col_idx; a.m_nnz = Mt->nnz; }
+    a.threshold = p.threshold; a.Cp = p.Cp; a.Cn = p.Cn; a.eps = p.eps; a.bias = p.bias;
+    a.max_nz = p.max_nonzeros; a.l2loss = p.solver_type == kSolverL2LossDual; a.max_iter = p.max_iter;
+    a.index = b_index.as<uint32_t>(); a.index_cap = index_cap; a.alpha = b_alpha.as<float>(); a.qd = b_qd.as<float>(); a.cost = b_cost.as<float>();
+    a.ysg = b_y.as<signed char>(); a.w = b_w.as<float>(); a.touched = b_touched.as<uint32_t>(); a.dw = dw;
+    a.next = b_next.as<uint32_t>(); a.n_redo = b_next.as<uint32_t>() + 1;
+    a.st_idx = b_stidx.as<uint32_t>(); a.st_val = b_stval.as<float>(); a.stride = stride;
+    a.cnt = b_cnt.as<unsigned long long>(); a.job_label = b_label.as<uint32_t>();
+    a.redo = b_redo.as<uint32_t>(); a.flags = flags.as<uint32_t>(); a.counters = b_ctr.as<unsigned long long>();
+
+    std::vector<Chunk> chunks;
+    for (uint32_t j0 = 0; j0 < jobs; j0 += batch) {
+        const uint32_t nb = std::min(batch, jobs - j0);
+        ++T.batches;
+        a.job0 = j0; a.n_jobs = nb; a.job_list = nullptr;
+        for (uint32_t ext = 0;; ++ext) {
+            a.table = b_table.as<uint32_t>(); a.table_n = table.size();
+            XRL_HIP(hipMemsetAsync(b_next.p, 0, 8, s));
+            hipLaunchKernelGGL(k13_solve, dim3(std::min(slots, a.n_jobs)), dim3(64), 0, s, a);
+            XRL_LAUNCH_CHECK();
+            uint32_t nr[2];
+            XRL_HIP(hipMemcpyAsync(nr, b_next.p, 8, hipMemcpyDeviceToHost, s));
+            XRL_HIP(hipStreamSynchronize(s));
+            if (!nr[1]) break;
+            if (ext >= kTrainMaxExtensions) fail(what + "the table of random words was extended " + std::to_string(ext) + " times and a job still reached its end");
+            grow_table((uint64_t)table.size() * 4);
+            ++T.extensions; T.reruns += nr[1];
+            XRL_HIP(hipMemcpyAsync(b_list.p, b_redo.p, (size_t)nr[1] * 4, hipMemcpyDeviceToDevice, s));
+            a.job_list = b_list.as<uint32_t>(); a.n_jobs = nr[1];
+        }
+        if (read_flags(flags, s) & kStageFull) fail(what + "a job emitted more entries than its staging row holds");
+        // the batch's rows, compacted in job order
+        Chunk c;
+        c.job0 = j0; c.n = nb;
+        c.ptr.reserve(((size_t)nb + 1) * 8);
+        const uint64_t total = scan_total(tmp, reinterpret_cast<const uint64_t*>(a.cnt + j0), c.ptr.as<uint64_t>(), nb, s);
+        c.idx.reserve(total * 4); c.val.reserve(total * 4);
+        launch_copy_rows(c.ptr.as<uint64_t>(), nb, nullptr, stride, a.st_idx, a.st_val, c.idx.as<uint32_t>(), c.val.as<float>(), kWhat, s);
+        XRL_HIP(hipStreamSynchronize(s));
+        chunks.push_back(std::move(c));
+    }
+
+    // W^T by label
+    DevBuf by_label;
+    by_label.reserve(((size_t)L + 1) * 8);
+    XRL_HIP(hipMemsetAsync(by_label.p, 0, ((size_t)L + 1) * 8, s));
+    if (jobs) {
+        hipLaunchKernelGGL(k13_label_counts, dim3(blocks_of(jobs, 256, kWhat)), dim3(256), 0, s, a.cnt, a.job_label, jobs, L, by_label.as<unsigned long long>());
+        XRL_LAUNCH_CHECK();
+    }
+    out.ptr.reserve(((size_t)L + 1) * 8);
+    out.nnz = scan_total(tmp, by_label.as<uint64_t>(), out.ptr.as<uint64_t>(), L, s);
+    out.idx.reserve(out.nnz * 4); out.val.reserve(out.nnz * 4);
+    for (const Chunk& c : chunks) {
+        hipLaunchKernelGGL(k13_place, dim3(blocks_of(c.n, 4, kWhat)), dim3(256), 0, s, c.ptr.as<unsigned long long>(), a.job_label + c.job0, c.n, L, c.idx.as<uint32_t>(),
+                           c.val.as<float>(), out.ptr.as<unsigned long long>(), out.idx.as<uint32_t>(), out.val.as<float>());
+        XRL_LAUNCH_CHECK();
+    }
+    uint64_t ctr[7];
+    XRL_HIP(hipMemcpyAsync(ctr, b_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s));
+    XRL_HIP(hipStreamSynchronize(s));
+    T.iters = ctr[0]; T.shrinks = ctr[1]; T.reactivations = ctr[2]; T.max_iter_stops = ctr[3]; T.clipped = ctr[4]; T.lane_rows = ctr[5]; T.wave_rows = ctr[6];
+}
+
+}  // namespace xrl

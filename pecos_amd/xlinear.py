@@ -9,8 +9,12 @@ Surface kept from the reference (same names, kwargs and error behaviour):
 * ``HierarchicalMLModel.{load, predict, get_pred_params, PredParams}``  pecos/xmc/base.py:1090-1680
 * ``MLModel.PredParams``                                                pecos/xmc/base.py:640-678
 
-Training, pruning and the python (non predict-only) model chain stay in the reference: loading
-with ``is_predict_only=False`` raises ``NotImplementedError``.
+* ``MLProblem``, ``MLModel.{TrainParams, train, save}``, ``HierarchicalMLModel.{TrainParams, train, save}``,
+  ``XLinearModel.{TrainParams, train, save}``                           pecos/xmc/base.py:488-880, 1371-1572
+  training on the device (K13): a trained model predicts natively and saves the reference's folder layout
+
+Pruning and the python (non predict-only) model chain stay in the reference: loading with
+``is_predict_only=False`` raises ``NotImplementedError``, and a loaded model cannot be saved.
 """
 import copy
 import dataclasses as dc
@@ -22,7 +26,7 @@ from os import path
 import numpy as np
 import scipy.sparse as smat
 
-from .core import ScipyCompressedSparseAllocator, clib
+from .core import ScipyCompressedSparseAllocator, ScipyCscF32, ScipyCsrF32, ScipyDrmF32, clib
 
 VALID_POST_PROCESSORS = ["noop", "sigmoid", "log-sigmoid"] + \
     [f"l{p}-hinge" for p in range(1, 5)] + [f"log-l{p}-hinge" for p in range(1, 5)]  # xmc/base.py:456-475
@@ -73,6 +77,145 @@ class MLModel:
     def load_pred_params(cls, folder):
         param = json.loads(open(f"{folder}/param.json", "r", encoding="utf-8").read())
         return cls.PredParams.from_dict(param["pred_kwargs"])
+
+    @dc.dataclass
+    class TrainParams(BaseParams):
+        """pecos/xmc/base.py:616-647, the same names and defaults."""
+        threshold: float = 0.1
+        max_nonzeros_per_label: int = None  # type: ignore
+        solver_type: str = "L2R_L2LOSS_SVC_DUAL"
+        Cp: float = 1.0
+        Cn: float = 1.0
+        max_iter: int = 100
+        eps: float = 0.1
+        bias: float = 1.0
+        threads: int = -1
+        verbose: int = 0
+        newton_eps: float = 0.01
+
+    def __init__(self, W=None, C=None, bias=-1.0, pred_params=None, **kwargs):
+        """One trained layer on the host: W ((features + (bias > 0)) x labels, CSC), C (labels x codes, CSC)."""
+        self.W, self.C, self.bias = W, C, bias
+        self.pred_params = self.PredParams.from_dict(pred_params)
+
+    @property
+    def nr_labels(self):
+        return self.W.shape[1]
+
+    @property
+    def nr_codes(self):
+        return self.C.shape[1]
+
+    @property
+    def nr_features(self):
+        return self.W.shape[0] - (1 if self.bias > 0 else 0)
+
+    @classmethod
+    def train(cls, prob, train_params=None, pred_params=None, **kwargs):
+        """One layer trained on the device (K13; ``clib.xlinear_single_layer_train``) from an :class:`MLProblem`."""
+        train_params = cls.TrainParams.from_dict(kwargs if train_params is None else train_params)
+        pred_params = cls.PredParams.from_dict(pred_params)
+        pred_params.override_with_kwargs(kwargs.get("pred_kwargs", None))
+        if pred_params.post_processor not in VALID_POST_PROCESSORS:
+            raise ValueError("pred_params is not valid!")
+        W = clib.xlinear_single_layer_train(prob.pX, prob.pY, prob.pC, prob.pM, prob.pR, **train_params.to_dict())
+        return cls(W=W, C=prob.C, bias=train_params.bias, pred_params=pred_params)
+
+    def save(self, folder):
+        """The reference's layer folder (pecos/xmc/base.py:807-830): param.json, W.npz, C.npz."""
+        os.makedirs(folder, exist_ok=True)
+        param = {"__meta__": {"class_fullname": "pecos.xmc.base###MLModel"}, "model": "MLModel", "nr_labels": self.nr_labels, "nr_features": self.nr_features,
+                 "nr_codes": self.nr_codes, "bias": self.bias, "pred_kwargs": self.pred_params.to_dict()}
+        with open(f"{folder}/param.json", "w", encoding="utf-8") as f:
+            f.write(json.dumps(param, indent=True))
+        smat.save_npz(f"{folder}/W.npz", smat.csc_matrix(self.W, dtype=np.float32), compressed=False)
+        smat.save_npz(f"{folder}/C.npz", smat.csc_matrix(self.C, dtype=np.float32), compressed=False)
+
+
+def _ones_column(rows):
+    """rows x 1, every entry stored with value 1: the one cluster every label (or instance) belongs to when no clustering is given."""
+    return smat.csc_matrix((np.ones(rows, dtype=np.float32), np.arange(rows), np.array([0, rows])), shape=(rows, 1))
+
+
+def _pattern_union(shape, mats):
+    """A float32 CSC of ``shape`` that stores a 1 wherever one of ``mats`` stores an entry (explicit zeros count), rows ascending inside
+    a column.  The trainer reads only the pattern of a matching matrix."""
+    rows, cols = [np.zeros(0, dtype=np.int64)], [np.zeros(0, dtype=np.int64)]
+    for A in mats:
+        A = smat.csc_matrix(A)
+        if A.shape != shape:
+            raise ValueError(f"a matching matrix has shape {A.shape}, the layer needs {shape}")
+        rows.append(A.indices.astype(np.int64))
+        cols.append(np.repeat(np.arange(A.shape[1], dtype=np.int64), np.diff(A.indptr)))
+    rows, cols = np.concatenate(rows), np.concatenate(cols)
+    U = smat.csc_matrix((np.ones(len(rows), dtype=np.float32), (rows, cols)), shape=shape)
+    U.sum_duplicates()
+    U.sort_indices()
+    U.data[:] = 1
+    return U
+
+
+class MLProblem(object):
+    """The five matrices of one layer's training as the views the native call takes: ``pX`` (instances x features; CSR or dense),
+    ``pY`` (instances x labels), ``pC`` (labels x clusters), ``pM`` (instances x clusters: whom a cluster's labels train against) and
+    ``pR`` (the cost of every positive, or None), the last four column-major float32.  What is not given is filled in as the reference
+    fills it in (pecos/xmc/base.py, MLProblem): without ``C`` all labels share one cluster; without ``M`` an instance is matched to
+    the clusters of its own labels -- the pattern of ``Y * C``, by the device sparse product -- or, under a single cluster, to that
+    cluster.  ``R`` must store exactly Y's entries and no negative value.  ``threads`` is accepted and ignored."""
+
+    def __init__(self, X, Y, C=None, M=None, R=None, threads=8):
+        self.dtype = np.float32
+        self.pX = self._feature_view(X)
+        labels = self._column_major("Y", Y)
+        n_inst, n_labels = labels.shape
+        clusters = _ones_column(n_labels) if C is None else self._column_major("C", C)
+        if clusters.shape[0] != n_labels:
+            raise ValueError(f"C has {clusters.shape[0]} rows, Y has {n_labels} labels")
+        if M is not None:
+            matching = self._column_major("M", M)
+            if matching.shape != (n_inst, clusters.shape[1]):
+                raise ValueError(f"M has shape {matching.shape}, Y and C need {(n_inst, clusters.shape[1])}")
+        elif clusters.shape[1] > 1:
+            matching = smat.csc_matrix(clib.sparse_matmul(labels, clusters), dtype=np.float32)
+        else:
+            matching = _ones_column(n_inst)
+        if not matching.has_sorted_indices:
+            matching = matching.sorted_indices()                      # (a copy: the caller's matrix stays as it is)
+        relevance = None if R is None else self._column_major("R", R)
+        if relevance is not None:
+            for part in ("indptr", "indices"):
+                if not np.array_equal(getattr(labels, part), getattr(relevance, part)):
+                    raise ValueError(f"Invalid relevance matrix: Y.{part} != R.{part}")
+            if relevance.nnz and relevance.data.min() < 0:
+                raise ValueError("Invalid relevance matrix: got value < 0")
+        self.pY, self.pC, self.pM = (ScipyCscF32.init_from(A) for A in (labels, clusters, matching))
+        self.pR = None if relevance is None else ScipyCscF32.init_from(relevance)
+
+    def _feature_view(self, X):
+        if isinstance(X, (ScipyCsrF32, ScipyDrmF32)):
+            return X
+        if X.dtype != self.dtype:
+            raise ValueError(f"X must be float32, got {X.dtype}")
+        if isinstance(X, smat.csr_matrix):
+            return ScipyCsrF32(X)
+        if isinstance(X, np.ndarray):
+            return ScipyDrmF32(X)
+        raise NotImplementedError("type(X) = {} is not supported.".format(type(X)))
+
+    def _column_major(self, name, A):
+        """A view's own matrix, or a sparse matrix as float32 CSC (a float32 CSC as it is, stored order kept)."""
+        if isinstance(A, ScipyCscF32):
+            return A.buf
+        if not smat.issparse(A):
+            raise NotImplementedError("type({}) = {} is not supported.".format(name, type(A)))
+        return A if isinstance(A, smat.csc_matrix) and A.dtype == self.dtype else A.tocsc().astype(self.dtype)
+
+    X = property(lambda self: self.pX.buf)
+    Y = property(lambda self: self.pY.buf)
+    C = property(lambda self: self.pC.buf)
+    M = property(lambda self: self.pM.buf)
+    R = property(lambda self: None if self.pR is None else self.pR.buf)
+    nr_labels = property(lambda self: self.pY.buf.shape[1])
 
 
 class HierarchicalMLModel:
@@ -213,6 +356,121 @@ class HierarchicalMLModel:
             model_chain=[MLModel.load_pred_params(f"{model_folder}/{d}.model") for d in range(depth)])
         return cls(model, pred_params=pred_params, is_predict_only=True)
 
+    @dc.dataclass
+    class TrainParams(BaseParams):
+        """pecos/xmc/base.py:1101-1113: the negative sampling scheme and the solver parameters, one per layer or one for all."""
+        neg_mining_chain: str = "tfn"
+        model_chain: MLModel.TrainParams = None  # type: ignore
+
+        @classmethod
+        def from_dict(cls, param=None):
+            if param is None:
+                return cls()
+            if isinstance(param, cls):
+                return copy.deepcopy(param)
+            chain = param.get("model_chain")
+            chain = [MLModel.TrainParams.from_dict(c) for c in chain] if isinstance(chain, (list, tuple)) else MLModel.TrainParams.from_dict(chain)
+            return cls(neg_mining_chain=param.get("neg_mining_chain", "tfn"), model_chain=chain)
+
+    @staticmethod
+    def _per_layer(value, depth, name):
+        if isinstance(value, (list, tuple)):
+            if len(value) != depth:
+                raise ValueError(f"len({name})={len(value)} != {depth}")
+            return list(value)
+        return [copy.deepcopy(value) for _ in range(depth)]
+
+    @classmethod
+    def train(cls, prob, clustering=None, relevance_chain=None, matching_chain=None, train_params=None, pred_params=None, **kwargs):
+        """The layers of a cluster chain (root first; None: one one-versus-all layer) trained on the device, top down
+        (pecos/xmc/base.py:1412-1572).  Layer t's labels are ``Y * C_last * ... * C_(t+1)`` and its negatives the instances matched to a
+        label's cluster: ``tfn`` = the layer above's labels (teacher forcing), ``usn`` = ``matching_chain[t]``, or both; the label chain and
+        the matching matrices go through the device sparse product.  A scheme with ``man`` (matcher-aware negatives) raises
+        ``NotImplementedError``: it needs a prediction of the half-trained chain.  Returns a model that predicts natively and can be saved."""
+        chain = [None] if clustering is None or clustering is False else [smat.csc_matrix(C, dtype=np.float32) for C in clustering]
+        depth = len(chain)
+        if chain[0] is not None and chain[-1].shape[0] != prob.nr_labels:
+            raise ValueError(f"the bottom clustering matrix has {chain[-1].shape[0]} rows, the problem {prob.nr_labels} labels")
+        if train_params is None:
+            tp = cls.TrainParams(neg_mining_chain=kwargs.get("negative_sampling_scheme", "tfn"), model_chain=MLModel.TrainParams.from_dict(kwargs))
+        else:
+            tp = cls.TrainParams.from_dict(train_params)
+            if tp.neg_mining_chain is None:
+                tp.neg_mining_chain = kwargs.get("negative_sampling_scheme", "tfn")
+        schemes = [s.lower() for s in cls._per_layer(tp.neg_mining_chain, depth, "neg_mining_chain")]
+        layer_params = cls._per_layer(tp.model_chain if tp.model_chain is not None else MLModel.TrainParams(), depth, "model_chain")
+        for s in schemes:
+            if "man" in s:
+                raise NotImplementedError(f"negative sampling scheme '{s}': matcher-aware negatives (man) need a prediction of the half-trained chain, "
+                                          "which this library does not run during training; use tfn, usn or tfn+usn")
+        pp = cls.PredParams(model_chain=MLModel.PredParams()) if pred_params is None else cls.PredParams.from_dict(pred_params)
+        pp.model_chain = cls._per_layer(pp.model_chain if pp.model_chain is not None else MLModel.PredParams(), depth, "pred_params.model_chain")
+        pp.override_with_kwargs(kwargs.get("pred_kwargs", None))
+        if chain[0] is None:
+            return cls._from_layers([MLModel.train(prob, train_params=layer_params[0], pred_params=pp.model_chain[0])], pp)
+        for name, given in (("matching_chain", matching_chain), ("relevance_chain", relevance_chain)):
+            if given is not None and len(given) != depth:
+                raise ValueError(f"len({name})={len(given)} != {depth}")
+        labels_of = cls._labels_per_layer(prob.Y, chain)
+        layers = []
+        for t in range(depth):
+            negatives = cls._matching(t, schemes[t], labels_of, chain, None if matching_chain is None else matching_chain[t])
+            layer_prob = MLProblem(prob.pX, labels_of[t], C=chain[t], M=negatives, R=None if relevance_chain is None else relevance_chain[t])
+            layers.append(MLModel.train(layer_prob, train_params=layer_params[t], pred_params=pp.model_chain[t]))
+        return cls._from_layers(layers, pp)
+
+    @staticmethod
+    def _labels_per_layer(Y, chain):
+        """labels_of[t] = instances x (nodes of layer t): the leaf labels rolled up through the clustering matrices below layer t, one
+        device sparse product per level, bottom up."""
+        labels_of = [None] * len(chain)
+        labels_of[-1] = Y
+        for t in range(len(chain) - 2, -1, -1):
+            labels_of[t] = clib.sparse_matmul(labels_of[t + 1], chain[t + 1]).tocsc()
+        return labels_of
+
+    @staticmethod
+    def _matching(t, scheme, labels_of, chain, user_supplied):
+        """Layer t's matching matrix (instances x clusters of layer t), or None for a root that is a single cluster (every instance
+        then trains every node).  ``tfn``: an instance is matched to the clusters that hold one of its own nodes -- the layer above's
+        labels, which for the top layer is one more product.  ``usn``: the caller's matrix.  Both: their union."""
+        C = chain[t]
+        if t == 0 and C.shape[1] == 1:
+            return None
+        parts = []
+        if "usn" in scheme and user_supplied is not None:
+            parts.append(user_supplied)
+        if "tfn" in scheme:
+            parts.append(labels_of[t - 1] if t else clib.sparse_matmul(labels_of[0], C))
+        return _pattern_union((labels_of[t].shape[0], C.shape[1]), parts)
+
+    @classmethod
+    def _from_layers(cls, layers, pred_params):
+        """Trained layers as a model: written once in the reference's layout and loaded natively; the layers stay for :meth:`save`."""
+        import tempfile
+        with tempfile.TemporaryDirectory() as tmp:
+            cls._write(tmp, layers)
+            model = cls.load(tmp)
+        model.layers = layers
+        model.pred_params = pred_params
+        return model
+
+    @staticmethod
+    def _write(folder, layers):
+        os.makedirs(folder, exist_ok=True)
+        param = {"__meta__": {"class_fullname": "pecos.xmc.base###HierarchicalMLModel"}, "model": "HierarchicalMLModel", "depth": len(layers),
+                 "nr_features": layers[-1].nr_features, "nr_codes": layers[-1].nr_codes, "nr_labels": layers[-1].nr_labels}
+        open(f"{folder}/param.json", "w", encoding="utf-8").write(json.dumps(param, indent=True))
+        for d, layer in enumerate(layers):
+            layer.save(f"{folder}/{d}.model")
+
+    def save(self, folder):
+        """The reference's folder layout (pecos/xmc/base.py:1371-1395), which :meth:`load` here and in the reference read.  Only a model
+        that was trained in this process holds its weights on the host; a loaded one is predict-only."""
+        if getattr(self, "layers", None) is None:
+            raise Exception("Model is predict only! save not supported!")
+        self._write(folder, self.layers)
+
     def _resolve_overrides(self, pred_params, kwargs):
         """xmc/base.py:1609-1654: merge kwargs, then only UNIFORM overrides are expressible natively."""
         if pred_params is None:
@@ -339,6 +597,57 @@ class XLinearModel:
         queries get the BINARY_SEARCH_CHUNKED arithmetic there (same labels, scores within ~3e-6 relative of the hash layout's)."""
         model = HierarchicalMLModel.load(path.join(model_folder, "ranker"), is_predict_only, **kwargs)
         return cls(model)
+
+    @dc.dataclass
+    class TrainParams(BaseParams):
+        """The part of pecos/xmc/xlinear/model.py:33-70 that is served: the full model, no relevance induction."""
+        mode: str = "full-model"
+        ranker_level: int = 1
+        nr_splits: int = 16
+        min_codes: int = None  # type: ignore
+        shallow: bool = False
+        rel_mode: str = "disable"
+        rel_norm: str = "no-norm"
+        hlm_args: HierarchicalMLModel.TrainParams = None  # type: ignore
+
+    @classmethod
+    def train(cls, X, Y, C=None, R=None, user_supplied_negatives=None, train_params=None, pred_params=None, **kwargs):
+        """An XR-Linear model trained on the device (pecos/xmc/xlinear/model.py:167-283): ``C`` is None (one-versus-all; ``R`` then gives
+        the costs), the bottom clustering matrix (labels x codes) or a chain, root first.  Solver parameters come as keywords
+        (``threshold``, ``solver_type``, ``Cp``, ``max_iter``, ``negative_sampling_scheme``, ...) or in ``train_params``;
+        ``beam_size`` / ``only_topk`` / ``post_processor`` or ``pred_kwargs`` set the saved prediction parameters.  Not served, and refused
+        by name: the ``matcher`` / ``ranker`` modes, relevance induction (``rel_mode`` other than ``disable``), user-supplied negatives."""
+        from .indexer import chain_from_partial
+        if train_params is None:
+            tp = cls.TrainParams.from_dict(kwargs)
+            tp.hlm_args = HierarchicalMLModel.TrainParams(neg_mining_chain=kwargs.get("negative_sampling_scheme", "tfn"), model_chain=MLModel.TrainParams.from_dict(kwargs))
+        else:
+            tp = cls.TrainParams.from_dict(train_params)
+            if isinstance(tp.hlm_args, dict):
+                tp.hlm_args = HierarchicalMLModel.TrainParams.from_dict(tp.hlm_args)
+        for what, bad in (("mode", tp.mode != "full-model"), ("rel_mode", tp.rel_mode != "disable"), ("user_supplied_negatives", user_supplied_negatives is not None)):
+            if bad:
+                raise NotImplementedError(f"XLinearModel.train: {what} = {getattr(tp, what, user_supplied_negatives)!r} is not served on the device")
+        hp = None
+        if pred_params is not None:
+            hp = cls.PredParams.from_dict(pred_params).hlm_args
+        if kwargs.get("pred_kwargs", None) is None:
+            kwargs["pred_kwargs"] = {k: kwargs.get(k, None) for k in ("beam_size", "only_topk", "post_processor")}
+        if C is None or (isinstance(C, (list, tuple)) and len(C) == 0):
+            clustering = None
+        else:                                                   # the given levels, completed upwards to a single root (ClusterChain.from_partial_chain)
+            top, rest = (C[0], [smat.csc_matrix(c, dtype=np.float32) for c in C[1:]]) if isinstance(C, (list, tuple)) else (C, [])
+            min_codes, nr_splits = (None, 16) if tp.shallow else (tp.min_codes or tp.nr_splits, tp.nr_splits)
+            clustering = chain_from_partial(top, min_codes=min_codes, nr_splits=nr_splits) + rest
+        prob = MLProblem(X, Y, R=R if clustering is None else None)
+        return cls(HierarchicalMLModel.train(prob, clustering=clustering, train_params=tp.hlm_args, pred_params=hp, **kwargs))
+
+    def save(self, model_folder):
+        """``model_folder/param.json`` and ``model_folder/ranker`` in the reference's layout (pecos/xmc/xlinear/model.py:92-103)."""
+        os.makedirs(model_folder, exist_ok=True)
+        with open(f"{model_folder}/param.json", "w", encoding="utf-8") as fout:
+            fout.write(json.dumps({"__meta__": {"class_fullname": "pecos.xmc.xlinear.model###XLinearModel"}, "model": "XLinearModel"}, indent=True))
+        self.model.save(path.join(model_folder, "ranker"))
 
     @classmethod
     def compile_mmap_model(cls, npz_folder, mmap_folder):
