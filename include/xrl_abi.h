@@ -566,7 +566,20 @@ int xrl_debug_embed_forms(uint64_t* out, uint32_t n);
  *     largest |w|, ties to the lower feature; when fewer than k pass, all of them and the bias (if it passes); otherwise the bias
  *     replaces the least kept feature when |b| > |w_least|.  The reference leaves the order inside such a label to std::nth_element; here
  *     a label's entries are ascending in both cases.
- * Not pinned: non-finite values in X, a relevance of 0, a row id stored twice in one column of Y or M.
+ * Pinned too (the reference's answer to each is sequential code that does not depend on `threads`, so none is refused):
+ *   Repeated row ids.  A row id stored more than once in a column of Y: at EVERY stored position, in stored order, the row is appended to
+ *     index when its cost reads 0 at that moment, then its cost becomes that position's R (or 1).  So the first occurrence of a row M
+ *     does not list is appended, an occurrence that follows one whose R is +-0 is appended AGAIN (a cost of 0 reads as "not listed"; also
+ *     in the pure form, where a job may list more instances than X has rows), and the last stored R stays.  A row id stored twice in a
+ *     column of M is listed twice; alpha and QD are per row.  The device orders the 64 positions of a step by lane number, not by atomics.
+ *   Non-finite values.  The set-up also runs w += (y * alpha) * x and b += (y * alpha) * bias with y * alpha = +-0 (:444-446): w[f] is a
+ *     NaN wherever an instance stores an inf or a NaN at f, b is a NaN under an infinite bias.  Every comparison is the reference's as
+ *     written: a NaN G neither shrinks nor counts as violated unless 0 < alpha < C, where PG = NaN; std::max(PGmax_new, PG) and std::min
+ *     (PGmin_new, PG) never take a NaN PG; min(max(., 0), C) passes a NaN alpha on and ignores a NaN C.  Roundings to fp32 overflow to inf
+ *     and go through subnormals; QD == 0 divides to +-inf (clipped at C under the L1 loss).  A NaN weight is NEVER emitted (it fails
+ *     fabs(v) >= threshold, and a NaN threshold fails everything); +-inf weights are, and tie by the lower feature.
+ *   Parameters.  Cp, Cn, eps, threshold, bias and R's values are used as given (0, negative, subnormal, inf, NaN).  The result has
+ *     d + (bias > 0) rows: a zero, negative or NaN bias adds no row and takes no part.
  * Capacity.  One wavefront owns one job at a time, with a slot of scratch (w, a bitmap of touched features, index, alpha, QD, cost, y);
  * jobs go in batches whose emission staging stays under the budget (4 GiB each for slots and staging; XRL_TRAIN_SCRATCH_BYTES in the
  * environment replaces it).  All jobs read ONE table of mt19937(0) outputs the host fills (XRL_TRAIN_RANDOM_WORDS = its first length,

@@ -120,6 +120,8 @@ __device__ __forceinline__ bool k13_draw(const uint32_t* __restrict__ table, uin
     return true;
 }
 
+__device__ __forceinline__ bool k13_not_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u; }
+
 __device__ __forceinline__ void k13_swap(uint32_t* a, uint32_t i, uint32_t j) { const uint32_t t = a[i]; a[i] = a[j]; a[j] = t; }
 
 // libstdc++'s std::shuffle (bits/stl_algo.h) of a[0, n) by one lane
@@ -186,27 +188,49 @@ __device__ void k13_job(const K13Args& a, uint32_t job, uint32_t slot, uint32_t 
     {
         uint64_t yb, ye;
         row_span(a.y_ptr, label, a.y_nnz, yb, ye);
+        // The reference walks the column one stored position after the other: a position appends its row when the row's cost is 0 at
+        // that moment ("not listed"), then stores its own cost.  A row id stored twice is therefore appended once per occurrence that
+        // meets a cost of 0, and the LAST stored cost stays.  Here 64 positions go per step, and the order is made the stored order BY
+        // LANE NUMBER, never by the order in which the memory serves the lanes: every lane finds the nearest lower lane with its row id
+        // (the cost that lane carries is the cost this lane meets) and whether a higher lane has it too; a lane without a lower twin
+        // reads cost[i] as the steps before left it, and only the lane without a higher twin stores -- one writer per address, no atomic.
         for (uint64_t x0 = yb; x0 < ye; x0 += 64u) {
             const uint64_t x = x0 + lane;
-            bool fresh = false;
+            const bool have = x < ye;
+            const uint32_t cnt = (uint32_t)min((uint64_t)64u, ye - x0);
             uint32_t i = 0;
-            if (x < ye) {
-                i = a.y_idx[x];
-                const float c = a.r_val ? a.r_val[x] : 1.0f;
-                const uint32_t old = atomicExch(reinterpret_cast<uint32_t*>(&cost[i]), __float_as_uint(c));
-                ysg[i] = 1;
-                fresh = __uint_as_float(old) == 0.0f;
+            float c = 1.0f;
+            if (have) { i = a.y_idx[x]; if (a.r_val) c = a.r_val[x]; }
+            bool lower = false, higher = false;
+            float met = 0.0f;
+            for (uint32_t l = 0; l < cnt; ++l) {                       // l is uniform: two lane reads a turn, at most 64 turns
+                const uint32_t il = (uint32_t)__builtin_amdgcn_readlane((int)i, (int)l);
+                const float cl = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(c), (int)l));
+                if (have && il == i) {
+                    if (l < lane) { lower = true; met = cl; }
+                    else if (l > lane) higher = true;
+                }
             }
+            if (have && !lower) met = cost[i];
+            const bool fresh = have && met == 0.0f;                    // +0 and -0 both read as "not listed"; a NaN does not
+            wave_sync_hbm();                                           // a first occurrence has read cost[i] before the last one stores to it
+            if (have && !higher) cost[i] = c;
+            if (have) ysg[i] = 1;
             const unsigned long long m = __ballot(fresh);
             const uint32_t at = n + lanes_below(m);
             if (fresh && at < a.index_cap) index[at] = i;
             n += (uint32_t)__popcll(m);
+            wave_sync_hbm();                                           // the next step's lanes read the costs this step stored
         }
-        if (n > a.index_cap) n = a.index_cap;                          // (cannot happen: the cap is the longest M column plus the longest Y column)
+        if (n > a.index_cap) n = a.index_cap;                          // (cannot happen: a stored position of Y appends at most once, and the cap counts them all)
     }
     wave_sync_hbm();
 
-    // ---- QD = diag + x'x + bias^2, alpha = 0, and the features the job can touch
+    // ---- QD = diag + x'x + bias^2, alpha = 0, and the features the job can touch.  The reference also adds y * alpha = (+-)0 times the row
+    //      to w and (+-)0 * bias to b here (:444-446): nothing for a finite entry (w is +0), a NaN where X stores an inf or a NaN and, with an
+    //      infinite bias, in b.  Every lane that meets such an entry stores the same quiet NaN, so no order shows; a NaN is never emitted and
+    //      every comparison reads any NaN alike.
+    const float kNaN = __uint_as_float(0x7FC00000u);
     for (uint32_t s0 = 0; s0 < n; s0 += 64u) {
         const uint32_t s = s0 + lane;
         const bool have = s < n;
@@ -221,6 +245,7 @@ __device__ void k13_job(const K13Args& a, uint32_t job, uint32_t slot, uint32_t 
                 const uint32_t f = a.x_idx[j];
                 acc = __fadd_rn(acc, __fmul_rn(v, v));
                 atomicOr(&touched[f >> 5], 1u << (f & 31u));
+                if (k13_not_finite(v)) w[f] = kNaN;
             }
         unsigned long long wm = __ballot(wide);
         ctr[5] += (unsigned long long)__popcll(__ballot(have && !wide));
@@ -238,6 +263,7 @@ __device__ void k13_job(const K13Args& a, uint32_t job, uint32_t slot, uint32_t 
                     const uint32_t f = a.x_idx[x];
                     p = __fmul_rn(v, v);
                     atomicOr(&touched[f >> 5], 1u << (f & 31u));
+                    if (k13_not_finite(v)) w[f] = kNaN;
                 }
                 ws = wave_chain(ws, p, (uint32_t)min((uint64_t)64u, ee - x0));
             }
@@ -257,7 +283,7 @@ __device__ void k13_job(const K13Args& a, uint32_t job, uint32_t slot, uint32_t 
     double pgmax_old = kInf, pgmin_old = -kInf;
     uint32_t active = n;
     uint64_t iter = 0, cur = 0;
-    float bw = 0.0f;
+    float bw = (n && a.bias == kInf) ? kNaN : 0.0f;                   // (+-)0 * inf of the set-up, once an instance exists
     bool table_end = false, converged = false;
     while (iter < a.max_iter) {
         double pgmax_new = -kInf, pgmin_new = kInf;
@@ -532,7 +558,9 @@ void train_layer_device(const char* what_c, const QueriesDev& X, const QueriesDe
     uint64_t sz[4];
     XRL_HIP(hipMemcpyAsync(sz, sizes.p, 32, hipMemcpyDeviceToHost, s));
     XRL_HIP(hipStreamSynchronize(s));
-    const uint64_t index_cap64 = coded ? sz[0] + sz[2] : (uint64_t)N;
+    // a stored position of Y appends its row when the row is not listed at that moment: with R a listed row can become unlisted (a cost
+    // of 0), so in the pure form too every stored position of the longest Y column may append
+    const uint64_t index_cap64 = coded ? sz[0] + sz[2] : (uint64_t)N + (r_val ? sz[2] : 0);
     if (index_cap64 >= (1ull << 31)) fail(what + "a job of 2^31 instances or more");
     const uint32_t index_cap = (uint32_t)(index_cap64 ? index_cap64 : 1);
     const uint64_t touched_max = coded ? sz[1] + sz[3] : X.nnz;

@@ -1,6 +1,6 @@
 """The rule of the ranker training (K13), stated in numpy with explicit float32 / float64 roundings, and what the training tests share:
 the ctypes caller of the host training entry points of any library (``c_xlinear_single_layer_train_*`` in the reference,
-``xrl_single_layer_train_*`` with the same argument list here), the case generators, and two deliberately wrong variants.
+``xrl_single_layer_train_*`` with the same argument list here), the case generators (cases() and, for inputs away from well-formed finite ones, edge_cases()), and deliberately wrong variants.
 
 The statement follows the reference at threads = 1 (pecos/core/xmc/linear_solver.hpp:420-528, 667-779, 797-860; utils/matrix.hpp:837-877,
 971-976).  Its shuffle restates the C++ standard library the reference is compiled with here (libstdc++: shuffle's two positions per draw
@@ -46,12 +46,35 @@ def jobs_of(Y, C, M):
     return [(k, int(l)) for k in range(C.shape[1]) for l in C.indices[C.indptr[k]:C.indptr[k + 1]]]
 
 
-def statement(X, Y, C=None, M=None, R=None, threshold=0.0, max_nonzeros=0, solver=L1_DUAL, Cp=1.0, Cn=1.0, max_iter=1000, eps=0.1, bias=1.0,
-              variant=None):
+VARIANTS = (None, "pairwise", "alpha64", "dup_last_first", "fmax", "nan_kept")
+FLT_MAX = float(np.finfo(np.float32).max)
+FLT_MIN = float(np.finfo(np.float32).tiny)
+
+
+def statement(*a, **kw):
     """The rule.  X: CSR (sorted rows) or ndarray; Y, C, M, R: CSC as stored (never canonicalised).  Returns dict(rows, cols, vals: the COO
-    in job order with a label's entries ascending; counters: iters, shrinks, reactivations, max_iter_stops, clipped; per_job: [(label,
-    iterations, instances)]).  variant: None, "pairwise" (the dot as a balanced tree) or "alpha64" (alpha kept in fp64)."""
-    assert variant in (None, "pairwise", "alpha64") and solver in (L1_DUAL, L2_DUAL)
+    in job order with a label's entries ascending; counters: iters, shrinks, reactivations, max_iter_stops, clipped, lane_rows, wave_rows
+    (instances whose feature row stores fewer than 64 entries / 64 and more, counted per listed position); trace: what the edge cases
+    claim to meet, see _statement; per_job: [(label, iterations, instances)]).  variant: None or one of the deliberately wrong ones:
+    "pairwise" (the dot as a balanced tree), "alpha64" (alpha kept in fp64), "dup_last_first" (inside a run of 64 stored positions of a
+    Y column the last occurrence of a repeated row id is served first), "fmax" / "nan_kept" (PGmax_new / PGmin_new by fmax / fmin, or
+    with std::max's arguments the other way round so that a NaN PG is kept).  Overflows, 0 * inf and divisions by zero are part of the
+    rule (IEEE results, as in the compiled reference), hence the errstate."""
+    with np.errstate(all="ignore"):
+        return _statement(*a, **kw)
+
+
+def _fmax(a, b):
+    return a if b != b else (b if a != a else max(a, b))
+
+
+def _fmin(a, b):
+    return a if b != b else (b if a != a else min(a, b))
+
+
+def _statement(X, Y, C=None, M=None, R=None, threshold=0.0, max_nonzeros=0, solver=L1_DUAL, Cp=1.0, Cn=1.0, max_iter=1000, eps=0.1, bias=1.0,
+               variant=None):
+    assert variant in VARIANTS and solver in (L1_DUAL, L2_DUAL)
     if not smat.issparse(X):
         from clustering_rule import as_full_csr
         X = as_full_csr(X)
@@ -62,7 +85,14 @@ def statement(X, Y, C=None, M=None, R=None, threshold=0.0, max_nonzeros=0, solve
     l2 = solver == L2_DUAL
     bias = float(bias)
     out_r, out_c, out_v, per_job = [], [], [], []
-    ctr = dict(iters=0, shrinks=0, reactivations=0, max_iter_stops=0, clipped=0)
+    ctr = dict(iters=0, shrinks=0, reactivations=0, max_iter_stops=0, clipped=0, lane_rows=0, wave_rows=0)
+    # what a case meets: alpha_inf (an alpha stored as inf), qd0_clipped (an update of an instance with QD == 0 clipped at C), nan_g_* (a NaN
+    # gradient met with alpha == 0 / == C / strictly between), qd_subnormal, t_overflow (a finite fp64 alpha above FLT_MAX rounded to inf on
+    # the store), dup_in_run / dup_across_runs (a row id stored again in one Y column within the same run of 64 stored positions / in a
+    # later run), reappends (a positive appended again because its cost read 0), nan_w_setup (entries of w made NaN by the set-up's 0 * x),
+    # qd_inf (x'x or the diagonal overflowed), dot_nonfinite (a dot product w'x that is inf or NaN)
+    trace = dict(alpha_inf=0, qd0_clipped=0, nan_g_zero=0, nan_g_at_c=0, nan_g_between=0, qd_subnormal=0, t_overflow=0, dup_in_run=0, dup_across_runs=0,
+                 reappends=0, nan_w_setup=0, qd_inf=0, dot_nonfinite=0)
     for code, label in jobs_of(Y, C, M):
         # -- init_worker
         cost, y = {}, {}
@@ -72,13 +102,34 @@ def statement(X, Y, C=None, M=None, R=None, threshold=0.0, max_nonzeros=0, solve
             index = [int(i) for i in M.indices[M.indptr[code]:M.indptr[code + 1]]]
         for i in index:
             y[i], cost[i] = -1, F32(1)
-        for p in range(Y.indptr[label], Y.indptr[label + 1]):
+        yb, ye = int(Y.indptr[label]), int(Y.indptr[label + 1])
+        seen_at = {}
+        for p in range(yb, ye):
             i = int(Y.indices[p])
-            y[i] = 1
-            if cost.get(i, F32(0)) == 0:
-                index.append(i)
-            cost[i] = F32(R.data[p]) if R is not None else F32(1)
+            if i in seen_at:
+                trace["dup_in_run" if (seen_at[i] - yb) // 64 == (p - yb) // 64 else "dup_across_runs"] += 1
+            seen_at[i] = p
+        if variant == "dup_last_first":
+            # the wrong order: within a run of 64 stored positions the occurrences are served last to first, appended in stored order
+            for r0 in range(yb, ye, 64):
+                fresh = {}
+                for p in reversed(range(r0, min(r0 + 64, ye))):
+                    i = int(Y.indices[p])
+                    y[i] = 1
+                    fresh[p] = cost.get(i, F32(0)) == 0
+                    cost[i] = F32(R.data[p]) if R is not None else F32(1)
+                index.extend(int(Y.indices[p]) for p in sorted(fresh) if fresh[p])
+        else:
+            for p in range(yb, ye):
+                i = int(Y.indices[p])
+                y[i] = 1
+                if cost.get(i, F32(0)) == 0:
+                    index.append(i)
+                    trace["reappends"] += i in cost                  # it had been listed: its cost has become 0 since
+                cost[i] = F32(R.data[p]) if R is not None else F32(1)
         n = len(index)
+        for i in index:
+            ctr["wave_rows" if len(rows_of[i][0]) >= 64 else "lane_rows"] += 1
         # -- set-up
         w = np.zeros(d, F32)
         b = F32(0)
@@ -93,6 +144,16 @@ def statement(X, Y, C=None, M=None, R=None, threshold=0.0, max_nonzeros=0, solve
             xx = _chain(v * v)
             QD[i] = F32(F64(q) + (F64(xx) + (bias * bias if bias > 0 else 0.0)))
             alpha[i] = F32(0) if variant != "alpha64" else F64(0)
+            trace["qd_subnormal"] += bool(0 < abs(float(QD[i])) < FLT_MIN)
+            trace["qd_inf"] += bool(QD[i] == INF)
+            # :444-446: w += (y * alpha) * x and b += (y * alpha) * bias with y * alpha = (+-)0: nothing for a finite entry, a NaN for an inf or a NaN
+            coef = F64(F32(y[i]) * F32(0))
+            bad = ~np.isfinite(v)
+            if bad.any():
+                trace["nan_w_setup"] += int(bad.sum())
+                w[f] = (w[f].astype(F64) + coef * v.astype(F64)).astype(F32)
+            if bias > 0:
+                b = F32(F64(b) + coef * bias)
         # -- the sweeps
         g = Mt19937(0)
         pgmax_old, pgmin_old = INF, -INF
@@ -108,11 +169,14 @@ def statement(X, Y, C=None, M=None, R=None, threshold=0.0, max_nonzeros=0, solve
                 f, v = rows_of[i]
                 yi = y[i]
                 dot = dot_sum(w[f] * v)
+                trace["dot_nonfinite"] += not np.isfinite(dot)
                 G = F64(yi) * (F64(dot) + (F64(b) * bias if bias > 0 else 0.0)) - 1.0
                 Cub = INF if l2 else class_cost(i)
                 diag = 0.5 / class_cost(i) if l2 else 0.0
                 G = G + F64(alpha[i]) * diag
                 PG, shrink = 0.0, False
+                if G != G:
+                    trace["nan_g_zero" if alpha[i] == 0 else "nan_g_at_c" if F64(alpha[i]) == Cub else "nan_g_between"] += 1
                 if alpha[i] == 0:
                     if G > pgmax_old:
                         shrink = True
@@ -130,7 +194,12 @@ def statement(X, Y, C=None, M=None, R=None, threshold=0.0, max_nonzeros=0, solve
                     index[s], index[active] = index[active], index[s]
                     ctr["shrinks"] += 1
                     continue
-                pgmax_new, pgmin_new = max(pgmax_new, PG), min(pgmin_new, PG)
+                if variant == "fmax":
+                    pgmax_new, pgmin_new = _fmax(pgmax_new, PG), _fmin(pgmin_new, PG)
+                elif variant == "nan_kept":                            # std::max(PG, PGmax_new): a NaN PG is returned, and then stays
+                    pgmax_new, pgmin_new = (pgmax_new if PG < pgmax_new else PG), (pgmin_new if pgmin_new < PG else PG)
+                else:                                                  # std::max(a, b) = a < b ? b : a; std::min(a, b) = b < a ? b : a
+                    pgmax_new, pgmin_new = (PG if pgmax_new < PG else pgmax_new), (PG if PG < pgmin_new else pgmin_new)
                 if abs(PG) > 1.0e-12:
                     old = F64(alpha[i])
                     t = old - G / F64(QD[i])
@@ -138,7 +207,10 @@ def statement(X, Y, C=None, M=None, R=None, threshold=0.0, max_nonzeros=0, solve
                     if Cub < t:
                         t = Cub
                         ctr["clipped"] += 1
+                        trace["qd0_clipped"] += bool(QD[i] == 0)
                     alpha[i] = F32(t) if variant != "alpha64" else F64(t)
+                    trace["t_overflow"] += bool(FLT_MAX < t < INF)
+                    trace["alpha_inf"] += bool(alpha[i] == INF)
                     dd = (F64(alpha[i]) - old) * F64(yi)
                     w[f] = (w[f].astype(F64) + dd * v.astype(F64)).astype(F32)
                     if bias > 0:
@@ -175,7 +247,7 @@ def statement(X, Y, C=None, M=None, R=None, threshold=0.0, max_nonzeros=0, solve
             out_r.append(int(k)); out_c.append(label); out_v.append(w[k])
         if push_bias:
             out_r.append(d); out_c.append(label); out_v.append(b)
-    return dict(rows=np.array(out_r, np.uint64), cols=np.array(out_c, np.uint64), vals=np.array(out_v, F32), counters=ctr, per_job=per_job)
+    return dict(rows=np.array(out_r, np.uint64), cols=np.array(out_c, np.uint64), vals=np.array(out_v, F32), counters=ctr, trace=trace, per_job=per_job)
 
 
 def canonical(rows, cols, vals):
@@ -258,6 +330,29 @@ def counters(path=OURS):
     lib.xrl_debug_train_counters.restype, lib.xrl_debug_train_counters.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]
     assert lib.xrl_debug_train_counters(out, len(COUNTERS)) == 0
     return dict(zip(COUNTERS, (int(v) for v in out)))
+
+
+# ------------------------------------------------------------------------------------------------ the resident form
+def as_stored_transpose(A):
+    """The CSC arrays of A as the CSR of its transpose, exactly as stored (what the solver reads)."""
+    t = smat.csr_matrix((A.shape[1], A.shape[0]), dtype=F32)
+    t.indptr, t.indices, t.data = A.indptr.astype(np.int64), A.indices.astype(np.int64), A.data.astype(F32)
+    return t
+
+
+def resident(X, Y, C, M, R, kw, stream=None):
+    """xrl_train_layer_device over uploaded handles -> (W^T as a scipy CSR with the stored order kept, counters)."""
+    from pecos_amd import DeviceMatrix, clib
+    hs = [DeviceMatrix.upload(X)] + [None if A is None else DeviceMatrix.upload(as_stored_transpose(A)) for A in (Y, C, M, R)]
+    out = DeviceMatrix(clib.train_layer_device(*(h and h.handle for h in hs), threshold=kw.get("threshold", 0.0), max_nonzeros_per_label=kw.get("max_nonzeros", 0),
+                                               solver_type=kw.get("solver", L1_DUAL), Cp=kw.get("Cp", 1.0), Cn=kw.get("Cn", 1.0), max_iter=kw.get("max_iter", 1000),
+                                               eps=kw.get("eps", 0.1), bias=kw.get("bias", 1.0), stream=stream))
+    return out.download(), clib.debug_train_counters()
+
+
+def wt_as_coo(Wt):
+    """W^T (CSR, labels x features) as (rows = features, cols = labels, vals) in stored order."""
+    return Wt.indices.astype(np.uint64), np.repeat(np.arange(Wt.shape[0]), np.diff(Wt.indptr)).astype(np.uint64), Wt.data
 
 
 # ------------------------------------------------------------------------------------------------ cases
@@ -406,6 +501,200 @@ def cases():
     return c
 
 
+# ------------------------------------------------------------------------------------------------ edge cases
+def set_entries(X, entries):
+    """A copy of X whose stored entry k of row r becomes v for every ((r, k), v); v may be a uint32 bit pattern (an int) so that a
+    signalling NaN keeps its payload."""
+    X = X.copy()
+    X.data = X.data.astype(F32)
+    for (r, k), v in entries.items():
+        assert k < X.indptr[r + 1] - X.indptr[r]
+        if isinstance(v, int):
+            X.data.view(np.uint32)[X.indptr[r] + k] = v
+        else:
+            X.data[X.indptr[r] + k] = v
+    return X
+
+
+def scale_rows(X, rows, scale):
+    X = X.copy()
+    X.data = X.data.astype(F32)
+    for r in rows:
+        X.data[X.indptr[r]:X.indptr[r + 1]] *= F32(scale)
+    return X
+
+
+SHORT_ROW, LONG_ROW = 3, 33
+
+
+def edge_base():
+    """40 rows x 80 features: rows 0 .. 29 store 5 entries (summed one row per lane), rows 30 .. 39 store 70 (two steps of the wavefront's
+    chain), three labels in the pure multi-label form; SHORT_ROW and LONG_ROW are positives of label 0."""
+    X = rows_csr(80, [5] * 30 + [70] * 10, 61, scale=0.5)
+    Y = raw_csc((40, 3), [([1, 3, 8, 20, 33, 35], [1] * 6), ([0, 2, 3, 30, 31], [1] * 5), (list(range(5, 40, 4)), [1] * 9)])
+    return X, Y
+
+
+def special_in_both_rows(X, v, second=None):
+    """v in the short row (entry 1) and in the long row (entries 10 and 66: both steps of the chain); `second` beside it in either row."""
+    e = {(SHORT_ROW, 1): v, (LONG_ROW, 10): v, (LONG_ROW, 66): v}
+    if second is not None:
+        e.update({(SHORT_ROW, 3): second, (LONG_ROW, 40): second})
+    return set_entries(X, e)
+
+
+def relevance_problem():
+    """Two codes of two labels; M's columns list rows 0 .. 19 and 10 .. 29, and every label has positives inside and outside its column."""
+    N = 40
+    X = rows_csr(30, [5] * N, 71)
+    Y = raw_csc((N, 4), [([1, 3, 5, 25, 27], [1] * 5), ([2, 3, 30], [1] * 3), ([12, 14, 3, 35], [1] * 4), ([11, 29, 0], [1] * 3)])
+    C = raw_csc((4, 2), [([0, 1], [1, 1]), ([2, 3], [1, 1])])
+    M = raw_csc((N, 2), [(list(range(0, 20)), [1] * 20), (list(range(10, 30)), [1] * 20)])
+    return X, Y, C, M
+
+
+def relevance_with(Y, v):
+    """Ordinary costs, and v on a positive M lists (row 3 of label 0, row 14 of label 2) and on one it does not (rows 25 and 35)."""
+    R = relevance(Y, 8)
+    for label, row in ((0, 3), (0, 25), (2, 14), (2, 35)):
+        p = Y.indptr[label] + list(Y.indices[Y.indptr[label]:Y.indptr[label + 1]]).index(row)
+        R.data[p] = v
+    return R
+
+
+def repeats_problem():
+    """100 rows, one code whose M column lists rows 0 .. 49.  Six labels of 72 stored positions and more (two runs of 64), a row id stored
+    again: label 0 / 1 inside the first run (listed row 7 / unlisted row 60, positions 1 and 40), label 2 / 3 across runs (positions 2 and
+    70), label 4 / 5 three times (positions 1, 30 and 69).  Between the occurrences lie unlisted rows, so where the repeated row is
+    appended shows in the order of index.  -> X, Y, C, M and {label: stored positions of the repeated row inside its column}."""
+    N = 100
+    X = rows_csr(20, [4] * N, 81)
+    rs = np.random.RandomState(82)
+    cols, where = [], {}
+    for label, (row, at) in enumerate(((7, (1, 40)), (60, (1, 40)), (9, (2, 70)), (62, (2, 70)), (11, (1, 30, 69)), (64, (1, 30, 69)))):
+        others = [int(r) for r in rs.permutation(N) if r != row][:72 - len(at)]
+        ids = []
+        for p in range(72):
+            ids.append(row if p in at else others.pop())
+        cols.append((ids, [1] * 72))
+        where[label] = at
+    Y = raw_csc((N, 6), cols)
+    C = raw_csc((6, 1), [(list(range(6)), [1] * 6)])
+    M = raw_csc((N, 1), [(list(range(50)), [1] * 50)])
+    return X, Y, C, M, where
+
+
+def repeats_relevance(Y, where, first_zero):
+    """Costs that differ between the occurrences of a repeated row (0.25, 4, 0.5 in stored order; the first 0 with first_zero)."""
+    R = relevance(Y, 9)
+    for label, at in where.items():
+        for k, p in enumerate(at):
+            R.data[Y.indptr[label] + p] = (0.0 if first_zero else 0.25, 4.0, 0.5)[k]
+    return R
+
+
+def overflow_problem(big=1e19):
+    """edge_base with rows 0 .. 4 scaled by 1e-20 (x'x is subnormal: with no diagonal the first step of alpha is 1 / QD, above FLT_MAX) and
+    rows 5 .. 9 and 30, 31 by `big` (x'x and the products w * v overflow)."""
+    X, Y = edge_base()
+    return scale_rows(scale_rows(X, range(0, 5), 1e-20), [5, 6, 7, 8, 9, 30, 31], big), Y
+
+
+def inf_ties_problem():
+    """ties_problem's duplicated columns with rows 0 .. 5 scaled by 1e-20 and no diagonal: w becomes +-inf on every feature (|w| ties among
+    f, f + 4 and f + 8), and a thirteenth feature that only row 10 stores, as an inf, makes w[12] a NaN at the set-up."""
+    X, Y = ties_problem()
+    D = np.concatenate([X.toarray(), np.zeros((X.shape[0], 1), F32)], axis=1)
+    D[10, 12] = 1.0
+    X = smat.csr_matrix(D)
+    X.sort_indices()
+    X = scale_rows(X, range(0, 6), 1e-20)
+    return set_entries(X, {(10, 12): INF}), Y
+
+
+def nan_pg_problem():
+    """An instance whose gradient becomes a NaN while its alpha lies strictly between 0 and C, beside instances that go on training: 40
+    ordinary rows over features 0 .. 75, and per private feature 76 .. 79 three rows of one entry each -- 1 (a positive: its alpha becomes
+    1), 1e-20 (a positive: without a diagonal its alpha becomes inf and w[f] = +inf) and 1e-20 (a negative: w[f] = inf - inf)."""
+    X = rows_csr(76, [5] * 30 + [70] * 10, 91, scale=0.5)
+    ptr, ind, val = list(X.indptr), list(X.indices), list(X.data)
+    for f in (76, 77, 78, 79):
+        for v in (1.0, 1e-20, 1e-20):
+            ind.append(f); val.append(v); ptr.append(len(ind))
+    Xn = smat.csr_matrix((52, 80), dtype=F32)
+    Xn.indptr, Xn.indices, Xn.data = np.array(ptr, np.int64), np.array(ind, np.int64), np.array(val, F32)
+    pos = [r for f in range(4) for r in (40 + 3 * f, 41 + 3 * f)]
+    Y = raw_csc((52, 3), [([1, 3, 8, 20, 33, 35] + pos, [1] * 14), ([0, 2, 3, 30, 31] + pos, [1] * 13), (list(range(5, 40, 4)) + pos, [1] * 17)])
+    return Xn, Y
+
+
+PARAM_VALUES = dict(
+    Cp=(0.0, 1e-310, 1e-30, 1e30, INF, float("nan"), -1.0), Cn=(0.0, 1e-310, 1e-30, 1e30, INF, float("nan"), -1.0),
+    eps=(0.0, -1.0, INF, float("nan")), threshold=(-1.0, -0.0, INF, float("nan"), 1e-45), bias=(1e-30, 1e20, INF, float("nan")))
+SNAN_BITS = 0x7FA00123                 # a signalling NaN with a payload
+
+
+def edge_cases():
+    """{name: (X, Y, C, M, R, keywords)} like cases(): non-finite, huge, tiny and zero values of X, instances with QD == 0, relevance values
+    away from ordinary costs, row ids stored twice and three times in a column of Y or M, solver parameters away from ordinary positive
+    numbers.  Every case is small enough for the plain-Python statement (N <= 200, d <= 80, at most 8 jobs, max_iter <= 30)."""
+    c = {}
+    Xb, Yb = edge_base()
+    Xr, Yr, Cr, Mr = relevance_problem()
+    Xd, Yd, Cd, Md, where = repeats_problem()
+    Xp, Yp, Cp_, Mp = problem(60, 30, 6, 2, 5, 8, 3)
+    Xo, Yo = overflow_problem()
+    Xt, Yt = inf_ties_problem()
+    zero_rows = set_entries(Xb, {(4, k): (0.0 if k % 2 else -0.0) for k in range(5)})
+    zero_rows.indptr = zero_rows.indptr.copy()
+    empty = zero_rows.copy()                                            # row 2 stores nothing, row 4 stores zeros of both signs
+    keep = np.ones(len(empty.data), bool)
+    keep[empty.indptr[2]:empty.indptr[3]] = False
+    empty.indices, empty.data = empty.indices[keep], empty.data[keep]
+    empty.indptr = np.concatenate([empty.indptr[:3], empty.indptr[3:] - 5])
+    for solver, tag in ((L1_DUAL, "l1"), (L2_DUAL, "l2")):
+        kw = dict(solver=solver, threshold=0.0, max_iter=10)
+        # ---- values of X
+        for name, X in (("qnan", special_in_both_rows(Xb, float("nan"))), ("snan", special_in_both_rows(Xb, SNAN_BITS)),
+                        ("pinf", special_in_both_rows(Xb, INF)), ("ninf", special_in_both_rows(Xb, -INF)), ("both", special_in_both_rows(Xb, INF, -INF)),
+                        ("zeros", special_in_both_rows(Xb, 0.0, -0.0))):
+            c[f"x_{name}_{tag}"] = (X, Yb, None, None, None, dict(kw))
+        for scale in (1e-20, 1e-23, 1e-30, 1e-40):
+            c[f"x_scale{scale:g}_b0_{tag}"] = (scale_rows(Xb, range(40), scale), Yb, None, None, None, dict(kw, bias=0.0))
+        c[f"x_scale1e-20_bneg_{tag}"] = (scale_rows(Xb, range(40), 1e-20), Yb, None, None, None, dict(kw, bias=-1.0))
+        for scale in (1e19, 1e25):
+            c[f"x_scale{scale:g}_{tag}"] = (scale_rows(Xb, [1, 8, 30, 33], scale), Yb, None, None, None, dict(kw))
+        c[f"x_overflow_{tag}"] = (Xo, Yo, None, None, None, dict(kw, Cp=1e39, Cn=1e39, bias=0.0, max_iter=6))
+        c[f"x_overflow25_{tag}"] = overflow_problem(1e25) + (None, None, None, dict(kw, Cp=1e39, Cn=1e39, bias=0.0, max_iter=6))
+        c[f"nan_pg_{tag}"] = nan_pg_problem() + (None, None, None, dict(kw, Cp=INF, Cn=INF, bias=0.0, eps=1e-3, max_iter=30))
+        # ---- QD == 0: an empty feature row and an all-zero one without a bias
+        for b, btag in ((0.0, "b0"), (-1.0, "bneg")):
+            c[f"qd0_{btag}_{tag}"] = (empty, Yb, None, None, None, dict(kw, bias=b))
+        # ---- relevance
+        for name, v in (("pzero", 0.0), ("nzero", -0.0), ("negative", -2.0), ("subnormal", 1e-40), ("1e30", 1e30), ("inf", INF), ("nan", float("nan"))):
+            c[f"rel_{name}_{tag}"] = (Xr, Yr, Cr, Mr, relevance_with(Yr, v), dict(kw, max_iter=15))
+        # ---- repeated row ids
+        c[f"dups_{tag}"] = (Xd, Yd, Cd, Md, None, dict(kw, max_iter=8, eps=1e-3))
+        c[f"dups_R_{tag}"] = (Xd, Yd, Cd, Md, repeats_relevance(Yd, where, False), dict(kw, max_iter=8, eps=1e-3))
+        c[f"dups_R0_{tag}"] = (Xd, Yd, Cd, Md, repeats_relevance(Yd, where, True), dict(kw, max_iter=8, eps=1e-3))
+        c[f"dups_pure_R0_{tag}"] = (Xd, Yd, None, None, repeats_relevance(Yd, where, True), dict(kw, max_iter=4, eps=1e-3))
+        Mm = raw_csc((40, 2), [(list(range(0, 20)) + [3, 6], [1] * 22), (list(range(10, 30)) + [12, 12], [1] * 22)])     # rows 3 and 12 are positives, 6 is not
+        c[f"mdup_{tag}"] = (Xr, Yr, Cr, Mm, None, dict(kw, max_iter=15))
+        # ---- solver parameters
+        for par, values in PARAM_VALUES.items():
+            for v in values:
+                name = f"par_{par}_{v!r}_{tag}".replace("-", "m").replace(".", "p").replace("+", "")
+                c[name] = (Xp, Yp, Cp_, Mp, None, dict(dict(kw, max_iter=12, threshold=0.01), **{par: v}))
+        for k in (1, 3):
+            c[f"inf_ties_maxnz{k}_{tag}"] = (Xt, Yt, None, None, None, dict(kw, Cp=INF, Cn=INF, bias=1e-25, max_nonzeros=k, max_iter=5))
+    return c
+
+
+# edge cases that also go through the dense entry point: the NaN and inf matrices, where every row stores every column (zeros that meet a NaN or an infinite w)
+EDGE_DENSE = tuple(f"x_{n}_{t}" for n in ("qnan", "snan", "pinf", "ninf", "both", "overflow", "overflow25") for t in ("l1", "l2"))
+REPEAT_CASES = tuple(f"{n}_{t}" for n in ("dups", "dups_R", "dups_R0", "dups_pure_R0", "mdup") for t in ("l1", "l2"))
+
+
 def scale_problem():
     """20 000 rows x 2 000 labels under 64 clusters (too large for the plain-Python statement: checked against the reference only)."""
     X, Y, C, M = problem(20000, 5000, 2000, 64, 20, 30, 41)
@@ -441,6 +730,21 @@ def digest(coo):
 
 # the cases on which each wrong variant must differ from the reference
 VARIANT_CASES = {"pairwise": ("order_l2", "order_l1"), "alpha64": ("order_l2", "order_l1")}
+# ... and the same for the edge cases.  "fmax" is listed without a case ON PURPOSE: PGmax_new starts at -inf and std::max(PGmax_new, PG) =
+# PGmax_new < PG ? PG : PGmax_new never takes a NaN PG, so PGmax_new is never a NaN, and for a first argument that is no NaN std::max and
+# fmax return the same number (up to the sign of a zero, which no later comparison reads); the same holds for std::min and fmin.  No
+# input can tell them apart -- tests/test_ranker_training_edges_cpu.py holds that on every case that meets a NaN PG.  The order of the
+# arguments is what matters under a NaN: "nan_kept" (std::max(PG, PGmax_new)) is the variant that differs.
+EDGE_VARIANT_CASES = {"dup_last_first": ("dups_l1", "dups_l2", "dups_R_l1", "dups_R_l2", "dups_R0_l1", "dups_R0_l2"), "fmax": (),
+                      "nan_kept": ("nan_pg_l1", "nan_pg_l2")}
+
+
+def dense_bits(X):
+    """X (CSR) as an ndarray with every stored value's bits kept (toarray() adds the values to zeros, which quiets a signalling NaN)."""
+    D = np.zeros(X.shape, F32)
+    for r in range(X.shape[0]):
+        D[r, X.indices[X.indptr[r]:X.indptr[r + 1]]] = X.data[X.indptr[r]:X.indptr[r + 1]]
+    return D
 
 
 def dense_ok(X):

@@ -10,6 +10,7 @@ import scipy.sparse as smat
 
 import ranker_training_rule as rr
 from conftest import GOLDEN
+from ranker_training_rule import as_stored_transpose, resident, wt_as_coo
 
 pytestmark = pytest.mark.gpu
 
@@ -67,28 +68,6 @@ def test_drm_entry_point(name):
     D = np.ascontiguousarray(X.toarray())
     got, err = rr.run_library(rr.OURS, D, Y, C, M, R, **kw)
     check(name, got, err, D, dense=True)
-
-
-def as_stored_transpose(A):
-    """The CSC arrays of A as the CSR of its transpose, exactly as stored (what the solver reads)."""
-    t = smat.csr_matrix((A.shape[1], A.shape[0]), dtype=np.float32)
-    t.indptr, t.indices, t.data = A.indptr.astype(np.int64), A.indices.astype(np.int64), A.data.astype(np.float32)
-    return t
-
-
-def resident(X, Y, C, M, R, kw, stream=None):
-    """xrl_train_layer_device over uploaded handles -> (W^T as a scipy CSR with the stored order kept, counters)."""
-    from pecos_amd import DeviceMatrix, clib
-    hs = [DeviceMatrix.upload(X)] + [None if A is None else DeviceMatrix.upload(as_stored_transpose(A)) for A in (Y, C, M, R)]
-    out = DeviceMatrix(clib.train_layer_device(*(h and h.handle for h in hs), threshold=kw.get("threshold", 0.0), max_nonzeros_per_label=kw.get("max_nonzeros", 0),
-                                               solver_type=kw.get("solver", rr.L1_DUAL), Cp=kw.get("Cp", 1.0), Cn=kw.get("Cn", 1.0), max_iter=kw.get("max_iter", 1000),
-                                               eps=kw.get("eps", 0.1), bias=kw.get("bias", 1.0), stream=stream))
-    return out.download(), clib.debug_train_counters()
-
-
-def wt_as_coo(Wt):
-    """W^T (CSR, labels x features) as (rows = features, cols = labels, vals) in stored order."""
-    return Wt.indices.astype(np.uint64), np.repeat(np.arange(Wt.shape[0]), np.diff(Wt.indptr)).astype(np.uint64), Wt.data
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
