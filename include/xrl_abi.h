@@ -613,6 +613,44 @@ void* xrl_train_layer_device(void* X, void* Yt, void* Ct_or_null, void* Mt_or_nu
                              int solver_type, double Cp, double Cn, uint64_t max_iter, double eps, double bias, void* hip_stream);
 int xrl_debug_train_counters(uint64_t* out, uint32_t n);
 
+/* Matcher-aware negatives (MAN) on the device: what joins a trained layer, its prediction and the next layer's matching matrix in HBM
+ * (K14, csrc/xrl_match.hip; pecos_amd.train_chain_device runs the reference's loop, pecos/xmc/base.py:1512-1572, over them).
+ * Rule U, xrl_smat_pattern_union_device(mats, n): n >= 1 matrix handles of one shape on one device.  A NEW owned CSR handle of that shape
+ *   that stores 1.0f at (r, c) wherever at least one operand stores an entry at (r, c).  Values are never read: explicit zeros, NaN and
+ *   negative values count.  An operand's row may store its columns in any order (a handle of xrl_smat_from_device_result is best first)
+ *   and the same column more than once; every output row is strictly ascending, the row pointer u64.  This is the reference's
+ *   M = csc_matrix(shape); M += binarized(A); M += binarized(B); ...; sort_indices() (base.py:1544-1565, 570-573) up to the values: where
+ *   the reference stores 2.0 or 3.0 (an entry listed by two or three sources) this stores 1.0 -- the trainer reads only M's pattern.
+ *   One wavefront per row orders the operands' column ids in LDS (rows of at most 1024 stored entries over all operands; longer rows
+ *   through a segmented sort in HBM) and drops equal neighbours; count, scan, fill.  Runs on hip_stream and synchronises it.
+ *   Refused, messages starting with the function's name.  Before a GPU is required: n == 0, a null handle, shapes that differ, operands
+ *   on two devices.  By a check kernel: a column id that is not below cols (a refusal, the id is never an address); a row that stores 2^31
+ *   entries or more over the operands.  NULL + xrl_last_error on failure.
+ * Rule P, xrl_single_layer_predict_device: the resident form of c_xlinear_single_layer_predict_csr_f32 -- the same rule and the same bits,
+ *   because it runs the same CSC route (K0 -> K1C -> K2) through the same row batches under the same workspace budget.  X: a CSR handle
+ *   of the instances, read in place.  Wt: labels x (features + (bias > 0)), the CSC of W as xrl_train_layer_device leaves it, copied
+ *   device to device (W never visits the host).  Ct: clusters x labels, the handle training took, copied to the host once for the tree
+ *   bookkeeping (nr_labels entries); NULL = one cluster that holds every label.  Codes: a fixed-stride result in HBM (row r is
+ *   d_codes_idx / d_codes_val [r * codes_stride ..], d_codes_cnt[r] entries; a count above the stride reads as the stride), used in place
+ *   as the initial beam; a parent may be listed more than once and every occurrence is prolongated.  All three NULL = no csr_codes:
+ *   with one cluster the implicit root, with several fill_ones (every cluster, score 1, no combine; libpecos.cpp:215-222).  The candidate
+ *   row is sized by one kernel over the codes -- per row the sum over listed parents of their child counts, max-reduced -- and ONE 8-byte
+ *   readback: after the copy of C, the call's only host synchronisation before the result.  Result: xrl_predict_device's contract -- row r of d_out_idx /
+ *   d_out_val (row stride out_stride >= only_topk) holds d_out_cnt[r] pairs best first, entries beyond the count untouched, labels in the
+ *   layer's own ids.  Runs on hip_stream (NULL: the default stream is synchronised, then a stream of the call's own) and synchronises it.
+ *   Refused, messages starting with the function's name: null handles or outputs; only_topk == 0; out_stride < only_topk; codes given in
+ *   part; operands on two devices; "Feature dimension of query and W do not match"; "Label dimension of C and
+ *   W do not match"; by the bound kernel, "csr_codes: parent id .. out of range" (found and refused, never followed).  0 / -1.
+ *   XRL_SINGLE_LAYER_MAX_BATCH_ROWS in the environment is the predict option max_batch_rows of the call's one-layer handle (tests).
+ *   xrl_debug_match_forms        FOR TESTS ONLY: out[0..n), n <= 5 <- {rows served in LDS, rows served by the HBM sort, entries read,
+ *                                entries written (all four summed over the unions since the load), the candidate bound of the last
+ *                                xrl_single_layer_predict_device} */
+void* xrl_smat_pattern_union_device(void* const* mats, uint32_t n, void* hip_stream);
+int xrl_single_layer_predict_device(void* X, void* Wt, void* Ct_or_null, const uint32_t* d_codes_idx, const float* d_codes_val, const uint32_t* d_codes_cnt,
+                                    uint32_t codes_stride, const char* post_processor, uint32_t only_topk, float bias, uint32_t* d_out_idx, float* d_out_val,
+                                    uint32_t* d_out_cnt, uint32_t out_stride, void* hip_stream);
+int xrl_debug_match_forms(uint64_t* out, uint32_t n);
+
 /* predict_on_selected_outputs on the device (K7 + K4): score a given set of labels per query row through the tree, with labels, plan and
  * scores resident in HBM.  The labels arrive in the fixed-stride form xrl_predict_device writes and xrl_ensemble_device reads: row r is
  * d_sel_idx[r*sel_stride ..], d_sel_cnt[r] entries long (NULL = sel_stride each; a count above the stride is read as the stride), in any

@@ -287,6 +287,10 @@ class corelib(object):
         "xrl_train_layer_device": (c_void_p, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_uint32, c_int, c_double, c_double, c_uint64, c_double,
                                               c_double, c_void_p]),
         "xrl_debug_train_counters": (c_int, [POINTER(c_uint64), c_uint32]),
+        "xrl_smat_pattern_union_device": (c_void_p, [POINTER(c_void_p), c_uint32, c_void_p]),
+        "xrl_single_layer_predict_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, c_float, c_void_p,
+                                                    c_void_p, c_void_p, c_uint32, c_void_p]),
+        "xrl_debug_match_forms": (c_int, [POINTER(c_uint64), c_uint32]),
         "xrl_inspect_model": (c_int, [c_char_p, POINTER(c_uint64), c_uint32]),
         "xrl_model_create": (c_void_p, [c_uint32, c_void_p, c_void_p, POINTER(c_float), POINTER(c_uint32), POINTER(c_char_p)]),
         "xrl_queries_upload_csr": (c_void_p, [c_void_p, POINTER(ScipyCsrF32)]),
@@ -716,6 +720,35 @@ class corelib(object):
         self.clib_float32.xrl_debug_train_counters(out, len(self.TRAIN_COUNTERS))
         self._check()
         return dict(zip(self.TRAIN_COUNTERS, (int(v) for v in out)))
+
+    # ------------------------------------------------------------------ matching matrices and a trained layer's prediction in HBM (K14)
+    MATCH_FORMS = ("lds_rows", "big_rows", "read", "written", "last_bound")
+
+    def smat_pattern_union_device(self, handles, stream=None):
+        """A new matrix handle that stores a 1 wherever one of the matrix handles (one shape, one device) stores an entry, rows ascending."""
+        handles = list(handles)
+        arr = (c_void_p * max(len(handles), 1))(*handles)
+        h = self.clib_float32.xrl_smat_pattern_union_device(arr, len(handles), c_void_p(stream or 0))
+        self._check()
+        return h
+
+    def single_layer_predict_device(self, X, Wt, Ct, codes_idx, codes_val, codes_cnt, codes_stride, post_processor, only_topk, bias, out_idx, out_val, out_cnt,
+                                    out_stride, stream=None):
+        """One layer predicted from matrix handles (X, W^T, C^T or None) and codes in HBM (raw addresses, all None: no csr_codes) into the
+        caller's fixed-stride device buffers; synchronises ``stream``."""
+        rc = self.clib_float32.xrl_single_layer_predict_device(c_void_p(X), c_void_p(Wt), c_void_p(Ct or 0), c_void_p(codes_idx or 0), c_void_p(codes_val or 0),
+                                                               c_void_p(codes_cnt or 0), int(codes_stride), self._cstr(post_processor), int(only_topk), float(bias),
+                                                               c_void_p(out_idx or 0), c_void_p(out_val or 0), c_void_p(out_cnt or 0), int(out_stride),
+                                                               c_void_p(stream or 0))
+        self._check()
+        return rc
+
+    def debug_match_forms(self):
+        """Debug counters of K14 since the load (``xrl_debug_match_forms``), by name."""
+        out = (c_uint64 * len(self.MATCH_FORMS))()
+        self.clib_float32.xrl_debug_match_forms(out, len(self.MATCH_FORMS))
+        self._check()
+        return dict(zip(self.MATCH_FORMS, (int(v) for v in out)))
 
     # ------------------------------------------------------------------ label clustering (K11)
     def run_clustering(self, py_feat_mat, train_params, codes=None):

@@ -1,10 +1,13 @@
 // In-memory models and the entry points around caller-owned weights: xrl_model_create, the single-layer API with its handle cache,
 // predict-on-selected-outputs, and the sparse inner products -- with their extern "C" wrappers.
+#include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <mutex>
 
 #include "xrl_host_pipeline.h"
+#include "xrl_match.h"
 
 using namespace xrl;
 
@@ -176,6 +179,100 @@ void single_layer_predict(const HostX& x, const ScipyCsrF32* csr_codes, ScipyCsc
     run_and_emit(m, X, o, alloc);
 }
 
+// The resident form (xrl_single_layer_predict_device): X, W^T and the codes are in HBM already.  The one-layer model is compiled around an
+// EMPTY weight pattern (tree bookkeeping only, from a host copy of C: nr_labels entries) and W's CSC arrays -- the CSR arrays of W^T -- are
+// copied device to device; then the same CSC route through the same predict_device as the host form.
+const Queries& sl_handle(const std::string& what, void* p, const char* name) {
+    if (!p) fail(what + "null matrix handle (" + name + ")");
+    const Queries& m = *static_cast<Queries*>(p);
+    if (m.dev.dense) fail(what + name + " must be a CSR handle");
+    return m;
+}
+
+void single_layer_predict_device(void* Xh, void* Wth, void* Cth, const uint32_t* d_ci, const float* d_cv, const uint32_t* d_cc, uint32_t c_stride, const char* pp,
+                                 uint32_t only_topk, float bias, uint32_t* d_oi, float* d_ov, uint32_t* d_oc, uint32_t out_stride, hipStream_t s) {
+    const std::string what = "xrl_single_layer_predict_device: ";
+    const Queries& x = sl_handle(what, Xh, "X");
+    const Queries& wt = sl_handle(what, Wth, "Wt");
+    const Queries* ct = Cth ? &sl_handle(what, Cth, "Ct") : nullptr;
+    if (only_topk == 0) fail(what + "only_topk must be positive");
+    if (out_stride < only_topk) fail(what + "out_stride (" + std::to_string(out_stride) + ") is smaller than only_topk (" + std::to_string(only_topk) + ")");
+    if (!d_oi || !d_ov || !d_oc) fail(what + "null output buffer");
+    const bool with_codes = d_ci || d_cv || d_cc;
+    if (with_codes && (!d_ci || !d_cv || !d_cc)) fail(what + "csr_codes: labels, scores and counts come together or not at all");
+    if (with_codes && c_stride == 0) fail(what + "csr_codes: a stride of 0");
+    const char* pps = pp ? pp : "noop";                    // (an unknown name is the identity, as in the host form and the reference)
+    for (const Queries* o : {&wt, ct})
+        if (o && o->device != x.device) fail(what + "the operands are on devices " + std::to_string(x.device) + " and " + std::to_string(o->device) + "; a predict needs all on one");
+    const uint32_t w_rows = wt.dev.cols, labels = wt.dev.rows;
+    if (x.dev.cols + (bias > 0 ? 1u : 0u) != w_rows)
+        fail(what + "Feature dimension of query and W do not match (X has " + std::to_string(x.dev.cols) + " columns, bias " + (bias > 0 ? "adds one" : "adds none") + ", W has " +
+             std::to_string(w_rows) + " rows)");
+    if (ct && ct->dev.cols != labels) fail(what + "Label dimension of C and W do not match (" + std::to_string(ct->dev.cols) + " != " + std::to_string(labels) + ")");
+    require_gpu();
+    use_device(x.device);
+
+    // the tree bookkeeping: C on the host (Ct's CSR arrays are C's CSC arrays), or one cluster that holds every label
+    HostCsc c;
+    c.rows = labels;
+    if (ct) {
+        c.cols = ct->dev.rows;
+        c.col_ptr.resize((size_t)c.cols + 1); c.row_idx.resize((size_t)ct->dev.nnz); c.val.resize((size_t)ct->dev.nnz);
+        XRL_HIP(hipStreamSynchronize(s));
+        download_csr(ct->dev, c.col_ptr.data(), c.row_idx.data(), c.val.data());
+        if (c.col_ptr[c.cols] != ct->dev.nnz) fail(what + "Ct's row pointer does not end at its entry count");
+        for (uint32_t p = 0; p < c.cols; ++p) if (c.col_ptr[p + 1] < c.col_ptr[p]) fail(what + "Ct's row pointer does not ascend");
+        for (uint32_t l : c.row_idx) if (l >= labels) fail(what + "Ct holds an id that is not below " + std::to_string(labels));
+    } else {
+        c.cols = 1; c.col_ptr = {0, labels};
+        c.row_idx.resize(labels); c.val.assign(labels, 1.f);
+        for (uint32_t i = 0; i < labels; ++i) c.row_idx[i] = i;
+    }
+    HostCsc w;                                             // shape only: compile_layer(structure_only) reads no weight
+    w.rows = w_rows; w.cols = labels; w.col_ptr.assign((size_t)labels + 1, 0);
+    Model m;
+    m.csc_route = true; m.weight_matrix_type = 0; m.device = x.device;
+    m.layers.push_back(compile_layer(w, c, bias, 0, "noop", nullptr, 0, /*structure_only=*/true));
+    Layer& L = *m.layers[0];
+    L.w_absmax = INFINITY;                                 // the weights were never on the host: nothing is priced with them (the CSC route does not prune)
+    finalize_model(m);
+    if (!s) { XRL_HIP(hipStreamSynchronize(nullptr)); s = m.stream; }   // the default stream: what it holds is done, then the model's own (as the host form runs)
+    L.d_csc_ptr.reserve(((size_t)labels + 1) * 8); L.d_csc_idx.reserve((size_t)wt.dev.nnz * 4); L.d_csc_val.reserve((size_t)wt.dev.nnz * 4);
+    XRL_HIP(hipMemcpyAsync(L.d_csc_ptr.p, wt.dev.row_ptr, ((size_t)labels + 1) * 8, hipMemcpyDeviceToDevice, s));
+    if (wt.dev.nnz) {
+        XRL_HIP(hipMemcpyAsync(L.d_csc_idx.p, wt.dev.col_idx, (size_t)wt.dev.nnz * 4, hipMemcpyDeviceToDevice, s));
+        XRL_HIP(hipMemcpyAsync(L.d_csc_val.p, wt.dev.val, (size_t)wt.dev.nnz * 4, hipMemcpyDeviceToDevice, s));
+    }
+    L.csc_ready = true;
+    m.ws = std::make_unique<Workspace>();
+    if (const char* e = std::getenv("XRL_SINGLE_LAYER_MAX_BATCH_ROWS")) m.opt.max_batch_rows = std::strtoll(e, nullptr, 10);   // (tests: few rows in several batches)
+
+    PredictOpts o; o.only_topk = only_topk; o.post_processor = pps; o.csc_route = true;
+    const uint32_t P = L.c_cols;
+    BeamDev init{};
+    if (with_codes) {
+        // the codes are used in place; their parents are checked and the candidate row sized by one kernel and one 8-byte readback
+        bool bad = false;
+        const uint64_t bound = beam_cand_bound_device(d_ci, d_cc, c_stride, x.dev.rows, L.dev.chunk_col, P, s, bad);
+        if (bad) fail(what + "csr_codes: parent id " + std::to_string(bound) + " out of range (C has " + std::to_string(P) + " columns)");
+        note_cand_bound(std::max<uint64_t>(1, bound));
+        o.initial_cand_bound = std::max<uint64_t>(1, bound);
+        init = BeamDev{const_cast<uint32_t*>(d_ci), const_cast<float*>(d_cv), const_cast<uint32_t*>(d_cc), c_stride};
+        o.initial = &init; o.initial_max = c_stride;
+    } else if (P > 1) {   // fill_ones(X.rows, C->cols): every parent, score 1, and NO combine
+        Workspace& ws = *m.ws;
+        const size_t n = (size_t)x.dev.rows * P;
+        ws.init_idx.reserve(n * 4); ws.init_val.reserve(n * 4); ws.init_cnt.reserve((size_t)x.dev.rows * 4);
+        fill_ones_beam_device(ws.init_idx.as<uint32_t>(), ws.init_val.as<float>(), ws.init_cnt.as<uint32_t>(), x.dev.rows, P, s);
+        init = BeamDev{ws.init_idx.as<uint32_t>(), ws.init_val.as<float>(), ws.init_cnt.as<uint32_t>(), P};
+        o.initial = &init; o.initial_max = P;
+        note_cand_bound(labels);
+    } else note_cand_bound(labels);
+    o.no_prev_pred = !with_codes;   // combine only when csr_codes were given (libpecos.cpp:215-222)
+    if (x.dev.rows) predict_device(m, x.dev, o, d_oi, d_ov, d_oc, out_stride, s, /*sync=*/true);
+    else XRL_HIP(hipStreamSynchronize(s));
+}
+
 // X to the device, the scores of S's pattern, and their hand-off through the allocator: S's row pointer, the scores in its order
 void predict_selected_emit(Model& m, const HostX& x, const ScipyCsrF32* S, const char* pp, const SelectedInit* init, py_sparse_allocator_t alloc) {
     QueriesDev X{};
@@ -287,6 +384,16 @@ void c_xlinear_single_layer_predict_on_selected_outputs_drm_f32(const ScipyDrmF3
                                                                 const char* post_processor_str, const int /*num_threads*/,
                                                                 const float bias, py_sparse_allocator_t pred_alloc) {
     guarded([&] { single_layer_selected(HostX(input_x), selected_outputs_csr, csr_codes, W, C, post_processor_str, bias, pred_alloc); });
+}
+
+int xrl_single_layer_predict_device(void* X, void* Wt, void* Ct_or_null, const uint32_t* d_codes_idx, const float* d_codes_val, const uint32_t* d_codes_cnt,
+                                    uint32_t codes_stride, const char* post_processor, uint32_t only_topk, float bias, uint32_t* d_out_idx, float* d_out_val,
+                                    uint32_t* d_out_cnt, uint32_t out_stride, void* hip_stream) {
+    return guarded_value(-1, [&] {
+        single_layer_predict_device(X, Wt, Ct_or_null, d_codes_idx, d_codes_val, d_codes_cnt, codes_stride, post_processor, only_topk, bias, d_out_idx, d_out_val,
+                                    d_out_cnt, out_stride, static_cast<hipStream_t>(hip_stream));
+        return 0;
+    });
 }
 
 void xrl_single_layer_cache_clear(void) {

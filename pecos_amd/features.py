@@ -470,6 +470,13 @@ class DeviceMatrix:
         mats = list(mats)
         return cls(clib.smat_hstack_device([m.handle for m in mats], stream=stream))
 
+    @classmethod
+    def pattern_union(cls, mats, stream=None):
+        """A new :class:`DeviceMatrix` that stores a 1 wherever one of ``mats`` (one shape, one device) stores an entry -- explicit zeros
+        and NaN count, values are never read --, every row ascending (K14; rule U at ``xrl_smat_pattern_union_device``)."""
+        mats = list(mats)
+        return cls(clib.smat_pattern_union_device([m.handle for m in mats], stream=stream))
+
 
 def result_to_csr_device(result, n_cols=0, stream=None):
     """A result triple (:func:`result_buffers`' form; counts may be None = full rows) as CSR tensors on its device: ``(crow int64 [rows + 1],

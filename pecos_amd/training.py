@@ -1,7 +1,20 @@
-"""Ranker training with the operands and the weights resident in HBM (K13): :func:`train_layer_device`, the last link of
-``label_embedding_device -> run_clustering_device -> train_layer_device``.  The weights are the reference's at ``threads = 1`` bit for
-bit (``xrl_train_layer_device`` in include/xrl_abi.h states the rule)."""
+"""Ranker training with the operands and the weights resident in HBM: :func:`train_layer_device` (K13), the last link of
+``label_embedding_device -> run_clustering_device -> train_layer_device``; :func:`single_layer_predict_device`, a trained layer's
+prediction from HBM; and :func:`train_chain_device`, the reference's layer loop (pecos/xmc/base.py:1512-1572) with X, Y, the label chain,
+the matching matrices (K14), the predictions and the weights in HBM from the first layer to the last -- which is what serves matcher-aware
+negatives (``man``).  The weights are the reference's at ``threads = 1`` bit for bit (``xrl_train_layer_device``,
+``xrl_smat_pattern_union_device`` and ``xrl_single_layer_predict_device`` in include/xrl_abi.h state the rules)."""
+import copy
+
 from .core import clib
+
+TRAIN_KEYS = ("threshold", "max_nonzeros_per_label", "solver_type", "Cp", "Cn", "max_iter", "eps", "bias")
+
+
+def _train_transposed(x, yt, ct, mt, rt, stream, **params):
+    """K13 over :class:`DeviceMatrix` operands that are transposed already."""
+    from .features import DeviceMatrix
+    return DeviceMatrix(clib.train_layer_device(x.handle, yt.handle, ct and ct.handle, mt and mt.handle, rt and rt.handle, stream=stream, **params))
 
 
 def train_layer_device(X, Y, C=None, M=None, R=None, threshold=0.1, max_nonzeros_per_label=None, solver_type="L2R_L2LOSS_SVC_DUAL", Cp=1.0, Cn=1.0,
@@ -14,7 +27,7 @@ def train_layer_device(X, Y, C=None, M=None, R=None, threshold=0.1, max_nonzeros
     (:meth:`DeviceMatrix.transpose`, scipy's stable order: a column's entries by ascending row).  Returns W^T as a new
     :class:`~pecos_amd.features.DeviceMatrix`: labels x (features + (bias > 0)) in CSR, which is the CSC of W.  Runs on ``stream``
     (default: torch's current one), which it synchronises."""
-    from .features import DeviceMatrix, _as_device_matrix, _operand_device, _stream_or_current
+    from .features import _as_device_matrix, _operand_device, _stream_or_current
     ops = [X, Y, C, M, R]
     dev = next((d for d in (_operand_device(o) for o in ops if o is not None) if d is not None), 0)
     s = _stream_or_current(dev, stream)
@@ -25,6 +38,145 @@ def train_layer_device(X, Y, C=None, M=None, R=None, threshold=0.1, max_nonzeros
         m = None
     yt = y.transpose(stream=s)
     ct, mt, rt = (None if o is None else o.transpose(stream=s) for o in (c, m, r))
-    h = clib.train_layer_device(x.handle, yt.handle, ct and ct.handle, mt and mt.handle, rt and rt.handle, threshold=threshold,
-                                max_nonzeros_per_label=max_nonzeros_per_label, solver_type=solver_type, Cp=Cp, Cn=Cn, max_iter=max_iter, eps=eps, bias=bias, stream=s)
-    return DeviceMatrix(h)
+    return _train_transposed(x, yt, ct, mt, rt, s, threshold=threshold, max_nonzeros_per_label=max_nonzeros_per_label, solver_type=solver_type, Cp=Cp, Cn=Cn,
+                             max_iter=max_iter, eps=eps, bias=bias)
+
+
+def _predict_transposed(x, wt, ct, codes, post_processor, only_topk, bias, stream, out_stride=None):
+    """``xrl_single_layer_predict_device`` over :class:`DeviceMatrix` operands (``ct`` = C^T or None) and a codes triple or None: a new
+    zeroed result triple of ``out_stride`` (default ``only_topk``) cells per row."""
+    import torch
+    from .features import result_buffers
+    info = x.info
+    rows, dev = info["rows"], torch.device("cuda", info["device"])
+    stride = only_topk if out_stride is None else out_stride
+    with torch.cuda.device(dev):
+        out = result_buffers(rows, max(int(stride), 0), dev, sync=True)
+        if codes is None:
+            ci = cv = cc = None
+            c_stride = 0
+        else:
+            ci, cv, cc = codes[:3]
+            if ci.dim() != 2 or ci.shape != cv.shape or ci.dtype != torch.int32 or cv.dtype != torch.float32:
+                raise ValueError("single_layer_predict_device: codes are (labels int32 [rows, k], scores float32 [rows, k], counts int32 [rows] or None)")
+            if ci.shape[0] != rows:
+                raise ValueError("single_layer_predict_device: Instance dimension of query and prev_layer_pred matrix do not match")
+            n_parents = 1 if ct is None else ct.shape[0]
+            if len(codes) > 3 and codes[3] is not None and codes[3] != n_parents:
+                raise ValueError("single_layer_predict_device: Label dimension of prev_layer_pred and C matrix do not match")
+            ci, cv = ci.contiguous(), cv.contiguous()
+            c_stride = ci.shape[1]
+            cc = torch.full((rows,), c_stride, dtype=torch.int32, device=dev) if cc is None else cc.contiguous()
+            if cc.dtype != torch.int32 or cc.shape != (rows,):
+                raise ValueError("single_layer_predict_device: counts are int32 [rows]")
+            torch.cuda.current_stream().synchronize()
+        clib.single_layer_predict_device(x.handle, wt.handle, ct and ct.handle, None if ci is None else ci.data_ptr(), None if cv is None else cv.data_ptr(),
+                                         None if cc is None else cc.data_ptr(), c_stride, post_processor, only_topk, bias,
+                                         out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), stride, stream=stream)
+    return out
+
+
+def single_layer_predict_device(X, Wt, C=None, codes=None, post_processor="l3-hinge", only_topk=20, bias=1.0, stream=None, out_stride=None):
+    """One layer's prediction with every operand in HBM: the resident form of ``clib.xlinear_single_layer_predict`` (the reference's
+    ``MLModel.predict`` on sparse X), the same bits.  ``X`` (instances x features) and ``C`` (labels x clusters; None: one cluster) are
+    operands as :func:`train_layer_device` takes them; ``Wt`` is that function's result (or any labels x (features + (bias > 0)) CSR
+    operand); ``codes`` is None or a result triple ``(parents int32 [rows, k], scores float32 [rows, k], counts int32 [rows] or None)``
+    -- this function's own output, fed back -- optionally with the parents' count as a fourth element.  Returns a result triple
+    ``(labels int32 [rows, out_stride], scores float32, counts int32 [rows])``, rows best first, on the operands' device.  Runs on
+    ``stream`` (default: torch's current one), which it synchronises."""
+    from .features import _as_device_matrix, _operand_device, _stream_or_current
+    ops = [X, Wt, C]
+    dev = next((d for d in (_operand_device(o) for o in ops if o is not None) if d is not None), None)
+    if dev is None:
+        dev = codes[0].device.index if codes is not None else 0
+    s = _stream_or_current(dev, stream)
+    x, wt, c = (None if o is None else _as_device_matrix(o, dev, None, stream) for o in ops)
+    ct = None if c is None else c.transpose(stream=s)
+    return _predict_transposed(x, wt, ct, codes, post_processor, only_topk, bias, s, out_stride)
+
+
+def _per_layer(value, depth, name):
+    if isinstance(value, (list, tuple)):
+        if len(value) != depth:
+            raise ValueError(f"len({name})={len(value)} != {depth}")
+        return list(value)
+    return [copy.deepcopy(value) for _ in range(depth)]
+
+
+def _params_dict(p):
+    d = p if isinstance(p, dict) else p.to_dict()
+    return {k: d[k] for k in TRAIN_KEYS if k in d}
+
+
+def train_chain_device(X, Y, chain, neg_mining_chain="tfn", matching_chain=None, relevance_chain=None, train_params=None, pred_params=None,
+                       return_matching=False, stream=None):
+    """The layers of a cluster chain trained top down with everything resident in HBM (pecos/xmc/base.py:1512-1572).  ``X`` (instances x
+    features) and ``Y`` (instances x labels) are operands as :func:`train_layer_device` takes them; ``chain`` is the list of ``C``
+    matrices, root first (an entry None: a one-versus-all layer, only as a one-element chain); ``neg_mining_chain`` is one scheme or one
+    per layer, a sum of ``tfn`` (the layer above's labels), ``usn`` (``matching_chain[t]``) and ``man`` (the prediction of the layers
+    trained so far, with layer t-1's own ``only_topk`` and ``post_processor`` from ``pred_params``); ``train_params`` / ``pred_params`` are
+    one ``MLModel.TrainParams`` / ``PredParams`` (or dict) or one per layer.  The label chain is ``Y_t = Y_(t+1) * C_(t+1)`` by the device
+    sparse product; layer t's matching matrix is K14's union of its sources, and the half-trained chain predicts X layer by layer through
+    :func:`single_layer_predict_device` whenever a scheme from layer t on contains ``man``, each result fed back as the next codes without
+    leaving HBM.  Returns the list of W^T as :class:`~pecos_amd.features.DeviceMatrix`; with ``return_matching`` also the list of matching
+    matrices (None where a layer has none) and the list of predictions that entered them (result triples, None where none was run).  X is
+    uploaded once; nothing but each ``C`` (a predict's tree bookkeeping) and 8-byte bounds and counters crosses to the host."""
+    from .features import DeviceMatrix, _as_device_matrix, _operand_device, _stream_or_current
+    from .xlinear import MLModel
+    chain = list(chain)
+    depth = len(chain)
+    if depth == 0:
+        raise ValueError("train_chain_device: an empty chain")
+    if any(C is None for C in chain) and depth != 1:
+        raise ValueError("train_chain_device: a layer without C is a one-element chain")
+    for name, given in (("matching_chain", matching_chain), ("relevance_chain", relevance_chain)):
+        if given is not None and len(given) != depth:
+            raise ValueError(f"len({name})={len(given)} != {depth}")
+    schemes = [s.lower() for s in _per_layer(neg_mining_chain, depth, "neg_mining_chain")]
+    tps = [_params_dict(MLModel.TrainParams.from_dict(p)) for p in _per_layer(MLModel.TrainParams() if train_params is None else train_params, depth, "train_params")]
+    pps = [MLModel.PredParams.from_dict(p) for p in _per_layer(MLModel.PredParams() if pred_params is None else pred_params, depth, "pred_params")]
+    ops = [X, Y] + chain + list(matching_chain or []) + list(relevance_chain or [])
+    dev = next((d for d in (_operand_device(o) for o in ops if o is not None) if d is not None), 0)
+    s = _stream_or_current(dev, stream)
+
+    def resident(o):
+        return None if o is None else _as_device_matrix(o, dev, None, stream)
+
+    x, cs = resident(X), [resident(C) for C in chain]
+    usn = [resident(m) for m in matching_chain] if matching_chain is not None else [None] * depth
+    rel = [resident(r) for r in relevance_chain] if relevance_chain is not None else [None] * depth
+    labels_of = [None] * depth                              # Y_t = Y_(t+1) * C_(t+1), bottom up
+    labels_of[-1] = resident(Y)
+    for t in range(depth - 2, -1, -1):
+        labels_of[t] = labels_of[t + 1].multiply(cs[t + 1], stream=s)
+    n_inst = x.shape[0]
+    cts = [None if c is None else c.transpose(stream=s) for c in cs]
+    weights, matchings, predictions = [], [], []
+    m_pred = None
+    for t in range(depth):
+        c, ct = cs[t], cts[t]
+        pred_t = None
+        if t > 0 and any("man" in sc for sc in schemes[t:]):
+            m_pred = _predict_transposed(x, weights[t - 1], cts[t - 1], m_pred, pps[t - 1].post_processor, pps[t - 1].only_topk, tps[t - 1]["bias"], s)
+            pred_t = m_pred
+        if c is None or (t == 0 and c.shape[1] == 1):
+            m = None
+        else:
+            parts = []
+            if "usn" in schemes[t] and usn[t] is not None:
+                parts.append(usn[t])
+            if "tfn" in schemes[t]:
+                parts.append(labels_of[t - 1] if t else labels_of[0].multiply(c, stream=s))
+            if "man" in schemes[t] and t > 0:
+                parts.append(DeviceMatrix.from_result(m_pred, c.shape[1], stream=s))
+            if not parts:                                   # a scheme that names no source, or only absent ones: an empty M, as in the reference
+                import scipy.sparse as smat
+                parts.append(DeviceMatrix.upload(smat.csr_matrix((n_inst, c.shape[1]), dtype="float32"), dev))
+            m = DeviceMatrix.pattern_union(parts, stream=s)
+        yt = labels_of[t].transpose(stream=s)
+        mt = None if m is None else m.transpose(stream=s)
+        rt = None if rel[t] is None else rel[t].transpose(stream=s)
+        weights.append(_train_transposed(x, yt, ct if m is not None else None, mt, rt, s, **tps[t]))
+        matchings.append(m)
+        predictions.append(pred_t)
+    return (weights, matchings, predictions) if return_matching else weights

@@ -121,6 +121,24 @@ class MLModel:
         W = clib.xlinear_single_layer_train(prob.pX, prob.pY, prob.pC, prob.pM, prob.pR, **train_params.to_dict())
         return cls(W=W, C=prob.C, bias=train_params.bias, pred_params=pred_params)
 
+    def get_pred_params(self):
+        return copy.deepcopy(self.pred_params)
+
+    def predict(self, X, csr_codes=None, pred_params=None, **kwargs):
+        """This layer's prediction of ``X`` (csr_matrix or ndarray, float32), with ``csr_codes`` (instances x codes) the prediction of
+        the layers above (pecos/xmc/base.py:890-949), through ``clib.xlinear_single_layer_predict``: a csr_matrix instances x labels, rows
+        best first.  ``only_topk`` / ``post_processor`` keywords override ``pred_params``."""
+        if X.shape[1] != self.nr_features:
+            raise ValueError("Feature dimension of query matrix does not match weight matrix")
+        pred_params = self.get_pred_params() if pred_params is None else self.PredParams.from_dict(pred_params)
+        pred_params.override_with_kwargs(kwargs)
+        if pred_params.post_processor not in VALID_POST_PROCESSORS:
+            raise ValueError("pred_params is not valid!")
+        pred_alloc = ScipyCompressedSparseAllocator()
+        clib.xlinear_single_layer_predict(X, csr_codes, self.W, self.C, pred_params.post_processor, pred_params.only_topk if pred_params.only_topk else 0,
+                                          kwargs.get("threads", -1), self.bias, pred_alloc)
+        return pred_alloc.get()
+
     def save(self, folder):
         """The reference's layer folder (pecos/xmc/base.py:807-830): param.json, W.npz, C.npz."""
         os.makedirs(folder, exist_ok=True)
@@ -387,6 +405,24 @@ class HierarchicalMLModel:
         label's cluster: ``tfn`` = the layer above's labels (teacher forcing), ``usn`` = ``matching_chain[t]``, or both; the label chain and
         the matching matrices go through the device sparse product.  A scheme with ``man`` (matcher-aware negatives) raises
         ``NotImplementedError``: it needs a prediction of the half-trained chain.  Returns a model that predicts natively and can be saved."""
+        chain, depth, schemes, layer_params, pp = cls._training_setup(prob, clustering, train_params, pred_params, kwargs, serves_man=False)
+        if chain[0] is None:
+            return cls._from_layers([MLModel.train(prob, train_params=layer_params[0], pred_params=pp.model_chain[0])], pp)
+        for name, given in (("matching_chain", matching_chain), ("relevance_chain", relevance_chain)):
+            if given is not None and len(given) != depth:
+                raise ValueError(f"len({name})={len(given)} != {depth}")
+        labels_of = cls._labels_per_layer(prob.Y, chain)
+        layers = []
+        for t in range(depth):
+            negatives = cls._matching(t, schemes[t], labels_of, chain, None if matching_chain is None else matching_chain[t])
+            layer_prob = MLProblem(prob.pX, labels_of[t], C=chain[t], M=negatives, R=None if relevance_chain is None else relevance_chain[t])
+            layers.append(MLModel.train(layer_prob, train_params=layer_params[t], pred_params=pp.model_chain[t]))
+        return cls._from_layers(layers, pp)
+
+    @classmethod
+    def _training_setup(cls, prob, clustering, train_params, pred_params, kwargs, serves_man):
+        """What :meth:`train` and :meth:`train_device` resolve alike: the chain as float32 CSC (``[None]``: one one-versus-all layer), its
+        depth, the per-layer schemes, solver parameters and the prediction parameters.  ``serves_man`` False refuses a scheme with ``man``."""
         chain = [None] if clustering is None or clustering is False else [smat.csc_matrix(C, dtype=np.float32) for C in clustering]
         depth = len(chain)
         if chain[0] is not None and chain[-1].shape[0] != prob.nr_labels:
@@ -400,23 +436,37 @@ class HierarchicalMLModel:
         schemes = [s.lower() for s in cls._per_layer(tp.neg_mining_chain, depth, "neg_mining_chain")]
         layer_params = cls._per_layer(tp.model_chain if tp.model_chain is not None else MLModel.TrainParams(), depth, "model_chain")
         for s in schemes:
-            if "man" in s:
+            if "man" in s and not serves_man:
                 raise NotImplementedError(f"negative sampling scheme '{s}': matcher-aware negatives (man) need a prediction of the half-trained chain, "
                                           "which this library does not run during training; use tfn, usn or tfn+usn")
         pp = cls.PredParams(model_chain=MLModel.PredParams()) if pred_params is None else cls.PredParams.from_dict(pred_params)
         pp.model_chain = cls._per_layer(pp.model_chain if pp.model_chain is not None else MLModel.PredParams(), depth, "pred_params.model_chain")
         pp.override_with_kwargs(kwargs.get("pred_kwargs", None))
+        return chain, depth, schemes, layer_params, pp
+
+    @classmethod
+    def train_device(cls, prob, clustering=None, relevance_chain=None, matching_chain=None, train_params=None, pred_params=None, **kwargs):
+        """:meth:`train` with X, Y, the label chain, the matching matrices, the predictions and the weights resident in HBM from the first
+        layer to the last (:func:`pecos_amd.train_chain_device`): the same arguments and parameter resolution, and every scheme that is a
+        sum of ``tfn``, ``usn`` and ``man`` (matcher-aware negatives: the layers trained so far predict X on the device and their
+        prediction joins the next layer's matching matrix).  The weights are downloaded once at the end; the model predicts natively and
+        can be saved.  Sparse X only."""
+        from .training import train_chain_device
+        chain, depth, schemes, layer_params, pp = cls._training_setup(prob, clustering, train_params, pred_params, kwargs, serves_man=True)
+        if not isinstance(prob.pX, ScipyCsrF32):
+            raise NotImplementedError("HierarchicalMLModel.train_device: dense X is not served in the resident form")
+        for p in pp.model_chain:
+            if p.post_processor not in VALID_POST_PROCESSORS:
+                raise ValueError("pred_params is not valid!")
         if chain[0] is None:
-            return cls._from_layers([MLModel.train(prob, train_params=layer_params[0], pred_params=pp.model_chain[0])], pp)
-        for name, given in (("matching_chain", matching_chain), ("relevance_chain", relevance_chain)):
-            if given is not None and len(given) != depth:
-                raise ValueError(f"len({name})={len(given)} != {depth}")
-        labels_of = cls._labels_per_layer(prob.Y, chain)
+            relevance_chain, matching_chain = (None if prob.R is None else [prob.R]), None
+        weights = train_chain_device(prob.X, prob.Y, chain, schemes, matching_chain, relevance_chain, layer_params, pp.model_chain)
         layers = []
-        for t in range(depth):
-            negatives = cls._matching(t, schemes[t], labels_of, chain, None if matching_chain is None else matching_chain[t])
-            layer_prob = MLProblem(prob.pX, labels_of[t], C=chain[t], M=negatives, R=None if relevance_chain is None else relevance_chain[t])
-            layers.append(MLModel.train(layer_prob, train_params=layer_params[t], pred_params=pp.model_chain[t]))
+        for t, wt in enumerate(weights):
+            Wt = wt.download()                               # labels x (features + (bias > 0)) in CSR = the CSC arrays of W
+            W = smat.csc_matrix((Wt.data, Wt.indices, Wt.indptr), shape=(Wt.shape[1], Wt.shape[0]), dtype=np.float32)
+            C = _ones_column(prob.nr_labels) if chain[t] is None else chain[t]
+            layers.append(MLModel(W=W, C=C, bias=layer_params[t].bias, pred_params=pp.model_chain[t]))
         return cls._from_layers(layers, pp)
 
     @staticmethod
@@ -617,6 +667,17 @@ class XLinearModel:
         (``threshold``, ``solver_type``, ``Cp``, ``max_iter``, ``negative_sampling_scheme``, ...) or in ``train_params``;
         ``beam_size`` / ``only_topk`` / ``post_processor`` or ``pred_kwargs`` set the saved prediction parameters.  Not served, and refused
         by name: the ``matcher`` / ``ranker`` modes, relevance induction (``rel_mode`` other than ``disable``), user-supplied negatives."""
+        return cls._train_through(HierarchicalMLModel.train, X, Y, C, R, user_supplied_negatives, train_params, pred_params, kwargs)
+
+    @classmethod
+    def train_device(cls, X, Y, C=None, R=None, train_params=None, pred_params=None, **kwargs):
+        """:meth:`train` through :meth:`HierarchicalMLModel.train_device`: the same arguments and refusals, the whole layer loop resident in
+        HBM, and ``negative_sampling_scheme`` may be any sum of ``tfn``, ``usn`` and ``man`` (``tfn+man`` is the reference CLI's
+        ``-ns tfn+man``).  The result saves, loads and predicts like :meth:`train`'s."""
+        return cls._train_through(HierarchicalMLModel.train_device, X, Y, C, R, kwargs.pop("user_supplied_negatives", None), train_params, pred_params, kwargs)
+
+    @classmethod
+    def _train_through(cls, train_chain, X, Y, C, R, user_supplied_negatives, train_params, pred_params, kwargs):
         from .indexer import chain_from_partial
         if train_params is None:
             tp = cls.TrainParams.from_dict(kwargs)
@@ -640,7 +701,7 @@ class XLinearModel:
             min_codes, nr_splits = (None, 16) if tp.shallow else (tp.min_codes or tp.nr_splits, tp.nr_splits)
             clustering = chain_from_partial(top, min_codes=min_codes, nr_splits=nr_splits) + rest
         prob = MLProblem(X, Y, R=R if clustering is None else None)
-        return cls(HierarchicalMLModel.train(prob, clustering=clustering, train_params=tp.hlm_args, pred_params=hp, **kwargs))
+        return cls(train_chain(prob, clustering=clustering, train_params=tp.hlm_args, pred_params=hp, **kwargs))
 
     def save(self, model_folder):
         """``model_folder/param.json`` and ``model_folder/ranker`` in the reference's layout (pecos/xmc/xlinear/model.py:92-103)."""
