@@ -78,6 +78,14 @@ inline void set_own_csr(Queries& q, int device, uint32_t rows, uint32_t cols) {
     set_view(q, device, csr_view(rows, cols, q.own.ptr.as<uint64_t>(), q.own.idx.as<uint32_t>(), q.own.val.as<float>(), q.own.nnz));
 }
 
+// A CSR matrix handle, named `name` in the refusals; `what` is the whole prefix of the message, its separator included.
+inline const Queries& csr_handle(const std::string& what, const void* p, const std::string& name) {
+    if (!p) fail(what + "null matrix handle (" + name + ")");
+    const Queries& m = *static_cast<const Queries*>(p);
+    if (m.dev.dense) fail(what + name + " must be a CSR handle");
+    return m;
+}
+
 // synchronous upload of the whole X into the given buffers (dense X: `val` only; a CSR without rows: a zero ptr[0]); `d` describes the device copy
 void upload_x(const HostX& x, DevBuf& ptr, DevBuf& idx, DevBuf& val, QueriesDev& d);
 

@@ -16,14 +16,6 @@ std::atomic<uint64_t> g_forms[4];                          // of this process si
 
 void count_forms(const EmbedForms& f) { g_forms[0] += f.t_lds; g_forms[1] += f.t_big; g_forms[2] += f.n_lane; g_forms[3] += f.n_wave; }
 
-// a CSR matrix handle, named `name` in the refusals
-const Queries& csr_handle(const std::string& what, void* p, const char* name) {
-    if (!p) fail(what + ": null matrix handle (" + name + ")");
-    const Queries& m = *static_cast<Queries*>(p);
-    if (m.dev.dense) fail(what + ": " + name + " must be a CSR handle");
-    return m;
-}
-
 void check_transposable(const std::string& what, const Queries& m) {
     if (m.dev.nnz >= 0xFFFFFFFFull) fail(what + ": a transpose serves fewer than 2^32 - 1 stored entries");
 }
@@ -50,7 +42,7 @@ extern "C" {
 void* xrl_smat_transpose_device(void* A, void* hip_stream) {
     return guarded_value((void*)nullptr, [&]() -> void* {
         const char* what = "xrl_smat_transpose_device";
-        const Queries& a = csr_handle(what, A, "A");
+        const Queries& a = csr_handle(std::string(what) + ": ", A, "A");
         check_transposable(what, a);
         require_gpu();
         use_device(a.device);
@@ -65,7 +57,7 @@ void* xrl_smat_transpose_device(void* A, void* hip_stream) {
 int xrl_smat_normalize_rows_device(void* A, int in_place, void** out, void* hip_stream) {
     return guarded_value(-1, [&] {
         const char* what = "xrl_smat_normalize_rows_device";
-        const Queries& a = csr_handle(what, A, "A");
+        const Queries& a = csr_handle(std::string(what) + ": ", A, "A");
         if (!in_place && !out) fail(std::string(what) + ": null argument (out)");
         require_gpu();
         use_device(a.device);
@@ -90,9 +82,9 @@ void* xrl_smat_hstack_device(void* const* mats, uint32_t n, void* hip_stream) {
         if (!mats || n == 0) fail(std::string(what) + ": no matrices");
         std::vector<QueriesDev> views;
         uint64_t cols = 0;
-        const Queries& first = csr_handle(what, mats[0], "matrix 0");
+        const Queries& first = csr_handle(std::string(what) + ": ", mats[0], "matrix 0");
         for (uint32_t i = 0; i < n; ++i) {
-            const Queries& m = csr_handle(what, mats[i], ("matrix " + std::to_string(i)).c_str());
+            const Queries& m = csr_handle(std::string(what) + ": ", mats[i], "matrix " + std::to_string(i));
             if (m.device != first.device)
                 fail(std::string(what) + ": the matrices are on devices " + std::to_string(first.device) + " and " + std::to_string(m.device) + "; an hstack needs all on one");
             if (m.dev.rows != first.dev.rows)
@@ -113,17 +105,17 @@ void* xrl_label_embedding_device(void* Y, void* X, void* Z_or_null, int method, 
     return guarded_value((void*)nullptr, [&]() -> void* {
         const std::string what = "xrl_label_embedding_device";
         if (method < 0 || method > 2) fail(what + ": unknown method " + std::to_string(method) + " (0 = pifa, 1 = pifa_lf_concat, 2 = pii)");
-        const Queries& y = csr_handle(what, Y, "Y");
+        const Queries& y = csr_handle(what + ": ", Y, "Y");
         check_transposable(what, y);
         const Queries* x = nullptr;
         const Queries* z = nullptr;
         if (method != 2) {
-            x = &csr_handle(what, X, "X");
+            x = &csr_handle(what + ": ", X, "X");
             if (x->device != y.device) fail(what + ": Y and X are on devices " + std::to_string(y.device) + " and " + std::to_string(x->device));
             if (y.dev.rows != x->dev.rows) fail(what + ": Y.rows != X.rows (" + std::to_string(y.dev.rows) + " != " + std::to_string(x->dev.rows) + ")");
         }
         if (method == 1) {
-            z = &csr_handle(what, Z_or_null, "Z");
+            z = &csr_handle(what + ": ", Z_or_null, "Z");
             if (z->device != y.device) fail(what + ": Y and Z are on devices " + std::to_string(y.device) + " and " + std::to_string(z->device));
             if (z->dev.rows != y.dev.cols) fail(what + ": Z.rows != Y.cols (" + std::to_string(z->dev.rows) + " != " + std::to_string(y.dev.cols) + ")");
             if ((uint64_t)x->dev.cols + z->dev.cols >= (1ull << 32)) fail(what + ": X.cols + Z.cols is 2^32 or more");

@@ -26,9 +26,7 @@ void* xrl_smat_pattern_union_device(void* const* mats, uint32_t n, void* hip_str
         std::vector<QueriesDev> ops;
         const Queries* first = nullptr;
         for (uint32_t k = 0; k < n; ++k) {
-            if (!mats[k]) fail(what + "null matrix handle (operand " + std::to_string(k) + ")");
-            const Queries& m = *static_cast<const Queries*>(mats[k]);
-            if (m.dev.dense) fail(what + "operand " + std::to_string(k) + " must be a CSR handle");
+            const Queries& m = csr_handle(what, mats[k], "operand " + std::to_string(k));
             if (!first) first = &m;
             if (m.dev.rows != first->dev.rows || m.dev.cols != first->dev.cols)
                 fail(what + "operand " + std::to_string(k) + " has shape " + std::to_string(m.dev.rows) + " x " + std::to_string(m.dev.cols) + ", operand 0 has " +

@@ -22,6 +22,14 @@ HostCsc host_csc(const ScipyCscF32* M, const char* what) {
     return h;
 }
 
+// labels x 1, every label in the one cluster: the C of a layer that is given none
+HostCsc one_cluster(uint32_t labels) {
+    HostCsc c; c.rows = labels; c.cols = 1; c.col_ptr = {0, labels};
+    c.row_idx.resize(labels); c.val.assign(labels, 1.f);
+    for (uint32_t i = 0; i < labels; ++i) c.row_idx[i] = i;
+    return c;
+}
+
 std::unique_ptr<Model> model_from_arrays(uint32_t depth, const ScipyCscF32* const* W, const ScipyCscF32* const* C,
                                          const float* bias, const uint32_t* only_topk, const char* const* pp, bool csc_route = false) {
     auto m = std::make_unique<Model>();
@@ -30,13 +38,7 @@ std::unique_ptr<Model> model_from_arrays(uint32_t depth, const ScipyCscF32* cons
     m->device = g_device;
     for (uint32_t d = 0; d < depth; ++d) {
         HostCsc w = host_csc(W[d], "W");
-        HostCsc c;
-        if (C && C[d]) c = host_csc(C[d], "C");
-        else {
-            c.rows = w.cols; c.cols = 1; c.col_ptr = {0, w.cols};
-            c.row_idx.resize(w.cols); c.val.assign(w.cols, 1.f);
-            for (uint32_t i = 0; i < w.cols; ++i) c.row_idx[i] = i;
-        }
+        HostCsc c = (C && C[d]) ? host_csc(C[d], "C") : one_cluster(w.cols);
         m->layers.push_back(compile_layer(w, c, bias[d], only_topk[d], pp[d] ? pp[d] : "noop", nullptr, 0, csc_route));
         m->layers.back()->w_host = std::make_shared<HostCsc>(std::move(w));
     }
@@ -182,19 +184,12 @@ void single_layer_predict(const HostX& x, const ScipyCsrF32* csr_codes, ScipyCsc
 // The resident form (xrl_single_layer_predict_device): X, W^T and the codes are in HBM already.  The one-layer model is compiled around an
 // EMPTY weight pattern (tree bookkeeping only, from a host copy of C: nr_labels entries) and W's CSC arrays -- the CSR arrays of W^T -- are
 // copied device to device; then the same CSC route through the same predict_device as the host form.
-const Queries& sl_handle(const std::string& what, void* p, const char* name) {
-    if (!p) fail(what + "null matrix handle (" + name + ")");
-    const Queries& m = *static_cast<Queries*>(p);
-    if (m.dev.dense) fail(what + name + " must be a CSR handle");
-    return m;
-}
-
 void single_layer_predict_device(void* Xh, void* Wth, void* Cth, const uint32_t* d_ci, const float* d_cv, const uint32_t* d_cc, uint32_t c_stride, const char* pp,
                                  uint32_t only_topk, float bias, uint32_t* d_oi, float* d_ov, uint32_t* d_oc, uint32_t out_stride, hipStream_t s) {
     const std::string what = "xrl_single_layer_predict_device: ";
-    const Queries& x = sl_handle(what, Xh, "X");
-    const Queries& wt = sl_handle(what, Wth, "Wt");
-    const Queries* ct = Cth ? &sl_handle(what, Cth, "Ct") : nullptr;
+    const Queries& x = csr_handle(what, Xh, "X");
+    const Queries& wt = csr_handle(what, Wth, "Wt");
+    const Queries* ct = Cth ? &csr_handle(what, Cth, "Ct") : nullptr;
     if (only_topk == 0) fail(what + "only_topk must be positive");
     if (out_stride < only_topk) fail(what + "out_stride (" + std::to_string(out_stride) + ") is smaller than only_topk (" + std::to_string(only_topk) + ")");
     if (!d_oi || !d_ov || !d_oc) fail(what + "null output buffer");
@@ -214,19 +209,15 @@ void single_layer_predict_device(void* Xh, void* Wth, void* Cth, const uint32_t*
 
     // the tree bookkeeping: C on the host (Ct's CSR arrays are C's CSC arrays), or one cluster that holds every label
     HostCsc c;
-    c.rows = labels;
-    if (ct) {
-        c.cols = ct->dev.rows;
+    if (!ct) c = one_cluster(labels);
+    else {
+        c.rows = labels; c.cols = ct->dev.rows;
         c.col_ptr.resize((size_t)c.cols + 1); c.row_idx.resize((size_t)ct->dev.nnz); c.val.resize((size_t)ct->dev.nnz);
         XRL_HIP(hipStreamSynchronize(s));
         download_csr(ct->dev, c.col_ptr.data(), c.row_idx.data(), c.val.data());
         if (c.col_ptr[c.cols] != ct->dev.nnz) fail(what + "Ct's row pointer does not end at its entry count");
         for (uint32_t p = 0; p < c.cols; ++p) if (c.col_ptr[p + 1] < c.col_ptr[p]) fail(what + "Ct's row pointer does not ascend");
         for (uint32_t l : c.row_idx) if (l >= labels) fail(what + "Ct holds an id that is not below " + std::to_string(labels));
-    } else {
-        c.cols = 1; c.col_ptr = {0, labels};
-        c.row_idx.resize(labels); c.val.assign(labels, 1.f);
-        for (uint32_t i = 0; i < labels; ++i) c.row_idx[i] = i;
     }
     HostCsc w;                                             // shape only: compile_layer(structure_only) reads no weight
     w.rows = w_rows; w.cols = labels; w.col_ptr.assign((size_t)labels + 1, 0);

@@ -111,13 +111,6 @@ void train_host(const char* what_c, const ScipyCsrF32& X, const ScipyCscF32* pY,
     else for (uint32_t l = 0; l < L; ++l) emit(l);
 }
 
-const Queries& csr_handle(const std::string& what, void* p, const char* name) {
-    if (!p) fail(what + "null matrix handle (" + name + ")");
-    const Queries& m = *static_cast<Queries*>(p);
-    if (m.dev.dense) fail(what + name + " must be a CSR handle");
-    return m;
-}
-
 }  // namespace
 
 extern "C" {

@@ -11,6 +11,12 @@ from .core import clib
 TRAIN_KEYS = ("threshold", "max_nonzeros_per_label", "solver_type", "Cp", "Cn", "max_iter", "eps", "bias")
 
 
+def _device_of(operands, default=0):
+    """The device of the first operand that lives on one (a :class:`DeviceMatrix` or CUDA tensors), else ``default``."""
+    from .features import _operand_device
+    return next((d for d in (_operand_device(o) for o in operands if o is not None) if d is not None), default)
+
+
 def _train_transposed(x, yt, ct, mt, rt, stream, **params):
     """K13 over :class:`DeviceMatrix` operands that are transposed already."""
     from .features import DeviceMatrix
@@ -27,9 +33,9 @@ def train_layer_device(X, Y, C=None, M=None, R=None, threshold=0.1, max_nonzeros
     (:meth:`DeviceMatrix.transpose`, scipy's stable order: a column's entries by ascending row).  Returns W^T as a new
     :class:`~pecos_amd.features.DeviceMatrix`: labels x (features + (bias > 0)) in CSR, which is the CSC of W.  Runs on ``stream``
     (default: torch's current one), which it synchronises."""
-    from .features import _as_device_matrix, _operand_device, _stream_or_current
+    from .features import _as_device_matrix, _stream_or_current
     ops = [X, Y, C, M, R]
-    dev = next((d for d in (_operand_device(o) for o in ops if o is not None) if d is not None), 0)
+    dev = _device_of(ops)
     s = _stream_or_current(dev, stream)
     x, y, c, m, r = (None if o is None else _as_device_matrix(o, dev, None, stream) for o in ops)
     if c is not None and m is None:
@@ -84,11 +90,9 @@ def single_layer_predict_device(X, Wt, C=None, codes=None, post_processor="l3-hi
     -- this function's own output, fed back -- optionally with the parents' count as a fourth element.  Returns a result triple
     ``(labels int32 [rows, out_stride], scores float32, counts int32 [rows])``, rows best first, on the operands' device.  Runs on
     ``stream`` (default: torch's current one), which it synchronises."""
-    from .features import _as_device_matrix, _operand_device, _stream_or_current
+    from .features import _as_device_matrix, _stream_or_current
     ops = [X, Wt, C]
-    dev = next((d for d in (_operand_device(o) for o in ops if o is not None) if d is not None), None)
-    if dev is None:
-        dev = codes[0].device.index if codes is not None else 0
+    dev = _device_of(ops, default=codes[0].device.index if codes is not None else 0)
     s = _stream_or_current(dev, stream)
     x, wt, c = (None if o is None else _as_device_matrix(o, dev, None, stream) for o in ops)
     ct = None if c is None else c.transpose(stream=s)
@@ -108,6 +112,38 @@ def _params_dict(p):
     return {k: d[k] for k in TRAIN_KEYS if k in d}
 
 
+def _label_chain(y, cs, stream):
+    """``Y_t = Y_(t+1) * C_(t+1)`` by the device sparse product, bottom up: one matrix per layer, the leaves' ``y`` last."""
+    labels_of = [y]
+    for c in reversed(cs[1:]):
+        labels_of.insert(0, labels_of[0].multiply(c, stream=stream))
+    return labels_of
+
+
+def _union_of_sources(t, scheme, labels_of, c, user_supplied, m_pred, stream):
+    """Layer t's matching matrix (instances x clusters of layer t): K14's union of the sources ``scheme`` names.  ``tfn``: the clusters that
+    hold one of an instance's own nodes -- the layer above's labels, which for the top layer is one more product; ``usn``: the caller's
+    matrix; ``man``: the prediction ``m_pred`` of the layers above.  None for a layer without ``c`` and for a root that is a single cluster
+    (every instance then trains every node); a scheme that names no source, or only absent ones, gives an empty M, as in the reference."""
+    from .features import DeviceMatrix
+    if c is None or (t == 0 and c.shape[1] == 1):
+        return None
+    shape = (labels_of[t].shape[0], c.shape[1])
+    parts = []
+    if "usn" in scheme and user_supplied is not None:
+        if user_supplied.shape != shape:
+            raise ValueError(f"a matching matrix has shape {user_supplied.shape}, the layer needs {shape}")
+        parts.append(user_supplied)
+    if "tfn" in scheme:
+        parts.append(labels_of[t - 1] if t else labels_of[0].multiply(c, stream=stream))
+    if "man" in scheme and t > 0:
+        parts.append(DeviceMatrix.from_result(m_pred, shape[1], stream=stream))
+    if not parts:
+        import scipy.sparse as smat
+        parts.append(DeviceMatrix.upload(smat.csr_matrix(shape, dtype="float32"), c.info["device"]))
+    return DeviceMatrix.pattern_union(parts, stream=stream)
+
+
 def train_chain_device(X, Y, chain, neg_mining_chain="tfn", matching_chain=None, relevance_chain=None, train_params=None, pred_params=None,
                        return_matching=False, stream=None):
     """The layers of a cluster chain trained top down with everything resident in HBM (pecos/xmc/base.py:1512-1572).  ``X`` (instances x
@@ -115,14 +151,18 @@ def train_chain_device(X, Y, chain, neg_mining_chain="tfn", matching_chain=None,
     matrices, root first (an entry None: a one-versus-all layer, only as a one-element chain); ``neg_mining_chain`` is one scheme or one
     per layer, a sum of ``tfn`` (the layer above's labels), ``usn`` (``matching_chain[t]``) and ``man`` (the prediction of the layers
     trained so far, with layer t-1's own ``only_topk`` and ``post_processor`` from ``pred_params``); ``train_params`` / ``pred_params`` are
-    one ``MLModel.TrainParams`` / ``PredParams`` (or dict) or one per layer.  The label chain is ``Y_t = Y_(t+1) * C_(t+1)`` by the device
-    sparse product; layer t's matching matrix is K14's union of its sources, and the half-trained chain predicts X layer by layer through
-    :func:`single_layer_predict_device` whenever a scheme from layer t on contains ``man``, each result fed back as the next codes without
-    leaving HBM.  Returns the list of W^T as :class:`~pecos_amd.features.DeviceMatrix`; with ``return_matching`` also the list of matching
-    matrices (None where a layer has none) and the list of predictions that entered them (result triples, None where none was run).  X is
-    uploaded once; nothing but each ``C`` (a predict's tree bookkeeping) and 8-byte bounds and counters crosses to the host."""
-    from .features import DeviceMatrix, _as_device_matrix, _operand_device, _stream_or_current
-    from .xlinear import MLModel
+    one ``MLModel.TrainParams`` / ``PredParams`` (or dict) or one per layer.  A ``relevance_chain[t]`` given as a host matrix is checked
+    as :class:`~pecos_amd.xlinear.MLProblem` checks R (``Y_t``'s pattern, no negative value; above the leaves ``Y_t`` is downloaded for
+    it) before any layer is trained.  This is the package's one layer loop: ``HierarchicalMLModel.train`` and ``train_device`` run it.
+    The label chain is ``Y_t = Y_(t+1) * C_(t+1)`` by the device sparse product; layer t's matching matrix is K14's union of its sources,
+    and the half-trained chain predicts X layer by layer through :func:`single_layer_predict_device` whenever a scheme from layer t on
+    contains ``man``, each result fed back as the next codes without leaving HBM.  Returns the list of W^T as
+    :class:`~pecos_amd.features.DeviceMatrix`; with ``return_matching`` also the list of matching matrices (None where a layer has none)
+    and the list of predictions that entered them (result triples, None where none was run).  X is uploaded once; nothing but each ``C``
+    (a predict's tree bookkeeping) and 8-byte bounds and counters crosses to the host."""
+    import scipy.sparse as smat
+    from .features import _as_device_matrix, _stream_or_current
+    from .xlinear import MLModel, check_relevance
     chain = list(chain)
     depth = len(chain)
     if depth == 0:
@@ -135,8 +175,10 @@ def train_chain_device(X, Y, chain, neg_mining_chain="tfn", matching_chain=None,
     schemes = [s.lower() for s in _per_layer(neg_mining_chain, depth, "neg_mining_chain")]
     tps = [_params_dict(MLModel.TrainParams.from_dict(p)) for p in _per_layer(MLModel.TrainParams() if train_params is None else train_params, depth, "train_params")]
     pps = [MLModel.PredParams.from_dict(p) for p in _per_layer(MLModel.PredParams() if pred_params is None else pred_params, depth, "pred_params")]
-    ops = [X, Y] + chain + list(matching_chain or []) + list(relevance_chain or [])
-    dev = next((d for d in (_operand_device(o) for o in ops if o is not None) if d is not None), 0)
+    host_leaves = relevance_chain is not None and smat.issparse(relevance_chain[-1]) and smat.issparse(Y)
+    if host_leaves:                                         # the leaves' relevance against the caller's own Y: checked before anything is uploaded
+        check_relevance(Y, relevance_chain[-1])
+    dev = _device_of([X, Y] + chain + list(matching_chain or []) + list(relevance_chain or []))
     s = _stream_or_current(dev, stream)
 
     def resident(o):
@@ -144,39 +186,24 @@ def train_chain_device(X, Y, chain, neg_mining_chain="tfn", matching_chain=None,
 
     x, cs = resident(X), [resident(C) for C in chain]
     usn = [resident(m) for m in matching_chain] if matching_chain is not None else [None] * depth
+    labels_of = _label_chain(resident(Y), cs, s)
+    for t, R in enumerate(relevance_chain or []):           # every other host matrix of the caller's before any layer is trained; Y_t comes down for it
+        if smat.issparse(R) and not (host_leaves and t == depth - 1):
+            check_relevance(labels_of[t].download(), R)
     rel = [resident(r) for r in relevance_chain] if relevance_chain is not None else [None] * depth
-    labels_of = [None] * depth                              # Y_t = Y_(t+1) * C_(t+1), bottom up
-    labels_of[-1] = resident(Y)
-    for t in range(depth - 2, -1, -1):
-        labels_of[t] = labels_of[t + 1].multiply(cs[t + 1], stream=s)
-    n_inst = x.shape[0]
     cts = [None if c is None else c.transpose(stream=s) for c in cs]
     weights, matchings, predictions = [], [], []
     m_pred = None
     for t in range(depth):
-        c, ct = cs[t], cts[t]
         pred_t = None
         if t > 0 and any("man" in sc for sc in schemes[t:]):
             m_pred = _predict_transposed(x, weights[t - 1], cts[t - 1], m_pred, pps[t - 1].post_processor, pps[t - 1].only_topk, tps[t - 1]["bias"], s)
             pred_t = m_pred
-        if c is None or (t == 0 and c.shape[1] == 1):
-            m = None
-        else:
-            parts = []
-            if "usn" in schemes[t] and usn[t] is not None:
-                parts.append(usn[t])
-            if "tfn" in schemes[t]:
-                parts.append(labels_of[t - 1] if t else labels_of[0].multiply(c, stream=s))
-            if "man" in schemes[t] and t > 0:
-                parts.append(DeviceMatrix.from_result(m_pred, c.shape[1], stream=s))
-            if not parts:                                   # a scheme that names no source, or only absent ones: an empty M, as in the reference
-                import scipy.sparse as smat
-                parts.append(DeviceMatrix.upload(smat.csr_matrix((n_inst, c.shape[1]), dtype="float32"), dev))
-            m = DeviceMatrix.pattern_union(parts, stream=s)
+        m = _union_of_sources(t, schemes[t], labels_of, cs[t], usn[t], m_pred, s)
         yt = labels_of[t].transpose(stream=s)
         mt = None if m is None else m.transpose(stream=s)
         rt = None if rel[t] is None else rel[t].transpose(stream=s)
-        weights.append(_train_transposed(x, yt, ct if m is not None else None, mt, rt, s, **tps[t]))
+        weights.append(_train_transposed(x, yt, cts[t] if m is not None else None, mt, rt, s, **tps[t]))
         matchings.append(m)
         predictions.append(pred_t)
     return (weights, matchings, predictions) if return_matching else weights

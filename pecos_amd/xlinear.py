@@ -27,6 +27,7 @@ import numpy as np
 import scipy.sparse as smat
 
 from .core import ScipyCompressedSparseAllocator, ScipyCscF32, ScipyCsrF32, ScipyDrmF32, clib
+from .training import _per_layer
 
 VALID_POST_PROCESSORS = ["noop", "sigmoid", "log-sigmoid"] + \
     [f"l{p}-hinge" for p in range(1, 5)] + [f"log-l{p}-hinge" for p in range(1, 5)]  # xmc/base.py:456-475
@@ -155,22 +156,26 @@ def _ones_column(rows):
     return smat.csc_matrix((np.ones(rows, dtype=np.float32), np.arange(rows), np.array([0, rows])), shape=(rows, 1))
 
 
-def _pattern_union(shape, mats):
-    """A float32 CSC of ``shape`` that stores a 1 wherever one of ``mats`` stores an entry (explicit zeros count), rows ascending inside
-    a column.  The trainer reads only the pattern of a matching matrix."""
-    rows, cols = [np.zeros(0, dtype=np.int64)], [np.zeros(0, dtype=np.int64)]
-    for A in mats:
-        A = smat.csc_matrix(A)
-        if A.shape != shape:
-            raise ValueError(f"a matching matrix has shape {A.shape}, the layer needs {shape}")
-        rows.append(A.indices.astype(np.int64))
-        cols.append(np.repeat(np.arange(A.shape[1], dtype=np.int64), np.diff(A.indptr)))
-    rows, cols = np.concatenate(rows), np.concatenate(cols)
-    U = smat.csc_matrix((np.ones(len(rows), dtype=np.float32), (rows, cols)), shape=shape)
-    U.sum_duplicates()
-    U.sort_indices()
-    U.data[:] = 1
-    return U
+def _every_entry_csr(D):
+    """A dense float32 array as the CSR that stores every entry, zeros included: what the dense training entry point trains on."""
+    rows, cols = D.shape
+    ids = np.int32 if D.size < 2 ** 31 else np.int64
+    return smat.csr_matrix((np.ascontiguousarray(D).reshape(-1), np.tile(np.arange(cols, dtype=ids), rows), np.arange(rows + 1, dtype=ids) * cols), shape=D.shape)
+
+
+def _csc_f32(A):
+    """A sparse matrix as float32 CSC (a float32 CSC as it is, stored order kept)."""
+    return A if isinstance(A, smat.csc_matrix) and A.dtype == np.float32 else A.tocsc().astype(np.float32)
+
+
+def check_relevance(Y, R):
+    """ValueError unless ``R`` stores exactly the entries of the label matrix ``Y`` (both read as float32 CSC) and no negative value."""
+    labels, relevance = _csc_f32(Y), _csc_f32(R)
+    for part in ("indptr", "indices"):
+        if not np.array_equal(getattr(labels, part), getattr(relevance, part)):
+            raise ValueError(f"Invalid relevance matrix: Y.{part} != R.{part}")
+    if relevance.nnz and relevance.data.min() < 0:
+        raise ValueError("Invalid relevance matrix: got value < 0")
 
 
 class MLProblem(object):
@@ -201,11 +206,7 @@ class MLProblem(object):
             matching = matching.sorted_indices()                      # (a copy: the caller's matrix stays as it is)
         relevance = None if R is None else self._column_major("R", R)
         if relevance is not None:
-            for part in ("indptr", "indices"):
-                if not np.array_equal(getattr(labels, part), getattr(relevance, part)):
-                    raise ValueError(f"Invalid relevance matrix: Y.{part} != R.{part}")
-            if relevance.nnz and relevance.data.min() < 0:
-                raise ValueError("Invalid relevance matrix: got value < 0")
+            check_relevance(labels, relevance)
         self.pY, self.pC, self.pM = (ScipyCscF32.init_from(A) for A in (labels, clusters, matching))
         self.pR = None if relevance is None else ScipyCscF32.init_from(relevance)
 
@@ -226,7 +227,7 @@ class MLProblem(object):
             return A.buf
         if not smat.issparse(A):
             raise NotImplementedError("type({}) = {} is not supported.".format(name, type(A)))
-        return A if isinstance(A, smat.csc_matrix) and A.dtype == self.dtype else A.tocsc().astype(self.dtype)
+        return _csc_f32(A)
 
     X = property(lambda self: self.pX.buf)
     Y = property(lambda self: self.pY.buf)
@@ -390,39 +391,48 @@ class HierarchicalMLModel:
             chain = [MLModel.TrainParams.from_dict(c) for c in chain] if isinstance(chain, (list, tuple)) else MLModel.TrainParams.from_dict(chain)
             return cls(neg_mining_chain=param.get("neg_mining_chain", "tfn"), model_chain=chain)
 
-    @staticmethod
-    def _per_layer(value, depth, name):
-        if isinstance(value, (list, tuple)):
-            if len(value) != depth:
-                raise ValueError(f"len({name})={len(value)} != {depth}")
-            return list(value)
-        return [copy.deepcopy(value) for _ in range(depth)]
-
     @classmethod
     def train(cls, prob, clustering=None, relevance_chain=None, matching_chain=None, train_params=None, pred_params=None, **kwargs):
-        """The layers of a cluster chain (root first; None: one one-versus-all layer) trained on the device, top down
-        (pecos/xmc/base.py:1412-1572).  Layer t's labels are ``Y * C_last * ... * C_(t+1)`` and its negatives the instances matched to a
-        label's cluster: ``tfn`` = the layer above's labels (teacher forcing), ``usn`` = ``matching_chain[t]``, or both; the label chain and
-        the matching matrices go through the device sparse product.  A scheme with ``man`` (matcher-aware negatives) raises
-        ``NotImplementedError``: it needs a prediction of the half-trained chain.  Returns a model that predicts natively and can be saved."""
-        chain, depth, schemes, layer_params, pp = cls._training_setup(prob, clustering, train_params, pred_params, kwargs, serves_man=False)
-        if chain[0] is None:
-            return cls._from_layers([MLModel.train(prob, train_params=layer_params[0], pred_params=pp.model_chain[0])], pp)
-        for name, given in (("matching_chain", matching_chain), ("relevance_chain", relevance_chain)):
-            if given is not None and len(given) != depth:
-                raise ValueError(f"len({name})={len(given)} != {depth}")
-        labels_of = cls._labels_per_layer(prob.Y, chain)
+        """The layers of a cluster chain (root first; None: one layer from the problem's own C and M, one-versus-all by default) trained on the device, top down
+        (pecos/xmc/base.py:1412-1572), through :func:`pecos_amd.train_chain_device`: X (sparse, or dense as the CSR of all its entries), Y,
+        the label chain ``Y * C_last * ... * C_(t+1)``, the matching matrices and the weights stay in HBM until the last layer is done, and
+        the weights are downloaded once.  A layer's negatives are the instances matched to a label's cluster: ``tfn`` = the layer above's
+        labels (teacher forcing), ``usn`` = ``matching_chain[t]``, or both.  A scheme with ``man`` (matcher-aware negatives) raises
+        ``NotImplementedError`` here; :meth:`train_device` serves it.  Returns a model that predicts natively and can be saved."""
+        return cls._train(False, prob, clustering, relevance_chain, matching_chain, train_params, pred_params, kwargs)
+
+    @classmethod
+    def train_device(cls, prob, clustering=None, relevance_chain=None, matching_chain=None, train_params=None, pred_params=None, **kwargs):
+        """:meth:`train` with every scheme that is a sum of ``tfn``, ``usn`` and ``man`` (matcher-aware negatives: the layers trained so far
+        predict X on the device and their prediction joins the next layer's matching matrix)."""
+        return cls._train(True, prob, clustering, relevance_chain, matching_chain, train_params, pred_params, kwargs)
+
+    @classmethod
+    def _train(cls, serves_man, prob, clustering, relevance_chain, matching_chain, train_params, pred_params, kwargs):
+        from .training import train_chain_device
+        chain, depth, schemes, layer_params, pp = cls._training_setup(prob, clustering, train_params, pred_params, kwargs, serves_man)
+        if chain[0] is None:                                 # one layer from the problem as it stands, as MLModel.train(prob) reads it
+            relevance_chain, matching_chain = (None if prob.R is None else [prob.R]), None
+            if prob.C.shape[1] > 1:                          # the problem's own clusters and matching matrix
+                chain, matching_chain, schemes = [prob.C], [prob.M], ["usn"]
+            elif prob.C.nnz != prob.nr_labels or prob.M.nnz != prob.Y.shape[0]:
+                raise NotImplementedError("a one-versus-all layer from a problem whose single cluster leaves out a label, or whose M leaves out "
+                                          "an instance, is not served on the device")
+        X = prob.X if isinstance(prob.pX, ScipyCsrF32) else _every_entry_csr(prob.X)
+        weights = train_chain_device(X, prob.Y, chain, schemes, matching_chain, relevance_chain, layer_params, pp.model_chain)
         layers = []
-        for t in range(depth):
-            negatives = cls._matching(t, schemes[t], labels_of, chain, None if matching_chain is None else matching_chain[t])
-            layer_prob = MLProblem(prob.pX, labels_of[t], C=chain[t], M=negatives, R=None if relevance_chain is None else relevance_chain[t])
-            layers.append(MLModel.train(layer_prob, train_params=layer_params[t], pred_params=pp.model_chain[t]))
+        for t, wt in enumerate(weights):
+            Wt = wt.download()                               # labels x (features + (bias > 0)) in CSR = the CSC arrays of W
+            W = smat.csc_matrix((Wt.data, Wt.indices, Wt.indptr), shape=(Wt.shape[1], Wt.shape[0]), dtype=np.float32)
+            C = prob.C if chain[t] is None else chain[t]
+            layers.append(MLModel(W=W, C=C, bias=layer_params[t].bias, pred_params=pp.model_chain[t]))
         return cls._from_layers(layers, pp)
 
     @classmethod
     def _training_setup(cls, prob, clustering, train_params, pred_params, kwargs, serves_man):
-        """What :meth:`train` and :meth:`train_device` resolve alike: the chain as float32 CSC (``[None]``: one one-versus-all layer), its
-        depth, the per-layer schemes, solver parameters and the prediction parameters.  ``serves_man`` False refuses a scheme with ``man``."""
+        """What :meth:`train` and :meth:`train_device` resolve, and refuse, before anything reaches a device: the chain as float32 CSC
+        (``[None]``: one one-versus-all layer), its depth, the per-layer schemes, solver parameters and the prediction parameters.
+        ``serves_man`` False refuses a scheme with ``man``."""
         chain = [None] if clustering is None or clustering is False else [smat.csc_matrix(C, dtype=np.float32) for C in clustering]
         depth = len(chain)
         if chain[0] is not None and chain[-1].shape[0] != prob.nr_labels:
@@ -433,66 +443,19 @@ class HierarchicalMLModel:
             tp = cls.TrainParams.from_dict(train_params)
             if tp.neg_mining_chain is None:
                 tp.neg_mining_chain = kwargs.get("negative_sampling_scheme", "tfn")
-        schemes = [s.lower() for s in cls._per_layer(tp.neg_mining_chain, depth, "neg_mining_chain")]
-        layer_params = cls._per_layer(tp.model_chain if tp.model_chain is not None else MLModel.TrainParams(), depth, "model_chain")
+        schemes = [s.lower() for s in _per_layer(tp.neg_mining_chain, depth, "neg_mining_chain")]
+        layer_params = _per_layer(tp.model_chain if tp.model_chain is not None else MLModel.TrainParams(), depth, "model_chain")
         for s in schemes:
             if "man" in s and not serves_man:
                 raise NotImplementedError(f"negative sampling scheme '{s}': matcher-aware negatives (man) need a prediction of the half-trained chain, "
                                           "which this library does not run during training; use tfn, usn or tfn+usn")
         pp = cls.PredParams(model_chain=MLModel.PredParams()) if pred_params is None else cls.PredParams.from_dict(pred_params)
-        pp.model_chain = cls._per_layer(pp.model_chain if pp.model_chain is not None else MLModel.PredParams(), depth, "pred_params.model_chain")
+        pp.model_chain = _per_layer(pp.model_chain if pp.model_chain is not None else MLModel.PredParams(), depth, "pred_params.model_chain")
         pp.override_with_kwargs(kwargs.get("pred_kwargs", None))
-        return chain, depth, schemes, layer_params, pp
-
-    @classmethod
-    def train_device(cls, prob, clustering=None, relevance_chain=None, matching_chain=None, train_params=None, pred_params=None, **kwargs):
-        """:meth:`train` with X, Y, the label chain, the matching matrices, the predictions and the weights resident in HBM from the first
-        layer to the last (:func:`pecos_amd.train_chain_device`): the same arguments and parameter resolution, and every scheme that is a
-        sum of ``tfn``, ``usn`` and ``man`` (matcher-aware negatives: the layers trained so far predict X on the device and their
-        prediction joins the next layer's matching matrix).  The weights are downloaded once at the end; the model predicts natively and
-        can be saved.  Sparse X only."""
-        from .training import train_chain_device
-        chain, depth, schemes, layer_params, pp = cls._training_setup(prob, clustering, train_params, pred_params, kwargs, serves_man=True)
-        if not isinstance(prob.pX, ScipyCsrF32):
-            raise NotImplementedError("HierarchicalMLModel.train_device: dense X is not served in the resident form")
         for p in pp.model_chain:
             if p.post_processor not in VALID_POST_PROCESSORS:
                 raise ValueError("pred_params is not valid!")
-        if chain[0] is None:
-            relevance_chain, matching_chain = (None if prob.R is None else [prob.R]), None
-        weights = train_chain_device(prob.X, prob.Y, chain, schemes, matching_chain, relevance_chain, layer_params, pp.model_chain)
-        layers = []
-        for t, wt in enumerate(weights):
-            Wt = wt.download()                               # labels x (features + (bias > 0)) in CSR = the CSC arrays of W
-            W = smat.csc_matrix((Wt.data, Wt.indices, Wt.indptr), shape=(Wt.shape[1], Wt.shape[0]), dtype=np.float32)
-            C = _ones_column(prob.nr_labels) if chain[t] is None else chain[t]
-            layers.append(MLModel(W=W, C=C, bias=layer_params[t].bias, pred_params=pp.model_chain[t]))
-        return cls._from_layers(layers, pp)
-
-    @staticmethod
-    def _labels_per_layer(Y, chain):
-        """labels_of[t] = instances x (nodes of layer t): the leaf labels rolled up through the clustering matrices below layer t, one
-        device sparse product per level, bottom up."""
-        labels_of = [None] * len(chain)
-        labels_of[-1] = Y
-        for t in range(len(chain) - 2, -1, -1):
-            labels_of[t] = clib.sparse_matmul(labels_of[t + 1], chain[t + 1]).tocsc()
-        return labels_of
-
-    @staticmethod
-    def _matching(t, scheme, labels_of, chain, user_supplied):
-        """Layer t's matching matrix (instances x clusters of layer t), or None for a root that is a single cluster (every instance
-        then trains every node).  ``tfn``: an instance is matched to the clusters that hold one of its own nodes -- the layer above's
-        labels, which for the top layer is one more product.  ``usn``: the caller's matrix.  Both: their union."""
-        C = chain[t]
-        if t == 0 and C.shape[1] == 1:
-            return None
-        parts = []
-        if "usn" in scheme and user_supplied is not None:
-            parts.append(user_supplied)
-        if "tfn" in scheme:
-            parts.append(labels_of[t - 1] if t else clib.sparse_matmul(labels_of[0], C))
-        return _pattern_union((labels_of[t].shape[0], C.shape[1]), parts)
+        return chain, depth, schemes, layer_params, pp
 
     @classmethod
     def _from_layers(cls, layers, pred_params):

@@ -2,12 +2,15 @@
 the compiled reference on the same box: the layer chains above the Eurlex-like leaf layer and the slice of an Amazon-670K-like leaf layer
 that scripts/ranker_training_probe.py generates (clusters grouped 16 to a parent up to a single root).
 
-    python scripts/man_training_probe.py [--problem eurlex|amazon|both] [--no-reference] [--runs N] [--out FILE.json]
+    python scripts/man_training_probe.py [--problem eurlex|amazon|both] [--no-reference] [--only-train] [--runs N] [--out FILE.json]
 
 resident      pecos_amd.train_chain_device: X, Y, the label chain, the matching matrices, the predictions and the weights stay in HBM
 host loop     the reference's loop in scipy (tests/matching_rule.chain_loop) over this library's HOST entry points: per layer an upload of
               X and the operands, the weights and the prediction copied back, the union on the host -- what residency is measured against
 reference     the same loop over the compiled reference (oracle/_ref), 16 threads and 1 thread, one run each
+train         HierarchicalMLModel.train under tfn with every operand on the host, as a user calls it: uploads, the loop, the download of
+              the weights and the model built from them; on the Eurlex-like chain, or with --only-train (nothing else, so the same file times any revision
+              that has train) on the problem asked for
 split         the resident loop once more, step by step, with stream events around each step: per layer the predict of the layer above,
               the union (with the wrap of the prediction as a CSR), the transposes, K13; the median of the timed runs
 Results are compared with the host loop's (and the reference's where it ran): every layer's weights, bit for bit."""
@@ -34,29 +37,21 @@ RUNS = 5
 
 
 def split_loop(x, y, chain_dev, pps, events):
-    """train_chain_device's loop under tfn+man, step by step; events(name, t) -> a context that times one step of layer t on the stream."""
-    from pecos_amd import DeviceMatrix
-    from pecos_amd.training import _predict_transposed, _train_transposed
+    """train_chain_device's steps under tfn+man, one at a time; events(name, t) -> a context that times one step of layer t on the stream."""
+    from pecos_amd.training import _label_chain, _union_of_sources, _predict_transposed, _train_transposed
     depth = len(chain_dev)
-    labels_of = [None] * depth
-    labels_of[-1] = y
     with events("label_chain", 0):
-        for t in range(depth - 2, -1, -1):
-            labels_of[t] = labels_of[t + 1].multiply(chain_dev[t + 1])
+        labels_of = _label_chain(y, chain_dev, None)
     weights, m_pred = [], None
     cts = []
     for t in range(depth):
-        c = chain_dev[t]
         with events("transposes", t):
-            cts.append(c.transpose())
+            cts.append(chain_dev[t].transpose())
         if t > 0:
             with events("predict", t):
                 m_pred = _predict_transposed(x, weights[t - 1], cts[t - 1], m_pred, pps[t - 1][0], pps[t - 1][1], 1.0, None)
-        m = None
-        if not (t == 0 and c.shape[1] == 1):
-            with events("union", t):
-                parts = [labels_of[t - 1] if t else labels_of[0].multiply(c)] + ([DeviceMatrix.from_result(m_pred, c.shape[1])] if t else [])
-                m = DeviceMatrix.pattern_union(parts)
+        with events("union", t):
+            m = _union_of_sources(t, "tfn+man", labels_of, chain_dev[t], None, m_pred, None)
         with events("transposes", t):
             yt = labels_of[t].transpose()
             mt = None if m is None else m.transpose()
@@ -70,16 +65,26 @@ def main():
     ap.add_argument("--problem", default="both", choices=["eurlex", "amazon", "both"])
     ap.add_argument("--no-reference", action="store_true")
     ap.add_argument("--runs", type=int, default=RUNS)
+    ap.add_argument("--only-train", action="store_true", help="time HierarchicalMLModel.train alone (runs on any revision that has it)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     runs_n = a.runs
     import contextlib
     import torch
     import pecos_amd
-    from pecos_amd import DeviceMatrix, MLModel, clib
+    from pecos_amd import DeviceMatrix, HierarchicalMLModel, MLModel, clib
+    from pecos_amd.xlinear import MLProblem
     from pecos_amd.indexer import chain_from_partial
     have_ref = mr.refpy_available() and not a.no_reference
     results = {}
+
+    def report(name, r):
+        results[name] = r
+        print(name, json.dumps(r), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            json.dump(results, open(a.out, "w"), indent=1)
+
     for name in (("eurlex", "amazon") if a.problem == "both" else (a.problem,)):
         X, Y, C, _ = rp.PROBLEMS[name]()
         chain = chain_from_partial(C, nr_splits=16)
@@ -87,6 +92,27 @@ def main():
         pps = [(POST, BEAM)] * depth
         pred_params = [MLModel.PredParams(only_topk=BEAM, post_processor=POST) for _ in range(depth)]
         r = dict(N=X.shape[0], d=X.shape[1], labels=Y.shape[1], chain=[list(c.shape) for c in chain], x_nnz=int(X.nnz), y_nnz=int(Y.nnz), beam=BEAM, post_processor=POST)
+
+        # HierarchicalMLModel.train under tfn as a user calls it: every operand on the host, the model built at the end
+        def train():
+            model = HierarchicalMLModel.train(MLProblem(X, Y), clustering=chain, negative_sampling_scheme="tfn", **TRAIN_KW)
+            torch.cuda.synchronize()
+            return model
+
+        if a.only_train or name == "eurlex":                             # (the Amazon-like slice only when asked for: about a minute per run)
+            train()                                                       # warm-up: module load, allocator
+            times = []
+            for _ in range(runs_n):
+                t0 = time.perf_counter()
+                model = train()
+                times.append(time.perf_counter() - t0)
+            r["train_tfn_s"] = statistics.median(times)
+            r["train_tfn_runs_s"] = times
+            r["train_tfn_w_nnz"] = [int(layer.W.nnz) for layer in model.layers]
+            del model
+        if a.only_train:
+            report(name, r)
+            continue
         t0 = time.perf_counter()
         x, y, chain_dev = DeviceMatrix.upload(X), DeviceMatrix.upload(smat.csr_matrix(Y)), [DeviceMatrix.upload(c) for c in chain]
         torch.cuda.synchronize()
@@ -152,11 +178,7 @@ def main():
                 for t in range(depth):
                     assert mr.same_bits(got[t], ref["W"][t]), f"{name}: layer {t} differs from the reference at {threads} threads"
             r["equals_reference"] = True
-        results[name] = r
-        print(name, json.dumps(r), flush=True)
-        if a.out:
-            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-            json.dump(results, open(a.out, "w"), indent=1)
+        report(name, r)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,8 @@
 """Matcher-aware negatives on the device: K14 (xrl_smat_pattern_union_device) against the numpy statement of the union rule; the bound
 kernel against the host loop's number; xrl_single_layer_predict_device against this library's host entry point and, where oracle/_ref is
 built, the live reference -- labels, order and score bits; train_chain_device / train_device against the reference as recorded in
-tests/golden/man_training_ref.npz, against HierarchicalMLModel.train on the schemes it serves, and end to end."""
+tests/golden/man_training_ref.npz, both and HierarchicalMLModel.train against the scipy loop over the host entry points, and end to end;
+dense X, a relevance chain and a misshapen matching matrix through train and train_device."""
 import os
 
 import numpy as np
@@ -344,20 +345,28 @@ def test_chain_against_the_recorded_reference(scheme, post):
         assert mr.same_bits(mr.wt_to_w(weights[t].download()), want["W"][t]), f"layer {t}: W"
 
 
+def sorted_csc(W):
+    W = smat.csc_matrix(W, dtype=F32, copy=True)
+    W.sort_indices()
+    return W
+
+
 @pytest.mark.parametrize("scheme", ["tfn", "usn", "tfn+usn"])
 def test_chain_equals_train_on_the_schemes_it_serves(scheme):
+    """HierarchicalMLModel.train and train_chain_device are one loop; the independent statement is the scipy loop over the per-layer host entry points."""
     import pecos_amd
     from pecos_amd import HierarchicalMLModel
     from pecos_amd.xlinear import MLProblem
     X, Y, _ = rr.e2e_problem()
     chain, usn = mr.recorded_chain(RECORDED), mr.usn_chain()
+    want = mr.chain_loop(X, Y, chain, [scheme] * 3, *mr.ours_host_backend(), mr.layer_pred_params("l3-hinge"), matching_chain=usn)["W"]
     model = HierarchicalMLModel.train(MLProblem(X, Y), clustering=chain, matching_chain=usn, negative_sampling_scheme=scheme, **mr.TRAIN_KW)
     weights, matchings, preds = pecos_amd.train_chain_device(X, smat.csr_matrix(Y), chain, scheme, matching_chain=usn, train_params=mr.TRAIN_KW, return_matching=True)
     assert preds == [None, None, None], "no scheme names man: nothing is predicted"
     for t, layer in enumerate(model.layers):
-        W = smat.csc_matrix(layer.W)
-        W.sort_indices()
-        assert W.nnz > 0 and mr.same_bits(mr.wt_to_w(weights[t].download()), W), f"layer {t}"
+        W = sorted_csc(layer.W)
+        assert W.nnz > 0 and mr.same_bits(W, want[t]), f"layer {t}: train"
+        assert mr.same_bits(mr.wt_to_w(weights[t].download()), want[t]), f"layer {t}: train_chain_device"
 
 
 def test_an_empty_scheme_gives_an_empty_m():
@@ -404,14 +413,140 @@ def test_train_device_save_load_predict(tmp_path):
 
 
 def test_one_versus_all_goes_through_the_same_function():
-    from pecos_amd import XLinearModel
+    from pecos_amd import XLinearModel, clib
+    from pecos_amd.core import ScipyCscF32, ScipyCsrF32
     X, Y, C, M = rr.problem(120, 60, 10, 3, 6, 8, 5)
+    want = sorted_csc(clib.xlinear_single_layer_train(ScipyCsrF32(X), ScipyCscF32(Y), None, None, None, threshold=0.05, max_iter=30))
     a = XLinearModel.train(X, Y, threshold=0.05, max_iter=30)
     b = XLinearModel.train_device(X, Y, threshold=0.05, max_iter=30, negative_sampling_scheme="tfn+man")
-    Wa, Wb = smat.csc_matrix(a.model.layers[0].W), smat.csc_matrix(b.model.layers[0].W)
-    Wa.sort_indices(); Wb.sort_indices()
-    assert Wa.nnz > 0 and mr.same_bits(Wa, Wb)
+    Wa, Wb = sorted_csc(a.model.layers[0].W), sorted_csc(b.model.layers[0].W)
+    assert Wa.nnz > 0 and mr.same_bits(Wa, want) and mr.same_bits(Wb, want)
     assert mr.same_bits(a.predict(X[:20]), b.predict(X[:20]))
+
+
+@pytest.mark.parametrize("own", ["C", "C and M", "C, M and R"])
+def test_one_layer_from_a_problem_with_its_own_clusters(own):
+    """Without a clustering, train returns MLModel.train(prob)'s layer: the problem's own C and M (given, or filled in as Y * C) and R."""
+    from pecos_amd import clib
+    from pecos_amd.xlinear import MLProblem
+    X, Y, C, M = rr.problem(120, 60, 10, 3, 6, 8, 5)
+    R = sorted_csc(Y)
+    R.data = np.random.RandomState(44).choice(np.array([0, 0.5, 1, 3], F32), R.nnz).astype(F32)
+    prob = MLProblem(X, Y, C=C, M=None if own == "C" else M, R=R if own == "C, M and R" else None)
+    want = sorted_csc(clib.xlinear_single_layer_train(prob.pX, prob.pY, prob.pC, prob.pM, prob.pR, **SMALL_KW))
+    pure = sorted_csc(clib.xlinear_single_layer_train(prob.pX, prob.pY, None, None, prob.pR, **SMALL_KW))
+    assert want.nnz > 0 and not mr.same_bits(want, pure), "C and M do not matter on this problem"
+    for name, train in trainers():
+        model = train(prob, **SMALL_KW)
+        assert len(model.layers) == 1 and model.layers[0].nr_codes == 3 and (smat.csc_matrix(model.layers[0].C) != smat.csc_matrix(C)).nnz == 0, name
+        assert mr.same_bits(sorted_csc(model.layers[0].W), want), name
+
+
+# ------------------------------------------------------------------------------------------------ what train took before it became this loop
+SMALL_KW = dict(threshold=0.05, max_iter=30)
+
+
+def small_chain():
+    """120 instances x 60 features x 10 labels under the two-layer chain 1 <- 3 <- 10."""
+    X, Y, C, _ = rr.problem(120, 60, 10, 3, 6, 8, 5)
+    return X, Y, [smat.csc_matrix(np.ones((3, 1), F32)), C]
+
+
+def trainers():
+    from pecos_amd import HierarchicalMLModel
+    return (("train", HierarchicalMLModel.train), ("train_device", HierarchicalMLModel.train_device))
+
+
+def test_dense_x_through_train_and_train_device():
+    """Dense X trains as the CSR that stores every entry, zeros included: a row and a column of zeros among them, and then an inf."""
+    from pecos_amd import clib
+    from pecos_amd.core import ScipyCscF32, ScipyDrmF32
+    from pecos_amd.xlinear import MLProblem
+    X, Y, chain = small_chain()
+    D = np.ascontiguousarray(X.toarray(), dtype=F32)
+    D[7, :] = 0
+    D[:, 11] = 0
+    every = mr.raw_csr(D.shape, [(np.arange(D.shape[1]), D[r]) for r in range(D.shape[0])])
+    assert every.nnz == D.size
+    pps = [("l3-hinge", 20)] * 2
+    want = mr.chain_loop(every, Y, chain, ["tfn"] * 2, *mr.ours_host_backend(SMALL_KW), pps)["W"]
+    flat = sorted_csc(clib.xlinear_single_layer_train(ScipyDrmF32(D), ScipyCscF32(Y), None, None, None, **SMALL_KW))
+    assert flat.nnz > 0
+    for name, train in trainers():
+        layers = train(MLProblem(D, Y), clustering=chain, **SMALL_KW).layers
+        assert len(layers) == 2
+        for t in range(2):
+            assert want[t].nnz > 0 and mr.same_bits(sorted_csc(layers[t].W), want[t]), f"{name}: layer {t}"
+        assert mr.same_bits(sorted_csc(train(MLProblem(D, Y), **SMALL_KW).layers[0].W), flat), f"{name}: one-versus-all"
+    # With finite X a stored zero adds +0 and changes no bit.  One inf in place of a zero makes them count: its w turns inf or NaN, and
+    # every other row's stored zero in that column then brings 0 * w = NaN into its sum, which a CSR without the zeros never sees.
+    r0, c0 = next((r, c) for r, c in np.argwhere(D == 0) if r != 7 and c != 11)
+    D[r0, c0] = np.inf
+    every = mr.raw_csr(D.shape, [(np.arange(D.shape[1]), D[r]) for r in range(D.shape[0])])
+    want = mr.chain_loop(every, Y, chain, ["tfn"] * 2, *mr.ours_host_backend(SMALL_KW), pps)["W"]
+    without_zeros = mr.chain_loop(smat.csr_matrix(D), Y, chain, ["tfn"] * 2, *mr.ours_host_backend(SMALL_KW), pps)["W"]
+    assert not all(mr.same_bits(want[t], without_zeros[t]) for t in range(2)), "the stored zeros do not matter on this problem"
+    for name, train in trainers():
+        layers = train(MLProblem(D, Y), clustering=chain, **SMALL_KW).layers
+        for t in range(2):
+            assert mr.same_bits(sorted_csc(layers[t].W), want[t]), f"{name}: layer {t} with an inf among the zeros"
+
+
+def small_relevance():
+    """(Y_0, R_0), (Y_1, R_1) of small_chain(): costs on each layer's own labels, a zero and values above 1 among them."""
+    X, Y, chain = small_chain()
+    out = []
+    for t, Yt in enumerate((sorted_csc(Y.tocsr() * chain[1].tocsr()), sorted_csc(Y))):
+        R = Yt.copy()
+        R.data = np.random.RandomState(40 + t).choice(np.array([0, 0.5, 1, 3], F32), R.nnz).astype(F32)
+        R.data[:2] = (0, 3)
+        out.append((Yt, R))
+    return out
+
+
+def test_relevance_chain_through_train():
+    from pecos_amd import HierarchicalMLModel, clib
+    from pecos_amd.core import ScipyCscF32, ScipyCsrF32
+    from pecos_amd.xlinear import MLProblem, _ones_column
+    X, Y, chain = small_chain()
+    (Y0, R0), (Y1, R1) = small_relevance()
+    layers = HierarchicalMLModel.train(MLProblem(X, Y), clustering=chain, relevance_chain=[R0, R1], **SMALL_KW).layers
+    M1 = mr.binarized(Y0)
+    M1.sort_indices()
+    for t, (Yt, M, R) in enumerate(((Y0, _ones_column(120), R0), (Y1, M1, R1))):
+        want = sorted_csc(clib.xlinear_single_layer_train(ScipyCsrF32(X), ScipyCscF32(Yt), ScipyCscF32(chain[t]), ScipyCscF32(M), ScipyCscF32(R), **SMALL_KW))
+        assert want.nnz > 0 and mr.same_bits(sorted_csc(layers[t].W), want), f"layer {t}"
+        unweighted = sorted_csc(clib.xlinear_single_layer_train(ScipyCsrF32(X), ScipyCscF32(Yt), ScipyCscF32(chain[t]), ScipyCscF32(M), None, **SMALL_KW))
+        assert not mr.same_bits(want, unweighted), f"layer {t}: the costs do not matter on this problem"
+
+
+@pytest.mark.parametrize("layer", [0, 1])
+@pytest.mark.parametrize("fault", ["moved", "negative"])
+def test_a_bad_relevance_matrix_is_refused_before_any_training(monkeypatch, layer, fault):
+    from pecos_amd import HierarchicalMLModel, clib
+    from pecos_amd.xlinear import MLProblem
+    X, Y, chain = small_chain()
+    rel = [R for _, R in small_relevance()]
+    bad = rel[layer].copy()
+    if fault == "negative":
+        bad.data[5] = -0.5
+    else:                                                                  # the first entry of column 0 goes to a row that the column does not store
+        col = bad.indices[bad.indptr[0]:bad.indptr[1]]
+        bad.indices[0] = np.setdiff1d(np.arange(120), col)[0]
+    rel[layer] = bad
+    launched = []
+    monkeypatch.setattr(type(clib), "train_layer_device", lambda self, *a, **kw: launched.append(a) or pytest.fail("a training was launched"))
+    with pytest.raises(ValueError, match="Invalid relevance matrix: " + ("got value < 0" if fault == "negative" else r"Y\.indices != R\.indices")):
+        HierarchicalMLModel.train(MLProblem(X, Y), clustering=chain, relevance_chain=rel, **SMALL_KW)
+    assert not launched
+
+
+def test_a_matching_chain_entry_of_the_wrong_shape_is_refused():
+    from pecos_amd.xlinear import MLProblem
+    X, Y, chain = small_chain()
+    for name, train in trainers():
+        with pytest.raises(ValueError, match=r"a matching matrix has shape \(120, 4\), the layer needs \(120, 3\)"):
+            train(MLProblem(X, Y), clustering=chain, matching_chain=[None, smat.csr_matrix((120, 4), dtype=F32)], negative_sampling_scheme="tfn+usn", **SMALL_KW)
 
 
 def test_against_the_live_reference_train():

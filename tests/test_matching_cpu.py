@@ -218,10 +218,22 @@ def test_train_device_refuses_what_train_refuses_in_the_same_words():
     with pytest.raises(ValueError, match=r"len\(neg_mining_chain\)=3 != 2"):
         HierarchicalMLModel.train_device(MLProblem(X, Y), clustering=[smat.csc_matrix(np.ones((2, 1), dtype=np.float32)), C],
                                          train_params=dict(neg_mining_chain=["tfn", "man", "man"], model_chain=dict()))
-    with pytest.raises(NotImplementedError, match="dense X"):
-        HierarchicalMLModel.train_device(MLProblem(np.ascontiguousarray(X.toarray()), Y), clustering=[smat.csc_matrix(np.ones((2, 1), dtype=np.float32)), C])
-    with pytest.raises(ValueError, match="pred_params is not valid"):
-        HierarchicalMLModel.train_device(MLProblem(X, Y), clustering=[smat.csc_matrix(np.ones((2, 1), dtype=np.float32)), C], pred_kwargs=dict(post_processor="nope"))
+    for features in (X, np.ascontiguousarray(X.toarray())):            # (dense X is served like sparse X: it meets the same refusals, none of its own)
+        with pytest.raises(ValueError, match="pred_params is not valid"):
+            HierarchicalMLModel.train_device(MLProblem(features, Y), clustering=[smat.csc_matrix(np.ones((2, 1), dtype=np.float32)), C], pred_kwargs=dict(post_processor="nope"))
+
+
+def test_a_single_cluster_of_the_problems_own_that_is_not_everything_is_refused():
+    """Without a clustering a problem's one cluster must hold every label and its M every instance: that is the pure form the loop trains."""
+    from pecos_amd import HierarchicalMLModel
+    from pecos_amd.xlinear import MLProblem
+    X, Y, C, M = _small()
+    part = smat.csc_matrix((np.ones(5, dtype=np.float32), np.arange(5), np.array([0, 5])), shape=(6, 1))
+    some = smat.csc_matrix((np.ones(29, dtype=np.float32), np.arange(29), np.array([0, 29])), shape=(30, 1))
+    for kw in (dict(C=part), dict(M=some)):
+        for train in (HierarchicalMLModel.train, HierarchicalMLModel.train_device):
+            with pytest.raises(NotImplementedError, match="whose single cluster leaves out a label, or whose M leaves out an instance"):
+                train(MLProblem(X, Y, **kw))
 
 
 def test_mlmodel_predict_refuses_a_wrong_feature_count():
