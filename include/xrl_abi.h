@@ -261,6 +261,55 @@ void* xrl_tfidf_predict_device_tok(void* vectorizer, void* model, void* corpus_p
 uint64_t xrl_tfidf_device_bytes(void* vectorizer, int device);
 /* debug: out[0..n), n <= 4 <- {segments served by the LDS form, by the global form, batches, calls} of the device tokenizer since the load */
 int xrl_debug_tfidf_device_forms(void* vectorizer, uint64_t* out, uint32_t n);
+/* ---- Training the vectorizer on the device (K15, csrc/xrl_tfidf_train.hip) ----------------------------------------------------------
+ * The reference's c_tfidf_train / c_tfidf_save under the xrl_ prefix, with its argument lists and its parameter structs
+ * (tfidf.hpp:66-116, :194-208; a ctypes caller passes the reference's TfidfVectorizerParam as it is).  The trained model is the
+ * reference's exactly: token id = rank of the token's bytes under unsigned-byte order (a prefix first), feature id = rank under
+ * (df, n-gram length, token ids) inside the kept window, idf = the reference's expression in its precision.
+ * The result is the handle type c_tfidf_load returns: every c_tfidf_* / xrl_tfidf_* call serves it, c_tfidf_destruct frees it.
+ * Refused by name, before a GPU is required where the arguments decide it: null arguments; nr_doc == 0; nr_doc >= 2^32;
+ * num_base_vect <= 0; a tok_type other than 10 / 20 / 30 ("received unknown tok_type: N"); tok_type 30 (char_wb: not served);
+ * "expect 0 < min_ngram <= max_ngram"; "expect 0 <= min_df_ratio < max_df_ratio <= 1.0"; a norm_p other than 1 / 2; after the
+ * vocabulary pass a max_ngram whose n-grams need more than 128 bits at the vocabulary's width; in char mode a document with status 1
+ * (the host tokenizer's message and the document number) or status 2 (refused with the document number) anywhere in the document. */
+typedef struct {            /* tfidf.hpp:66-116  TfidfBaseVectorizerParam */
+    int32_t min_ngram, max_ngram;
+    int32_t max_length, max_feature;
+    float min_df_ratio, max_df_ratio;
+    int32_t min_df_cnt, max_df_cnt;
+    bool binary, use_idf, smooth_idf, add_one_idf, sublinear_tf, keep_frequent_feature;
+    int32_t norm_p, tok_type;
+} TfidfBaseVectorizerParam;
+typedef struct {            /* tfidf.hpp:194-208  TfidfVectorizerParam */
+    TfidfBaseVectorizerParam* base_param_ptr;
+    int32_t num_base_vect;
+    int32_t norm_p;
+} TfidfVectorizerParam;
+/* host corpus (char** + lens): packed on `threads` host threads, copied once, trained on the library's device (xrl_set_device) */
+void* xrl_tfidf_train(void* corpus_ptr /* const char** */, const size_t* doc_lens, size_t nr_doc, const TfidfVectorizerParam* param, int threads);
+/* the resident form: text, offsets and lengths in HBM on `device` as for xrl_tfidf_counts_device; the text never visits the host
+ * (offsets and lengths are read back: 16 bytes a document).  hip_stream NULL = a stream of the call's own.  Synchronises the stream. */
+void* xrl_tfidf_train_device(int device, const uint8_t* d_text, const uint64_t* d_doc_off, const uint64_t* d_doc_len, uint64_t nr_doc,
+                             const TfidfVectorizerParam* param, void* hip_stream);
+/* c_tfidf_save's folder: meta.json, <i>.base/tokenizer/{config.json,vocab.txt}, <i>.base/vectorizer/{config.json,tfidf-model.txt}, idf
+ * printed with %f.  Serves trained and loaded handles (a loaded one states the training parameters its folder held).  The order of
+ * the lines of vocab.txt / tfidf-model.txt is not the reference's hash-table order; the content is.  No GPU needed. */
+void xrl_tfidf_save(void* vectorizer, const char* model_dir);
+/* text in HBM -> the weighted X as an xrl_smat_* matrix handle on `device`; no XR-Linear model handle is needed.  d_status as for
+ * xrl_tfidf_counts_device.  hip_stream NULL = the vectorizer's own stream. */
+void* xrl_tfidf_transform_device(void* vectorizer, int device, const uint8_t* d_text, const uint64_t* d_doc_off, const uint64_t* d_doc_len,
+                                 uint64_t nr_doc, uint32_t* d_status /* nr_doc, may be NULL */, void* hip_stream);
+/* The content of base vectorizer `base`, for comparison without files.  sizes[5] <- {tokens, token bytes, n-grams, token ids of all
+ * n-grams, idf entries}.  Every array may be NULL (sizes only); otherwise tok_bytes [sizes[1]], tok_off [sizes[0] + 1], tok_ids
+ * [sizes[0]], ng_flat [sizes[3]], ng_off [sizes[2] + 1], ng_ids [sizes[2]], idf [sizes[4]].  Entries come in table order, not id
+ * order.  Returns 0, or -1 with xrl_last_error set.  No GPU needed. */
+int xrl_tfidf_export(void* vectorizer, uint32_t base, uint64_t* sizes, uint8_t* tok_bytes, uint64_t* tok_off, int32_t* tok_ids, int32_t* ng_flat,
+                     uint64_t* ng_off, uint32_t* ng_ids, float* idf);
+/* debug: out[0..n), n <= 11 <- {documents the vocabulary pass walked, (document, base) segments of the df pass served by the LDS form,
+ * by the global form, df batches, distinct tokens, distinct n-grams before the filter, byte comparisons of tokens of more than 8
+ * bytes, reruns of the vocabulary pass with a larger table, wall microseconds of the vocabulary passes (host sort and table build
+ * included), of the df batches, of merge + filter + order + idf} of the training that made this handle (zeros for a loaded one) */
+int xrl_debug_tfidf_train_forms(void* vectorizer, uint64_t* out, uint32_t n);
 /* xrl_queries_concat_device_ex for a CSR query handle (e.g. xrl_tfidf_predict_device's): [X of the handle | X_emb] as a NEW handle on the
  * same device (XR-Transformer's concat_model call site, pecos/xmc/xtransformer/model.py:589-603, with both halves device-resident). */
 void* xrl_queries_concat_handle(void* model, void* queries, uint32_t dense_cols, const float* d_emb, int normalize_emb, void* hip_stream);

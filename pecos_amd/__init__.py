@@ -6,6 +6,7 @@ Only what the hot path needs lives here: ``csrc/`` (HIP kernels + C ABI), :mod:`
 """
 from .core import clib  # noqa: F401
 from .features import DeviceMatrix, Metrics, metrics_device, metrics_sums_device, result_to_csr_device, sparse_matmul_device  # noqa: F401
+from .features import Preprocessor, Tfidf, tfidf_train_device, tfidf_transform_device  # noqa: F401
 from .indexer import HierarchicalKMeans, LabelEmbeddingFactory, label_embedding_device, run_clustering_device  # noqa: F401
 from .training import single_layer_predict_device, train_chain_device, train_layer_device  # noqa: F401
 from .xlinear import HierarchicalMLModel, MLModel, MLProblem, XLinearModel  # noqa: F401
@@ -13,4 +14,4 @@ from .xlinear import HierarchicalMLModel, MLModel, MLProblem, XLinearModel  # no
 __all__ = ["clib", "XLinearModel", "HierarchicalMLModel", "MLModel", "MLProblem", "Metrics", "metrics_device", "metrics_sums_device",
            "DeviceMatrix", "sparse_matmul_device", "result_to_csr_device", "HierarchicalKMeans", "run_clustering_device",
            "LabelEmbeddingFactory", "label_embedding_device", "train_layer_device", "train_chain_device",
-           "single_layer_predict_device"]
+           "single_layer_predict_device", "Tfidf", "Preprocessor", "tfidf_train_device", "tfidf_transform_device"]

@@ -19,7 +19,7 @@ import contextlib
 import ctypes
 import sys
 import os
-from ctypes import (CFUNCTYPE, POINTER, byref, c_bool, c_char_p, c_double, c_float, c_int, c_int64,
+from ctypes import (CFUNCTYPE, POINTER, byref, c_bool, c_char_p, c_double, c_float, c_int, c_int32, c_int64,
                     c_uint32, c_uint64, c_void_p, cast)
 
 import numpy as np
@@ -40,6 +40,63 @@ class ClusteringParam(ctypes.Structure):
         super().__init__()
         for name, _ in self._fields_:
             setattr(self, name, kw[name] if name in kw else getattr(params, name))
+
+
+TFIDF_TOKENIZER_CODES = {"word": 10, "char": 20, "char_wb": 30}  # tfidf.hpp:281-285
+
+
+class TfidfBaseVectorizerParam(ctypes.Structure):
+    """struct TfidfBaseVectorizerParam of include/xrl_abi.h (tfidf.hpp:66-116), filled from a config dict the way the reference's class
+    of the same name is (base.py:53-126): ``norm`` / ``analyzer`` / ``truncate_length`` / ``ngram_range`` are aliases of ``norm_p`` /
+    ``tok_type`` / ``max_length`` / (``min_ngram``, ``max_ngram``), and the dict is updated in place with the resolved names."""
+    _fields_ = [("min_ngram", c_int32), ("max_ngram", c_int32), ("max_length", c_int32), ("max_feature", c_int32),
+                ("min_df_ratio", c_float), ("max_df_ratio", c_float), ("min_df_cnt", c_int32), ("max_df_cnt", c_int32),
+                ("binary", c_bool), ("use_idf", c_bool), ("smooth_idf", c_bool), ("add_one_idf", c_bool), ("sublinear_tf", c_bool),
+                ("keep_frequent_feature", c_bool), ("norm_p", c_int32), ("tok_type", c_int32)]
+    DEFAULTS = dict(min_ngram=1, max_ngram=1, max_length=-1, max_feature=0, min_df_ratio=0.0, max_df_ratio=1.0, min_df_cnt=0, max_df_cnt=-1,
+                    binary=False, use_idf=True, smooth_idf=True, add_one_idf=False, sublinear_tf=False, keep_frequent_feature=True, norm_p=2,
+                    tok_type=TFIDF_TOKENIZER_CODES["word"])
+
+    def __init__(self, config_dict=None):
+        super().__init__()
+        cfg = {} if config_dict is None else config_dict
+
+        def named(key, alias):
+            return cfg.get(key, cfg.get(alias, self.DEFAULTS[key]))
+
+        norm_p = named("norm_p", "norm")
+        if isinstance(norm_p, str):                      # "l1" / "l2"
+            norm_p = int(norm_p[1:])
+        if norm_p not in (1, 2):
+            raise NotImplementedError("norm_p only support 1 or 2")
+        cfg["norm_p"] = norm_p
+        tok_type = named("tok_type", "analyzer")
+        cfg["tok_type"] = TFIDF_TOKENIZER_CODES[tok_type] if isinstance(tok_type, str) else tok_type
+        cfg["max_length"] = named("max_length", "truncate_length")
+        if "ngram_range" in cfg:
+            cfg["min_ngram"], cfg["max_ngram"] = cfg["ngram_range"][0], cfg["ngram_range"][1]
+        for name, _ in self._fields_:
+            setattr(self, name, cfg.get(name, self.DEFAULTS[name]))
+
+
+class TfidfVectorizerParam(ctypes.Structure):
+    """struct TfidfVectorizerParam (tfidf.hpp:194-208): the base parameters side by side and the ensemble's norm."""
+    _fields_ = [("base_param_ptr", POINTER(TfidfBaseVectorizerParam)), ("num_base_vect", c_int32), ("norm_p", c_int32)]
+
+    def __init__(self, base_vect_param_list, norm_p):
+        super().__init__()
+        self.num_base_vect = len(base_vect_param_list)
+        self._base = (TfidfBaseVectorizerParam * max(1, self.num_base_vect))(*base_vect_param_list)   # (kept alive with the struct)
+        self.base_param_ptr = cast(self._base, POINTER(TfidfBaseVectorizerParam))
+        self.norm_p = norm_p
+
+    @classmethod
+    def from_config(cls, config):
+        """A single base config, or {"base_vect_configs": [...], "norm_p": ...} (base.py:1766-1778)."""
+        if "base_vect_configs" not in config:
+            bases = [TfidfBaseVectorizerParam(config)]
+            return cls(bases, bases[0].norm_p)
+        return cls([TfidfBaseVectorizerParam(c) for c in config["base_vect_configs"]], config["norm_p"])
 
 
 class _MatView(ctypes.Structure):
@@ -315,6 +372,12 @@ class corelib(object):
         "xrl_tfidf_predict_device_tok": (c_void_p, [c_void_p, c_void_p, c_void_p, POINTER(c_uint64), c_uint64, c_int, c_int]),
         "xrl_tfidf_device_bytes": (c_uint64, [c_void_p, c_int]),
         "xrl_debug_tfidf_device_forms": (c_int, [c_void_p, POINTER(c_uint64), c_uint32]),
+        "xrl_tfidf_train": (c_void_p, [c_void_p, POINTER(c_uint64), c_uint64, POINTER(TfidfVectorizerParam), c_int]),
+        "xrl_tfidf_train_device": (c_void_p, [c_int, c_void_p, c_void_p, c_void_p, c_uint64, POINTER(TfidfVectorizerParam), c_void_p]),
+        "xrl_tfidf_save": (None, [c_void_p, c_char_p]),
+        "xrl_tfidf_transform_device": (c_void_p, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p]),
+        "xrl_tfidf_export": (c_int, [c_void_p, c_uint32, POINTER(c_uint64), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+        "xrl_debug_tfidf_train_forms": (c_int, [c_void_p, POINTER(c_uint64), c_uint32]),
         "xrl_queries_concat_handle": (c_void_p, [c_void_p, c_void_p, c_uint32, c_void_p, c_int, c_void_p]),
         "xrl_predict_device": (c_int, [c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int]),
         "xrl_predict_device_rows": (c_int, [c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_int, c_uint32, c_uint32]),
@@ -963,6 +1026,64 @@ class corelib(object):
         self.clib_float32.xrl_debug_tfidf_device_forms(c_void_p(model), out, 4)
         self._check()
         return dict(zip(("lds_segments", "global_segments", "batches", "calls"), (int(v) for v in out)))
+
+    # ---- TF-IDF training on the device (K15; pecos/core/base.py:1706-1818: tfidf_save / tfidf_train)
+    def tfidf_train(self, trn_corpus, config=None):
+        """Train a vectorizer on a list of str / bytes: the reference's ``corelib.tfidf_train`` with the corpus uploaded once and every
+        pass over it on the device.  ``config``: one base config or {"base_vect_configs": [...], "norm_p": ...}, with the reference's
+        aliases (:class:`TfidfBaseVectorizerParam`).  Returns the handle ``tfidf_load`` returns."""
+        if isinstance(trn_corpus, str):
+            raise NotImplementedError(f"tfidf_train from a corpus file or folder ({trn_corpus!r}) is not offered by pecos_amd: read the lines and pass a list")
+        config = {} if config is None else config
+        params = TfidfVectorizerParam.from_config(config)
+        arr, lens, nr_doc = self._corpus_arrays(trn_corpus)
+        h = self.clib_float32.xrl_tfidf_train(arr, lens.ctypes.data_as(POINTER(c_uint64)), nr_doc, byref(params), int(config.get("threads", -1)))
+        self._check()
+        return h
+
+    def tfidf_train_device(self, device, text_addr, off_addr, len_addr, nr_doc, config, stream=None):
+        """The resident form: document bytes, offsets and lengths in HBM on ``device`` (raw addresses, as for ``tfidf_counts_device``)."""
+        params = TfidfVectorizerParam.from_config(config)
+        h = self.clib_float32.xrl_tfidf_train_device(int(device), c_void_p(text_addr), c_void_p(off_addr), c_void_p(len_addr), nr_doc, byref(params), c_void_p(stream or 0))
+        self._check()
+        return h
+
+    def tfidf_save(self, model, save_dir):
+        """The reference's folder layout (``c_tfidf_save``) of a trained or loaded vectorizer handle."""
+        self.clib_float32.xrl_tfidf_save(c_void_p(model), c_char_p(save_dir.encode("utf-8")))
+        self._check()
+
+    def tfidf_transform_device(self, model, device, text_addr, off_addr, len_addr, nr_doc, status_addr=None, stream=None):
+        """Document bytes in HBM -> the weighted X as a matrix handle on ``device`` (K9 + the weighting tail); needs no XR-Linear model."""
+        h = self.clib_float32.xrl_tfidf_transform_device(c_void_p(model), int(device), c_void_p(text_addr), c_void_p(off_addr), c_void_p(len_addr), nr_doc,
+                                                        c_void_p(status_addr or 0), c_void_p(stream or 0))
+        self._check()
+        return h
+
+    def tfidf_export(self, model, base=0):
+        """The content of one base vectorizer: ({token bytes: id}, {tuple of token ids: feature id}, idf float32 [nr_features])."""
+        sizes = (c_uint64 * 5)()
+        null = c_void_p(0)
+        self.clib_float32.xrl_tfidf_export(c_void_p(model), base, sizes, null, null, null, null, null, null, null)
+        self._check()
+        nt, nbytes, ng, nflat, nidf = (int(v) for v in sizes)
+        tok_bytes, tok_off, tok_ids = np.zeros(max(nbytes, 1), np.uint8), np.zeros(nt + 1, np.uint64), np.zeros(max(nt, 1), np.int32)
+        ng_flat, ng_off, ng_ids, idf = np.zeros(max(nflat, 1), np.int32), np.zeros(ng + 1, np.uint64), np.zeros(max(ng, 1), np.uint32), np.zeros(max(nidf, 1), np.float32)
+        self.clib_float32.xrl_tfidf_export(c_void_p(model), base, sizes, *(c_void_p(a.ctypes.data) for a in (tok_bytes, tok_off, tok_ids, ng_flat, ng_off, ng_ids, idf)))
+        self._check()
+        raw = tok_bytes.tobytes()
+        vocab = {raw[int(tok_off[i]):int(tok_off[i + 1])]: int(tok_ids[i]) for i in range(nt)}
+        ngrams = {tuple(int(t) for t in ng_flat[int(ng_off[i]):int(ng_off[i + 1])]): int(ng_ids[i]) for i in range(ng)}
+        return vocab, ngrams, idf[:nidf].copy()
+
+    def tfidf_train_forms(self, model):
+        """Debug counters of the training that made this handle (zeros for a loaded one)."""
+        out = (c_uint64 * 11)()
+        self.clib_float32.xrl_debug_tfidf_train_forms(c_void_p(model), out, 11)
+        self._check()
+        return dict(zip(("vocab_docs", "df_lds_segments", "df_global_segments", "batches", "distinct_tokens", "distinct_ngrams", "long_compares", "table_grows",
+                         "us_vocab", "us_df", "us_order"),
+                        (int(v) for v in out)))
 
     def queries_concat_handle(self, c_model, queries, dense_cols, emb_addr, normalize_emb=False, stream=None):
         h = self.clib_float32.xrl_queries_concat_handle(c_void_p(c_model), c_void_p(queries), dense_cols, c_void_p(emb_addr), 1 if normalize_emb else 0, c_void_p(stream or 0))

@@ -222,6 +222,15 @@ void TfidfBase::load(const std::string& dir) {
         if (np.type == JsonValue::STRING && np.str == "l1") norm_p = 1;
         else if (np.type == JsonValue::STRING && np.str == "l2") norm_p = 2;
         else fail("Unknown normalization type");
+        // the training parameters, kept for xrl_tfidf_save (absent keys keep the defaults)
+        if (const JsonValue* v = kw.get("max_feature")) max_feature = as_int(*v, cf);
+        if (const JsonValue* v = kw.get("min_df_cnt")) min_df_cnt = as_int(*v, cf);
+        if (const JsonValue* v = kw.get("max_df_cnt")) max_df_cnt = as_int(*v, cf);
+        if (const JsonValue* v = kw.get("min_df_ratio")) { if (v->type == JsonValue::NUMBER) min_df_ratio = (float)v->num; }
+        if (const JsonValue* v = kw.get("max_df_ratio")) { if (v->type == JsonValue::NUMBER) max_df_ratio = (float)v->num; }
+        if (const JsonValue* v = kw.get("smooth_idf")) smooth_idf = as_bool(*v, cf);
+        if (const JsonValue* v = kw.get("add_one_idf")) add_one_idf = as_bool(*v, cf);
+        if (const JsonValue* v = kw.get("keep_frequent_feature")) keep_frequent_feature = as_bool(*v, cf);
     }
     // ---- features: id, idf, n-gram
     {

@@ -138,6 +138,10 @@ struct TfidfBase {
     int tok_type = 10;                       // 10 word, 20 char, 30 char_wb (tfidf.hpp:281-285)
     int min_ngram = 1, max_ngram = 1, max_length = -1, norm_p = 2;
     bool binary = false, use_idf = true, sublinear_tf = false;
+    // training parameters: predict never reads them; training sets them and the loader keeps them so that a saved folder states them again
+    int max_feature = 0, min_df_cnt = 0, max_df_cnt = -1;
+    float min_df_ratio = 0.0f, max_df_ratio = 1.0f;           // (the defaults of the reference's Tfidf.train: a folder without the key states them)
+    bool smooth_idf = true, add_one_idf = false, keep_frequent_feature = true;
     TokenTable vocab;
     NgramTable features;
     std::vector<float> idf;                                    // [nr_features]

@@ -13,7 +13,11 @@
 
 #include "xrl_abi_common.h"
 #include "xrl_tfidf.h"
+#include "xrl_tfidf_train.h"
 #include "xrl_tokenize.h"
+
+#include <sys/stat.h>
+#include <cerrno>
 
 using namespace xrl;
 
@@ -76,6 +80,7 @@ struct TfidfHandle {
     mutable std::mutex dev_mu;
     mutable std::map<int, std::unique_ptr<DeviceTables>> dev_tables;
     mutable std::atomic<uint64_t> forms[4] = {};    // segments served by the LDS form, by the global form; batches; calls (xrl_debug_tfidf_device_forms)
+    TrainForms train_forms;                         // what training did (xrl_debug_tfidf_train_forms); zeros for a loaded handle
     const DeviceTables& tables_on(int device) const {
         std::lock_guard<std::mutex> g(dev_mu);
         auto it = dev_tables.find(device);
@@ -463,6 +468,273 @@ int xrl_debug_tfidf_device_forms(void* vectorizer, uint64_t* out, uint32_t n) {
         if (!vectorizer || !out) fail("xrl_debug_tfidf_device_forms: null argument");
         const TfidfHandle& H = *static_cast<TfidfHandle*>(vectorizer);
         for (uint32_t i = 0; i < n && i < 4; ++i) out[i] = H.forms[i].load();
+        return 0;
+    });
+}
+
+// ---- training (K15, xrl_tfidf_train.hip), saving, export
+// what the arguments alone decide: refused before a GPU is required
+static void check_train_args(const std::string& w, const TfidfVectorizerParam* param, uint64_t nr_doc) {
+    if (!param) fail(w + "null param");
+    if (nr_doc == 0) fail(w + "Invalid nr_doc 0");
+    if (nr_doc > 0xFFFFFFFFull) fail(w + "too many documents (2^32 or more)");
+    if (param->num_base_vect <= 0) fail(w + "num_base_vect must be positive");
+    if (!param->base_param_ptr) fail(w + "null base_param_ptr");
+    if (param->norm_p != 1 && param->norm_p != 2) fail(w + "invalid normalize option, norm_p: [ 1| 2]");
+    for (int32_t b = 0; b < param->num_base_vect; ++b) {
+        const TfidfBaseVectorizerParam& P = param->base_param_ptr[b];
+        if (P.tok_type != 10 && P.tok_type != 20 && P.tok_type != 30) fail(w + "received unknown tok_type: " + std::to_string(P.tok_type));
+        if (P.tok_type == 30) fail(w + "tok_type 30 (char_wb) is not served by device training");
+        if (P.min_df_ratio < 0 || P.max_df_ratio <= P.min_df_ratio || P.max_df_ratio > 1.0) fail(w + "expect 0 <= min_df_ratio < max_df_ratio <= 1.0");
+        if (P.min_ngram <= 0 || P.min_ngram > P.max_ngram) fail(w + "expect 0 < min_ngram <= max_ngram");
+        if (P.norm_p != 1 && P.norm_p != 2) fail(w + "invalid normalize option, norm_p: [ 1| 2]");
+    }
+}
+
+static TfidfHandle* train_handle(const std::string& w, const TfidfVectorizerParam* param, const uint8_t* d_text, const uint64_t* d_doc_off, const uint64_t* d_doc_len,
+                                 const uint64_t* h_doc_off, const uint64_t* h_doc_len, uint64_t nr_doc, hipStream_t s) {
+    auto h = std::make_unique<TfidfHandle>();
+    TfidfVectorizer& V = h->v;
+    const std::vector<TfidfBaseVectorizerParam> params(param->base_param_ptr, param->base_param_ptr + param->num_base_vect);
+    V.base.resize(params.size());
+    V.norm_p = param->norm_p;
+    for (size_t b = 0; b < params.size(); ++b) {
+        const TfidfBaseVectorizerParam& P = params[b];
+        TfidfBase& B = V.base[b];
+        B.tok_type = P.tok_type; B.min_ngram = P.min_ngram; B.max_ngram = P.max_ngram; B.max_length = P.max_length; B.norm_p = P.norm_p;
+        B.binary = P.binary; B.use_idf = P.use_idf; B.sublinear_tf = P.sublinear_tf;
+        B.max_feature = P.max_feature; B.min_df_cnt = P.min_df_cnt; B.max_df_cnt = P.max_df_cnt; B.min_df_ratio = P.min_df_ratio; B.max_df_ratio = P.max_df_ratio;
+        B.smooth_idf = P.smooth_idf; B.add_one_idf = P.add_one_idf; B.keep_frequent_feature = P.keep_frequent_feature;
+    }
+    uint64_t first_bad[2];
+    tfidf_train_device(V.base, params, d_text, d_doc_off, d_doc_len, h_doc_off, h_doc_len, nr_doc, s, h->train_forms, first_bad);
+    if (first_bad[0] != ~0ull) fail(w + "the string is not utf-8 encoded! (document " + std::to_string(first_bad[0]) + ")");
+    if (first_bad[1] != ~0ull)
+        fail(w + "document " + std::to_string(first_bad[1]) + " holds a UTF-8 lead byte followed by too few continuation bytes, which the reference's "
+             "sequential decode reads along another path: not served by device training");
+    uint64_t tot = 0;
+    for (const auto& b : V.base) { tot += b.nr_features; h->idf_all.insert(h->idf_all.end(), b.idf.begin(), b.idf.end()); }
+    if (tot > 0xFFFFFFFFull) fail(w + "too many features");
+    V.nr_features = (uint32_t)tot;
+    return h.release();
+}
+
+// the tokens and n-grams a base vectorizer's tables hold, in table order
+static void enumerate_base(const TfidfBase& B, std::vector<std::pair<std::string, int32_t>>& tokens, std::vector<int32_t>& flat, std::vector<uint64_t>& off,
+                           std::vector<uint32_t>& ids) {
+    tokens.clear(); flat.clear(); ids.clear(); off.assign(1, 0);
+    for (size_t i = 0; i < B.vocab.s.size(); ++i) {
+        const tft::ShortEntry& e = B.vocab.s[i];
+        if (!e.len) continue;
+        std::string t(e.len, '\0');
+        for (uint32_t j = 0; j < e.len; ++j) t[j] = (char)(uint8_t)(e.key >> (8 * j));
+        tokens.emplace_back(std::move(t), e.idx);
+    }
+    for (size_t i = 0; i < B.vocab.l.size(); ++i) {
+        const tft::LongEntry& e = B.vocab.l[i];
+        if (e.len) tokens.emplace_back(B.vocab.arena.substr(e.off, e.len), e.idx);
+    }
+    const NgramTable& G = B.features;
+    for (size_t t = 0; t < G.uni.size(); ++t)
+        if (G.uni[t] != NgramTable::kNone) { flat.push_back((int32_t)t); off.push_back(flat.size()); ids.push_back(G.uni[t] - 1u); }
+    const uint64_t field = G.pack_bits >= 64 ? ~0ull : (1ull << G.pack_bits) - 1;
+    for (size_t i = 0; i < G.packed.size(); ++i) {
+        const tft::PackedEntry& e = G.packed[i];
+        if (e.id1 == NgramTable::kNone) continue;
+        for (unsigned sh = 0; sh < 64; sh += G.pack_bits) {
+            const uint64_t f = (e.key >> sh) & field;
+            if (!f) break;
+            flat.push_back((int32_t)(uint32_t)(f - 1));
+        }
+        off.push_back(flat.size()); ids.push_back(e.id1 - 1u);
+    }
+    for (size_t i = 0; i < G.gen.size(); ++i) {
+        const tft::GenEntry& e = G.gen[i];
+        if (e.id1 == NgramTable::kNone) continue;
+        flat.insert(flat.end(), G.arena.begin() + e.off, G.arena.begin() + e.off + e.n);
+        off.push_back(flat.size()); ids.push_back(e.id1 - 1u);
+    }
+}
+
+static void make_dir(const std::string& d, const char* what) {
+    if (mkdir(d.c_str(), 0777) == -1 && errno != EEXIST) fail(std::string("xrl_tfidf_save: Unable to create ") + what + " at " + d);
+}
+static std::FILE* open_w(const std::string& f) {
+    std::FILE* fp = std::fopen(f.c_str(), "wb");
+    if (!fp) fail("xrl_tfidf_save: Unable to save to " + f);
+    return fp;
+}
+// a float as nlohmann prints it: the double it converts to, with enough digits to read back exactly, always with a '.' or an exponent
+static std::string json_float(float v) {
+    char buf[64];
+    std::snprintf(buf, sizeof(buf), "%.17g", (double)v);
+    std::string s(buf);
+    if (s.find_first_of(".en") == std::string::npos) s += ".0";
+    return s;
+}
+
+static void save_base(const TfidfBase& B, const std::string& dir) {
+    make_dir(dir, "save folder");
+    make_dir(dir + "/tokenizer", "save folder");
+    make_dir(dir + "/vectorizer", "save folder");
+    std::vector<std::pair<std::string, int32_t>> tokens; std::vector<int32_t> flat; std::vector<uint64_t> off; std::vector<uint32_t> ids;
+    enumerate_base(B, tokens, flat, off, ids);
+    std::FILE* fp = open_w(dir + "/tokenizer/config.json");
+    std::fprintf(fp, "{\n    \"token_type\": %d\n}", B.tok_type);
+    std::fclose(fp);
+    fp = open_w(dir + "/tokenizer/vocab.txt");
+    std::fprintf(fp, "%zu\n", tokens.size());
+    for (const auto& t : tokens) { std::fprintf(fp, "%d\t", t.second); std::fwrite(t.first.data(), 1, t.first.size(), fp); std::fputc('\n', fp); }
+    std::fclose(fp);
+    const auto tf = [](bool b) { return b ? "true" : "false"; };
+    fp = open_w(dir + "/vectorizer/config.json");
+    std::fprintf(fp,
+                 "{\n    \"kwargs\": {\n        \"add_one_idf\": %s,\n        \"binary\": %s,\n        \"keep_frequent_feature\": %s,\n        \"max_df_cnt\": %d,\n"
+                 "        \"max_df_ratio\": %s,\n        \"max_feature\": %d,\n        \"max_length\": %d,\n        \"min_df_cnt\": %d,\n        \"min_df_ratio\": %s,\n"
+                 "        \"ngram_range\": [\n            %d,\n            %d\n        ],\n        \"norm_p\": \"%s\",\n        \"smooth_idf\": %s,\n"
+                 "        \"sublinear_tf\": %s,\n        \"use_idf\": %s\n    },\n    \"type\": \"tfidf\"\n}",
+                 tf(B.add_one_idf), tf(B.binary), tf(B.keep_frequent_feature), B.max_df_cnt, json_float(B.max_df_ratio).c_str(), B.max_feature, B.max_length, B.min_df_cnt,
+                 json_float(B.min_df_ratio).c_str(), B.min_ngram, B.max_ngram, B.norm_p == 1 ? "l1" : "l2", tf(B.smooth_idf), tf(B.sublinear_tf), tf(B.use_idf));
+    std::fclose(fp);
+    fp = open_w(dir + "/vectorizer/tfidf-model.txt");
+    std::fprintf(fp, "%zu\n", ids.size());
+    for (size_t f = 0; f < ids.size(); ++f) {
+        const float v = ids[f] < B.idf.size() ? B.idf[ids[f]] : 0.0f;
+        std::fprintf(fp, "%d\t%f\t%zu", (int)ids[f], v, (size_t)(off[f + 1] - off[f]));
+        for (uint64_t i = off[f]; i < off[f + 1]; ++i) std::fprintf(fp, i == off[f] ? "\t%d" : " %d", flat[i]);
+        std::fputc('\n', fp);
+    }
+    std::fclose(fp);
+}
+
+void* xrl_tfidf_train(void* corpus_ptr, const size_t* doc_lens, size_t nr_doc, const TfidfVectorizerParam* param, int threads) {
+    return guarded_value((void*)nullptr, [&]() -> void* {
+        const std::string w = "xrl_tfidf_train: ";
+        if (!corpus_ptr || !doc_lens) fail(w + "null corpus");
+        check_train_args(w, param, nr_doc);
+        require_gpu();
+        use_device(g_device);
+        const char* const* corpus = static_cast<const char* const*>(corpus_ptr);
+        // the corpus packed into pinned staging as [offsets u64 | lengths u64 | bytes], one copy to the device (as xrl_tfidf_predict_device_tok)
+        std::vector<uint64_t> off((size_t)nr_doc + 1, 0), len((size_t)nr_doc);
+        for (size_t d = 0; d < nr_doc; ++d) { len[d] = doc_lens[d]; off[d + 1] = off[d] + doc_lens[d]; }
+        const size_t head = nr_doc * 16, total = head + (size_t)off[nr_doc];
+        PinnedStage stage;
+        char* st = static_cast<char*>(stage.need(total + 16));
+        std::memcpy(st, off.data(), nr_doc * 8);
+        std::memcpy(st + nr_doc * 8, len.data(), nr_doc * 8);
+        {
+            unsigned nt = threads > 0 ? (unsigned)threads : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+            nt = (unsigned)std::max<size_t>(1, std::min<size_t>(nt, (size_t)off[nr_doc] >> 20));
+            auto work = [&](unsigned t) {
+                for (size_t d = nr_doc * t / nt, e = nr_doc * (t + 1) / nt; d < e; ++d)
+                    if (doc_lens[d]) std::memcpy(st + head + off[d], corpus[d], doc_lens[d]);
+            };
+            std::vector<std::thread> th;
+            for (unsigned t = 1; t < nt; ++t) th.emplace_back(work, t);
+            work(0);
+            for (auto& x : th) x.join();
+        }
+        hipStream_t s = nullptr;
+        XRL_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        struct Drop { hipStream_t s; ~Drop() { (void)hipStreamDestroy(s); } } drop{s};
+        DevBuf d_in;
+        d_in.reserve(total + 16);
+        XRL_HIP(hipMemcpyAsync(d_in.p, st, total, hipMemcpyHostToDevice, s));
+        const uint64_t* d_off = d_in.as<uint64_t>();
+        return train_handle(w, param, reinterpret_cast<const uint8_t*>(d_in.p) + head, d_off, d_off + nr_doc, off.data(), len.data(), nr_doc, s);
+    });
+}
+
+void* xrl_tfidf_train_device(int device, const uint8_t* d_text, const uint64_t* d_doc_off, const uint64_t* d_doc_len, uint64_t nr_doc,
+                             const TfidfVectorizerParam* param, void* hip_stream) {
+    return guarded_value((void*)nullptr, [&]() -> void* {
+        const std::string w = "xrl_tfidf_train_device: ";
+        if (!d_text || !d_doc_off || !d_doc_len) fail(w + "null text, offsets or lengths");
+        check_train_args(w, param, nr_doc);
+        require_gpu();
+        use_device(device);
+        hipStream_t s = static_cast<hipStream_t>(hip_stream), own = nullptr;
+        if (!s) { XRL_HIP(hipStreamCreateWithFlags(&own, hipStreamNonBlocking)); s = own; }
+        struct Drop { hipStream_t s; ~Drop() { if (s) (void)hipStreamDestroy(s); } } drop{own};
+        std::vector<uint64_t> off((size_t)nr_doc), len((size_t)nr_doc);
+        XRL_HIP(hipMemcpyAsync(off.data(), d_doc_off, nr_doc * 8, hipMemcpyDeviceToHost, s));
+        XRL_HIP(hipMemcpyAsync(len.data(), d_doc_len, nr_doc * 8, hipMemcpyDeviceToHost, s));
+        XRL_HIP(hipStreamSynchronize(s));
+        return train_handle(w, param, d_text, d_doc_off, d_doc_len, off.data(), len.data(), nr_doc, s);
+    });
+}
+
+void xrl_tfidf_save(void* vectorizer, const char* model_dir) {
+    guarded([&] {
+        if (!vectorizer || !model_dir) fail("xrl_tfidf_save: null argument");
+        const TfidfVectorizer& V = static_cast<TfidfHandle*>(vectorizer)->v;
+        const std::string dir(model_dir);
+        make_dir(dir, "save folder");
+        std::FILE* fp = open_w(dir + "/meta.json");
+        std::fprintf(fp, "{\n    \"kwargs\": {\n        \"norm_p\": %d,\n        \"num_base_vect\": %zu\n    },\n    \"type\": \"tfidf\"\n}", V.norm_p, V.base.size());
+        std::fclose(fp);
+        for (size_t b = 0; b < V.base.size(); ++b) save_base(V.base[b], dir + "/" + std::to_string(b) + ".base");
+    });
+}
+
+void* xrl_tfidf_transform_device(void* vectorizer, int device, const uint8_t* d_text, const uint64_t* d_doc_off, const uint64_t* d_doc_len, uint64_t nr_doc,
+                                 uint32_t* d_status, void* hip_stream) {
+    return guarded_value((void*)nullptr, [&]() -> void* {
+        const std::string w = "xrl_tfidf_transform_device: ";
+        if (!vectorizer) fail(w + "null vectorizer handle");
+        if (nr_doc && (!d_text || !d_doc_off || !d_doc_len)) fail(w + "null text, offsets or lengths");
+        if (nr_doc > 0xFFFFFFFFull) fail("tfidf: too many documents");
+        require_gpu();
+        const TfidfHandle& H = *static_cast<TfidfHandle*>(vectorizer);
+        use_device(device);
+        std::lock_guard<std::mutex> stage_lock(H.stage.mu);      // (the pooled stream is handed out under this lock)
+        hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : H.stream_on(device);
+        if (!d_status) return tfidf_device_text_to_x(H, d_text, d_doc_off, d_doc_len, nullptr, nr_doc, device, s).release();
+        TokCounts C;
+        tfidf_count_on_device(H, d_text, d_doc_off, d_doc_len, nullptr, nr_doc, d_status, device, s, C);
+        auto q = std::make_unique<Queries>();
+        q->own = std::move(C.csr);
+        tfidf_weight_counts(H, q.get(), nullptr, (uint32_t)nr_doc, device, s);
+        return q.release();
+    });
+}
+
+int xrl_tfidf_export(void* vectorizer, uint32_t base, uint64_t* sizes, uint8_t* tok_bytes, uint64_t* tok_off, int32_t* tok_ids, int32_t* ng_flat, uint64_t* ng_off,
+                     uint32_t* ng_ids, float* idf) {
+    return guarded_value(-1, [&]() -> int {
+        if (!vectorizer || !sizes) fail("xrl_tfidf_export: null argument");
+        const TfidfVectorizer& V = static_cast<TfidfHandle*>(vectorizer)->v;
+        if (base >= V.base.size()) fail("xrl_tfidf_export: base " + std::to_string(base) + " of " + std::to_string(V.base.size()));
+        const TfidfBase& B = V.base[base];
+        std::vector<std::pair<std::string, int32_t>> tokens; std::vector<int32_t> flat; std::vector<uint64_t> off; std::vector<uint32_t> ids;
+        enumerate_base(B, tokens, flat, off, ids);
+        uint64_t bytes = 0;
+        for (const auto& t : tokens) bytes += t.first.size();
+        sizes[0] = tokens.size(); sizes[1] = bytes; sizes[2] = ids.size(); sizes[3] = flat.size(); sizes[4] = B.idf.size();
+        uint64_t at = 0;
+        for (size_t i = 0; i < tokens.size(); ++i) {
+            if (tok_off) tok_off[i] = at;
+            if (tok_bytes) std::memcpy(tok_bytes + at, tokens[i].first.data(), tokens[i].first.size());
+            if (tok_ids) tok_ids[i] = tokens[i].second;
+            at += tokens[i].first.size();
+        }
+        if (tok_off) tok_off[tokens.size()] = at;
+        if (ng_flat && !flat.empty()) std::memcpy(ng_flat, flat.data(), flat.size() * 4);
+        if (ng_off) std::memcpy(ng_off, off.data(), off.size() * 8);
+        if (ng_ids && !ids.empty()) std::memcpy(ng_ids, ids.data(), ids.size() * 4);
+        if (idf && !B.idf.empty()) std::memcpy(idf, B.idf.data(), B.idf.size() * 4);
+        return 0;
+    });
+}
+
+int xrl_debug_tfidf_train_forms(void* vectorizer, uint64_t* out, uint32_t n) {
+    return guarded_value(-1, [&]() -> int {
+        if (!vectorizer || !out) fail("xrl_debug_tfidf_train_forms: null argument");
+        const TrainForms& F = static_cast<TfidfHandle*>(vectorizer)->train_forms;
+        const uint64_t v[11] = {F.vocab_docs, F.df_lds, F.df_global, F.batches, F.distinct_tokens, F.distinct_ngrams, F.long_compares, F.table_grows,
+                                F.us_vocab, F.us_df, F.us_order};
+        for (uint32_t i = 0; i < n && i < 11; ++i) out[i] = v[i];
         return 0;
     });
 }

@@ -22,6 +22,7 @@
 #include "xrl_tokenize.h"
 #include "xrl_device.h"
 #include "xrl_devprim.h"
+#include "xrl_token_walk.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -48,8 +49,6 @@ struct K9Args {
     uint32_t* status;                                      // [nr_doc]
     int32_t* g_tok; const uint64_t* tok_base; uint64_t* keys; const uint64_t* key_base;   // global form
 };
-
-__device__ __forceinline__ bool is_cont(uint8_t c) { return (c & 0xC0u) == 0x80u; }
 
 // feature id + 1 of the n-gram at t (0: none), TfidfBase::count's rule
 __device__ uint32_t ngram_id1(const tft::NgramView& G, const int32_t* t, int n, bool packable, bool in_packed, bool in_gen) {
@@ -83,61 +82,16 @@ __global__ void __launch_bounds__(64) k9_count(K9Args a) {
     const char* const doc = reinterpret_cast<const char*>(a.text) + a.doc_off[d];
     int32_t* const tok = BIG ? a.g_tok + a.tok_base[a.big0 + blockIdx.x] : s_tok;
 
-    // ---- tokens
-    uint64_t count = 0;
+    // ---- tokens (the walk: xrl_token_walk.h)
     uint32_t status = 0;
-    if (a.tok_type == 10) {
-        unsigned long long carry = 1ull;
-        for (uint64_t p0 = 0; p0 < len && count < tb; p0 += 64u) {
-            const uint64_t pos = p0 + lane;
-            const char c = pos < len ? doc[pos] : ' ';
-            const unsigned long long sp = __ballot(c == ' ');
-            const unsigned long long starts = ~sp & ((sp << 1) | carry);
-            carry = sp >> 63;
-            if ((starts >> lane) & 1ull) {
-                const uint64_t ord = count + lanes_below(starts);
-                if (ord < tb) {
-                    const unsigned long long m = sp >> lane;
-                    uint64_t end;
-                    if (m) end = pos + (uint64_t)__builtin_ctzll(m);
-                    else { end = p0 + 64u; while (end < len && doc[end] != ' ') ++end; }
-                    const uint64_t n = end - pos;
-                    int32_t t;
-                    if (n <= 8) {
-                        const uint64_t key = tft::load_key(doc + pos, (size_t)n, doc + len);
-                        t = tft::find_short(a.tv, key, (uint32_t)n, tft::short_slot(a.tv.s_shift, key, (uint32_t)n));
-                    } else t = tft::find_long(a.tv, doc + pos, (size_t)n, tft::hash_long(doc + pos, (size_t)n));
-                    tok[ord] = t;
-                }
-            }
-            count += (uint64_t)__popcll(starts);
-        }
-    } else {
-        for (uint64_t p0 = 0; p0 < len && count < tb; p0 += 64u) {
-            const uint64_t pos = p0 + lane;
-            const bool valid = pos < len;
-            const uint8_t c = valid ? (uint8_t)doc[pos] : (uint8_t)0x80;
-            const bool start = valid && !is_cont(c);
-            const unsigned long long starts = __ballot(start);
-            uint32_t viol = 0;
-            if (start) {
-                const uint64_t ord = count + lanes_below(starts);
-                if (ord < tb) {                            // (positions past the max_length cut are not checked; nor does the host)
-                    const uint64_t cs = c >= 0xF0 ? 4 : c >= 0xE0 ? 3 : c >= 0xC0 ? 2 : 1;
-                    const uint64_t n = cs < len - pos ? cs : len - pos;
-                    bool inner = true;
-                    for (uint64_t i = 1; i < n; ++i) inner &= is_cont((uint8_t)doc[pos + i]);
-                    if (pos + cs < len && is_cont((uint8_t)doc[pos + cs])) viol = 1;      // the host's next character starts on a continuation byte
-                    else if (!inner) viol = 2;                                          // the host skips a byte that starts a character here
-                    const uint64_t key = tft::load_key(doc + pos, (size_t)n, doc + len);
-                    tok[ord] = tft::find_short(a.tv, key, (uint32_t)n, tft::short_slot(a.tv.s_shift, key, (uint32_t)n));
-                }
-            } else if (pos == 0 && valid) viol = 1;
-            const unsigned long long vm = __ballot(viol != 0);
-            if (vm && !status) status = (uint32_t)__shfl((int)viol, __builtin_ctzll(vm), 64);
-            count += (uint64_t)__popcll(starts);
-        }
-    }
+    const uint64_t count = tokw::walk_tokens(doc, len, a.tok_type, tb, lane, status, [&](uint64_t ord, uint64_t pos, uint64_t n) {
+        int32_t t;
+        if (n <= 8) {
+            const uint64_t key = tft::load_key(doc + pos, (size_t)n, doc + len);
+            t = tft::find_short(a.tv, key, (uint32_t)n, tft::short_slot(a.tv.s_shift, key, (uint32_t)n));
+        } else t = tft::find_long(a.tv, doc + pos, (size_t)n, tft::hash_long(doc + pos, (size_t)n));
+        tok[ord] = t;
+    });
     if (status) {
         if (lane == 0) {
             a.seg_cnt[seg] = 0;

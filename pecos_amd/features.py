@@ -237,11 +237,37 @@ def predict_text_from_torch(vectorizer, model, text_u8, doc_off, doc_len, beam_s
     return idx, sc, cnt
 
 
+def tfidf_train_device(text_u8, doc_off, doc_len, config, device=None, stream=None):
+    """Train a :class:`Tfidf` on documents whose bytes are already in HBM (K15; tensors as for :func:`tfidf_counts_device`): the text never
+    visits the host.  ``config`` as for :meth:`Tfidf.train`; ``device`` defaults to the tensors' device."""
+    text_u8, doc_off, doc_len = _device_text(text_u8, doc_off, doc_len)
+    dev = text_u8.device.index if device is None else int(device)
+    assert dev == text_u8.device.index, "the text must live on the training device"
+    n = int(doc_len.numel())
+    text_addr = text_u8.data_ptr() if text_u8.numel() else doc_len.data_ptr()
+    return Tfidf(clib.tfidf_train_device(dev, text_addr, doc_off.data_ptr(), doc_len.data_ptr(), n, Tfidf._full_config(config), stream=stream))
+
+
+def tfidf_transform_device(vectorizer, text_u8, doc_off, doc_len, status=None, stream=None):
+    """Text in HBM -> the weighted X as a :class:`DeviceMatrix` on the text's device (K9 + the weighting tail): what ``Tfidf.predict``
+    returns, resident, with no XR-Linear model needed -- the X of a training pipeline.  ``status`` as for :func:`tfidf_counts_device`."""
+    import torch
+    if isinstance(vectorizer, Preprocessor):
+        vectorizer = vectorizer.vectorizer
+    text_u8, doc_off, doc_len = _device_text(text_u8, doc_off, doc_len)
+    if status is not None:
+        assert status.is_cuda and status.dtype == torch.int32 and status.shape == doc_len.shape and status.is_contiguous()
+    n = int(doc_len.numel())
+    text_addr = text_u8.data_ptr() if text_u8.numel() else doc_len.data_ptr()
+    return DeviceMatrix(clib.tfidf_transform_device(vectorizer.model, text_u8.device.index, text_addr, doc_off.data_ptr(), doc_len.data_ptr(), n,
+                                                    status.data_ptr() if status is not None else None, stream=stream))
+
+
 class Tfidf:
-    """The PREDICT half of the reference's ``pecos.utils.featurization.text.vectorizers.Tfidf`` (vectorizers.py:163-308): ``load`` a
-    folder the reference saved, ``predict`` a list of strings to a scipy CSR -- same names, arguments and result -- with the tokenizer on
-    host threads and the weighting / normalisation on the device; plus ``predict_device``, which leaves X in HBM.  Training and saving
-    stay the reference's."""
+    """The reference's ``pecos.utils.featurization.text.vectorizers.Tfidf`` (vectorizers.py:163-308): ``load`` a folder the reference
+    saved, ``predict`` a list of strings to a scipy CSR -- same names, arguments and result -- with the tokenizer on host threads and
+    the weighting / normalisation on the device; ``predict_device``, which leaves X in HBM; ``train`` on the device (K15) and ``save``
+    in the reference's layout."""
 
     def __init__(self, model=None):
         self.model = model
@@ -258,6 +284,39 @@ class Tfidf:
         if not os.path.exists(load_dir):
             raise ValueError(f"tfidf model not exist at {load_dir}")
         return cls(clib.tfidf_load(load_dir))
+
+    # the defaults of the reference's Tfidf.train (vectorizers.py:243-268)
+    DEFAULTS = {"ngram_range": (1, 1), "truncate_length": -1, "max_feature": 0, "min_df_ratio": 0.0, "max_df_ratio": 1.0, "min_df_cnt": 0,
+                "max_df_cnt": -1, "binary": False, "use_idf": True, "smooth_idf": True, "add_one_idf": False, "sublinear_tf": False,
+                "keep_frequent_feature": True, "norm": "l2", "analyzer": "word", "buffer_size": 0, "threads": -1}
+    DEFAULTS_META = {"norm_p": 2, "buffer_size": 0, "threads": -1, "base_vect_configs": [DEFAULTS]}
+
+    @classmethod
+    def _full_config(cls, config):
+        """The caller's config over the defaults; a key the reference does not know raises its ``Unknown argument``."""
+        def base(c):
+            unknown = [k for k in c if k not in cls.DEFAULTS]
+            if unknown:
+                raise ValueError(f"Unknown argument: {unknown}")
+            return {**cls.DEFAULTS, **c}
+        config = {} if config is None else config
+        if "base_vect_configs" not in config:
+            return base(config)
+        config = dict(config, base_vect_configs=[base(c) for c in config["base_vect_configs"]])
+        return {**cls.DEFAULTS_META, **config}
+
+    @classmethod
+    def train(cls, trn_corpus, config=None, dtype=np.float32):
+        """The reference's ``Tfidf.train`` (vectorizers.py:175-289) for a list of strings, trained on the device (K15).  The model is the
+        reference's: the same vocabulary, feature ids and idf."""
+        if dtype != np.float32:
+            raise NotImplementedError("Tfidf.train: only dtype=np.float32 is offered")
+        return cls(clib.tfidf_train(trn_corpus, cls._full_config(config)))
+
+    def save(self, save_dir):
+        import os
+        os.makedirs(save_dir, exist_ok=True)
+        clib.tfidf_save(self.model, save_dir)
 
     @property
     def nr_features(self):
@@ -299,6 +358,23 @@ class Preprocessor:
         if vtype != "tfidf":
             raise NotImplementedError(f"vectorizer type {vtype!r}: only 'tfidf' has a device-resident predict path; use the reference's Preprocessor")
         return cls(Tfidf.load(preprocessor_folder), config)
+
+    @classmethod
+    def train(cls, vectorizer_config, trn_corpus, dtype=np.float32):
+        """``Preprocessor.train`` (preprocess.py) for {"type": "tfidf", "kwargs": {...}}: the vectorizer is trained on the device."""
+        vtype = vectorizer_config.get("type", None)
+        if vtype != "tfidf":
+            raise NotImplementedError(f"vectorizer type {vtype!r}: only 'tfidf' is trained by pecos_amd; use the reference's Preprocessor")
+        config = {"type": "tfidf", "kwargs": vectorizer_config.get("kwargs", {})}
+        return cls(Tfidf.train(trn_corpus, dict(config["kwargs"]), dtype=dtype), config)
+
+    def save(self, preprocessor_folder):
+        import json
+        import os
+        os.makedirs(preprocessor_folder, exist_ok=True)
+        with open(os.path.join(preprocessor_folder, "config.json"), "w", encoding="utf-8") as fout:
+            fout.write(json.dumps(self.config or {"type": "tfidf", "kwargs": {}}))
+        self.vectorizer.save(preprocessor_folder)
 
     @property
     def nr_features(self):
