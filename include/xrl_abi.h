@@ -547,6 +547,18 @@ int xrl_debug_cluster_forms(uint64_t* out, uint32_t n);
  *   rounded.  A square that overflows gives s = inf and a row of zeros; an inf entry becomes NaN and a NaN entry makes the whole row NaN
  *   (with the bits an x86 host leaves: the first NaN of the row quieted, a NaN entry its own bits quieted, inf / inf 0xFFC00000).
  *   Column ids and the row pointer are unchanged; duplicates and unsorted rows are walked as stored.
+ * R1a, row normalisation under norm="l1" (inplace_csr_row_normalize_l1).  Per row, s is a DOUBLE that starts at +0.0; the stored entries
+ *   are walked in STORED order: s = s + fabs((double)v), one chain (rows below 64 entries one per lane, longer ones by the wavefront, 64
+ *   entries a step, the adds serial and identical on every lane).  s == 0.0: the row stays as it is.  Otherwise every entry becomes
+ *   (float)((double)v / s): one double division, rounded to float once.  An inf entry gives s = inf: finite entries become signed zeros,
+ *   the inf entries 0xFFC00000.  A NaN entry makes the whole row NaN with the bits an x86 host leaves: the first NaN of the row with its
+ *   sign cleared (fabs) and quieted, a NaN entry its own bits quieted.  Duplicates and unsorted rows are walked as stored.
+ * R1b, row normalisation under norm="max" (min_max_axis, then X.data /= norms).  n = the fp32 maximum of |v| over the row's stored entries
+ *   (order-free: a wavefront reduction); n is NaN if any entry is a NaN, whichever lane holds it (numpy's maximum).  n == 0: the row stays
+ *   as it is.  Otherwise every entry becomes v / n, ONE fp32 division; inf / inf is 0xFFC00000.  In a row with a NaN every entry becomes a
+ *   NaN: a NaN entry its own bits quieted, the others "a NaN" (0x7FC00000 here; on the host the payload follows numpy's reduction order,
+ *   so the contract is "is a NaN").  The reference sums entries with one column id before it takes the maximum: a row whose column ids
+ *   are not STRICTLY ASCENDING is refused by a check kernel, by row, before a value is written (norm = 3 only).
  * R2, transposition = M.T.tocsr() (scipy's csr_tocsc).  Output row j holds every stored entry of column j ordered by SOURCE POSITION:
  *   source row ascending, stored order inside a source row.  Duplicates are kept, not summed; explicit zeros are kept; the output's
  *   column ids are the source row ids.  A function of the input only: integer atomics count and claim slots, the order inside an output
@@ -566,7 +578,9 @@ int xrl_debug_cluster_forms(uint64_t* out, uint32_t n);
  *   xrl_smat_normalize_rows_device  R1 (L2 only).  in_place: writes the handle's own val array -- for a handle that wraps caller memory
  *                                   (xrl_smat_from_device_csr) that IS the caller's array; `out` is not touched.  Otherwise *out <- a NEW
  *                                   owned handle and A stays as it is.  0, or -1 + xrl_last_error
- *   xrl_smat_hstack_device          a NEW owned handle [mats[0] mats[1] ...]: one row count, one device, n >= 1
+ *   xrl_smat_normalize_rows_norm_device  the same call under norm 1 = l1 (R1a), 2 = l2 (R1: the same kernel and bytes as the call above),
+ *                                   3 = max (R1b); any other norm is refused before a GPU is required
+ *   xrl_smat_hstack_device         a NEW owned handle [mats[0] mats[1] ...]: one row count, one device, n >= 1
  *   xrl_label_embedding_device      method 0 = pifa (R3), 1 = pifa_lf_concat (R5), 2 = pii (R4; X is ignored and may be NULL).  A NEW owned
  *                                   handle; the intermediates are freed; Y, X and Z stay as they are (the normalised Y is a private copy)
  *   xrl_debug_embed_forms           FOR TESTS ONLY: out[0..n), n <= 5 <- {CAP, transposed rows served in LDS, by the big form, normalised
@@ -574,6 +588,7 @@ int xrl_debug_cluster_forms(uint64_t* out, uint32_t n);
  *                                   was loaded; rows without entries are served by neither */
 void* xrl_smat_transpose_device(void* A, void* hip_stream);
 int xrl_smat_normalize_rows_device(void* A, int in_place, void** out, void* hip_stream);
+int xrl_smat_normalize_rows_norm_device(void* A, int norm, int in_place, void** out, void* hip_stream);
 void* xrl_smat_hstack_device(void* const* mats, uint32_t n, void* hip_stream);
 void* xrl_label_embedding_device(void* Y, void* X, void* Z_or_null, int method, int normalized_Y, void* hip_stream);
 int xrl_debug_embed_forms(uint64_t* out, uint32_t n);
@@ -691,6 +706,13 @@ int xrl_debug_train_counters(uint64_t* out, uint32_t n);
  *   part; operands on two devices; "Feature dimension of query and W do not match"; "Label dimension of C and
  *   W do not match"; by the bound kernel, "csr_codes: parent id .. out of range" (found and refused, never followed).  0 / -1.
  *   XRL_SINGLE_LAYER_MAX_BATCH_ROWS in the environment is the predict option max_batch_rows of the call's one-layer handle (tests).
+ * Rule C, xrl_smat_check_relevance_device(Y, R, status): does R store exactly Y's entries and no negative value -- what MLProblem asks of a
+ *   relevance matrix (check_relevance), answered in HBM.  Y and R: CSR handles of one shape on one device (both read as stored, so hand in
+ *   both in the same orientation).  status[0] <- 0: equal row pointers, equal column ids position by position, no value of R below 0;
+ *   1: the row pointers differ; 2: the column ids differ; 3: a value of R is below 0 (-0.0 and NaN are not below 0).  The code is the
+ *   first of these that the host check meets (1 before 2 before 3); status[1] <- the first row that offends so (for code 1: the first row
+ *   whose end differs).  One pass, one wavefront per row, every span clamped to both nnz; one readback; runs on hip_stream and
+ *   synchronises it.  Refused before a GPU is required: null handles, dense handles, null status, shapes that differ, two devices.  0 / -1.
  *   xrl_debug_match_forms        FOR TESTS ONLY: out[0..n), n <= 5 <- {rows served in LDS, rows served by the HBM sort, entries read,
  *                                entries written (all four summed over the unions since the load), the candidate bound of the last
  *                                xrl_single_layer_predict_device} */
@@ -698,6 +720,7 @@ void* xrl_smat_pattern_union_device(void* const* mats, uint32_t n, void* hip_str
 int xrl_single_layer_predict_device(void* X, void* Wt, void* Ct_or_null, const uint32_t* d_codes_idx, const float* d_codes_val, const uint32_t* d_codes_cnt,
                                     uint32_t codes_stride, const char* post_processor, uint32_t only_topk, float bias, uint32_t* d_out_idx, float* d_out_val,
                                     uint32_t* d_out_cnt, uint32_t out_stride, void* hip_stream);
+int xrl_smat_check_relevance_device(void* Y, void* R, uint64_t* status, void* hip_stream);
 int xrl_debug_match_forms(uint64_t* out, uint32_t n);
 
 /* predict_on_selected_outputs on the device (K7 + K4): score a given set of labels per query row through the tree, with labels, plan and

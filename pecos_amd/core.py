@@ -334,6 +334,7 @@ class corelib(object):
         "xrl_debug_cluster_forms": (c_int, [POINTER(c_uint64), c_uint32]),
         "xrl_smat_transpose_device": (c_void_p, [c_void_p, c_void_p]),
         "xrl_smat_normalize_rows_device": (c_int, [c_void_p, c_int, POINTER(c_void_p), c_void_p]),
+        "xrl_smat_normalize_rows_norm_device": (c_int, [c_void_p, c_int, c_int, POINTER(c_void_p), c_void_p]),
         "xrl_smat_hstack_device": (c_void_p, [POINTER(c_void_p), c_uint32, c_void_p]),
         "xrl_label_embedding_device": (c_void_p, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
         "xrl_debug_embed_forms": (c_int, [POINTER(c_uint64), c_uint32]),
@@ -347,6 +348,7 @@ class corelib(object):
         "xrl_smat_pattern_union_device": (c_void_p, [POINTER(c_void_p), c_uint32, c_void_p]),
         "xrl_single_layer_predict_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, c_float, c_void_p,
                                                     c_void_p, c_void_p, c_uint32, c_void_p]),
+        "xrl_smat_check_relevance_device": (c_int, [c_void_p, c_void_p, POINTER(c_uint64), c_void_p]),
         "xrl_debug_match_forms": (c_int, [POINTER(c_uint64), c_uint32]),
         "xrl_inspect_model": (c_int, [c_char_p, POINTER(c_uint64), c_uint32]),
         "xrl_model_create": (c_void_p, [c_uint32, c_void_p, c_void_p, POINTER(c_float), POINTER(c_uint32), POINTER(c_char_p)]),
@@ -701,11 +703,18 @@ class corelib(object):
         self._check()
         return t
 
-    def smat_normalize_rows_device(self, h, in_place=False, stream=None):
-        """L2 row normalisation in sklearn's arithmetic: a new matrix handle, or with ``in_place`` None after the handle's own values
-        (the caller's array, for a wrapped handle) were rewritten."""
+    ROW_NORMS = {"l1": 1, "l2": 2, "max": 3}
+
+    def smat_normalize_rows_device(self, h, in_place=False, stream=None, norm="l2"):
+        """Row normalisation in sklearn's arithmetic (``norm``: l2, l1 or max): a new matrix handle, or with ``in_place`` None after the
+        handle's own values (the caller's array, for a wrapped handle) were rewritten."""
         out = c_void_p()
-        self.clib_float32.xrl_smat_normalize_rows_device(c_void_p(h), 1 if in_place else 0, byref(out), c_void_p(stream or 0))
+        if norm == "l2":
+            self.clib_float32.xrl_smat_normalize_rows_device(c_void_p(h), 1 if in_place else 0, byref(out), c_void_p(stream or 0))
+        else:
+            if norm not in self.ROW_NORMS:
+                raise ValueError(f"'{norm}' is not a supported norm; supported: {sorted(self.ROW_NORMS)}")
+            self.clib_float32.xrl_smat_normalize_rows_norm_device(c_void_p(h), self.ROW_NORMS[norm], 1 if in_place else 0, byref(out), c_void_p(stream or 0))
         self._check()
         return None if in_place else out.value
 
@@ -794,6 +803,14 @@ class corelib(object):
         h = self.clib_float32.xrl_smat_pattern_union_device(arr, len(handles), c_void_p(stream or 0))
         self._check()
         return h
+
+    def smat_check_relevance_device(self, Y, R, stream=None):
+        """``(code, row)`` of ``xrl_smat_check_relevance_device`` over two matrix handles: code 0 when R stores exactly Y's entries and no
+        negative value, else 1 (row pointers), 2 (column ids) or 3 (a value below 0) and the first row that offends."""
+        status = (c_uint64 * 2)()
+        self.clib_float32.xrl_smat_check_relevance_device(c_void_p(Y), c_void_p(R), status, c_void_p(stream or 0))
+        self._check()
+        return int(status[0]), int(status[1])
 
     def single_layer_predict_device(self, X, Wt, Ct, codes_idx, codes_val, codes_cnt, codes_stride, post_processor, only_topk, bias, out_idx, out_val, out_cnt,
                                     out_stride, stream=None):

@@ -1,5 +1,5 @@
 // K12 (xrl_embed.hip): the two primitives the label embeddings need on a CSR in HBM (u64 row_ptr, u32 col_idx, f32 val) -- the stable
-// transpose (scipy's csr_tocsc) and the L2 row normalisation in sklearn's arithmetic -- and the hstack of CSRs.  The rules are stated
+// transpose (scipy's csr_tocsc) and the row normalisation (l2, l1, max) in sklearn's arithmetic -- and the hstack of CSRs.  The rules are stated
 // in include/xrl_abi.h at xrl_label_embedding_device.
 #pragma once
 #include <vector>
@@ -23,8 +23,9 @@ struct EmbedForms { uint64_t t_lds = 0, t_big = 0, n_lane = 0, n_wave = 0; };
 // explicit zeros kept.  A: a CSR view with nnz < 2^32.  Fails when an entry of A names a column >= A.cols.  Enqueues on s and synchronises it.
 void transpose_device(const char* what, const QueriesDev& A, hipStream_t s, DevCsr& out, EmbedForms& forms);
 
-// out_val[x] <- A.val[x] / ||row||_2 by the rule R1; out_val may be A.val (in place).  Enqueues on s and synchronises it.
-void normalize_rows_device(const char* what, const QueriesDev& A, float* out_val, hipStream_t s, EmbedForms& forms);
+// out_val[x] <- A.val[x] / ||row|| by the rule R1 (norm = 2: l2), R1a (1: l1) or R1b (3: max); out_val may be A.val (in place).  norm = 3
+// fails, before a value is written, on a row whose column ids are not strictly ascending.  Enqueues on s and synchronises it.
+void normalize_rows_device(const char* what, const QueriesDev& A, float* out_val, hipStream_t s, EmbedForms& forms, int norm = 2);
 
 // out <- [M0 M1 ...] of CSR views with one row count (the callers check it, and that the widths sum below 2^32).  Enqueues on s and synchronises it.
 void hstack_device(const char* what, const std::vector<QueriesDev>& mats, hipStream_t s, DevCsr& out);

@@ -9,10 +9,14 @@
 //                                    (source row ascending, stored order inside it); then (source row of the position, val[position]) is
 //                                    gathered, the source row by bisection of the source's row pointer
 //                    big form        rows above CAP: one rocPRIM segmented radix sort of the positions in HBM, k12_t_big_gather
-//   normalise        k12_normalize   one wavefront per 64 rows (fewer when the rows are long on average).  The sum of a row is ONE fp64 chain in stored order of the rounded fp32 squares:
-//                                    rows below 64 entries one per lane, longer ones by the wavefront (64 squares a step, the adds serial on
-//                                    every lane).  The divide pass walks the 64 rows' entries 64 at a time, an entry finding its row by
-//                                    bisection of the 64 row starts in LDS.  NaN results take the bits the reference's host gives them.
+//   normalise        k12_normalize<NORM>  one wavefront per 64 rows (fewer when the rows are long on average).  NORM = 2 (R1): the sum of a row is ONE fp64 chain in
+//                                    stored order of the rounded fp32 squares: rows below 64 entries one per lane, longer ones by the wavefront (64 squares a
+//                                    step, the adds serial on every lane).  NORM = 1 (R1a): the same chain over |v| widened to double, no square root.
+//                                    NORM = 3 (R1b): the fp32 maximum of |v| -- order-free, so the wavefront form keeps a maximum per lane and the lanes
+//                                    meet in a butterfly; a NaN entry is found by ballot, never by the maximum.  The divide pass walks the 64 rows' entries
+//                                    64 at a time, an entry finding its row by bisection of the 64 row starts in LDS.  NaN results take the bits the
+//                                    reference's host gives them (R1b: a NaN).
+//                    k12_check_ascending  R1b only, before anything is written: a row whose ids are not strictly ascending is refused
 //   hstack           k12_add_lens (counts, then the write cursors) around the shared row copy of xrl_devprim.h
 //
 // Bounds: every row span is clamped to the arrays' nnz; a claimed slot and a sorted position are below nnz before they index; an LDS index
@@ -139,7 +143,20 @@ __global__ void __launch_bounds__(256) k12_t_big_gather(K12T a, const uint32_t* 
 }
 
 // ---- normalise
+// NORM = 2: rule R1 (the sum of the rounded fp32 squares, n = sqrt); 1: R1a (the sum of |v| widened to double, n = s); 3: R1b (the fp32
+// maximum of |v|, order-free).  One row's term of the chain, and what a NaN entry leaves as the NaN of the row.
+template <int NORM> __device__ __forceinline__ double k12_term(float v) {
+    if (NORM == 2) return (double)__fmul_rn(v, v);
+    return fabs((double)v);                                // (NORM == 3: |v| widened exactly; the maximum of widened floats is a float)
+}
+template <int NORM> __device__ __forceinline__ uint32_t k12_row_nan(float v) {
+    if (NORM == 2) return __float_as_uint(v) | kQuiet;
+    if (NORM == 1) return (__float_as_uint(v) & 0x7FFFFFFFu) | kQuiet;     // fabs clears the sign before the chain sees the NaN
+    return 0x7FC00000u;                                    // R1b: "a NaN" (numpy's reduction order picks the payload on the host)
+}
+
 // words[0] <- rows (with entries) summed one per lane, words[1] <- by the wavefront
+template <int NORM>
 __global__ void __launch_bounds__(256)
 k12_normalize(const uint64_t* __restrict__ ptr, const float* val, float* out, uint64_t row0, uint64_t rows, uint64_t nnz, uint32_t per_wave,
               unsigned long long* __restrict__ words) {
@@ -154,15 +171,16 @@ k12_normalize(const uint64_t* __restrict__ ptr, const float* val, float* out, ui
     uint64_t b = 0, e = 0;
     if (valid) row_span(ptr, r0 + lane, nnz, b, e);
     const bool wave = valid && e - b >= kEmbedWaveRow;
-    // s: the fp64 chain from +0 of the rounded fp32 squares, in stored order.  nanb: the first NaN entry, quieted -- what the host's
-    // chain, square root and division hand on as the NaN of the row
+    // s: the fp64 chain from +0 of the row's terms, in stored order (NORM = 3: their maximum).  nanb: the first NaN entry, quieted -- what
+    // the host's chain, square root and division hand on as the NaN of the row
     double s = 0.0;
     uint32_t nanb = 0;
     if (valid && !wave)
         for (uint64_t x = b; x < e; ++x) {
             const float v = val[x];
-            if (v != v && !nanb) nanb = __float_as_uint(v) | kQuiet;
-            s = __dadd_rn(s, (double)__fmul_rn(v, v));
+            if (v != v && !nanb) nanb = k12_row_nan<NORM>(v);
+            if (NORM == 3) { if (v == v) s = fmax(s, k12_term<NORM>(v)); }
+            else s = __dadd_rn(s, k12_term<NORM>(v));
         }
     unsigned long long todo = __ballot(wave);
     const unsigned long long m_lane = __ballot(valid && !wave && e > b);
@@ -179,17 +197,24 @@ k12_normalize(const uint64_t* __restrict__ ptr, const float* val, float* out, ui
         for (uint64_t x0 = wb; x0 < we; x0 += 64u) {
             const uint64_t x = x0 + lane;
             const float v = x < we ? val[x] : 0.0f;
-            const double p = (double)__fmul_rn(v, v);
+            const double p = k12_term<NORM>(v);
             const unsigned long long mn = __ballot(v != v);
-            if (!tn && mn) tn = (uint32_t)__shfl((int)__float_as_uint(v), __ffsll((long long)mn) - 1) | kQuiet;
-            const uint32_t n = (uint32_t)min((uint64_t)64u, we - x0);
-            t = wave_chain(t, p, n);
+            if (!tn && mn) tn = k12_row_nan<NORM>(__uint_as_float((uint32_t)__shfl((int)__float_as_uint(v), __ffsll((long long)mn) - 1)));
+            if (NORM == 3) { if (v == v) t = fmax(t, p); }         // (per lane; the lanes meet below.  Which lane saw a NaN does not matter: the ballot)
+            else {
+                const uint32_t n = (uint32_t)min((uint64_t)64u, we - x0);
+                t = wave_chain(t, p, n);
+            }
+        }
+        if (NORM == 3) {
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) t = fmax(t, __shfl_xor(t, d, 64));
         }
         if ((int)lane == i) { s = t; nanb = tn; }
     }
     const uint64_t lo = __shfl(b, 0), hi = __shfl(e, (int)n_valid - 1);
     s_b[w][lane] = valid ? b : hi;
-    s_n[w][lane] = (nanb == 0 && s == 0.0) ? 0.0 : sqrt(s);        // 0: the row stays as it is
+    s_n[w][lane] = (nanb == 0 && s == 0.0) ? 0.0 : (NORM == 2 ? sqrt(s) : s);      // 0: the row stays as it is
     s_nan[w][lane] = nanb;
     wave_sync_lds();
     for (uint64_t x0 = lo; x0 < hi; x0 += 64u) {
@@ -202,11 +227,22 @@ k12_normalize(const uint64_t* __restrict__ ptr, const float* val, float* out, ui
         float o = v;
         if (nb) o = __uint_as_float(v != v ? (__float_as_uint(v) | kQuiet) : nb);
         else if (nn != 0.0) {
-            o = (float)((double)v / nn);
+            o = NORM == 3 ? __fdiv_rn(v, (float)nn) : (float)((double)v / nn);
             if (o != o) o = __uint_as_float(0xFFC00000u);  // inf / inf: the host's default NaN
         }
         out[x] = o;
     }
+}
+
+// R1b refuses a row that is not strictly ascending (sklearn sums duplicate ids before its maximum): word <- max of (rows - r) over such rows r
+__global__ void __launch_bounds__(256)
+k12_check_ascending(const uint64_t* __restrict__ ptr, const uint32_t* __restrict__ col, uint64_t nnz, uint32_t rows, unsigned long long* __restrict__ word) {
+    const uint64_t x = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (x == 0 || x >= nnz || col[x] > col[x - 1]) return;
+    const uint32_t r = segment_of(ptr, rows, x);
+    uint64_t b, e;
+    row_span(ptr, r, nnz, b, e);
+    if (x > b && x < e) atomicMax(word, (unsigned long long)(rows - r));
 }
 
 // ---- hstack
@@ -275,17 +311,26 @@ void transpose_device(const char* what, const QueriesDev& A, hipStream_t s, DevC
     XRL_HIP(hipStreamSynchronize(s));                      // the scratch goes with this scope
 }
 
-void normalize_rows_device(const char* what, const QueriesDev& A, float* out_val, hipStream_t s, EmbedForms& forms) {
+void normalize_rows_device(const char* what, const QueriesDev& A, float* out_val, hipStream_t s, EmbedForms& forms, int norm) {
     if (A.rows == 0 || A.nnz == 0) { XRL_HIP(hipStreamSynchronize(s)); return; }
     DevBuf words;
-    words.reserve(16);
-    XRL_HIP(hipMemsetAsync(words.p, 0, 16, s));
+    words.reserve(24);
+    XRL_HIP(hipMemsetAsync(words.p, 0, 24, s));
+    if (norm == 3) {                                       // before a value is written: an in-place call leaves a refused matrix as it was
+        hipLaunchKernelGGL(k12_check_ascending, dim3(blocks_of(A.nnz, 256, what)), dim3(256), 0, s, A.row_ptr, A.col_idx, A.nnz, A.rows, words.as<unsigned long long>() + 2);
+        XRL_LAUNCH_CHECK();
+        uint64_t bad = 0;
+        XRL_HIP(hipMemcpyAsync(&bad, words.as<uint64_t>() + 2, 8, hipMemcpyDeviceToHost, s));
+        XRL_HIP(hipStreamSynchronize(s));
+        if (bad) fail(std::string(what) + ": norm = max: row " + std::to_string(A.rows - bad) + " does not store its column ids strictly ascending (a repeated id is summed by the reference before its maximum; not served)");
+    }
     // a wavefront sums its long rows one after the other: it gets fewer rows the longer they are on average (about 4096 entries' worth)
     uint32_t per_wave = 64;
     while (per_wave > 1 && A.nnz / A.rows * per_wave > 4096) per_wave >>= 1;
     const uint64_t per_launch = (1ull << 25) * per_wave;   // rows of one launch: 2^23 workgroups
+    auto* kernel = norm == 1 ? k12_normalize<1> : norm == 3 ? k12_normalize<3> : k12_normalize<2>;
     for (uint64_t r0 = 0; r0 < A.rows; r0 += per_launch) {
-        hipLaunchKernelGGL(k12_normalize, dim3(blocks_of(std::min<uint64_t>(per_launch, A.rows - r0), 4 * per_wave, what)), dim3(256), 0, s, A.row_ptr, A.val, out_val, r0,
+        hipLaunchKernelGGL(kernel, dim3(blocks_of(std::min<uint64_t>(per_launch, A.rows - r0), 4 * per_wave, what)), dim3(256), 0, s, A.row_ptr, A.val, out_val, r0,
                            (uint64_t)A.rows, A.nnz, per_wave, words.as<unsigned long long>());
         XRL_LAUNCH_CHECK();
     }

@@ -35,6 +35,26 @@ void copy_pattern(const QueriesDev& v, hipStream_t s, DevCsr& out) {
     if (v.nnz) XRL_HIP(hipMemcpyAsync(out.idx.p, v.col_idx, v.nnz * 4, hipMemcpyDeviceToDevice, s));
 }
 
+// both row normalisation entry points: the handle's rows by `norm`, in place or into a new owned handle
+int normalize_rows_handle(const char* what, void* A, int norm, int in_place, void** out, void* hip_stream) {
+    const Queries& a = csr_handle(std::string(what) + ": ", A, "A");
+    if (!in_place && !out) fail(std::string(what) + ": null argument (out)");
+    require_gpu();
+    use_device(a.device);
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    EmbedForms f;
+    if (in_place) {
+        normalize_rows_device(what, a.dev, const_cast<float*>(a.dev.val), s, f, norm);
+    } else {
+        DevCsr n;
+        copy_pattern(a.dev, s, n);
+        normalize_rows_device(what, a.dev, n.val.as<float>(), s, f, norm);
+        *out = own_handle(std::move(n), a.device, a.dev.rows, a.dev.cols).release();
+    }
+    count_forms(f);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -55,24 +75,14 @@ void* xrl_smat_transpose_device(void* A, void* hip_stream) {
 }
 
 int xrl_smat_normalize_rows_device(void* A, int in_place, void** out, void* hip_stream) {
+    return guarded_value(-1, [&] { return normalize_rows_handle("xrl_smat_normalize_rows_device", A, 2, in_place, out, hip_stream); });
+}
+
+int xrl_smat_normalize_rows_norm_device(void* A, int norm, int in_place, void** out, void* hip_stream) {
     return guarded_value(-1, [&] {
-        const char* what = "xrl_smat_normalize_rows_device";
-        const Queries& a = csr_handle(std::string(what) + ": ", A, "A");
-        if (!in_place && !out) fail(std::string(what) + ": null argument (out)");
-        require_gpu();
-        use_device(a.device);
-        hipStream_t s = static_cast<hipStream_t>(hip_stream);
-        EmbedForms f;
-        if (in_place) {
-            normalize_rows_device(what, a.dev, const_cast<float*>(a.dev.val), s, f);
-        } else {
-            DevCsr n;
-            copy_pattern(a.dev, s, n);
-            normalize_rows_device(what, a.dev, n.val.as<float>(), s, f);
-            *out = own_handle(std::move(n), a.device, a.dev.rows, a.dev.cols).release();
-        }
-        count_forms(f);
-        return 0;
+        const char* what = "xrl_smat_normalize_rows_norm_device";
+        if (norm < 1 || norm > 3) fail(std::string(what) + ": unknown norm " + std::to_string(norm) + " (1 = l1, 2 = l2, 3 = max)");
+        return normalize_rows_handle(what, A, norm, in_place, out, hip_stream);
     });
 }
 

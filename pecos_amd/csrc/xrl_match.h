@@ -21,6 +21,12 @@ struct MatchCounters { uint64_t lds_rows = 0, big_rows = 0, read = 0, written = 
 // (message starts with `what`) when an operand stores a column id that is not below cols, or a row holds 2^31 entries or more.
 void pattern_union_device(const char* what, const std::vector<QueriesDev>& ops, uint32_t rows, uint32_t cols, hipStream_t s, DevCsr& out, MatchCounters& c);
 
+// Does R (CSR view; same shape and device as Y: the callers check it) store exactly Y's entries and no value below 0?  status[0] <- 0 yes,
+// 1 the row pointers differ, 2 the column ids differ, 3 a value of R is below 0 (-0.0 and NaN are not) -- the first of these that
+// check_relevance meets; status[1] <- the first row that offends so.  One pass (a wavefront per row), one 8-byte readback, one
+// synchronise of s.  Every row span is clamped to both matrices' nnz.
+void check_relevance_device(const QueriesDev& Y, const QueriesDev& R, hipStream_t s, uint64_t status[2]);
+
 // A fixed-stride beam in HBM (idx [rows * stride], cnt [rows]; a count above the stride reads as the stride) against a layer's child
 // ranges (chunk_col [n_parents + 1]): the largest per-row sum over the listed parents of their child counts, every occurrence of a
 // repeated parent counted.  One 8-byte readback, one synchronise of s.  A parent id that is not below n_parents is never followed:

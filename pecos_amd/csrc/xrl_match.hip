@@ -13,9 +13,14 @@
 //   k14_beam_bound   a beam in HBM against a layer's child ranges: per row the sum over listed parents of their child counts, the
 //                    maximum in one u64 (what the host form of the single-layer predict computes in a loop over csr_codes)
 //   k14_fill_ones    the beam of fill_ones
+//   k14_check_relevance  does R store exactly Y's entries and no value below 0 (MLProblem's check of a relevance matrix; rule C in
+//                    include/xrl_abi.h): one wavefront per row compares the row's ends, then -- where the spans agree -- the column ids
+//                    position by position and R's values against 0; the least (code << 40 | row) over the offending rows lands in one
+//                    u64 by atomicMin: one pass, one 8-byte readback
 //
 // Bounds: every row span is clamped to the operand's nnz; an LDS index is below CAP and a scratch index below its row's share before the
-// write; an output index is below the row's end in the scanned row pointer; a parent id is below n_parents before chunk_col is read.
+// write; an output index is below the row's end in the scanned row pointer; a parent id is below n_parents before chunk_col is read; the
+// check reads entries only inside a span that both matrices' clamped row pointers agree on.
 #include "xrl_match.h"
 #include "xrl_device.h"
 #include "xrl_devprim.h"
@@ -242,7 +247,52 @@ __global__ void __launch_bounds__(256) k14_fill_ones(uint32_t* __restrict__ idx,
     if (p == 0) cnt[x / n_parents] = n_parents;
 }
 
+// ---- the relevance check: does R store exactly Y's entries, and no value below 0?
+// One wavefront per row.  word <- the least (code << 40 | row) over the rows that offend: code 1 = the row's end (row 0: also its start)
+// differs between the row pointers, 2 = a column id differs at some position of a row whose span is the same in both, 3 = a value of R in
+// such a row is below 0 (-0.0 and NaN are not).  The least key is the first check that fails in check_relevance's order, at its first row.
+__global__ void __launch_bounds__(256)
+k14_check_relevance(const uint64_t* __restrict__ y_ptr, const uint32_t* __restrict__ y_idx, uint64_t y_nnz, const uint64_t* __restrict__ r_ptr,
+                    const uint32_t* __restrict__ r_idx, const float* __restrict__ r_val, uint64_t r_nnz, uint32_t rows, unsigned long long* __restrict__ word) {
+    const uint64_t i = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (i >= rows) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t code = 0;
+    if (y_ptr[i + 1] != r_ptr[i + 1] || (i == 0 && y_ptr[0] != r_ptr[0])) code = 1;
+    else if (y_ptr[i] == r_ptr[i]) {                       // (a start that differs is the row above's end: reported there)
+        uint64_t b, e, rb, re;
+        row_span(y_ptr, i, y_nnz, b, e);
+        row_span(r_ptr, i, r_nnz, rb, re);
+        if (rb != b || re != e) code = 1;                  // (the clamps differ: a pointer past one matrix's entries)
+        else {
+            bool ids = false, neg = false;
+            for (uint64_t x = b + lane; x < e; x += 64u) {
+                ids = ids || y_idx[x] != r_idx[x];
+                neg = neg || r_val[x] < 0.0f;
+            }
+            if (__ballot(ids)) code = 2;
+            else if (__ballot(neg)) code = 3;
+        }
+    }
+    if (lane == 0 && code) atomicMin(word, ((unsigned long long)code << 40) | i);
+}
+
 }  // namespace
+
+void check_relevance_device(const QueriesDev& Y, const QueriesDev& R, hipStream_t s, uint64_t status[2]) {
+    status[0] = 0; status[1] = 0;
+    if (Y.rows == 0) { XRL_HIP(hipStreamSynchronize(s)); return; }
+    DevBuf d_word;
+    d_word.reserve(8);
+    XRL_HIP(hipMemsetAsync(d_word.p, 0xFF, 8, s));
+    hipLaunchKernelGGL(k14_check_relevance, dim3(blocks_of(Y.rows, 4, "check_relevance")), dim3(256), 0, s, Y.row_ptr, Y.col_idx, Y.nnz, R.row_ptr, R.col_idx, R.val, R.nnz,
+                       Y.rows, d_word.as<unsigned long long>());
+    XRL_LAUNCH_CHECK();
+    uint64_t key = 0;
+    XRL_HIP(hipMemcpyAsync(&key, d_word.p, 8, hipMemcpyDeviceToHost, s));
+    XRL_HIP(hipStreamSynchronize(s));
+    if (key != ~0ull) { status[0] = key >> 40; status[1] = key & ((1ull << 40) - 1); }
+}
 
 void pattern_union_device(const char* what_c, const std::vector<QueriesDev>& ops, uint32_t rows_u, uint32_t cols, hipStream_t s, DevCsr& Z, MatchCounters& c) {
     const std::string what = std::string(what_c) + ": ";

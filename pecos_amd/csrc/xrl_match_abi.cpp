@@ -46,6 +46,23 @@ void* xrl_smat_pattern_union_device(void* const* mats, uint32_t n, void* hip_str
     });
 }
 
+int xrl_smat_check_relevance_device(void* Y, void* R, uint64_t* status, void* hip_stream) {
+    return guarded_value(-1, [&] {
+        const std::string what = "xrl_smat_check_relevance_device: ";
+        const Queries& y = csr_handle(what, Y, "Y");
+        const Queries& r = csr_handle(what, R, "R");
+        if (!status) fail(what + "null argument (status)");
+        if (y.dev.rows != r.dev.rows || y.dev.cols != r.dev.cols)
+            fail(what + "R has shape " + std::to_string(r.dev.rows) + " x " + std::to_string(r.dev.cols) + ", Y has " + std::to_string(y.dev.rows) + " x " +
+                 std::to_string(y.dev.cols));
+        if (y.device != r.device) fail(what + "Y and R are on devices " + std::to_string(y.device) + " and " + std::to_string(r.device));
+        require_gpu();
+        use_device(y.device);
+        check_relevance_device(y.dev, r.dev, static_cast<hipStream_t>(hip_stream), status);
+        return 0;
+    });
+}
+
 int xrl_debug_match_forms(uint64_t* out, uint32_t n) {
     return guarded_value(-1, [&] {
         if (!out) fail("xrl_debug_match_forms: null argument");

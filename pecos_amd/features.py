@@ -534,11 +534,28 @@ class DeviceMatrix:
         """The transpose as a new :class:`DeviceMatrix`, rows in scipy's ``.T.tocsr()`` order (K12; rule R2 at ``xrl_label_embedding_device``)."""
         return DeviceMatrix(clib.smat_transpose_device(self.handle, stream=stream))
 
-    def normalize_rows(self, in_place=False, stream=None):
-        """Rows scaled to unit L2 norm in sklearn's arithmetic (K12; rule R1).  ``in_place`` rewrites this matrix's values -- the wrapped
-        tensor's, for :meth:`from_torch` -- and returns ``self``; otherwise a new :class:`DeviceMatrix`."""
-        h = clib.smat_normalize_rows_device(self.handle, in_place, stream=stream)
+    def normalize_rows(self, in_place=False, stream=None, norm="l2"):
+        """Rows scaled to unit ``norm`` (``l2``, ``l1`` or ``max``) in sklearn's arithmetic (K12; rules R1, R1a, R1b).  ``in_place``
+        rewrites this matrix's values -- the wrapped tensor's, for :meth:`from_torch` -- and returns ``self``; otherwise a new
+        :class:`DeviceMatrix`.  ``max`` refuses a row whose column ids are not strictly ascending."""
+        h = clib.smat_normalize_rows_device(self.handle, in_place, stream=stream, norm=norm)
         return self if in_place else DeviceMatrix(h)
+
+    @staticmethod
+    def check_relevance(Y, R, by_columns=True, stream=None):
+        """ValueError, in :func:`pecos_amd.xlinear.check_relevance`'s words, unless ``R`` stores exactly the entries of ``Y`` and no
+        negative value: both :class:`DeviceMatrix` of one shape, compared where they are (K14's check kernel; rule C).  The host check
+        reads both column-major, so ``by_columns`` compares the device transposes -- which of ``indptr`` and ``indices`` the message names
+        is then the host's; False compares the rows as stored."""
+        if Y.shape != R.shape:
+            raise ValueError(f"Invalid relevance matrix: R has shape {R.shape}, Y has {Y.shape}")
+        if by_columns:
+            Y, R = Y.transpose(stream=stream), R.transpose(stream=stream)
+        code, _ = clib.smat_check_relevance_device(Y.handle, R.handle, stream=stream)
+        if code in (1, 2):
+            raise ValueError(f"Invalid relevance matrix: Y.{'indptr' if code == 1 else 'indices'} != R.{'indptr' if code == 1 else 'indices'}")
+        if code == 3:
+            raise ValueError("Invalid relevance matrix: got value < 0")
 
     @classmethod
     def hstack(cls, mats, stream=None):

@@ -144,6 +144,97 @@ def _union_of_sources(t, scheme, labels_of, c, user_supplied, m_pred, stream):
     return DeviceMatrix.pattern_union(parts, stream=stream)
 
 
+def _shape_of(o):
+    """(rows, cols) of an operand: a scipy matrix or :class:`DeviceMatrix` (``.shape``), or CSR tensors ``(crow, col, val, (rows, cols))``."""
+    return tuple(int(v) for v in (o[3] if isinstance(o, (tuple, list)) else o.shape))
+
+
+class _Shaped(object):
+    """Stands in for a matrix where only its shape is read."""
+
+    def __init__(self, shape):
+        self.shape = shape
+
+
+def _partial_chain_check(D, chain):
+    """``ClusterChain.matrix_chain_dimension_check`` over operands of any served kind, from their shapes alone: ``(nr_insts, nr_labels)``."""
+    from .cluster_chain import ClusterChain
+    shapes = {k: None if v is None else _Shaped(_shape_of(v)) for k, v in D.items()}
+    return ClusterChain([_Shaped(_shape_of(c)) for c in chain]).matrix_chain_dimension_check(shapes)
+
+
+def _nothing_given(D):
+    return D is None or all(D[k] is None for k in D)
+
+
+def relevance_chain_device(R_dict, chain, norm_type, induce, stream=None):
+    """``ClusterChain.generate_relevance_chain`` (pecos/utils/cluster_util.py:240-281) with every matrix resident in HBM.  ``R_dict`` maps
+    layers above the leaves (0: instances x labels) to relevance matrices; ``chain`` is the list of ``C``, root first; operands are scipy
+    matrices (uploaded as CSR), CSR tensors or :class:`~pecos_amd.features.DeviceMatrix`.  Level 0 is ``R_dict.get(0)``; level i is
+    ``R_dict[i]`` when given, else under ``induce`` the device product of level i-1 and ``chain[-i]`` (K10, explicit zeros kept, rows
+    sorted), else None; the levels are then normalised by row under ``norm_type`` (``l1``, ``l2``, ``max``; None and ``no-norm``: as they
+    are) by K12 -- a caller's level into a copy, never in place -- and returned root side first without the root: a list of ``len(chain)``
+    :class:`DeviceMatrix` or None, which :func:`train_chain_device` takes as ``relevance_chain``.  Dimension errors are the reference's,
+    as ``ValueError``, before a device is touched.  Runs on ``stream`` (default: torch's current one), which every step synchronises."""
+    from .core import clib as _clib
+    from .features import _as_device_matrix, _stream_or_current
+    chain = list(chain)
+    if _nothing_given(R_dict):
+        return [None] * len(chain)
+    _partial_chain_check(R_dict, chain)
+    if norm_type not in (None, "no-norm") and norm_type not in _clib.ROW_NORMS:
+        raise ValueError(f"'{norm_type}' is not a supported norm")
+    dev = _device_of(list(R_dict.values()) + chain)
+    s = _stream_or_current(dev, stream)
+    levels, given = [], []
+    for i in range(len(chain) + 1):
+        if R_dict.get(i, None) is not None:
+            levels.append(_as_device_matrix(R_dict[i], dev, None, stream))
+            given.append(True)
+        elif i > 0 and levels[i - 1] is not None and induce:
+            levels.append(levels[i - 1].multiply(_as_device_matrix(chain[-i], dev, None, stream), eliminate_zeros=False, sorted_indices=True, stream=s))
+            given.append(False)
+        else:
+            levels.append(None)
+            given.append(False)
+    if norm_type not in (None, "no-norm"):                  # (after the last product: a level is induced from the one below as it was given)
+        levels = [None if m is None else m.normalize_rows(in_place=not own, stream=s, norm=norm_type) for m, own in zip(levels, given)]
+    levels.reverse()
+    return levels[1:]
+
+
+def matching_chain_device(M_dict, chain, stream=None):
+    """``ClusterChain.generate_matching_chain`` (pecos/utils/cluster_util.py:206-238) with every matrix resident in HBM: the chain of
+    instance-to-cluster matching matrices of user-supplied negatives.  Level 0 is the pattern of ``M_dict[0]`` (instances x labels), or
+    empty; level i is the pattern of the device product of level i-1 and ``chain[-i]`` (K10), united with ``M_dict[i]`` when given (K14).
+    Only the pattern is the contract: the trainer reads nothing else of a matching matrix.  Returns the levels root side first without the
+    label level: a list of ``len(chain)`` :class:`DeviceMatrix` (all None when nothing is given), which :func:`train_chain_device` takes
+    as ``matching_chain``.  Operands, errors and the stream are :func:`relevance_chain_device`'s."""
+    import scipy.sparse as smat
+    from .features import DeviceMatrix, _as_device_matrix, _stream_or_current
+    chain = list(chain)
+    if _nothing_given(M_dict):
+        return [None] * len(chain)
+    nr_insts, nr_labels = _partial_chain_check(M_dict, chain)
+    dev = _device_of(list(M_dict.values()) + chain)
+    s = _stream_or_current(dev, stream)
+
+    def given(i):
+        return None if M_dict.get(i, None) is None else _as_device_matrix(M_dict[i], dev, None, stream)
+
+    level = given(0)
+    if level is None:
+        level = DeviceMatrix.upload(smat.csr_matrix((nr_insts, nr_labels), dtype="float32"), dev)
+    levels = []
+    for i in range(1, len(chain) + 1):
+        level = level.multiply(_as_device_matrix(chain[-i], dev, None, stream), eliminate_zeros=False, sorted_indices=True, stream=s)
+        own = given(i)
+        level = DeviceMatrix.pattern_union([level] if own is None else [level, own], stream=s)
+        levels.append(level)
+    levels.reverse()
+    return levels
+
+
 def train_chain_device(X, Y, chain, neg_mining_chain="tfn", matching_chain=None, relevance_chain=None, train_params=None, pred_params=None,
                        return_matching=False, stream=None):
     """The layers of a cluster chain trained top down with everything resident in HBM (pecos/xmc/base.py:1512-1572).  ``X`` (instances x

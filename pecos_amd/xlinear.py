@@ -12,6 +12,8 @@ Surface kept from the reference (same names, kwargs and error behaviour):
 * ``MLProblem``, ``MLModel.{TrainParams, train, save}``, ``HierarchicalMLModel.{TrainParams, train, save}``,
   ``XLinearModel.{TrainParams, train, save}``                           pecos/xmc/base.py:488-880, 1371-1572
   training on the device (K13): a trained model predicts natively and saves the reference's folder layout
+* ``XLinearModel.train_ext``: the reference's ``XLinearModel.train`` with relevance induction, user-supplied negatives and the
+  ``matcher`` / ``ranker`` modes                                          pecos/xmc/xlinear/model.py:219-283
 
 Pruning and the python (non predict-only) model chain stay in the reference: loading with
 ``is_predict_only=False`` raises ``NotImplementedError``, and a loaded model cannot be saved.
@@ -20,6 +22,7 @@ import copy
 import dataclasses as dc
 import json
 import os
+import types
 from glob import glob
 from os import path
 
@@ -139,6 +142,13 @@ class MLModel:
         clib.xlinear_single_layer_predict(X, csr_codes, self.W, self.C, pred_params.post_processor, pred_params.only_topk if pred_params.only_topk else 0,
                                           kwargs.get("threads", -1), self.bias, pred_alloc)
         return pred_alloc.get()
+
+    @classmethod
+    def load(cls, folder):
+        """A layer folder written by :meth:`save` here or by the reference: W and C as float32 CSC on the host."""
+        param = json.loads(open(f"{folder}/param.json", "r", encoding="utf-8").read())
+        W, C = (smat.csc_matrix(smat.load_npz(f"{folder}/{name}.npz"), dtype=np.float32) for name in ("W", "C"))
+        return cls(W=W, C=C, bias=param["bias"], pred_params=param["pred_kwargs"])
 
     def save(self, folder):
         """The reference's layer folder (pecos/xmc/base.py:807-830): param.json, W.npz, C.npz."""
@@ -373,7 +383,13 @@ class HierarchicalMLModel:
             model = clib.xlinear_load_predict_only(model_folder, **kwargs)
         pred_params = cls.PredParams(
             model_chain=[MLModel.load_pred_params(f"{model_folder}/{d}.model") for d in range(depth)])
-        return cls(model, pred_params=pred_params, is_predict_only=True)
+        loaded = cls(model, pred_params=pred_params, is_predict_only=True)
+        top = f"{model_folder}/0.model/C.npz"
+        if not bool(param.get("is_mmap", False)) and path.exists(top) and smat.load_npz(top).shape[1] > 1:
+            # a top layer of several clusters (a ranker-mode model): the beam search has no single root to start from; such a model
+            # predicts layer by layer, the top layer without codes, as the reference's python path does
+            loaded.layerwise = [MLModel.load(f"{model_folder}/{d}.model") for d in range(depth)]
+        return loaded
 
     @dc.dataclass
     class TrainParams(BaseParams):
@@ -420,12 +436,16 @@ class HierarchicalMLModel:
                                           "an instance, is not served on the device")
         X = prob.X if isinstance(prob.pX, ScipyCsrF32) else _every_entry_csr(prob.X)
         weights = train_chain_device(X, prob.Y, chain, schemes, matching_chain, relevance_chain, layer_params, pp.model_chain)
+        return cls._from_weights(weights, [prob.C if C is None else C for C in chain], layer_params, pp)
+
+    @classmethod
+    def _from_weights(cls, weights, chain, layer_params, pp):
+        """The model of a layer loop's resident weights (W^T per layer) over the host chain: the weights are downloaded once."""
         layers = []
         for t, wt in enumerate(weights):
             Wt = wt.download()                               # labels x (features + (bias > 0)) in CSR = the CSC arrays of W
             W = smat.csc_matrix((Wt.data, Wt.indices, Wt.indptr), shape=(Wt.shape[1], Wt.shape[0]), dtype=np.float32)
-            C = prob.C if chain[t] is None else chain[t]
-            layers.append(MLModel(W=W, C=C, bias=layer_params[t].bias, pred_params=pp.model_chain[t]))
+            layers.append(MLModel(W=W, C=chain[t], bias=layer_params[t].bias, pred_params=pp.model_chain[t]))
         return cls._from_layers(layers, pp)
 
     @classmethod
@@ -486,17 +506,7 @@ class HierarchicalMLModel:
 
     def _resolve_overrides(self, pred_params, kwargs):
         """xmc/base.py:1609-1654: merge kwargs, then only UNIFORM overrides are expressible natively."""
-        if pred_params is None:
-            pred_params = self.get_pred_params()
-        elif isinstance(pred_params, self.PredParams):
-            pred_params = self.PredParams.from_dict(pred_params)
-            if isinstance(pred_params.model_chain, MLModel.PredParams):
-                pred_params.model_chain = [copy.deepcopy(pred_params.model_chain) for _ in range(self.depth)]
-            elif len(pred_params.model_chain) != self.depth:
-                raise ValueError(f"len(params.model_chain)={len(pred_params.model_chain)} != {self.depth}")
-        else:
-            raise ValueError("unknown type(pred_params)!!")
-        pred_params.override_with_kwargs(kwargs)
+        pred_params = self._merged_pred_params(pred_params, kwargs)
         old_chain = self.get_pred_params().model_chain
         new_chain = pred_params.model_chain
         if all(o.post_processor == n.post_processor for o, n in zip(old_chain, new_chain)):
@@ -513,10 +523,30 @@ class HierarchicalMLModel:
             raise NotImplementedError("when is_predict_only=True, beam_size is not supported for overriding")
         return beam, pp, new_chain[-1].only_topk
 
+    def _merged_pred_params(self, pred_params, kwargs):
+        """xmc/base.py:1609-1619: the model's own prediction parameters, or the given ones per layer, overridden by the keywords."""
+        if pred_params is None:
+            pred_params = self.get_pred_params()
+        elif isinstance(pred_params, self.PredParams):
+            pred_params = self.PredParams.from_dict(pred_params)
+            if isinstance(pred_params.model_chain, MLModel.PredParams):
+                pred_params.model_chain = [copy.deepcopy(pred_params.model_chain) for _ in range(self.depth)]
+            elif len(pred_params.model_chain) != self.depth:
+                raise ValueError(f"len(params.model_chain)={len(pred_params.model_chain)} != {self.depth}")
+        else:
+            raise ValueError("unknown type(pred_params)!!")
+        pred_params.override_with_kwargs(kwargs)
+        return pred_params
+
     def predict(self, X, csr_codes=None, pred_params=None, **kwargs):
         assert X.dtype == np.float32
         assert isinstance(X, smat.csr_matrix) or (isinstance(X, np.ndarray) and X.flags["C_CONTIGUOUS"])
         assert X.shape[1] == self.nr_features
+        if getattr(self, "layerwise", None):                 # (xmc/base.py:1670-1680: a top layer of several clusters has no single root)
+            chain = self._merged_pred_params(pred_params, kwargs).model_chain
+            for layer, pp in zip(self.layerwise, chain):
+                csr_codes = layer.predict(X, csr_codes=csr_codes, pred_params=pp, threads=kwargs.get("threads", -1))
+            return csr_codes
         if csr_codes is not None:
             raise NotImplementedError("is_predict_only=True did not support csr_codes being not None")
         beam, pp, topk = self._resolve_overrides(pred_params, kwargs)
@@ -640,8 +670,8 @@ class XLinearModel:
         return cls._train_through(HierarchicalMLModel.train_device, X, Y, C, R, kwargs.pop("user_supplied_negatives", None), train_params, pred_params, kwargs)
 
     @classmethod
-    def _train_through(cls, train_chain, X, Y, C, R, user_supplied_negatives, train_params, pred_params, kwargs):
-        from .indexer import chain_from_partial
+    def _resolved_train_params(cls, train_params, kwargs):
+        """The ``TrainParams`` of a train call from ``train_params`` or, without them, from the keywords (model.py:199-206)."""
         if train_params is None:
             tp = cls.TrainParams.from_dict(kwargs)
             tp.hlm_args = HierarchicalMLModel.TrainParams(neg_mining_chain=kwargs.get("negative_sampling_scheme", "tfn"), model_chain=MLModel.TrainParams.from_dict(kwargs))
@@ -649,14 +679,93 @@ class XLinearModel:
             tp = cls.TrainParams.from_dict(train_params)
             if isinstance(tp.hlm_args, dict):
                 tp.hlm_args = HierarchicalMLModel.TrainParams.from_dict(tp.hlm_args)
-        for what, bad in (("mode", tp.mode != "full-model"), ("rel_mode", tp.rel_mode != "disable"), ("user_supplied_negatives", user_supplied_negatives is not None)):
-            if bad:
-                raise NotImplementedError(f"XLinearModel.train: {what} = {getattr(tp, what, user_supplied_negatives)!r} is not served on the device")
+        return tp
+
+    @classmethod
+    def _resolved_pred_params(cls, pred_params, kwargs):
+        """The ``HierarchicalMLModel.PredParams`` of a train call, or None (model.py:208-217); ``kwargs`` gets its ``pred_kwargs``."""
         hp = None
         if pred_params is not None:
             hp = cls.PredParams.from_dict(pred_params).hlm_args
         if kwargs.get("pred_kwargs", None) is None:
             kwargs["pred_kwargs"] = {k: kwargs.get(k, None) for k in ("beam_size", "only_topk", "post_processor")}
+        return hp
+
+    @classmethod
+    def train_ext(cls, X, Y, C=None, R=None, user_supplied_negatives=None, train_params=None, pred_params=None, **kwargs):
+        """:meth:`train_device` with every option of the reference's ``XLinearModel.train`` (pecos/xmc/xlinear/model.py:219-283):
+        ``rel_mode`` ``induce`` / ``ranker-only`` with ``rel_norm`` ``l1`` / ``l2`` / ``max`` / ``no-norm`` (cost-sensitive training from
+        ``R``, or from the binarized ``Y``), ``user_supplied_negatives`` (a dict of matching matrices keyed by layers above the leaves,
+        for schemes with ``usn``), and the ``matcher`` / ``ranker`` modes with ``ranker_level``.  The chain is completed from a partial
+        one (``shallow``, ``min_codes``, ``nr_splits``); X, Y and the chain are uploaded once; the matching and relevance chains are
+        built in HBM (:func:`pecos_amd.training.matching_chain_device`, ``relevance_chain_device``) and never visit the host; a relevance
+        level the caller gave is checked against the loop's ``Y_t`` by the device check (:meth:`DeviceMatrix.check_relevance`) before
+        the first layer is trained.  Every ``ValueError`` of the reference comes before a device is touched.  Without ``C`` this is
+        :meth:`train_device` (``R`` gives the one-versus-all costs).  The result saves, loads and predicts like :meth:`train_device`'s;
+        a ``ranker``-mode model has a top layer of several clusters and predicts without codes as the reference does."""
+        from .cluster_chain import ClusterChain
+        from .features import DeviceMatrix, _as_device_matrix, _stream_or_current
+        from .training import _device_of, _partial_chain_check, matching_chain_device, relevance_chain_device, train_chain_device
+        tp, hp = cls._resolved_train_params(train_params, kwargs), cls._resolved_pred_params(pred_params, kwargs)
+        no_chain =C is None or (isinstance(C, (list, tuple)) and len(C) == 0)
+        if tp.mode not in ("full-model", "matcher", "ranker"):
+            raise ValueError(f"Wrong value for the mode attribute: {tp.mode}")
+        if no_chain:
+            if tp.mode != "full-model":
+                raise ValueError(f"Expect non-trivial clustering for {tp.mode} mode")
+            return cls(HierarchicalMLModel.train_device(MLProblem(X, Y, R=R), clustering=None, train_params=tp.hlm_args, pred_params=hp, **kwargs))
+        if tp.rel_mode not in ("disable", "induce", "ranker-only"):
+            raise ValueError(f"Wrong value for rel_mode: {tp.rel_mode}")
+        min_codes, nr_splits = (None, 16) if tp.shallow else (tp.min_codes or tp.nr_splits, tp.nr_splits)
+        chain = ClusterChain.from_partial_chain(C.chain if isinstance(C, ClusterChain) else C, min_codes=min_codes, nr_splits=nr_splits)
+        level = int(tp.ranker_level)
+        if tp.mode != "full-model" and not 0 < level < len(chain) + (tp.mode == "ranker"):
+            raise ValueError(f"ranker_level = {level} leaves no layer to train in {tp.mode} mode: the chain has {len(chain)} layers")
+        if not isinstance(X, np.ndarray) and not smat.issparse(X):
+            raise NotImplementedError("type(X) = {} is not supported.".format(type(X)))
+        if X.dtype != np.float32:
+            raise ValueError(f"X must be float32, got {X.dtype}")
+        if chain[-1].shape[0] != Y.shape[1]:
+            raise ValueError(f"the bottom clustering matrix has {chain[-1].shape[0]} rows, the problem {Y.shape[1]} labels")
+        usn = user_supplied_negatives
+        for D in (usn, None if R is None else {0: R}):
+            if D is not None and not all(D[k] is None for k in D) and _partial_chain_check(D, chain)[0] != Y.shape[0]:
+                raise ValueError("M_dict first dim do not match")
+        cut = slice(None) if tp.mode == "full-model" else slice(None, -level) if tp.mode == "matcher" else slice(-level, None)
+        host_chain = list(chain)[cut]
+
+        labels = types.SimpleNamespace(nr_labels=host_chain[-1].shape[0])        # what _training_setup reads of a problem
+        _, _, schemes, layer_params, pp = HierarchicalMLModel._training_setup(labels, host_chain, tp.hlm_args, hp, kwargs, True)
+
+        dev = _device_of([X, Y, R] + list((usn or {}).values()))
+        s = _stream_or_current(dev, None)
+        x = _as_device_matrix(X if smat.issparse(X) else _every_entry_csr(X), dev, None, None)
+        y = _as_device_matrix(Y, dev, None, None)
+        cs = [DeviceMatrix.upload(c, dev) for c in chain]
+        matching = matching_chain_device(usn, cs, stream=s)
+        given = None
+        if tp.rel_mode == "disable" or (tp.rel_mode == "ranker-only" and R is None):      # ({0: None}: nothing given, a chain of None)
+            relevance = [None] * len(cs)
+        else:
+            given = None if R is None else _as_device_matrix(R, dev, None, None)
+            level0 = given if given is not None else DeviceMatrix.pattern_union([y], stream=s)          # binarized(Y)
+            relevance = relevance_chain_device({0: level0}, cs, tp.rel_norm, tp.rel_mode == "induce", stream=s)
+        if tp.mode == "matcher":
+            for c in reversed(cs[-level:]):
+                y = y.multiply(c, stream=s)
+        elif given is not None:                             # the caller's level is the leaves': against the loop's own Y there
+            DeviceMatrix.check_relevance(y, relevance[-1], stream=s)
+        weights = train_chain_device(x, y, cs[cut], schemes, matching[cut], relevance[cut], layer_params, pp.model_chain, stream=s)
+        return cls(HierarchicalMLModel._from_weights(weights, host_chain, layer_params, pp))
+
+    @classmethod
+    def _train_through(cls, train_chain, X, Y, C, R, user_supplied_negatives, train_params, pred_params, kwargs):
+        from .indexer import chain_from_partial
+        tp = cls._resolved_train_params(train_params, kwargs)
+        for what, bad in (("mode", tp.mode != "full-model"), ("rel_mode", tp.rel_mode != "disable"), ("user_supplied_negatives", user_supplied_negatives is not None)):
+            if bad:
+                raise NotImplementedError(f"XLinearModel.train: {what} = {getattr(tp, what, user_supplied_negatives)!r} is not served on the device")
+        hp = cls._resolved_pred_params(pred_params, kwargs)
         if C is None or (isinstance(C, (list, tuple)) and len(C) == 0):
             clustering = None
         else:                                                   # the given levels, completed upwards to a single root (ClusterChain.from_partial_chain)
