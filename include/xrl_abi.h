@@ -677,6 +677,64 @@ void* xrl_train_layer_device(void* X, void* Yt, void* Ct_or_null, void* Mt_or_nu
                              int solver_type, double Cp, double Cn, uint64_t max_iter, double eps, double bias, void* hip_stream);
 int xrl_debug_train_counters(uint64_t* out, uint32_t n);
 
+/* The primal solver for the L2-loss SVC on the device (K16, csrc/xrl_newton.hip): L2R_L2LOSS_SVC_PRIMAL = 2 of the reference's solver table,
+ * SVMWorker::solve_l2r_l2_svc_primal (linear_solver.hpp:407-417) over l2r_erm_fun / l2r_l2_svc_fun (:62-323), NEWTON::newton / pcg / norm
+ * (utils/newton.hpp:98-273) and the vector helpers (utils/matrix.hpp:862-976).  Jobs, instances and emission are xrl_train_layer_device's
+ * above, and so are the pinned answers to repeated row ids; the weights are the reference's at threads = 1 bit for bit (tests/
+ * primal_training_rule.py states the rule in numpy).  The solver arrives under names of its own because the refusal of solver 2 through
+ * the three entry points above is part of their contract.
+ * Rule N, one job.  value_type is float: w, b, g, M, s, r, d, Hd, z, wx, tmp, their bias parts and c_i = fl32((double)cost_i * (y_i > 0 ? Cp :
+ *   Cn)) are fp32; f, alpha, beta, zTr, dHd, Q, gnorm, wTw, sTs, wTs, gTs, xTs are fp64.  Every dot product is an fp32 chain from +0 of fp32
+ *   products in index order, returned as fp32; norm is an fp64 chain of (double)g_i * g_i plus (double)bg * bg, then sqrt.  An axpy with an
+ *   fp64 factor is y <- fl32((double)y + a * (double)x); with an fp32 factor it is fp32 throughout.  r / M is the fp32 quotient.  With
+ *   bias <= 0 every bias part stays 0.
+ *   fun:  wx_i = fl32((double)(w . x_i) + bias * (double)b) (bias > 0; else the dot); f = sum over index of (double)c_i * t * t with t = 1 -
+ *     (double)y_i * wx_i where t > 0, an fp64 chain in index order, + 0.5 * wTw; wTw = (double)(w . w) + (double)b * b.
+ *   grad: in index order tmp_i = wx_i * y_i (fp32); where tmp_i < 1, instance i is active: I[sizeI] = i and tmp[sizeI] = (c_i * y_i) *
+ *     (tmp_i - 1) (fp32).  THE REFERENCE COMPACTS INTO tmp ITSELF: an instance whose row id is below sizeI at its turn overwrites that
+ *     compacted slot with its raw tmp_i, and X_I' reads it.  This happens when a positive that M does not list is appended to index and
+ *     its row id is below the count of active instances then; it is reproduced as written.  g = w + 2 * sum_I tmp[k] * x_I[k] (fp32 axpys
+ *     in I's order, then x + 2y in fp32); bg = b + 2 * (sum of fl32((double)bg + bias * (double)tmp[k])).
+ *   newton: w = 0; f, g at 0; gnorm0 = gnorm = norm(g).  gnorm <= eps * gnorm0 ends before the first iteration.  Up to 1000 iterations
+ *     (NEWTON's own default: max_iter is NOT used): M = 1 + sum_I (x * x) * (2 * c_i) (fp32), bM = 1 + sum of bias * bias * 2 * (double)c_i
+ *     rounded per term, then M <- fl32(0.99 + 0.01 * (double)M); s = pcg(); the line search; a step of 0 ends the job; grad; gnorm <= eps *
+ *     gnorm0 ends it; so does |fold - f| <= 1e-12 * |f|.
+ *   pcg: s = 0, r = -g, z = r / M, d = z; zTr = z . r; cgtol = min(0.5, sqrt(sqrt(zTr))); at most max(d + (bias > 0), 5) steps WITH d THE
+ *     FEATURE COUNT OF X: Hd = d + 2 X_I' (c .* (X_I d)) with xTs_i = (double)c_i * ((double)(d . x_i) + bias * (double)bd) and fp64-factor
+ *     axpys; dHd = d . Hd; dHd <= 1e-16 ends; alpha = zTr / dHd; s += alpha d; r -= alpha Hd; newQ = -0.5 * (double)fl32((s . r) - (s . g)) -
+ *     0.5 * (double)fl32(bs * br - bs * bg); newQ <= 0 and newQ - Q <= 0 or the run ends ("quadratic approximation > 0"); step * (newQ - Q) >=
+ *     cgtol * newQ ends; z = r / M; beta = (z . r) / zTr; d <- fl32((double)d + (beta - 1) * (double)d), then d <- fl32((double)d + (double)z).
+ *   line search (l2r_l2_svc_fun's own; the base class's is dead code): tmp = X s (as wx above, with bs), sTs, wTs, gTs; alpha = 1, up to 20
+ *     times: f = loss(wx + alpha * tmp) + (alpha * alpha * sTs + wTw) / 2 + alpha * wTs; f - fold <= 0.01 * alpha * gTs accepts, else alpha
+ *     halves.  Accepted: wx_i <- fl32((double)wx_i + alpha * (double)tmp_i) ONCE PER LISTED POSITION, w += alpha s, b += alpha bs, wTw +=
+ *     alpha * alpha * sTs + 2 * alpha * wTs.  After 20 halvings f = fold and the step is 0.
+ *   wx and wTw (updated by the line search, read by grad and the next line search) and sizeI and I (from grad into the preconditioner
+ *     and Hv) persist across the calls.
+ * The compressed form.  A feature that no instance of a job stores stays +-0 in every vector and 1 in M, adds +-0 to chains that start at
+ *   +0, and is emitted as +0.  The device therefore walks only the job's touched features, in ascending order -- as long as every scalar
+ *   multiplied into a vector is finite.  A job whose pcg meets a non-finite alpha or beta fails the call, naming the first such label; a
+ *   non-finite value stored in X fails it before training (a check kernel).  Cp, Cn, eps, bias, threshold and R's values are used as given.
+ * Refused before a GPU is required, with the function's name first: solvers 1 and 3 (the message names the entry point above that serves
+ *   them), 7 (its inner Newton steps call log in fp64, and the device's log is not the host library's), unknown solvers; and every
+ *   refusal of the entry points above (nulls, shapes, two devices, 2^31 rows, 2^32 - 1 jobs, a label twice in C, R's pattern).
+ *   xrl_single_layer_train_newton_csr_f32 / _drm_f32   xrl_single_layer_train_*'s argument lists and result, solver_type == 2
+ *   xrl_train_layer_newton_device   xrl_train_layer_device's argument list and result: a NEW owned W^T handle
+ *   xrl_debug_newton_counters    FOR TESTS ONLY: of the last primal training of this process, out[0..n), n <= 20 <- {jobs, batches, slots,
+ *                                staging stride, Newton iterations, CG steps, Hv calls, line-search halvings, jobs ended before the
+ *                                first iteration, jobs ended by the gradient test, by a failed line search, by a small actual reduction,
+ *                                by the 1000-iteration cap, CG runs ended by dHd <= 1e-16, by the Q test, by a positive quadratic
+ *                                approximation, by the step cap, instances (per listed position) whose feature row is summed one per
+ *                                lane, by a wavefront (64 entries and more), jobs flagged non-finite} */
+void xrl_single_layer_train_newton_csr_f32(const ScipyCsrF32* pX, const ScipyCscF32* pY, const ScipyCscF32* pC, const ScipyCscF32* pM, const ScipyCscF32* pR,
+                                           py_coo_allocator_t coo_alloc, double threshold, uint32_t max_nonzeros_per_label, int solver_type, double Cp, double Cn,
+                                           size_t max_iter, double eps, double bias, int threads);
+void xrl_single_layer_train_newton_drm_f32(const ScipyDrmF32* pX, const ScipyCscF32* pY, const ScipyCscF32* pC, const ScipyCscF32* pM, const ScipyCscF32* pR,
+                                           py_coo_allocator_t coo_alloc, double threshold, uint32_t max_nonzeros_per_label, int solver_type, double Cp, double Cn,
+                                           size_t max_iter, double eps, double bias, int threads);
+void* xrl_train_layer_newton_device(void* X, void* Yt, void* Ct_or_null, void* Mt_or_null, void* Rt_or_null, double threshold, uint32_t max_nonzeros_per_label,
+                                    int solver_type, double Cp, double Cn, uint64_t max_iter, double eps, double bias, void* hip_stream);
+int xrl_debug_newton_counters(uint64_t* out, uint32_t n);
+
 /* Matcher-aware negatives (MAN) on the device: what joins a trained layer, its prediction and the next layer's matching matrix in HBM
  * (K14, csrc/xrl_match.hip; pecos_amd.train_chain_device runs the reference's loop, pecos/xmc/base.py:1512-1572, over them).
  * Rule U, xrl_smat_pattern_union_device(mats, n): n >= 1 matrix handles of one shape on one device.  A NEW owned CSR handle of that shape

@@ -344,7 +344,14 @@ class corelib(object):
                                                         _coo_alloc_t, c_double, c_uint32, c_int, c_double, c_double, c_uint64, c_double, c_double, c_int]),
         "xrl_train_layer_device": (c_void_p, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_uint32, c_int, c_double, c_double, c_uint64, c_double,
                                               c_double, c_void_p]),
+        "xrl_single_layer_train_newton_csr_f32": (None, [POINTER(ScipyCsrF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32),
+                                                         _coo_alloc_t, c_double, c_uint32, c_int, c_double, c_double, c_uint64, c_double, c_double, c_int]),
+        "xrl_single_layer_train_newton_drm_f32": (None, [POINTER(ScipyDrmF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32),
+                                                         _coo_alloc_t, c_double, c_uint32, c_int, c_double, c_double, c_uint64, c_double, c_double, c_int]),
+        "xrl_train_layer_newton_device": (c_void_p, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_uint32, c_int, c_double, c_double, c_uint64,
+                                                     c_double, c_double, c_void_p]),
         "xrl_debug_train_counters": (c_int, [POINTER(c_uint64), c_uint32]),
+        "xrl_debug_newton_counters": (c_int, [POINTER(c_uint64), c_uint32]),
         "xrl_smat_pattern_union_device": (c_void_p, [POINTER(c_void_p), c_uint32, c_void_p]),
         "xrl_single_layer_predict_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, c_float, c_void_p,
                                                     c_void_p, c_void_p, c_uint32, c_void_p]),
@@ -755,6 +762,11 @@ class corelib(object):
             return XLINEAR_SOLVERS[solver_type]
         return int(solver_type)
 
+    def _train_symbol(self, solver_type, pattern):
+        """The entry point that serves a solver: K16's (``..._newton...``) for L2R_L2LOSS_SVC_PRIMAL, K13's for every other number (which
+        refuses what it does not serve)."""
+        return getattr(self.clib_float32, pattern.format("_newton" if self._solver_number(solver_type) == XLINEAR_SOLVERS["L2R_L2LOSS_SVC_PRIMAL"] else ""))
+
     def xlinear_single_layer_train(self, pX, pY, pC, pM, pR, threshold=0.1, max_nonzeros_per_label=None, solver_type="L2R_L2LOSS_SVC_DUAL", Cp=1.0, Cn=1.0,
                                    max_iter=1000, eps=0.1, bias=1.0, threads=-1, verbose=0, **kwargs):
         """One layer's weights trained on the device (K13; ``xrl_single_layer_train_{csr,drm}_f32``, the reference's argument list under this
@@ -762,12 +774,11 @@ class corelib(object):
         ScipyCsrF32 or ScipyDrmF32 view, ``pY`` / ``pC`` / ``pM`` / ``pR`` are ScipyCscF32 views (``pC`` / ``pM`` None: pure multi-label,
         ``pR`` None: every positive costs 1).  Returns the float32 ``csc_matrix`` W, (features + (bias > 0)) x labels.  The weights are
         the reference's at threads = 1 bit for bit; ``threads`` and ``verbose`` are accepted and ignored."""
-        clib = self.clib_float32
         coo_alloc = ScipyCoordinateSparseAllocator(dtype=np.float32)
         if isinstance(pX, ScipyCsrF32):
-            train = clib.xrl_single_layer_train_csr_f32
+            train = self._train_symbol(solver_type, "xrl_single_layer_train{}_csr_f32")
         elif isinstance(pX, ScipyDrmF32):
-            train = clib.xrl_single_layer_train_drm_f32
+            train = self._train_symbol(solver_type, "xrl_single_layer_train{}_drm_f32")
         else:
             raise NotImplementedError("type(pX) = {} not implemented".format(type(pX)))
         train(byref(pX), byref(pY), byref(pC) if pC is not None else None, byref(pM) if pM is not None else None, byref(pR) if pR is not None else None,
@@ -780,7 +791,7 @@ class corelib(object):
                            Cn=1.0, max_iter=1000, eps=0.1, bias=1.0, stream=None):
         """A new matrix handle with W^T (labels x (features + (bias > 0)), CSR = the CSC of W) trained from matrix handles: X and the
         TRANSPOSES of Y, C, M and R (free it with :meth:`smat_free`)."""
-        h = self.clib_float32.xrl_train_layer_device(c_void_p(X), c_void_p(Yt), c_void_p(Ct or 0), c_void_p(Mt or 0), c_void_p(Rt or 0), threshold,
+        h = self._train_symbol(solver_type, "xrl_train_layer{}_device")(c_void_p(X), c_void_p(Yt), c_void_p(Ct or 0), c_void_p(Mt or 0), c_void_p(Rt or 0), threshold,
                                                      0 if max_nonzeros_per_label is None else max_nonzeros_per_label, self._solver_number(solver_type), Cp, Cn,
                                                      max_iter, eps, bias, c_void_p(stream or 0))
         self._check()
@@ -792,6 +803,16 @@ class corelib(object):
         self.clib_float32.xrl_debug_train_counters(out, len(self.TRAIN_COUNTERS))
         self._check()
         return dict(zip(self.TRAIN_COUNTERS, (int(v) for v in out)))
+
+    NEWTON_COUNTERS = ("jobs", "batches", "slots", "stride", "newton_iters", "cg_iters", "hv_calls", "halvings", "end_before_first", "end_gradient",
+                       "end_linesearch", "end_actred", "end_cap", "cg_dhd", "cg_q", "cg_positive", "cg_cap", "lane_rows", "wave_rows", "nonfinite_jobs")
+
+    def newton_counters(self):
+        """What the last primal training (L2R_L2LOSS_SVC_PRIMAL, K16) of this process ran (``xrl_debug_newton_counters``), by name."""
+        out = (c_uint64 * len(self.NEWTON_COUNTERS))()
+        self.clib_float32.xrl_debug_newton_counters(out, len(self.NEWTON_COUNTERS))
+        self._check()
+        return dict(zip(self.NEWTON_COUNTERS, (int(v) for v in out)))
 
     # ------------------------------------------------------------------ matching matrices and a trained layer's prediction in HBM (K14)
     MATCH_FORMS = ("lds_rows", "big_rows", "read", "written", "last_bound")

@@ -15,30 +15,21 @@
 //                    jobs run again from their start.  Loop bounds: a sweep visits at most `active` coordinates (each visit advances or
 //                    shrinks), sweeps <= max_iter, a draw's rejections end with the table.
 //   k13_label_counts, k13_place   the jobs' staged rows -> W^T by label
+// A job's set-up and emission are xrl_train_job.h's, shared with K16 (xrl_newton.hip); train_layer below drives a layer for either solver.
 #include <cstdlib>
 #include <random>
 
 #include "xrl_device.h"
 #include "xrl_devprim.h"
+#include "xrl_newton.h"
 #include "xrl_train.h"
+#include "xrl_train_job.h"
 
 namespace xrl {
 
 namespace {
 
 constexpr const char* kWhat = "K13";
-
-enum : uint32_t { kBadPtr = 1u, kBadId = 2u, kUnsorted = 4u, kDiffers = 8u, kTwice = 16u, kStageFull = 32u };
-
-// What a wavefront's lanes wrote to HBM is visible to its other lanes afterwards.  A slot is touched by ONE wavefront, so workgroup scope
-// is all that is needed: the workgroup's CU has one vector L1, write-through, which its own stores and atomics keep coherent, so the fence
-// is a drain of the memory counters and no cache is invalidated.  Nothing in a slot is ever read by another workgroup during the launch.
-__device__ __forceinline__ void wave_sync_hbm() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ uint32_t first_lane(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
 __global__ void __launch_bounds__(256)
 k13_check(const uint64_t* __restrict__ ptr, const uint32_t* __restrict__ idx, uint32_t rows, uint64_t nnz, uint32_t bound, int sorted, uint32_t* __restrict__ flags) {
@@ -85,20 +76,13 @@ k13_sizes(const uint64_t* __restrict__ m_ptr, const uint32_t* __restrict__ m_idx
     if (lane == 0) { atomicMax(&out[isy ? 2 : 0], (unsigned long long)(e - b)); atomicMax(&out[isy ? 3 : 1], sum); }
 }
 
-struct K13Args {
-    const uint64_t* x_ptr; const uint32_t* x_idx; const float* x_val; uint64_t x_nnz; uint32_t N, d;
-    const uint64_t* y_ptr; const uint32_t* y_idx; const float* r_val; uint64_t y_nnz;
-    const uint64_t* c_ptr; const uint32_t* c_idx; uint32_t K;            // null: job j is label j, its instances are all rows
-    const uint64_t* m_ptr; const uint32_t* m_idx; uint64_t m_nnz;
-    double threshold, Cp, Cn, eps, bias;
-    uint32_t max_nz; int l2loss; uint64_t max_iter;
-    // a slot's scratch, [slot * its size]
-    uint32_t* index; uint32_t index_cap; float* alpha; float* qd; float* cost; signed char* ysg; float* w; uint32_t* touched; uint32_t dw;
+struct K13Args : TrainJobArgs {
+    int l2loss; uint64_t max_iter;
+    // the rest of a slot's scratch, [slot * its size]
+    float* alpha; float* qd;
     const uint32_t* table; uint64_t table_n;
-    const uint32_t* job_list; uint32_t job0, n_jobs; uint32_t* next;      // job_list null: jobs job0 .. job0 + n_jobs - 1
-    uint32_t* st_idx; float* st_val; uint32_t stride;                     // staging row of job j: (j - job0) * stride
-    unsigned long long* cnt; uint32_t* job_label;                         // per job
-    uint32_t* redo; uint32_t* n_redo; uint32_t* flags;
+    const uint32_t* job_list; uint32_t n_jobs; uint32_t* next;            // job_list null: jobs job0 .. job0 + n_jobs - 1
+    uint32_t* redo; uint32_t* n_redo;
     unsigned long long* counters;                                          // iters, shrinks, reactivations, max_iter stops, clipped, lane rows, wave rows
 };
 
@@ -150,11 +134,6 @@ __device__ bool k13_shuffle(uint32_t* a, uint32_t n, const uint32_t* __restrict_
     return true;
 }
 
-__device__ __forceinline__ uint32_t k13_word_mask(uint32_t wd, uint32_t d) { return (uint64_t)wd * 32u + 32u <= d ? 0xFFFFFFFFu : (1u << (d - wd * 32u)) - 1u; }
-
-// (|w| bits, lower feature first) of a staged entry: the larger key is kept first
-__device__ __forceinline__ uint64_t k13_key(float v, uint32_t f) { return ((uint64_t)(__float_as_uint(v) & 0x7FFFFFFFu) << 32) | (0xFFFFFFFFu - f); }
-
 __device__ void k13_job(const K13Args& a, uint32_t job, uint32_t slot, uint32_t lane, unsigned long long (&ctr)[7]) {
     uint32_t* index = a.index + (uint64_t)slot * a.index_cap;
     float* alpha = a.alpha + (uint64_t)slot * a.N;
@@ -170,61 +149,7 @@ __device__ void k13_job(const K13Args& a, uint32_t job, uint32_t slot, uint32_t 
     uint32_t label = job, code = 0;
     if (a.c_ptr) { label = a.c_idx[job]; code = segment_of(a.c_ptr, a.K, (uint64_t)job); }
 
-    // ---- the instances (init_worker): M's column as stored, then Y's positives that are not among them, as stored
-    uint32_t n = 0;
-    if (a.m_ptr) {
-        uint64_t mb, me;
-        row_span(a.m_ptr, code, a.m_nnz, mb, me);
-        for (uint64_t x = mb + lane; x < me; x += 64u) {
-            const uint32_t i = a.m_idx[x];
-            index[x - mb] = i; cost[i] = 1.0f; ysg[i] = -1;
-        }
-        n = (uint32_t)(me - mb);
-    } else {
-        for (uint32_t i = lane; i < a.N; i += 64u) { index[i] = i; cost[i] = 1.0f; ysg[i] = -1; }
-        n = a.N;
-    }
-    wave_sync_hbm();
-    {
-        uint64_t yb, ye;
-        row_span(a.y_ptr, label, a.y_nnz, yb, ye);
-        // The reference walks the column one stored position after the other: a position appends its row when the row's cost is 0 at
-        // that moment ("not listed"), then stores its own cost.  A row id stored twice is therefore appended once per occurrence that
-        // meets a cost of 0, and the LAST stored cost stays.  Here 64 positions go per step, and the order is made the stored order BY
-        // LANE NUMBER, never by the order in which the memory serves the lanes: every lane finds the nearest lower lane with its row id
-        // (the cost that lane carries is the cost this lane meets) and whether a higher lane has it too; a lane without a lower twin
-        // reads cost[i] as the steps before left it, and only the lane without a higher twin stores -- one writer per address, no atomic.
-        for (uint64_t x0 = yb; x0 < ye; x0 += 64u) {
-            const uint64_t x = x0 + lane;
-            const bool have = x < ye;
-            const uint32_t cnt = (uint32_t)min((uint64_t)64u, ye - x0);
-            uint32_t i = 0;
-            float c = 1.0f;
-            if (have) { i = a.y_idx[x]; if (a.r_val) c = a.r_val[x]; }
-            bool lower = false, higher = false;
-            float met = 0.0f;
-            for (uint32_t l = 0; l < cnt; ++l) {                       // l is uniform: two lane reads a turn, at most 64 turns
-                const uint32_t il = (uint32_t)__builtin_amdgcn_readlane((int)i, (int)l);
-                const float cl = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(c), (int)l));
-                if (have && il == i) {
-                    if (l < lane) { lower = true; met = cl; }
-                    else if (l > lane) higher = true;
-                }
-            }
-            if (have && !lower) met = cost[i];
-            const bool fresh = have && met == 0.0f;                    // +0 and -0 both read as "not listed"; a NaN does not
-            wave_sync_hbm();                                           // a first occurrence has read cost[i] before the last one stores to it
-            if (have && !higher) cost[i] = c;
-            if (have) ysg[i] = 1;
-            const unsigned long long m = __ballot(fresh);
-            const uint32_t at = n + lanes_below(m);
-            if (fresh && at < a.index_cap) index[at] = i;
-            n += (uint32_t)__popcll(m);
-            wave_sync_hbm();                                           // the next step's lanes read the costs this step stored
-        }
-        if (n > a.index_cap) n = a.index_cap;                          // (cannot happen: a stored position of Y appends at most once, and the cap counts them all)
-    }
-    wave_sync_hbm();
+    const uint32_t n = train_job_setup(a, label, code, lane, index, cost, ysg);
 
     // ---- QD = diag + x'x + bias^2, alpha = 0, and the features the job can touch.  The reference also adds y * alpha = (+-)0 times the row
     //      to w and (+-)0 * bias to b here (:444-446): nothing for a finite entry (w is +0), a NaN where X stores an inf or a NaN and, with an
@@ -360,85 +285,11 @@ __device__ void k13_job(const K13Args& a, uint32_t job, uint32_t slot, uint32_t 
     if (!converged && !table_end) ++ctr[3];
     wave_sync_hbm();                                                   // lane 0's last swaps of index, and the last axpy, before every lane reads them below
 
-    // ---- emission (SVMJob::solve): the entries with |w| >= threshold by ascending feature into the job's staging row; w and the bitmap
-    //      go back to zero on the way.  A job the table failed stages nothing.
-    const uint32_t bj = job - a.job0;
-    uint32_t* sidx = a.st_idx + (uint64_t)bj * a.stride;
-    float* sval = a.st_val + (uint64_t)bj * a.stride;
-    const bool every = a.threshold <= 0.0;
-    uint32_t c = 0, full = 0;
-    for (uint32_t w0 = 0; w0 < a.dw; w0 += 64u) {
-        const uint32_t wd = w0 + lane;
-        uint32_t bits = 0;
-        if (wd < a.dw) {
-            bits = touched[wd];
-            if (bits) touched[wd] = 0u;
-            if (every) bits = k13_word_mask(wd, a.d);
-        }
-        uint32_t mine = 0;
-        if (!table_end)
-            for (uint32_t bb = bits; bb; bb &= bb - 1u) mine += (double)fabsf(w[wd * 32u + (uint32_t)__builtin_ctz(bb)]) >= a.threshold ? 1u : 0u;
-        uint32_t incl = mine;
-        for (int dlt = 1; dlt < 64; dlt <<= 1) { const uint32_t t = __shfl_up(incl, dlt, 64); if ((int)lane >= dlt) incl += t; }
-        uint32_t at = c + incl - mine;
-        for (uint32_t bb = bits; bb; bb &= bb - 1u) {
-            const uint32_t f = wd * 32u + (uint32_t)__builtin_ctz(bb);
-            const float v = w[f];
-            w[f] = 0.0f;
-            if (!table_end && (double)fabsf(v) >= a.threshold) {
-                if (at < a.stride) { sidx[at] = f; sval[at] = v; } else full = 1;
-                ++at;
-            }
-        }
-        c += (uint32_t)__shfl(incl, 63);
-    }
-    // the instances' marks
-    for (uint32_t s = lane; s < n; s += 64u) cost[index[s]] = 0.0f;
-    wave_sync_hbm();
-    if (__ballot(full)) { if (lane == 0) atomicOr(a.flags, (uint32_t)kStageFull); c = min(c, a.stride); }
-    if (table_end) {                                                   // the job runs again from its start: this attempt is not counted
+    // ---- emission; a job the table failed stages nothing and runs again from its start: this attempt is not counted
+    if (!train_job_emit(a, job, label, lane, w, touched, cost, index, n, bw, table_end)) {
         if (lane == 0) a.redo[atomicAdd(a.n_redo, 1u)] = job;
         for (int k = 0; k < 7; ++k) ctr[k] = before[k];
-        return;
     }
-    bool push_bias = a.bias > 0 && (double)fabsf(bw) >= a.threshold;
-    if (a.max_nz && c >= a.max_nz) {
-        // the max_nz largest |w|, ties to the lower feature: T = the max_nz-th largest key, by bisection over the key's value (64 steps)
-        unsigned long long lo = 0, hi = ~0ull;
-        while (lo < hi) {
-            const unsigned long long mid = lo + ((hi - lo) >> 1) + 1ull;
-            uint32_t ge = 0;
-            for (uint32_t x0 = 0; x0 < c; x0 += 64u) {
-                const uint32_t x = x0 + lane;
-                ge += (uint32_t)__popcll(__ballot(x < c && k13_key(sval[x], sidx[x]) >= mid));
-            }
-            if (ge >= a.max_nz) lo = mid; else hi = mid - 1ull;
-        }
-        // the bias competes with the least kept feature (:764-773)
-        const float least = __uint_as_float((uint32_t)(lo >> 32));
-        bool drop_least = false;
-        if (a.bias > 0) {
-            if (fabsf(bw) > least) drop_least = true; else push_bias = false;
-        }
-        uint32_t kept = 0;
-        for (uint32_t x0 = 0; x0 < c; x0 += 64u) {
-            const uint32_t x = x0 + lane;
-            uint32_t f = 0;
-            float v = 0.0f;
-            bool keep = false;
-            if (x < c) { f = sidx[x]; v = sval[x]; const unsigned long long k = k13_key(v, f); keep = drop_least ? k > lo : k >= lo; }
-            const unsigned long long m = __ballot(keep);
-            if (keep) { sidx[kept + lanes_below(m)] = f; sval[kept + lanes_below(m)] = v; }
-            kept += (uint32_t)__popcll(m);
-            wave_sync_hbm();
-        }
-        c = kept;
-    }
-    if (push_bias) {
-        if (c < a.stride) { if (lane == 0) { sidx[c] = a.d; sval[c] = bw; } ++c; }
-        else if (lane == 0) atomicOr(a.flags, (uint32_t)kStageFull);
-    }
-    if (lane == 0) { a.cnt[job] = c; a.job_label[job] = label; }
 }
 
 __global__ void __launch_bounds__(64) k13_solve(K13Args a) {
@@ -515,10 +366,14 @@ void check_train_params(const std::string& what, const TrainParams& p) {
         fail(what + "unknown solver_type " + std::to_string(p.solver_type) + " (1 = L2R_L2LOSS_SVC_DUAL, 3 = L2R_L1LOSS_SVC_DUAL)");
 }
 
-void train_layer_device(const char* what_c, const QueriesDev& X, const QueriesDev& Yt, const float* r_val, const QueriesDev* Ct, const QueriesDev* Mt,
-                        const TrainParams& p, hipStream_t s, DevCsr& out, TrainCounters& T) {
+namespace {
+
+// One layer, whichever solver: the checks, the sizes of a slot and of a staging row, the batches under the scratch budget, and W^T by
+// label.  newton (NT) or the dual coordinate descent (T); the caller has refused the solvers its entry point does not serve.
+void train_layer(const char* what_c, const QueriesDev& X, const QueriesDev& Yt, const float* r_val, const QueriesDev* Ct, const QueriesDev* Mt,
+                 const TrainParams& p, hipStream_t s, DevCsr& out, TrainCounters& T, NewtonCounters* NT) {
     const std::string what = std::string(what_c) + ": ";
-    check_train_params(what, p);
+    const bool newton = NT != nullptr;
     const bool coded = Ct && Mt;
     const uint32_t N = X.rows, d = X.cols, L = Yt.rows;
     const uint64_t jobs64 = coded ? Ct->nnz : L;
@@ -529,6 +384,7 @@ void train_layer_device(const char* what_c, const QueriesDev& X, const QueriesDe
     flags.reserve(4);
     XRL_HIP(hipMemsetAsync(flags.p, 0, 4, s));
     check_csr(what, "X", X, d, true, flags, s);
+    if (newton) newton_check_finite(what, X, s);
     check_csr(what, "Y", Yt, N, false, flags, s);
     if (coded) {
         check_csr(what, "C", *Ct, L, false, flags, s);
@@ -569,14 +425,15 @@ void train_layer_device(const char* what_c, const QueriesDev& X, const QueriesDe
     const uint32_t dw = (d + 31u) / 32u;
 
     const uint64_t budget = env_u64("XRL_TRAIN_SCRATCH_BYTES", kTrainScratchBytes);
-    const uint64_t slot_bytes = (uint64_t)index_cap * 4 + (uint64_t)N * 13 + (uint64_t)d * 4 + (uint64_t)dw * 4;
+    const uint64_t slot_bytes = (uint64_t)index_cap * 4 + (uint64_t)N * (newton ? 5 : 13) + (uint64_t)d * 4 + (uint64_t)dw * 4 + (newton ? newton_slot_bytes(N, d, index_cap) : 0);
     const uint32_t slots = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({budget / std::max<uint64_t>(slot_bytes, 1), kTrainMaxSlots, std::max<uint32_t>(jobs, 1)}));
     const uint32_t batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(budget / (stride64 * 8), std::max<uint32_t>(jobs, 1)));
     T.jobs = jobs; T.slots = slots; T.stride = stride;
 
     DevBuf b_index, b_alpha, b_qd, b_cost, b_y, b_w, b_touched, b_next, b_stidx, b_stval, b_cnt, b_label, b_redo, b_ctr, b_table, b_list;
     b_index.reserve((size_t)slots * index_cap * 4);
-    b_alpha.reserve((size_t)slots * N * 4); b_qd.reserve((size_t)slots * N * 4); b_cost.reserve((size_t)slots * N * 4); b_y.reserve((size_t)slots * N);
+    if (!newton) { b_alpha.reserve((size_t)slots * N * 4); b_qd.reserve((size_t)slots * N * 4); }
+    b_cost.reserve((size_t)slots * N * 4); b_y.reserve((size_t)slots * N);
     b_w.reserve((size_t)slots * d * 4); b_touched.reserve((size_t)slots * dw * 4);
     // a slot is clean between jobs: cost, w and the bitmap are zero (every job leaves them so)
     if (N) XRL_HIP(hipMemsetAsync(b_cost.p, 0, (size_t)slots * N * 4, s));
@@ -601,7 +458,9 @@ void train_layer_device(const char* what_c, const QueriesDev& X, const QueriesDe
         b_table.release();
         b_table.upload(table);
     };
-    grow_table(env_u64("XRL_TRAIN_RANDOM_WORDS", kTrainRandomWords));
+    if (!newton) grow_table(env_u64("XRL_TRAIN_RANDOM_WORDS", kTrainRandomWords));
+    NewtonScratch nsc;
+    if (newton) newton_reserve(nsc, slots, N, d, index_cap, s);
 
     K13Args a{};
     a.x_ptr = X.row_ptr; a.x_idx = X.col_idx; a.x_val = X.val; a.x_nnz = X.nnz; a.N = N; a.d = d;
@@ -621,7 +480,18 @@ void train_layer_device(const char* what_c, const QueriesDev& X, const QueriesDe
         const uint32_t nb = std::min(batch, jobs - j0);
         ++T.batches;
         a.job0 = j0; a.n_jobs = nb; a.job_list = nullptr;
-        for (uint32_t ext = 0;; ++ext) {
+        if (newton) {
+            XRL_HIP(hipMemsetAsync(b_next.p, 0, 8, s));
+            newton_launch(a, nsc, nb, a.next, std::min(slots, nb), s);
+            const uint32_t bad = newton_bad_job(nsc, s);
+            if (bad != 0xFFFFFFFFu) {
+                uint32_t label = 0;
+                XRL_HIP(hipMemcpy(&label, a.job_label + bad, 4, hipMemcpyDeviceToHost));
+                fail(what + "label " + std::to_string(label) + ": the conjugate-gradient steps met a step length that is not finite; the reference then puts NaNs into " +
+                     "features that no instance of the label stores, which this form does not cover");
+            }
+        }
+        for (uint32_t ext = 0; !newton; ++ext) {
             a.table = b_table.as<uint32_t>(); a.table_n = table.size();
             XRL_HIP(hipMemsetAsync(b_next.p, 0, 8, s));
             hipLaunchKernelGGL(k13_solve, dim3(std::min(slots, a.n_jobs)), dim3(64), 0, s, a);
@@ -664,10 +534,30 @@ void train_layer_device(const char* what_c, const QueriesDev& X, const QueriesDe
                            c.val.as<float>(), out.ptr.as<unsigned long long>(), out.idx.as<uint32_t>(), out.val.as<float>());
         XRL_LAUNCH_CHECK();
     }
+    if (newton) {
+        NT->jobs = T.jobs; NT->batches = T.batches; NT->slots = T.slots; NT->stride = T.stride;
+        newton_read_counters(nsc, *NT, s);
+        return;
+    }
     uint64_t ctr[7];
     XRL_HIP(hipMemcpyAsync(ctr, b_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s));
     XRL_HIP(hipStreamSynchronize(s));
     T.iters = ctr[0]; T.shrinks = ctr[1]; T.reactivations = ctr[2]; T.max_iter_stops = ctr[3]; T.clipped = ctr[4]; T.lane_rows = ctr[5]; T.wave_rows = ctr[6];
+}
+
+}  // namespace
+
+void train_layer_device(const char* what, const QueriesDev& X, const QueriesDev& Yt, const float* r_val, const QueriesDev* Ct, const QueriesDev* Mt,
+                        const TrainParams& p, hipStream_t s, DevCsr& out, TrainCounters& T) {
+    check_train_params(std::string(what) + ": ", p);
+    train_layer(what, X, Yt, r_val, Ct, Mt, p, s, out, T, nullptr);
+}
+
+void train_layer_newton_device(const char* what, const QueriesDev& X, const QueriesDev& Yt, const float* r_val, const QueriesDev* Ct, const QueriesDev* Mt,
+                               const TrainParams& p, hipStream_t s, DevCsr& out, NewtonCounters& NT) {
+    check_newton_params(std::string(what) + ": ", p);
+    TrainCounters T;
+    train_layer(what, X, Yt, r_val, Ct, Mt, p, s, out, T, &NT);
 }
 
 }  // namespace xrl

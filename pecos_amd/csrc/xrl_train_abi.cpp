@@ -7,6 +7,7 @@
 #include <mutex>
 
 #include "xrl_abi_common.h"
+#include "xrl_newton.h"
 #include "xrl_train.h"
 
 using namespace xrl;
@@ -16,7 +17,15 @@ namespace {
 std::mutex g_counters_mu;
 TrainCounters g_counters;                                  // of the last training of this process
 
+NewtonCounters g_newton_counters;                          // of the last primal training of this process
+
 void keep_counters(const TrainCounters& c) { std::lock_guard<std::mutex> g(g_counters_mu); g_counters = c; }
+void keep_counters(const NewtonCounters& c) { std::lock_guard<std::mutex> g(g_counters_mu); g_newton_counters = c; }
+
+// the solvers an entry point serves: K13's two dual ones, or (newton) K16's primal one
+void check_solver(const std::string& what, const TrainParams& p, bool newton) {
+    if (newton) check_newton_params(what, p); else check_train_params(what, p);
+}
 
 TrainParams make_params(double threshold, uint32_t max_nonzeros, int solver_type, double Cp, double Cn, uint64_t max_iter, double eps, double bias) {
     TrainParams p;
@@ -50,9 +59,9 @@ void upload_pattern(const ScipyCscF32* m, Uploaded& u) {
 
 // upload, train, copy back as the reference's COO at threads = 1: jobs code-major in C's stored order
 void train_host(const char* what_c, const ScipyCsrF32& X, const ScipyCscF32* pY, const ScipyCscF32* pC, const ScipyCscF32* pM, const ScipyCscF32* pR,
-                py_coo_allocator_t coo_alloc, const TrainParams& p) {
+                py_coo_allocator_t coo_alloc, const TrainParams& p, bool newton) {
     const std::string what = std::string(what_c) + ": ";
-    check_train_params(what, p);
+    check_solver(what, p, newton);
     if (!pY) fail(what + "null Y");
     if (!coo_alloc) fail(what + "null allocator");
     check_csc(what, "Y", pY);
@@ -90,9 +99,15 @@ void train_host(const char* what_c, const ScipyCsrF32& X, const ScipyCscF32* pY,
     if (coded) { upload_pattern(pC, c); upload_pattern(pM, m); }
     if (pR) r.upload_raw(pR->val, (size_t)pY->col_ptr[pY->cols] * 4);
     DevCsr wt;
-    TrainCounters counters;
-    train_layer_device(what_c, x.v, y.v, pR ? r.as<float>() : nullptr, coded ? &c.v : nullptr, coded ? &m.v : nullptr, p, nullptr, wt, counters);
-    keep_counters(counters);
+    if (newton) {
+        NewtonCounters counters;
+        train_layer_newton_device(what_c, x.v, y.v, pR ? r.as<float>() : nullptr, coded ? &c.v : nullptr, coded ? &m.v : nullptr, p, nullptr, wt, counters);
+        keep_counters(counters);
+    } else {
+        TrainCounters counters;
+        train_layer_device(what_c, x.v, y.v, pR ? r.as<float>() : nullptr, coded ? &c.v : nullptr, coded ? &m.v : nullptr, p, nullptr, wt, counters);
+        keep_counters(counters);
+    }
     const uint32_t L = pY->cols;
     std::vector<uint64_t> ptr((size_t)L + 1);
     std::vector<uint32_t> idx((size_t)wt.nnz);
@@ -111,51 +126,39 @@ void train_host(const char* what_c, const ScipyCsrF32& X, const ScipyCscF32* pY,
     else for (uint32_t l = 0; l < L; ++l) emit(l);
 }
 
-}  // namespace
-
-extern "C" {
-
-void xrl_single_layer_train_csr_f32(const ScipyCsrF32* pX, const ScipyCscF32* pY, const ScipyCscF32* pC, const ScipyCscF32* pM, const ScipyCscF32* pR,
-                                          py_coo_allocator_t coo_alloc, double threshold, uint32_t max_nonzeros_per_label, int solver_type, double Cp, double Cn,
-                                          size_t max_iter, double eps, double bias, int threads) {
+void train_csr(const char* what, bool newton, const ScipyCsrF32* pX, const ScipyCscF32* pY, const ScipyCscF32* pC, const ScipyCscF32* pM, const ScipyCscF32* pR,
+               py_coo_allocator_t coo_alloc, const TrainParams& p) {
     guarded([&] {
-        const char* what = "xrl_single_layer_train_csr_f32";
-        (void)threads;
         if (!pX || !pX->row_ptr) fail(std::string(what) + ": null X");
         if (pX->rows >= (1u << 31)) fail(std::string(what) + ": 2^31 rows or more");          // (before the row pointer's end is read)
         if (pX->rows && pX->row_ptr[pX->rows] && (!pX->col_idx || !pX->val)) fail(std::string(what) + ": null indices or values (X)");
-        train_host(what, *pX, pY, pC, pM, pR, coo_alloc, make_params(threshold, max_nonzeros_per_label, solver_type, Cp, Cn, max_iter, eps, bias));
+        train_host(what, *pX, pY, pC, pM, pR, coo_alloc, p, newton);
     });
 }
 
 // the same computation on rows that store every entry, zeros included: the reference's dense rows are walked over all cols
-void xrl_single_layer_train_drm_f32(const ScipyDrmF32* pX, const ScipyCscF32* pY, const ScipyCscF32* pC, const ScipyCscF32* pM, const ScipyCscF32* pR,
-                                          py_coo_allocator_t coo_alloc, double threshold, uint32_t max_nonzeros_per_label, int solver_type, double Cp, double Cn,
-                                          size_t max_iter, double eps, double bias, int threads) {
+void train_drm(const char* what, bool newton, const ScipyDrmF32* pX, const ScipyCscF32* pY, const ScipyCscF32* pC, const ScipyCscF32* pM, const ScipyCscF32* pR,
+               py_coo_allocator_t coo_alloc, const TrainParams& p) {
     guarded([&] {
-        const char* what = "xrl_single_layer_train_drm_f32";
-        (void)threads;
         if (!pX) fail(std::string(what) + ": null X");
         if (pX->rows >= (1u << 31)) fail(std::string(what) + ": 2^31 rows or more");
         if (pX->rows && pX->cols && !pX->val) fail(std::string(what) + ": null values (X)");
-        const TrainParams p = make_params(threshold, max_nonzeros_per_label, solver_type, Cp, Cn, max_iter, eps, bias);
-        check_train_params(std::string(what) + ": ", p);                                            // refusals come before the index arrays are built
+        check_solver(std::string(what) + ": ", p, newton);                                          // refusals come before the index arrays are built
         const uint64_t n = (uint64_t)pX->rows * pX->cols;
         std::vector<uint64_t> ptr((size_t)pX->rows + 1);
         std::vector<uint32_t> idx((size_t)n);
         for (uint64_t r = 0; r <= pX->rows; ++r) ptr[r] = r * pX->cols;
         for (uint64_t i = 0; i < n; ++i) idx[i] = (uint32_t)(i % pX->cols);
         const ScipyCsrF32 csr{pX->rows, pX->cols, ptr.data(), idx.data(), pX->val};
-        train_host(what, csr, pY, pC, pM, pR, coo_alloc, p);
+        train_host(what, csr, pY, pC, pM, pR, coo_alloc, p, newton);
     });
 }
 
-void* xrl_train_layer_device(void* X, void* Yt, void* Ct_or_null, void* Mt_or_null, void* Rt_or_null, double threshold, uint32_t max_nonzeros_per_label,
-                             int solver_type, double Cp, double Cn, uint64_t max_iter, double eps, double bias, void* hip_stream) {
+void* train_resident(const char* what_c, bool newton, void* X, void* Yt, void* Ct_or_null, void* Mt_or_null, void* Rt_or_null, const TrainParams& p, void* hip_stream) {
     return guarded_value((void*)nullptr, [&]() -> void* {
-        const std::string what = "xrl_train_layer_device: ";
-        const TrainParams p = make_params(threshold, max_nonzeros_per_label, solver_type, Cp, Cn, max_iter, eps, bias);
-        check_train_params(what, p);
+        const std::string what = std::string(what_c) + ": ";
+        const double bias = p.bias;
+        check_solver(what, p, newton);
         const Queries& x = csr_handle(what, X, "X");
         const Queries& y = csr_handle(what, Yt, "Yt");
         if (Ct_or_null && !Mt_or_null) fail(what + "Ct comes without Mt");
@@ -176,13 +179,76 @@ void* xrl_train_layer_device(void* X, void* Yt, void* Ct_or_null, void* Mt_or_nu
         require_gpu();
         use_device(x.device);
         hipStream_t s = static_cast<hipStream_t>(hip_stream);
-        if (r) same_pattern_device("xrl_train_layer_device", y.dev, r->dev, s);
+        if (r) same_pattern_device(what_c, y.dev, r->dev, s);
         auto out = std::make_unique<Queries>();
-        TrainCounters counters;
-        train_layer_device("xrl_train_layer_device", x.dev, y.dev, r ? r->dev.val : nullptr, c ? &c->dev : nullptr, m ? &m->dev : nullptr, p, s, out->own, counters);
-        keep_counters(counters);
+        if (newton) {
+            NewtonCounters counters;
+            train_layer_newton_device(what_c, x.dev, y.dev, r ? r->dev.val : nullptr, c ? &c->dev : nullptr, m ? &m->dev : nullptr, p, s, out->own, counters);
+            keep_counters(counters);
+        } else {
+            TrainCounters counters;
+            train_layer_device(what_c, x.dev, y.dev, r ? r->dev.val : nullptr, c ? &c->dev : nullptr, m ? &m->dev : nullptr, p, s, out->own, counters);
+            keep_counters(counters);
+        }
         set_own_csr(*out, x.device, y.dev.rows, x.dev.cols + (bias > 0 ? 1u : 0u));
         return out.release();
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+void xrl_single_layer_train_csr_f32(const ScipyCsrF32* pX, const ScipyCscF32* pY, const ScipyCscF32* pC, const ScipyCscF32* pM, const ScipyCscF32* pR,
+                                          py_coo_allocator_t coo_alloc, double threshold, uint32_t max_nonzeros_per_label, int solver_type, double Cp, double Cn,
+                                          size_t max_iter, double eps, double bias, int threads) {
+    (void)threads;
+    train_csr("xrl_single_layer_train_csr_f32", false, pX, pY, pC, pM, pR, coo_alloc, make_params(threshold, max_nonzeros_per_label, solver_type, Cp, Cn, max_iter, eps, bias));
+}
+
+void xrl_single_layer_train_drm_f32(const ScipyDrmF32* pX, const ScipyCscF32* pY, const ScipyCscF32* pC, const ScipyCscF32* pM, const ScipyCscF32* pR,
+                                          py_coo_allocator_t coo_alloc, double threshold, uint32_t max_nonzeros_per_label, int solver_type, double Cp, double Cn,
+                                          size_t max_iter, double eps, double bias, int threads) {
+    (void)threads;
+    train_drm("xrl_single_layer_train_drm_f32", false, pX, pY, pC, pM, pR, coo_alloc, make_params(threshold, max_nonzeros_per_label, solver_type, Cp, Cn, max_iter, eps, bias));
+}
+
+void* xrl_train_layer_device(void* X, void* Yt, void* Ct_or_null, void* Mt_or_null, void* Rt_or_null, double threshold, uint32_t max_nonzeros_per_label,
+                             int solver_type, double Cp, double Cn, uint64_t max_iter, double eps, double bias, void* hip_stream) {
+    return train_resident("xrl_train_layer_device", false, X, Yt, Ct_or_null, Mt_or_null, Rt_or_null,
+                          make_params(threshold, max_nonzeros_per_label, solver_type, Cp, Cn, max_iter, eps, bias), hip_stream);
+}
+
+// ---- the primal L2-loss SVC (K16): the same argument lists, solver_type == 2
+void xrl_single_layer_train_newton_csr_f32(const ScipyCsrF32* pX, const ScipyCscF32* pY, const ScipyCscF32* pC, const ScipyCscF32* pM, const ScipyCscF32* pR,
+                                           py_coo_allocator_t coo_alloc, double threshold, uint32_t max_nonzeros_per_label, int solver_type, double Cp, double Cn,
+                                           size_t max_iter, double eps, double bias, int threads) {
+    (void)threads;
+    train_csr("xrl_single_layer_train_newton_csr_f32", true, pX, pY, pC, pM, pR, coo_alloc, make_params(threshold, max_nonzeros_per_label, solver_type, Cp, Cn, max_iter, eps, bias));
+}
+
+void xrl_single_layer_train_newton_drm_f32(const ScipyDrmF32* pX, const ScipyCscF32* pY, const ScipyCscF32* pC, const ScipyCscF32* pM, const ScipyCscF32* pR,
+                                           py_coo_allocator_t coo_alloc, double threshold, uint32_t max_nonzeros_per_label, int solver_type, double Cp, double Cn,
+                                           size_t max_iter, double eps, double bias, int threads) {
+    (void)threads;
+    train_drm("xrl_single_layer_train_newton_drm_f32", true, pX, pY, pC, pM, pR, coo_alloc, make_params(threshold, max_nonzeros_per_label, solver_type, Cp, Cn, max_iter, eps, bias));
+}
+
+void* xrl_train_layer_newton_device(void* X, void* Yt, void* Ct_or_null, void* Mt_or_null, void* Rt_or_null, double threshold, uint32_t max_nonzeros_per_label,
+                                    int solver_type, double Cp, double Cn, uint64_t max_iter, double eps, double bias, void* hip_stream) {
+    return train_resident("xrl_train_layer_newton_device", true, X, Yt, Ct_or_null, Mt_or_null, Rt_or_null,
+                          make_params(threshold, max_nonzeros_per_label, solver_type, Cp, Cn, max_iter, eps, bias), hip_stream);
+}
+
+int xrl_debug_newton_counters(uint64_t* out, uint32_t n) {
+    return guarded_value(-1, [&] {
+        if (!out) fail("xrl_debug_newton_counters: null argument");
+        std::lock_guard<std::mutex> g(g_counters_mu);
+        const NewtonCounters& c = g_newton_counters;
+        const uint64_t v[kNewtonCounterCount] = {c.jobs, c.batches, c.slots, c.stride, c.newton_iters, c.cg_iters, c.hv_calls, c.halvings, c.end_before_first, c.end_gradient,
+                                                 c.end_linesearch, c.end_actred, c.end_cap, c.cg_dhd, c.cg_q, c.cg_positive, c.cg_cap, c.lane_rows, c.wave_rows, c.nonfinite_jobs};
+        for (uint32_t i = 0; i < n && i < kNewtonCounterCount; ++i) out[i] = v[i];
+        return 0;
     });
 }
 

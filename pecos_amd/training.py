@@ -108,8 +108,12 @@ def _per_layer(value, depth, name):
 
 
 def _params_dict(p):
+    """A layer's solver keywords.  The primal solver stops at ``newton_eps`` (0.01 unless given), not at ``eps`` (pecos/xmc/base.py:868-870)."""
     d = p if isinstance(p, dict) else p.to_dict()
-    return {k: d[k] for k in TRAIN_KEYS if k in d}
+    out = {k: d[k] for k in TRAIN_KEYS if k in d}
+    if clib._solver_number(out.get("solver_type", 1)) == 2:
+        out["eps"] = d.get("newton_eps", 0.01)
+    return out
 
 
 def _label_chain(y, cs, stream):

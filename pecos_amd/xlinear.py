@@ -116,8 +116,11 @@ class MLModel:
 
     @classmethod
     def train(cls, prob, train_params=None, pred_params=None, **kwargs):
-        """One layer trained on the device (K13; ``clib.xlinear_single_layer_train``) from an :class:`MLProblem`."""
+        """One layer trained on the device (K13, or K16 for ``L2R_L2LOSS_SVC_PRIMAL``, which stops at ``newton_eps`` as in
+        pecos/xmc/base.py:868-870; ``clib.xlinear_single_layer_train``) from an :class:`MLProblem`."""
         train_params = cls.TrainParams.from_dict(kwargs if train_params is None else train_params)
+        if train_params.solver_type == "L2R_L2LOSS_SVC_PRIMAL":
+            train_params.eps = train_params.newton_eps
         pred_params = cls.PredParams.from_dict(pred_params)
         pred_params.override_with_kwargs(kwargs.get("pred_kwargs", None))
         if pred_params.post_processor not in VALID_POST_PROCESSORS:
