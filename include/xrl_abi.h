@@ -781,6 +781,52 @@ int xrl_single_layer_predict_device(void* X, void* Wt, void* Ct_or_null, const u
 int xrl_smat_check_relevance_device(void* Y, void* R, uint64_t* status, void* hip_stream);
 int xrl_debug_match_forms(uint64_t* out, uint32_t n);
 
+/* HNSW search on the device (K17, csrc/xrl_hnsw.hip): a folder saved by the reference's HNSW.save (c_model/: config.json + index.mmap_store) is
+ * loaded into HBM and queried there; ids, order and distance bits are those of c_ann_hnsw_predict_{csr,drm}_{ip,l2}_f32 on the same folder
+ * (sparse: on any x86 host; dense: the reference's avx512f clone -- DESIGN.md section 9 states both distance rules, the traversal and the
+ * libstdc++ heaps).  Search only: nothing here trains or saves a graph, and the product-quantised index is not loaded.  The names are this
+ * library's own on purpose: a handle of one library is never a handle of the other.
+ *   xrl_hnsw_load(model_dir, device, &handle)   reads config.json (hnsw_t selects csr/drm x ip/l2; any other string is refused with "Inconsistent
+ *       HNSW_T: ...", a version other than v2.0 with "Unable to load memory-mapped file with version = ..."), reads index.mmap_store, checks
+ *       on the host and refuses by name: a neighbour id >= num_node, a degree above maxM0 / maxM, a node listed twice in one neighbourhood,
+ *       init_node >= num_node, a sparse item whose ids are not strictly ascending or reach feat_dim, a non-finite stored value, records that
+ *       leave the buffer.  Then splits the interleaved node records into arrays and uploads them.  0 / -1 + xrl_last_error.
+ *   xrl_hnsw_check_folder(model_dir, out, n)    the same reading and the same refusals without a GPU; out as xrl_hnsw_info.  0 / -1.
+ *   xrl_hnsw_info(handle, out, n)               out[0..n), n <= 10 <- {num_node, feat_dim, maxM, maxM0, efC, max_level, init_node, data type
+ *       (0 csr, 1 drm), metric (0 ip, 1 l2), bytes held in HBM}.
+ *   xrl_hnsw_searchers_create(handle, n)        device scratch for n wavefronts (at most 2048): visited marks and cand heaps.  A predict without
+ *       searchers allocates per call and sizes the slots itself.  NULL + xrl_last_error on failure.  A searchers handle serves the index it was
+ *       made for and ONE call at a time (a call regrows and reuses its work buffers until its last synchronisation): a call that finds the
+ *       handle in use, on another thread or stream, is refused by name and never queued; make one handle per concurrent caller.
+ *   xrl_hnsw_predict_{csr,drm}_f32              the reference's argument list on host arrays; `threads` is accepted and ignored.  Uploads,
+ *       searches, copies back; row r writes its found entries (at most topk) at r * topk and leaves the rest of the row untouched.
+ *   xrl_hnsw_predict_device                     the resident form.  Queries: dense [rows, cols] at d_val with row_stride >= cols (d_row_ptr NULL), or
+ *       a CSR triple d_row_ptr u64 [rows + 1], d_col_idx u32, d_val f32 with nnz stored entries.  Outputs d_idx / d_dist with row stride
+ *       out_stride >= topk, and d_count [rows].  Runs on hip_stream; one synchronisation at the end, for the overflow flag of the cand heaps
+ *       (a query that overflows its slot's cand capacity -- 4096 entries, XRL_HNSW_CAND_CAP in the environment for tests -- runs again with
+ *       an entry per node).
+ *   Refused by name, outputs unchanged: a null handle, the wrong data type for the handle, cols != feat_dim, topk == 0, efS == 0, out_stride <
+ *   topk, row_stride < cols, null outputs, searchers of another index or in use, and by a check kernel row pointers that are not ascending within nnz, a query row with unsorted, repeated or out-of-range ids or a non-finite query value.  0 / -1.
+ *   xrl_debug_hnsw_counters(out, n, reset)      FOR TESTS: out[0..n), n <= 8 <- {distance evaluations, pops, admissions, upper-level passes, the
+ *       largest cand size, queries rerun, queries served by the LDS form of the topk heap, by the HBM form}, summed since the last reset.
+ *       The first five count the attempt of a query that produced its answer: what an abandoned attempt (a cand heap that overflowed) did
+ *       before it stopped is NOT counted, so they equal the reference's traversal and understate the work done by what the reruns repeat.
+ *   xrl_debug_hnsw_caps(out, n)                 out[0..n), n <= 4 <- {CAP (largest efS' = max(efS, topk) of the LDS form), the default cand capacity,
+ *       the largest degree staged in LDS, the largest slot count} */
+int xrl_hnsw_load(const char* model_dir, int device, void** handle);
+int xrl_hnsw_check_folder(const char* model_dir, uint64_t* out, uint32_t n);
+void xrl_hnsw_destruct(void* handle);
+int xrl_hnsw_info(void* handle, uint64_t* out, uint32_t n);
+void* xrl_hnsw_searchers_create(void* handle, uint32_t num_searcher);
+void xrl_hnsw_searchers_destruct(void* searchers);
+int xrl_hnsw_predict_csr_f32(void* handle, const ScipyCsrF32* pX, uint32_t* ret_idx, float* ret_val, uint32_t efS, uint32_t topk, int32_t threads, void* searchers);
+int xrl_hnsw_predict_drm_f32(void* handle, const ScipyDrmF32* pX, uint32_t* ret_idx, float* ret_val, uint32_t efS, uint32_t topk, int32_t threads, void* searchers);
+int xrl_hnsw_predict_device(void* handle, uint32_t rows, uint32_t cols, const float* d_val, uint64_t row_stride, const uint64_t* d_row_ptr, const uint32_t* d_col_idx,
+                            uint64_t nnz, uint32_t efS, uint32_t topk, uint32_t* d_idx, float* d_dist, uint32_t* d_count, uint64_t out_stride, void* searchers,
+                            void* hip_stream);
+int xrl_debug_hnsw_counters(uint64_t* out, uint32_t n, int reset);
+int xrl_debug_hnsw_caps(uint64_t* out, uint32_t n);
+
 /* predict_on_selected_outputs on the device (K7 + K4): score a given set of labels per query row through the tree, with labels, plan and
  * scores resident in HBM.  The labels arrive in the fixed-stride form xrl_predict_device writes and xrl_ensemble_device reads: row r is
  * d_sel_idx[r*sel_stride ..], d_sel_cnt[r] entries long (NULL = sel_stride each; a count above the stride is read as the stride), in any

@@ -357,6 +357,18 @@ class corelib(object):
                                                     c_void_p, c_void_p, c_uint32, c_void_p]),
         "xrl_smat_check_relevance_device": (c_int, [c_void_p, c_void_p, POINTER(c_uint64), c_void_p]),
         "xrl_debug_match_forms": (c_int, [POINTER(c_uint64), c_uint32]),
+        "xrl_hnsw_load": (c_int, [c_char_p, c_int, POINTER(c_void_p)]),
+        "xrl_hnsw_check_folder": (c_int, [c_char_p, POINTER(c_uint64), c_uint32]),
+        "xrl_hnsw_destruct": (None, [c_void_p]),
+        "xrl_hnsw_info": (c_int, [c_void_p, POINTER(c_uint64), c_uint32]),
+        "xrl_hnsw_searchers_create": (c_void_p, [c_void_p, c_uint32]),
+        "xrl_hnsw_searchers_destruct": (None, [c_void_p]),
+        "xrl_hnsw_predict_csr_f32": (c_int, [c_void_p, POINTER(ScipyCsrF32), POINTER(c_uint32), POINTER(c_float), c_uint32, c_uint32, c_int32, c_void_p]),
+        "xrl_hnsw_predict_drm_f32": (c_int, [c_void_p, POINTER(ScipyDrmF32), POINTER(c_uint32), POINTER(c_float), c_uint32, c_uint32, c_int32, c_void_p]),
+        "xrl_hnsw_predict_device": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, c_void_p,
+                                            c_void_p, c_uint64, c_void_p, c_void_p]),
+        "xrl_debug_hnsw_counters": (c_int, [POINTER(c_uint64), c_uint32, c_int]),
+        "xrl_debug_hnsw_caps": (c_int, [POINTER(c_uint64), c_uint32]),
         "xrl_inspect_model": (c_int, [c_char_p, POINTER(c_uint64), c_uint32]),
         "xrl_model_create": (c_void_p, [c_uint32, c_void_p, c_void_p, POINTER(c_float), POINTER(c_uint32), POINTER(c_char_p)]),
         "xrl_queries_upload_csr": (c_void_p, [c_void_p, POINTER(ScipyCsrF32)]),
@@ -850,6 +862,69 @@ class corelib(object):
         self.clib_float32.xrl_debug_match_forms(out, len(self.MATCH_FORMS))
         self._check()
         return dict(zip(self.MATCH_FORMS, (int(v) for v in out)))
+
+    # ------------------------------------------------------------------ HNSW search (K17)
+    HNSW_INFO = ("num_node", "feat_dim", "maxM", "maxM0", "efC", "max_level", "init_node", "data_type", "metric_type", "device_bytes")
+    HNSW_COUNTERS = ("dist", "pops", "admissions", "passes", "max_cand", "rerun", "lds_queries", "hbm_queries")
+
+    def _hnsw_info(self, out):
+        d = dict(zip(self.HNSW_INFO, (int(v) for v in out)))
+        d["data_type"], d["metric_type"] = ("csr", "drm")[d["data_type"]], ("ip", "l2")[d["metric_type"]]
+        return d
+
+    def hnsw_load(self, c_model_dir, device=0):
+        """``xrl_hnsw_load``: the reference's ``c_model`` folder (config.json + index.mmap_store) into HBM -> handle."""
+        h = c_void_p()
+        self.clib_float32.xrl_hnsw_load(self._cstr(c_model_dir), int(device), ctypes.byref(h))
+        self._check()
+        return h
+
+    def hnsw_check_folder(self, c_model_dir):
+        """The loader's reading and refusals without a GPU (``xrl_hnsw_check_folder``) -> the info dictionary."""
+        out = (c_uint64 * 10)()
+        self.clib_float32.xrl_hnsw_check_folder(self._cstr(c_model_dir), out, 10)
+        self._check()
+        return self._hnsw_info(out)
+
+    def hnsw_destruct(self, h):
+        self.clib_float32.xrl_hnsw_destruct(h)
+
+    def hnsw_info(self, h):
+        out = (c_uint64 * 10)()
+        self.clib_float32.xrl_hnsw_info(h, out, 10)
+        self._check()
+        return self._hnsw_info(out)
+
+    def hnsw_searchers_create(self, h, num_searcher):
+        p = self.clib_float32.xrl_hnsw_searchers_create(h, int(num_searcher))
+        self._check()
+        return c_void_p(p)
+
+    def hnsw_searchers_destruct(self, p):
+        self.clib_float32.xrl_hnsw_searchers_destruct(p)
+
+    def hnsw_predict(self, h, pX, data_type, indices, distances, efS, topk, threads=1, searchers=None):
+        """``xrl_hnsw_predict_{csr,drm}_f32`` into the caller's ``indices`` uint32 / ``distances`` float32 arrays of rows * topk entries."""
+        fn = getattr(self.clib_float32, "xrl_hnsw_predict_%s_f32" % data_type)
+        fn(h, ctypes.byref(pX), indices.ctypes.data_as(POINTER(c_uint32)), distances.ctypes.data_as(POINTER(c_float)), efS, topk, threads, searchers)
+        self._check()
+
+    def hnsw_predict_device(self, h, rows, cols, val_addr, row_stride, row_ptr_addr, col_idx_addr, nnz, efS, topk, d_idx, d_dist, d_count, out_stride,
+                            searchers=None, stream=None):
+        self.clib_float32.xrl_hnsw_predict_device(h, rows, cols, c_void_p(val_addr or 0), row_stride, c_void_p(row_ptr_addr or 0), c_void_p(col_idx_addr or 0), nnz,
+                                                  efS, topk, c_void_p(d_idx), c_void_p(d_dist), c_void_p(d_count), out_stride, searchers, c_void_p(stream or 0))
+        self._check()
+
+    def debug_hnsw_counters(self, reset=False):
+        """Counters of K17 since the last reset (``xrl_debug_hnsw_counters``), by name."""
+        out = (c_uint64 * len(self.HNSW_COUNTERS))()
+        self.clib_float32.xrl_debug_hnsw_counters(out, len(self.HNSW_COUNTERS), 1 if reset else 0)
+        return dict(zip(self.HNSW_COUNTERS, (int(v) for v in out)))
+
+    def debug_hnsw_caps(self):
+        out = (c_uint64 * 4)()
+        self.clib_float32.xrl_debug_hnsw_caps(out, 4)
+        return dict(zip(("CAP", "cand_cap", "lds_degree", "max_slots"), (int(v) for v in out)))
 
     # ------------------------------------------------------------------ label clustering (K11)
     def run_clustering(self, py_feat_mat, train_params, codes=None):
