@@ -800,6 +800,10 @@ int xrl_debug_match_forms(uint64_t* out, uint32_t n);
  *       handle in use, on another thread or stream, is refused by name and never queued; make one handle per concurrent caller.
  *   xrl_hnsw_predict_{csr,drm}_f32              the reference's argument list on host arrays; `threads` is accepted and ignored.  Uploads,
  *       searches, copies back; row r writes its found entries (at most topk) at r * topk and leaves the rest of the row untouched.
+ *       Finite inputs are served whatever their distances become: a distance that overflows is +inf or -inf as the reference's, a NaN distance
+ *       (inf + -inf; the inputs are finite, so it is never a caller's NaN) carries the x86 host's default NaN 0xFFC00000, and NaNs sit in a
+ *       row where libstdc++'s heaps leave them under the reference's comparisons, which are all false under a NaN -- among the numbers, not
+ *       after them.  Subnormal distances are kept.  The same holds for xrl_hnsw_predict_device.
  *   xrl_hnsw_predict_device                     the resident form.  Queries: dense [rows, cols] at d_val with row_stride >= cols (d_row_ptr NULL), or
  *       a CSR triple d_row_ptr u64 [rows + 1], d_col_idx u32, d_val f32 with nnz stored entries.  Outputs d_idx / d_dist with row stride
  *       out_stride >= topk, and d_count [rows].  Runs on hip_stream; one synchronisation at the end, for the overflow flag of the cand heaps

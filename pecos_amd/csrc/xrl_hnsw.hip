@@ -76,6 +76,12 @@ template <bool MAX> __device__ __forceinline__ void heap_pop(float* d, uint32_t*
 }
 
 // ---- distances
+// A NaN distance carries the host's default NaN.  The loader and the check kernels admit finite values only, so no operand of either rule is
+// ever a NaN of the caller's: every NaN is born of an invalid operation on finite or infinite values (inf + -inf), which an x86 host answers
+// with 0xFFC00000 -- sign bit set -- and then carries unchanged through the later additions and the final (float)(1.0 - (double)s) or
+// -2 * dot.  The device's default NaN is 0x7FC00000, and a negated operand flips a NaN's sign, so the bits are set once, at the end.  (K10's
+// host_nan in xrl_spgemm.hip also hands on a caller's NaN payload; there is none to hand on here.)  The comparisons stay the reference's.
+__device__ __forceinline__ float host_default_nan(float d) { return d == d ? d : __uint_as_float(0xFFC00000u); }
 // Dense, the avx512f clone: called by all 64 lanes, the 16 lanes of a group share `node`; every lane of the group returns the distance.
 __device__ __forceinline__ float dense_dist(const HnswDev& g, const float* __restrict__ q, uint32_t node, uint32_t lane) {
     const float* __restrict__ v = g.feat + (uint64_t)node * g.feat_dim;
@@ -104,7 +110,7 @@ __device__ __forceinline__ float dense_dist(const HnswDev& g, const float* __res
         if (g.l2) { const float df = __fsub_rn(x, y); s = __fmaf_rn(df, df, s); }
         else s = __fmaf_rn(x, y, s);
     }
-    return g.l2 ? s : (float)(1.0 - (double)s);
+    return host_default_nan(g.l2 ? s : (float)(1.0 - (double)s));
 }
 
 // Sparse: one lane merges the query's row [qb, qe) with the item's; the products of the matching ids are added one by one in ascending id order.
@@ -119,7 +125,7 @@ __device__ __forceinline__ float sparse_dist(const HnswArgs& a, uint64_t qb, uin
         else if (x < y) ++qb;
         else ++ib;
     }
-    return a.g.l2 ? (float)((double)__fadd_rn(0.0f, 0.0f) - 2.0 * (double)dot) : (float)(1.0 - (double)dot);
+    return host_default_nan(a.g.l2 ? (float)((double)__fadd_rn(0.0f, 0.0f) - 2.0 * (double)dot) : (float)(1.0 - (double)dot));
 }
 
 struct QueryRow { const float* q; uint64_t qb, qe; };

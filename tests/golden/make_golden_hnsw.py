@@ -1,8 +1,11 @@
 """Records tests/golden/hnsw/: four indexes trained by the compiled reference (csr / drm x ip / l2, at most 600 items, M = 8, threads = 1),
 their queries, and the reference's ids and distance bits at (efS, topk) = (1, 1), (20, 10), (10, 20), (50, 50), plus the CPU flags of the
 recording host.  Dense distances depend on the reference's CPU clone: without avx512f the dense fixtures are refused.
+range_edges.npz holds what the reference returns for hnsw_rule.range_edge_cases() -- distances that overflow fp32 and NaNs in the queues --
+as ids and distance bits only (the indexes are written from the generators by the tests); it is recorded on its own and leaves the rest alone.
 
-    python tests/golden/make_golden_hnsw.py        (needs oracle/_ref/libpecos_float32.so)
+    python tests/golden/make_golden_hnsw.py                  (needs oracle/_ref/libpecos_float32.so)
+    python tests/golden/make_golden_hnsw.py range_edges      (range_edges.npz only)
 """
 import json
 import os
@@ -31,6 +34,30 @@ def items_and_queries(kind, seed):
     return X.tocsr().astype(np.float32), hr.sparse_items(24, 300, 12, seed + 100)
 
 
+def record_range_edges():
+    """ids (u8: at most 64 nodes) and distance bits of every case and setting, in the layout of hr.range_edge_blocks; run twice and with 4
+    searchers, and refused if the reference does not repeat itself."""
+    import tempfile
+    cases = hr.range_edge_cases()
+    idx, bits, layout = [], [], []
+    for name, efS, topk, at in hr.range_edge_blocks(cases):
+        ix, Q, _ = cases[name]
+        with tempfile.TemporaryDirectory() as d:
+            hr.write_folder(ix, d)
+            got = hr.run_reference(d, Q, efS, topk)
+            for threads in (1, 4):
+                again = hr.run_reference(d, Q, efS, topk, threads=threads)
+                assert np.array_equal(got[0], again[0]) and np.array_equal(got[1].view(np.uint32), again[1].view(np.uint32)), (name, efS, topk, "the reference is not deterministic")
+        assert got[0].max() < 256
+        idx.append(got[0].astype(np.uint8).reshape(-1))
+        bits.append(got[1].view(np.uint32).reshape(-1))
+        layout.append("%s:%d:%d:%d" % (name, efS, topk, at.stop))
+    path = os.path.join(OUT, "range_edges.npz")
+    np.savez_compressed(path, idx=np.concatenate(idx), bits=np.concatenate(bits), layout=np.array(layout))
+    assert os.path.getsize(path) <= 16 * 1024, os.path.getsize(path)
+    print("recorded", path, os.path.getsize(path), "bytes")
+
+
 def main():
     if not hr.have_reference():
         sys.exit("oracle/_ref/libpecos_float32.so is missing: build it first")
@@ -38,6 +65,8 @@ def main():
     if "avx512f" not in flags:
         sys.exit("this host has no avx512f: the dense fixtures would record another clone of the reference's distance functions; refused")
     os.makedirs(OUT, exist_ok=True)
+    if sys.argv[1:] == ["range_edges"]:
+        return record_range_edges()
     manifest = {"cpu_flags": flags, "settings": [list(s) for s in SETTINGS], "cases": {}}
     for name, (kind, metric, seed) in CASES.items():
         folder = os.path.join(OUT, name)
@@ -68,6 +97,7 @@ def main():
         shutil.rmtree(tmp)
     np.savez_compressed(os.path.join(OUT, "heap_orders.npz"), **orders)
     json.dump(manifest, open(os.path.join(OUT, "manifest.json"), "w"), indent=1, sort_keys=True)
+    record_range_edges()
     print("recorded", OUT)
 
 

@@ -7,6 +7,8 @@ The statement:
   dense    the reference's avx512f clone: 16 fused accumulators, the 4-wide fold, unfused groups of 4, a fused scalar tail
   search   the reference's predict_single / search_level, over libstdc++'s push_heap / pop_heap / sort_heap with a comparator that reads
            the distance only
+  NaN      finite inputs only, so every NaN distance is the x86 host's default NaN 0xFFC00000 (numpy on x86 leaves the same bits); the
+           traversal's comparisons are the reference's as written, all false under a NaN
 """
 import ctypes
 import json
@@ -205,37 +207,58 @@ class Index(object):
         return np.array([sparse_dist(q[0], q[1], *self.row(self.items, n), self.l2) for n in nodes], dtype=F32)
 
 
-def search_one(ix, q, efS, topk, trace=None, dense_mode="rule", ties="dist", upper="pass"):
-    """predict_single for one query -> [(dist, id)] ascending.  trace: a dict of counters to add to.  dense_mode / ties / upper select a
-    WRONG variant (upper="step": move to a better neighbour at once and fetch ITS list, instead of finishing the pass)."""
+HOST_NAN, POSITIVE_NAN = np.uint32(0xFFC00000).view(F32), np.uint32(0x7FC00000).view(F32)
+NAN_VARIANTS = ("upper_not_ge", "break_not_le", "admit_not_ge", "positive_nan")
+# where the statement met a NaN (beside COUNTERS in a trace; the device does not count these): an upper level entered with a NaN curr_dist, an
+# upper-level neighbour at a NaN distance, the break test with a NaN on either side, the admission test decided by `d < ub` (the heap full) with a
+# NaN on either side, pops of the pop-down to topk over a heap that holds a NaN
+NAN_COUNTERS = ("nan_entry", "nan_upper", "nan_break", "nan_admit", "nan_popdown")
+
+
+def search_one(ix, q, efS, topk, trace=None, dense_mode="rule", ties="dist", upper="pass", nan="rule"):
+    """predict_single for one query -> [(dist, id)] ascending.  trace: a dict of counters to add to.  dense_mode / ties / upper / nan select
+    a WRONG variant (upper="step": move to a better neighbour at once and fetch ITS list, instead of finishing the pass; nan: one of
+    NAN_VARIANTS -- a comparison written as the negation of its opposite, which differs exactly under a NaN, or every NaN distance given
+    the positive default NaN 0x7FC00000 instead of the host's 0xFFC00000)."""
     t = trace if trace is not None else {}
-    for k in COUNTERS:
+    for k in COUNTERS + NAN_COUNTERS:
         t.setdefault(k, 0)
+
+    def dist(nodes):
+        ds = np.asarray(ix.dist(q, nodes, dense_mode), dtype=F32)
+        return np.where(np.isnan(ds), POSITIVE_NAN, ds) if nan == "positive_nan" else ds
+
+    lt_upper = (lambda d, c: not (d >= c)) if nan == "upper_not_ge" else (lambda d, c: d < c)
+    gt_break = (lambda c, u: not (c <= u)) if nan == "break_not_le" else (lambda c, u: c > u)
+    lt_admit = (lambda d, u: not (d >= u)) if nan == "admit_not_ge" else (lambda d, u: d < u)
     curr = ix.init_node
-    curr_dist = ix.dist(q, [curr], dense_mode)[0]
+    curr_dist = dist([curr])[0]
     t["dist"] += 1
     for level in range(ix.max_level, 0, -1):
-        changed = True
-        while changed:
-            changed = False
+        t["nan_entry"] += int(np.isnan(curr_dist))
+        changed, left = True, ix.num_node + 1          # (the rule's passes end by themselves: curr_dist falls strictly; a wrong variant's need not)
+        while changed and left:
+            changed, left = False, left - 1
             t["passes"] += 1
             nb = ix.neighbours(curr, level)
-            ds = ix.dist(q, nb, dense_mode) if len(nb) else []
+            ds = dist(nb) if len(nb) else []
             t["dist"] += len(nb)
             for j in range(len(nb)):
-                if ds[j] < curr_dist:
+                t["nan_upper"] += int(np.isnan(ds[j]))
+                if lt_upper(ds[j], curr_dist):
                     curr_dist, curr, changed = ds[j], int(nb[j]), True
                     if upper == "step":
                         break
     ef = max(efS, topk)
     visited = {curr}
-    ub = ix.dist(q, [curr], dense_mode)[0]
+    ub = dist([curr])[0]
     t["dist"] += 1
     top, cand = [(ub, curr)], [(ub, curr)]
     max_cand = 1
     while cand:
         c = cand[0]
-        if c[0] > ub:
+        t["nan_break"] += int(np.isnan(c[0]) or np.isnan(ub))
+        if gt_break(c[0], ub):
             break
         pop_heap(cand, len(cand), "min", ties)
         cand.pop()
@@ -245,10 +268,11 @@ def search_one(ix, q, efS, topk, trace=None, dense_mode="rule", ties="dist", upp
             if int(nb) not in visited:
                 visited.add(int(nb))
                 fresh.append(int(nb))
-        ds = ix.dist(q, fresh, dense_mode) if fresh else []
+        ds = dist(fresh) if fresh else []
         t["dist"] += len(fresh)
         for d, nb in zip(ds, fresh):
-            if len(top) < ef or d < ub:
+            t["nan_admit"] += int(len(top) >= ef and (np.isnan(d) or np.isnan(ub)))
+            if len(top) < ef or lt_admit(d, ub):
                 cand.append((d, nb))
                 push_heap(cand, "min", ties)
                 max_cand = max(max_cand, len(cand))
@@ -261,6 +285,7 @@ def search_one(ix, q, efS, topk, trace=None, dense_mode="rule", ties="dist", upp
                 t["admissions"] += 1
     if topk < efS:
         while len(top) > topk:
+            t["nan_popdown"] += int(any(np.isnan(d) for d, _ in top))
             pop_heap(top, len(top), "max", ties)
             top.pop()
     sort_heap(top, "max", ties)
@@ -274,12 +299,13 @@ def statement(ix, X, efS, topk, fill_idx=0, fill_val=0.0, **variant):
     idx = np.full((rows, topk), fill_idx, dtype=np.uint32)
     dist = np.full((rows, topk), fill_val, dtype=F32)
     count = np.zeros(rows, dtype=np.uint32)
-    trace = {k: 0 for k in COUNTERS}
+    trace = {k: 0 for k in COUNTERS + NAN_COUNTERS}
     if smat.issparse(X):
         X = X.tocsr().astype(F32)
         X.sort_indices()
     for r in range(rows):
-        got = search_one(ix, ix.row(X, r), efS, topk, trace, **variant)
+        with np.errstate(over="ignore", invalid="ignore", under="ignore"):     # overflowing and NaN distances are part of the rule
+            got = search_one(ix, ix.row(X, r), efS, topk, trace, **variant)
         count[r] = len(got)
         for k, (d, i) in enumerate(got):
             idx[r, k], dist[r, k] = i, d
@@ -617,3 +643,153 @@ def heap_lists():
     for n in range(1, 71):
         yield "equal", n, np.full(n, 0.5, dtype=np.float32)
         yield "two", n, rs.choice(np.array([0.25, 0.5], dtype=np.float32), size=n)
+
+
+# ------------------------------------------------------------------------------------------------ cases: distances that leave fp32's range
+# Finite inputs only: the loader and the check kernels refuse the rest.  BIG * 2 and BIG + BIG overflow, BIG - BIG is 0, and inf + -inf is the
+# host's default NaN 0xFFC00000.  Vectors are written as {position: value}; every other position is +0 (dense) or not stored (sparse).
+BIG = F32(3e38)
+FLT_MAX = np.finfo(F32).max
+
+
+def _dense(rows, dim):
+    A = np.zeros((len(rows), dim), dtype=F32)
+    for r, row in enumerate(rows):
+        for k, v in row.items():
+            A[r, k] = v
+    return A
+
+
+def _csr(rows, dim):
+    """Every listed entry is STORED, a zero or a -0.0 too."""
+    ptr = np.cumsum([0] + [len(row) for row in rows])
+    ids = np.array([k for row in rows for k in sorted(row)], dtype=np.int32)
+    vals = np.array([row[k] for row in rows for k in sorted(row)], dtype=F32)
+    return smat.csr_matrix((vals, ids, ptr), shape=(len(rows), dim))
+
+
+def _rows(rows, dim, kind):
+    return _dense(rows, dim) if kind == "drm" else _csr([{k: v for k, v in row.items() if v != 0} for row in rows], dim)
+
+
+def seed_rows():
+    """The nine items and three queries of 20 dimensions every type is run on: under a query of twos item 0 is inf + -inf, items 1 and 2 the
+    two infinities, items 7 and 8 the same in the dense rule's unfused group of 4."""
+    B = BIG
+    items = [{0: B, 1: -B, 4: 1.0}, {0: B, 1: B}, {0: -B, 1: -B}, {k: (1.0, 2.0)[k] if k < 2 else 0.5 for k in range(20)}, {0: -1.0, 1: 0.25},
+             {0: -B, 1: 1.0, 2: B}, {0: 1e-30, 1: 1e-30}, {16: B, 17: -B}, {16: B, 17: B, 18: B, 19: -B}]
+    queries = [{k: 2.0 for k in (0, 1, 2, 16, 17, 18, 19)}, {0: 1e-30, 1: -1e-30}, {k: 1.0 if k else B for k in range(20)}]
+    return items, queries
+
+
+STAGE_POSITIONS = {3: (0, 1, 2),                     # the fused tail alone
+                   4: (0, 1, 3),                     # one unfused group
+                   16: (0, 1, 4, 8, 12),             # one fused block: lanes that meet in the fold's first, second and last addition
+                   23: (0, 4, 16, 17, 20, 22),       # 16 + 4 + 3: a fused lane, its fold partner, two lanes of the unfused group, two tail elements
+                   39: (0, 16, 32, 36)}              # 32 + 4 + 3: positions 0 and 16 share accumulator lane 0
+
+
+def stage_rows(ln):
+    """Dense vectors of length ln with BIG and -BIG (and BIG and BIG) at every pair of STAGE_POSITIONS, in both orders: the overflow and the
+    inf + -inf land in one accumulator lane, across lanes in the fold, in an unfused group, in the tail.  Then sums that reach FLT_MAX
+    exactly, pass it by a quarter and by half an ulp (the tie rounds to even: the overflow), zeros, -0.0 and values whose squares are
+    subnormal.  At 39 also 36 powers of two whose squares are the 24 bits of FLT_MAX, every partial sum exact in any order, then with
+    2^51 and 2^52 in the fused tail (a quarter ulp more, and the overflow).  Queries: twos, ones, +-BIG at the positions, 1e-20 at both
+    ends (dense l2 distances of 1e-40 .. 4e-40), zeros."""
+    P = STAGE_POSITIONS[ln]
+    a, b = 0, ln - 1
+    items = []
+    for i in P:
+        for j in P:
+            if i != j:
+                items.append({i: BIG, j: -BIG})
+            if i < j:
+                items.append({i: BIG, j: BIG})
+    items += [{a: 2.0 ** 127, b: 2.0 ** 127 - 2.0 ** 104}, {a: FLT_MAX, b: 2.0 ** 102}, {a: FLT_MAX, b: 2.0 ** 103},
+              {}, {a: -0.0, b: 1e-20}, {a: 1e-20, b: -1e-20}, {a: 1.0, b: -0.0}]
+    if ln == 39:
+        bits = [2.0 ** (e // 2) for e in range(127, 103, -1) for _ in range(1 + e % 2)]         # an odd exponent is two equal squares
+        assert len(bits) == 36 and sum(x * x for x in bits) == float(FLT_MAX)
+        items += [dict(enumerate(bits)), dict(enumerate(bits + [2.0 ** 51])), dict(enumerate(bits + [0.0, 2.0 ** 52]))]
+    queries = [{k: 2.0 for k in range(ln)}, {k: 1.0 for k in range(ln)}, {p: (BIG if n % 2 == 0 else -BIG) for n, p in enumerate(P)},
+               {a: 1e-20, b: 1e-20}, {}]
+    return items, queries
+
+
+def sparse_dot_rows():
+    """Sparse rows of 40 columns: the chain 0 + inf + -inf, both infinities from products and from the addition, FLT_MAX reached exactly (l2:
+    -2 * FLT_MAX overflows in the final rounding from fp64), the tie at FLT_MAX + half an ulp, products and sums that are subnormal
+    (l2 shows -2e-40; ip hides them behind 1 -), stored zeros and stored -0.0 that match an id on either side, and an empty row."""
+    B = BIG
+    items = [{0: B, 1: -B}, {0: -B, 1: B, 2: 1.0}, {0: B, 1: B}, {0: -B, 1: -B}, {0: 2.0 ** 127, 5: 2.0 ** 127 - 2.0 ** 104}, {0: FLT_MAX, 5: 2.0 ** 103},
+             {0: FLT_MAX, 5: 2.0 ** 102}, {3: 1e-20}, {3: 1e-20, 7: 1e-20}, {3: 1e-25}, {3: -1e-20, 7: 1e-20}, {0: 0.0, 1: 2.0, 2: -0.0}, {0: -0.0}, {2: 0.0, 3: 0.0},
+             {1: 0.5, 39: B}, {}, {0: 1.0, 1: 1.0, 2: 1.0, 3: 1.0, 5: 1.0, 7: 1.0, 39: 1.0}]
+    queries = [{0: 2.0, 1: 2.0, 2: 2.0}, {0: 1.0, 1: 1.0, 5: 1.0}, {3: 1e-20, 7: 1e-20}, {0: 0.0, 1: 1.0, 2: B, 3: -0.0}, {0: 2.0, 1: -2.0, 39: 2.0}, {},
+               {0: -0.0, 2: -0.0}, {3: -1e-20, 7: -1e-25}]
+    return items, queries
+
+
+# A distance by name, as items of 4 dimensions (one unfused group of the dense rule, a chain of the sparse one).  Under the query (2, 2, 0, 1):
+# ip: "nan" NaN, "lo" -inf, "hi" +inf, a number x the distance 1 - x;  sparse l2 is -2 * dot, so "lo" and "hi" change places;  dense l2 has no
+# NaN (its terms are squares): every named kind is +inf there.  The other queries turn the kinds into each other.
+KIND_ROWS = {"nan": {0: BIG, 1: -BIG}, "nan2": {0: -BIG, 1: BIG}, "lo": {0: BIG, 1: BIG}, "hi": {0: -BIG, 1: -BIG}}
+KIND_QUERIES = [{0: 2.0, 1: 2.0, 3: 1.0}, {0: 2.0, 1: -2.0, 3: 1.0}, {0: 1.0, 1: 1.0, 3: 1.0}, {3: 1.0}]
+
+
+def kind_rows(kinds):
+    return [dict(KIND_ROWS[k]) if k in KIND_ROWS else {3: float(k)} for k in kinds]
+
+
+def range_edge_cases():
+    """{name: (Index, queries, [(efS, topk), ...])}: at most 64 nodes, 8 queries and 40 dimensions each; all four types."""
+    cases = {}
+    types = [(k, m) for k in ("csr", "drm") for m in ("ip", "l2")]
+    items, queries = seed_rows()
+    for kind, metric in types:
+        for init in (0, 3):
+            ix = Index(_rows(items, 20, kind), full_graph(9), init_node=init, metric=metric)
+            cases["seed_%s_%s_init%d" % (kind, metric, init)] = (ix, _rows(queries, 20, kind), [(9, 9)])
+    for ln in sorted(STAGE_POSITIONS):
+        items, queries = stage_rows(ln)
+        for metric in ("ip", "l2"):
+            ix = Index(_dense(items, ln), full_graph(len(items)), metric=metric)
+            cases["stages_%s_len%d" % (metric, ln)] = (ix, _dense(queries, ln), [(len(items), len(items))])
+    items, queries = sparse_dot_rows()
+    for metric in ("ip", "l2"):
+        ix = Index(_csr(items, 40), full_graph(len(items)), metric=metric)
+        cases["sparse_dot_%s" % metric] = (ix, _csr(queries, 40), [(len(items), len(items))])
+    # NaN in the traversal: two upper levels, the entry point a NaN (init 0) or finite among NaN neighbours (init 4); efS below, at and above the
+    # node count, topk below efS (the pop-down runs over a heap that holds NaNs) and above it
+    rs = np.random.RandomState(17)
+    kinds = [str(k) for k in rs.choice(["nan", "nan2", "nan", "lo", "hi", "0.25", "0.5", "-1.0", "3.0"], size=24)]
+    kinds[0], kinds[4], kinds[8], kinds[2] = "nan", "0.75", "nan2", "-2.0"
+    l0, l1, levels, _ = random_graph(24, 4, 18, levels=2, maxM=3)
+    for kind, metric in (("csr", "ip"), ("drm", "ip"), ("csr", "l2")):
+        for init in (0, 4):
+            ix = Index(_rows(kind_rows(kinds), 4, kind), l0, l1, maxM=3, max_level=levels, init_node=init, metric=metric)
+            cases["nan_walk_%s_%s_init%d" % (kind, metric, init)] = (ix, _rows(KIND_QUERIES, 4, kind), [(4, 4), (24, 24), (12, 5), (3, 8), (30, 24), (1, 1)])
+    # ties: twelve nodes at each infinity, efS below the size of a tie
+    kinds = [str(k) for k in np.random.RandomState(19).permutation(["lo"] * 12 + ["hi"] * 12 + ["0.5", "0.5", "-1.0", "2.0", "0.0", "7.0"])]
+    l0, l1, levels, init = random_graph(30, 5, 20, levels=1)
+    for kind, metric in types:
+        ix = Index(_rows(kind_rows(kinds), 4, kind), l0, l1, max_level=levels, init_node=init, metric=metric)
+        cases["inf_ties_%s_%s" % (kind, metric)] = (ix, _rows(KIND_QUERIES, 4, kind), [(5, 5), (5, 3), (30, 30), (8, 20)])
+    return cases
+
+
+def range_edge_blocks(cases):
+    """The layout of the recording tests/golden/hnsw/range_edges.npz: one block of rows * topk entries per (case by name, setting in order)."""
+    at = 0
+    for name in sorted(cases):
+        ix, Q, settings = cases[name]
+        for efS, topk in settings:
+            yield name, efS, topk, slice(at, at + Q.shape[0] * topk)
+            at += Q.shape[0] * topk
+
+
+def range_edge_recording(path, cases):
+    """{(name, efS, topk): (idx u32 [rows, topk], distance bits u32 [rows, topk])} as the compiled reference returned them on an avx512f host."""
+    rec = np.load(path)
+    blocks = list(range_edge_blocks(cases))
+    assert rec["layout"].tolist() == ["%s:%d:%d:%d" % (n, e, t, s.stop) for n, e, t, s in blocks], "the cases changed: record range_edges.npz again"
+    return {(n, e, t): (rec["idx"][s].astype(np.uint32).reshape(-1, t), rec["bits"][s].reshape(-1, t)) for n, e, t, s in blocks}

@@ -28,6 +28,13 @@ def same(a, b):
     return np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32))
 
 
+def first_difference(got, want):
+    """(row, position, got bits, wanted bits) of the first entry whose bits differ, for the assertion's message."""
+    g, w = got.view(np.uint32), want.view(np.uint32)
+    r, k = np.argwhere(g != w)[0]
+    return int(r), int(k), hex(g[r, k]), hex(w[r, k])
+
+
 def check(folder, ix, Q, efS, topk, m=None, searchers=None, form=None, what=""):
     """One host call against the statement (answer, tails, counters) and the live reference; -> the counters."""
     own = m is None
@@ -40,7 +47,7 @@ def check(folder, ix, Q, efS, topk, m=None, searchers=None, form=None, what=""):
         assert err is None, err
         want = hr.statement(ix, Q, efS, topk, fill_idx=PI, fill_val=PF)
         assert np.array_equal(idx, want[0]), (what, "ids, order or untouched tails differ from the statement")
-        assert np.array_equal(dist.view(np.uint32), want[1].view(np.uint32)), (what, "distance bits differ from the statement")
+        assert np.array_equal(dist.view(np.uint32), want[1].view(np.uint32)), (what, "distance bits differ from the statement", first_difference(dist, want[1]))
         assert {k: c[k] for k in TRACED} == {k: want[3][k] for k in TRACED} or Q.shape[0] == 0, (what, c, want[3])
         cap = hr.caps()["CAP"]
         rows = Q.shape[0]

@@ -1,6 +1,9 @@
 """HNSW search (K17) without a GPU: the numpy statement of the rule against the recording under tests/golden/hnsw/ and against the compiled
 reference when oracle/_ref is there (dense comparisons only where the host has avx512f: the dense rule is that clone's), the wrong
-variants shown to differ, the heap restatement, the folder reader and writer, every refusal that needs no GPU, and the Python surface."""
+variants shown to differ, the heap restatement, the folder reader and writer, every refusal that needs no GPU, and the Python surface.
+The cases of hnsw_rule.range_edge_cases() -- finite inputs whose distances overflow fp32 or are NaN -- agree three ways: statement, live
+reference, the recording golden/hnsw/range_edges.npz; a test shows each case to hold what it is named for, and the comparisons written
+as negations of their opposites (and a positive NaN) are shown to differ."""
 import ctypes
 import json
 import os
@@ -176,6 +179,163 @@ def test_per_pass_upper_level_update_is_the_references(tmp_path):
     ix, Q = per_step_case()
     folder = hr.write_folder(ix, str(tmp_path / "u"))
     assert hr.run_reference(folder, Q, 1, 1)[0][0, 0] == 2
+
+
+# ------------------------------------------------------------------------------------------------ distances that leave fp32's range
+EDGE_CASES = hr.range_edge_cases()
+EDGE_REC = hr.range_edge_recording(os.path.join(GOLDEN, "range_edges.npz"), EDGE_CASES)
+_edge_statements = {}
+
+
+def edge_statement(name, efS, topk):
+    """Computed once per (case, setting) and shared; nothing writes to it."""
+    if (name, efS, topk) not in _edge_statements:
+        ix, Q, _ = EDGE_CASES[name]
+        _edge_statements[(name, efS, topk)] = hr.statement(ix, Q, efS, topk)
+    return _edge_statements[(name, efS, topk)]
+
+
+def test_range_edge_cases_stay_small_and_finite():
+    assert {(ix.data_type, ix.metric) for ix, _, _ in EDGE_CASES.values()} == {(k, m) for k in ("csr", "drm") for m in ("ip", "l2")}
+    for name, (ix, Q, settings) in EDGE_CASES.items():
+        assert ix.num_node <= 64 and Q.shape[0] <= 8 and ix.feat_dim <= 40 and settings, name
+        for A in (ix.items, Q):
+            assert np.isfinite(A.data if smat.issparse(A) else A).all(), name
+
+
+@pytest.mark.parametrize("name", sorted(EDGE_CASES))
+def test_range_edges_statement_matches_the_recording(name):
+    for efS, topk in EDGE_CASES[name][2]:
+        idx, dist, _, _ = edge_statement(name, efS, topk)
+        assert np.array_equal(idx, EDGE_REC[(name, efS, topk)][0]), (name, efS, topk)
+        assert np.array_equal(dist.view(np.uint32), EDGE_REC[(name, efS, topk)][1]), (name, efS, topk)
+
+
+@pytest.mark.parametrize("name", sorted(EDGE_CASES))
+def test_range_edges_live_reference_matches_the_recording(tmp_path, name):
+    ix, Q, settings = EDGE_CASES[name]
+    gate(ix.data_type)
+    folder = hr.write_folder(ix, str(tmp_path / "m"))
+    assert hr.check_folder(folder)[1] is None                       # finite inputs: the loader serves them
+    for efS, topk in settings:
+        for threads in (1, 4):                                       # the reference repeats itself, with 1 and with 4 searchers
+            idx, dist = hr.run_reference(folder, Q, efS, topk, threads=threads)
+            assert np.array_equal(idx, EDGE_REC[(name, efS, topk)][0]) and np.array_equal(dist.view(np.uint32), EDGE_REC[(name, efS, topk)][1]), (name, efS, topk, threads)
+
+
+@pytest.mark.parametrize("name", sorted(n for n in EDGE_CASES if (EDGE_CASES[n][0].num_node,) * 2 in EDGE_CASES[n][2]))
+def test_range_edges_efS_above_the_node_count_admits_every_visited_node(name):
+    """What lets the GPU tests hold the HBM heap form (efS = CAP + 1) against the recording of (num_node, num_node)."""
+    ix, Q, _ = EDGE_CASES[name]
+    n = ix.num_node
+    a, b = edge_statement(name, n, n), hr.statement(ix, Q, hr.caps()["CAP"] + 1, n)
+    assert same(a, b) and {k: a[3][k] for k in hr.COUNTERS[:5]} == {k: b[3][k] for k in hr.COUNTERS[:5]}
+
+
+def bits_of(name):
+    return np.concatenate([edge_statement(name, e, t)[1].view(np.uint32).reshape(-1) for e, t in EDGE_CASES[name][2]])
+
+
+def rows_of(name):
+    for e, t in EDGE_CASES[name][2]:
+        idx, dist, count, _ = edge_statement(name, e, t)
+        for r in range(dist.shape[0]):
+            yield dist[r, :count[r]]
+
+
+def nan_inside(row):
+    """A NaN with a number before it and a number after it: sort_heap leaves NaNs where its comparisons drop them."""
+    k = np.flatnonzero(np.isnan(row))
+    return len(k) > 0 and any((~np.isnan(row[:i])).any() and (~np.isnan(row[i + 1:])).any() for i in k)
+
+
+NAN, PINF, NINF, MAXF = 0xFFC00000, 0x7F800000, 0xFF800000, 0x7F7FFFFF
+
+
+def is_subnormal(bits):
+    return ((bits & 0x7F800000) == 0) & ((bits & 0x007FFFFF) != 0)
+
+
+def test_range_edge_cases_cover_what_they_claim():
+    for name in EDGE_CASES:
+        ix = EDGE_CASES[name][0]
+        b = bits_of(name)
+        nans = b[(b & 0x7FFFFFFF) > 0x7F800000]
+        assert (nans == NAN).all(), (name, "every NaN of the rule is the host's default NaN")
+        if (ix.data_type, ix.metric) == ("drm", "l2"):                # sums of squares: no NaN and no -inf
+            assert PINF in b and NINF not in b and len(nans) == 0, name
+        elif name != "stages_ip_len3":                                # (length 3 is the fused tail alone: both infinities, never a NaN)
+            assert len(nans) and PINF in b and NINF in b, name
+        if name.startswith(("seed", "nan_walk", "sparse_dot", "stages_ip_len23")) and (ix.data_type, ix.metric) != ("drm", "l2"):
+            assert any(nan_inside(row) for row in rows_of(name)), (name, "a NaN strictly inside a sorted row")
+    assert PINF in bits_of("stages_ip_len3") and NINF in bits_of("stages_ip_len3") and not np.isnan(bits_of("stages_ip_len3").view(np.float32)).any()
+    # the issue's row: seed, dense ip, query 0
+    row = edge_statement("seed_drm_ip_init0", 9, 9)[1][0]
+    assert np.array_equal(row.view(np.uint32), np.array([-np.inf, -10, np.nan, np.nan, np.nan, 1, 2.5, np.inf, np.nan], np.float32).view(np.uint32) | (np.isnan(row) * np.uint32(0x80000000)))
+    # FLT_MAX reached exactly and not passed; 1 - FLT_MAX is -FLT_MAX; sparse l2 doubles it past the range
+    assert MAXF in bits_of("stages_l2_len39") and (MAXF | 0x80000000) in bits_of("sparse_dot_ip")
+    assert all((MAXF | 0x80000000) in bits_of("stages_ip_len%d" % ln) for ln in hr.STAGE_POSITIONS)
+    # subnormal outputs: l2 only
+    for name in ["sparse_dot_l2"] + ["stages_l2_len%d" % ln for ln in hr.STAGE_POSITIONS]:
+        assert is_subnormal(bits_of(name)).any(), name
+    assert not is_subnormal(bits_of("sparse_dot_ip")).any()
+    # the vector on which the fused and the unfused reading of the 16-lane loop differ: BIG and -BIG in accumulator lane 0
+    v = hr._dense([{0: hr.BIG, 16: -hr.BIG}], 39)
+    q = np.full(39, 2.0, np.float32)
+    ix = EDGE_CASES["stages_ip_len39"][0]
+    assert any(np.array_equal(v[0].view(np.uint32), it.view(np.uint32)) for it in ix.items) and np.array_equal(EDGE_CASES["stages_ip_len39"][1][0], q)
+    with np.errstate(all="ignore"):
+        assert hr.dense_dist(q, v, False).view(np.uint32)[0] == NINF and hr.dense_dist(q, v, False, "unfused_main").view(np.uint32)[0] == NAN
+    # -0.0 and zeros that are stored
+    sp = EDGE_CASES["sparse_dot_ip"]
+    for A in (sp[0].items, sp[1]):
+        assert (A.data.view(np.uint32) == 0x80000000).any() and (A.data.view(np.uint32) == 0).any()
+    assert (EDGE_CASES["stages_ip_len23"][0].items.view(np.uint32) == 0x80000000).any()
+    # NaN where the traversal decides
+    for name in (n for n in EDGE_CASES if n.startswith("nan_walk")):
+        ix, Q, settings = EDGE_CASES[name]
+        assert ix.max_level >= 1
+        t = {s: edge_statement(name, *s)[3] for s in settings}
+        assert all(tr["nan_upper"] > 0 and (tr["nan_break"] > 0 or s == (1, 1)) for s, tr in t.items()), name
+        assert all((tr["nan_entry"] > 0) == name.endswith("init0") for tr in t.values()), name
+        assert t[(4, 4)]["nan_admit"] > 0 and t[(24, 24)]["nan_admit"] == 0 and t[(12, 5)]["nan_popdown"] > 0, name
+        if name.endswith("init0"):                                    # query 0 enters at a NaN and never moves on the upper levels
+            got = edge_statement(name, 1, 1)
+            assert got[0][0, 0] == 0 and got[1].view(np.uint32)[0, 0] == NAN
+    # ties larger than efS at both infinities
+    for name in (n for n in EDGE_CASES if n.startswith("inf_ties")):
+        ix, Q, _ = EDGE_CASES[name]
+        full = edge_statement(name, 30, 30)[1].view(np.uint32)
+        if (ix.data_type, ix.metric) == ("drm", "l2"):
+            assert ((full == PINF).sum(axis=1) >= 12).any(), name
+        else:
+            assert (((full == PINF).sum(axis=1) == 12) & ((full == NINF).sum(axis=1) == 12)).any(), name
+            assert (edge_statement(name, 5, 5)[1].view(np.uint32) == NINF).all(axis=1).any(), name
+
+
+@pytest.mark.parametrize("variant", hr.NAN_VARIANTS)
+def test_wrong_nan_variants_differ(variant):
+    """The three comparisons written as the negation of their opposites, and NaN distances with the positive default NaN."""
+    differ = [name for name, (ix, Q, settings) in EDGE_CASES.items() if name.startswith(("nan_walk", "seed_csr"))
+              for efS, topk in settings if not same(edge_statement(name, efS, topk), hr.statement(ix, Q, efS, topk, nan=variant))]
+    assert differ, variant
+    if variant != "positive_nan":                                     # a comparison: ids or finite distances move, not only NaN bits
+        name = "nan_walk_csr_ip_init0"
+        ix, Q, _ = EDGE_CASES[name]
+        assert not np.array_equal(edge_statement(name, 4, 4)[0], hr.statement(ix, Q, 4, 4, nan=variant)[0])
+
+
+def test_fma32_at_the_range_edges():
+    """One rounding, also where the sum is infinite and where a product overflows only once it is rounded."""
+    f = np.float32
+    B, M, inf = hr.BIG, hr.FLT_MAX, f(np.inf)
+    with np.errstate(all="ignore"):
+        cases = [((B, f(2), -inf), -inf), ((B, f(2), inf), inf), ((B, f(2), -B), B), ((B, f(2), f(0)), inf), ((-B, f(2), B), -B),
+                 ((f(2.0 ** 52), f(2.0 ** 52), M), inf), ((f(2.0 ** 51), f(2.0 ** 51), M), M), ((f(2.0 ** 64), f(2.0 ** 64), -M), f(2.0 ** 104)),
+                 ((inf, inf, f(1)), inf), ((f(1e-20), f(1e-20), f(0)), f(np.float64(f(1e-20)) ** 2)), ((f(2), f(3), hr.HOST_NAN), hr.HOST_NAN)]
+        for (a, b, c), want in cases:
+            got = hr.fma32(np.array([a]), np.array([b]), np.array([c]))
+            assert got.dtype == np.float32 and got.view(np.uint32)[0] == np.array([want], np.float32).view(np.uint32)[0], (a, b, c, got, want)
 
 
 # ------------------------------------------------------------------------------------------------ the heaps
