@@ -478,6 +478,11 @@ class corelib(object):
             self.clib_float32.xrl_clear_error()
             raise RuntimeError(err.decode("utf-8", "replace"))
 
+    def _checked(self, value):
+        """``value``, the result of a native call, once that call is known to have left no error."""
+        self._check()
+        return value
+
     # ------------------------------------------------------------------ device management (additive)
     def device_count(self):
         return int(self.clib_float32.xrl_device_count())
@@ -1011,9 +1016,7 @@ class corelib(object):
 
     # ---- TF-IDF query producer (pecos/core/base.py:1696-1725, 1820-1862: tfidf_load / tfidf_destruct / tfidf_predict)
     def tfidf_load(self, load_dir):
-        h = self.clib_float32.c_tfidf_load(c_char_p(load_dir.encode("utf-8")))
-        self._check()
-        return h
+        return self._checked(self.clib_float32.c_tfidf_load(c_char_p(load_dir.encode("utf-8"))))
 
     def tfidf_destruct(self, model):
         if self._lib is not None and model:
@@ -1093,9 +1096,7 @@ class corelib(object):
         return pred_alloc.get()
 
     def tfidf_nr_features(self, model):
-        v = int(self.clib_float32.xrl_tfidf_nr_features(c_void_p(model)))
-        self._check()
-        return v
+        return self._checked(int(self.clib_float32.xrl_tfidf_nr_features(c_void_p(model))))
 
     TOKENIZERS = {"host": 0, "device": 1}
 
@@ -1116,22 +1117,16 @@ class corelib(object):
     def tfidf_counts_device(self, model, c_model, text_addr, off_addr, len_addr, nr_doc, status_addr=None, stream=None):
         """Document bytes in HBM (raw device addresses: u8 text, u64 offsets, u64 lengths) -> the term-count CSR as a query handle (K9);
         ``status_addr`` (u32 [nr_doc]) takes the per-document status instead of an error."""
-        h = self.clib_float32.xrl_tfidf_counts_device(c_void_p(model), c_void_p(c_model), c_void_p(text_addr), c_void_p(off_addr), c_void_p(len_addr), nr_doc,
-                                                     c_void_p(status_addr or 0), c_void_p(stream or 0))
-        self._check()
-        return h
+        return self._checked(self.clib_float32.xrl_tfidf_counts_device(c_void_p(model), c_void_p(c_model), c_void_p(text_addr), c_void_p(off_addr), c_void_p(len_addr), nr_doc,
+                                                                       c_void_p(status_addr or 0), c_void_p(stream or 0)))
 
     def tfidf_predict_device_text(self, model, c_model, text_addr, off_addr, len_addr, nr_doc, stream=None):
         """Document bytes in HBM -> tf-idf X on c_model's device (K9 + the weighting tail): a query handle for predict_device."""
-        h = self.clib_float32.xrl_tfidf_predict_device_text(c_void_p(model), c_void_p(c_model), c_void_p(text_addr), c_void_p(off_addr), c_void_p(len_addr), nr_doc,
-                                                           c_void_p(stream or 0))
-        self._check()
-        return h
+        return self._checked(self.clib_float32.xrl_tfidf_predict_device_text(c_void_p(model), c_void_p(c_model), c_void_p(text_addr), c_void_p(off_addr), c_void_p(len_addr), nr_doc,
+                                                                             c_void_p(stream or 0)))
 
     def tfidf_device_bytes(self, model, device):
-        v = int(self.clib_float32.xrl_tfidf_device_bytes(c_void_p(model), int(device)))
-        self._check()
-        return v
+        return self._checked(int(self.clib_float32.xrl_tfidf_device_bytes(c_void_p(model), int(device))))
 
     def tfidf_device_forms(self, model):
         """Debug counters of the device tokenizer since the load: segments served by the LDS form, by the global form, batches, calls."""
@@ -1150,16 +1145,12 @@ class corelib(object):
         config = {} if config is None else config
         params = TfidfVectorizerParam.from_config(config)
         arr, lens, nr_doc = self._corpus_arrays(trn_corpus)
-        h = self.clib_float32.xrl_tfidf_train(arr, lens.ctypes.data_as(POINTER(c_uint64)), nr_doc, byref(params), int(config.get("threads", -1)))
-        self._check()
-        return h
+        return self._checked(self.clib_float32.xrl_tfidf_train(arr, lens.ctypes.data_as(POINTER(c_uint64)), nr_doc, byref(params), int(config.get("threads", -1))))
 
     def tfidf_train_device(self, device, text_addr, off_addr, len_addr, nr_doc, config, stream=None):
         """The resident form: document bytes, offsets and lengths in HBM on ``device`` (raw addresses, as for ``tfidf_counts_device``)."""
         params = TfidfVectorizerParam.from_config(config)
-        h = self.clib_float32.xrl_tfidf_train_device(int(device), c_void_p(text_addr), c_void_p(off_addr), c_void_p(len_addr), nr_doc, byref(params), c_void_p(stream or 0))
-        self._check()
-        return h
+        return self._checked(self.clib_float32.xrl_tfidf_train_device(int(device), c_void_p(text_addr), c_void_p(off_addr), c_void_p(len_addr), nr_doc, byref(params), c_void_p(stream or 0)))
 
     def tfidf_save(self, model, save_dir):
         """The reference's folder layout (``c_tfidf_save``) of a trained or loaded vectorizer handle."""
@@ -1168,10 +1159,8 @@ class corelib(object):
 
     def tfidf_transform_device(self, model, device, text_addr, off_addr, len_addr, nr_doc, status_addr=None, stream=None):
         """Document bytes in HBM -> the weighted X as a matrix handle on ``device`` (K9 + the weighting tail); needs no XR-Linear model."""
-        h = self.clib_float32.xrl_tfidf_transform_device(c_void_p(model), int(device), c_void_p(text_addr), c_void_p(off_addr), c_void_p(len_addr), nr_doc,
-                                                        c_void_p(status_addr or 0), c_void_p(stream or 0))
-        self._check()
-        return h
+        return self._checked(self.clib_float32.xrl_tfidf_transform_device(c_void_p(model), int(device), c_void_p(text_addr), c_void_p(off_addr), c_void_p(len_addr), nr_doc,
+                                                                          c_void_p(status_addr or 0), c_void_p(stream or 0)))
 
     def tfidf_export(self, model, base=0):
         """The content of one base vectorizer: ({token bytes: id}, {tuple of token ids: feature id}, idf float32 [nr_features])."""

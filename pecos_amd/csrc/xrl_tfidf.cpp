@@ -1,4 +1,4 @@
-// Host half of the TF-IDF query producer (see xrl_tfidf.h): model files, tokenizer, n-gram lookup, term counts.
+// Host half of the TF-IDF query producer (see xrl_tfidf.h): model files (load, save, enumeration), tokenizer, n-gram lookup, term counts.
 //
 // Restated from the reference's behaviour (pecos/core/utils/tfidf.hpp), not from its code layout:
 //   Tokenizer::load            :363-386   config.json {"token_type"}, vocab.txt "<n>\n<idx>\t<token>\n..."
@@ -10,6 +10,7 @@
 //                                         ascending ids -- NOTE the predict path does not pad char_wb words with spaces (only the
 //                                         training path's count_ngrams does, :452-487); this mirrors predict
 //   Vectorizer::load / predict :1247-1266, 1405-1430   single folder or meta.json + <i>.base; hstack with column offsets
+//   BaseVectorizer / Vectorizer::save                  the same folders written, byte for byte (behind xrl_tfidf_save)
 #include "xrl_tfidf.h"
 
 #include <algorithm>
@@ -23,6 +24,8 @@
 #include <thread>
 
 #include <sys/mman.h>
+#include <sys/stat.h>
+#include <cerrno>
 
 #include "xrl_io.h"
 
@@ -544,10 +547,113 @@ void TfidfVectorizer::load(const std::string& dir) {
         for (int i = 0; i < nb; ++i) base[(size_t)i].load(dir + "/" + std::to_string(i) + ".base");
     }
     if (norm_p != 1 && norm_p != 2) fail("invalid normalize option, norm_p: [ 1| 2]");
+    finish("tfidf: ");
+}
+
+void TfidfVectorizer::finish(const std::string& who) {
     uint64_t tot = 0;
-    for (const auto& b : base) tot += b.nr_features;
-    if (tot > 0xFFFFFFFFull) fail("tfidf: too many features");
+    idf_all.clear();
+    for (const auto& b : base) { tot += b.nr_features; idf_all.insert(idf_all.end(), b.idf.begin(), b.idf.end()); }
+    if (tot > 0xFFFFFFFFull) fail(who + "too many features");
     nr_features = (uint32_t)tot;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------ save
+void TfidfBase::enumerate(std::vector<std::pair<std::string, int32_t>>& tokens, std::vector<int32_t>& flat, std::vector<uint64_t>& off, std::vector<uint32_t>& ids) const {
+    tokens.clear(); flat.clear(); ids.clear(); off.assign(1, 0);
+    for (size_t i = 0; i < vocab.s.size(); ++i) {
+        const tft::ShortEntry& e = vocab.s[i];
+        if (!e.len) continue;
+        std::string t(e.len, '\0');
+        for (uint32_t j = 0; j < e.len; ++j) t[j] = (char)(uint8_t)(e.key >> (8 * j));
+        tokens.emplace_back(std::move(t), e.idx);
+    }
+    for (size_t i = 0; i < vocab.l.size(); ++i) {
+        const tft::LongEntry& e = vocab.l[i];
+        if (e.len) tokens.emplace_back(vocab.arena.substr(e.off, e.len), e.idx);
+    }
+    const NgramTable& G = features;
+    for (size_t t = 0; t < G.uni.size(); ++t)
+        if (G.uni[t] != NgramTable::kNone) { flat.push_back((int32_t)t); off.push_back(flat.size()); ids.push_back(G.uni[t] - 1u); }
+    const uint64_t field = G.pack_bits >= 64 ? ~0ull : (1ull << G.pack_bits) - 1;
+    for (size_t i = 0; i < G.packed.size(); ++i) {
+        const tft::PackedEntry& e = G.packed[i];
+        if (e.id1 == NgramTable::kNone) continue;
+        for (unsigned sh = 0; sh < 64; sh += G.pack_bits) {
+            const uint64_t f = (e.key >> sh) & field;
+            if (!f) break;
+            flat.push_back((int32_t)(uint32_t)(f - 1));
+        }
+        off.push_back(flat.size()); ids.push_back(e.id1 - 1u);
+    }
+    for (size_t i = 0; i < G.gen.size(); ++i) {
+        const tft::GenEntry& e = G.gen[i];
+        if (e.id1 == NgramTable::kNone) continue;
+        flat.insert(flat.end(), G.arena.begin() + e.off, G.arena.begin() + e.off + e.n);
+        off.push_back(flat.size()); ids.push_back(e.id1 - 1u);
+    }
+}
+
+namespace {
+// (the refusals of saving name the entry point that saves, xrl_tfidf_save)
+void make_dir(const std::string& d) {
+    if (mkdir(d.c_str(), 0777) == -1 && errno != EEXIST) fail("xrl_tfidf_save: Unable to create save folder at " + d);
+}
+std::FILE* open_w(const std::string& f) {
+    std::FILE* fp = std::fopen(f.c_str(), "wb");
+    if (!fp) fail("xrl_tfidf_save: Unable to save to " + f);
+    return fp;
+}
+// a float as nlohmann prints it: the double it converts to, with enough digits to read back exactly, always with a '.' or an exponent
+std::string json_float(float v) {
+    char buf[64];
+    std::snprintf(buf, sizeof(buf), "%.17g", (double)v);
+    std::string s(buf);
+    if (s.find_first_of(".en") == std::string::npos) s += ".0";
+    return s;
+}
+}  // namespace
+
+void TfidfBase::save(const std::string& dir) const {
+    make_dir(dir);
+    make_dir(dir + "/tokenizer");
+    make_dir(dir + "/vectorizer");
+    std::vector<std::pair<std::string, int32_t>> tokens; std::vector<int32_t> flat; std::vector<uint64_t> off; std::vector<uint32_t> ids;
+    enumerate(tokens, flat, off, ids);
+    std::FILE* fp = open_w(dir + "/tokenizer/config.json");
+    std::fprintf(fp, "{\n    \"token_type\": %d\n}", tok_type);
+    std::fclose(fp);
+    fp = open_w(dir + "/tokenizer/vocab.txt");
+    std::fprintf(fp, "%zu\n", tokens.size());
+    for (const auto& t : tokens) { std::fprintf(fp, "%d\t", t.second); std::fwrite(t.first.data(), 1, t.first.size(), fp); std::fputc('\n', fp); }
+    std::fclose(fp);
+    const auto tf = [](bool b) { return b ? "true" : "false"; };
+    fp = open_w(dir + "/vectorizer/config.json");
+    std::fprintf(fp,
+                 "{\n    \"kwargs\": {\n        \"add_one_idf\": %s,\n        \"binary\": %s,\n        \"keep_frequent_feature\": %s,\n        \"max_df_cnt\": %d,\n"
+                 "        \"max_df_ratio\": %s,\n        \"max_feature\": %d,\n        \"max_length\": %d,\n        \"min_df_cnt\": %d,\n        \"min_df_ratio\": %s,\n"
+                 "        \"ngram_range\": [\n            %d,\n            %d\n        ],\n        \"norm_p\": \"%s\",\n        \"smooth_idf\": %s,\n"
+                 "        \"sublinear_tf\": %s,\n        \"use_idf\": %s\n    },\n    \"type\": \"tfidf\"\n}",
+                 tf(add_one_idf), tf(binary), tf(keep_frequent_feature), max_df_cnt, json_float(max_df_ratio).c_str(), max_feature, max_length, min_df_cnt,
+                 json_float(min_df_ratio).c_str(), min_ngram, max_ngram, norm_p == 1 ? "l1" : "l2", tf(smooth_idf), tf(sublinear_tf), tf(use_idf));
+    std::fclose(fp);
+    fp = open_w(dir + "/vectorizer/tfidf-model.txt");
+    std::fprintf(fp, "%zu\n", ids.size());
+    for (size_t f = 0; f < ids.size(); ++f) {
+        const float v = ids[f] < idf.size() ? idf[ids[f]] : 0.0f;
+        std::fprintf(fp, "%d\t%f\t%zu", (int)ids[f], v, (size_t)(off[f + 1] - off[f]));
+        for (uint64_t i = off[f]; i < off[f + 1]; ++i) std::fprintf(fp, i == off[f] ? "\t%d" : " %d", flat[i]);
+        std::fputc('\n', fp);
+    }
+    std::fclose(fp);
+}
+
+void TfidfVectorizer::save(const std::string& dir) const {
+    make_dir(dir);
+    std::FILE* fp = open_w(dir + "/meta.json");
+    std::fprintf(fp, "{\n    \"kwargs\": {\n        \"norm_p\": %d,\n        \"num_base_vect\": %zu\n    },\n    \"type\": \"tfidf\"\n}", norm_p, base.size());
+    std::fclose(fp);
+    for (size_t b = 0; b < base.size(); ++b) base[b].save(dir + "/" + std::to_string(b) + ".base");
 }
 
 // Documents go to the threads in small dynamic chunks (document lengths are far from uniform); every thread appends to its own arrays and

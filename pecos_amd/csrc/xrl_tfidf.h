@@ -149,6 +149,10 @@ struct TfidfBase {
     unsigned sort_shift = 0;                                   // feature id >> sort_shift in [0, 256): the bucket pass of the per-document sort
 
     void load(const std::string& dir);
+    // the folder `load` reads, byte for byte as the reference's BaseVectorizer::save writes it (features in table order)
+    void save(const std::string& dir) const;
+    // what the tables hold, in table order: (token bytes, token index) pairs; the n-grams as token ids (flat, off) with their feature ids
+    void enumerate(std::vector<std::pair<std::string, int32_t>>& tokens, std::vector<int32_t>& flat, std::vector<uint64_t>& off, std::vector<uint32_t>& ids) const;
     // term counts of one document APPENDED to out: ascending feature ids + col_off, counts as floats (tfidf.hpp:775-796); returns how many
     size_t count(const char* doc, size_t len, TfidfScratch& S, uint32_t col_off, TfidfOut& out) const;
 };
@@ -157,8 +161,14 @@ struct TfidfVectorizer {
     std::vector<TfidfBase> base;
     int norm_p = 2;                          // the ensemble's norm (meta.json); == base[0].norm_p for a folder saved from one BaseVectorizer
     uint32_t nr_features = 0;                // sum over the base vectorizers (hstack)
+    std::vector<float> idf_all;              // the base vectorizers' idf side by side (hstack column order)
 
     void load(const std::string& dir);       // Vectorizer::load, tfidf.hpp:1247-1266
+    void save(const std::string& dir) const; // Vectorizer::save: meta.json + <i>.base, whatever the number of base vectorizers
+    // nr_features and idf_all from the filled base vectorizers: the last step of load and of training (`who` starts the refusal)
+    void finish(const std::string& who);
+    // the ensemble's own normalisation runs after the base vectorizers' (Vectorizer::predict, tfidf.hpp:1405-1430) unless it would repeat base 0's
+    bool ensemble_norm_runs() const { return base.size() > 1 || norm_p != base[0].norm_p; }
     // Host half for a corpus: per (document, base vectorizer) SEGMENT the term counts, laid out as the hstacked CSR (document-major,
     // base vectorizers side by side, column ids offset).  seg_ptr has nr_doc * base.size() + 1 entries.
     // The CALLER owns the destination: once the total is known `provide(nnz, col, cnt)` is called (on the calling thread) and must hand back

@@ -1,5 +1,7 @@
 // TF-IDF query producer (libpecos.cpp:398-445): c_tfidf_load / c_tfidf_destruct / c_tfidf_predict with the
-// reference's signatures, and xrl_tfidf_predict_device, which leaves X in HBM for xrl_predict_device.
+// reference's signatures, and the xrl_tfidf_* entry points that leave X in HBM for xrl_predict_device, count on the device (K9) and train
+// there (K15).  Host texts reach X through tfidf_to_device (host counts) or pack_corpus + tfidf_text_to_queries (device counts); text in
+// HBM through tfidf_text_to_queries alone.  The model files, saving included, are xrl_tfidf.cpp's.
 #include <atomic>
 #include <cfloat>
 #include <cmath>
@@ -15,9 +17,6 @@
 #include "xrl_tfidf.h"
 #include "xrl_tfidf_train.h"
 #include "xrl_tokenize.h"
-
-#include <sys/stat.h>
-#include <cerrno>
 
 using namespace xrl;
 
@@ -39,35 +38,65 @@ struct PinnedStage {
     }
 };
 
-// dst <- src on host threads, 1 MiB pieces
-void parallel_copy(void* dst, const void* src, size_t bytes, int threads) {
-    const size_t piece = (size_t)1 << 20, n = (bytes + piece - 1) / piece;
-    unsigned nt = threads > 0 ? (unsigned)threads : std::min(32u, std::max(1u, std::thread::hardware_concurrency()));
-    nt = (unsigned)std::max<size_t>(1, std::min<size_t>(nt, n));
-    std::atomic<size_t> next{0};
-    auto work = [&] {
-        for (;;) {
-            const size_t i = next.fetch_add(1, std::memory_order_relaxed);
-            if (i >= n) break;
-            std::memcpy(static_cast<char*>(dst) + i * piece, static_cast<const char*>(src) + i * piece, std::min(piece, bytes - i * piece));
-        }
-    };
+// The one threaded host copy of this file: copy(t, nt) moves share t of nt of a payload of `bytes` bytes, on nt host threads (the
+// caller's is one).  nt is the caller's `threads`, or without one (<= 0) the hardware's up to 16; never more than one thread per whole
+// MiB of payload, and at least one.
+template <class Copy> void copy_on_host_threads(size_t bytes, int threads, const Copy& copy) {
+    unsigned nt = threads > 0 ? (unsigned)threads : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    nt = (unsigned)std::max<size_t>(1, std::min<size_t>(nt, bytes >> 20));
     std::vector<std::thread> th;
-    for (unsigned t = 1; t < nt; ++t) th.emplace_back(work);
-    work();
+    for (unsigned t = 1; t < nt; ++t) th.emplace_back(copy, t, nt);
+    copy(0u, nt);
     for (auto& x : th) x.join();
+}
+
+// dst <- src on host threads, one contiguous share each
+void parallel_copy(void* dst, const void* src, size_t bytes, int threads) {
+    copy_on_host_threads(bytes, threads, [&](unsigned t, unsigned nt) {
+        const size_t b = bytes / nt * t, e = t + 1 == nt ? bytes : bytes / nt * (t + 1);
+        std::memcpy(static_cast<char*>(dst) + b, static_cast<const char*>(src) + b, e - b);
+    });
+}
+
+// A host corpus packed into pinned staging as [offsets u64 | lengths u64 | bytes] on host threads: one copy takes it to the device.
+// The staging stays the host copy of the offsets and lengths, so it must outlive their readers.
+struct PackedCorpus {
+    const char* st = nullptr; size_t nr_doc = 0, head = 0, total = 0;         // staging; its header's bytes; header + text
+    const uint64_t* off() const { return reinterpret_cast<const uint64_t*>(st); }
+    const uint64_t* len() const { return off() + nr_doc; }
+    // (every caller's next step: the device copy, ordered on s, in a buffer with the 16 spare bytes the staging has)
+    DevBuf upload(hipStream_t s) const {
+        DevBuf d;
+        d.reserve(total + 16);
+        if (total) XRL_HIP(hipMemcpyAsync(d.p, st, total, hipMemcpyHostToDevice, s));
+        return d;
+    }
+};
+PackedCorpus pack_corpus(PinnedStage& stage, const char* const* corpus, const size_t* doc_lens, size_t nr_doc, int threads) {
+    uint64_t bytes = 0;
+    for (size_t d = 0; d < nr_doc; ++d) bytes += doc_lens[d];
+    PackedCorpus P;
+    P.nr_doc = nr_doc; P.head = nr_doc * 16; P.total = P.head + (size_t)bytes;
+    char* const st = static_cast<char*>(stage.need(P.total + 16));
+    P.st = st;
+    uint64_t* const off = reinterpret_cast<uint64_t*>(st); uint64_t* const len = off + nr_doc;
+    uint64_t at = 0;
+    for (size_t d = 0; d < nr_doc; ++d) { off[d] = at; len[d] = doc_lens[d]; at += doc_lens[d]; }
+    copy_on_host_threads((size_t)bytes, threads, [&](unsigned t, unsigned nt) {
+        for (size_t d = nr_doc * t / nt, e = nr_doc * (t + 1) / nt; d < e; ++d)
+            if (len[d]) std::memcpy(st + P.head + off[d], corpus[d], len[d]);
+    });
+    return P;
 }
 
 struct TfidfHandle {
     TfidfVectorizer v;
-    std::vector<float> idf_all;                  // the base vectorizers' idf side by side (hstack column order)
     mutable PinnedStage stage;
     // c_tfidf_predict's stream, created once per (handle, device) instead of per call
     mutable std::mutex stream_mu;
     mutable hipStream_t stream = nullptr;
     mutable int stream_device = -1;
-    // call with the staging lock (stage.mu) HELD and keep it until the stream has been synchronised: a caller that switched devices
-    // replaces the stream, which must not happen under another thread's transfer
+    // call with the staging lock (stage.mu) HELD: StagedStream does
     hipStream_t stream_on(int device) const {
         std::lock_guard<std::mutex> g(stream_mu);
         if (stream && stream_device != device) { (void)hipSetDevice(stream_device); (void)hipStreamDestroy(stream); stream = nullptr; (void)hipSetDevice(device); }
@@ -116,6 +145,27 @@ struct TfidfHandle {
     }
 };
 
+// What every device call of a handle starts with: `device` set, the handle's staging lock taken, a stream chosen -- the caller's, else
+// the model's, else the handle's pooled one.  The lock lives as long as this object, and this object until the stream has been
+// synchronised: the staging buffer belongs to the transfer enqueued on the stream, and a call that switched devices REPLACES the pooled
+// stream, which must not happen under another thread's transfer.
+struct StagedStream {
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s = nullptr;
+    StagedStream(const TfidfHandle& H, int device, void* caller, hipStream_t model) {
+        use_device(device);
+        lock = std::unique_lock<std::mutex>(H.stage.mu);
+        s = caller ? static_cast<hipStream_t>(caller) : model ? model : H.stream_on(device);
+    }
+};
+
+// the hstacked CSR's row pointer out of the segment pointer of nb base vectorizers side by side: every nb-th entry
+std::vector<uint64_t> row_ptr_of(const std::vector<uint64_t>& seg_ptr, size_t nb, size_t rows) {
+    std::vector<uint64_t> row_ptr(rows + 1);
+    for (size_t r = 0; r <= rows; ++r) row_ptr[r] = seg_ptr[r * nb];
+    return row_ptr;
+}
+
 // c.ptr holds the SEGMENT pointer of nb base vectorizers side by side -> the hstacked CSR's row pointer (every nb-th entry; h_seg: the
 // segment pointer on the host when the host counted, nullptr: gathered by a kernel on s).  Returns the segment pointer, which the work
 // enqueued on s may still read: the caller keeps it until s is synchronised.
@@ -123,9 +173,7 @@ DevBuf seg_to_row_ptr(DevCsr& c, const std::vector<uint64_t>* h_seg, uint32_t nb
     if (nb == 1) return {};
     DevBuf seg = std::move(c.ptr);
     if (h_seg) {
-        std::vector<uint64_t> row_ptr((size_t)rows + 1);
-        for (size_t r = 0; r <= rows; ++r) row_ptr[r] = (*h_seg)[r * nb];
-        c.ptr.upload(row_ptr);
+        c.ptr.upload(row_ptr_of(*h_seg, nb, rows));
     } else {
         c.ptr.reserve(((size_t)rows + 1) * 8);
         launch_seg_to_row_ptr(seg.as<uint64_t>(), nb, rows, c.ptr.as<uint64_t>(), s);
@@ -140,16 +188,16 @@ void tfidf_weight_counts(const TfidfHandle& H, Queries* q, const std::vector<uin
     const uint32_t nb = (uint32_t)V.base.size();
     DevCsr& c = q->own;
     DevBuf d_idf, d_err;
-    d_idf.upload(H.idf_all);
+    d_idf.upload(V.idf_all);
     d_err.reserve(4); XRL_HIP(hipMemsetAsync(d_err.p, 0, 4, s));
     for (uint32_t b = 0; b < nb; ++b) {
         const TfidfBase& B = V.base[b];
         launch_tfidf_weight(c.ptr.as<uint64_t>(), c.idx.as<uint32_t>(), c.val.as<float>(), B.use_idf ? d_idf.as<float>() : nullptr, rows, V.nr_features,
                             B.binary ? 1 : 0, B.sublinear_tf ? 1 : 0, B.norm_p, c.val.as<float>(), s, nb, b, d_err.as<uint32_t>());
     }
-    // whole rows: the hstacked CSR's row pointer; the ensemble's normalisation (Vectorizer::predict, tfidf.hpp:1405-1430)
+    // whole rows: the hstacked CSR's row pointer; the ensemble's normalisation
     const DevBuf seg = seg_to_row_ptr(c, h_seg, nb, rows, s);
-    if (nb > 1 || V.norm_p != V.base[0].norm_p)
+    if (V.ensemble_norm_runs())
         launch_tfidf_weight(c.ptr.as<uint64_t>(), c.idx.as<uint32_t>(), c.val.as<float>(), nullptr, rows, V.nr_features, 0, 0, V.norm_p, c.val.as<float>(), s);
     uint32_t err = 0;
     XRL_HIP(hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, s));
@@ -159,13 +207,13 @@ void tfidf_weight_counts(const TfidfHandle& H, Queries* q, const std::vector<uin
 }
 
 // texts -> term counts (host threads, into pinned staging) -> device -> weighting + normalisation (K5): a query handle that owns its three arrays
-std::unique_ptr<Queries> tfidf_to_device(const TfidfHandle& H, const char* const* corpus, const size_t* doc_lens, size_t nr_doc, int threads, int device, hipStream_t s) {
+std::unique_ptr<Queries> tfidf_to_device(const TfidfHandle& H, const char* const* corpus, const size_t* doc_lens, size_t nr_doc, int threads, int device,
+                                         hipStream_t model_stream) {
     if (nr_doc > 0xFFFFFFFFull) fail("tfidf: too many documents");
     const TfidfVectorizer& V = H.v;
     const uint32_t rows = (uint32_t)nr_doc;
-    use_device(device);
-    std::lock_guard<std::mutex> stage_lock(H.stage.mu);          // held until the stream has consumed the staging buffer (the synchronize below)
-    if (!s) s = H.stream_on(device);                             // the handle's pooled stream, taken under the staging lock
+    const StagedStream on(H, device, nullptr, model_stream);     // (until tfidf_weight_counts has synchronised)
+    const hipStream_t s = on.s;
     std::vector<uint64_t> seg_ptr;
     uint32_t* h_col = nullptr; float* h_cnt = nullptr; uint64_t nnz = 0;
     V.count_corpus(corpus, doc_lens, nr_doc, threads, seg_ptr, [&](uint64_t n, uint32_t*& c, float*& v) {
@@ -204,15 +252,29 @@ void tfidf_count_on_device(const TfidfHandle& H, const uint8_t* d_text, const ui
              "which the host tokenizer decodes along another path: use the host tokenizer for this text");
 }
 
-// text -> counts (K9) -> the weighting tail: X ready for xrl_predict_device
-std::unique_ptr<Queries> tfidf_device_text_to_x(const TfidfHandle& H, const uint8_t* d_text, const uint64_t* d_doc_off, const uint64_t* d_doc_len,
-                                                const uint64_t* h_doc_len, uint64_t nr_doc, int device, hipStream_t s) {
+// The one path from text in HBM to a query handle: counts (K9), then either the weighting tail (X ready for xrl_predict_device) or, for
+// the counts themselves, the row pointer alone.  d_status as for tfidf_count_on_device.  Synchronised when it returns.
+std::unique_ptr<Queries> tfidf_text_to_queries(const TfidfHandle& H, const uint8_t* d_text, const uint64_t* d_doc_off, const uint64_t* d_doc_len,
+                                               const uint64_t* h_doc_len, uint64_t nr_doc, uint32_t* d_status, bool weighted, int device, hipStream_t s) {
     TokCounts C;
-    tfidf_count_on_device(H, d_text, d_doc_off, d_doc_len, h_doc_len, nr_doc, nullptr, device, s, C);
+    tfidf_count_on_device(H, d_text, d_doc_off, d_doc_len, h_doc_len, nr_doc, d_status, device, s, C);
+    const uint32_t nb = (uint32_t)H.v.base.size(), rows = (uint32_t)nr_doc;
     auto q = std::make_unique<Queries>();
     q->own = std::move(C.csr);
-    tfidf_weight_counts(H, q.get(), nullptr, (uint32_t)nr_doc, device, s);
+    if (weighted) { tfidf_weight_counts(H, q.get(), nullptr, rows, device, s); return q; }
+    const DevBuf seg = seg_to_row_ptr(q->own, nullptr, nb, rows, s);
+    if (nb > 1) XRL_HIP(hipStreamSynchronize(s));                // (the segment pointer goes with this scope)
+    set_own_csr(*q, device, rows, H.v.nr_features);
     return q;
+}
+
+// the caller's arrays for a rows x cols CSR of nnz entries: ONE allocator call, refused when it hands back nothing to write to
+struct CsrArrays { uint32_t* indices = nullptr; uint64_t* indptr = nullptr; float* data = nullptr; };
+CsrArrays alloc_csr(py_sparse_allocator_t alloc, uint64_t rows, uint64_t cols, uint64_t nnz) {
+    CsrArrays a;
+    alloc(false, rows, cols, nnz, &a.indices, &a.indptr, &a.data);
+    if (!a.indptr || (nnz && (!a.indices || !a.data))) fail("allocator returned null");
+    return a;
 }
 }  // namespace
 
@@ -223,7 +285,6 @@ void* c_tfidf_load(const char* model_dir) {
         if (!model_dir) fail("null model_dir");
         auto h = std::make_unique<TfidfHandle>();
         h->v.load(model_dir);
-        for (const auto& b : h->v.base) h->idf_all.insert(h->idf_all.end(), b.idf.begin(), b.idf.end());
         return h.release();
     });
 }
@@ -274,30 +335,24 @@ static void tfidf_predict_small_on_host(const TfidfHandle& H, const char* const*
     const uint64_t nnz = seg_ptr.empty() ? 0 : seg_ptr.back();
     for (uint32_t b = 0; b < nb; ++b) {
         const TfidfBase& B = V.base[b];
-        tfidf_weight_host(seg_ptr.data(), h_col.data(), h_val.data(), B.use_idf ? H.idf_all.data() : nullptr, rows, V.nr_features, B.binary, B.sublinear_tf, B.norm_p, nb, b);
+        tfidf_weight_host(seg_ptr.data(), h_col.data(), h_val.data(), B.use_idf ? V.idf_all.data() : nullptr, rows, V.nr_features, B.binary, B.sublinear_tf, B.norm_p, nb, b);
     }
-    std::vector<uint64_t> row_ptr((size_t)rows + 1);
-    for (size_t r = 0; r <= rows; ++r) row_ptr[r] = seg_ptr[r * nb];
-    if (nb > 1 || V.norm_p != V.base[0].norm_p)
+    const std::vector<uint64_t> row_ptr = row_ptr_of(seg_ptr, nb, rows);
+    if (V.ensemble_norm_runs())
         tfidf_weight_host(row_ptr.data(), h_col.data(), h_val.data(), nullptr, rows, V.nr_features, false, false, V.norm_p, 1, 0);
-    uint32_t* indices = nullptr; uint64_t* indptr = nullptr; float* data = nullptr;
-    pred_alloc(false, rows, V.nr_features, nnz, &indices, &indptr, &data);
-    if (!indptr || (nnz && (!indices || !data))) fail("allocator returned null");
-    std::memcpy(indptr, row_ptr.data(), ((size_t)rows + 1) * 8);
-    if (nnz) { std::memcpy(indices, h_col.data(), (size_t)nnz * 4); std::memcpy(data, h_val.data(), (size_t)nnz * 4); }
+    const CsrArrays out = alloc_csr(pred_alloc, rows, V.nr_features, nnz);
+    std::memcpy(out.indptr, row_ptr.data(), ((size_t)rows + 1) * 8);
+    if (nnz) { std::memcpy(out.indices, h_col.data(), (size_t)nnz * 4); std::memcpy(out.data, h_val.data(), (size_t)nnz * 4); }
 }
 
 static void tfidf_predict_to_host(const TfidfHandle& H, const char* const* corpus, const size_t* doc_lens, size_t nr_doc, int threads, py_sparse_allocator_t pred_alloc) {
     const char* hs = std::getenv("XRL_TFIDF_HOST_DOCS");                     // XRL_TFIDF_HOST_DOCS=0: always the device (tests; read per call)
     if (!(hs && hs[0] == '0') && nr_doc <= kTfidfHostDocs) { tfidf_predict_small_on_host(H, corpus, doc_lens, nr_doc, pred_alloc); return; }
-    use_device(g_device);
-    // (stream = nullptr: tfidf_to_device takes the handle's pooled stream under its staging lock and holds the lock until it has synchronised)
+    // (no model, so no model stream: the handle's pooled one)
     std::unique_ptr<Queries> q = tfidf_to_device(H, corpus, doc_lens, nr_doc, threads, g_device, nullptr);
-    uint32_t* indices = nullptr; uint64_t* indptr = nullptr; float* data = nullptr;
     const uint64_t nnz = q->dev.nnz;
-    pred_alloc(false, q->dev.rows, q->dev.cols, nnz, &indices, &indptr, &data);
-    if (!indptr || (nnz && (!indices || !data))) fail("allocator returned null");
-    XRL_HIP(hipMemcpy(indptr, q->dev.row_ptr, ((size_t)q->dev.rows + 1) * 8, hipMemcpyDeviceToHost));
+    const CsrArrays out = alloc_csr(pred_alloc, q->dev.rows, q->dev.cols, nnz);
+    XRL_HIP(hipMemcpy(out.indptr, q->dev.row_ptr, ((size_t)q->dev.rows + 1) * 8, hipMemcpyDeviceToHost));
     if (nnz) {
         // D2H into the pinned staging buffer (link speed), then host threads spread it over the allocator's fresh arrays: their first touch
         // in parallel, instead of the runtime's single-threaded pageable path
@@ -306,8 +361,8 @@ static void tfidf_predict_to_host(const TfidfHandle& H, const char* const* corpu
         char* st = static_cast<char*>(H.stage.need(2 * nb4));
         XRL_HIP(hipMemcpy(st, q->dev.col_idx, nb4, hipMemcpyDeviceToHost));
         XRL_HIP(hipMemcpy(st + nb4, q->dev.val, nb4, hipMemcpyDeviceToHost));
-        parallel_copy(indices, st, nb4, threads);
-        parallel_copy(data, st + nb4, nb4, threads);
+        parallel_copy(out.indices, st, nb4, threads);
+        parallel_copy(out.data, st + nb4, nb4, threads);
     }
 }
 
@@ -357,56 +412,25 @@ void c_tfidf_predict_from_file(void* ptr, void* corpus_fname_ptr, size_t fname_l
     });
 }
 
+// host texts -> X on the model's device, behind xrl_tfidf_predict_device (tokenizer 0) and xrl_tfidf_predict_device_tok, which check their
+// arguments in their own words first.  Tokenizer 1: the corpus goes through the handle's staging to the device in one copy, K9 counts.
+static void* tfidf_predict_device_from_host(void* vectorizer, void* model, void* corpus_ptr, const size_t* doc_lens, size_t nr_doc, int tokenizer, int threads) {
+    Model& m = *as_model(model);
+    const TfidfHandle& H = *static_cast<TfidfHandle*>(vectorizer);
+    const char* const* corpus = static_cast<const char* const*>(corpus_ptr);
+    if (tokenizer == 0) return tfidf_to_device(H, corpus, doc_lens, nr_doc, threads, m.device, m.stream).release();
+    const StagedStream on(H, m.device, nullptr, m.stream);
+    const PackedCorpus P = pack_corpus(H.stage, corpus, doc_lens, nr_doc, threads);
+    const DevBuf d_in = P.upload(on.s);
+    const uint64_t* d_off = d_in.as<uint64_t>();
+    return tfidf_text_to_queries(H, d_in.as<uint8_t>() + P.head, d_off, d_off + nr_doc, P.len(), nr_doc, nullptr, true, m.device, on.s).release();
+}
+
 void* xrl_tfidf_predict_device(void* vectorizer, void* model, void* corpus_ptr, const size_t* doc_lens, size_t nr_doc, int threads) {
     return guarded_value((void*)nullptr, [&]() -> void* {
         if (!vectorizer) fail("xrl_tfidf_predict_device: null vectorizer handle");
         if (nr_doc && (!corpus_ptr || !doc_lens)) fail("xrl_tfidf_predict_device: null corpus");
-        Model& m = *as_model(model);
-        const TfidfHandle& H = *static_cast<TfidfHandle*>(vectorizer);
-        return tfidf_to_device(H, static_cast<const char* const*>(corpus_ptr), doc_lens, nr_doc, threads, m.device, m.stream).release();
-    });
-}
-
-// ---- the device tokenizer (K9): document bytes in HBM.  Null arguments are refused before the GPU is touched.
-static void check_device_text_args(const char* what, void* vectorizer, void* model, const void* d_text, const void* d_doc_off, const void* d_doc_len, uint64_t nr_doc) {
-    const std::string w = std::string(what) + ": ";
-    if (!vectorizer) fail(w + "null vectorizer handle");
-    if (!model) fail(w + "null model handle");
-    if (nr_doc && (!d_text || !d_doc_off || !d_doc_len)) fail(w + "null text, offsets or lengths");
-    if (nr_doc > 0xFFFFFFFFull) fail("tfidf: too many documents");
-}
-
-void* xrl_tfidf_counts_device(void* vectorizer, void* model, const uint8_t* d_text, const uint64_t* d_doc_off, const uint64_t* d_doc_len, uint64_t nr_doc,
-                              uint32_t* d_status, void* hip_stream) {
-    return guarded_value((void*)nullptr, [&]() -> void* {
-        check_device_text_args("xrl_tfidf_counts_device", vectorizer, model, d_text, d_doc_off, d_doc_len, nr_doc);
-        Model& m = *as_model(model);
-        const TfidfHandle& H = *static_cast<TfidfHandle*>(vectorizer);
-        use_device(m.device);
-        std::lock_guard<std::mutex> stage_lock(H.stage.mu);      // (the pooled stream is handed out under this lock)
-        hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : m.stream ? m.stream : H.stream_on(m.device);
-        TokCounts C;
-        tfidf_count_on_device(H, d_text, d_doc_off, d_doc_len, nullptr, nr_doc, d_status, m.device, s, C);
-        const uint32_t nb = (uint32_t)H.v.base.size(), rows = (uint32_t)nr_doc;
-        auto q = std::make_unique<Queries>();
-        q->own = std::move(C.csr);
-        const DevBuf seg = seg_to_row_ptr(q->own, nullptr, nb, rows, s);
-        if (nb > 1) XRL_HIP(hipStreamSynchronize(s));            // (the segment pointer goes with this scope)
-        set_own_csr(*q, m.device, rows, H.v.nr_features);
-        return q.release();
-    });
-}
-
-void* xrl_tfidf_predict_device_text(void* vectorizer, void* model, const uint8_t* d_text, const uint64_t* d_doc_off, const uint64_t* d_doc_len, uint64_t nr_doc,
-                                    void* hip_stream) {
-    return guarded_value((void*)nullptr, [&]() -> void* {
-        check_device_text_args("xrl_tfidf_predict_device_text", vectorizer, model, d_text, d_doc_off, d_doc_len, nr_doc);
-        Model& m = *as_model(model);
-        const TfidfHandle& H = *static_cast<TfidfHandle*>(vectorizer);
-        use_device(m.device);
-        std::lock_guard<std::mutex> stage_lock(H.stage.mu);
-        hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : m.stream ? m.stream : H.stream_on(m.device);
-        return tfidf_device_text_to_x(H, d_text, d_doc_off, d_doc_len, nullptr, nr_doc, m.device, s).release();
+        return tfidf_predict_device_from_host(vectorizer, model, corpus_ptr, doc_lens, nr_doc, 0, threads);
     });
 }
 
@@ -417,38 +441,41 @@ void* xrl_tfidf_predict_device_tok(void* vectorizer, void* model, void* corpus_p
         if (nr_doc && (!corpus_ptr || !doc_lens)) fail("xrl_tfidf_predict_device_tok: null corpus");
         if (tokenizer != 0 && tokenizer != 1) fail("xrl_tfidf_predict_device_tok: tokenizer must be 0 (host) or 1 (device)");
         if (nr_doc > 0xFFFFFFFFull) fail("tfidf: too many documents");
-        Model& m = *as_model(model);
-        const TfidfHandle& H = *static_cast<TfidfHandle*>(vectorizer);
-        const char* const* corpus = static_cast<const char* const*>(corpus_ptr);
-        if (tokenizer == 0) return tfidf_to_device(H, corpus, doc_lens, nr_doc, threads, m.device, m.stream).release();
-        use_device(m.device);
-        std::lock_guard<std::mutex> stage_lock(H.stage.mu);      // held until the stream has consumed the staging buffer
-        hipStream_t s = m.stream ? m.stream : H.stream_on(m.device);
-        // the corpus packed into the pinned staging as [offsets u64 | lengths u64 | bytes], one copy to the device
-        std::vector<uint64_t> off((size_t)nr_doc + 1, 0);
-        for (size_t d = 0; d < nr_doc; ++d) off[d + 1] = off[d] + doc_lens[d];
-        const size_t head = nr_doc * 16, total = head + (size_t)off[nr_doc];
-        char* st = static_cast<char*>(H.stage.need(total + 16));
-        std::memcpy(st, off.data(), nr_doc * 8);
-        for (size_t d = 0; d < nr_doc; ++d) reinterpret_cast<uint64_t*>(st + nr_doc * 8)[d] = doc_lens[d];
-        {
-            unsigned nt = threads > 0 ? (unsigned)threads : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-            nt = (unsigned)std::max<size_t>(1, std::min<size_t>(nt, (size_t)off[nr_doc] >> 20));
-            auto work = [&](unsigned t) {
-                for (size_t d = nr_doc * t / nt, e = nr_doc * (t + 1) / nt; d < e; ++d)
-                    if (doc_lens[d]) std::memcpy(st + head + off[d], corpus[d], doc_lens[d]);
-            };
-            std::vector<std::thread> th;
-            for (unsigned t = 1; t < nt; ++t) th.emplace_back(work, t);
-            work(0);
-            for (auto& x : th) x.join();
-        }
-        DevBuf d_in;
-        d_in.reserve(total + 16);
-        if (total) XRL_HIP(hipMemcpyAsync(d_in.p, st, total, hipMemcpyHostToDevice, s));
-        const uint64_t* d_off = d_in.as<uint64_t>();
-        return tfidf_device_text_to_x(H, reinterpret_cast<const uint8_t*>(d_in.p) + head, d_off, d_off + nr_doc, reinterpret_cast<const uint64_t*>(st + nr_doc * 8), nr_doc,
-                                      m.device, s).release();
+        return tfidf_predict_device_from_host(vectorizer, model, corpus_ptr, doc_lens, nr_doc, tokenizer, threads);
+    });
+}
+
+// ---- the device tokenizer (K9): document bytes in HBM.  Null arguments are refused before the GPU is touched (model_missing: false too
+// for the entry point that takes a device instead of a model).
+static void check_device_text_args(const std::string& w, void* vectorizer, bool model_missing, const void* d_text, const void* d_doc_off, const void* d_doc_len,
+                                   uint64_t nr_doc) {
+    if (!vectorizer) fail(w + "null vectorizer handle");
+    if (model_missing) fail(w + "null model handle");
+    if (nr_doc && (!d_text || !d_doc_off || !d_doc_len)) fail(w + "null text, offsets or lengths");
+    if (nr_doc > 0xFFFFFFFFull) fail("tfidf: too many documents");
+}
+
+// resident text -> a query handle on the model's device and, without a caller's stream, the model's stream
+static void* tfidf_model_text_to_queries(const char* what, void* vectorizer, void* model, const uint8_t* d_text, const uint64_t* d_doc_off, const uint64_t* d_doc_len,
+                                         uint64_t nr_doc, uint32_t* d_status, bool weighted, void* hip_stream) {
+    check_device_text_args(what, vectorizer, !model, d_text, d_doc_off, d_doc_len, nr_doc);
+    Model& m = *as_model(model);
+    const TfidfHandle& H = *static_cast<TfidfHandle*>(vectorizer);
+    const StagedStream on(H, m.device, hip_stream, m.stream);
+    return tfidf_text_to_queries(H, d_text, d_doc_off, d_doc_len, nullptr, nr_doc, d_status, weighted, m.device, on.s).release();
+}
+
+void* xrl_tfidf_counts_device(void* vectorizer, void* model, const uint8_t* d_text, const uint64_t* d_doc_off, const uint64_t* d_doc_len, uint64_t nr_doc,
+                              uint32_t* d_status, void* hip_stream) {
+    return guarded_value((void*)nullptr, [&] {
+        return tfidf_model_text_to_queries("xrl_tfidf_counts_device: ", vectorizer, model, d_text, d_doc_off, d_doc_len, nr_doc, d_status, false, hip_stream);
+    });
+}
+
+void* xrl_tfidf_predict_device_text(void* vectorizer, void* model, const uint8_t* d_text, const uint64_t* d_doc_off, const uint64_t* d_doc_len, uint64_t nr_doc,
+                                    void* hip_stream) {
+    return guarded_value((void*)nullptr, [&] {
+        return tfidf_model_text_to_queries("xrl_tfidf_predict_device_text: ", vectorizer, model, d_text, d_doc_off, d_doc_len, nr_doc, nullptr, true, hip_stream);
     });
 }
 
@@ -498,113 +525,15 @@ static TfidfHandle* train_handle(const std::string& w, const TfidfVectorizerPara
     const std::vector<TfidfBaseVectorizerParam> params(param->base_param_ptr, param->base_param_ptr + param->num_base_vect);
     V.base.resize(params.size());
     V.norm_p = param->norm_p;
-    for (size_t b = 0; b < params.size(); ++b) {
-        const TfidfBaseVectorizerParam& P = params[b];
-        TfidfBase& B = V.base[b];
-        B.tok_type = P.tok_type; B.min_ngram = P.min_ngram; B.max_ngram = P.max_ngram; B.max_length = P.max_length; B.norm_p = P.norm_p;
-        B.binary = P.binary; B.use_idf = P.use_idf; B.sublinear_tf = P.sublinear_tf;
-        B.max_feature = P.max_feature; B.min_df_cnt = P.min_df_cnt; B.max_df_cnt = P.max_df_cnt; B.min_df_ratio = P.min_df_ratio; B.max_df_ratio = P.max_df_ratio;
-        B.smooth_idf = P.smooth_idf; B.add_one_idf = P.add_one_idf; B.keep_frequent_feature = P.keep_frequent_feature;
-    }
+    for (size_t b = 0; b < params.size(); ++b) set_base_params(V.base[b], params[b]);
     uint64_t first_bad[2];
     tfidf_train_device(V.base, params, d_text, d_doc_off, d_doc_len, h_doc_off, h_doc_len, nr_doc, s, h->train_forms, first_bad);
     if (first_bad[0] != ~0ull) fail(w + "the string is not utf-8 encoded! (document " + std::to_string(first_bad[0]) + ")");
     if (first_bad[1] != ~0ull)
         fail(w + "document " + std::to_string(first_bad[1]) + " holds a UTF-8 lead byte followed by too few continuation bytes, which the reference's "
              "sequential decode reads along another path: not served by device training");
-    uint64_t tot = 0;
-    for (const auto& b : V.base) { tot += b.nr_features; h->idf_all.insert(h->idf_all.end(), b.idf.begin(), b.idf.end()); }
-    if (tot > 0xFFFFFFFFull) fail(w + "too many features");
-    V.nr_features = (uint32_t)tot;
+    V.finish(w);
     return h.release();
-}
-
-// the tokens and n-grams a base vectorizer's tables hold, in table order
-static void enumerate_base(const TfidfBase& B, std::vector<std::pair<std::string, int32_t>>& tokens, std::vector<int32_t>& flat, std::vector<uint64_t>& off,
-                           std::vector<uint32_t>& ids) {
-    tokens.clear(); flat.clear(); ids.clear(); off.assign(1, 0);
-    for (size_t i = 0; i < B.vocab.s.size(); ++i) {
-        const tft::ShortEntry& e = B.vocab.s[i];
-        if (!e.len) continue;
-        std::string t(e.len, '\0');
-        for (uint32_t j = 0; j < e.len; ++j) t[j] = (char)(uint8_t)(e.key >> (8 * j));
-        tokens.emplace_back(std::move(t), e.idx);
-    }
-    for (size_t i = 0; i < B.vocab.l.size(); ++i) {
-        const tft::LongEntry& e = B.vocab.l[i];
-        if (e.len) tokens.emplace_back(B.vocab.arena.substr(e.off, e.len), e.idx);
-    }
-    const NgramTable& G = B.features;
-    for (size_t t = 0; t < G.uni.size(); ++t)
-        if (G.uni[t] != NgramTable::kNone) { flat.push_back((int32_t)t); off.push_back(flat.size()); ids.push_back(G.uni[t] - 1u); }
-    const uint64_t field = G.pack_bits >= 64 ? ~0ull : (1ull << G.pack_bits) - 1;
-    for (size_t i = 0; i < G.packed.size(); ++i) {
-        const tft::PackedEntry& e = G.packed[i];
-        if (e.id1 == NgramTable::kNone) continue;
-        for (unsigned sh = 0; sh < 64; sh += G.pack_bits) {
-            const uint64_t f = (e.key >> sh) & field;
-            if (!f) break;
-            flat.push_back((int32_t)(uint32_t)(f - 1));
-        }
-        off.push_back(flat.size()); ids.push_back(e.id1 - 1u);
-    }
-    for (size_t i = 0; i < G.gen.size(); ++i) {
-        const tft::GenEntry& e = G.gen[i];
-        if (e.id1 == NgramTable::kNone) continue;
-        flat.insert(flat.end(), G.arena.begin() + e.off, G.arena.begin() + e.off + e.n);
-        off.push_back(flat.size()); ids.push_back(e.id1 - 1u);
-    }
-}
-
-static void make_dir(const std::string& d, const char* what) {
-    if (mkdir(d.c_str(), 0777) == -1 && errno != EEXIST) fail(std::string("xrl_tfidf_save: Unable to create ") + what + " at " + d);
-}
-static std::FILE* open_w(const std::string& f) {
-    std::FILE* fp = std::fopen(f.c_str(), "wb");
-    if (!fp) fail("xrl_tfidf_save: Unable to save to " + f);
-    return fp;
-}
-// a float as nlohmann prints it: the double it converts to, with enough digits to read back exactly, always with a '.' or an exponent
-static std::string json_float(float v) {
-    char buf[64];
-    std::snprintf(buf, sizeof(buf), "%.17g", (double)v);
-    std::string s(buf);
-    if (s.find_first_of(".en") == std::string::npos) s += ".0";
-    return s;
-}
-
-static void save_base(const TfidfBase& B, const std::string& dir) {
-    make_dir(dir, "save folder");
-    make_dir(dir + "/tokenizer", "save folder");
-    make_dir(dir + "/vectorizer", "save folder");
-    std::vector<std::pair<std::string, int32_t>> tokens; std::vector<int32_t> flat; std::vector<uint64_t> off; std::vector<uint32_t> ids;
-    enumerate_base(B, tokens, flat, off, ids);
-    std::FILE* fp = open_w(dir + "/tokenizer/config.json");
-    std::fprintf(fp, "{\n    \"token_type\": %d\n}", B.tok_type);
-    std::fclose(fp);
-    fp = open_w(dir + "/tokenizer/vocab.txt");
-    std::fprintf(fp, "%zu\n", tokens.size());
-    for (const auto& t : tokens) { std::fprintf(fp, "%d\t", t.second); std::fwrite(t.first.data(), 1, t.first.size(), fp); std::fputc('\n', fp); }
-    std::fclose(fp);
-    const auto tf = [](bool b) { return b ? "true" : "false"; };
-    fp = open_w(dir + "/vectorizer/config.json");
-    std::fprintf(fp,
-                 "{\n    \"kwargs\": {\n        \"add_one_idf\": %s,\n        \"binary\": %s,\n        \"keep_frequent_feature\": %s,\n        \"max_df_cnt\": %d,\n"
-                 "        \"max_df_ratio\": %s,\n        \"max_feature\": %d,\n        \"max_length\": %d,\n        \"min_df_cnt\": %d,\n        \"min_df_ratio\": %s,\n"
-                 "        \"ngram_range\": [\n            %d,\n            %d\n        ],\n        \"norm_p\": \"%s\",\n        \"smooth_idf\": %s,\n"
-                 "        \"sublinear_tf\": %s,\n        \"use_idf\": %s\n    },\n    \"type\": \"tfidf\"\n}",
-                 tf(B.add_one_idf), tf(B.binary), tf(B.keep_frequent_feature), B.max_df_cnt, json_float(B.max_df_ratio).c_str(), B.max_feature, B.max_length, B.min_df_cnt,
-                 json_float(B.min_df_ratio).c_str(), B.min_ngram, B.max_ngram, B.norm_p == 1 ? "l1" : "l2", tf(B.smooth_idf), tf(B.sublinear_tf), tf(B.use_idf));
-    std::fclose(fp);
-    fp = open_w(dir + "/vectorizer/tfidf-model.txt");
-    std::fprintf(fp, "%zu\n", ids.size());
-    for (size_t f = 0; f < ids.size(); ++f) {
-        const float v = ids[f] < B.idf.size() ? B.idf[ids[f]] : 0.0f;
-        std::fprintf(fp, "%d\t%f\t%zu", (int)ids[f], v, (size_t)(off[f + 1] - off[f]));
-        for (uint64_t i = off[f]; i < off[f + 1]; ++i) std::fprintf(fp, i == off[f] ? "\t%d" : " %d", flat[i]);
-        std::fputc('\n', fp);
-    }
-    std::fclose(fp);
 }
 
 void* xrl_tfidf_train(void* corpus_ptr, const size_t* doc_lens, size_t nr_doc, const TfidfVectorizerParam* param, int threads) {
@@ -614,35 +543,14 @@ void* xrl_tfidf_train(void* corpus_ptr, const size_t* doc_lens, size_t nr_doc, c
         check_train_args(w, param, nr_doc);
         require_gpu();
         use_device(g_device);
-        const char* const* corpus = static_cast<const char* const*>(corpus_ptr);
-        // the corpus packed into pinned staging as [offsets u64 | lengths u64 | bytes], one copy to the device (as xrl_tfidf_predict_device_tok)
-        std::vector<uint64_t> off((size_t)nr_doc + 1, 0), len((size_t)nr_doc);
-        for (size_t d = 0; d < nr_doc; ++d) { len[d] = doc_lens[d]; off[d + 1] = off[d] + doc_lens[d]; }
-        const size_t head = nr_doc * 16, total = head + (size_t)off[nr_doc];
-        PinnedStage stage;
-        char* st = static_cast<char*>(stage.need(total + 16));
-        std::memcpy(st, off.data(), nr_doc * 8);
-        std::memcpy(st + nr_doc * 8, len.data(), nr_doc * 8);
-        {
-            unsigned nt = threads > 0 ? (unsigned)threads : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-            nt = (unsigned)std::max<size_t>(1, std::min<size_t>(nt, (size_t)off[nr_doc] >> 20));
-            auto work = [&](unsigned t) {
-                for (size_t d = nr_doc * t / nt, e = nr_doc * (t + 1) / nt; d < e; ++d)
-                    if (doc_lens[d]) std::memcpy(st + head + off[d], corpus[d], doc_lens[d]);
-            };
-            std::vector<std::thread> th;
-            for (unsigned t = 1; t < nt; ++t) th.emplace_back(work, t);
-            work(0);
-            for (auto& x : th) x.join();
-        }
+        PinnedStage stage;                                       // (there is no handle yet: a staging of the call's own)
+        const PackedCorpus P = pack_corpus(stage, static_cast<const char* const*>(corpus_ptr), doc_lens, nr_doc, threads);
         hipStream_t s = nullptr;
         XRL_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         struct Drop { hipStream_t s; ~Drop() { (void)hipStreamDestroy(s); } } drop{s};
-        DevBuf d_in;
-        d_in.reserve(total + 16);
-        XRL_HIP(hipMemcpyAsync(d_in.p, st, total, hipMemcpyHostToDevice, s));
+        const DevBuf d_in = P.upload(s);
         const uint64_t* d_off = d_in.as<uint64_t>();
-        return train_handle(w, param, reinterpret_cast<const uint8_t*>(d_in.p) + head, d_off, d_off + nr_doc, off.data(), len.data(), nr_doc, s);
+        return train_handle(w, param, d_in.as<uint8_t>() + P.head, d_off, d_off + nr_doc, P.off(), P.len(), nr_doc, s);
     });
 }
 
@@ -668,35 +576,18 @@ void* xrl_tfidf_train_device(int device, const uint8_t* d_text, const uint64_t* 
 void xrl_tfidf_save(void* vectorizer, const char* model_dir) {
     guarded([&] {
         if (!vectorizer || !model_dir) fail("xrl_tfidf_save: null argument");
-        const TfidfVectorizer& V = static_cast<TfidfHandle*>(vectorizer)->v;
-        const std::string dir(model_dir);
-        make_dir(dir, "save folder");
-        std::FILE* fp = open_w(dir + "/meta.json");
-        std::fprintf(fp, "{\n    \"kwargs\": {\n        \"norm_p\": %d,\n        \"num_base_vect\": %zu\n    },\n    \"type\": \"tfidf\"\n}", V.norm_p, V.base.size());
-        std::fclose(fp);
-        for (size_t b = 0; b < V.base.size(); ++b) save_base(V.base[b], dir + "/" + std::to_string(b) + ".base");
+        static_cast<TfidfHandle*>(vectorizer)->v.save(model_dir);
     });
 }
 
 void* xrl_tfidf_transform_device(void* vectorizer, int device, const uint8_t* d_text, const uint64_t* d_doc_off, const uint64_t* d_doc_len, uint64_t nr_doc,
                                  uint32_t* d_status, void* hip_stream) {
     return guarded_value((void*)nullptr, [&]() -> void* {
-        const std::string w = "xrl_tfidf_transform_device: ";
-        if (!vectorizer) fail(w + "null vectorizer handle");
-        if (nr_doc && (!d_text || !d_doc_off || !d_doc_len)) fail(w + "null text, offsets or lengths");
-        if (nr_doc > 0xFFFFFFFFull) fail("tfidf: too many documents");
+        check_device_text_args("xrl_tfidf_transform_device: ", vectorizer, false, d_text, d_doc_off, d_doc_len, nr_doc);
         require_gpu();
         const TfidfHandle& H = *static_cast<TfidfHandle*>(vectorizer);
-        use_device(device);
-        std::lock_guard<std::mutex> stage_lock(H.stage.mu);      // (the pooled stream is handed out under this lock)
-        hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : H.stream_on(device);
-        if (!d_status) return tfidf_device_text_to_x(H, d_text, d_doc_off, d_doc_len, nullptr, nr_doc, device, s).release();
-        TokCounts C;
-        tfidf_count_on_device(H, d_text, d_doc_off, d_doc_len, nullptr, nr_doc, d_status, device, s, C);
-        auto q = std::make_unique<Queries>();
-        q->own = std::move(C.csr);
-        tfidf_weight_counts(H, q.get(), nullptr, (uint32_t)nr_doc, device, s);
-        return q.release();
+        const StagedStream on(H, device, hip_stream, nullptr);   // (no model: the caller's stream or the pooled one)
+        return tfidf_text_to_queries(H, d_text, d_doc_off, d_doc_len, nullptr, nr_doc, d_status, true, device, on.s).release();
     });
 }
 
@@ -708,7 +599,7 @@ int xrl_tfidf_export(void* vectorizer, uint32_t base, uint64_t* sizes, uint8_t* 
         if (base >= V.base.size()) fail("xrl_tfidf_export: base " + std::to_string(base) + " of " + std::to_string(V.base.size()));
         const TfidfBase& B = V.base[base];
         std::vector<std::pair<std::string, int32_t>> tokens; std::vector<int32_t> flat; std::vector<uint64_t> off; std::vector<uint32_t> ids;
-        enumerate_base(B, tokens, flat, off, ids);
+        B.enumerate(tokens, flat, off, ids);
         uint64_t bytes = 0;
         for (const auto& t : tokens) bytes += t.first.size();
         sizes[0] = tokens.size(); sizes[1] = bytes; sizes[2] = ids.size(); sizes[3] = flat.size(); sizes[4] = B.idf.size();
@@ -745,15 +636,13 @@ void xrl_tfidf_counts(void* ptr, void* corpus_ptr, const size_t* doc_lens, size_
         if (!ptr || !alloc || (nr_doc && (!corpus_ptr || !doc_lens))) fail("xrl_tfidf_counts: null argument");
         const TfidfVectorizer& V = static_cast<TfidfHandle*>(ptr)->v;
         std::vector<uint64_t> seg_ptr;
-        uint32_t* indices = nullptr; uint64_t* indptr = nullptr; float* data = nullptr;
+        CsrArrays out;
         // the allocator's arrays ARE the destination: the worker threads fill (and first-touch) them in parallel
         V.count_corpus(static_cast<const char* const*>(corpus_ptr), doc_lens, nr_doc, threads, seg_ptr, [&](uint64_t n, uint32_t*& c, float*& v) {
-            alloc(false, nr_doc, V.nr_features, n, &indices, &indptr, &data);
-            if (!indptr || (n && (!indices || !data))) fail("allocator returned null");
-            c = indices; v = data;
+            out = alloc_csr(alloc, nr_doc, V.nr_features, n);
+            c = out.indices; v = out.data;
         });
-        const size_t nb = V.base.size();
-        for (size_t r = 0; r <= nr_doc; ++r) indptr[r] = seg_ptr[r * nb];
+        std::memcpy(out.indptr, row_ptr_of(seg_ptr, V.base.size(), nr_doc).data(), (nr_doc + 1) * 8);
     });
 }
 

@@ -33,7 +33,15 @@ struct TrainForms {
     uint64_t us_vocab = 0, us_df = 0, us_order = 0;   // wall microseconds: vocabulary passes (host sort and table build included), df batches, merge + filter + order + idf
 };
 
-// bases[b]'s parameters are set by the caller; the call fills vocab, features, idf, nr_features, sort_shift.  d_text / d_doc_off / d_doc_len
+// the caller's parameters of one base vectorizer as the fields `load` would have read from a folder that states them
+inline void set_base_params(TfidfBase& B, const TfidfBaseVectorizerParam& P) {
+    B.tok_type = P.tok_type; B.min_ngram = P.min_ngram; B.max_ngram = P.max_ngram; B.max_length = P.max_length; B.norm_p = P.norm_p;
+    B.binary = P.binary; B.use_idf = P.use_idf; B.sublinear_tf = P.sublinear_tf;
+    B.max_feature = P.max_feature; B.min_df_cnt = P.min_df_cnt; B.max_df_cnt = P.max_df_cnt; B.min_df_ratio = P.min_df_ratio; B.max_df_ratio = P.max_df_ratio;
+    B.smooth_idf = P.smooth_idf; B.add_one_idf = P.add_one_idf; B.keep_frequent_feature = P.keep_frequent_feature;
+}
+
+// bases[b]'s parameters are set by the caller (set_base_params); the call fills vocab, features, idf, nr_features, sort_shift.  d_text / d_doc_off / d_doc_len
 // are device pointers; h_doc_off / h_doc_len the same arrays on the host.  first_bad: the lowest document with char status 1 / 2 (~0: none);
 // when one is set nothing was trained.  Synchronises s.
 void tfidf_train_device(std::vector<TfidfBase>& bases, const std::vector<TfidfBaseVectorizerParam>& params, const uint8_t* d_text, const uint64_t* d_doc_off,

@@ -184,9 +184,9 @@ def predict_tfidf_from_torch(model, crow, col, count, n_cols, idf=None, binary=F
 
 
 def _device_text(text_u8, doc_off, doc_len):
-    """The device tokenizer's inputs checked and made contiguous: (text uint8, offsets int64, lengths int64) CUDA tensors on one device
-    (the int64 tensors hold the u64 values).  The copies, if any, run on torch's current stream, which is then synchronised: K9 runs on
-    the model's stream."""
+    """The device tokenizer's inputs checked and made contiguous: ``(text uint8, offsets int64, lengths int64, text_addr, n)`` -- CUDA tensors
+    on one device (the int64 tensors hold the u64 values; keep them alive over the call), the address to pass for the text and the number
+    of documents.  The copies, if any, run on torch's current stream, which is then synchronised: K9 runs on the model's stream."""
     import torch
     assert text_u8.is_cuda and doc_off.is_cuda and doc_len.is_cuda and text_u8.device == doc_off.device == doc_len.device
     assert text_u8.dtype == torch.uint8 and doc_off.dtype == torch.int64 and doc_len.dtype == torch.int64
@@ -195,7 +195,23 @@ def _device_text(text_u8, doc_off, doc_len):
         text_u8 = text_u8.contiguous()
     doc_off, doc_len = doc_off.contiguous(), doc_len.contiguous()
     torch.cuda.current_stream(text_u8.device).synchronize()
-    return text_u8, doc_off, doc_len
+    # (an empty tensor has no address: the library wants one for every array of a non-empty corpus)
+    text_addr = text_u8.data_ptr() if text_u8.numel() else doc_len.data_ptr()
+    return text_u8, doc_off, doc_len, text_addr, int(doc_len.numel())
+
+
+def _status_addr(status, doc_len):
+    """The address of the optional per-document ``status`` tensor (int32 [n], CUDA, contiguous), or None."""
+    import torch
+    if status is None:
+        return None
+    assert status.is_cuda and status.dtype == torch.int32 and status.shape == doc_len.shape and status.is_contiguous()
+    return status.data_ptr()
+
+
+def _tfidf_of(vectorizer):
+    """The :class:`Tfidf` behind a :class:`Preprocessor`, or the :class:`Tfidf` itself."""
+    return vectorizer.vectorizer if isinstance(vectorizer, Preprocessor) else vectorizer
 
 
 def tfidf_counts_device(vectorizer, model, text_u8, doc_off, doc_len, status=None, stream=None):
@@ -204,33 +220,21 @@ def tfidf_counts_device(vectorizer, model, text_u8, doc_off, doc_len, status=Non
     (gaps, overlaps and any order are fine).  Returns a query handle (``clib.freeing`` / ``clib.queries_download``) holding the hstacked CSR
     of term COUNTS, equal to ``clib.tfidf_counts`` of the same documents.  ``status``: optional int32 [n] CUDA tensor that takes each
     document's status (0 fine; 1 / 2: not decodable in parallel, row left empty) instead of a RuntimeError."""
-    import torch
-    if isinstance(vectorizer, Preprocessor):
-        vectorizer = vectorizer.vectorizer
-    text_u8, doc_off, doc_len = _device_text(text_u8, doc_off, doc_len)
-    if status is not None:
-        assert status.is_cuda and status.dtype == torch.int32 and status.shape == doc_len.shape and status.is_contiguous()
-    n = int(doc_len.numel())
-    # (an empty tensor has no address: the library wants one for every array of a non-empty corpus)
-    text_addr = text_u8.data_ptr() if text_u8.numel() else doc_len.data_ptr()
-    return clib.tfidf_counts_device(vectorizer.model, model.model.model_chain, text_addr, doc_off.data_ptr(), doc_len.data_ptr(), n,
-                                    status.data_ptr() if status is not None else None, stream=stream)
+    text_u8, doc_off, doc_len, text_addr, n = _device_text(text_u8, doc_off, doc_len)
+    return clib.tfidf_counts_device(_tfidf_of(vectorizer).model, model.model.model_chain, text_addr, doc_off.data_ptr(), doc_len.data_ptr(), n,
+                                    _status_addr(status, doc_len), stream=stream)
 
 
 def predict_text_from_torch(vectorizer, model, text_u8, doc_off, doc_len, beam_size=None, only_topk=None, post_processor=None, stream=None):
     """Text that is already in HBM (tensors as for :func:`tfidf_counts_device`) -> term counts (K9) -> tf-idf weighting (K5) -> beam search,
     with no host copy of the text, of X or of the result: returns (labels, scores, counts) CUDA tensors like :func:`predict_from_torch`."""
     import torch
-    if isinstance(vectorizer, Preprocessor):
-        vectorizer = vectorizer.vectorizer
     h = model.model.model_chain
-    text_u8, doc_off, doc_len = _device_text(text_u8, doc_off, doc_len)
-    rows = int(doc_len.numel())
+    text_u8, doc_off, doc_len, text_addr, rows = _device_text(text_u8, doc_off, doc_len)
     k = clib.effective_topk(h, only_topk)
     idx, sc, cnt = result_buffers(rows, k, doc_len.device, sync=True)
     s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-    text_addr = text_u8.data_ptr() if text_u8.numel() else doc_len.data_ptr()
-    q = clib.tfidf_predict_device_text(vectorizer.model, h, text_addr, doc_off.data_ptr(), doc_len.data_ptr(), rows, stream=s or None)
+    q = clib.tfidf_predict_device_text(_tfidf_of(vectorizer).model, h, text_addr, doc_off.data_ptr(), doc_len.data_ptr(), rows, stream=s or None)
     with clib.freeing(q):
         if rows:
             clib.predict_device(h, q, beam_size, post_processor, only_topk, idx.data_ptr(), sc.data_ptr(), cnt.data_ptr(), k, stream=s or None, sync=True)
@@ -240,27 +244,18 @@ def predict_text_from_torch(vectorizer, model, text_u8, doc_off, doc_len, beam_s
 def tfidf_train_device(text_u8, doc_off, doc_len, config, device=None, stream=None):
     """Train a :class:`Tfidf` on documents whose bytes are already in HBM (K15; tensors as for :func:`tfidf_counts_device`): the text never
     visits the host.  ``config`` as for :meth:`Tfidf.train`; ``device`` defaults to the tensors' device."""
-    text_u8, doc_off, doc_len = _device_text(text_u8, doc_off, doc_len)
+    text_u8, doc_off, doc_len, text_addr, n = _device_text(text_u8, doc_off, doc_len)
     dev = text_u8.device.index if device is None else int(device)
     assert dev == text_u8.device.index, "the text must live on the training device"
-    n = int(doc_len.numel())
-    text_addr = text_u8.data_ptr() if text_u8.numel() else doc_len.data_ptr()
     return Tfidf(clib.tfidf_train_device(dev, text_addr, doc_off.data_ptr(), doc_len.data_ptr(), n, Tfidf._full_config(config), stream=stream))
 
 
 def tfidf_transform_device(vectorizer, text_u8, doc_off, doc_len, status=None, stream=None):
     """Text in HBM -> the weighted X as a :class:`DeviceMatrix` on the text's device (K9 + the weighting tail): what ``Tfidf.predict``
     returns, resident, with no XR-Linear model needed -- the X of a training pipeline.  ``status`` as for :func:`tfidf_counts_device`."""
-    import torch
-    if isinstance(vectorizer, Preprocessor):
-        vectorizer = vectorizer.vectorizer
-    text_u8, doc_off, doc_len = _device_text(text_u8, doc_off, doc_len)
-    if status is not None:
-        assert status.is_cuda and status.dtype == torch.int32 and status.shape == doc_len.shape and status.is_contiguous()
-    n = int(doc_len.numel())
-    text_addr = text_u8.data_ptr() if text_u8.numel() else doc_len.data_ptr()
-    return DeviceMatrix(clib.tfidf_transform_device(vectorizer.model, text_u8.device.index, text_addr, doc_off.data_ptr(), doc_len.data_ptr(), n,
-                                                    status.data_ptr() if status is not None else None, stream=stream))
+    text_u8, doc_off, doc_len, text_addr, n = _device_text(text_u8, doc_off, doc_len)
+    return DeviceMatrix(clib.tfidf_transform_device(_tfidf_of(vectorizer).model, text_u8.device.index, text_addr, doc_off.data_ptr(), doc_len.data_ptr(), n,
+                                                    _status_addr(status, doc_len), stream=stream))
 
 
 class Tfidf:
@@ -328,9 +323,8 @@ class Tfidf:
     def predict_device(self, xlinear_model, corpus, threads=-1, tokenizer="host"):
         """Texts -> X resident on ``xlinear_model``'s GPU: a query handle (to be freed: ``clib.freeing``) for ``clib.predict_device``.
         ``tokenizer="host"`` counts the terms on host threads and uploads the counts; ``"device"`` uploads the text and counts on the GPU (K9)."""
-        if tokenizer == "host":              # (the call as it always was)
-            return clib.tfidf_predict_device(self.model, xlinear_model.model.model_chain, corpus, threads)
-        return clib.tfidf_predict_device(self.model, xlinear_model.model.model_chain, corpus, threads, tokenizer=tokenizer)
+        extra = {} if tokenizer == "host" else {"tokenizer": tokenizer}      # (the default call stays the call as it always was)
+        return clib.tfidf_predict_device(self.model, xlinear_model.model.model_chain, corpus, threads, **extra)
 
 
 class Preprocessor:

@@ -3,6 +3,7 @@ the live compiled reference, the idf expression pinned by the reference's in-mem
 rounding of the df-ratio products, every refusal the arguments alone decide, the Python config handling, and the exported symbols."""
 import copy
 import ctypes
+import json
 import math
 import os
 import sys
@@ -221,6 +222,34 @@ def test_a_folder_without_the_training_keys_is_saved_with_the_reference_defaults
         assert b["config"]["kwargs"][k] == Tfidf.DEFAULTS[k], k
     assert b["config"]["kwargs"]["max_df_ratio"] == 1.0
     assert (b["vocab"], b["ngrams"], b["idf_text"]) == ({b"a": 0, b"bb": 1}, {(0,): 0, (0, 1): 1}, {0: "1.500000", 1: "0.250000"})
+
+
+GOLDEN_MODELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tfidf_models")
+
+
+@pytest.mark.parametrize("name", sorted(os.listdir(GOLDEN_MODELS)))
+def test_a_loaded_folder_saves_to_the_reference_bytes_and_loads_back(name, tmp_path):
+    # load -> save -> load needs no GPU.  The golden folders were written by the reference: the json files of the saved folder are theirs
+    # byte for byte (key order, indentation, floats, no trailing newline), and both handles export the same content
+    from pecos_amd import clib
+    from pecos_amd.features import Tfidf
+    src, dst = os.path.join(GOLDEN_MODELS, name, "model"), str(tmp_path / "saved")
+    a = Tfidf.load(src)
+    a.save(dst)
+    b = Tfidf.load(dst)
+    nb = json.load(open(os.path.join(src, "meta.json")))["kwargs"]["num_base_vect"]
+    files = ["meta.json"] + [f"{i}.base/{part}/config.json" for i in range(nb) for part in ("tokenizer", "vectorizer")]
+    for f in files:
+        assert open(os.path.join(dst, f), "rb").read() == open(os.path.join(src, f), "rb").read(), f
+    assert a.nr_features == b.nr_features
+    for i in range(nb):
+        (va, ga, ia), (vb, gb, ib) = clib.tfidf_export(a.model, i), clib.tfidf_export(b.model, i)
+        assert va == vb and ga == gb and len(va) > 0 and len(ga) > 0, (name, i)
+        assert np.array_equal(ia.view(np.uint32), ib.view(np.uint32)), (name, i)
+        # the content is the golden folder's own: every token of its vocab.txt with its index
+        lines = open(os.path.join(src, f"{i}.base", "tokenizer", "vocab.txt"), "rb").read().split(b"\n")[1:]
+        want = {t: int(k) for k, t in (ln.split(b"\t", 1) for ln in lines if b"\t" in ln) if t}
+        assert va == want, (name, i)
 
 
 # ---- the Python layer
