@@ -504,7 +504,15 @@ int xrl_debug_spgemm_forms(uint64_t* out, uint32_t n);
  *      half by id; the node stops when its first half is what it was before the sort;
  *   3. the node's children are the midpoint split of its whole range; a level that sampled scores and sorts the whole range once more
  *      with the last centre.
- * label_codes[elements[i]] = the leaf that owns position i.  Non-finite feature values are not pinned.
+ * label_codes[elements[i]] = the leaf that owns position i.
+ * Range.  Finite feature values are served by the rule, whatever leaves fp32's range on the way, for as long as no centre entry and no
+ * score of any iteration of any node is a NaN.  A product, a sum or a norm that overflows is +-inf as the reference's: ||c||^2 = +inf is
+ * positive, its scale is 1.0 / sqrt(inf) = 0.0, every finite entry of that half's centre becomes +-0 (both halves: the centre is zeros,
+ * every score ties at 0 and the id splits the range); scores of +inf tie with each other, as do scores of -inf, and the id decides among
+ * them.  ||c||^2 that is a positive subnormal scales like any other; ||c||^2 whose every square underflows is 0 and the centre is not
+ * scaled.  Subnormal products and sums are kept.  Finite inputs that do produce a NaN (inf - inf in a centre or a score chain, 0 * inf
+ * under an infinite norm) are as unpinned as non-finite feature values: the split's order (a < b, or a == b and the lower id) is no
+ * strict weak order over a NaN and the reference's std::sort has no defined answer.  Neither is refused.
  * Refused before a GPU is required (messages start with the function's name): null pointers; 2^depth > rows; depth > 30; a sampled
  * node of fewer than 2 elements; the reference's invalid rates (0 < min <= max <= 1, 0 <= warmup_ratio <= 1); a partition_algo other
  * than 0 or 5.  Refused by a check kernel: a row whose column ids are not strictly ascending, or an id >= cols.  Scratch is one level

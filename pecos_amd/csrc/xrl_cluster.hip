@@ -239,7 +239,8 @@ __global__ void __launch_bounds__(256) k11_norm_segs(const uint32_t* __restrict_
 }
 
 // One wavefront per (side, node): ||c||^2 as one fp32 chain of c[f] * c[f] (matrix.hpp:862-868, or :886-897 past the switch), then the
-// scale 1.0 / sqrt((double)||c||^2) when it is positive (clustering.hpp:375-384); 0 stands for "not scaled".
+// scale 1.0 / sqrt((double)||c||^2) when it is positive (clustering.hpp:375-384).  A chain that overflows to +inf is positive: its scale
+// is 1.0 / inf = 0.0 and the centre becomes zeros, as the reference's does.  -1 stands for "not scaled": a real scale is never negative.
 __global__ void __launch_bounds__(256) k11_norm(K11Level a, const uint64_t* __restrict__ order /* null: run order */, double* __restrict__ scale) {
     const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (w >= 2 * a.nodes) return;
@@ -255,7 +256,7 @@ __global__ void __launch_bounds__(256) k11_norm(K11Level a, const uint64_t* __re
         const uint32_t n = min(64u, e - x0);
         acc = wave_chain(acc, p, n);
     }
-    if (lane == 0) scale[w] = acc > 0.0f ? 1.0 / sqrt((double)acc) : 0.0;
+    if (lane == 0) scale[w] = acc > 0.0f ? 1.0 / sqrt((double)acc) : -1.0;
 }
 
 // c = c1 * s1 - c2 * s2, each scaled value the double product rounded to float (matrix.hpp:1027-1047), the difference c1 + (-c2)
@@ -266,8 +267,8 @@ __global__ void __launch_bounds__(256) k11_combine(K11Level a, const double* __r
     if (!a.active[nd]) return;
     const double s1 = scale[nd], s2 = scale[a.nodes + nd];
     float c1 = a.c[r], c2 = a.c2[r];
-    if (s1 != 0.0) c1 = (float)((double)c1 * s1);
-    if (s2 != 0.0) c2 = (float)((double)c2 * s2);
+    if (s1 >= 0.0) c1 = (float)((double)c1 * s1);
+    if (s2 >= 0.0) c2 = (float)((double)c2 * s2);
     a.c[r] = __fadd_rn(c1, -c2);
 }
 

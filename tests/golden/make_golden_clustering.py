@@ -1,7 +1,9 @@
 """Records tests/golden/clustering_ref.npz and clustering_chains.npz from the compiled reference (oracle/_ref, threads = 1):
 the reference's codes of every case of tests/clustering_rule.py (CSR, and dense where the case is small), and the chains of the
 reference's HierarchicalKMeans.gen for a handful of parameter sets.  ``--search`` looks for near-duplicate seeds on which the order
-preconditions hold (tests/test_clustering_cpu.py asserts them).  Run from the repository root where the reference is built."""
+preconditions hold (tests/test_clustering_cpu.py asserts them).  ``range_edges`` writes clustering_range_edges.npz alone: the reference's
+codes of clustering_rule.range_edge_cases() and of the widest-ids case renumbered into 2^24 columns, each run twice and required equal.
+Run from the repository root where the reference is built."""
 import os
 import sys
 
@@ -56,6 +58,21 @@ def record_chains(path):
     np.savez_compressed(path, **out)
 
 
+def record_range_edges(path):
+    out = {}
+
+    def twice(X, depth, kw):
+        a, b = cr.reference(X, depth, **kw), cr.reference(X, depth, **kw)
+        assert np.array_equal(a, b), "the reference answered differently the second time"
+        return a
+    for name, (X, depth, kw) in cr.range_edge_cases().items():
+        out[name + "__csr"] = twice(X, depth, kw)
+        if cr.dense_ok(X):
+            out[name + "__drm"] = twice(X.toarray(), depth, kw)
+    out["wide_ids_2p24__csr"] = twice(cr.wide_ids(1 << 24), cr.WIDE_IDS_DEPTH, cr.WIDE_IDS_KW)
+    np.savez_compressed(path, **out)
+
+
 def search(algo, seeds=range(0, 40)):
     for s in seeds:
         X = cr.near_duplicate(seed=s)
@@ -72,6 +89,8 @@ def search(algo, seeds=range(0, 40)):
 if __name__ == "__main__":
     if "--search" in sys.argv:
         print({a: search(a) for a in (cr.SKMEANS, cr.KMEANS)})
+    elif "range_edges" in sys.argv:
+        record_range_edges(os.path.join(HERE, "clustering_range_edges.npz"))
     else:
         record_codes(os.path.join(HERE, "clustering_ref.npz"))
         record_chains(os.path.join(HERE, "clustering_chains.npz"))

@@ -1,6 +1,8 @@
 """The CPU half of the label clustering (K11): the numpy statement of the rule (tests/clustering_rule.py) against the compiled reference at
 threads = 1 on every case of the GPU half, sampled ones included; the host plan (xrl_debug_cluster_plan) against the statement's draws;
-the order preconditions of the near-duplicate cases, without which those cases pin nothing; every refusal that needs no GPU;
+the order preconditions of the near-duplicate cases, without which those cases pin nothing; the range-edge cases (statement against the
+recording, what each claims, no NaN in any iteration, the unscaled-centre variant changes their codes) and the widest column ids
+renumbered into 2^24 columns at the reference; every refusal that needs no GPU;
 TrainParams, depth inference and the chain builder against the recorded goldens; the reference's link_clustering prototypes."""
 import ctypes
 import os
@@ -89,6 +91,161 @@ def test_near_duplicate_cases_pin_the_order(tag, algo):
 def test_plain_random_data_pins_no_order():
     X, depth, kw = CASES["rand300_sk_s0"]
     assert np.array_equal(cr.statement(X, depth, variant="reverse_walk", **kw)["codes"], truth("rand300_sk_s0")["codes"])
+
+
+# ------------------------------------------------------------------------------------------------ the range edges
+EDGES = cr.range_edge_cases()
+EDGES_RECORDED = np.load(os.path.join(GOLDEN, "clustering_range_edges.npz"))
+FLT_MIN = float(np.finfo(np.float32).tiny)
+_edge_truth = {}
+
+
+def edge_truth(name):
+    if name not in _edge_truth:
+        X, depth, kw = EDGES[name]
+        _edge_truth[name] = cr.statement(X, depth, trace=True, **kw)
+    return _edge_truth[name]
+
+
+def test_range_edge_cases_are_small():
+    for name, (X, depth, kw) in EDGES.items():
+        assert X.shape[0] <= 128 and depth <= 4, name
+        assert np.all(np.isfinite(X.data)), name
+
+
+@pytest.mark.parametrize("name", sorted(EDGES))
+def test_range_edge_statement_equals_the_reference(name):
+    X, depth, kw = EDGES[name]
+    assert np.array_equal(edge_truth(name)["codes"], EDGES_RECORDED[name + "__csr"]), "the statement differs from the recorded reference"
+    if HAVE_REF:
+        assert np.array_equal(edge_truth(name)["codes"], cr.reference(X, depth, **kw)), "the statement differs from the live reference"
+
+
+@pytest.mark.parametrize("name", sorted(n for n, c in EDGES.items() if cr.dense_ok(c[0]) and c[0].shape[0] * c[0].shape[1] <= 200_000))
+def test_range_edge_statement_equals_the_reference_dense(name):
+    X, depth, kw = EDGES[name]
+    D = np.ascontiguousarray(X.toarray())
+    got = cr.statement(cr.as_full_csr(D), depth, **kw)["codes"]
+    assert np.array_equal(got, EDGES_RECORDED[name + "__drm"])
+    if HAVE_REF:
+        assert np.array_equal(got, cr.reference(D, depth, **kw))
+
+
+@pytest.mark.parametrize("name", sorted(EDGES))
+def test_range_edge_cases_meet_no_nan(name):
+    """The contract's condition, a property of the inputs: no centre entry, no norm and no score of any iteration of any node is a NaN.
+    A case that fails this is outside the contract: redraw it."""
+    bad = {k: v["nans"] for k, v in edge_truth(name)["trace"].items() if v["nans"]}
+    assert not bad, f"{name}: NaNs at (node, iteration) {bad}"
+
+
+def _level(nid):
+    return nid.bit_length() - 1
+
+
+def _scored(t, key):
+    s, we, _, _ = t["work"][key[0]]
+    return we - s
+
+
+@pytest.mark.parametrize("name", sorted(EDGES))
+def test_range_edge_cases_hold_what_they_claim(name):
+    """Every case meets, somewhere in the statement's trace, the edge it is named after.  Under KMEANS there is no norm: the cases named
+    after one run the same inputs, and the claim is where their scores sit in fp32's range."""
+    X, depth, kw = EDGES[name]
+    t = edge_truth(name)
+    tr = t["trace"]
+    sk = kw["algo"] == cr.SKMEANS
+    kind = name.rsplit("_", 1)[0]
+    finite = np.abs(t["scores"][np.isfinite(t["scores"])]).astype(np.float64)
+    both = [k for k, v in tr.items() if v["inf_sides"] == "RL"]
+    if "first_touch" in kind:
+        assert all(t["first_touch"]), "not in first-touch order from the root"
+    elif "dense" in kind:
+        assert not any(t["first_touch"]), "the norm order switches"
+    if not sk and kind in ("collapse_dense", "collapse_first_touch", "one_half", "one_half_first_touch", "late_dense", "late_first_touch"):
+        assert finite.max() > 1e35 and not any(v["inf_scores"] for v in tr.values())
+        return
+    if not sk and kind in ("subnormal_norm", "zero_norm"):
+        assert 0 < finite[finite > 0].min() < FLT_MIN or (kind == "zero_norm" and (t["scores"] == 0).any())
+        return
+    if kind in ("collapse_dense", "collapse_first_touch", "all_but_first_centre"):
+        assert both and sum(v["zeroed"] for v in tr.values()) >= 2 * len(both)
+        assert not any(v["inf_scores"] for v in tr.values())
+    elif kind in ("inf_scores_dense", "inf_scores_first_touch"):
+        assert sum(v["inf_scores"] for v in tr.values()) > 0
+        assert not sk or both
+    elif kind in ("one_half", "one_half_first_touch"):
+        assert [k for k, v in tr.items() if v["inf_sides"] == "R"] and [k for k, v in tr.items() if v["inf_sides"] == "L"]
+        assert tr[(1, 1)]["inf_norms"] == 1, "the root's first split is not the block against the rest"
+        for d in (1, 2):        # the scale is per node and side: some nodes of the level overflow and some do not
+            per_node = {nid: sum(v["inf_norms"] for k, v in tr.items() if k[0] == nid) for nid in range(1 << d, 2 << d)}
+            assert any(per_node.values()) and not all(per_node.values()), f"level {d}: {per_node}"
+    elif kind in ("late_dense", "late_first_touch"):
+        late = [k for k, v in tr.items() if v["runs"] >= 64 and any(a is not None and a >= 64 for a in v["inf_at"])]
+        assert late, "no norm overflows past the 64th term of its chain"
+    elif kind == "inf_ties":
+        assert [k for k, v in tr.items() if v["id_decides"] and v["pos_inf"] and v["neg_inf"]], "no node with +inf and -inf and the id deciding"
+        if not sk:
+            assert [k for k, v in tr.items() if v["pos_inf"] == _scored(t, k)], "no node whose scores are all +inf"
+            assert [k for k, v in tr.items() if v["neg_inf"] == _scored(t, k)], "no node whose scores are all -inf"
+            assert np.all(np.isinf(t["scores"]))
+    elif kind == "subnormal_norm":
+        sub = [a for v in tr.values() if v["norms"] for a in v["norms"] if 0 < a < FLT_MIN]
+        assert sub and max(1.0 / np.sqrt(np.float64(a)) for a in sub) > 1e20
+    elif kind == "zero_norm":
+        assert [k for k, v in tr.items() if v.get("zero_norm_sides")]
+    elif kind == "sampled":
+        whole = [k for k in tr if k[1] == "whole"]
+        assert len(whole) == (1 << depth) - 1, "a level is not sampled"
+        assert all(_scored(t, k) == (X.shape[0] >> _level(k[0])) // 2 for k in whole), "a node does not work on half of its range"
+        if sk:
+            assert sum(v["zeroed"] for v in tr.values()) > 0
+        else:
+            assert sum(v["inf_scores"] for v in tr.values()) > 0 and sum(tr[k]["inf_scores"] for k in whole) > 0
+    else:
+        raise AssertionError(f"{name}: a case without a claim")
+
+
+@pytest.mark.parametrize("name", sorted(n for n, c in EDGES.items() if c[2]["algo"] == cr.SKMEANS
+                                        and n.rsplit("_", 1)[0] not in ("subnormal_norm", "zero_norm")))
+def test_unscaled_on_inf_changes_the_codes(name):
+    """Keeping the summed centre of a half whose norm is infinite, where the rule zeroes it, changes codes on every SKMEANS case that
+    meets an infinite norm: a device that does so cannot pass them."""
+    X, depth, kw = EDGES[name]
+    assert sum(v["zeroed"] for v in edge_truth(name)["trace"].values()) > 0, "no centre is zeroed by an infinite norm"
+    changed = int((cr.statement(X, depth, variant="unscaled_on_inf", **kw)["codes"] != edge_truth(name)["codes"]).sum())
+    assert changed >= 1, "worthless case: the unscaled centre changes no code"
+
+
+def test_trace_and_variant_leave_plain_data_alone():
+    X, depth, kw = CASES["rand300_sk_s0"]
+    t = cr.statement(X, depth, trace=True, variant="unscaled_on_inf", **kw)
+    assert np.array_equal(t["codes"], truth("rand300_sk_s0")["codes"]) and np.array_equal(t["scores"], truth("rand300_sk_s0")["scores"])
+    assert not any(v["inf_norms"] or v["inf_scores"] or v["nans"] or v["zeroed"] for v in t["trace"].values())
+
+
+def test_widest_ids_renumbering_leaves_the_codes():
+    """The column ids enter the rule through their order and the first-touch switch only: the compact matrix under a strictly increasing
+    renumbering into 2^24 columns has, at the reference, the codes the statement gives the compact matrix in first-touch order from
+    the root (nnz=0).  The reference cannot hold a centre of 2^32 - 1 columns; the device is compared with the same statement."""
+    from pecos_amd import clib
+    from pecos_amd.core import ClusteringParam
+    compact, depth, kw = cr.wide_ids(), cr.WIDE_IDS_DEPTH, cr.WIDE_IDS_KW
+    t = cr.statement(compact, depth, nnz=0, **kw)
+    assert all(t["first_touch"])
+    other = cr.statement(compact, depth, nnz=0, variant="ascending_norm", **kw)
+    assert not np.array_equal(t["codes"], other["codes"]), "the norm order changes no code: the case pins no order"
+    assert np.array_equal(t["codes"], EDGES_RECORDED["wide_ids_2p24__csr"])
+    if HAVE_REF:
+        assert np.array_equal(cr.reference(cr.wide_ids(1 << 24), depth, **kw), t["codes"])
+    wide = cr.wide_ids(0xFFFFFFFF)
+    assert wide.shape == (600, 0xFFFFFFFF) and wide.indices.max() == 0xFFFFFFFE and wide.indices.min() == 0
+    assert np.array_equal(np.argsort(wide.indices, kind="stable"), np.argsort(compact.indices, kind="stable")), "the renumbering is not increasing"
+    plan = clib.debug_cluster_plan(wide.shape[0], wide.shape[1], wide.nnz, depth, ClusteringParam(partition_algo=cr.SKMEANS, seed=kw["seed"], kmeans_max_iter=20, threads=1,
+                                                                                                  max_sample_rate=1.0, min_sample_rate=1.0, warmup_ratio=1.0))
+    assert plan["level_info"][:, 1].astype(bool).tolist() == [True] * depth
+    assert np.array_equal(plan["node_seed"], t["node_seed"])
 
 
 # ------------------------------------------------------------------------------------------------ refusals, before a GPU is needed
