@@ -839,6 +839,57 @@ int xrl_hnsw_predict_device(void* handle, uint32_t rows, uint32_t cols, const fl
 int xrl_debug_hnsw_counters(uint64_t* out, uint32_t n, int reset);
 int xrl_debug_hnsw_caps(uint64_t* out, uint32_t n);
 
+/* PairwiseANN on the device (K18, csrc/xrl_pairwise.hip): the reference's pecos::ann::PairwiseANN over X_trn [N, d] and Y_csc [N, L] resident in
+ * HBM.  Pair b = (query row b -- row 0 under is_same_input --, label_keys[b]) scans column label_keys[b] of Y exactly and keeps the only_topk
+ * nearest: row ids, distances (bits), Y values and their order are those of c_pairwise_ann_predict_{csr,drm}_ip_f32 (sparse: on any x86 host;
+ * dense: the reference's avx512f clone).  An entry is a position of the column: a row id stored twice gives two entries, an
+ * explicit zero of Y is an entry.  The names are this library's own on purpose.
+ *   xrl_pairwise_train_{csr,drm}_f32(pX, pY, device, &handle)   uploads X and Y and checks them on the device.  0 / -1 + xrl_last_error.
+ *   xrl_pairwise_from_device(...)      the resident build: X a dense base with row stride (d_x_row_ptr NULL) or CSR arrays, the transpose of Y as
+ *       CSR arrays [num_label rows] in HBM (= Y_csc); copies device to device on hip_stream, runs the same checks, synchronises the stream.
+ *   xrl_pairwise_save(handle, dir)     config.json and index.mmap_store byte for byte as the reference's PairwiseANN::save writes them.
+ *   xrl_pairwise_load(dir, device, &handle) / xrl_pairwise_check_folder(dir, out, n)   the reader, the second without a GPU: "Inconsistent
+ *       PairwiseANN_T: ..." for another pairwise_ann_t, "Unable to load memory-mapped file with version = ..." for a version other than v1.0,
+ *       and the build's refusals, checked on the host.  out as xrl_pairwise_info.
+ *   xrl_pairwise_info(handle, out, n)  out[0..n), n <= 8 <- {num_input_keys, num_label_keys, feat_dim, data type (0 csr, 1 drm), nnz of Y, nnz of
+ *       X, the longest column of Y, bytes held in HBM}.
+ *   xrl_pairwise_searchers_create(handle, n)   n wavefront slots (at most 2048, cut so that their HBM scratch -- 12 bytes per entry of the longest
+ *       column, none if no column is above CAP -- stays within 1 GiB).  One call at a time, as K17's.
+ *   xrl_pairwise_predict_{csr,drm}_f32 the reference's argument list on host arrays (searchers may be NULL: scratch of the call).  Pair b writes
+ *       its min(column length, only_topk) entries at b * only_topk + k: Imat row id, Mmat 1, Dmat distance, Vmat the Y value, nearest first;
+ *       the cells after them are not touched.  only_topk == 0 writes nothing.
+ *   xrl_pairwise_predict_device        the resident form: queries (dense with q_row_stride, or a CSR triple), label keys and the four outputs in
+ *       HBM, output row stride out_stride >= only_topk, on hip_stream, one synchronisation at the end.
+ *   Refused by name, outputs and index unchanged: X.rows != Y.rows ("X_trn.rows != Y_csc.rows"), a Y row id >= X.rows, column pointers of Y that
+ *   are not ascending, unsorted or repeated ids in a sparse row of X_trn or of the queries, a column id >= feat_dim, a non-finite value of X_trn
+ *   or of the queries, a label key >= num_label_keys, queries without a row under is_same_input, otherwise a row count other than batch_size,
+ *   the wrong data type or width, out_stride < only_topk, searchers of another index or in use.
+ *   xrl_debug_pairwise_counters(out, n, reset)   FOR TESTS: out[0..n), n <= 6 <- {pairs served by the sorted form, by the stream form, by the
+ *       replay form, distance evaluations, second passes (a stream-form pair whose distances were computed again for the replay), the longest
+ *       column met}, since the last reset.
+ *   xrl_debug_pairwise_caps(out, n)    out[0..n), n <= 4 <- {CAP, KEEP, the floats of a query staged in LDS, the largest slot count} */
+int xrl_pairwise_train_csr_f32(const ScipyCsrF32* pX, const ScipyCscF32* pY, int device, void** handle);
+int xrl_pairwise_train_drm_f32(const ScipyDrmF32* pX, const ScipyCscF32* pY, int device, void** handle);
+int xrl_pairwise_from_device(int device, uint32_t num_input, uint32_t num_label, uint32_t feat_dim, const float* d_x_val, uint64_t x_row_stride, const uint64_t* d_x_row_ptr,
+                             const uint32_t* d_x_col_idx, uint64_t x_nnz, const uint64_t* d_yt_row_ptr, const uint32_t* d_yt_col_idx, const float* d_yt_val, uint64_t y_nnz,
+                             void* hip_stream, void** handle);
+int xrl_pairwise_load(const char* model_dir, int device, void** handle);
+int xrl_pairwise_check_folder(const char* model_dir, uint64_t* out, uint32_t n);
+int xrl_pairwise_save(void* handle, const char* model_dir);
+void xrl_pairwise_destruct(void* handle);
+int xrl_pairwise_info(void* handle, uint64_t* out, uint32_t n);
+void* xrl_pairwise_searchers_create(void* handle, uint32_t num_searcher);
+void xrl_pairwise_searchers_destruct(void* searchers);
+int xrl_pairwise_predict_csr_f32(void* handle, void* searchers, uint32_t batch_size, uint32_t only_topk, const ScipyCsrF32* pQ, const uint32_t* label_keys, uint32_t* Imat,
+                                 uint32_t* Mmat, float* Dmat, float* Vmat, int is_same_input);
+int xrl_pairwise_predict_drm_f32(void* handle, void* searchers, uint32_t batch_size, uint32_t only_topk, const ScipyDrmF32* pQ, const uint32_t* label_keys, uint32_t* Imat,
+                                 uint32_t* Mmat, float* Dmat, float* Vmat, int is_same_input);
+int xrl_pairwise_predict_device(void* handle, void* searchers, uint32_t batch_size, uint32_t only_topk, uint32_t q_rows, uint32_t q_cols, const float* d_q_val,
+                                uint64_t q_row_stride, const uint64_t* d_q_row_ptr, const uint32_t* d_q_col_idx, uint64_t q_nnz, const uint32_t* d_label_keys, uint32_t* d_Imat,
+                                uint32_t* d_Mmat, float* d_Dmat, float* d_Vmat, uint64_t out_stride, int is_same_input, void* hip_stream);
+int xrl_debug_pairwise_counters(uint64_t* out, uint32_t n, int reset);
+int xrl_debug_pairwise_caps(uint64_t* out, uint32_t n);
+
 /* predict_on_selected_outputs on the device (K7 + K4): score a given set of labels per query row through the tree, with labels, plan and
  * scores resident in HBM.  The labels arrive in the fixed-stride form xrl_predict_device writes and xrl_ensemble_device reads: row r is
  * d_sel_idx[r*sel_stride ..], d_sel_cnt[r] entries long (NULL = sel_stride each; a count above the stride is read as the stride), in any

@@ -369,6 +369,25 @@ class corelib(object):
                                             c_void_p, c_uint64, c_void_p, c_void_p]),
         "xrl_debug_hnsw_counters": (c_int, [POINTER(c_uint64), c_uint32, c_int]),
         "xrl_debug_hnsw_caps": (c_int, [POINTER(c_uint64), c_uint32]),
+        "xrl_pairwise_train_csr_f32": (c_int, [POINTER(ScipyCsrF32), POINTER(ScipyCscF32), c_int, POINTER(c_void_p)]),
+        "xrl_pairwise_train_drm_f32": (c_int, [POINTER(ScipyDrmF32), POINTER(ScipyCscF32), c_int, POINTER(c_void_p)]),
+        "xrl_pairwise_from_device": (c_int, [c_int, c_uint32, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p,
+                                             c_uint64, c_void_p, POINTER(c_void_p)]),
+        "xrl_pairwise_load": (c_int, [c_char_p, c_int, POINTER(c_void_p)]),
+        "xrl_pairwise_check_folder": (c_int, [c_char_p, POINTER(c_uint64), c_uint32]),
+        "xrl_pairwise_save": (c_int, [c_void_p, c_char_p]),
+        "xrl_pairwise_destruct": (None, [c_void_p]),
+        "xrl_pairwise_info": (c_int, [c_void_p, POINTER(c_uint64), c_uint32]),
+        "xrl_pairwise_searchers_create": (c_void_p, [c_void_p, c_uint32]),
+        "xrl_pairwise_searchers_destruct": (None, [c_void_p]),
+        "xrl_pairwise_predict_csr_f32": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, POINTER(ScipyCsrF32), POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32),
+                                                 POINTER(c_float), POINTER(c_float), c_int]),
+        "xrl_pairwise_predict_drm_f32": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, POINTER(ScipyDrmF32), POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32),
+                                                 POINTER(c_float), POINTER(c_float), c_int]),
+        "xrl_pairwise_predict_device": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_void_p]),
+        "xrl_debug_pairwise_counters": (c_int, [POINTER(c_uint64), c_uint32, c_int]),
+        "xrl_debug_pairwise_caps": (c_int, [POINTER(c_uint64), c_uint32]),
         "xrl_inspect_model": (c_int, [c_char_p, POINTER(c_uint64), c_uint32]),
         "xrl_model_create": (c_void_p, [c_uint32, c_void_p, c_void_p, POINTER(c_float), POINTER(c_uint32), POINTER(c_char_p)]),
         "xrl_queries_upload_csr": (c_void_p, [c_void_p, POINTER(ScipyCsrF32)]),
@@ -930,6 +949,91 @@ class corelib(object):
         out = (c_uint64 * 4)()
         self.clib_float32.xrl_debug_hnsw_caps(out, 4)
         return dict(zip(("CAP", "cand_cap", "lds_degree", "max_slots"), (int(v) for v in out)))
+
+    # ------------------------------------------------------------------ PairwiseANN (K18)
+    PAIRWISE_INFO = ("num_input_keys", "num_label_keys", "feat_dim", "data_type", "nnz_of_Y", "nnz_of_X", "max_col", "device_bytes")
+    PAIRWISE_COUNTERS = ("sorted", "stream", "replay", "dist", "second_pass", "max_col")
+
+    def _pairwise_info(self, out):
+        d = dict(zip(self.PAIRWISE_INFO, (int(v) for v in out)))
+        d["data_type"] = ("csr", "drm")[d["data_type"]]
+        return d
+
+    def pairwise_train(self, pX, data_type, pY, device=0):
+        """``xrl_pairwise_train_{csr,drm}_f32``: X_trn and Y_csc into HBM, checked there -> handle."""
+        h = c_void_p()
+        getattr(self.clib_float32, "xrl_pairwise_train_%s_f32" % data_type)(byref(pX), byref(pY), int(device), byref(h))
+        self._check()
+        return h
+
+    def pairwise_from_device(self, device, num_input, num_label, feat_dim, x_val, x_stride, x_row_ptr, x_col_idx, x_nnz, yt_row_ptr, yt_col_idx, yt_val, y_nnz, stream=None):
+        """``xrl_pairwise_from_device``: the index from arrays in HBM (addresses; ``x_row_ptr`` 0 for a dense X) -> handle."""
+        h = c_void_p()
+        self.clib_float32.xrl_pairwise_from_device(int(device), num_input, num_label, feat_dim, c_void_p(x_val or 0), x_stride, c_void_p(x_row_ptr or 0),
+                                                   c_void_p(x_col_idx or 0), x_nnz, c_void_p(yt_row_ptr or 0), c_void_p(yt_col_idx or 0), c_void_p(yt_val or 0), y_nnz,
+                                                   c_void_p(stream or 0), byref(h))
+        self._check()
+        return h
+
+    def pairwise_load(self, c_model_dir, device=0):
+        h = c_void_p()
+        self.clib_float32.xrl_pairwise_load(self._cstr(c_model_dir), int(device), byref(h))
+        self._check()
+        return h
+
+    def pairwise_check_folder(self, c_model_dir):
+        """The reader's refusals without a GPU (``xrl_pairwise_check_folder``) -> the info dictionary."""
+        out = (c_uint64 * 8)()
+        self.clib_float32.xrl_pairwise_check_folder(self._cstr(c_model_dir), out, 8)
+        self._check()
+        return self._pairwise_info(out)
+
+    def pairwise_save(self, h, c_model_dir):
+        self.clib_float32.xrl_pairwise_save(h, self._cstr(c_model_dir))
+        self._check()
+
+    def pairwise_destruct(self, h):
+        self.clib_float32.xrl_pairwise_destruct(h)
+
+    def pairwise_info(self, h):
+        out = (c_uint64 * 8)()
+        self.clib_float32.xrl_pairwise_info(h, out, 8)
+        self._check()
+        return self._pairwise_info(out)
+
+    def pairwise_searchers_create(self, h, num_searcher):
+        p = self.clib_float32.xrl_pairwise_searchers_create(h, int(num_searcher))
+        self._check()
+        return c_void_p(p)
+
+    def pairwise_searchers_destruct(self, p):
+        self.clib_float32.xrl_pairwise_searchers_destruct(p)
+
+    def pairwise_predict(self, h, searchers, batch_size, only_topk, pQ, data_type, label_keys, Imat, Mmat, Dmat, Vmat, is_same_input=False):
+        """``xrl_pairwise_predict_{csr,drm}_f32`` into the caller's four host arrays of batch_size * only_topk entries."""
+        fn = getattr(self.clib_float32, "xrl_pairwise_predict_%s_f32" % data_type)
+        u32, f32 = POINTER(c_uint32), POINTER(c_float)
+        fn(h, searchers, batch_size, only_topk, byref(pQ), label_keys.ctypes.data_as(u32), Imat.ctypes.data_as(u32), Mmat.ctypes.data_as(u32),
+           Dmat.ctypes.data_as(f32), Vmat.ctypes.data_as(f32), 1 if is_same_input else 0)
+        self._check()
+
+    def pairwise_predict_device(self, h, searchers, batch_size, only_topk, q_rows, q_cols, q_val, q_stride, q_row_ptr, q_col_idx, q_nnz, keys, Imat, Mmat, Dmat, Vmat,
+                                out_stride, is_same_input=False, stream=None):
+        self.clib_float32.xrl_pairwise_predict_device(h, searchers, batch_size, only_topk, q_rows, q_cols, c_void_p(q_val or 0), q_stride, c_void_p(q_row_ptr or 0),
+                                                      c_void_p(q_col_idx or 0), q_nnz, c_void_p(keys), c_void_p(Imat), c_void_p(Mmat), c_void_p(Dmat), c_void_p(Vmat),
+                                                      out_stride, 1 if is_same_input else 0, c_void_p(stream or 0))
+        self._check()
+
+    def debug_pairwise_counters(self, reset=False):
+        """Counters of K18 since the last reset (``xrl_debug_pairwise_counters``), by name."""
+        out = (c_uint64 * len(self.PAIRWISE_COUNTERS))()
+        self.clib_float32.xrl_debug_pairwise_counters(out, len(self.PAIRWISE_COUNTERS), 1 if reset else 0)
+        return dict(zip(self.PAIRWISE_COUNTERS, (int(v) for v in out)))
+
+    def debug_pairwise_caps(self):
+        out = (c_uint64 * 4)()
+        self.clib_float32.xrl_debug_pairwise_caps(out, 4)
+        return dict(zip(("CAP", "KEEP", "query_lds", "max_slots"), (int(v) for v in out)))
 
     # ------------------------------------------------------------------ label clustering (K11)
     def run_clustering(self, py_feat_mat, train_params, codes=None):
