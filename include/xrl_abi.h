@@ -839,6 +839,35 @@ int xrl_hnsw_predict_device(void* handle, uint32_t rows, uint32_t cols, const fl
 int xrl_debug_hnsw_counters(uint64_t* out, uint32_t n, int reset);
 int xrl_debug_hnsw_caps(uint64_t* out, uint32_t n);
 
+/* HNSW graph construction on the device (K19, csrc/xrl_hnsw_train.hip): the reference's HNSW::train at threads = 1.  A folder written by
+ * xrl_hnsw_save after one of the trainers has the index.mmap_store and config.json of c_ann_hnsw_train_* -> c_ann_hnsw_save_* on the same items,
+ * byte for byte (sparse: on any x86 host; dense: the reference's avx512f clone).  `threads` is accepted and ignored: the
+ * reference's own graph depends on it through lock timing.  Not pinned: items of which some pairwise distance is a NaN (std::sort has no defined
+ * answer there).  The names are this library's own, never c_ann_hnsw_train_* / _save_* (INTEGRATION.md); the handle is an ordinary index handle
+ * that xrl_hnsw_predict_* serves at once and xrl_hnsw_destruct frees.
+ *   xrl_hnsw_train_{csr,drm}_f32(pX, M, efC, threads, max_level_upper_bound, metric, device, &handle)   from host matrices; metric "ip" / "l2".
+ *   xrl_hnsw_train_device(...)   the items are in HBM on `device`: a dense base d_val with row_stride >= cols (d_row_ptr NULL, smat NULL), CSR
+ *       arrays d_row_ptr u64 [rows + 1], d_col_idx u32, d_val f32 with nnz stored entries, or an xrl_smat handle (then rows .. nnz are taken
+ *       from it).  They are copied device to device into the index's own arrays; runs on hip_stream and synchronises it.
+ *   xrl_hnsw_save(handle, c_model_dir)   any index handle, trained or loaded: downloads the graph and the items, re-interleaves the node
+ *       records and the upper-level table, writes index.mmap_store and config.json (nlohmann::json::dump(4) text) as the reference does.
+ *   Refused by name before a GPU is required: M < 2 (1 / log(M) is not finite at 1), M > 128 (maxM0 above the neighbourhood staged in LDS),
+ *   efC == 0, efC > CAP (1024), no rows, an unknown metric, null arguments, row_stride < cols; by the check kernels: row pointers that are not
+ *   ascending within nnz, unsorted, repeated or out-of-range column ids, a non-finite value.  0 / -1 + xrl_last_error.
+ *   xrl_debug_hnsw_levels(n, M, max_level_upper_bound, out)   FOR TESTS: out[0..n) <- the level of every node as the host plans them (mt19937
+ *       seeded 0, (uint32)(-log(u) * (float)(1 / log(M))), capped when the bound is >= 0); needs no GPU.
+ *   xrl_debug_hnsw_train_counters(out, n, reset)   FOR TESTS: out[0..n), n <= 6 <- {distance evaluations of the searches and descents, of the
+ *       heuristic over a search's result, of the reverse links, neighbour lists rewritten by a reverse link, lists sorted by the rank form, by
+ *       the replay of std::sort}, since the last reset. */
+int xrl_hnsw_train_csr_f32(const ScipyCsrF32* pX, uint32_t M, uint32_t efC, int32_t threads, int32_t max_level_upper_bound, const char* metric, int device, void** handle);
+int xrl_hnsw_train_drm_f32(const ScipyDrmF32* pX, uint32_t M, uint32_t efC, int32_t threads, int32_t max_level_upper_bound, const char* metric, int device, void** handle);
+int xrl_hnsw_train_device(int device, uint32_t rows, uint32_t cols, const float* d_val, uint64_t row_stride, const uint64_t* d_row_ptr, const uint32_t* d_col_idx,
+                          uint64_t nnz, void* smat, uint32_t M, uint32_t efC, int32_t threads, int32_t max_level_upper_bound, const char* metric, void* hip_stream,
+                          void** handle);
+int xrl_hnsw_save(void* handle, const char* c_model_dir);
+int xrl_debug_hnsw_levels(uint32_t n, uint32_t M, int32_t max_level_upper_bound, uint32_t* out);
+int xrl_debug_hnsw_train_counters(uint64_t* out, uint32_t n, int reset);
+
 /* PairwiseANN on the device (K18, csrc/xrl_pairwise.hip): the reference's pecos::ann::PairwiseANN over X_trn [N, d] and Y_csc [N, L] resident in
  * HBM.  Pair b = (query row b -- row 0 under is_same_input --, label_keys[b]) scans column label_keys[b] of Y exactly and keeps the only_topk
  * nearest: row ids, distances (bits), Y values and their order are those of c_pairwise_ann_predict_{csr,drm}_ip_f32 (sparse: on any x86 host;

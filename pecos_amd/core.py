@@ -369,6 +369,13 @@ class corelib(object):
                                             c_void_p, c_uint64, c_void_p, c_void_p]),
         "xrl_debug_hnsw_counters": (c_int, [POINTER(c_uint64), c_uint32, c_int]),
         "xrl_debug_hnsw_caps": (c_int, [POINTER(c_uint64), c_uint32]),
+        "xrl_hnsw_train_csr_f32": (c_int, [POINTER(ScipyCsrF32), c_uint32, c_uint32, c_int32, c_int32, c_char_p, c_int, POINTER(c_void_p)]),
+        "xrl_hnsw_train_drm_f32": (c_int, [POINTER(ScipyDrmF32), c_uint32, c_uint32, c_int32, c_int32, c_char_p, c_int, POINTER(c_void_p)]),
+        "xrl_hnsw_train_device": (c_int, [c_int, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_int32, c_int32, c_char_p,
+                                          c_void_p, POINTER(c_void_p)]),
+        "xrl_hnsw_save": (c_int, [c_void_p, c_char_p]),
+        "xrl_debug_hnsw_levels": (c_int, [c_uint32, c_uint32, c_int32, POINTER(c_uint32)]),
+        "xrl_debug_hnsw_train_counters": (c_int, [POINTER(c_uint64), c_uint32, c_int]),
         "xrl_pairwise_train_csr_f32": (c_int, [POINTER(ScipyCsrF32), POINTER(ScipyCscF32), c_int, POINTER(c_void_p)]),
         "xrl_pairwise_train_drm_f32": (c_int, [POINTER(ScipyDrmF32), POINTER(ScipyCscF32), c_int, POINTER(c_void_p)]),
         "xrl_pairwise_from_device": (c_int, [c_int, c_uint32, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p,
@@ -949,6 +956,41 @@ class corelib(object):
         out = (c_uint64 * 4)()
         self.clib_float32.xrl_debug_hnsw_caps(out, 4)
         return dict(zip(("CAP", "cand_cap", "lds_degree", "max_slots"), (int(v) for v in out)))
+
+    # ------------------------------------------------------------------ HNSW graph construction (K19)
+    HNSW_TRAIN_COUNTERS = ("dist_search", "dist_select", "dist_reverse", "rewritten", "sort_rank", "sort_replay")
+
+    def hnsw_train(self, pX, data_type, M, efC, threads, max_level_upper_bound, metric_type, device=0):
+        """``xrl_hnsw_train_{csr,drm}_f32``: the items into HBM, the graph built there -> an index handle."""
+        h = c_void_p()
+        getattr(self.clib_float32, "xrl_hnsw_train_%s_f32" % data_type)(byref(pX), M, efC, threads, max_level_upper_bound, self._cstr(metric_type), int(device), byref(h))
+        self._check()
+        return h
+
+    def hnsw_train_device(self, device, rows, cols, val_addr, row_stride, row_ptr_addr, col_idx_addr, nnz, matrix, M, efC, threads, max_level_upper_bound, metric_type,
+                          stream=None):
+        """``xrl_hnsw_train_device``: items in HBM (addresses; ``row_ptr_addr`` 0 for a dense base; or ``matrix``, an ``xrl_smat`` handle) -> an index handle."""
+        h = c_void_p()
+        self.clib_float32.xrl_hnsw_train_device(int(device), rows, cols, c_void_p(val_addr or 0), row_stride, c_void_p(row_ptr_addr or 0), c_void_p(col_idx_addr or 0), nnz,
+                                                matrix, M, efC, threads, max_level_upper_bound, self._cstr(metric_type), c_void_p(stream or 0), byref(h))
+        self._check()
+        return h
+
+    def hnsw_save(self, h, c_model_dir):
+        self.clib_float32.xrl_hnsw_save(h, self._cstr(c_model_dir))
+        self._check()
+
+    def debug_hnsw_levels(self, n, M, max_level_upper_bound=-1):
+        """The level of every node as the trainer plans them on the host (``xrl_debug_hnsw_levels``; no GPU)."""
+        out = np.zeros(n, dtype=np.uint32)
+        self.clib_float32.xrl_debug_hnsw_levels(n, M, max_level_upper_bound, out.ctypes.data_as(POINTER(c_uint32)))
+        self._check()
+        return out
+
+    def debug_hnsw_train_counters(self, reset=False):
+        out = (c_uint64 * len(self.HNSW_TRAIN_COUNTERS))()
+        self.clib_float32.xrl_debug_hnsw_train_counters(out, len(self.HNSW_TRAIN_COUNTERS), 1 if reset else 0)
+        return dict(zip(self.HNSW_TRAIN_COUNTERS, (int(v) for v in out)))
 
     # ------------------------------------------------------------------ PairwiseANN (K18)
     PAIRWISE_INFO = ("num_input_keys", "num_label_keys", "feat_dim", "data_type", "nnz_of_Y", "nnz_of_X", "max_col", "device_bytes")

@@ -106,7 +106,7 @@ std::unique_ptr<HnswIndex> load_index(const std::string& dir, int device, bool u
         const uint32_t* rec = reinterpret_cast<const uint32_t*>(buf + at);
         check_neighbourhood(what, i, 0, rec, d.maxM0, N, seen);
         l0_deg[i] = rec[0];
-        std::memcpy(&l0_nbr[(size_t)i * d.maxM0], rec + 1, 4ull * rec[0]);
+        std::memcpy(&l0_nbr[(size_t)i * d.maxM0], rec + 1, 4ull * d.maxM0);   // (the whole record: what lies past the degree is never read by a search, and xrl_hnsw_save writes it back)
         const uint32_t len = rec[1 + d.maxM0];
         const float* fv = reinterpret_cast<const float*>(rec + 2 + d.maxM0);
         if (d.dense) {
@@ -128,7 +128,7 @@ std::unique_ptr<HnswIndex> load_index(const std::string& dir, int device, bool u
             const uint32_t* rec1 = buf1 + (uint64_t)i * node_mem1 + (uint64_t)(l - 1) * level_mem1;
             check_neighbourhood(what, i, l, rec1, d.maxM, N, seen);
             l1_deg[(size_t)i * d.l1_levels + (l - 1)] = rec1[0];
-            std::memcpy(&l1_nbr[((size_t)i * d.l1_levels + (l - 1)) * d.maxM], rec1 + 1, 4ull * rec1[0]);
+            std::memcpy(&l1_nbr[((size_t)i * d.l1_levels + (l - 1)) * d.maxM], rec1 + 1, 4ull * d.maxM);
         }
     }
     ix->bytes = 4ull * (l0_deg.size() + l0_nbr.size() + l1_deg.size() + l1_nbr.size() + feat.size() + idx.size() + val.size()) + 8ull * row_ptr.size();
