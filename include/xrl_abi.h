@@ -518,17 +518,30 @@ int xrl_debug_spgemm_forms(uint64_t* out, uint32_t n);
  * than 0 or 5.  Refused by a check kernel: a row whose column ids are not strictly ascending, or an id >= cols.  Scratch is one level
  * at a time; when it does not fit the message names the bytes needed.
  *   c_run_clustering_csr_f32 / _drm_f32   the reference's signatures: upload, run, copy label_codes [rows] back.  The dense form is the
- *                                same computation on rows that store every entry, zeros included, always with the dense norm order.
+ *                                same computation on rows that store every entry, zeros included, always with the dense norm order; it
+ *                                uploads the caller's array as it is (rows * cols * 4 bytes) and runs xrl_run_clustering_dense_device's kernels.
  *   xrl_run_clustering_device    the feature matrix is an xrl_smat_* CSR handle (e.g. the label embedding xrl_label_embedding_device leaves in HBM); d_codes [rows]
  *                                and d_scores (NULL or [depth * rows]: the reference's `scores` array as it stands after each level) are
  *                                in HBM on the handle's device.  Runs on hip_stream and synchronises it every iteration.  0, or -1 +
  *                                xrl_last_error.
+ *   xrl_run_clustering_dense_device   the feature matrix is dense and row-major in HBM on `device` (K11D, csrc/xrl_cluster_dense.hip): entry
+ *                                (r, f) at d_val[r * row_stride + f], row_stride >= cols; the floats between cols and the stride are never
+ *                                read and d_val is not written.  The rule on rows that store all `cols` columns in ascending order: codes
+ *                                and scores are bit for bit those of the CSR of all rows * cols entries, with no such CSR, no layout sort
+ *                                and no scratch per entry -- per level the centres take 4 * 2^d * cols bytes (8 for SKMEANS) beside the
+ *                                split's 48 bytes per row; rows * cols may exceed 2^32.  d_codes, d_scores, the stream and the
+ *                                synchronisation are xrl_run_clustering_device's.  Refused before a GPU is required, beside the plan's
+ *                                refusals above: null d_val / param / d_codes, row_stride < cols, rows >= 2^32.  There is no check kernel
+ *                                (the ids are implicit).  0, or -1 + xrl_last_error.
  *   xrl_debug_cluster_plan       FOR TESTS ONLY, needs no GPU: the draws.  node_seed [2^(depth+1)]; level_info [2 * depth] = {sampled,
  *                                first-touch norm order} per level; work [4 * 2^depth], by node id = {range start, working end, position
  *                                of r, position of l}; perm [depth * rows] = each level's shuffle as source positions.  Each may be NULL.
  *   xrl_debug_cluster_forms      FOR TESTS ONLY: of the last clustering of this process, out[0..n) <- {runs served one per lane, runs
  *                                served by a wavefront (64 entries and more), segmented sorts issued, level at which the norm order
- *                                switched (~0: never, or KMEANS), depth, iterations run at level 0, 1, ...}; runs count once per level */
+ *                                switched (~0: never, or KMEANS), depth, iterations run at level 0, 1, ...}; runs count once per level.  After a
+ *                                dense clustering both run counts are 0 and the sorts are the split's only.
+ *   xrl_debug_cluster_dense_forms   FOR TESTS ONLY: of the last clustering of this process, out[0..n) <- {score tiles served by the
+ *                                one-node form, by the mixed form, centre chains (node, side, feature) walked}; 0 after a CSR clustering */
 typedef struct {            /* clustering.hpp:35-72  ClusteringParam */
     size_t partition_algo;
     int seed;
@@ -543,6 +556,9 @@ int xrl_run_clustering_device(void* smat, uint64_t depth, const ClusteringParam*
 int xrl_debug_cluster_plan(uint64_t rows, uint64_t cols, uint64_t nnz, uint64_t depth, const ClusteringParam* param, uint32_t* node_seed, uint32_t* level_info,
                            uint32_t* work, uint32_t* perm);
 int xrl_debug_cluster_forms(uint64_t* out, uint32_t n);
+int xrl_run_clustering_dense_device(int device, uint64_t rows, uint64_t cols, const float* d_val, uint64_t row_stride, uint64_t depth, const ClusteringParam* param,
+                                    uint32_t* d_codes, float* d_scores /* NULL or [depth * rows] */, void* hip_stream);
+int xrl_debug_cluster_dense_forms(uint64_t* out, uint32_t n);
 
 /* ------------------------------------------------------------------------------------------
  * LABEL EMBEDDINGS ON THE DEVICE (K12, csrc/xrl_embed.hip, composed with K10): LabelEmbeddingFactory.create (pecos/xmc/base.py:1903-2094)

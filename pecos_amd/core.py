@@ -332,6 +332,8 @@ class corelib(object):
         "xrl_run_clustering_device": (c_int, [c_void_p, c_uint64, POINTER(ClusteringParam), c_void_p, c_void_p, c_void_p]),
         "xrl_debug_cluster_plan": (c_int, [c_uint64, c_uint64, c_uint64, c_uint64, POINTER(ClusteringParam), c_void_p, c_void_p, c_void_p, c_void_p]),
         "xrl_debug_cluster_forms": (c_int, [POINTER(c_uint64), c_uint32]),
+        "xrl_run_clustering_dense_device": (c_int, [c_int, c_uint64, c_uint64, c_void_p, c_uint64, c_uint64, POINTER(ClusteringParam), c_void_p, c_void_p, c_void_p]),
+        "xrl_debug_cluster_dense_forms": (c_int, [POINTER(c_uint64), c_uint32]),
         "xrl_smat_transpose_device": (c_void_p, [c_void_p, c_void_p]),
         "xrl_smat_normalize_rows_device": (c_int, [c_void_p, c_int, POINTER(c_void_p), c_void_p]),
         "xrl_smat_normalize_rows_norm_device": (c_int, [c_void_p, c_int, c_int, POINTER(c_void_p), c_void_p]),
@@ -1101,6 +1103,20 @@ class corelib(object):
                                                          c_void_p(stream or 0))
         self._check()
         return rc
+
+    def run_clustering_dense_device(self, device, rows, cols, d_val, row_stride, depth, param, d_codes, d_scores=None, stream=None):
+        """Cluster the rows of a dense row-major float32 matrix at the device address ``d_val`` (K11D); ``row_stride`` in floats, >= cols."""
+        rc = self.clib_float32.xrl_run_clustering_dense_device(int(device), int(rows), int(cols), c_void_p(d_val), int(row_stride), int(depth), byref(param),
+                                                               c_void_p(d_codes), c_void_p(d_scores or 0), c_void_p(stream or 0))
+        self._check()
+        return rc
+
+    def debug_cluster_dense_forms(self):
+        """Of the last clustering, when it was dense: dict(one_node_tiles, mixed_tiles, centre_chains)."""
+        out = (c_uint64 * 3)()
+        self.clib_float32.xrl_debug_cluster_dense_forms(out, 3)
+        self._check()
+        return dict(zip(("one_node_tiles", "mixed_tiles", "centre_chains"), (int(v) for v in out)))
 
     def debug_cluster_plan(self, rows, cols, nnz, depth, param):
         """The draws of a clustering, without a GPU: dict(node_seed [2^(depth+1)], level_info [depth, 2] = (sampled, first-touch),

@@ -37,11 +37,46 @@ struct ClusterForms {
     uint64_t lane_runs = 0, wave_runs = 0, seg_sorts = 0;
     uint32_t switch_level = kClusterNoSwitch;
     std::vector<uint32_t> iters;                // per level
+    uint64_t one_node_tiles = 0, mixed_tiles = 0, centre_chains = 0;     // K11D: score tiles by form, centre chains walked
 };
+
+// What every kernel of a level reads, whatever the layout of X: the element order, the scores and the level's nodes, in HBM.
+struct ClusterLevelDev {
+    uint32_t rows;
+    uint32_t* elem; uint32_t* pos_of; float* score;      // [rows]
+    uint32_t nodes;
+    const uint32_t* beg;        // [nodes + 1]
+    const uint32_t* work_end;   // [nodes]  end of the range the iterations work on
+    const uint32_t* active;     // [nodes]
+};
+
+// The two steps that depend on the layout of X, "make the centre" and "score"; everything else of a clustering -- the levels, the
+// iterations, the split, the flags, the sampled levels' permutation, the codes -- is cluster_levels (xrl_cluster.hip), which both
+// cluster_device (CSR) and cluster_dense_device call.
+struct ClusterFeatures {
+    virtual ~ClusterFeatures() = default;
+    // once per level, after the level's permutation: the layout and a zeroed centre (max_iter = 0 scores with it)
+    virtual void begin_level(uint32_t d, const ClusterLevel& lv, const ClusterLevelDev& a, hipStream_t s) = 0;
+    // iteration 0: centre = x[elem[r_pos[node]]] - x[elem[l_pos[node]]]
+    virtual void first_centre(const uint32_t* r_pos, const uint32_t* l_pos, hipStream_t s) = 0;
+    // later iterations: the centre of the two halves; alpha [2 * nodes] for KMEANS, null for SKMEANS (norms and scales included)
+    virtual void centre(const float* alpha, hipStream_t s) = 0;
+    // score[e] for the positions below end[node] of every active node
+    virtual void score(const uint32_t* end, hipStream_t s) = 0;
+};
+
+// forms.seg_sorts counts the split's sorts; feat counts its own.  d_codes [rows], d_scores nullptr or [depth * rows].
+void cluster_levels(const ClusterPlan& plan, const ClusteringParam& param, ClusterFeatures& feat, uint32_t* d_codes, float* d_scores, hipStream_t s,
+                    ClusterForms& forms);
 
 // X: a CSR view in HBM.  d_codes [rows], d_scores nullptr or [depth * rows].  Enqueues on s and synchronises it at least once per
 // iteration.  Fails on a row whose column ids are not strictly ascending or reach X.cols.
 void cluster_device(const char* what, const QueriesDev& X, const ClusterPlan& plan, const ClusteringParam& param, uint32_t* d_codes, float* d_scores,
                     hipStream_t s, ClusterForms& forms);
+
+// K11D (xrl_cluster_dense.hip): the same clustering of a dense row-major matrix in HBM, base[r * row_stride + f], row_stride >= cols;
+// the bytes between cols and the stride are never read.  No layout sort and no scratch per entry.
+void cluster_dense_device(const char* what, const float* base, uint64_t rows, uint64_t cols, uint64_t row_stride, const ClusterPlan& plan,
+                          const ClusteringParam& param, uint32_t* d_codes, float* d_scores, hipStream_t s, ClusterForms& forms);
 
 }  // namespace xrl

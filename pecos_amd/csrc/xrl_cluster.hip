@@ -24,17 +24,9 @@ namespace {
 constexpr const char* kWhat = "clustering";
 constexpr uint32_t kNoElem = 0xFFFFFFFFu;
 
-struct K11Level {
+struct K11Level : ClusterLevelDev {
     // X
     const uint64_t* x_ptr; const float* x_val;
-    uint32_t rows;
-    // elements
-    uint32_t* elem; uint32_t* pos_of; float* score;
-    // the level's nodes
-    uint32_t nodes;
-    const uint32_t* beg;        // [nodes + 1]
-    const uint32_t* work_end;   // [nodes]  end of the range the iterations work on
-    const uint32_t* active;     // [nodes]
     // the level's layout
     const uint64_t* keys;       // [nnz] sorted (feature << 32 | element id), per node
     const uint32_t* xent;       // [nnz] the entry of X behind each key
@@ -286,7 +278,7 @@ __global__ void __launch_bounds__(256) k11_score(K11Level a, const uint32_t* __r
 
 // the split's sort keys and segments: the scored range of every active node, and its two halves
 __global__ void __launch_bounds__(256)
-k11_split_keys(K11Level a, const uint32_t* __restrict__ end, uint64_t* __restrict__ keys, uint32_t* __restrict__ seg_b, uint32_t* __restrict__ seg_e,
+k11_split_keys(ClusterLevelDev a, const uint32_t* __restrict__ end, uint64_t* __restrict__ keys, uint32_t* __restrict__ seg_b, uint32_t* __restrict__ seg_e,
                uint32_t* __restrict__ half_b, uint32_t* __restrict__ half_e) {
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
     if (p < a.nodes) {
@@ -305,7 +297,7 @@ __global__ void __launch_bounds__(256) k11_split_ids(const uint64_t* __restrict_
 }
 
 // the new order of every active node's scored range; changed[node] when its first half differs from what it was (clustering.hpp:202-212)
-__global__ void __launch_bounds__(256) k11_commit(K11Level a, const uint32_t* __restrict__ end, const uint32_t* __restrict__ ids, uint32_t* __restrict__ changed) {
+__global__ void __launch_bounds__(256) k11_commit(ClusterLevelDev a, const uint32_t* __restrict__ end, const uint32_t* __restrict__ ids, uint32_t* __restrict__ changed) {
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
     if (p >= a.rows) return;
     const uint32_t nd = segment_of(a.beg, a.nodes, p);
@@ -332,57 +324,173 @@ k11_codes(const uint32_t* __restrict__ elem, const uint32_t* __restrict__ leaf_b
 
 uint32_t grid(uint64_t n) { return blocks_of(n ? n : 1, 256, kWhat); }
 
+// "make the centre" and "score" over a CSR: the level's layout (one key per stored entry, sorted per node) and the runs' chains
+struct CsrFeatures final : ClusterFeatures {
+    const std::string what;
+    const QueriesDev& X;
+    const bool SK;
+    ClusterForms& forms;
+    const uint32_t L;
+    const uint64_t nnz;
+    const unsigned feature_bits;
+    K11Level a{};
+    bool first_touch = false;
+    DevBuf tmp, len, ent_off, keys, keys2, xent, xent2, flag, slot, run_of, node_ent, node_run, counts;
+    DevBuf run_start, run_node, c, c2, first, nkeys, nkeys2, nseg, scale;
+
+    // the sorts look only at the key bits that can differ: a feature id is below cols
+    static unsigned bits_of(uint64_t below) { unsigned b = 1; while (b < 32 && ((below - 1) >> b)) ++b; return b; }
+
+    CsrFeatures(const std::string& what_, const QueriesDev& X_, bool SK_, ClusterForms& forms_)
+        : what(what_), X(X_), SK(SK_), forms(forms_), L(X_.rows), nnz(X_.nnz), feature_bits(bits_of(std::max<uint64_t>(X_.cols, 1))) {}
+
+    template <class Call> void seg_sort(Call&& call) { with_rocprim_tmp(tmp, call); ++forms.seg_sorts; }
+
+    // the scratch check, the check kernel and the buffers that last the whole clustering
+    void check(hipStream_t s) {
+        // scratch of one level: per entry two 8-byte keys, two entry ids, the head flag, its scan and the run id (36 bytes), then per run
+        // up to 60 bytes; per row 48
+        size_t free_b = 0, total_b = 0;
+        XRL_HIP(hipMemGetInfo(&free_b, &total_b));
+        const uint64_t need_entries = 36ull * nnz + 48ull * L + (64ull << 10) * 2;
+        if (need_entries > free_b) fail(what + "the scratch of one level needs " + std::to_string(need_entries) + " bytes, " + std::to_string(free_b) + " are free");
+        DevBuf bad;
+        bad.reserve(4);
+        XRL_HIP(hipMemsetAsync(bad.p, 0, 4, s));
+        hipLaunchKernelGGL(k11_check, dim3(grid(L)), dim3(256), 0, s, X.row_ptr, X.col_idx, L, X.cols, nnz, bad.as<uint32_t>());
+        XRL_LAUNCH_CHECK();
+        uint32_t h_bad = 0;
+        XRL_HIP(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, s));
+        XRL_HIP(hipStreamSynchronize(s));
+        if (h_bad & 2u) fail(what + "row pointers must ascend from 0 to nnz");
+        if (h_bad) fail(what + "a row's column ids must be strictly ascending and below cols");
+        len.reserve(((size_t)L + 1) * 4); ent_off.reserve(((size_t)L + 1) * 4);
+        keys.reserve((size_t)nnz * 8); keys2.reserve((size_t)nnz * 8);
+        xent.reserve((size_t)nnz * 4); xent2.reserve((size_t)nnz * 4); run_of.reserve((size_t)nnz * 4);
+        flag.reserve(((size_t)nnz + 1) * 4); slot.reserve(((size_t)nnz + 1) * 4);
+        counts.reserve(16);
+        XRL_HIP(hipMemsetAsync(counts.p, 0, 16, s));
+    }
+
+    void begin_level(uint32_t d, const ClusterLevel& lv, const ClusterLevelDev& lvl, hipStream_t s) override {
+        const uint32_t nodes = lvl.nodes;
+        hipLaunchKernelGGL(k11_rowlen, dim3(grid(L)), dim3(256), 0, s, X.row_ptr, lvl.elem, L, lvl.pos_of, len.as<uint32_t>());
+        XRL_LAUNCH_CHECK();
+        exclusive_scan(tmp, len.as<uint32_t>(), ent_off.as<uint32_t>(), (size_t)L + 1, s);
+        node_ent.reserve(((size_t)nodes + 1) * 4); node_run.reserve(((size_t)nodes + 1) * 4);
+        hipLaunchKernelGGL(k11_node_ent, dim3(grid(nodes + 1)), dim3(256), 0, s, lvl.beg, ent_off.as<uint32_t>(), nodes, node_ent.as<uint32_t>());
+        XRL_LAUNCH_CHECK();
+        uint32_t runs = 0;
+        if (nnz) {
+            hipLaunchKernelGGL(k11_expand, dim3(blocks_of(L, 4, kWhat)), dim3(256), 0, s, X.row_ptr, X.col_idx, lvl.elem, ent_off.as<uint32_t>(), L,
+                               keys.as<uint64_t>(), xent.as<uint32_t>());
+            XRL_LAUNCH_CHECK();
+            seg_sort([&](void* t, size_t& bytes) {
+                return rocprim::segmented_radix_sort_pairs(t, bytes, keys.as<uint64_t>(), keys2.as<uint64_t>(), xent.as<uint32_t>(), xent2.as<uint32_t>(), (unsigned int)nnz,
+                                                           nodes, node_ent.as<uint32_t>(), node_ent.as<uint32_t>() + 1, 0u, 32u + feature_bits, s);
+            });
+            hipLaunchKernelGGL(k11_heads, dim3(grid(nnz)), dim3(256), 0, s, keys2.as<uint64_t>(), node_ent.as<uint32_t>(), nodes, (uint32_t)nnz, flag.as<uint32_t>());
+            XRL_LAUNCH_CHECK();
+            runs = scan_total(tmp, flag.as<uint32_t>(), slot.as<uint32_t>(), (size_t)nnz, s);
+        } else {
+            XRL_HIP(hipMemsetAsync(slot.p, 0, 4, s));
+        }
+        const uint64_t need_runs = 60ull * runs + 64;
+        size_t free_b = 0, total_b = 0;
+        XRL_HIP(hipMemGetInfo(&free_b, &total_b));
+        if (need_runs > free_b + run_start.cap + run_node.cap + c.cap + c2.cap + first.cap + nkeys.cap + nkeys2.cap)
+            fail(what + "the runs of level " + std::to_string(d) + " need " + std::to_string(need_runs) + " bytes of scratch, " + std::to_string(free_b) + " are free");
+        run_start.reserve(((size_t)runs + 1) * 4); run_node.reserve(((size_t)runs + 1) * 4);
+        c.reserve(((size_t)runs + 1) * 4);
+        XRL_HIP(hipMemsetAsync(c.p, 0, ((size_t)runs + 1) * 4, s));       // max_iter = 0: the final assignment scores with a zero centre
+        first_touch = lv.first_touch;
+        if (SK) {
+            c2.reserve(((size_t)runs + 1) * 4); first.reserve(((size_t)runs + 1) * 8); scale.reserve((size_t)nodes * 16);
+            if (lv.first_touch) { nkeys.reserve(((size_t)runs + 1) * 16); nkeys2.reserve(((size_t)runs + 1) * 16); nseg.reserve((2 * (size_t)nodes + 1) * 4); }
+        }
+        hipLaunchKernelGGL(k11_runs, dim3(grid(nnz)), dim3(256), 0, s, flag.as<uint32_t>(), slot.as<uint32_t>(), xent2.as<uint32_t>(), node_ent.as<uint32_t>(), nodes,
+                           (uint32_t)nnz, runs, run_of.as<uint32_t>(), run_start.as<uint32_t>(), run_node.as<uint32_t>());
+        XRL_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k11_node_run, dim3(grid(nodes + 1)), dim3(256), 0, s, node_ent.as<uint32_t>(), slot.as<uint32_t>(), nodes, node_run.as<uint32_t>());
+        XRL_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k11_count_forms, dim3(grid(runs)), dim3(256), 0, s, run_start.as<uint32_t>(), runs, counts.as<unsigned long long>());
+        XRL_LAUNCH_CHECK();
+        if (SK && lv.first_touch) {
+            hipLaunchKernelGGL(k11_norm_segs, dim3(grid(nodes)), dim3(256), 0, s, node_run.as<uint32_t>(), nodes, runs, nseg.as<uint32_t>());
+            XRL_LAUNCH_CHECK();
+        }
+        a = K11Level{};
+        static_cast<ClusterLevelDev&>(a) = lvl;
+        a.x_ptr = X.row_ptr; a.x_val = X.val;
+        a.keys = keys2.as<uint64_t>(); a.xent = xent2.as<uint32_t>(); a.run_start = run_start.as<uint32_t>(); a.run_node = run_node.as<uint32_t>();
+        a.run_of = run_of.as<uint32_t>(); a.node_run = node_run.as<uint32_t>(); a.runs = runs;
+        a.c = c.as<float>(); a.c2 = c2.as<float>(); a.first = first.as<uint32_t>();
+    }
+
+    void first_centre(const uint32_t* r_pos, const uint32_t* l_pos, hipStream_t s) override {
+        hipLaunchKernelGGL(k11_first_centre, dim3(grid(a.runs)), dim3(256), 0, s, a, r_pos, l_pos);
+        XRL_LAUNCH_CHECK();
+    }
+
+    void centre(const float* alpha, hipStream_t s) override {
+        const uint32_t runs = a.runs, nodes = a.nodes;
+        if (!SK) {
+            hipLaunchKernelGGL(k11_centre<false>, dim3(grid(runs)), dim3(256), 0, s, a, alpha);
+            XRL_LAUNCH_CHECK();
+            return;
+        }
+        hipLaunchKernelGGL(k11_centre<true>, dim3(grid(runs)), dim3(256), 0, s, a, (const float*)nullptr);
+        XRL_LAUNCH_CHECK();
+        const uint64_t* order = nullptr;
+        if (first_touch && runs) {
+            hipLaunchKernelGGL(k11_norm_keys, dim3(grid(2ull * runs)), dim3(256), 0, s, first.as<uint32_t>(), 2 * runs, runs, nkeys.as<uint64_t>());
+            XRL_LAUNCH_CHECK();
+            seg_sort([&](void* t, size_t& bytes) {
+                return rocprim::segmented_radix_sort_keys(t, bytes, nkeys.as<uint64_t>(), nkeys2.as<uint64_t>(), 2 * runs, 2 * nodes, nseg.as<uint32_t>(),
+                                                          nseg.as<uint32_t>() + 1, 0u, 64u, s);
+            });
+            order = nkeys2.as<uint64_t>();
+        }
+        hipLaunchKernelGGL(k11_norm, dim3(blocks_of(2ull * nodes, 4, kWhat)), dim3(256), 0, s, a, order, scale.as<double>());
+        XRL_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k11_combine, dim3(grid(runs)), dim3(256), 0, s, a, scale.as<double>());
+        XRL_LAUNCH_CHECK();
+    }
+
+    void score(const uint32_t* end, hipStream_t s) override {
+        hipLaunchKernelGGL(k11_score, dim3(grid(L)), dim3(256), 0, s, a, end);
+        XRL_LAUNCH_CHECK();
+    }
+
+    void finish(hipStream_t s) {
+        unsigned long long h_counts[2] = {0, 0};
+        XRL_HIP(hipMemcpyAsync(h_counts, counts.p, 16, hipMemcpyDeviceToHost, s));
+        XRL_HIP(hipStreamSynchronize(s));
+        forms.lane_runs = h_counts[0]; forms.wave_runs = h_counts[1];
+    }
+};
+
 }  // namespace
 
-void cluster_device(const char* what_c, const QueriesDev& X, const ClusterPlan& plan, const ClusteringParam& param, uint32_t* d_codes, float* d_scores,
-                    hipStream_t s, ClusterForms& forms) {
-    const std::string what = std::string(what_c) + ": ";
+void cluster_levels(const ClusterPlan& plan, const ClusteringParam& param, ClusterFeatures& feat, uint32_t* d_codes, float* d_scores, hipStream_t s,
+                    ClusterForms& forms) {
     const uint32_t L = plan.rows, depth = plan.depth;
-    const uint64_t nnz = X.nnz;
     const bool SK = param.partition_algo == 5;
-    if (X.dense || !X.row_ptr) fail(what + "the feature matrix must be a CSR");
-    if (X.rows != L) fail(what + "the plan is for another row count");
-    if (nnz > 0xFFFFFFF0ull) fail(what + "more than 2^32 - 16 stored entries");
-    forms = ClusterForms{};
     forms.switch_level = SK ? plan.switch_level : kClusterNoSwitch;
     forms.iters.assign(depth, 0u);
 
-    // scratch of one level: per entry two 8-byte keys, two entry ids, the head flag, its scan and the run id (36 bytes), then per run
-    // up to 60 bytes; per row 48
-    size_t free_b = 0, total_b = 0;
-    XRL_HIP(hipMemGetInfo(&free_b, &total_b));
-    const uint64_t need_entries = 36ull * nnz + 48ull * L + (64ull << 10) * 2;
-    if (need_entries > free_b) fail(what + "the scratch of one level needs " + std::to_string(need_entries) + " bytes, " + std::to_string(free_b) + " are free");
-
-    DevBuf bad, tmp;
-    bad.reserve(4);
-    XRL_HIP(hipMemsetAsync(bad.p, 0, 4, s));
-    hipLaunchKernelGGL(k11_check, dim3(grid(L)), dim3(256), 0, s, X.row_ptr, X.col_idx, L, X.cols, nnz, bad.as<uint32_t>());
-    XRL_LAUNCH_CHECK();
-    uint32_t h_bad = 0;
-    XRL_HIP(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, s));
-    XRL_HIP(hipStreamSynchronize(s));
-    if (h_bad & 2u) fail(what + "row pointers must ascend from 0 to nnz");
-    if (h_bad) fail(what + "a row's column ids must be strictly ascending and below cols");
-
-    DevBuf elem, elem2, ids, pos_of, score, len, ent_off, keys, keys2, xent, xent2, flag, slot, run_of, skeys, skeys2;
-    DevBuf beg, work_end, whole_end, active, changed, r_pos, l_pos, alpha, perm, node_ent, node_run, seg, half, counts, leaf_beg;
-    DevBuf run_start, run_node, c, c2, first, nkeys, nkeys2, nseg, scale;
-    for (DevBuf* b : {&elem, &elem2, &ids, &pos_of, &score, &len, &ent_off}) b->reserve(((size_t)L + 1) * 4);
+    DevBuf tmp, elem, elem2, ids, pos_of, score, skeys, skeys2;
+    DevBuf beg, work_end, whole_end, active, changed, r_pos, l_pos, alpha, perm, seg, half, leaf_beg;
+    for (DevBuf* b : {&elem, &elem2, &ids, &pos_of, &score}) b->reserve(((size_t)L + 1) * 4);
     skeys.reserve((size_t)L * 8); skeys2.reserve((size_t)L * 8);
-    keys.reserve((size_t)nnz * 8); keys2.reserve((size_t)nnz * 8);
-    xent.reserve((size_t)nnz * 4); xent2.reserve((size_t)nnz * 4); run_of.reserve((size_t)nnz * 4);
-    flag.reserve(((size_t)nnz + 1) * 4); slot.reserve(((size_t)nnz + 1) * 4);
-    counts.reserve(16);
-    XRL_HIP(hipMemsetAsync(counts.p, 0, 16, s));
     XRL_HIP(hipMemsetAsync(score.p, 0, (size_t)L * 4, s));
     hipLaunchKernelGGL(k11_iota, dim3(grid(L)), dim3(256), 0, s, elem.as<uint32_t>(), L);
     XRL_LAUNCH_CHECK();
 
     auto seg_sort = [&](auto&& call) { with_rocprim_tmp(tmp, call); ++forms.seg_sorts; };
-    // the sorts look only at the key bits that can differ: a feature id is below cols, an element id below L
-    auto bits_of = [](uint64_t below) { unsigned b = 1; while (b < 32 && ((below - 1) >> b)) ++b; return b; };
-    const unsigned feature_bits = bits_of(std::max<uint64_t>(X.cols, 1)), element_bits = bits_of(L);
+    // the sorts look only at the key bits that can differ: an element id is below L
+    unsigned element_bits = 1;
+    while (element_bits < 32 && (((uint64_t)L - 1) >> element_bits)) ++element_bits;
 
     for (uint32_t d = 0; d < depth; ++d) {
         const ClusterLevel& lv = plan.levels[d];
@@ -412,66 +520,17 @@ void cluster_device(const char* what_c, const QueriesDev& X, const ClusterPlan& 
             std::swap(elem, elem2);
         }
 
-        // ---- the level's layout
-        hipLaunchKernelGGL(k11_rowlen, dim3(grid(L)), dim3(256), 0, s, X.row_ptr, elem.as<uint32_t>(), L, pos_of.as<uint32_t>(), len.as<uint32_t>());
-        XRL_LAUNCH_CHECK();
-        exclusive_scan(tmp, len.as<uint32_t>(), ent_off.as<uint32_t>(), (size_t)L + 1, s);
-        node_ent.reserve(((size_t)nodes + 1) * 4); node_run.reserve(((size_t)nodes + 1) * 4);
-        hipLaunchKernelGGL(k11_node_ent, dim3(grid(nodes + 1)), dim3(256), 0, s, beg.as<uint32_t>(), ent_off.as<uint32_t>(), nodes, node_ent.as<uint32_t>());
-        XRL_LAUNCH_CHECK();
-        uint32_t runs = 0;
-        if (nnz) {
-            hipLaunchKernelGGL(k11_expand, dim3(blocks_of(L, 4, kWhat)), dim3(256), 0, s, X.row_ptr, X.col_idx, elem.as<uint32_t>(), ent_off.as<uint32_t>(), L,
-                               keys.as<uint64_t>(), xent.as<uint32_t>());
-            XRL_LAUNCH_CHECK();
-            seg_sort([&](void* t, size_t& bytes) {
-                return rocprim::segmented_radix_sort_pairs(t, bytes, keys.as<uint64_t>(), keys2.as<uint64_t>(), xent.as<uint32_t>(), xent2.as<uint32_t>(), (unsigned int)nnz,
-                                                           nodes, node_ent.as<uint32_t>(), node_ent.as<uint32_t>() + 1, 0u, 32u + feature_bits, s);
-            });
-            hipLaunchKernelGGL(k11_heads, dim3(grid(nnz)), dim3(256), 0, s, keys2.as<uint64_t>(), node_ent.as<uint32_t>(), nodes, (uint32_t)nnz, flag.as<uint32_t>());
-            XRL_LAUNCH_CHECK();
-            runs = scan_total(tmp, flag.as<uint32_t>(), slot.as<uint32_t>(), (size_t)nnz, s);
-        } else {
-            XRL_HIP(hipMemsetAsync(slot.p, 0, 4, s));
-        }
-        const uint64_t need_runs = 60ull * runs + 64;
-        XRL_HIP(hipMemGetInfo(&free_b, &total_b));
-        if (need_runs > free_b + run_start.cap + run_node.cap + c.cap + c2.cap + first.cap + nkeys.cap + nkeys2.cap)
-            fail(what + "the runs of level " + std::to_string(d) + " need " + std::to_string(need_runs) + " bytes of scratch, " + std::to_string(free_b) + " are free");
-        run_start.reserve(((size_t)runs + 1) * 4); run_node.reserve(((size_t)runs + 1) * 4);
-        c.reserve(((size_t)runs + 1) * 4);
-        XRL_HIP(hipMemsetAsync(c.p, 0, ((size_t)runs + 1) * 4, s));       // max_iter = 0: the final assignment scores with a zero centre
-        if (SK) {
-            c2.reserve(((size_t)runs + 1) * 4); first.reserve(((size_t)runs + 1) * 8); scale.reserve((size_t)nodes * 16);
-            if (lv.first_touch) { nkeys.reserve(((size_t)runs + 1) * 16); nkeys2.reserve(((size_t)runs + 1) * 16); nseg.reserve((2 * (size_t)nodes + 1) * 4); }
-        }
-        hipLaunchKernelGGL(k11_runs, dim3(grid(nnz)), dim3(256), 0, s, flag.as<uint32_t>(), slot.as<uint32_t>(), xent2.as<uint32_t>(), node_ent.as<uint32_t>(), nodes,
-                           (uint32_t)nnz, runs, run_of.as<uint32_t>(), run_start.as<uint32_t>(), run_node.as<uint32_t>());
-        XRL_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k11_node_run, dim3(grid(nodes + 1)), dim3(256), 0, s, node_ent.as<uint32_t>(), slot.as<uint32_t>(), nodes, node_run.as<uint32_t>());
-        XRL_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k11_count_forms, dim3(grid(runs)), dim3(256), 0, s, run_start.as<uint32_t>(), runs, counts.as<unsigned long long>());
-        XRL_LAUNCH_CHECK();
-        if (SK && lv.first_touch) {
-            hipLaunchKernelGGL(k11_norm_segs, dim3(grid(nodes)), dim3(256), 0, s, node_run.as<uint32_t>(), nodes, runs, nseg.as<uint32_t>());
-            XRL_LAUNCH_CHECK();
-        }
-
-        K11Level a{};
-        a.x_ptr = X.row_ptr; a.x_val = X.val; a.rows = L;
-        a.elem = elem.as<uint32_t>(); a.pos_of = pos_of.as<uint32_t>(); a.score = score.as<float>();
+        ClusterLevelDev a{};
+        a.rows = L; a.elem = elem.as<uint32_t>(); a.pos_of = pos_of.as<uint32_t>(); a.score = score.as<float>();
         a.nodes = nodes; a.beg = beg.as<uint32_t>(); a.work_end = work_end.as<uint32_t>(); a.active = active.as<uint32_t>();
-        a.keys = keys2.as<uint64_t>(); a.xent = xent2.as<uint32_t>(); a.run_start = run_start.as<uint32_t>(); a.run_node = run_node.as<uint32_t>();
-        a.run_of = run_of.as<uint32_t>(); a.node_run = node_run.as<uint32_t>(); a.runs = runs;
-        a.c = c.as<float>(); a.c2 = c2.as<float>(); a.first = first.as<uint32_t>();
+        feat.begin_level(d, lv, a, s);
         seg.reserve((size_t)nodes * 8); half.reserve((size_t)nodes * 16);
         uint32_t* seg_b = seg.as<uint32_t>(); uint32_t* seg_e = seg_b + nodes;
         uint32_t* half_b = half.as<uint32_t>(); uint32_t* half_e = half_b + 2 * (size_t)nodes;
 
         // score the range [beg, end) of every active node with the current centre and split it
         auto assign = [&](const uint32_t* end) {
-            hipLaunchKernelGGL(k11_score, dim3(grid(L)), dim3(256), 0, s, a, end);
-            XRL_LAUNCH_CHECK();
+            feat.score(end, s);
             hipLaunchKernelGGL(k11_split_keys, dim3(grid(std::max(L, nodes))), dim3(256), 0, s, a, end, skeys.as<uint64_t>(), seg_b, seg_e, half_b, half_e);
             XRL_LAUNCH_CHECK();
             seg_sort([&](void* t, size_t& bytes) {
@@ -487,30 +546,8 @@ void cluster_device(const char* what_c, const QueriesDev& X, const ClusterPlan& 
         };
 
         for (uint64_t k = 0; k < param.kmeans_max_iter; ++k) {
-            if (k == 0) {
-                hipLaunchKernelGGL(k11_first_centre, dim3(grid(runs)), dim3(256), 0, s, a, r_pos.as<uint32_t>(), l_pos.as<uint32_t>());
-                XRL_LAUNCH_CHECK();
-            } else if (!SK) {
-                hipLaunchKernelGGL(k11_centre<false>, dim3(grid(runs)), dim3(256), 0, s, a, alpha.as<float>());
-                XRL_LAUNCH_CHECK();
-            } else {
-                hipLaunchKernelGGL(k11_centre<true>, dim3(grid(runs)), dim3(256), 0, s, a, (const float*)nullptr);
-                XRL_LAUNCH_CHECK();
-                const uint64_t* order = nullptr;
-                if (lv.first_touch && runs) {
-                    hipLaunchKernelGGL(k11_norm_keys, dim3(grid(2ull * runs)), dim3(256), 0, s, first.as<uint32_t>(), 2 * runs, runs, nkeys.as<uint64_t>());
-                    XRL_LAUNCH_CHECK();
-                    seg_sort([&](void* t, size_t& bytes) {
-                        return rocprim::segmented_radix_sort_keys(t, bytes, nkeys.as<uint64_t>(), nkeys2.as<uint64_t>(), 2 * runs, 2 * nodes, nseg.as<uint32_t>(),
-                                                                  nseg.as<uint32_t>() + 1, 0u, 64u, s);
-                    });
-                    order = nkeys2.as<uint64_t>();
-                }
-                hipLaunchKernelGGL(k11_norm, dim3(blocks_of(2ull * nodes, 4, kWhat)), dim3(256), 0, s, a, order, scale.as<double>());
-                XRL_LAUNCH_CHECK();
-                hipLaunchKernelGGL(k11_combine, dim3(grid(runs)), dim3(256), 0, s, a, scale.as<double>());
-                XRL_LAUNCH_CHECK();
-            }
+            if (k == 0) feat.first_centre(r_pos.as<uint32_t>(), l_pos.as<uint32_t>(), s);
+            else feat.centre(SK ? nullptr : alpha.as<float>(), s);
             assign(work_end.as<uint32_t>());
             hipLaunchKernelGGL(k11_flags, dim3(grid(nodes)), dim3(256), 0, s, active.as<uint32_t>(), changed.as<uint32_t>(), nodes);
             XRL_LAUNCH_CHECK();
@@ -532,10 +569,20 @@ void cluster_device(const char* what_c, const QueriesDev& X, const ClusterPlan& 
     leaf_beg.upload(plan.leaf_beg);
     hipLaunchKernelGGL(k11_codes, dim3(grid(L)), dim3(256), 0, s, elem.as<uint32_t>(), leaf_beg.as<uint32_t>(), 1u << depth, L, d_codes);
     XRL_LAUNCH_CHECK();
-    unsigned long long h_counts[2] = {0, 0};
-    XRL_HIP(hipMemcpyAsync(h_counts, counts.p, 16, hipMemcpyDeviceToHost, s));
     XRL_HIP(hipStreamSynchronize(s));
-    forms.lane_runs = h_counts[0]; forms.wave_runs = h_counts[1];
+}
+
+void cluster_device(const char* what_c, const QueriesDev& X, const ClusterPlan& plan, const ClusteringParam& param, uint32_t* d_codes, float* d_scores,
+                    hipStream_t s, ClusterForms& forms) {
+    const std::string what = std::string(what_c) + ": ";
+    if (X.dense || !X.row_ptr) fail(what + "the feature matrix must be a CSR");
+    if (X.rows != plan.rows) fail(what + "the plan is for another row count");
+    if (X.nnz > 0xFFFFFFF0ull) fail(what + "more than 2^32 - 16 stored entries");
+    forms = ClusterForms{};
+    CsrFeatures feat(what, X, param.partition_algo == 5, forms);
+    feat.check(s);
+    cluster_levels(plan, param, feat, d_codes, d_scores, s, forms);
+    feat.finish(s);
 }
 
 }  // namespace xrl

@@ -1,6 +1,7 @@
-// Label clustering (K11, xrl_cluster.hip): c_run_clustering_csr_f32 / c_run_clustering_drm_f32 with the reference's signatures
-// (libpecos.cpp:357-370 -> Tree::run_clustering, clustering.hpp:403-503), the resident form xrl_run_clustering_device over an
-// xrl_smat_* handle, and the two exports the tests read.  Every argument is checked, and the plan drawn, before a GPU is required.
+// Label clustering (K11, xrl_cluster.hip; K11D, xrl_cluster_dense.hip): c_run_clustering_csr_f32 / c_run_clustering_drm_f32 with the
+// reference's signatures (libpecos.cpp:357-370 -> Tree::run_clustering, clustering.hpp:403-503), the resident forms
+// xrl_run_clustering_device over an xrl_smat_* handle and xrl_run_clustering_dense_device over a dense matrix in HBM, and the exports
+// the tests read.  Every argument is checked, and the plan drawn, before a GPU is required.
 #include <mutex>
 
 #include "xrl_abi_common.h"
@@ -51,13 +52,16 @@ void c_run_clustering_drm_f32(const ScipyDrmF32* X, size_t depth, ClusteringPara
         if (!X || !param || !label_codes) fail(std::string(what) + ": null argument");
         if (X->rows && X->cols && !X->val) fail(std::string(what) + ": null values");
         const uint64_t n = (uint64_t)X->rows * X->cols;
-        const ClusterPlan plan = make_cluster_plan(what, X->rows, X->cols, n, depth, param);        // refusals come before the index arrays are built
-        std::vector<uint64_t> ptr((size_t)X->rows + 1);
-        std::vector<uint32_t> idx((size_t)n);
-        for (uint64_t r = 0; r <= X->rows; ++r) ptr[r] = r * X->cols;
-        for (uint64_t i = 0; i < n; ++i) idx[i] = (uint32_t)(i % X->cols);
-        const ScipyCsrF32 csr{X->rows, X->cols, ptr.data(), idx.data(), X->val};
-        cluster_host(what, csr, plan, param, label_codes);
+        const ClusterPlan plan = make_cluster_plan(what, X->rows, X->cols, n, depth, param);        // refusals come before a GPU is required
+        require_gpu();
+        use_device(g_device);
+        DevBuf val, codes;                                                                           // the caller's array as it is: 4 bytes per entry
+        val.upload_raw(X->val, (size_t)n * 4);
+        codes.reserve((size_t)X->rows * 4);
+        ClusterForms forms;
+        cluster_dense_device(what, val.as<float>(), X->rows, X->cols, X->cols, plan, *param, codes.as<uint32_t>(), nullptr, nullptr, forms);
+        keep_forms(forms);
+        XRL_HIP(hipMemcpy(label_codes, codes.p, (size_t)X->rows * 4, hipMemcpyDeviceToHost));
     });
 }
 
@@ -73,6 +77,23 @@ int xrl_run_clustering_device(void* smat, uint64_t depth, const ClusteringParam*
         use_device(m.device);
         ClusterForms forms;
         cluster_device(what, m.dev, plan, *param, d_codes, d_scores, static_cast<hipStream_t>(hip_stream), forms);
+        keep_forms(forms);
+        return 0;
+    });
+}
+
+int xrl_run_clustering_dense_device(int device, uint64_t rows, uint64_t cols, const float* d_val, uint64_t row_stride, uint64_t depth, const ClusteringParam* param,
+                                    uint32_t* d_codes, float* d_scores, void* hip_stream) {
+    return guarded_value(-1, [&] {
+        const char* what = "xrl_run_clustering_dense_device";
+        if (!d_val || !param || !d_codes) fail(std::string(what) + ": null argument");
+        if (row_stride < cols) fail(std::string(what) + ": row_stride " + std::to_string(row_stride) + " is below cols " + std::to_string(cols));
+        if (rows >= (1ull << 32)) fail(std::string(what) + ": " + std::to_string(rows) + " rows, element ids are 32-bit");
+        const ClusterPlan plan = make_cluster_plan(what, rows, cols, rows * cols, depth, param);
+        require_gpu();
+        use_device(device);
+        ClusterForms forms;
+        cluster_dense_device(what, d_val, rows, cols, row_stride, plan, *param, d_codes, d_scores, static_cast<hipStream_t>(hip_stream), forms);
         keep_forms(forms);
         return 0;
     });
@@ -108,6 +129,16 @@ int xrl_debug_cluster_forms(uint64_t* out, uint32_t n) {
                                 g_forms.switch_level == kClusterNoSwitch ? ~0ull : (uint64_t)g_forms.switch_level, (uint64_t)g_forms.iters.size()};
         v.insert(v.end(), g_forms.iters.begin(), g_forms.iters.end());
         for (uint32_t i = 0; i < n && i < v.size(); ++i) out[i] = v[i];
+        return 0;
+    });
+}
+
+int xrl_debug_cluster_dense_forms(uint64_t* out, uint32_t n) {
+    return guarded_value(-1, [&] {
+        if (!out) fail("xrl_debug_cluster_dense_forms: null argument");
+        std::lock_guard<std::mutex> g(g_forms_mu);
+        const uint64_t v[3] = {g_forms.one_node_tiles, g_forms.mixed_tiles, g_forms.centre_chains};
+        for (uint32_t i = 0; i < n && i < 3; ++i) out[i] = v[i];
         return 0;
     });
 }

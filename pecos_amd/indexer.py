@@ -117,24 +117,38 @@ class HierarchicalKMeans(object):
 
 def run_clustering_device(feat, depth, partition_algo=HierarchicalKMeans.SKMEANS, seed=0, kmeans_max_iter=20, max_sample_rate=1.0, min_sample_rate=1.0,
                           warmup_ratio=1.0, return_scores=False, stream=None, dtype=None):
-    """Leaf codes of the rows of ``feat`` -- a :class:`~pecos_amd.features.DeviceMatrix`, CSR tensors ``(crow, col, val, (rows, cols))`` or
-    a scipy sparse matrix -- computed and left in HBM: an int32 tensor ``[rows]`` (``dtype=torch.uint32`` for that type), and with
-    ``return_scores`` also the float32 ``[depth, rows]`` scores as they stand after each level.  Runs on ``stream`` (default: torch's
-    current one), which it synchronises."""
+    """Leaf codes of the rows of ``feat`` -- a :class:`~pecos_amd.features.DeviceMatrix`, CSR tensors ``(crow, col, val, (rows, cols))``,
+    a scipy sparse matrix, or a dense 2-D float32 CUDA tensor (K11D: an embedding a model left in HBM; read in place when its last
+    dimension is contiguous and its row stride is at least ``cols``, ``.contiguous()`` otherwise, never changed) -- computed and left in
+    HBM: an int32 tensor ``[rows]`` (``dtype=torch.uint32`` for that type), and with ``return_scores`` also the float32 ``[depth, rows]``
+    scores as they stand after each level.  Runs on ``stream`` (default: torch's current one), which it synchronises."""
     import torch
     from .features import _as_device_matrix, _operand_device, _stream_or_current
-    dev = _operand_device(feat)
-    m = _as_device_matrix(feat, 0 if dev is None else dev, None, stream)
-    info = m.info
-    tdev = torch.device("cuda", info["device"])
-    codes = torch.zeros(info["rows"], dtype=torch.int32, device=tdev)
-    scores = torch.zeros((depth, info["rows"]), dtype=torch.float32, device=tdev) if return_scores else None
+    dense = isinstance(feat, torch.Tensor)
+    if dense:
+        if feat.dim() != 2 or feat.dtype != torch.float32 or not feat.is_cuda:
+            raise ValueError("run_clustering_device: a tensor operand must be a 2-D float32 CUDA tensor")
+        rows, cols = feat.shape
+        if not (cols == 0 or (feat.stride(1) == 1 and feat.stride(0) >= cols) or rows == 1):
+            feat = feat.contiguous()
+        row_stride = max(feat.stride(0), cols) if rows > 1 else cols
+        device = feat.device.index
+    else:
+        dev = _operand_device(feat)
+        m = _as_device_matrix(feat, 0 if dev is None else dev, None, stream)
+        rows, device = m.info["rows"], m.info["device"]
+    tdev = torch.device("cuda", device)
+    codes = torch.zeros(rows, dtype=torch.int32, device=tdev)
+    scores = torch.zeros((depth, rows), dtype=torch.float32, device=tdev) if return_scores else None
     param = ClusteringParam(partition_algo=partition_algo, seed=seed, kmeans_max_iter=kmeans_max_iter, threads=1, max_sample_rate=max_sample_rate,
                             min_sample_rate=min_sample_rate, warmup_ratio=warmup_ratio)
     if stream is not None:
         torch.cuda.current_stream(tdev).synchronize()      # the zero fills above ran on torch's stream
-    clib.run_clustering_device(m.handle, depth, param, codes.data_ptr(), scores.data_ptr() if return_scores else None,
-                               stream=_stream_or_current(info["device"], stream))
+    d_scores, stream = scores.data_ptr() if return_scores else None, _stream_or_current(device, stream)
+    if dense:
+        clib.run_clustering_dense_device(device, rows, cols, feat.data_ptr(), row_stride, depth, param, codes.data_ptr(), d_scores, stream=stream)
+    else:
+        clib.run_clustering_device(m.handle, depth, param, codes.data_ptr(), d_scores, stream=stream)
     if dtype is not None:
         codes = codes.view(dtype)
     return (codes, scores) if return_scores else codes

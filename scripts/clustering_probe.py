@@ -13,6 +13,13 @@ compared with the reference's at threads = 1.
     rocprofv3 --kernel-trace -d DIR -o k11 -f csv -- python scripts/clustering_probe.py --device-only --reps 1 --warm 1 --out FILE.md   (kernel times: a run of its own)
     python scripts/clustering_probe.py --render FILE.md.json --kernel-stats TRACE.csv --out profiles/clustering.md                 (no GPU: the tables)
 
+Dense embeddings (K11D): --dense times, at 768 columns and the two row counts above with the default TrainParams (SKMEANS, 20 iterations,
+depth from max_leaf_size = 100), c_run_clustering_drm_f32 and the resident tensor form, and samples the device memory in use.  --so PATH
+times the host entry point of another build of the library (the parent commit's, which has no tensor form) in a process of its own:
+
+    timeout 900 python scripts/clustering_probe.py --dense [--so PARENT.so] [--reference] --out FILE.json
+    rocprofv3 --kernel-trace -d DIR -o k11d -f csv -- python scripts/clustering_probe.py --dense --reps 1 --warm 0 --out FILE.json
+
 One process, one GPU."""
 import argparse
 import csv
@@ -117,6 +124,62 @@ def measure(args):
     return res
 
 
+def measure_dense(args):
+    """c_run_clustering_drm_f32 (of --so, default this build) and, with this build, run_clustering_device on a CUDA tensor."""
+    import torch
+    import clustering_rule as cr
+    import pecos_amd
+    from pecos_amd import HierarchicalKMeans, clib
+    so = args.so or cr.OURS
+    p = HierarchicalKMeans.TrainParams()
+    res = dict(so=os.path.basename(os.path.dirname(os.path.dirname(so))) if args.so else "this build", so_sha256_16=hashlib.sha256(open(so, "rb").read()).hexdigest()[:16],
+               device=torch.cuda.get_device_name(0), reps=args.reps, warm=args.warm, shapes={})
+    for name in args.shapes.split(","):
+        rows, depth = SHAPES[name][0], p.infer_binary_tree_depth(SHAPES[name][0])
+        D = np.random.default_rng(len(name)).standard_normal((rows, 768), dtype=np.float32)
+        kw = dict(algo=cr.SKMEANS if p.spherical else cr.KMEANS, seed=p.seed, max_iter=p.kmeans_max_iter)
+        row = dict(rows=rows, cols=768, depth=depth)
+        print(name, row, flush=True)
+        low, stop = [torch.cuda.mem_get_info()[0]], threading.Event()
+        base = low[0]
+
+        def watch():
+            while not stop.wait(0.02):
+                low[0] = min(low[0], torch.cuda.mem_get_info()[0])
+        th = threading.Thread(target=watch, daemon=True)
+        th.start()
+        row["host_entry_ms"], got = timed(lambda: cr.run_library(so, D, depth, **kw), args.reps, args.warm)
+        assert got[1] is None, got[1]
+        row["host_entry_peak_bytes"] = int(base - low[0])
+        print(" c_run_clustering_drm_f32", row["host_entry_ms"], "peak device bytes", row["host_entry_peak_bytes"], flush=True)
+        if not args.so:
+            T = torch.from_numpy(D).cuda()
+            torch.cuda.synchronize()
+            low[0] = base = torch.cuda.mem_get_info()[0]
+
+            def resident():
+                c = pecos_amd.run_clustering_device(T, depth, partition_algo=kw["algo"], seed=kw["seed"], kmeans_max_iter=kw["max_iter"])
+                torch.cuda.synchronize()
+                return c
+            row["tensor_ms"], codes = timed(resident, args.reps, args.warm)
+            row["tensor_peak_bytes"] = int(base - low[0])
+            row["forms"], row["dense_forms"] = clib.debug_cluster_forms(), clib.debug_cluster_dense_forms()
+            assert np.array_equal(codes.cpu().numpy().view(np.uint32), got[0])
+            print(" tensor form", row["tensor_ms"], "peak device bytes beyond the matrix", row["tensor_peak_bytes"], row["forms"], row["dense_forms"], flush=True)
+            del T
+        stop.set()
+        th.join()
+        if args.reference and os.path.exists(cr.REF):
+            for threads in (16, 1):
+                t0 = time.perf_counter()
+                ref = with_heartbeat(lambda: cr.reference(D, depth, threads=threads, **kw), f"reference, {threads} threads")
+                row[f"reference_t{threads}_ms"] = (time.perf_counter() - t0) * 1e3
+                print(f" reference threads={threads}", row[f"reference_t{threads}_ms"], flush=True)
+            row["codes_equal_reference_t1"] = bool(np.array_equal(ref, got[0]))
+        res["shapes"][name] = row
+    return res
+
+
 def per_level(stats_csv, res, runs_per_shape):
     """From a --device-only trace (runs_per_shape clusterings per shape, shapes in order): kernel time per level of the LAST run of each shape (a level
     starts at its k11_rowlen launch), and the share of the chain kernels."""
@@ -194,11 +257,18 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--warm", type=int, default=1)
     ap.add_argument("--device-only", action="store_true")
+    ap.add_argument("--dense", action="store_true", help="the dense shapes (K11D); --out is then a JSON file")
+    ap.add_argument("--so", help="--dense: time the host entry point of this other build of libxrl_amd.so only")
+    ap.add_argument("--reference", action="store_true", help="--dense: also the compiled reference at 16 and 1 threads")
     ap.add_argument("--render")
     ap.add_argument("--kernel-stats")
     ap.add_argument("--trace-runs", type=int, default=2, help="clusterings per shape in the traced run (its warm-ups + reps)")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "clustering.md"))
     args = ap.parse_args()
+    if args.dense:
+        json.dump(measure_dense(args), open(args.out, "w"), indent=1)
+        print("wrote", args.out)
+        return
     if args.render:
         res = json.load(open(args.render))
     else:
