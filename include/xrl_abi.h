@@ -597,7 +597,7 @@ int xrl_debug_cluster_dense_forms(uint64_t* out, uint32_t n);
  * stream) and SYNCHRONISES it before it returns.  Refused, before a GPU is required (messages start with the function's name): null
  * handles; dense handles; Y.rows != X.rows; Z.rows != Y.cols; an unknown method; operands on two devices; widths that add up to 2^32 or
  * more; 2^32 - 1 entries or more to transpose.  Refused by a kernel: an entry to transpose whose column id is not below cols.  Zero
- * rows, zero columns and nnz == 0 succeed and give empty handles.  Dense X / Z and pifa_lf_convex_combine are not served.
+ * rows, zero columns and nnz == 0 succeed and give empty handles.  A dense X (and Z) is served by xrl_label_embedding_dense_device below; pifa_lf_convex_combine is not served.
  *   xrl_smat_transpose_device       a NEW owned handle, cols x rows, by R2
  *   xrl_smat_normalize_rows_device  R1 (L2 only).  in_place: writes the handle's own val array -- for a handle that wraps caller memory
  *                                   (xrl_smat_from_device_csr) that IS the caller's array; `out` is not touched.  Otherwise *out <- a NEW
@@ -616,6 +616,40 @@ int xrl_smat_normalize_rows_norm_device(void* A, int norm, int in_place, void** 
 void* xrl_smat_hstack_device(void* const* mats, uint32_t n, void* hip_stream);
 void* xrl_label_embedding_device(void* Y, void* X, void* Z_or_null, int method, int normalized_Y, void* hip_stream);
 int xrl_debug_embed_forms(uint64_t* out, uint32_t n);
+
+/* ------------------------------------------------------------------------------------------
+ * LABEL EMBEDDINGS OVER DENSE FEATURES (K12D, csrc/xrl_embed_dense.hip): LabelEmbeddingFactory.pifa / pifa_lf_concat for a dense row-major
+ * float32 X (samples x features) in HBM -- the branch `YT.dot(X)` of pecos/xmc/base.py:1967-1975 -- written once as the dense row-major
+ * matrix xrl_run_clustering_dense_device takes.
+ * R3D, in two parts.
+ *   The product is scipy's csr_matvecs: P[r, k] starts at +0.0 and takes the stored entries (i, a) of row r of the CSR in STORED order,
+ *   P[r, k] = fl32(P[r, k] + fl32(a * X[i, k])) -- one fp32 chain per output element, the product and the sum rounded separately (no
+ *   fma), the same for any row stride of X.  Bit for bit scipy's YT.dot(X).
+ *   The normalisation is R1 applied to the dense row: s is a double from +0.0, s = s + (double)fl32(v * v) over the row's columns in
+ *   ascending order; s == 0.0 leaves the row as it is; otherwise every element becomes (float)((double)v / sqrt(s)); NaN and inf as in
+ *   R1.  Zeros add +0.0 to a non-negative chain, so this is bit for bit sklearn's normalize(csr_matrix(P)) -- the arithmetic of the CSR
+ *   path.  It is NOT pinned to sklearn's dense path, whose norms come from np.einsum("ij,ij->i") in an order that belongs to numpy's
+ *   build: the two differ by a few ulp (DESIGN.md 9 gives the bound and the measured distance).
+ * pifa(Y, X): Yn = R1(Y) when normalized_Y, else Y; YT = R2(Yn); E = the normalised product of YT and X.  pifa_lf_concat(Y, X, Z), Z
+ * dense, labels x label-features: [E | Z], E written straight into the left block and Z copied into the right one.
+ * Every call runs on hip_stream and SYNCHRONISES it before it returns; 0, or -1 + xrl_last_error.  Strides are in floats.  Refused,
+ * before a GPU is required (messages start with the function's name): a null or dense handle; a row stride below the width; A.cols !=
+ * x_rows; a null X, Z or out that has elements; out overlapping X or Z; an unknown method (pii has no dense operand; a dense / sparse mix
+ * of X and Z and pifa_lf_convex_combine are not served); widths that add up to 2^32 or more; 2^32 - 1 entries or more to transpose.
+ * Refused by a kernel: an entry of A whose column id is not below A.cols.  Zero labels, zero columns and an empty Y succeed.
+ *   xrl_smat_matmul_dense_device      d_out[r * out_row_stride + out_col0 + k] <- the product's first part alone (no normalisation), A an
+ *                                     xrl_smat_* CSR handle, r < A.rows, k < x_cols: the roll-up of a dense embedding
+ *   xrl_label_embedding_dense_device  method 0 = pifa, 1 = pifa_lf_concat; Y an xrl_smat_* CSR handle (samples x labels) that stays as it
+ *                                     is; d_X [Y.rows x x_cols], d_Z [Y.cols x z_cols] (method 1), d_out [Y.cols x (x_cols + z_cols)]
+ *   xrl_debug_embed_dense_forms       FOR TESTS ONLY: out[0..n), n <= 4 <- {the long form's threshold (xrl_embed.h: kEmbedDenseLong), rows
+ *                                     served by the narrow form, by the slab form, by the long form} of this process since the load
+ *   xrl_debug_embed_dense_long        FOR THE PROBE ONLY: the long form's threshold of this process; 0 puts kEmbedDenseLong back */
+int xrl_smat_matmul_dense_device(void* A, const float* d_X, uint64_t x_rows, uint64_t x_cols, uint64_t x_row_stride, float* d_out, uint64_t out_row_stride,
+                                 uint64_t out_col0, void* hip_stream);
+int xrl_label_embedding_dense_device(void* Y, const float* d_X, uint64_t x_cols, uint64_t x_row_stride, const float* d_Z_or_null, uint64_t z_cols, uint64_t z_row_stride,
+                                     int method, int normalized_Y, float* d_out, uint64_t out_row_stride, void* hip_stream);
+int xrl_debug_embed_dense_forms(uint64_t* out, uint32_t n);
+int xrl_debug_embed_dense_long(uint32_t long_min);
 
 /* ------------------------------------------------------------------------------------------
  * RANKER TRAINING ON THE DEVICE (K13, csrc/xrl_train.hip): one layer of XR-Linear's weights from X (N x d), the label matrix Y (N x L),

@@ -11,7 +11,8 @@ from .indexer import HierarchicalKMeans, LabelEmbeddingFactory, label_embedding_
 from .cluster_chain import ClusterChain  # noqa: F401
 from .training import matching_chain_device, relevance_chain_device, single_layer_predict_device, train_chain_device, train_layer_device  # noqa: F401
 from .ann import HNSW, HNSWProductQuantizer4Bits, PairwiseANN, hnsw_predict_device  # noqa: F401
-from . import hnsw, pairwise  # noqa: F401
+from . import embedding, hnsw, pairwise  # noqa: F401
+from .embedding import label_embedding_dense_device, sparse_dense_matmul_device  # noqa: F401
 from .pairwise import pairwise_predict_device  # noqa: F401
 from .xlinear import HierarchicalMLModel, MLModel, MLProblem, XLinearModel  # noqa: F401
 
@@ -19,4 +20,5 @@ __all__ = ["clib", "XLinearModel", "HierarchicalMLModel", "MLModel", "MLProblem"
            "DeviceMatrix", "sparse_matmul_device", "result_to_csr_device", "HierarchicalKMeans", "run_clustering_device",
            "LabelEmbeddingFactory", "label_embedding_device", "train_layer_device", "train_chain_device",
            "single_layer_predict_device", "ClusterChain", "relevance_chain_device", "matching_chain_device", "Tfidf", "Preprocessor", "tfidf_train_device", "tfidf_transform_device",
-           "HNSW", "PairwiseANN", "HNSWProductQuantizer4Bits", "hnsw_predict_device", "hnsw", "pairwise", "pairwise_predict_device"]
+           "HNSW", "PairwiseANN", "HNSWProductQuantizer4Bits", "hnsw_predict_device", "hnsw", "pairwise", "pairwise_predict_device",
+           "embedding", "label_embedding_dense_device", "sparse_dense_matmul_device"]

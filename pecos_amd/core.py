@@ -340,6 +340,10 @@ class corelib(object):
         "xrl_smat_hstack_device": (c_void_p, [POINTER(c_void_p), c_uint32, c_void_p]),
         "xrl_label_embedding_device": (c_void_p, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
         "xrl_debug_embed_forms": (c_int, [POINTER(c_uint64), c_uint32]),
+        "xrl_smat_matmul_dense_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_uint64, c_void_p, c_uint64, c_uint64, c_void_p]),
+        "xrl_label_embedding_dense_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_uint64, c_uint64, c_int, c_int, c_void_p, c_uint64, c_void_p]),
+        "xrl_debug_embed_dense_forms": (c_int, [POINTER(c_uint64), c_uint32]),
+        "xrl_debug_embed_dense_long": (c_int, [c_uint32]),
         "xrl_single_layer_train_csr_f32": (None, [POINTER(ScipyCsrF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32),
                                                         _coo_alloc_t, c_double, c_uint32, c_int, c_double, c_double, c_uint64, c_double, c_double, c_int]),
         "xrl_single_layer_train_drm_f32": (None, [POINTER(ScipyDrmF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32), POINTER(ScipyCscF32),
@@ -794,6 +798,41 @@ class corelib(object):
         self.clib_float32.xrl_debug_embed_forms(out, 5)
         self._check()
         return dict(zip(("cap", "t_lds", "t_big", "n_lane", "n_wave"), (int(v) for v in out)))
+
+    # ------------------------------------------------------------------ label embeddings over dense features (K12D)
+    EMBED_DENSE_METHODS = {"pifa": 0, "pifa_lf_concat": 1}
+
+    def smat_matmul_dense_device(self, A, d_X, x_rows, x_cols, x_row_stride, d_out, out_row_stride, out_col0=0, stream=None):
+        """``out[:, out_col0 : out_col0 + x_cols] <- A * X`` for a CSR handle ``A`` and a dense row-major float32 ``X`` at the device address
+        ``d_X`` (strides in floats), in scipy's order of additions."""
+        rc = self.clib_float32.xrl_smat_matmul_dense_device(c_void_p(A), c_void_p(d_X or 0), int(x_rows), int(x_cols), int(x_row_stride), c_void_p(d_out or 0),
+                                                            int(out_row_stride), int(out_col0), c_void_p(stream or 0))
+        self._check()
+        return rc
+
+    def label_embedding_dense_device(self, Y, d_X, x_cols, x_row_stride, d_Z, z_cols, z_row_stride, method, normalized_Y, d_out, out_row_stride, stream=None):
+        """The PIFA embedding of the CSR handle ``Y`` over the dense ``X`` at ``d_X`` (and, ``pifa_lf_concat``, next to the dense ``Z`` at
+        ``d_Z``) written to the dense ``[Y.cols, x_cols + z_cols]`` matrix at ``d_out``; ``method`` is a name of :attr:`EMBED_DENSE_METHODS` or its number."""
+        m = self.EMBED_DENSE_METHODS.get(method, method) if isinstance(method, str) else method
+        if not isinstance(m, int):
+            raise NotImplementedError(f"label embedding method '{method}' is not served over dense features; served: {sorted(self.EMBED_DENSE_METHODS)}")
+        rc = self.clib_float32.xrl_label_embedding_dense_device(c_void_p(Y), c_void_p(d_X or 0), int(x_cols), int(x_row_stride), c_void_p(d_Z or 0), int(z_cols),
+                                                                int(z_row_stride), m, 1 if normalized_Y else 0, c_void_p(d_out or 0), int(out_row_stride),
+                                                                c_void_p(stream or 0))
+        self._check()
+        return rc
+
+    def debug_embed_dense_forms(self):
+        """Debug counters of K12D since the load: the long form's threshold, rows served by the narrow, the slab and the long form."""
+        out = (c_uint64 * 4)()
+        self.clib_float32.xrl_debug_embed_dense_forms(out, 4)
+        self._check()
+        return dict(zip(("long_min", "narrow", "slab", "long"), (int(v) for v in out)))
+
+    def debug_embed_dense_long(self, long_min=0):
+        """For the probe: the long form's threshold of this process (0: the built-in one)."""
+        self.clib_float32.xrl_debug_embed_dense_long(int(long_min))
+        self._check()
 
     # ------------------------------------------------------------------ ranker training (K13)
     TRAIN_COUNTERS = ("jobs", "batches", "slots", "stride", "iters", "shrinks", "reactivations", "max_iter_stops", "clipped", "lane_rows", "wave_rows",

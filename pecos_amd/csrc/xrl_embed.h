@@ -30,4 +30,21 @@ void normalize_rows_device(const char* what, const QueriesDev& A, float* out_val
 // out <- [M0 M1 ...] of CSR views with one row count (the callers check it, and that the widths sum below 2^32).  Enqueues on s and synchronises it.
 void hstack_device(const char* what, const std::vector<QueriesDev>& mats, hipStream_t s, DevCsr& out);
 
+// ---- K12D (xrl_embed_dense.hip): a CSR times a dense row-major matrix in HBM, the rule R3D of xrl_label_embedding_dense_device
+// A row of A with this many entries and more is served one column per lane (64-column slabs) instead of four: more wavefronts share
+// the serial walk of its entries.  Picked from the first timing (profiles/label_embedding_dense.md).
+constexpr uint32_t kEmbedDenseLong = 512;
+
+// rows of A served by the narrow form (cols <= 128, several rows to a wavefront), the slab form and the long form
+struct EmbedDenseForms { uint64_t narrow = 0, slab = 0, lng = 0; };
+
+// out[r * out_stride + out_col0 + k] <- the fp32 chain, from +0.0 and in stored order over row r of A, of fl32(a * x[i * x_stride + k]), k < cols;
+// with `normalize` every row is then divided by its norm under R1 before it is written.  A: a CSR view whose cols are x's rows; x_stride >=
+// cols, out_stride >= out_col0 + cols; long_min >= 1 (kEmbedDenseLong but in the probe).  Fails when an entry of A names a column >= A.cols.
+// Enqueues on s and synchronises it.
+void spmm_dense_device(const char* what, const QueriesDev& A, const float* x, uint64_t x_stride, uint32_t cols, float* out, uint64_t out_stride, uint64_t out_col0,
+                       bool normalize, uint32_t long_min, hipStream_t s, EmbedDenseForms& forms);
+// dst[r * dst_stride + k] <- src[r * src_stride + k], r < rows, k < cols.  Enqueues on s.
+void copy_block_device(const char* what, const float* src, uint64_t src_stride, float* dst, uint64_t dst_stride, uint64_t rows, uint32_t cols, hipStream_t s);
+
 }  // namespace xrl

@@ -1,6 +1,7 @@
 // Label embeddings on the device (K12, xrl_embed.hip, composed with K10): the transpose, row normalisation and hstack of matrix handles,
-// and xrl_label_embedding_device = LabelEmbeddingFactory.create (pecos/xmc/base.py:1903-2094) for CSR operands.  Every argument is
-// checked before a GPU is required.
+// and xrl_label_embedding_device = LabelEmbeddingFactory.create (pecos/xmc/base.py:1903-2094) for CSR operands; over dense features
+// (K12D, xrl_embed_dense.hip) xrl_smat_matmul_dense_device and xrl_label_embedding_dense_device.  Every argument is checked before a GPU
+// is required.
 #include <atomic>
 #include <memory>
 
@@ -13,6 +14,28 @@ using namespace xrl;
 namespace {
 
 std::atomic<uint64_t> g_forms[4];                          // of this process since the load: EmbedForms' four counts
+
+std::atomic<uint64_t> g_dense_forms[3];                    // ... EmbedDenseForms' three counts
+std::atomic<uint32_t> g_dense_long{kEmbedDenseLong};       // the long form's threshold (xrl_debug_embed_dense_long)
+
+void count_forms(const EmbedDenseForms& f) { g_dense_forms[0] += f.narrow; g_dense_forms[1] += f.slab; g_dense_forms[2] += f.lng; }
+
+// a dense operand of K12D: rows x cols floats at p, row stride `stride`; what cannot be read is refused
+void check_dense(const std::string& what, const char* name, const void* p, uint64_t rows, uint64_t cols, uint64_t stride) {
+    if (cols >= (1ull << 32)) fail(what + ": " + name + " has 2^32 columns or more (" + std::to_string(cols) + ")");
+    if (stride < cols) fail(what + ": the row stride of " + name + " (" + std::to_string(stride) + ") is below its width (" + std::to_string(cols) + ")");
+    if (!p && rows && cols) fail(what + ": null argument (" + name + ")");
+}
+
+// the bytes [first, last) a dense window touches (empty: first == last)
+struct Span { uintptr_t first, last; };
+Span span_of(const float* p, uint64_t rows, uint64_t cols, uint64_t stride) {
+    const uintptr_t b = reinterpret_cast<uintptr_t>(p);
+    return rows && cols ? Span{b, b + (uintptr_t)(((rows - 1) * stride + cols) * 4)} : Span{b, b};
+}
+void check_apart(const std::string& what, const char* name, Span in, Span out) {
+    if (in.first < in.last && out.first < out.last && in.first < out.last && out.first < in.last) fail(what + ": out overlaps " + name);
+}
 
 void count_forms(const EmbedForms& f) { g_forms[0] += f.t_lds; g_forms[1] += f.t_big; g_forms[2] += f.n_lane; g_forms[3] += f.n_wave; }
 
@@ -160,6 +183,86 @@ void* xrl_label_embedding_device(void* Y, void* X, void* Z_or_null, int method, 
         DevCsr h;
         hstack_device(what.c_str(), {e->dev, z->dev}, s, h);
         return own_handle(std::move(h), y.device, y.dev.cols, x->dev.cols + z->dev.cols).release();
+    });
+}
+
+int xrl_smat_matmul_dense_device(void* A, const float* d_X, uint64_t x_rows, uint64_t x_cols, uint64_t x_row_stride, float* d_out, uint64_t out_row_stride,
+                                 uint64_t out_col0, void* hip_stream) {
+    return guarded_value(-1, [&] {
+        const std::string what = "xrl_smat_matmul_dense_device";
+        const Queries& a = csr_handle(what + ": ", A, "A");
+        check_dense(what, "X", d_X, x_rows, x_cols, x_row_stride);
+        if (a.dev.cols != x_rows) fail(what + ": A.cols != X.rows (" + std::to_string(a.dev.cols) + " != " + std::to_string(x_rows) + ")");
+        if (out_row_stride < out_col0 + x_cols)
+            fail(what + ": the row stride of out (" + std::to_string(out_row_stride) + ") is below out_col0 + X.cols (" + std::to_string(out_col0 + x_cols) + ")");
+        if (!d_out && a.dev.rows && x_cols) fail(what + ": null argument (out)");
+        check_apart(what, "X", span_of(d_X, x_rows, x_cols, x_row_stride), span_of(d_out + out_col0, a.dev.rows, x_cols, out_row_stride));
+        require_gpu();
+        use_device(a.device);
+        EmbedDenseForms f;
+        spmm_dense_device(what.c_str(), a.dev, d_X, x_row_stride, (uint32_t)x_cols, d_out, out_row_stride, out_col0, false, g_dense_long.load(),
+                          static_cast<hipStream_t>(hip_stream), f);
+        count_forms(f);
+        return 0;
+    });
+}
+
+int xrl_label_embedding_dense_device(void* Y, const float* d_X, uint64_t x_cols, uint64_t x_row_stride, const float* d_Z_or_null, uint64_t z_cols, uint64_t z_row_stride,
+                                     int method, int normalized_Y, float* d_out, uint64_t out_row_stride, void* hip_stream) {
+    return guarded_value(-1, [&] {
+        const std::string what = "xrl_label_embedding_dense_device";
+        if (method < 0 || method > 1) fail(what + ": unknown method " + std::to_string(method) + " (0 = pifa, 1 = pifa_lf_concat; pii has no dense operand)");
+        const Queries& y = csr_handle(what + ": ", Y, "Y");
+        check_transposable(what, y);
+        const uint64_t samples = y.dev.rows, labels = y.dev.cols;
+        if (method == 0) z_cols = 0;
+        check_dense(what, "X", d_X, samples, x_cols, x_row_stride);
+        if (method == 1) check_dense(what, "Z", d_Z_or_null, labels, z_cols, z_row_stride);
+        const uint64_t width = x_cols + z_cols;
+        if (width >= (1ull << 32)) fail(what + ": X.cols + Z.cols is 2^32 or more");
+        if (out_row_stride < width) fail(what + ": the row stride of out (" + std::to_string(out_row_stride) + ") is below its width (" + std::to_string(width) + ")");
+        if (!d_out && labels && width) fail(what + ": null argument (out)");
+        const Span o = span_of(d_out, labels, width, out_row_stride);
+        check_apart(what, "X", span_of(d_X, samples, x_cols, x_row_stride), o);
+        check_apart(what, "Z", span_of(d_Z_or_null, labels, z_cols, z_row_stride), o);
+        require_gpu();
+        use_device(y.device);
+        hipStream_t s = static_cast<hipStream_t>(hip_stream);
+        EmbedForms f;
+        EmbedDenseForms fd;
+        DevCsr yt;
+        {
+            QueriesDev yn = y.dev;
+            DevBuf nval;                                   // the normalised Y is a private copy of its values: Y stays as it is
+            if (normalized_Y) {
+                nval.reserve(y.dev.nnz * 4);
+                normalize_rows_device(what.c_str(), y.dev, nval.as<float>(), s, f);
+                yn.val = nval.as<float>();
+            }
+            transpose_device(what.c_str(), yn, s, yt, f);
+        }
+        const QueriesDev ytv = csr_view(y.dev.cols, y.dev.rows, yt.ptr.as<uint64_t>(), yt.idx.as<uint32_t>(), yt.val.as<float>(), yt.nnz);
+        if (z_cols) copy_block_device(what.c_str(), d_Z_or_null, z_row_stride, d_out + x_cols, out_row_stride, labels, (uint32_t)z_cols, s);
+        spmm_dense_device(what.c_str(), ytv, d_X, x_row_stride, (uint32_t)x_cols, d_out, out_row_stride, 0, true, g_dense_long.load(), s, fd);
+        count_forms(f);
+        count_forms(fd);
+        return 0;
+    });
+}
+
+int xrl_debug_embed_dense_forms(uint64_t* out, uint32_t n) {
+    return guarded_value(-1, [&] {
+        if (!out) fail("xrl_debug_embed_dense_forms: null argument");
+        const uint64_t v[4] = {g_dense_long.load(), g_dense_forms[0].load(), g_dense_forms[1].load(), g_dense_forms[2].load()};
+        for (uint32_t i = 0; i < n && i < 4; ++i) out[i] = v[i];
+        return 0;
+    });
+}
+
+int xrl_debug_embed_dense_long(uint32_t long_min) {
+    return guarded_value(-1, [&] {
+        g_dense_long.store(long_min ? long_min : kEmbedDenseLong);
+        return 0;
     });
 }
 
