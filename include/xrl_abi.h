@@ -723,7 +723,27 @@ int xrl_debug_embed_dense_long(uint32_t long_min);
  *                                Runs on hip_stream and synchronises it per batch.  NULL + xrl_last_error on failure.
  *   xrl_debug_train_counters     FOR TESTS ONLY: of the last training of this process, out[0..n), n <= 13 <- {jobs, batches, slots, staging
  *                                stride, sweeps, shrink events, re-activations, jobs stopped by max_iter, alpha clipped at C, x'x rows
- *                                summed one per lane, by a wavefront (64 entries and more), table extensions, jobs run again} */
+ *                                summed one per lane, by a wavefront (64 entries and more), table extensions, jobs run again}
+ * OVER DENSE FEATURES (K13D, csrc/xrl_train_dense.hip): X a dense row-major float32 matrix (N x d) in HBM, read in place -- the E or X that
+ * xrl_label_embedding_dense_device and xrl_run_clustering_dense_device leave or take there.
+ * R13D.  THE RULE above on rows that store EVERY column, zeros included: the reference's dense trainer walks every column of a row in
+ *   ascending order (do_dot_product(dense, dense), matrix.hpp:862-868; do_axpy(dense, dense), :965-969), one unfused fp32 loop each, which
+ *   is the rule on the CSR of all N * d entries.  dot and xx are ONE fp32 chain from +0 over columns 0 .. d-1 of fl32(w[f] * X[i, f])
+ *   and fl32(X[i, f] * X[i, f]), the product and the sum rounded separately (no fma), the same for any row stride; the axpy updates every
+ *   column.  No zero is skipped: a stored zero that meets an infinite or NaN w gives a NaN product, and the set-up's (+-)0 * x makes
+ *   w[f] a NaN wherever a listed instance holds an inf or a NaN at f.  W^T equals xrl_train_layer_device's on that CSR in rows, columns
+ *   and value bits, and the counters keep their meanings: per listed position a row counts as summed by a wavefront when d >= 64, one
+ *   per lane otherwise.
+ *   xrl_train_layer_dense_device  d_X [rows x cols] at row_stride >= cols floats (the floats between cols and the stride are never read;
+ *                                d_X is not written) on `device`; the other arguments, the result and the failure convention are
+ *                                xrl_train_layer_device's, and so is every refusal that does not concern X's CSR arrays, in the same
+ *                                words.  Refused too, before a GPU is required: a null d_X with a non-empty shape; row_stride < cols;
+ *                                cols > 16384 (w is kept in registers up to 1024 columns, in LDS up to 16384); a solver other than 1
+ *                                and 3 (solver 2 keeps its own names and the CSR route).  Zero rows, zero columns and zero labels
+ *                                succeed.  xrl_single_layer_train_drm_f32 takes this route up to 16384 columns -- the caller's array is
+ *                                uploaded as it is, no index array is built -- and the CSR of all entries above.
+ *   xrl_debug_train_dense_forms  FOR TESTS ONLY: out[0..n), n <= 4 <- {the register form's column limit, the LDS form's column limit,
+ *                                jobs served by the register form, by the LDS form} of this process since the load */
 typedef void (*py_coo_allocator_t)(uint64_t rows, uint64_t cols, uint64_t nnz, void* row_pp, void* col_pp, void* val_pp);   /* matrix.hpp:46: u64 rows, u64 cols, f32 values */
 void xrl_single_layer_train_csr_f32(const ScipyCsrF32* pX, const ScipyCscF32* pY, const ScipyCscF32* pC, const ScipyCscF32* pM, const ScipyCscF32* pR,
                                     py_coo_allocator_t coo_alloc, double threshold, uint32_t max_nonzeros_per_label, int solver_type, double Cp, double Cn,
@@ -734,6 +754,10 @@ void xrl_single_layer_train_drm_f32(const ScipyDrmF32* pX, const ScipyCscF32* pY
 void* xrl_train_layer_device(void* X, void* Yt, void* Ct_or_null, void* Mt_or_null, void* Rt_or_null, double threshold, uint32_t max_nonzeros_per_label,
                              int solver_type, double Cp, double Cn, uint64_t max_iter, double eps, double bias, void* hip_stream);
 int xrl_debug_train_counters(uint64_t* out, uint32_t n);
+void* xrl_train_layer_dense_device(int device, const float* d_X, uint64_t rows, uint64_t cols, uint64_t row_stride, void* Yt, void* Ct_or_null, void* Mt_or_null,
+                                   void* Rt_or_null, double threshold, uint32_t max_nonzeros_per_label, int solver_type, double Cp, double Cn, uint64_t max_iter,
+                                   double eps, double bias, void* hip_stream);
+int xrl_debug_train_dense_forms(uint64_t* out, uint32_t n);
 
 /* The primal solver for the L2-loss SVC on the device (K16, csrc/xrl_newton.hip): L2R_L2LOSS_SVC_PRIMAL = 2 of the reference's solver table,
  * SVMWorker::solve_l2r_l2_svc_primal (linear_solver.hpp:407-417) over l2r_erm_fun / l2r_l2_svc_fun (:62-323), NEWTON::newton / pcg / norm

@@ -46,6 +46,28 @@ constexpr uint32_t kTrainCounterCount = 13;
 void train_layer_device(const char* what, const QueriesDev& X, const QueriesDev& Yt, const float* r_val, const QueriesDev* Ct, const QueriesDev* Mt,
                         const TrainParams& p, hipStream_t s, DevCsr& out, TrainCounters& counters);
 
+// ---- K13D (xrl_train_dense.hip): the same jobs over a dense row-major X in HBM, read in place
+// A step is 256 columns: lane l of the wavefront owns columns 256 s + 4 l .. + 3 of every step s.  Up to kTrainDenseRegSteps steps w and
+// the current row live in the owning lane's registers; above, up to kTrainDenseMaxCols columns, w lives in the workgroup's LDS.
+constexpr uint32_t kTrainDenseStep = 256, kTrainDenseRegSteps = 4;
+constexpr uint32_t kTrainDenseRegCols = kTrainDenseStep * kTrainDenseRegSteps, kTrainDenseMaxCols = 16384;
+// the LDS a CU gives the LDS form's workgroups (one wavefront each)
+constexpr uint32_t kTrainDenseLdsPerCu = 160u << 10;
+
+struct TrainDenseX { const float* val; uint32_t rows, cols; uint64_t row_stride; };   // row_stride >= cols, in floats; cols <= kTrainDenseMaxCols
+
+// train_layer_device for a dense X: the same W^T (R13D in include/xrl_abi.h), the same counters.
+void train_layer_dense_device(const char* what, const TrainDenseX& X, const QueriesDev& Yt, const float* r_val, const QueriesDev* Ct, const QueriesDev* Mt,
+                              const TrainParams& p, hipStream_t s, DevCsr& out, TrainCounters& counters);
+
+struct K13Args;
+// the most wavefronts K13D trains at once over `cols` columns: K13's count, in the LDS form what the CUs' LDS holds
+uint32_t train_dense_max_slots(uint32_t cols);
+// k13d_solve over `blocks` slots on s; `first`: the jobs are counted under the form that serves them (not a run after a table extension)
+void train_dense_launch(const K13Args& a, const TrainDenseX& X, uint32_t blocks, bool first, hipStream_t s);
+// {register-form column limit, LDS-form column limit, jobs served by the register form, by the LDS form} of this process since the load
+void train_dense_forms(uint64_t (&out)[4]);
+
 // fails unless B's row pointer and column ids are A's (the relevance matrix against Y^T; shapes and nnz already agree).  Synchronises s.
 void same_pattern_device(const char* what, const QueriesDev& A, const QueriesDev& B, hipStream_t s);
 

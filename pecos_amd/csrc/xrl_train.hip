@@ -15,7 +15,8 @@
 //                    jobs run again from their start.  Loop bounds: a sweep visits at most `active` coordinates (each visit advances or
 //                    shrinks), sweeps <= max_iter, a draw's rejections end with the table.
 //   k13_label_counts, k13_place   the jobs' staged rows -> W^T by label
-// A job's set-up and emission are xrl_train_job.h's, shared with K16 (xrl_newton.hip); train_layer below drives a layer for either solver.
+// A job's set-up and emission are xrl_train_job.h's, shared with K16 (xrl_newton.hip); the shuffle and a launch's arguments are there too,
+// shared with K13D (xrl_train_dense.hip: the same jobs over a dense X).  train_layer below drives a layer for either solver and either X.
 #include <cstdlib>
 #include <random>
 
@@ -60,9 +61,10 @@ __global__ void __launch_bounds__(256) k13_labels(const uint32_t* __restrict__ c
 }
 
 // rows [0, m_rows) of M^T then rows of Y^T: out[0] / out[2] <- the longest row, out[1] / out[3] <- the largest sum of the feature-row lengths of a row's instances
+// (x_ptr null: a dense X, every feature row stores x_cols entries)
 __global__ void __launch_bounds__(256)
 k13_sizes(const uint64_t* __restrict__ m_ptr, const uint32_t* __restrict__ m_idx, uint32_t m_rows, const uint64_t* __restrict__ y_ptr, const uint32_t* __restrict__ y_idx,
-          uint32_t y_rows, const uint64_t* __restrict__ x_ptr, unsigned long long* __restrict__ out) {
+          uint32_t y_rows, const uint64_t* __restrict__ x_ptr, uint32_t x_cols, unsigned long long* __restrict__ out) {
     const uint32_t r0 = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (r0 >= m_rows + y_rows) return;
     const bool isy = r0 >= m_rows;
@@ -71,67 +73,9 @@ k13_sizes(const uint64_t* __restrict__ m_ptr, const uint32_t* __restrict__ m_idx
     const uint32_t* idx = isy ? y_idx : m_idx;
     const uint64_t b = ptr[r], e = ptr[r + 1];
     unsigned long long sum = 0;
-    for (uint64_t x = b + lane; x < e; x += 64u) { const uint32_t i = idx[x]; sum += x_ptr[i + 1] - x_ptr[i]; }
+    for (uint64_t x = b + lane; x < e; x += 64u) { const uint32_t i = idx[x]; sum += x_ptr ? x_ptr[i + 1] - x_ptr[i] : x_cols; }
     for (int d = 1; d < 64; d <<= 1) sum += __shfl_xor(sum, d, 64);
     if (lane == 0) { atomicMax(&out[isy ? 2 : 0], (unsigned long long)(e - b)); atomicMax(&out[isy ? 3 : 1], sum); }
-}
-
-struct K13Args : TrainJobArgs {
-    int l2loss; uint64_t max_iter;
-    // the rest of a slot's scratch, [slot * its size]
-    float* alpha; float* qd;
-    const uint32_t* table; uint64_t table_n;
-    const uint32_t* job_list; uint32_t n_jobs; uint32_t* next;            // job_list null: jobs job0 .. job0 + n_jobs - 1
-    uint32_t* redo; uint32_t* n_redo;
-    unsigned long long* counters;                                          // iters, shrinks, reactivations, max_iter stops, clipped, lane rows, wave rows
-};
-
-// one uniform draw in [0, range), 1 <= range < 2^32: libstdc++'s uniform_int_distribution over a 32-bit generator (_S_nd: Lemire's
-// multiply with the (-range) % range rejection).  false: the table ended.
-__device__ __forceinline__ bool k13_draw(const uint32_t* __restrict__ table, uint64_t tn, uint64_t& cur, uint32_t range, uint32_t& out) {
-    if (cur >= tn) return false;
-    uint64_t prod = (uint64_t)table[cur++] * range;
-    uint32_t low = (uint32_t)prod;
-    if (low < range) {
-        const uint32_t thr = (0u - range) % range;
-        while (low < thr) {
-            if (cur >= tn) return false;
-            prod = (uint64_t)table[cur++] * range;
-            low = (uint32_t)prod;
-        }
-    }
-    out = (uint32_t)(prod >> 32);
-    return true;
-}
-
-__device__ __forceinline__ bool k13_not_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u; }
-
-__device__ __forceinline__ void k13_swap(uint32_t* a, uint32_t i, uint32_t j) { const uint32_t t = a[i]; a[i] = a[j]; a[j] = t; }
-
-// libstdc++'s std::shuffle (bits/stl_algo.h) of a[0, n) by one lane
-__device__ bool k13_shuffle(uint32_t* a, uint32_t n, const uint32_t* __restrict__ table, uint64_t tn, uint64_t& cur) {
-    if (n < 2) return true;
-    uint32_t r;
-    if (n <= 65535u) {
-        uint32_t i = 1;
-        if ((n & 1u) == 0) {
-            if (!k13_draw(table, tn, cur, 2u, r)) return false;
-            k13_swap(a, 1, r);
-            i = 2;
-        }
-        for (; i < n; i += 2) {
-            const uint32_t sr = i + 1u;
-            if (!k13_draw(table, tn, cur, sr * (sr + 1u), r)) return false;
-            k13_swap(a, i, r / (sr + 1u));
-            k13_swap(a, i + 1, r % (sr + 1u));
-        }
-        return true;
-    }
-    for (uint32_t i = 1; i < n; ++i) {
-        if (!k13_draw(table, tn, cur, i + 1u, r)) return false;
-        k13_swap(a, i, r);
-    }
-    return true;
 }
 
 __device__ void k13_job(const K13Args& a, uint32_t job, uint32_t slot, uint32_t lane, unsigned long long (&ctr)[7]) {
@@ -369,8 +313,9 @@ void check_train_params(const std::string& what, const TrainParams& p) {
 namespace {
 
 // One layer, whichever solver: the checks, the sizes of a slot and of a staging row, the batches under the scratch budget, and W^T by
-// label.  newton (NT) or the dual coordinate descent (T); the caller has refused the solvers its entry point does not serve.
-void train_layer(const char* what_c, const QueriesDev& X, const QueriesDev& Yt, const float* r_val, const QueriesDev* Ct, const QueriesDev* Mt,
+// label.  newton (NT) or the dual coordinate descent (T); the caller has refused the solvers its entry point does not serve.  D: X is the
+// dense row-major matrix D describes (K13D serves the jobs); of X itself only rows, cols and nnz = rows * cols are then read.
+void train_layer(const char* what_c, const QueriesDev& X, const TrainDenseX* D, const QueriesDev& Yt, const float* r_val, const QueriesDev* Ct, const QueriesDev* Mt,
                  const TrainParams& p, hipStream_t s, DevCsr& out, TrainCounters& T, NewtonCounters* NT) {
     const std::string what = std::string(what_c) + ": ";
     const bool newton = NT != nullptr;
@@ -383,7 +328,7 @@ void train_layer(const char* what_c, const QueriesDev& X, const QueriesDev& Yt, 
     DevBuf flags, tmp;
     flags.reserve(4);
     XRL_HIP(hipMemsetAsync(flags.p, 0, 4, s));
-    check_csr(what, "X", X, d, true, flags, s);
+    if (!D) check_csr(what, "X", X, d, true, flags, s);
     if (newton) newton_check_finite(what, X, s);
     check_csr(what, "Y", Yt, N, false, flags, s);
     if (coded) {
@@ -407,7 +352,7 @@ void train_layer(const char* what_c, const QueriesDev& X, const QueriesDev& Yt, 
         const uint32_t mr = coded ? Mt->rows : 0u;
         if (mr + L) {
             hipLaunchKernelGGL(k13_sizes, dim3(blocks_of((uint64_t)mr + L, 4, kWhat)), dim3(256), 0, s, coded ? Mt->row_ptr : nullptr, coded ? Mt->col_idx : nullptr, mr,
-                               Yt.row_ptr, Yt.col_idx, L, X.row_ptr, sizes.as<unsigned long long>());
+                               Yt.row_ptr, Yt.col_idx, L, X.row_ptr, d, sizes.as<unsigned long long>());
             XRL_LAUNCH_CHECK();
         }
     }
@@ -426,7 +371,8 @@ void train_layer(const char* what_c, const QueriesDev& X, const QueriesDev& Yt, 
 
     const uint64_t budget = env_u64("XRL_TRAIN_SCRATCH_BYTES", kTrainScratchBytes);
     const uint64_t slot_bytes = (uint64_t)index_cap * 4 + (uint64_t)N * (newton ? 5 : 13) + (uint64_t)d * 4 + (uint64_t)dw * 4 + (newton ? newton_slot_bytes(N, d, index_cap) : 0);
-    const uint32_t slots = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({budget / std::max<uint64_t>(slot_bytes, 1), kTrainMaxSlots, std::max<uint32_t>(jobs, 1)}));
+    const uint32_t slots = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({budget / std::max<uint64_t>(slot_bytes, 1), D ? train_dense_max_slots(d) : kTrainMaxSlots,
+                                                                                std::max<uint32_t>(jobs, 1)}));
     const uint32_t batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(budget / (stride64 * 8), std::max<uint32_t>(jobs, 1)));
     T.jobs = jobs; T.slots = slots; T.stride = stride;
 
@@ -494,7 +440,8 @@ void train_layer(const char* what_c, const QueriesDev& X, const QueriesDev& Yt, 
         for (uint32_t ext = 0; !newton; ++ext) {
             a.table = b_table.as<uint32_t>(); a.table_n = table.size();
             XRL_HIP(hipMemsetAsync(b_next.p, 0, 8, s));
-            hipLaunchKernelGGL(k13_solve, dim3(std::min(slots, a.n_jobs)), dim3(64), 0, s, a);
+            if (D) train_dense_launch(a, *D, std::min(slots, a.n_jobs), ext == 0, s);
+            else hipLaunchKernelGGL(k13_solve, dim3(std::min(slots, a.n_jobs)), dim3(64), 0, s, a);
             XRL_LAUNCH_CHECK();
             uint32_t nr[2];
             XRL_HIP(hipMemcpyAsync(nr, b_next.p, 8, hipMemcpyDeviceToHost, s));
@@ -550,14 +497,22 @@ void train_layer(const char* what_c, const QueriesDev& X, const QueriesDev& Yt, 
 void train_layer_device(const char* what, const QueriesDev& X, const QueriesDev& Yt, const float* r_val, const QueriesDev* Ct, const QueriesDev* Mt,
                         const TrainParams& p, hipStream_t s, DevCsr& out, TrainCounters& T) {
     check_train_params(std::string(what) + ": ", p);
-    train_layer(what, X, Yt, r_val, Ct, Mt, p, s, out, T, nullptr);
+    train_layer(what, X, nullptr, Yt, r_val, Ct, Mt, p, s, out, T, nullptr);
+}
+
+void train_layer_dense_device(const char* what, const TrainDenseX& D, const QueriesDev& Yt, const float* r_val, const QueriesDev* Ct, const QueriesDev* Mt,
+                              const TrainParams& p, hipStream_t s, DevCsr& out, TrainCounters& T) {
+    check_train_params(std::string(what) + ": ", p);
+    QueriesDev X{};
+    X.rows = D.rows; X.cols = D.cols; X.nnz = (uint64_t)D.rows * D.cols;
+    train_layer(what, X, &D, Yt, r_val, Ct, Mt, p, s, out, T, nullptr);
 }
 
 void train_layer_newton_device(const char* what, const QueriesDev& X, const QueriesDev& Yt, const float* r_val, const QueriesDev* Ct, const QueriesDev* Mt,
                                const TrainParams& p, hipStream_t s, DevCsr& out, NewtonCounters& NT) {
     check_newton_params(std::string(what) + ": ", p);
     TrainCounters T;
-    train_layer(what, X, Yt, r_val, Ct, Mt, p, s, out, T, &NT);
+    train_layer(what, X, nullptr, Yt, r_val, Ct, Mt, p, s, out, T, &NT);
 }
 
 }  // namespace xrl

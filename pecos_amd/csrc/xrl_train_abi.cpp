@@ -1,8 +1,10 @@
 // Ranker training (K13, xrl_train.hip): xrl_single_layer_train_csr_f32 / _drm_f32 with the signatures of the reference's
 // c_xlinear_single_layer_train_* (libpecos.cpp:277-316 -> multilabel_train_with_codes, linear_solver.hpp:797-860) under this library's own
 // prefix -- a binding that takes this library first and the reference for the rest keeps the reference's trainer and all its solvers --,
-// the resident form xrl_train_layer_device over xrl_smat_* handles, and the counters the tests read.  Every argument is checked before a
+// the resident forms xrl_train_layer_device over xrl_smat_* handles and xrl_train_layer_dense_device over a dense X in HBM (K13D,
+// xrl_train_dense.hip), and the counters the tests read.  Every argument is checked before a
 // GPU is required where no data is read.
+#include <cstdlib>
 #include <memory>
 #include <mutex>
 
@@ -59,7 +61,7 @@ void upload_pattern(const ScipyCscF32* m, Uploaded& u) {
 
 // upload, train, copy back as the reference's COO at threads = 1: jobs code-major in C's stored order
 void train_host(const char* what_c, const ScipyCsrF32& X, const ScipyCscF32* pY, const ScipyCscF32* pC, const ScipyCscF32* pM, const ScipyCscF32* pR,
-                py_coo_allocator_t coo_alloc, const TrainParams& p, bool newton) {
+                py_coo_allocator_t coo_alloc, const TrainParams& p, bool newton, bool dense = false) {
     const std::string what = std::string(what_c) + ": ";
     check_solver(what, p, newton);
     if (!pY) fail(what + "null Y");
@@ -94,7 +96,8 @@ void train_host(const char* what_c, const ScipyCsrF32& X, const ScipyCscF32* pY,
     use_device(g_device);
     Uploaded x, y, c, m;
     DevBuf r;
-    upload(HostX(&X), x);
+    if (dense) x.own.val.upload_raw(X.val, (size_t)X.rows * X.cols * 4);                           // dense: X carries the shape and the values, 4 bytes per entry
+    else upload(HostX(&X), x);
     upload_pattern(pY, y);
     if (coded) { upload_pattern(pC, c); upload_pattern(pM, m); }
     if (pR) r.upload_raw(pR->val, (size_t)pY->col_ptr[pY->cols] * 4);
@@ -105,7 +108,10 @@ void train_host(const char* what_c, const ScipyCsrF32& X, const ScipyCscF32* pY,
         keep_counters(counters);
     } else {
         TrainCounters counters;
-        train_layer_device(what_c, x.v, y.v, pR ? r.as<float>() : nullptr, coded ? &c.v : nullptr, coded ? &m.v : nullptr, p, nullptr, wt, counters);
+        if (dense)
+            train_layer_dense_device(what_c, TrainDenseX{x.own.val.as<float>(), X.rows, X.cols, X.cols}, y.v, pR ? r.as<float>() : nullptr, coded ? &c.v : nullptr,
+                                     coded ? &m.v : nullptr, p, nullptr, wt, counters);
+        else train_layer_device(what_c, x.v, y.v, pR ? r.as<float>() : nullptr, coded ? &c.v : nullptr, coded ? &m.v : nullptr, p, nullptr, wt, counters);
         keep_counters(counters);
     }
     const uint32_t L = pY->cols;
@@ -144,6 +150,11 @@ void train_drm(const char* what, bool newton, const ScipyDrmF32* pX, const Scipy
         if (pX->rows >= (1u << 31)) fail(std::string(what) + ": 2^31 rows or more");
         if (pX->rows && pX->cols && !pX->val) fail(std::string(what) + ": null values (X)");
         check_solver(std::string(what) + ": ", p, newton);                                          // refusals come before the index arrays are built
+        if (!newton && pX->cols <= kTrainDenseMaxCols && !std::getenv("XRL_TRAIN_DRM_CSR")) {        // K13D: the array as it is (the variable: the probe's way to the route below)
+            const ScipyCsrF32 shape{pX->rows, pX->cols, nullptr, nullptr, pX->val};
+            train_host(what, shape, pY, pC, pM, pR, coo_alloc, p, newton, true);
+            return;
+        }
         const uint64_t n = (uint64_t)pX->rows * pX->cols;
         std::vector<uint64_t> ptr((size_t)pX->rows + 1);
         std::vector<uint32_t> idx((size_t)n);
@@ -154,12 +165,25 @@ void train_drm(const char* what, bool newton, const ScipyDrmF32* pX, const Scipy
     });
 }
 
-void* train_resident(const char* what_c, bool newton, void* X, void* Yt, void* Ct_or_null, void* Mt_or_null, void* Rt_or_null, const TrainParams& p, void* hip_stream) {
+// The refusals of a dense X that read no data (the resident entry point's; the host route falls back to the CSR of all entries instead)
+void check_dense_x(const std::string& what, const float* d_X, uint64_t rows, uint64_t cols, uint64_t row_stride) {
+    if (!d_X && rows && cols) fail(what + "null X");
+    if (row_stride < cols) fail(what + "row_stride " + std::to_string(row_stride) + " is below cols " + std::to_string(cols));
+    if (cols > kTrainDenseMaxCols)
+        fail(what + std::to_string(cols) + " columns: a dense X is served up to " + std::to_string(kTrainDenseMaxCols) + " (w is kept in registers or LDS); wider features train in CSR form");
+    if (rows >= (1ull << 31)) fail(what + "2^31 rows or more");
+}
+
+// X: a CSR handle, or (dense) null with *dx describing the matrix on dense_device
+void* train_resident(const char* what_c, bool newton, void* X, const TrainDenseX* dx, int dense_device, void* Yt, void* Ct_or_null, void* Mt_or_null, void* Rt_or_null,
+                     const TrainParams& p, void* hip_stream) {
     return guarded_value((void*)nullptr, [&]() -> void* {
         const std::string what = std::string(what_c) + ": ";
         const double bias = p.bias;
         check_solver(what, p, newton);
-        const Queries& x = csr_handle(what, X, "X");
+        Queries dense_x;                                                   // a dense X as the shape checks below read it: device, rows, cols
+        if (dx) { dense_x.device = dense_device; dense_x.dev.rows = dx->rows; dense_x.dev.cols = dx->cols; }
+        const Queries& x = dx ? dense_x : csr_handle(what, X, "X");
         const Queries& y = csr_handle(what, Yt, "Yt");
         if (Ct_or_null && !Mt_or_null) fail(what + "Ct comes without Mt");
         const Queries* c = Ct_or_null ? &csr_handle(what, Ct_or_null, "Ct") : nullptr;
@@ -187,7 +211,8 @@ void* train_resident(const char* what_c, bool newton, void* X, void* Yt, void* C
             keep_counters(counters);
         } else {
             TrainCounters counters;
-            train_layer_device(what_c, x.dev, y.dev, r ? r->dev.val : nullptr, c ? &c->dev : nullptr, m ? &m->dev : nullptr, p, s, out->own, counters);
+            if (dx) train_layer_dense_device(what_c, *dx, y.dev, r ? r->dev.val : nullptr, c ? &c->dev : nullptr, m ? &m->dev : nullptr, p, s, out->own, counters);
+            else train_layer_device(what_c, x.dev, y.dev, r ? r->dev.val : nullptr, c ? &c->dev : nullptr, m ? &m->dev : nullptr, p, s, out->own, counters);
             keep_counters(counters);
         }
         set_own_csr(*out, x.device, y.dev.rows, x.dev.cols + (bias > 0 ? 1u : 0u));
@@ -215,8 +240,24 @@ void xrl_single_layer_train_drm_f32(const ScipyDrmF32* pX, const ScipyCscF32* pY
 
 void* xrl_train_layer_device(void* X, void* Yt, void* Ct_or_null, void* Mt_or_null, void* Rt_or_null, double threshold, uint32_t max_nonzeros_per_label,
                              int solver_type, double Cp, double Cn, uint64_t max_iter, double eps, double bias, void* hip_stream) {
-    return train_resident("xrl_train_layer_device", false, X, Yt, Ct_or_null, Mt_or_null, Rt_or_null,
+    return train_resident("xrl_train_layer_device", false, X, nullptr, 0, Yt, Ct_or_null, Mt_or_null, Rt_or_null,
                           make_params(threshold, max_nonzeros_per_label, solver_type, Cp, Cn, max_iter, eps, bias), hip_stream);
+}
+
+void* xrl_train_layer_dense_device(int device, const float* d_X, uint64_t rows, uint64_t cols, uint64_t row_stride, void* Yt, void* Ct_or_null, void* Mt_or_null,
+                                   void* Rt_or_null, double threshold, uint32_t max_nonzeros_per_label, int solver_type, double Cp, double Cn, uint64_t max_iter,
+                                   double eps, double bias, void* hip_stream) {
+    const char* what = "xrl_train_layer_dense_device";
+    const TrainParams p = make_params(threshold, max_nonzeros_per_label, solver_type, Cp, Cn, max_iter, eps, bias);
+    TrainDenseX dx{};
+    if (guarded_value(-1, [&] {
+            check_train_params(std::string(what) + ": ", p);
+            check_dense_x(std::string(what) + ": ", d_X, rows, cols, row_stride);
+            dx = TrainDenseX{d_X, (uint32_t)rows, (uint32_t)cols, row_stride};
+            return 0;
+        }))
+        return nullptr;
+    return train_resident(what, false, nullptr, &dx, device, Yt, Ct_or_null, Mt_or_null, Rt_or_null, p, hip_stream);
 }
 
 // ---- the primal L2-loss SVC (K16): the same argument lists, solver_type == 2
@@ -236,7 +277,7 @@ void xrl_single_layer_train_newton_drm_f32(const ScipyDrmF32* pX, const ScipyCsc
 
 void* xrl_train_layer_newton_device(void* X, void* Yt, void* Ct_or_null, void* Mt_or_null, void* Rt_or_null, double threshold, uint32_t max_nonzeros_per_label,
                                     int solver_type, double Cp, double Cn, uint64_t max_iter, double eps, double bias, void* hip_stream) {
-    return train_resident("xrl_train_layer_newton_device", true, X, Yt, Ct_or_null, Mt_or_null, Rt_or_null,
+    return train_resident("xrl_train_layer_newton_device", true, X, nullptr, 0, Yt, Ct_or_null, Mt_or_null, Rt_or_null,
                           make_params(threshold, max_nonzeros_per_label, solver_type, Cp, Cn, max_iter, eps, bias), hip_stream);
 }
 
@@ -248,6 +289,16 @@ int xrl_debug_newton_counters(uint64_t* out, uint32_t n) {
         const uint64_t v[kNewtonCounterCount] = {c.jobs, c.batches, c.slots, c.stride, c.newton_iters, c.cg_iters, c.hv_calls, c.halvings, c.end_before_first, c.end_gradient,
                                                  c.end_linesearch, c.end_actred, c.end_cap, c.cg_dhd, c.cg_q, c.cg_positive, c.cg_cap, c.lane_rows, c.wave_rows, c.nonfinite_jobs};
         for (uint32_t i = 0; i < n && i < kNewtonCounterCount; ++i) out[i] = v[i];
+        return 0;
+    });
+}
+
+int xrl_debug_train_dense_forms(uint64_t* out, uint32_t n) {
+    return guarded_value(-1, [&] {
+        if (!out) fail("xrl_debug_train_dense_forms: null argument");
+        uint64_t v[4];
+        train_dense_forms(v);
+        for (uint32_t i = 0; i < n && i < 4; ++i) out[i] = v[i];
         return 0;
     });
 }

@@ -38,6 +38,65 @@ __device__ __forceinline__ uint32_t k13_word_mask(uint32_t wd, uint32_t d) { ret
 // (|w| bits, lower feature first) of a staged entry: the larger key is kept first
 __device__ __forceinline__ uint64_t k13_key(float v, uint32_t f) { return ((uint64_t)(__float_as_uint(v) & 0x7FFFFFFFu) << 32) | (0xFFFFFFFFu - f); }
 
+// ---- the dual coordinate descent's own part of a launch and its serial pieces, shared by K13 (xrl_train.hip) and K13D (xrl_train_dense.hip)
+struct K13Args : TrainJobArgs {
+    int l2loss; uint64_t max_iter;
+    // the rest of a slot's scratch, [slot * its size]
+    float* alpha; float* qd;
+    const uint32_t* table; uint64_t table_n;
+    const uint32_t* job_list; uint32_t n_jobs; uint32_t* next;            // job_list null: jobs job0 .. job0 + n_jobs - 1
+    uint32_t* redo; uint32_t* n_redo;
+    unsigned long long* counters;                                          // iters, shrinks, reactivations, max_iter stops, clipped, lane rows, wave rows
+};
+
+// one uniform draw in [0, range), 1 <= range < 2^32: libstdc++'s uniform_int_distribution over a 32-bit generator (_S_nd: Lemire's
+// multiply with the (-range) % range rejection).  false: the table ended.
+__device__ __forceinline__ bool k13_draw(const uint32_t* __restrict__ table, uint64_t tn, uint64_t& cur, uint32_t range, uint32_t& out) {
+    if (cur >= tn) return false;
+    uint64_t prod = (uint64_t)table[cur++] * range;
+    uint32_t low = (uint32_t)prod;
+    if (low < range) {
+        const uint32_t thr = (0u - range) % range;
+        while (low < thr) {
+            if (cur >= tn) return false;
+            prod = (uint64_t)table[cur++] * range;
+            low = (uint32_t)prod;
+        }
+    }
+    out = (uint32_t)(prod >> 32);
+    return true;
+}
+
+__device__ __forceinline__ bool k13_not_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u; }
+
+__device__ __forceinline__ void k13_swap(uint32_t* a, uint32_t i, uint32_t j) { const uint32_t t = a[i]; a[i] = a[j]; a[j] = t; }
+
+// libstdc++'s std::shuffle (bits/stl_algo.h) of a[0, n) by one lane
+__device__ bool k13_shuffle(uint32_t* a, uint32_t n, const uint32_t* __restrict__ table, uint64_t tn, uint64_t& cur) {
+    if (n < 2) return true;
+    uint32_t r;
+    if (n <= 65535u) {
+        uint32_t i = 1;
+        if ((n & 1u) == 0) {
+            if (!k13_draw(table, tn, cur, 2u, r)) return false;
+            k13_swap(a, 1, r);
+            i = 2;
+        }
+        for (; i < n; i += 2) {
+            const uint32_t sr = i + 1u;
+            if (!k13_draw(table, tn, cur, sr * (sr + 1u), r)) return false;
+            k13_swap(a, i, r / (sr + 1u));
+            k13_swap(a, i + 1, r % (sr + 1u));
+        }
+        return true;
+    }
+    for (uint32_t i = 1; i < n; ++i) {
+        if (!k13_draw(table, tn, cur, i + 1u, r)) return false;
+        k13_swap(a, i, r);
+    }
+    return true;
+}
+
 // ---- the instances (init_worker): M's column as stored, then Y's positives that are not among them, as stored.  -> their count; index,
 //      cost and ysg (by row id) are written and visible to every lane
 __device__ __forceinline__ uint32_t train_job_setup(const TrainJobArgs& a, uint32_t label, uint32_t code, uint32_t lane, uint32_t* index, float* cost, signed char* ysg) {

@@ -17,9 +17,33 @@ def _device_of(operands, default=0):
     return next((d for d in (_operand_device(o) for o in operands if o is not None) if d is not None), default)
 
 
+def _is_tensor(X):
+    import sys
+    torch = sys.modules.get("torch")
+    return torch is not None and isinstance(X, torch.Tensor)
+
+
+def _dense_x(X, who):
+    """None unless ``X`` is a torch tensor; then the 2-D float32 CUDA tensor K13D reads in place: its last dimension contiguous and its row
+    stride at least ``cols`` (``.contiguous()`` otherwise)."""
+    if not _is_tensor(X):
+        return None
+    import torch
+    if X.dim() != 2 or X.dtype != torch.float32 or not X.is_cuda:
+        raise ValueError(f"{who}: a tensor X must be a 2-D float32 CUDA tensor")
+    rows, cols = X.shape
+    if not (cols == 0 or rows <= 1 or (X.stride(1) == 1 and X.stride(0) >= cols)):
+        X = X.contiguous()
+    return X
+
+
 def _train_transposed(x, yt, ct, mt, rt, stream, **params):
-    """K13 over :class:`DeviceMatrix` operands that are transposed already."""
+    """K13 over :class:`DeviceMatrix` operands that are transposed already; K13D when ``x`` is a dense tensor (:func:`_dense_x`)."""
     from .features import DeviceMatrix
+    if not isinstance(x, DeviceMatrix):
+        rows, cols = x.shape
+        return DeviceMatrix(clib.train_layer_dense_device(x.device.index, x.data_ptr(), rows, cols, max(x.stride(0), cols) if rows > 1 else cols, yt.handle,
+                                                          ct and ct.handle, mt and mt.handle, rt and rt.handle, stream=stream, **params))
     return DeviceMatrix(clib.train_layer_device(x.handle, yt.handle, ct and ct.handle, mt and mt.handle, rt and rt.handle, stream=stream, **params))
 
 
@@ -29,15 +53,19 @@ def train_layer_device(X, Y, C=None, M=None, R=None, threshold=0.1, max_nonzeros
     clusters; None: pure multi-label), the matching matrix ``M`` (instances x clusters; None with C: ``Y * C`` by the device sparse
     product) and the relevance ``R`` (Y's pattern; None: every positive costs 1).  An operand is a
     :class:`~pecos_amd.features.DeviceMatrix`, CSR tensors ``(crow, col, val, (rows, cols))`` or a float32 scipy sparse matrix (uploaded
-    in CSR form); none of them is changed.  The solver reads columns, so Y, C, M and R are transposed on the device
+    in CSR form); none of them is changed.  ``X`` may also be a dense 2-D float32 CUDA tensor at any row stride >= its columns (K13D: an
+    embedding left in HBM, read in place; up to 16384 columns, the dual SVC solvers): the weights are those of the CSR of all its entries.  The solver reads columns, so Y, C, M and R are transposed on the device
     (:meth:`DeviceMatrix.transpose`, scipy's stable order: a column's entries by ascending row).  Returns W^T as a new
     :class:`~pecos_amd.features.DeviceMatrix`: labels x (features + (bias > 0)) in CSR, which is the CSC of W.  Runs on ``stream``
     (default: torch's current one), which it synchronises."""
     from .features import _as_device_matrix, _stream_or_current
-    ops = [X, Y, C, M, R]
-    dev = _device_of(ops)
+    dense = _dense_x(X, "train_layer_device")
+    ops = [None if dense is not None else X, Y, C, M, R]
+    dev = dense.device.index if dense is not None else _device_of(ops)
     s = _stream_or_current(dev, stream)
     x, y, c, m, r = (None if o is None else _as_device_matrix(o, dev, None, stream) for o in ops)
+    if dense is not None:
+        x = dense
     if c is not None and m is None:
         m = y.multiply(c, stream=s)
     if c is None:
@@ -242,7 +270,8 @@ def matching_chain_device(M_dict, chain, stream=None):
 def train_chain_device(X, Y, chain, neg_mining_chain="tfn", matching_chain=None, relevance_chain=None, train_params=None, pred_params=None,
                        return_matching=False, stream=None):
     """The layers of a cluster chain trained top down with everything resident in HBM (pecos/xmc/base.py:1512-1572).  ``X`` (instances x
-    features) and ``Y`` (instances x labels) are operands as :func:`train_layer_device` takes them; ``chain`` is the list of ``C``
+    features) and ``Y`` (instances x labels) are operands as :func:`train_layer_device` takes them (a dense tensor ``X`` when every layer
+    uses a dual SVC solver and no scheme names ``man``: the prediction and the primal solver read the CSR form); ``chain`` is the list of ``C``
     matrices, root first (an entry None: a one-versus-all layer, only as a one-element chain); ``neg_mining_chain`` is one scheme or one
     per layer, a sum of ``tfn`` (the layer above's labels), ``usn`` (``matching_chain[t]``) and ``man`` (the prediction of the layers
     trained so far, with layer t-1's own ``only_topk`` and ``post_processor`` from ``pred_params``); ``train_params`` / ``pred_params`` are
@@ -273,13 +302,20 @@ def train_chain_device(X, Y, chain, neg_mining_chain="tfn", matching_chain=None,
     host_leaves = relevance_chain is not None and smat.issparse(relevance_chain[-1]) and smat.issparse(Y)
     if host_leaves:                                         # the leaves' relevance against the caller's own Y: checked before anything is uploaded
         check_relevance(Y, relevance_chain[-1])
-    dev = _device_of([X, Y] + chain + list(matching_chain or []) + list(relevance_chain or []))
+    if _is_tensor(X):                                       # what a dense X cannot serve is said before the tensor itself is looked at
+        if any("man" in sc for sc in schemes):
+            raise NotImplementedError("train_chain_device: neg_mining_chain 'man' predicts X with the half-trained chain, which needs X in CSR form; a dense tensor X is not served")
+        primal = [tp.get("solver_type", "L2R_L2LOSS_SVC_DUAL") for tp in tps if clib._solver_number(tp.get("solver_type", 1)) not in (1, 3)]
+        if primal:
+            raise NotImplementedError(f"train_chain_device: solver_type {primal[0]} needs X in CSR form; a dense tensor X is served by the dual SVC solvers")
+    dense = _dense_x(X, "train_chain_device")
+    dev = dense.device.index if dense is not None else _device_of([X, Y] + chain + list(matching_chain or []) + list(relevance_chain or []))
     s = _stream_or_current(dev, stream)
 
     def resident(o):
         return None if o is None else _as_device_matrix(o, dev, None, stream)
 
-    x, cs = resident(X), [resident(C) for C in chain]
+    x, cs = dense if dense is not None else resident(X), [resident(C) for C in chain]
     usn = [resident(m) for m in matching_chain] if matching_chain is not None else [None] * depth
     labels_of = _label_chain(resident(Y), cs, s)
     for t, R in enumerate(relevance_chain or []):           # every other host matrix of the caller's before any layer is trained; Y_t comes down for it
