@@ -816,6 +816,28 @@ void xrl_single_layer_train_newton_drm_f32(const ScipyDrmF32* pX, const ScipyCsc
 void* xrl_train_layer_newton_device(void* X, void* Yt, void* Ct_or_null, void* Mt_or_null, void* Rt_or_null, double threshold, uint32_t max_nonzeros_per_label,
                                     int solver_type, double Cp, double Cn, uint64_t max_iter, double eps, double bias, void* hip_stream);
 int xrl_debug_newton_counters(uint64_t* out, uint32_t n);
+/* OVER DENSE FEATURES (K16D, csrc/xrl_newton_dense.hip): X a dense row-major float32 matrix (N x d) in HBM, read in place.
+ * R16D.  Rule N above on rows that store EVERY column, zeros included: W^T equals xrl_train_layer_newton_device's on the CSR of all N * d
+ *   entries in rows, columns and value bits.  Every feature is touched: each vector step walks 0 .. d-1, pcg takes at most max(d + (bias >
+ *   0), 5) steps.  A row's dot product is ONE fp32 chain from +0 over columns 0 .. d-1 of fl32(v[f] * X[i, f]), the same for any row
+ *   stride; X_I' u and the preconditioner's diagonal are, per feature, ONE chain over I's order (fp64-factor axpys for Hv, fp32 throughout
+ *   for grad and M); no zero is skipped.  The counters keep their meanings: a listed position counts as summed by a wavefront when d >= 64,
+ *   one per lane otherwise.  The by-feature vectors w, g, M, s, r, d, Hd, z are kept in LDS up to 1780 columns and in HBM scratch above;
+ *   the answer does not depend on which.
+ *   xrl_train_layer_newton_dense_device  xrl_train_layer_dense_device's argument list, result and failure convention, solver_type == 2.
+ *                                Refused before a GPU is required, under this name: solvers 1 and 3 (the message names
+ *                                xrl_train_layer_dense_device, which serves them), 7 and unknown solvers as the entry points above refuse
+ *                                them; a null d_X with a non-empty shape, row_stride < cols, cols > 16384, 2^31 rows and every shape,
+ *                                null, device and pattern refusal in xrl_train_layer_dense_device's words.  Refused by a check kernel that
+ *                                reads only the cols floats of a row: a value that is not finite ("X stores a value that is not finite").
+ *                                Zero rows, zero columns and zero labels succeed.  xrl_single_layer_train_newton_drm_f32 takes this
+ *                                route up to 16384 columns -- the caller's array is uploaded as it is -- and the CSR of all entries above.
+ *   xrl_debug_newton_dense_forms  FOR TESTS ONLY: out[0..n), n <= 4 <- {the column limit of the form that keeps the vectors in LDS, the
+ *                                column limit, jobs served with the vectors in LDS, from scratch} of this process since the load */
+void* xrl_train_layer_newton_dense_device(int device, const float* d_X, uint64_t rows, uint64_t cols, uint64_t row_stride, void* Yt, void* Ct_or_null, void* Mt_or_null,
+                                          void* Rt_or_null, double threshold, uint32_t max_nonzeros_per_label, int solver_type, double Cp, double Cn, uint64_t max_iter,
+                                          double eps, double bias, void* hip_stream);
+int xrl_debug_newton_dense_forms(uint64_t* out, uint32_t n);
 
 /* Matcher-aware negatives (MAN) on the device: what joins a trained layer, its prediction and the next layer's matching matrix in HBM
  * (K14, csrc/xrl_match.hip; pecos_amd.train_chain_device runs the reference's loop, pecos/xmc/base.py:1512-1572, over them).

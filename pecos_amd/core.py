@@ -360,6 +360,9 @@ class corelib(object):
         "xrl_train_layer_dense_device": (c_void_p, [c_int, c_void_p, c_uint64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_uint32, c_int,
                                                     c_double, c_double, c_uint64, c_double, c_double, c_void_p]),
         "xrl_debug_train_dense_forms": (c_int, [POINTER(c_uint64), c_uint32]),
+        "xrl_train_layer_newton_dense_device": (c_void_p, [c_int, c_void_p, c_uint64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_uint32,
+                                                           c_int, c_double, c_double, c_uint64, c_double, c_double, c_void_p]),
+        "xrl_debug_newton_dense_forms": (c_int, [POINTER(c_uint64), c_uint32]),
         "xrl_debug_newton_counters": (c_int, [POINTER(c_uint64), c_uint32]),
         "xrl_smat_pattern_union_device": (c_void_p, [POINTER(c_void_p), c_uint32, c_void_p]),
         "xrl_single_layer_predict_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_char_p, c_uint32, c_float, c_void_p,
@@ -900,6 +903,25 @@ class corelib(object):
         self.clib_float32.xrl_debug_train_dense_forms(out, 4)
         self._check()
         return dict(zip(("reg_cols", "lds_cols", "reg_jobs", "lds_jobs"), (int(v) for v in out)))
+
+    def train_layer_newton_dense_device(self, device, d_X, rows, cols, row_stride, Yt, Ct=None, Mt=None, Rt=None, threshold=0.1, max_nonzeros_per_label=None,
+                                        solver_type="L2R_L2LOSS_SVC_PRIMAL", Cp=1.0, Cn=1.0, max_iter=1000, eps=0.1, bias=1.0, stream=None):
+        """:meth:`train_layer_dense_device` under the primal solver L2R_L2LOSS_SVC_PRIMAL (K16D): a new W^T handle with the bits of
+        ``xrl_train_layer_newton_device`` on the CSR of all ``rows * cols`` entries."""
+        h = self.clib_float32.xrl_train_layer_newton_dense_device(int(device), c_void_p(d_X or 0), int(rows), int(cols), int(row_stride), c_void_p(Yt),
+                                                                  c_void_p(Ct or 0), c_void_p(Mt or 0), c_void_p(Rt or 0), threshold,
+                                                                  0 if max_nonzeros_per_label is None else max_nonzeros_per_label, self._solver_number(solver_type),
+                                                                  Cp, Cn, max_iter, eps, bias, c_void_p(stream or 0))
+        self._check()
+        return h
+
+    def debug_newton_dense_forms(self):
+        """Debug counters of K16D since the load: the column limit of the form that keeps the by-feature vectors in LDS, the column limit,
+        and the jobs served with the vectors in LDS and from scratch."""
+        out = (c_uint64 * 4)()
+        self.clib_float32.xrl_debug_newton_dense_forms(out, 4)
+        self._check()
+        return dict(zip(("lds_cols", "max_cols", "lds_jobs", "scratch_jobs"), (int(v) for v in out)))
 
     def debug_train_counters(self):
         """What the last training of this process ran (``xrl_debug_train_counters``), by name."""

@@ -28,8 +28,25 @@ constexpr uint32_t kNewtonDeviceCounters = 16;                 // the last 16, s
 void train_layer_newton_device(const char* what, const QueriesDev& X, const QueriesDev& Yt, const float* r_val, const QueriesDev* Ct, const QueriesDev* Mt,
                                const TrainParams& p, hipStream_t s, DevCsr& out, NewtonCounters& counters);
 
-// refusals that read no data: every solver but 2, each with its reason; `what` starts the message
-void check_newton_params(const std::string& what, const TrainParams& p);
+// refusals that read no data: every solver but 2, each with its reason; `what` starts the message (dense: the dual solvers' entry point
+// that is named is the dense one)
+void check_newton_params(const std::string& what, const TrainParams& p, bool dense = false);
+
+// ---- K16D (xrl_newton_dense.hip): the same jobs and solver over a dense row-major X in HBM, read in place (R16D in include/xrl_abi.h)
+// A row pass stages 64 listed rows x kNewtonDensePanel columns in LDS at a pitch of kNewtonDensePanel + 1 floats, beside the panel of the
+// vector the rows are multiplied with; the eight by-feature vectors live behind the tile while the workgroup's LDS stays within
+// kNewtonDenseWgLds -- what a launch gets without asking for more, and a size at which two workgroups share a CU's 160 KB.
+constexpr uint32_t kNewtonDensePanel = 32, kNewtonDensePitch = kNewtonDensePanel + 1;
+constexpr uint32_t kNewtonDenseTileFloats = 64 * kNewtonDensePitch + kNewtonDensePanel;
+constexpr uint32_t kNewtonDenseWgLds = 64u << 10, kNewtonDenseVectors = 8;
+constexpr uint32_t kNewtonDenseLdsCols = (kNewtonDenseWgLds - kNewtonDenseTileFloats * 4) / (kNewtonDenseVectors * 4);
+static_assert(kNewtonDenseLdsCols == 1780 && 2 * kNewtonDenseWgLds <= kTrainDenseLdsPerCu, "the LDS form's column limit");
+
+// train_layer_newton_device for a dense X of at most kTrainDenseMaxCols columns: the same W^T and counters as on the CSR of all its entries
+void train_layer_newton_dense_device(const char* what, const TrainDenseX& X, const QueriesDev& Yt, const float* r_val, const QueriesDev* Ct, const QueriesDev* Mt,
+                                     const TrainParams& p, hipStream_t s, DevCsr& out, NewtonCounters& counters);
+// {the LDS form's column limit, the column limit, jobs served with the vectors in LDS, from the slot's scratch} of this process since the load
+void newton_dense_forms(uint64_t (&out)[4]);
 
 // ---- what the layer's driver (xrl_train.hip) uses
 struct TrainJobArgs;
@@ -48,5 +65,10 @@ void newton_launch(const TrainJobArgs& base, const NewtonScratch& sc, uint32_t n
 uint32_t newton_bad_job(const NewtonScratch& sc, hipStream_t s);
 void newton_read_counters(const NewtonScratch& sc, NewtonCounters& c, hipStream_t s);
 void newton_check_finite(const std::string& what, const QueriesDev& X, hipStream_t s);
+void newton_fail_not_finite(const std::string& what);
+// K16D's counterparts: the most wavefronts at once over `cols` columns, k16d_solve over `blocks` slots, the check of X's stored values
+uint32_t newton_dense_max_slots(uint32_t cols);
+void newton_dense_launch(const TrainJobArgs& base, const NewtonScratch& sc, const TrainDenseX& X, uint32_t n_jobs, uint32_t* next, uint32_t blocks, hipStream_t s);
+void newton_dense_check_finite(const std::string& what, const TrainDenseX& X, hipStream_t s);
 
 }  // namespace xrl

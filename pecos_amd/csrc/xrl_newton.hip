@@ -15,6 +15,7 @@
 #include "xrl_device.h"
 #include "xrl_devprim.h"
 #include "xrl_newton.h"
+#include "xrl_newton_job.h"
 #include "xrl_train_job.h"
 
 namespace xrl {
@@ -23,21 +24,10 @@ namespace {
 
 constexpr const char* kWhat = "K16";
 
-struct K16Args : TrainJobArgs {
-    float* wx; float* tmp; uint32_t* I; float* tq; float* dots; uint32_t* tlist; float* vec;
-    uint32_t n_jobs; uint32_t* next;
-    unsigned long long* counters; uint32_t* bad_job;
-};
-
-enum { cNewton, cCg, cHv, cHalvings, cBefore, cGradient, cLine, cActred, cCap, cgDhd, cgQ, cgPositive, cgCap, cLaneRows, cWaveRows, cNonfinite, kCtr };
-static_assert(kCtr == (int)kNewtonDeviceCounters, "the counters");
-
 __global__ void __launch_bounds__(256) k16_finite(const float* __restrict__ val, uint64_t nnz, uint32_t* __restrict__ flag) {
     const uint64_t x = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (x < nnz && (__float_as_uint(val[x]) & 0x7F800000u) == 0x7F800000u) atomicOr(flag, 1u);
 }
-
-__device__ __forceinline__ bool k16_finite_d(double v) { return (__double_as_longlong(v) & 0x7FF0000000000000ll) != 0x7FF0000000000000ll; }
 
 // one job's view of its slot and the solver's state that outlives a step
 struct K16Job {
@@ -452,12 +442,17 @@ void newton_reserve(NewtonScratch& sc, uint32_t slots, uint32_t N, uint32_t d, u
     XRL_HIP(hipMemsetAsync(sc.bad.p, 0xFF, 4, s));
 }
 
-void newton_launch(const TrainJobArgs& base, const NewtonScratch& sc, uint32_t n_jobs, uint32_t* next, uint32_t blocks, hipStream_t s) {
+K16Args newton_args(const TrainJobArgs& base, const NewtonScratch& sc, uint32_t n_jobs, uint32_t* next) {
     K16Args a{};
     static_cast<TrainJobArgs&>(a) = base;
     a.wx = sc.wx.as<float>(); a.tmp = sc.tmp.as<float>(); a.I = sc.I.as<uint32_t>(); a.tq = sc.tq.as<float>(); a.dots = sc.dots.as<float>();
     a.tlist = sc.tlist.as<uint32_t>(); a.vec = sc.vec.as<float>();
     a.n_jobs = n_jobs; a.next = next; a.counters = sc.ctr.as<unsigned long long>(); a.bad_job = sc.bad.as<uint32_t>();
+    return a;
+}
+
+void newton_launch(const TrainJobArgs& base, const NewtonScratch& sc, uint32_t n_jobs, uint32_t* next, uint32_t blocks, hipStream_t s) {
+    const K16Args a = newton_args(base, sc, n_jobs, next);
     hipLaunchKernelGGL(k16_solve, dim3(blocks), dim3(64), 0, s, a);
     XRL_LAUNCH_CHECK();
 }
@@ -489,13 +484,17 @@ void newton_check_finite(const std::string& what, const QueriesDev& X, hipStream
     uint32_t f = 0;
     XRL_HIP(hipMemcpyAsync(&f, flag.p, 4, hipMemcpyDeviceToHost, s));
     XRL_HIP(hipStreamSynchronize(s));
-    if (f) fail(what + "X stores a value that is not finite (a NaN or an infinity); the primal solver's features that no instance stores would become NaNs, which this form does not cover");
+    if (f) newton_fail_not_finite(what);
 }
 
-void check_newton_params(const std::string& what, const TrainParams& p) {
+void newton_fail_not_finite(const std::string& what) {
+    fail(what + "X stores a value that is not finite (a NaN or an infinity); the primal solver's features that no instance stores would become NaNs, which this form does not cover");
+}
+
+void check_newton_params(const std::string& what, const TrainParams& p, bool dense) {
     if (p.solver_type == kSolverL2LossDual || p.solver_type == kSolverL1LossDual)
         fail(what + "solver " + (p.solver_type == kSolverL2LossDual ? "L2R_L2LOSS_SVC_DUAL" : "L2R_L1LOSS_SVC_DUAL") +
-             " is served by the entry point without `newton` in its name (xrl_single_layer_train_{csr,drm}_f32, xrl_train_layer_device)");
+             " is served by the entry point without `newton` in its name (" + (dense ? "xrl_train_layer_dense_device" : "xrl_single_layer_train_{csr,drm}_f32, xrl_train_layer_device") + ")");
     if (p.solver_type == 7)
         fail(what + "solver L2R_LR_DUAL is not served on the device: its inner Newton steps call log in fp64, and the device's log is not the host library's, so its weights could not be the reference's bit for bit");
     if (p.solver_type != kSolverL2LossPrimal)

@@ -314,7 +314,7 @@ namespace {
 
 // One layer, whichever solver: the checks, the sizes of a slot and of a staging row, the batches under the scratch budget, and W^T by
 // label.  newton (NT) or the dual coordinate descent (T); the caller has refused the solvers its entry point does not serve.  D: X is the
-// dense row-major matrix D describes (K13D serves the jobs); of X itself only rows, cols and nnz = rows * cols are then read.
+// dense row-major matrix D describes (K13D or, newton, K16D serves the jobs); of X itself only rows, cols and nnz = rows * cols are then read.
 void train_layer(const char* what_c, const QueriesDev& X, const TrainDenseX* D, const QueriesDev& Yt, const float* r_val, const QueriesDev* Ct, const QueriesDev* Mt,
                  const TrainParams& p, hipStream_t s, DevCsr& out, TrainCounters& T, NewtonCounters* NT) {
     const std::string what = std::string(what_c) + ": ";
@@ -329,7 +329,8 @@ void train_layer(const char* what_c, const QueriesDev& X, const TrainDenseX* D, 
     flags.reserve(4);
     XRL_HIP(hipMemsetAsync(flags.p, 0, 4, s));
     if (!D) check_csr(what, "X", X, d, true, flags, s);
-    if (newton) newton_check_finite(what, X, s);
+    if (newton && D) newton_dense_check_finite(what, *D, s);
+    else if (newton) newton_check_finite(what, X, s);
     check_csr(what, "Y", Yt, N, false, flags, s);
     if (coded) {
         check_csr(what, "C", *Ct, L, false, flags, s);
@@ -371,7 +372,7 @@ void train_layer(const char* what_c, const QueriesDev& X, const TrainDenseX* D, 
 
     const uint64_t budget = env_u64("XRL_TRAIN_SCRATCH_BYTES", kTrainScratchBytes);
     const uint64_t slot_bytes = (uint64_t)index_cap * 4 + (uint64_t)N * (newton ? 5 : 13) + (uint64_t)d * 4 + (uint64_t)dw * 4 + (newton ? newton_slot_bytes(N, d, index_cap) : 0);
-    const uint32_t slots = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({budget / std::max<uint64_t>(slot_bytes, 1), D ? train_dense_max_slots(d) : kTrainMaxSlots,
+    const uint32_t slots = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({budget / std::max<uint64_t>(slot_bytes, 1), D ? (newton ? newton_dense_max_slots(d) : train_dense_max_slots(d)) : kTrainMaxSlots,
                                                                                 std::max<uint32_t>(jobs, 1)}));
     const uint32_t batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(budget / (stride64 * 8), std::max<uint32_t>(jobs, 1)));
     T.jobs = jobs; T.slots = slots; T.stride = stride;
@@ -428,7 +429,8 @@ void train_layer(const char* what_c, const QueriesDev& X, const TrainDenseX* D, 
         a.job0 = j0; a.n_jobs = nb; a.job_list = nullptr;
         if (newton) {
             XRL_HIP(hipMemsetAsync(b_next.p, 0, 8, s));
-            newton_launch(a, nsc, nb, a.next, std::min(slots, nb), s);
+            if (D) newton_dense_launch(a, nsc, *D, nb, a.next, std::min(slots, nb), s);
+            else newton_launch(a, nsc, nb, a.next, std::min(slots, nb), s);
             const uint32_t bad = newton_bad_job(nsc, s);
             if (bad != 0xFFFFFFFFu) {
                 uint32_t label = 0;
@@ -513,6 +515,15 @@ void train_layer_newton_device(const char* what, const QueriesDev& X, const Quer
     check_newton_params(std::string(what) + ": ", p);
     TrainCounters T;
     train_layer(what, X, nullptr, Yt, r_val, Ct, Mt, p, s, out, T, &NT);
+}
+
+void train_layer_newton_dense_device(const char* what, const TrainDenseX& D, const QueriesDev& Yt, const float* r_val, const QueriesDev* Ct, const QueriesDev* Mt,
+                                     const TrainParams& p, hipStream_t s, DevCsr& out, NewtonCounters& NT) {
+    check_newton_params(std::string(what) + ": ", p, true);
+    QueriesDev X{};
+    X.rows = D.rows; X.cols = D.cols; X.nnz = (uint64_t)D.rows * D.cols;
+    TrainCounters T;
+    train_layer(what, X, &D, Yt, r_val, Ct, Mt, p, s, out, T, &NT);
 }
 
 }  // namespace xrl

@@ -2,8 +2,8 @@
 // c_xlinear_single_layer_train_* (libpecos.cpp:277-316 -> multilabel_train_with_codes, linear_solver.hpp:797-860) under this library's own
 // prefix -- a binding that takes this library first and the reference for the rest keeps the reference's trainer and all its solvers --,
 // the resident forms xrl_train_layer_device over xrl_smat_* handles and xrl_train_layer_dense_device over a dense X in HBM (K13D,
-// xrl_train_dense.hip), and the counters the tests read.  Every argument is checked before a
-// GPU is required where no data is read.
+// xrl_train_dense.hip), their counterparts for the primal solver (K16, xrl_newton.hip; K16D over a dense X, xrl_newton_dense.hip), and the
+// counters the tests read.  Every argument is checked before a GPU is required where no data is read.
 #include <cstdlib>
 #include <memory>
 #include <mutex>
@@ -25,8 +25,8 @@ void keep_counters(const TrainCounters& c) { std::lock_guard<std::mutex> g(g_cou
 void keep_counters(const NewtonCounters& c) { std::lock_guard<std::mutex> g(g_counters_mu); g_newton_counters = c; }
 
 // the solvers an entry point serves: K13's two dual ones, or (newton) K16's primal one
-void check_solver(const std::string& what, const TrainParams& p, bool newton) {
-    if (newton) check_newton_params(what, p); else check_train_params(what, p);
+void check_solver(const std::string& what, const TrainParams& p, bool newton, bool dense = false) {
+    if (newton) check_newton_params(what, p, dense); else check_train_params(what, p);
 }
 
 TrainParams make_params(double threshold, uint32_t max_nonzeros, int solver_type, double Cp, double Cn, uint64_t max_iter, double eps, double bias) {
@@ -104,7 +104,10 @@ void train_host(const char* what_c, const ScipyCsrF32& X, const ScipyCscF32* pY,
     DevCsr wt;
     if (newton) {
         NewtonCounters counters;
-        train_layer_newton_device(what_c, x.v, y.v, pR ? r.as<float>() : nullptr, coded ? &c.v : nullptr, coded ? &m.v : nullptr, p, nullptr, wt, counters);
+        if (dense)
+            train_layer_newton_dense_device(what_c, TrainDenseX{x.own.val.as<float>(), X.rows, X.cols, X.cols}, y.v, pR ? r.as<float>() : nullptr, coded ? &c.v : nullptr,
+                                            coded ? &m.v : nullptr, p, nullptr, wt, counters);
+        else train_layer_newton_device(what_c, x.v, y.v, pR ? r.as<float>() : nullptr, coded ? &c.v : nullptr, coded ? &m.v : nullptr, p, nullptr, wt, counters);
         keep_counters(counters);
     } else {
         TrainCounters counters;
@@ -150,7 +153,7 @@ void train_drm(const char* what, bool newton, const ScipyDrmF32* pX, const Scipy
         if (pX->rows >= (1u << 31)) fail(std::string(what) + ": 2^31 rows or more");
         if (pX->rows && pX->cols && !pX->val) fail(std::string(what) + ": null values (X)");
         check_solver(std::string(what) + ": ", p, newton);                                          // refusals come before the index arrays are built
-        if (!newton && pX->cols <= kTrainDenseMaxCols && !std::getenv("XRL_TRAIN_DRM_CSR")) {        // K13D: the array as it is (the variable: the probe's way to the route below)
+        if (pX->cols <= kTrainDenseMaxCols && !std::getenv("XRL_TRAIN_DRM_CSR")) {                   // K13D / K16D: the array as it is (the variable: the probe's way to the route below)
             const ScipyCsrF32 shape{pX->rows, pX->cols, nullptr, nullptr, pX->val};
             train_host(what, shape, pY, pC, pM, pR, coo_alloc, p, newton, true);
             return;
@@ -180,7 +183,7 @@ void* train_resident(const char* what_c, bool newton, void* X, const TrainDenseX
     return guarded_value((void*)nullptr, [&]() -> void* {
         const std::string what = std::string(what_c) + ": ";
         const double bias = p.bias;
-        check_solver(what, p, newton);
+        check_solver(what, p, newton, dx != nullptr);
         Queries dense_x;                                                   // a dense X as the shape checks below read it: device, rows, cols
         if (dx) { dense_x.device = dense_device; dense_x.dev.rows = dx->rows; dense_x.dev.cols = dx->cols; }
         const Queries& x = dx ? dense_x : csr_handle(what, X, "X");
@@ -207,7 +210,8 @@ void* train_resident(const char* what_c, bool newton, void* X, const TrainDenseX
         auto out = std::make_unique<Queries>();
         if (newton) {
             NewtonCounters counters;
-            train_layer_newton_device(what_c, x.dev, y.dev, r ? r->dev.val : nullptr, c ? &c->dev : nullptr, m ? &m->dev : nullptr, p, s, out->own, counters);
+            if (dx) train_layer_newton_dense_device(what_c, *dx, y.dev, r ? r->dev.val : nullptr, c ? &c->dev : nullptr, m ? &m->dev : nullptr, p, s, out->own, counters);
+            else train_layer_newton_device(what_c, x.dev, y.dev, r ? r->dev.val : nullptr, c ? &c->dev : nullptr, m ? &m->dev : nullptr, p, s, out->own, counters);
             keep_counters(counters);
         } else {
             TrainCounters counters;
@@ -218,6 +222,20 @@ void* train_resident(const char* what_c, bool newton, void* X, const TrainDenseX
         set_own_csr(*out, x.device, y.dev.rows, x.dev.cols + (bias > 0 ? 1u : 0u));
         return out.release();
     });
+}
+
+// the two resident entry points over a dense X: the solver's and X's refusals, then train_resident
+void* train_resident_dense(const char* what, bool newton, int device, const float* d_X, uint64_t rows, uint64_t cols, uint64_t row_stride, void* Yt, void* Ct_or_null,
+                           void* Mt_or_null, void* Rt_or_null, const TrainParams& p, void* hip_stream) {
+    TrainDenseX dx{};
+    if (guarded_value(-1, [&] {
+            check_solver(std::string(what) + ": ", p, newton, true);
+            check_dense_x(std::string(what) + ": ", d_X, rows, cols, row_stride);
+            dx = TrainDenseX{d_X, (uint32_t)rows, (uint32_t)cols, row_stride};
+            return 0;
+        }))
+        return nullptr;
+    return train_resident(what, newton, nullptr, &dx, device, Yt, Ct_or_null, Mt_or_null, Rt_or_null, p, hip_stream);
 }
 
 }  // namespace
@@ -247,17 +265,8 @@ void* xrl_train_layer_device(void* X, void* Yt, void* Ct_or_null, void* Mt_or_nu
 void* xrl_train_layer_dense_device(int device, const float* d_X, uint64_t rows, uint64_t cols, uint64_t row_stride, void* Yt, void* Ct_or_null, void* Mt_or_null,
                                    void* Rt_or_null, double threshold, uint32_t max_nonzeros_per_label, int solver_type, double Cp, double Cn, uint64_t max_iter,
                                    double eps, double bias, void* hip_stream) {
-    const char* what = "xrl_train_layer_dense_device";
-    const TrainParams p = make_params(threshold, max_nonzeros_per_label, solver_type, Cp, Cn, max_iter, eps, bias);
-    TrainDenseX dx{};
-    if (guarded_value(-1, [&] {
-            check_train_params(std::string(what) + ": ", p);
-            check_dense_x(std::string(what) + ": ", d_X, rows, cols, row_stride);
-            dx = TrainDenseX{d_X, (uint32_t)rows, (uint32_t)cols, row_stride};
-            return 0;
-        }))
-        return nullptr;
-    return train_resident(what, false, nullptr, &dx, device, Yt, Ct_or_null, Mt_or_null, Rt_or_null, p, hip_stream);
+    return train_resident_dense("xrl_train_layer_dense_device", false, device, d_X, rows, cols, row_stride, Yt, Ct_or_null, Mt_or_null, Rt_or_null,
+                                make_params(threshold, max_nonzeros_per_label, solver_type, Cp, Cn, max_iter, eps, bias), hip_stream);
 }
 
 // ---- the primal L2-loss SVC (K16): the same argument lists, solver_type == 2
@@ -279,6 +288,23 @@ void* xrl_train_layer_newton_device(void* X, void* Yt, void* Ct_or_null, void* M
                                     int solver_type, double Cp, double Cn, uint64_t max_iter, double eps, double bias, void* hip_stream) {
     return train_resident("xrl_train_layer_newton_device", true, X, nullptr, 0, Yt, Ct_or_null, Mt_or_null, Rt_or_null,
                           make_params(threshold, max_nonzeros_per_label, solver_type, Cp, Cn, max_iter, eps, bias), hip_stream);
+}
+
+void* xrl_train_layer_newton_dense_device(int device, const float* d_X, uint64_t rows, uint64_t cols, uint64_t row_stride, void* Yt, void* Ct_or_null, void* Mt_or_null,
+                                          void* Rt_or_null, double threshold, uint32_t max_nonzeros_per_label, int solver_type, double Cp, double Cn, uint64_t max_iter,
+                                          double eps, double bias, void* hip_stream) {
+    return train_resident_dense("xrl_train_layer_newton_dense_device", true, device, d_X, rows, cols, row_stride, Yt, Ct_or_null, Mt_or_null, Rt_or_null,
+                                make_params(threshold, max_nonzeros_per_label, solver_type, Cp, Cn, max_iter, eps, bias), hip_stream);
+}
+
+int xrl_debug_newton_dense_forms(uint64_t* out, uint32_t n) {
+    return guarded_value(-1, [&] {
+        if (!out) fail("xrl_debug_newton_dense_forms: null argument");
+        uint64_t v[4];
+        newton_dense_forms(v);
+        for (uint32_t i = 0; i < n && i < 4; ++i) out[i] = v[i];
+        return 0;
+    });
 }
 
 int xrl_debug_newton_counters(uint64_t* out, uint32_t n) {

@@ -35,20 +35,6 @@ struct K13DArgs : K13Args {
     int vec;                                                           // every row starts 16-byte aligned
 };
 
-__device__ __forceinline__ uint32_t lane_u32(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }   // l is uniform
-__device__ __forceinline__ float lane_f32(float v, uint32_t l) { return __uint_as_float(lane_u32(__float_as_uint(v), l)); }
-
-// columns c0 .. c0 + 3 of a row (c0 % 4 == 0); those at cols and beyond read as +0 and are never loaded
-__device__ __forceinline__ float4 k13d_load(const float* __restrict__ row, uint32_t c0, uint32_t cols, int vec) {
-    if (vec && c0 + 4u <= cols) return *reinterpret_cast<const float4*>(row + c0);
-    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (c0 < cols) v.x = row[c0];
-    if (c0 + 1u < cols) v.y = row[c0 + 1u];
-    if (c0 + 2u < cols) v.z = row[c0 + 2u];
-    if (c0 + 3u < cols) v.w = row[c0 + 3u];
-    return v;
-}
-
 __device__ __forceinline__ float4 k13d_mul(const float4& a, const float4& b) {
     return make_float4(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y), __fmul_rn(a.z, b.z), __fmul_rn(a.w, b.w));
 }

@@ -97,6 +97,21 @@ __device__ bool k13_shuffle(uint32_t* a, uint32_t n, const uint32_t* __restrict_
     return true;
 }
 
+// ---- a dense row-major X (K13D, K16D): a lane's value read by every lane, and the four columns a lane owns of a 256-column step
+__device__ __forceinline__ uint32_t lane_u32(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }   // l is uniform
+__device__ __forceinline__ float lane_f32(float v, uint32_t l) { return __uint_as_float(lane_u32(__float_as_uint(v), l)); }
+
+// columns c0 .. c0 + 3 of a row (c0 % 4 == 0); those at cols and beyond read as +0 and are never loaded
+__device__ __forceinline__ float4 k13d_load(const float* __restrict__ row, uint32_t c0, uint32_t cols, int vec) {
+    if (vec && c0 + 4u <= cols) return *reinterpret_cast<const float4*>(row + c0);
+    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (c0 < cols) v.x = row[c0];
+    if (c0 + 1u < cols) v.y = row[c0 + 1u];
+    if (c0 + 2u < cols) v.z = row[c0 + 2u];
+    if (c0 + 3u < cols) v.w = row[c0 + 3u];
+    return v;
+}
+
 // ---- the instances (init_worker): M's column as stored, then Y's positives that are not among them, as stored.  -> their count; index,
 //      cost and ysg (by row id) are written and visible to every lane
 __device__ __forceinline__ uint32_t train_job_setup(const TrainJobArgs& a, uint32_t label, uint32_t code, uint32_t lane, uint32_t* index, float* cost, signed char* ysg) {

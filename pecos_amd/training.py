@@ -38,12 +38,16 @@ def _dense_x(X, who):
 
 
 def _train_transposed(x, yt, ct, mt, rt, stream, **params):
-    """K13 over :class:`DeviceMatrix` operands that are transposed already; K13D when ``x`` is a dense tensor (:func:`_dense_x`)."""
+    """K13 (K16 under the primal solver) over :class:`DeviceMatrix` operands that are transposed already; K13D (K16D) when ``x`` is a dense
+    tensor (:func:`_dense_x`)."""
+    from .core import XLINEAR_SOLVERS
     from .features import DeviceMatrix
     if not isinstance(x, DeviceMatrix):
         rows, cols = x.shape
-        return DeviceMatrix(clib.train_layer_dense_device(x.device.index, x.data_ptr(), rows, cols, max(x.stride(0), cols) if rows > 1 else cols, yt.handle,
-                                                          ct and ct.handle, mt and mt.handle, rt and rt.handle, stream=stream, **params))
+        primal = clib._solver_number(params.get("solver_type", "L2R_L2LOSS_SVC_DUAL")) == XLINEAR_SOLVERS["L2R_L2LOSS_SVC_PRIMAL"]
+        train = clib.train_layer_newton_dense_device if primal else clib.train_layer_dense_device
+        return DeviceMatrix(train(x.device.index, x.data_ptr(), rows, cols, max(x.stride(0), cols) if rows > 1 else cols, yt.handle,
+                                  ct and ct.handle, mt and mt.handle, rt and rt.handle, stream=stream, **params))
     return DeviceMatrix(clib.train_layer_device(x.handle, yt.handle, ct and ct.handle, mt and mt.handle, rt and rt.handle, stream=stream, **params))
 
 
@@ -54,7 +58,7 @@ def train_layer_device(X, Y, C=None, M=None, R=None, threshold=0.1, max_nonzeros
     product) and the relevance ``R`` (Y's pattern; None: every positive costs 1).  An operand is a
     :class:`~pecos_amd.features.DeviceMatrix`, CSR tensors ``(crow, col, val, (rows, cols))`` or a float32 scipy sparse matrix (uploaded
     in CSR form); none of them is changed.  ``X`` may also be a dense 2-D float32 CUDA tensor at any row stride >= its columns (K13D: an
-    embedding left in HBM, read in place; up to 16384 columns, the dual SVC solvers): the weights are those of the CSR of all its entries.  The solver reads columns, so Y, C, M and R are transposed on the device
+    embedding left in HBM, read in place; up to 16384 columns; K16D under L2R_L2LOSS_SVC_PRIMAL): the weights are those of the CSR of all its entries.  The solver reads columns, so Y, C, M and R are transposed on the device
     (:meth:`DeviceMatrix.transpose`, scipy's stable order: a column's entries by ascending row).  Returns W^T as a new
     :class:`~pecos_amd.features.DeviceMatrix`: labels x (features + (bias > 0)) in CSR, which is the CSC of W.  Runs on ``stream``
     (default: torch's current one), which it synchronises."""
